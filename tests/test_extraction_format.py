@@ -1,7 +1,7 @@
 """CPU: the extractor's on-disk format against the reference's own fixture
-tests/visualgenome/frcnn/train.arrow.  The fixture itself cannot travel to the GPU box, so the facts it pins
-(column names / Arrow types / metadata keys / feature description) were read from it in the build container and
-are restated here; when the reference is mounted the test re-reads the fixture and checks them directly."""
+tests/visualgenome/frcnn/train.arrow.  The facts it pins (column names / Arrow types / metadata keys / feature
+description) are restated here, and tests/golden/vg_frcnn_train_schema.arrow keeps the fixture's schema (every
+field with its field metadata, and the schema metadata) as a zero-row Arrow stream, which the test re-reads."""
 import json
 import os
 
@@ -11,7 +11,7 @@ import pytest
 
 from vltk_amd.extraction import ExtractionWriter, load_extraction
 
-FIXTURE = "/root/reference/tests/visualgenome/frcnn/train.arrow"
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vg_frcnn_train_schema.arrow")
 PINNED_COLUMNS = {"attr_ids": "list<item: float>", "box": "list<item: list<item: float>>",
                   "features": "list<item: list<item: float>>", "imgid": "string", "object_ids": "list<item: float>"}
 PINNED_META = {"huggingface", "img_to_row_map", "model_config", "dataset", "processor_args"}
@@ -67,7 +67,6 @@ def test_duplicate_and_shape_errors(tmp_path):
     assert table.column("object_ids").to_pylist()[2] == [12.0, 13.0, 14.0, 15.0]      # row "c" = row 3 of that batch
 
 
-@pytest.mark.skipif(not os.path.exists(FIXTURE), reason="reference fixture only exists in the build container")
 def test_matches_reference_fixture(tmp_path):
     with pa.memory_map(FIXTURE) as m:
         ref = pa.ipc.open_stream(m).read_all()          # plain Arrow read: nothing from the file is executed

@@ -62,7 +62,6 @@ def main():
         import bench
         sys.exit(bench.launch_ranks(a, script=__file__))
 
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")          # bench.py: RCCL's streams must not share the forward's queues
     json_fd = os.dup(1)                                        # RCCL's banner and everything else: stderr
     os.dup2(2, 1)
     import numpy as np

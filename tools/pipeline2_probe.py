@@ -9,7 +9,6 @@ import torch
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 from vltk_amd import FRCNN, make_state_dict, synthetic_images, vg_c4_config  # noqa: E402
 
 
