@@ -148,6 +148,28 @@ int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
                      const vk_roi_params *rp, const vk_outputs *out_dev, void *stream, int64_t *ticket);
 int vk_forward_end(vk_handle *h, int64_t ticket);
 
+/* Region features for caller-supplied boxes (the reference's `proposals=` slot, frcnn.py:1924-1964, which is broken
+ * upstream: `proposal_boxes` is never bound when proposals are given).  Detection, but with the RPN replaced by the
+ * caller's boxes, each kept in input order and none dropped:
+ *   boxes_dev : [N,B,4] f32 (x0,y0,x1,y1), device; rows b >= counts[n] are ignored.  0 <= counts[n] <= B <= 1024.
+ *   counts    : host [N] int32, copied into the ticket's pinned slot before this call returns (like image_hw).
+ *   out_dev   : vk_outputs of capacity B per image.
+ * Coordinates are in the frame of the returned boxes: network-input pixels without scales_yx; with scales_yx
+ * original-image pixels, divided on the device (fp32 IEEE division) by scales_yx[n][1] (x) and scales_yx[n][0] (y) --
+ * the inverse of frcnn.py:1280-1283.  Per box: _clip_box to image_hw[n] (frcnn.py:147-153; a non-finite box raises its
+ * assertion from vk_forward_end, :148), RoIPool 14x14 at 1/16 on res4, the Res5 head and the spatial mean
+ * (roi_features, :1391-1403), cls_score -> soft-max over C+1, obj_probs / obj_ids = max / arg-max over the first C
+ * (do_nms :117-127), the attribute branch on that class (attr_probs / attr_ids as _predict_attrs :1257-1260).  boxes out =
+ * the clipped box times the scales; no box regression, no NMS; preds_per_image[n] = counts[n].
+ * The ticket belongs to vk_forward_begin's ring and is finished with vk_forward_end; detection and given-box forwards
+ * may be in flight together, in order.  B == 0: every image is empty, preds_per_image is zeroed and nothing else runs.
+ * Stages of the last forward: "res4", "proposal_boxes" [N,B,4] (clipped, network pixels), "proposal_counts",
+ * "pooled", "feature_pooled", "obj_logits", "attr_logits"; the RPN's and the regression's are not produced. */
+int vk_forward_boxes_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
+                           const int32_t *image_hw, const float *scales_yx,
+                           const float *boxes_dev, int B, const int32_t *counts,
+                           const vk_outputs *out_dev, void *stream, int64_t *ticket);
+
 /* Intermediate tensors of the last forward, for stage-level parity tests.
  * name in {"res4","rpn_out","proposal_boxes","proposal_logits",
  * "proposal_counts","pooled","feature_pooled","obj_logits","attr_logits","chosen_deltas","keep_ids"};

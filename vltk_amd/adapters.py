@@ -36,7 +36,7 @@ from .config import Config, vg_c4_config
 
 # string keys of vltk/vars.py:38-60 that the extraction loop uses
 IMG, SIZE, SCALE, RAWSIZE, FILEPATH, IMGID, SPLIT = "image", "size", "wh_scale", "rawsize", "filepath", "imgid", "split"
-FEATURES, BOX = "features", "box"
+FEATURES, BOX, BOXES = "features", "box", "boxes"
 SPLITALIASES = ("test", "dev", "eval", "val", "validation", "evaluation", "train")       # vltk/vars.py:63-71
 IMGFILES = ("jpeg", "jpg", "png")                                                         # abc/adapter.py:25
 
@@ -229,9 +229,11 @@ class FRCNN:
 
     @staticmethod
     def forward(model, entry):
+        """entry["boxes"] (vltk's vars.boxes, [K, 4] in original-image pixels), when present: region features for exactly
+        those boxes (FRCNN.forward(proposals=...)) instead of detection."""
         size, scale_wh, image = entry[SIZE], entry[SCALE], entry[IMG]
         model_out = model(images=image.unsqueeze(0), image_shapes=torch.as_tensor(size).unsqueeze(0),
-                          padding="max_detections", pad_value=0.0, location="cpu")
+                          padding="max_detections", pad_value=0.0, location="cpu", **FRCNN._given(model, [entry]))
         return FRCNN._rows(model_out, [scale_wh], 0)
 
     @staticmethod
@@ -239,7 +241,8 @@ class FRCNN:
         """Batched counterpart: images must share one (padded) size.  Returns the same dict with B rows."""
         images = torch.stack([e[IMG] for e in entries])
         sizes = torch.stack([torch.as_tensor(e[SIZE]) for e in entries])
-        model_out = model(images=images, image_shapes=sizes, padding="max_detections", pad_value=0.0, location="cpu")
+        model_out = model(images=images, image_shapes=sizes, padding="max_detections", pad_value=0.0, location="cpu",
+                          **FRCNN._given(model, entries))
         out = None
         for i, e in enumerate(entries):
             row = FRCNN._rows(model_out, [e[SCALE]], i)
@@ -249,6 +252,22 @@ class FRCNN:
                 for k, v in row.items():
                     out[k].extend(v)
         return out
+
+    @staticmethod
+    def _given(model, entries):
+        """`proposals=` for entries that carry boxes: original pixels -> the processed image's (times wh_scale, the inverse
+        of what _rows does to the outputs), and the rows padded to model.roi_outputs.max_detections (the schema's width
+        inside extract()).  {} when no entry has boxes; all or none must."""
+        has = [e.get(BOXES) is not None for e in entries]
+        if not any(has):
+            return {}
+        if not all(has):
+            raise ValueError("entries of one batch must all carry boxes or none")
+        props = []
+        for e in entries:
+            b = torch.as_tensor(np.asarray(e[BOXES], dtype=np.float32)).reshape(-1, 4).clone()
+            props.append(rescale_box(b, torch.as_tensor(e[SCALE], dtype=torch.float32)))
+        return {"proposals": props, "max_detections": int(model.roi_outputs.max_detections)}
 
     @staticmethod
     def _rows(model_out, scales, i):
@@ -310,7 +329,11 @@ class FRCNN:
         """`VisnExtraction.extract` (abc/extraction.py:95-246).  Extra keyword arguments are matched by name, as
         upstream (extraction.py:198): `dataset_name` (what the one in-tree caller passes, dataset/builder.py:36-38),
         `schema`'s (max_detections, visual_dim), `setup`'s (path, synthetic, precision, seed, model_config), plus
-        `model=(model, model_config)` to reuse a built model and `batch_size` (images per forward, default 32).
+        `model=(model, model_config)` to reuse a built model and `batch_size` (images per forward, default 32), and
+        `boxes={imgid: [K, 4] boxes in original-image pixels}`: region features for exactly those boxes, in their order
+        (FRCNN.forward(proposals=...)) instead of detection.  Every image of every split needs an entry and K may not
+        exceed the schema's max_detections (ValueError before anything is written); the rows keep the schema, `box`
+        holding the given boxes clipped to the image and rounded, `features` zero-padded to the schema's width.
         With torch.distributed initialised the images of every split shard across the ranks (parallel.py); the dict is
         returned on rank 0 (empty elsewhere).  `model.roi_outputs.{max,min}_detections` are set to the schema's width for
         the call and restored afterwards.  The reference-processor mode (`processor="reference"` / a `processor_config`)
@@ -326,6 +349,9 @@ class FRCNN:
         savedir = cls._make_save_path(datadir, dataset_name, extractor_name)
         prebuilt = kwargs.pop("model", None)
         batch_size = int(kwargs.pop("batch_size", 32))
+        given = kwargs.pop("boxes", None)
+        if given is not None:
+            given = {str(k): np.asarray(v, dtype=np.float32).reshape(-1, 4) for k, v in given.items()}
         if prebuilt is not None:
             model, model_config = prebuilt
         else:
@@ -341,14 +367,14 @@ class FRCNN:
                 model.roi_outputs.max_detections = D
                 model.roi_outputs.min_detections = min(int(model.roi_outputs.min_detections), D)
             splitdict = cls._extract_splits(model, model_config, searchdirs, valid_splits, savedir, dataset_name, subset_ids,
-                                            processor, processor_config, batch_size, D, F, kwargs)
+                                            processor, processor_config, batch_size, D, F, kwargs, given)
         finally:
             model.roi_outputs.max_detections, model.roi_outputs.min_detections = saved_limits
         return splitdict
 
     @classmethod
     def _extract_splits(cls, model, model_config, searchdirs, valid_splits, savedir, dataset_name, subset_ids, processor,
-                        processor_config, batch_size, D, F, kwargs):
+                        processor_config, batch_size, D, F, kwargs, given=None):
         from .extraction import ExtractionWriter, load_extraction
         # files -> per split (id, path), in the reference's terms: split = parent directory, id = stem up to the first dot
         print(f"extracting from {searchdirs}")
@@ -366,6 +392,13 @@ class FRCNN:
                 continue
             seen[split].add(img_id)
             per_split[split].append((img_id, path))
+        if given is not None:       # checked for EVERY split before the first one is written
+            missing = sorted(i for it in per_split.values() for i, _ in it if i not in given)
+            if missing:
+                raise ValueError(f"boxes: no entry for {len(missing)} image(s): {missing[:20]}; nothing was written")
+            wide = {i: len(given[i]) for it in per_split.values() for i, _ in it if len(given[i]) > D}
+            if wide:
+                raise ValueError(f"boxes: more boxes than max_detections={D} for {wide}; nothing was written")
         cfgd = model_config.to_dict() if hasattr(model_config, "to_dict") else model_config
         gpu_path = processor is None and processor_config is None
         if not gpu_path:
@@ -396,7 +429,7 @@ class FRCNN:
             savefile = os.path.join(savedir, f"{split}.arrow")
             if gpu_path:
                 cls._extract_split_gpu(model, model_config, items, savefile, dataset_name, pargs, cfgd, batch_size, F,
-                                       rank, world)
+                                       rank, world, given)
             else:
                 fkw = _collect_args(cls.forward, kwargs)
                 fkw.pop("model", None), fkw.pop("entry", None)
@@ -407,6 +440,8 @@ class FRCNN:
                         entry[SIZE] = _proc_attr(processor, "_size")
                         entry[SCALE] = _proc_attr(processor, "_scale")
                         entry[RAWSIZE] = _proc_attr(processor, "_rawsize")
+                        if given is not None:
+                            entry[BOXES] = given[img_id]
                         out = cls.forward(model=model, entry=entry, **fkw)
                         assert isinstance(out, dict), "model outputs should be in dict format"
                         w.write_batch([img_id], np.asarray(out["object_ids"], np.float32), np.asarray(out["attr_ids"], np.float32),
@@ -419,12 +454,13 @@ class FRCNN:
         return splitdict
 
     @classmethod
-    def _extract_split_gpu(cls, model, model_config, items, savefile, dataset_name, pargs, cfgd, batch_size, F, rank, world):
+    def _extract_split_gpu(cls, model, model_config, items, savefile, dataset_name, pargs, cfgd, batch_size, F, rank, world,
+                           given=None):
         from .parallel import shard_indices
         from .pipeline import ExtractionPipeline
         from .preprocess import Preprocess
         pipe = ExtractionPipeline(model, Preprocess(model_config, device=model.device), savefile, batch_size=batch_size,
-                                  visual_dim=F, dataset=dataset_name, processor_args=pargs, model_config=cfgd)
+                                  visual_dim=F, dataset=dataset_name, processor_args=pargs, model_config=cfgd, boxes=given)
         pipe.set_global_ids([i for i, _ in items])
         lo, hi = shard_indices(len(items), rank, world)
         mine = items[lo:hi]

@@ -367,7 +367,8 @@ static void conv_out_hw(int H, int W, int k, int s, int p, int d, int *Ho, int *
     *Wo = (W + 2 * p - (d * (k - 1) + 1)) / s + 1;
 }
 
-static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D) {
+// R: RoI rows per image (POST_NMS_TOPK_TEST for detection, B for given boxes); D: the output width of keep_ids
+static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D, int R) {
     Plan p;
     memset(&p, 0, sizeof(p));
     const vk_config &c = h->cfg;
@@ -386,7 +387,7 @@ static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D) {
     for (int s = 1; s < 3; ++s) conv_out_hw(p.Hs[s - 1], p.Ws[s - 1], 1, 2, 0, 1, &p.Hs[s], &p.Ws[s]);
     p.Hf = p.Hs[2];
     p.Wf = p.Ws[2];
-    p.R = c.post_nms_topk;
+    p.R = R;
     p.K = N * p.R;
     p.P = c.pooler_resolution;
     p.chunk = std::min(h->head_chunk > 0 ? h->head_chunk : p.K, p.K);
@@ -1101,27 +1102,18 @@ int vk_forward(vk_handle *h, const float *images_dev, int N, int H, int W, const
     return vk_forward_end(h, ticket);
 }
 
-int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W, const int32_t *image_hw,
-                     const float *scales_yx, const vk_roi_params *rp, const vk_outputs *out, void *stream, int64_t *ticket) {
-    VK_REQUIRE(h && images_dev && image_hw && rp && out && ticket, VK_EINVAL, "forward: null argument");
-    VK_REQUIRE(h->next_ticket - h->oldest_open < vk_handle::VK_MAX_INFLIGHT, VK_EINVAL,
-               "forward_begin: %d forwards are already in flight; end the oldest first", vk_handle::VK_MAX_INFLIGHT);
-    VK_REQUIRE(h->finalized, VK_EINVAL, "forward: vk_finalize has not been called");
-    VK_REQUIRE(N >= 1 && H >= 32 && W >= 32, VK_EINVAL, "forward: bad input size N=%d H=%d W=%d", N, H, W);
-    VK_REQUIRE(rp->num_nms_thresh >= 1 && rp->num_nms_thresh <= VK_MAX_NMS_THRESH, VK_EINVAL, "forward: 1..%d nms thresholds", VK_MAX_NMS_THRESH);
-    VK_REQUIRE(rp->max_detections >= 1 && rp->max_detections <= h->cfg.post_nms_topk, VK_EINVAL,
-               "forward: max_detections=%d must be in 1..POST_NMS_TOPK_TEST", rp->max_detections);
-    // image_shapes only bound the box clipping (frcnn.py:147-153); the reference does not check them
-    // against the tensor size (its own adapter passes PIL (w,h) order, adapters/frcnn.py:50-52)
-    for (int n = 0; n < N; ++n)
-        VK_REQUIRE(image_hw[2 * n] >= 1 && image_hw[2 * n + 1] >= 1, VK_EINVAL, "forward: image_shapes[%d]=(%d,%d) must be positive",
-                   n, image_hw[2 * n], image_hw[2 * n + 1]);
-    VK_CHECK_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    const vk_config &c = h->cfg;
-    const int D = rp->max_detections;
+}  // extern "C"
 
-    Plan need = make_plan(h, nullptr, N, H, W, D);
+namespace vk {
+
+// ---- the pieces of a forward shared by vk_forward_begin (detection) and vk_forward_boxes_begin (given boxes) ----
+
+// Arena for R RoI rows per image, the stage map cleared, the caller's host arrays copied into the ticket's pinned slot
+// (consumed before _begin returns, and the host-to-device copies are truly asynchronous), the non-finite flag zeroed.
+// counts (given boxes only): host [N] -> p.prop_counts.
+static int fwd_open(vk_handle *h, int N, int H, int W, int R, int D, const int32_t *image_hw, const float *scales_yx,
+                    const int32_t *counts, hipStream_t s, Plan *out) {
+    Plan need = make_plan(h, nullptr, N, H, W, D, R);
     if (need.total > h->arena_bytes) {
         if (h->arena) {
             VK_CHECK_HIP(hipDeviceSynchronize());
@@ -1132,18 +1124,14 @@ int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
         VK_CHECK_HIP(hipMalloc((void **)&h->arena, need.total));
         h->arena_bytes = need.total;
     }
-    Plan p = make_plan(h, h->arena, N, H, W, D);
+    Plan &p = *out;
+    p = make_plan(h, h->arena, N, H, W, D, R);
     h->stages_out.clear();
-    struct TimerScope {   // per-launch events only inside this forward
-        explicit TimerScope(KernelTimer *t) { g_timer = t; }
-        ~TimerScope() { g_timer = nullptr; }
-    } timer_scope(h->ktimer);
-    const bool tm = h->timing;
-    if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[0], s));
+    if (h->timing) VK_CHECK_HIP(hipEventRecord(h->ev[0], s));
 
-    // the caller's host arrays are copied into the ticket's pinned slot: consumed before this call returns, and the
-    // host-to-device copies are truly asynchronous
-    const size_t meta_need = (sizeof(int32_t) + sizeof(float)) * 2 * (size_t)N;
+    // slot layout: image_hw [N,2] i32 | scales_yx [N,2] f32 | counts [N] i32
+    const size_t hw_bytes = sizeof(int32_t) * 2 * (size_t)N, sc_bytes = sizeof(float) * 2 * (size_t)N;
+    const size_t meta_need = hw_bytes + sc_bytes + sizeof(int32_t) * (size_t)N;
     if (meta_need > h->meta_cap) {
         VK_CHECK_HIP(hipDeviceSynchronize());
         if (h->meta_host) VK_CHECK_HIP(hipHostFree(h->meta_host));
@@ -1152,16 +1140,25 @@ int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
         VK_CHECK_HIP(hipHostMalloc((void **)&h->meta_host, h->meta_cap * vk_handle::VK_MAX_INFLIGHT, hipHostMallocDefault));
     }
     char *meta = h->meta_host + (size_t)(h->next_ticket % vk_handle::VK_MAX_INFLIGHT) * h->meta_cap;
-    memcpy(meta, image_hw, sizeof(int32_t) * 2 * N);
-    VK_CHECK_HIP(hipMemcpyAsync(p.image_hw, meta, sizeof(int32_t) * 2 * N, hipMemcpyHostToDevice, s));
+    memcpy(meta, image_hw, hw_bytes);
+    VK_CHECK_HIP(hipMemcpyAsync(p.image_hw, meta, hw_bytes, hipMemcpyHostToDevice, s));
     if (scales_yx) {
-        memcpy(meta + sizeof(int32_t) * 2 * N, scales_yx, sizeof(float) * 2 * N);
-        VK_CHECK_HIP(hipMemcpyAsync(p.scales, meta + sizeof(int32_t) * 2 * N, sizeof(float) * 2 * N, hipMemcpyHostToDevice, s));
+        memcpy(meta + hw_bytes, scales_yx, sc_bytes);
+        VK_CHECK_HIP(hipMemcpyAsync(p.scales, meta + hw_bytes, sc_bytes, hipMemcpyHostToDevice, s));
+    }
+    if (counts) {
+        memcpy(meta + hw_bytes + sc_bytes, counts, sizeof(int32_t) * (size_t)N);
+        VK_CHECK_HIP(hipMemcpyAsync(p.prop_counts, meta + hw_bytes + sc_bytes, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, s));
     }
     VK_CHECK_HIP(hipMemsetAsync(p.nonfinite, 0, sizeof(int32_t), s));
+    return VK_OK;
+}
 
-    // ---- backbone (ResNet.forward frcnn.py:1076-1090) ----
-    VK_TRY(stem_impl(images_dev, N, H, W, h->stem.w, h->stem.b, c.stem_out_channels, c.caffe_maxpool, p.bufA, h->dt,
+// backbone (ResNet.forward frcnn.py:1076-1090): images -> res4 (stage "res4"), then the stage event ev[1]
+static int fwd_backbone(vk_handle *h, const Plan &p, const float *images_dev, hipStream_t s, const void **res4_out) {
+    const vk_config &c = h->cfg;
+    const int N = p.N;
+    VK_TRY(stem_impl(images_dev, N, p.H, p.W, h->stem.w, h->stem.b, c.stem_out_channels, c.caffe_maxpool, p.bufA, h->dt,
                      p.img_pad, p.stem_out, s, p.nonfinite));
     void *cur = p.bufA, *nxt = p.bufB;
     int ch = p.Hs[0], cw = p.Ws[0];
@@ -1215,30 +1212,18 @@ int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
         }
     }
     VK_REQUIRE(ch == p.Hf && cw == p.Wf, VK_EINVAL, "internal: res4 geometry mismatch (%dx%d vs %dx%d)", ch, cw, p.Hf, p.Wf);
-    const void *res4 = cur;
-    set_stage(h, "res4", res4, h->dt, {N, p.Hf, p.Wf, h->res4_c});
-    if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[1], s));
+    *res4_out = cur;
+    set_stage(h, "res4", cur, h->dt, {N, p.Hf, p.Wf, h->res4_c});
+    if (h->timing) VK_CHECK_HIP(hipEventRecord(h->ev[1], s));
+    return VK_OK;
+}
 
-    // ---- RPN head (RPNHead.forward frcnn.py:1561-1572) ----
-    const int ld_rpn = (5 * h->A + 7) / 8 * 8;
-    VK_TRY(run_conv(h, h->rpn_conv, res4, N, p.Hf, p.Wf, nullptr, p.rpn_hid, true, h->dt, 0, s));
-    VK_TRY(run_conv(h, h->rpn_heads, p.rpn_hid, N, p.Hf, p.Wf, nullptr, p.rpn_out, false, VK_F32, ld_rpn, s));
-    set_stage(h, "rpn_out", p.rpn_out, VK_F32, {N, p.Hf, p.Wf, ld_rpn});
-    if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[2], s));
-
-    // ---- proposals (RPN.inference frcnn.py:1615-1638) ----
-    VK_TRY(vk_rpn_proposals(p.rpn_out, ld_rpn, p.rpn_out + h->A, ld_rpn, N, p.Hf, p.Wf, h->A, h->cell_anchors, 16,
-                            c.anchor_offset, p.image_hw, c.rpn_bbox_weights, c.rpn_min_size, c.rpn_nms_thresh,
-                            c.pre_nms_topk, c.post_nms_topk, p.prop_boxes, p.prop_logits, p.prop_counts, p.nonfinite,
-                            p.rpn_ws, p.rpn_ws_bytes, s));
-    VK_TRY(launch_make_rois(p.prop_boxes, N, p.R, p.rois, s));
-    set_stage(h, "proposal_boxes", p.prop_boxes, VK_F32, {N, p.R, 4});
-    set_stage(h, "proposal_logits", p.prop_logits, VK_F32, {N, p.R});
-    set_stage(h, "proposal_counts", p.prop_counts, VK_I32, {N});
-    if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[3], s));
-
-    // ---- RoI heads (Res5ROIHeads.forward frcnn.py:1391-1403), chunked over RoIs ----
-    const int P = p.P;
+// RoI pool + Res5 head + spatial mean over the p.K rows of p.rois (Res5ROIHeads.forward frcnn.py:1391-1403, chunked over
+// RoIs), then the class / attribute branches of the box predictor (FastRCNNOutputLayers.forward frcnn.py:1726-1740; the
+// box regression is the caller's).  Stages "pooled" (one chunk only), "feature_pooled", "obj_logits", "attr_logits".
+static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s) {
+    const vk_config &c = h->cfg;
+    const int N = p.N, P = p.P;
     auto ensure_side = [&]() -> int {
         if (!h->side) {
             VK_CHECK_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
@@ -1297,7 +1282,6 @@ int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
     if (p.chunk >= p.K) set_stage(h, "pooled", p.pooled, h->dt, {p.K, P, P, h->res4_c});
     set_stage(h, "feature_pooled", p.feat, VK_F32, {p.K, h->res5_c});
 
-    // ---- box predictor (FastRCNNOutputLayers.forward frcnn.py:1726-1740) ----
     const int C = c.num_classes, F = h->res5_c, E = h->emb_dim, AT = c.num_attrs;
     const int ld_cls = (C + 1 + 7) / 8 * 8, ld_attr = (AT + 1 + 7) / 8 * 8;
     VK_TRY(launch_concat_embed(p.feat, nullptr, nullptr, F, 0, p.K, p.featT, h->pdt, s));
@@ -1307,9 +1291,91 @@ int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
     VK_TRY(run_conv(h, h->fc_attr, p.concat, p.K, 1, 1, nullptr, p.attr_hid, true, h->pdt, 0, s));
     VK_TRY(run_conv(h, h->attr_score, p.attr_hid, p.K, 1, 1, nullptr, p.attr_logits, false, VK_F32, ld_attr, s));
     VK_TRY(launch_softmax_argmax(p.attr_logits, ld_attr, p.K, AT, AT, p.attr_prob, p.attr_cls, nullptr, s));
-    VK_TRY(launch_chosen_deltas(p.featT, F, h->bbox_w, h->bbox_b, p.obj_cls, c.cls_agnostic_bbox_reg, F, p.K, p.chosen, h->pdt, s));
     set_stage(h, "obj_logits", p.cls_logits, VK_F32, {p.K, ld_cls});
     set_stage(h, "attr_logits", p.attr_logits, VK_F32, {p.K, ld_attr});
+    return VK_OK;
+}
+
+// the forward's last stage event, the read-back of the non-finite flag into the ticket's pinned slot (the reference
+// asserts finite boxes on the host, frcnn.py:148), the ticket's completion event.  nonfinite == nullptr: a forward that
+// launched nothing (given boxes, B == 0)
+static int fwd_close(vk_handle *h, const int32_t *nonfinite, hipStream_t s, int64_t *ticket) {
+    if (h->timing && nonfinite) {
+        VK_CHECK_HIP(hipEventRecord(h->ev[5], s));
+        h->ev_valid = true;
+    }
+    if (!h->flag_host) {
+        VK_CHECK_HIP(hipHostMalloc((void **)&h->flag_host, sizeof(int32_t) * vk_handle::VK_MAX_INFLIGHT, hipHostMallocDefault));
+        for (auto &e : h->ev_done) VK_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    const int slot = (int)(h->next_ticket % vk_handle::VK_MAX_INFLIGHT);
+    if (nonfinite)
+        VK_CHECK_HIP(hipMemcpyAsync(&h->flag_host[slot], nonfinite, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    else
+        h->flag_host[slot] = 0;     // nothing was computed (given boxes, B == 0); the slot's previous forward has ended
+    VK_CHECK_HIP(hipEventRecord(h->ev_done[slot], s));
+    *ticket = h->next_ticket++;
+    return VK_OK;
+}
+
+struct TimerScope {   // per-launch events only inside one forward
+    explicit TimerScope(KernelTimer *t) { g_timer = t; }
+    ~TimerScope() { g_timer = nullptr; }
+};
+
+}  // namespace vk
+
+extern "C" {
+
+int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W, const int32_t *image_hw,
+                     const float *scales_yx, const vk_roi_params *rp, const vk_outputs *out, void *stream, int64_t *ticket) {
+    VK_REQUIRE(h && images_dev && image_hw && rp && out && ticket, VK_EINVAL, "forward: null argument");
+    VK_REQUIRE(h->next_ticket - h->oldest_open < vk_handle::VK_MAX_INFLIGHT, VK_EINVAL,
+               "forward_begin: %d forwards are already in flight; end the oldest first", vk_handle::VK_MAX_INFLIGHT);
+    VK_REQUIRE(h->finalized, VK_EINVAL, "forward: vk_finalize has not been called");
+    VK_REQUIRE(N >= 1 && H >= 32 && W >= 32, VK_EINVAL, "forward: bad input size N=%d H=%d W=%d", N, H, W);
+    VK_REQUIRE(rp->num_nms_thresh >= 1 && rp->num_nms_thresh <= VK_MAX_NMS_THRESH, VK_EINVAL, "forward: 1..%d nms thresholds", VK_MAX_NMS_THRESH);
+    VK_REQUIRE(rp->max_detections >= 1 && rp->max_detections <= h->cfg.post_nms_topk, VK_EINVAL,
+               "forward: max_detections=%d must be in 1..POST_NMS_TOPK_TEST", rp->max_detections);
+    // image_shapes only bound the box clipping (frcnn.py:147-153); the reference does not check them
+    // against the tensor size (its own adapter passes PIL (w,h) order, adapters/frcnn.py:50-52)
+    for (int n = 0; n < N; ++n)
+        VK_REQUIRE(image_hw[2 * n] >= 1 && image_hw[2 * n + 1] >= 1, VK_EINVAL, "forward: image_shapes[%d]=(%d,%d) must be positive",
+                   n, image_hw[2 * n], image_hw[2 * n + 1]);
+    VK_CHECK_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const vk_config &c = h->cfg;
+    const int D = rp->max_detections;
+    TimerScope timer_scope(h->ktimer);
+    const bool tm = h->timing;
+
+    Plan p;
+    VK_TRY(fwd_open(h, N, H, W, c.post_nms_topk, D, image_hw, scales_yx, nullptr, s, &p));
+    const void *res4 = nullptr;
+    VK_TRY(fwd_backbone(h, p, images_dev, s, &res4));
+
+    // ---- RPN head (RPNHead.forward frcnn.py:1561-1572) ----
+    const int ld_rpn = (5 * h->A + 7) / 8 * 8;
+    VK_TRY(run_conv(h, h->rpn_conv, res4, N, p.Hf, p.Wf, nullptr, p.rpn_hid, true, h->dt, 0, s));
+    VK_TRY(run_conv(h, h->rpn_heads, p.rpn_hid, N, p.Hf, p.Wf, nullptr, p.rpn_out, false, VK_F32, ld_rpn, s));
+    set_stage(h, "rpn_out", p.rpn_out, VK_F32, {N, p.Hf, p.Wf, ld_rpn});
+    if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[2], s));
+
+    // ---- proposals (RPN.inference frcnn.py:1615-1638) ----
+    VK_TRY(vk_rpn_proposals(p.rpn_out, ld_rpn, p.rpn_out + h->A, ld_rpn, N, p.Hf, p.Wf, h->A, h->cell_anchors, 16,
+                            c.anchor_offset, p.image_hw, c.rpn_bbox_weights, c.rpn_min_size, c.rpn_nms_thresh,
+                            c.pre_nms_topk, c.post_nms_topk, p.prop_boxes, p.prop_logits, p.prop_counts, p.nonfinite,
+                            p.rpn_ws, p.rpn_ws_bytes, s));
+    VK_TRY(launch_make_rois(p.prop_boxes, N, p.R, p.rois, s));
+    set_stage(h, "proposal_boxes", p.prop_boxes, VK_F32, {N, p.R, 4});
+    set_stage(h, "proposal_logits", p.prop_logits, VK_F32, {N, p.R});
+    set_stage(h, "proposal_counts", p.prop_counts, VK_I32, {N});
+    if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[3], s));
+
+    // ---- RoI heads + box predictor; the arg-max class's box regression ----
+    VK_TRY(fwd_head(h, p, res4, s));
+    const int F = h->res5_c;
+    VK_TRY(launch_chosen_deltas(p.featT, F, h->bbox_w, h->bbox_b, p.obj_cls, c.cls_agnostic_bbox_reg, F, p.K, p.chosen, h->pdt, s));
     set_stage(h, "chosen_deltas", p.chosen, VK_F32, {p.K, 4});
     if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[4], s));
 
@@ -1345,21 +1411,61 @@ int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
     a.nonfinite = p.nonfinite;
     VK_TRY(launch_roi_final(a, N, s));
     set_stage(h, "keep_ids", p.keep_ids, VK_I64, {N, D});
-    if (tm) {
-        VK_CHECK_HIP(hipEventRecord(h->ev[5], s));
-        h->ev_valid = true;
-    }
+    return fwd_close(h, p.nonfinite, s, ticket);
+}
 
-    // the reference asserts finite boxes on the host (frcnn.py:148): one 4-byte read-back into the ticket's pinned slot
-    if (!h->flag_host) {
-        VK_CHECK_HIP(hipHostMalloc((void **)&h->flag_host, sizeof(int32_t) * vk_handle::VK_MAX_INFLIGHT, hipHostMallocDefault));
-        for (auto &e : h->ev_done) VK_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+int vk_forward_boxes_begin(vk_handle *h, const float *images_dev, int N, int H, int W, const int32_t *image_hw,
+                           const float *scales_yx, const float *boxes_dev, int B, const int32_t *counts, const vk_outputs *out,
+                           void *stream, int64_t *ticket) {
+    // the arguments first, then the handle: every check here runs before anything touches the device
+    VK_REQUIRE(images_dev && image_hw && counts && out && ticket, VK_EINVAL, "forward_boxes: null argument");
+    VK_REQUIRE(N >= 1 && H >= 32 && W >= 32, VK_EINVAL, "forward_boxes: bad input size N=%d H=%d W=%d", N, H, W);
+    VK_REQUIRE(B >= 0 && B <= 1024, VK_EINVAL, "forward_boxes: B=%d boxes per image must be in 0..1024", B);
+    VK_REQUIRE(B == 0 || boxes_dev, VK_EINVAL, "forward_boxes: null boxes with B=%d", B);
+    VK_REQUIRE(out->preds_per_image, VK_EINVAL, "forward_boxes: null preds_per_image");
+    VK_REQUIRE(B == 0 || (out->obj_ids && out->obj_probs && out->attr_ids && out->attr_probs && out->boxes && out->roi_features),
+               VK_EINVAL, "forward_boxes: null output array");
+    VK_REQUIRE(B == 0 || ((uintptr_t)out->roi_features & 15) == 0, VK_EINVAL, "forward_boxes: roi_features must be 16-byte aligned");
+    for (int n = 0; n < N; ++n) {
+        VK_REQUIRE(counts[n] >= 0 && counts[n] <= B, VK_EINVAL, "forward_boxes: counts[%d]=%d must be in 0..B=%d", n, counts[n], B);
+        VK_REQUIRE(image_hw[2 * n] >= 1 && image_hw[2 * n + 1] >= 1, VK_EINVAL,
+                   "forward_boxes: image_shapes[%d]=(%d,%d) must be positive", n, image_hw[2 * n], image_hw[2 * n + 1]);
     }
-    const int slot = (int)(h->next_ticket % vk_handle::VK_MAX_INFLIGHT);
-    VK_CHECK_HIP(hipMemcpyAsync(&h->flag_host[slot], p.nonfinite, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    VK_CHECK_HIP(hipEventRecord(h->ev_done[slot], s));
-    *ticket = h->next_ticket++;
-    return VK_OK;
+    VK_REQUIRE(h, VK_EINVAL, "forward_boxes: null handle");
+    VK_REQUIRE(h->next_ticket - h->oldest_open < vk_handle::VK_MAX_INFLIGHT, VK_EINVAL,
+               "forward_boxes_begin: %d forwards are already in flight; end the oldest first", vk_handle::VK_MAX_INFLIGHT);
+    VK_REQUIRE(h->finalized, VK_EINVAL, "forward_boxes: vk_finalize has not been called");
+    VK_CHECK_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (B == 0) {       // every image is empty: a zero-detection block, no kernel, no stage events
+        h->stages_out.clear();
+        h->ev_valid = false;
+        VK_CHECK_HIP(hipMemsetAsync(out->preds_per_image, 0, sizeof(int64_t) * (size_t)N, s));
+        return fwd_close(h, nullptr, s, ticket);
+    }
+    TimerScope timer_scope(h->ktimer);
+    const bool tm = h->timing;
+
+    Plan p;
+    VK_TRY(fwd_open(h, N, H, W, B, B, image_hw, scales_yx, counts, s, &p));
+    const void *res4 = nullptr;
+    VK_TRY(fwd_backbone(h, p, images_dev, s, &res4));
+    if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[2], s));          // no RPN head
+
+    // ---- the caller's boxes in place of the proposals: scale, finite check, _clip_box (frcnn.py:147-153), RoI rows ----
+    VK_TRY(launch_given_boxes_ingest(boxes_dev, p.prop_counts, p.image_hw, scales_yx ? p.scales : nullptr, N, B, p.prop_boxes,
+                                     p.rois, p.nonfinite, s));
+    set_stage(h, "proposal_boxes", p.prop_boxes, VK_F32, {N, B, 4});
+    set_stage(h, "proposal_counts", p.prop_counts, VK_I32, {N});
+    if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[3], s));
+
+    VK_TRY(fwd_head(h, p, res4, s));
+    if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[4], s));
+
+    // ---- outputs: every box in input order, no regression, no NMS ----
+    VK_TRY(launch_given_box_outputs(p.obj_prob, p.obj_cls, p.attr_prob, p.attr_cls, p.prop_boxes, p.prop_counts,
+                                    scales_yx ? p.scales : nullptr, p.feat, h->res5_c, N, B, *out, s));
+    return fwd_close(h, p.nonfinite, s, ticket);
 }
 
 int vk_forward_end(vk_handle *h, int64_t ticket) {

@@ -163,4 +163,13 @@ int launch_chosen_deltas(const void *x, int ldx, const void *w, const float *bia
 int launch_roi_final(RoiFinalArgs &a, int N, hipStream_t s);
 int launch_make_rois(const float *boxes, int N, int R, float *rois, hipStream_t s);
 
+// ---- given_boxes.hip (vk_forward_boxes_begin) ----
+// boxes [N,B,4] (rows >= counts[n] ignored) -> / scales_yx -> non-finite flag -> _clip_box -> prop_boxes [N,B,4], rois [N*B,5]
+int launch_given_boxes_ingest(const float *boxes, const int32_t *counts, const int32_t *image_hw, const float *scales_yx, int N,
+                              int B, float *prop_boxes, float *rois, int32_t *nonfinite, hipStream_t s);
+// vk_outputs [N,B] from the per-row predictions, the clipped boxes times the scales and the feature rows
+int launch_given_box_outputs(const float *obj_prob, const int32_t *obj_cls, const float *attr_prob, const int32_t *attr_cls,
+                             const float *prop_boxes, const int32_t *counts, const float *scales_yx, const float *feat, int F,
+                             int N, int B, const vk_outputs &out, hipStream_t s);
+
 }  // namespace vk

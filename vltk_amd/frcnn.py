@@ -69,6 +69,64 @@ def _c_config(cfg, precision):
 
 _TORCH_DT = {L.VK_F32: torch.float32, L.VK_F16: torch.float16, L.VK_I64: torch.int64, L.VK_I32: torch.int32}
 
+MAX_GIVEN_BOXES = 1024          # boxes per image of vk_forward_boxes_begin
+
+
+def _validate_proposals(proposals, N):
+    """-> (one [N, K, 4] tensor or a list of N [K_i, 4] tensors, counts int32 [N]); ValueError on a bad shape."""
+    if isinstance(proposals, (torch.Tensor, np.ndarray)):
+        t = torch.as_tensor(proposals)
+        if t.dim() != 3 or t.shape[2] != 4:
+            raise ValueError(f"proposals as one array must be [N, K, 4], got shape {tuple(t.shape)}")
+        if t.shape[0] != N:
+            raise ValueError(f"proposals: {t.shape[0]} images of boxes for {N} images")
+        if t.shape[1] > MAX_GIVEN_BOXES:
+            raise ValueError(f"proposals: {t.shape[1]} boxes per image, at most {MAX_GIVEN_BOXES}")
+        return t, np.full(N, t.shape[1], dtype=np.int32)
+    items = list(proposals)
+    if len(items) != N:
+        raise ValueError(f"proposals: {len(items)} images of boxes for {N} images")
+    ts = []
+    for i, b in enumerate(items):
+        t = b if isinstance(b, torch.Tensor) else torch.as_tensor(np.asarray(b, dtype=np.float32))
+        if t.numel() == 0 and t.dim() == 1:          # [] for an image without boxes
+            t = t.reshape(0, 4)
+        if t.dim() != 2 or t.shape[1] != 4:
+            raise ValueError(f"proposals[{i}] must be [K, 4], got {tuple(t.shape)}")
+        if t.shape[0] > MAX_GIVEN_BOXES:
+            raise ValueError(f"proposals[{i}]: {t.shape[0]} boxes, at most {MAX_GIVEN_BOXES}")
+        ts.append(t)
+    return ts, np.asarray([t.shape[0] for t in ts], dtype=np.int32).reshape(N)
+
+
+def pack_proposals(proposals, N, device=None):
+    """Validate caller-supplied boxes and pack them for vk_forward_boxes_begin.
+
+    proposals: a sequence of N arrays / tensors of shape [K_i, 4] (x0, y0, x1, y1; K_i may be 0), or one [N, K, 4]
+    array / tensor.  Returns (boxes, counts): boxes a contiguous float32 [N, B, 4] tensor on `device` (B = max K_i; rows
+    >= K_i are zero), counts a host int32 numpy array [N].  Raises ValueError on a wrong N, a wrong shape or K_i > 1024.
+    Non-finite values pass: the device flags them and the forward raises the reference's assertion (frcnn.py:148)."""
+    ts, counts = _validate_proposals(proposals, N)
+    if isinstance(ts, torch.Tensor):
+        return ts.to(device=device, dtype=torch.float32).contiguous(), counts
+    B = int(counts.max(initial=0))
+    if all(t.device.type == "cpu" for t in ts):       # one host-to-device copy
+        host = np.zeros((N, B, 4), dtype=np.float32)
+        for i, t in enumerate(ts):
+            host[i, :t.shape[0]] = t.detach().to(torch.float32).numpy()
+        return torch.from_numpy(host).to(device), counts
+    out = torch.zeros((N, B, 4), dtype=torch.float32, device=device)
+    for i, t in enumerate(ts):
+        out[i, :t.shape[0]] = t.detach().to(device=out.device, dtype=torch.float32)
+    return out, counts
+
+
+def check_given_width(width, max_detections):
+    """Given boxes are never truncated: an explicit max_detections below the widest image's box count is an error."""
+    if max_detections is not None and int(max_detections) < width:
+        raise ValueError(f"max_detections={int(max_detections)} is smaller than the {width} boxes given for one image; "
+                         "given boxes are never truncated")
+
 
 class _Ticket:
     """State of one forward in flight; the model keeps these in issue order (`FRCNN._open`)."""
@@ -77,7 +135,7 @@ class _Ticket:
 
     def __init__(self, ticket, block, images):
         self.ticket, self.block = ticket, block
-        self.images = images           # keeps the input alive until the kernels have read it
+        self.images = images           # keeps the input (and given boxes) alive until the kernels have read it
         self.done, self.error = False, None
 
 
@@ -86,8 +144,9 @@ class PendingForward:
     (garbage-collected) without a wait closes its own ticket and every older one that is still open, in order, so an
     out-of-order drop cannot leave tickets open (the results of those older forwards stay available to their handles)."""
 
-    def __init__(self, model, state, hw):
+    def __init__(self, model, state, hw, given_width=None):
         self.model, self._state, self.hw = model, state, hw
+        self.given_width = given_width      # given boxes: the output width (max boxes per image); None for detection
 
     @property
     def ticket(self):
@@ -108,6 +167,8 @@ class PendingForward:
         return st.block
 
     def wait(self, **kwargs):
+        if self.given_width is not None:
+            check_given_width(self.given_width, kwargs.get("max_detections"))
         return FRCNN._format(self.wait_raw(), self.hw, **kwargs)
 
     def __del__(self):
@@ -119,6 +180,8 @@ class PendingForward:
 
 
 class FRCNN:
+    given_boxes = True                   # forward(proposals=...): region features for caller-supplied boxes (C4 only)
+
     def __new__(cls, cfg=None, *a, **k):
         # several RPN input levels = the FPN detector (frcnn_fpn.py, a build extension); one = the reference's C4 model
         if cls is FRCNN and cfg is not None and len(cfg.RPN.IN_FEATURES) > 1:
@@ -267,17 +330,29 @@ class FRCNN:
 
     def forward(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None, **kwargs):
         """kwargs (v1.0.0 semantics): max_detections, return_tensors {"np","pt",None},
-        padding {None,"max_detections","max_batch"}, pad_value, location {"cuda","cpu"}."""
+        padding {None,"max_detections","max_batch"}, pad_value, location {"cuda","cpu"}.
+
+        proposals (C4 model): region features for caller-supplied boxes instead of detection.  A sequence of N
+        [K_i, 4] arrays / tensors (x0, y0, x1, y1; 0 <= K_i <= 1024) or one [N, K, 4] tensor, in the frame of the
+        returned `boxes`: network-input pixels, or original-image pixels when `scales_yx` is given (x is divided by
+        scales_yx[n][1], y by scales_yx[n][0] on the device).  Every box is kept, in input order: clipped to
+        image_shapes[n] (_clip_box frcnn.py:147-153; a non-finite box raises its AssertionError), RoI-pooled, run through
+        the Res5 head (roi_features) and the box predictor (obj_probs / obj_ids: max / arg-max of the soft-max over the
+        first C classes; attr_probs / attr_ids on that class); `boxes` = the clipped box times the scales, with no box
+        regression and no NMS; preds_per_image[n] = K_i.  roi_outputs.{nms_thresh, min_detections, max_detections}
+        are not used; the output width is max K_i, and an explicit max_detections below it raises ValueError."""
+        if proposals is not None and self.given_boxes:         # before anything is enqueued
+            counts = _validate_proposals(proposals, len(images))[1]
+            check_given_width(int(counts.max(initial=0)), kwargs.get("max_detections"))
         return self.forward_async(images, image_shapes, gt_boxes, proposals, scales_yx, ignorey).wait(**kwargs)
 
     def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None):
-        """Enqueue a forward and return at once (vk_forward_begin); `.wait(**kwargs)` on the returned handle finishes it
-        (vk_forward_end) and formats the outputs like forward().  Up to four may be in flight; they must be waited for
-        in order, on the same stream.  The caller must not modify `images` before wait() returns."""
+        """Enqueue a forward and return at once (vk_forward_begin, or vk_forward_boxes_begin with `proposals`, see
+        forward()); `.wait(**kwargs)` on the returned handle finishes it (vk_forward_end) and formats the outputs like
+        forward().  Up to four may be in flight, detection and given-box forwards mixed; they must be waited for in
+        order, on the same stream.  The caller must not modify `images` (or the proposals) before wait() returns."""
         if self.training:
             raise NotImplementedError()            # frcnn.py:1930-1931
-        if proposals is not None:
-            raise NotImplementedError("precomputed proposals: the reference path is broken (frcnn.py:1957-1963)")
         if ignorey is not None:
             raise NotImplementedError("ignorey is not supported")
         if not self._finalized:
@@ -291,6 +366,21 @@ class FRCNN:
         sc = None
         if scales_yx is not None:
             sc = np.ascontiguousarray(np.asarray(torch.as_tensor(scales_yx).cpu(), dtype=np.float32).reshape(N, 2))
+        F = self.config.RESNETS.RES2_OUT_CHANNELS * 8
+        dev = self.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ticket = C.c_int64(-1)
+        if proposals is not None:
+            boxes, counts = pack_proposals(proposals, N, dev)
+            B = boxes.shape[1]
+            bufs = OutputBlock(output_spec(N, B, F), device=dev)
+            out = L.vk_outputs(*[bufs[k].data_ptr() for k in bufs])
+            L.call("vk_forward_boxes_begin", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p),
+                   sc.ctypes.data_as(C.c_void_p) if sc is not None else None, boxes.data_ptr() if B else None, B,
+                   counts.ctypes.data_as(C.c_void_p), C.byref(out), C.c_void_p(stream), C.byref(ticket))
+            st = _Ticket(ticket.value, bufs, (images, boxes))
+            self._open.append(st)
+            return PendingForward(self, st, hw, given_width=B)
         ro = self.roi_outputs
         D = int(ro.max_detections)
         rp = L.vk_roi_params()
@@ -301,13 +391,9 @@ class FRCNN:
         for i, t in enumerate(thr):
             rp.nms_thresh[i] = float(t)
         rp.min_detections, rp.max_detections = int(ro.min_detections), D
-        F = self.config.RESNETS.RES2_OUT_CHANNELS * 8
-        dev = self.device
         # one flat block, the seven arrays are views (so the multi-GPU exchange is a single all-gather: parallel.py)
         bufs = OutputBlock(output_spec(N, D, F), device=dev)
         out = L.vk_outputs(*[bufs[k].data_ptr() for k in bufs])
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ticket = C.c_int64(-1)
         L.call("vk_forward_begin", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p),
                sc.ctypes.data_as(C.c_void_p) if sc is not None else None, C.byref(rp), C.byref(out),
                C.c_void_p(stream), C.byref(ticket))

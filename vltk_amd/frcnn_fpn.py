@@ -175,6 +175,7 @@ class _Done:
 
 class FRCNNFPN(FRCNN):
     STAGES = ("res2", "res3", "res4", "res5")
+    given_boxes = False                  # forward(proposals=...) raises NotImplementedError (forward_async)
 
     def __init__(self, cfg, precision=None, device=None):
         if not torch.cuda.is_available():

@@ -6,7 +6,9 @@ hundreds of images per second on an MI355X everything around the forward has to 
 
     loader thread      next batch of raw HWC images (uint8 or float, BGR 0-255) is collected while the GPU works
     main thread        upload -> GPU pre-processing (vltk_amd.Preprocess: the legacy contract, scales_yx = raw/size)
-                       -> FRCNN forward with `scales_yx` (boxes come back in raw-image coordinates, frcnn.py:1280-1283)
+                       -> FRCNN forward with `scales_yx` (boxes come back in raw-image coordinates, frcnn.py:1280-1283);
+                          with `boxes` (imgid -> [K, 4] in raw-image coordinates) the given-box forward
+                          (FRCNN.forward(proposals=...)), its [B, max K] block widened to the schema's D with zeros
                        -> [world > 1: ONE all-gather of the flat output block, parallel.py]
                        -> asynchronous device-to-host copy of the flat block into a pinned ring slot (copy stream)
     writer thread      waits for the slot's event, rounds the boxes (adapters/frcnn.py:57) and streams the rows to the
@@ -41,8 +43,10 @@ class ExtractionPipeline:
     preprocess: vltk_amd.preprocess.Preprocess (or a callable (raws, ids) -> (ids, images, sizes, scales_yx))."""
 
     def __init__(self, model, preprocess, savefile, batch_size=32, visual_dim=2048, dataset=None, processor_args=None,
-                 model_config=None, group=None, depth=2):
+                 model_config=None, group=None, depth=2, boxes=None):
         self.model, self.preprocess = model, preprocess
+        # given boxes: imgid -> [K, 4] (raw-image pixels, K <= max_detections) for every image this rank sees
+        self.boxes = None if boxes is None else {str(k): v for k, v in boxes.items()}
         self.B, self.F = int(batch_size), int(visual_dim)
         self.D = int(model.roi_outputs.max_detections)
         self.group = group
@@ -146,6 +150,8 @@ class ExtractionPipeline:
 
         def finish(p, ids, n_valid, step):
             blk = p.wait_raw()
+            if self.boxes is not None:
+                blk = self._widen(blk)
             slot = step % self.depth
             if self.rank == 0:
                 # back-pressure: at most `depth` batches in flight; slot s owns pinned buffer s AND gather buffer s, so
@@ -192,10 +198,13 @@ class ExtractionPipeline:
                 else:
                     dev_raws = [torch.from_numpy(r) for r in raws]
                 _, images, sizes, scales_yx = self.preprocess(dev_raws, list(range(self.B)))
+                kw = {}
+                if self.boxes is not None:                    # the padding repeats of the last image repeat its boxes
+                    kw["proposals"] = [self.boxes[i] for i in ids] + [self.boxes[ids[-1]]] * (self.B - n_valid)
                 if hasattr(self.model, "forward_async"):      # enqueue this batch behind the previous one, then finish that one
-                    p = self.model.forward_async(images, sizes, scales_yx=scales_yx)
+                    p = self.model.forward_async(images, sizes, scales_yx=scales_yx, **kw)
                 else:
-                    self.model(images, sizes, scales_yx=scales_yx)
+                    self.model(images, sizes, scales_yx=scales_yx, **kw)
                     p = _Finished(self.model.forward_padded())
                 if prev is not None:
                     finish(*prev)
@@ -209,6 +218,22 @@ class ExtractionPipeline:
         if self._writer_error is not None:
             raise self._writer_error
         return self.writer.close() if self.rank == 0 else None
+
+    def _widen(self, blk):
+        """A given-box block [B, max K, ...] -> the step's [B, D, ...] block, zeros beyond max K (on the device)."""
+        w = blk["obj_ids"].shape[1]
+        if w == self.D:
+            return blk
+        if w > self.D:
+            raise ValueError(f"{w} boxes for one image, more than max_detections={self.D}")
+        out = OutputBlock(self.spec, device=blk["obj_ids"].device)
+        out.flat.zero_()
+        for k, v in blk.items():
+            if k == "preds_per_image":
+                out[k].copy_(v)
+            else:
+                out[k][:, :w].copy_(v)
+        return out
 
     # ids held by other ranks: rank 0 needs them to label the gathered rows.  Default: the caller registered the
     # global id list with set_global_ids(); a one-rank run never gets here.
