@@ -109,6 +109,8 @@ int vk_version(void);
  *                                               frcnn.py:1862-1881
  * vk_finalize      <- model.eval() + BN folding / NHWC repack (frcnn.py:1920; Conv2d :794-822)
  * vk_destroy       <- Python GC
+ * One process may hold handles on several devices (the device index of vk_create); the kernel launchers keep their state
+ * (LDS limits, scratch pages, CU count) per device.
  */
 int vk_create(const vk_config *cfg, int device, vk_handle **out);
 int vk_load_weights(vk_handle *h, const char *name, const void *host_ptr,

@@ -49,7 +49,6 @@ constexpr int BN_TH = 8, BN_TW = 32, BN_PH = 10, BN_PW = 34, BN_NP = BN_PH * BN_
 constexpr int bn_chpx(int cin) { return cin == 256 ? 32 : 128; }
 constexpr int bn_ring(int cin) { return cin == 256 ? 5 : 3; }
 constexpr int BN_T1_BYTES = BN_NP * 128, BN_T2_BYTES = BN_TH * BN_TW * 128;
-constexpr int BN_TRASH_BYTES = 1 << 16;
 
 template <int CIN>
 constexpr int bn_smem() { return bn_ring(CIN) * bn_chpx(CIN) * CIN * 2 + BN_T1_BYTES + BN_T2_BYTES + 384 * 4; }   // + the biases
@@ -782,18 +781,9 @@ int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, c
                        const float *b2, const void *w3, const float *b3, void *y, bool concurrent, hipStream_t stream) {
     VK_REQUIRE(bneck_fused_eligible(cin, 64, 256, 1, 1, proj, N, H, W, VK_F16) || getenv("VK_BNECK_FUSED"), VK_EINVAL,
                "bneck_fused: shape not eligible");
-    int dev = 0;
-    VK_CHECK_HIP(hipGetDevice(&dev));
-    VK_REQUIRE(dev >= 0 && dev < VK_MAX_DEVICES, VK_EINVAL, "bneck_fused: device index %d", dev);
-    static char *trash[VK_MAX_DEVICES] = {};
-    static int n_cu[VK_MAX_DEVICES] = {};
-    static bool attr[VK_MAX_DEVICES][2] = {};
-    if (!trash[dev]) {
-        VK_CHECK_HIP(hipMalloc((void **)&trash[dev], BN_TRASH_BYTES));
-        hipDeviceProp_t prop;
-        VK_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
-        n_cu[dev] = prop.multiProcessorCount > 8 ? prop.multiProcessorCount / 8 * 8 : 8;
-    }
+    DeviceState *ds = nullptr;
+    VK_TRY(device_state(&ds));
+    const int n_cu = ds->n_cu > 8 ? ds->n_cu / 8 * 8 : 8;
     BneckK k;
     k.x = (const char *)x;
     k.w1 = (const char *)w1;
@@ -803,7 +793,7 @@ int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, c
     k.b2 = b2;
     k.b3 = b3;
     k.y = (char *)y;
-    k.trash = trash[dev];
+    k.trash = ds->bn_trash;
     k.N = N;
     k.H = H;
     k.W = W;
@@ -824,7 +814,7 @@ int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, c
         r.b2 = b2;
         r.b3 = b3;
         r.y = (char *)y;
-        r.trash = trash[dev];
+        r.trash = ds->bn_trash;
         r.N = N;
         r.H = H;
         r.W = W;
@@ -832,7 +822,7 @@ int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, c
         r.strips = ceil_div(W, r.tw);
         // rows per unit: the split of the image height that takes the fewest steps over the rounds of the grid (a unit of ru rows
         // takes ru + 4 steps and a prologue; at least 16 rows per unit)
-        const int grid_ = n_cu[dev];
+        const int grid_ = n_cu;
         long best = -1;
         r.vsplit = 1;
         for (int vs = 1; vs <= std::max(1, H / 16); ++vs) {
@@ -850,14 +840,8 @@ int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, c
         VK_REQUIRE(nu > 0 && nu < (1L << 31), VK_EINVAL, "bneck_fused: %ld units", nu);
         r.nunits = (int)nu;
         r.stamps = nullptr;
-        static bool rattr[VK_MAX_DEVICES][2] = {};
-        KernelTimer *tmr = g_timer;
-        hipEvent_t f0 = nullptr, f1 = nullptr;
-        if (tmr) {
-            f0 = tmr->get();
-            f1 = tmr->get();
-            VK_CHECK_HIP(hipEventRecord(f0, stream));
-        }
+        Timed t;
+        VK_TRY(t.begin(stream));
 #ifdef VK_ABLATION
         if (const char *sf = getenv("VK_BNECK_STAMPS")) {     // diagnostic: one stamped launch, 8 words per wave appended to the file
             const size_t nb = (size_t)grid_ * 4 * 8 * sizeof(unsigned long);
@@ -865,19 +849,19 @@ int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, c
             VK_CHECK_HIP(hipMemsetAsync(r.stamps, 0, nb, stream));
             const int dbg = getenv("VK_BNECK_DBG") ? atoi(getenv("VK_BNECK_DBG")) : 0;
             if (proj) {
-                VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bneck64_rows_kernel<64, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, br_smem<64>()));
+                VK_TRY(set_max_lds(bneck64_rows_kernel<64, true, true>, br_smem<64>()));
                 hipLaunchKernelGGL((bneck64_rows_kernel<64, true, true>), dim3(grid_), dim3(512), br_smem<64>(), stream, r);
             } else {
                 switch (dbg) {
 #define VKN_DBG_CASE(D_)                                                                                                                   \
     case D_:                                                                                                                               \
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bneck64_rows_kernel<256, false, true, D_>), hipFuncAttributeMaxDynamicSharedMemorySize, br_smem<256>())); \
+        VK_TRY(set_max_lds(bneck64_rows_kernel<256, false, true, D_>, br_smem<256>()));                                                     \
         hipLaunchKernelGGL((bneck64_rows_kernel<256, false, true, D_>), dim3(grid_), dim3(512), br_smem<256>(), stream, r);                 \
         break;
                     VKN_DBG_CASE(1) VKN_DBG_CASE(2) VKN_DBG_CASE(4) VKN_DBG_CASE(8) VKN_DBG_CASE(16) VKN_DBG_CASE(7) VKN_DBG_CASE(15) VKN_DBG_CASE(31) VKN_DBG_CASE(24) VKN_DBG_CASE(3)
 #undef VKN_DBG_CASE
                     default:
-                        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bneck64_rows_kernel<256, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, br_smem<256>()));
+                        VK_TRY(set_max_lds(bneck64_rows_kernel<256, false, true>, br_smem<256>()));
                         hipLaunchKernelGGL((bneck64_rows_kernel<256, false, true>), dim3(grid_), dim3(512), br_smem<256>(), stream, r);
                 }
             }
@@ -898,30 +882,20 @@ int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, c
         }
 #endif
         if (proj) {
-            if (!rattr[dev][1]) {
-                VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bneck64_rows_kernel<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, br_smem<64>()));
-                rattr[dev][1] = true;
-            }
+            VK_TRY(set_max_lds(bneck64_rows_kernel<64, true>, br_smem<64>()));
             hipLaunchKernelGGL((bneck64_rows_kernel<64, true>), dim3(grid_), dim3(512), br_smem<64>(), stream, r);
         } else {
-            if (!rattr[dev][0]) {
-                VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bneck64_rows_kernel<256, false>), hipFuncAttributeMaxDynamicSharedMemorySize, br_smem<256>()));
-                rattr[dev][0] = true;
-            }
+            VK_TRY(set_max_lds(bneck64_rows_kernel<256, false>, br_smem<256>()));
             hipLaunchKernelGGL((bneck64_rows_kernel<256, false>), dim3(grid_), dim3(512), br_smem<256>(), stream, r);
         }
         VK_CHECK_HIP(hipGetLastError());
-        if (tmr) {
-            VK_CHECK_HIP(hipEventRecord(f1, stream));
-            const double M = (double)N * H * W;
-            const double fl = 2.0 * M * (64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64));
-            tmr->recs.push_back({concurrent ? 6 : 11, fl, f0, f1, (int)M, 256, cin, 3, 1,
-                                 2.0 * (M * cin + M * 256 + 64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64))});
-        }
-        return VK_OK;
+        const double M = (double)N * H * W;
+        const double fl = 2.0 * M * (64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64));
+        return t.end(stream, concurrent ? 6 : 11, fl, (int)M, 256, cin, 3, 1,
+                     2.0 * (M * cin + M * 256 + 64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64)));
     }
     VK_REQUIRE((long)N * H * W * 512 < (1L << 31), VK_EINVAL, "bneck_fused: the tile form keeps signed 32-bit byte offsets");
-    const int grid = n_cu[dev];                   // a multiple of 8: every XCD walks its own range of tiles
+    const int grid = n_cu;                        // a multiple of 8: every XCD walks its own range of tiles
     k.stamps = nullptr;
 #ifdef VK_ABLATION
     if (const char *sf = getenv("VK_BNECK_STAMPS")) {     // diagnostic: one stamped launch, 8 words per wave appended to the file
@@ -929,10 +903,10 @@ int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, c
         VK_CHECK_HIP(hipMalloc((void **)&k.stamps, nb));
         VK_CHECK_HIP(hipMemsetAsync(k.stamps, 0, nb, stream));
         if (proj) {
-            VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bneck64_kernel<64, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bn_smem<64>()));
+            VK_TRY(set_max_lds(bneck64_kernel<64, true, true>, bn_smem<64>()));
             hipLaunchKernelGGL((bneck64_kernel<64, true, true>), dim3(grid), dim3(256), bn_smem<64>(), stream, k);
         } else {
-            VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bneck64_kernel<256, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bn_smem<256>()));
+            VK_TRY(set_max_lds(bneck64_kernel<256, false, true>, bn_smem<256>()));
             hipLaunchKernelGGL((bneck64_kernel<256, false, true>), dim3(grid), dim3(256), bn_smem<256>(), stream, k);
         }
         VK_CHECK_HIP(hipStreamSynchronize(stream));
@@ -951,35 +925,20 @@ int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, c
         return VK_OK;
     }
 #endif
-    KernelTimer *tm = g_timer;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (tm) {
-        e0 = tm->get();
-        e1 = tm->get();
-        VK_CHECK_HIP(hipEventRecord(e0, stream));
-    }
+    Timed t;
+    VK_TRY(t.begin(stream));
     if (proj) {
-        if (!attr[dev][1]) {
-            VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bneck64_kernel<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bn_smem<64>()));
-            attr[dev][1] = true;
-        }
+        VK_TRY(set_max_lds(bneck64_kernel<64, true>, bn_smem<64>()));
         hipLaunchKernelGGL((bneck64_kernel<64, true>), dim3(grid), dim3(256), bn_smem<64>(), stream, k);
     } else {
-        if (!attr[dev][0]) {
-            VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bneck64_kernel<256, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bn_smem<256>()));
-            attr[dev][0] = true;
-        }
+        VK_TRY(set_max_lds(bneck64_kernel<256, false>, bn_smem<256>()));
         hipLaunchKernelGGL((bneck64_kernel<256, false>), dim3(grid), dim3(256), bn_smem<256>(), stream, k);
     }
     VK_CHECK_HIP(hipGetLastError());
-    if (tm) {
-        VK_CHECK_HIP(hipEventRecord(e1, stream));
-        const double M = (double)N * H * W;
-        const double fl = 2.0 * M * (64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64));
-        tm->recs.push_back({concurrent ? 6 : 11, fl, e0, e1, (int)M, 256, cin, 3, 1,
-                            2.0 * (M * cin + M * 256 + 64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64))});
-    }
-    return VK_OK;
+    const double M = (double)N * H * W;
+    const double fl = 2.0 * M * (64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64));
+    return t.end(stream, concurrent ? 6 : 11, fl, (int)M, 256, cin, 3, 1,
+                 2.0 * (M * cin + M * 256 + 64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64)));
 }
 
 }  // namespace vk

@@ -258,23 +258,9 @@ bool conv3x3_blk_eligible(const ConvArgs &a) { return blk_variant(a) != 0; }
 template <int CB, int TH, int TW, int VW, int DIL>
 static int launch_blk(const ConvArgs &a, hipStream_t stream) {
     constexpr int smem = 2 * ((((TH + 2 * DIL) * (TW + 2 * DIL) + 7) / 8 + 7) / 8) * 8 * 1024 + 256;
-    // per device: the zero page lives in the memory of the device that reads it, and the LDS attribute is set on each
-    // device's copy of the code object (a process may hold handles on several GPUs: vk_create takes a device index)
-    int dev = 0;
-    VK_CHECK_HIP(hipGetDevice(&dev));
-    VK_REQUIRE(dev >= 0 && dev < VK_MAX_DEVICES, VK_EINVAL, "conv3x3_blk: device index %d", dev);
-    static char *zero_pages[VK_MAX_DEVICES] = {};
-    if (!zero_pages[dev]) {
-        VK_CHECK_HIP(hipMalloc((void **)&zero_pages[dev], 256));
-        VK_CHECK_HIP(hipMemset(zero_pages[dev], 0, 256));
-    }
-    char *zero_page = zero_pages[dev];
-    static bool attr_set[VK_MAX_DEVICES] = {};
-    if (!attr_set[dev]) {
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_blk_kernel<CB, TH, TW, VW, DIL>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set[dev] = true;
-    }
+    DeviceState *ds = nullptr;
+    VK_TRY(device_state(&ds));
+    VK_TRY(set_max_lds(conv3x3_blk_kernel<CB, TH, TW, VW, DIL>, smem));
     BlkK k;
     k.x = (const char *)a.x;
     k.w = (const char *)a.w;
@@ -291,7 +277,7 @@ static int launch_blk(const ConvArgs &a, hipStream_t stream) {
     const long nt = (long)a.N * k.tiles_x * k.tiles_y;
     VK_REQUIRE(nt > 0 && nt < (1L << 31), VK_EINVAL, "conv3x3_blk: %ld tiles", nt);
     k.ntiles = (int)nt;
-    k.zero = zero_page;
+    k.zero = ds->zero_page;
     const int slabs = a.Cin / 64;
     // one workgroup per CU over all slabs; a workgroup keeps its slab's weights in registers across its tiles
     int gx = 256 / slabs;
@@ -299,21 +285,12 @@ static int launch_blk(const ConvArgs &a, hipStream_t stream) {
     if (gx > k.ntiles) gx = k.ntiles;
     const int cg = a.groups > 1 ? a.Cin / a.groups : a.Cin;
     const long M = (long)a.N * a.H * a.W;
-    KernelTimer *tm = g_timer;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (tm) {
-        e0 = tm->get();
-        e1 = tm->get();
-        VK_CHECK_HIP(hipEventRecord(e0, stream));
-    }
+    Timed t;
+    VK_TRY(t.begin(stream));
     hipLaunchKernelGGL((conv3x3_blk_kernel<CB, TH, TW, VW, DIL>), dim3(gx, slabs), dim3(512), smem, stream, k);
     VK_CHECK_HIP(hipGetLastError());
-    if (tm) {
-        VK_CHECK_HIP(hipEventRecord(e1, stream));
-        tm->recs.push_back({a.concurrent ? 6 : 7, 2.0 * (double)M * a.Cout * 9.0 * cg, e0, e1, (int)M, a.Cout, a.Cin, 3, 1,
-                            2.0 * (double)M * a.Cin * 2.0 + (double)a.Cout * 9.0 * cg * 2.0});
-    }
-    return VK_OK;
+    return t.end(stream, a.concurrent ? 6 : 7, 2.0 * (double)M * a.Cout * 9.0 * cg, (int)M, a.Cout, a.Cin, 3, 1,
+                 2.0 * (double)M * a.Cin * 2.0 + (double)a.Cout * 9.0 * cg * 2.0);
 }
 
 int launch_conv3x3_blk(const ConvArgs &a, hipStream_t stream) {

@@ -600,16 +600,9 @@ static int panel_pp(const ConvArgs &a, int mi = 8) {
     return reach <= 64 ? 3 : (reach <= 128 ? 4 : 0);
 }
 
-// 8 or 9 row tiles per wave (256- or 288-pixel tiles): whichever takes fewer MFMA rows over the rounds of the grid on this device.
-// VK_PANEL_MI=8 / 9 forces one where it is legal (A/B switch and bit-identity tests; re-read per call).
-static int panel_mi(const ConvArgs &a, long M) {
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 8;
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+// 8 or 9 row tiles per wave (256- or 288-pixel tiles): whichever takes fewer MFMA rows over the rounds of the grid on a device
+// of n_cu CUs.  VK_PANEL_MI=8 / 9 forces one where it is legal (A/B switch and bit-identity tests; re-read per call).
+static int panel_mi(const ConvArgs &a, long M, int n_cu) {
     if (panel_pp(a, 9) == 0) return 8;
     if (const char *v = getenv("VK_PANEL_MI")) {
         if (v[0] == '8') return 8;
@@ -637,6 +630,8 @@ bool conv3x3_panel_eligible(const ConvArgs &a) {
 }
 
 int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream) {
+    DeviceState *ds = nullptr;
+    VK_TRY(device_state(&ds));
     PanelK k;
     k.x = (const char *)a.x;
     k.w = (const char *)a.w;
@@ -657,16 +652,11 @@ int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream) {
     k.cstages = a.Cin / 32;
     k.wrow_bytes = 9 * a.Cin * 2;
     k.relu = a.relu;
-    const int mi = panel_mi(a, M), pp = panel_pp(a, mi);
+    const int mi = panel_mi(a, M, ds->n_cu), pp = panel_pp(a, mi);
     k.m_tiles = ceil_div(k.M, mi * 32);
     k.n_tiles = a.Cout / 256;
-    KernelTimer *tm = g_timer;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (tm) {
-        e0 = tm->get();
-        e1 = tm->get();
-        VK_CHECK_HIP(hipEventRecord(e0, stream));
-    }
+    Timed t;
+    VK_TRY(t.begin(stream));
     const int total_tiles = k.m_tiles * k.n_tiles;
     k.tile_ctr = nullptr;
     k.static_tiles = total_tiles;
@@ -687,12 +677,7 @@ int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream) {
     k.stamps = nullptr;
 #define VKP_LAUNCH(PP_, DBG_, TAG_, MI_)                                                                                                   \
     do {                                                                                                                                   \
-        static bool attr_ = false;                                                                                                         \
-        if (!attr_) {                                                                                                                      \
-            VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_panel_kernel<PP_, DBG_, TAG_, MI_>),                  \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PP_ * 128 * 64 + P_NW * P_WSLOT + (PP_ == 3 ? 256 : 0)));            \
-            attr_ = true;                                                                                                                  \
-        }                                                                                                                                  \
+        VK_TRY(set_max_lds(conv3x3_panel_kernel<PP_, DBG_, TAG_, MI_>, 2 * PP_ * 128 * 64 + P_NW * P_WSLOT + (PP_ == 3 ? 256 : 0)));        \
         hipLaunchKernelGGL((conv3x3_panel_kernel<PP_, DBG_, TAG_, MI_>), grid, block, smem, stream, k);                                     \
     } while (0)
 #ifdef VK_ABLATION      // stamp / timing-only (dbg 1: WRONG results) / LDS-epilogue builds: tools/ builds only (make ABLATION=1)
@@ -745,12 +730,8 @@ int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream) {
         VKP_LAUNCH(4, 0, 0, 9);
 #undef VKP_LAUNCH
     VK_CHECK_HIP(hipGetLastError());
-    if (tm) {
-        VK_CHECK_HIP(hipEventRecord(e1, stream));
-        tm->recs.push_back({a.concurrent ? 6 : 4, 2.0 * (double)k.M * a.Cout * 9 * a.Cin, e0, e1, k.M, a.Cout, a.Cin, 9, 1,
-                            2.0 * ((double)k.M * a.Cin + (double)k.M * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * 9 * a.Cin)});
-    }
-    return VK_OK;
+    return t.end(stream, a.concurrent ? 6 : 4, 2.0 * (double)k.M * a.Cout * 9 * a.Cin, k.M, a.Cout, a.Cin, 9, 1,
+                 2.0 * ((double)k.M * a.Cin + (double)k.M * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * 9 * a.Cin));
 }
 
 }  // namespace vk

@@ -20,9 +20,6 @@
 #include <type_traits>
 #include <vector>
 
-#include <atomic>
-#include <mutex>
-
 #include "vk_common.h"
 
 namespace vk {
@@ -483,22 +480,9 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
 // in advance, and the workgroup that draws the last one writes the zero back.  (A slot comes round again after 256 launches WITH a tail; a handle keeps at most
 // four forwards of seven such launches in flight, and the wrap is exercised by every bench run.)
 int acquire_tile_counter(unsigned **ctr) {
-    static unsigned *ring[VK_MAX_DEVICES];
-    static std::atomic<unsigned> next[VK_MAX_DEVICES];
-    static std::mutex mu;
-    int dev = 0;
-    VK_CHECK_HIP(hipGetDevice(&dev));
-    VK_REQUIRE(dev >= 0 && dev < VK_MAX_DEVICES, VK_EINVAL, "device %d beyond VK_MAX_DEVICES", dev);
-    if (!ring[dev]) {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!ring[dev]) {
-            unsigned *r = nullptr;
-            VK_CHECK_HIP(hipMalloc((void **)&r, 256 * sizeof(unsigned)));
-            VK_CHECK_HIP(hipMemset(r, 0, 256 * sizeof(unsigned)));      // (synchronous: done before any launch can use a word)
-            ring[dev] = r;
-        }
-    }
-    *ctr = ring[dev] + (next[dev].fetch_add(1) & 255u);
+    DeviceState *ds = nullptr;
+    VK_TRY(device_state(&ds));
+    *ctr = ds->tile_ring + (ds->tile_next.fetch_add(1) & 255u);
     return VK_OK;
 }
 
@@ -526,14 +510,8 @@ bool conv_gemm4_eligible(const ConvArgs &a) {
 }
 
 int launch_conv_gemm4(const ConvArgs &a, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_gemm4_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, G_SMEM + 32768));
-#ifdef VK_ABLATION
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_gemm4_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, G_SMEM + 32768));
-#endif
-        attr_set = true;
-    }
+    DeviceState *ds = nullptr;
+    VK_TRY(device_state(&ds));
     const int cin2 = a.x2 ? a.Cin2 : 0;
     Gemm4K k;
     k.x = (const char *)a.x;
@@ -558,23 +536,11 @@ int launch_conv_gemm4(const ConvArgs &a, hipStream_t stream) {
     k.n_tiles = a.Cout / 256;
     VK_REQUIRE(k.stages >= 8 && k.stages % 4 == 0, VK_EINVAL, "conv_gemm4: K = %d", a.Cin + cin2);
 
-    KernelTimer *tm = g_timer;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (tm) {
-        e0 = tm->get();
-        e1 = tm->get();
-        VK_CHECK_HIP(hipEventRecord(e0, stream));
-    }
+    Timed t;
+    VK_TRY(t.begin(stream));
     k.stamps = nullptr;
     // persistent workgroups, one per CU; a multiple of 8 so that a workgroup's tiles (bid, bid + grid, ...) stay on its XCD
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        VK_CHECK_HIP(hipGetDevice(&dev));
-        VK_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
-        n_cu = prop.multiProcessorCount > 8 ? prop.multiProcessorCount / 8 * 8 : 8;
-    }
+    const int n_cu = ds->n_cu > 8 ? ds->n_cu / 8 * 8 : 8;
     const int total_tiles = k.m_tiles * k.n_tiles;
     const int grid_wgs = total_tiles < n_cu ? total_tiles : n_cu;
     k.tile_ctr = nullptr;
@@ -596,12 +562,14 @@ int launch_conv_gemm4(const ConvArgs &a, hipStream_t stream) {
         switch (d ? atoi(d) : 0) {
 #define VKG_DBG_CASE(D_)                                                                                                   \
     case D_:                                                                                                               \
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_gemm4_kernel<true, D_>), hipFuncAttributeMaxDynamicSharedMemorySize, G_SMEM + 32768)); \
+        VK_TRY(set_max_lds(conv_gemm4_kernel<true, D_>, G_SMEM + 32768));                                                 \
         hipLaunchKernelGGL((conv_gemm4_kernel<true, D_>), dim3(nwg), dim3(256), smem_bytes, stream, k);                        \
         break;
             VKG_DBG_CASE(1) VKG_DBG_CASE(2) VKG_DBG_CASE(3) VKG_DBG_CASE(4) VKG_DBG_CASE(8) VKG_DBG_CASE(12) VKG_DBG_CASE(13) VKG_DBG_CASE(15)
 #undef VKG_DBG_CASE
-            default: hipLaunchKernelGGL(conv_gemm4_kernel<true>, dim3(nwg), dim3(256), smem_bytes, stream, k);
+            default:
+                VK_TRY(set_max_lds(conv_gemm4_kernel<true>, G_SMEM + 32768));
+                hipLaunchKernelGGL(conv_gemm4_kernel<true>, dim3(nwg), dim3(256), smem_bytes, stream, k);
         }
         VK_CHECK_HIP(hipStreamSynchronize(stream));
         std::vector<unsigned long> h((size_t)nwg * 8);
@@ -617,28 +585,21 @@ int launch_conv_gemm4(const ConvArgs &a, hipStream_t stream) {
             fclose(f);
         }
     } else if (getenv("VK_GEMM4_DBG") && atoi(getenv("VK_GEMM4_DBG")) == 128) {      // bisect: builtin MFMAs
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_gemm4_kernel<false, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, G_SMEM + 32768));
+        VK_TRY(set_max_lds(conv_gemm4_kernel<false, 128>, G_SMEM + 32768));
         hipLaunchKernelGGL((conv_gemm4_kernel<false, 128>), dim3(grid_wgs), dim3(256), smem_bytes, stream, k);
     } else
 #endif
-    if (a.concurrent) {
-        static bool attr1 = false;
-        if (!attr1) {
-            VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_gemm4_kernel<false, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, G_SMEM + 32768));
-            attr1 = true;
-        }
-        hipLaunchKernelGGL((conv_gemm4_kernel<false, 0, 1>), dim3(grid_wgs), dim3(256), smem_bytes, stream, k);
-    } else {
+    if (!a.concurrent) {
+        VK_TRY(set_max_lds(conv_gemm4_kernel<false>, G_SMEM + 32768));
         hipLaunchKernelGGL(conv_gemm4_kernel<false>, dim3(grid_wgs), dim3(256), smem_bytes, stream, k);
+    } else {
+        VK_TRY(set_max_lds(conv_gemm4_kernel<false, 0, 1>, G_SMEM + 32768));
+        hipLaunchKernelGGL((conv_gemm4_kernel<false, 0, 1>), dim3(grid_wgs), dim3(256), smem_bytes, stream, k);
     }
     VK_CHECK_HIP(hipGetLastError());
-    if (tm) {
-        VK_CHECK_HIP(hipEventRecord(e1, stream));
-        const int K = a.Cin + cin2;
-        tm->recs.push_back({a.concurrent ? 6 : 10, 2.0 * (double)M * a.Cout * K, e0, e1, (int)M, a.Cout, K, 1, 1,
-                            2.0 * ((double)M * K + (double)M * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * K)});
-    }
-    return VK_OK;
+    const int K = a.Cin + cin2;
+    return t.end(stream, a.concurrent ? 6 : 10, 2.0 * (double)M * a.Cout * K, (int)M, a.Cout, K, 1, 1,
+                 2.0 * ((double)M * K + (double)M * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * K));
 }
 
 }  // namespace vk

@@ -341,30 +341,16 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvK p) {
 template <typename T, typename OutT, int BN, bool STEM>
 static int launch_t(const ConvK &k, hipStream_t stream) {
     constexpr int smem = 2 * (CONV_BM * 128 + BN * 128);
-    static bool attr_set = false;
-    if (!attr_set) {
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma_kernel<T, OutT, BN, STEM>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set = true;
-    }
+    VK_TRY(set_max_lds(conv_mfma_kernel<T, OutT, BN, STEM>, smem));
     dim3 grid(k.m_tiles * k.n_tiles), block(256);
-    KernelTimer *tm = g_timer;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (tm) {
-        e0 = tm->get();
-        e1 = tm->get();
-        VK_CHECK_HIP(hipEventRecord(e0, stream));
-    }
+    Timed t;
+    VK_TRY(t.begin(stream));
     hipLaunchKernelGGL((conv_mfma_kernel<T, OutT, BN, STEM>), grid, block, smem, stream, k);
     VK_CHECK_HIP(hipGetLastError());
-    if (tm) {
-        VK_CHECK_HIP(hipEventRecord(e1, stream));
-        int bucket = 3;
-        if (sizeof(T) == 2 && !STEM) bucket = sizeof(OutT) == 4 ? 2 : 1;
-        if (k.concurrent) bucket = 6;
-        tm->recs.push_back({bucket, k.alg_flops, e0, e1, k.M, k.cout8, k.cin_bytes / (int)sizeof(T), k.ktiles / k.kt_per_tap, k.stride, k.alg_bytes});
-    }
-    return VK_OK;
+    int bucket = 3;
+    if (sizeof(T) == 2 && !STEM) bucket = sizeof(OutT) == 4 ? 2 : 1;
+    if (k.concurrent) bucket = 6;
+    return t.end(stream, bucket, k.alg_flops, k.M, k.cout8, k.cin_bytes / (int)sizeof(T), k.ktiles / k.kt_per_tap, k.stride, k.alg_bytes);
 }
 
 int launch_conv(const ConvArgs &a, hipStream_t stream) {

@@ -444,43 +444,24 @@ bool conv256_eligible(const ConvArgs &a) {
     return M >= 4 * R_BM;
 }
 
+template <int DBG, bool DUAL = false>
+static int launch_256(const Conv256K &k, hipStream_t stream) {
+    VK_TRY(set_max_lds(conv_mfma256_kernel<DBG, DUAL>, R_SMEM));
+    hipLaunchKernelGGL((conv_mfma256_kernel<DBG, DUAL>), dim3(k.m_tiles * k.n_tiles), dim3(512), R_SMEM, stream, k);
+    VK_CHECK_HIP(hipGetLastError());
+    return VK_OK;
+}
+
 int launch_conv256(const ConvArgs &a, hipStream_t stream) {
-    static char *zero_page = nullptr;
-    if (!zero_page) {
-        VK_CHECK_HIP(hipMalloc((void **)&zero_page, 256));
-        VK_CHECK_HIP(hipMemset(zero_page, 0, 256));
-    }
-    static bool attr_set = false;
-    if (!attr_set) {
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma256_kernel<0>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, R_SMEM));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma256_kernel<1>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, R_SMEM));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma256_kernel<2>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, R_SMEM));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma256_kernel<3>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, R_SMEM));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma256_kernel<4>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, R_SMEM));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma256_kernel<8>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, R_SMEM));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma256_kernel<16>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, R_SMEM));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma256_kernel<32>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, R_SMEM));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma256_kernel<64>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, R_SMEM));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma256_kernel<96>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, R_SMEM));
-        attr_set = true;
-    }
+    DeviceState *ds = nullptr;
+    VK_TRY(device_state(&ds));
     Conv256K k;
     k.x = (const char *)a.x;
     k.w = (const char *)a.w;
     k.bias = a.bias;
     k.res = (const char *)a.res;
     k.y = (char *)a.y;
-    k.zero = zero_page;
+    k.zero = ds->zero_page;
     k.H = a.H;
     k.W = a.W;
     k.Ho = a.Ho;
@@ -504,52 +485,36 @@ int launch_conv256(const ConvArgs &a, hipStream_t stream) {
     k.relu = a.relu;
     k.m_tiles = ceil_div(k.M, R_BM);
     k.n_tiles = a.Cout / R_BN;
-    KernelTimer *tm = g_timer;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (tm) {
-        e0 = tm->get();
-        e1 = tm->get();
-        VK_CHECK_HIP(hipEventRecord(e0, stream));
-    }
+    Timed t;
+    VK_TRY(t.begin(stream));
     const int dbg = getenv("VK_CONV256_DBG") ? atoi(getenv("VK_CONV256_DBG")) : 0;   // re-read: lets one process A/B variants
-    const dim3 grid(k.m_tiles * k.n_tiles), block(512);
+    int st;
     if (a.x2) {
-        static bool dual_attr = false;
-        if (!dual_attr) {
-            VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma256_kernel<0, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, R_SMEM));
-            dual_attr = true;
-        }
-        hipLaunchKernelGGL((conv_mfma256_kernel<0, true>), grid, block, R_SMEM, stream, k);
+        st = launch_256<0, true>(k, stream);
     } else
 #ifdef VK_ABLATION      // timing-only ablation builds (WRONG results): tools/ builds only (make ABLATION=1)
     switch (dbg) {
-        case 1: hipLaunchKernelGGL(conv_mfma256_kernel<1>, grid, block, R_SMEM, stream, k); break;
-        case 2: hipLaunchKernelGGL(conv_mfma256_kernel<2>, grid, block, R_SMEM, stream, k); break;
-        case 3: hipLaunchKernelGGL(conv_mfma256_kernel<3>, grid, block, R_SMEM, stream, k); break;
-        case 4: hipLaunchKernelGGL(conv_mfma256_kernel<4>, grid, block, R_SMEM, stream, k); break;
-        case 8: hipLaunchKernelGGL(conv_mfma256_kernel<8>, grid, block, R_SMEM, stream, k); break;
-        case 16: hipLaunchKernelGGL(conv_mfma256_kernel<16>, grid, block, R_SMEM, stream, k); break;
-        case 32: hipLaunchKernelGGL(conv_mfma256_kernel<32>, grid, block, R_SMEM, stream, k); break;
-        case 64: hipLaunchKernelGGL(conv_mfma256_kernel<64>, grid, block, R_SMEM, stream, k); break;
-        case 96: hipLaunchKernelGGL(conv_mfma256_kernel<96>, grid, block, R_SMEM, stream, k); break;
-        default: hipLaunchKernelGGL(conv_mfma256_kernel<0>, grid, block, R_SMEM, stream, k);
+        case 1: st = launch_256<1>(k, stream); break;
+        case 2: st = launch_256<2>(k, stream); break;
+        case 3: st = launch_256<3>(k, stream); break;
+        case 4: st = launch_256<4>(k, stream); break;
+        case 8: st = launch_256<8>(k, stream); break;
+        case 16: st = launch_256<16>(k, stream); break;
+        case 32: st = launch_256<32>(k, stream); break;
+        case 64: st = launch_256<64>(k, stream); break;
+        case 96: st = launch_256<96>(k, stream); break;
+        default: st = launch_256<0>(k, stream);
     }
 #else
     {
         (void)dbg;
-        hipLaunchKernelGGL(conv_mfma256_kernel<0>, grid, block, R_SMEM, stream, k);
+        st = launch_256<0>(k, stream);
     }
 #endif
-    VK_CHECK_HIP(hipGetLastError());
-    if (tm) {
-        VK_CHECK_HIP(hipEventRecord(e1, stream));
-        const int K = a.kh * a.kw * a.Cin + (a.x2 ? a.Cin2 : 0);
-        tm->recs.push_back({a.concurrent ? 6 : (a.x2 ? 9 : 0), 2.0 * (double)k.M * a.Cout * K, e0, e1, k.M, a.Cout, a.x2 ? K : a.Cin, a.kh * a.kw, a.stride,
-                            2.0 * ((double)a.N * a.H * a.W * (a.Cin + (a.x2 ? a.Cin2 : 0)) + (double)k.M * a.Cout * (a.res ? 2 : 1) +
-                                   (double)a.Cout * K)});
-    }
-    return VK_OK;
+    VK_TRY(st);
+    const int K = a.kh * a.kw * a.Cin + (a.x2 ? a.Cin2 : 0);
+    return t.end(stream, a.concurrent ? 6 : (a.x2 ? 9 : 0), 2.0 * (double)k.M * a.Cout * K, k.M, a.Cout, a.x2 ? K : a.Cin, a.kh * a.kw, a.stride,
+                 2.0 * ((double)a.N * a.H * a.W * (a.Cin + (a.x2 ? a.Cin2 : 0)) + (double)k.M * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * K));
 }
 
 }  // namespace vk

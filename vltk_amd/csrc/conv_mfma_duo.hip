@@ -576,25 +576,14 @@ bool conv_duo_eligible(const ConvArgs &a) {
     return a.Cin <= 512 || M < 400000;
 }
 
+template <typename ET, bool STAMP, int DBG = 0, bool GELU = false, int TAG = 0>
+static int launch_duo(const DuoK &k, dim3 grid, hipStream_t stream) {
+    VK_TRY(set_max_lds(conv_duo_kernel<ET, STAMP, 3, DBG, GELU, TAG>, d_smem(3)));
+    hipLaunchKernelGGL((conv_duo_kernel<ET, STAMP, 3, DBG, GELU, TAG>), grid, dim3(256), d_smem(3), stream, k);
+    return VK_OK;
+}
+
 int launch_conv_duo(const ConvArgs &a, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_duo_kernel<_Float16, false, 3>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, d_smem(3)));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_duo_kernel<__bf16, false, 3>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, d_smem(3)));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_duo_kernel<_Float16, false, 3, 0, false, 1>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, d_smem(3)));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_duo_kernel<__bf16, false, 3, 0, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, d_smem(3)));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_duo_kernel<_Float16, true, 3>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, d_smem(3)));
-#define VKD_DBG_ATTR(D) VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_duo_kernel<_Float16, true, 3, D>), \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, d_smem(3)))
-        VKD_DBG_ATTR(1); VKD_DBG_ATTR(3); VKD_DBG_ATTR(4); VKD_DBG_ATTR(7); VKD_DBG_ATTR(8); VKD_DBG_ATTR(11); VKD_DBG_ATTR(12);
-#undef VKD_DBG_ATTR
-        attr_set = true;
-    }
     DuoK k;
     k.x = (const char *)a.x;
     k.w = (const char *)a.w;
@@ -624,27 +613,24 @@ int launch_conv_duo(const ConvArgs &a, hipStream_t stream) {
     k.relu = a.relu;
     k.m_tiles = ceil_div(k.M, D_BM);
     k.n_tiles = a.Cout / D_BN;
-    KernelTimer *tm = g_timer;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (tm) {
-        e0 = tm->get();
-        e1 = tm->get();
-        VK_CHECK_HIP(hipEventRecord(e0, stream));
-    }
-    const dim3 grid(k.m_tiles * k.n_tiles), block(256);
+    Timed t;
+    VK_TRY(t.begin(stream));
+    const dim3 grid(k.m_tiles * k.n_tiles);
     k.pool_part = (int *)a.pool_part;
     k.stamps = nullptr;
+    int st;
 #ifdef VK_ABLATION      // stamp / timing-only builds: tools/ builds only (make ABLATION=1)
     if (const char *sf = getenv("VK_DUO_STAMPS")) {      // diagnostic: one launch, phase stamps appended to the file
         const size_t nb = (size_t)grid.x * 12 * sizeof(unsigned long);
         VK_CHECK_HIP(hipMalloc((void **)&k.stamps, nb));
         const int dbg = getenv("VK_DUO_DBG") ? atoi(getenv("VK_DUO_DBG")) : 0;
         if (false) {}
-#define VKD_DBG_RUN(D) else if (dbg == D) hipLaunchKernelGGL((conv_duo_kernel<_Float16, true, 3, D>), grid, block, d_smem(3), stream, k)
+#define VKD_DBG_RUN(D) else if (dbg == D) st = launch_duo<_Float16, true, D>(k, grid, stream)
         VKD_DBG_RUN(1); VKD_DBG_RUN(3); VKD_DBG_RUN(4); VKD_DBG_RUN(7); VKD_DBG_RUN(8); VKD_DBG_RUN(11); VKD_DBG_RUN(12);
 #undef VKD_DBG_RUN
         else
-            hipLaunchKernelGGL((conv_duo_kernel<_Float16, true, 3>), grid, block, d_smem(3), stream, k);
+            st = launch_duo<_Float16, true>(k, grid, stream);
+        VK_TRY(st);
         VK_CHECK_HIP(hipStreamSynchronize(stream));
         std::vector<unsigned long> h((size_t)grid.x * 12);
         VK_CHECK_HIP(hipMemcpy(h.data(), k.stamps, nb, hipMemcpyDeviceToHost));
@@ -661,21 +647,18 @@ int launch_conv_duo(const ConvArgs &a, hipStream_t stream) {
     } else
 #endif
         if (a.dt == VK_BF16 && a.relu == 2)
-            hipLaunchKernelGGL((conv_duo_kernel<__bf16, false, 3, 0, true>), grid, block, d_smem(3), stream, k);
+            st = launch_duo<__bf16, false, 0, true>(k, grid, stream);
         else if (a.dt == VK_BF16)
-            hipLaunchKernelGGL((conv_duo_kernel<__bf16, false, 3>), grid, block, d_smem(3), stream, k);
+            st = launch_duo<__bf16, false>(k, grid, stream);
         else if (a.concurrent)
-            hipLaunchKernelGGL((conv_duo_kernel<_Float16, false, 3, 0, false, 1>), grid, block, d_smem(3), stream, k);
+            st = launch_duo<_Float16, false, 0, false, 1>(k, grid, stream);
         else
-            hipLaunchKernelGGL((conv_duo_kernel<_Float16, false, 3>), grid, block, d_smem(3), stream, k);
+            st = launch_duo<_Float16, false>(k, grid, stream);
+    VK_TRY(st);
     VK_CHECK_HIP(hipGetLastError());
-    if (tm) {
-        VK_CHECK_HIP(hipEventRecord(e1, stream));
-        const int K = a.Cin + (a.x2 ? a.Cin2 : 0);
-        tm->recs.push_back({a.concurrent ? 6 : 5, 2.0 * (double)k.M * a.Cout * K, e0, e1, k.M, a.Cout, K, 1, a.stride,
-                            2.0 * ((double)a.N * a.H * a.W * K + (double)k.M * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * K)});
-    }
-    return VK_OK;
+    const int K = a.Cin + (a.x2 ? a.Cin2 : 0);
+    return t.end(stream, a.concurrent ? 6 : 5, 2.0 * (double)k.M * a.Cout * K, k.M, a.Cout, K, 1, a.stride,
+                 2.0 * ((double)a.N * a.H * a.W * K + (double)k.M * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * K));
 }
 
 }  // namespace vk

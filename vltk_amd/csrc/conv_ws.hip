@@ -464,11 +464,7 @@ bool conv_ws_eligible(const ConvArgs &a) {
 template <int KC, int NW = 8, int DBG = 0, bool POOL = false, bool DUAL = false, bool STRIDED = false>
 static int launch_ws(const WsK &k, hipStream_t stream) {
     constexpr int smem = 6 * WS_BM * 256 + 4 * WS_BM * 128 + 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_ws_kernel<KC, NW, DBG, POOL, DUAL, STRIDED>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set = true;
-    }
+    VK_TRY(set_max_lds(conv_ws_kernel<KC, NW, DBG, POOL, DUAL, STRIDED>, smem));
     hipLaunchKernelGGL((conv_ws_kernel<KC, NW, DBG, POOL, DUAL, STRIDED>), dim3(256), dim3(NW * 64), smem, stream, k);
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
@@ -498,23 +494,14 @@ int launch_conv_ws(const ConvArgs &a, hipStream_t stream) {
     k.HoWo = a.Ho * a.Wo;
     k.stride = a.stride;
 
-    KernelTimer *tm = g_timer;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (tm) {
-        e0 = tm->get();
-        e1 = tm->get();
-        VK_CHECK_HIP(hipEventRecord(e0, stream));
-    }
+    Timed t;
+    VK_TRY(t.begin(stream));
     int st;
     if (a.pool_part) {                                   // fused mean: zero the per-image sums, then the POOL build
         VK_CHECK_HIP(hipMemsetAsync(k.pool, 0, (size_t)(M / k.HW) * a.Cout * sizeof(double), stream));
         VK_TRY((launch_ws<16, 8, 0, true>(k, stream)));
-        if (tm) {
-            VK_CHECK_HIP(hipEventRecord(e1, stream));
-            tm->recs.push_back({a.concurrent ? 6 : 8, 2.0 * (double)M * a.Cout * a.Cin, e0, e1, (int)M, a.Cout, a.Cin, 1, 1,
-                                2.0 * ((double)M * a.Cin + (double)M * a.Cout * (a.res ? 1 : 0) + (double)a.Cout * a.Cin)});
-        }
-        return VK_OK;
+        return t.end(stream, a.concurrent ? 6 : 8, 2.0 * (double)M * a.Cout * a.Cin, (int)M, a.Cout, a.Cin, 1, 1,
+                     2.0 * ((double)M * a.Cin + (double)M * a.Cout * (a.res ? 1 : 0) + (double)a.Cout * a.Cin));
     }
     const char *nwv = getenv("VK_WS_WAVES");             // "4" / "8": A/B switch, re-read per call
     const int nw = nwv ? atoi(nwv) : 8;
@@ -576,13 +563,9 @@ int launch_conv_ws(const ConvArgs &a, hipStream_t stream) {
 #undef VKW_DBG_CASE
     }
     VK_TRY(st);
-    if (tm) {
-        VK_CHECK_HIP(hipEventRecord(e1, stream));
-        const int K = a.Cin + (a.x2 ? a.Cin2 : 0);
-        tm->recs.push_back({a.concurrent ? 6 : 8, 2.0 * (double)M * a.Cout * K, e0, e1, (int)M, a.Cout, K, 1, 1,
-                            2.0 * ((double)M * K + (double)M * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * K)});
-    }
-    return VK_OK;
+    const int K = a.Cin + (a.x2 ? a.Cin2 : 0);
+    return t.end(stream, a.concurrent ? 6 : 8, 2.0 * (double)M * a.Cout * K, (int)M, a.Cout, K, 1, 1,
+                 2.0 * ((double)M * K + (double)M * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * K));
 }
 
 }  // namespace vk

@@ -443,12 +443,7 @@ int vk_attention(const void *q, int ldq, const void *k, int ldk, const void *v, 
     const dim3 grid(B * heads), block(256);
 #define VK_ATT(T)                                                                                                        \
     do {                                                                                                                 \
-        static bool attr = false;                                                                                        \
-        if (!attr) {                                                                                                     \
-            VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&attention_kernel<T>),                        \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                   \
-            attr = true;                                                                                                 \
-        }                                                                                                                \
+        VK_TRY(set_max_lds(attention_kernel<T>, 160 * 1024));                                                            \
         hipLaunchKernelGGL(attention_kernel<T>, grid, block, smem, s, (const T *)q, ldq, (const T *)k, ldk, (const T *)v, ldv, mask, \
                            (T *)out, ldo, heads, Lq, Lk, d, scale);                                                     \
     } while (0)

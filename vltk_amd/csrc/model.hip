@@ -14,6 +14,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <map>
+#include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -60,6 +62,66 @@ void KernelTimer::collect() {
 }
 KernelTimer::~KernelTimer() {
     for (auto e : all) (void)hipEventDestroy(e);
+}
+
+int Timed::begin(hipStream_t stream) {
+    if (!tm) return VK_OK;
+    e0 = tm->get();
+    e1 = tm->get();
+    VK_CHECK_HIP(hipEventRecord(e0, stream));
+    return VK_OK;
+}
+int Timed::end(hipStream_t stream, int bucket, double flops, int M, int cout, int cin, int k, int stride, double bytes) {
+    if (!tm) return VK_OK;
+    VK_CHECK_HIP(hipEventRecord(e1, stream));
+    tm->recs.push_back({bucket, flops, e0, e1, M, cout, cin, k, stride, bytes});
+    return VK_OK;
+}
+
+// Launcher state per device: published once fully built; the lock only serialises the first launch on each device.
+static std::atomic<DeviceState *> g_devices[VK_MAX_DEVICES];
+static std::mutex g_devices_mu;
+
+int device_state(DeviceState **out) {
+    int dev = 0;
+    VK_CHECK_HIP(hipGetDevice(&dev));
+    VK_REQUIRE(dev >= 0 && dev < VK_MAX_DEVICES, VK_EINVAL, "device %d beyond VK_MAX_DEVICES", dev);
+    DeviceState *d = g_devices[dev].load(std::memory_order_acquire);
+    if (!d) {
+        std::lock_guard<std::mutex> lock(g_devices_mu);
+        d = g_devices[dev].load(std::memory_order_relaxed);
+        if (!d) {
+            hipDeviceProp_t prop;
+            VK_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
+            // one allocation: [zero page 256 B][tile ring 256 words][bneck scratch]; the first two start zeroed, and the
+            // scratch comes last so that nothing it receives can land in them
+            char *p = nullptr;
+            VK_CHECK_HIP(hipMalloc((void **)&p, 256 + 256 * sizeof(unsigned) + BN_TRASH_BYTES));
+            VK_CHECK_HIP(hipMemset(p, 0, 256 + 256 * sizeof(unsigned)));     // (synchronous: done before any launch can read it)
+            d = new DeviceState;
+            d->n_cu = prop.multiProcessorCount;
+            d->zero_page = p;
+            d->tile_ring = (unsigned *)(p + 256);
+            d->bn_trash = p + 256 + 256 * sizeof(unsigned);
+            d->tile_next = 0;
+            g_devices[dev].store(d, std::memory_order_release);
+        }
+    }
+    *out = d;
+    return VK_OK;
+}
+
+static std::set<std::pair<int, const void *>> g_lds_set;     // (device, kernel) pairs whose LDS limit is raised
+static std::mutex g_lds_mu;
+
+int set_max_lds(const void *kernel, size_t bytes) {
+    int dev = 0;
+    VK_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_lds_mu);
+    if (g_lds_set.count({dev, kernel})) return VK_OK;
+    VK_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    g_lds_set.insert({dev, kernel});
+    return VK_OK;
 }
 
 static thread_local char g_err[1024] = "";

@@ -699,12 +699,7 @@ int vk_rpn_proposals(const float *logits, int ld_logits, const float *deltas, in
     if (const char *e = getenv("VK_RPN_STOP")) cfg.stop = atoi(e);
 #endif
     const size_t smem = (size_t)sortn * 8 + 2048;
-    static bool attr_set = false;
-    if (!attr_set) {
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rpn_select_decode_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, RPN_MAX_PRE * 8 + 2048));
-        attr_set = true;
-    }
+    VK_TRY(set_max_lds(rpn_select_decode_kernel, RPN_MAX_PRE * 8 + 2048));
     hipLaunchKernelGGL(rpn_select_decode_kernel, dim3(N), dim3(RPN_THREADS), smem, s, logits, ld_logits, deltas, ld_deltas,
                        Hf, Wf, A, cell_anchors, image_hw, cfg, pre_topk, sortn, w.cand_boxes, w.cand_logit, w.cand_valid,
                        w.cand_count, nonfinite_flag);
@@ -772,16 +767,6 @@ int vk_rpn_proposals_multilevel(const float *const *logits, const int32_t *ld_lo
     MlWs w = carve_ml_ws(workspace, N, levels, pre_topk, post_topk);
     VK_REQUIRE(workspace && workspace_bytes >= w.total, VK_EINVAL, "rpn_ml: workspace too small (%zu < %zu)", workspace_bytes, w.total);
     hipStream_t s = (hipStream_t)stream;
-    static bool attr_set = false;
-    if (!attr_set) {
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rpn_select_decode_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, RPN_MAX_PRE * 8 + 2048));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rpn_select_decode_levels_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, RPN_MAX_PRE * 8 + 2048));
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rpn_merge_levels_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, RPN_MAX_PRE * 8 + 256));
-        attr_set = true;
-    }
     LevelCands lc;
     memset(&lc, 0, sizeof(lc));
     lc.levels = levels;
@@ -823,10 +808,12 @@ int vk_rpn_proposals_multilevel(const float *const *logits, const int32_t *ld_lo
     cfg.stride = 0;                                  // per level, from sl.stride
     cfg.offset = offset;
     cfg.stop = 0;
+    VK_TRY(set_max_lds(rpn_select_decode_levels_kernel, RPN_MAX_PRE * 8 + 2048));
     hipLaunchKernelGGL(rpn_select_decode_levels_kernel, dim3(N, levels), dim3(RPN_THREADS), (size_t)max_sortn * 8 + 2048, s, sl, A, image_hw, cfg,
                        pre_topk, nonfinite_flag);
     VK_CHECK_HIP(hipGetLastError());
     const int cap = levels * pre_topk, sortn = next_pow2(cap), nwords = ceil_div(cap, 64);
+    VK_TRY(set_max_lds(rpn_merge_levels_kernel, RPN_MAX_PRE * 8 + 256));
     hipLaunchKernelGGL(rpn_merge_levels_kernel, dim3(N), dim3(RPN_THREADS), (size_t)sortn * 8 + 256, s, lc, cap, sortn, w.m_boxes, w.m_shift,
                        w.m_logit, w.m_count);
     VK_CHECK_HIP(hipGetLastError());
@@ -861,12 +848,7 @@ int vk_nms(const float *boxes, const float *scores, int n, double thresh, int64_
     p += 256;
     RpnWs w = carve_rpn_ws(p, 1, n, n);
     const int sortn = next_pow2(n);
-    static bool attr_set = false;
-    if (!attr_set) {
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sort_scores_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, RPN_MAX_PRE * 8));
-        attr_set = true;
-    }
+    VK_TRY(set_max_lds(sort_scores_kernel, RPN_MAX_PRE * 8));
     hipLaunchKernelGGL(sort_scores_kernel, dim3(1), dim3(RPN_THREADS), (size_t)sortn * 8, s, scores, n, sortn, boxes,
                        sorted_boxes, order, cnt);
     VK_CHECK_HIP(hipGetLastError());

@@ -162,17 +162,9 @@ bool stem_pool_eligible(int cout, vk_dtype dt) {
 // x: stem_pack's bordered image [N, Hp, Wp, 4]; y: [N, H2, W2, 64]
 int launch_stem_pool(const void *x, int N, int Hp, int Wp, int H1, int W1, const void *w, const float *bias, int caffe, void *y,
                      hipStream_t stream) {
-    static bool attr_set = false;
-    static int n_cu = 0;
-    if (!attr_set) {
-        VK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&stem_pool_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SP_SMEM));
-        int dev = 0;
-        hipDeviceProp_t prop;
-        VK_CHECK_HIP(hipGetDevice(&dev));
-        VK_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        attr_set = true;
-    }
+    DeviceState *ds = nullptr;
+    VK_TRY(device_state(&ds));
+    VK_TRY(set_max_lds(stem_pool_kernel, SP_SMEM));
     StemPoolK k;
     k.x = (const char *)x;
     k.w = (const char *)w;
@@ -198,23 +190,14 @@ int launch_stem_pool(const void *x, int N, int Hp, int Wp, int H1, int W1, const
     const long nt = (long)N * k.tiles_x * k.tiles_y;
     VK_REQUIRE(nt > 0 && nt < (1L << 31), VK_EINVAL, "stem_pool: %ld tiles", nt);
     k.ntiles = (int)nt;
-    const int grid = (int)std::min<long>(nt, (long)n_cu * 3);
-    KernelTimer *tm = g_timer;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (tm) {
-        e0 = tm->get();
-        e1 = tm->get();
-        VK_CHECK_HIP(hipEventRecord(e0, stream));
-    }
+    const int grid = (int)std::min<long>(nt, (long)ds->n_cu * 3);
+    Timed t;
+    VK_TRY(t.begin(stream));
     hipLaunchKernelGGL(stem_pool_kernel, dim3(grid), dim3(256), SP_SMEM, stream, k);
     VK_CHECK_HIP(hipGetLastError());
-    if (tm) {
-        VK_CHECK_HIP(hipEventRecord(e1, stream));
-        const long M = (long)N * H1 * W1;
-        tm->recs.push_back({3, 2.0 * (double)M * 64 * 147, e0, e1, (int)std::min<long>(M, 1L << 30), 64, 4, 7, 2,
-                            (double)N * Hp * Wp * 8 + (double)N * k.H2 * k.W2 * 128 + 64.0 * 512});
-    }
-    return VK_OK;
+    const long M = (long)N * H1 * W1;
+    return t.end(stream, 3, 2.0 * (double)M * 64 * 147, (int)std::min<long>(M, 1L << 30), 64, 4, 7, 2,
+                 (double)N * Hp * Wp * 8 + (double)N * k.H2 * k.W2 * 128 + 64.0 * 512);
 }
 
 }  // namespace vk

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -48,7 +49,7 @@ static inline size_t dtype_size(vk_dtype dt) {
     return 0;
 }
 
-constexpr int VK_MAX_DEVICES = 64;      // per-device statics of the launchers (zero pages, function attributes)
+constexpr int VK_MAX_DEVICES = 64;      // slots of per-device launcher state (DeviceState)
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -123,6 +124,32 @@ struct KernelTimer {
     ~KernelTimer();
 };
 extern thread_local KernelTimer *g_timer;
+
+// One timed launch: begin() before it, end() after it with the launch's timer bucket and algorithmic counts.  Both do nothing
+// when g_timer is null.
+struct Timed {
+    KernelTimer *tm = g_timer;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int begin(hipStream_t stream);
+    int end(hipStream_t stream, int bucket, double flops, int M, int cout, int cin, int k, int stride, double bytes);
+};
+
+// ---- launcher state, per device (model.hip) ----
+// A process may hold handles on several devices: everything a launcher keeps between launches lives here, one record per
+// device, created on the first launch on that device (under a lock) and kept for the life of the process.
+constexpr int BN_TRASH_BYTES = 1 << 16;
+struct DeviceState {
+    int n_cu;                         // hipDeviceProp_t::multiProcessorCount, as reported (launchers do their own rounding)
+    const char *zero_page;            // 256 zero bytes, never written (conv3x3_blk, conv_mfma256)
+    char *bn_trash;                   // BN_TRASH_BYTES of write-only scratch (bneck_fused stores into it)
+    unsigned *tile_ring;              // 256 words, zeroed once (acquire_tile_counter)
+    std::atomic<unsigned> tile_next;  // the ring's cursor
+};
+int device_state(DeviceState **out);  // the current HIP device's record
+// hipFuncAttributeMaxDynamicSharedMemorySize, once per (device, kernel); later calls are a lookup
+int set_max_lds(const void *kernel, size_t bytes);
+template <typename... A>
+static inline int set_max_lds(void (*kernel)(A...), size_t bytes) { return set_max_lds(reinterpret_cast<const void *>(kernel), bytes); }
 
 // ---- pool.hip ----
 int launch_stem_pack(const float *x, void *y, int N, int H, int W, int Hp, int Wp, vk_dtype dt, hipStream_t s, int32_t *nonfinite = nullptr);
