@@ -97,6 +97,23 @@ typedef struct vk_outputs {
     float   *roi_features;     /* [N, D, 2048]  */
 } vk_outputs;
 
+/* ignorey: horizontal bands whose RPN proposals are removed or trimmed (find_top_rpn_proposals frcnn.py:328-366),
+ * applied per image after the decode and before the clip.  `bands` holds [N][max_per_image][2] values (y0, y1) of
+ * double (f64 = 1) or float (f64 = 0), ALREADY divided by scales_yx[n][1] (the reference's quirk: the x scale, on y);
+ * image n uses its first counts[n] rows, in order.  0 <= counts[n] <= max_per_image <= VK_MAX_IGNOREY.  A NULL
+ * vk_ignorey, or max_per_image == 0, means no bands: exactly the entry point without _ignorey.  For each band, with
+ * g0, g1 the band and (y0, y1) a box's current rows, compared in the bands' dtype: g1 <= y1 && g0 >= y0 removes the
+ * box; otherwise, unless y0 > g1 && y1 > g0, |g0 - y0| < |g1 - y1| sets y0 = trunc(g1) and |g1 - y1| < |g0 - y0|
+ * sets y1 = trunc(g0).  A removed box keeps its candidate slot, flagged like a size-filtered one, and is not checked
+ * for non-finite values. */
+#define VK_MAX_IGNOREY 64
+typedef struct vk_ignorey {
+    const void    *bands;
+    const int32_t *counts;
+    int32_t        max_per_image;
+    int32_t        f64;
+} vk_ignorey;
+
 typedef struct vk_handle vk_handle;
 
 const char *vk_last_error(void);
@@ -149,6 +166,13 @@ int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
                      const int32_t *image_hw, const float *scales_yx,
                      const vk_roi_params *rp, const vk_outputs *out_dev, void *stream, int64_t *ticket);
 int vk_forward_end(vk_handle *h, int64_t ticket);
+/* vk_forward_begin with ignorey bands (see vk_ignorey; NULL = vk_forward_begin).  bands and counts are HOST arrays,
+ * copied into the ticket's slot before the call returns, like image_hw; every band must be finite with |value| < 2^31.
+ * The reference applies bands only when scales_yx is given (frcnn.py:328): with scales_yx NULL the bands are ignored. */
+int vk_forward_begin_ignorey(vk_handle *h, const float *images_dev, int N, int H, int W,
+                             const int32_t *image_hw, const float *scales_yx,
+                             const vk_roi_params *rp, const vk_outputs *out_dev, void *stream, int64_t *ticket,
+                             const vk_ignorey *ignorey);
 
 /* Region features for caller-supplied boxes (the reference's `proposals=` slot, frcnn.py:1924-1964, which is broken
  * upstream: `proposal_boxes` is never bound when proposals are given).  Detection, but with the RPN replaced by the
@@ -308,6 +332,22 @@ int vk_relu_copy(const void *x, void *y, long n, vk_dtype dt, void *stream);
  * anchors / stride, clip, size filter; concat level-major; batched NMS (torchvision form: boxes shifted by
  * level * (max coordinate + 1)); first post_nms_topk.  levels * pre_nms_topk <= 8192.  Outputs as vk_rpn_proposals. */
 size_t vk_rpn_multilevel_workspace_bytes(int N, int levels, int pre_topk, int post_topk);
+/* The two RPN entries with ignorey bands (see vk_ignorey; NULL = the entry without _ignorey): bands and counts are
+ * DEVICE arrays here, read by the decode kernel; counts[n] above max_per_image is taken as max_per_image.  The
+ * multi-level form gives every level of image n the same bands. */
+int vk_rpn_proposals_multilevel_ignorey(const float *const *logits, const int32_t *ld_logits, const float *const *deltas,
+                                        const int32_t *ld_deltas, int levels, int N, const int32_t *Hs, const int32_t *Ws,
+                                        int A, const float *const *cell_anchors, const int32_t *strides, float offset,
+                                        const int32_t *image_hw, const float *bbox_weights4_host, float min_size,
+                                        double nms_thresh, int pre_topk, int post_topk, float *out_boxes,
+                                        float *out_logits, int32_t *out_counts, int32_t *nonfinite_flag, void *workspace,
+                                        size_t workspace_bytes, void *stream, const vk_ignorey *ignorey);
+int vk_rpn_proposals_ignorey(const float *logits, int ld_logits, const float *deltas, int ld_deltas,
+                             int N, int Hf, int Wf, int A, const float *cell_anchors, int stride, float offset,
+                             const int32_t *image_hw, const float *bbox_weights4_host, float min_size,
+                             double nms_thresh, int pre_topk, int post_topk,
+                             float *out_boxes, float *out_logits, int32_t *out_counts, int32_t *nonfinite_flag,
+                             void *workspace, size_t workspace_bytes, void *stream, const vk_ignorey *ignorey);
 int vk_rpn_proposals_multilevel(const float *const *logits, const int32_t *ld_logits, const float *const *deltas,
                                 const int32_t *ld_deltas, int levels, int N, const int32_t *Hs, const int32_t *Ws, int A,
                                 const float *const *cell_anchors, const int32_t *strides, float offset,

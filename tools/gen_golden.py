@@ -286,6 +286,135 @@ def e2e(ref, name, n, h, w, shapes, post_topk, det, seed, depth=101):
           "min cls margin %.2e" % out["cls_margin"].min())
 
 
+# ---------------------------------------------------------------------------
+def band_restatement(boxes, bands):
+    """find_top_rpn_proposals frcnn.py:328-366 for one image, in slots: boxes [K, 4] f32 (pre-band top-k), bands [J, 2]
+    already divided by scales_yx[n, 1] (their dtype is the comparison dtype) -> (boxes with the survivors trimmed, keep
+    mask, per-branch counts {drop, top, bottom}).  The tests' copy is tests/ignorey_util.py."""
+    b = boxes.clone()
+    keep = torch.ones(b.shape[0], dtype=torch.bool)
+    cnt = {"drop": 0, "top": 0, "bottom": 0}
+    for g in bands:
+        y0, y1 = b[:, 1].to(g.dtype), b[:, 3].to(g.dtype)
+        drop = keep & (g[1] <= y1) & (g[0] >= y0)
+        above = (y0 > g[1]) & (y1 > g[0])
+        to_clip = keep & ~drop & ~above
+        top = to_clip & ((g[1] - y1).abs() < (g[0] - y0).abs())
+        bottom = to_clip & ((g[0] - y0).abs() < (g[1] - y1).abs())
+        b[bottom, 1] = int(g[1])
+        b[top, 3] = int(g[0])
+        keep &= ~drop
+        cnt["drop"] += int(drop.sum())
+        cnt["top"] += int(top.sum())
+        cnt["bottom"] += int(bottom.sum())
+    return b, keep, cnt
+
+
+def e2e_ignorey(ref, n=2, h=160, w=224, shapes=((160, 224), (144, 200)), post_topk=30, det=12, seed=1234):
+    """tests/golden/e2e_ignorey.npz: FRCNN.forward(..., scales_yx=, ignorey=) of the reference on e2e_r101_small's setup.
+    Per case and image: the pre-band top-k candidates (boxes, logits), the post-band boxes (survivors, trimmed, before
+    _clip_box) and keep mask, the proposals and the final outputs."""
+    import inspect
+    cfg = Config(vg_c4_config_dict(depth=101, post_nms_topk=post_topk, detections=det))
+    sd = make_state_dict(cfg, seed=seed)
+    net = ref.FRCNN(cfg).eval()
+    net.load_state_dict(to_torch_sd(sd), strict=True)
+    images = torch.from_numpy(synthetic_images(n, h, w, seed=seed))
+    for i, (hh, ww) in enumerate(shapes):
+        images[i, :, hh:, :] = 0
+        images[i, :, :, ww:] = 0
+    scales = torch.tensor([[1.25, 1.5], [2.0, 1.75]], dtype=torch.float32)      # x != y: pins the x-scale quirk
+
+    clip0 = ref._clip_box
+    seen = []
+
+    def clip_spy(t, size):
+        fr = inspect.currentframe().f_back
+        if fr.f_code.co_name == "find_top_rpn_proposals":
+            loc = fr.f_locals
+            k = loc["n"]
+            seen.append({"pre_boxes": loc["topk_proposals"][k].clone(), "pre_logits": loc["topk_scores"][k].clone(),
+                         "post_boxes": t.clone(), "post_logits": loc["scores_per_img"].clone()})
+        return clip0(t, size)
+
+    def run(idx, ignorey):
+        stages, seen[:] = {}, []
+        hooks = [net.proposal_generator.rpn_head.register_forward_hook(lambda m, i, o: stages.update(obj=o[0][0])),
+                 net.proposal_generator.register_forward_hook(lambda m, i, o: stages.update(pboxes=o[0], plogits=o[1]))]
+        ref._clip_box = clip_spy
+        try:
+            with torch.no_grad():
+                o = net(images[idx], torch.tensor(shapes)[idx], scales_yx=scales[idx], ignorey=ignorey)
+        finally:
+            ref._clip_box = clip0
+            for hk in hooks:
+                hk.remove()
+        tie_free(np_(stages["obj"]), "ignorey rpn logits")
+        return o, stages, [dict(d) for d in seen]
+
+    out = {"images_seed": np.asarray(seed), "shapes": np.asarray(shapes), "nhw": np.asarray([n, h, w]),
+           "post_topk": np.asarray(post_topk), "det": np.asarray(det), "depth": np.asarray(101),
+           "weights_seed": np.asarray(seed), "scales_yx": np_(scales)}
+    # the candidates the cases are drawn from (one band far above every box: the reference then filters a copy, so
+    # topk_proposals stays the pre-band top-k the spy reads)
+    _, st0, seen0 = run([0, 1], torch.zeros((2, 1, 2)) + torch.tensor([-3e4, -2.9e4]))
+    base = {}
+    for idx in ([0], [0, 1]):
+        _, stb, _ = run(idx, None)
+        base[tuple(idx)] = stb
+    pre0 = seen0[0]["pre_boxes"]
+    sx0 = float(scales[0, 1])
+    p0 = st0["pboxes"][0]          # post-NMS proposals of image 0 (no band changed them: the band above lies far outside)
+    # processed-pixel bands on image 0: trim the bottom of proposal 1, the top of proposal 2, then drop proposal 0
+    a, b_, c = p0[1], p0[2], p0[0]
+    bands_px = [[float(a[1]) - 2.3, float(a[1]) + 4.6], [float(b_[3]) - 4.4, float(b_[3]) + 2.7],
+                [float(c[1]) + 3.3, float(c[3]) - 3.3]]
+    cases = {
+        "trim_drop": ([0], torch.tensor([bands_px], dtype=torch.float32) * sx0),
+        "outside": ([0], torch.tensor([[[-2.0e4, -1.0e4]]], dtype=torch.float32) * sx0),
+        "f64": ([0], torch.tensor([bands_px], dtype=torch.float64) * sx0 + 1e-9),
+    }
+    # N = 2, image 0 only trims (a band below every candidate: each one's y1 -> int(g0), then the clip); image 1 drops too
+    for v in (1.0e3, 5.0e3, 2.0e4, 1.0e5):
+        if float(pre0[:, 3].max()) < v:
+            break
+    p1 = st0["pboxes"][1]
+    sx1 = float(scales[1, 1])
+    cases["batched"] = ([0, 1], torch.tensor([[[v * sx0, (v + 1) * sx0]], [[(float(p1[0][1]) + 2.2) * sx1, (float(p1[0][3]) - 2.2) * sx1]]],
+                                            dtype=torch.float32))
+    names = []
+    for name, (idx, ig) in cases.items():
+        o, st, sn = run(idx, ig)
+        assert len(sn) == len(idx), (name, len(sn))
+        names.append(name)
+        out[f"{name}_images"] = np.asarray(idx)
+        out[f"{name}_ignorey"] = np_(ig)
+        for j, i in enumerate(idx):
+            d = sn[j]
+            g = ig[j] * 1 / scales[i, 1]                                       # frcnn.py:331
+            rb, keep, cnt = band_restatement(d["pre_boxes"], g)
+            assert torch.equal(rb[keep], d["post_boxes"]) and torch.equal(d["pre_logits"][keep], d["post_logits"]), name
+            pb, pb0 = st["pboxes"][j], base[tuple(idx)]["pboxes"][j]
+            changed = pb.shape != pb0.shape or not torch.equal(pb, pb0)      # against the same run without bands
+            if name == "outside":
+                assert not changed and cnt["drop"] == 0, (name, cnt)
+            elif name == "batched":
+                assert changed and (j > 0 or (cnt["drop"] == 0 and cnt["top"] > 0)), (name, j, cnt)
+            else:
+                assert changed and all(c_ > 0 for c_ in cnt.values()), (name, j, cnt)
+            print(f"ignorey {name} image {i}: {cnt} survivors {int(keep.sum())}/{len(keep)} proposals {len(st['pboxes'][j])}"
+                  f" changed {changed}")
+            out[f"{name}_{j}_pre_boxes"], out[f"{name}_{j}_pre_logits"] = np_(d["pre_boxes"]), np_(d["pre_logits"])
+            out[f"{name}_{j}_post_boxes"], out[f"{name}_{j}_keep"] = np_(rb), np_(keep)
+            out[f"{name}_{j}_proposal_boxes"], out[f"{name}_{j}_proposal_logits"] = np_(st["pboxes"][j]), np_(st["plogits"][j])
+            for k in ("obj_ids", "obj_probs", "attr_ids", "attr_probs", "boxes", "roi_features"):
+                out[f"{name}_{j}_{k}"] = np_(o[k][j])
+        out[f"{name}_preds_per_image"] = np_(o["preds_per_image"])
+    out["cases"] = np.asarray(names)
+    np.savez_compressed(os.path.join(OUT, "e2e_ignorey.npz"), **out)
+    print("e2e_ignorey.npz:", names)
+
+
 VARIANTS = {
     # tag: config overrides (section, key, value) on the depth-50 build config
     "resnext50_8x8d": [("resnets", "num_groups", 8), ("resnets", "width_per_group", 8)],
@@ -436,6 +565,12 @@ def fpn_ops(ref):
 if __name__ == "__main__" and "--fpn" in sys.argv:
     os.makedirs(OUT, exist_ok=True)
     fpn_ops(load_reference())
+    sys.exit(0)
+
+if __name__ == "__main__" and "--ignorey" in sys.argv:
+    os.makedirs(OUT, exist_ok=True)
+    torch.set_num_threads(8)
+    e2e_ignorey(load_reference())
     sys.exit(0)
 
 if __name__ == "__main__" and "--x152" in sys.argv:

@@ -21,6 +21,7 @@ VK_F32, VK_F16, VK_I64, VK_I32, VK_BF16 = 0, 1, 2, 3, 4
 VK_ACT_NONE, VK_ACT_RELU, VK_ACT_GELU, VK_ACT_TANH = 0, 1, 2, 3
 VK_MAX_ANCHOR_DIM = 8
 VK_MAX_NMS_THRESH = 8
+VK_MAX_IGNOREY = 64
 
 # status code -> the Python exception type the reference raises in the same situation
 # (frcnn.py:1930 NotImplementedError, :148 AssertionError, :1789/:1850 EnvironmentError/OSError)
@@ -67,6 +68,10 @@ class vk_outputs(C.Structure):
     ]
 
 
+class vk_ignorey(C.Structure):
+    _fields_ = [("bands", C.c_void_p), ("counts", C.c_void_p), ("max_per_image", C.c_int32), ("f64", C.c_int32)]
+
+
 _P, _I, _F, _D, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes): every symbol include/vltk_hip.h declares
@@ -83,6 +88,8 @@ SIGNATURES = {
     "vk_forward": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(vk_roi_params), C.POINTER(vk_outputs), _P]),
     "vk_forward_begin": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(vk_roi_params), C.POINTER(vk_outputs), _P,
                               C.POINTER(C.c_int64)]),
+    "vk_forward_begin_ignorey": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(vk_roi_params), C.POINTER(vk_outputs), _P,
+                                      C.POINTER(C.c_int64), C.POINTER(vk_ignorey)]),
     "vk_forward_boxes_begin": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, C.POINTER(vk_outputs), _P, C.POINTER(C.c_int64)]),
     "vk_forward_end": (_I, [_P, C.c_int64]),
     "vk_get_stage": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(C.c_int64), C.POINTER(_I)]),
@@ -110,6 +117,8 @@ SIGNATURES = {
     "vk_relu_copy": (_I, [_P, _P, C.c_long, _I, _P]),
     "vk_rpn_multilevel_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "vk_rpn_proposals_multilevel": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P, _F, _P, _P, _F, _D, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vk_rpn_proposals_multilevel_ignorey": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P, _F, _P, _P, _F, _D, _I, _I, _P, _P, _P, _P,
+                                                 _P, _SZ, _P, C.POINTER(vk_ignorey)]),
     "vk_conv2d": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vk_nchw_to_nhwc": (_I, [_P, _I, _I, _I, _I, _P, _I, _P]),
     "vk_nhwc_to_nchw": (_I, [_P, _I, _I, _I, _I, _P, _I, _P]),
@@ -123,6 +132,8 @@ SIGNATURES = {
     "vk_rpn_workspace_bytes": (_SZ, [_I, _I, _I]),
     "vk_rpn_proposals": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _F, _P, C.POINTER(_F), _F, _D, _I, _I,
                               _P, _P, _P, _P, _P, _SZ, _P]),
+    "vk_rpn_proposals_ignorey": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _F, _P, C.POINTER(_F), _F, _D, _I, _I,
+                                      _P, _P, _P, _P, _P, _SZ, _P, C.POINTER(vk_ignorey)]),
     "vk_nms": (_I, [_P, _P, _I, _D, _P, _P, _P, _SZ, _P]),
     "vk_nms_workspace_bytes": (_SZ, [_I]),
     "vk_roi_pool": (_I, [_P, _I, _I, _I, _I, _P, _I, _F, _I, _P, _I, _P]),

@@ -33,10 +33,12 @@ import numpy as np
 import torch
 
 from .config import Config, vg_c4_config
+from .frcnn import MAX_IGNOREY
 
 # string keys of vltk/vars.py:38-60 that the extraction loop uses
 IMG, SIZE, SCALE, RAWSIZE, FILEPATH, IMGID, SPLIT = "image", "size", "wh_scale", "rawsize", "filepath", "imgid", "split"
 FEATURES, BOX, BOXES = "features", "box", "boxes"
+IGNOREY = "ignorey"
 SPLITALIASES = ("test", "dev", "eval", "val", "validation", "evaluation", "train")       # vltk/vars.py:63-71
 IMGFILES = ("jpeg", "jpg", "png")                                                         # abc/adapter.py:25
 
@@ -230,10 +232,12 @@ class FRCNN:
     @staticmethod
     def forward(model, entry):
         """entry["boxes"] (vltk's vars.boxes, [K, 4] in original-image pixels), when present: region features for exactly
-        those boxes (FRCNN.forward(proposals=...)) instead of detection."""
+        those boxes (FRCNN.forward(proposals=...)) instead of detection.  entry["ignorey"] ([J, 2] rows (y0, y1) in
+        original-image pixels), when present: bands whose proposals are removed or trimmed (FRCNN.forward(ignorey=...))."""
         size, scale_wh, image = entry[SIZE], entry[SCALE], entry[IMG]
         model_out = model(images=image.unsqueeze(0), image_shapes=torch.as_tensor(size).unsqueeze(0),
-                          padding="max_detections", pad_value=0.0, location="cpu", **FRCNN._given(model, [entry]))
+                          padding="max_detections", pad_value=0.0, location="cpu", **FRCNN._given(model, [entry]),
+                          **FRCNN._bands([entry]))
         return FRCNN._rows(model_out, [scale_wh], 0)
 
     @staticmethod
@@ -242,7 +246,7 @@ class FRCNN:
         images = torch.stack([e[IMG] for e in entries])
         sizes = torch.stack([torch.as_tensor(e[SIZE]) for e in entries])
         model_out = model(images=images, image_shapes=sizes, padding="max_detections", pad_value=0.0, location="cpu",
-                          **FRCNN._given(model, entries))
+                          **FRCNN._given(model, entries), **FRCNN._bands(entries))
         out = None
         for i, e in enumerate(entries):
             row = FRCNN._rows(model_out, [e[SCALE]], i)
@@ -268,6 +272,22 @@ class FRCNN:
             b = torch.as_tensor(np.asarray(e[BOXES], dtype=np.float32)).reshape(-1, 4).clone()
             props.append(rescale_box(b, torch.as_tensor(e[SCALE], dtype=torch.float32)))
         return {"proposals": props, "max_detections": int(model.roi_outputs.max_detections)}
+
+    @staticmethod
+    def _bands(entries):
+        """`ignorey=` for entries that carry bands (entry["ignorey"], [J, 2] rows in original-image pixels; an entry without
+        one has none).  {} when no entry has any.  These forwards run without scales_yx, so the rows are taken to the processed
+        image here, times the entry's x scale (the reference's quirk: it divides y by the x scale, frcnn.py:331), and
+        scales_yx = 1 (an exact no-op on the output boxes) lets the model apply them."""
+        if not any(e.get(IGNOREY) is not None for e in entries):
+            return {}
+        bands = []
+        for e in entries:
+            b = e.get(IGNOREY)
+            b = torch.zeros((0, 2)) if b is None else torch.as_tensor(b).reshape(-1, 2)
+            sx = torch.as_tensor(e[SCALE], dtype=torch.float32).reshape(-1)[0]
+            bands.append(b * sx.to(torch.float64 if b.dtype == torch.float64 else torch.float32))
+        return {"ignorey": bands, "scales_yx": torch.ones((len(entries), 2), dtype=torch.float32)}
 
     @staticmethod
     def _rows(model_out, scales, i):
@@ -334,6 +354,8 @@ class FRCNN:
         (FRCNN.forward(proposals=...)) instead of detection.  Every image of every split needs an entry and K may not
         exceed the schema's max_detections (ValueError before anything is written); the rows keep the schema, `box`
         holding the given boxes clipped to the image and rounded, `features` zero-padded to the schema's width.
+        `ignorey={imgid: [J, 2] rows (y0, y1) in original-image pixels}`: bands whose RPN proposals are removed or trimmed
+        (FRCNN.forward(ignorey=...)); an image without an entry has none, J <= 64 (ValueError before anything is written).
         With torch.distributed initialised the images of every split shard across the ranks (parallel.py); the dict is
         returned on rank 0 (empty elsewhere).  `model.roi_outputs.{max,min}_detections` are set to the schema's width for
         the call and restored afterwards.  The reference-processor mode (`processor="reference"` / a `processor_config`)
@@ -352,6 +374,17 @@ class FRCNN:
         given = kwargs.pop("boxes", None)
         if given is not None:
             given = {str(k): np.asarray(v, dtype=np.float32).reshape(-1, 4) for k, v in given.items()}
+        bands = kwargs.pop("ignorey", None)
+        if bands is not None:
+            if given is not None:
+                raise ValueError("ignorey removes / trims RPN proposals: there are none with boxes=")
+            bands = {str(k): torch.as_tensor(v).detach().cpu().reshape(-1, 2) for k, v in bands.items()}
+            wide = {k: len(v) for k, v in bands.items() if len(v) > MAX_IGNOREY}
+            if wide:
+                raise ValueError(f"ignorey: more than {MAX_IGNOREY} bands for {wide}; nothing was written")
+            bad = sorted(k for k, v in bands.items() if v.dtype == torch.bool or v.is_complex() or not torch.isfinite(v.double()).all())
+            if bad:
+                raise ValueError(f"ignorey: bands that are not finite real numbers for {bad[:20]}; nothing was written")
         if prebuilt is not None:
             model, model_config = prebuilt
         else:
@@ -367,14 +400,14 @@ class FRCNN:
                 model.roi_outputs.max_detections = D
                 model.roi_outputs.min_detections = min(int(model.roi_outputs.min_detections), D)
             splitdict = cls._extract_splits(model, model_config, searchdirs, valid_splits, savedir, dataset_name, subset_ids,
-                                            processor, processor_config, batch_size, D, F, kwargs, given)
+                                            processor, processor_config, batch_size, D, F, kwargs, given, bands)
         finally:
             model.roi_outputs.max_detections, model.roi_outputs.min_detections = saved_limits
         return splitdict
 
     @classmethod
     def _extract_splits(cls, model, model_config, searchdirs, valid_splits, savedir, dataset_name, subset_ids, processor,
-                        processor_config, batch_size, D, F, kwargs, given=None):
+                        processor_config, batch_size, D, F, kwargs, given=None, bands=None):
         from .extraction import ExtractionWriter, load_extraction
         # files -> per split (id, path), in the reference's terms: split = parent directory, id = stem up to the first dot
         print(f"extracting from {searchdirs}")
@@ -429,7 +462,7 @@ class FRCNN:
             savefile = os.path.join(savedir, f"{split}.arrow")
             if gpu_path:
                 cls._extract_split_gpu(model, model_config, items, savefile, dataset_name, pargs, cfgd, batch_size, F,
-                                       rank, world, given)
+                                       rank, world, given, bands)
             else:
                 fkw = _collect_args(cls.forward, kwargs)
                 fkw.pop("model", None), fkw.pop("entry", None)
@@ -442,6 +475,8 @@ class FRCNN:
                         entry[RAWSIZE] = _proc_attr(processor, "_rawsize")
                         if given is not None:
                             entry[BOXES] = given[img_id]
+                        if bands is not None and img_id in bands:
+                            entry[IGNOREY] = bands[img_id]
                         out = cls.forward(model=model, entry=entry, **fkw)
                         assert isinstance(out, dict), "model outputs should be in dict format"
                         w.write_batch([img_id], np.asarray(out["object_ids"], np.float32), np.asarray(out["attr_ids"], np.float32),
@@ -455,12 +490,13 @@ class FRCNN:
 
     @classmethod
     def _extract_split_gpu(cls, model, model_config, items, savefile, dataset_name, pargs, cfgd, batch_size, F, rank, world,
-                           given=None):
+                           given=None, bands=None):
         from .parallel import shard_indices
         from .pipeline import ExtractionPipeline
         from .preprocess import Preprocess
         pipe = ExtractionPipeline(model, Preprocess(model_config, device=model.device), savefile, batch_size=batch_size,
-                                  visual_dim=F, dataset=dataset_name, processor_args=pargs, model_config=cfgd, boxes=given)
+                                  visual_dim=F, dataset=dataset_name, processor_args=pargs, model_config=cfgd, boxes=given,
+                                  ignorey=bands)
         pipe.set_global_ids([i for i, _ in items])
         lo, hi = shard_indices(len(items), rank, world)
         mine = items[lo:hi]

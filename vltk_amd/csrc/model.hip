@@ -412,6 +412,8 @@ struct Plan {
     float *rpn_out, *prop_boxes, *prop_logits, *rois;
     int32_t *prop_counts, *image_hw, *nonfinite;
     float *scales;
+    void *bands;             // ignorey: [N][<= VK_MAX_IGNOREY][2] f32 or f64, as the ticket's slot holds them
+    int32_t *band_counts;    // [N]
     void *rpn_ws;
     size_t rpn_ws_bytes;
     void *pooled, *h_t1, *h_t2, *h_a, *h_b, *h_sc;
@@ -509,6 +511,8 @@ static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D, int 
     p.attr_cls = (int32_t *)cv.take((size_t)p.K * sizeof(int32_t));
     p.max_class = (int32_t *)cv.take((size_t)p.K * sizeof(int32_t));
     p.keep_ids = (int64_t *)cv.take((size_t)N * D * sizeof(int64_t));
+    p.bands = cv.take((size_t)N * VK_MAX_IGNOREY * 2 * sizeof(double));
+    p.band_counts = (int32_t *)cv.take((size_t)N * sizeof(int32_t));
     p.total = cv.off;
     return p;
 }
@@ -1172,9 +1176,10 @@ namespace vk {
 
 // Arena for R RoI rows per image, the stage map cleared, the caller's host arrays copied into the ticket's pinned slot
 // (consumed before _begin returns, and the host-to-device copies are truly asynchronous), the non-finite flag zeroed.
-// counts (given boxes only): host [N] -> p.prop_counts.
+// counts (given boxes only): host [N] -> p.prop_counts.  ig (detection only; host arrays, checked by the caller, or null):
+// its counts -> p.band_counts, its [N][max_per_image][2] bands -> p.bands.
 static int fwd_open(vk_handle *h, int N, int H, int W, int R, int D, const int32_t *image_hw, const float *scales_yx,
-                    const int32_t *counts, hipStream_t s, Plan *out) {
+                    const int32_t *counts, const vk_ignorey *ig, hipStream_t s, Plan *out) {
     Plan need = make_plan(h, nullptr, N, H, W, D, R);
     if (need.total > h->arena_bytes) {
         if (h->arena) {
@@ -1191,9 +1196,12 @@ static int fwd_open(vk_handle *h, int N, int H, int W, int R, int D, const int32
     h->stages_out.clear();
     if (h->timing) VK_CHECK_HIP(hipEventRecord(h->ev[0], s));
 
-    // slot layout: image_hw [N,2] i32 | scales_yx [N,2] f32 | counts [N] i32
+    // slot layout: image_hw [N,2] i32 | scales_yx [N,2] f32 | counts [N] i32 | band counts [N] i32 | (8-aligned) bands
     const size_t hw_bytes = sizeof(int32_t) * 2 * (size_t)N, sc_bytes = sizeof(float) * 2 * (size_t)N;
-    const size_t meta_need = hw_bytes + sc_bytes + sizeof(int32_t) * (size_t)N;
+    const size_t cnt_bytes = sizeof(int32_t) * (size_t)N;
+    const size_t band_off = align_up(hw_bytes + sc_bytes + 2 * cnt_bytes, 8);
+    const size_t band_bytes = ig ? (size_t)N * ig->max_per_image * 2 * (ig->f64 ? sizeof(double) : sizeof(float)) : 0;
+    const size_t meta_need = ig ? band_off + band_bytes : hw_bytes + sc_bytes + cnt_bytes;
     if (meta_need > h->meta_cap) {
         VK_CHECK_HIP(hipDeviceSynchronize());
         if (h->meta_host) VK_CHECK_HIP(hipHostFree(h->meta_host));
@@ -1211,6 +1219,12 @@ static int fwd_open(vk_handle *h, int N, int H, int W, int R, int D, const int32
     if (counts) {
         memcpy(meta + hw_bytes + sc_bytes, counts, sizeof(int32_t) * (size_t)N);
         VK_CHECK_HIP(hipMemcpyAsync(p.prop_counts, meta + hw_bytes + sc_bytes, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, s));
+    }
+    if (ig) {
+        memcpy(meta + hw_bytes + sc_bytes + cnt_bytes, ig->counts, cnt_bytes);
+        VK_CHECK_HIP(hipMemcpyAsync(p.band_counts, meta + hw_bytes + sc_bytes + cnt_bytes, cnt_bytes, hipMemcpyHostToDevice, s));
+        memcpy(meta + band_off, ig->bands, band_bytes);
+        VK_CHECK_HIP(hipMemcpyAsync(p.bands, meta + band_off, band_bytes, hipMemcpyHostToDevice, s));
     }
     VK_CHECK_HIP(hipMemsetAsync(p.nonfinite, 0, sizeof(int32_t), s));
     return VK_OK;
@@ -1391,7 +1405,32 @@ extern "C" {
 
 int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W, const int32_t *image_hw,
                      const float *scales_yx, const vk_roi_params *rp, const vk_outputs *out, void *stream, int64_t *ticket) {
+    return vk_forward_begin_ignorey(h, images_dev, N, H, W, image_hw, scales_yx, rp, out, stream, ticket, nullptr);
+}
+
+int vk_forward_begin_ignorey(vk_handle *h, const float *images_dev, int N, int H, int W, const int32_t *image_hw,
+                             const float *scales_yx, const vk_roi_params *rp, const vk_outputs *out, void *stream, int64_t *ticket,
+                             const vk_ignorey *ignorey) {
     VK_REQUIRE(h && images_dev && image_hw && rp && out && ticket, VK_EINVAL, "forward: null argument");
+    // the reference filters by the bands only when scales_yx is given too (frcnn.py:328); no bands == the plain launch sequence
+    const vk_ignorey *ig = scales_yx && ignorey && ignorey->max_per_image > 0 ? ignorey : nullptr;
+    if (ig) {
+        VK_REQUIRE(ig->max_per_image <= VK_MAX_IGNOREY, VK_EINVAL, "ignorey: max_per_image=%d must be in 0..%d", ig->max_per_image,
+                   VK_MAX_IGNOREY);
+        VK_REQUIRE(ig->bands && ig->counts, VK_EINVAL, "ignorey: null bands / counts");
+        VK_REQUIRE(ig->f64 == 0 || ig->f64 == 1, VK_EINVAL, "ignorey: f64=%d must be 0 or 1", ig->f64);
+        for (int n = 0; n < N; ++n) {
+            const int J = ig->counts[n];
+            VK_REQUIRE(J >= 0 && J <= ig->max_per_image, VK_EINVAL, "ignorey: counts[%d]=%d must be in 0..%d", n, J, ig->max_per_image);
+            for (int k = 0; k < 2 * J; ++k) {
+                const size_t at = ((size_t)n * ig->max_per_image) * 2 + k;
+                const double v = ig->f64 ? static_cast<const double *>(ig->bands)[at] : (double)static_cast<const float *>(ig->bands)[at];
+                // int() of the band (frcnn.py:365-366) raises on these in the reference
+                VK_REQUIRE(std::isfinite(v) && std::fabs(v) < 2147483648.0, VK_EINVAL, "ignorey: image %d band %d holds %g (must be finite, "
+                           "|value| < 2^31)", n, k / 2, v);
+            }
+        }
+    }
     VK_REQUIRE(h->next_ticket - h->oldest_open < vk_handle::VK_MAX_INFLIGHT, VK_EINVAL,
                "forward_begin: %d forwards are already in flight; end the oldest first", vk_handle::VK_MAX_INFLIGHT);
     VK_REQUIRE(h->finalized, VK_EINVAL, "forward: vk_finalize has not been called");
@@ -1412,7 +1451,7 @@ int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
     const bool tm = h->timing;
 
     Plan p;
-    VK_TRY(fwd_open(h, N, H, W, c.post_nms_topk, D, image_hw, scales_yx, nullptr, s, &p));
+    VK_TRY(fwd_open(h, N, H, W, c.post_nms_topk, D, image_hw, scales_yx, nullptr, ig, s, &p));
     const void *res4 = nullptr;
     VK_TRY(fwd_backbone(h, p, images_dev, s, &res4));
 
@@ -1424,10 +1463,17 @@ int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
     if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[2], s));
 
     // ---- proposals (RPN.inference frcnn.py:1615-1638) ----
-    VK_TRY(vk_rpn_proposals(p.rpn_out, ld_rpn, p.rpn_out + h->A, ld_rpn, N, p.Hf, p.Wf, h->A, h->cell_anchors, 16,
-                            c.anchor_offset, p.image_hw, c.rpn_bbox_weights, c.rpn_min_size, c.rpn_nms_thresh,
-                            c.pre_nms_topk, c.post_nms_topk, p.prop_boxes, p.prop_logits, p.prop_counts, p.nonfinite,
-                            p.rpn_ws, p.rpn_ws_bytes, s));
+    vk_ignorey ig_dev{};
+    if (ig) {
+        ig_dev.bands = p.bands;
+        ig_dev.counts = p.band_counts;
+        ig_dev.max_per_image = ig->max_per_image;
+        ig_dev.f64 = ig->f64;
+    }
+    VK_TRY(vk_rpn_proposals_ignorey(p.rpn_out, ld_rpn, p.rpn_out + h->A, ld_rpn, N, p.Hf, p.Wf, h->A, h->cell_anchors, 16,
+                                    c.anchor_offset, p.image_hw, c.rpn_bbox_weights, c.rpn_min_size, c.rpn_nms_thresh,
+                                    c.pre_nms_topk, c.post_nms_topk, p.prop_boxes, p.prop_logits, p.prop_counts, p.nonfinite,
+                                    p.rpn_ws, p.rpn_ws_bytes, s, ig ? &ig_dev : nullptr));
     VK_TRY(launch_make_rois(p.prop_boxes, N, p.R, p.rois, s));
     set_stage(h, "proposal_boxes", p.prop_boxes, VK_F32, {N, p.R, 4});
     set_stage(h, "proposal_logits", p.prop_logits, VK_F32, {N, p.R});
@@ -1509,7 +1555,7 @@ int vk_forward_boxes_begin(vk_handle *h, const float *images_dev, int N, int H, 
     const bool tm = h->timing;
 
     Plan p;
-    VK_TRY(fwd_open(h, N, H, W, B, B, image_hw, scales_yx, counts, s, &p));
+    VK_TRY(fwd_open(h, N, H, W, B, B, image_hw, scales_yx, counts, nullptr, s, &p));
     const void *res4 = nullptr;
     VK_TRY(fwd_backbone(h, p, images_dev, s, &res4));
     if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[2], s));          // no RPN head

@@ -19,12 +19,14 @@
 //   rpn_select_decode  1 WG (1024 thr) / image: 4-pass 8-bit radix select of the pre_topk-th
 //                      best logit, index-ordered compaction (wave ballots), bitonic sort of
 //                      <= 8192 (key,index) pairs in LDS, then decode+clip+filter of the sorted
-//                      candidates.
+//                      candidates.  The _bands instantiations also apply the caller's ignorey
+//                      bands (frcnn.py:328-366) between the decode and the clip.
 //   nms_mask           64x64 IoU blocks -> 64-bit suppression masks (upper triangle only).
 //   nms_scan           1 WG / image: greedy sweep over 64-box chunks; in-chunk resolution with
 //                      v_readlane on the diagonal words, cross-chunk propagation by one lane per
 //                      mask word; stops as soon as post_topk boxes are kept.
 #include <cfloat>
+#include <type_traits>
 
 #include "vk_common.h"
 
@@ -84,13 +86,43 @@ __device__ __forceinline__ void clip4(float b[4], float h, float w) {
     b[3] = fminf(fmaxf(b[3], 0.f), h);
 }
 
+// ignorey bands (find_top_rpn_proposals frcnn.py:328-366), already divided by scales_yx[n][1] on the host: [N][max_per_image][2] of
+// T (float or double, torch's promoted dtype), counts [N]; the same for every thread of an image's workgroup (scalar loads)
+struct BandTab {
+    const void *bands;
+    const int32_t *counts;
+    int max_per_image;
+};
+
+// One image's bands, in order, on one decoded box, in T (the box is widened, as torch compares f32 with f64).  Returns false when a
+// band removed it (the box spans the whole band); a survivor is trimmed with the reference's pre-trim tests: clip_top sets y1 =
+// int(g0), clip_bottom sets y0 = int(g1).  A removed box is left alone by the later bands; a NaN box is never removed nor trimmed.
+template <typename T>
+__device__ __forceinline__ bool apply_bands(const T *__restrict__ g, int J, float b[4]) {
+    bool alive = true;
+    for (int j = 0; j < J; ++j) {
+        const T g0 = g[2 * j], g1 = g[2 * j + 1];
+        const T y0 = (T)b[1], y1 = (T)b[3];
+        const bool drop = g1 <= y1 && g0 >= y0;
+        const bool above = y0 > g1 && y1 > g0;                 // box_ignore_above; box_ignore_below is always false
+        const bool to_clip = alive && !drop && !above;
+        const T d_top = fabs(g1 - y1), d_bot = fabs(g0 - y0);
+        if (to_clip && d_bot < d_top) b[1] = (float)trunc(g1);  // clip_bottom
+        if (to_clip && d_top < d_bot) b[3] = (float)trunc(g0);  // clip_top
+        alive = alive && !drop;
+    }
+    return alive;
+}
+
 // ---------------------------------------------------------------------------
 // workspace per image: cand_boxes [pre][4] f32, cand_logit [pre] f32, cand_valid [pre] u8 (as i32 words), cand_count [1]
+// BT: void (no bands: the code of the kernels without ignorey) or the bands' dtype
+template <typename BT>
 __device__ __forceinline__ void rpn_select_decode_body(
     const float *__restrict__ logits, int ld_logits, const float *__restrict__ deltas, int ld_deltas, int Hf, int Wf,
     int A, const float *__restrict__ cell_anchors, const int32_t *__restrict__ image_hw, DecodeCfg cfg, int pre_topk,
     int sortn /* pow2 >= min(pre_topk, HWA) */, float *__restrict__ cand_boxes, float *__restrict__ cand_logit,
-    int32_t *__restrict__ cand_valid, int32_t *__restrict__ cand_count, int32_t *__restrict__ nonfinite) {
+    int32_t *__restrict__ cand_valid, int32_t *__restrict__ cand_count, int32_t *__restrict__ nonfinite, BandTab bt) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     // all LDS in the one dynamic array (keeps its base 16-byte aligned): keys | hist | wave counts | scalars
     unsigned long long *skey = reinterpret_cast<unsigned long long *>(smem_raw);   // [sortn]
@@ -225,6 +257,12 @@ __device__ __forceinline__ void rpn_select_decode_body(
 #endif
     // ---- decode + clip + size filter of the K sorted candidates ----
     const float img_h = (float)image_hw[2 * n], img_w = (float)image_hw[2 * n + 1];
+    int nbands = 0;
+    const void *gband = nullptr;
+    if constexpr (!std::is_void<BT>::value) {
+        nbands = min(bt.counts[n], bt.max_per_image);
+        gband = static_cast<const BT *>(bt.bands) + (long)n * bt.max_per_image * 2;
+    }
     bool bad = false;
     for (int e = tid; e < K; e += RPN_THREADS) {
         const uint32_t idx = (uint32_t)(skey[e] & 0xFFFFFFFFull);
@@ -238,9 +276,11 @@ __device__ __forceinline__ void rpn_select_decode_body(
         float d[4] = {dp[0], dp[1], dp[2], dp[3]};
         float b[4];
         apply_deltas1(anc, d, cfg.wx, cfg.wy, cfg.ww, cfg.wh, cfg.scale_clamp, b);
-        if (!finite4(b)) bad = true;
+        bool kept = true;        // removed by a band: keeps its slot, flagged invalid like a size-filtered box
+        if constexpr (!std::is_void<BT>::value) kept = apply_bands(static_cast<const BT *>(gband), nbands, b);
+        if (kept && !finite4(b)) bad = true;    // frcnn.py:148 sees the survivors only
         clip4(b, img_h, img_w);
-        const bool valid = ((b[2] - b[0]) > cfg.min_size) && ((b[3] - b[1]) > cfg.min_size);
+        const bool valid = kept && ((b[2] - b[0]) > cfg.min_size) && ((b[3] - b[1]) > cfg.min_size);
         float *ob = cand_boxes + ((long)n * pre_topk + e) * 4;
         ob[0] = b[0];
         ob[1] = b[1];
@@ -258,8 +298,18 @@ __global__ __launch_bounds__(RPN_THREADS) void rpn_select_decode_kernel(
     int A, const float *__restrict__ cell_anchors, const int32_t *__restrict__ image_hw, DecodeCfg cfg, int pre_topk,
     int sortn, float *__restrict__ cand_boxes, float *__restrict__ cand_logit, int32_t *__restrict__ cand_valid,
     int32_t *__restrict__ cand_count, int32_t *__restrict__ nonfinite) {
-    rpn_select_decode_body(logits, ld_logits, deltas, ld_deltas, Hf, Wf, A, cell_anchors, image_hw, cfg, pre_topk, sortn, cand_boxes, cand_logit,
-                           cand_valid, cand_count, nonfinite);
+    rpn_select_decode_body<void>(logits, ld_logits, deltas, ld_deltas, Hf, Wf, A, cell_anchors, image_hw, cfg, pre_topk, sortn, cand_boxes,
+                                 cand_logit, cand_valid, cand_count, nonfinite, BandTab{});
+}
+
+template <typename BT>
+__global__ __launch_bounds__(RPN_THREADS) void rpn_select_decode_bands_kernel(
+    const float *__restrict__ logits, int ld_logits, const float *__restrict__ deltas, int ld_deltas, int Hf, int Wf,
+    int A, const float *__restrict__ cell_anchors, const int32_t *__restrict__ image_hw, DecodeCfg cfg, int pre_topk,
+    int sortn, float *__restrict__ cand_boxes, float *__restrict__ cand_logit, int32_t *__restrict__ cand_valid,
+    int32_t *__restrict__ cand_count, int32_t *__restrict__ nonfinite, BandTab bt) {
+    rpn_select_decode_body<BT>(logits, ld_logits, deltas, ld_deltas, Hf, Wf, A, cell_anchors, image_hw, cfg, pre_topk, sortn, cand_boxes,
+                               cand_logit, cand_valid, cand_count, nonfinite, bt);
 }
 
 // Every level of a pyramid in ONE launch (grid = images x levels): a level's selection is one workgroup per image, so five launches of
@@ -275,8 +325,19 @@ __global__ __launch_bounds__(RPN_THREADS) void rpn_select_decode_levels_kernel(S
                                                                                DecodeCfg cfg, int pre_topk, int32_t *__restrict__ nonfinite) {
     const int l = blockIdx.y;
     cfg.stride = sl.stride[l];
-    rpn_select_decode_body(sl.logits[l], sl.ld_logits[l], sl.deltas[l], sl.ld_deltas[l], sl.Hf[l], sl.Wf[l], A, sl.cell_anchors[l], image_hw, cfg,
-                           pre_topk, sl.sortn[l], sl.cand_boxes[l], sl.cand_logit[l], sl.cand_valid[l], sl.cand_count[l], nonfinite);
+    rpn_select_decode_body<void>(sl.logits[l], sl.ld_logits[l], sl.deltas[l], sl.ld_deltas[l], sl.Hf[l], sl.Wf[l], A, sl.cell_anchors[l], image_hw,
+                                 cfg, pre_topk, sl.sortn[l], sl.cand_boxes[l], sl.cand_logit[l], sl.cand_valid[l], sl.cand_count[l], nonfinite,
+                                 BandTab{});
+}
+// every level of an image gets the image's bands (each candidate is tested on its own, so per level == over the concatenation)
+template <typename BT>
+__global__ __launch_bounds__(RPN_THREADS) void rpn_select_decode_levels_bands_kernel(SelectLevels sl, int A, const int32_t *__restrict__ image_hw,
+                                                                                     DecodeCfg cfg, int pre_topk, int32_t *__restrict__ nonfinite,
+                                                                                     BandTab bt) {
+    const int l = blockIdx.y;
+    cfg.stride = sl.stride[l];
+    rpn_select_decode_body<BT>(sl.logits[l], sl.ld_logits[l], sl.deltas[l], sl.ld_deltas[l], sl.Hf[l], sl.Wf[l], A, sl.cell_anchors[l], image_hw,
+                               cfg, pre_topk, sl.sortn[l], sl.cand_boxes[l], sl.cand_logit[l], sl.cand_valid[l], sl.cand_count[l], nonfinite, bt);
 }
 
 // ---------------------------------------------------------------------------
@@ -508,6 +569,22 @@ __global__ void box_decode_kernel(const float *__restrict__ deltas, const float 
     out[4 * i + 3] = o[3];
 }
 
+// the caller's band table -> BandTab; *on = false for NULL or max_per_image == 0 (the plain kernels run, as without ignorey)
+static int band_tab(const vk_ignorey *ig, BandTab *bt, bool *on, bool *f64) {
+    *on = ig && ig->max_per_image > 0;
+    *f64 = false;
+    memset(bt, 0, sizeof(*bt));
+    if (!*on) return VK_OK;
+    VK_REQUIRE(ig->max_per_image <= VK_MAX_IGNOREY, VK_EINVAL, "ignorey: max_per_image=%d must be in 0..%d", ig->max_per_image, VK_MAX_IGNOREY);
+    VK_REQUIRE(ig->bands && ig->counts, VK_EINVAL, "ignorey: null bands / counts");
+    VK_REQUIRE(ig->f64 == 0 || ig->f64 == 1, VK_EINVAL, "ignorey: f64=%d must be 0 or 1", ig->f64);
+    bt->bands = ig->bands;
+    bt->counts = ig->counts;
+    bt->max_per_image = ig->max_per_image;
+    *f64 = ig->f64 != 0;
+    return VK_OK;
+}
+
 static int next_pow2(int v) {
     int p = 2;
     while (p < v) p <<= 1;
@@ -675,6 +752,16 @@ int vk_rpn_proposals(const float *logits, int ld_logits, const float *deltas, in
                      const float *bbox_weights4_host, float min_size, double nms_thresh, int pre_topk, int post_topk,
                      float *out_boxes, float *out_logits, int32_t *out_counts, int32_t *nonfinite_flag, void *workspace,
                      size_t workspace_bytes, void *stream) {
+    return vk_rpn_proposals_ignorey(logits, ld_logits, deltas, ld_deltas, N, Hf, Wf, A, cell_anchors, stride, offset, image_hw,
+                                    bbox_weights4_host, min_size, nms_thresh, pre_topk, post_topk, out_boxes, out_logits, out_counts,
+                                    nonfinite_flag, workspace, workspace_bytes, stream, nullptr);
+}
+
+int vk_rpn_proposals_ignorey(const float *logits, int ld_logits, const float *deltas, int ld_deltas, int N, int Hf, int Wf, int A,
+                             const float *cell_anchors, int stride, float offset, const int32_t *image_hw,
+                             const float *bbox_weights4_host, float min_size, double nms_thresh, int pre_topk, int post_topk,
+                             float *out_boxes, float *out_logits, int32_t *out_counts, int32_t *nonfinite_flag, void *workspace,
+                             size_t workspace_bytes, void *stream, const vk_ignorey *ignorey) {
     VK_REQUIRE(N > 0 && Hf > 0 && Wf > 0 && A > 0, VK_EINVAL, "rpn: empty problem");
     VK_REQUIRE(pre_topk > 0 && pre_topk <= RPN_MAX_PRE, VK_EINVAL, "rpn: pre_nms_topk=%d must be in 1..%d", pre_topk, RPN_MAX_PRE);
     VK_REQUIRE(post_topk > 0 && post_topk <= pre_topk, VK_EINVAL, "rpn: post_nms_topk=%d must be in 1..pre_nms_topk", post_topk);
@@ -682,6 +769,9 @@ int vk_rpn_proposals(const float *logits, int ld_logits, const float *deltas, in
     VK_REQUIRE(HWA < (1L << 31), VK_EINVAL, "rpn: too many anchors");
     RpnWs w = carve_rpn_ws(workspace, N, pre_topk, post_topk);
     VK_REQUIRE(workspace && workspace_bytes >= w.total, VK_EINVAL, "rpn: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+    BandTab bt;
+    bool bands_on, f64;
+    VK_TRY(band_tab(ignorey, &bt, &bands_on, &f64));
     hipStream_t s = (hipStream_t)stream;
     const int K = (int)(pre_topk < HWA ? pre_topk : HWA);
     const int sortn = next_pow2(K);
@@ -699,10 +789,22 @@ int vk_rpn_proposals(const float *logits, int ld_logits, const float *deltas, in
     if (const char *e = getenv("VK_RPN_STOP")) cfg.stop = atoi(e);
 #endif
     const size_t smem = (size_t)sortn * 8 + 2048;
-    VK_TRY(set_max_lds(rpn_select_decode_kernel, RPN_MAX_PRE * 8 + 2048));
-    hipLaunchKernelGGL(rpn_select_decode_kernel, dim3(N), dim3(RPN_THREADS), smem, s, logits, ld_logits, deltas, ld_deltas,
-                       Hf, Wf, A, cell_anchors, image_hw, cfg, pre_topk, sortn, w.cand_boxes, w.cand_logit, w.cand_valid,
-                       w.cand_count, nonfinite_flag);
+    if (!bands_on) {
+        VK_TRY(set_max_lds(rpn_select_decode_kernel, RPN_MAX_PRE * 8 + 2048));
+        hipLaunchKernelGGL(rpn_select_decode_kernel, dim3(N), dim3(RPN_THREADS), smem, s, logits, ld_logits, deltas, ld_deltas,
+                           Hf, Wf, A, cell_anchors, image_hw, cfg, pre_topk, sortn, w.cand_boxes, w.cand_logit, w.cand_valid,
+                           w.cand_count, nonfinite_flag);
+    } else if (f64) {
+        VK_TRY(set_max_lds(rpn_select_decode_bands_kernel<double>, RPN_MAX_PRE * 8 + 2048));
+        hipLaunchKernelGGL(rpn_select_decode_bands_kernel<double>, dim3(N), dim3(RPN_THREADS), smem, s, logits, ld_logits, deltas, ld_deltas,
+                           Hf, Wf, A, cell_anchors, image_hw, cfg, pre_topk, sortn, w.cand_boxes, w.cand_logit, w.cand_valid,
+                           w.cand_count, nonfinite_flag, bt);
+    } else {
+        VK_TRY(set_max_lds(rpn_select_decode_bands_kernel<float>, RPN_MAX_PRE * 8 + 2048));
+        hipLaunchKernelGGL(rpn_select_decode_bands_kernel<float>, dim3(N), dim3(RPN_THREADS), smem, s, logits, ld_logits, deltas, ld_deltas,
+                           Hf, Wf, A, cell_anchors, image_hw, cfg, pre_topk, sortn, w.cand_boxes, w.cand_logit, w.cand_valid,
+                           w.cand_count, nonfinite_flag, bt);
+    }
     VK_CHECK_HIP(hipGetLastError());
     const int nb = ceil_div(K, 64);
     VK_TRY(launch_nms(w.cand_boxes, w.cand_valid, w.cand_count, N, pre_topk, nb, nms_thresh, post_topk, w.mask, w.keep_idx, w.keep_count,
@@ -759,6 +861,17 @@ int vk_rpn_proposals_multilevel(const float *const *logits, const int32_t *ld_lo
                                 const int32_t *strides, float offset, const int32_t *image_hw, const float *bbox_weights4_host,
                                 float min_size, double nms_thresh, int pre_topk, int post_topk, float *out_boxes, float *out_logits,
                                 int32_t *out_counts, int32_t *nonfinite_flag, void *workspace, size_t workspace_bytes, void *stream) {
+    return vk_rpn_proposals_multilevel_ignorey(logits, ld_logits, deltas, ld_deltas, levels, N, Hs, Ws, A, cell_anchors, strides, offset,
+                                               image_hw, bbox_weights4_host, min_size, nms_thresh, pre_topk, post_topk, out_boxes,
+                                               out_logits, out_counts, nonfinite_flag, workspace, workspace_bytes, stream, nullptr);
+}
+
+int vk_rpn_proposals_multilevel_ignorey(const float *const *logits, const int32_t *ld_logits, const float *const *deltas,
+                                        const int32_t *ld_deltas, int levels, int N, const int32_t *Hs, const int32_t *Ws, int A,
+                                        const float *const *cell_anchors, const int32_t *strides, float offset, const int32_t *image_hw,
+                                        const float *bbox_weights4_host, float min_size, double nms_thresh, int pre_topk, int post_topk,
+                                        float *out_boxes, float *out_logits, int32_t *out_counts, int32_t *nonfinite_flag, void *workspace,
+                                        size_t workspace_bytes, void *stream, const vk_ignorey *ignorey) {
     VK_REQUIRE(logits && deltas && Hs && Ws && cell_anchors && strides && image_hw && bbox_weights4_host, VK_EINVAL, "rpn_ml: null argument");
     VK_REQUIRE(levels >= 1 && levels <= RPN_MAX_LEVELS && N > 0 && A > 0, VK_EINVAL, "rpn_ml: 1..%d levels", RPN_MAX_LEVELS);
     VK_REQUIRE(pre_topk > 0 && (long)levels * pre_topk <= RPN_MAX_PRE, VK_EINVAL,
@@ -766,6 +879,9 @@ int vk_rpn_proposals_multilevel(const float *const *logits, const int32_t *ld_lo
     VK_REQUIRE(post_topk > 0 && post_topk <= levels * pre_topk, VK_EINVAL, "rpn_ml: post_nms_topk=%d out of range", post_topk);
     MlWs w = carve_ml_ws(workspace, N, levels, pre_topk, post_topk);
     VK_REQUIRE(workspace && workspace_bytes >= w.total, VK_EINVAL, "rpn_ml: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+    BandTab bt;
+    bool bands_on, f64;
+    VK_TRY(band_tab(ignorey, &bt, &bands_on, &f64));
     hipStream_t s = (hipStream_t)stream;
     LevelCands lc;
     memset(&lc, 0, sizeof(lc));
@@ -808,9 +924,20 @@ int vk_rpn_proposals_multilevel(const float *const *logits, const int32_t *ld_lo
     cfg.stride = 0;                                  // per level, from sl.stride
     cfg.offset = offset;
     cfg.stop = 0;
-    VK_TRY(set_max_lds(rpn_select_decode_levels_kernel, RPN_MAX_PRE * 8 + 2048));
-    hipLaunchKernelGGL(rpn_select_decode_levels_kernel, dim3(N, levels), dim3(RPN_THREADS), (size_t)max_sortn * 8 + 2048, s, sl, A, image_hw, cfg,
-                       pre_topk, nonfinite_flag);
+    const size_t sel_smem = (size_t)max_sortn * 8 + 2048;
+    if (!bands_on) {
+        VK_TRY(set_max_lds(rpn_select_decode_levels_kernel, RPN_MAX_PRE * 8 + 2048));
+        hipLaunchKernelGGL(rpn_select_decode_levels_kernel, dim3(N, levels), dim3(RPN_THREADS), sel_smem, s, sl, A, image_hw, cfg, pre_topk,
+                           nonfinite_flag);
+    } else if (f64) {
+        VK_TRY(set_max_lds(rpn_select_decode_levels_bands_kernel<double>, RPN_MAX_PRE * 8 + 2048));
+        hipLaunchKernelGGL(rpn_select_decode_levels_bands_kernel<double>, dim3(N, levels), dim3(RPN_THREADS), sel_smem, s, sl, A, image_hw, cfg,
+                           pre_topk, nonfinite_flag, bt);
+    } else {
+        VK_TRY(set_max_lds(rpn_select_decode_levels_bands_kernel<float>, RPN_MAX_PRE * 8 + 2048));
+        hipLaunchKernelGGL(rpn_select_decode_levels_bands_kernel<float>, dim3(N, levels), dim3(RPN_THREADS), sel_smem, s, sl, A, image_hw, cfg,
+                           pre_topk, nonfinite_flag, bt);
+    }
     VK_CHECK_HIP(hipGetLastError());
     const int cap = levels * pre_topk, sortn = next_pow2(cap), nwords = ceil_div(cap, 64);
     VK_TRY(set_max_lds(rpn_merge_levels_kernel, RPN_MAX_PRE * 8 + 256));

@@ -13,6 +13,7 @@ CPU path: constructing the model without the library or without a GPU raises.
 """
 import ctypes as C
 import os
+import warnings
 from collections import OrderedDict
 
 import numpy as np
@@ -119,6 +120,70 @@ def pack_proposals(proposals, N, device=None):
     for i, t in enumerate(ts):
         out[i, :t.shape[0]] = t.detach().to(device=out.device, dtype=torch.float32)
     return out, counts
+
+
+MAX_IGNOREY = L.VK_MAX_IGNOREY  # bands per image of ignorey=
+
+
+def _validate_ignorey(ignorey, N):
+    """-> (a list of N [J_i, 2] CPU tensors, f64): ValueError on a bad shape, more than 64 bands for one image or a dtype
+    that is not a real number.  f64: ignorey (one of its arrays) is float64 -- torch's promoted dtype of the reference's
+    `ignorey * 1 / scales_yx[n, 1]` with float32 scales; anything else computes in float32."""
+    if isinstance(ignorey, (torch.Tensor, np.ndarray)):
+        t = torch.as_tensor(ignorey)
+        if t.dim() != 3 or t.shape[2] != 2:                # assert ignorey.ndim == 3 (frcnn.py:329)
+            raise ValueError(f"ignorey as one array must be [N, J, 2], got shape {tuple(t.shape)}")
+        if t.shape[0] != N:
+            raise ValueError(f"ignorey: {t.shape[0]} images of bands for {N} images")
+        items = list(t.detach().cpu())
+    else:
+        items = list(ignorey)
+        if len(items) != N:
+            raise ValueError(f"ignorey: {len(items)} images of bands for {N} images")
+    ts = []
+    for i, b in enumerate(items):
+        t = torch.as_tensor(b).detach().cpu()
+        if t.numel() == 0 and t.dim() == 1:          # [] for an image without bands
+            t = t.reshape(0, 2)
+        if t.dim() != 2 or t.shape[1] != 2:
+            raise ValueError(f"ignorey[{i}] must be [J, 2] (y0, y1 rows), got {tuple(t.shape)}")
+        if t.shape[0] > MAX_IGNOREY:
+            raise ValueError(f"ignorey[{i}]: {t.shape[0]} bands, at most {MAX_IGNOREY}")
+        if t.dtype == torch.bool or t.is_complex():
+            raise ValueError(f"ignorey[{i}]: dtype {t.dtype} is not a real number")
+        ts.append(t)
+    return ts, any(t.dtype == torch.float64 for t in ts)
+
+
+def pack_ignorey(ignorey, scales_yx, N):
+    """Validate ignorey= and scale it for vk_forward_begin_ignorey / vk_rpn_proposals*_ignorey.
+
+    ignorey: one [N, J, 2] array / tensor (the reference's form) or a sequence of N [J_i, 2] ones (J_i may be 0), rows
+    (y0, y1) in the frame scales_yx maps to (original-image pixels).  scales_yx: host float32 [N, 2] or None.  Returns
+    None when there is nothing to apply -- no band at all, or no scales_yx, which the reference ignores ignorey without
+    (frcnn.py:328; a UserWarning here) -- else (bands, counts, f64): bands a C-contiguous [N, max J_i, 2] float32 /
+    float64 numpy array holding ignorey[n] * 1 / scales_yx[n, 1] computed by torch on the CPU exactly as frcnn.py:331 does
+    (the x scale on y values: the reference's quirk, kept), rows >= J_i zero; counts int32 [N].  ValueError on a bad
+    shape, J_i > 64, or a scaled band that is not finite or not below 2^31 in magnitude (the reference's int() raises)."""
+    ts, f64 = _validate_ignorey(ignorey, N)
+    if scales_yx is None:
+        warnings.warn("ignorey is ignored without scales_yx, as in the reference (frcnn.py:328)", UserWarning, stacklevel=3)
+        return None
+    counts = np.asarray([t.shape[0] for t in ts], dtype=np.int32).reshape(N)
+    J = int(counts.max(initial=0))
+    if J == 0:
+        return None
+    dt = torch.float64 if f64 else torch.float32
+    sc = torch.from_numpy(np.ascontiguousarray(np.asarray(scales_yx, dtype=np.float32).reshape(N, 2)))
+    bands = np.zeros((N, J, 2), dtype=np.float64 if f64 else np.float32)
+    for n, t in enumerate(ts):
+        if t.shape[0] == 0:
+            continue
+        g = (t.to(dt) * 1 / sc[n, 1]).numpy()                 # frcnn.py:331
+        if not (np.isfinite(g).all() and (np.abs(g) < 2.0 ** 31).all()):
+            raise ValueError(f"ignorey[{n}]: bands / scales_yx[{n}][1] must be finite and below 2^31 in magnitude, got {g.tolist()}")
+        bands[n, :t.shape[0]] = g
+    return bands, counts, f64
 
 
 def check_given_width(width, max_detections):
@@ -340,7 +405,12 @@ class FRCNN:
         the Res5 head (roi_features) and the box predictor (obj_probs / obj_ids: max / arg-max of the soft-max over the
         first C classes; attr_probs / attr_ids on that class); `boxes` = the clipped box times the scales, with no box
         regression and no NMS; preds_per_image[n] = K_i.  roi_outputs.{nms_thresh, min_detections, max_detections}
-        are not used; the output width is max K_i, and an explicit max_detections below it raises ValueError."""
+        are not used; the output width is max K_i, and an explicit max_detections below it raises ValueError.
+
+        ignorey (detection only; with `proposals` a ValueError): horizontal bands whose RPN proposals are removed or
+        trimmed (find_top_rpn_proposals frcnn.py:328-366) -- one [N, J, 2] array / tensor or N [J_i, 2] ones, rows (y0, y1)
+        divided by scales_yx[n][1]; at most 64 per image.  Applied only with scales_yx, as in the reference (a UserWarning
+        without).  See pack_ignorey and DESIGN §13."""
         if proposals is not None and self.given_boxes:         # before anything is enqueued
             counts = _validate_proposals(proposals, len(images))[1]
             check_given_width(int(counts.max(initial=0)), kwargs.get("max_detections"))
@@ -353,19 +423,21 @@ class FRCNN:
         order, on the same stream.  The caller must not modify `images` (or the proposals) before wait() returns."""
         if self.training:
             raise NotImplementedError()            # frcnn.py:1930-1931
-        if ignorey is not None:
-            raise NotImplementedError("ignorey is not supported")
+        if ignorey is not None and proposals is not None:
+            raise ValueError("ignorey removes / trims RPN proposals: there are none with proposals=")
         if not self._finalized:
             raise RuntimeError("no weights loaded: call load_state_dict / from_pretrained first")
         images = torch.as_tensor(images)
         if images.dim() != 4 or images.shape[1] != 3:
             raise ValueError(f"images must be [N,3,H,W], got {tuple(images.shape)}")
-        images = images.to(device=self.device, dtype=torch.float32).contiguous()
-        N, _, H, W = images.shape
-        hw = np.ascontiguousarray(np.asarray(torch.as_tensor(image_shapes).cpu()).reshape(N, 2), dtype=np.int32)
+        N = images.shape[0]
         sc = None
         if scales_yx is not None:
             sc = np.ascontiguousarray(np.asarray(torch.as_tensor(scales_yx).cpu(), dtype=np.float32).reshape(N, 2))
+        ig = pack_ignorey(ignorey, sc, N) if ignorey is not None else None        # before anything is enqueued
+        images = images.to(device=self.device, dtype=torch.float32).contiguous()
+        N, _, H, W = images.shape
+        hw = np.ascontiguousarray(np.asarray(torch.as_tensor(image_shapes).cpu()).reshape(N, 2), dtype=np.int32)
         F = self.config.RESNETS.RES2_OUT_CHANNELS * 8
         dev = self.device
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -394,9 +466,15 @@ class FRCNN:
         # one flat block, the seven arrays are views (so the multi-GPU exchange is a single all-gather: parallel.py)
         bufs = OutputBlock(output_spec(N, D, F), device=dev)
         out = L.vk_outputs(*[bufs[k].data_ptr() for k in bufs])
-        L.call("vk_forward_begin", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p),
-               sc.ctypes.data_as(C.c_void_p) if sc is not None else None, C.byref(rp), C.byref(out),
-               C.c_void_p(stream), C.byref(ticket))
+        if ig is None:
+            L.call("vk_forward_begin", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p),
+                   sc.ctypes.data_as(C.c_void_p) if sc is not None else None, C.byref(rp), C.byref(out),
+                   C.c_void_p(stream), C.byref(ticket))
+        else:                                      # the host bands are copied into the ticket's slot before the call returns
+            bands, bcounts, f64 = ig
+            igs = L.vk_ignorey(bands.ctypes.data, bcounts.ctypes.data, bands.shape[1], int(f64))
+            L.call("vk_forward_begin_ignorey", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p),
+                   sc.ctypes.data_as(C.c_void_p), C.byref(rp), C.byref(out), C.c_void_p(stream), C.byref(ticket), C.byref(igs))
         st = _Ticket(ticket.value, bufs, images)
         self._open.append(st)
         return PendingForward(self, st, hw)

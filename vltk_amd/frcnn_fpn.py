@@ -20,7 +20,7 @@ import torch
 
 from . import _lib as L
 from .config import CONFIG_NAME, WEIGHTS_NAME, Config          # noqa: F401
-from .frcnn import FRCNN, ROIOutputs, _TORCH_DT
+from .frcnn import FRCNN, ROIOutputs, _TORCH_DT, pack_ignorey
 from .parallel import OutputBlock, output_spec
 from .weights import BLOCKS_PER_STAGE, fpn_layer_spec
 
@@ -325,13 +325,17 @@ class FRCNNFPN(FRCNN):
     def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None):
         if self.training:
             raise NotImplementedError()
-        if proposals is not None or ignorey is not None:
-            raise NotImplementedError("precomputed proposals / ignorey are not supported")
+        if proposals is not None:
+            raise NotImplementedError("precomputed proposals are not supported")
         if not self._finalized:
             raise RuntimeError("no weights loaded: call load_state_dict / from_pretrained first")
         images = torch.as_tensor(images)
         if images.dim() != 4 or images.shape[1] != 3:
             raise ValueError(f"images must be [N,3,H,W], got {tuple(images.shape)}")
+        sc = None
+        if scales_yx is not None:
+            sc = np.ascontiguousarray(np.asarray(torch.as_tensor(scales_yx).cpu(), dtype=np.float32).reshape(images.shape[0], 2))
+        ig = pack_ignorey(ignorey, sc, images.shape[0]) if ignorey is not None else None     # before anything is enqueued
         images = images.to(device=self.device, dtype=torch.float32).contiguous()
         N, _, H, W = images.shape
         hw = np.ascontiguousarray(np.asarray(torch.as_tensor(image_shapes).cpu()).reshape(N, 2), dtype=np.int32)
@@ -394,11 +398,17 @@ class FRCNNFPN(FRCNN):
         nbw = L.load().vk_rpn_multilevel_workspace_bytes(N, nl, pre, R)
         wsp = torch.empty(nbw, dtype=torch.uint8, device=dev)
         wts = (C.c_float * 4)(*[float(v) for v in cfg.RPN.BBOX_REG_WEIGHTS])
-        L.call("vk_rpn_proposals_multilevel", P_([h_.data_ptr() for h_ in heads]), I_([ld] * nl),
-               P_([h_.data_ptr() + 4 * A for h_ in heads]), I_([ld] * nl), nl, N, I_([h_.shape[1] for h_ in heads]),
-               I_([h_.shape[2] for h_ in heads]), A, P_([c_.data_ptr() for c_ in self.cells]), I_([4 * 2 ** i for i in range(nl)]),
-               float(cfg.ANCHOR_GENERATOR.OFFSET), hw_dev.data_ptr(), wts, float(cfg.PROPOSAL_GENERATOR.MIN_SIZE),
-               float(cfg.RPN.NMS_THRESH), pre, R, pb.data_ptr(), pl.data_ptr(), pc.data_ptr(), flag.data_ptr(), wsp.data_ptr(), nbw, s)
+        rpn_args = (P_([h_.data_ptr() for h_ in heads]), I_([ld] * nl),
+                    P_([h_.data_ptr() + 4 * A for h_ in heads]), I_([ld] * nl), nl, N, I_([h_.shape[1] for h_ in heads]),
+                    I_([h_.shape[2] for h_ in heads]), A, P_([c_.data_ptr() for c_ in self.cells]), I_([4 * 2 ** i for i in range(nl)]),
+                    float(cfg.ANCHOR_GENERATOR.OFFSET), hw_dev.data_ptr(), wts, float(cfg.PROPOSAL_GENERATOR.MIN_SIZE),
+                    float(cfg.RPN.NMS_THRESH), pre, R, pb.data_ptr(), pl.data_ptr(), pc.data_ptr(), flag.data_ptr(), wsp.data_ptr(), nbw, s)
+        if ig is None:
+            L.call("vk_rpn_proposals_multilevel", *rpn_args)
+        else:                                      # device copies of the bands; kept in the stage map until the next forward
+            st["ignorey_bands"], st["ignorey_counts"] = torch.from_numpy(ig[0]).to(dev), torch.from_numpy(ig[1]).to(dev)
+            igs = L.vk_ignorey(st["ignorey_bands"].data_ptr(), st["ignorey_counts"].data_ptr(), ig[0].shape[1], int(ig[2]))
+            L.call("vk_rpn_proposals_multilevel_ignorey", *rpn_args, C.byref(igs))
         st["proposal_boxes"], st["proposal_logits"], st["proposal_counts"] = pb, pl, pc
         self._mark(evs)
         # ---- box head: RoIAlign by level (ROIPooler.forward's level loop :1200-1224, level rule :444-460) + FCs ----
@@ -450,8 +460,8 @@ class FRCNNFPN(FRCNN):
         bufs.flat.zero_()
         out = L.vk_outputs(*[bufs[k].data_ptr() for k in bufs])
         sc_dev = None
-        if scales_yx is not None:
-            sc_dev = torch.from_numpy(np.ascontiguousarray(np.asarray(torch.as_tensor(scales_yx).cpu(), dtype=np.float32).reshape(N, 2))).to(dev)
+        if sc is not None:
+            sc_dev = torch.from_numpy(sc).to(dev)
         keep = torch.zeros((N, D), dtype=torch.int64, device=dev)
         wts2 = (C.c_float * 4)(*[float(v) for v in cfg.ROI_BOX_HEAD.BBOX_REG_WEIGHTS])
         L.call("vk_roi_outputs", cls_logits.data_ptr(), cls_logits.shape[1], attr_logits.data_ptr(), attr_logits.shape[1],

@@ -43,10 +43,12 @@ class ExtractionPipeline:
     preprocess: vltk_amd.preprocess.Preprocess (or a callable (raws, ids) -> (ids, images, sizes, scales_yx))."""
 
     def __init__(self, model, preprocess, savefile, batch_size=32, visual_dim=2048, dataset=None, processor_args=None,
-                 model_config=None, group=None, depth=2, boxes=None):
+                 model_config=None, group=None, depth=2, boxes=None, ignorey=None):
         self.model, self.preprocess = model, preprocess
         # given boxes: imgid -> [K, 4] (raw-image pixels, K <= max_detections) for every image this rank sees
         self.boxes = None if boxes is None else {str(k): v for k, v in boxes.items()}
+        # ignorey bands: imgid -> [J, 2] rows (y0, y1) in raw-image pixels, J <= 64; an image without an entry has none
+        self.ignorey = None if ignorey is None else {str(k): v for k, v in ignorey.items()}
         self.B, self.F = int(batch_size), int(visual_dim)
         self.D = int(model.roi_outputs.max_detections)
         self.group = group
@@ -201,6 +203,9 @@ class ExtractionPipeline:
                 kw = {}
                 if self.boxes is not None:                    # the padding repeats of the last image repeat its boxes
                     kw["proposals"] = [self.boxes[i] for i in ids] + [self.boxes[ids[-1]]] * (self.B - n_valid)
+                if self.ignorey is not None:                  # (scales_yx takes them to the processed image, frcnn.py:331)
+                    none = np.zeros((0, 2), dtype=np.float32)
+                    kw["ignorey"] = [self.ignorey.get(i, none) for i in ids] + [self.ignorey.get(ids[-1], none)] * (self.B - n_valid)
                 if hasattr(self.model, "forward_async"):      # enqueue this batch behind the previous one, then finish that one
                     p = self.model.forward_async(images, sizes, scales_yx=scales_yx, **kw)
                 else:
