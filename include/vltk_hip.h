@@ -196,6 +196,25 @@ int vk_forward_boxes_begin(vk_handle *h, const float *images_dev, int N, int H, 
                            const float *boxes_dev, int B, const int32_t *counts,
                            const vk_outputs *out_dev, void *stream, int64_t *ticket);
 
+/* The two ends of vk_forward_boxes_begin as stage-level calls, for a binding that composes the forward itself (the FPN
+ * detector, vltk_amd/frcnn_fpn.py).  Every array is a device array; nothing is copied to or from the host.
+ * vk_given_boxes_ingest: boxes [N,B,4] f32 (rows b >= counts[n] ignored), counts [N] i32, image_hw [N,2] i32, scales_yx
+ *   [N,2] f32 or NULL -> divide by the scales, flag a non-finite box (atomic OR of 1 into *nonfinite, which the caller
+ *   zeroes), _clip_box to image_hw (frcnn.py:147-153) -> prop_boxes [N,B,4], rois [N*B,5] (batch, x0, y0, x1, y1; padding
+ *   rows zero-size at the origin), and with levels != NULL each row's level [N*B] i32 by assign_boxes_to_levels
+ *   (frcnn.py:444-460, bit-equal to vk_assign_levels on the same rois).  N >= 1, 1 <= B <= 1024.
+ * vk_given_box_outputs: vk_outputs of capacity B per image from the per-row predictions [N*B] (obj_prob / obj_cls of the
+ *   soft-max over C+1 and arg-max over C, attr_prob / attr_cls), prop_boxes times the scales, and feat [N*B, F] f32 rows;
+ *   rows b >= counts[n] are zero, preds_per_image[n] = counts[n].  F a positive multiple of 4; feat and roi_features
+ *   16-byte aligned. */
+int vk_given_boxes_ingest(const float *boxes_dev, const int32_t *counts_dev, const int32_t *image_hw_dev,
+                          const float *scales_yx_dev, int N, int B, float *prop_boxes, float *rois, int32_t *levels,
+                          int min_level, int max_level, float canonical_box_size, int canonical_level, int32_t *nonfinite,
+                          void *stream);
+int vk_given_box_outputs(const float *obj_prob, const int32_t *obj_cls, const float *attr_prob, const int32_t *attr_cls,
+                         const float *prop_boxes, const int32_t *counts_dev, const float *scales_yx_dev, const float *feat,
+                         int F, int N, int B, const vk_outputs *out_dev, void *stream);
+
 /* Intermediate tensors of the last forward, for stage-level parity tests.
  * name in {"res4","rpn_out","proposal_boxes","proposal_logits",
  * "proposal_counts","pooled","feature_pooled","obj_logits","attr_logits","chosen_deltas","keep_ids"};

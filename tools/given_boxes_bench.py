@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Images/s of region features for caller-supplied boxes (FRCNN.forward(proposals=...)) beside detection, on one GPU.
 
-    python tools/given_boxes_bench.py [--batch 32 --steps 10 --warmup 3 --ks 10,36,100 --out profiles/given_boxes_bench.json]
+    python tools/given_boxes_bench.py [--arch r101|r101-fpn --batch 32 --steps 10 --warmup 3 --ks 10,36,100 --out FILE]
 
-Per precision (fp16, fp32), in one process: detection (R = 300 proposals, up to 100 detections, as bench.py), then given
-boxes with K boxes per image for each K, on the same 800x1333 synthetic batch resident in HBM.  Every shape is warmed
+--arch r101 (default): the C4 model, detection with R = 300 proposals; --arch r101-fpn: the FPN detector (fpn_config()),
+detection with R = 1000, as `bench.py --arch r101-fpn`.  Per precision (fp16, fp32), in one process: detection (up to
+100 detections, as bench.py), then given boxes with K boxes per image for each K, on the same 800x1333 synthetic batch resident in HBM.  Every shape is warmed
 up; a timed window is `steps` forwards issued back to back (the next one enqueued before the previous one is waited for,
 as the extraction pipeline runs them) between two device synchronisations, read with a host clock.  One stage-timed
 forward per mode follows the window (HIP events; not part of the images/s).  Writes one JSON file and prints it.
@@ -54,6 +55,7 @@ def timed(m, x, hw, steps, warmup, proposals=None):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--arch", default="r101", choices=["r101", "r101-fpn"])
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--height", type=int, default=800)
     ap.add_argument("--width", type=int, default=1333)
@@ -61,23 +63,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--ks", default="10,36,100")
     ap.add_argument("--precisions", default="fp16,fp32")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "given_boxes_bench.json"))
+    ap.add_argument("--out", default=None, help="default profiles/given_boxes_bench.json (r101), given_boxes_bench_fpn.json (r101-fpn)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "given_boxes_bench.json" if a.arch == "r101" else "given_boxes_bench_fpn.json")
     import torch
-    from vltk_amd import FRCNN, make_state_dict, synthetic_images, vg_c4_config
+    from vltk_amd import FRCNN, fpn_config, make_state_dict, synthetic_images, vg_c4_config
     if not torch.cuda.is_available():
         raise SystemExit("given_boxes_bench needs a GPU")
     N, H, W = a.batch, a.height, a.width
-    cfg = vg_c4_config(post_nms_topk=300, detections=100)
+    R = 1000 if a.arch == "r101-fpn" else 300
+    cfg = fpn_config(post_nms_topk=R, detections=100) if a.arch == "r101-fpn" else vg_c4_config(post_nms_topk=R, detections=100)
     sd = make_state_dict(cfg, seed=1234)
     x = torch.from_numpy(synthetic_images(N, H, W, seed=1234)).cuda()
     hw = torch.tensor([[H, W]] * N)
     ks = [int(k) for k in a.ks.split(",")]
-    res = {"batch": N, "image": [H, W], "steps": a.steps, "warmup": a.warmup, "device": torch.cuda.get_device_name(0),
+    res = {"arch": a.arch, "batch": N, "image": [H, W], "steps": a.steps, "warmup": a.warmup, "device": torch.cuda.get_device_name(0),
            "modes": {}}
     for prec in a.precisions.split(","):
         m = FRCNN(cfg, precision=prec).load_state_dict(sd).eval()
-        r = {"detection_R300": timed(m, x, hw, a.steps, a.warmup)}
+        r = {f"detection_R{R}": timed(m, x, hw, a.steps, a.warmup)}
         for k in ks:
             props = random_boxes(N, k, H, W, seed=k).cuda()
             r[f"given_K{k}"] = timed(m, x, hw, a.steps, a.warmup, props)

@@ -92,6 +92,8 @@ SIGNATURES = {
                                       C.POINTER(C.c_int64), C.POINTER(vk_ignorey)]),
     "vk_forward_boxes_begin": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, C.POINTER(vk_outputs), _P, C.POINTER(C.c_int64)]),
     "vk_forward_end": (_I, [_P, C.c_int64]),
+    "vk_given_boxes_ingest": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _F, _I, _P, _P]),
+    "vk_given_box_outputs": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(vk_outputs), _P]),
     "vk_get_stage": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_I), C.POINTER(C.c_int64), C.POINTER(_I)]),
     "vk_memcpy_d2d": (_I, [_P, _P, _SZ, _P]),
     "vk_enable_stage_timing": (_I, [_P, _I]),

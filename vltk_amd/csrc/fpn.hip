@@ -301,10 +301,7 @@ __global__ void assign_levels_kernel(const float *__restrict__ boxes, int ld, in
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= K) return;
     const float *b = boxes + (long)k * ld;
-    const float area = (b[2] - b[0]) * (b[3] - b[1]);
-    float lv = floorf((float)canonical_level + log2f(sqrtf(area) / canonical_size + 1e-8f));
-    lv = fminf(fmaxf(lv, (float)min_level), (float)max_level);      // NaN (negative area) clamps like torch.clamp: stays NaN -> cast
-    out[k] = (int32_t)lv - min_level;
+    out[k] = box_level(b[0], b[1], b[2], b[3], min_level, max_level, canonical_size, canonical_level);
 }
 
 template <typename T>

@@ -1,9 +1,11 @@
-// Region features for caller-supplied boxes on gfx950: the two ends of vk_forward_boxes_begin.  The RoI pool, the Res5
-// head and the box predictor between them are the detection path's own launches (model.hip fwd_head).
+// Region features for caller-supplied boxes on gfx950: the two ends of vk_forward_boxes_begin (C4), and of the FPN
+// detector's host-composed given-box forward (vk_given_boxes_ingest / vk_given_box_outputs, the ingest with levels).  The
+// RoI pool, the head and the box predictor between them are the detection path's own launches.
 //
 // Replaces (reference vltk/modeling/frcnn.py), for boxes given instead of the RPN's proposals:
 //   _clip_box (assert finite, clamp to the image)                  :147-153
 //   convert_boxes_to_pooler_format                                 :426-441
+//   assign_boxes_to_levels (FPN form only, box_level)              :444-460
 //   ROIOutputs._predict_objs / _predict_attrs, the scales multiply :1252-1260, :1280-1283
 // with every box kept, in input order: no box regression and no NMS (do_nms :116-143 is not applied).
 //
@@ -14,13 +16,22 @@ namespace vk {
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
+// The pyramid-level rule of the FPN form of the ingest (box_level, vk_common.h); unused in the C4 form.
+struct LevelRule {
+    int32_t *levels;
+    int min_level, max_level;
+    float canonical_size;
+    int canonical_level;
+};
+
 // One thread per (n, b) of the [N, B] box grid.  Rows b >= counts[n] are padding: a zero box in prop_boxes and a
-// zero-size RoI at the image origin (in-image for RoIPool, its features are never returned).
-__global__ __launch_bounds__(256) void given_boxes_ingest_kernel(const float *__restrict__ boxes, const int32_t *__restrict__ counts,
-                                                                 const int32_t *__restrict__ image_hw,
-                                                                 const float *__restrict__ scales_yx, int B, int total,
-                                                                 float *__restrict__ prop_boxes, float *__restrict__ rois,
-                                                                 int32_t *__restrict__ nonfinite) {
+// zero-size RoI at the image origin (in-image for RoIPool / RoIAlign, its features are never returned).  LEVELS: also
+// the row's pyramid level, from the clipped box (padding rows: the lowest level).
+template <bool LEVELS>
+__device__ __forceinline__ void ingest_row(const float *__restrict__ boxes, const int32_t *__restrict__ counts,
+                                           const int32_t *__restrict__ image_hw, const float *__restrict__ scales_yx, int B,
+                                           int total, float *__restrict__ prop_boxes, float *__restrict__ rois,
+                                           int32_t *__restrict__ nonfinite, const LevelRule &lr) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= total) return;
     const int n = k / B, b = k - n * B;
@@ -56,6 +67,27 @@ __global__ __launch_bounds__(256) void given_boxes_ingest_kernel(const float *__
     r[2] = y0;
     r[3] = x1;
     r[4] = y1;
+    if constexpr (LEVELS)   // assign_boxes_to_levels frcnn.py:444-460 on the RoI row just written
+        lr.levels[k] = box_level(x0, y0, x1, y1, lr.min_level, lr.max_level, lr.canonical_size, lr.canonical_level);
+}
+
+// the C4 model's ingest (RoIPool on res4: no levels)
+__global__ __launch_bounds__(256) void given_boxes_ingest_kernel(const float *__restrict__ boxes, const int32_t *__restrict__ counts,
+                                                                 const int32_t *__restrict__ image_hw,
+                                                                 const float *__restrict__ scales_yx, int B, int total,
+                                                                 float *__restrict__ prop_boxes, float *__restrict__ rois,
+                                                                 int32_t *__restrict__ nonfinite) {
+    ingest_row<false>(boxes, counts, image_hw, scales_yx, B, total, prop_boxes, rois, nonfinite, LevelRule{});
+}
+
+// the FPN detector's ingest (RoIAlign over p2..p5: one level per row)
+__global__ __launch_bounds__(256) void given_boxes_ingest_levels_kernel(const float *__restrict__ boxes,
+                                                                        const int32_t *__restrict__ counts,
+                                                                        const int32_t *__restrict__ image_hw,
+                                                                        const float *__restrict__ scales_yx, int B, int total,
+                                                                        float *__restrict__ prop_boxes, float *__restrict__ rois,
+                                                                        int32_t *__restrict__ nonfinite, LevelRule lr) {
+    ingest_row<true>(boxes, counts, image_hw, scales_yx, B, total, prop_boxes, rois, nonfinite, lr);
 }
 
 // One 128-thread workgroup per output row (b, n): the row's scalars from thread 0, its F-float feature row with 16-byte
@@ -123,6 +155,19 @@ int launch_given_boxes_ingest(const float *boxes, const int32_t *counts, const i
     return VK_OK;
 }
 
+int launch_given_boxes_ingest_levels(const float *boxes, const int32_t *counts, const int32_t *image_hw, const float *scales_yx,
+                                     int N, int B, float *prop_boxes, float *rois, int32_t *levels, int min_level, int max_level,
+                                     float canonical_size, int canonical_level, int32_t *nonfinite, hipStream_t s) {
+    VK_REQUIRE(N >= 1 && B >= 1 && B <= 1024, VK_EINVAL, "given_boxes_ingest: N=%d B=%d", N, B);
+    VK_REQUIRE(min_level <= max_level, VK_EINVAL, "given_boxes_ingest: levels %d..%d", min_level, max_level);
+    const int total = N * B;
+    const LevelRule lr{levels, min_level, max_level, canonical_size, canonical_level};
+    hipLaunchKernelGGL(given_boxes_ingest_levels_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, boxes, counts, image_hw,
+                       scales_yx, B, total, prop_boxes, rois, nonfinite, lr);
+    VK_CHECK_HIP(hipGetLastError());
+    return VK_OK;
+}
+
 int launch_given_box_outputs(const float *obj_prob, const int32_t *obj_cls, const float *attr_prob, const int32_t *attr_cls,
                              const float *prop_boxes, const int32_t *counts, const float *scales_yx, const float *feat, int F,
                              int N, int B, const vk_outputs &out, hipStream_t s) {
@@ -135,3 +180,36 @@ int launch_given_box_outputs(const float *obj_prob, const int32_t *obj_cls, cons
 }
 
 }  // namespace vk
+
+// ---- the two ends as C entry points, for callers that compose the forward themselves (the FPN detector, frcnn_fpn.py) ----
+extern "C" {
+
+int vk_given_boxes_ingest(const float *boxes, const int32_t *counts, const int32_t *image_hw, const float *scales_yx, int N, int B,
+                          float *prop_boxes, float *rois, int32_t *levels, int min_level, int max_level, float canonical_box_size,
+                          int canonical_level, int32_t *nonfinite, void *stream) {
+    VK_REQUIRE(boxes && counts && image_hw && prop_boxes && rois && nonfinite, VK_EINVAL, "given_boxes_ingest: null argument");
+    VK_REQUIRE(N >= 1 && B >= 1 && B <= 1024, VK_EINVAL, "given_boxes_ingest: N=%d must be >= 1 and B=%d in 1..1024", N, B);
+    if (!levels)
+        return vk::launch_given_boxes_ingest(boxes, counts, image_hw, scales_yx, N, B, prop_boxes, rois, nonfinite, (hipStream_t)stream);
+    VK_REQUIRE(min_level <= max_level, VK_EINVAL, "given_boxes_ingest: min_level=%d > max_level=%d", min_level, max_level);
+    return vk::launch_given_boxes_ingest_levels(boxes, counts, image_hw, scales_yx, N, B, prop_boxes, rois, levels, min_level,
+                                                max_level, canonical_box_size, canonical_level, nonfinite, (hipStream_t)stream);
+}
+
+int vk_given_box_outputs(const float *obj_prob, const int32_t *obj_cls, const float *attr_prob, const int32_t *attr_cls,
+                         const float *prop_boxes, const int32_t *counts, const float *scales_yx, const float *feat, int F, int N,
+                         int B, const vk_outputs *out, void *stream) {
+    VK_REQUIRE(obj_prob && obj_cls && attr_prob && attr_cls && prop_boxes && counts && feat && out, VK_EINVAL,
+               "given_box_outputs: null argument");
+    VK_REQUIRE(out->obj_ids && out->obj_probs && out->attr_ids && out->attr_probs && out->boxes && out->preds_per_image &&
+                   out->roi_features,
+               VK_EINVAL, "given_box_outputs: null output array");
+    VK_REQUIRE(N >= 1 && B >= 1 && B <= 1024, VK_EINVAL, "given_box_outputs: N=%d must be >= 1 and B=%d in 1..1024", N, B);
+    VK_REQUIRE(F > 0 && F % 4 == 0, VK_EINVAL, "given_box_outputs: F=%d must be a positive multiple of 4", F);
+    VK_REQUIRE((((uintptr_t)feat | (uintptr_t)out->roi_features) & 15) == 0, VK_EINVAL,
+               "given_box_outputs: feat and roi_features must be 16-byte aligned");
+    return vk::launch_given_box_outputs(obj_prob, obj_cls, attr_prob, attr_cls, prop_boxes, counts, scales_yx, feat, F, N, B, *out,
+                                        (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -190,10 +190,26 @@ int launch_chosen_deltas(const void *x, int ldx, const void *w, const float *bia
 int launch_roi_final(RoiFinalArgs &a, int N, hipStream_t s);
 int launch_make_rois(const float *boxes, int N, int R, float *rois, hipStream_t s);
 
-// ---- given_boxes.hip (vk_forward_boxes_begin) ----
+// assign_boxes_to_levels frcnn.py:444-460 for one box: floor(canonical_level + log2(sqrt(area) / canonical_size + 1e-8)),
+// clamped to [min_level, max_level], minus min_level.  The one copy of the rule: fpn.hip's assign_levels_kernel and
+// given_boxes.hip's ingest both call it, and both files build with -ffp-contract=off, so their levels are bit-equal.
+__device__ __forceinline__ int32_t box_level(float x0, float y0, float x1, float y1, int min_level, int max_level,
+                                             float canonical_size, int canonical_level) {
+    const float area = (x1 - x0) * (y1 - y0);
+    float lv = floorf((float)canonical_level + log2f(sqrtf(area) / canonical_size + 1e-8f));
+    lv = fminf(fmaxf(lv, (float)min_level), (float)max_level);      // NaN (negative area) clamps like torch.clamp: stays NaN -> cast
+    return (int32_t)lv - min_level;
+}
+
+// ---- given_boxes.hip (vk_forward_boxes_begin, vk_given_boxes_ingest, vk_given_box_outputs) ----
 // boxes [N,B,4] (rows >= counts[n] ignored) -> / scales_yx -> non-finite flag -> _clip_box -> prop_boxes [N,B,4], rois [N*B,5]
 int launch_given_boxes_ingest(const float *boxes, const int32_t *counts, const int32_t *image_hw, const float *scales_yx, int N,
                               int B, float *prop_boxes, float *rois, int32_t *nonfinite, hipStream_t s);
+// the same, plus each row's pyramid level (box_level of the clipped box) into levels [N*B]: the FPN detector's RoI input
+// in one launch (in place of vk_make_rois + vk_assign_levels)
+int launch_given_boxes_ingest_levels(const float *boxes, const int32_t *counts, const int32_t *image_hw, const float *scales_yx,
+                                     int N, int B, float *prop_boxes, float *rois, int32_t *levels, int min_level, int max_level,
+                                     float canonical_size, int canonical_level, int32_t *nonfinite, hipStream_t s);
 // vk_outputs [N,B] from the per-row predictions, the clipped boxes times the scales and the feature rows
 int launch_given_box_outputs(const float *obj_prob, const int32_t *obj_cls, const float *attr_prob, const int32_t *attr_cls,
                              const float *prop_boxes, const int32_t *counts, const float *scales_yx, const float *feat, int F,

@@ -245,7 +245,7 @@ class PendingForward:
 
 
 class FRCNN:
-    given_boxes = True                   # forward(proposals=...): region features for caller-supplied boxes (C4 only)
+    given_boxes = True                   # forward(proposals=...): region features for caller-supplied boxes
 
     def __new__(cls, cfg=None, *a, **k):
         # several RPN input levels = the FPN detector (frcnn_fpn.py, a build extension); one = the reference's C4 model
@@ -397,12 +397,12 @@ class FRCNN:
         """kwargs (v1.0.0 semantics): max_detections, return_tensors {"np","pt",None},
         padding {None,"max_detections","max_batch"}, pad_value, location {"cuda","cpu"}.
 
-        proposals (C4 model): region features for caller-supplied boxes instead of detection.  A sequence of N
+        proposals (C4 and FPN models): region features for caller-supplied boxes instead of detection.  A sequence of N
         [K_i, 4] arrays / tensors (x0, y0, x1, y1; 0 <= K_i <= 1024) or one [N, K, 4] tensor, in the frame of the
         returned `boxes`: network-input pixels, or original-image pixels when `scales_yx` is given (x is divided by
         scales_yx[n][1], y by scales_yx[n][0] on the device).  Every box is kept, in input order: clipped to
         image_shapes[n] (_clip_box frcnn.py:147-153; a non-finite box raises its AssertionError), RoI-pooled, run through
-        the Res5 head (roi_features) and the box predictor (obj_probs / obj_ids: max / arg-max of the soft-max over the
+        the Res5 head (the FPN model: RoIAlign by level and the FC head) (roi_features) and the box predictor (obj_probs / obj_ids: max / arg-max of the soft-max over the
         first C classes; attr_probs / attr_ids on that class); `boxes` = the clipped box times the scales, with no box
         regression and no NMS; preds_per_image[n] = K_i.  roi_outputs.{nms_thresh, min_detections, max_detections}
         are not used; the output width is max K_i, and an explicit max_detections below it raises ValueError.

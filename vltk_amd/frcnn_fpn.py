@@ -20,7 +20,7 @@ import torch
 
 from . import _lib as L
 from .config import CONFIG_NAME, WEIGHTS_NAME, Config          # noqa: F401
-from .frcnn import FRCNN, ROIOutputs, _TORCH_DT, pack_ignorey
+from .frcnn import FRCNN, ROIOutputs, _TORCH_DT, check_given_width, pack_ignorey, pack_proposals
 from .parallel import OutputBlock, output_spec
 from .weights import BLOCKS_PER_STAGE, fpn_layer_spec
 
@@ -163,19 +163,22 @@ class _Bottleneck:
 class _Done:
     """A forward that has already finished (this model runs its forward synchronously)."""
 
-    def __init__(self, model, block, hw):
+    def __init__(self, model, block, hw, given_width=None):
         self.model, self.block, self.hw = model, block, hw
+        self.given_width = given_width      # given boxes: the output width (max boxes per image); None for detection
 
     def wait_raw(self):
         return self.block
 
     def wait(self, **kwargs):
+        if self.given_width is not None:
+            check_given_width(self.given_width, kwargs.get("max_detections"))
         return FRCNN._format(self.block, self.hw, **kwargs)
 
 
 class FRCNNFPN(FRCNN):
     STAGES = ("res2", "res3", "res4", "res5")
-    given_boxes = False                  # forward(proposals=...) raises NotImplementedError (forward_async)
+    given_boxes = True                   # forward(proposals=...): region features for caller-supplied boxes (DESIGN §12)
 
     def __init__(self, cfg, precision=None, device=None):
         if not torch.cuda.is_available():
@@ -323,10 +326,12 @@ class FRCNNFPN(FRCNN):
 
     # ---- forward ----
     def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None):
+        """Detection, or with `proposals` region features for exactly those boxes (FRCNN.forward).  The forward
+        runs to its end here; the returned handle's wait() / wait_raw() only format / hand out the outputs."""
         if self.training:
             raise NotImplementedError()
-        if proposals is not None:
-            raise NotImplementedError("precomputed proposals are not supported")
+        if ignorey is not None and proposals is not None:
+            raise ValueError("ignorey removes / trims RPN proposals: there are none with proposals=")
         if not self._finalized:
             raise RuntimeError("no weights loaded: call load_state_dict / from_pretrained first")
         images = torch.as_tensor(images)
@@ -335,6 +340,8 @@ class FRCNNFPN(FRCNN):
         sc = None
         if scales_yx is not None:
             sc = np.ascontiguousarray(np.asarray(torch.as_tensor(scales_yx).cpu(), dtype=np.float32).reshape(images.shape[0], 2))
+        if proposals is not None:
+            return self._forward_boxes(images, image_shapes, proposals, sc)
         ig = pack_ignorey(ignorey, sc, images.shape[0]) if ignorey is not None else None     # before anything is enqueued
         images = images.to(device=self.device, dtype=torch.float32).contiguous()
         N, _, H, W = images.shape
@@ -345,39 +352,9 @@ class FRCNNFPN(FRCNN):
         evs = [] if self._timing is not None else None
         st = self._stages = {}
         self._mark(evs)
-        # ---- bottom-up ----
-        ho, wo = C.c_int(), C.c_int()
-        L.load().vk_stem_out_hw(H, W, int(bool(cfg.MODEL.MAX_POOL)), C.byref(ho), C.byref(wo))
-        x = torch.empty((N, ho.value, wo.value, self.stem_c), dtype=self.tdt, device=dev)
-        nb = L.load().vk_stem_workspace_bytes(N, H, W, self.stem_c, self.dt)
-        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-        L.call("vk_stem", images.data_ptr(), N, H, W, self.stem_w.data_ptr(), self.stem_b.data_ptr(), self.stem_c,
-               int(bool(cfg.MODEL.MAX_POOL)), x.data_ptr(), self.dt, ws.data_ptr(), nb, s)
-        feats = []
-        for name, blocks in zip(self.STAGES, self.stages):
-            for blk in blocks:
-                x = blk(x)
-            feats.append(x)
-            st[name] = x
+        feats = self._bottom_up(images, st)
         self._mark(evs)
-        # ---- neck (detectron2 FPN; top block LastLevelMaxPool frcnn.py:825-836) ----
-        prev = self.lateral[3](feats[3])
-        pyr = [self.output[3](prev)]
-        for i in (2, 1, 0):
-            lat = self.lateral[i](feats[i])
-            n_, h_, w_, c_ = lat.shape
-            y = torch.empty_like(lat)
-            L.call("vk_upsample2x_add", lat.data_ptr(), prev.data_ptr(), y.data_ptr(), n_, h_, w_, prev.shape[1], prev.shape[2], c_, self.dt, s)
-            prev = y
-            pyr.insert(0, self.output[i](prev))
-        if len(cfg.RPN.IN_FEATURES) == 5:
-            p5 = pyr[-1]
-            n_, h_, w_, c_ = p5.shape
-            p6 = torch.empty((n_, (h_ - 1) // 2 + 1, (w_ - 1) // 2 + 1, c_), dtype=self.tdt, device=dev)
-            L.call("vk_subsample2", p5.data_ptr(), p6.data_ptr(), n_, h_, w_, c_, self.dt, s)
-            pyr.append(p6)
-        for i, p_ in enumerate(pyr):
-            st[f"p{i + 2}"] = p_
+        pyr = self._neck(feats, st, len(cfg.RPN.IN_FEATURES) == 5)
         self._mark(evs)
         # ---- RPN head over every level ----
         A, nl = self.A, len(pyr)
@@ -417,34 +394,15 @@ class FRCNNFPN(FRCNN):
         L.call("vk_make_rois", pb.data_ptr(), N, R, rois.data_ptr(), s)
         lv = torch.zeros(K, dtype=torch.int32, device=dev)
         L.call("vk_assign_levels", rois.data_ptr() + 4, 5, K, 2, 5, 224.0, 4, lv.data_ptr(), s)
-        P, fc = int(cfg.ROI_BOX_HEAD.POOLER_RESOLUTION), pyr[0].shape[3]
-        pooled = torch.empty((K, P, P, fc), dtype=self.tdt, device=dev)
-        maps = (C.c_void_p * 4)(*[p_.data_ptr() for p_ in pyr[:4]])
-        L.call("vk_roi_align", maps, (C.c_int32 * 4)(*[p_.shape[1] for p_ in pyr[:4]]), (C.c_int32 * 4)(*[p_.shape[2] for p_ in pyr[:4]]),
-               (C.c_float * 4)(1 / 4, 1 / 8, 1 / 16, 1 / 32), 4, N, fc, rois.data_ptr(), lv.data_ptr(), K, P,
-               int(cfg.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO), 1, pooled.data_ptr(), self.dt, s)
-        st["pooled"], st["levels"] = pooled, lv
-        x = pooled.view(K, P * P * fc)
-        for i, fcl in enumerate(self.fcs):
-            x = fcl(x, relu=True, out_f32=(i + 1 == len(self.fcs)))
-        feat = x                                                                              # [K, FC_DIM] f32 = roi_features
-        st["box_features"] = feat
+        feat = self._box_head(pyr, rois, lv, N, K, st)                                         # [K, FC_DIM] f32 = roi_features
         self._mark(evs)
         # ---- predictor (FastRCNNOutputLayers.forward :1726-1740) ----
-        F_, Cn, At, E = feat.shape[1], int(cfg.ROI_HEADS.NUM_CLASSES), int(cfg.ROI_BOX_HEAD.NUM_ATTRS), self.emb.shape[1]
-        cls_logits = self.cls_score(feat, out_f32=True)
-        obj_prob = torch.empty(K, dtype=torch.float32, device=dev)
-        obj_cls = torch.empty(K, dtype=torch.int32, device=dev)
-        max_class = torch.empty(K, dtype=torch.int32, device=dev)
-        L.call("vk_softmax_argmax", cls_logits.data_ptr(), cls_logits.shape[1], K, Cn + 1, Cn, obj_prob.data_ptr(), obj_cls.data_ptr(),
-               max_class.data_ptr(), s)
-        cat = torch.empty((K, F_ + E), dtype=torch.float32, device=dev)
-        L.call("vk_concat_embed", feat.data_ptr(), F_, self.emb.data_ptr(), E, max_class.data_ptr(), K, cat.data_ptr(), L.VK_F32, s)
-        attr_logits = self.attr_score(self.fc_attr(cat, relu=True), out_f32=True)
+        F_, Cn, At = feat.shape[1], int(cfg.ROI_HEADS.NUM_CLASSES), int(cfg.ROI_BOX_HEAD.NUM_ATTRS)
+        cls_logits, obj_prob, obj_cls, attr_logits = self._predictor(feat, K, st)
         chosen = torch.empty((K, 4), dtype=torch.float32, device=dev)
         L.call("vk_chosen_deltas", feat.data_ptr(), F_, self.bbox_w.data_ptr(), self.bbox_b.data_ptr(), obj_cls.data_ptr(),
                int(bool(cfg.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG)), F_, K, chosen.data_ptr(), L.VK_F32, s)
-        st["obj_logits"], st["attr_logits"], st["chosen_deltas"] = cls_logits, attr_logits, chosen
+        st["chosen_deltas"] = chosen
         # ---- outputs (ROIOutputs.inference :1262-1294) ----
         ro = self.roi_outputs
         D = int(ro.max_detections)
@@ -476,3 +434,147 @@ class FRCNNFPN(FRCNN):
             raise AssertionError("Box tensor contains infinite or NaN!")          # frcnn.py:148
         self._last_padded = bufs
         return _Done(self, bufs, hw)
+
+    def _forward_boxes(self, images, image_shapes, proposals, sc):
+        """Region features for caller-supplied boxes (FRCNN.forward's `proposals`): bottom-up -> neck (no P6) ->
+        vk_given_boxes_ingest (scale, finite check, _clip_box, RoI rows and levels in one launch) -> RoIAlign -> FCs ->
+        cls_score / soft-max -> attribute branch -> vk_given_box_outputs.  No RPN head, proposals, box regression or NMS."""
+        cfg, dev = self.config, self.device
+        N = images.shape[0]
+        boxes, counts = pack_proposals(proposals, N, dev)              # ValueError on a bad shape, before anything runs
+        if int(cfg.ROI_BOX_HEAD.FC_DIM) % 4:
+            raise ValueError(f"given boxes need ROI_BOX_HEAD.FC_DIM a multiple of 4, got {int(cfg.ROI_BOX_HEAD.FC_DIM)}")
+        images = images.to(device=dev, dtype=torch.float32).contiguous()
+        _, _, H, W = images.shape
+        hw = np.ascontiguousarray(np.asarray(torch.as_tensor(image_shapes).cpu()).reshape(N, 2), dtype=np.int32)
+        if (hw < 1).any():
+            raise ValueError("image_shapes must be positive")
+        B, F_ = boxes.shape[1], (self.fcs[-1].nout + 7) // 8 * 8              # F_: the feature row width, as detection's
+        bufs = OutputBlock(output_spec(N, B, F_), device=dev)
+        st = self._stages = {}
+        if B == 0:                                  # every image is empty: nothing to compute, no stage events
+            bufs["preds_per_image"].zero_()
+            if self._timing is not None:
+                self._timing.pop("ev", None)
+            self._last_padded = bufs
+            return _Done(self, bufs, hw, given_width=0)
+        s = self._stream()
+        evs = [] if self._timing is not None else None
+        # counts | image_hw | scales_yx: one host-to-device copy
+        meta = np.zeros(N * (3 if sc is None else 5), dtype=np.int32)
+        meta[:N], meta[N:3 * N] = counts, hw.reshape(-1)
+        if sc is not None:
+            meta[3 * N:] = sc.reshape(-1).view(np.int32)
+        meta_dev = torch.from_numpy(meta).to(dev)
+        cnt_dev, hw_dev = meta_dev[:N], meta_dev[N:3 * N]
+        sc_ptr = meta_dev[3 * N:].data_ptr() if sc is not None else None
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._mark(evs)
+        feats = self._bottom_up(images, st)
+        self._mark(evs)
+        pyr = self._neck(feats, st, False)
+        self._mark(evs)
+        self._mark(evs)                             # no RPN head
+        # ---- the caller's boxes in place of the proposals: scale, finite check, _clip_box (frcnn.py:147-153), RoI rows, levels ----
+        K = N * B
+        pb = torch.empty((N, B, 4), dtype=torch.float32, device=dev)
+        rois = torch.empty((K, 5), dtype=torch.float32, device=dev)
+        lv = torch.empty(K, dtype=torch.int32, device=dev)
+        L.call("vk_given_boxes_ingest", boxes.data_ptr(), cnt_dev.data_ptr(), hw_dev.data_ptr(), sc_ptr, N, B, pb.data_ptr(),
+               rois.data_ptr(), lv.data_ptr(), 2, 5, 224.0, 4, flag.data_ptr(), s)
+        st["proposal_boxes"], st["proposal_counts"] = pb, cnt_dev
+        self._mark(evs)
+        feat = self._box_head(pyr, rois, lv, N, K, st)
+        self._mark(evs)
+        _, obj_prob, obj_cls, attr_logits = self._predictor(feat, K, st)
+        At = int(cfg.ROI_BOX_HEAD.NUM_ATTRS)
+        attr_prob = torch.empty(K, dtype=torch.float32, device=dev)
+        attr_cls = torch.empty(K, dtype=torch.int32, device=dev)
+        L.call("vk_softmax_argmax", attr_logits.data_ptr(), attr_logits.shape[1], K, At, At, attr_prob.data_ptr(),
+               attr_cls.data_ptr(), None, s)                                                # _predict_attrs :1257-1260
+        out = L.vk_outputs(*[bufs[k].data_ptr() for k in bufs])
+        L.call("vk_given_box_outputs", obj_prob.data_ptr(), obj_cls.data_ptr(), attr_prob.data_ptr(), attr_cls.data_ptr(),
+               pb.data_ptr(), cnt_dev.data_ptr(), sc_ptr, feat.data_ptr(), F_, N, B, C.byref(out), s)
+        self._mark(evs)
+        if evs is not None:
+            self._timing["ev"] = evs
+        if int(flag.cpu()) != 0:
+            raise AssertionError("Box tensor contains infinite or NaN!")          # frcnn.py:148
+        self._last_padded = bufs
+        return _Done(self, bufs, hw, given_width=B)
+
+    # ---- the stages shared by detection and given boxes ----
+    def _bottom_up(self, images, st):
+        """stem + res2..res5 (build_backbone frcnn.py:200-261 with res5 as a backbone stage) -> [C2, C3, C4, C5] NHWC."""
+        cfg, dev, s = self.config, self.device, self._stream()
+        N, _, H, W = images.shape
+        ho, wo = C.c_int(), C.c_int()
+        L.load().vk_stem_out_hw(H, W, int(bool(cfg.MODEL.MAX_POOL)), C.byref(ho), C.byref(wo))
+        x = torch.empty((N, ho.value, wo.value, self.stem_c), dtype=self.tdt, device=dev)
+        nb = L.load().vk_stem_workspace_bytes(N, H, W, self.stem_c, self.dt)
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+        L.call("vk_stem", images.data_ptr(), N, H, W, self.stem_w.data_ptr(), self.stem_b.data_ptr(), self.stem_c,
+               int(bool(cfg.MODEL.MAX_POOL)), x.data_ptr(), self.dt, ws.data_ptr(), nb, s)
+        feats = []
+        for name, blocks in zip(self.STAGES, self.stages):
+            for blk in blocks:
+                x = blk(x)
+            feats.append(x)
+            st[name] = x
+        return feats
+
+    def _neck(self, feats, st, p6):
+        """detectron2 FPN top-down path -> [P2..P5] (+ P6 by the top block LastLevelMaxPool frcnn.py:825-836)."""
+        s = self._stream()
+        prev = self.lateral[3](feats[3])
+        pyr = [self.output[3](prev)]
+        for i in (2, 1, 0):
+            lat = self.lateral[i](feats[i])
+            n_, h_, w_, c_ = lat.shape
+            y = torch.empty_like(lat)
+            L.call("vk_upsample2x_add", lat.data_ptr(), prev.data_ptr(), y.data_ptr(), n_, h_, w_, prev.shape[1], prev.shape[2], c_, self.dt, s)
+            prev = y
+            pyr.insert(0, self.output[i](prev))
+        if p6:
+            p5 = pyr[-1]
+            n_, h_, w_, c_ = p5.shape
+            p6 = torch.empty((n_, (h_ - 1) // 2 + 1, (w_ - 1) // 2 + 1, c_), dtype=self.tdt, device=self.device)
+            L.call("vk_subsample2", p5.data_ptr(), p6.data_ptr(), n_, h_, w_, c_, self.dt, s)
+            pyr.append(p6)
+        for i, p_ in enumerate(pyr):
+            st[f"p{i + 2}"] = p_
+        return pyr
+
+    def _box_head(self, pyr, rois, lv, N, K, st):
+        """RoIAlign 7x7 over P2..P5 by level (ROIPooler.forward's level loop :1200-1224) -> fc1 -> fc2: [K, FC_DIM] f32."""
+        cfg = self.config
+        P, fc = int(cfg.ROI_BOX_HEAD.POOLER_RESOLUTION), pyr[0].shape[3]
+        pooled = torch.empty((K, P, P, fc), dtype=self.tdt, device=self.device)
+        maps = (C.c_void_p * 4)(*[p_.data_ptr() for p_ in pyr[:4]])
+        L.call("vk_roi_align", maps, (C.c_int32 * 4)(*[p_.shape[1] for p_ in pyr[:4]]), (C.c_int32 * 4)(*[p_.shape[2] for p_ in pyr[:4]]),
+               (C.c_float * 4)(1 / 4, 1 / 8, 1 / 16, 1 / 32), 4, N, fc, rois.data_ptr(), lv.data_ptr(), K, P,
+               int(cfg.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO), 1, pooled.data_ptr(), self.dt, self._stream())
+        st["pooled"], st["levels"] = pooled, lv
+        x = pooled.view(K, P * P * fc)
+        for i, fcl in enumerate(self.fcs):
+            x = fcl(x, relu=True, out_f32=(i + 1 == len(self.fcs)))
+        st["box_features"] = x
+        return x
+
+    def _predictor(self, feat, K, st):
+        """cls_score -> soft-max over C+1 (obj_prob / obj_cls over the first C, the raw arg-max class) -> the attribute
+        branch on the raw arg-max class (FastRCNNOutputLayers.forward :1726-1740).  -> (cls_logits, obj_prob, obj_cls,
+        attr_logits)."""
+        cfg, dev, s = self.config, self.device, self._stream()
+        F_, Cn, E = feat.shape[1], int(cfg.ROI_HEADS.NUM_CLASSES), self.emb.shape[1]
+        cls_logits = self.cls_score(feat, out_f32=True)
+        obj_prob = torch.empty(K, dtype=torch.float32, device=dev)
+        obj_cls = torch.empty(K, dtype=torch.int32, device=dev)
+        max_class = torch.empty(K, dtype=torch.int32, device=dev)
+        L.call("vk_softmax_argmax", cls_logits.data_ptr(), cls_logits.shape[1], K, Cn + 1, Cn, obj_prob.data_ptr(), obj_cls.data_ptr(),
+               max_class.data_ptr(), s)
+        cat = torch.empty((K, F_ + E), dtype=torch.float32, device=dev)
+        L.call("vk_concat_embed", feat.data_ptr(), F_, self.emb.data_ptr(), E, max_class.data_ptr(), K, cat.data_ptr(), L.VK_F32, s)
+        attr_logits = self.attr_score(self.fc_attr(cat, relu=True), out_f32=True)
+        st["obj_logits"], st["attr_logits"] = cls_logits, attr_logits
+        return cls_logits, obj_prob, obj_cls, attr_logits
