@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of FRCNN feature extraction (BASELINE.json metric) on N MI355X of one node.
 
-    python bench.py [--gpus N --steps K --warmup W --dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W --dump-outputs DIR --full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Called plainly with --gpus N > 1 (no WORLD_SIZE in the environment) the process starts the N ranks itself, as children
@@ -16,6 +16,12 @@ completed inside the timed region.  Images shard across ranks
 --dump-outputs DIR: after the timed steps, rank 0 writes the arrays the last timed step returned (the gathered output
 block: obj_ids, obj_probs, attr_ids, attr_probs, boxes, preds_per_image, roi_features) as DIR/<name>.npy, so that two
 builds run with the same arguments (same seeded weights and images) can be compared output for output.
+
+A plain run sets up, warms up, times the K steps, dumps (if asked) and prints the headline line: nothing else.
+--full adds what takes runs of its own, all after the timed steps: the breakdown pass (the K steps again with a HIP event
+pair around every conv launch and every stage) and the `roofline` record built from it, and on rank 0 the `parity` record
+(r101; --no-parity skips it) and, for the C4 models on one GPU, the `cpu_baseline` (the oracle on the CPU; --no-cpu-baseline
+skips it).
 """
 import argparse
 import json
@@ -84,6 +90,71 @@ def stage_fractions(st, B, R, arch):
             e["frac_of_mfma_peak"] = round(gf[k] / ms / PEAK_F16_TFLOPS, 4)
         out[k] = e
     return out
+
+
+def fpn_roofline(st, a, B, world, dt):
+    """--full, FPN detector: the whole forward's algorithmic flops over the headline step time, and per stage over the
+    breakdown pass's stage timers `st` (the detector is composed on the host from stage-level C-ABI calls: no per-kernel buckets)."""
+    gf = fpn_gflop_per_image(a.proposals)
+    tot = sum(gf.values())
+    stages = {}
+    for k, ms in st.items():
+        e = {"ms": round(float(ms), 3)}
+        if k in gf and ms > 0:
+            e["tflops"] = round(gf[k] * B / ms, 1)
+            e["frac_of_mfma_peak"] = round(gf[k] * B / ms / PEAK_F16_TFLOPS, 4)
+        stages[k] = e
+    ach = tot * world * B * a.steps / dt / 1e3
+    return {"bound": "mfma", "achieved": round(ach / world, 2), "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(ach / world / PEAK_F16_TFLOPS, 4), "traffic": None,
+            "kernel": "whole forward (algorithmic conv / GEMM flops of the model over the step time; this path has stage "
+                      "timers only)",
+            "alg_gflop_per_image": {k: round(v, 1) for k, v in dict(gf, total=tot).items()},
+            "stages_last_step": stages}
+
+
+def c4_roofline(kt, st, a, B, dt_timers):
+    """--full, C4 models: the kernel with the most GPU time in the breakdown pass (per-launch timers `kt`), every conv
+    kernel, the last step's stages `st`, and the committed PMC figures of the dominant kernel with their source files."""
+    # res3 / res4 run as two half-batches on two streams: those launches overlap in time (their summed durations are
+    # not wall time), so they are reported apart and the per-kernel figures cover the launches that ran alone
+    conc = kt.pop("two_stream_backbone")
+    dom_key = max(kt, key=lambda k: kt[k]["ms"])          # the kernel with the most GPU time in the timed region
+    dom = kt[dom_key]
+    dom_name, dom_desc = KERNEL_NAMES[dom_key]
+    ach = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
+    traffic, traffic_src, traffic_alg, traffic_sym = pmc_traffic(B, a.proposals, dom_name)
+    mfma_busy, mfma_src = pmc_mfma(dom_name)
+    all_ms = sum(v["ms"] for v in kt.values())
+    all_fl = sum(v["flops"] for v in kt.values())
+    return {"bound": "mfma", "achieved": round(ach, 2), "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(ach / PEAK_F16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
+            # `traffic` covers the launches the PMC filter selects (e.g. the Res5 conv2 launches of the panel kernel);
+            # traffic_alg_bytes are the algorithmic bytes of exactly those, alg_bytes_per_launch the average over ALL launches
+            "traffic_launches": traffic_sym, "traffic_alg_bytes": traffic_alg,
+            "mfma_busy": mfma_busy, "mfma_busy_source": mfma_src,
+            # the chip runs this step at its package power limit (DESIGN.md 6b): what f16 MFMA SUSTAINS on random operands,
+            # measured by tools/micro/mfma_power.hip -- `peak` / `frac` stay the nominal issue peak of the guide
+            "power_limited_sustained_tflops": POWER_CEILING,
+            "alg_bytes_per_launch": round(dom["bytes"] / max(dom["launches"], 1)),
+            "alg_gflop_per_launch": round(dom["flops"] / max(dom["launches"], 1) / 1e9, 2),
+            "kernel": f"{dom_name} ({dom_desc}, f16 in / f32 acc; all its launches in the timed region)",
+            "launches": dom["launches"], "avg_launch_ms": round(dom["ms"] / max(dom["launches"], 1), 5),
+            "alg_gflop_per_image": round(conv_gflop_per_image(a.proposals, a.arch), 1),
+            "per_kernel": {KERNEL_NAMES[k][0] + ("" if k in ("conv_mfma256", "conv3x3_panel", "conv_duo", "conv3x3_blk", "conv_ws", "conv_mfma256_dual", "conv_gemm4", "bneck64") else ":" + k):
+                           {"launches": v["launches"], "ms_per_step": round(v["ms"] / a.steps, 3),
+                            "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1)}
+                           for k, v in kt.items() if v["ms"] > 0},
+            "two_stream_backbone_launches": {"launches": conc["launches"], "summed_ms_per_step": round(conc["ms"] / a.steps, 3),
+                                             "gflop_per_step": round(conc["flops"] / a.steps / 1e9, 1),
+                                             "note": "res3/res4 half-batches on two streams; durations overlap, see "
+                                                     "stages_last_step.backbone for their wall time"},
+            "stages_last_step": stage_fractions(st, B, a.proposals, a.arch),
+            "all_conv_kernels_that_ran_alone": {"ms_per_step": round(all_ms / a.steps, 3),
+                                                "tflops": round(all_fl / (all_ms * 1e-3) / 1e12, 2) if all_ms else 0.0,
+                                                "share_of_step": round(all_ms / (dt_timers * 1e3), 4)},
+            "note": "per-kernel and per-stage figures are from the breakdown pass (timers on), value / ms_per_step "
+                    "from the headline pass (timers off)"}
 
 
 PMC_TRAFFIC_FILES = ("r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json")
@@ -272,6 +343,17 @@ def cpu_baseline(cfg, sd, R, det, seed, n_images=4, repeats=3):
                       f"{[int(v) for v in out['preds_per_image']]} detections"}
 
 
+def side_records(a, world):
+    """The records --full adds on rank 0 beside the roofline: `parity` for r101 (the golden fixture and the strict mode
+    are C4 ResNet-101), `cpu_baseline` for the C4 models on one GPU (the CPU oracle is C4 only: no FPN model)."""
+    recs = []
+    if a.arch == "r101" and not a.no_parity:
+        recs.append("parity")
+    if a.arch != "r101-fpn" and world == 1 and not a.no_cpu_baseline:
+        recs.append("cpu_baseline")
+    return recs
+
+
 DUMP_LIMIT_BYTES = 64 << 20
 
 
@@ -361,8 +443,11 @@ def main():
                     help="RPN.POST_NMS_TOPK_TEST = RoIs through the box head (default 300; 1000 for r101-fpn)")
     ap.add_argument("--detections", type=int, default=100)
     ap.add_argument("--head-chunk", type=int, default=-1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the fp16-vs-fp32 parity record (a few seconds, outside the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the breakdown pass with per-launch timers (ms_per_step_with_timers, roofline), "
+                         "the parity record (r101) and the CPU baseline (C4 models) (off by default: a plain run reports the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (the C4 oracle on 4 images)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the fp16-vs-fp32 parity record (a few seconds, outside the timed region)")
     ap.add_argument("--arch", default="r101", choices=["r101", "x152", "r101-fpn"],
                     help="r101 = the BASELINE workload (configs[1], C4: the model the reference has); x152 = ResNeXt-152 32x8d C4 "
                          "(SURVEY.md 8d config c4, extra); r101-fpn = the FPN detector (build extension, UNPINNED vs the reference, extra)")
@@ -479,120 +564,65 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     dumped = dump_outputs(out, a.dump_outputs) if a.dump_outputs and rank == 0 else None
-    # breakdown pass (outside the headline): the same steps again with a HIP event pair around every conv launch and
-    # every stage; its own wall time is reported as ms_per_step_with_timers
-    model.enable_kernel_timing(True)
-    model.enable_stage_timing(True)
-    model.kernel_timing(reset=True)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(a.steps):
-        step()
-    drain()
-    barrier()
-    dt_timers = time.perf_counter() - t1
+    assert out["roi_features"].shape[0] == world * B
+    dt_timers = None
+    if a.full:
+        # breakdown pass (outside the headline): the same steps again with a HIP event pair around every conv launch and
+        # every stage; its own wall time is reported as ms_per_step_with_timers
+        model.enable_kernel_timing(True)
+        model.enable_stage_timing(True)
+        model.kernel_timing(reset=True)
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(a.steps):
+            step()
+        drain()
+        barrier()
+        dt_timers = time.perf_counter() - t1
     n_ranks_seen = dist.get_world_size() if use_pg else 1
     if use_pg:
-        t = torch.tensor([dt, dt_timers], dtype=torch.float64, device=f"cuda:{local_rank}")
+        t = torch.tensor([dt, dt_timers or 0.0], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, dt_timers = float(t[0].item()), float(t[1].item())
-    kt = model.kernel_timing()
-    st = model.stage_timing_ms()                 # HIP events of the LAST step's stages (backbone / RPN head / proposals / RoI heads / outputs)
-    assert out["roi_features"].shape[0] == world * B
+        dt = float(t[0].item())
+        if a.full:
+            dt_timers = float(t[1].item())
 
-    if rank == 0 and a.arch == "r101-fpn":
-        # the FPN detector is composed on the host from stage-level C-ABI calls: stage timers only (no per-kernel buckets)
-        gf = fpn_gflop_per_image(a.proposals)
-        tot = sum(gf.values())
-        stages = {}
-        for k, ms in st.items():
-            e = {"ms": round(float(ms), 3)}
-            if k in gf and ms > 0:
-                e["tflops"] = round(gf[k] * B / ms, 1)
-                e["frac_of_mfma_peak"] = round(gf[k] * B / ms / PEAK_F16_TFLOPS, 4)
-            stages[k] = e
-        ach = tot * world * B * a.steps / dt / 1e3
+    if rank == 0:
+        if a.arch == "r101-fpn":
+            workload = ("EXTRA, UNPINNED vs the reference (it has no FPN model, SURVEY.md D1): ResNet-101-FPN Faster R-CNN fp16 "
+                        f"(detectron2 layout: FPN neck, RPN over P2-P6, RoIAlign 7x7, 2-FC box head), {B} synthetic 800x1333 "
+                        f"images per GPU per step, R={a.proposals} proposals, max {a.detections} detections/img, seeded synthetic weights")
+        else:
+            workload = (("configs[1]: ResNet-101-C4 fp16" if a.arch == "r101" else "EXTRA (SURVEY.md 8d c4): ResNeXt-152 32x8d C4 fp16") +
+                        " (the reference has no FPN: SURVEY.md D1), "
+                        f"{B} synthetic 800x1333 images per GPU per step, R={a.proposals} RPN proposals "
+                        f"through the Res5 head, max {a.detections} detections/img, seeded synthetic weights")
         line = {
             "metric": "images/sec FRCNN feature extraction, 800x1333 batch",
             "value": round(world * B * a.steps / dt, 3), "unit": "images/sec", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
-            "ms_per_step_with_timers": round(dt_timers / a.steps * 1e3, 3), "n_ranks_seen": n_ranks_seen,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
-            "config": {"workload": "EXTRA, UNPINNED vs the reference (it has no FPN model, SURVEY.md D1): ResNet-101-FPN Faster R-CNN fp16 "
-                                   f"(detectron2 layout: FPN neck, RPN over P2-P6, RoIAlign 7x7, 2-FC box head), {B} synthetic 800x1333 "
-                                   f"images per GPU per step, R={a.proposals} proposals, max {a.detections} detections/img, seeded synthetic weights",
-                       "global_batch": world * B, "parallelism": f"image-sharded x{world}, all-gather of output blocks"},
-            "roofline": {"bound": "mfma", "achieved": round(ach / world, 2), "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(ach / world / PEAK_F16_TFLOPS, 4), "traffic": None,
-                         "kernel": "whole forward (algorithmic conv / GEMM flops of the model over the step time; this path has stage "
-                                   "timers only)",
-                         "alg_gflop_per_image": {k: round(v, 1) for k, v in dict(gf, total=tot).items()},
-                         "stages_last_step": stages},
-        }
-        if dumped:
-            line["dump_outputs"] = dumped
-        sys.stdout.flush()
-        os.write(json_fd, (json.dumps(line) + "\n").encode())
-    elif rank == 0:
-        # res3 / res4 run as two half-batches on two streams: those launches overlap in time (their summed durations are
-        # not wall time), so they are reported apart and the per-kernel figures cover the launches that ran alone
-        conc = kt.pop("two_stream_backbone")
-        dom_key = max(kt, key=lambda k: kt[k]["ms"])          # the kernel with the most GPU time in the timed region
-        dom = kt[dom_key]
-        dom_name, dom_desc = KERNEL_NAMES[dom_key]
-        ach = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
-        traffic, traffic_src, traffic_alg, traffic_sym = pmc_traffic(B, a.proposals, dom_name)
-        mfma_busy, mfma_src = pmc_mfma(dom_name)
-        all_ms = sum(v["ms"] for v in kt.values())
-        all_fl = sum(v["flops"] for v in kt.values())
-        line = {
-            "metric": "images/sec FRCNN feature extraction, 800x1333 batch",
-            "value": round(world * B * a.steps / dt, 3), "unit": "images/sec", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
-            "ms_per_step_with_timers": round(dt_timers / a.steps * 1e3, 3), "n_ranks_seen": n_ranks_seen,
-            "higher_is_better": True,
+            **({"ms_per_step_with_timers": round(dt_timers / a.steps * 1e3, 3)} if a.full else {}),
+            "n_ranks_seen": n_ranks_seen, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
-            "config": {"workload": ("configs[1]: ResNet-101-C4 fp16" if a.arch == "r101" else "EXTRA (SURVEY.md 8d c4): ResNeXt-152 32x8d C4 fp16") +
-                                   " (the reference has no FPN: SURVEY.md D1), "
-                                   f"{B} synthetic 800x1333 images per GPU per step, R={a.proposals} RPN proposals "
-                                   f"through the Res5 head, max {a.detections} detections/img, seeded synthetic weights",
-                       "global_batch": world * B, "parallelism": f"image-sharded x{world}, all-gather of output blocks"},
-            "roofline": {"bound": "mfma", "achieved": round(ach, 2), "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(ach / PEAK_F16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                         # `traffic` covers the launches the PMC filter selects (e.g. the Res5 conv2 launches of the panel kernel);
-                         # traffic_alg_bytes are the algorithmic bytes of exactly those, alg_bytes_per_launch the average over ALL launches
-                         "traffic_launches": traffic_sym, "traffic_alg_bytes": traffic_alg,
-                         "mfma_busy": mfma_busy, "mfma_busy_source": mfma_src,
-                         # the chip runs this step at its package power limit: what f16 MFMA SUSTAINS on random operands,
-                         # measured by tools/micro/mfma_power.hip -- `peak` / `frac` stay the nominal issue peak of the guide
-                         "power_limited_sustained_tflops": POWER_CEILING,
-                         "alg_bytes_per_launch": round(dom["bytes"] / max(dom["launches"], 1)),
-                         "alg_gflop_per_launch": round(dom["flops"] / max(dom["launches"], 1) / 1e9, 2),
-                         "kernel": f"{dom_name} ({dom_desc}, f16 in / f32 acc; all its launches in the timed region)",
-                         "launches": dom["launches"], "avg_launch_ms": round(dom["ms"] / max(dom["launches"], 1), 5),
-                         "alg_gflop_per_image": round(conv_gflop_per_image(a.proposals, a.arch), 1),
-                         "per_kernel": {KERNEL_NAMES[k][0] + ("" if k in ("conv_mfma256", "conv3x3_panel", "conv_duo", "conv3x3_blk", "conv_ws", "conv_mfma256_dual", "conv_gemm4", "bneck64") else ":" + k):
-                                        {"launches": v["launches"], "ms_per_step": round(v["ms"] / a.steps, 3),
-                                         "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1)}
-                                        for k, v in kt.items() if v["ms"] > 0},
-                         "two_stream_backbone_launches": {"launches": conc["launches"], "summed_ms_per_step": round(conc["ms"] / a.steps, 3),
-                                                          "gflop_per_step": round(conc["flops"] / a.steps / 1e9, 1),
-                                                          "note": "res3/res4 half-batches on two streams; durations overlap, see "
-                                                                  "stages_last_step.backbone for their wall time"},
-                         "stages_last_step": stage_fractions(st, B, a.proposals, a.arch),
-                         "all_conv_kernels_that_ran_alone": {"ms_per_step": round(all_ms / a.steps, 3),
-                                              "tflops": round(all_fl / (all_ms * 1e-3) / 1e12, 2) if all_ms else 0.0,
-                                              "share_of_step": round(all_ms / (dt_timers * 1e3), 4)},
-                         "note": "per-kernel and per-stage figures are from the breakdown pass (timers on), value / ms_per_step "
-                                 "from the headline pass (timers off)"},
+            "config": {"workload": workload, "global_batch": world * B,
+                       "parallelism": f"image-sharded x{world}, all-gather of output blocks"},
         }
-        if a.arch == "r101" and not a.no_parity:
-            try:
-                line["parity"] = parity_record(f"cuda:{local_rank}")
-            except Exception as e:          # never lose the bench line to the side record
-                line["parity"] = {"error": repr(e)}
-        if world == 1 and not a.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(cfg, sd, a.proposals, a.detections, seed=0xF2C)
+        if a.full:
+            # HIP events of the breakdown pass: every conv launch, and the LAST step's stages (backbone / RPN head /
+            # proposals / RoI heads / outputs)
+            kt, st = model.kernel_timing(), model.stage_timing_ms()
+            if a.arch == "r101-fpn":
+                line["roofline"] = fpn_roofline(st, a, B, world, dt)
+            else:
+                line["roofline"] = c4_roofline(kt, st, a, B, dt_timers)
+            recs = side_records(a, world)
+            if "parity" in recs:
+                try:
+                    line["parity"] = parity_record(f"cuda:{local_rank}")
+                except Exception as e:          # never lose the bench line to the side record
+                    line["parity"] = {"error": repr(e)}
+            if "cpu_baseline" in recs:
+                line["cpu_baseline"] = cpu_baseline(cfg, sd, a.proposals, a.detections, seed=0xF2C)
         if dumped:
             line["dump_outputs"] = dumped
         sys.stdout.flush()

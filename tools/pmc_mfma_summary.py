@@ -67,7 +67,7 @@ rows.sort(key=lambda r: -r["gpu_ms"])
 for r in rows[:top]:
     print(f"{r['kernel']:70s} n={r['dispatches']:4d} gpu_ms={r['gpu_ms']:9.3f} mfma_busy={r['mfma_busy_frac']} clock_ghz={r['effective_clock_ghz']}")
 if "--json" in sys.argv:
-    out = {"command": "rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -- python3 bench.py --steps 1 --warmup 0 "
+    out = {"command": "rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -- python3 bench.py --full --steps 1 --warmup 0 "
                       "--no-cpu-baseline --no-parity",
            "formulas": {"mfma_busy_frac": "SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 * 1024 SIMDs)",
                         "effective_clock_ghz": "GRBM_GUI_ACTIVE / 8 / dispatch duration (profiled passes clock 2-5 % below un-profiled ones)"},
