@@ -290,10 +290,23 @@ int vk_conv1x1_dual(const void *x1, int cin1, const void *x2, int cin2, long M,
  * intermediates stay in LDS (rounded to f16 there, as the layer-by-layer path rounds them in HBM), x is read once.
  * proj == 0: identity shortcut, cin == 256, w3 = conv3's packed rows [256][64].  proj != 0: projection shortcut of block 0,
  * cin == 64, w3 = [conv3 row | shortcut row] per output channel and b3 = the two folded biases summed (vk_conv1x1_dual's
- * layout).  w1 [>=64][cin], w2 [>=64][9*64] as vk_pack_conv_weight writes them.  x [N,H,W,cin], y [N,H,W,256]; N*H*W*512 < 2^31. */
+ * layout).  w1 [>=64][cin], w2 [>=64][9*64] as vk_pack_conv_weight writes them.  x [N,H,W,cin], y [N,H,W,256];
+ * N*H*W*512 < 2^32 - 2^20. */
 int vk_bottleneck64(const void *x, int N, int H, int W, int cin, int proj,
                     const void *w1_packed, const float *b1_packed, const void *w2_packed, const float *b2_packed,
                     const void *w3_packed, const float *b3_packed, void *y, void *stream);
+
+/* Host-only dispatch rules of a BottleneckBlock, asked by the C4 model and by callers that compose the backbone themselves
+ * (the FPN detector, vltk_amd/frcnn_fpn.py), so that both run the same kernels for the same block.
+ * vk_fuse_shortcut: 1 when conv3 (input cin channels) and a projection shortcut (input cin_shortcut channels) run as one
+ * dual-source GEMM (vk_conv1x1_dual): f16, stride-1 block, cout % 256 == 0, both inputs multiples of 32 channels; 0 with
+ * VK_NO_FUSED_SHORTCUT set.
+ * vk_bottleneck64_eligible: 1 when the block runs as vk_bottleneck64 on its input [N,H,W,cin]: cmid bottleneck channels,
+ * stride = conv1's times conv2's, conv2's dilation and groups, proj = a projection shortcut and fused_shortcut = that
+ * vk_fuse_shortcut said yes for it; 0 with VK_BNECK_FUSED=0. */
+int vk_fuse_shortcut(int cin, int cin_shortcut, int cout, int stride, vk_dtype dt);
+int vk_bottleneck64_eligible(int cin, int cmid, int cout, int stride, int dil, int groups, int proj, int fused_shortcut,
+                             long N, int H, int W, vk_dtype dt);
 
 /* Last Res5 conv3 with the RoI's spatial mean folded into its epilogue (`res5(x).mean(dim=[2,3])`, frcnn.py:1401):
  * out_mean[n][c] = mean over the HW rows of image n of relu?(x . W^T + bias + residual), summed EXACTLY (integer

@@ -47,6 +47,44 @@ def test_stem_geometry(lib):
     assert (ho.value, wo.value) == (40, 56)
 
 
+
+def _resnet101_blocks(H, W):
+    """(stage, block, cin, bottleneck width, cout, stride, projection, input H, input W) of every res2..res5 block of
+    ResNet-101 behind a stem that gives H x W."""
+    cin = 64
+    for name, n, mid, cout, stride in (("res2", 3, 64, 256, 1), ("res3", 4, 128, 512, 2), ("res4", 23, 256, 1024, 2),
+                                       ("res5", 3, 512, 2048, 2)):
+        for b in range(n):
+            s = stride if b == 0 else 1
+            yield name, b, cin, mid, cout, s, b == 0, H, W
+            H, W, cin = (H - 1) // s + 1, (W - 1) // s + 1, cout
+
+
+@pytest.mark.parametrize("dt", [L.VK_F16, L.VK_F32], ids=["fp16", "fp32"])
+def test_block_rules_resnet101(lib, dt, monkeypatch):
+    """The two block predicates the C4 model and the FPN detector both ask, for every ResNet-101 block of a
+    32 x 800 x 1333 batch (the FPN detector's stem: 200 x 334 into res2): in fp16 res2.0's projection shortcut is part of
+    conv3's GEMM (the other stages start with stride 2) and res2's three blocks run as vk_bottleneck64; in fp32 neither."""
+    for v in ("VK_BNECK_FUSED", "VK_BNECK_ROWS", "VK_NO_FUSED_SHORTCUT"):
+        monkeypatch.delenv(v, raising=False)
+    ho, wo = C.c_int(), C.c_int()
+    lib.vk_stem_out_hw(800, 1333, 0, C.byref(ho), C.byref(wo))
+    fused, whole = set(), set()
+    for name, b, cin, mid, cout, s, proj, H, W in _resnet101_blocks(ho.value, wo.value):
+        f = proj and lib.vk_fuse_shortcut(mid, cin, cout, s, dt) == 1
+        if f:
+            fused.add((name, b))
+        if lib.vk_bottleneck64_eligible(cin, mid, cout, s, 1, 1, int(proj), int(f), 32, H, W, dt):
+            whole.add((name, b))
+    f16 = dt == L.VK_F16
+    assert fused == ({("res2", 0)} if f16 else set())
+    assert whole == ({("res2", 0), ("res2", 1), ("res2", 2)} if f16 else set())
+    # the row form's 32-bit offsets: 64 images of 200 x 334 (2.19 GB of res2 map) still fit, 128 do not
+    assert lib.vk_bottleneck64_eligible(256, 64, 256, 1, 1, 1, 0, 0, 64, 200, 334, dt) == int(f16)
+    assert lib.vk_bottleneck64_eligible(256, 64, 256, 1, 1, 1, 0, 0, 128, 200, 334, dt) == 0
+    monkeypatch.setenv("VK_BNECK_FUSED", "0")
+    assert lib.vk_bottleneck64_eligible(256, 64, 256, 1, 1, 1, 0, 0, 32, 200, 334, dt) == 0
+
 def _half_bits(a):
     return np.asarray(a, dtype=np.float16).view(np.uint16)
 

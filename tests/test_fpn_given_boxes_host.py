@@ -104,7 +104,7 @@ def _host_only_model():
 
     def launched(*a, **k):
         pytest.fail("a device stage was reached")
-    m._bottom_up = m._neck = m._box_head = m._predictor = launched
+    m._bottom_up = m.neck = m._box_head = m._predictor = launched
     return m
 
 

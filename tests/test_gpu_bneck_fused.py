@@ -13,7 +13,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from vltk_amd import _lib as L                        # noqa: E402
-from vltk_amd import FRCNN, make_state_dict, synthetic_images, vg_c4_config   # noqa: E402
+from vltk_amd import FRCNN, fpn_config, make_state_dict, synthetic_images, vg_c4_config   # noqa: E402
 
 import gpu_util as G                                   # noqa: E402
 
@@ -163,11 +163,19 @@ def test_bottleneck64_beyond_two_gigabytes():
         assert torch.equal(y[n:n + 1], y1), n
 
 
-@pytest.mark.parametrize("case", ["three_ragged", "one_small", "two_full_size"])
+@pytest.mark.parametrize("case", ["three_ragged", "one_small", "two_full_size", "fpn"])
 def test_model_with_and_without_the_fused_block(case, monkeypatch):
     """The whole forward with res2 on the fused kernel (default) and on the layer-by-layer kernels (VK_BNECK_FUSED=0):
-    identical outputs and res4 -- a ragged batch, a single small image, and two images at the bench's size (800 x 1333, ResNet-101)."""
-    if case == "two_full_size":
+    identical outputs and res4 -- a ragged batch, a single small image, and two images at the bench's size (800 x 1333, ResNet-101)
+    -- and on the FPN detector identical outputs and res2..res5."""
+    stages = ("res4",)
+    if case == "fpn":
+        cfg = fpn_config(depth=50, post_nms_topk=200, pre_nms_topk=300, detections=10)
+        sd = make_state_dict(cfg, seed=3)
+        x = torch.from_numpy(synthetic_images(2, 320, 448, seed=5))
+        shapes = torch.tensor([[320, 448], [300, 400]])
+        stages = ("res2", "res3", "res4", "res5")
+    elif case == "two_full_size":
         cfg = vg_c4_config(post_nms_topk=300, detections=100)
         sd = make_state_dict(cfg, seed=1234)
         x = torch.from_numpy(synthetic_images(2, 800, 1333, seed=0xF2C))
@@ -185,10 +193,11 @@ def test_model_with_and_without_the_fused_block(case, monkeypatch):
     m = FRCNN(cfg, precision="fp16").load_state_dict(sd).eval()
     m(x, shapes)
     a = {k: v.clone() for k, v in m.forward_padded().items()}
-    r4 = m.get_stage("res4")
+    st = {k: m.get_stage(k).clone() for k in stages}
     monkeypatch.setenv("VK_BNECK_FUSED", "0")
     m(x, shapes)
     b = m.forward_padded()
-    assert torch.equal(r4, m.get_stage("res4"))
+    for k in stages:
+        assert torch.equal(st[k], m.get_stage(k)), k
     for k in a:
         assert torch.equal(a[k], b[k]), k

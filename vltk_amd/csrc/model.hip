@@ -329,17 +329,10 @@ static int pack_conv_host(vk_handle *h, const ConvLayer &L, std::vector<char> &p
     return vk_pack_conv_weight(w->data.data(), bn.data(), nullptr, L.cout, L.cin, L.k, L.k, L.groups, h->dt, packed.data(), pb.data());
 }
 
-// The same rule is restated in oracle/frcnn_oracle.py (fp16 emulation): keep the two in step.
-static bool can_fuse_shortcut(const vk_handle *h, const Block &b) {
-    static const bool off = getenv("VK_NO_FUSED_SHORTCUT") != nullptr;      // A/B switch
-    return !off && h->dt == VK_F16 && b.has_shortcut && b.shortcut.stride == 1 && b.conv3.cout % 256 == 0 &&
-           b.conv3.cin % 32 == 0 && b.shortcut.cin % 32 == 0;
-}
-
 static int finalize_block(vk_handle *h, Block &b) {
     VK_TRY(finalize_conv(h, b.conv1));
     VK_TRY(finalize_conv(h, b.conv2));
-    b.fused_shortcut = can_fuse_shortcut(h, b);
+    b.fused_shortcut = b.has_shortcut && vk_fuse_shortcut(b.conv3.cin, b.shortcut.cin, b.conv3.cout, b.shortcut.stride, h->dt);
     if (!b.fused_shortcut) {
         if (b.has_shortcut) VK_TRY(finalize_conv(h, b.shortcut));
         return finalize_conv(h, b.conv3);
@@ -573,8 +566,8 @@ static int run_block(vk_handle *h, const Block &b, const void *x, int N, int H, 
         N = nb;
     }
     // res2: the whole block as one kernel (bneck_fused.hip) -- x is read once, t1 / t2 never leave the CU
-    if (h->dt == VK_F16 && !pool_part && b.conv1.stride == 1 && b.conv2.stride == 1 && b.conv2.dil == 1 && (!b.has_shortcut || b.fused_shortcut) &&
-        bneck_fused_eligible(b.conv1.cin, b.conv1.cout, b.conv3.cout, 1, b.conv2.groups, b.has_shortcut, N, H, W, h->dt)) {
+    if (!pool_part && vk_bottleneck64_eligible(b.conv1.cin, b.conv1.cout, b.conv3.cout, b.conv1.stride * b.conv2.stride, b.conv2.dil,
+                                               b.conv2.groups, b.has_shortcut, b.fused_shortcut, N, H, W, h->dt)) {
         if (Ho) *Ho = H;
         if (Wo) *Wo = W;
         return launch_bneck_fused(x, N, H, W, b.conv1.cin, b.has_shortcut, b.conv1.w, b.conv1.b, b.conv2.w, b.conv2.b, b.conv3.w, b.conv3.b, y,
@@ -778,6 +771,18 @@ int vk_linear(const void *x, long M, int K, const void *w_packed, const float *b
     a.dt = dt;
     a.out_dt = out_dt;
     return launch_conv(a, (hipStream_t)stream);
+}
+
+// The fused-shortcut rule is restated in oracle/frcnn_oracle.py (fp16 emulation): keep the two in step.
+int vk_fuse_shortcut(int cin, int cin_shortcut, int cout, int stride, vk_dtype dt) {
+    static const bool off = getenv("VK_NO_FUSED_SHORTCUT") != nullptr;      // A/B switch
+    return !off && dt == VK_F16 && stride == 1 && cout % 256 == 0 && cin % 32 == 0 && cin_shortcut % 32 == 0;
+}
+
+int vk_bottleneck64_eligible(int cin, int cmid, int cout, int stride, int dil, int groups, int proj, int fused_shortcut, long N,
+                             int H, int W, vk_dtype dt) {
+    return stride == 1 && dil == 1 && (!proj || fused_shortcut) &&
+           bneck_fused_eligible(cin, cmid, cout, stride, groups, proj != 0, N, H, W, dt);
 }
 
 int vk_bottleneck64(const void *x, int N, int H, int W, int cin, int proj, const void *w1, const float *b1, const void *w2,

@@ -21,6 +21,7 @@ import torch
 
 from . import _lib as L
 from .config import CONFIG_NAME, WEIGHTS_NAME, Config
+from .layers import DTYPES, TORCH_DTYPES, stream
 from .parallel import OutputBlock, output_spec
 
 
@@ -34,8 +35,20 @@ class ROIOutputs:
         nms_thresh = cfg.ROI_HEADS.NMS_THRESH_TEST
         self.nms_thresh = list(nms_thresh) if isinstance(nms_thresh, (list, tuple)) else [nms_thresh]
 
+    def params(self):
+        """The knobs as the library's vk_roi_params; ValueError beyond VK_MAX_NMS_THRESH thresholds."""
+        thr = list(self.nms_thresh)
+        if len(thr) > L.VK_MAX_NMS_THRESH:
+            raise ValueError(f"at most {L.VK_MAX_NMS_THRESH} NMS thresholds")
+        rp = L.vk_roi_params()
+        rp.num_nms_thresh = len(thr)
+        for i, t in enumerate(thr):
+            rp.nms_thresh[i] = float(t)
+        rp.min_detections, rp.max_detections = int(self.min_detections), int(self.max_detections)
+        return rp
 
-def _c_config(cfg, precision):
+
+def _c_config(cfg, dt):
     c = L.vk_config()
     r = cfg.RESNETS
     c.depth, c.num_groups, c.width_per_group = r.DEPTH, r.NUM_GROUPS, r.WIDTH_PER_GROUP
@@ -64,11 +77,9 @@ def _c_config(cfg, precision):
     c.cls_agnostic_bbox_reg = int(bool(cfg.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG))
     for i, v in enumerate(cfg.ROI_BOX_HEAD.BBOX_REG_WEIGHTS):
         c.roi_bbox_weights[i] = v
-    c.precision = {"fp16": L.VK_F16, "fp32": L.VK_F32}[precision]
+    c.precision = dt
     return c
 
-
-_TORCH_DT = {L.VK_F32: torch.float32, L.VK_F16: torch.float16, L.VK_I64: torch.int64, L.VK_I32: torch.int32}
 
 MAX_GIVEN_BOXES = 1024          # boxes per image of vk_forward_boxes_begin
 
@@ -213,6 +224,13 @@ class PendingForward:
         self.model, self._state, self.hw = model, state, hw
         self.given_width = given_width      # given boxes: the output width (max boxes per image); None for detection
 
+    @classmethod
+    def finished(cls, model, block, hw, given_width=None):
+        """A handle over a forward that has already run to its end (the FPN detector's forward is synchronous)."""
+        st = _Ticket(-1, block, None)
+        st.done = True
+        return cls(model, st, hw, given_width)
+
     @property
     def ticket(self):
         return self._state.ticket
@@ -255,6 +273,13 @@ class FRCNN:
         return object.__new__(cls)
 
     def __init__(self, cfg, precision=None, device=None):
+        self._init_host(cfg, precision, device)
+        self._h = C.c_void_p()
+        L.call("vk_create", C.byref(_c_config(cfg, self.dt)), self.device.index, C.byref(self._h))
+
+    def _init_host(self, cfg, precision, device):
+        """What the C4 model and the FPN detector (frcnn_fpn.py) set up alike: the GPU and library checks, the device, the
+        precision, ROIOutputs and the forward bookkeeping."""
         if not torch.cuda.is_available():
             raise RuntimeError("vltk_amd.FRCNN needs an AMD GPU (HIP device); there is no CPU fallback")
         L.load()
@@ -262,17 +287,16 @@ class FRCNN:
         self.min_detections = cfg.min_detections
         self.max_detections = cfg.max_detections
         dev = torch.device(device if device is not None else cfg.MODEL.DEVICE)
-        if dev.type != "cuda":
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if dev.index is None:
+        if dev.type != "cuda" or dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
         self.device = dev
         self.precision = precision or os.environ.get("VLTK_AMD_PRECISION", "fp16")
+        if self.precision not in ("fp16", "fp32"):
+            raise KeyError(self.precision)
+        self.dt, self.tdt = DTYPES[self.precision]
         self.roi_outputs = ROIOutputs(cfg)
         self.training = False
-        self._h = C.c_void_p()
         self._open = []                # _Ticket of every forward in flight, oldest first
-        L.call("vk_create", C.byref(_c_config(cfg, self.precision)), dev.index, C.byref(self._h))
         self._finalized = False
 
     # ---- nn.Module-like surface -----------------------------------------
@@ -381,11 +405,9 @@ class FRCNN:
         shape = (C.c_int64 * 4)()
         L.call("vk_get_stage", self._h, name.encode(), C.byref(ptr), C.byref(dt), shape, C.byref(nd))
         shp = [int(shape[i]) for i in range(nd.value)]
-        tdt = _TORCH_DT[dt.value]
-        out = torch.empty(shp, dtype=tdt, device=self.device)
+        out = torch.empty(shp, dtype=TORCH_DTYPES[dt.value], device=self.device)
         nbytes = out.numel() * out.element_size()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.call("vk_memcpy_d2d", out.data_ptr(), ptr.value, nbytes, C.c_void_p(stream))
+        L.call("vk_memcpy_d2d", out.data_ptr(), ptr.value, nbytes, stream(self.device))
         torch.cuda.synchronize(self.device)
         return out
 
@@ -416,11 +438,10 @@ class FRCNN:
             check_given_width(int(counts.max(initial=0)), kwargs.get("max_detections"))
         return self.forward_async(images, image_shapes, gt_boxes, proposals, scales_yx, ignorey).wait(**kwargs)
 
-    def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None):
-        """Enqueue a forward and return at once (vk_forward_begin, or vk_forward_boxes_begin with `proposals`, see
-        forward()); `.wait(**kwargs)` on the returned handle finishes it (vk_forward_end) and formats the outputs like
-        forward().  Up to four may be in flight, detection and given-box forwards mixed; they must be waited for in
-        order, on the same stream.  The caller must not modify `images` (or the proposals) before wait() returns."""
+    def _prepare(self, images, image_shapes, proposals, scales_yx, ignorey):
+        """The argument checks and host-side parsing both detectors' forward_async start with; nothing is enqueued.
+        -> (images [N,3,H,W] f32 on the device, image_shapes int32 [N,2], scales_yx f32 [N,2] or None, pack_proposals'
+        (boxes, counts) or None, pack_ignorey's result or None)."""
         if self.training:
             raise NotImplementedError()            # frcnn.py:1930-1931
         if ignorey is not None and proposals is not None:
@@ -434,47 +455,45 @@ class FRCNN:
         sc = None
         if scales_yx is not None:
             sc = np.ascontiguousarray(np.asarray(torch.as_tensor(scales_yx).cpu(), dtype=np.float32).reshape(N, 2))
-        ig = pack_ignorey(ignorey, sc, N) if ignorey is not None else None        # before anything is enqueued
+        ig = pack_ignorey(ignorey, sc, N) if ignorey is not None else None
+        given = pack_proposals(proposals, N, self.device) if proposals is not None else None
         images = images.to(device=self.device, dtype=torch.float32).contiguous()
-        N, _, H, W = images.shape
         hw = np.ascontiguousarray(np.asarray(torch.as_tensor(image_shapes).cpu()).reshape(N, 2), dtype=np.int32)
+        return images, hw, sc, given, ig
+
+    def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None):
+        """Enqueue a forward and return at once (vk_forward_begin, or vk_forward_boxes_begin with `proposals`, see
+        forward()); `.wait(**kwargs)` on the returned handle finishes it (vk_forward_end) and formats the outputs like
+        forward().  Up to four may be in flight, detection and given-box forwards mixed; they must be waited for in
+        order, on the same stream.  The caller must not modify `images` (or the proposals) before wait() returns."""
+        images, hw, sc, given, ig = self._prepare(images, image_shapes, proposals, scales_yx, ignorey)
+        N, _, H, W = images.shape
         F = self.config.RESNETS.RES2_OUT_CHANNELS * 8
-        dev = self.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        dev, s = self.device, stream(self.device)
+        scp = sc.ctypes.data_as(C.c_void_p) if sc is not None else None
         ticket = C.c_int64(-1)
-        if proposals is not None:
-            boxes, counts = pack_proposals(proposals, N, dev)
+        if given is not None:
+            boxes, counts = given
             B = boxes.shape[1]
             bufs = OutputBlock(output_spec(N, B, F), device=dev)
             out = L.vk_outputs(*[bufs[k].data_ptr() for k in bufs])
-            L.call("vk_forward_boxes_begin", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p),
-                   sc.ctypes.data_as(C.c_void_p) if sc is not None else None, boxes.data_ptr() if B else None, B,
-                   counts.ctypes.data_as(C.c_void_p), C.byref(out), C.c_void_p(stream), C.byref(ticket))
+            L.call("vk_forward_boxes_begin", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p), scp,
+                   boxes.data_ptr() if B else None, B, counts.ctypes.data_as(C.c_void_p), C.byref(out), s, C.byref(ticket))
             st = _Ticket(ticket.value, bufs, (images, boxes))
             self._open.append(st)
             return PendingForward(self, st, hw, given_width=B)
-        ro = self.roi_outputs
-        D = int(ro.max_detections)
-        rp = L.vk_roi_params()
-        thr = list(ro.nms_thresh)
-        rp.num_nms_thresh = len(thr)
-        if len(thr) > L.VK_MAX_NMS_THRESH:
-            raise ValueError(f"at most {L.VK_MAX_NMS_THRESH} NMS thresholds")
-        for i, t in enumerate(thr):
-            rp.nms_thresh[i] = float(t)
-        rp.min_detections, rp.max_detections = int(ro.min_detections), D
+        rp = self.roi_outputs.params()
         # one flat block, the seven arrays are views (so the multi-GPU exchange is a single all-gather: parallel.py)
-        bufs = OutputBlock(output_spec(N, D, F), device=dev)
+        bufs = OutputBlock(output_spec(N, rp.max_detections, F), device=dev)
         out = L.vk_outputs(*[bufs[k].data_ptr() for k in bufs])
         if ig is None:
-            L.call("vk_forward_begin", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p),
-                   sc.ctypes.data_as(C.c_void_p) if sc is not None else None, C.byref(rp), C.byref(out),
-                   C.c_void_p(stream), C.byref(ticket))
+            L.call("vk_forward_begin", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p), scp, C.byref(rp),
+                   C.byref(out), s, C.byref(ticket))
         else:                                      # the host bands are copied into the ticket's slot before the call returns
             bands, bcounts, f64 = ig
             igs = L.vk_ignorey(bands.ctypes.data, bcounts.ctypes.data, bands.shape[1], int(f64))
-            L.call("vk_forward_begin_ignorey", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p),
-                   sc.ctypes.data_as(C.c_void_p), C.byref(rp), C.byref(out), C.c_void_p(stream), C.byref(ticket), C.byref(igs))
+            L.call("vk_forward_begin_ignorey", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p), scp,
+                   C.byref(rp), C.byref(out), s, C.byref(ticket), C.byref(igs))
         st = _Ticket(ticket.value, bufs, images)
         self._open.append(st)
         return PendingForward(self, st, hw)

@@ -13,167 +13,59 @@ Same call surface and outputs as the C4 model (roi_features are `ROI_BOX_HEAD.FC
 logic (Python, as in the reference); every arithmetic step is a C-ABI call into libvltk_hip.so -- no CPU path.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
 
 from . import _lib as L
 from .config import CONFIG_NAME, WEIGHTS_NAME, Config          # noqa: F401
-from .frcnn import FRCNN, ROIOutputs, _TORCH_DT, check_given_width, pack_ignorey, pack_proposals
+from .fpn import FPNNeck, MultiLevelRoIAlign
+from .frcnn import FRCNN, PendingForward
+from .layers import Conv, Linear, f32, stream
 from .parallel import OutputBlock, output_spec
 from .weights import BLOCKS_PER_STAGE, fpn_layer_spec
 
-_DT = {"fp32": (L.VK_F32, torch.float32), "fp16": (L.VK_F16, torch.float16)}
-
-
-def _np(a):
-    return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32)
-
-
-def _pack(w, bn, bias, dt, groups=1):
-    """-> (packed weight bytes, f32 bias [packed cout]) as numpy, BN folded by the library (vk_pack_conv_weight)."""
-    w = _np(w)
-    if w.ndim == 2:
-        w = w.reshape(w.shape[0], w.shape[1], 1, 1)
-    cout, cin, kh, kw = w.shape
-    cin *= groups
-    lib = L.load()
-    wp = np.zeros(lib.vk_packed_weight_bytes(cout, cin, kh, kw, groups, dt), np.uint8)
-    bp = np.zeros(lib.vk_packed_cout(cout), np.float32)
-    bnp = np.ascontiguousarray(np.concatenate([_np(v).reshape(-1) for v in bn])) if bn is not None else None
-    bi = _np(bias) if bias is not None else None
-    L.call("vk_pack_conv_weight", w.ctypes.data_as(C.c_void_p), bnp.ctypes.data_as(C.c_void_p) if bnp is not None else None,
-           bi.ctypes.data_as(C.c_void_p) if bi is not None else None, cout, cin, kh, kw, groups, dt,
-           wp.ctypes.data_as(C.c_void_p), bp.ctypes.data_as(C.c_void_p))
-    return wp, bp
-
-
-class _Layer:
-    """conv (+ folded BN / bias) (+ residual) (+ ReLU) on NHWC device tensors: Conv2d.forward frcnn.py:794-822."""
-
-    def __init__(self, model, w, bn=None, bias=None, stride=1, pad=0, dil=1, groups=1):
-        w = _np(w)
-        if w.ndim == 2:
-            w = w.reshape(w.shape[0], w.shape[1], 1, 1)
-        self.m = model
-        self.cout, self.cin, self.k = w.shape[0], w.shape[1] * groups, w.shape[2]
-        self.stride, self.pad, self.dil, self.groups = stride, pad, dil, groups
-        self.host = _pack(w, bn, bias, model.dt, groups)
-        self.w = torch.from_numpy(self.host[0]).to(model.device)
-        self.b = torch.from_numpy(self.host[1]).to(model.device)
-
-    def out_hw(self, H, W):
-        e = self.dil * (self.k - 1) + 1
-        return (H + 2 * self.pad - e) // self.stride + 1, (W + 2 * self.pad - e) // self.stride + 1
-
-    def __call__(self, x, relu=False, residual=None, out_f32=False):
-        m = self.m
-        N, H, W, cin = x.shape
-        assert cin == self.cin, (cin, self.cin)
-        Ho, Wo = self.out_hw(H, W)
-        ldy = (self.cout + 7) // 8 * 8
-        y = torch.empty((N, Ho, Wo, ldy), dtype=torch.float32 if out_f32 else m.tdt, device=m.device)
-        L.call("vk_conv2d", x.data_ptr(), N, H, W, cin, self.w.data_ptr(), self.b.data_ptr(),
-               residual.data_ptr() if residual is not None else None, y.data_ptr(), self.cout, ldy, self.k, self.k,
-               self.stride, self.pad, self.dil, self.groups, int(relu), m.dt, L.VK_F32 if out_f32 else m.dt, m._stream())
-        return y
-
-
-class _Linear:
-    """nn.Linear (+ ReLU) through the MFMA GEMMs (vk_linear); `fp32`: exact-f32 MFMA whatever the model's mode."""
-
-    def __init__(self, model, w, bias, fp32=False):
-        self.m = model
-        w = _np(w)
-        self.nout, self.k = w.shape
-        self.dt, self.tdt = (L.VK_F32, torch.float32) if fp32 else (model.dt, model.tdt)
-        wp, bp = _pack(w, None, bias, self.dt)
-        self.w, self.b = torch.from_numpy(wp).to(model.device), torch.from_numpy(bp).to(model.device)
-
-    def __call__(self, x, relu=False, out_f32=False):
-        m = self.m
-        M = x.shape[0]
-        assert x.shape[1] == self.k and x.is_contiguous() and x.dtype == self.tdt
-        ldy = (self.nout + 7) // 8 * 8
-        y = torch.empty((M, ldy), dtype=torch.float32 if out_f32 else self.tdt, device=m.device)
-        if M:
-            L.call("vk_linear", x.data_ptr(), M, self.k, self.w.data_ptr(), self.b.data_ptr(), None, y.data_ptr(), self.nout, ldy,
-                   L.VK_ACT_RELU if relu else L.VK_ACT_NONE, self.dt, L.VK_F32 if out_f32 else self.dt, m._stream())
-        return y
-
 
 class _Bottleneck:
-    """BottleneckBlock frcnn.py:903-979.  A stride-1 projection shortcut is part of conv3's GEMM in the fast mode
-    (`out = conv3(t); out += shortcut(x)` as one dual-source GEMM, vk_conv1x1_dual), as in the C4 model."""
+    """BottleneckBlock frcnn.py:903-979.  The library decides, as for the C4 model, whether a stride-1 projection shortcut
+    is part of conv3's GEMM (`out = conv3(t); out += shortcut(x)` as one dual-source GEMM, vk_conv1x1_dual: vk_fuse_shortcut)
+    and whether the whole block runs as one kernel (csrc/bneck_fused.hip, vk_bottleneck64: vk_bottleneck64_eligible)."""
 
     def __init__(self, model, sd, p, stride, groups, stride_in_1x1, dil=1):
-        def bn(q):
-            return [sd[f"{q}.norm.weight"], sd[f"{q}.norm.bias"], sd[f"{q}.norm.running_mean"], sd[f"{q}.norm.running_var"]]
+        def conv(q, **kw):
+            bn = [sd[f"{q}.norm.{s}"] for s in ("weight", "bias", "running_mean", "running_var")]
+            return Conv(sd[q + ".weight"], model.precision, model.device, bn, **kw)
         s1, s3 = (stride, 1) if stride_in_1x1 else (1, stride)             # frcnn.py:932
-        self.m = model
-        self.conv1 = _Layer(model, sd[p + ".conv1.weight"], bn(p + ".conv1"), stride=s1)
-        self.conv2 = _Layer(model, sd[p + ".conv2.weight"], bn(p + ".conv2"), stride=s3, pad=dil, dil=dil, groups=groups)
-        self.conv3 = _Layer(model, sd[p + ".conv3.weight"], bn(p + ".conv3"))
+        self.m, self.stride = model, stride
+        self.conv1 = conv(p + ".conv1", stride=s1)
+        self.conv2 = conv(p + ".conv2", stride=s3, pad=dil, dil=dil, groups=groups)
+        self.conv3 = conv(p + ".conv3")
         self.shortcut, self.fused = None, None
         if (p + ".shortcut.weight") in sd:
-            self.shortcut = _Layer(model, sd[p + ".shortcut.weight"], bn(p + ".shortcut"), stride=stride)
-            c3, sc = self.conv3, self.shortcut
-            if model.dt == L.VK_F16 and stride == 1 and c3.cout % 256 == 0 and c3.cin % 64 == 0 and sc.cin % 64 == 0:
-                rows = c3.host[1].shape[0]
-                cat = np.concatenate([c3.host[0].reshape(rows, -1), sc.host[0].reshape(rows, -1)], axis=1)
-                self.fused = (torch.from_numpy(np.ascontiguousarray(cat).reshape(-1)).to(model.device),
-                              torch.from_numpy(c3.host[1] + sc.host[1]).to(model.device))
-
-    def _whole_block_kernel(self, x):
-        """res2's blocks (64 bottleneck channels, 256 out, stride 1, f16) run as ONE kernel: csrc/bneck_fused.hip, as in the C4
-        model (bit-identical to the layer-by-layer kernels; VK_BNECK_FUSED=0 switches it off)."""
-        m, c1, c2, c3 = self.m, self.conv1, self.conv2, self.conv3
-        if m.dt != L.VK_F16 or os.environ.get("VK_BNECK_FUSED") == "0":
-            return False
-        if not (c1.cout == 64 and c3.cout == 256 and c1.stride == 1 and c2.stride == 1 and c2.dil == 1 and c2.groups == 1):
-            return False
-        proj = self.shortcut is not None
-        if (proj and (self.fused is None or c1.cin != 64)) or (not proj and c1.cin != 256):
-            return False
-        N, H, W, _ = x.shape
-        return N * H * W * 512 < (1 << 31)
+            c3, sc = self.conv3, conv(p + ".shortcut", stride=stride)
+            self.shortcut = sc
+            if L.load().vk_fuse_shortcut(c3.cin, sc.cin, c3.cout, stride, model.dt):
+                rows = c3.b.shape[0]                # per output channel [conv3 row | shortcut row]; the folded biases summed
+                self.fused = (torch.cat([c3.w.view(rows, -1), sc.w.view(rows, -1)], 1).reshape(-1), c3.b + sc.b)
 
     def __call__(self, x):
-        m = self.m
-        if self._whole_block_kernel(x):
-            N, H, W, cin = x.shape
-            proj = self.shortcut is not None
-            w3, b3 = (self.fused if proj else (self.conv3.w, self.conv3.b))
+        m, c1, c2, c3 = self.m, self.conv1, self.conv2, self.conv3
+        N, H, W, cin = x.shape
+        proj = self.shortcut is not None
+        if L.load().vk_bottleneck64_eligible(cin, c1.cout, c3.cout, self.stride, c2.dil, c2.groups, int(proj),
+                                            int(self.fused is not None), N, H, W, m.dt):
+            w3, b3 = self.fused if proj else (c3.w, c3.b)
             y = torch.empty((N, H, W, 256), dtype=m.tdt, device=m.device)
-            L.call("vk_bottleneck64", x.data_ptr(), N, H, W, cin, int(proj), self.conv1.w.data_ptr(), self.conv1.b.data_ptr(),
-                   self.conv2.w.data_ptr(), self.conv2.b.data_ptr(), w3.data_ptr(), b3.data_ptr(), y.data_ptr(), m._stream())
+            L.call("vk_bottleneck64", x.data_ptr(), N, H, W, cin, int(proj), c1.w.data_ptr(), c1.b.data_ptr(),
+                   c2.w.data_ptr(), c2.b.data_ptr(), w3.data_ptr(), b3.data_ptr(), y.data_ptr(), stream(m.device))
             return y
-        t = self.conv2(self.conv1(x, relu=True), relu=True)
+        t = c2(c1(x, relu=True), relu=True)
         if self.fused is not None:
-            N, H, W, c1 = t.shape
-            y = torch.empty((N, H, W, self.conv3.cout), dtype=m.tdt, device=m.device)
-            L.call("vk_conv1x1_dual", t.data_ptr(), c1, x.data_ptr(), x.shape[3], N * H * W, self.fused[0].data_ptr(),
-                   self.fused[1].data_ptr(), None, y.data_ptr(), self.conv3.cout, 1, m._stream())
+            y = torch.empty((N, H, W, c3.cout), dtype=m.tdt, device=m.device)
+            L.call("vk_conv1x1_dual", t.data_ptr(), t.shape[3], x.data_ptr(), cin, N * H * W, self.fused[0].data_ptr(),
+                   self.fused[1].data_ptr(), None, y.data_ptr(), c3.cout, 1, stream(m.device))
             return y
-        res = self.shortcut(x) if self.shortcut is not None else x
-        return self.conv3(t, relu=True, residual=res)
-
-
-class _Done:
-    """A forward that has already finished (this model runs its forward synchronously)."""
-
-    def __init__(self, model, block, hw, given_width=None):
-        self.model, self.block, self.hw = model, block, hw
-        self.given_width = given_width      # given boxes: the output width (max boxes per image); None for detection
-
-    def wait_raw(self):
-        return self.block
-
-    def wait(self, **kwargs):
-        if self.given_width is not None:
-            check_given_width(self.given_width, kwargs.get("max_detections"))
-        return FRCNN._format(self.block, self.hw, **kwargs)
+        return c3(t, relu=True, residual=self.shortcut(x) if proj else x)
 
 
 class FRCNNFPN(FRCNN):
@@ -181,22 +73,7 @@ class FRCNNFPN(FRCNN):
     given_boxes = True                   # forward(proposals=...): region features for caller-supplied boxes
 
     def __init__(self, cfg, precision=None, device=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("vltk_amd.FRCNN needs an AMD GPU (HIP device); there is no CPU fallback")
-        L.load()
-        self.config = cfg
-        self.min_detections, self.max_detections = cfg.min_detections, cfg.max_detections
-        dev = torch.device(device if device is not None else cfg.MODEL.DEVICE)
-        if dev.type != "cuda" or dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
-        self.precision = precision or os.environ.get("VLTK_AMD_PRECISION", "fp16")
-        self.dt, self.tdt = _DT[self.precision]
-        self.roi_outputs = ROIOutputs(cfg)
-        self.training = False
-        self._h = None
-        self._open = []
-        self._finalized = False
+        self._init_host(cfg, precision, device)
         self._stages = {}
         self._timing = None
         self.visual_dim = int(cfg.ROI_BOX_HEAD.FC_DIM)
@@ -205,12 +82,6 @@ class FRCNNFPN(FRCNN):
             raise ValueError("levels * PRE_NMS_TOPK_TEST must be <= 8192 and POST_NMS_TOPK_TEST <= 1024")
         if len(cfg.ROI_HEADS.IN_FEATURES) != 4 or levels not in (4, 5):
             raise ValueError("the FPN detector pools from p2..p5 and proposes from p2..p5(+p6)")
-
-    def __del__(self):
-        pass
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def expected_keys(self):
         keys = []
@@ -238,18 +109,18 @@ class FRCNNFPN(FRCNN):
             raise OSError(f"missing key(s) in state_dict: {missing[:5]}{' ...' if len(missing) > 5 else ''}")
         if extra:
             raise OSError(f"unexpected key(s) in state_dict: {extra[:5]}{' ...' if len(extra) > 5 else ''}")
-        cfg, r = self.config, self.config.RESNETS
+        cfg, r, prec, dev = self.config, self.config.RESNETS, self.precision, self.device
         # stem (BasicStem frcnn.py:857-888)
         p = "backbone.bottom_up.stem.conv1"
-        w = _np(sd[p + ".weight"])
+        w = f32(sd[p + ".weight"])
         self.stem_c = w.shape[0]
         lib = L.load()
         wp = np.zeros(lib.vk_packed_stem_bytes(self.stem_c, self.dt), np.uint8)
         bp = np.zeros(lib.vk_packed_cout(self.stem_c), np.float32)
-        bn = np.ascontiguousarray(np.concatenate([_np(sd[f"{p}.norm.{s}"]) for s in ("weight", "bias", "running_mean", "running_var")]))
+        bn = np.ascontiguousarray(np.concatenate([f32(sd[f"{p}.norm.{s}"]) for s in ("weight", "bias", "running_mean", "running_var")]))
         L.call("vk_pack_stem_weight", w.ctypes.data_as(C.c_void_p), bn.ctypes.data_as(C.c_void_p), self.stem_c, self.dt,
                wp.ctypes.data_as(C.c_void_p), bp.ctypes.data_as(C.c_void_p))
-        self.stem_w, self.stem_b = torch.from_numpy(wp).to(self.device), torch.from_numpy(bp).to(self.device)
+        self.stem_w, self.stem_b = torch.from_numpy(wp).to(dev), torch.from_numpy(bp).to(dev)
         # bottom-up stages (build_backbone frcnn.py:200-261 with res5 as a backbone stage)
         self.stages = []
         for si, name in enumerate(self.STAGES):
@@ -258,36 +129,38 @@ class FRCNNFPN(FRCNN):
                 stride = (1 if si == 0 else 2) if b == 0 else 1
                 blocks.append(_Bottleneck(self, sd, f"backbone.bottom_up.{name}.{b}", stride, r.NUM_GROUPS, bool(r.STRIDE_IN_1X1)))
             self.stages.append(blocks)
-        # neck
-        self.lateral = [_Layer(self, sd[f"backbone.fpn_lateral{l}.weight"], None, sd[f"backbone.fpn_lateral{l}.bias"]) for l in (2, 3, 4, 5)]
-        self.output = [_Layer(self, sd[f"backbone.fpn_output{l}.weight"], None, sd[f"backbone.fpn_output{l}.bias"], pad=1) for l in (2, 3, 4, 5)]
+        # neck (P6 only for the 5-level RPN: forward_async) and the RoIAlign pooler over P2..P5
+        self.neck = FPNNeck([(sd[f"backbone.fpn_lateral{l}.weight"], sd[f"backbone.fpn_lateral{l}.bias"]) for l in (2, 3, 4, 5)],
+                            [(sd[f"backbone.fpn_output{l}.weight"], sd[f"backbone.fpn_output{l}.bias"]) for l in (2, 3, 4, 5)], prec, dev)
+        P, fc = int(cfg.ROI_BOX_HEAD.POOLER_RESOLUTION), int(cfg.FPN.OUT_CHANNELS)
+        self.pooler = MultiLevelRoIAlign(P, (1 / 4, 1 / 8, 1 / 16, 1 / 32), int(cfg.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO),
+                                         precision=prec, device=dev)
         # RPN head (RPNHead frcnn.py:1513-1572): 3x3 + ReLU, then [objectness | deltas] as one 1x1 GEMM with f32 output
         q = "proposal_generator.rpn_head."
-        self.rpn_conv = _Layer(self, sd[q + "conv.weight"], None, sd[q + "conv.bias"], pad=1)
+        self.rpn_conv = Conv(sd[q + "conv.weight"], prec, dev, bias=sd[q + "conv.bias"], pad=1)
         self.A = int(sd[q + "objectness_logits.weight"].shape[0])
-        self.rpn_out = _Layer(self, np.concatenate([_np(sd[q + "objectness_logits.weight"]), _np(sd[q + "anchor_deltas.weight"])], 0), None,
-                              np.concatenate([_np(sd[q + "objectness_logits.bias"]), _np(sd[q + "anchor_deltas.bias"])], 0))
-        self.cells = [torch.from_numpy(_np(sd[f"proposal_generator.anchor_generator.cell_anchors.{i}"])).to(self.device)
+        self.rpn_out = Conv(np.concatenate([f32(sd[q + "objectness_logits.weight"]), f32(sd[q + "anchor_deltas.weight"])], 0), prec, dev,
+                            bias=np.concatenate([f32(sd[q + "objectness_logits.bias"]), f32(sd[q + "anchor_deltas.bias"])], 0))
+        self.cells = [torch.from_numpy(f32(sd[f"proposal_generator.anchor_generator.cell_anchors.{i}"])).to(dev)
                       for i in range(len(cfg.RPN.IN_FEATURES))]
         # box head: fc1 expects detectron2's (c, y, x) flatten; the pooled tensor here is [K, y, x, c]
-        P, fc = int(cfg.ROI_BOX_HEAD.POOLER_RESOLUTION), int(cfg.FPN.OUT_CHANNELS)
         self.fcs = []
         for i in range(int(cfg.ROI_BOX_HEAD.NUM_FC)):
-            w = _np(sd[f"roi_heads.box_head.fc{i + 1}.weight"])
+            w = f32(sd[f"roi_heads.box_head.fc{i + 1}.weight"])
             if i == 0:
                 w = np.ascontiguousarray(w.reshape(w.shape[0], fc, P * P).transpose(0, 2, 1).reshape(w.shape[0], -1))
-            self.fcs.append(_Linear(self, w, sd[f"roi_heads.box_head.fc{i + 1}.bias"]))
+            self.fcs.append(Linear(w, sd[f"roi_heads.box_head.fc{i + 1}.bias"], prec, dev))
         # predictor (FastRCNNOutputLayers frcnn.py:1676-1740): fp32 in both modes, as in the C4 model (csrc/model.hip pdt)
         bp_ = "roi_heads.box_predictor."
-        self.cls_score = _Linear(self, sd[bp_ + "cls_score.weight"], sd[bp_ + "cls_score.bias"], fp32=True)
-        self.bbox_w = torch.from_numpy(_np(sd[bp_ + "bbox_pred.weight"])).to(self.device).contiguous()
-        self.bbox_b = torch.from_numpy(_np(sd[bp_ + "bbox_pred.bias"])).to(self.device)
+        self.cls_score = Linear(sd[bp_ + "cls_score.weight"], sd[bp_ + "cls_score.bias"], "fp32", dev)
+        self.bbox_w = torch.from_numpy(f32(sd[bp_ + "bbox_pred.weight"])).to(dev).contiguous()
+        self.bbox_b = torch.from_numpy(f32(sd[bp_ + "bbox_pred.bias"])).to(dev)
         self.use_attr = bool(cfg.ROI_BOX_HEAD.ATTR)
         if not self.use_attr:
             raise NotImplementedError("ROI_BOX_HEAD.ATTR=false: the reference's Res5ROIHeads unpacks three outputs (frcnn.py:1400)")
-        self.emb = torch.from_numpy(_np(sd[bp_ + "cls_embedding.weight"])).to(self.device).contiguous()
-        self.fc_attr = _Linear(self, sd[bp_ + "fc_attr.weight"], sd[bp_ + "fc_attr.bias"], fp32=True)
-        self.attr_score = _Linear(self, sd[bp_ + "attr_score.weight"], sd[bp_ + "attr_score.bias"], fp32=True)
+        self.emb = torch.from_numpy(f32(sd[bp_ + "cls_embedding.weight"])).to(dev).contiguous()
+        self.fc_attr = Linear(sd[bp_ + "fc_attr.weight"], sd[bp_ + "fc_attr.bias"], "fp32", dev)
+        self.attr_score = Linear(sd[bp_ + "attr_score.weight"], sd[bp_ + "attr_score.bias"], "fp32", dev)
         self._finalized = True
         return self
 
@@ -328,33 +201,22 @@ class FRCNNFPN(FRCNN):
     def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None):
         """Detection, or with `proposals` region features for exactly those boxes (FRCNN.forward).  The forward
         runs to its end here; the returned handle's wait() / wait_raw() only format / hand out the outputs."""
-        if self.training:
-            raise NotImplementedError()
-        if ignorey is not None and proposals is not None:
-            raise ValueError("ignorey removes / trims RPN proposals: there are none with proposals=")
-        if not self._finalized:
-            raise RuntimeError("no weights loaded: call load_state_dict / from_pretrained first")
-        images = torch.as_tensor(images)
-        if images.dim() != 4 or images.shape[1] != 3:
-            raise ValueError(f"images must be [N,3,H,W], got {tuple(images.shape)}")
-        sc = None
-        if scales_yx is not None:
-            sc = np.ascontiguousarray(np.asarray(torch.as_tensor(scales_yx).cpu(), dtype=np.float32).reshape(images.shape[0], 2))
-        if proposals is not None:
-            return self._forward_boxes(images, image_shapes, proposals, sc)
-        ig = pack_ignorey(ignorey, sc, images.shape[0]) if ignorey is not None else None     # before anything is enqueued
-        images = images.to(device=self.device, dtype=torch.float32).contiguous()
-        N, _, H, W = images.shape
-        hw = np.ascontiguousarray(np.asarray(torch.as_tensor(image_shapes).cpu()).reshape(N, 2), dtype=np.int32)
+        images, hw, sc, given, ig = self._prepare(images, image_shapes, proposals, scales_yx, ignorey)
+        if given is not None and int(self.config.ROI_BOX_HEAD.FC_DIM) % 4:
+            raise ValueError(f"given boxes need ROI_BOX_HEAD.FC_DIM a multiple of 4, got {int(self.config.ROI_BOX_HEAD.FC_DIM)}")
         if (hw < 1).any():
             raise ValueError("image_shapes must be positive")
-        cfg, dev, s = self.config, self.device, self._stream()
+        if given is not None:
+            return self._forward_boxes(images, hw, *given, sc)
+        N = images.shape[0]
+        cfg, dev, s = self.config, self.device, stream(self.device)
         evs = [] if self._timing is not None else None
         st = self._stages = {}
         self._mark(evs)
         feats = self._bottom_up(images, st)
         self._mark(evs)
-        pyr = self._neck(feats, st, len(cfg.RPN.IN_FEATURES) == 5)
+        pyr = self.neck(feats, p6=len(cfg.RPN.IN_FEATURES) == 5)
+        st.update((f"p{i + 2}", p_) for i, p_ in enumerate(pyr))
         self._mark(evs)
         # ---- RPN head over every level ----
         A, nl = self.A, len(pyr)
@@ -388,13 +250,11 @@ class FRCNNFPN(FRCNN):
             L.call("vk_rpn_proposals_multilevel_ignorey", *rpn_args, C.byref(igs))
         st["proposal_boxes"], st["proposal_logits"], st["proposal_counts"] = pb, pl, pc
         self._mark(evs)
-        # ---- box head: RoIAlign by level (ROIPooler.forward's level loop :1200-1224, level rule :444-460) + FCs ----
+        # ---- box head: RoI rows, then RoIAlign by level and the FCs ----
         K = N * R
         rois = torch.empty((K, 5), dtype=torch.float32, device=dev)
         L.call("vk_make_rois", pb.data_ptr(), N, R, rois.data_ptr(), s)
-        lv = torch.zeros(K, dtype=torch.int32, device=dev)
-        L.call("vk_assign_levels", rois.data_ptr() + 4, 5, K, 2, 5, 224.0, 4, lv.data_ptr(), s)
-        feat = self._box_head(pyr, rois, lv, N, K, st)                                         # [K, FC_DIM] f32 = roi_features
+        feat = self._box_head(pyr, rois, None, st)                                             # [K, FC_DIM] f32 = roi_features
         self._mark(evs)
         # ---- predictor (FastRCNNOutputLayers.forward :1726-1740) ----
         F_, Cn, At = feat.shape[1], int(cfg.ROI_HEADS.NUM_CLASSES), int(cfg.ROI_BOX_HEAD.NUM_ATTRS)
@@ -404,23 +264,14 @@ class FRCNNFPN(FRCNN):
                int(bool(cfg.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG)), F_, K, chosen.data_ptr(), L.VK_F32, s)
         st["chosen_deltas"] = chosen
         # ---- outputs (ROIOutputs.inference :1262-1294) ----
-        ro = self.roi_outputs
-        D = int(ro.max_detections)
-        rp = L.vk_roi_params()
-        thr = list(ro.nms_thresh)
-        if len(thr) > L.VK_MAX_NMS_THRESH:
-            raise ValueError(f"at most {L.VK_MAX_NMS_THRESH} NMS thresholds")
-        rp.num_nms_thresh = len(thr)
-        for i, t in enumerate(thr):
-            rp.nms_thresh[i] = float(t)
-        rp.min_detections, rp.max_detections = int(ro.min_detections), D
-        bufs = OutputBlock(output_spec(N, D, F_), device=dev)
+        rp = self.roi_outputs.params()
+        bufs = OutputBlock(output_spec(N, rp.max_detections, F_), device=dev)
         bufs.flat.zero_()
         out = L.vk_outputs(*[bufs[k].data_ptr() for k in bufs])
         sc_dev = None
         if sc is not None:
             sc_dev = torch.from_numpy(sc).to(dev)
-        keep = torch.zeros((N, D), dtype=torch.int64, device=dev)
+        keep = torch.zeros((N, rp.max_detections), dtype=torch.int64, device=dev)
         wts2 = (C.c_float * 4)(*[float(v) for v in cfg.ROI_BOX_HEAD.BBOX_REG_WEIGHTS])
         L.call("vk_roi_outputs", cls_logits.data_ptr(), cls_logits.shape[1], attr_logits.data_ptr(), attr_logits.shape[1],
                chosen.data_ptr(), 4, 1, pb.data_ptr(), pc.data_ptr(), feat.data_ptr(), F_, N, R, Cn, At, hw_dev.data_ptr(),
@@ -433,22 +284,14 @@ class FRCNNFPN(FRCNN):
         if int(flag.cpu().sum()) != 0:
             raise AssertionError("Box tensor contains infinite or NaN!")          # frcnn.py:148
         self._last_padded = bufs
-        return _Done(self, bufs, hw)
+        return PendingForward.finished(self, bufs, hw)
 
-    def _forward_boxes(self, images, image_shapes, proposals, sc):
+    def _forward_boxes(self, images, hw, boxes, counts, sc):
         """Region features for caller-supplied boxes (FRCNN.forward's `proposals`): bottom-up -> neck (no P6) ->
         vk_given_boxes_ingest (scale, finite check, _clip_box, RoI rows and levels in one launch) -> RoIAlign -> FCs ->
         cls_score / soft-max -> attribute branch -> vk_given_box_outputs.  No RPN head, proposals, box regression or NMS."""
         cfg, dev = self.config, self.device
         N = images.shape[0]
-        boxes, counts = pack_proposals(proposals, N, dev)              # ValueError on a bad shape, before anything runs
-        if int(cfg.ROI_BOX_HEAD.FC_DIM) % 4:
-            raise ValueError(f"given boxes need ROI_BOX_HEAD.FC_DIM a multiple of 4, got {int(cfg.ROI_BOX_HEAD.FC_DIM)}")
-        images = images.to(device=dev, dtype=torch.float32).contiguous()
-        _, _, H, W = images.shape
-        hw = np.ascontiguousarray(np.asarray(torch.as_tensor(image_shapes).cpu()).reshape(N, 2), dtype=np.int32)
-        if (hw < 1).any():
-            raise ValueError("image_shapes must be positive")
         B, F_ = boxes.shape[1], (self.fcs[-1].nout + 7) // 8 * 8              # F_: the feature row width, as detection's
         bufs = OutputBlock(output_spec(N, B, F_), device=dev)
         st = self._stages = {}
@@ -457,8 +300,8 @@ class FRCNNFPN(FRCNN):
             if self._timing is not None:
                 self._timing.pop("ev", None)
             self._last_padded = bufs
-            return _Done(self, bufs, hw, given_width=0)
-        s = self._stream()
+            return PendingForward.finished(self, bufs, hw, given_width=0)
+        s = stream(dev)
         evs = [] if self._timing is not None else None
         # counts | image_hw | scales_yx: one host-to-device copy
         meta = np.zeros(N * (3 if sc is None else 5), dtype=np.int32)
@@ -472,7 +315,8 @@ class FRCNNFPN(FRCNN):
         self._mark(evs)
         feats = self._bottom_up(images, st)
         self._mark(evs)
-        pyr = self._neck(feats, st, False)
+        pyr = self.neck(feats, p6=False)
+        st.update((f"p{i + 2}", p_) for i, p_ in enumerate(pyr))
         self._mark(evs)
         self._mark(evs)                             # no RPN head
         # ---- the caller's boxes in place of the proposals: scale, finite check, _clip_box (frcnn.py:147-153), RoI rows, levels ----
@@ -484,7 +328,7 @@ class FRCNNFPN(FRCNN):
                rois.data_ptr(), lv.data_ptr(), 2, 5, 224.0, 4, flag.data_ptr(), s)
         st["proposal_boxes"], st["proposal_counts"] = pb, cnt_dev
         self._mark(evs)
-        feat = self._box_head(pyr, rois, lv, N, K, st)
+        feat = self._box_head(pyr, rois, lv, st)
         self._mark(evs)
         _, obj_prob, obj_cls, attr_logits = self._predictor(feat, K, st)
         At = int(cfg.ROI_BOX_HEAD.NUM_ATTRS)
@@ -501,12 +345,12 @@ class FRCNNFPN(FRCNN):
         if int(flag.cpu()) != 0:
             raise AssertionError("Box tensor contains infinite or NaN!")          # frcnn.py:148
         self._last_padded = bufs
-        return _Done(self, bufs, hw, given_width=B)
+        return PendingForward.finished(self, bufs, hw, given_width=B)
 
     # ---- the stages shared by detection and given boxes ----
     def _bottom_up(self, images, st):
         """stem + res2..res5 (build_backbone frcnn.py:200-261 with res5 as a backbone stage) -> [C2, C3, C4, C5] NHWC."""
-        cfg, dev, s = self.config, self.device, self._stream()
+        cfg, dev, s = self.config, self.device, stream(self.device)
         N, _, H, W = images.shape
         ho, wo = C.c_int(), C.c_int()
         L.load().vk_stem_out_hw(H, W, int(bool(cfg.MODEL.MAX_POOL)), C.byref(ho), C.byref(wo))
@@ -523,39 +367,12 @@ class FRCNNFPN(FRCNN):
             st[name] = x
         return feats
 
-    def _neck(self, feats, st, p6):
-        """detectron2 FPN top-down path -> [P2..P5] (+ P6 by the top block LastLevelMaxPool frcnn.py:825-836)."""
-        s = self._stream()
-        prev = self.lateral[3](feats[3])
-        pyr = [self.output[3](prev)]
-        for i in (2, 1, 0):
-            lat = self.lateral[i](feats[i])
-            n_, h_, w_, c_ = lat.shape
-            y = torch.empty_like(lat)
-            L.call("vk_upsample2x_add", lat.data_ptr(), prev.data_ptr(), y.data_ptr(), n_, h_, w_, prev.shape[1], prev.shape[2], c_, self.dt, s)
-            prev = y
-            pyr.insert(0, self.output[i](prev))
-        if p6:
-            p5 = pyr[-1]
-            n_, h_, w_, c_ = p5.shape
-            p6 = torch.empty((n_, (h_ - 1) // 2 + 1, (w_ - 1) // 2 + 1, c_), dtype=self.tdt, device=self.device)
-            L.call("vk_subsample2", p5.data_ptr(), p6.data_ptr(), n_, h_, w_, c_, self.dt, s)
-            pyr.append(p6)
-        for i, p_ in enumerate(pyr):
-            st[f"p{i + 2}"] = p_
-        return pyr
-
-    def _box_head(self, pyr, rois, lv, N, K, st):
-        """RoIAlign 7x7 over P2..P5 by level (ROIPooler.forward's level loop :1200-1224) -> fc1 -> fc2: [K, FC_DIM] f32."""
-        cfg = self.config
-        P, fc = int(cfg.ROI_BOX_HEAD.POOLER_RESOLUTION), pyr[0].shape[3]
-        pooled = torch.empty((K, P, P, fc), dtype=self.tdt, device=self.device)
-        maps = (C.c_void_p * 4)(*[p_.data_ptr() for p_ in pyr[:4]])
-        L.call("vk_roi_align", maps, (C.c_int32 * 4)(*[p_.shape[1] for p_ in pyr[:4]]), (C.c_int32 * 4)(*[p_.shape[2] for p_ in pyr[:4]]),
-               (C.c_float * 4)(1 / 4, 1 / 8, 1 / 16, 1 / 32), 4, N, fc, rois.data_ptr(), lv.data_ptr(), K, P,
-               int(cfg.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO), 1, pooled.data_ptr(), self.dt, self._stream())
-        st["pooled"], st["levels"] = pooled, lv
-        x = pooled.view(K, P * P * fc)
+    def _box_head(self, pyr, rois, levels, st):
+        """RoIAlign 7x7 over P2..P5 by level (fpn.MultiLevelRoIAlign: ROIPooler.forward's level loop :1200-1224, the levels
+        assigned there by the rule of :444-460 unless given) -> fc1 -> fc2: [K, FC_DIM] f32."""
+        pooled, st["levels"] = self.pooler(pyr[:4], rois, levels)
+        st["pooled"] = pooled
+        x = pooled.view(pooled.shape[0], -1)
         for i, fcl in enumerate(self.fcs):
             x = fcl(x, relu=True, out_f32=(i + 1 == len(self.fcs)))
         st["box_features"] = x
@@ -565,7 +382,7 @@ class FRCNNFPN(FRCNN):
         """cls_score -> soft-max over C+1 (obj_prob / obj_cls over the first C, the raw arg-max class) -> the attribute
         branch on the raw arg-max class (FastRCNNOutputLayers.forward :1726-1740).  -> (cls_logits, obj_prob, obj_cls,
         attr_logits)."""
-        cfg, dev, s = self.config, self.device, self._stream()
+        cfg, dev, s = self.config, self.device, stream(self.device)
         F_, Cn, E = feat.shape[1], int(cfg.ROI_HEADS.NUM_CLASSES), self.emb.shape[1]
         cls_logits = self.cls_score(feat, out_f32=True)
         obj_prob = torch.empty(K, dtype=torch.float32, device=dev)

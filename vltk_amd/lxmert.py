@@ -7,13 +7,13 @@ the host-side mirror of `transformers.LxmertModel` (modeling_lxmert.py v5.15: `L
 name.  All arithmetic runs in `libvltk_hip.so` (MFMA GEMM with bias / residual / GELU / tanh epilogues, LayerNorm,
 attention, embedding kernels); torch only owns the device buffers.  No CPU fallback.
 """
-import ctypes as C
 import zlib
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from .layers import DTYPES, pack, stream
 
 DEFAULT_CONFIG = dict(vocab_size=30522, hidden_size=768, num_attention_heads=12, intermediate_size=3072, l_layers=9, x_layers=5,
                       r_layers=5, max_position_embeddings=512, type_vocab_size=2, visual_feat_dim=2048, visual_pos_dim=4)
@@ -102,9 +102,6 @@ def make_lxmert_state_dict(cfg, seed=0):
     return sd
 
 
-_DT = {"fp32": (L.VK_F32, torch.float32), "fp16": (L.VK_F16, torch.float16), "bf16": (L.VK_BF16, torch.bfloat16)}
-
-
 class LxmertEncoder:
     """`transformers.LxmertModel` on the HIP path: `model(input_ids, visual_feats, visual_pos, attention_mask=None,
     visual_attention_mask=None, token_type_ids=None)` -> (language_output, vision_output, pooled_output)."""
@@ -114,7 +111,7 @@ class LxmertEncoder:
             raise RuntimeError("vltk_amd.LxmertEncoder needs a GPU: there is no CPU fallback")
         L.load()
         self.cfg = dict(config)
-        self.dt, self.tdt = _DT[precision]
+        self.dt, self.tdt = DTYPES[precision]
         self.device = torch.device(device)
         self.es = 4 if precision == "fp32" else 2
         self.ktile = 128 // self.es                    # elements per 128-byte K-tile of the GEMM
@@ -126,15 +123,9 @@ class LxmertEncoder:
         """nn.Linear weight [N, K] (+ bias) -> device (packed rows padded to the K-tile, f32 bias)."""
         N, K = w.shape
         Kp = (K + self.ktile - 1) // self.ktile * self.ktile
-        wp_ = np.zeros((N, Kp, 1, 1), np.float32)
-        wp_[:, :K, 0, 0] = w
-        lib = L.load()
-        nb = lib.vk_packed_weight_bytes(N, Kp, 1, 1, 1, self.dt)
-        wp = np.zeros(nb, np.uint8)
-        bp = np.zeros(lib.vk_packed_cout(N), np.float32)
-        bb = np.ascontiguousarray(b, dtype=np.float32)
-        L.call("vk_pack_conv_weight", wp_.ctypes.data_as(C.c_void_p), None, bb.ctypes.data_as(C.c_void_p), N, Kp, 1, 1, 1, self.dt,
-               wp.ctypes.data_as(C.c_void_p), bp.ctypes.data_as(C.c_void_p))
+        wk = np.zeros((N, Kp), np.float32)
+        wk[:, :K] = w
+        wp, bp = pack(wk, self.dt, bias=b)
         return torch.from_numpy(wp).to(self.device), torch.from_numpy(bp).to(self.device), N, Kp
 
     def load_state_dict(self, sd, strict=True):
@@ -199,9 +190,6 @@ class LxmertEncoder:
         return self
 
     # ---- ops (each one call into the C ABI) ----------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _linear(self, x, name, act=L.VK_ACT_NONE, residual=None):
         w, b, N, Kp = self._lin[name]
         M, K = x.shape
@@ -212,7 +200,7 @@ class LxmertEncoder:
         ldy = (N + 7) // 8 * 8
         y = torch.empty((M, ldy), dtype=self.tdt, device=self.device)
         L.call("vk_linear", x.data_ptr(), M, Kp, w.data_ptr(), b.data_ptr(), residual.data_ptr() if residual is not None else None,
-               y.data_ptr(), N, ldy, act, self.dt, self.dt, self._stream())
+               y.data_ptr(), N, ldy, act, self.dt, self.dt, stream(self.device))
         return y if ldy == N else y[:, :N]
 
     def _layernorm(self, x, name, out=None, scale=1.0, accumulate=False):
@@ -220,14 +208,14 @@ class LxmertEncoder:
         M, Cc = x.shape
         y = torch.empty((M, Cc), dtype=self.tdt, device=self.device) if out is None else out
         L.call("vk_layernorm", x.data_ptr(), x.stride(0), g.data_ptr(), b.data_ptr(), y.data_ptr(), y.stride(0), M, Cc, LN_EPS, scale,
-               int(accumulate), self.dt, self._stream())
+               int(accumulate), self.dt, stream(self.device))
         return y
 
     def _attention(self, q, k, v, mask, B, Lq, Lk):
         H, heads = self.cfg["hidden_size"], self.cfg["num_attention_heads"]
         out = torch.empty((B * Lq, H), dtype=self.tdt, device=self.device)
         L.call("vk_attention", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
-               mask.data_ptr() if mask is not None else None, out.data_ptr(), H, B, heads, Lq, Lk, H // heads, self.dt, self._stream())
+               mask.data_ptr() if mask is not None else None, out.data_ptr(), H, B, heads, Lq, Lk, H // heads, self.dt, stream(self.device))
         return out
 
     # ---- layers (modeling_lxmert.py) -----------------------------------------------------------------------------
@@ -309,7 +297,7 @@ class LxmertEncoder:
         g, b = self._ln["embeddings.LayerNorm"]
         L.call("vk_embed_layernorm", ids.data_ptr(), tts.data_ptr(), B, Lq, self._tab["word_embeddings"].data_ptr(),
                self._tab["position_embeddings"].data_ptr(), self._tab["token_type_embeddings"].data_ptr(), g.data_ptr(), b.data_ptr(),
-               lang.data_ptr(), H, LN_EPS, self.dt, self._stream())
+               lang.data_ptr(), H, LN_EPS, self.dt, stream(self.device))
         # visual feature encoder :468-476: (LN(fc(feats)) + LN(fc(pos))) / 2
         vf = visual_feats.to(dev).reshape(B * V, -1).to(self.tdt).contiguous()
         vp = visual_pos.to(dev).reshape(B * V, -1).to(self.tdt).contiguous()
@@ -333,7 +321,7 @@ class LxmertEncoder:
         w, bb, N, Kp = self._lin["pooler.dense"]
         pooled = torch.empty((B, H), dtype=self.tdt, device=dev)
         L.call("vk_conv2d", lang.data_ptr(), B, Lq, 1, H, w.data_ptr(), bb.data_ptr(), None, pooled.data_ptr(), H, H, 1, 1, Lq, 0, 1, 1,
-               L.VK_ACT_TANH, self.dt, self.dt, self._stream())
+               L.VK_ACT_TANH, self.dt, self.dt, stream(self.device))
         return lang.view(B, Lq, H), visn.view(B, V, H), pooled
 
 

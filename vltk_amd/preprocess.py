@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .layers import stream
 
 
 def resized_hw(h, w, min_size, max_size):
@@ -61,8 +62,7 @@ class Preprocess:
         out = torch.empty((N, 3, Hmax, Wmax), dtype=torch.float32, device=self.device)
         ptrs = (C.c_void_p * N)(*[r.data_ptr() for r in raws])
         L.call("vk_preprocess", ptrs, raw_hw.ctypes.data_as(C.c_void_p), new_hw.ctypes.data_as(C.c_void_p), N, Hmax, Wmax,
-               self.mean, self.std, self.pad_value, out.data_ptr(),
-               C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+               self.mean, self.std, self.pad_value, out.data_ptr(), stream(self.device))
         sizes = torch.from_numpy(new_hw.astype(np.int64))
         scales_yx = torch.true_divide(torch.from_numpy(raw_hw.astype(np.int64)), sizes)
         return good_ids, out, sizes, scales_yx
