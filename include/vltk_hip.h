@@ -277,6 +277,24 @@ int vk_conv2d(const void *x, int N, int H, int W, int cin,
               void *y, int cout, int ldy, int kh, int kw, int stride, int pad, int dil, int groups,
               int relu, vk_dtype dt, vk_dtype out_dt, void *stream);
 
+/* Which kernel a convolution launch runs on, asked of the dispatcher itself (host only, touches no device): the launch
+ * entry points below switch on the same function, under the same A/B environment switches, re-read per call.
+ * Geometry as vk_conv2d (N, H, W: the input; Ho / Wo follow); flags in place of pointers: cin2 > 0 is the dual-source form
+ * (vk_conv1x1_dual: N = H = 1, W = M), has_residual a residual pointer, fused_mean vk_conv1x1_meanpool (N images of
+ * H x W = 1 x HW).  vk_linear is N = H = 1, W = M, cin = K, cout = N, relu = act.  Returns a VK_ROUTE_* or, where the launch
+ * would refuse the layer, the negative of its VK_E* code.  Not askable: vk_stem's convolution (always the generic kernel's stem
+ * form, or stem_pool.hip as one kernel) and the sub-form a kernel picks for itself (the panel kernel's 8 or 9 row tiles, the
+ * weight-stationary kernel's wave count, the fused block's rows / tile form). */
+#define VK_ROUTE_GENERIC 0   /* conv_mfma_kernel: im2col, 128 x {64,128} tile; f32 / f16 / bf16, grouped, stem form */
+#define VK_ROUTE_RING 1      /* conv_mfma256_kernel: 256 x 256 LDS-ring tile */
+#define VK_ROUTE_DUO 2       /* conv_duo_kernel: 1x1, 128 x 256 tile, two workgroups per CU (f16 / bf16) */
+#define VK_ROUTE_WS 3        /* conv_ws_kernel: 1x1, K <= 512, weight-stationary */
+#define VK_ROUTE_GEMM4 4     /* conv_gemm4_kernel: 1x1, K >= 1024, four waves of 128 x 128 */
+#define VK_ROUTE_PANEL 5     /* conv3x3_panel_kernel: 3x3, LDS-resident input panel */
+#define VK_ROUTE_BLK 6       /* conv3x3_blk_kernel: 3x3 over narrow channel blocks */
+int vk_conv_route(int N, int H, int W, int cin, int cin2, int has_residual, int fused_mean, int cout, int ldy, int kh, int kw,
+                  int stride, int pad, int dil, int groups, int relu, vk_dtype dt, vk_dtype out_dt);
+
 /* conv3 + projection shortcut of a stride-1 BottleneckBlock as ONE f16 GEMM (`out = conv3(t) ; out += shortcut(x)`,
  * frcnn.py:970-977): y[M,cout] = relu?([x1 | x2] . W^T + bias (+ residual)), W rows = [conv3 row (cin1) | shortcut row
  * (cin2)] as packed by vk_pack_conv_weight and concatenated per output channel, bias = the two folded biases

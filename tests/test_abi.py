@@ -162,3 +162,118 @@ def test_workspace_sizes(lib):
     assert lib.vk_rpn_workspace_bytes(2, 63000, 6000) > 2 * 6000 * 94 * 8
     assert lib.vk_nms_workspace_bytes(300) > 300 * 16
     assert lib.vk_stem_workspace_bytes(1, 800, 1333, 64, L.VK_F16) > 400 * 667 * 64 * 2
+
+
+def _clear_switches(monkeypatch):
+    for v in list(os.environ):
+        if v.startswith("VK_"):
+            monkeypatch.delenv(v)
+
+
+def _resnet101_c4_convs(lib, dt, batch=32, rois=300):
+    """(layer, gpu_util.conv_route arguments) of every convolution launch of ResNet-101-C4 on a batch of 800 x 1333 images:
+    res2 whole, res3 / res4 as the two half-batches the model runs on two streams, the RPN head on res4, res5 (stride 1,
+    dilation 2) on batch x rois RoIs of 14 x 14 with the spatial mean folded into the last conv3 in fp16 (model.hip
+    run_block).  res2's blocks are listed layer by layer although fp16 runs them as vk_bottleneck64
+    (test_block_rules_resnet101): that is what VK_BNECK_FUSED=0 launches."""
+    ho, wo = C.c_int(), C.c_int()
+    lib.vk_stem_out_hw(800, 1333, 1, C.byref(ho), C.byref(wo))
+    blocks = [(n, b, cin, mid, cout, s, proj, batch if n == "res2" else batch // 2, H, W, 1)
+              for n, b, cin, mid, cout, s, proj, H, W in _resnet101_blocks(ho.value, wo.value) if n != "res5"]
+    H4, W4 = [((H - 1) // s + 1, (W - 1) // s + 1) for n, b, _, _, _, s, _, H, W in _resnet101_blocks(ho.value, wo.value) if n == "res4"][-1]
+    blocks += [("res5", b, 1024 if b == 0 else 2048, 512, 2048, 1, b == 0, batch * rois, 14, 14, 2) for b in range(3)]
+    for name, b, cin, mid, cout, s, proj, N, H, W, dil in blocks:
+        tag = f"{name}.{b}"
+        Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+        fused = proj and lib.vk_fuse_shortcut(mid, cin, cout, s, dt) == 1
+        mean = name == "res5" and b == 2 and dt == L.VK_F16
+        if proj and not fused:
+            yield tag + ".shortcut", dict(N=N, H=H, W=W, cin=cin, cout=cout, stride=s, dt=dt)
+        yield tag + ".conv1", dict(N=N, H=H, W=W, cin=cin, cout=mid, stride=s, relu=1, dt=dt)
+        yield tag + ".conv2", dict(N=N, H=Ho, W=Wo, cin=mid, cout=mid, k=3, pad=dil, dil=dil, relu=1, dt=dt)
+        if fused:
+            yield tag + ".conv3", dict(N=N, H=Ho, W=Wo, cin=mid, cin2=cin, cout=cout, relu=1, dt=dt)
+        else:
+            yield tag + ".conv3", dict(N=N, H=Ho, W=Wo, cin=mid, cout=cout, relu=1, res=True, mean=mean, dt=dt)
+    yield "rpn.conv", dict(N=batch, H=H4, W=W4, cin=1024, cout=1024, k=3, pad=1, relu=1, dt=dt)
+    yield "rpn.heads", dict(N=batch, H=H4, W=W4, cin=1024, cout=75, dt=dt, out_dt=L.VK_F32)
+
+
+# fp16 production routing, layer by layer ("*": every block of the stage not listed on its own)
+RESNET101_C4_ROUTES = {
+    "res2.*.conv1": "generic", "res2.*.conv2": "blk", "res2.*.conv3": "ws",              # (res2.0.conv3: 64 + 64 channels, two inputs)
+    "res3.0.shortcut": "ws", "res3.*.conv1": "generic", "res3.*.conv2": "generic", "res3.*.conv3": "ws",
+    "res4.0.shortcut": "ws", "res4.0.conv1": "ws", "res4.*.conv1": "gemm4", "res4.*.conv2": "panel", "res4.*.conv3": "ws",
+    "res5.*.conv1": "gemm4", "res5.*.conv2": "panel", "res5.0.conv3": "gemm4", "res5.*.conv3": "ws",   # (res5.2.conv3: the fused mean)
+    "rpn.conv": "panel", "rpn.heads": "generic",
+}
+
+
+@pytest.mark.parametrize("dt", [L.VK_F16, L.VK_F32], ids=["fp16", "fp32"])
+def test_conv_routes_resnet101_c4(lib, dt, monkeypatch):
+    """Which kernel runs every convolution of the flagship model at the benchmark's size (32 x 800 x 1333, 300 RoIs per image),
+    as a table: a change of production routing is a visible diff here.  fp32 strict mode runs the generic kernel throughout."""
+    import gpu_util as G
+    _clear_switches(monkeypatch)
+    got = {}
+    for layer, geom in _resnet101_c4_convs(lib, dt):
+        got[layer] = G.conv_route(**geom)
+    if dt == L.VK_F32:
+        assert set(got.values()) == {"generic"}
+        return
+    want = {}
+    for layer in got:
+        want[layer] = RESNET101_C4_ROUTES.get(layer) or RESNET101_C4_ROUTES["{}.*.{}".format(*layer.split(".")[::2])]
+    assert got == want, {k: (got[k], want[k]) for k in got if got[k] != want[k]}
+    assert len(got) == 3 * 33 + 2 + 2           # 33 blocks, a shortcut conv in res3.0 / res4.0 (res2.0's and res5.0's ride in conv3), the RPN's two
+
+
+def test_gpu_tests_run_the_kernels_they_name(lib, monkeypatch):
+    """Every launch of the GPU conv tests that names its kernel (`expect_route=` in tests/test_gpu_stages.py,
+    test_gpu_bneck_fused.py, test_gpu_lxmert.py::test_linear, test_gpu_conv_exact.py), asked of the dispatcher here, under that
+    run's environment: no A/B test compares a kernel with itself, and each table covers every kernel its test is about."""
+    import gpu_util as G
+    import test_gpu_bneck_fused
+    import test_gpu_conv_exact
+    import test_gpu_lxmert
+    import test_gpu_stages
+    seen = {}
+    for mod in (test_gpu_stages, test_gpu_bneck_fused, test_gpu_lxmert, test_gpu_conv_exact):
+        n = 0
+        for label, env, geom, route in mod.route_plan():
+            _clear_switches(monkeypatch)
+            for k, v in env.items():
+                if v is not None:
+                    monkeypatch.setenv(k, v)
+            assert G.conv_route(**geom) == route, (label, env, geom)
+            seen.setdefault(mod.__name__, set()).add(route)
+            n += 1
+        assert n > 0
+    assert seen["test_gpu_stages"] == set(G.ROUTES) and seen["test_gpu_conv_exact"] == set(G.ROUTES)
+    assert seen["test_gpu_lxmert"] == {"generic", "duo"}
+
+
+def test_conv_route_refuses_what_the_launch_refuses(lib):
+    import gpu_util as G
+    with pytest.raises(ValueError, match="multiple of"):
+        G.conv_route(1, 8, 8, 48, 64)                       # Cin not a whole number of K-tiles
+    with pytest.raises(ValueError, match="dual-source"):
+        G.conv_route(1, 1, 4096, 64, 100, cin2=64)          # Cout % 256 != 0
+    with pytest.raises(ValueError, match="fused-mean"):
+        G.conv_route(4, 1, 64, 512, 512, mean=True, res=True)       # fewer than 128 rows per image
+    assert lib.vk_conv_route(0, 8, 8, 64, 0, 0, 0, 64, 64, 1, 1, 1, 0, 1, 1, 0, L.VK_F16, L.VK_F16) == -L.VK_EINVAL
+
+
+def test_every_pinned_launch_states_its_route():
+    """No test of the three GPU files that sets a kernel switch launches without `expect_route=` (the switch may be set through
+    a `*_legs` / `*_env` table: then the test calls `_set_env`): such a test states a route, and none of its launches of the four
+    entry points is a bare `L.call`."""
+    pat = re.compile(r"VK_(CONV|WS|GEMM4|PANEL)\w*|_set_env\(")
+    for name in ("test_gpu_stages.py", "test_gpu_bneck_fused.py", "test_gpu_lxmert.py"):
+        src = open(os.path.join(ROOT, "tests", name)).read()
+        for body in re.split(r"\n(?=def |@pytest)", src):
+            m = re.match(r"def (test_\w+)", body)
+            if m and pat.search(body) and ("setenv(" in body or "_set_env(" in body):
+                assert "expect_route=" in body, f"{name}::{m.group(1)} sets a kernel switch and launches without expect_route"
+                bare = re.search(r'L\.call\("(vk_conv2d|vk_conv1x1_dual|vk_conv1x1_meanpool|vk_linear)"', body)
+                assert not bare, f"{name}::{m.group(1)} launches {bare.group(1)} under a kernel switch without stating its route"

@@ -69,10 +69,40 @@ def packed(p, proj):
     return w1d, b1d, w2d, b2d, w3d, b3d
 
 
+def layer_routes(N, H, W, proj):
+    """The kernels of run_layers' three launches: conv1 (64 outputs: the generic kernel's 64-wide tile), the dense 64 -> 64 3x3
+    (block kernel), conv3 (+ residual / + shortcut as a second input): weight-stationary from 1024 pixels on, below that the
+    generic kernel (one input) / the two-per-CU kernel (two)."""
+    return "generic", "blk", "ws" if N * H * W >= 1024 else ("duo" if proj else "generic")
+
+
+def layer_geoms(N, H, W, proj):
+    cin = 64 if proj else 256
+    c3 = dict(N=1, H=1, W=N * H * W, cin=64, cin2=cin, cout=256, relu=1) if proj else dict(N=N, H=H, W=W, cin=64, cout=256, relu=1, res=True)
+    return dict(N=N, H=H, W=W, cin=cin, cout=64, relu=1), dict(N=N, H=H, W=W, cin=64, cout=64, k=3, pad=1, relu=1), c3
+
+
+FUSED_SHAPES = [(2, 16, 64), (1, 8, 32), (3, 13, 45), (2, 40, 70), (1, 5, 7), (1, 1, 1), (2, 3, 31), (1, 67, 30), (1, 200, 333)]
+
+
+def route_plan():
+    """(label, environment, gpu_util.conv_route arguments, kernel) of every run_layers launch, for the CPU suite (tests/test_abi.py)."""
+    for shape in FUSED_SHAPES + [(8, 200, 333)]:
+        for proj in (False, True):
+            for geom, r in zip(layer_geoms(*shape, proj), layer_routes(*shape, proj)):
+                yield f"run_layers[{shape}-{proj}]", {}, geom, r
+
+
+def fused_eligible(N, H, W, cin, proj):
+    """vk_bottleneck64_eligible for the block these tests build (its rows / tile form is VK_BNECK_ROWS, read by the launcher)."""
+    return L.load().vk_bottleneck64_eligible(cin, 64, 256, 1, 1, 1, int(proj), int(proj), N, H, W, L.VK_F16) == 1
+
+
 def run_fused(x, p, proj):
     w1d, b1d, w2d, b2d, w3d, b3d = packed(p, proj)
     xd = G.to_nhwc(x, L.VK_F16)
     N, H, W, cin = xd.shape
+    assert fused_eligible(N, H, W, cin, proj), "the model would not run this block on vk_bottleneck64"
     y = torch.full((N, H, W, 256), float("nan"), dtype=torch.float16, device=G.DEV)
     L.call("vk_bottleneck64", G.P(xd), N, H, W, cin, int(proj), G.P(w1d), G.P(b1d), G.P(w2d), G.P(b2d), G.P(w3d), G.P(b3d), G.P(y), G.stream())
     torch.cuda.synchronize()
@@ -88,19 +118,24 @@ def run_layers(x, p, proj):
     t1 = torch.empty((N, H, W, 64), dtype=torch.float16, device=G.DEV)
     t2 = torch.empty_like(t1)
     y = torch.empty((N, H, W, 256), dtype=torch.float16, device=G.DEV)
-    L.call("vk_conv2d", G.P(xd), N, H, W, cin, G.P(w1d), G.P(b1d), None, G.P(t1), 64, 64, 1, 1, 1, 0, 1, 1, 1, dt, dt, G.stream())
-    L.call("vk_conv2d", G.P(t1), N, H, W, 64, G.P(w2d), G.P(b2d), None, G.P(t2), 64, 64, 3, 3, 1, 1, 1, 1, 1, dt, dt, G.stream())
+    r1, r2, r3 = layer_routes(N, H, W, proj)
+    G.launch("vk_conv2d", G.P(xd), N, H, W, cin, G.P(w1d), G.P(b1d), None, G.P(t1), 64, 64, 1, 1, 1, 0, 1, 1, 1, dt, dt, G.stream(),
+             expect_route=r1)
+    G.launch("vk_conv2d", G.P(t1), N, H, W, 64, G.P(w2d), G.P(b2d), None, G.P(t2), 64, 64, 3, 3, 1, 1, 1, 1, 1, dt, dt, G.stream(),
+             expect_route=r2)
     if proj:
-        L.call("vk_conv1x1_dual", G.P(t2), 64, G.P(xd), cin, N * H * W, G.P(w3d), G.P(b3d), None, G.P(y), 256, 1, G.stream())
+        G.launch("vk_conv1x1_dual", G.P(t2), 64, G.P(xd), cin, N * H * W, G.P(w3d), G.P(b3d), None, G.P(y), 256, 1, G.stream(),
+                 expect_route=r3)
     else:
-        L.call("vk_conv2d", G.P(t2), N, H, W, 64, G.P(w3d), G.P(b3d), G.P(xd), G.P(y), 256, 256, 1, 1, 1, 0, 1, 1, 1, dt, dt, G.stream())
+        G.launch("vk_conv2d", G.P(t2), N, H, W, 64, G.P(w3d), G.P(b3d), G.P(xd), G.P(y), 256, 256, 1, 1, 1, 0, 1, 1, 1, dt, dt, G.stream(),
+                 expect_route=r3)
     torch.cuda.synchronize()
     return y
 
 
 @pytest.mark.parametrize("form", ["rows", "tiles"])
 @pytest.mark.parametrize("proj", [False, True], ids=["identity", "projection"])
-@pytest.mark.parametrize("shape", [(2, 16, 64), (1, 8, 32), (3, 13, 45), (2, 40, 70), (1, 5, 7), (1, 1, 1), (2, 3, 31), (1, 67, 30), (1, 200, 333)],
+@pytest.mark.parametrize("shape", FUSED_SHAPES,
                          ids=lambda s: "x".join(map(str, s)))
 def test_bottleneck64_vs_reference_and_layers(shape, proj, form, monkeypatch):
     """Both forms of the kernel (row-streaming column strips, the default; 8 x 32 tiles): whole strips / tiles, ragged edges in both
@@ -152,6 +187,7 @@ def test_bottleneck64_beyond_two_gigabytes():
     p = make_block(5, 256, False)
     w1d, b1d, w2d, b2d, w3d, b3d = packed(p, False)
     y = torch.full((N, H, W, 256), float("nan"), dtype=torch.float16, device=G.DEV)
+    assert fused_eligible(N, H, W, 256, False)
     L.call("vk_bottleneck64", G.P(xd), N, H, W, 256, 0, G.P(w1d), G.P(b1d), G.P(w2d), G.P(b2d), G.P(w3d), G.P(b3d), G.P(y), G.stream())
     torch.cuda.synchronize()
     assert torch.isfinite(y[-1].float()).all() and torch.isfinite(y[0].float()).all()

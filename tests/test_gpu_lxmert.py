@@ -34,11 +34,33 @@ def g(golden_dir):
     return np.load(os.path.join(golden_dir, "lxmert_small.npz"))
 
 
+# the last two: LXMERT's feed-forward (768 -> 3072 with GELU, 3072 -> 768 with the residual) at a benchmark batch's row count, ragged
+# against the 128-row tile
+LINEAR_CASES = [(77, 128, 128, 0, False), (396, 256, 768, 2, False), (108, 768, 256, 0, True),
+                (33, 2048, 128, 3, False), (640, 128, 384, 1, True), (2600, 768, 3072, 2, False), (2600, 3072, 768, 0, True)]
+
+
+def linear_route(dt, M, K, N, act, res):
+    """Below 1024 rows every linear runs on the generic kernel; from there on the two-per-CU kernel takes the f16 and bf16 ones,
+    its GELU epilogue in the bf16 build only."""
+    if M < 1024 or dt == L.VK_F32 or (act == 2 and dt != L.VK_BF16):
+        return "generic"
+    return "duo"
+
+
+def route_plan():
+    """(label, environment, gpu_util.conv_route arguments, kernel) of test_linear's launches, for the CPU suite (tests/test_abi.py)."""
+    for dt in (L.VK_F32, L.VK_F16, L.VK_BF16):
+        for M, K, N, act, res in LINEAR_CASES:
+            yield (f"test_linear[{M}-{K}-{N}-{act}-{res}-{dt}]", {}, dict(N=1, H=1, W=M, cin=K, cout=N, relu=act, res=res, dt=dt),
+                   linear_route(dt, M, K, N, act, res))
+
+
 @pytest.mark.parametrize("dt", [L.VK_F32, L.VK_F16, L.VK_BF16], ids=IDS)
-@pytest.mark.parametrize("M,K,N,act,res", [(77, 128, 128, 0, False), (396, 256, 768, 2, False), (108, 768, 256, 0, True),
-                                           (33, 2048, 128, 3, False), (640, 128, 384, 1, True)])
+@pytest.mark.parametrize("M,K,N,act,res", LINEAR_CASES)
 def test_linear(dt, M, K, N, act, res):
-    """nn.Linear + residual + {ReLU, GELU(erf), tanh} on the MFMA GEMM (bf16: v_mfma_f32_16x16x32_bf16)."""
+    """nn.Linear + residual + {ReLU, GELU(erf), tanh} on the MFMA GEMM (bf16: v_mfma_f32_16x16x32_bf16); from 1024 rows on the
+    two-per-CU kernel (its bf16 build with the GELU epilogue is what the encoder's linears run on at benchmark batch sizes)."""
     gen = np.random.Generator(np.random.PCG64(M + K))
     td = TDT[dt]
     x = torch.from_numpy(gen.standard_normal((M, K)).astype(np.float32)).to(td)
@@ -48,7 +70,8 @@ def test_linear(dt, M, K, N, act, res):
     wp, bp = G.pack_conv(w.reshape(N, K, 1, 1), None, b, dt)
     xd, rd = x.to(G.DEV), (r.to(G.DEV) if res else None)
     y = torch.empty((M, N), dtype=td, device=G.DEV)
-    L.call("vk_linear", G.P(xd), M, K, G.P(wp), G.P(bp), G.P(rd), G.P(y), N, N, act, dt, dt, G.stream())
+    G.launch("vk_linear", G.P(xd), M, K, G.P(wp), G.P(bp), G.P(rd), G.P(y), N, N, act, dt, dt, G.stream(),
+             expect_route=linear_route(dt, M, K, N, act, res))
     torch.cuda.synchronize()
     ref = x.float() @ torch.from_numpy(w).to(td).float().t() + torch.from_numpy(b)
     if res:

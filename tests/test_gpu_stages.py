@@ -4,8 +4,14 @@ Tolerances (metric: max|a-b| / max|ref|):
   * convolution / GEMM, fp32 strict mode ...... 2e-5 (exact-f32 MFMA, different summation order)
   * convolution / GEMM, fp16 fast mode ........ 1e-3 against the fp16-emulating oracle
     (same fp16-rounded operands, fp32 accumulate; differences = summation order + one fp16 ulp)
+  * convolution on integer data ............... bit-exact (tests/test_gpu_conv_exact.py: the anchor of every conv kernel)
   * pooling, NMS, top-k, index outputs ........ bit-exact
   * box decode ................................ 2e-6 (expf implementations differ by <= 1 ulp)
+
+Every launch of a test that is about one kernel names that kernel (`expect_route=`): the dispatcher is asked
+(vk_conv_route) immediately before the launch, so a change of an eligibility rule cannot quietly empty an A/B test.  The
+`*_legs` functions below hold, per case, the environment of each run and the kernel it must run on; tests/test_abi.py
+checks the same tables against the dispatcher without a GPU (`route_plan`).
 """
 import ctypes as C
 import os
@@ -69,14 +75,59 @@ CONV_CASES = [
 ]
 
 
+# fp16 route of the cases that are named after a shape, not a kernel, under test_conv's first environment
+CONV_SHAPE_ROUTES = {"1x1": "generic", "1x1_narrow": "generic", "1x1_s2": "generic", "3x3": "blk", "3x3_wide": "generic",
+                     "3x3_dil2": "generic", "1x1_res": "generic", "3x3_s2": "generic", "1x1_big": "ws"}
+# the cases that the weight-stationary kernel takes when nothing pins it: that run is kept as a second leg
+CONV_ALSO_WS = ("ring_s2", "ring_s4", "ring_1x1_k512", "ring_1x1_s2", "duo_s2", "duo_s4", "duo_s16", "duo_s2_stride2")
+
+
+def _set_env(monkeypatch, env):
+    for k, v in env.items():
+        if v is None:
+            monkeypatch.delenv(k, raising=False)
+        else:
+            monkeypatch.setenv(k, v)
+
+
+# test_conv's further runs of a panel case, each bit-identical to the first: 288- and 256-pixel tiles (9 / 8 row tiles per wave; the
+# launcher picks by grid rounds), then the epilogue straight from the accumulators against its first form through LDS (halo-64
+# build: VK_CONV256_DBG=8)
+PANEL_FORM_LEGS = (({"VK_PANEL_MI": "9"}, "panel"), ({"VK_PANEL_MI": "8"}, "panel"), ({"VK_PANEL_MI": "8", "VK_CONV256_DBG": "8"}, "panel"))
+
+
+def panel_mi9_legal(W, dil):
+    """conv3x3_panel.hip panel_pp: 9 row tiles need the halo dil * (W + 1) <= 112; beyond that VK_PANEL_MI=9 silently runs 8 and the
+    8 / 9 comparison would be empty."""
+    return dil * (W + 1) <= 112
+
+
+def conv_geom(case, dt):
+    _, N, H, W, cin, cout, k, stride, pad, dil, use_res, relu = case
+    return dict(N=N, H=H, W=W, cin=cin, cout=cout, k=k, stride=stride, pad=pad, dil=dil, relu=int(relu), res=use_res, dt=dt)
+
+
+def conv_legs(case, dt):
+    """[(environment, kernel)] of test_conv's runs.  The dispatcher re-reads the switches per call: "ring_*" cases pin the
+    256x256 ring kernel and "duo_*" the two-per-CU kernel, which the weight-stationary / four-wave / panel kernels would
+    otherwise take over; fp32 always runs the generic kernel."""
+    name = case[0]
+    ring = name.startswith("ring_")
+    env = {"VK_CONV_DUO": "0" if ring else "1", "VK_CONV3X3_PANEL": "0" if ring else "1", "VK_CONV_WS": None, "VK_CONV_GEMM4": None}
+    if dt != L.VK_F16:
+        return [(env, "generic")]
+    if ring or name.startswith("duo_"):
+        legs = [(dict(env, VK_CONV_WS="0", VK_CONV_GEMM4="0"), "ring" if ring else "duo")]
+        if name in CONV_ALSO_WS:
+            legs.append((env, "ws"))
+        return legs
+    return [(env, "panel" if name.startswith("panel_") else CONV_SHAPE_ROUTES[name])]
+
+
 @pytest.mark.parametrize("dt", [L.VK_F32, L.VK_F16], ids=["fp32", "fp16"])
 @pytest.mark.parametrize("case", CONV_CASES, ids=[c[0] for c in CONV_CASES])
 def test_conv(case, dt, monkeypatch):
     _, N, H, W, cin, cout, k, stride, pad, dil, use_res, relu = case
-    # the dispatcher re-reads these per call: "ring_*" cases pin the 256x256 ring kernel, which the 1x1 /
-    # panel kernels would otherwise take over
-    monkeypatch.setenv("VK_CONV_DUO", "0" if case[0].startswith("ring_") else "1")
-    monkeypatch.setenv("VK_CONV3X3_PANEL", "0" if case[0].startswith("ring_") else "1")
     g = _rng(zlib.crc32(case[0].encode()))
     x = torch.from_numpy(g.standard_normal((N, cin, H, W)).astype(np.float32))
     w = (g.standard_normal((cout, cin, k, k)) * (2.0 / (cin * k * k)) ** 0.5).astype(np.float32)
@@ -84,7 +135,6 @@ def test_conv(case, dt, monkeypatch):
     Ho = (H + 2 * pad - (dil * (k - 1) + 1)) // stride + 1
     Wo = (W + 2 * pad - (dil * (k - 1) + 1)) // stride + 1
     res = torch.from_numpy(g.standard_normal((N, cout, Ho, Wo)).astype(np.float32)) if use_res else None
-    y = G.conv2d(x, w, bn=bn, residual_nchw=res, stride=stride, pad=pad, dil=dil, relu=relu, dt=dt)
     wf, bf = G.fold_ref(w, bn, dt)
     q = (lambda t: t.half().float()) if dt == L.VK_F16 else (lambda t: t)
     ref = F.conv2d(q(x), wf, None, stride, pad, dil) + bf.view(1, -1, 1, 1)
@@ -94,17 +144,17 @@ def test_conv(case, dt, monkeypatch):
         ref = F.relu(ref)
     ref = q(ref)
     tol = 1e-3 if dt == L.VK_F16 else 2e-5
-    assert G.rel_err(y, ref) <= tol
+    for env, route in conv_legs(case, dt):
+        _set_env(monkeypatch, env)
+        y = G.conv2d(x, w, bn=bn, residual_nchw=res, stride=stride, pad=pad, dil=dil, relu=relu, dt=dt, expect_route=route)
+        assert G.rel_err(y, ref) <= tol, route
     if case[0].startswith("panel_") and dt == L.VK_F16:
-        # 256- and 288-pixel tiles (8 / 9 row tiles per wave; the launcher picks by grid rounds) give the same bits
-        monkeypatch.setenv("VK_PANEL_MI", "9")
-        y9 = G.conv2d(x, w, bn=bn, residual_nchw=res, stride=stride, pad=pad, dil=dil, relu=relu, dt=dt)
-        monkeypatch.setenv("VK_PANEL_MI", "8")
-        y8 = G.conv2d(x, w, bn=bn, residual_nchw=res, stride=stride, pad=pad, dil=dil, relu=relu, dt=dt)
-        assert torch.equal(y8, y9) and torch.equal(y, y8)
-        # the panel kernel's epilogue straight from the accumulators against its first form through LDS (halo-64 build: VK_CONV256_DBG=8)
-        monkeypatch.setenv("VK_CONV256_DBG", "8")
-        assert torch.equal(y, G.conv2d(x, w, bn=bn, residual_nchw=res, stride=stride, pad=pad, dil=dil, relu=relu, dt=dt))
+        assert panel_mi9_legal(W, dil)
+        ys = []
+        for env, route in PANEL_FORM_LEGS:
+            _set_env(monkeypatch, env)
+            ys.append(G.conv2d(x, w, bn=bn, residual_nchw=res, stride=stride, pad=pad, dil=dil, relu=relu, dt=dt, expect_route=route))
+        assert all(torch.equal(y, t) for t in ys)
 
 
 GROUPED_CASES = [
@@ -118,19 +168,35 @@ GROUPED_CASES = [
 ]
 
 
+def grouped_geom(case, dt):
+    _, N, H, W, c, groups, stride, dil = case
+    return dict(N=N, H=H, W=W, cin=c, cout=c, k=3, stride=stride, pad=dil, dil=dil, groups=groups, relu=1, dt=dt)
+
+
+def grouped_legs(case, dt):
+    """The slice-diagonal form of the generic kernel; in fp16 the block kernel takes the four ResNeXt shapes first (that run
+    is the second leg)."""
+    legs = [({"VK_CONV3X3_BLK": "0"}, "generic")]
+    if dt == L.VK_F16 and case[0].startswith("x152_"):
+        legs.append(({"VK_CONV3X3_BLK": None}, "blk"))
+    return legs
+
+
 @pytest.mark.parametrize("dt", [L.VK_F32, L.VK_F16], ids=["fp32", "fp16"])
 @pytest.mark.parametrize("case", GROUPED_CASES, ids=[c[0] for c in GROUPED_CASES])
-def test_grouped_conv(case, dt):
+def test_grouped_conv(case, dt, monkeypatch):
     _, N, H, W, c, groups, stride, dil = case
     g = _rng(zlib.crc32(case[0].encode()))
     x = torch.from_numpy(g.standard_normal((N, c, H, W)).astype(np.float32))
     w = (g.standard_normal((c, c // groups, 3, 3)) * (2.0 / (c // groups * 9)) ** 0.5).astype(np.float32)
     bn = (g.uniform(0.5, 1.5, c), g.standard_normal(c) * 0.1, g.standard_normal(c) * 0.1, g.uniform(0.5, 1.5, c))
-    y = G.conv2d(x, w, bn=bn, stride=stride, pad=dil, dil=dil, relu=True, dt=dt, groups=groups)
     wf, bf = G.fold_ref(w, bn, dt)
     q = (lambda t: t.half().float()) if dt == L.VK_F16 else (lambda t: t)
     ref = q(F.relu(F.conv2d(q(x), wf, None, stride, dil, dil, groups) + bf.view(1, -1, 1, 1)))
-    assert G.rel_err(y, ref) <= (1e-3 if dt == L.VK_F16 else 2e-5)
+    for env, route in grouped_legs(case, dt):
+        _set_env(monkeypatch, env)
+        y = G.conv2d(x, w, bn=bn, stride=stride, pad=dil, dil=dil, relu=True, dt=dt, groups=groups, expect_route=route)
+        assert G.rel_err(y, ref) <= (1e-3 if dt == L.VK_F16 else 2e-5), route
 
 
 BLK_CASES = [
@@ -145,6 +211,14 @@ BLK_CASES = [
 ]
 
 
+BLK_LEGS = (("1", "blk"), ("0", "generic"))                 # VK_CONV3X3_BLK, kernel
+
+
+def blk_geom(case):
+    _, N, H, W, c, groups, dil = case
+    return dict(N=N, H=H, W=W, cin=c, cout=c, k=3, pad=dil, dil=dil, groups=groups, relu=int(c != 128))
+
+
 @pytest.mark.parametrize("case", BLK_CASES, ids=[c[0] for c in BLK_CASES])
 def test_conv3x3_blk_kernel(case, monkeypatch):
     """conv3x3_blk.hip against the fp32 reference AND bit-for-bit against the im2col kernel it replaces (same K order; the
@@ -155,9 +229,9 @@ def test_conv3x3_blk_kernel(case, monkeypatch):
     w = (g.standard_normal((c, c // groups, 3, 3)) * (2.0 / (c // groups * 9)) ** 0.5).astype(np.float32)
     bn = (g.uniform(0.5, 1.5, c), g.standard_normal(c) * 0.1, g.standard_normal(c) * 0.1, g.uniform(0.5, 1.5, c))
     ys = []
-    for on in ("1", "0"):
+    for on, route in BLK_LEGS:
         monkeypatch.setenv("VK_CONV3X3_BLK", on)
-        ys.append(G.conv2d(x, w, bn=bn, stride=1, pad=dil, dil=dil, relu=(c != 128), dt=L.VK_F16, groups=groups))
+        ys.append(G.conv2d(x, w, bn=bn, stride=1, pad=dil, dil=dil, relu=(c != 128), dt=L.VK_F16, groups=groups, expect_route=route))
     assert torch.equal(ys[0], ys[1])
     wf, bf = G.fold_ref(w, bn, L.VK_F16)
     ref = F.conv2d(x.half().float(), wf, None, 1, dil, dil, groups) + bf.view(1, -1, 1, 1)
@@ -165,9 +239,29 @@ def test_conv3x3_blk_kernel(case, monkeypatch):
     assert G.rel_err(ys[0], ref) <= 1e-3
 
 
-@pytest.mark.parametrize("M,c1,c2,cout,res", [(1500, 64, 64, 256, False), (33403, 64, 64, 256, False), (9000, 64, 64, 512, True), (4000, 512, 1024, 512, False),
-                                              (130, 128, 256, 256, True), (2600, 128, 192, 256, True),
-                                              (2500, 512, 1024, 2048, False), (1030, 256, 768, 256, True)])
+DUAL_CASES = [(1500, 64, 64, 256, False), (33403, 64, 64, 256, False), (9000, 64, 64, 512, True), (4000, 512, 1024, 512, False),
+              (130, 128, 256, 256, True), (2600, 128, 192, 256, True),
+              (2500, 512, 1024, 2048, False), (1030, 256, 768, 256, True)]
+# the switches test_conv1x1_dual turns off, run after run, and the kernel of each run: 64 + 64 channels; K >= 1024 at M >= 2048;
+# K >= 1024 below the four-wave GEMM's floor; short K
+DUAL_OFF = ((), ("VK_CONV_WS",), ("VK_CONV_WS", "VK_CONV_GEMM4"), ("VK_CONV_WS", "VK_CONV_GEMM4", "VK_CONV256_DUAL"))
+
+
+def dual_geom(M, c1, c2, cout, res):
+    return dict(N=1, H=1, W=M, cin=c1, cin2=c2, cout=cout, relu=1, res=res)
+
+
+def dual_legs(M, c1, c2, cout, res):
+    if c1 == 64 and c2 == 64:
+        routes = ("ws", "duo", "duo", "duo")
+    elif c1 + c2 >= 1024:
+        routes = ("gemm4", "gemm4", "ring", "duo") if M >= 2048 else ("ring", "ring", "ring", "duo")
+    else:
+        routes = ("duo",) * 4
+    return [(dict({"VK_CONV_GEMM4": "2"}, **{k: "0" for k in off}), r) for off, r in zip(DUAL_OFF, routes)]
+
+
+@pytest.mark.parametrize("M,c1,c2,cout,res", DUAL_CASES)
 def test_conv1x1_dual(M, c1, c2, cout, res, monkeypatch):
     """conv3 + stride-1 projection shortcut as one GEMM (`out += shortcut`, frcnn.py:970-977): two inputs, K = c1 + c2.
     K >= 1024 runs on the 256 x 256 ring kernel, shorter K on the two-per-CU kernel; where both apply they give the same bits."""
@@ -185,18 +279,20 @@ def test_conv1x1_dual(M, c1, c2, cout, res, monkeypatch):
     wcat = torch.cat([p1.view(rows, c1 * 2), p2.view(rows, c2 * 2)], dim=1).contiguous()
     x1d, x2d, rd = x1.to(G.DEV), x2.to(G.DEV), (r.to(G.DEV) if res else None)
     y = torch.empty((M, cout), dtype=torch.float16, device=G.DEV)
-    monkeypatch.setenv("VK_CONV_GEMM4", "2")                # the four-wave GEMM also on grids this small
-    L.call("vk_conv1x1_dual", G.P(x1d), c1, G.P(x2d), c2, M, G.P(wcat), G.P(b1 + b2), G.P(rd), G.P(y), cout, 1, G.stream())
+    legs = dual_legs(M, c1, c2, cout, res)
+    _set_env(monkeypatch, legs[0][0])                       # VK_CONV_GEMM4=2: the four-wave GEMM also on grids this small
+    G.launch("vk_conv1x1_dual", G.P(x1d), c1, G.P(x2d), c2, M, G.P(wcat), G.P(b1 + b2), G.P(rd), G.P(y), cout, 1, G.stream(),
+             expect_route=legs[0][1])
     torch.cuda.synchronize()
     # the same layer on the other kernels that take it: weight-stationary kernel (64 + 64 channels) / four-wave GEMM (K >= 1024) ->
     # ring kernel -> two-per-CU kernel
-    for off in (("VK_CONV_WS",), ("VK_CONV_WS", "VK_CONV_GEMM4"), ("VK_CONV_WS", "VK_CONV_GEMM4", "VK_CONV256_DUAL")):
-        for k in off:
-            monkeypatch.setenv(k, "0")
+    for env, route in legs[1:]:
+        _set_env(monkeypatch, env)
         y2 = torch.full_like(y, float("nan"))
-        L.call("vk_conv1x1_dual", G.P(x1d), c1, G.P(x2d), c2, M, G.P(wcat), G.P(b1 + b2), G.P(rd), G.P(y2), cout, 1, G.stream())
+        G.launch("vk_conv1x1_dual", G.P(x1d), c1, G.P(x2d), c2, M, G.P(wcat), G.P(b1 + b2), G.P(rd), G.P(y2), cout, 1, G.stream(),
+                 expect_route=route)
         torch.cuda.synchronize()
-        assert torch.equal(y, y2), off
+        assert torch.equal(y, y2), env
     f1, fb1 = G.fold_ref(w1, bn1, L.VK_F16)
     f2, fb2 = G.fold_ref(w2, bn2, L.VK_F16)
     ref = x1.float() @ f1.view(cout, c1).t() + x2.float() @ f2.view(cout, c2).t() + (fb1 + fb2)
@@ -206,8 +302,33 @@ def test_conv1x1_dual(M, c1, c2, cout, res, monkeypatch):
     assert G.rel_err(y.float().cpu(), ref) <= 1e-3
 
 
-@pytest.mark.parametrize("N,HW,cin,cout", [(7, 196, 128, 256), (23, 196, 512, 512), (3, 255, 64, 256), (1, 128, 64, 256),
-                                           (301, 196, 512, 2048), (40, 130, 256, 1024), (9, 130, 512, 256)])
+MEANPOOL_CASES = [(7, 196, 128, 256), (23, 196, 512, 512), (3, 255, 64, 256), (1, 128, 64, 256),
+                  (301, 196, 512, 2048), (40, 130, 256, 1024), (9, 130, 512, 256)]
+
+
+def meanpool_geom(N, HW, cin, cout):
+    return dict(N=N, H=1, W=HW, cin=cin, cout=cout, relu=1, res=True, mean=True)
+
+
+def meanpool_route(N, HW, cin, cout):
+    """The weight-stationary kernel's fp64 sums from K = 512 and 1024 rows on; else the two-per-CU kernel's integer partials."""
+    return "ws" if cin == 512 and N * HW >= 1024 else "duo"
+
+
+def meanpool_legs(N, HW, cin, cout):
+    """(environment, images, kernel) of test_conv1x1_meanpool's launches: the default kernel (run twice), the two-per-CU kernel, and
+    -- from three images on -- the default kernel on the images behind the first two."""
+    legs = [({"VK_CONV_WS": None}, N, meanpool_route(N, HW, cin, cout)), ({"VK_CONV_WS": "0"}, N, "duo")]
+    if N > 2:
+        legs.append(({"VK_CONV_WS": None}, N - 2, meanpool_route(N - 2, HW, cin, cout)))
+    return legs
+
+
+NONFINITE_SHAPE = (12, 196, 512, 512)
+NONFINITE_LEGS = {"1": "ws", "0": "duo"}                    # VK_CONV_WS -> kernel of test_conv1x1_meanpool_nonfinite
+
+
+@pytest.mark.parametrize("N,HW,cin,cout", MEANPOOL_CASES)
 def test_conv1x1_meanpool(N, HW, cin, cout, monkeypatch):
     """Last Res5 conv3 + residual + ReLU with `.mean(dim=[2,3])` (frcnn.py:1401) folded into the epilogue: equal to
     conv -> f16 -> mean, bit-reproducible, and the same bits from the weight-stationary kernel (K = 512: 64-row tiles,
@@ -222,32 +343,37 @@ def test_conv1x1_meanpool(N, HW, cin, cout, monkeypatch):
     wp, bp = G.pack_conv(w, bn, None, L.VK_F16)
     xd, rd = x.to(G.DEV), r.to(G.DEV)
     nb = L.load().vk_conv1x1_meanpool_workspace_bytes(N, HW, cout)
+    legs = meanpool_legs(N, HW, cin, cout)
     outs = []
+    _set_env(monkeypatch, legs[0][0])
     for _ in range(2):
         ws = torch.empty(nb, dtype=torch.uint8, device=G.DEV)
         out = torch.empty((N, cout), dtype=torch.float32, device=G.DEV)
-        L.call("vk_conv1x1_meanpool", G.P(xd), N, HW, cin, G.P(wp), G.P(bp), G.P(rd), cout, 1, G.P(out), G.P(ws), nb, G.stream())
+        G.launch("vk_conv1x1_meanpool", G.P(xd), N, HW, cin, G.P(wp), G.P(bp), G.P(rd), cout, 1, G.P(out), G.P(ws), nb, G.stream(),
+                 expect_route=legs[0][2])
         torch.cuda.synchronize()
         outs.append(out.cpu())
     assert torch.equal(outs[0], outs[1])
-    monkeypatch.setenv("VK_CONV_WS", "0")
+    _set_env(monkeypatch, legs[1][0])
     ws = torch.empty(nb, dtype=torch.uint8, device=G.DEV)
     out = torch.empty((N, cout), dtype=torch.float32, device=G.DEV)
-    L.call("vk_conv1x1_meanpool", G.P(xd), N, HW, cin, G.P(wp), G.P(bp), G.P(rd), cout, 1, G.P(out), G.P(ws), nb, G.stream())
+    G.launch("vk_conv1x1_meanpool", G.P(xd), N, HW, cin, G.P(wp), G.P(bp), G.P(rd), cout, 1, G.P(out), G.P(ws), nb, G.stream(),
+             expect_route=legs[1][2])
     torch.cuda.synchronize()
     assert torch.equal(outs[0], out.cpu())
-    monkeypatch.delenv("VK_CONV_WS")
     wf, bf = G.fold_ref(w, bn, L.VK_F16)
     y = F.relu(x.float() @ wf.view(cout, cin).t() + bf + r.float()).half().float()
     ref = y.view(N, HW, cout).mean(dim=1)
     assert G.rel_err(outs[0], ref) <= 1e-3
     # position independence: the same images behind a different number of leading rows give the same bits
-    if N > 2:
-        k = 2
+    for env, n2, route in legs[2:]:
+        _set_env(monkeypatch, env)
+        k = N - n2
         out2 = torch.empty((N - k, cout), dtype=torch.float32, device=G.DEV)
         ws = torch.empty(nb, dtype=torch.uint8, device=G.DEV)
         xs, rs = xd[k * HW:].contiguous(), rd[k * HW:].contiguous()
-        L.call("vk_conv1x1_meanpool", G.P(xs), N - k, HW, cin, G.P(wp), G.P(bp), G.P(rs), cout, 1, G.P(out2), G.P(ws), nb, G.stream())
+        G.launch("vk_conv1x1_meanpool", G.P(xs), N - k, HW, cin, G.P(wp), G.P(bp), G.P(rs), cout, 1, G.P(out2), G.P(ws), nb, G.stream(),
+                 expect_route=route)
         torch.cuda.synchronize()
         assert torch.equal(out2.cpu(), outs[0][k:])
 
@@ -257,7 +383,7 @@ def test_conv1x1_meanpool_nonfinite(ws, monkeypatch):
     """An output that overflows f16 makes that image's mean of that channel NaN and touches nothing else -- on both
     fused-mean kernels, including an image that shares its 64-row tile with the overflowing one."""
     monkeypatch.setenv("VK_CONV_WS", ws)
-    N, HW, cin, cout = 12, 196, 512, 512
+    N, HW, cin, cout = NONFINITE_SHAPE
     g = _rng(5)
     M = N * HW
     x = torch.from_numpy(g.standard_normal((M, cin)).astype(np.float32)).half()
@@ -272,7 +398,8 @@ def test_conv1x1_meanpool_nonfinite(ws, monkeypatch):
         rd = rr.to(G.DEV)
         ws_ = torch.empty(nb, dtype=torch.uint8, device=G.DEV)
         out = torch.empty((N, cout), dtype=torch.float32, device=G.DEV)
-        L.call("vk_conv1x1_meanpool", G.P(xd), N, HW, cin, G.P(wp), G.P(bp), G.P(rd), cout, 1, G.P(out), G.P(ws_), nb, G.stream())
+        G.launch("vk_conv1x1_meanpool", G.P(xd), N, HW, cin, G.P(wp), G.P(bp), G.P(rd), cout, 1, G.P(out), G.P(ws_), nb, G.stream(),
+                 expect_route=NONFINITE_LEGS[ws])
         torch.cuda.synchronize()
         return out.cpu()
 
@@ -290,19 +417,34 @@ def test_conv1x1_meanpool_nonfinite(ws, monkeypatch):
     assert torch.equal(out[~mask], clean[~mask])
 
 
-@pytest.mark.parametrize("kernel", ["duo", "ring", "panel"])
+def scale_shape(kernel):
+    return (64, 14, 14, 256, 512, 3, 2, 2) if kernel == "panel" else (300, 14, 14, 512, 2048, 1, 0, 1)
+
+
+def scale_env(kernel):
+    """The named kernel; "ws": nothing pinned, the weight-stationary kernel takes 512 -> 2048 as it does in production."""
+    if kernel == "ws":
+        return {"VK_CONV_DUO": None, "VK_CONV3X3_PANEL": None, "VK_CONV_WS": None, "VK_CONV_GEMM4": None}
+    return {"VK_CONV_DUO": "1" if kernel == "duo" else "0", "VK_CONV3X3_PANEL": "1" if kernel == "panel" else "0", "VK_CONV_WS": "0",
+            "VK_CONV_GEMM4": "0"}
+
+
+def scale_geom(kernel):
+    N, H, W, cin, cout, k, pad, dil = scale_shape(kernel)
+    return dict(N=N, H=H, W=W, cin=cin, cout=cout, k=k, pad=pad, dil=dil, relu=1, res=True)
+
+
+SCALE_KERNELS = ["duo", "ring", "panel", "ws"]
+
+
+@pytest.mark.parametrize("kernel", SCALE_KERNELS)
 def test_conv_reproducible_at_scale(kernel, monkeypatch):
     """Thousands of workgroups, launched back to back: bit-identical output run to run and no wrong block.  (A copy
     of a fragment register whose hand-issued ds_read was still in flight once made rare 16-row blocks wrong on a
     loaded GPU: tests/test_asm_hazards.py checks the compiled code, this checks the device.)"""
-    monkeypatch.setenv("VK_CONV_DUO", "1" if kernel == "duo" else "0")
-    monkeypatch.setenv("VK_CONV3X3_PANEL", "1" if kernel == "panel" else "0")
+    _set_env(monkeypatch, scale_env(kernel))
     g = _rng(99)
-    k = 3 if kernel == "panel" else 1
-    pad = dil = 2 if k == 3 else 1
-    if k == 1:
-        pad = 0
-    N, H, W, cin, cout = (64, 14, 14, 256, 512) if kernel == "panel" else (300, 14, 14, 512, 2048)
+    N, H, W, cin, cout, k, pad, dil = scale_shape(kernel)
     M = N * H * W
     x = torch.randn((N, H, W, cin)).half().to(G.DEV)
     r = torch.randn((M, cout)).half().to(G.DEV)
@@ -311,8 +453,8 @@ def test_conv_reproducible_at_scale(kernel, monkeypatch):
     ys = []
     for _ in range(4):
         y = torch.empty((M, cout), dtype=torch.float16, device=G.DEV)
-        L.call("vk_conv2d", G.P(x), N, H, W, cin, G.P(wp), G.P(bp), G.P(r), G.P(y), cout, cout, k, k, 1, pad, dil, 1, 1,
-               L.VK_F16, L.VK_F16, G.stream())
+        G.launch("vk_conv2d", G.P(x), N, H, W, cin, G.P(wp), G.P(bp), G.P(r), G.P(y), cout, cout, k, k, 1, pad, dil, 1, 1,
+                 L.VK_F16, L.VK_F16, G.stream(), expect_route=kernel)
         torch.cuda.synchronize()
         ys.append(y)
     for y in ys[1:]:
@@ -323,24 +465,38 @@ def test_conv_reproducible_at_scale(kernel, monkeypatch):
     assert float((ys[0].float() - ref).abs().max()) <= 0.02 * float(ref.abs().max())
 
 
+ONE_BY_ONE_GEOM = dict(N=2, H=30, W=40, cin=256, cout=512, relu=1, res=True)
+ONE_BY_ONE_LEGS = (({"VK_CONV_WS": "0", "VK_CONV_DUO": "0"}, "ring"), ({"VK_CONV_WS": "0", "VK_CONV_DUO": "1"}, "duo"),
+                   ({"VK_CONV_WS": None, "VK_CONV_DUO": None}, "ws"))
+
+
 def test_conv_1x1_kernels_bit_identical(monkeypatch):
     """The two 1x1 kernels (256x256 ring, 128x256 two-per-CU) walk K in the same order with the same MFMA: a
-    layer's bits do not depend on which of them the dispatcher picks (it picks by problem size)."""
+    layer's bits do not depend on which of them the dispatcher picks (it picks by problem size) -- nor on the weight-stationary
+    kernel, which takes this layer when nothing is pinned."""
     g = _rng(11)
     x = torch.from_numpy(g.standard_normal((2, 256, 30, 40)).astype(np.float32))
     w = (g.standard_normal((512, 256, 1, 1)) * 0.08).astype(np.float32)
     b = g.standard_normal(512).astype(np.float32)
     res = torch.from_numpy(g.standard_normal((2, 512, 30, 40)).astype(np.float32))
     ys = []
-    for duo in ("0", "1"):
-        monkeypatch.setenv("VK_CONV_DUO", duo)
-        ys.append(G.conv2d(x, w, bias=b, residual_nchw=res, relu=True, dt=L.VK_F16))
-    assert torch.equal(ys[0], ys[1])
+    for env, route in ONE_BY_ONE_LEGS:
+        _set_env(monkeypatch, env)
+        ys.append(G.conv2d(x, w, bias=b, residual_nchw=res, relu=True, dt=L.VK_F16, expect_route=route))
+    assert torch.equal(ys[0], ys[1]) and torch.equal(ys[0], ys[2])
 
 
-@pytest.mark.parametrize("M_hw,cin,cout,res", [((7, 50, 84), 256, 1024, True), ((200, 14, 14), 512, 2048, True), ((3, 37, 41), 128, 512, True),
-                                               ((200, 14, 14), 512, 512, False), ((1, 32, 33), 512, 256, True),
-                                               ((2, 100, 167), 64, 256, True), ((1, 33, 35), 64, 512, False)])
+WS_CASES = [((7, 50, 84), 256, 1024, True), ((200, 14, 14), 512, 2048, True), ((3, 37, 41), 128, 512, True),
+            ((200, 14, 14), 512, 512, False), ((1, 32, 33), 512, 256, True),
+            ((2, 100, 167), 64, 256, True), ((1, 33, 35), 64, 512, False)]
+WS_LEGS = (("1", "8", "ws"), ("0", "8", "duo"), ("1", "4", "ws"), ("1", "8", "ws"))      # VK_CONV_WS, VK_WS_WAVES, kernel
+
+
+def ws_geom(M_hw, cin, cout, res):
+    return dict(N=M_hw[0], H=M_hw[1], W=M_hw[2], cin=cin, cout=cout, relu=1, res=res)
+
+
+@pytest.mark.parametrize("M_hw,cin,cout,res", WS_CASES)
 def test_conv_ws_kernel_bit_identical(M_hw, cin, cout, res, monkeypatch):
     """conv_ws.hip (weight-stationary 1x1, K <= 512: weights in registers, pixels through an LDS-DMA ring that runs across
     tile boundaries) against the two-per-CU kernel on the same layer: bit-identical (same K order, same epilogue
@@ -353,10 +509,10 @@ def test_conv_ws_kernel_bit_identical(M_hw, cin, cout, res, monkeypatch):
     bn = (g.uniform(0.5, 1.5, cout), g.standard_normal(cout) * 0.1, g.standard_normal(cout) * 0.1, g.uniform(0.5, 1.5, cout))
     r = torch.from_numpy(g.standard_normal((N, cout, H, W)).astype(np.float32)) if res else None
     ys = []
-    for ws, waves in (("1", "8"), ("0", "8"), ("1", "4"), ("1", "8")):
+    for ws, waves, route in WS_LEGS:
         monkeypatch.setenv("VK_CONV_WS", ws)
         monkeypatch.setenv("VK_WS_WAVES", waves)            # two waves per SIMD (the default) / one
-        ys.append(G.conv2d(x, w, bn=bn, residual_nchw=r, relu=True, dt=L.VK_F16))
+        ys.append(G.conv2d(x, w, bn=bn, residual_nchw=r, relu=True, dt=L.VK_F16, expect_route=route))
     assert all(torch.equal(ys[0], y) for y in ys[1:])
     wf, bf = G.fold_ref(w, bn, L.VK_F16)
     ref = F.conv2d(x.half().float(), wf) + bf.view(1, -1, 1, 1)
@@ -365,8 +521,23 @@ def test_conv_ws_kernel_bit_identical(M_hw, cin, cout, res, monkeypatch):
     assert G.rel_err(ys[0], F.relu(ref).half().float()) <= 1e-3
 
 
-@pytest.mark.parametrize("M_hw,cin,cout,stride,relu", [((3, 100, 167), 256, 512, 2, False), ((5, 50, 84), 512, 1024, 2, False),
-                                                       ((2, 51, 85), 512, 256, 2, True), ((1, 67, 40), 256, 256, 3, True)])
+# the one-image stride-3 case has 322 output rows, below both kernels' floor of 1024: the generic kernel runs it (twice); the
+# four-image one is the stride-3 layer on the two kernels the test is about
+WS_STRIDED_CASES = [((3, 100, 167), 256, 512, 2, False), ((5, 50, 84), 512, 1024, 2, False),
+                    ((2, 51, 85), 512, 256, 2, True), ((1, 67, 40), 256, 256, 3, True), ((4, 67, 40), 256, 256, 3, True)]
+
+
+def ws_strided_geom(M_hw, cin, cout, stride, relu):
+    return dict(N=M_hw[0], H=M_hw[1], W=M_hw[2], cin=cin, cout=cout, stride=stride, relu=int(relu))
+
+
+def ws_strided_legs(M_hw, cin, cout, stride, relu):
+    """(VK_WS_STRIDED, kernel) of the three runs."""
+    small = M_hw[0] * ((M_hw[1] - 1) // stride + 1) * ((M_hw[2] - 1) // stride + 1) < 1024
+    return [(sw, "generic" if small else r) for sw, r in (("1", "ws"), ("0", "duo"), ("1", "ws"))]
+
+
+@pytest.mark.parametrize("M_hw,cin,cout,stride,relu", WS_STRIDED_CASES)
 def test_conv_ws_strided_bit_identical(M_hw, cin, cout, stride, relu, monkeypatch):
     """conv_ws.hip on strided 1x1 convs (the stride-2 projection shortcuts and first conv1s of res3 / res4, frcnn.py:934-941: the DMA
     lane maps its output row to an input pixel) against the two-per-CU kernel: bit-identical, odd sizes, ragged tiles."""
@@ -376,18 +547,26 @@ def test_conv_ws_strided_bit_identical(M_hw, cin, cout, stride, relu, monkeypatc
     w = (g.standard_normal((cout, cin, 1, 1)) * (2.0 / cin) ** 0.5).astype(np.float32)
     bn = (g.uniform(0.5, 1.5, cout), g.standard_normal(cout) * 0.1, g.standard_normal(cout) * 0.1, g.uniform(0.5, 1.5, cout))
     ys = []
-    for sw in ("1", "0", "1"):
+    for sw, route in ws_strided_legs(M_hw, cin, cout, stride, relu):
         monkeypatch.setenv("VK_WS_STRIDED", sw)
-        ys.append(G.conv2d(x, w, bn=bn, stride=stride, relu=relu, dt=L.VK_F16))
+        ys.append(G.conv2d(x, w, bn=bn, stride=stride, relu=relu, dt=L.VK_F16, expect_route=route))
     assert torch.equal(ys[0], ys[1]) and torch.equal(ys[0], ys[2])
     wf, bf = G.fold_ref(w, bn, L.VK_F16)
     ref = F.conv2d(x.half().float(), wf, None, stride) + bf.view(1, -1, 1, 1)
     assert G.rel_err(ys[0], (F.relu(ref) if relu else ref).half().float()) <= 1e-3
 
 
-@pytest.mark.parametrize("M_hw,cin,cout,res,relu", [((13, 14, 14), 2048, 512, False, True), ((11, 14, 14), 1024, 512, False, True),
-                                                    ((17, 14, 14), 1024, 256, True, True), ((2, 50, 84), 1024, 256, False, False),
-                                                    ((1, 45, 47), 1152, 512, True, False)])
+GEMM4_CASES = [((13, 14, 14), 2048, 512, False, True), ((11, 14, 14), 1024, 512, False, True),
+               ((17, 14, 14), 1024, 256, True, True), ((2, 50, 84), 1024, 256, False, False),
+               ((1, 45, 47), 1152, 512, True, False)]
+GEMM4_LEGS = (("2", "1", "gemm4"), ("0", "1", "duo"), ("0", "0", "ring"), ("2", "1", "gemm4"))   # VK_CONV_GEMM4, VK_CONV_DUO, kernel
+
+
+def gemm4_geom(M_hw, cin, cout, res, relu):
+    return dict(N=M_hw[0], H=M_hw[1], W=M_hw[2], cin=cin, cout=cout, relu=int(relu), res=res)
+
+
+@pytest.mark.parametrize("M_hw,cin,cout,res,relu", GEMM4_CASES)
 def test_conv_gemm4_kernel_bit_identical(M_hw, cin, cout, res, relu, monkeypatch):
     """conv_gemm4.hip (1x1, K >= 1024: 256 x 256 tile, four waves of 128 x 128, accumulators in AGPRs) against the kernels that
     take the layer without it (two-per-CU / ring): bit-identical, with full and ragged tiles, with and without residual / ReLU,
@@ -399,10 +578,10 @@ def test_conv_gemm4_kernel_bit_identical(M_hw, cin, cout, res, relu, monkeypatch
     bn = (g.uniform(0.5, 1.5, cout), g.standard_normal(cout) * 0.1, g.standard_normal(cout) * 0.1, g.uniform(0.5, 1.5, cout))
     r = torch.from_numpy(g.standard_normal((N, cout, H, W)).astype(np.float32)) if res else None
     ys = []
-    for g4, duo in (("2", "1"), ("0", "1"), ("0", "0"), ("2", "1")):      # "2": also on grids this small
+    for g4, duo, route in GEMM4_LEGS:                       # "2": also on grids this small
         monkeypatch.setenv("VK_CONV_GEMM4", g4)
         monkeypatch.setenv("VK_CONV_DUO", duo)
-        ys.append(G.conv2d(x, w, bn=bn, residual_nchw=r, relu=relu, dt=L.VK_F16))
+        ys.append(G.conv2d(x, w, bn=bn, residual_nchw=r, relu=relu, dt=L.VK_F16, expect_route=route))
     assert all(torch.equal(ys[0], y) for y in ys[1:])
     wf, bf = G.fold_ref(w, bn, L.VK_F16)
     ref = F.conv2d(x.half().float(), wf) + bf.view(1, -1, 1, 1)
@@ -413,17 +592,31 @@ def test_conv_gemm4_kernel_bit_identical(M_hw, cin, cout, res, relu, monkeypatch
     assert G.rel_err(ys[0], ref.half().float()) <= 1e-3
 
 
-@pytest.mark.parametrize("M,c1,c2,cout,relu,use_res", [(40000, 2048, 0, 512, True, False), (39917, 512, 1024, 2048, True, False),
-                                                        (70001, 1024, 0, 512, False, False), (33000, 2048, 0, 2048, True, True),
-                                                        # res4's conv1 (full and half batch: 525 / 263 tiles), other grids of full rounds + a few tiles
-                                                        (67200, 1024, 0, 256, True, False), (134400, 1024, 0, 256, True, False),
-                                                        (66000, 512, 1024, 512, True, False), (66500, 2048, 0, 256, True, True),
-                                                        # rows beyond the descriptor's 14-bit stride (stride = pitch / 2 or / 4, index = row * 2 or * 4):
-                                                        # the FPN box head's fc1 (12544 -> 1024 at 32 x 1000 RoIs) and a 33 KB row
-                                                        (32000, 12544, 0, 1024, True, False), (2100, 16512, 0, 256, False, False)])
+GEMM4_MANY_CASES = [(40000, 2048, 0, 512, True, False), (39917, 512, 1024, 2048, True, False),
+                    (70001, 1024, 0, 512, False, False), (33000, 2048, 0, 2048, True, True),
+                    # res4's conv1 (full and half batch: 525 / 263 tiles), other grids of full rounds + a few tiles
+                    (67200, 1024, 0, 256, True, False), (134400, 1024, 0, 256, True, False),
+                    (66000, 512, 1024, 512, True, False), (66500, 2048, 0, 256, True, True),
+                    # rows beyond the descriptor's 14-bit stride (stride = pitch / 2 or / 4, index = row * 2 or * 4):
+                    # the FPN box head's fc1 (12544 -> 1024 at 32 x 1000 RoIs) and a 33 KB row
+                    (32000, 12544, 0, 1024, True, False), (2100, 16512, 0, 256, False, False)]
+
+
+def gemm4_many_geom(M, c1, c2, cout, relu, use_res):
+    return dict(N=1, H=1, W=M, cin=c1, cin2=c2, cout=cout, relu=int(relu), res=use_res)
+
+
+def gemm4_many_legs(M, c1, c2, cout, relu, use_res):
+    """(VK_CONV_GEMM4, kernel): without the four-wave GEMM the two-input layers run on the ring kernel, the others on the
+    two-per-CU kernel (M < 400 000)."""
+    return [("2", "gemm4"), ("0", "ring" if c2 else "duo")]
+
+
+@pytest.mark.parametrize("M,c1,c2,cout,relu,use_res", GEMM4_MANY_CASES)
 def test_conv_gemm4_many_tiles_per_workgroup(M, c1, c2, cout, relu, use_res, monkeypatch):
     """conv_gemm4's persistent workgroups at sizes where each walks several tiles (one LDS ring across tile boundaries, the
-    next tile's first stages requested by the previous tile's last ones, a ragged last tile): bit-identical to the ring kernel."""
+    next tile's first stages requested by the previous tile's last ones, a ragged last tile): bit-identical to the kernel that
+    takes the layer without it (two inputs: the ring kernel; one: the two-per-CU kernel)."""
     g = torch.Generator(device="cpu").manual_seed(M + c1)
     x1 = (torch.randn((M, c1), generator=g) * 0.7).half().to(G.DEV)
     x2 = (torch.randn((M, c2), generator=g) * 0.7).half().to(G.DEV) if c2 else None
@@ -433,14 +626,15 @@ def test_conv_gemm4_many_tiles_per_workgroup(M, c1, c2, cout, relu, use_res, mon
     wd, bd = G.pack_conv(w, None, b, L.VK_F16)
     res = (torch.randn((M, cout), generator=g) * 0.5).half().to(G.DEV) if use_res else None     # (ResNeXt's conv3: K = 2048 with the identity shortcut)
     ys = []
-    for g4 in ("2", "0"):                                   # "2": also on grids below its usual floor (here 2 - 5 tiles per workgroup)
+    for g4, route in gemm4_many_legs(M, c1, c2, cout, relu, use_res):   # "2": also on grids below its usual floor (here 2 - 5 tiles per workgroup)
         monkeypatch.setenv("VK_CONV_GEMM4", g4)
         y = torch.full((M, cout), float("nan"), dtype=torch.float16, device=G.DEV)
         if c2:
-            L.call("vk_conv1x1_dual", G.P(x1), c1, G.P(x2), c2, M, G.P(wd), G.P(bd), None, G.P(y), cout, int(relu), G.stream())
+            G.launch("vk_conv1x1_dual", G.P(x1), c1, G.P(x2), c2, M, G.P(wd), G.P(bd), None, G.P(y), cout, int(relu), G.stream(),
+                     expect_route=route)
         else:
-            L.call("vk_conv2d", G.P(x1), 1, 1, M, c1, G.P(wd), G.P(bd), G.P(res), G.P(y), cout, cout, 1, 1, 1, 0, 1, 1, int(relu), L.VK_F16,
-                   L.VK_F16, G.stream())
+            G.launch("vk_conv2d", G.P(x1), 1, 1, M, c1, G.P(wd), G.P(bd), G.P(res), G.P(y), cout, cout, 1, 1, 1, 0, 1, 1, int(relu), L.VK_F16,
+                     L.VK_F16, G.stream(), expect_route=route)
         torch.cuda.synchronize()
         ys.append(y)
     assert torch.equal(ys[0], ys[1])
@@ -454,13 +648,19 @@ def test_conv_gemm4_many_tiles_per_workgroup(M, c1, c2, cout, relu, use_res, mon
     assert G.rel_err(ys[0][rows].float().cpu(), ref.cpu()) <= 1e-3
 
 
+F32OUT_SHAPE = (2, 128, 9, 13, 75)                          # N, cin, H, W, cout
+F32OUT_GEOM = dict(N=2, H=9, W=13, cin=128, cout=75, out_dt=L.VK_F32)
+
+
 def test_conv_bias_f32_out():
     """fp16 operands, fp32 output with bias and a channel count that is not a multiple of 8 (RPN heads: 75)."""
     g = _rng(7)
-    x = torch.from_numpy(g.standard_normal((2, 128, 9, 13)).astype(np.float32))
-    w = (g.standard_normal((75, 128, 1, 1)) * 0.1).astype(np.float32)
-    b = g.standard_normal(75).astype(np.float32)
-    y = G.conv2d(x, w, bias=b, dt=L.VK_F16, out_dt=L.VK_F32)
+    N, cin, H, W, cout = F32OUT_SHAPE
+    assert (N, H, W, cin, cout) == tuple(F32OUT_GEOM[k] for k in ("N", "H", "W", "cin", "cout"))
+    x = torch.from_numpy(g.standard_normal((N, cin, H, W)).astype(np.float32))
+    w = (g.standard_normal((cout, cin, 1, 1)) * 0.1).astype(np.float32)
+    b = g.standard_normal(cout).astype(np.float32)
+    y = G.conv2d(x, w, bias=b, dt=L.VK_F16, out_dt=L.VK_F32, expect_route="generic")
     ref = F.conv2d(x.half().float(), torch.from_numpy(w).half().float(), torch.from_numpy(b))
     assert y.shape == ref.shape
     assert G.rel_err(y, ref) <= 1e-5
@@ -831,10 +1031,18 @@ def test_roi_outputs_golden(kat, tag):
         assert (bufs["roi_features"][i, n:] == 0).all() and (bufs["boxes"][i, n:] == 0).all()
 
 
-@pytest.mark.parametrize("name,switch,shape", [
+DYNAMIC_TAIL_CASES = [
     ("panel 3x3", "VK_PANEL_DYNAMIC", (5400, 14, 14, 512, 512, 3, 2, 2)),        # 7350 tiles of 288 pixels x 2 column tiles
     ("gemm4 1x1", "VK_GEMM4_DYNAMIC", (5400, 14, 14, 1024, 512, 1, 0, 1)),       # 8270 tiles on 256 persistent workgroups
-])
+]
+
+
+def dynamic_tail_geom(shape):
+    N, H, W, cin, cout, k, pad, dil = shape
+    return dict(N=N, H=H, W=W, cin=cin, cout=cout, k=k, pad=pad, dil=dil, relu=1)
+
+
+@pytest.mark.parametrize("name,switch,shape", DYNAMIC_TAIL_CASES)
 def test_dynamic_tile_tail_is_bit_identical(monkeypatch, name, switch, shape):
     """Long launches hand their last tiles out through an atomic counter (the XCDs of a chip differ in speed).  Which workgroup
     computes a tile must not change a bit: the same launch with every tile static, twice with the tail (the hand-out order differs
@@ -848,7 +1056,8 @@ def test_dynamic_tile_tail_is_bit_identical(monkeypatch, name, switch, shape):
 
     def run():
         y = torch.full((N, H, W, cout), float("nan"), dtype=torch.float16, device=G.DEV)
-        L.call("vk_conv2d", G.P(x), N, H, W, cin, G.P(wd), G.P(bd), None, G.P(y), cout, cout, k, k, 1, pad, dil, 1, 1, L.VK_F16, L.VK_F16, G.stream())
+        G.launch("vk_conv2d", G.P(x), N, H, W, cin, G.P(wd), G.P(bd), None, G.P(y), cout, cout, k, k, 1, pad, dil, 1, 1, L.VK_F16, L.VK_F16,
+                 G.stream(), expect_route=name.split()[0])
         torch.cuda.synchronize()
         return y
     monkeypatch.setenv(switch, "0")
@@ -857,3 +1066,51 @@ def test_dynamic_tile_tail_is_bit_identical(monkeypatch, name, switch, shape):
     monkeypatch.delenv(switch)
     for _ in range(2):
         assert torch.equal(run(), ref), name
+
+
+def route_plan():
+    """(label, environment, gpu_util.conv_route arguments, kernel) of every run above that names its kernel: what the GPU
+    tests assert launch by launch, as a table the CPU suite checks against the dispatcher (tests/test_abi.py)."""
+    f16, f32 = L.VK_F16, L.VK_F32
+    for dt in (f32, f16):
+        for c in CONV_CASES:
+            for env, r in conv_legs(c, dt):
+                yield f"test_conv[{c[0]}-{dt}]", env, conv_geom(c, dt), r
+            if c[0].startswith("panel_") and dt == f16:
+                assert panel_mi9_legal(c[3], c[9]), c[0]
+                for e, r in PANEL_FORM_LEGS:
+                    yield f"test_conv[{c[0]}-form]", dict(conv_legs(c, dt)[0][0], **e), conv_geom(c, dt), r
+        for c in GROUPED_CASES:
+            for env, r in grouped_legs(c, dt):
+                yield f"test_grouped_conv[{c[0]}-{dt}]", env, grouped_geom(c, dt), r
+    for c in BLK_CASES:
+        for on, r in BLK_LEGS:
+            yield f"test_conv3x3_blk_kernel[{c[0]}]", {"VK_CONV3X3_BLK": on}, blk_geom(c), r
+    for c in DUAL_CASES:
+        for env, r in dual_legs(*c):
+            yield f"test_conv1x1_dual[{c}]", env, dual_geom(*c), r
+    for c in MEANPOOL_CASES:
+        for env, n, r in meanpool_legs(*c):
+            yield f"test_conv1x1_meanpool[{c}]", env, meanpool_geom(n, *c[1:]), r
+    for ws, r in NONFINITE_LEGS.items():
+        yield f"test_conv1x1_meanpool_nonfinite[{ws}]", {"VK_CONV_WS": ws}, meanpool_geom(*NONFINITE_SHAPE), r
+    for kernel in SCALE_KERNELS:
+        yield f"test_conv_reproducible_at_scale[{kernel}]", scale_env(kernel), scale_geom(kernel), kernel
+    for env, r in ONE_BY_ONE_LEGS:
+        yield "test_conv_1x1_kernels_bit_identical", env, ONE_BY_ONE_GEOM, r
+    for c in WS_CASES:
+        for ws, waves, r in WS_LEGS:
+            yield f"test_conv_ws_kernel_bit_identical[{c}]", {"VK_CONV_WS": ws, "VK_WS_WAVES": waves}, ws_geom(*c), r
+    for c in WS_STRIDED_CASES:
+        for sw, r in ws_strided_legs(*c):
+            yield f"test_conv_ws_strided_bit_identical[{c}]", {"VK_WS_STRIDED": sw}, ws_strided_geom(*c), r
+    for c in GEMM4_CASES:
+        for g4, duo, r in GEMM4_LEGS:
+            yield f"test_conv_gemm4_kernel_bit_identical[{c}]", {"VK_CONV_GEMM4": g4, "VK_CONV_DUO": duo}, gemm4_geom(*c), r
+    for c in GEMM4_MANY_CASES:
+        for g4, r in gemm4_many_legs(*c):
+            yield f"test_conv_gemm4_many_tiles_per_workgroup[{c}]", {"VK_CONV_GEMM4": g4}, gemm4_many_geom(*c), r
+    yield "test_conv_bias_f32_out", {}, F32OUT_GEOM, "generic"
+    for name, switch, shape in DYNAMIC_TAIL_CASES:
+        for env in ({switch: "0"}, {}):
+            yield f"test_dynamic_tile_tail_is_bit_identical[{name}]", env, dynamic_tail_geom(shape), name.split()[0]

@@ -19,6 +19,7 @@ elif os.environ.get("VLTK_AMD_ABLATION_LIB") == "1":
 VK_OK, VK_EINVAL, VK_ENOTIMPL, VK_ENONFINITE, VK_EWEIGHTS, VK_EHIP, VK_ENOMEM = range(7)
 VK_F32, VK_F16, VK_I64, VK_I32, VK_BF16 = 0, 1, 2, 3, 4
 VK_ACT_NONE, VK_ACT_RELU, VK_ACT_GELU, VK_ACT_TANH = 0, 1, 2, 3
+VK_ROUTE_GENERIC, VK_ROUTE_RING, VK_ROUTE_DUO, VK_ROUTE_WS, VK_ROUTE_GEMM4, VK_ROUTE_PANEL, VK_ROUTE_BLK = range(7)
 VK_MAX_ANCHOR_DIM = 8
 VK_MAX_NMS_THRESH = 8
 VK_MAX_IGNOREY = 64
@@ -104,6 +105,7 @@ SIGNATURES = {
     "vk_conv_slice_channels": (_I, [_I, _I]),
     "vk_packed_cout": (_I, [_I]),
     "vk_pack_conv_weight": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "vk_conv_route": (_I, [_I] * 18),
     "vk_conv1x1_dual": (_I, [_P, _I, _P, _I, C.c_long, _P, _P, _P, _P, _I, _I, _P]),
     "vk_bottleneck64": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vk_fuse_shortcut": (_I, [_I, _I, _I, _I, _I]),

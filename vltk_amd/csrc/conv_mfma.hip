@@ -353,35 +353,46 @@ static int launch_t(const ConvK &k, hipStream_t stream) {
     return t.end(stream, bucket, k.alg_flops, k.M, k.cout8, k.cin_bytes / (int)sizeof(T), k.ktiles / k.kt_per_tap, k.stride, k.alg_bytes);
 }
 
-int launch_conv(const ConvArgs &a, hipStream_t stream) {
-    const bool grouped = a.groups > 1;
+// Which kernel takes the layer: the dispatcher's one decision (host only: eligibility rules and their A/B switches, re-read per
+// call).  launch_conv switches on it and vk_conv_route (model.hip) returns it, so the query cannot drift from the launch.
+// Order: fused-mean and dual-source forms first; then block -> panel -> weight-stationary -> four-wave GEMM -> two-per-CU -> ring ->
+// generic.  A form no kernel takes is -VK_EINVAL with the error text set.
+int conv_route(const ConvArgs &a) {
     if (a.pool_part) {
-        VK_REQUIRE(conv_duo_pool_ok(a) && (!a.x2 || conv_duo_dual_ok(a)) && a.relu <= 1 && a.ldy == a.Cout, VK_EINVAL,
-                   "conv: the fused-mean form is 1x1, stride 1, f16, Cout %% 256 == 0, Ho*Wo >= 128");
+        if (!(conv_duo_pool_ok(a) && (!a.x2 || conv_duo_dual_ok(a)) && a.relu <= 1 && a.ldy == a.Cout)) {
+            set_error("conv: the fused-mean form is 1x1, stride 1, f16, Cout %% 256 == 0, Ho*Wo >= 128");
+            return -VK_EINVAL;
+        }
         // per-image fp64 sums (conv_ws) or per-tile integer partials (two-per-CU kernel): launch_pool_finish asks the same function
-        if (conv_ws_pool_ok(a)) return launch_conv_ws(a, stream);
-        return launch_conv_duo(a, stream);
+        return conv_ws_pool_ok(a) ? VK_ROUTE_WS : VK_ROUTE_DUO;
     }
     if (a.x2) {
-        if (conv_ws_eligible(a)) return launch_conv_ws(a, stream);           // 64 + 64 channels (res2's first conv3 + shortcut)
-        if (conv_gemm4_eligible(a)) return launch_conv_gemm4(a, stream);
-        if (conv256_dual_ok(a)) return launch_conv256(a, stream);
-        VK_REQUIRE(conv_duo_dual_ok(a), VK_EINVAL,
-                   "conv: the dual-source form is 1x1, stride 1, f16, Cout %% 256 == 0, Cin and Cin2 multiples of 32");
-        return launch_conv_duo(a, stream);
+        if (conv_ws_eligible(a)) return VK_ROUTE_WS;           // 64 + 64 channels (res2's first conv3 + shortcut)
+        if (conv_gemm4_eligible(a)) return VK_ROUTE_GEMM4;
+        if (conv256_dual_ok(a)) return VK_ROUTE_RING;
+        if (!conv_duo_dual_ok(a)) {
+            set_error("conv: the dual-source form is 1x1, stride 1, f16, Cout %% 256 == 0, Cin and Cin2 multiples of 32");
+            return -VK_EINVAL;
+        }
+        return VK_ROUTE_DUO;
     }
-    if (conv3x3_blk_eligible(a)) return launch_conv3x3_blk(a, stream);
-    if (!grouped) {
-        if (conv3x3_panel_eligible(a)) return launch_conv3x3_panel(a, stream);
-        if (conv_ws_eligible(a)) return launch_conv_ws(a, stream);
-        if (conv_gemm4_eligible(a)) return launch_conv_gemm4(a, stream);
-        if (conv_duo_eligible(a)) return launch_conv_duo(a, stream);
-        if (conv256_eligible(a)) return launch_conv256(a, stream);
+    if (conv3x3_blk_eligible(a)) return VK_ROUTE_BLK;
+    if (a.groups <= 1) {
+        if (conv3x3_panel_eligible(a)) return VK_ROUTE_PANEL;
+        if (conv_ws_eligible(a)) return VK_ROUTE_WS;
+        if (conv_gemm4_eligible(a)) return VK_ROUTE_GEMM4;
+        if (conv_duo_eligible(a)) return VK_ROUTE_DUO;
+        if (conv256_eligible(a)) return VK_ROUTE_RING;
     }
+    return VK_ROUTE_GENERIC;
+}
+
+// The generic kernel's launch record from the layer (and what it refuses).
+static int generic_plan(const ConvArgs &a, ConvK &k) {
+    const bool grouped = a.groups > 1;
     const int es = (int)dtype_size(a.dt);
     VK_REQUIRE(a.dt == VK_F16 || a.dt == VK_F32 || a.dt == VK_BF16, VK_EINVAL, "conv: dtype must be f16, bf16 or f32");
     VK_REQUIRE(a.out_dt == a.dt || a.out_dt == VK_F32, VK_EINVAL, "conv: out dtype must equal dtype or be f32");
-    ConvK k;
     k.x = (const char *)a.x;
     k.w = (const char *)a.w;
     k.bias = a.bias;
@@ -434,9 +445,35 @@ int launch_conv(const ConvArgs &a, hipStream_t stream) {
     k.m_tiles = ceil_div(k.M, CONV_BM);
     const bool narrow = a.Cout <= 64 || a.stem || grouped;
     k.n_tiles = ceil_div(a.Cout, narrow ? 64 : 128);
+    if (a.dt == VK_BF16) VK_REQUIRE(!a.stem, VK_EINVAL, "conv: no bf16 stem");
+    return VK_OK;
+}
+
+// vk_conv_route's answer: the route, or -VK_E* where launch_conv refuses the layer
+int conv_route_checked(const ConvArgs &a) {
+    const int r = conv_route(a);
+    if (r != VK_ROUTE_GENERIC) return r;
+    ConvK k;
+    const int s = generic_plan(a, k);
+    return s == VK_OK ? r : -s;
+}
+
+int launch_conv(const ConvArgs &a, hipStream_t stream) {
+    switch (conv_route(a)) {
+        case VK_ROUTE_GENERIC: break;
+        case VK_ROUTE_RING: return launch_conv256(a, stream);
+        case VK_ROUTE_DUO: return launch_conv_duo(a, stream);
+        case VK_ROUTE_WS: return launch_conv_ws(a, stream);
+        case VK_ROUTE_GEMM4: return launch_conv_gemm4(a, stream);
+        case VK_ROUTE_PANEL: return launch_conv3x3_panel(a, stream);
+        case VK_ROUTE_BLK: return launch_conv3x3_blk(a, stream);
+        default: return VK_EINVAL;                        // refused: conv_route set the error text
+    }
+    ConvK k;
+    VK_TRY(generic_plan(a, k));
+    const bool narrow = a.Cout <= 64 || a.stem || a.groups > 1;
     const bool f32out = (a.out_dt == VK_F32);
     if (a.dt == VK_BF16) {      // LXMERT-style encoder GEMMs (N3): same tiling, v_mfma_f32_16x16x32_bf16
-        VK_REQUIRE(!a.stem, VK_EINVAL, "conv: no bf16 stem");
         if (f32out) return narrow ? launch_t<__bf16, float, 64, false>(k, stream) : launch_t<__bf16, float, 128, false>(k, stream);
         return narrow ? launch_t<__bf16, __bf16, 64, false>(k, stream) : launch_t<__bf16, __bf16, 128, false>(k, stream);
     }

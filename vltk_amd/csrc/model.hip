@@ -689,27 +689,20 @@ int vk_pack_stem_weight(const float *w, const float *bn, int cout, vk_dtype dt, 
     return VK_OK;
 }
 
-int vk_conv2d(const void *x, int N, int H, int W, int cin, const void *w_packed, const float *bias_packed,
-              const void *residual, void *y, int cout, int ldy, int kh, int kw, int stride, int pad, int dil, int groups,
-              int relu, vk_dtype dt, vk_dtype out_dt, void *stream) {
-    VK_REQUIRE(kh == kw && kh >= 1 && stride >= 1 && dil >= 1 && pad >= 0 && groups >= 1, VK_EINVAL, "conv2d: bad geometry");
-    ConvArgs a;
+// The layer of a stage-level launch as the dispatcher sees it: the one place vk_conv2d, vk_conv1x1_dual, vk_linear,
+// vk_conv1x1_meanpool and vk_conv_route build their ConvArgs, so what the query describes is what the launch passes.  The
+// pointers (and Cin2 with x2) are the caller's to set.
+static void fill_conv_args(ConvArgs &a, int N, int H, int W, int cin, int cout, int ldy, int k, int stride, int pad, int dil, int groups,
+                           int relu, vk_dtype dt, vk_dtype out_dt) {
     memset(&a, 0, sizeof(a));
-    a.x = x;
-    a.w = w_packed;
-    a.bias = bias_packed;
-    a.res = residual;
-    a.y = y;
     a.N = N;
     a.H = H;
     a.W = W;
     a.Cin = cin;
-    conv_out_hw(H, W, kh, stride, pad, dil, &a.Ho, &a.Wo);
-    VK_REQUIRE(a.Ho > 0 && a.Wo > 0 && N > 0, VK_EINVAL, "conv2d: empty output");
+    conv_out_hw(H, W, k, stride, pad, dil, &a.Ho, &a.Wo);
     a.Cout = cout;
     a.ldy = ldy;
-    a.kh = kh;
-    a.kw = kw;
+    a.kh = a.kw = k;
     a.stride = stride;
     a.pad = pad;
     a.dil = dil;
@@ -717,33 +710,56 @@ int vk_conv2d(const void *x, int N, int H, int W, int cin, const void *w_packed,
     a.relu = relu;
     a.dt = dt;
     a.out_dt = out_dt;
+}
+
+int vk_conv2d(const void *x, int N, int H, int W, int cin, const void *w_packed, const float *bias_packed,
+              const void *residual, void *y, int cout, int ldy, int kh, int kw, int stride, int pad, int dil, int groups,
+              int relu, vk_dtype dt, vk_dtype out_dt, void *stream) {
+    VK_REQUIRE(kh == kw && kh >= 1 && stride >= 1 && dil >= 1 && pad >= 0 && groups >= 1, VK_EINVAL, "conv2d: bad geometry");
+    ConvArgs a;
+    fill_conv_args(a, N, H, W, cin, cout, ldy, kh, stride, pad, dil, groups, relu, dt, out_dt);
+    VK_REQUIRE(a.Ho > 0 && a.Wo > 0 && N > 0, VK_EINVAL, "conv2d: empty output");
+    a.x = x;
+    a.w = w_packed;
+    a.bias = bias_packed;
+    a.res = residual;
+    a.y = y;
     return launch_conv(a, (hipStream_t)stream);
+}
+
+int vk_conv_route(int N, int H, int W, int cin, int cin2, int has_residual, int fused_mean, int cout, int ldy, int kh, int kw,
+                  int stride, int pad, int dil, int groups, int relu, vk_dtype dt, vk_dtype out_dt) {
+    if (!(kh == kw && kh >= 1 && stride >= 1 && dil >= 1 && pad >= 0 && groups >= 1 && cin2 >= 0)) {
+        set_error("conv_route: bad geometry");
+        return -VK_EINVAL;
+    }
+    static const char here = 0;              // the rules only ask whether a pointer is set
+    ConvArgs a;
+    fill_conv_args(a, N, H, W, cin, cout, ldy, kh, stride, pad, dil, groups, relu, dt, out_dt);
+    if (!(a.Ho > 0 && a.Wo > 0 && N > 0)) {
+        set_error("conv_route: empty output");
+        return -VK_EINVAL;
+    }
+    a.x = a.w = &here;
+    a.res = has_residual ? &here : nullptr;
+    a.x2 = cin2 > 0 ? &here : nullptr;
+    a.Cin2 = cin2;
+    a.pool_part = fused_mean ? (float *)&here : nullptr;
+    return conv_route_checked(a);
 }
 
 int vk_conv1x1_dual(const void *x1, int cin1, const void *x2, int cin2, long M, const void *w_packed, const float *bias_packed,
                     const void *residual, void *y, int cout, int relu, void *stream) {
     VK_REQUIRE(x1 && x2 && M > 0 && M < (1L << 31), VK_EINVAL, "conv1x1_dual: bad arguments");
     ConvArgs a;
-    memset(&a, 0, sizeof(a));
+    fill_conv_args(a, 1, 1, (int)M, cin1, cout, cout, 1, 1, 0, 1, 1, relu, VK_F16, VK_F16);
     a.x = x1;
     a.x2 = x2;
-    a.Cin = cin1;
     a.Cin2 = cin2;
     a.w = w_packed;
     a.bias = bias_packed;
     a.res = residual;
     a.y = y;
-    a.N = 1;
-    a.H = a.Ho = 1;
-    a.W = a.Wo = (int)M;
-    a.Cout = cout;
-    a.ldy = cout;
-    a.kh = a.kw = 1;
-    a.stride = 1;
-    a.dil = 1;
-    a.groups = 1;
-    a.relu = relu;
-    a.dt = a.out_dt = VK_F16;
     return launch_conv(a, (hipStream_t)stream);
 }
 
@@ -751,25 +767,12 @@ int vk_linear(const void *x, long M, int K, const void *w_packed, const float *b
               int act, vk_dtype dt, vk_dtype out_dt, void *stream) {
     VK_REQUIRE(x && w_packed && bias_packed && y && M > 0 && M < (1L << 31), VK_EINVAL, "linear: bad arguments");
     ConvArgs a;
-    memset(&a, 0, sizeof(a));
+    fill_conv_args(a, 1, 1, (int)M, K, N, ldy, 1, 1, 0, 1, 1, act, dt, out_dt);
     a.x = x;
-    a.Cin = K;
     a.w = w_packed;
     a.bias = bias_packed;
     a.res = residual;
     a.y = y;
-    a.N = 1;
-    a.H = a.Ho = 1;
-    a.W = a.Wo = (int)M;
-    a.Cout = N;
-    a.ldy = ldy;
-    a.kh = a.kw = 1;
-    a.stride = 1;
-    a.dil = 1;
-    a.groups = 1;
-    a.relu = act;
-    a.dt = dt;
-    a.out_dt = out_dt;
     return launch_conv(a, (hipStream_t)stream);
 }
 
@@ -803,24 +806,12 @@ int vk_conv1x1_meanpool(const void *x, int N, int HW, int cin, const void *w_pac
     VK_REQUIRE(x && out_mean && workspace && N > 0 && HW > 0, VK_EINVAL, "conv1x1_meanpool: bad arguments");
     VK_REQUIRE(workspace_bytes >= vk_conv1x1_meanpool_workspace_bytes(N, HW, cout), VK_EINVAL, "conv1x1_meanpool: workspace too small");
     ConvArgs a;
-    memset(&a, 0, sizeof(a));
+    fill_conv_args(a, N, 1, HW, cin, cout, cout, 1, 1, 0, 1, 1, relu, VK_F16, VK_F16);
     a.x = x;
-    a.Cin = cin;
     a.w = w_packed;
     a.bias = bias_packed;
     a.res = residual;
     a.pool_part = (float *)workspace;
-    a.N = N;
-    a.H = a.Ho = 1;
-    a.W = a.Wo = HW;
-    a.Cout = cout;
-    a.ldy = cout;
-    a.kh = a.kw = 1;
-    a.stride = 1;
-    a.dil = 1;
-    a.groups = 1;
-    a.relu = relu;
-    a.dt = a.out_dt = VK_F16;
     VK_TRY(launch_conv(a, (hipStream_t)stream));
     return launch_pool_finish((const float *)workspace, N, HW, cin, cout, false, out_mean, (hipStream_t)stream);
 }

@@ -78,6 +78,8 @@ struct ConvArgs {
     vk_dtype dt, out_dt;
 };
 int launch_conv(const ConvArgs &a, hipStream_t stream);
+int conv_route(const ConvArgs &a);            // the VK_ROUTE_* launch_conv switches on (host only); -VK_EINVAL: no kernel takes the form
+int conv_route_checked(const ConvArgs &a);    // the same, and -VK_E* where the generic kernel refuses the layer (vk_conv_route)
 bool conv256_eligible(const ConvArgs &a);                 // conv_mfma256.hip
 int launch_conv256(const ConvArgs &a, hipStream_t stream);
 bool conv3x3_panel_eligible(const ConvArgs &a);           // conv3x3_panel.hip (LDS-resident input panel, 9 taps per fetch)
