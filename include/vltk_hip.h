@@ -84,6 +84,22 @@ typedef struct vk_roi_params {
     int32_t max_detections;
 } vk_roi_params;
 
+/* Selection mode of the detections (model.roi_outputs.selection) and its knobs.
+ * VK_SELECT_CLASS_MAX: the reference's ROIOutputs.inference (class-max NMS over the threshold list); score_thresh is
+ *   accepted and unused, as upstream (do_nms frcnn.py:116 never reads it).
+ * VK_SELECT_PER_CLASS: NMS per class at roi.nms_thresh[0] (roi.num_nms_thresh must be 1), a box's confidence = its best
+ *   class that survives NMS (0 and class 0 when it survives in none; ties to the smaller class), ranked by confidence
+ *   descending (ties to the lower proposal row), the first min(max(#{(double)confidence >= score_thresh},
+ *   min_detections), max_detections, proposals of the image) are the output.  0 <= score_thresh <= 1 and
+ *   min_detections <= max_detections, else VK_EINVAL.  The contract in full: DESIGN.md section 15. */
+#define VK_SELECT_CLASS_MAX 0
+#define VK_SELECT_PER_CLASS 1
+typedef struct vk_select_params {
+    int32_t       mode;
+    double        score_thresh;
+    vk_roi_params roi;
+} vk_select_params;
+
 /* Device output block of one forward (caller-allocated, fixed capacity D =
  * max_detections per image; rows >= preds_per_image[n] are zero).  Mirrors the
  * OrderedDict returned by FRCNN.inference (frcnn.py:1996-2004). */
@@ -173,6 +189,18 @@ int vk_forward_begin_ignorey(vk_handle *h, const float *images_dev, int N, int H
                              const int32_t *image_hw, const float *scales_yx,
                              const vk_roi_params *rp, const vk_outputs *out_dev, void *stream, int64_t *ticket,
                              const vk_ignorey *ignorey);
+/* The detection forward with a selection mode (see vk_select_params); ignorey as above, NULL for none.  VK_SELECT_CLASS_MAX
+ * is exactly the entry point above on sp->roi.  VK_SELECT_PER_CLASS computes, after the box head, the soft-max of every class
+ * (stage "obj_scores" [K, ld] f32, K = N * POST_NMS_TOPK_TEST; the first C+1 columns of a row), bbox_pred over all 4C rows
+ * through the linear path in the predictor's precision (stage "box_deltas" [K, ld] f32, class c at columns 4c..4c+3; the 4
+ * columns of the one box with CLS_AGNOSTIC_BBOX_REG), then the selection (stages "max_conf" [N, R] f32, "attr_prob" [K] and "keep_ids");
+ * "chosen_deltas" is not produced.  A non-finite box of ANY class raises the reference's assertion from vk_forward_end
+ * (_clip_box runs on all R*C boxes, do_nms frcnn.py:121).  Its scores, deltas and confidences live in an arena of their own,
+ * taken on the first per-class forward (K * (5C + 4) floats: 0.31 GB at 32 x 300 x 1600) and never by the other mode. */
+int vk_forward_begin_select(vk_handle *h, const float *images_dev, int N, int H, int W,
+                            const int32_t *image_hw, const float *scales_yx,
+                            const vk_select_params *sp, const vk_outputs *out_dev, void *stream, int64_t *ticket,
+                            const vk_ignorey *ignorey);
 
 /* Region features for caller-supplied boxes (the reference's `proposals=` slot, frcnn.py:1924-1964, which is broken
  * upstream: `proposal_boxes` is never bound when proposals are given).  Detection, but with the RPN replaced by the
@@ -217,7 +245,9 @@ int vk_given_box_outputs(const float *obj_prob, const int32_t *obj_cls, const fl
 
 /* Intermediate tensors of the last forward, for stage-level parity tests.
  * name in {"res4","rpn_out","proposal_boxes","proposal_logits",
- * "proposal_counts","pooled","feature_pooled","obj_logits","attr_logits","chosen_deltas","keep_ids"};
+ * "proposal_counts","pooled","feature_pooled","obj_logits","attr_logits","chosen_deltas","keep_ids"}
+ * and, after a per-class forward (vk_forward_begin_select), {"obj_scores","box_deltas","max_conf","attr_prob"}
+ * ("attr_prob" [K] f32: each row's attribute probability, what attr_probs gathers);
  * "rpn_out" is the fused RPN head output [N,Hf,Wf,ld]: columns [0,A) objectness, [A,5A) deltas.
  * Returns a device pointer owned by the handle (valid until the next forward),
  * its dtype and its shape (up to 4 dims). */
@@ -490,6 +520,31 @@ int vk_roi_outputs(const float *obj_logits, int ld_obj, const float *attr_logits
                    int N, int R, int C, int A, const int32_t *image_hw, const float *scales_yx_dev,
                    const float *weights4_host, const vk_roi_params *rp, const vk_outputs *out,
                    int64_t *keep_ids_out, int32_t *nonfinite_flag, void *stream);
+
+/* Per-class selection (VK_SELECT_PER_CLASS, see vk_select_params) as a stage-level call, independent of a handle, in the
+ * manner of vk_roi_outputs; every array is a device array except weights4_host and sp.
+ *   obj_scores [K, ld_scores] f32: class probabilities (non-negative; vk_class_probs of the logits), the first C columns used;
+ *   attr_logits [K, ld_attr] f32 or NULL (attr_probs / attr_ids are then zero); box_deltas [K, ld_box] f32: class c at
+ *   columns 4c..4c+3, or with cls_agnostic the one box at columns 0..3; proposals [N, R, 4] + counts [N]; features [K, F]
+ *   f32 (F a multiple of 4, 16-byte aligned like out->roi_features); out of capacity sp->roi.max_detections per image;
+ *   keep_ids_out [N, max_detections] i64 and max_conf_out [N, R] f32 are optional; *nonfinite_flag is OR-ed with 1 when a
+ *   decoded box of any (row < counts[n], class) is not finite (the caller zeroes it).  1 <= R <= 1024, max_detections <= R.
+ * Synchronises `stream` before it returns (its scratch is freed).
+ * vk_class_probs: out[k][c] = soft-max(logits[k][0:n])[c] for c < n (ROIOutputs._predict_objs frcnn.py:1252-1255), in the
+ * arithmetic of vk_softmax_argmax.
+ * vk_class_boxes: out [N*R, C, 4] f32 = every (row, class) box exactly as the per-class NMS holds it (decode of box_deltas on
+ * the proposals, _clip_box to image_hw); rows >= counts[n] are zero; *nonfinite_flag (optional) is OR-ed with 1 as above.  The
+ * forward never materialises these; this is for callers and tests that want the device's own bits.  Does not synchronise. */
+int vk_class_boxes(const float *box_deltas, int ld_box, int cls_agnostic, const float *proposals, const int32_t *counts,
+                   int N, int R, int C, const int32_t *image_hw, const float *weights4_host, float *out,
+                   int32_t *nonfinite_flag, void *stream);
+int vk_class_probs(const float *logits, int ld, int K, int n, float *out, int ld_out, void *stream);
+int vk_per_class_select(const float *obj_scores, int ld_scores, const float *attr_logits, int ld_attr,
+                        const float *box_deltas, int ld_box, int cls_agnostic,
+                        const float *proposals, const int32_t *counts, const float *features, int F,
+                        int N, int R, int C, int A, const int32_t *image_hw, const float *scales_yx_dev,
+                        const float *weights4_host, const vk_select_params *sp, const vk_outputs *out,
+                        int64_t *keep_ids_out, float *max_conf_out, int32_t *nonfinite_flag, void *stream);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,7 @@ VK_ROUTE_GENERIC, VK_ROUTE_RING, VK_ROUTE_DUO, VK_ROUTE_WS, VK_ROUTE_GEMM4, VK_R
 VK_MAX_ANCHOR_DIM = 8
 VK_MAX_NMS_THRESH = 8
 VK_MAX_IGNOREY = 64
+VK_SELECT_CLASS_MAX, VK_SELECT_PER_CLASS = 0, 1
 
 # status code -> the Python exception type the reference raises in the same situation
 # (frcnn.py:1930 NotImplementedError, :148 AssertionError, :1789/:1850 EnvironmentError/OSError)
@@ -61,6 +62,10 @@ class vk_roi_params(C.Structure):
     ]
 
 
+class vk_select_params(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("score_thresh", C.c_double), ("roi", vk_roi_params)]
+
+
 class vk_outputs(C.Structure):
     _fields_ = [
         ("obj_ids", C.c_void_p), ("obj_probs", C.c_void_p), ("attr_ids", C.c_void_p),
@@ -91,6 +96,8 @@ SIGNATURES = {
                               C.POINTER(C.c_int64)]),
     "vk_forward_begin_ignorey": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(vk_roi_params), C.POINTER(vk_outputs), _P,
                                       C.POINTER(C.c_int64), C.POINTER(vk_ignorey)]),
+    "vk_forward_begin_select": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(vk_select_params), C.POINTER(vk_outputs), _P,
+                                     C.POINTER(C.c_int64), C.POINTER(vk_ignorey)]),
     "vk_forward_boxes_begin": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, C.POINTER(vk_outputs), _P, C.POINTER(C.c_int64)]),
     "vk_forward_end": (_I, [_P, C.c_int64]),
     "vk_given_boxes_ingest": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _F, _I, _P, _P]),
@@ -151,6 +158,10 @@ SIGNATURES = {
     "vk_chosen_deltas": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P]),
     "vk_roi_outputs": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, C.POINTER(_F),
                             C.POINTER(vk_roi_params), C.POINTER(vk_outputs), _P, _P, _P]),
+    "vk_class_boxes": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, C.POINTER(_F), _P, _P, _P]),
+    "vk_class_probs": (_I, [_P, _I, _I, _I, _P, _I, _P]),
+    "vk_per_class_select": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, C.POINTER(_F),
+                                 C.POINTER(vk_select_params), C.POINTER(vk_outputs), _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -180,7 +180,7 @@ struct vk_handle {
     std::vector<Block> res5;
     ConvLayer rpn_conv, rpn_heads;                  // rpn_heads = [objectness | anchor_deltas] fused 1x1
     ConvLayer cls_score, fc_attr, attr_score;       // plain GEMMs (1x1 "convs" over K RoIs)
-    void *bbox_w = nullptr;                         // [4C][F] in dt, unpadded rows (gathered per RoI)
+    void *bbox_w = nullptr;                         // [4C][F] in pdt (the predictor's precision), unpadded rows (gathered per RoI)
     float *bbox_b = nullptr;
     void *emb = nullptr;                            // [C+1][F/8] in dt
     float *cell_anchors = nullptr;                  // [A][4]
@@ -190,6 +190,12 @@ struct vk_handle {
     // arena
     char *arena = nullptr;
     size_t arena_bytes = 0;
+    // per-class selection (vk_forward_begin_select): its scores / all-class deltas / confidences live apart from the arena,
+    // so that the class-max mode never pays for them; taken on the first per-class forward, grown on need
+    char *pc_arena = nullptr;
+    size_t pc_arena_bytes = 0;
+    const void *bbox_lin_w = nullptr;               // bbox_pred as the linear path reads it: rows padded to whole 128-row tiles
+    const float *bbox_lin_b = nullptr;              // (bbox_w / bbox_b themselves when 4C is already a multiple of 128)
     int head_chunk = 9600;                           // RoIs per Res5 chunk (vk_set_option "head_chunk")
     int backbone_streams = 2;                        // 2: res3/res4 as two half-batches on two streams (option "backbone_streams")
     int backbone_split_min_batch = 8;                // ... from this batch size on (option "backbone_split_min_batch")
@@ -1105,6 +1111,7 @@ int vk_destroy(vk_handle *h) {
     (void)hipDeviceSynchronize();
     for (void *p : h->owned) (void)hipFree(p);
     if (h->arena) (void)hipFree(h->arena);
+    if (h->pc_arena) (void)hipFree(h->pc_arena);
     for (auto &e : h->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : h->ev_done)
@@ -1404,9 +1411,138 @@ int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
     return vk_forward_begin_ignorey(h, images_dev, N, H, W, image_hw, scales_yx, rp, out, stream, ticket, nullptr);
 }
 
+static int check_select_params(const vk_select_params *sp, const char *who) {
+    const vk_roi_params &rp = sp->roi;
+    VK_REQUIRE(rp.num_nms_thresh == 1, VK_EINVAL, "%s: per-class selection takes one NMS threshold, got a list of %d", who, rp.num_nms_thresh);
+    VK_REQUIRE(sp->score_thresh >= 0.0 && sp->score_thresh <= 1.0, VK_EINVAL, "%s: score_thresh=%g must be in [0, 1]", who, sp->score_thresh);
+    VK_REQUIRE(rp.min_detections <= rp.max_detections, VK_EINVAL, "%s: min_detections=%d exceeds max_detections=%d", who,
+               rp.min_detections, rp.max_detections);
+    return VK_OK;
+}
+
+// The per-class end of a detection forward (after fwd_head): soft-max of every class, bbox_pred over all its rows through the
+// linear path, per-class NMS + finalize (per_class.hip).  Stages "obj_scores", "box_deltas", "max_conf", "keep_ids".
+static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp, const float *scales_dev, const vk_outputs *out,
+                         hipStream_t s) {
+    const vk_config &c = h->cfg;
+    const int C = c.num_classes, F = h->res5_c, K = p.K, D = sp->roi.max_detections;
+    const int nrow = 4 * (c.cls_agnostic_bbox_reg ? 1 : C);
+    const int ld_cls = (C + 1 + 7) / 8 * 8, ld_box = (nrow + 7) / 8 * 8;
+    if (!h->bbox_lin_w) {      // first per-class forward: bbox_pred in the packed form (dense 1x1: row-major rows, zero rows up to a whole tile)
+        const int cp = vk_packed_cout(nrow);
+        if (cp == nrow) {
+            h->bbox_lin_w = h->bbox_w;
+            h->bbox_lin_b = h->bbox_b;
+        } else {
+            const size_t row = (size_t)F * dtype_size(h->pdt);
+            void *w = nullptr, *b = nullptr;
+            VK_TRY(dev_alloc(h, (size_t)cp * row, &w));
+            VK_TRY(dev_alloc(h, (size_t)cp * sizeof(float), &b));
+            VK_CHECK_HIP(hipMemsetAsync(w, 0, (size_t)cp * row, s));
+            VK_CHECK_HIP(hipMemsetAsync(b, 0, (size_t)cp * sizeof(float), s));
+            VK_CHECK_HIP(hipMemcpyAsync(w, h->bbox_w, (size_t)nrow * row, hipMemcpyDeviceToDevice, s));
+            VK_CHECK_HIP(hipMemcpyAsync(b, h->bbox_b, (size_t)nrow * sizeof(float), hipMemcpyDeviceToDevice, s));
+            h->bbox_lin_w = w;
+            h->bbox_lin_b = (const float *)b;
+        }
+    }
+    Carver cv(nullptr);
+    const size_t o_scores = cv.off;
+    cv.take((size_t)K * ld_cls * sizeof(float));
+    const size_t o_deltas = cv.off;
+    cv.take((size_t)K * ld_box * sizeof(float));
+    const size_t o_best = cv.off;
+    cv.take((size_t)K * sizeof(unsigned long long));
+    const size_t o_conf = cv.off;
+    cv.take((size_t)K * sizeof(float));
+    if (cv.off > h->pc_arena_bytes) {
+        if (h->pc_arena) {
+            VK_CHECK_HIP(hipDeviceSynchronize());
+            VK_CHECK_HIP(hipFree(h->pc_arena));
+            h->pc_arena = nullptr;
+            h->pc_arena_bytes = 0;
+        }
+        VK_CHECK_HIP(hipMalloc((void **)&h->pc_arena, cv.off));
+        h->pc_arena_bytes = cv.off;
+    }
+    float *scores = (float *)(h->pc_arena + o_scores), *deltas = (float *)(h->pc_arena + o_deltas);
+    float *max_conf = (float *)(h->pc_arena + o_conf);
+
+    VK_TRY(launch_class_probs(p.cls_logits, ld_cls, K, C + 1, scores, ld_cls, s));
+    ConvArgs g;
+    fill_conv_args(g, 1, 1, K, F, nrow, ld_box, 1, 1, 0, 1, 1, 0, h->pdt, VK_F32);
+    g.x = p.featT;
+    g.w = h->bbox_lin_w;
+    g.bias = h->bbox_lin_b;
+    g.y = deltas;
+    VK_TRY(launch_conv(g, s));
+    set_stage(h, "obj_scores", scores, VK_F32, {K, ld_cls});
+    set_stage(h, "box_deltas", deltas, VK_F32, {K, ld_box});
+    set_stage(h, "attr_prob", p.attr_prob, VK_F32, {K});
+    if (h->timing) VK_CHECK_HIP(hipEventRecord(h->ev[4], s));
+
+    PerClassArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scores = scores;
+    a.ld_scores = ld_cls;
+    a.deltas = deltas;
+    a.ld_box = ld_box;
+    a.agnostic = c.cls_agnostic_bbox_reg ? 1 : 0;
+    a.proposals = p.prop_boxes;
+    a.counts = p.prop_counts;
+    a.features = p.feat;
+    a.attr_prob = p.attr_prob;
+    a.attr_cls = p.attr_cls;
+    a.F = F;
+    a.R = p.R;
+    a.D = D;
+    a.C = C;
+    a.image_hw = p.image_hw;
+    a.scales_yx = scales_dev;
+    a.wx = c.roi_bbox_weights[0];
+    a.wy = c.roi_bbox_weights[1];
+    a.ww = c.roi_bbox_weights[2];
+    a.wh = c.roi_bbox_weights[3];
+    a.clampv = (float)std::log(1000.0 / 16.0);
+    a.thresh = sp->roi.nms_thresh[0];
+    a.score_thresh = sp->score_thresh;
+    a.mind = sp->roi.min_detections;
+    a.maxd = sp->roi.max_detections;
+    a.best = (unsigned long long *)(h->pc_arena + o_best);
+    a.max_conf = max_conf;
+    a.out = *out;
+    a.keep_ids = p.keep_ids;
+    a.nonfinite = p.nonfinite;
+    VK_TRY(launch_per_class_select(a, p.N, s));
+    set_stage(h, "max_conf", max_conf, VK_F32, {p.N, p.R});
+    set_stage(h, "keep_ids", p.keep_ids, VK_I64, {p.N, D});
+    return VK_OK;
+}
+
+// vk_forward_begin_ignorey / vk_forward_begin_select: sel == nullptr is the class-max mode on rp, else rp == &sel->roi
+static int forward_detect(vk_handle *h, const float *images_dev, int N, int H, int W, const int32_t *image_hw,
+                          const float *scales_yx, const vk_roi_params *rp, const vk_select_params *sel, const vk_outputs *out,
+                          void *stream, int64_t *ticket, const vk_ignorey *ignorey);
+
 int vk_forward_begin_ignorey(vk_handle *h, const float *images_dev, int N, int H, int W, const int32_t *image_hw,
                              const float *scales_yx, const vk_roi_params *rp, const vk_outputs *out, void *stream, int64_t *ticket,
                              const vk_ignorey *ignorey) {
+    return forward_detect(h, images_dev, N, H, W, image_hw, scales_yx, rp, nullptr, out, stream, ticket, ignorey);
+}
+
+int vk_forward_begin_select(vk_handle *h, const float *images_dev, int N, int H, int W, const int32_t *image_hw,
+                            const float *scales_yx, const vk_select_params *sp, const vk_outputs *out, void *stream, int64_t *ticket,
+                            const vk_ignorey *ignorey) {
+    VK_REQUIRE(sp, VK_EINVAL, "forward: null argument");
+    VK_REQUIRE(sp->mode == VK_SELECT_CLASS_MAX || sp->mode == VK_SELECT_PER_CLASS, VK_EINVAL, "forward: unknown selection mode %d", sp->mode);
+    if (sp->mode == VK_SELECT_PER_CLASS) VK_TRY(check_select_params(sp, "forward"));
+    return forward_detect(h, images_dev, N, H, W, image_hw, scales_yx, &sp->roi, sp->mode == VK_SELECT_PER_CLASS ? sp : nullptr, out,
+                          stream, ticket, ignorey);
+}
+
+static int forward_detect(vk_handle *h, const float *images_dev, int N, int H, int W, const int32_t *image_hw,
+                          const float *scales_yx, const vk_roi_params *rp, const vk_select_params *sel, const vk_outputs *out,
+                          void *stream, int64_t *ticket, const vk_ignorey *ignorey) {
     VK_REQUIRE(h && images_dev && image_hw && rp && out && ticket, VK_EINVAL, "forward: null argument");
     // the reference filters by the bands only when scales_yx is given too (frcnn.py:328); no bands == the plain launch sequence
     const vk_ignorey *ig = scales_yx && ignorey && ignorey->max_per_image > 0 ? ignorey : nullptr;
@@ -1478,6 +1614,10 @@ int vk_forward_begin_ignorey(vk_handle *h, const float *images_dev, int N, int H
 
     // ---- RoI heads + box predictor; the arg-max class's box regression ----
     VK_TRY(fwd_head(h, p, res4, s));
+    if (sel) {                 // per-class selection: every class's box regression, NMS per class
+        VK_TRY(fwd_per_class(h, p, sel, scales_yx ? p.scales : nullptr, out, s));
+        return fwd_close(h, p.nonfinite, s, ticket);
+    }
     const int F = h->res5_c;
     VK_TRY(launch_chosen_deltas(p.featT, F, h->bbox_w, h->bbox_b, p.obj_cls, c.cls_agnostic_bbox_reg, F, p.K, p.chosen, h->pdt, s));
     set_stage(h, "chosen_deltas", p.chosen, VK_F32, {p.K, 4});
@@ -1690,6 +1830,99 @@ int vk_roi_outputs(const float *obj_logits, int ld_obj, const float *attr_logits
         a.keep_ids = keep_ids_out;
         a.nonfinite = nonfinite_flag;
         st = launch_roi_final(a, N, s);
+    }
+    hipError_t e = hipStreamSynchronize(s);
+    (void)hipFree(scratch);
+    if (st != VK_OK) return st;
+    VK_CHECK_HIP(e);
+    return VK_OK;
+}
+
+int vk_class_probs(const float *logits, int ld, int K, int n, float *out, int ld_out, void *stream) {
+    VK_REQUIRE(logits && out && K >= 0 && n >= 1 && ld >= n && ld_out >= n, VK_EINVAL, "class_probs: bad arguments");
+    return launch_class_probs(logits, ld, K, n, out, ld_out, (hipStream_t)stream);
+}
+
+int vk_class_boxes(const float *box_deltas, int ld_box, int cls_agnostic, const float *proposals, const int32_t *counts, int N, int R,
+                   int C, const int32_t *image_hw, const float *weights4_host, float *out, int32_t *nonfinite_flag, void *stream) {
+    VK_REQUIRE(box_deltas && proposals && counts && image_hw && weights4_host && out, VK_EINVAL, "class_boxes: null argument");
+    PerClassArgs a;
+    memset(&a, 0, sizeof(a));
+    a.deltas = box_deltas;
+    a.ld_box = ld_box;
+    a.agnostic = cls_agnostic ? 1 : 0;
+    a.proposals = proposals;
+    a.counts = counts;
+    a.R = R;
+    a.C = C;
+    a.image_hw = image_hw;
+    a.wx = weights4_host[0];
+    a.wy = weights4_host[1];
+    a.ww = weights4_host[2];
+    a.wh = weights4_host[3];
+    a.clampv = (float)std::log(1000.0 / 16.0);
+    a.nonfinite = nonfinite_flag;
+    return launch_class_boxes(a, N, out, (hipStream_t)stream);
+}
+
+int vk_per_class_select(const float *obj_scores, int ld_scores, const float *attr_logits, int ld_attr, const float *box_deltas,
+                        int ld_box, int cls_agnostic, const float *proposals, const int32_t *counts, const float *features, int F,
+                        int N, int R, int C, int A, const int32_t *image_hw, const float *scales_yx_dev,
+                        const float *weights4_host, const vk_select_params *sp, const vk_outputs *out, int64_t *keep_ids_out,
+                        float *max_conf_out, int32_t *nonfinite_flag, void *stream) {
+    VK_REQUIRE(obj_scores && box_deltas && proposals && counts && features && image_hw && weights4_host && sp && out && nonfinite_flag,
+               VK_EINVAL, "per_class_select: null argument");
+    VK_REQUIRE(sp->mode == VK_SELECT_PER_CLASS, VK_EINVAL, "per_class_select: mode=%d is not VK_SELECT_PER_CLASS", sp->mode);
+    VK_TRY(check_select_params(sp, "per_class_select"));
+    VK_REQUIRE(N >= 1 && N <= 65535 && R >= 1 && R <= 1024 && C >= 1, VK_EINVAL, "per_class_select: N=%d R=%d C=%d (R at most 1024)", N, R, C);
+    VK_REQUIRE(sp->roi.max_detections >= 1 && sp->roi.max_detections <= R, VK_EINVAL, "per_class_select: max_detections=%d must be in 1..R=%d",
+               sp->roi.max_detections, R);
+    VK_REQUIRE(F >= 4 && F % 4 == 0, VK_EINVAL, "per_class_select: F=%d must be a positive multiple of 4", F);
+    VK_REQUIRE(!attr_logits || (A >= 1 && ld_attr >= A), VK_EINVAL, "per_class_select: A=%d ld_attr=%d", A, ld_attr);
+    hipStream_t s = (hipStream_t)stream;
+    const int K = N * R;
+    // scratch: the best-class words and the per-row attribute predictions (freed after the stream drains; stage-level entry point only)
+    char *scratch = nullptr;
+    const size_t per = align_up((size_t)K * 8, 256);
+    VK_CHECK_HIP(hipMalloc((void **)&scratch, per * 3));
+    float *attr_prob = (float *)(scratch + per);
+    int32_t *attr_cls = (int32_t *)(scratch + 2 * per);
+    int st = VK_OK;
+    if (attr_logits) st = launch_softmax_argmax(attr_logits, ld_attr, K, A, A, attr_prob, attr_cls, nullptr, s);
+    if (st == VK_OK) {
+        PerClassArgs a;
+        memset(&a, 0, sizeof(a));
+        a.scores = obj_scores;
+        a.ld_scores = ld_scores;
+        a.deltas = box_deltas;
+        a.ld_box = ld_box;
+        a.agnostic = cls_agnostic ? 1 : 0;
+        a.proposals = proposals;
+        a.counts = counts;
+        a.features = features;
+        a.attr_prob = attr_logits ? attr_prob : nullptr;
+        a.attr_cls = attr_logits ? attr_cls : nullptr;
+        a.F = F;
+        a.R = R;
+        a.D = sp->roi.max_detections;
+        a.C = C;
+        a.image_hw = image_hw;
+        a.scales_yx = scales_yx_dev;
+        a.wx = weights4_host[0];
+        a.wy = weights4_host[1];
+        a.ww = weights4_host[2];
+        a.wh = weights4_host[3];
+        a.clampv = (float)std::log(1000.0 / 16.0);
+        a.thresh = sp->roi.nms_thresh[0];
+        a.score_thresh = sp->score_thresh;
+        a.mind = sp->roi.min_detections;
+        a.maxd = sp->roi.max_detections;
+        a.best = (unsigned long long *)scratch;
+        a.max_conf = max_conf_out;
+        a.out = *out;
+        a.keep_ids = keep_ids_out;
+        a.nonfinite = nonfinite_flag;
+        st = launch_per_class_select(a, N, s);
     }
     hipError_t e = hipStreamSynchronize(s);
     (void)hipFree(scratch);

@@ -24,13 +24,6 @@ namespace vk {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ uint32_t desc_key32(float v) {
-    uint32_t u = __float_as_uint(v);
-    if (u == 0x80000000u) u = 0u;
-    uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ~asc;
-}
-
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
@@ -134,30 +127,6 @@ __global__ __launch_bounds__(256) void chosen_deltas_kernel(const T *__restrict_
         for (int j = 0; j < 4; ++j) out[(long)k * 4 + j] = acc[j] + bias[row0 + j];
     }
 }
-
-
-__device__ __forceinline__ void apply_deltas_roi(const float a[4], const float d[4], float wx, float wy, float ww,
-                                                 float wh, float clampv, float o[4]) {
-    float widths = a[2] - a[0];
-    float heights = a[3] - a[1];
-    float ctr_x = a[0] + 0.5f * widths;
-    float ctr_y = a[1] + 0.5f * heights;
-    float dx = d[0] / wx;
-    float dy = d[1] / wy;
-    float dw = d[2] / ww;
-    float dh = d[3] / wh;
-    dw = dw > clampv ? clampv : dw;
-    dh = dh > clampv ? clampv : dh;
-    float pcx = dx * widths + ctr_x;
-    float pcy = dy * heights + ctr_y;
-    float pw = expf(dw) * widths;
-    float ph = expf(dh) * heights;
-    o[0] = pcx - 0.5f * pw;
-    o[1] = pcy - 0.5f * ph;
-    o[2] = pcx + 0.5f * pw;
-    o[3] = pcy + 0.5f * ph;
-}
-
 // One workgroup per image.  LDS: keys[Rp2] u64 | box[R][4] f32 | removed[R] i32 | kept[D] i32
 __global__ __launch_bounds__(256) void roi_final_kernel(RoiFinalArgs a, int Rp2) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];

@@ -192,6 +192,68 @@ int launch_chosen_deltas(const void *x, int ldx, const void *w, const float *bia
 int launch_roi_final(RoiFinalArgs &a, int N, hipStream_t s);
 int launch_make_rois(const float *boxes, int N, int R, float *rois, hipStream_t s);
 
+// Sort key of a score for an ascending sort that ranks scores descending (-0 ranks as +0); the low word of the 64-bit key
+// holds the row index, so ties go to the lower index.  Shared by roi_out.hip and per_class.hip.
+__device__ __forceinline__ uint32_t desc_key32(float v) {
+    uint32_t u = __float_as_uint(v);
+    if (u == 0x80000000u) u = 0u;
+    uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ~asc;
+}
+
+// Box2BoxTransform.apply_deltas (frcnn.py:548-584) for one box, reference op order.  The one copy of the RoI decode:
+// roi_out.hip (the arg-max class's box) and per_class.hip (every class's box) both call it, and both files build with
+// -ffp-contract=off, so the two selection modes decode a (proposal, deltas) pair to the same bits.
+__device__ __forceinline__ void apply_deltas_roi(const float a[4], const float d[4], float wx, float wy, float ww,
+                                                 float wh, float clampv, float o[4]) {
+    float widths = a[2] - a[0];
+    float heights = a[3] - a[1];
+    float ctr_x = a[0] + 0.5f * widths;
+    float ctr_y = a[1] + 0.5f * heights;
+    float dx = d[0] / wx;
+    float dy = d[1] / wy;
+    float dw = d[2] / ww;
+    float dh = d[3] / wh;
+    dw = dw > clampv ? clampv : dw;
+    dh = dh > clampv ? clampv : dh;
+    float pcx = dx * widths + ctr_x;
+    float pcy = dy * heights + ctr_y;
+    float pw = expf(dw) * widths;
+    float ph = expf(dh) * heights;
+    o[0] = pcx - 0.5f * pw;
+    o[1] = pcy - 0.5f * ph;
+    o[2] = pcx + 0.5f * pw;
+    o[3] = pcy + 0.5f * ph;
+}
+
+// ---- per_class.hip (roi_outputs.selection = "per_class": vk_forward_begin_select, vk_per_class_select, vk_class_probs) ----
+struct PerClassArgs {
+    const float *scores;      // [K, ld_scores] class probabilities; the first C columns are used
+    int ld_scores;
+    const float *deltas;      // [K, ld_box]: 4 deltas per class (class c at column 4c), or 4 in all when agnostic
+    int ld_box, agnostic;
+    const float *proposals;   // [N, R, 4]
+    const int32_t *counts;    // [N]
+    const float *features;    // [K, F]
+    const float *attr_prob;   // [K] or nullptr
+    const int32_t *attr_cls;
+    int F, R, D, C;
+    const int32_t *image_hw;
+    const float *scales_yx;
+    float wx, wy, ww, wh, clampv;
+    double thresh, score_thresh;
+    int mind, maxd;
+    unsigned long long *best;   // [K] scratch: (score bits << 32) | (C - c) of the best surviving class, 0 = none
+    float *max_conf;            // [K] out (optional): max_conf[r], 0 for rows >= counts[n]
+    vk_outputs out;
+    int64_t *keep_ids;
+    int32_t *nonfinite;
+};
+int launch_class_probs(const float *logits, int ld, int K, int n, float *out, int ld_out, hipStream_t s);
+int launch_per_class_select(PerClassArgs &a, int N, hipStream_t s);
+// out [N*R, C, 4]: every (row, class) box as the NMS kernel holds it; uses deltas, proposals, counts, image_hw, the weights
+int launch_class_boxes(PerClassArgs &a, int N, float *out, hipStream_t s);
+
 // assign_boxes_to_levels frcnn.py:444-460 for one box: floor(canonical_level + log2(sqrt(area) / canonical_size + 1e-8)),
 // clamped to [min_level, max_level], minus min_level.  The one copy of the rule: fpn.hip's assign_levels_kernel and
 // given_boxes.hip's ingest both call it, and both files build with -ffp-contract=off, so their levels are bit-equal.

@@ -5,7 +5,8 @@ vltk/modeling/frcnn.py:1743-2004): `FRCNN(cfg)`, `FRCNN.from_pretrained(path,
 config=...)` (local paths only), `model(images, image_shapes, scales_yx=...,
 **kwargs)` returning the 7-key OrderedDict, and the mutable
 `model.roi_outputs.{nms_thresh, score_thresh, min_detections, max_detections}`
-attributes callers set (tests/frcnn_test.py:16-19).
+attributes callers set (tests/frcnn_test.py:16-19), plus `model.roi_outputs.selection`
+("class_max", the reference's rule, or "per_class": NMS per class with a live score_thresh).
 
 All arithmetic runs in libvltk_hip.so (hand-written gfx950 kernels); torch is
 used only to own device memory and to hand out result tensors.  There is no
@@ -25,15 +26,29 @@ from .layers import DTYPES, TORCH_DTYPES, stream
 from .parallel import OutputBlock, output_spec
 
 
+SELECTIONS = ("class_max", "per_class")
+
+
 class ROIOutputs:
-    """The mutable knobs of the reference's ROIOutputs (frcnn.py:1229-1240)."""
+    """The mutable knobs of the reference's ROIOutputs (frcnn.py:1229-1240), and `selection`, which is this project's.
+
+    selection = "class_max" (the default): the reference's rule -- NMS over each box's arg-max class, over the list of
+    nms_thresh, until the count lands in [min_detections, max_detections].  score_thresh is accepted and unused, as
+    upstream (do_nms frcnn.py:116 never reads it).
+
+    selection = "per_class" (C4 model): NMS per class at the one nms_thresh, a box's confidence is
+    its best class that survives NMS, boxes are ranked by confidence and those at or above score_thresh are kept, the
+    count bounded to [min_detections, max_detections] (and the image's proposals).  obj_ids / obj_probs / boxes are that
+    class, its probability and its regressed box; attr_ids / attr_probs are the reference's per-proposal values.  A list
+    of several nms_thresh, min_detections > max_detections or a score_thresh outside [0, 1] is a ValueError."""
 
     def __init__(self, cfg):
-        self.score_thresh = cfg.ROI_HEADS.SCORE_THRESH_TEST     # accepted and unused, as upstream (frcnn.py:116)
+        self.score_thresh = cfg.ROI_HEADS.SCORE_THRESH_TEST     # read by selection = "per_class" only
         self.min_detections = cfg.MIN_DETECTIONS
         self.max_detections = cfg.MAX_DETECTIONS
         nms_thresh = cfg.ROI_HEADS.NMS_THRESH_TEST
         self.nms_thresh = list(nms_thresh) if isinstance(nms_thresh, (list, tuple)) else [nms_thresh]
+        self.selection = "class_max"
 
     def params(self):
         """The knobs as the library's vk_roi_params; ValueError beyond VK_MAX_NMS_THRESH thresholds."""
@@ -46,6 +61,27 @@ class ROIOutputs:
             rp.nms_thresh[i] = float(t)
         rp.min_detections, rp.max_detections = int(self.min_detections), int(self.max_detections)
         return rp
+
+    def select_params(self):
+        """Validate `selection` and its knobs -> None for "class_max" (the forward then takes params()), the library's
+        vk_select_params for "per_class".  ValueError: an unknown selection; in "per_class" a list of more (or fewer) than
+        one nms_thresh (never silently ignored), min_detections > max_detections, a score_thresh outside [0, 1]."""
+        sel = getattr(self, "selection", "class_max")
+        if sel not in SELECTIONS:
+            raise ValueError(f"roi_outputs.selection={sel!r} must be one of {SELECTIONS}")
+        if sel == "class_max":
+            return None
+        thr = list(self.nms_thresh)
+        if len(thr) != 1:
+            raise ValueError(f'selection="per_class" takes one nms_thresh, got the list {thr}')
+        if int(self.min_detections) > int(self.max_detections):
+            raise ValueError(f"min_detections={int(self.min_detections)} exceeds max_detections={int(self.max_detections)}")
+        score = float(self.score_thresh)
+        if not 0.0 <= score <= 1.0:
+            raise ValueError(f"score_thresh={score} must be in [0, 1]")
+        sp = L.vk_select_params()
+        sp.mode, sp.score_thresh, sp.roi = L.VK_SELECT_PER_CLASS, score, self.params()
+        return sp
 
 
 def _c_config(cfg, dt):
@@ -432,7 +468,11 @@ class FRCNN:
         ignorey (detection only; with `proposals` a ValueError): horizontal bands whose RPN proposals are removed or
         trimmed (find_top_rpn_proposals frcnn.py:328-366) -- one [N, J, 2] array / tensor or N [J_i, 2] ones, rows (y0, y1)
         divided by scales_yx[n][1]; at most 64 per image.  Applied only with scales_yx, as in the reference (a UserWarning
-        without).  See pack_ignorey and DESIGN §13."""
+        without).  See pack_ignorey and DESIGN §13.
+
+        Which detections come out is roi_outputs.selection's: "class_max" (the reference's rule, the default) or
+        "per_class" (NMS per class, a live score_thresh; see ROIOutputs and DESIGN §15).  The given-box forward ignores
+        roi_outputs; ignorey composes with either selection, because it acts on the proposals."""
         if proposals is not None and self.given_boxes:         # before anything is enqueued
             counts = _validate_proposals(proposals, len(images))[1]
             check_given_width(int(counts.max(initial=0)), kwargs.get("max_detections"))
@@ -462,10 +502,11 @@ class FRCNN:
         return images, hw, sc, given, ig
 
     def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None):
-        """Enqueue a forward and return at once (vk_forward_begin, or vk_forward_boxes_begin with `proposals`, see
-        forward()); `.wait(**kwargs)` on the returned handle finishes it (vk_forward_end) and formats the outputs like
-        forward().  Up to four may be in flight, detection and given-box forwards mixed; they must be waited for in
-        order, on the same stream.  The caller must not modify `images` (or the proposals) before wait() returns."""
+        """Enqueue a forward and return at once (vk_forward_begin, vk_forward_begin_select with
+        roi_outputs.selection = "per_class", or vk_forward_boxes_begin with `proposals`, see forward()); `.wait(**kwargs)`
+        on the returned handle finishes it (vk_forward_end) and formats the outputs like forward().  Up to four may be in
+        flight, detection and given-box forwards mixed; they must be waited for in order, on the same stream.  The caller
+        must not modify `images` (or the proposals) before wait() returns."""
         images, hw, sc, given, ig = self._prepare(images, image_shapes, proposals, scales_yx, ignorey)
         N, _, H, W = images.shape
         F = self.config.RESNETS.RES2_OUT_CHANNELS * 8
@@ -482,11 +523,19 @@ class FRCNN:
             st = _Ticket(ticket.value, bufs, (images, boxes))
             self._open.append(st)
             return PendingForward(self, st, hw, given_width=B)
+        sp = self.roi_outputs.select_params()        # None: selection = "class_max", the entry points below
         rp = self.roi_outputs.params()
         # one flat block, the seven arrays are views (so the multi-GPU exchange is a single all-gather: parallel.py)
         bufs = OutputBlock(output_spec(N, rp.max_detections, F), device=dev)
         out = L.vk_outputs(*[bufs[k].data_ptr() for k in bufs])
-        if ig is None:
+        if sp is not None:                           # per-class NMS with a live score_thresh; ignorey acts before it
+            igs = None
+            if ig is not None:
+                bands, bcounts, f64 = ig
+                igs = C.byref(L.vk_ignorey(bands.ctypes.data, bcounts.ctypes.data, bands.shape[1], int(f64)))
+            L.call("vk_forward_begin_select", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p), scp,
+                   C.byref(sp), C.byref(out), s, C.byref(ticket), igs)
+        elif ig is None:
             L.call("vk_forward_begin", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p), scp, C.byref(rp),
                    C.byref(out), s, C.byref(ticket))
         else:                                      # the host bands are copied into the ticket's slot before the call returns

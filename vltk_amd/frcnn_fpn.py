@@ -200,7 +200,10 @@ class FRCNNFPN(FRCNN):
     # ---- forward ----
     def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None):
         """Detection, or with `proposals` region features for exactly those boxes (FRCNN.forward).  The forward
-        runs to its end here; the returned handle's wait() / wait_raw() only format / hand out the outputs."""
+        runs to its end here; the returned handle's wait() / wait_raw() only format / hand out the outputs.
+        roi_outputs.selection = "per_class" is the C4 model's: detection with it raises ValueError here."""
+        if proposals is None and self.roi_outputs.select_params() is not None:       # before anything is enqueued
+            raise ValueError('roi_outputs.selection="per_class" is not available on the FPN detector (C4 model only)')
         images, hw, sc, given, ig = self._prepare(images, image_shapes, proposals, scales_yx, ignorey)
         if given is not None and int(self.config.ROI_BOX_HEAD.FC_DIM) % 4:
             raise ValueError(f"given boxes need ROI_BOX_HEAD.FC_DIM a multiple of 4, got {int(self.config.ROI_BOX_HEAD.FC_DIM)}")
