@@ -151,9 +151,25 @@ int vk_load_weights(vk_handle *h, const char *name, const void *host_ptr,
 int vk_finalize(vk_handle *h);
 int vk_destroy(vk_handle *h);
 
-/* Tunables.  "head_chunk": RoIs per Res5-head chunk (0 = all RoIs in one pass; default 9600 or
- * the VK_HEAD_CHUNK environment variable).  Results do not depend on it. */
+/* Tunables.  Results do not depend on any of them (bit for bit); a value out of range is VK_EINVAL.
+ *   "head_chunk"               RoIs per Res5-head chunk, 0 = all RoIs in one pass (default 9600, VK_HEAD_CHUNK)
+ *   "backbone_streams"         1..4: res3 / res4 as that many image groups on as many streams (default 2, VK_BACKBONE_STREAMS)
+ *   "backbone_split_min_batch" ... from this batch size on (default 8)
+ *   "head_streams"             1 or 2: each Res5 chunk as two half-chunks on two streams (default 1, VK_HEAD_STREAMS)
+ *   "head_split_min_rois"      ... for chunks of at least this many RoIs (default 512)
+ *   "forward_lanes"            1 or 2 (default 2, VK_FORWARD_LANES): with 2, forwards of one handle that are in flight
+ *                              together (vk_forward_begin) alternate between two working sets and two internal streams and
+ *                              run beside each other on the device; the second working set is allocated when two forwards
+ *                              first overlap (if it does not fit, the handle stays with one).  1: one working set, every
+ *                              forward on the caller's stream.  The per-launch and per-stage timers force 1 while they are on.
+ * The environment variables are read by vk_create.  vk_option_check validates a value without a handle and
+ * vk_option_default gives the value a new handle starts with (the variable, where it holds a valid value); both are host only.
+ * vk_get_option reads an option back, and two read-only counters for tests and tools: "working_sets" (arenas the handle
+ * holds: 0, 1 or 2) and "lane_forwards" (forwards that ran on a stream of the handle's own since vk_create). */
 int vk_set_option(vk_handle *h, const char *key, int value);
+int vk_get_option(vk_handle *h, const char *key, int *value);
+int vk_option_check(const char *key, int value);
+int vk_option_default(const char *key, int *value);
 
 /* Number of weight tensors the model expects and their names (strict load). */
 int vk_num_weights(vk_handle *h, int *count);
@@ -175,9 +191,14 @@ int vk_forward(vk_handle *h, const float *images_dev, int N, int H, int W,
  * (the reference's loop is strictly serial, abc/extraction.py:189-213; on the GPU that leaves the device idle while the
  * host formats one batch and launches the next).  vk_forward_begin enqueues everything on `stream` and returns a
  * ticket; vk_forward_end(ticket) waits for that forward only, and raises the non-finite assertion (frcnn.py:148).
- * Tickets must be ended in order; at most 4 may be open.  All forwards of a handle share its workspace: they must be
- * enqueued on the same stream (they are stream-ordered, not concurrent); `image_hw` / `scales_yx` are consumed before
- * _begin returns; the output buffers of different tickets must be distinct.  vk_forward == begin + end. */
+ * Tickets must be ended in order; at most 4 may be open.  `image_hw` / `scales_yx` are consumed before _begin returns.
+ * With "forward_lanes" = 2 (the default) a forward that begins while another is open runs on a stream of the handle's
+ * own, in the working set the open one does not use: it starts once everything enqueued on `stream` before _begin has
+ * finished (inputs ready), and vk_forward_end makes `stream` wait for the ticket's completion before it returns, so
+ * work enqueued on `stream` after _end sees the outputs.  Until _end of its ticket, `images_dev`, the given boxes and
+ * the out_dev buffers belong to that forward: they must not be written, freed or reused (for another ticket or
+ * anything else), not even by work enqueued on `stream` after _begin, which no longer orders behind the forward; and
+ * `stream` must stay alive.  Pass the same stream to every _begin.  vk_forward == begin + end. */
 int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
                      const int32_t *image_hw, const float *scales_yx,
                      const vk_roi_params *rp, const vk_outputs *out_dev, void *stream, int64_t *ticket);

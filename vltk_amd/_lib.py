@@ -89,6 +89,9 @@ SIGNATURES = {
     "vk_finalize": (_I, [_P]),
     "vk_destroy": (_I, [_P]),
     "vk_set_option": (_I, [_P, C.c_char_p, _I]),
+    "vk_get_option": (_I, [_P, C.c_char_p, C.POINTER(_I)]),
+    "vk_option_check": (_I, [C.c_char_p, _I]),
+    "vk_option_default": (_I, [C.c_char_p, C.POINTER(_I)]),
     "vk_num_weights": (_I, [_P, C.POINTER(_I)]),
     "vk_weight_name": (_I, [_P, _I, C.POINTER(C.c_char_p)]),
     "vk_forward": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(vk_roi_params), C.POINTER(vk_outputs), _P]),

@@ -8,7 +8,7 @@
 //
 // Data layout in HBM: every activation is NHWC in the handle's precision; one arena
 // (single hipMalloc, re-grown only when a larger problem arrives) holds all intermediates
-// so the steady state allocates nothing.  The Res5 head runs over RoI *chunks* so that the
+// so the steady state allocates nothing; a second one serves forwards that overlap (fwd_route).  The Res5 head runs over RoI *chunks* so that the
 // chunk's intermediates (pooled 14x14x1024 -> ... -> 14x14x2048) stay resident in the
 // 256 MiB Infinity Cache between consecutive convolutions instead of round-tripping HBM.
 #include <cmath>
@@ -163,6 +163,12 @@ static const int kBlocks[3][4] = {{3, 4, 6, 3}, {3, 4, 23, 3}, {3, 8, 36, 3}};  
 
 using namespace vk;
 
+// the built-in values of the options (vk_set_option); vk_option_default puts the VK_* variables over them
+static constexpr struct {
+    int head_chunk = 9600, backbone_streams = 2, backbone_split_min_batch = 8, head_streams = 1, head_split_min_rois = 512;
+    int forward_lanes = 2;
+} kDefaults;
+
 struct vk_handle {
     vk_config cfg;
     int device = 0;
@@ -187,20 +193,36 @@ struct vk_handle {
     int A = 0, res4_c = 0, res5_c = 0, hid = 0, emb_dim = 0;
     std::vector<void *> owned;                      // device allocations to free
 
-    // arena
-    char *arena = nullptr;
-    size_t arena_bytes = 0;
-    // per-class selection (vk_forward_begin_select): its scores / all-class deltas / confidences live apart from the arena,
-    // so that the class-max mode never pays for them; taken on the first per-class forward, grown on need
-    char *pc_arena = nullptr;
-    size_t pc_arena_bytes = 0;
+    // Everything a forward writes between fwd_open and fwd_close, twice (option "forward_lanes" = 2): ticket t works in
+    // sets[t & 1] on lanes[t & 1], so that consecutive forwards run beside each other on the device.  The second set is
+    // taken the first time a forward begins while another is open; until then (and with one lane) every forward uses
+    // sets[0] on the caller's stream.
+    struct WorkSet {
+        char *arena = nullptr;
+        size_t arena_bytes = 0;
+        // per-class selection (vk_forward_begin_select): its scores / all-class deltas / confidences live apart from the arena,
+        // so that the class-max mode never pays for them; taken on the first per-class forward, grown on need
+        char *pc_arena = nullptr;
+        size_t pc_arena_bytes = 0;
+    } sets[2];
+    struct Lane {
+        hipStream_t main = nullptr;                  // the lane's own stream (two-set mode only)
+        hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+        hipEvent_t more_joins[2] = {nullptr, nullptr};
+    } lanes[2];
+    int forward_lanes = kDefaults.forward_lanes;                           // option "forward_lanes" / VK_FORWARD_LANES: 1 = every forward on the caller's stream
+    bool two_sets = false;                           // forwards have overlapped: tickets alternate between the sets from now on
+    bool two_sets_failed = false;                    // the second arena could not be allocated: one set for the rest of the handle's life
+    int64_t lane_forwards = 0;                       // forwards that were enqueued on a lane's stream (vk_get_option "lane_forwards")
+    int cur_set = 0;                                 // the set / caller's stream of the forward being enqueued (fwd_open .. fwd_close)
+    hipStream_t cur_caller = nullptr;
     const void *bbox_lin_w = nullptr;               // bbox_pred as the linear path reads it: rows padded to whole 128-row tiles
     const float *bbox_lin_b = nullptr;              // (bbox_w / bbox_b themselves when 4C is already a multiple of 128)
-    int head_chunk = 9600;                           // RoIs per Res5 chunk (vk_set_option "head_chunk")
-    int backbone_streams = 2;                        // 2: res3/res4 as two half-batches on two streams (option "backbone_streams")
-    int backbone_split_min_batch = 8;                // ... from this batch size on (option "backbone_split_min_batch")
-    int head_streams = 1;                            // 2: each Res5 chunk as two half-chunks on two streams (option "head_streams")
-    int head_split_min_rois = 512;                   // ... for chunks of at least this many RoIs (option "head_split_min_rois")
+    int head_chunk = kDefaults.head_chunk;                           // RoIs per Res5 chunk (vk_set_option "head_chunk")
+    int backbone_streams = kDefaults.backbone_streams;                        // 2: res3/res4 as two half-batches on two streams (option "backbone_streams")
+    int backbone_split_min_batch = kDefaults.backbone_split_min_batch;                // ... from this batch size on (option "backbone_split_min_batch")
+    int head_streams = kDefaults.head_streams;                            // 2: each Res5 chunk as two half-chunks on two streams (option "head_streams")
+    int head_split_min_rois = kDefaults.head_split_min_rois;                   // ... for chunks of at least this many RoIs (option "head_split_min_rois")
 
     // stage bookkeeping of the last forward
     struct Stage {
@@ -213,10 +235,10 @@ struct vk_handle {
     KernelTimer *ktimer = nullptr;
     bool timing = false;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipStream_t side = nullptr;                     // second stream of the res4 stage (half-batch pipelining)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipStream_t more_sides[2] = {nullptr, nullptr};  // third / fourth stream when backbone_streams is 3 / 4
-    hipEvent_t more_joins[2] = {nullptr, nullptr};
+    // second stream of the res4 stage (half-batch pipelining), third / fourth when backbone_streams is 3 / 4.  Both lanes
+    // fork onto the same side streams (the fork / join events are the lane's): a process stays within four streams
+    hipStream_t side = nullptr;
+    hipStream_t more_sides[2] = {nullptr, nullptr};
     bool ev_valid = false;
     // forwards in flight (vk_forward_begin .. vk_forward_end): ticket t uses slot t % VK_MAX_INFLIGHT
     static constexpr int VK_MAX_INFLIGHT = 4;
@@ -224,6 +246,10 @@ struct vk_handle {
     char *meta_host = nullptr;                      // pinned [VK_MAX_INFLIGHT][meta_cap]: image_hw + scales_yx of each forward
     size_t meta_cap = 0;
     hipEvent_t ev_done[VK_MAX_INFLIGHT] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev_in[VK_MAX_INFLIGHT] = {nullptr, nullptr, nullptr, nullptr};        // the caller's stream at _begin (inputs ready)
+    hipStream_t slot_stream[VK_MAX_INFLIGHT] = {nullptr, nullptr, nullptr, nullptr}; // where the ticket's forward was enqueued
+    hipStream_t slot_caller[VK_MAX_INFLIGHT] = {nullptr, nullptr, nullptr, nullptr}; // the stream its caller passed
+    int slot_set[VK_MAX_INFLIGHT] = {-1, -1, -1, -1};                                // its working set (-1: it launched nothing)
     int64_t next_ticket = 0, oldest_open = 0;       // tickets [oldest_open, next_ticket) have not been ended
 };
 
@@ -904,12 +930,10 @@ int vk_create(const vk_config *cfg, int device, vk_handle **out) {
     h->device = device;
     h->dt = (vk_dtype)cfg->precision;
     if (getenv("VK_PREDICTOR_FP16")) h->pdt = h->dt;            // A/B switch: round 1's 16-bit predictor
-    const char *env = getenv("VK_HEAD_CHUNK");
-    if (env && atoi(env) > 0) h->head_chunk = atoi(env);
-    if (const char *bs = getenv("VK_BACKBONE_STREAMS"))
-        if (bs[0] >= '1' && bs[0] <= '4') h->backbone_streams = bs[0] - '0';
-    if (const char *hs = getenv("VK_HEAD_STREAMS"))
-        if (hs[0] == '1' || hs[0] == '2') h->head_streams = hs[0] - '0';
+    (void)vk_option_default("head_chunk", &h->head_chunk);              // the built-in defaults or the VK_* variables
+    (void)vk_option_default("backbone_streams", &h->backbone_streams);
+    (void)vk_option_default("head_streams", &h->head_streams);
+    (void)vk_option_default("forward_lanes", &h->forward_lanes);
     const int di = cfg->depth == 50 ? 0 : (cfg->depth == 101 ? 1 : 2);
     add_conv_names(h->names, "backbone.stem.conv1", true);
     h->stem = ConvLayer{"backbone.stem.conv1", 3, cfg->stem_out_channels, 7, 2, 3, 1, true, true};
@@ -1075,34 +1099,74 @@ int vk_finalize(vk_handle *h) {
     return VK_OK;
 }
 
-int vk_set_option(vk_handle *h, const char *key, int value) {
-    VK_REQUIRE(h && key, VK_EINVAL, "set_option: null argument");
+int vk_option_check(const char *key, int value) {
+    VK_REQUIRE(key, VK_EINVAL, "option: null key");
     if (!strcmp(key, "head_chunk")) {
         VK_REQUIRE(value >= 0, VK_EINVAL, "head_chunk must be >= 0 (0 = all RoIs at once)");
-        h->head_chunk = value;
-        return VK_OK;
-    }
-    if (!strcmp(key, "backbone_streams")) {
+    } else if (!strcmp(key, "backbone_streams")) {
         VK_REQUIRE(value >= 1 && value <= 4, VK_EINVAL, "backbone_streams must be 1..4");
-        h->backbone_streams = value;
-        return VK_OK;
-    }
-    if (!strcmp(key, "head_streams")) {
+    } else if (!strcmp(key, "head_streams")) {
         VK_REQUIRE(value == 1 || value == 2, VK_EINVAL, "head_streams must be 1 or 2");
-        h->head_streams = value;
-        return VK_OK;
-    }
-    if (!strcmp(key, "head_split_min_rois")) {
+    } else if (!strcmp(key, "forward_lanes")) {
+        VK_REQUIRE(value == 1 || value == 2, VK_EINVAL, "forward_lanes must be 1 or 2");
+    } else if (!strcmp(key, "head_split_min_rois")) {
         VK_REQUIRE(value >= 2, VK_EINVAL, "head_split_min_rois must be >= 2");
-        h->head_split_min_rois = value;
-        return VK_OK;
-    }
-    if (!strcmp(key, "backbone_split_min_batch")) {
+    } else if (!strcmp(key, "backbone_split_min_batch")) {
         VK_REQUIRE(value >= 2, VK_EINVAL, "backbone_split_min_batch must be >= 2");
-        h->backbone_split_min_batch = value;
-        return VK_OK;
+    } else {
+        VK_REQUIRE(false, VK_EINVAL, "unknown option '%s'", key);
     }
-    VK_REQUIRE(false, VK_EINVAL, "unknown option '%s'", key);
+    return VK_OK;
+}
+
+int vk_option_default(const char *key, int *value) {
+    VK_REQUIRE(key && value, VK_EINVAL, "option: null argument");
+    if (!strcmp(key, "head_chunk")) {
+        const char *env = getenv("VK_HEAD_CHUNK");
+        *value = env && atoi(env) > 0 ? atoi(env) : kDefaults.head_chunk;          // (0 is set with vk_set_option only)
+    } else if (!strcmp(key, "backbone_streams")) {
+        const char *bs = getenv("VK_BACKBONE_STREAMS");
+        *value = bs && bs[0] >= '1' && bs[0] <= '4' ? bs[0] - '0' : kDefaults.backbone_streams;
+    } else if (!strcmp(key, "head_streams")) {
+        const char *hs = getenv("VK_HEAD_STREAMS");
+        *value = hs && (hs[0] == '1' || hs[0] == '2') ? hs[0] - '0' : kDefaults.head_streams;
+    } else if (!strcmp(key, "forward_lanes")) {     // "1" or "2" exactly; anything else is ignored
+        const char *fl = getenv("VK_FORWARD_LANES");
+        *value = fl && (fl[0] == '1' || fl[0] == '2') && !fl[1] ? fl[0] - '0' : kDefaults.forward_lanes;
+    } else if (!strcmp(key, "head_split_min_rois")) {
+        *value = kDefaults.head_split_min_rois;
+    } else if (!strcmp(key, "backbone_split_min_batch")) {
+        *value = kDefaults.backbone_split_min_batch;
+    } else {
+        VK_REQUIRE(false, VK_EINVAL, "unknown option '%s'", key);
+    }
+    return VK_OK;
+}
+
+int vk_get_option(vk_handle *h, const char *key, int *value) {
+    VK_REQUIRE(h && key && value, VK_EINVAL, "get_option: null argument");
+    if (!strcmp(key, "head_chunk")) *value = h->head_chunk;
+    else if (!strcmp(key, "backbone_streams")) *value = h->backbone_streams;
+    else if (!strcmp(key, "head_streams")) *value = h->head_streams;
+    else if (!strcmp(key, "forward_lanes")) *value = h->forward_lanes;
+    else if (!strcmp(key, "head_split_min_rois")) *value = h->head_split_min_rois;
+    else if (!strcmp(key, "backbone_split_min_batch")) *value = h->backbone_split_min_batch;
+    else if (!strcmp(key, "working_sets")) *value = (h->sets[0].arena ? 1 : 0) + (h->sets[1].arena ? 1 : 0);   // read-only: arenas held
+    else if (!strcmp(key, "lane_forwards")) *value = (int)std::min<int64_t>(h->lane_forwards, INT32_MAX);    // read-only: forwards enqueued on a lane's stream
+    else VK_REQUIRE(false, VK_EINVAL, "unknown option '%s'", key);
+    return VK_OK;
+}
+
+int vk_set_option(vk_handle *h, const char *key, int value) {
+    VK_REQUIRE(h && key, VK_EINVAL, "set_option: null argument");
+    VK_TRY(vk_option_check(key, value));
+    if (!strcmp(key, "head_chunk")) h->head_chunk = value;
+    if (!strcmp(key, "backbone_streams")) h->backbone_streams = value;
+    if (!strcmp(key, "head_streams")) h->head_streams = value;
+    if (!strcmp(key, "forward_lanes")) h->forward_lanes = value;
+    if (!strcmp(key, "head_split_min_rois")) h->head_split_min_rois = value;
+    if (!strcmp(key, "backbone_split_min_batch")) h->backbone_split_min_batch = value;
+    return VK_OK;
 }
 
 int vk_destroy(vk_handle *h) {
@@ -1110,21 +1174,28 @@ int vk_destroy(vk_handle *h) {
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     for (void *p : h->owned) (void)hipFree(p);
-    if (h->arena) (void)hipFree(h->arena);
-    if (h->pc_arena) (void)hipFree(h->pc_arena);
+    for (auto &ws : h->sets) {
+        if (ws.arena) (void)hipFree(ws.arena);
+        if (ws.pc_arena) (void)hipFree(ws.pc_arena);
+    }
     for (auto &e : h->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : h->ev_done)
         if (e) (void)hipEventDestroy(e);
+    for (auto &e : h->ev_in)
+        if (e) (void)hipEventDestroy(e);
     if (h->flag_host) (void)hipHostFree(h->flag_host);
     if (h->meta_host) (void)hipHostFree(h->meta_host);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->side) (void)hipStreamDestroy(h->side);
-    for (int i = 0; i < 2; ++i) {
-        if (h->more_joins[i]) (void)hipEventDestroy(h->more_joins[i]);
-        if (h->more_sides[i]) (void)hipStreamDestroy(h->more_sides[i]);
+    for (auto &ln : h->lanes) {
+        if (ln.ev_fork) (void)hipEventDestroy(ln.ev_fork);
+        if (ln.ev_join) (void)hipEventDestroy(ln.ev_join);
+        for (auto &e : ln.more_joins)
+            if (e) (void)hipEventDestroy(e);
+        if (ln.main) (void)hipStreamDestroy(ln.main);
     }
+    if (h->side) (void)hipStreamDestroy(h->side);
+    for (auto &st : h->more_sides)
+        if (st) (void)hipStreamDestroy(st);
     delete h->ktimer;
     delete h;
     return VK_OK;
@@ -1157,6 +1228,12 @@ int vk_get_stage(vk_handle *h, const char *name, const void **dev_ptr, vk_dtype 
     VK_REQUIRE(h && name && dev_ptr && dtype && shape && ndim, VK_EINVAL, "null argument");
     auto it = h->stages_out.find(name);
     VK_REQUIRE(it != h->stages_out.end(), VK_EINVAL, "unknown stage '%s' (or no forward has run)", name);
+    // the stages are the most recently begun forward's, in its working set; where that forward is still open on a lane's
+    // stream, a copy on the caller's stream would not be ordered behind it
+    if (h->next_ticket > h->oldest_open) {
+        const int slot = (int)((h->next_ticket - 1) % vk_handle::VK_MAX_INFLIGHT);
+        if (h->slot_stream[slot] != h->slot_caller[slot]) VK_CHECK_HIP(hipEventSynchronize(h->ev_done[slot]));
+    }
     *dev_ptr = it->second.ptr;
     *dtype = it->second.dt;
     *ndim = it->second.ndim;
@@ -1177,25 +1254,96 @@ namespace vk {
 
 // ---- the pieces of a forward shared by vk_forward_begin (detection) and vk_forward_boxes_begin (given boxes) ----
 
+// The pinned flag words and the per-ticket events, on the first forward.
+static int ensure_ticket_state(vk_handle *h) {
+    if (h->flag_host) return VK_OK;
+    for (auto &e : h->ev_done) VK_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto &e : h->ev_in) VK_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    VK_CHECK_HIP(hipHostMalloc((void **)&h->flag_host, sizeof(int32_t) * vk_handle::VK_MAX_INFLIGHT, hipHostMallocDefault));
+    return VK_OK;
+}
+
+// One working set's arena of at least `bytes`.  Growing frees the old block after hipDeviceSynchronize, which also waits
+// for a forward in flight on the other set (it keeps its own block).  soft: a failed allocation is reported as 1 with
+// the HIP error cleared, not as an error.
+static int ensure_arena(vk_handle *h, int set, size_t bytes, bool soft) {
+    vk_handle::WorkSet &ws = h->sets[set];
+    if (bytes <= ws.arena_bytes) return VK_OK;
+    if (ws.arena) {
+        VK_CHECK_HIP(hipDeviceSynchronize());
+        VK_CHECK_HIP(hipFree(ws.arena));
+        ws.arena = nullptr;
+        ws.arena_bytes = 0;
+    }
+    if (soft) {
+        if (hipMalloc((void **)&ws.arena, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            ws.arena = nullptr;
+            return 1;
+        }
+    } else {
+        VK_CHECK_HIP(hipMalloc((void **)&ws.arena, bytes));
+    }
+    ws.arena_bytes = bytes;
+    return VK_OK;
+}
+
+// Where the forward that is about to be enqueued (ticket h->next_ticket) runs: its working set (h->cur_set, with an arena
+// of arena_need bytes) and its stream (*s_out).
+// One lane (option "forward_lanes" = 1, timers on, no forward has overlapped another yet, or the second arena did not fit):
+// set 0 on the caller's stream, as a handle with one arena does.  The per-launch and per-stage timers need this: their
+// event pairs bracket launches whose durations must not overlap.
+// Two lanes: ticket t takes set t & 1 and the lane's own stream, which waits for the caller's stream as it stands now
+// (inputs ready); vk_forward_end makes the caller's stream wait for the ticket's completion event in turn.
+// Either way the stream waits for every open ticket that was enqueued on another stream and shares the set (one lane:
+// every such ticket), so a change of mode between two forwards stays ordered.  Tickets that have ended are complete.
+static int fwd_route(vk_handle *h, size_t arena_need, hipStream_t caller, hipStream_t *s_out) {
+    VK_TRY(ensure_ticket_state(h));
+    const int64_t t = h->next_ticket;
+    const int slot = (int)(t % vk_handle::VK_MAX_INFLIGHT);
+    bool laned = h->forward_lanes == 2 && !h->two_sets_failed && !h->ktimer && !h->timing;
+    if (laned && !h->two_sets && t > h->oldest_open) h->two_sets = true;
+    laned = laned && h->two_sets;
+    int set = laned ? (int)(t & 1) : 0;
+    if (set == 1 && ensure_arena(h, 1, arena_need, true) != VK_OK) {      // no room for a second set: not an error
+        h->two_sets_failed = true;
+        laned = false;
+        set = 0;
+    }
+    VK_TRY(ensure_arena(h, set, arena_need, false));
+    hipStream_t s = caller;
+    if (laned) {
+        vk_handle::Lane &ln = h->lanes[set];
+        // (both lanes at the default priority: the second one at the lowest measured the same)
+        if (!ln.main) VK_CHECK_HIP(hipStreamCreateWithFlags(&ln.main, hipStreamNonBlocking));
+        s = ln.main;
+        h->lane_forwards++;
+        VK_CHECK_HIP(hipEventRecord(h->ev_in[slot], caller));
+        VK_CHECK_HIP(hipStreamWaitEvent(s, h->ev_in[slot], 0));
+    }
+    for (int64_t u = h->oldest_open; u < t; ++u) {
+        const int us = (int)(u % vk_handle::VK_MAX_INFLIGHT);
+        if (h->slot_stream[us] == s || (laned && h->slot_set[us] != set)) continue;
+        VK_CHECK_HIP(hipStreamWaitEvent(s, h->ev_done[us], 0));
+    }
+    h->cur_set = set;
+    h->cur_caller = caller;
+    *s_out = s;
+    return VK_OK;
+}
+
 // Arena for R RoI rows per image, the stage map cleared, the caller's host arrays copied into the ticket's pinned slot
 // (consumed before _begin returns, and the host-to-device copies are truly asynchronous), the non-finite flag zeroed.
 // counts (given boxes only): host [N] -> p.prop_counts.  ig (detection only; host arrays, checked by the caller, or null):
 // its counts -> p.band_counts, its [N][max_per_image][2] bands -> p.bands.
+// `caller` is the stream the caller passed; *s_out is the stream the forward is enqueued on (fwd_route).
 static int fwd_open(vk_handle *h, int N, int H, int W, int R, int D, const int32_t *image_hw, const float *scales_yx,
-                    const int32_t *counts, const vk_ignorey *ig, hipStream_t s, Plan *out) {
+                    const int32_t *counts, const vk_ignorey *ig, hipStream_t caller, Plan *out, hipStream_t *s_out) {
     Plan need = make_plan(h, nullptr, N, H, W, D, R);
-    if (need.total > h->arena_bytes) {
-        if (h->arena) {
-            VK_CHECK_HIP(hipDeviceSynchronize());
-            VK_CHECK_HIP(hipFree(h->arena));
-            h->arena = nullptr;
-            h->arena_bytes = 0;
-        }
-        VK_CHECK_HIP(hipMalloc((void **)&h->arena, need.total));
-        h->arena_bytes = need.total;
-    }
+    VK_TRY(fwd_route(h, need.total, caller, s_out));
+    hipStream_t s = *s_out;
     Plan &p = *out;
-    p = make_plan(h, h->arena, N, H, W, D, R);
+    p = make_plan(h, h->sets[h->cur_set].arena, N, H, W, D, R);
     h->stages_out.clear();
     if (h->timing) VK_CHECK_HIP(hipEventRecord(h->ev[0], s));
 
@@ -1233,10 +1381,25 @@ static int fwd_open(vk_handle *h, int N, int H, int W, int R, int D, const int32
     return VK_OK;
 }
 
+// The handle's side streams (shared by the lanes) and the lane's fork / join events for a split into ns streams.
+static int ensure_sides(vk_handle *h, vk_handle::Lane &ln, int ns) {
+    if (!h->side) VK_CHECK_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
+    if (!ln.ev_fork) {
+        VK_CHECK_HIP(hipEventCreateWithFlags(&ln.ev_fork, hipEventDisableTiming));
+        VK_CHECK_HIP(hipEventCreateWithFlags(&ln.ev_join, hipEventDisableTiming));
+    }
+    for (int i = 0; i < ns - 2; ++i) {
+        if (!h->more_sides[i]) VK_CHECK_HIP(hipStreamCreateWithFlags(&h->more_sides[i], hipStreamNonBlocking));
+        if (!ln.more_joins[i]) VK_CHECK_HIP(hipEventCreateWithFlags(&ln.more_joins[i], hipEventDisableTiming));
+    }
+    return VK_OK;
+}
+
 // backbone (ResNet.forward frcnn.py:1076-1090): images -> res4 (stage "res4"), then the stage event ev[1]
 static int fwd_backbone(vk_handle *h, const Plan &p, const float *images_dev, hipStream_t s, const void **res4_out) {
     const vk_config &c = h->cfg;
     const int N = p.N;
+    vk_handle::Lane &ln = h->lanes[h->cur_set];
     VK_TRY(stem_impl(images_dev, N, p.H, p.W, h->stem.w, h->stem.b, c.stem_out_channels, c.caffe_maxpool, p.bufA, h->dt,
                      p.img_pad, p.stem_out, s, p.nonfinite));
     void *cur = p.bufA, *nxt = p.bufB;
@@ -1250,24 +1413,15 @@ static int fwd_backbone(vk_handle *h, const Plan &p, const float *images_dev, hi
         hipStream_t gs_[4] = {s, nullptr, nullptr, nullptr};
         hipEvent_t gj_[4] = {nullptr, nullptr, nullptr, nullptr};
         if (split) {
-            if (!h->side) {
-                VK_CHECK_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-                VK_CHECK_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-                VK_CHECK_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-            }
-            for (int i = 0; i < ns - 2; ++i)
-                if (!h->more_sides[i]) {
-                    VK_CHECK_HIP(hipStreamCreateWithFlags(&h->more_sides[i], hipStreamNonBlocking));
-                    VK_CHECK_HIP(hipEventCreateWithFlags(&h->more_joins[i], hipEventDisableTiming));
-                }
+            VK_TRY(ensure_sides(h, ln, ns));
             gs_[1] = h->side;
-            gj_[1] = h->ev_join;
+            gj_[1] = ln.ev_join;
             for (int i = 2; i < ns; ++i) {
                 gs_[i] = h->more_sides[i - 2];
-                gj_[i] = h->more_joins[i - 2];
+                gj_[i] = ln.more_joins[i - 2];
             }
-            VK_CHECK_HIP(hipEventRecord(h->ev_fork, s));
-            for (int i = 1; i < ns; ++i) VK_CHECK_HIP(hipStreamWaitEvent(gs_[i], h->ev_fork, 0));
+            VK_CHECK_HIP(hipEventRecord(ln.ev_fork, s));
+            for (int i = 1; i < ns; ++i) VK_CHECK_HIP(hipStreamWaitEvent(gs_[i], ln.ev_fork, 0));
         }
         for (auto &b : h->stages[st]) {
             int ho, wo;
@@ -1303,14 +1457,7 @@ static int fwd_backbone(vk_handle *h, const Plan &p, const float *images_dev, hi
 static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s) {
     const vk_config &c = h->cfg;
     const int N = p.N, P = p.P;
-    auto ensure_side = [&]() -> int {
-        if (!h->side) {
-            VK_CHECK_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-            VK_CHECK_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            VK_CHECK_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-        }
-        return VK_OK;
-    };
+    vk_handle::Lane &ln = h->lanes[h->cur_set];
     const size_t es5 = dtype_size(h->dt);
     for (int k0 = 0; k0 < p.K; k0 += p.chunk) {
         const int kc = std::min(p.chunk, p.K - k0);
@@ -1321,9 +1468,9 @@ static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s
         const bool split = h->head_streams == 2 && kc >= 2 && kc >= h->head_split_min_rois && h->dt == VK_F16;
         const int ka = split ? kc / 2 : kc;
         if (split) {
-            VK_TRY(ensure_side());
-            VK_CHECK_HIP(hipEventRecord(h->ev_fork, s));
-            VK_CHECK_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
+            VK_TRY(ensure_sides(h, ln, 2));
+            VK_CHECK_HIP(hipEventRecord(ln.ev_fork, s));
+            VK_CHECK_HIP(hipStreamWaitEvent(h->side, ln.ev_fork, 0));
         }
         const void *x = p.pooled;
         int hh = P, ww = P;
@@ -1353,8 +1500,8 @@ static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s
                                           p.feat + (size_t)(k0 + n0) * h->res5_c, hs));
         }
         if (split) {
-            VK_CHECK_HIP(hipEventRecord(h->ev_join, h->side));
-            VK_CHECK_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
+            VK_CHECK_HIP(hipEventRecord(ln.ev_join, h->side));
+            VK_CHECK_HIP(hipStreamWaitEvent(s, ln.ev_join, 0));
         }
         if (!p.pool_part) VK_TRY(vk_mean_pool(x, kc, hh * ww, h->res5_c, p.feat + (size_t)k0 * h->res5_c, h->dt, s));
     }
@@ -1383,11 +1530,11 @@ static int fwd_close(vk_handle *h, const int32_t *nonfinite, hipStream_t s, int6
         VK_CHECK_HIP(hipEventRecord(h->ev[5], s));
         h->ev_valid = true;
     }
-    if (!h->flag_host) {
-        VK_CHECK_HIP(hipHostMalloc((void **)&h->flag_host, sizeof(int32_t) * vk_handle::VK_MAX_INFLIGHT, hipHostMallocDefault));
-        for (auto &e : h->ev_done) VK_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    VK_TRY(ensure_ticket_state(h));
     const int slot = (int)(h->next_ticket % vk_handle::VK_MAX_INFLIGHT);
+    h->slot_stream[slot] = s;
+    h->slot_caller[slot] = h->cur_caller;
+    h->slot_set[slot] = nonfinite ? h->cur_set : -1;
     if (nonfinite)
         VK_CHECK_HIP(hipMemcpyAsync(&h->flag_host[slot], nonfinite, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     else
@@ -1442,6 +1589,7 @@ static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp
             VK_CHECK_HIP(hipMemsetAsync(b, 0, (size_t)cp * sizeof(float), s));
             VK_CHECK_HIP(hipMemcpyAsync(w, h->bbox_w, (size_t)nrow * row, hipMemcpyDeviceToDevice, s));
             VK_CHECK_HIP(hipMemcpyAsync(b, h->bbox_b, (size_t)nrow * sizeof(float), hipMemcpyDeviceToDevice, s));
+            VK_CHECK_HIP(hipStreamSynchronize(s));      // once per handle: the next forward may read them from another stream
             h->bbox_lin_w = w;
             h->bbox_lin_b = (const float *)b;
         }
@@ -1455,18 +1603,19 @@ static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp
     cv.take((size_t)K * sizeof(unsigned long long));
     const size_t o_conf = cv.off;
     cv.take((size_t)K * sizeof(float));
-    if (cv.off > h->pc_arena_bytes) {
-        if (h->pc_arena) {
+    vk_handle::WorkSet &ws = h->sets[h->cur_set];
+    if (cv.off > ws.pc_arena_bytes) {
+        if (ws.pc_arena) {
             VK_CHECK_HIP(hipDeviceSynchronize());
-            VK_CHECK_HIP(hipFree(h->pc_arena));
-            h->pc_arena = nullptr;
-            h->pc_arena_bytes = 0;
+            VK_CHECK_HIP(hipFree(ws.pc_arena));
+            ws.pc_arena = nullptr;
+            ws.pc_arena_bytes = 0;
         }
-        VK_CHECK_HIP(hipMalloc((void **)&h->pc_arena, cv.off));
-        h->pc_arena_bytes = cv.off;
+        VK_CHECK_HIP(hipMalloc((void **)&ws.pc_arena, cv.off));
+        ws.pc_arena_bytes = cv.off;
     }
-    float *scores = (float *)(h->pc_arena + o_scores), *deltas = (float *)(h->pc_arena + o_deltas);
-    float *max_conf = (float *)(h->pc_arena + o_conf);
+    float *scores = (float *)(ws.pc_arena + o_scores), *deltas = (float *)(ws.pc_arena + o_deltas);
+    float *max_conf = (float *)(ws.pc_arena + o_conf);
 
     VK_TRY(launch_class_probs(p.cls_logits, ld_cls, K, C + 1, scores, ld_cls, s));
     ConvArgs g;
@@ -1508,7 +1657,7 @@ static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp
     a.score_thresh = sp->score_thresh;
     a.mind = sp->roi.min_detections;
     a.maxd = sp->roi.max_detections;
-    a.best = (unsigned long long *)(h->pc_arena + o_best);
+    a.best = (unsigned long long *)(ws.pc_arena + o_best);
     a.max_conf = max_conf;
     a.out = *out;
     a.keep_ids = p.keep_ids;
@@ -1576,14 +1725,14 @@ static int forward_detect(vk_handle *h, const float *images_dev, int N, int H, i
         VK_REQUIRE(image_hw[2 * n] >= 1 && image_hw[2 * n + 1] >= 1, VK_EINVAL, "forward: image_shapes[%d]=(%d,%d) must be positive",
                    n, image_hw[2 * n], image_hw[2 * n + 1]);
     VK_CHECK_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = nullptr;            // the forward's stream: the caller's, or the ticket's lane (fwd_route)
     const vk_config &c = h->cfg;
     const int D = rp->max_detections;
     TimerScope timer_scope(h->ktimer);
     const bool tm = h->timing;
 
     Plan p;
-    VK_TRY(fwd_open(h, N, H, W, c.post_nms_topk, D, image_hw, scales_yx, nullptr, ig, s, &p));
+    VK_TRY(fwd_open(h, N, H, W, c.post_nms_topk, D, image_hw, scales_yx, nullptr, ig, (hipStream_t)stream, &p, &s));
     const void *res4 = nullptr;
     VK_TRY(fwd_backbone(h, p, images_dev, s, &res4));
 
@@ -1681,9 +1830,10 @@ int vk_forward_boxes_begin(vk_handle *h, const float *images_dev, int N, int H, 
     VK_REQUIRE(h->finalized, VK_EINVAL, "forward_boxes: vk_finalize has not been called");
     VK_CHECK_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    if (B == 0) {       // every image is empty: a zero-detection block, no kernel, no stage events
+    if (B == 0) {       // every image is empty: a zero-detection block, no kernel, no stage events; on the caller's stream, no working set
         h->stages_out.clear();
         h->ev_valid = false;
+        h->cur_caller = s;
         VK_CHECK_HIP(hipMemsetAsync(out->preds_per_image, 0, sizeof(int64_t) * (size_t)N, s));
         return fwd_close(h, nullptr, s, ticket);
     }
@@ -1691,7 +1841,7 @@ int vk_forward_boxes_begin(vk_handle *h, const float *images_dev, int N, int H, 
     const bool tm = h->timing;
 
     Plan p;
-    VK_TRY(fwd_open(h, N, H, W, B, B, image_hw, scales_yx, counts, nullptr, s, &p));
+    VK_TRY(fwd_open(h, N, H, W, B, B, image_hw, scales_yx, counts, nullptr, (hipStream_t)stream, &p, &s));
     const void *res4 = nullptr;
     VK_TRY(fwd_backbone(h, p, images_dev, s, &res4));
     if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[2], s));          // no RPN head
@@ -1719,6 +1869,8 @@ int vk_forward_end(vk_handle *h, int64_t ticket) {
     const int slot = (int)(ticket % vk_handle::VK_MAX_INFLIGHT);
     h->oldest_open++;
     VK_CHECK_HIP(hipSetDevice(h->device));
+    // a forward that ran on a lane's stream: whatever the caller enqueues next on its own stream sees the outputs
+    if (h->slot_stream[slot] != h->slot_caller[slot]) VK_CHECK_HIP(hipStreamWaitEvent(h->slot_caller[slot], h->ev_done[slot], 0));
     VK_CHECK_HIP(hipEventSynchronize(h->ev_done[slot]));
     if (h->ktimer) h->ktimer->collect();
     VK_REQUIRE(h->flag_host[slot] == 0, VK_ENONFINITE, "Box tensor contains infinite or NaN!");

@@ -412,6 +412,12 @@ class FRCNN:
     def set_option(self, key, value):
         L.call("vk_set_option", self._h, key.encode(), int(value))
 
+    def get_option(self, key):
+        """An option's current value; also the read-only "working_sets" and "lane_forwards" (vk_get_option)."""
+        v = C.c_int()
+        L.call("vk_get_option", self._h, key.encode(), C.byref(v))
+        return v.value
+
     def enable_stage_timing(self, on=True):
         L.call("vk_enable_stage_timing", self._h, int(on))
 
@@ -506,7 +512,10 @@ class FRCNN:
         roi_outputs.selection = "per_class", or vk_forward_boxes_begin with `proposals`, see forward()); `.wait(**kwargs)`
         on the returned handle finishes it (vk_forward_end) and formats the outputs like forward().  Up to four may be in
         flight, detection and given-box forwards mixed; they must be waited for in order, on the same stream.  The caller
-        must not modify `images` (or the proposals) before wait() returns."""
+        must not modify `images` (or the proposals) before wait() returns.  Forwards in flight together run beside each
+        other on the device (option "forward_lanes", 2 by default: two working sets and two streams of the model's own;
+        `set_option("forward_lanes", 1)` keeps them one after the other on the current stream); the results are the same
+        bits, and wait() orders the current stream behind the forward."""
         images, hw, sc, given, ig = self._prepare(images, image_shapes, proposals, scales_yx, ignorey)
         N, _, H, W = images.shape
         F = self.config.RESNETS.RES2_OUT_CHANNELS * 8

@@ -147,6 +147,11 @@ class ExtractionPipeline:
         if self.world > 1:
             gbuf = [torch.empty(self.world * nbytes, dtype=torch.uint8, device=dev) for _ in range(self.depth)]
         on_gpu = dev.type == "cuda"
+        # This loop keeps a copy and an upload stream beside the compute stream.  With the model's two forward lanes and
+        # their side stream a rank would hold six streams on four hardware queues, and streams that share a queue
+        # serialise (DESIGN.md sections 6b, 7).  That has not been measured, so the extraction loop keeps one lane.
+        if on_gpu and hasattr(self.model, "set_option"):
+            self.model.set_option("forward_lanes", 1)
         copy_stream = torch.cuda.Stream(device=dev) if on_gpu else None
         upload_stream = torch.cuda.Stream(device=dev) if on_gpu else None
 
