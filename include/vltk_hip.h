@@ -264,9 +264,41 @@ int vk_given_box_outputs(const float *obj_prob, const int32_t *obj_cls, const fl
                          const float *prop_boxes, const int32_t *counts_dev, const float *scales_yx_dev, const float *feat,
                          int F, int N, int B, const vk_outputs *out_dev, void *stream);
 
+/* Grid features (this project's mode, no counterpart in the reference): the backbone, then the Res5
+ * stage ONCE over the whole res4 map (roi_heads.res5 run convolutionally, frcnn.py:1344-1355) -> M [N,Hm,Wm,F] (Hm x Wm =
+ * res4's Hf x Wf, halved by block 0's stride under RES5HALVE; S = 16, or 32 then), average-pooled to a Gh x Gw grid over
+ * each image's content, and the box predictor on every cell's row.  No RPN head, no proposals, no RoIPool, no NMS.
+ * Per image n with (h, w) = image_hw[n], in integers: fh = min(Hm, max(1, (h + S - 1) / S)), fw likewise; cell (i, j) is
+ * row i * Gw + j and covers map rows floor(i * fh / Gh) .. ceil((i + 1) * fh / Gh) (exclusive) and columns likewise from
+ * fw, Gw (adaptive_avg_pool2d's bins; with fh < Gh neighbouring cells share a pixel).
+ *   roi_features[n, row, c] = (float)(sum of (double)M[n, y, x, c] / (double)count), the sum taken in y-outer, x-inner order;
+ *   boxes[n, row]           = (xs * S, ys * S, min(xe * S, w), min(ye * S, h)), times the scales as frcnn.py:1280-1283;
+ *   obj_ids / obj_probs / attr_ids / attr_probs: the predictor on the row exactly as vk_forward_boxes_begin produces them;
+ *   preds_per_image[n] = Gh * Gw.  out_dev: vk_outputs of capacity Gh * Gw per image.  1 <= Gh, Gw and Gh * Gw <= 1024.
+ * The ticket belongs to vk_forward_begin's ring and is finished with vk_forward_end; grid, detection and given-box
+ * forwards may be in flight together, in order.  The working set's Res5 buffers are sized for the whole map; a plan that
+ * could not hold it is refused with VK_EINVAL before anything is enqueued.
+ * Stages of the last forward: "res4", "grid_res5_0" / "grid_res5_1" (the first two Res5 blocks' outputs, [N,Hm,Wm,F]),
+ * "grid_map" [N,Hm,Wm,F] (the third's; all in the handle's dtype), "feature_pooled" [N*G,F], "proposal_boxes" [N,G,4]
+ * (the cell boxes in network pixels, BEFORE the scales), "obj_logits", "attr_logits". */
+int vk_forward_grid_begin(vk_handle *h, const float *images_dev, int N, int H, int W,
+                          const int32_t *image_hw, const float *scales_yx, int Gh, int Gw,
+                          const vk_outputs *out_dev, void *stream, int64_t *ticket);
+
+/* The pooling stage of vk_forward_grid_begin on its own, independent of a handle.  Every array is a device array.
+ * map [N,Hm,Wm,C] NHWC in dt (VK_F16 or VK_F32); image_hw_dev [N,2] i32; scales_yx_dev [N,2] f32 or NULL (boxes in
+ * network pixels); S: input pixels per map pixel; feat_out [N*Gh*Gw, ldf] f32 (ldf >= C); boxes_out [N,Gh*Gw,4] f32.
+ * One workgroup per (cell, image); a lane owns 8 consecutive channels (16-byte loads) when C is a multiple of 8 and the
+ * map is 16-byte aligned, single channels otherwise; fp64 sums in a fixed order, no atomics: a host restatement of the
+ * rule above is bit-equal.  image_hw values below 1 or beyond the map are clamped into it (fh, fw in 1..Hm, 1..Wm). */
+int vk_grid_pool(const void *map, int N, int Hm, int Wm, int C, vk_dtype dt, const int32_t *image_hw_dev,
+                 const float *scales_yx_dev, int S, int Gh, int Gw, float *feat_out, int ldf, float *boxes_out,
+                 void *stream);
+
 /* Intermediate tensors of the last forward, for stage-level parity tests.
  * name in {"res4","rpn_out","proposal_boxes","proposal_logits",
- * "proposal_counts","pooled","feature_pooled","obj_logits","attr_logits","chosen_deltas","keep_ids"}
+ * "proposal_counts","pooled","feature_pooled","obj_logits","attr_logits","chosen_deltas","keep_ids"},
+ * after a grid forward (vk_forward_grid_begin) {"grid_res5_0","grid_res5_1","grid_map"},
  * and, after a per-class forward (vk_forward_begin_select), {"obj_scores","box_deltas","max_conf","attr_prob"}
  * ("attr_prob" [K] f32: each row's attribute probability, what attr_probs gathers);
  * "rpn_out" is the fused RPN head output [N,Hf,Wf,ld]: columns [0,A) objectness, [A,5A) deltas.

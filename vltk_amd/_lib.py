@@ -102,6 +102,8 @@ SIGNATURES = {
     "vk_forward_begin_select": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(vk_select_params), C.POINTER(vk_outputs), _P,
                                      C.POINTER(C.c_int64), C.POINTER(vk_ignorey)]),
     "vk_forward_boxes_begin": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, C.POINTER(vk_outputs), _P, C.POINTER(C.c_int64)]),
+    "vk_forward_grid_begin": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, C.POINTER(vk_outputs), _P, C.POINTER(C.c_int64)]),
+    "vk_grid_pool": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
     "vk_forward_end": (_I, [_P, C.c_int64]),
     "vk_given_boxes_ingest": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _F, _I, _P, _P]),
     "vk_given_box_outputs": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(vk_outputs), _P]),

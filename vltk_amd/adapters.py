@@ -39,6 +39,7 @@ from .frcnn import MAX_IGNOREY
 IMG, SIZE, SCALE, RAWSIZE, FILEPATH, IMGID, SPLIT = "image", "size", "wh_scale", "rawsize", "filepath", "imgid", "split"
 FEATURES, BOX, BOXES = "features", "box", "boxes"
 IGNOREY = "ignorey"
+GRID = "grid"
 SPLITALIASES = ("test", "dev", "eval", "val", "validation", "evaluation", "train")       # vltk/vars.py:63-71
 IMGFILES = ("jpeg", "jpg", "png")                                                         # abc/adapter.py:25
 
@@ -233,11 +234,12 @@ class FRCNN:
     def forward(model, entry):
         """entry["boxes"] (vltk's vars.boxes, [K, 4] in original-image pixels), when present: region features for exactly
         those boxes (FRCNN.forward(proposals=...)) instead of detection.  entry["ignorey"] ([J, 2] rows (y0, y1) in
-        original-image pixels), when present: bands whose proposals are removed or trimmed (FRCNN.forward(ignorey=...))."""
+        original-image pixels), when present: bands whose proposals are removed or trimmed (FRCNN.forward(ignorey=...)).
+        entry["grid"] = (Gh, Gw), when present: grid features (FRCNN.forward(grid=...)), Gh * Gw rows."""
         size, scale_wh, image = entry[SIZE], entry[SCALE], entry[IMG]
         model_out = model(images=image.unsqueeze(0), image_shapes=torch.as_tensor(size).unsqueeze(0),
                           padding="max_detections", pad_value=0.0, location="cpu", **FRCNN._given(model, [entry]),
-                          **FRCNN._bands([entry]))
+                          **FRCNN._bands([entry]), **FRCNN._grid(model, [entry]))
         return FRCNN._rows(model_out, [scale_wh], 0)
 
     @staticmethod
@@ -246,7 +248,7 @@ class FRCNN:
         images = torch.stack([e[IMG] for e in entries])
         sizes = torch.stack([torch.as_tensor(e[SIZE]) for e in entries])
         model_out = model(images=images, image_shapes=sizes, padding="max_detections", pad_value=0.0, location="cpu",
-                          **FRCNN._given(model, entries), **FRCNN._bands(entries))
+                          **FRCNN._given(model, entries), **FRCNN._bands(entries), **FRCNN._grid(model, entries))
         out = None
         for i, e in enumerate(entries):
             row = FRCNN._rows(model_out, [e[SCALE]], i)
@@ -272,6 +274,17 @@ class FRCNN:
             b = torch.as_tensor(np.asarray(e[BOXES], dtype=np.float32)).reshape(-1, 4).clone()
             props.append(rescale_box(b, torch.as_tensor(e[SCALE], dtype=torch.float32)))
         return {"proposals": props, "max_detections": int(model.roi_outputs.max_detections)}
+
+    @staticmethod
+    def _grid(model, entries):
+        """`grid=` for entries that carry one (entry["grid"] = (Gh, Gw); all entries of a batch the same), the rows padded to
+        model.roi_outputs.max_detections like given boxes.  {} when no entry has one."""
+        grids = {None if e.get(GRID) is None else tuple(e[GRID]) for e in entries}
+        if grids == {None}:
+            return {}
+        if len(grids) != 1:
+            raise ValueError("entries of one batch must all carry the same grid")
+        return {"grid": grids.pop(), "max_detections": int(model.roi_outputs.max_detections)}
 
     @staticmethod
     def _bands(entries):
@@ -356,6 +369,9 @@ class FRCNN:
         holding the given boxes clipped to the image and rounded, `features` zero-padded to the schema's width.
         `ignorey={imgid: [J, 2] rows (y0, y1) in original-image pixels}`: bands whose RPN proposals are removed or trimmed
         (FRCNN.forward(ignorey=...)); an image without an entry has none, J <= 64 (ValueError before anything is written).
+        `grid=(Gh, Gw)`: grid features (FRCNN.forward(grid=...)) instead of detection: Gh * Gw rows per image, `box` holding
+        the cells' extents; Gh * Gw may not exceed the schema's max_detections and `grid` excludes `boxes` and `ignorey`
+        (ValueError before anything is written).
         With torch.distributed initialised the images of every split shard across the ranks (parallel.py); the dict is
         returned on rank 0 (empty elsewhere).  `model.roi_outputs.{max,min}_detections` are set to the schema's width for
         the call and restored afterwards.  The reference-processor mode (`processor="reference"` / a `processor_config`)
@@ -375,6 +391,14 @@ class FRCNN:
         if given is not None:
             given = {str(k): np.asarray(v, dtype=np.float32).reshape(-1, 4) for k, v in given.items()}
         bands = kwargs.pop("ignorey", None)
+        grid = kwargs.pop("grid", None)
+        if grid is not None:
+            from .frcnn import check_grid
+            if given is not None:
+                raise ValueError("grid= pools fixed cells: it cannot be combined with boxes=")
+            if bands is not None:
+                raise ValueError("ignorey removes / trims RPN proposals: there are none with grid=")
+            grid = check_grid(grid)
         if bands is not None:
             if given is not None:
                 raise ValueError("ignorey removes / trims RPN proposals: there are none with boxes=")
@@ -399,15 +423,17 @@ class FRCNN:
             if D != int(model.roi_outputs.max_detections):                  # rows are padded to the schema's width
                 model.roi_outputs.max_detections = D
                 model.roi_outputs.min_detections = min(int(model.roi_outputs.min_detections), D)
+            if grid is not None and grid[0] * grid[1] > D:
+                raise ValueError(f"grid={grid}: {grid[0] * grid[1]} cells, more than max_detections={D}; nothing was written")
             splitdict = cls._extract_splits(model, model_config, searchdirs, valid_splits, savedir, dataset_name, subset_ids,
-                                            processor, processor_config, batch_size, D, F, kwargs, given, bands)
+                                            processor, processor_config, batch_size, D, F, kwargs, given, bands, grid)
         finally:
             model.roi_outputs.max_detections, model.roi_outputs.min_detections = saved_limits
         return splitdict
 
     @classmethod
     def _extract_splits(cls, model, model_config, searchdirs, valid_splits, savedir, dataset_name, subset_ids, processor,
-                        processor_config, batch_size, D, F, kwargs, given=None, bands=None):
+                        processor_config, batch_size, D, F, kwargs, given=None, bands=None, grid=None):
         from .extraction import ExtractionWriter, load_extraction
         # files -> per split (id, path), in the reference's terms: split = parent directory, id = stem up to the first dot
         print(f"extracting from {searchdirs}")
@@ -462,7 +488,7 @@ class FRCNN:
             savefile = os.path.join(savedir, f"{split}.arrow")
             if gpu_path:
                 cls._extract_split_gpu(model, model_config, items, savefile, dataset_name, pargs, cfgd, batch_size, F,
-                                       rank, world, given, bands)
+                                       rank, world, given, bands, grid)
             else:
                 fkw = _collect_args(cls.forward, kwargs)
                 fkw.pop("model", None), fkw.pop("entry", None)
@@ -477,6 +503,8 @@ class FRCNN:
                             entry[BOXES] = given[img_id]
                         if bands is not None and img_id in bands:
                             entry[IGNOREY] = bands[img_id]
+                        if grid is not None:
+                            entry[GRID] = grid
                         out = cls.forward(model=model, entry=entry, **fkw)
                         assert isinstance(out, dict), "model outputs should be in dict format"
                         w.write_batch([img_id], np.asarray(out["object_ids"], np.float32), np.asarray(out["attr_ids"], np.float32),
@@ -490,13 +518,13 @@ class FRCNN:
 
     @classmethod
     def _extract_split_gpu(cls, model, model_config, items, savefile, dataset_name, pargs, cfgd, batch_size, F, rank, world,
-                           given=None, bands=None):
+                           given=None, bands=None, grid=None):
         from .parallel import shard_indices
         from .pipeline import ExtractionPipeline
         from .preprocess import Preprocess
         pipe = ExtractionPipeline(model, Preprocess(model_config, device=model.device), savefile, batch_size=batch_size,
                                   visual_dim=F, dataset=dataset_name, processor_args=pargs, model_config=cfgd, boxes=given,
-                                  ignorey=bands)
+                                  ignorey=bands, grid=grid)
         pipe.set_global_ids([i for i, _ in items])
         lo, hi = shard_indices(len(items), rank, world)
         mine = items[lo:hi]

@@ -442,6 +442,7 @@ struct Plan {
     void *rpn_ws;
     size_t rpn_ws_bytes;
     void *pooled, *h_t1, *h_t2, *h_a, *h_b, *h_sc;
+    size_t head_rows;        // pixels that h_t1 .. h_sc hold each (a Res5 chunk, or the whole res4 map of a grid forward)
     float *pool_part;        // per-tile column sums of the last Res5 conv3 (fused spatial mean), or nullptr
     float *feat;
     void *featT, *concat, *attr_hid;
@@ -456,8 +457,10 @@ static void conv_out_hw(int H, int W, int k, int s, int p, int d, int *Ho, int *
     *Wo = (W + 2 * p - (d * (k - 1) + 1)) / s + 1;
 }
 
-// R: RoI rows per image (POST_NMS_TOPK_TEST for detection, B for given boxes); D: the output width of keep_ids
-static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D, int R) {
+// R: RoI rows per image (POST_NMS_TOPK_TEST for detection, B for given boxes, Gh * Gw for a grid); D: the output width of
+// keep_ids.  whole_map (grid forward): Res5 runs over the res4 map itself, so the head buffers hold at least N * Hf * Wf
+// pixels -- with R = Gh * Gw alone a 1 x 1 grid would get 196 rows per image for a map of thousands.
+static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D, int R, bool whole_map = false) {
     Plan p;
     memset(&p, 0, sizeof(p));
     const vk_config &c = h->cfg;
@@ -511,9 +514,11 @@ static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D, int 
     p.nonfinite = (int32_t *)cv.take(sizeof(int32_t));
     p.rpn_ws_bytes = vk_rpn_workspace_bytes(N, p.Hf * p.Wf * h->A, c.pre_nms_topk);
     p.rpn_ws = cv.take(p.rpn_ws_bytes);
-    const size_t rows = (size_t)p.chunk * p.P * p.P;
+    const size_t roi_rows = (size_t)p.chunk * p.P * p.P;
+    const size_t rows = whole_map ? std::max(roi_rows, Mf) : roi_rows;
     const int mid5 = c.num_groups * c.width_per_group * 8;
-    p.pooled = cv.take(rows * h->res4_c * es);
+    p.head_rows = rows;
+    p.pooled = cv.take(roi_rows * h->res4_c * es);
     p.h_t1 = cv.take(rows * mid5 * es);
     p.h_t2 = cv.take(rows * mid5 * es);
     p.h_a = cv.take(rows * h->res5_c * es);
@@ -521,7 +526,7 @@ static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D, int 
     p.h_sc = cv.take(rows * h->res5_c * es);
     p.pool_part = nullptr;
     // + one tile: two half-chunks on two streams keep separate partials and each rounds its tile count up
-    if (fused_mean_ok(h, p.P, rows)) p.pool_part = (float *)cv.take(conv_duo_pool_part_bytes((long)rows + 128, h->res5_c));
+    if (fused_mean_ok(h, p.P, roi_rows)) p.pool_part = (float *)cv.take(conv_duo_pool_part_bytes((long)roi_rows + 128, h->res5_c));
     p.feat = (float *)cv.take((size_t)p.K * h->res5_c * sizeof(float));
     const size_t pes = dtype_size(h->pdt);
     p.featT = cv.take((size_t)p.K * h->res5_c * pes);
@@ -1338,12 +1343,13 @@ static int fwd_route(vk_handle *h, size_t arena_need, hipStream_t caller, hipStr
 // its counts -> p.band_counts, its [N][max_per_image][2] bands -> p.bands.
 // `caller` is the stream the caller passed; *s_out is the stream the forward is enqueued on (fwd_route).
 static int fwd_open(vk_handle *h, int N, int H, int W, int R, int D, const int32_t *image_hw, const float *scales_yx,
-                    const int32_t *counts, const vk_ignorey *ig, hipStream_t caller, Plan *out, hipStream_t *s_out) {
-    Plan need = make_plan(h, nullptr, N, H, W, D, R);
+                    const int32_t *counts, const vk_ignorey *ig, hipStream_t caller, Plan *out, hipStream_t *s_out,
+                    bool whole_map = false) {
+    Plan need = make_plan(h, nullptr, N, H, W, D, R, whole_map);
     VK_TRY(fwd_route(h, need.total, caller, s_out));
     hipStream_t s = *s_out;
     Plan &p = *out;
-    p = make_plan(h, h->sets[h->cur_set].arena, N, H, W, D, R);
+    p = make_plan(h, h->sets[h->cur_set].arena, N, H, W, D, R, whole_map);
     h->stages_out.clear();
     if (h->timing) VK_CHECK_HIP(hipEventRecord(h->ev[0], s));
 
@@ -1453,9 +1459,9 @@ static int fwd_backbone(vk_handle *h, const Plan &p, const float *images_dev, hi
 
 // RoI pool + Res5 head + spatial mean over the p.K rows of p.rois (Res5ROIHeads.forward frcnn.py:1391-1403, chunked over
 // RoIs), then the class / attribute branches of the box predictor (FastRCNNOutputLayers.forward frcnn.py:1726-1740; the
-// box regression is the caller's).  Stages "pooled" (one chunk only), "feature_pooled", "obj_logits", "attr_logits".
+// box regression is the caller's: fwd_predictor).  Stages "pooled" (one chunk only), "feature_pooled", "obj_logits", "attr_logits".
+static int fwd_predictor(vk_handle *h, const Plan &p, hipStream_t s);
 static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s) {
-    const vk_config &c = h->cfg;
     const int N = p.N, P = p.P;
     vk_handle::Lane &ln = h->lanes[h->cur_set];
     const size_t es5 = dtype_size(h->dt);
@@ -1506,6 +1512,14 @@ static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s
         if (!p.pool_part) VK_TRY(vk_mean_pool(x, kc, hh * ww, h->res5_c, p.feat + (size_t)k0 * h->res5_c, h->dt, s));
     }
     if (p.chunk >= p.K) set_stage(h, "pooled", p.pooled, h->dt, {p.K, P, P, h->res4_c});
+    return fwd_predictor(h, p, s);
+}
+
+// The class / attribute branches of the box predictor on the p.K feature rows of p.feat (FastRCNNOutputLayers.forward
+// frcnn.py:1726-1740): the one copy, behind the RoI head (fwd_head) and behind the grid pooling (vk_forward_grid_begin).
+// Stages "feature_pooled", "obj_logits", "attr_logits".
+static int fwd_predictor(vk_handle *h, const Plan &p, hipStream_t s) {
+    const vk_config &c = h->cfg;
     set_stage(h, "feature_pooled", p.feat, VK_F32, {p.K, h->res5_c});
 
     const int C = c.num_classes, F = h->res5_c, E = h->emb_dim, AT = c.num_attrs;
@@ -1859,6 +1873,76 @@ int vk_forward_boxes_begin(vk_handle *h, const float *images_dev, int N, int H, 
     // ---- outputs: every box in input order, no regression, no NMS ----
     VK_TRY(launch_given_box_outputs(p.obj_prob, p.obj_cls, p.attr_prob, p.attr_cls, p.prop_boxes, p.prop_counts,
                                     scales_yx ? p.scales : nullptr, p.feat, h->res5_c, N, B, *out, s));
+    return fwd_close(h, p.nonfinite, s, ticket);
+}
+
+int vk_forward_grid_begin(vk_handle *h, const float *images_dev, int N, int H, int W, const int32_t *image_hw,
+                          const float *scales_yx, int Gh, int Gw, const vk_outputs *out, void *stream, int64_t *ticket) {
+    // the arguments first, then the handle: every check here runs before anything touches the device
+    VK_REQUIRE(images_dev && image_hw && out && ticket, VK_EINVAL, "forward_grid: null argument");
+    VK_REQUIRE(N >= 1 && H >= 32 && W >= 32, VK_EINVAL, "forward_grid: bad input size N=%d H=%d W=%d", N, H, W);
+    VK_REQUIRE(Gh >= 1 && Gw >= 1 && (long)Gh * Gw <= 1024, VK_EINVAL, "forward_grid: grid (%d, %d) must have 1..1024 cells", Gh, Gw);
+    VK_REQUIRE(out->obj_ids && out->obj_probs && out->attr_ids && out->attr_probs && out->boxes && out->preds_per_image &&
+                   out->roi_features,
+               VK_EINVAL, "forward_grid: null output array");
+    VK_REQUIRE(((uintptr_t)out->roi_features & 15) == 0, VK_EINVAL, "forward_grid: roi_features must be 16-byte aligned");
+    for (int n = 0; n < N; ++n)
+        VK_REQUIRE(image_hw[2 * n] >= 1 && image_hw[2 * n + 1] >= 1, VK_EINVAL,
+                   "forward_grid: image_shapes[%d]=(%d,%d) must be positive", n, image_hw[2 * n], image_hw[2 * n + 1]);
+    VK_REQUIRE(h, VK_EINVAL, "forward_grid: null handle");
+    VK_REQUIRE(h->next_ticket - h->oldest_open < vk_handle::VK_MAX_INFLIGHT, VK_EINVAL,
+               "forward_grid_begin: %d forwards are already in flight; end the oldest first", vk_handle::VK_MAX_INFLIGHT);
+    VK_REQUIRE(h->finalized, VK_EINVAL, "forward_grid: vk_finalize has not been called");
+    const int G = Gh * Gw;
+    // the working set this forward will get must hold the whole map in each head buffer: refuse before anything is enqueued
+    const Plan need = make_plan(h, nullptr, N, H, W, G, G, true);
+    const size_t map_rows = (size_t)N * need.Hf * need.Wf;
+    VK_REQUIRE(need.head_rows >= map_rows, VK_EINVAL, "forward_grid: the working set holds %zu Res5 rows, the %d x %d x %d map needs %zu",
+               need.head_rows, N, need.Hf, need.Wf, map_rows);
+    VK_CHECK_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    TimerScope timer_scope(h->ktimer);
+    const bool tm = h->timing;
+
+    Plan p;
+    std::vector<int32_t> counts((size_t)N, G);          // every cell is a row: fwd_open copies them into the ticket's slot
+    VK_TRY(fwd_open(h, N, H, W, G, G, image_hw, scales_yx, counts.data(), nullptr, (hipStream_t)stream, &p, &s, true));
+    VK_REQUIRE(p.head_rows >= map_rows, VK_EINVAL, "internal: grid plan of %zu rows for a map of %zu", p.head_rows, map_rows);
+    const void *res4 = nullptr;
+    VK_TRY(fwd_backbone(h, p, images_dev, s, &res4));
+    if (tm) {                                            // no RPN head, no proposals
+        VK_CHECK_HIP(hipEventRecord(h->ev[2], s));
+        VK_CHECK_HIP(hipEventRecord(h->ev[3], s));
+    }
+
+    // ---- Res5 over the whole map (roi_heads.res5 on res4, frcnn.py:1344-1355): one launch per layer, no chunks ----
+    // Each block's output stays in a buffer of its own (stages "grid_res5_<b>", the last one "grid_map"): h_sc is free from
+    // block 1 on, because only block 0 has a projection shortcut.
+    const void *x = res4;
+    void *outs[3] = {p.h_a, p.h_b, p.h_sc};
+    int hh = p.Hf, ww = p.Wf;
+    for (size_t bi = 0; bi < h->res5.size(); ++bi) {
+        int ho, wo;
+        void *y = outs[bi % 3];
+        VK_TRY(run_block(h, h->res5[bi], x, N, hh, ww, p.h_t1, p.h_t2, p.h_sc, y, s, &ho, &wo));
+        hh = ho;
+        ww = wo;
+        x = y;
+        if (bi + 1 < h->res5.size() && bi < 2) set_stage(h, bi == 0 ? "grid_res5_0" : "grid_res5_1", y, h->dt, {N, hh, ww, h->res5_c});
+    }
+    VK_REQUIRE((size_t)N * hh * ww <= map_rows, VK_EINVAL, "internal: Res5 map %dx%d is larger than res4's %dx%d", hh, ww, p.Hf, p.Wf);
+    set_stage(h, "grid_map", x, h->dt, {N, hh, ww, h->res5_c});
+
+    // ---- the cells: fp64 average per cell and channel, the cell boxes in network pixels (scaled by the output kernel) ----
+    const int S = h->cfg.res5_halve ? 32 : 16;          // res4's stride, doubled by block 0's under RES5HALVE
+    VK_TRY(vk_grid_pool(x, N, hh, ww, h->res5_c, h->dt, p.image_hw, nullptr, S, Gh, Gw, p.feat, h->res5_c, p.prop_boxes, s));
+    set_stage(h, "proposal_boxes", p.prop_boxes, VK_F32, {N, G, 4});
+    VK_TRY(fwd_predictor(h, p, s));
+    if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[4], s));
+
+    // ---- outputs: every cell in row-major order, counts all G ----
+    VK_TRY(launch_given_box_outputs(p.obj_prob, p.obj_cls, p.attr_prob, p.attr_cls, p.prop_boxes, p.prop_counts,
+                                    scales_yx ? p.scales : nullptr, p.feat, h->res5_c, N, G, *out, s));
     return fwd_close(h, p.nonfinite, s, ticket);
 }
 

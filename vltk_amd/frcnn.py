@@ -240,6 +240,24 @@ def check_given_width(width, max_detections):
                          "given boxes are never truncated")
 
 
+MAX_GRID_CELLS = 1024  # cells per image of grid=
+
+
+def check_grid(grid):
+    """grid= -> (Gh, Gw) as ints: two integers >= 1 with Gh * Gw <= 1024; anything else is a ValueError."""
+    try:
+        gh, gw = grid
+    except (TypeError, ValueError):
+        raise ValueError(f"grid must be (Gh, Gw), got {grid!r}") from None
+    for v in (gh, gw):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"grid must be two integers, got {grid!r}")
+    gh, gw = int(gh), int(gw)
+    if gh < 1 or gw < 1 or gh * gw > MAX_GRID_CELLS:
+        raise ValueError(f"grid=({gh}, {gw}) must have Gh, Gw >= 1 and at most {MAX_GRID_CELLS} cells")
+    return gh, gw
+
+
 class _Ticket:
     """State of one forward in flight; the model keeps these in issue order (`FRCNN._open`)."""
 
@@ -300,6 +318,7 @@ class PendingForward:
 
 class FRCNN:
     given_boxes = True                   # forward(proposals=...): region features for caller-supplied boxes
+    grid_features = True                 # forward(grid=(Gh, Gw)): Res5 over the whole map, pooled to a grid of cells
 
     def __new__(cls, cfg=None, *a, **k):
         # several RPN input levels = the FPN detector (frcnn_fpn.py, a build extension); one = the reference's C4 model
@@ -457,7 +476,7 @@ class FRCNN:
     def __call__(self, *a, **k):
         return self.forward(*a, **k)
 
-    def forward(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None, **kwargs):
+    def forward(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None, grid=None, **kwargs):
         """kwargs (v1.0.0 semantics): max_detections, return_tensors {"np","pt",None},
         padding {None,"max_detections","max_batch"}, pad_value, location {"cuda","cpu"}.
 
@@ -476,13 +495,33 @@ class FRCNN:
         divided by scales_yx[n][1]; at most 64 per image.  Applied only with scales_yx, as in the reference (a UserWarning
         without).  See pack_ignorey and DESIGN §13.
 
+        grid=(Gh, Gw) (C4 model only; with `proposals` or `ignorey` a ValueError): grid features instead of detection --
+        the Res5 stage runs once over the whole res4 map and the result is average-pooled over each image's content to
+        Gh x Gw cells (adaptive_avg_pool2d's bins), row i * Gw + j for cell (i, j).  Every image gets exactly Gh * Gw
+        rows (preds_per_image), the same 2048-wide roi_features, the box predictor's obj / attr outputs on each row as
+        the given-box forward produces them, and `boxes` = the cell's extent in network pixels (times scales_yx).  No
+        RPN, no NMS; roi_outputs is not used; 1 <= Gh, Gw, Gh * Gw <= 1024, and an explicit max_detections below
+        Gh * Gw raises ValueError.  The rule is this project's: parity unpinned for the rule.
+
         Which detections come out is roi_outputs.selection's: "class_max" (the reference's rule, the default) or
         "per_class" (NMS per class, a live score_thresh; see ROIOutputs and DESIGN §15).  The given-box forward ignores
         roi_outputs; ignorey composes with either selection, because it acts on the proposals."""
         if proposals is not None and self.given_boxes:         # before anything is enqueued
             counts = _validate_proposals(proposals, len(images))[1]
             check_given_width(int(counts.max(initial=0)), kwargs.get("max_detections"))
-        return self.forward_async(images, image_shapes, gt_boxes, proposals, scales_yx, ignorey).wait(**kwargs)
+        if grid is not None:                                   # before anything is enqueued
+            self._check_grid_args(grid, proposals, ignorey)
+            gh, gw = check_grid(grid)
+            check_given_width(gh * gw, kwargs.get("max_detections"))
+        return self.forward_async(images, image_shapes, gt_boxes, proposals, scales_yx, ignorey, grid).wait(**kwargs)
+
+    def _check_grid_args(self, grid, proposals, ignorey):
+        if not self.grid_features:
+            raise ValueError("grid= is the C4 model's: the FPN detector has no Res5 stage to run over a map")
+        if proposals is not None:
+            raise ValueError("grid= pools fixed cells: it cannot be combined with proposals=")
+        if ignorey is not None:
+            raise ValueError("ignorey removes / trims RPN proposals: there are none with grid=")
 
     def _prepare(self, images, image_shapes, proposals, scales_yx, ignorey):
         """The argument checks and host-side parsing both detectors' forward_async start with; nothing is enqueued.
@@ -507,21 +546,34 @@ class FRCNN:
         hw = np.ascontiguousarray(np.asarray(torch.as_tensor(image_shapes).cpu()).reshape(N, 2), dtype=np.int32)
         return images, hw, sc, given, ig
 
-    def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None):
+    def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None, grid=None):
         """Enqueue a forward and return at once (vk_forward_begin, vk_forward_begin_select with
-        roi_outputs.selection = "per_class", or vk_forward_boxes_begin with `proposals`, see forward()); `.wait(**kwargs)`
+        roi_outputs.selection = "per_class", vk_forward_boxes_begin with `proposals`, or vk_forward_grid_begin with `grid`,
+        see forward()); `.wait(**kwargs)`
         on the returned handle finishes it (vk_forward_end) and formats the outputs like forward().  Up to four may be in
         flight, detection and given-box forwards mixed; they must be waited for in order, on the same stream.  The caller
         must not modify `images` (or the proposals) before wait() returns.  Forwards in flight together run beside each
         other on the device (option "forward_lanes", 2 by default: two working sets and two streams of the model's own;
         `set_option("forward_lanes", 1)` keeps them one after the other on the current stream); the results are the same
         bits, and wait() orders the current stream behind the forward."""
+        if grid is not None:
+            self._check_grid_args(grid, proposals, ignorey)
+            grid = check_grid(grid)
         images, hw, sc, given, ig = self._prepare(images, image_shapes, proposals, scales_yx, ignorey)
         N, _, H, W = images.shape
         F = self.config.RESNETS.RES2_OUT_CHANNELS * 8
         dev, s = self.device, stream(self.device)
         scp = sc.ctypes.data_as(C.c_void_p) if sc is not None else None
         ticket = C.c_int64(-1)
+        if grid is not None:
+            gh, gw = grid
+            bufs = OutputBlock(output_spec(N, gh * gw, F), device=dev)
+            out = L.vk_outputs(*[bufs[k].data_ptr() for k in bufs])
+            L.call("vk_forward_grid_begin", self._h, images.data_ptr(), N, H, W, hw.ctypes.data_as(C.c_void_p), scp, gh, gw,
+                   C.byref(out), s, C.byref(ticket))
+            st = _Ticket(ticket.value, bufs, images)
+            self._open.append(st)
+            return PendingForward(self, st, hw, given_width=gh * gw)
         if given is not None:
             boxes, counts = given
             B = boxes.shape[1]

@@ -71,6 +71,7 @@ class _Bottleneck:
 class FRCNNFPN(FRCNN):
     STAGES = ("res2", "res3", "res4", "res5")
     given_boxes = True                   # forward(proposals=...): region features for caller-supplied boxes
+    grid_features = False                # forward(grid=...) is the C4 model's: a ValueError here
 
     def __init__(self, cfg, precision=None, device=None):
         self._init_host(cfg, precision, device)
@@ -198,10 +199,13 @@ class FRCNNFPN(FRCNN):
             evs.append(e)
 
     # ---- forward ----
-    def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None):
+    def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None, grid=None):
         """Detection, or with `proposals` region features for exactly those boxes (FRCNN.forward).  The forward
         runs to its end here; the returned handle's wait() / wait_raw() only format / hand out the outputs.
-        roi_outputs.selection = "per_class" is the C4 model's: detection with it raises ValueError here."""
+        roi_outputs.selection = "per_class" is the C4 model's: detection with it raises ValueError here, and
+        so does grid=."""
+        if grid is not None:                                                         # before anything is enqueued
+            self._check_grid_args(grid, proposals, ignorey)
         if proposals is None and self.roi_outputs.select_params() is not None:       # before anything is enqueued
             raise ValueError('roi_outputs.selection="per_class" is not available on the FPN detector (C4 model only)')
         images, hw, sc, given, ig = self._prepare(images, image_shapes, proposals, scales_yx, ignorey)

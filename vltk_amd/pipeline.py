@@ -8,7 +8,9 @@ hundreds of images per second on an MI355X everything around the forward has to 
     main thread        upload -> GPU pre-processing (vltk_amd.Preprocess: the legacy contract, scales_yx = raw/size)
                        -> FRCNN forward with `scales_yx` (boxes come back in raw-image coordinates, frcnn.py:1280-1283);
                           with `boxes` (imgid -> [K, 4] in raw-image coordinates) the given-box forward
-                          (FRCNN.forward(proposals=...)), its [B, max K] block widened to the schema's D with zeros
+                          (FRCNN.forward(proposals=...)), its [B, max K] block widened to the schema's D with zeros;
+                          with `grid` = (Gh, Gw) the grid forward (FRCNN.forward(grid=...)): Gh * Gw rows per image,
+                          widened to D the same way
                        -> [world > 1: ONE all-gather of the flat output block, parallel.py]
                        -> asynchronous device-to-host copy of the flat block into a pinned ring slot (copy stream)
     writer thread      waits for the slot's event, rounds the boxes (adapters/frcnn.py:57) and streams the rows to the
@@ -43,8 +45,20 @@ class ExtractionPipeline:
     preprocess: vltk_amd.preprocess.Preprocess (or a callable (raws, ids) -> (ids, images, sizes, scales_yx))."""
 
     def __init__(self, model, preprocess, savefile, batch_size=32, visual_dim=2048, dataset=None, processor_args=None,
-                 model_config=None, group=None, depth=2, boxes=None, ignorey=None):
+                 model_config=None, group=None, depth=2, boxes=None, ignorey=None, grid=None):
         self.model, self.preprocess = model, preprocess
+        # grid features: (Gh, Gw) cells per image in place of detection; Gh * Gw <= max_detections rows are written
+        self.grid = None
+        if grid is not None:
+            from .frcnn import check_grid
+            if boxes is not None:
+                raise ValueError("grid= pools fixed cells: it cannot be combined with boxes=")
+            if ignorey is not None:
+                raise ValueError("ignorey removes / trims RPN proposals: there are none with grid=")
+            self.grid = check_grid(grid)
+            if self.grid[0] * self.grid[1] > int(model.roi_outputs.max_detections):
+                raise ValueError(f"grid={self.grid}: {self.grid[0] * self.grid[1]} cells for one image, more than "
+                                 f"max_detections={int(model.roi_outputs.max_detections)}")
         # given boxes: imgid -> [K, 4] (raw-image pixels, K <= max_detections) for every image this rank sees
         self.boxes = None if boxes is None else {str(k): v for k, v in boxes.items()}
         # ignorey bands: imgid -> [J, 2] rows (y0, y1) in raw-image pixels, J <= 64; an image without an entry has none
@@ -157,7 +171,7 @@ class ExtractionPipeline:
 
         def finish(p, ids, n_valid, step):
             blk = p.wait_raw()
-            if self.boxes is not None:
+            if self.boxes is not None or self.grid is not None:
                 blk = self._widen(blk)
             slot = step % self.depth
             if self.rank == 0:
@@ -211,6 +225,8 @@ class ExtractionPipeline:
                 if self.ignorey is not None:                  # (scales_yx takes them to the processed image, frcnn.py:331)
                     none = np.zeros((0, 2), dtype=np.float32)
                     kw["ignorey"] = [self.ignorey.get(i, none) for i in ids] + [self.ignorey.get(ids[-1], none)] * (self.B - n_valid)
+                if self.grid is not None:
+                    kw["grid"] = self.grid
                 if hasattr(self.model, "forward_async"):      # enqueue this batch behind the previous one, then finish that one
                     p = self.model.forward_async(images, sizes, scales_yx=scales_yx, **kw)
                 else:
@@ -230,7 +246,7 @@ class ExtractionPipeline:
         return self.writer.close() if self.rank == 0 else None
 
     def _widen(self, blk):
-        """A given-box block [B, max K, ...] -> the step's [B, D, ...] block, zeros beyond max K (on the device)."""
+        """A given-box block [B, max K, ...] (or a grid block [B, Gh * Gw, ...]) -> the step's [B, D, ...] block, zeros beyond max K (on the device)."""
         w = blk["obj_ids"].shape[1]
         if w == self.D:
             return blk
