@@ -162,10 +162,17 @@ int vk_destroy(vk_handle *h);
  *                              run beside each other on the device; the second working set is allocated when two forwards
  *                              first overlap (if it does not fit, the handle stays with one).  1: one working set, every
  *                              forward on the caller's stream.  The per-launch and per-stage timers force 1 while they are on.
+ *   "head_dedupe"              0 or 1 (default 1, VK_HEAD_DEDUPE): with 1, block 0 of the Res5 head pools each DISTINCT RoIPool
+ *                              window of a chunk once and runs its conv1 once per distinct window (vk_roi_windows and the
+ *                              entry points next to it); the dense [K,P,P,C] pooled tensor is then not written during the
+ *                              forward (the stage "pooled" is built when it is asked for).  Taken per chunk in the f16 mode,
+ *                              with stride-1 Res5 and "head_streams" = 1, where both 1x1 GEMMs of block 0 run as
+ *                              VK_ROUTE_GEMM4; every other chunk takes the plain path.
  * The environment variables are read by vk_create.  vk_option_check validates a value without a handle and
  * vk_option_default gives the value a new handle starts with (the variable, where it holds a valid value); both are host only.
  * vk_get_option reads an option back, and two read-only counters for tests and tools: "working_sets" (arenas the handle
- * holds: 0, 1 or 2) and "lane_forwards" (forwards that ran on a stream of the handle's own since vk_create). */
+ * holds: 0, 1 or 2), "lane_forwards" (forwards that ran on a stream of the handle's own since vk_create) and
+ * "dedupe_chunks" (Res5 chunks that took the "head_dedupe" path since vk_create). */
 int vk_set_option(vk_handle *h, const char *key, int value);
 int vk_get_option(vk_handle *h, const char *key, int *value);
 int vk_option_check(const char *key, int value);
@@ -538,6 +545,30 @@ size_t vk_nms_workspace_bytes(int n);
  * -> out [K,P,P,C] NHWC. */
 int vk_roi_pool(const void *feat, int N, int H, int W, int C, const float *rois, int K,
                 float spatial_scale, int P, void *out, vk_dtype dt, void *stream);
+
+/* The distinct RoIPool windows of K RoIs (rois [K,5] f32 as for vk_roi_pool, on N maps of H x W cells).  Bin (ph, pw) of RoI k
+ * is row (k * P + ph) * P + pw; its window is the clamped cell range [y0, y1) x [x0, x1) that vk_roi_pool takes the maximum
+ * over (an empty range is a window too: a row of zeros).  idx [K*P*P] i32: the id of each row's window; win [K*P*P][5] i32,
+ * of which the first *u_dev rows are written: (image, y0, y1, x0, x1) of each id; u_dev [1] i32: the number of ids.  An id is
+ * the rank of (image, y0, y1, x0, x1), compared in that order, among the windows present.  Nothing is read back to the host.
+ * The workspace (vk_roi_windows_workspace_bytes, 16-byte aligned; 0 = the maps are too large for the table) holds one bit per
+ * possible window. */
+size_t vk_roi_windows_workspace_bytes(int N, int H, int W);
+int vk_roi_windows(const float *rois, int K, int N, int H, int W, int P, float spatial_scale, int32_t *idx, int32_t *win,
+                   int32_t *u_dev, void *workspace, size_t workspace_bytes, void *stream);
+/* out [*u_dev][C] (f16): row i is what vk_roi_pool writes for every bin whose window is win[i], bit for bit.  max_u: the rows
+ * `out` can hold (ids from max_u on are not written). */
+int vk_roi_pool_windows(const void *feat, int N, int H, int W, int C, const int32_t *win, const int32_t *u_dev, int max_u,
+                        void *out, vk_dtype dt, void *stream);
+/* dst[row] = src[idx[row]] for rows of row_bytes bytes (a multiple of 16) */
+int vk_gather_rows(const void *src, const int32_t *idx, long rows, int row_bytes, void *dst, void *stream);
+/* The VK_ROUTE_GEMM4 kernel on de-duplicated rows (f16): y[m] = relu?([x1[m] | x2[x2_idx[m]]] . W^T + bias) for m < M', where
+ * M' = min(*m_dev, M) when m_dev is given (M then only bounds the launch) and M otherwise.  x2 / x2_idx may be null (one input,
+ * x2 [M,cin2] read by m).  Weights and bias as for vk_conv1x1_dual.  VK_EINVAL where vk_conv_route would not give
+ * VK_ROUTE_GEMM4 for the layer at M rows, or, with two inputs, cin1 is not a multiple of 128 from 256 on.  A row's bits do not depend on its
+ * position, on M' or on which of these forms computes it. */
+int vk_conv1x1_rows(const void *x1, int cin1, const void *x2, int cin2, long M, const int32_t *m_dev, const int32_t *x2_idx,
+                    const void *w_packed, const float *bias_packed, void *y, int cout, int relu, void *stream);
 
 /* mean over the P*P positions of each RoI  <- frcnn.py:1401: x [K,S,C] (dt) -> out [K,C] f32 */
 int vk_mean_pool(const void *x, int K, int S, int C, float *out, vk_dtype dt, void *stream);

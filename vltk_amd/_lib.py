@@ -155,6 +155,11 @@ SIGNATURES = {
     "vk_nms": (_I, [_P, _P, _I, _D, _P, _P, _P, _SZ, _P]),
     "vk_nms_workspace_bytes": (_SZ, [_I]),
     "vk_roi_pool": (_I, [_P, _I, _I, _I, _I, _P, _I, _F, _I, _P, _I, _P]),
+    "vk_roi_windows_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "vk_roi_windows": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _SZ, _P]),
+    "vk_roi_pool_windows": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
+    "vk_gather_rows": (_I, [_P, _P, C.c_long, _I, _P, _P]),
+    "vk_conv1x1_rows": (_I, [_P, _I, _P, _I, C.c_long, _P, _P, _P, _P, _P, _I, _I, _P]),
     "vk_mean_pool": (_I, [_P, _I, _I, _I, _P, _I, _P]),
     "vk_box_decode": (_I, [_P, _P, _I, _I, C.POINTER(_F), _P, _P]),
     "vk_make_rois": (_I, [_P, _I, _I, _P, _P]),

@@ -51,6 +51,9 @@ struct Gemm4K {
     unsigned *tile_ctr;      // nullptr: every tile is static
     int static_tiles;
     unsigned ctr_last;       // the launch's last fetch (every workgroup fetches until its first miss): whoever draws it zeroes the word for its next user
+    // DD launches (Res5 block 0 over the distinct RoIPool windows, roi_windows.hip):
+    const int *m_dev;        // the row count lives on the device (at most M, which sizes the grid): tiles beyond it are not walked
+    const int *x2_idx;       // [M] row of x2 that output row m reads (x2 is then [*, cin2], not [M, cin2]); x still goes by m
 };
 
 constexpr int G_ROWB = 64, G_NSLOT = 4;
@@ -71,8 +74,12 @@ struct Gemm4Tile {                      // what depends on the tile: origin, the
 
 // TAG 1: the same code under a second symbol for launches of the two-stream backbone section (res4's conv1 half-batches), so that
 // profilers list the launches that overlap another stream apart from the ones that run alone (see conv_mfma_duo.hip)
+// TAG 2 (DD): the form for launches over de-duplicated rows -- M read from device memory and / or the second input addressed through a row
+// index.  Which input a pixel piece belongs to (and with it the lane's index register) is then a compile-time constant of each
+// copy of the K loop's body, not a run-time select (a v_cndmask in the loop would break the rule below).
 template <bool STAMP, int DBG = 0, int TAG = 0>
 __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
+    constexpr bool DD = TAG == 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     // PERSISTENT workgroups, one per CU (the launcher sizes the grid), each walking tiles bid, bid + grid, ... as ONE stream of
@@ -82,7 +89,17 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
     // XCD-aware (bijective) tile map, column tiles of one row tile next to each other on one XCD (conv_mfma.hip); the grid is
     // a multiple of 8 (or the whole tile count), so a workgroup's tiles all map to its own XCD.
     const int bid = blockIdx.x;
-    const int total_tiles = p.m_tiles * p.n_tiles;
+    int Mrows = p.M, m_tiles = p.m_tiles;
+    if constexpr (DD) {
+        if (p.m_dev) {
+            Mrows = min(__builtin_amdgcn_readfirstlane(*p.m_dev), p.M);
+            m_tiles = (Mrows + 255) >> 8;
+        }
+    }
+    const int total_tiles = m_tiles * p.n_tiles;
+    if constexpr (DD) {
+        if (bid >= total_tiles) return;                     // (the grid is sized by the host's bound on M)
+    }
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -121,22 +138,49 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
         const int slrow = (stid & 63) >> 2;
 #pragma unroll
         // (the index is shared by both inputs, so a layer with two of them needs xmul == x2mul: the launcher checks)
-        for (int i = 0; i < 4; ++i) T.xi[i] = (unsigned)min((wave * 4 + i) * 16 + slrow, p.M - 1 - T.m0) * (unsigned)p.xmul;   // rows past M are computed and dropped
+        for (int i = 0; i < 4; ++i) T.xi[i] = (unsigned)min((wave * 4 + i) * 16 + slrow, Mrows - 1 - T.m0) * (unsigned)p.xmul;   // rows past M are computed and dropped
         T.rx1 = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + (long)T.m0 * p.cin_bytes), (short)(p.cin_bytes / p.xmul), 0x7fffffff, 0x00020000);
-        T.rx2 = __builtin_amdgcn_make_buffer_rsrc((void *)((p.x2 ? p.x2 : p.x) + (long)T.m0 * p.cin2_bytes),
+        const bool indexed = DD && p.x2_idx;                // (uniform) the second input's rows come from the index, from its row 0
+        T.rx2 = __builtin_amdgcn_make_buffer_rsrc((void *)((p.x2 ? p.x2 : p.x) + (indexed ? 0L : (long)T.m0 * p.cin2_bytes)),
                                                   (short)(p.x2 ? p.cin2_bytes / p.x2mul : p.cin_bytes / p.xmul), 0x7fffffff, 0x00020000);
         T.rw = __builtin_amdgcn_make_buffer_rsrc((void *)(p.w + (long)T.n0 * p.wrow_bytes), 0, 0x7fffffff, 0x00020000);
+    };
+    // DD: the lane's row indices into the second input for the tile being computed.  Requested at the tile's start by asm, so that
+    // hipcc puts no vmcnt wait of its own into the K loop; first used by the requests of stage st1, which ride on stage st1 - 4:
+    // at least four stages (st1 >= 8 in DD launches), each with eight newer LDS-DMA pieces and a counted wait, lie in between.
+    unsigned xi2[4] = {0u, 0u, 0u, 0u};
+    auto load_xi2 = [&](const Gemm4Tile &T) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (p.x2_idx) {
+                const int *ip = p.x2_idx + T.m0 + (int)T.xi[i];      // (xmul == 1 in DD launches)
+                asm volatile("global_load_dword %0, %1, off" : "=v"(xi2[i]) : "v"(ip) : "memory");
+            } else {
+                xi2[i] = T.xi[i];
+            }
+        }
     };
     const int dma_x0 = (wave * 4) * 1024;                  // byte offset of this wave's first pixel-row piece in a slot
     const int dma_w0 = G_XB + (wave * 4) * 1024;
     bool steady = false;                                    // DBG builds: inside the FULL loop
     // stage = the K stage (of tile T) the piece belongs to, slot = its ring slot (compile time in the loop body)
-    auto req_x = [&](const Gemm4Tile &T, int stage, int slot, int i) {
+    // SEC (DD only): 0 = a stage of the first input, 1 = of the second; 2 = decided at run time (the plain form)
+    auto req_x = [&](auto sec_c, const Gemm4Tile &T, int stage, int slot, int i) {
+        constexpr int SEC = decltype(sec_c)::value;
         if ((DBG & 1) && steady) return;
-        const bool second = stage >= st1;                   // uniform
-        __builtin_amdgcn_struct_ptr_buffer_load_lds(second ? T.rx2 : T.rx1, (__attribute__((address_space(3))) void *)(smem + slot * G_SLOT + dma_x0 + i * 1024),
-                                                    16, T.xi[i], xo, (second ? stage - st1 : stage) * G_ROWB, 0, 0);
+        if constexpr (SEC == 2) {
+            const bool second = stage >= st1;                   // uniform
+            __builtin_amdgcn_struct_ptr_buffer_load_lds(second ? T.rx2 : T.rx1, (__attribute__((address_space(3))) void *)(smem + slot * G_SLOT + dma_x0 + i * 1024),
+                                                        16, T.xi[i], xo, (second ? stage - st1 : stage) * G_ROWB, 0, 0);
+        } else if constexpr (SEC == 0) {
+            __builtin_amdgcn_struct_ptr_buffer_load_lds(T.rx1, (__attribute__((address_space(3))) void *)(smem + slot * G_SLOT + dma_x0 + i * 1024), 16,
+                                                        T.xi[i], xo, stage * G_ROWB, 0, 0);
+        } else {
+            __builtin_amdgcn_struct_ptr_buffer_load_lds(T.rx2, (__attribute__((address_space(3))) void *)(smem + slot * G_SLOT + dma_x0 + i * 1024), 16,
+                                                        xi2[i], xo, (stage - st1) * G_ROWB, 0, 0);
+        }
     };
+    constexpr int SEC_FIRST = DD ? 0 : 2;                   // a tile's stages 0..3 (st1 >= 4 in DD launches: the launcher checks)
     auto req_w = [&](const Gemm4Tile &T, int stage, int slot, int i) {
         if ((DBG & 1) && steady) return;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(T.rw, (__attribute__((address_space(3))) void *)(smem + slot * G_SLOT + dma_w0 + i * 1024), 16, wv[i],
@@ -236,12 +280,12 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
     // SL = s & 3, REM = S - s (stages left including this one; 99 = steady state) and CONT (the workgroup has a next tile:
     // stages beyond this tile's are the next tile's first ones) are compile-time constants: which requests and waits exist is
     // decided per copy of the code, so there is no run-time flag (hipcc turns those into VALU compares).
-    auto pre = [&](auto rem_c, auto sl_c, int s, const half8 (&wcur)[8]) {
+    auto pre = [&](auto sec_c, auto rem_c, auto sl_c, int s, const half8 (&wcur)[8]) {
         constexpr int REM = decltype(rem_c)::value;
         constexpr bool FULL = REM == 99;
         constexpr int SL = decltype(sl_c)::value, S3 = (SL + 3) & 3;
         // stage s+3: of this tile, or of the next one (its stage 3 - REM)
-#define VKG_RQX3() do { if constexpr (REM > 3) req_x(A, s + 3, S3, 3); else req_x(B, 3 - REM, S3, 3); } while (0)
+#define VKG_RQX3() do { if constexpr (REM > 3) req_x(sec_c, A, s + 3, S3, 3); else req_x(VKG_IC(SEC_FIRST), B, 3 - REM, S3, 3); } while (0)
 #define VKG_RQW(I) do { if constexpr (REM > 3) req_w(A, s + 3, S3, I); else req_w(B, 3 - REM, S3, I); } while (0)
         VKG_WAIT2(xw[0]); VKG_SB();
         VKG_ROW(0, xw[0], wcur, VKG_DSRX(xw[3], SL, 3072, FULL), VKG_RQX3(), VKG_NONE, VKG_NONE);
@@ -264,11 +308,11 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
             asm volatile("s_waitcnt vmcnt(16)\n\ts_barrier" ::: "memory");
         VKG_SB();
     };
-    auto post = [&](auto rem_c, auto sl_c, int s, const half8 (&wcur)[8], half8 (&wnext)[8]) {
+    auto post = [&](auto sec_c, auto rem_c, auto sl_c, int s, const half8 (&wcur)[8], half8 (&wnext)[8]) {
         constexpr int REM = decltype(rem_c)::value;
         constexpr bool FULL = REM == 99;
         constexpr int SL = decltype(sl_c)::value, SN = (SL + 1) & 3;          // this stage's slot (== the slot of stage s+4), the next stage's
-#define VKG_RQX(I) do { if constexpr (REM > 4) req_x(A, s + 4, SL, I); else req_x(B, 4 - REM, SL, I); } while (0)
+#define VKG_RQX(I) do { if constexpr (REM > 4) req_x(sec_c, A, s + 4, SL, I); else req_x(VKG_IC(SEC_FIRST), B, 4 - REM, SL, I); } while (0)
 #define VKG_W2(A_, B_, OFF)                                                     \
     do {                                                                        \
         if constexpr ((DBG & 8) && FULL) {                                      \
@@ -290,13 +334,13 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
 #pragma unroll
     for (int st = 0; st < 3; ++st) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) req_x(A, st, st, i);
+        for (int i = 0; i < 4; ++i) req_x(VKG_IC(SEC_FIRST), A, st, st, i);
 #pragma unroll
         for (int i = 0; i < 4; ++i) req_w(A, st, st, i);
     }
-    req_x(A, 3, 3, 0);
-    req_x(A, 3, 3, 1);
-    req_x(A, 3, 3, 2);
+    req_x(VKG_IC(SEC_FIRST), A, 3, 3, 0);
+    req_x(VKG_IC(SEC_FIRST), A, 3, 3, 1);
+    req_x(VKG_IC(SEC_FIRST), A, 3, 3, 2);
     asm volatile("s_waitcnt vmcnt(19) lgkmcnt(0)\n\ts_barrier" ::: "memory");     // stage 0 (the 8 oldest of 27 pieces) has landed; bias is in LDS
     VKG_DSR(wa[0], wa0, 0, 0);
     VKG_DSR(wa[1], wa1, 0, 0);
@@ -332,6 +376,7 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
         // B = the workgroup's next tile; on its last tile the stream simply requests this tile's first stages once more (nobody
         // reads them): the K loop and its tail then hold no run-time condition at all
         setup_tile(has_next ? nt : tt, B);
+        if constexpr (DD) load_xi2(A);
         // zero the accumulators HERE (pinned: hipcc otherwise sinks the zeroing to just before each accumulator's first asm MFMA and,
         // not seeing a matrix instruction there, leaves out the wait states a v_accvgpr write needs before an MFMA reads it as SrcC)
 #pragma unroll
@@ -345,29 +390,37 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
         asm volatile("s_nop 7" ::: "memory");
         if constexpr (STAMP) asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_c0), "=s"(t_r0)::"memory");
 
-        pre(VKG_IC(99), VKG_IC(0), 0, wa);
+        pre(VKG_IC(SEC_FIRST), VKG_IC(99), VKG_IC(0), 0, wa);
         int s = 0;
         steady = true;
-        for (; s + 8 <= S; s += 4) {           // four stages per iteration: the slots are compile-time constants
-            post(VKG_IC(99), VKG_IC(0), s, wa, wb);
-            pre(VKG_IC(99), VKG_IC(1), s + 1, wb);
-            post(VKG_IC(99), VKG_IC(1), s + 1, wb, wa);
-            pre(VKG_IC(99), VKG_IC(2), s + 2, wa);
-            post(VKG_IC(99), VKG_IC(2), s + 2, wa, wb);
-            pre(VKG_IC(99), VKG_IC(3), s + 3, wb);
-            post(VKG_IC(99), VKG_IC(3), s + 3, wb, wa);
-            pre(VKG_IC(99), VKG_IC(0), s + 4, wa);
+        // four stages per iteration: the slots are compile-time constants.  An iteration at s requests pixel pieces of the stages
+        // s + 4 .. s + 7 only, and st1 is a multiple of 4 in DD launches, so all of them belong to one input.
+        auto four = [&](auto sec_c) {
+            post(sec_c, VKG_IC(99), VKG_IC(0), s, wa, wb);
+            pre(sec_c, VKG_IC(99), VKG_IC(1), s + 1, wb);
+            post(sec_c, VKG_IC(99), VKG_IC(1), s + 1, wb, wa);
+            pre(sec_c, VKG_IC(99), VKG_IC(2), s + 2, wa);
+            post(sec_c, VKG_IC(99), VKG_IC(2), s + 2, wa, wb);
+            pre(sec_c, VKG_IC(99), VKG_IC(3), s + 3, wb);
+            post(sec_c, VKG_IC(99), VKG_IC(3), s + 3, wb, wa);
+            pre(sec_c, VKG_IC(99), VKG_IC(0), s + 4, wa);
+        };
+        if constexpr (DD) {
+            for (; s + 8 <= S && s + 4 < st1; s += 4) four(VKG_IC(0));
+            for (; s + 8 <= S; s += 4) four(VKG_IC(1));
+        } else {
+            for (; s + 8 <= S; s += 4) four(VKG_IC(2));
         }
         steady = false;
         // s == S - 4, its rows 0-4 done: the last four stages; the requests riding on their rows are the next tile's first stages,
         // and the last POST reads the next tile's first fragments.
-        post(VKG_IC(4), VKG_IC(0), s, wa, wb);
-        pre(VKG_IC(3), VKG_IC(1), s + 1, wb);
-        post(VKG_IC(3), VKG_IC(1), s + 1, wb, wa);
-        pre(VKG_IC(2), VKG_IC(2), s + 2, wa);
-        post(VKG_IC(2), VKG_IC(2), s + 2, wa, wb);
-        pre(VKG_IC(1), VKG_IC(3), s + 3, wb);
-        post(VKG_IC(1), VKG_IC(3), s + 3, wb, wa);
+        post(VKG_IC(SEC_FIRST), VKG_IC(4), VKG_IC(0), s, wa, wb);
+        pre(VKG_IC(SEC_FIRST), VKG_IC(3), VKG_IC(1), s + 1, wb);
+        post(VKG_IC(SEC_FIRST), VKG_IC(3), VKG_IC(1), s + 1, wb, wa);
+        pre(VKG_IC(SEC_FIRST), VKG_IC(2), VKG_IC(2), s + 2, wa);
+        post(VKG_IC(SEC_FIRST), VKG_IC(2), VKG_IC(2), s + 2, wa, wb);
+        pre(VKG_IC(SEC_FIRST), VKG_IC(1), VKG_IC(3), s + 3, wb);
+        post(VKG_IC(SEC_FIRST), VKG_IC(1), VKG_IC(3), s + 3, wb, wa);
         // the epilogue is compiler-scheduled code: no hand-issued read may be in flight across it
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xw[0]), "+v"(xw[1]), "+v"(xw[2])::"memory");
         if constexpr (STAMP) {
@@ -415,7 +468,7 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
                 const long m = em0 + wr * 128 + mi * 16 + ej;
                 half8 rr[4];
                 if constexpr (RES) {          // (these loads retire in order behind the next tile's requests: a layer with a residual waits for them)
-                    const long mr = min(m, (long)p.M - 1);
+                    const long mr = min(m, (long)Mrows - 1);
 #pragma unroll
                     for (int qn = 0; qn < 4; ++qn) rr[qn] = *reinterpret_cast<const half8 *>(p.res + (mr * p.ldy + ch0 + qn * 32) * 2);
                 }
@@ -429,11 +482,11 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
                     half4 h0 = __builtin_convertvector(x0, half4), h1 = __builtin_convertvector(x1, half4);
                     half8 o = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
                     if constexpr (RELU) o = __builtin_elementwise_max(o, half8{0, 0, 0, 0, 0, 0, 0, 0});
-                    if (FULL || m < p.M) *reinterpret_cast<half8 *>(p.y + (m * p.ldy + ch0 + qn * 32) * 2) = o;
+                    if (FULL || m < Mrows) *reinterpret_cast<half8 *>(p.y + (m * p.ldy + ch0 + qn * 32) * 2) = o;
                 }
             }
         };
-        const bool full = em0 + 256 <= p.M;
+        const bool full = em0 + 256 <= Mrows;
         auto by_full = [&](auto r_, auto l_) {
             if (full)
                 epilogue(r_, l_, std::true_type{});
@@ -526,7 +579,13 @@ int launch_conv_gemm4(const ConvArgs &a, hipStream_t stream) {
     k.cin2_bytes = cin2 * 2;
     k.xmul = k.cin_bytes < 16384 ? 1 : (k.cin_bytes < 2 * 16384 ? 2 : 4);
     k.x2mul = 1;
+    k.m_dev = a.m_dev;
+    k.x2_idx = a.x2_idx;
+    const bool dd = a.m_dev || a.x2_idx;
     VK_REQUIRE(k.xmul == 1 || !a.x2, VK_EINVAL, "conv_gemm4: a two-input layer needs rows below 16 KiB");
+    VK_REQUIRE(!a.x2_idx || a.x2, VK_EINVAL, "conv_gemm4: a row index needs a second input");
+    VK_REQUIRE(!dd || (!a.concurrent && k.xmul == 1 && (!a.x2 || (a.Cin % 128 == 0 && a.Cin >= 256))), VK_EINVAL,
+               "conv_gemm4: device M / indexed rows need a first input of whole groups of four stages, two at least");
     k.stages = (a.Cin + cin2) / 32;
     k.st1 = a.x2 ? a.Cin / 32 : k.stages;
     k.wrow_bytes = (a.Cin + cin2) * 2;
@@ -547,7 +606,7 @@ int launch_conv_gemm4(const ConvArgs &a, hipStream_t stream) {
     k.static_tiles = total_tiles;
     const char *dyn_env = getenv("VK_GEMM4_DYNAMIC");                        // "0": every tile static (A/B switch and bit-identity test; re-read per call)
     const bool dyn_off = dyn_env && dyn_env[0] == '0';
-    if (!dyn_off && total_tiles >= 16 * grid_wgs && a.Cout <= 4096) {     // long launches: the last eighth of a workgroup's tiles is dynamic
+    if (!dyn_off && !a.m_dev && total_tiles >= 16 * grid_wgs && a.Cout <= 4096) {     // long launches (a device-side M keeps the static walk: the tail's fetch count must be known here): the last eighth of a workgroup's tiles is dynamic
         VK_TRY(acquire_tile_counter(&k.tile_ctr));
         k.static_tiles = (total_tiles / grid_wgs) * 7 / 8 * grid_wgs;
         k.ctr_last = (unsigned)(total_tiles - k.static_tiles + grid_wgs - 1);     // the tail's tiles + one miss per workgroup
@@ -589,7 +648,10 @@ int launch_conv_gemm4(const ConvArgs &a, hipStream_t stream) {
         hipLaunchKernelGGL((conv_gemm4_kernel<false, 128>), dim3(grid_wgs), dim3(256), smem_bytes, stream, k);
     } else
 #endif
-    if (!a.concurrent) {
+    if (dd) {
+        VK_TRY(set_max_lds(conv_gemm4_kernel<false, 0, 2>, G_SMEM + 32768));
+        hipLaunchKernelGGL((conv_gemm4_kernel<false, 0, 2>), dim3(grid_wgs), dim3(256), smem_bytes, stream, k);
+    } else if (!a.concurrent) {
         VK_TRY(set_max_lds(conv_gemm4_kernel<false>, G_SMEM + 32768));
         hipLaunchKernelGGL(conv_gemm4_kernel<false>, dim3(grid_wgs), dim3(256), smem_bytes, stream, k);
     } else {

@@ -167,6 +167,7 @@ using namespace vk;
 static constexpr struct {
     int head_chunk = 9600, backbone_streams = 2, backbone_split_min_batch = 8, head_streams = 1, head_split_min_rois = 512;
     int forward_lanes = 2;
+    int head_dedupe = 1;
 } kDefaults;
 
 struct vk_handle {
@@ -223,6 +224,18 @@ struct vk_handle {
     int backbone_split_min_batch = kDefaults.backbone_split_min_batch;                // ... from this batch size on (option "backbone_split_min_batch")
     int head_streams = kDefaults.head_streams;                            // 2: each Res5 chunk as two half-chunks on two streams (option "head_streams")
     int head_split_min_rois = kDefaults.head_split_min_rois;                   // ... for chunks of at least this many RoIs (option "head_split_min_rois")
+    int head_dedupe = kDefaults.head_dedupe;                              // 1: Res5 block 0 pools and convolves each distinct RoIPool window once (option "head_dedupe")
+    int64_t dedupe_chunks = 0;                                            // head chunks that took that path (vk_get_option "dedupe_chunks")
+    // "pooled" after a forward whose one chunk took the dedupe path: the dense tensor was never written; vk_get_stage expands
+    // src[idx] into the plan's buffer the first time the stage is asked for
+    struct {
+        bool pending = false;
+        const void *src = nullptr;
+        const int32_t *idx = nullptr;
+        long rows = 0;
+        int row_bytes = 0;
+        void *dst = nullptr;
+    } pooled_expand;
 
     // stage bookkeeping of the last forward
     struct Stage {
@@ -417,6 +430,16 @@ static bool fused_mean_ok(const vk_handle *h, int P, size_t rows) {
            (long)rows * mid5 * 2 < (1L << 32);
 }
 
+// What does not depend on a chunk's size in the decision for the dedupe path of Res5 block 0 (fwd_head has the rest: the two GEMMs'
+// routes): the plan carves the table's buffers on this.
+static bool head_dedupe_planned(const vk_handle *h) {
+    if (!h->head_dedupe || h->dt != VK_F16 || h->cfg.res5_halve != 0 || h->head_streams != 1 || h->res5.size() < 2) return false;
+    const Block &b = h->res5[0];
+    for (size_t i = 1; i < h->res5.size(); ++i)          // (h_sc holds the distinct pooled rows until the forward ends)
+        if (h->res5[i].has_shortcut && !h->res5[i].fused_shortcut) return false;
+    return b.fused_shortcut && b.conv1.stride == 1 && b.conv2.stride == 1 && b.conv3.cin % 128 == 0 && b.conv3.cin >= 256 && b.conv2.cout == b.conv3.cin;
+}
+
 struct Carver {
     char *base;
     size_t off = 0;
@@ -442,6 +465,12 @@ struct Plan {
     void *rpn_ws;
     size_t rpn_ws_bytes;
     void *pooled, *h_t1, *h_t2, *h_a, *h_b, *h_sc;
+    // the dedupe path of Res5 block 0 (fwd_head), or null: idx [chunk rows], win [chunk rows][5], one window count per chunk, the
+    // table's workspace.  The distinct pooled rows live in h_sc (unused where the shortcut is fused) and conv1's distinct rows in
+    // h_t2 (dead until conv2 writes it), each large enough for a chunk without a single repeated window.
+    int32_t *dd_idx, *dd_win, *dd_u;
+    void *dd_ws;
+    size_t dd_ws_bytes;
     size_t head_rows;        // pixels that h_t1 .. h_sc hold each (a Res5 chunk, or the whole res4 map of a grid forward)
     float *pool_part;        // per-tile column sums of the last Res5 conv3 (fused spatial mean), or nullptr
     float *feat;
@@ -524,6 +553,16 @@ static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D, int 
     p.h_a = cv.take(rows * h->res5_c * es);
     p.h_b = cv.take(rows * h->res5_c * es);
     p.h_sc = cv.take(rows * h->res5_c * es);
+    if (head_dedupe_planned(h) && !whole_map && p.chunk > 0) {
+        const size_t ws = vk_roi_windows_workspace_bytes(N, p.Hf, p.Wf);
+        if (ws > 0 && ws <= ((size_t)1 << 30) && roi_rows < ((size_t)1 << 31)) {
+            p.dd_ws_bytes = ws;
+            p.dd_ws = cv.take(ws);
+            p.dd_idx = (int32_t *)cv.take(roi_rows * sizeof(int32_t));
+            p.dd_win = (int32_t *)cv.take(roi_rows * 5 * sizeof(int32_t));
+            p.dd_u = (int32_t *)cv.take((size_t)ceil_div(p.K, p.chunk) * sizeof(int32_t));
+        }
+    }
     p.pool_part = nullptr;
     // + one tile: two half-chunks on two streams keep separate partials and each rounds its tile count up
     if (fused_mean_ok(h, p.P, roi_rows)) p.pool_part = (float *)cv.take(conv_duo_pool_part_bytes((long)roi_rows + 128, h->res5_c));
@@ -547,9 +586,9 @@ static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D, int 
     return p;
 }
 
-static int run_conv(vk_handle *h, const ConvLayer &L, const void *x, int N, int H, int W, const void *res, void *y,
-                    bool relu, vk_dtype out_dt, int ldy, hipStream_t s, int *Ho = nullptr, int *Wo = nullptr,
-                    const void *x2 = nullptr, int cin2 = 0, float *pool_part = nullptr, bool concurrent = false) {
+static ConvArgs layer_args(const vk_handle *h, const ConvLayer &L, const void *x, int N, int H, int W, const void *res, void *y,
+                           bool relu, vk_dtype out_dt, int ldy, const void *x2 = nullptr, int cin2 = 0, float *pool_part = nullptr,
+                           bool concurrent = false) {
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.concurrent = concurrent ? 1 : 0;
@@ -577,6 +616,13 @@ static int run_conv(vk_handle *h, const ConvLayer &L, const void *x, int N, int 
     a.stem = 0;
     a.dt = L.dt >= 0 ? (vk_dtype)L.dt : h->dt;
     a.out_dt = out_dt;
+    return a;
+}
+
+static int run_conv(vk_handle *h, const ConvLayer &L, const void *x, int N, int H, int W, const void *res, void *y,
+                    bool relu, vk_dtype out_dt, int ldy, hipStream_t s, int *Ho = nullptr, int *Wo = nullptr,
+                    const void *x2 = nullptr, int cin2 = 0, float *pool_part = nullptr, bool concurrent = false) {
+    const ConvArgs a = layer_args(h, L, x, N, H, W, res, y, relu, out_dt, ldy, x2, cin2, pool_part, concurrent);
     if (Ho) *Ho = a.Ho;
     if (Wo) *Wo = a.Wo;
     return launch_conv(a, s);
@@ -800,6 +846,24 @@ int vk_conv1x1_dual(const void *x1, int cin1, const void *x2, int cin2, long M, 
     return launch_conv(a, (hipStream_t)stream);
 }
 
+int vk_conv1x1_rows(const void *x1, int cin1, const void *x2, int cin2, long M, const int32_t *m_dev, const int32_t *x2_idx,
+                    const void *w_packed, const float *bias_packed, void *y, int cout, int relu, void *stream) {
+    VK_REQUIRE(x1 && w_packed && bias_packed && y && M > 0 && M < (1L << 31), VK_EINVAL, "conv1x1_rows: bad arguments");
+    VK_REQUIRE(!x2_idx || x2, VK_EINVAL, "conv1x1_rows: a row index needs a second input");
+    ConvArgs a;
+    fill_conv_args(a, 1, 1, (int)M, cin1, cout, cout, 1, 1, 0, 1, 1, relu, VK_F16, VK_F16);
+    a.x = x1;
+    a.x2 = x2;
+    a.Cin2 = x2 ? cin2 : 0;
+    a.w = w_packed;
+    a.bias = bias_packed;
+    a.y = y;
+    VK_REQUIRE(conv_route(a) == VK_ROUTE_GEMM4, VK_EINVAL, "conv1x1_rows: the layer does not run as VK_ROUTE_GEMM4 at %ld rows", M);
+    a.m_dev = m_dev;
+    a.x2_idx = x2_idx;
+    return launch_conv_gemm4(a, (hipStream_t)stream);
+}
+
 int vk_linear(const void *x, long M, int K, const void *w_packed, const float *bias_packed, const void *residual, void *y, int N, int ldy,
               int act, vk_dtype dt, vk_dtype out_dt, void *stream) {
     VK_REQUIRE(x && w_packed && bias_packed && y && M > 0 && M < (1L << 31), VK_EINVAL, "linear: bad arguments");
@@ -939,6 +1003,7 @@ int vk_create(const vk_config *cfg, int device, vk_handle **out) {
     (void)vk_option_default("backbone_streams", &h->backbone_streams);
     (void)vk_option_default("head_streams", &h->head_streams);
     (void)vk_option_default("forward_lanes", &h->forward_lanes);
+    (void)vk_option_default("head_dedupe", &h->head_dedupe);
     const int di = cfg->depth == 50 ? 0 : (cfg->depth == 101 ? 1 : 2);
     add_conv_names(h->names, "backbone.stem.conv1", true);
     h->stem = ConvLayer{"backbone.stem.conv1", 3, cfg->stem_out_channels, 7, 2, 3, 1, true, true};
@@ -1114,6 +1179,8 @@ int vk_option_check(const char *key, int value) {
         VK_REQUIRE(value == 1 || value == 2, VK_EINVAL, "head_streams must be 1 or 2");
     } else if (!strcmp(key, "forward_lanes")) {
         VK_REQUIRE(value == 1 || value == 2, VK_EINVAL, "forward_lanes must be 1 or 2");
+    } else if (!strcmp(key, "head_dedupe")) {
+        VK_REQUIRE(value == 0 || value == 1, VK_EINVAL, "head_dedupe must be 0 or 1");
     } else if (!strcmp(key, "head_split_min_rois")) {
         VK_REQUIRE(value >= 2, VK_EINVAL, "head_split_min_rois must be >= 2");
     } else if (!strcmp(key, "backbone_split_min_batch")) {
@@ -1138,6 +1205,9 @@ int vk_option_default(const char *key, int *value) {
     } else if (!strcmp(key, "forward_lanes")) {     // "1" or "2" exactly; anything else is ignored
         const char *fl = getenv("VK_FORWARD_LANES");
         *value = fl && (fl[0] == '1' || fl[0] == '2') && !fl[1] ? fl[0] - '0' : kDefaults.forward_lanes;
+    } else if (!strcmp(key, "head_dedupe")) {       // "0" or "1" exactly; anything else is ignored
+        const char *hd = getenv("VK_HEAD_DEDUPE");
+        *value = hd && (hd[0] == '0' || hd[0] == '1') && !hd[1] ? hd[0] - '0' : kDefaults.head_dedupe;
     } else if (!strcmp(key, "head_split_min_rois")) {
         *value = kDefaults.head_split_min_rois;
     } else if (!strcmp(key, "backbone_split_min_batch")) {
@@ -1154,6 +1224,8 @@ int vk_get_option(vk_handle *h, const char *key, int *value) {
     else if (!strcmp(key, "backbone_streams")) *value = h->backbone_streams;
     else if (!strcmp(key, "head_streams")) *value = h->head_streams;
     else if (!strcmp(key, "forward_lanes")) *value = h->forward_lanes;
+    else if (!strcmp(key, "head_dedupe")) *value = h->head_dedupe;
+    else if (!strcmp(key, "dedupe_chunks")) *value = (int)std::min<int64_t>(h->dedupe_chunks, INT32_MAX);   // read-only: head chunks that took the dedupe path
     else if (!strcmp(key, "head_split_min_rois")) *value = h->head_split_min_rois;
     else if (!strcmp(key, "backbone_split_min_batch")) *value = h->backbone_split_min_batch;
     else if (!strcmp(key, "working_sets")) *value = (h->sets[0].arena ? 1 : 0) + (h->sets[1].arena ? 1 : 0);   // read-only: arenas held
@@ -1169,6 +1241,7 @@ int vk_set_option(vk_handle *h, const char *key, int value) {
     if (!strcmp(key, "backbone_streams")) h->backbone_streams = value;
     if (!strcmp(key, "head_streams")) h->head_streams = value;
     if (!strcmp(key, "forward_lanes")) h->forward_lanes = value;
+    if (!strcmp(key, "head_dedupe")) h->head_dedupe = value;
     if (!strcmp(key, "head_split_min_rois")) h->head_split_min_rois = value;
     if (!strcmp(key, "backbone_split_min_batch")) h->backbone_split_min_batch = value;
     return VK_OK;
@@ -1238,6 +1311,14 @@ int vk_get_stage(vk_handle *h, const char *name, const void **dev_ptr, vk_dtype 
     if (h->next_ticket > h->oldest_open) {
         const int slot = (int)((h->next_ticket - 1) % vk_handle::VK_MAX_INFLIGHT);
         if (h->slot_stream[slot] != h->slot_caller[slot]) VK_CHECK_HIP(hipEventSynchronize(h->ev_done[slot]));
+    }
+    // "pooled" of a forward that pooled each distinct window once: the dense tensor is built now, on the stream that forward's
+    // caller passed (ordered behind the forward there: it ran on that stream, has been waited for above, or has ended)
+    if (h->pooled_expand.pending && !strcmp(name, "pooled") && h->next_ticket > 0) {
+        const auto &e = h->pooled_expand;
+        const int slot = (int)((h->next_ticket - 1) % vk_handle::VK_MAX_INFLIGHT);
+        VK_TRY(vk_gather_rows(e.src, e.idx, e.rows, e.row_bytes, e.dst, h->slot_caller[slot]));
+        h->pooled_expand.pending = false;
     }
     *dev_ptr = it->second.ptr;
     *dtype = it->second.dt;
@@ -1351,6 +1432,7 @@ static int fwd_open(vk_handle *h, int N, int H, int W, int R, int D, const int32
     Plan &p = *out;
     p = make_plan(h, h->sets[h->cur_set].arena, N, H, W, D, R, whole_map);
     h->stages_out.clear();
+    h->pooled_expand.pending = false;
     if (h->timing) VK_CHECK_HIP(hipEventRecord(h->ev[0], s));
 
     // slot layout: image_hw [N,2] i32 | scales_yx [N,2] f32 | counts [N] i32 | band counts [N] i32 | (8-aligned) bands
@@ -1461,10 +1543,45 @@ static int fwd_backbone(vk_handle *h, const Plan &p, const float *images_dev, hi
 // RoIs), then the class / attribute branches of the box predictor (FastRCNNOutputLayers.forward frcnn.py:1726-1740; the
 // box regression is the caller's: fwd_predictor).  Stages "pooled" (one chunk only), "feature_pooled", "obj_logits", "attr_logits".
 static int fwd_predictor(vk_handle *h, const Plan &p, hipStream_t s);
+
+// Res5 block 0 of the chunk of kc RoIs at row k0, each distinct RoIPool window pooled and run through conv1 once (roi_windows.hip,
+// DESIGN.md 6c): window table -> pool of the U distinct windows -> conv1 over U rows (M read on the device) -> gather into the dense
+// [kc, P, P, mid] input of conv2 -> conv2 -> the fused conv3 + shortcut GEMM, whose second input is pooled_u[idx].  Every row of
+// the output h_a goes through the same kernels with the same K order as on the plain path, so it has the same bits.
+static int head_block0_dedupe(vk_handle *h, const Plan &p, const void *res4, int k0, int kc, hipStream_t s) {
+    const Block &b = h->res5[0];
+    const int P = p.P;
+    const long rows = (long)kc * P * P;
+    const size_t es = dtype_size(h->dt);
+    int32_t *u = p.dd_u + k0 / p.chunk;
+    void *pooled_u = p.h_sc, *t1_u = p.h_t2;
+    VK_TRY(vk_roi_windows(p.rois + 5 * (size_t)k0, kc, p.N, p.Hf, p.Wf, P, 1.0f / 16.0f, p.dd_idx, p.dd_win, u, p.dd_ws, p.dd_ws_bytes, s));
+    VK_TRY(vk_roi_pool_windows(res4, p.N, p.Hf, p.Wf, h->res4_c, p.dd_win, u, (int)rows, pooled_u, h->dt, s));
+    ConvArgs a1 = layer_args(h, b.conv1, pooled_u, 1, 1, (int)rows, nullptr, t1_u, true, h->dt, 0);
+    a1.m_dev = u;
+    VK_TRY(launch_conv_gemm4(a1, s));
+    VK_TRY(vk_gather_rows(t1_u, p.dd_idx, rows, (int)(b.conv1.cout * es), p.h_t1, s));
+    VK_TRY(run_conv(h, b.conv2, p.h_t1, kc, P, P, nullptr, p.h_t2, true, h->dt, 0, s));
+    ConvArgs a3 = layer_args(h, b.conv3, p.h_t2, 1, 1, (int)rows, nullptr, p.h_a, true, h->dt, 0, pooled_u, b.shortcut.cin);
+    a3.x2_idx = p.dd_idx;
+    VK_TRY(launch_conv_gemm4(a3, s));
+    h->dedupe_chunks++;
+    if (p.chunk >= p.K) {
+        h->pooled_expand.pending = true;
+        h->pooled_expand.src = pooled_u;
+        h->pooled_expand.idx = p.dd_idx;
+        h->pooled_expand.rows = rows;
+        h->pooled_expand.row_bytes = (int)(h->res4_c * es);
+        h->pooled_expand.dst = p.pooled;
+    }
+    return VK_OK;
+}
+
 static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s) {
     const int N = p.N, P = p.P;
     vk_handle::Lane &ln = h->lanes[h->cur_set];
     const size_t es5 = dtype_size(h->dt);
+    int dd_chunks = 0;
     for (int k0 = 0; k0 < p.K; k0 += p.chunk) {
         const int kc = std::min(p.chunk, p.K - k0);
         // option "head_streams" = 2: the chunk's two halves run on two streams (RoIs are independent; the halves use disjoint
@@ -1480,18 +1597,35 @@ static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s
         }
         const void *x = p.pooled;
         int hh = P, ww = P;
+        // Res5 block 0 over the chunk's distinct RoIPool windows (head_block0_dedupe) where its two GEMMs take conv_gemm4 at this
+        // chunk size; the plain path otherwise
+        bool dd = p.dd_idx && !split && head_dedupe_planned(h);
+        if (dd) {
+            const Block &b0 = h->res5[0];
+            const ConvArgs a1 = layer_args(h, b0.conv1, p.h_sc, 1, 1, kc * P * P, nullptr, p.h_t2, true, h->dt, 0);
+            const ConvArgs a3 = layer_args(h, b0.conv3, p.h_t2, 1, 1, kc * P * P, nullptr, p.h_a, true, h->dt, 0, p.h_sc, b0.shortcut.cin);
+            dd = conv_route(a1) == VK_ROUTE_GEMM4 && conv_route(a3) == VK_ROUTE_GEMM4;
+        }
         for (int half = 0; half < (split ? 2 : 1); ++half) {
             const int n0 = half ? ka : 0, nb = half ? kc - ka : ka;
             hipStream_t hs = half ? h->side : s;
-            VK_TRY(vk_roi_pool(res4, N, p.Hf, p.Wf, h->res4_c, p.rois + 5 * (size_t)(k0 + n0), nb, 1.0f / 16.0f, P,
-                               (char *)p.pooled + (size_t)n0 * P * P * h->res4_c * es5, h->dt, hs));
+            if (dd) {
+                VK_TRY(head_block0_dedupe(h, p, res4, k0, kc, hs));
+                dd_chunks++;
+            } else
+                VK_TRY(vk_roi_pool(res4, N, p.Hf, p.Wf, h->res4_c, p.rois + 5 * (size_t)(k0 + n0), nb, 1.0f / 16.0f, P,
+                                   (char *)p.pooled + (size_t)n0 * P * P * h->res4_c * es5, h->dt, hs));
             // the fused mean's per-tile partials: the second half gets its own region (tiles are counted per launch)
             float *pp = p.pool_part ? (float *)((char *)p.pool_part + (half ? conv_duo_pool_part_bytes((long)ka * P * P, h->res5_c) : 0)) : nullptr;
             void *a = p.h_a, *b2 = p.h_b;
             x = p.pooled;
             hh = P;
             ww = P;
-            for (size_t bi = 0; bi < h->res5.size(); ++bi) {
+            if (dd) {              // block 0 has written h_a (stride 1: the map stays P x P)
+                x = a;
+                std::swap(a, b2);
+            }
+            for (size_t bi = dd ? 1 : 0; bi < h->res5.size(); ++bi) {
                 int ho, wo;
                 const bool last = bi + 1 == h->res5.size();
                 VK_TRY(run_block(h, h->res5[bi], x, kc, hh, ww, p.h_t1, p.h_t2, p.h_sc, a, hs, &ho, &wo, last ? pp : nullptr,
@@ -1512,6 +1646,8 @@ static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s
         if (!p.pool_part) VK_TRY(vk_mean_pool(x, kc, hh * ww, h->res5_c, p.feat + (size_t)k0 * h->res5_c, h->dt, s));
     }
     if (p.chunk >= p.K) set_stage(h, "pooled", p.pooled, h->dt, {p.K, P, P, h->res4_c});
+    if (dd_chunks > 0 && dd_chunks == ceil_div(p.K, p.chunk))      // (every chunk took the dedupe path: each count has been written)
+        set_stage(h, "head_windows", p.dd_u, VK_I32, {dd_chunks});    // distinct RoIPool windows per chunk
     return fwd_predictor(h, p, s);
 }
 
@@ -1846,6 +1982,7 @@ int vk_forward_boxes_begin(vk_handle *h, const float *images_dev, int N, int H, 
     hipStream_t s = (hipStream_t)stream;
     if (B == 0) {       // every image is empty: a zero-detection block, no kernel, no stage events; on the caller's stream, no working set
         h->stages_out.clear();
+        h->pooled_expand.pending = false;
         h->ev_valid = false;
         h->cur_caller = s;
         VK_CHECK_HIP(hipMemsetAsync(out->preds_per_image, 0, sizeof(int64_t) * (size_t)N, s));

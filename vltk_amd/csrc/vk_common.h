@@ -75,6 +75,8 @@ struct ConvArgs {
     int Cin2;
     int relu;
     int stem;            // 1: K-tiles are runs of consecutive input pixels (7x7 s2 stem)
+    const int32_t *m_dev;   // conv_gemm4 only: the row count M is read on the device (N * Ho * Wo bounds it and sizes the grid)
+    const int32_t *x2_idx;  // conv_gemm4 only: output row m reads row x2_idx[m] of x2
     vk_dtype dt, out_dt;
 };
 int launch_conv(const ConvArgs &a, hipStream_t stream);
