@@ -15,6 +15,7 @@ from vltk_amd import _lib as L                         # noqa: E402
 from vltk_amd.fpn import FPNNeck, LastLevelP6P7, MultiLevelRoIAlign   # noqa: E402
 
 import gpu_util as G                                   # noqa: E402
+from proposals_util import _ml_call                    # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -133,31 +134,6 @@ def test_fpn_neck_vs_oracle(precision, td, tol):
     for a, b in zip(got, ref):
         assert tuple(nchw(a).shape) == tuple(b.shape)
         assert G.rel_err(nchw(a), b) <= tol
-
-
-def _ml_call(objs, dlts, cells, strides, shapes, pre, post, thr, min_size=0.0):
-    import ctypes as C
-    nl, N, A = len(objs), objs[0].shape[0], objs[0].shape[1]
-    lg = [o.permute(0, 2, 3, 1).contiguous().to(G.DEV) for o in objs]                      # [N,H,W,A]
-    dl = [d.view(N, A, 4, d.shape[2], d.shape[3]).permute(0, 3, 4, 1, 2).reshape(N, d.shape[2], d.shape[3], 4 * A).contiguous().to(G.DEV)
-          for d in dlts]                                                                   # [N,H,W,4A] in (a, coord) order
-    ce = [torch.from_numpy(np.ascontiguousarray(c, np.float32)).to(G.DEV) for c in cells]
-    P_ = lambda ts: (C.c_void_p * nl)(*[t.data_ptr() for t in ts])
-    I_ = lambda vs: (C.c_int32 * nl)(*[int(v) for v in vs])
-    hw = torch.tensor(shapes, dtype=torch.int32, device=G.DEV)
-    wts = (C.c_float * 4)(1.0, 1.0, 1.0, 1.0)
-    ob = torch.zeros((N, post, 4), device=G.DEV)
-    ol = torch.zeros((N, post), device=G.DEV)
-    oc = torch.zeros(N, dtype=torch.int32, device=G.DEV)
-    flag = torch.zeros(1, dtype=torch.int32, device=G.DEV)
-    nb = L.load().vk_rpn_multilevel_workspace_bytes(N, nl, pre, post)
-    ws = torch.empty(nb, dtype=torch.uint8, device=G.DEV)
-    L.call("vk_rpn_proposals_multilevel", P_(lg), I_([A] * nl), P_(dl), I_([4 * A] * nl), nl, N, I_([o.shape[2] for o in objs]),
-           I_([o.shape[3] for o in objs]), A, P_(ce), I_(strides), 0.0, G.P(hw), wts, min_size, thr, pre, post, G.P(ob), G.P(ol), G.P(oc),
-           G.P(flag), G.P(ws), nb, G.stream())
-    torch.cuda.synchronize()
-    assert int(flag) == 0
-    return ob.cpu(), ol.cpu(), oc.cpu()
 
 
 def test_multilevel_proposals_vs_reference(g):

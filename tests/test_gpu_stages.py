@@ -30,6 +30,7 @@ from vltk_amd import _lib as L                 # noqa: E402
 from vltk_amd.config import Config, vg_c4_config_dict   # noqa: E402
 
 import gpu_util as G                           # noqa: E402
+from proposals_util import _nms_gpu, _rpn_gpu  # noqa: E402  (the proposal stage's call helpers)
 
 
 def _rng(seed):
@@ -856,17 +857,6 @@ def test_box_decode(kat, tag, w):
     assert G.rel_err(out.cpu(), kat[tag + "/y"]) <= 2e-6
 
 
-def _nms_gpu(boxes, scores, thr):
-    n = len(boxes)
-    bd, sd_ = torch.from_numpy(boxes).to(G.DEV), torch.from_numpy(scores).to(G.DEV)
-    keep = torch.zeros(max(n, 1), dtype=torch.int64, device=G.DEV)
-    cnt = torch.zeros(1, dtype=torch.int32, device=G.DEV)
-    ws = torch.empty(L.load().vk_nms_workspace_bytes(n), dtype=torch.uint8, device=G.DEV)
-    L.call("vk_nms", G.P(bd), G.P(sd_), n, float(thr), G.P(keep), G.P(cnt), G.P(ws), ws.numel(), G.stream())
-    torch.cuda.synchronize()
-    return keep[: int(cnt.item())].cpu().numpy()
-
-
 @pytest.mark.parametrize("n,thr,ties", [(1, 0.5, False), (37, 0.3, False), (300, 0.3, True), (1000, 0.7, True),
                                         (6000, 0.7, False), (6000, 0.5, True)])
 def test_nms_bit_exact(n, thr, ties):
@@ -920,27 +910,6 @@ def test_nms_two_phases_bit_exact(monkeypatch, lead):
 
 def test_nms_empty():
     assert len(_nms_gpu(np.zeros((0, 4), np.float32), np.zeros((0,), np.float32), 0.5)) == 0
-
-
-def _rpn_gpu(obj, dlt, shapes, cell, pre, post, thr, min_size=0.0):
-    """obj [N,A,H,W], dlt [N,4A,H,W] (oracle layout) -> GPU proposals via the C ABI."""
-    N, A, Hf, Wf = obj.shape
-    lg = obj.permute(0, 2, 3, 1).contiguous().to(G.DEV)            # [N,H,W,A]
-    dl = dlt.permute(0, 2, 3, 1).contiguous().to(G.DEV)            # [N,H,W,4A]
-    ca = torch.from_numpy(np.ascontiguousarray(cell, dtype=np.float32)).to(G.DEV)
-    hw = torch.tensor(shapes, dtype=torch.int32, device=G.DEV)
-    ob = torch.zeros((N, post, 4), dtype=torch.float32, device=G.DEV)
-    ol = torch.zeros((N, post), dtype=torch.float32, device=G.DEV)
-    oc = torch.zeros((N,), dtype=torch.int32, device=G.DEV)
-    flag = torch.zeros((1,), dtype=torch.int32, device=G.DEV)
-    ws = torch.empty(L.load().vk_rpn_workspace_bytes(N, Hf * Wf * A, pre), dtype=torch.uint8, device=G.DEV)
-    L.call("vk_rpn_proposals", G.P(lg), A, G.P(dl), 4 * A, N, Hf, Wf, A, G.P(ca), 16, 0.0, G.P(hw),
-           (C.c_float * 4)(1.0, 1.0, 1.0, 1.0), float(min_size), float(thr), pre, post, G.P(ob), G.P(ol), G.P(oc),
-           G.P(flag), G.P(ws), ws.numel(), G.stream())
-    torch.cuda.synchronize()
-    assert int(flag.item()) == 0
-    cnt = oc.cpu().tolist()
-    return [(ob[i, :cnt[i]].cpu(), ol[i, :cnt[i]].cpu()) for i in range(N)]
 
 
 def test_rpn_proposals_golden(kat):
