@@ -91,9 +91,19 @@ typedef struct vk_roi_params {
  *   class that survives NMS (0 and class 0 when it survives in none; ties to the smaller class), ranked by confidence
  *   descending (ties to the lower proposal row), the first min(max(#{(double)confidence >= score_thresh},
  *   min_detections), max_detections, proposals of the image) are the output.  0 <= score_thresh <= 1 and
- *   min_detections <= max_detections, else VK_EINVAL.  The contract in full: DESIGN.md section 15. */
+ *   min_detections <= max_detections, else VK_EINVAL.  The contract in full: DESIGN.md section 15.
+ * VK_SELECT_DETECTIONS: a detector's output (detectron2's fast_rcnn_inference_single_image).  Every (proposal, class) pair
+ *   with (double)score > score_thresh (strict) is a candidate, NMS per class at roi.nms_thresh[0] (roi.num_nms_thresh must
+ *   be 1) over the candidates, the survivors of all classes ranked by score descending, then lower proposal row, then
+ *   lower class; the first min(#survivors, max_detections) are the output: a proposal may come out under several classes,
+ *   and an image may yield nothing.  0 <= score_thresh <= 1, min_detections == 0 (the rule has no minimum count) and
+ *   1 <= max_detections <= 1024 (it may exceed the proposals per image), else VK_EINVAL.  DESIGN.md section 18.
+ *   VK_DETECTIONS_LDS_KEYS: an image with at most this many NMS survivors is ranked by a sort in LDS, one with more by a
+ *   radix select over the survivors in global memory; the results do not depend on the path. */
 #define VK_SELECT_CLASS_MAX 0
 #define VK_SELECT_PER_CLASS 1
+#define VK_SELECT_DETECTIONS 2
+#define VK_DETECTIONS_LDS_KEYS 4096
 typedef struct vk_select_params {
     int32_t       mode;
     double        score_thresh;
@@ -224,7 +234,12 @@ int vk_forward_begin_ignorey(vk_handle *h, const float *images_dev, int N, int H
  * columns of the one box with CLS_AGNOSTIC_BBOX_REG), then the selection (stages "max_conf" [N, R] f32, "attr_prob" [K] and "keep_ids");
  * "chosen_deltas" is not produced.  A non-finite box of ANY class raises the reference's assertion from vk_forward_end
  * (_clip_box runs on all R*C boxes, do_nms frcnn.py:121).  Its scores, deltas and confidences live in an arena of their own,
- * taken on the first per-class forward (K * (5C + 4) floats: 0.31 GB at 32 x 300 x 1600) and never by the other mode. */
+ * taken on the first per-class forward (K * (5C + 4) floats: 0.31 GB at 32 x 300 x 1600) and never by the other mode.
+ * VK_SELECT_DETECTIONS computes the same "obj_scores" and "box_deltas", then the detector-style selection; its stages are
+ * "obj_scores", "box_deltas", "attr_prob", "keep_ids" [N, max_detections] i64 (the proposal row of each output row) and
+ * "n_survivors" [N] i32; max_detections may exceed POST_NMS_TOPK_TEST (at most 1024) and min_detections must be 0.  The
+ * non-finite rule is the per-class mode's.  Its arena is a third allocation, taken on the first forward in this mode and by
+ * no other: about K * (5C + 2) floats + N * R * C * 10 bytes (0.46 GB at 32 x 300 x 1600), DESIGN.md section 18. */
 int vk_forward_begin_select(vk_handle *h, const float *images_dev, int N, int H, int W,
                             const int32_t *image_hw, const float *scales_yx,
                             const vk_select_params *sp, const vk_outputs *out_dev, void *stream, int64_t *ticket,
@@ -629,6 +644,24 @@ int vk_per_class_select(const float *obj_scores, int ld_scores, const float *att
                         int N, int R, int C, int A, const int32_t *image_hw, const float *scales_yx_dev,
                         const float *weights4_host, const vk_select_params *sp, const vk_outputs *out,
                         int64_t *keep_ids_out, float *max_conf_out, int32_t *nonfinite_flag, void *stream);
+
+/* Detector-style selection (VK_SELECT_DETECTIONS, see vk_select_params and DESIGN.md section 18) as a stage-level call,
+ * independent of a handle.  The arguments are vk_per_class_select's without max_conf_out, with these differences:
+ * sp->mode must be VK_SELECT_DETECTIONS, sp->roi.min_detections 0 and 1 <= sp->roi.max_detections <= 1024 (it may exceed
+ * R); C < 2^20; keep_ids_out [N, max_detections] i64 (optional) is the proposal row of each output row, so rows that share
+ * a proposal can be seen; n_survivors_out [N] i32 (optional) is the image's count of (row, class) pairs that survive the
+ * per-class NMS, before the cut to max_detections.  out->preds_per_image[n] = min(n_survivors, max_detections), possibly 0;
+ * rows beyond it are zero.  *nonfinite_flag is OR-ed with 1 when a decoded box of any (row < counts[n], class) is not finite,
+ * candidate or not.  Does not synchronise: its scratch (N * R * C * 10 bytes and small change) is taken from and returned to
+ * the device's memory pool in stream order.
+ * vk_detections_lds_keys() returns VK_DETECTIONS_LDS_KEYS of the library as built. */
+int vk_detections_select(const float *obj_scores, int ld_scores, const float *attr_logits, int ld_attr,
+                         const float *box_deltas, int ld_box, int cls_agnostic,
+                         const float *proposals, const int32_t *counts, const float *features, int F,
+                         int N, int R, int C, int A, const int32_t *image_hw, const float *scales_yx_dev,
+                         const float *weights4_host, const vk_select_params *sp, const vk_outputs *out,
+                         int64_t *keep_ids_out, int32_t *n_survivors_out, int32_t *nonfinite_flag, void *stream);
+int vk_detections_lds_keys(void);
 
 #ifdef __cplusplus
 }

@@ -23,7 +23,7 @@ VK_ROUTE_GENERIC, VK_ROUTE_RING, VK_ROUTE_DUO, VK_ROUTE_WS, VK_ROUTE_GEMM4, VK_R
 VK_MAX_ANCHOR_DIM = 8
 VK_MAX_NMS_THRESH = 8
 VK_MAX_IGNOREY = 64
-VK_SELECT_CLASS_MAX, VK_SELECT_PER_CLASS = 0, 1
+VK_SELECT_CLASS_MAX, VK_SELECT_PER_CLASS, VK_SELECT_DETECTIONS = 0, 1, 2
 
 # status code -> the Python exception type the reference raises in the same situation
 # (frcnn.py:1930 NotImplementedError, :148 AssertionError, :1789/:1850 EnvironmentError/OSError)
@@ -172,6 +172,9 @@ SIGNATURES = {
     "vk_class_probs": (_I, [_P, _I, _I, _I, _P, _I, _P]),
     "vk_per_class_select": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, C.POINTER(_F),
                                  C.POINTER(vk_select_params), C.POINTER(vk_outputs), _P, _P, _P, _P]),
+    "vk_detections_select": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, C.POINTER(_F),
+                                  C.POINTER(vk_select_params), C.POINTER(vk_outputs), _P, _P, _P, _P]),
+    "vk_detections_lds_keys": (_I, []),
 }
 
 _lib = None

@@ -205,6 +205,9 @@ struct vk_handle {
         // so that the class-max mode never pays for them; taken on the first per-class forward, grown on need
         char *pc_arena = nullptr;
         size_t pc_arena_bytes = 0;
+        // selection = "detections": its scores / deltas / candidate and survivor lists, a third allocation on the same terms
+        char *det_arena = nullptr;
+        size_t det_arena_bytes = 0;
     } sets[2];
     struct Lane {
         hipStream_t main = nullptr;                  // the lane's own stream (two-set mode only)
@@ -1255,6 +1258,7 @@ int vk_destroy(vk_handle *h) {
     for (auto &ws : h->sets) {
         if (ws.arena) (void)hipFree(ws.arena);
         if (ws.pc_arena) (void)hipFree(ws.pc_arena);
+        if (ws.det_arena) (void)hipFree(ws.det_arena);
     }
     for (auto &e : h->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1717,56 +1721,60 @@ static int check_select_params(const vk_select_params *sp, const char *who) {
     return VK_OK;
 }
 
-// The per-class end of a detection forward (after fwd_head): soft-max of every class, bbox_pred over all its rows through the
-// linear path, per-class NMS + finalize (per_class.hip).  Stages "obj_scores", "box_deltas", "max_conf", "keep_ids".
-static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp, const float *scales_dev, const vk_outputs *out,
-                         hipStream_t s) {
-    const vk_config &c = h->cfg;
-    const int C = c.num_classes, F = h->res5_c, K = p.K, D = sp->roi.max_detections;
-    const int nrow = 4 * (c.cls_agnostic_bbox_reg ? 1 : C);
-    const int ld_cls = (C + 1 + 7) / 8 * 8, ld_box = (nrow + 7) / 8 * 8;
-    if (!h->bbox_lin_w) {      // first per-class forward: bbox_pred in the packed form (dense 1x1: row-major rows, zero rows up to a whole tile)
-        const int cp = vk_packed_cout(nrow);
-        if (cp == nrow) {
-            h->bbox_lin_w = h->bbox_w;
-            h->bbox_lin_b = h->bbox_b;
-        } else {
-            const size_t row = (size_t)F * dtype_size(h->pdt);
-            void *w = nullptr, *b = nullptr;
-            VK_TRY(dev_alloc(h, (size_t)cp * row, &w));
-            VK_TRY(dev_alloc(h, (size_t)cp * sizeof(float), &b));
-            VK_CHECK_HIP(hipMemsetAsync(w, 0, (size_t)cp * row, s));
-            VK_CHECK_HIP(hipMemsetAsync(b, 0, (size_t)cp * sizeof(float), s));
-            VK_CHECK_HIP(hipMemcpyAsync(w, h->bbox_w, (size_t)nrow * row, hipMemcpyDeviceToDevice, s));
-            VK_CHECK_HIP(hipMemcpyAsync(b, h->bbox_b, (size_t)nrow * sizeof(float), hipMemcpyDeviceToDevice, s));
-            VK_CHECK_HIP(hipStreamSynchronize(s));      // once per handle: the next forward may read them from another stream
-            h->bbox_lin_w = w;
-            h->bbox_lin_b = (const float *)b;
-        }
-    }
-    Carver cv(nullptr);
-    const size_t o_scores = cv.off;
-    cv.take((size_t)K * ld_cls * sizeof(float));
-    const size_t o_deltas = cv.off;
-    cv.take((size_t)K * ld_box * sizeof(float));
-    const size_t o_best = cv.off;
-    cv.take((size_t)K * sizeof(unsigned long long));
-    const size_t o_conf = cv.off;
-    cv.take((size_t)K * sizeof(float));
-    vk_handle::WorkSet &ws = h->sets[h->cur_set];
-    if (cv.off > ws.pc_arena_bytes) {
-        if (ws.pc_arena) {
-            VK_CHECK_HIP(hipDeviceSynchronize());
-            VK_CHECK_HIP(hipFree(ws.pc_arena));
-            ws.pc_arena = nullptr;
-            ws.pc_arena_bytes = 0;
-        }
-        VK_CHECK_HIP(hipMalloc((void **)&ws.pc_arena, cv.off));
-        ws.pc_arena_bytes = cv.off;
-    }
-    float *scores = (float *)(ws.pc_arena + o_scores), *deltas = (float *)(ws.pc_arena + o_deltas);
-    float *max_conf = (float *)(ws.pc_arena + o_conf);
+static int check_detections_params(const vk_select_params *sp, const char *who) {
+    const vk_roi_params &rp = sp->roi;
+    VK_REQUIRE(rp.num_nms_thresh == 1, VK_EINVAL, "%s: the detections selection takes one NMS threshold, got a list of %d", who, rp.num_nms_thresh);
+    VK_REQUIRE(sp->score_thresh >= 0.0 && sp->score_thresh <= 1.0, VK_EINVAL, "%s: score_thresh=%g must be in [0, 1]", who, sp->score_thresh);
+    VK_REQUIRE(rp.min_detections == 0, VK_EINVAL, "%s: min_detections=%d must be 0 with the detections selection: a detector reports "
+               "nothing when nothing clears score_thresh, so there is no minimum count to fill (clear the config's MIN_DETECTIONS)",
+               who, rp.min_detections);
+    VK_REQUIRE(rp.max_detections >= 1 && rp.max_detections <= 1024, VK_EINVAL, "%s: max_detections=%d must be in 1..1024", who,
+               rp.max_detections);
+    return VK_OK;
+}
 
+// Shared by the two all-class selections (after fwd_head).  bbox_pred in the packed form of the linear path, once per handle
+// (dense 1x1: row-major rows, zero rows up to a whole tile).
+static int ensure_bbox_lin(vk_handle *h, int nrow, int F, hipStream_t s) {
+    if (h->bbox_lin_w) return VK_OK;
+    const int cp = vk_packed_cout(nrow);
+    if (cp == nrow) {
+        h->bbox_lin_w = h->bbox_w;
+        h->bbox_lin_b = h->bbox_b;
+        return VK_OK;
+    }
+    const size_t row = (size_t)F * dtype_size(h->pdt);
+    void *w = nullptr, *b = nullptr;
+    VK_TRY(dev_alloc(h, (size_t)cp * row, &w));
+    VK_TRY(dev_alloc(h, (size_t)cp * sizeof(float), &b));
+    VK_CHECK_HIP(hipMemsetAsync(w, 0, (size_t)cp * row, s));
+    VK_CHECK_HIP(hipMemsetAsync(b, 0, (size_t)cp * sizeof(float), s));
+    VK_CHECK_HIP(hipMemcpyAsync(w, h->bbox_w, (size_t)nrow * row, hipMemcpyDeviceToDevice, s));
+    VK_CHECK_HIP(hipMemcpyAsync(b, h->bbox_b, (size_t)nrow * sizeof(float), hipMemcpyDeviceToDevice, s));
+    VK_CHECK_HIP(hipStreamSynchronize(s));      // once per handle: the next forward may read them from another stream
+    h->bbox_lin_w = w;
+    h->bbox_lin_b = (const float *)b;
+    return VK_OK;
+}
+
+// a selection's own arena (WorkSet::pc_arena / det_arena), grown on need
+static int grow_select_arena(char **arena, size_t *bytes, size_t need) {
+    if (need <= *bytes) return VK_OK;
+    if (*arena) {
+        VK_CHECK_HIP(hipDeviceSynchronize());
+        VK_CHECK_HIP(hipFree(*arena));
+        *arena = nullptr;
+        *bytes = 0;
+    }
+    VK_CHECK_HIP(hipMalloc((void **)arena, need));
+    *bytes = need;
+    return VK_OK;
+}
+
+// soft-max of every class and bbox_pred over all its rows through the linear path: stages "obj_scores", "box_deltas", "attr_prob"
+static int class_scores_and_deltas(vk_handle *h, const Plan &p, float *scores, int ld_cls, float *deltas, int ld_box, int nrow,
+                                   hipStream_t s) {
+    const int C = h->cfg.num_classes, F = h->res5_c, K = p.K;
     VK_TRY(launch_class_probs(p.cls_logits, ld_cls, K, C + 1, scores, ld_cls, s));
     ConvArgs g;
     fill_conv_args(g, 1, 1, K, F, nrow, ld_box, 1, 1, 0, 1, 1, 0, h->pdt, VK_F32);
@@ -1779,8 +1787,12 @@ static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp
     set_stage(h, "box_deltas", deltas, VK_F32, {K, ld_box});
     set_stage(h, "attr_prob", p.attr_prob, VK_F32, {K});
     if (h->timing) VK_CHECK_HIP(hipEventRecord(h->ev[4], s));
+    return VK_OK;
+}
 
-    PerClassArgs a;
+static void fill_select_args(PerClassArgs &a, const vk_handle *h, const Plan &p, const vk_select_params *sp, const float *scores,
+                             int ld_cls, const float *deltas, int ld_box, const float *scales_dev, const vk_outputs *out) {
+    const vk_config &c = h->cfg;
     memset(&a, 0, sizeof(a));
     a.scores = scores;
     a.ld_scores = ld_cls;
@@ -1792,10 +1804,10 @@ static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp
     a.features = p.feat;
     a.attr_prob = p.attr_prob;
     a.attr_cls = p.attr_cls;
-    a.F = F;
+    a.F = h->res5_c;
     a.R = p.R;
-    a.D = D;
-    a.C = C;
+    a.D = sp->roi.max_detections;
+    a.C = c.num_classes;
     a.image_hw = p.image_hw;
     a.scales_yx = scales_dev;
     a.wx = c.roi_bbox_weights[0];
@@ -1807,18 +1819,83 @@ static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp
     a.score_thresh = sp->score_thresh;
     a.mind = sp->roi.min_detections;
     a.maxd = sp->roi.max_detections;
-    a.best = (unsigned long long *)(ws.pc_arena + o_best);
-    a.max_conf = max_conf;
     a.out = *out;
     a.keep_ids = p.keep_ids;
     a.nonfinite = p.nonfinite;
+}
+
+// The per-class end of a detection forward (after fwd_head): soft-max of every class, bbox_pred over all its rows through the
+// linear path, per-class NMS + finalize (per_class.hip).  Stages "obj_scores", "box_deltas", "max_conf", "keep_ids".
+static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp, const float *scales_dev, const vk_outputs *out,
+                         hipStream_t s) {
+    const vk_config &c = h->cfg;
+    const int C = c.num_classes, F = h->res5_c, K = p.K, D = sp->roi.max_detections;
+    const int nrow = 4 * (c.cls_agnostic_bbox_reg ? 1 : C);
+    const int ld_cls = (C + 1 + 7) / 8 * 8, ld_box = (nrow + 7) / 8 * 8;
+    VK_TRY(ensure_bbox_lin(h, nrow, F, s));
+    Carver cv(nullptr);
+    const size_t o_scores = cv.off;
+    cv.take((size_t)K * ld_cls * sizeof(float));
+    const size_t o_deltas = cv.off;
+    cv.take((size_t)K * ld_box * sizeof(float));
+    const size_t o_best = cv.off;
+    cv.take((size_t)K * sizeof(unsigned long long));
+    const size_t o_conf = cv.off;
+    cv.take((size_t)K * sizeof(float));
+    vk_handle::WorkSet &ws = h->sets[h->cur_set];
+    VK_TRY(grow_select_arena(&ws.pc_arena, &ws.pc_arena_bytes, cv.off));
+    float *scores = (float *)(ws.pc_arena + o_scores), *deltas = (float *)(ws.pc_arena + o_deltas);
+    float *max_conf = (float *)(ws.pc_arena + o_conf);
+    VK_TRY(class_scores_and_deltas(h, p, scores, ld_cls, deltas, ld_box, nrow, s));
+
+    PerClassArgs a;
+    fill_select_args(a, h, p, sp, scores, ld_cls, deltas, ld_box, scales_dev, out);
+    a.best = (unsigned long long *)(ws.pc_arena + o_best);
+    a.max_conf = max_conf;
     VK_TRY(launch_per_class_select(a, p.N, s));
     set_stage(h, "max_conf", max_conf, VK_F32, {p.N, p.R});
     set_stage(h, "keep_ids", p.keep_ids, VK_I64, {p.N, D});
     return VK_OK;
 }
 
-// vk_forward_begin_ignorey / vk_forward_begin_select: sel == nullptr is the class-max mode on rp, else rp == &sel->roi
+// The detector-style end of a detection forward: the same scores and all-class deltas, then
+// detections.hip.  Stages "obj_scores", "box_deltas", "attr_prob", "keep_ids", "n_survivors".
+static int fwd_detections(vk_handle *h, const Plan &p, const vk_select_params *sp, const float *scales_dev, const vk_outputs *out,
+                          hipStream_t s) {
+    const vk_config &c = h->cfg;
+    const int C = c.num_classes, F = h->res5_c, K = p.K, D = sp->roi.max_detections;
+    VK_REQUIRE(p.N <= 65535 && p.R <= 1024 && C < (1 << 20), VK_EINVAL, "forward: the detections selection takes N=%d <= 65535, "
+               "R=%d <= 1024, C=%d < 2^20", p.N, p.R, C);
+    const int nrow = 4 * (c.cls_agnostic_bbox_reg ? 1 : C);
+    const int ld_cls = (C + 1 + 7) / 8 * 8, ld_box = (nrow + 7) / 8 * 8;
+    VK_TRY(ensure_bbox_lin(h, nrow, F, s));
+    Carver cv(nullptr);
+    const size_t o_scores = cv.off;
+    cv.take((size_t)K * ld_cls * sizeof(float));
+    const size_t o_deltas = cv.off;
+    cv.take((size_t)K * ld_box * sizeof(float));
+    const size_t o_nsurv = cv.off;
+    cv.take((size_t)p.N * sizeof(int32_t));
+    const size_t o_work = cv.off;
+    cv.take(det_workspace_bytes(p.N, p.R, C));
+    vk_handle::WorkSet &ws = h->sets[h->cur_set];
+    VK_TRY(grow_select_arena(&ws.det_arena, &ws.det_arena_bytes, cv.off));
+    float *scores = (float *)(ws.det_arena + o_scores), *deltas = (float *)(ws.det_arena + o_deltas);
+    VK_TRY(class_scores_and_deltas(h, p, scores, ld_cls, deltas, ld_box, nrow, s));
+
+    DetArgs d;
+    memset(&d, 0, sizeof(d));
+    fill_select_args(d.pc, h, p, sp, scores, ld_cls, deltas, ld_box, scales_dev, out);
+    det_carve(d, ws.det_arena + o_work, p.N, p.R, C);
+    d.n_survivors = (int32_t *)(ws.det_arena + o_nsurv);
+    VK_TRY(launch_detections_select(d, p.N, s));
+    set_stage(h, "keep_ids", p.keep_ids, VK_I64, {p.N, D});
+    set_stage(h, "n_survivors", d.n_survivors, VK_I32, {p.N});
+    return VK_OK;
+}
+
+// vk_forward_begin_ignorey / vk_forward_begin_select: sel == nullptr is the class-max mode on rp, else rp == &sel->roi and
+// sel->mode is VK_SELECT_PER_CLASS or VK_SELECT_DETECTIONS
 static int forward_detect(vk_handle *h, const float *images_dev, int N, int H, int W, const int32_t *image_hw,
                           const float *scales_yx, const vk_roi_params *rp, const vk_select_params *sel, const vk_outputs *out,
                           void *stream, int64_t *ticket, const vk_ignorey *ignorey);
@@ -1833,9 +1910,11 @@ int vk_forward_begin_select(vk_handle *h, const float *images_dev, int N, int H,
                             const float *scales_yx, const vk_select_params *sp, const vk_outputs *out, void *stream, int64_t *ticket,
                             const vk_ignorey *ignorey) {
     VK_REQUIRE(sp, VK_EINVAL, "forward: null argument");
-    VK_REQUIRE(sp->mode == VK_SELECT_CLASS_MAX || sp->mode == VK_SELECT_PER_CLASS, VK_EINVAL, "forward: unknown selection mode %d", sp->mode);
+    VK_REQUIRE(sp->mode == VK_SELECT_CLASS_MAX || sp->mode == VK_SELECT_PER_CLASS || sp->mode == VK_SELECT_DETECTIONS, VK_EINVAL,
+               "forward: unknown selection mode %d", sp->mode);
     if (sp->mode == VK_SELECT_PER_CLASS) VK_TRY(check_select_params(sp, "forward"));
-    return forward_detect(h, images_dev, N, H, W, image_hw, scales_yx, &sp->roi, sp->mode == VK_SELECT_PER_CLASS ? sp : nullptr, out,
+    if (sp->mode == VK_SELECT_DETECTIONS) VK_TRY(check_detections_params(sp, "forward"));
+    return forward_detect(h, images_dev, N, H, W, image_hw, scales_yx, &sp->roi, sp->mode == VK_SELECT_CLASS_MAX ? nullptr : sp, out,
                           stream, ticket, ignorey);
 }
 
@@ -1867,8 +1946,11 @@ static int forward_detect(vk_handle *h, const float *images_dev, int N, int H, i
     VK_REQUIRE(h->finalized, VK_EINVAL, "forward: vk_finalize has not been called");
     VK_REQUIRE(N >= 1 && H >= 32 && W >= 32, VK_EINVAL, "forward: bad input size N=%d H=%d W=%d", N, H, W);
     VK_REQUIRE(rp->num_nms_thresh >= 1 && rp->num_nms_thresh <= VK_MAX_NMS_THRESH, VK_EINVAL, "forward: 1..%d nms thresholds", VK_MAX_NMS_THRESH);
-    VK_REQUIRE(rp->max_detections >= 1 && rp->max_detections <= h->cfg.post_nms_topk, VK_EINVAL,
-               "forward: max_detections=%d must be in 1..POST_NMS_TOPK_TEST", rp->max_detections);
+    if (sel && sel->mode == VK_SELECT_DETECTIONS)       // a proposal may come out under several classes (check_detections_params)
+        VK_REQUIRE(N <= 65535, VK_EINVAL, "forward: the detections selection takes at most 65535 images, got N=%d", N);
+    else
+        VK_REQUIRE(rp->max_detections >= 1 && rp->max_detections <= h->cfg.post_nms_topk, VK_EINVAL,
+                   "forward: max_detections=%d must be in 1..POST_NMS_TOPK_TEST", rp->max_detections);
     // image_shapes only bound the box clipping (frcnn.py:147-153); the reference does not check them
     // against the tensor size (its own adapter passes PIL (w,h) order, adapters/frcnn.py:50-52)
     for (int n = 0; n < N; ++n)
@@ -1913,8 +1995,11 @@ static int forward_detect(vk_handle *h, const float *images_dev, int N, int H, i
 
     // ---- RoI heads + box predictor; the arg-max class's box regression ----
     VK_TRY(fwd_head(h, p, res4, s));
-    if (sel) {                 // per-class selection: every class's box regression, NMS per class
-        VK_TRY(fwd_per_class(h, p, sel, scales_yx ? p.scales : nullptr, out, s));
+    if (sel) {                 // every class's box regression, NMS per class: one output per proposal, or a detector's triples
+        if (sel->mode == VK_SELECT_DETECTIONS)
+            VK_TRY(fwd_detections(h, p, sel, scales_yx ? p.scales : nullptr, out, s));
+        else
+            VK_TRY(fwd_per_class(h, p, sel, scales_yx ? p.scales : nullptr, out, s));
         return fwd_close(h, p.nonfinite, s, ticket);
     }
     const int F = h->res5_c;
@@ -2299,6 +2384,74 @@ int vk_per_class_select(const float *obj_scores, int ld_scores, const float *att
     }
     hipError_t e = hipStreamSynchronize(s);
     (void)hipFree(scratch);
+    if (st != VK_OK) return st;
+    VK_CHECK_HIP(e);
+    return VK_OK;
+}
+
+int vk_detections_lds_keys(void) { return VK_DETECTIONS_LDS_KEYS; }
+
+int vk_detections_select(const float *obj_scores, int ld_scores, const float *attr_logits, int ld_attr, const float *box_deltas,
+                         int ld_box, int cls_agnostic, const float *proposals, const int32_t *counts, const float *features, int F,
+                         int N, int R, int C, int A, const int32_t *image_hw, const float *scales_yx_dev,
+                         const float *weights4_host, const vk_select_params *sp, const vk_outputs *out, int64_t *keep_ids_out,
+                         int32_t *n_survivors_out, int32_t *nonfinite_flag, void *stream) {
+    VK_REQUIRE(obj_scores && box_deltas && proposals && counts && features && image_hw && weights4_host && sp && out && nonfinite_flag,
+               VK_EINVAL, "detections_select: null argument");
+    VK_REQUIRE(sp->mode == VK_SELECT_DETECTIONS, VK_EINVAL, "detections_select: mode=%d is not VK_SELECT_DETECTIONS", sp->mode);
+    VK_TRY(check_detections_params(sp, "detections_select"));
+    VK_REQUIRE(N >= 1 && N <= 65535 && R >= 1 && R <= 1024 && C >= 1 && C < (1 << 20), VK_EINVAL,
+               "detections_select: N=%d R=%d C=%d (N at most 65535, R at most 1024, C below 2^20)", N, R, C);
+    VK_REQUIRE(F >= 4 && F % 4 == 0, VK_EINVAL, "detections_select: F=%d must be a positive multiple of 4", F);
+    VK_REQUIRE(!attr_logits || (A >= 1 && ld_attr >= A), VK_EINVAL, "detections_select: A=%d ld_attr=%d", A, ld_attr);
+    VK_REQUIRE(ld_scores >= C && ld_box >= (cls_agnostic ? 4 : 4 * C), VK_EINVAL, "detections_select: row strides ld_scores=%d "
+               "ld_box=%d are shorter than the rows", ld_scores, ld_box);
+    hipStream_t s = (hipStream_t)stream;
+    const int K = N * R;
+    // scratch: the per-row attribute predictions and the candidate / survivor lists, from the device's pool in stream order
+    const size_t per = align_up((size_t)K * 4, 256);
+    char *scratch = nullptr;
+    VK_CHECK_HIP(hipMallocAsync((void **)&scratch, 2 * per + det_workspace_bytes(N, R, C), s));
+    float *attr_prob = (float *)scratch;
+    int32_t *attr_cls = (int32_t *)(scratch + per);
+    int st = VK_OK;
+    if (attr_logits) st = launch_softmax_argmax(attr_logits, ld_attr, K, A, A, attr_prob, attr_cls, nullptr, s);
+    if (st == VK_OK) {
+        DetArgs d;
+        memset(&d, 0, sizeof(d));
+        PerClassArgs &a = d.pc;
+        a.scores = obj_scores;
+        a.ld_scores = ld_scores;
+        a.deltas = box_deltas;
+        a.ld_box = ld_box;
+        a.agnostic = cls_agnostic ? 1 : 0;
+        a.proposals = proposals;
+        a.counts = counts;
+        a.features = features;
+        a.attr_prob = attr_logits ? attr_prob : nullptr;
+        a.attr_cls = attr_logits ? attr_cls : nullptr;
+        a.F = F;
+        a.R = R;
+        a.D = sp->roi.max_detections;
+        a.C = C;
+        a.image_hw = image_hw;
+        a.scales_yx = scales_yx_dev;
+        a.wx = weights4_host[0];
+        a.wy = weights4_host[1];
+        a.ww = weights4_host[2];
+        a.wh = weights4_host[3];
+        a.clampv = (float)std::log(1000.0 / 16.0);
+        a.thresh = sp->roi.nms_thresh[0];
+        a.score_thresh = sp->score_thresh;
+        a.maxd = sp->roi.max_detections;
+        a.out = *out;
+        a.keep_ids = keep_ids_out;
+        a.nonfinite = nonfinite_flag;
+        det_carve(d, scratch + 2 * per, N, R, C);
+        d.n_survivors = n_survivors_out;
+        st = launch_detections_select(d, N, s);
+    }
+    hipError_t e = hipFreeAsync(scratch, s);
     if (st != VK_OK) return st;
     VK_CHECK_HIP(e);
     return VK_OK;

@@ -59,20 +59,7 @@ __global__ __launch_bounds__(256) void class_probs_kernel(const float *__restric
     for (int c = lane; c < n; c += 64) o[c] = expf(x[c] - m) / s;
 }
 
-// The box of (row, class): decode + the finite-ness the reference asserts before the clip + _clip_box.
-__device__ __forceinline__ bool pc_box(const PerClassArgs &a, long row, int c, float img_w, float img_h, float b[4]) {
-    const float *p = a.proposals + row * 4;
-    const float pr[4] = {p[0], p[1], p[2], p[3]};
-    const float *dp = a.deltas + row * a.ld_box + (a.agnostic ? 0 : 4 * c);
-    const float d[4] = {dp[0], dp[1], dp[2], dp[3]};
-    apply_deltas_roi(pr, d, a.wx, a.wy, a.ww, a.wh, a.clampv, b);
-    const bool finite = isfinite(b[0]) && isfinite(b[1]) && isfinite(b[2]) && isfinite(b[3]);
-    b[0] = fminf(fmaxf(b[0], 0.f), img_w);
-    b[1] = fminf(fmaxf(b[1], 0.f), img_h);
-    b[2] = fminf(fmaxf(b[2], 0.f), img_w);
-    b[3] = fminf(fmaxf(b[3], 0.f), img_h);
-    return finite;
-}
+// pc_box, the box of (row, class), is in vk_common.h: detections.hip decodes with the same function.
 
 // One wavefront per (class, image): blockIdx.y = n, and blockIdx.x -> class so that the workgroups one XCD receives
 // (consecutive workgroup ids go round the 8 XCDs) hold a contiguous run of classes: the classes that share a cache line of

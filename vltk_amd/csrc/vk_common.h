@@ -256,6 +256,39 @@ int launch_per_class_select(PerClassArgs &a, int N, hipStream_t s);
 // out [N*R, C, 4]: every (row, class) box as the NMS kernel holds it; uses deltas, proposals, counts, image_hw, the weights
 int launch_class_boxes(PerClassArgs &a, int N, float *out, hipStream_t s);
 
+// The box of (row, class): decode + the finite-ness the reference asserts before the clip + _clip_box.  The one copy:
+// per_class.hip and detections.hip both call it (both build with -ffp-contract=off), so a (row, class) box holds the
+// same bits in every kernel of either selection.
+__device__ __forceinline__ bool pc_box(const PerClassArgs &a, long row, int c, float img_w, float img_h, float b[4]) {
+    const float *p = a.proposals + row * 4;
+    const float pr[4] = {p[0], p[1], p[2], p[3]};
+    const float *dp = a.deltas + row * a.ld_box + (a.agnostic ? 0 : 4 * c);
+    const float d[4] = {dp[0], dp[1], dp[2], dp[3]};
+    apply_deltas_roi(pr, d, a.wx, a.wy, a.ww, a.wh, a.clampv, b);
+    const bool finite = isfinite(b[0]) && isfinite(b[1]) && isfinite(b[2]) && isfinite(b[3]);
+    b[0] = fminf(fmaxf(b[0], 0.f), img_w);
+    b[1] = fminf(fmaxf(b[1], 0.f), img_h);
+    b[2] = fminf(fmaxf(b[2], 0.f), img_w);
+    b[3] = fminf(fmaxf(b[3], 0.f), img_h);
+    return finite;
+}
+
+// ---- detections.hip (roi_outputs.selection = "detections": vk_forward_begin_select, vk_detections_select) ----
+// pc: scores, deltas, proposals, counts, features, attr_*, F, R, C, image_hw, scales_yx, the weights, thresh, score_thresh,
+// D (= max_detections), out, keep_ids, nonfinite as in the per-class mode; mind, maxd, best and max_conf are unused.
+struct DetArgs {
+    PerClassArgs pc;
+    int32_t *cand_cnt;             // [N * C] candidates of (image, class); followed by surv_cnt, zeroed by the launcher
+    int32_t *surv_cnt;             // [N] NMS survivors of the image
+    uint16_t *cand;                // [N * C][R] candidate rows, in no particular order
+    unsigned long long *surv;      // [N][R * C] survivor keys (desc_key32(score) << 32) | (r << 20 | c), in no particular order
+    int32_t *n_survivors;          // [N] out (optional)
+};
+// bytes of the region that cand_cnt .. surv are carved from (det_carve), 256-byte aligned pieces
+size_t det_workspace_bytes(int N, int R, int C);
+void det_carve(DetArgs &d, char *base, int N, int R, int C);
+int launch_detections_select(DetArgs &d, int N, hipStream_t s);
+
 // assign_boxes_to_levels frcnn.py:444-460 for one box: floor(canonical_level + log2(sqrt(area) / canonical_size + 1e-8)),
 // clamped to [min_level, max_level], minus min_level.  The one copy of the rule: fpn.hip's assign_levels_kernel and
 // given_boxes.hip's ingest both call it, and both files build with -ffp-contract=off, so their levels are bit-equal.

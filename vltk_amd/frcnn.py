@@ -6,7 +6,8 @@ config=...)` (local paths only), `model(images, image_shapes, scales_yx=...,
 **kwargs)` returning the 7-key OrderedDict, and the mutable
 `model.roi_outputs.{nms_thresh, score_thresh, min_detections, max_detections}`
 attributes callers set (tests/frcnn_test.py:16-19), plus `model.roi_outputs.selection`
-("class_max", the reference's rule, or "per_class": NMS per class with a live score_thresh).
+("class_max", the reference's rule; "per_class": NMS per class with a live score_thresh; or
+"detections": a detector's (box, class, score) triples, NMS per class over the pairs above score_thresh).
 
 All arithmetic runs in libvltk_hip.so (hand-written gfx950 kernels); torch is
 used only to own device memory and to hand out result tensors.  There is no
@@ -26,7 +27,8 @@ from .layers import DTYPES, TORCH_DTYPES, stream
 from .parallel import OutputBlock, output_spec
 
 
-SELECTIONS = ("class_max", "per_class")
+SELECTIONS = ("class_max", "per_class", "detections")
+MAX_DETECTIONS_DETECTIONS = 1024      # the library's bound on max_detections with selection = "detections"
 
 
 class ROIOutputs:
@@ -40,10 +42,19 @@ class ROIOutputs:
     its best class that survives NMS, boxes are ranked by confidence and those at or above score_thresh are kept, the
     count bounded to [min_detections, max_detections] (and the image's proposals).  obj_ids / obj_probs / boxes are that
     class, its probability and its regressed box; attr_ids / attr_probs are the reference's per-proposal values.  A list
-    of several nms_thresh, min_detections > max_detections or a score_thresh outside [0, 1] is a ValueError."""
+    of several nms_thresh, min_detections > max_detections or a score_thresh outside [0, 1] is a ValueError.
+
+    selection = "detections" (C4 model): a detector's output, the rule of detectron2's
+    fast_rcnn_inference_single_image.  Every (proposal, class) pair whose probability is strictly above score_thresh is a
+    candidate, NMS runs per class at the one nms_thresh, and the best max_detections (box, class, score) triples of the
+    image come out, ranked by score (then lower proposal, then lower class).  A proposal may come out under several
+    classes (stage "keep_ids" is each output row's proposal) and an image may yield nothing; roi_features / attr_ids /
+    attr_probs of a row are its proposal's.  min_detections must be 0 -- the rule has no minimum count, and the config's
+    MIN_DETECTIONS, which it starts as, must be cleared on purpose; 1 <= max_detections <= 1024, which may exceed POST_NMS_TOPK_TEST; one
+    nms_thresh and a score_thresh in [0, 1]; anything else is a ValueError."""
 
     def __init__(self, cfg):
-        self.score_thresh = cfg.ROI_HEADS.SCORE_THRESH_TEST     # read by selection = "per_class" only
+        self.score_thresh = cfg.ROI_HEADS.SCORE_THRESH_TEST     # read by selection = "per_class" and "detections" only
         self.min_detections = cfg.MIN_DETECTIONS
         self.max_detections = cfg.MAX_DETECTIONS
         nms_thresh = cfg.ROI_HEADS.NMS_THRESH_TEST
@@ -64,8 +75,9 @@ class ROIOutputs:
 
     def select_params(self):
         """Validate `selection` and its knobs -> None for "class_max" (the forward then takes params()), the library's
-        vk_select_params for "per_class".  ValueError: an unknown selection; in "per_class" a list of more (or fewer) than
-        one nms_thresh (never silently ignored), min_detections > max_detections, a score_thresh outside [0, 1]."""
+        vk_select_params for "per_class" and "detections".  ValueError: an unknown selection; in either of those a list of
+        more (or fewer) than one nms_thresh (never silently ignored) or a score_thresh outside [0, 1]; in "per_class"
+        min_detections > max_detections; in "detections" a min_detections other than 0 or a max_detections outside 1..1024."""
         sel = getattr(self, "selection", "class_max")
         if sel not in SELECTIONS:
             raise ValueError(f"roi_outputs.selection={sel!r} must be one of {SELECTIONS}")
@@ -73,14 +85,22 @@ class ROIOutputs:
             return None
         thr = list(self.nms_thresh)
         if len(thr) != 1:
-            raise ValueError(f'selection="per_class" takes one nms_thresh, got the list {thr}')
-        if int(self.min_detections) > int(self.max_detections):
-            raise ValueError(f"min_detections={int(self.min_detections)} exceeds max_detections={int(self.max_detections)}")
+            raise ValueError(f'selection="{sel}" takes one nms_thresh, got the list {thr}')
+        lo, hi = int(self.min_detections), int(self.max_detections)
+        if sel == "detections":
+            if lo != 0:
+                raise ValueError(f'selection="detections" reports nothing when nothing clears score_thresh, so it has no '
+                                 f"minimum count to fill: min_detections={lo} must be 0 (it starts as the config's MIN_DETECTIONS; set it to 0)")
+            if not 1 <= hi <= MAX_DETECTIONS_DETECTIONS:
+                raise ValueError(f'selection="detections": max_detections={hi} must be in 1..{MAX_DETECTIONS_DETECTIONS}')
+        elif lo > hi:
+            raise ValueError(f"min_detections={lo} exceeds max_detections={hi}")
         score = float(self.score_thresh)
         if not 0.0 <= score <= 1.0:
             raise ValueError(f"score_thresh={score} must be in [0, 1]")
         sp = L.vk_select_params()
-        sp.mode, sp.score_thresh, sp.roi = L.VK_SELECT_PER_CLASS, score, self.params()
+        sp.mode = L.VK_SELECT_DETECTIONS if sel == "detections" else L.VK_SELECT_PER_CLASS
+        sp.score_thresh, sp.roi = score, self.params()
         return sp
 
 
@@ -504,8 +524,10 @@ class FRCNN:
         Gh * Gw raises ValueError.  The rule is this project's: parity unpinned for the rule.
 
         Which detections come out is roi_outputs.selection's: "class_max" (the reference's rule, the default) or
-        "per_class" (NMS per class, a live score_thresh; see ROIOutputs and DESIGN §15).  The given-box forward ignores
-        roi_outputs; ignorey composes with either selection, because it acts on the proposals."""
+        "per_class" (NMS per class, a live score_thresh; see ROIOutputs and DESIGN §15), or "detections" (a detector's
+        output: every (proposal, class) pair above score_thresh, NMS per class, the best max_detections triples; possibly
+        none).  The given-box and grid forwards ignore roi_outputs; ignorey composes with every selection,
+        because it acts on the proposals."""
         if proposals is not None and self.given_boxes:         # before anything is enqueued
             counts = _validate_proposals(proposals, len(images))[1]
             check_given_width(int(counts.max(initial=0)), kwargs.get("max_detections"))
@@ -548,7 +570,7 @@ class FRCNN:
 
     def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None, grid=None):
         """Enqueue a forward and return at once (vk_forward_begin, vk_forward_begin_select with
-        roi_outputs.selection = "per_class", vk_forward_boxes_begin with `proposals`, or vk_forward_grid_begin with `grid`,
+        roi_outputs.selection = "per_class" or "detections", vk_forward_boxes_begin with `proposals`, or vk_forward_grid_begin with `grid`,
         see forward()); `.wait(**kwargs)`
         on the returned handle finishes it (vk_forward_end) and formats the outputs like forward().  Up to four may be in
         flight, detection and given-box forwards mixed; they must be waited for in order, on the same stream.  The caller
@@ -589,7 +611,7 @@ class FRCNN:
         # one flat block, the seven arrays are views (so the multi-GPU exchange is a single all-gather: parallel.py)
         bufs = OutputBlock(output_spec(N, rp.max_detections, F), device=dev)
         out = L.vk_outputs(*[bufs[k].data_ptr() for k in bufs])
-        if sp is not None:                           # per-class NMS with a live score_thresh; ignorey acts before it
+        if sp is not None:                           # "per_class" / "detections": NMS per class; ignorey acts before it
             igs = None
             if ig is not None:
                 bands, bcounts, f64 = ig

@@ -20,7 +20,7 @@ import torch
 from . import _lib as L
 from .config import CONFIG_NAME, WEIGHTS_NAME, Config          # noqa: F401
 from .fpn import FPNNeck, MultiLevelRoIAlign
-from .frcnn import FRCNN, PendingForward
+from .frcnn import FRCNN, SELECTIONS, PendingForward
 from .layers import Conv, Linear, f32, stream
 from .parallel import OutputBlock, output_spec
 from .weights import BLOCKS_PER_STAGE, fpn_layer_spec
@@ -202,12 +202,15 @@ class FRCNNFPN(FRCNN):
     def forward_async(self, images, image_shapes, gt_boxes=None, proposals=None, scales_yx=None, ignorey=None, grid=None):
         """Detection, or with `proposals` region features for exactly those boxes (FRCNN.forward).  The forward
         runs to its end here; the returned handle's wait() / wait_raw() only format / hand out the outputs.
-        roi_outputs.selection = "per_class" is the C4 model's: detection with it raises ValueError here, and
-        so does grid=."""
+        roi_outputs.selection = "per_class" and "detections" are the C4 model's: detection with either
+        raises ValueError here, and so does grid=."""
         if grid is not None:                                                         # before anything is enqueued
             self._check_grid_args(grid, proposals, ignorey)
-        if proposals is None and self.roi_outputs.select_params() is not None:       # before anything is enqueued
-            raise ValueError('roi_outputs.selection="per_class" is not available on the FPN detector (C4 model only)')
+        if proposals is None:                                                        # before anything is enqueued
+            sel = getattr(self.roi_outputs, "selection", "class_max")
+            if sel in SELECTIONS and sel != "class_max":         # whatever its knobs hold: the mode itself is not here
+                raise ValueError(f'roi_outputs.selection="{sel}" is not available on the FPN detector (C4 model only)')
+            self.roi_outputs.select_params()                     # an unknown selection raises
         images, hw, sc, given, ig = self._prepare(images, image_shapes, proposals, scales_yx, ignorey)
         if given is not None and int(self.config.ROI_BOX_HEAD.FC_DIM) % 4:
             raise ValueError(f"given boxes need ROI_BOX_HEAD.FC_DIM a multiple of 4, got {int(self.config.ROI_BOX_HEAD.FC_DIM)}")
