@@ -399,6 +399,11 @@ int vk_conv2d(const void *x, int N, int H, int W, int cin,
 #define VK_ROUTE_BLK 6       /* conv3x3_blk_kernel: 3x3 over narrow channel blocks */
 int vk_conv_route(int N, int H, int W, int cin, int cin2, int has_residual, int fused_mean, int cout, int ldy, int kh, int kw,
                   int stride, int pad, int dil, int groups, int relu, vk_dtype dt, vk_dtype out_dt);
+/* How a VK_ROUTE_PANEL launch of N images of H x W with this dilation splits (host only; VK_PANEL_PHASE is re-read per call):
+ * the number of leading images that run in the kernel's phase-interleaved form (whole groups of 16; dilation 2, even H, even
+ * W <= 14), 0 = none.  The other N - that many images run in the plain form, in a second launch when both counts are non-zero.
+ * The two forms give the same bits. */
+int vk_panel_phase_images(int N, int H, int W, int dil);
 
 /* conv3 + projection shortcut of a stride-1 BottleneckBlock as ONE f16 GEMM (`out = conv3(t) ; out += shortcut(x)`,
  * frcnn.py:970-977): y[M,cout] = relu?([x1 | x2] . W^T + bias (+ residual)), W rows = [conv3 row (cin1) | shortcut row

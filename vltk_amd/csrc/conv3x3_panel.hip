@@ -19,6 +19,11 @@
 //     counted lgkmcnt, counted vmcnt (the count depends only on the tap index: compile-time).
 //   * same per-wave geometry (2x4 waves, 128x64 per wave, 16x16x32 f16 MFMA) and the same LDS-staged
 //     whole-row epilogue as conv_mfma256.hip.
+//   * PHASE form (dilation 2, even H, even W <= 14): the kernel's INTERNAL row order is
+//     [group of 16 images][phase = (y & 1, x & 1)][qy][qx][image % 16], so an aligned 16-row MFMA tile is one position of
+//     the (H/2) x (W/2) grid of one phase in 16 images: a tap is a uniform shift of (dy * W/2 + dx) * 16 rows and is inside
+//     the image for all 16 rows or for none.  Validity is a per-wave scalar, a (row tile, tap) outside the image issues no MFMAs.
+//     x and y keep their natural [image][y][x] rows: only the DMA source row of a panel piece and the epilogue's row are permuted.
 #include <cstdio>
 #include <type_traits>
 #include <vector>
@@ -54,7 +59,23 @@ struct PanelK {
     unsigned *tile_ctr;       // nullptr: every workgroup is its own tile
     int static_tiles;
     unsigned ctr_last;        // the launch's last fetch (one per tail workgroup): whoever draws it zeroes the word for its next user
+    // PHASE form only
+    int groups;               // M / (16 * HW)
+    unsigned rcp_w2;          // 65536 / (W / 2) + 1: q / (W / 2) == (q * rcp_w2) >> 16 for q < 9362
 };
+
+// PHASE form: 16-row block `gb` of a group ([phase][qy][qx], HW blocks) -> its position in the phase's grid, and the natural row
+// (y * W + x) of the block's pixel inside an image.  Uniform arithmetic, no division.
+struct PhaseBlk {
+    int qy, qx, row;
+};
+__device__ __forceinline__ PhaseBlk phase_blk(const PanelK &p, int gb) {
+    const int W2 = p.W >> 1, Q = p.HW >> 2;
+    const int ph = (gb >= Q ? 1 : 0) + (gb >= 2 * Q ? 1 : 0) + (gb >= 3 * Q ? 1 : 0);
+    const int q = gb - ph * Q;
+    const int qy = (int)(((unsigned)q * p.rcp_w2) >> 16), qx = q - qy * W2;
+    return {qy, qx, (2 * qy + (ph >> 1)) * p.W + 2 * qx + (ph & 1)};
+}
 
 constexpr int P_NW = 6;                     // weight ring slots
 constexpr int P_WSLOT = 256 * 64;           // 16 KiB
@@ -97,10 +118,14 @@ __device__ __forceinline__ void vm_wait() {
 // height does not change a bit of the output; it changes how many rounds a grid takes (res4 at 32 x 800 x 1333: 525 tiles of 256
 // = 2.05 rounds on 256 CUs, paid as 3; 467 tiles of 288 = 1.82 rounds, paid as 2 x 9/8), and a step carries 36 instead of 32
 // MFMAs per wave over the same barrier, weight reads and DMA.  The launcher picks per launch.
-template <int PP, int DBG, int TAG = 0, int MI = 8>
+// PHASE: 0 = rows in their natural order; 2 = the phase-interleaved internal row order with a scalar branch around the MFMAs of
+// each (row tile, tap); 1 = the same order with the MFMAs of invalid taps still issued on zeroed fragments (tools build: the
+// addressing alone)
+template <int PP, int DBG, int TAG = 0, int MI = 8, int PHASE = 0>
 __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(MI == 8 || MI == 9, "8 or 9 row tiles per wave");
+    static_assert(!PHASE || (PP == 4 && MI == 8 && !(DBG & 9)), "the phase form: halo 128 = (W / 2 + 1) * 16 at W = 14, 256-row tiles");
     static_assert(MI == 8 || !(DBG & 8), "the LDS-staged epilogue is written for 128-row halves");
     constexpr int TILE = 2 * MI * 16;             // pixels per tile
     constexpr int PROWS = PP * 128;               // panel rows
@@ -117,9 +142,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     const int nwg = p.m_tiles * p.n_tiles;        // tiles (== gridDim.x unless the launch has a dynamic tail)
     unsigned long st_k0 = 0;
     if constexpr (DBG & 4) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_k0)::"memory");
-    if constexpr (PP == 3) {
+    if constexpr (PP == 3 || PHASE) {
         if (p.tile_ctr && bid >= p.static_tiles) {               // (uniform) one atomic per workgroup, through the spare LDS behind the zero row
-            int *mail = reinterpret_cast<int *>(smem + 2 * PP * 128 * 64 + P_NW * P_WSLOT + 128);
+            // (PHASE: PP = 4 has no spare LDS; the word is the panel's first, and a second barrier keeps the prologue's DMA off it)
+            int *mail = reinterpret_cast<int *>(smem + (PHASE ? 0 : 2 * PP * 128 * 64 + P_NW * P_WSLOT + 128));
             if (threadIdx.x == 0) {
                 const unsigned v = atomicAdd(p.tile_ctr, 1u);
                 if (v == p.ctr_last) *p.tile_ctr = 0u;
@@ -127,6 +153,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
             }
             __syncthreads();
             bid = __builtin_amdgcn_readfirstlane(*mail);
+            if constexpr (PHASE) __syncthreads();
             if (bid >= nwg) return;
         }
     }
@@ -149,7 +176,46 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     // 32-bit byte offsets from the (uniform) tensor bases: the launcher checks both tensors are < 4 GiB
     const unsigned wsrc0 = (unsigned)(n0 + wave * 32 + lrow) * (unsigned)p.wrow_bytes + lchunk * 16;   // piece i: + i*16 rows
     const unsigned wstep = 16u * p.wrow_bytes;
+    // PHASE: block m0 / 16 + off of the internal order -> its group (return value: the block inside the group), clamped into the tensor
+    int g0 = 0, gb0 = 0;
+    if constexpr (PHASE) {
+        g0 = (m0 >> 4) / p.HW;
+        gb0 = (m0 >> 4) - g0 * p.HW;
+    }
+    auto blk_of = [&](int off, int &G) -> int {
+        int t = gb0 + off;
+        G = g0;
+        while (t < 0) {
+            t += p.HW;
+            --G;
+        }
+        while (t >= p.HW) {
+            t -= p.HW;
+            ++G;
+        }
+        if (G < 0) G = 0, t = 0;
+        if (G >= p.groups) G = p.groups - 1, t = p.HW - 1;
+        return t;
+    };
+    // PHASE: a wave's 16 rows of a panel piece are one block: image lrow of the group (per lane) at one pixel (uniform).  The PP
+    // source offsets are found once per tile; rows outside the tensor are clamped to a real block as below.
+    [[maybe_unused]] unsigned ps_lane = 0, ps_blk[PP] = {};
+    if constexpr (PHASE) {
+        ps_lane = (unsigned)(lrow * p.HW) * (unsigned)p.cin_bytes + lchunk * 16;
+#pragma unroll
+        for (int q2 = 0; q2 < PP; ++q2) {
+            int G;
+            const int t = blk_of(wave - HALO / 16 + q2 * 8, G);
+            ps_blk[q2] = __builtin_amdgcn_readfirstlane((unsigned)(G * 16 * p.HW + phase_blk(p, t).row) * (unsigned)p.cin_bytes);
+        }
+    }
     auto req_panel = [&](int cs, int piece) {                 // rows (piece*8 + wave)*16 .. +15 of panel(cs)
+        if constexpr (PHASE) {
+            unsigned pl = ps_lane;
+            asm volatile("" : "+v"(pl));                       // opaque (see x_addr_of)
+            VKP_GLDS16(p.x + (pl + (ps_blk[piece] + cs * 64)), smem + (cs & 1) * PBYTES + (piece * 8 + wave) * 1024);
+            return;
+        }
         int pf = pm_first;
         asm volatile("" : "+v"(pf));                           // opaque (see x_addr_of)
         // rows outside [0, M) are only ever read by taps the validity mask zeroes: any finite-or-not data
@@ -180,7 +246,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     }
     const int jbase = HALO + wr * (MI * 16) + j;              // panel row of fragment pixel mi = 0 at zero shift
     auto x_addr_of = [&](int parity, int tap) -> unsigned {   // byte address of fragment row mi = 0 (panel `parity`, tap)
-        const int shift = ((tap / 3 - 1) * p.W + (tap % 3 - 1)) * p.dil;
+        const int shift = PHASE ? ((tap / 3 - 1) * (p.W >> 1) + (tap % 3 - 1)) * 16 : ((tap / 3 - 1) * p.W + (tap % 3 - 1)) * p.dil;
         int jb = jbase;
         asm volatile("" : "+v"(jb));                           // opaque: the 18 (panel, tap) addresses must not be hoisted
         const int rb = jb + shift;                             // >= 0: HALO >= dil*(W+1)
@@ -215,6 +281,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     // zero a fragment whose pixel is outside the image for this tap (4 v_cndmask), then 4 MFMAs
 #define VKP_MMA_ROW(MI, XR, WF, TM)                                                                  \
     do {                                                                                             \
+        if constexpr (PHASE == 2) {                                                                  \
+            if (((TM) >> (MI)) & 1u) { /* uniform: s_bitcmp1 + s_cbranch */                          \
+                __builtin_amdgcn_s_setprio(1);                                                       \
+                _Pragma("unroll") for (int ni = 0; ni < 4; ++ni) acc[MI][ni] =                       \
+                    __builtin_amdgcn_mfma_f32_16x16x32_f16(WF[ni], XR, acc[MI][ni], 0, 0, 0);        \
+                __builtin_amdgcn_s_setprio(0);                                                       \
+            }                                                                                        \
+            break;                                                                                   \
+        }                                                                                            \
         if constexpr (!(DBG & 1) && !ZROW) {                                                         \
             uintx4 u_ = __builtin_bit_cast(uintx4, XR);                                              \
             const bool v_ = ((TM) >> (MI)) & 1u;                                                     \
@@ -256,7 +331,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         // opaque copy of the mask word BEFORE the shift: otherwise hipcc hoists either the 72 (tap, row-tile)
         // lane masks (SGPR pairs) or the 9 shifted words out of the loop and spills them
         unsigned tw = J < 3 ? vm0 : (J < 6 ? vm1 : vm2);
-        asm volatile("" : "+v"(tw));
+        if constexpr (PHASE)
+            asm volatile("" : "+s"(tw));                       // (the phase form's words are per wave)
+        else
+            asm volatile("" : "+v"(tw));
         return tw >> ((J % 3) * 9);
     };
     auto tap_word = [&](auto j_c) -> unsigned {       // the unshifted word (VKP_DSRX extracts its bit itself)
@@ -361,7 +439,24 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     // two uniform divisions; a lane's row is at most MI*16 - 1 pixels further: column by a float reciprocal with an exact
     // +-1 correction (operands < 2^24), at most one image wrap when the image has >= MI*16 pixels.  Tap validity is separable:
     // three row tests, three column tests.  Images smaller than a wave's rows keep the division form.
-    if (p.HW >= MI * 16 + p.W) {
+    if constexpr (PHASE) {
+        // one bit per (row tile, tap), the same for the wave's 64 lanes: row tile mi is grid position (qy, qx) of a phase in 16
+        // images, tap (dy, dx) is inside the image iff 0 <= qy + dy < H / 2 and 0 <= qx + dx < W / 2
+        unsigned u0 = 0, u1 = 0, u2 = 0;
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) {
+            int G;
+            const PhaseBlk b = phase_blk(p, blk_of(wr * MI + mi, G));
+            const unsigned c0 = b.qx >= 1, c2 = b.qx + 1 < (p.W >> 1);
+            const unsigned cw = m0 + (wr * MI + mi) * 16 < p.M ? (c0 << mi) | (1u << (9 + mi)) | (c2 << (18 + mi)) : 0u;
+            u0 |= b.qy >= 1 ? cw : 0u;
+            u1 |= cw;
+            u2 |= b.qy + 1 < (p.H >> 1) ? cw : 0u;
+        }
+        vm0 = __builtin_amdgcn_readfirstlane(u0);
+        vm1 = __builtin_amdgcn_readfirstlane(u1);
+        vm2 = __builtin_amdgcn_readfirstlane(u2);
+    } else if (p.HW >= MI * 16 + p.W) {
         const int mbase = m0 + wr * (MI * 16);
         const int rem0 = mbase % p.HW, ho0 = rem0 / p.W, wo0 = rem0 - ho0 * p.W;
         const float rcpw = 1.0f / (float)p.W;
@@ -463,6 +558,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     // arithmetic, same bits.  DBG & 8: the first form, through LDS in two 128-row halves so that HBM sees whole 512-B rows
     // (two barriers more, 64 ds_write_b128 + 32 ds_read_b128 per thread and tile).
     if constexpr (!(DBG & 8)) {
+        // (PHASE: the epilogue places its row tiles afresh: held from the prologue, their 16 scalars would be spilled across the K loop)
+        if constexpr (PHASE) asm volatile("" : "+s"(g0), "+s"(gb0));
         auto epilogue = [&](auto res_c, auto relu_c, auto full_c) {
             constexpr bool RES = decltype(res_c)::value, RELU = decltype(relu_c)::value, FULL = decltype(full_c)::value;
             // row tile outer, channel half inner: the two 64-byte halves of a pixel's 128-byte line (this wave's 64 channels) leave in
@@ -477,9 +574,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
                 const long m = m0 + wr * (MI * 16) + mi * 16 + j;
+                long mo = m;                                   // the row of y and of the residual
+                if constexpr (PHASE) {                         // (clamped into the tensor: rows >= M are not stored)
+                    int G;
+                    const int t = blk_of(wr * MI + mi, G);
+                    mo = (long)(G * 16 + j) * p.HW + phase_blk(p, t).row;
+                }
                 half8 rr[2];
                 if constexpr (RES) {
-                    const long mr = min(m, (long)p.M - 1);
+                    const long mr = min(mo, (long)p.M - 1);
 #pragma unroll
                     for (int qn = 0; qn < 2; ++qn) rr[qn] = *reinterpret_cast<const half8 *>(p.res + (mr * p.ldy + ch0 + qn * 32) * 2);
                 }
@@ -493,7 +596,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
                     half4 h0 = __builtin_convertvector(x0, half4), h1 = __builtin_convertvector(x1, half4);
                     half8 o = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
                     if constexpr (RELU) o = __builtin_elementwise_max(o, half8{0, 0, 0, 0, 0, 0, 0, 0});
-                    if (FULL || m < p.M) *reinterpret_cast<half8 *>(p.y + (m * p.ldy + ch0 + qn * 32) * 2) = o;
+                    if (FULL || m < p.M) *reinterpret_cast<half8 *>(p.y + (mo * p.ldy + ch0 + qn * 32) * 2) = o;
                 }
             }
         };
@@ -629,7 +732,35 @@ bool conv3x3_panel_eligible(const ConvArgs &a) {
     return true;
 }
 
+// The leading images of the launch that take the PHASE form (whole groups of 16), 0 = none.  f16 is implied by the panel kernel;
+// dilation 2, even H, even W <= 14 (halo (W / 2 + 1) * 16 <= 128 rows); H <= 1024 keeps the reciprocal of W / 2 exact.
+// VK_PANEL_PHASE=0 selects the plain form (A/B switch and bit-identity tests; re-read per call).
+int conv3x3_panel_phase_images(const ConvArgs &a) {
+    const char *v = getenv("VK_PANEL_PHASE");
+    if (v && v[0] == '0') return 0;
+    if (a.dil != 2 || a.H % 2 != 0 || a.W % 2 != 0 || a.W > 14 || a.H > 1024 || a.N < 16) return 0;
+    return a.N / 16 * 16;
+}
+
+static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase);
+
 int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream) {
+    const int np = conv3x3_panel_phase_images(a);
+    if (np == 0) return launch_panel_one(a, stream, false);
+    ConvArgs b = a;
+    b.N = np;
+    VK_TRY(launch_panel_one(b, stream, true));
+    if (np == a.N) return VK_OK;
+    // the remainder (fewer than 16 images) in the plain form: a row's bits do not depend on the form or on its launch
+    const size_t rows = (size_t)np * a.H * a.W;
+    b.N = a.N - np;
+    b.x = (const char *)a.x + rows * a.Cin * 2;
+    b.y = (char *)a.y + rows * a.ldy * 2;
+    if (a.res) b.res = (const char *)a.res + rows * a.ldy * 2;
+    return launch_panel_one(b, stream, false);
+}
+
+static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
     DeviceState *ds = nullptr;
     VK_TRY(device_state(&ds));
     PanelK k;
@@ -652,7 +783,9 @@ int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream) {
     k.cstages = a.Cin / 32;
     k.wrow_bytes = 9 * a.Cin * 2;
     k.relu = a.relu;
-    const int mi = panel_mi(a, M, ds->n_cu), pp = panel_pp(a, mi);
+    const int mi = phase ? 8 : panel_mi(a, M, ds->n_cu), pp = phase ? 4 : panel_pp(a, mi);
+    k.groups = phase ? a.N / 16 : 0;
+    k.rcp_w2 = phase ? 65536u / (unsigned)(a.W / 2) + 1u : 0u;
     k.m_tiles = ceil_div(k.M, mi * 32);
     k.n_tiles = a.Cout / 256;
     Timed t;
@@ -663,7 +796,7 @@ int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream) {
     int n_wgs = total_tiles;
     const char *dyn_env = getenv("VK_PANEL_DYNAMIC");                        // "0": every tile static (A/B switch and bit-identity test; re-read per call)
     const bool dyn_off = dyn_env && dyn_env[0] == '0';
-    if (!dyn_off && pp == 3 && total_tiles >= 16 * 256) {          // many rounds on every CU: the last sixteenth is handed out dynamically
+    if (!dyn_off && (pp == 3 || phase) && total_tiles >= 16 * 256) {          // many rounds on every CU: the last sixteenth is handed out dynamically
         VK_TRY(acquire_tile_counter(&k.tile_ctr));
         k.static_tiles = total_tiles * 15 / 16 / 8 * 8;             // (a multiple of 8: whole rounds of the XCD map; even: column-tile pairs stay together)
         n_wgs = total_tiles + (total_tiles / 32 + 63) / 64 * 64;    // spare workgroups: an XCD 3 % faster than the mean can take 3 % more tiles
@@ -712,7 +845,16 @@ int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream) {
         VKP_LAUNCH(3, 32, 0, 9);
     else
 #endif
-    if (mi == 8 && pp == 3 && a.concurrent)
+#ifdef VK_ABLATION      // VK_PANEL_PHASE=A: the phase form's row order with every MFMA still issued, on zeroed fragments (what the order alone costs)
+    if (const char *pv = getenv("VK_PANEL_PHASE"); phase && pv && pv[0] == 'A') {
+        VK_TRY(set_max_lds(conv3x3_panel_kernel<4, 0, 0, 8, 1>, smem));
+        hipLaunchKernelGGL((conv3x3_panel_kernel<4, 0, 0, 8, 1>), grid, block, smem, stream, k);
+    } else
+#endif
+    if (phase) {        // (one symbol: the form is not launched beside another stream's kernels)
+        VK_TRY(set_max_lds(conv3x3_panel_kernel<4, 0, 0, 8, 2>, smem));
+        hipLaunchKernelGGL((conv3x3_panel_kernel<4, 0, 0, 8, 2>), grid, block, smem, stream, k);
+    } else if (mi == 8 && pp == 3 && a.concurrent)
         VKP_LAUNCH(3, 0, 1, 8);
     else if (mi == 8 && pp == 3)
         VKP_LAUNCH(3, 0, 0, 8);
