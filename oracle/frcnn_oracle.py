@@ -187,7 +187,7 @@ class FRCNNOracle:
             ss = stride if stride_shortcut is None else stride_shortcut
             w3, wsc = self.sd[prefix + ".conv3.weight"], self.sd[prefix + ".shortcut.weight"]
             # fp16 emulation of the HIP path: a stride-1 projection shortcut is part of conv3's GEMM there
-            # (vk_fuse_shortcut, csrc/model.hip), so it is never rounded to f16 on its own
+            # (vk_fuse_shortcut, csrc/stage_api.hip), so it is never rounded to f16 on its own
             fused = (self.emulate is not None and ss == 1 and w3.shape[0] % 256 == 0 and w3.shape[1] % 32 == 0
                      and wsc.shape[1] % 32 == 0)
             sc = self._conv_bn(x, prefix + ".shortcut", stride=ss, round_out=not fused)

@@ -39,7 +39,9 @@ def test_set_option_validates_through_option_check():
     body = src[src.index("int vk_set_option("):]
     body = body[:body.index("\n}\n")]
     assert re.search(r"VK_TRY\(vk_option_check\(key, value\)\);", body)
-    assert body.index("vk_option_check") < body.index("h->forward_lanes = value")
+    stores = [m.start() for m in re.finditer(r"h->[^;=]*=(?!=)", body)]       # every store through the handle, whichever option
+    assert stores and body.index("VK_TRY(vk_option_check(key, value));") < min(stores)
+    assert not re.search(r"\bif\b|\bstrcmp\b", body)      # no per-option branch: the one store serves every key of the table
     lib = L.load()
     for key, good, bad in ((b"backbone_streams", (1, 4), (0, 5)), (b"head_streams", (1, 2), (0, 3)), (b"head_chunk", (0, 9600), (-1,)),
                            (b"head_split_min_rois", (2,), (1,)), (b"backbone_split_min_batch", (2,), (1,))):
@@ -79,8 +81,16 @@ def test_create_reads_the_defaults_from_option_default():
     src = open(os.path.join(ROOT, "vltk_amd", "csrc", "model.hip")).read()
     body = src[src.index("int vk_create("):]
     body = body[:body.index("\n}\n")]
-    assert 'vk_option_default("forward_lanes", &h->forward_lanes)' in body
+    assert re.search(r"for \(const OptionRow &o : kOptions\) \(void\)vk_option_default\(o\.key, &\(h->\*o\.member\)\);", body)
     assert "getenv(\"VK_FORWARD_LANES\")" not in body
+    # no option's variable is read here: every VK_* name in the option table, and VK_PREDICTOR_FP16 (an A/B switch) may stay
+    table = src[src.index("kOptions[] = {"):]
+    table = table[:table.index("\n};\n")]
+    variables = re.findall(r'"(VK_[A-Z_]+)"', table)
+    assert len(variables) == 5 and "VK_FORWARD_LANES" in variables, variables
+    for v in variables:
+        assert v not in body, v
+    assert set(re.findall(r'getenv\("(\w+)"\)', body)) <= {"VK_PREDICTOR_FP16"}
 
 
 def test_header_documents_the_option_and_the_buffer_lifetime():

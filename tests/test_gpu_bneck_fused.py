@@ -49,7 +49,7 @@ def reference(x, p, proj):
     y = F.conv2d(t2, w3) + b3.view(1, -1, 1, 1)
     if proj:
         wsc, bsc = G.fold_ref(p["wsc"], p["bnsc"], L.VK_F16)
-        y = y + F.conv2d(x, wsc) + bsc.view(1, -1, 1, 1)       # not rounded on its own: part of conv3's GEMM (model.hip can_fuse_shortcut)
+        y = y + F.conv2d(x, wsc) + bsc.view(1, -1, 1, 1)       # not rounded on its own: part of conv3's GEMM (stage_api.hip vk_fuse_shortcut)
     else:
         y = y + x
     return _h(F.relu(y))

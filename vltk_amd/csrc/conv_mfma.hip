@@ -354,7 +354,7 @@ static int launch_t(const ConvK &k, hipStream_t stream) {
 }
 
 // Which kernel takes the layer: the dispatcher's one decision (host only: eligibility rules and their A/B switches, re-read per
-// call).  launch_conv switches on it and vk_conv_route (model.hip) returns it, so the query cannot drift from the launch.
+// call).  launch_conv switches on it and vk_conv_route (stage_api.hip) returns it, so the query cannot drift from the launch.
 // Order: fused-mean and dual-source forms first; then block -> panel -> weight-stationary -> four-wave GEMM -> two-per-CU -> ring ->
 // generic.  A form no kernel takes is -VK_EINVAL with the error text set.
 int conv_route(const ConvArgs &a) {

@@ -11,126 +11,16 @@
 // so the steady state allocates nothing; a second one serves forwards that overlap (fwd_route).  The Res5 head runs over RoI *chunks* so that the
 // chunk's intermediates (pooled 14x14x1024 -> ... -> 14x14x2048) stay resident in the
 // 256 MiB Infinity Cache between consecutive convolutions instead of round-tripping HBM.
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <map>
-#include <mutex>
-#include <set>
 #include <string>
 #include <vector>
 
 #include "vk_common.h"
 
 namespace vk {
-
-thread_local KernelTimer *g_timer = nullptr;
-
-hipEvent_t KernelTimer::get() {
-    if (pool.empty()) {
-        hipEvent_t e = nullptr;
-        (void)hipEventCreate(&e);
-        all.push_back(e);
-        return e;
-    }
-    hipEvent_t e = pool.back();
-    pool.pop_back();
-    return e;
-}
-void KernelTimer::collect() {
-    const char *logp = getenv("VK_CONV_LOG");   // debug: one line per conv launch (shape, ms, TFLOP/s)
-    FILE *lf = logp ? fopen(logp, "a") : nullptr;
-    std::vector<Rec> pending;       // launches of a forward that is still in flight (vk_forward_begin without its _end yet)
-    for (auto &r : recs) {
-        float t = 0.f;
-        if (hipEventQuery(r.e1) != hipSuccess) {
-            pending.push_back(r);
-            continue;
-        }
-        if (hipEventElapsedTime(&t, r.e0, r.e1) == hipSuccess) {
-            if (lf) fprintf(lf, "%d %d %d %d %d %d %.5f %.1f\n", r.bucket, r.M, r.cout, r.cin, r.k, r.stride, t, r.flops / (t * 1e-3) / 1e12);
-            launches[r.bucket] += 1;
-            ms[r.bucket] += t;
-            flops[r.bucket] += r.flops;
-            bytes[r.bucket] += r.bytes;
-        }
-        pool.push_back(r.e0);
-        pool.push_back(r.e1);
-    }
-    if (lf) fclose(lf);
-    recs.swap(pending);
-    (void)hipGetLastError();        // hipEventQuery's "not ready" must not show up in a later launch check
-}
-KernelTimer::~KernelTimer() {
-    for (auto e : all) (void)hipEventDestroy(e);
-}
-
-int Timed::begin(hipStream_t stream) {
-    if (!tm) return VK_OK;
-    e0 = tm->get();
-    e1 = tm->get();
-    VK_CHECK_HIP(hipEventRecord(e0, stream));
-    return VK_OK;
-}
-int Timed::end(hipStream_t stream, int bucket, double flops, int M, int cout, int cin, int k, int stride, double bytes) {
-    if (!tm) return VK_OK;
-    VK_CHECK_HIP(hipEventRecord(e1, stream));
-    tm->recs.push_back({bucket, flops, e0, e1, M, cout, cin, k, stride, bytes});
-    return VK_OK;
-}
-
-// Launcher state per device: published once fully built; the lock only serialises the first launch on each device.
-static std::atomic<DeviceState *> g_devices[VK_MAX_DEVICES];
-static std::mutex g_devices_mu;
-
-int device_state(DeviceState **out) {
-    int dev = 0;
-    VK_CHECK_HIP(hipGetDevice(&dev));
-    VK_REQUIRE(dev >= 0 && dev < VK_MAX_DEVICES, VK_EINVAL, "device %d beyond VK_MAX_DEVICES", dev);
-    DeviceState *d = g_devices[dev].load(std::memory_order_acquire);
-    if (!d) {
-        std::lock_guard<std::mutex> lock(g_devices_mu);
-        d = g_devices[dev].load(std::memory_order_relaxed);
-        if (!d) {
-            hipDeviceProp_t prop;
-            VK_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
-            // one allocation: [zero page 256 B][tile ring 256 words][bneck scratch]; the first two start zeroed, and the
-            // scratch comes last so that nothing it receives can land in them
-            char *p = nullptr;
-            VK_CHECK_HIP(hipMalloc((void **)&p, 256 + 256 * sizeof(unsigned) + BN_TRASH_BYTES));
-            VK_CHECK_HIP(hipMemset(p, 0, 256 + 256 * sizeof(unsigned)));     // (synchronous: done before any launch can read it)
-            d = new DeviceState;
-            d->n_cu = prop.multiProcessorCount;
-            d->zero_page = p;
-            d->tile_ring = (unsigned *)(p + 256);
-            d->bn_trash = p + 256 + 256 * sizeof(unsigned);
-            d->tile_next = 0;
-            g_devices[dev].store(d, std::memory_order_release);
-        }
-    }
-    *out = d;
-    return VK_OK;
-}
-
-static std::set<std::pair<int, const void *>> g_lds_set;     // (device, kernel) pairs whose LDS limit is raised
-static std::mutex g_lds_mu;
-
-int set_max_lds(const void *kernel, size_t bytes) {
-    int dev = 0;
-    VK_CHECK_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_lds_mu);
-    if (g_lds_set.count({dev, kernel})) return VK_OK;
-    VK_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    g_lds_set.insert({dev, kernel});
-    return VK_OK;
-}
-
-static thread_local char g_err[1024] = "";
-void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
 
 struct HostTensor {
     std::vector<int64_t> shape;
@@ -163,13 +53,6 @@ static const int kBlocks[3][4] = {{3, 4, 6, 3}, {3, 4, 23, 3}, {3, 8, 36, 3}};  
 
 using namespace vk;
 
-// the built-in values of the options (vk_set_option); vk_option_default puts the VK_* variables over them
-static constexpr struct {
-    int head_chunk = 9600, backbone_streams = 2, backbone_split_min_batch = 8, head_streams = 1, head_split_min_rois = 512;
-    int forward_lanes = 2;
-    int head_dedupe = 1;
-} kDefaults;
-
 struct vk_handle {
     vk_config cfg;
     int device = 0;
@@ -194,7 +77,7 @@ struct vk_handle {
     int A = 0, res4_c = 0, res5_c = 0, hid = 0, emb_dim = 0;
     std::vector<void *> owned;                      // device allocations to free
 
-    // Everything a forward writes between fwd_open and fwd_close, twice (option "forward_lanes" = 2): ticket t works in
+    // Everything a forward writes between fwd_open and fwd_close, twice (option forward_lanes = 2): ticket t works in
     // sets[t & 1] on lanes[t & 1], so that consecutive forwards run beside each other on the device.  The second set is
     // taken the first time a forward begins while another is open; until then (and with one lane) every forward uses
     // sets[0] on the caller's stream.
@@ -214,7 +97,7 @@ struct vk_handle {
         hipEvent_t ev_fork = nullptr, ev_join = nullptr;
         hipEvent_t more_joins[2] = {nullptr, nullptr};
     } lanes[2];
-    int forward_lanes = kDefaults.forward_lanes;                           // option "forward_lanes" / VK_FORWARD_LANES: 1 = every forward on the caller's stream
+    int forward_lanes = 0;                           // 1 = every forward on the caller's stream
     bool two_sets = false;                           // forwards have overlapped: tickets alternate between the sets from now on
     bool two_sets_failed = false;                    // the second arena could not be allocated: one set for the rest of the handle's life
     int64_t lane_forwards = 0;                       // forwards that were enqueued on a lane's stream (vk_get_option "lane_forwards")
@@ -222,12 +105,13 @@ struct vk_handle {
     hipStream_t cur_caller = nullptr;
     const void *bbox_lin_w = nullptr;               // bbox_pred as the linear path reads it: rows padded to whole 128-row tiles
     const float *bbox_lin_b = nullptr;              // (bbox_w / bbox_b themselves when 4C is already a multiple of 128)
-    int head_chunk = kDefaults.head_chunk;                           // RoIs per Res5 chunk (vk_set_option "head_chunk")
-    int backbone_streams = kDefaults.backbone_streams;                        // 2: res3/res4 as two half-batches on two streams (option "backbone_streams")
-    int backbone_split_min_batch = kDefaults.backbone_split_min_batch;                // ... from this batch size on (option "backbone_split_min_batch")
-    int head_streams = kDefaults.head_streams;                            // 2: each Res5 chunk as two half-chunks on two streams (option "head_streams")
-    int head_split_min_rois = kDefaults.head_split_min_rois;                   // ... for chunks of at least this many RoIs (option "head_split_min_rois")
-    int head_dedupe = kDefaults.head_dedupe;                              // 1: Res5 block 0 pools and convolves each distinct RoIPool window once (option "head_dedupe")
+    // the writable options (kOptions below has their keys, defaults and ranges; vk_create sets them)
+    int head_chunk = 0;                             // RoIs per Res5 chunk, 0 = all at once
+    int backbone_streams = 0;                       // 2: res3/res4 as two half-batches on two streams
+    int backbone_split_min_batch = 0;               // ... from this batch size on
+    int head_streams = 0;                           // 2: each Res5 chunk as two half-chunks on two streams
+    int head_split_min_rois = 0;                    // ... for chunks of at least this many RoIs
+    int head_dedupe = 0;                            // 1: Res5 block 0 pools and convolves each distinct RoIPool window once
     int64_t dedupe_chunks = 0;                                            // head chunks that took that path (vk_get_option "dedupe_chunks")
     // "pooled" after a forward whose one chunk took the dedupe path: the dense tensor was never written; vk_get_stage expands
     // src[idx] into the plan's buffer the first time the stage is asked for
@@ -268,6 +152,39 @@ struct vk_handle {
     int slot_set[VK_MAX_INFLIGHT] = {-1, -1, -1, -1};                                // its working set (-1: it launched nothing)
     int64_t next_ticket = 0, oldest_open = 0;       // tickets [oldest_open, next_ticket) have not been ended
 };
+
+// The writable options (vk_set_option / vk_get_option), one row each: vk_option_check, vk_option_default, vk_set_option,
+// vk_get_option and vk_create all loop over this table.  A value is legal in [lo, hi].  `env` names the VK_* variable that
+// vk_option_default puts over the built-in default, read by one of three rules.
+enum EnvRule {
+    ENV_NONE,
+    ENV_ATOI_POSITIVE,      // atoi of the text where that is > 0 (a 0 is set with vk_set_option only)
+    ENV_FIRST_DIGIT,        // the first character, where it is a digit in [lo, hi]
+    ENV_ONE_DIGIT,          // the same, and nothing may follow it: anything else is ignored
+};
+static constexpr struct OptionRow {
+    const char *key;
+    int vk_handle::*member;
+    int def, lo, hi;
+    const char *range_msg;
+    const char *env;
+    EnvRule rule;
+} kOptions[] = {
+    {"head_chunk", &vk_handle::head_chunk, 9600, 0, INT_MAX, "head_chunk must be >= 0 (0 = all RoIs at once)", "VK_HEAD_CHUNK", ENV_ATOI_POSITIVE},
+    {"backbone_streams", &vk_handle::backbone_streams, 2, 1, 4, "backbone_streams must be 1..4", "VK_BACKBONE_STREAMS", ENV_FIRST_DIGIT},
+    {"head_streams", &vk_handle::head_streams, 1, 1, 2, "head_streams must be 1 or 2", "VK_HEAD_STREAMS", ENV_FIRST_DIGIT},
+    {"forward_lanes", &vk_handle::forward_lanes, 2, 1, 2, "forward_lanes must be 1 or 2", "VK_FORWARD_LANES", ENV_ONE_DIGIT},
+    {"head_dedupe", &vk_handle::head_dedupe, 1, 0, 1, "head_dedupe must be 0 or 1", "VK_HEAD_DEDUPE", ENV_ONE_DIGIT},
+    {"head_split_min_rois", &vk_handle::head_split_min_rois, 512, 2, INT_MAX, "head_split_min_rois must be >= 2", nullptr, ENV_NONE},
+    {"backbone_split_min_batch", &vk_handle::backbone_split_min_batch, 8, 2, INT_MAX, "backbone_split_min_batch must be >= 2", nullptr, ENV_NONE},
+};
+
+static const OptionRow *find_option(const char *key) {
+    for (const OptionRow &o : kOptions)
+        if (!strcmp(key, o.key)) return &o;
+    set_error("unknown option '%s'", key);
+    return nullptr;
+}
 
 namespace vk {
 
@@ -332,49 +249,43 @@ static const HostTensor *get_t(vk_handle *h, const std::string &name, std::vecto
     return &it->second;
 }
 
-static int finalize_conv(vk_handle *h, ConvLayer &L) {
+// The four BatchNorm tensors of the conv at `prefix`, one after the other: [weight | bias | running_mean | running_var] x cout
+static int gather_bn(vk_handle *h, const std::string &prefix, int cout, std::vector<float> &bn) {
+    const char *parts[4] = {".norm.weight", ".norm.bias", ".norm.running_mean", ".norm.running_var"};
+    bn.resize(4 * (size_t)cout);
+    for (int i = 0; i < 4; ++i) {
+        const HostTensor *t = get_t(h, prefix + parts[i], {cout});
+        if (!t) return VK_EWEIGHTS;
+        memcpy(bn.data() + (size_t)i * cout, t->data.data(), sizeof(float) * cout);
+    }
+    return VK_OK;
+}
+
+// Packed rows (BN folded, or with the layer's plain bias) + bias of one conv on the host, in the layer's precision
+static int pack_conv_host(vk_handle *h, const ConvLayer &L, std::vector<char> &packed, std::vector<float> &pb) {
     const HostTensor *w = get_t(h, L.prefix + ".weight", {L.cout, L.cin / L.groups, L.k, L.k});
     if (!w) return VK_EWEIGHTS;
     std::vector<float> bn;
-    const float *bnp = nullptr, *bias = nullptr;
+    const float *bias = nullptr;
     if (L.bn) {
-        const char *parts[4] = {".norm.weight", ".norm.bias", ".norm.running_mean", ".norm.running_var"};
-        bn.resize(4 * (size_t)L.cout);
-        for (int i = 0; i < 4; ++i) {
-            const HostTensor *t = get_t(h, L.prefix + parts[i], {L.cout});
-            if (!t) return VK_EWEIGHTS;
-            memcpy(bn.data() + (size_t)i * L.cout, t->data.data(), sizeof(float) * L.cout);
-        }
-        bnp = bn.data();
+        VK_TRY(gather_bn(h, L.prefix, L.cout, bn));
     } else {
         const HostTensor *t = get_t(h, L.prefix + ".bias", {L.cout});
         if (!t) return VK_EWEIGHTS;
         bias = t->data.data();
     }
     const vk_dtype ldt = L.dt >= 0 ? (vk_dtype)L.dt : h->dt;
-    const size_t wb = vk_packed_weight_bytes(L.cout, L.cin, L.k, L.k, L.groups, ldt);
-    std::vector<char> packed(wb);
-    std::vector<float> pb(vk_packed_cout(L.cout));
-    VK_TRY(vk_pack_conv_weight(w->data.data(), bnp, bias, L.cout, L.cin, L.k, L.k, L.groups, ldt, packed.data(), pb.data()));
-    VK_TRY(upload(h, packed.data(), wb, &L.w));
-    VK_TRY(upload(h, pb.data(), pb.size() * sizeof(float), (void **)&L.b));
-    return VK_OK;
+    packed.resize(vk_packed_weight_bytes(L.cout, L.cin, L.k, L.k, L.groups, ldt));
+    pb.resize(vk_packed_cout(L.cout));
+    return vk_pack_conv_weight(w->data.data(), L.bn ? bn.data() : nullptr, bias, L.cout, L.cin, L.k, L.k, L.groups, ldt, packed.data(), pb.data());
 }
 
-// BN-folded packed rows + bias of one conv on the host (finalize_conv without the upload)
-static int pack_conv_host(vk_handle *h, const ConvLayer &L, std::vector<char> &packed, std::vector<float> &pb) {
-    const HostTensor *w = get_t(h, L.prefix + ".weight", {L.cout, L.cin / L.groups, L.k, L.k});
-    if (!w) return VK_EWEIGHTS;
-    std::vector<float> bn(4 * (size_t)L.cout);
-    const char *parts[4] = {".norm.weight", ".norm.bias", ".norm.running_mean", ".norm.running_var"};
-    for (int i = 0; i < 4; ++i) {
-        const HostTensor *t = get_t(h, L.prefix + parts[i], {L.cout});
-        if (!t) return VK_EWEIGHTS;
-        memcpy(bn.data() + (size_t)i * L.cout, t->data.data(), sizeof(float) * L.cout);
-    }
-    packed.resize(vk_packed_weight_bytes(L.cout, L.cin, L.k, L.k, L.groups, h->dt));
-    pb.resize(vk_packed_cout(L.cout));
-    return vk_pack_conv_weight(w->data.data(), bn.data(), nullptr, L.cout, L.cin, L.k, L.k, L.groups, h->dt, packed.data(), pb.data());
+static int finalize_conv(vk_handle *h, ConvLayer &L) {
+    std::vector<char> packed;
+    std::vector<float> pb;
+    VK_TRY(pack_conv_host(h, L, packed, pb));
+    VK_TRY(upload(h, packed.data(), packed.size(), &L.w));
+    return upload(h, pb.data(), pb.size() * sizeof(float), (void **)&L.b);
 }
 
 static int finalize_block(vk_handle *h, Block &b) {
@@ -399,25 +310,6 @@ static int finalize_block(vk_handle *h, Block &b) {
     VK_TRY(upload(h, cat.data(), cat.size(), &b.conv3.w));
     VK_TRY(upload(h, b3.data(), b3.size() * sizeof(float), (void **)&b.conv3.b));
     return VK_OK;
-}
-
-static void to_dt(const float *src, size_t n, vk_dtype dt, void *dst) {
-    if (dt == VK_F16) {
-        _Float16 *d = (_Float16 *)dst;
-        for (size_t i = 0; i < n; ++i) d[i] = (_Float16)src[i];
-    } else if (dt == VK_BF16) {          // round to nearest even, like torch's float -> bfloat16
-        uint16_t *d = (uint16_t *)dst;
-        for (size_t i = 0; i < n; ++i) {
-            uint32_t u;
-            memcpy(&u, &src[i], 4);
-            if ((u & 0x7fffffffu) > 0x7f800000u)
-                d[i] = (uint16_t)((u >> 16) | 0x40);              // NaN stays NaN
-            else
-                d[i] = (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-        }
-    } else {
-        memcpy(dst, src, n * sizeof(float));
-    }
 }
 
 // ---- arena ----
@@ -483,11 +375,6 @@ struct Plan {
     int64_t *keep_ids;
     size_t total;
 };
-
-static void conv_out_hw(int H, int W, int k, int s, int p, int d, int *Ho, int *Wo) {
-    *Ho = (H + 2 * p - (d * (k - 1) + 1)) / s + 1;
-    *Wo = (W + 2 * p - (d * (k - 1) + 1)) / s + 1;
-}
 
 // R: RoI rows per image (POST_NMS_TOPK_TEST for detection, B for given boxes, Gh * Gw for a grid); D: the output width of
 // keep_ids.  whole_map (grid forward): Res5 runs over the res4 map itself, so the head buffers hold at least N * Hf * Wf
@@ -589,19 +476,29 @@ static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D, int 
     return p;
 }
 
-static ConvArgs layer_args(const vk_handle *h, const ConvLayer &L, const void *x, int N, int H, int W, const void *res, void *y,
-                           bool relu, vk_dtype out_dt, int ldy, const void *x2 = nullptr, int cin2 = 0, float *pool_part = nullptr,
-                           bool concurrent = false) {
+// What a layer's launch may set beyond the layer itself, its input and its output: name what you set, the rest stays off.
+struct ConvOpts {
+    const void *res = nullptr;      // residual, added before the ReLU
+    const void *x2 = nullptr;       // second input of a dual-source 1x1 (the block's input under a fused shortcut), cin2 channels
+    int cin2 = 0;
+    float *pool_part = nullptr;     // fused spatial mean: the per-tile column sums go here
+    bool concurrent = false;        // launched beside another stream's kernels
+    int out_dt = -1;                // -1: the layer's own precision
+    int ldy = 0;                    // 0: cout rounded up to 8
+    bool relu = false;
+};
+
+static ConvArgs layer_args(const vk_handle *h, const ConvLayer &L, const void *x, int N, int H, int W, void *y, ConvOpts o) {
     ConvArgs a;
     memset(&a, 0, sizeof(a));
-    a.concurrent = concurrent ? 1 : 0;
+    a.concurrent = o.concurrent ? 1 : 0;
     a.x = x;
-    a.x2 = x2;
-    a.Cin2 = cin2;
-    a.pool_part = pool_part;
+    a.x2 = o.x2;
+    a.Cin2 = o.cin2;
+    a.pool_part = o.pool_part;
     a.w = L.w;
     a.bias = L.b;
-    a.res = res;
+    a.res = o.res;
     a.y = y;
     a.N = N;
     a.H = H;
@@ -609,23 +506,22 @@ static ConvArgs layer_args(const vk_handle *h, const ConvLayer &L, const void *x
     a.Cin = L.cin;
     conv_out_hw(H, W, L.k, L.stride, L.pad, L.dil, &a.Ho, &a.Wo);
     a.Cout = L.cout;
-    a.ldy = ldy > 0 ? ldy : (L.cout + 7) / 8 * 8;
+    a.ldy = o.ldy > 0 ? o.ldy : (L.cout + 7) / 8 * 8;
     a.kh = a.kw = L.k;
     a.stride = L.stride;
     a.pad = L.pad;
     a.dil = L.dil;
     a.groups = L.groups;
-    a.relu = relu;
+    a.relu = o.relu;
     a.stem = 0;
     a.dt = L.dt >= 0 ? (vk_dtype)L.dt : h->dt;
-    a.out_dt = out_dt;
+    a.out_dt = o.out_dt >= 0 ? (vk_dtype)o.out_dt : a.dt;
     return a;
 }
 
-static int run_conv(vk_handle *h, const ConvLayer &L, const void *x, int N, int H, int W, const void *res, void *y,
-                    bool relu, vk_dtype out_dt, int ldy, hipStream_t s, int *Ho = nullptr, int *Wo = nullptr,
-                    const void *x2 = nullptr, int cin2 = 0, float *pool_part = nullptr, bool concurrent = false) {
-    const ConvArgs a = layer_args(h, L, x, N, H, W, res, y, relu, out_dt, ldy, x2, cin2, pool_part, concurrent);
+static int run_conv(vk_handle *h, const ConvLayer &L, const void *x, int N, int H, int W, void *y, hipStream_t s, ConvOpts o,
+                    int *Ho = nullptr, int *Wo = nullptr) {
+    const ConvArgs a = layer_args(h, L, x, N, H, W, y, o);
     if (Ho) *Ho = a.Ho;
     if (Wo) *Wo = a.Wo;
     return launch_conv(a, s);
@@ -661,15 +557,14 @@ static int run_block(vk_handle *h, const Block &b, const void *x, int N, int H, 
     }
     const void *res = x;
     if (b.has_shortcut && !b.fused_shortcut) {
-        VK_TRY(run_conv(h, b.shortcut, x, N, H, W, nullptr, sc, false, h->dt, 0, s, nullptr, nullptr, nullptr, 0, nullptr, cc));
+        VK_TRY(run_conv(h, b.shortcut, x, N, H, W, sc, s, {.concurrent = cc}));
         res = sc;
     }
-    VK_TRY(run_conv(h, b.conv1, x, N, H, W, nullptr, t1, true, h->dt, 0, s, &h1, &w1, nullptr, 0, nullptr, cc));
-    VK_TRY(run_conv(h, b.conv2, t1, N, h1, w1, nullptr, t2, true, h->dt, 0, s, &h2, &w2, nullptr, 0, nullptr, cc));
+    VK_TRY(run_conv(h, b.conv1, x, N, H, W, t1, s, {.concurrent = cc, .relu = true}, &h1, &w1));
+    VK_TRY(run_conv(h, b.conv2, t1, N, h1, w1, t2, s, {.concurrent = cc, .relu = true}, &h2, &w2));
     if (b.fused_shortcut)      // stride-1 block: t2 and x cover the same pixels
-        return run_conv(h, b.conv3, t2, N, h2, w2, nullptr, y, true, h->dt, 0, s, Ho, Wo, x, b.shortcut.cin, pool_part, cc);
-    VK_TRY(run_conv(h, b.conv3, t2, N, h2, w2, res, y, true, h->dt, 0, s, Ho, Wo, nullptr, 0, pool_part, cc));
-    return VK_OK;
+        return run_conv(h, b.conv3, t2, N, h2, w2, y, s, {.x2 = x, .cin2 = b.shortcut.cin, .pool_part = pool_part, .concurrent = cc, .relu = true}, Ho, Wo);
+    return run_conv(h, b.conv3, t2, N, h2, w2, y, s, {.res = res, .pool_part = pool_part, .concurrent = cc, .relu = true}, Ho, Wo);
 }
 
 static void set_stage(vk_handle *h, const char *name, const void *ptr, vk_dtype dt, std::initializer_list<int64_t> shape) {
@@ -685,304 +580,6 @@ static void set_stage(vk_handle *h, const char *name, const void *ptr, vk_dtype 
 
 extern "C" {
 
-const char *vk_last_error(void) { return g_err; }
-int vk_version(void) { return 1; }
-
-int vk_packed_cout(int cout) { return (cout + CONV_COUT_ALIGN - 1) / CONV_COUT_ALIGN * CONV_COUT_ALIGN; }
-
-int vk_conv_slice_channels(int cin, int groups) {
-    if (groups <= 1) return cin;
-    if (cin <= 0 || cin % groups != 0) return -1;
-    const int cpg = cin / groups;
-    if (cpg & (cpg - 1)) return -1;                     // power of two: slices and groups nest
-    return std::min(std::max(cpg, 64), cin);
-}
-
-size_t vk_packed_weight_bytes(int cout, int cin, int kh, int kw, int groups, vk_dtype dt) {
-    const int sw = vk_conv_slice_channels(cin, groups);
-    return sw <= 0 ? 0 : (size_t)vk_packed_cout(cout) * kh * kw * sw * dtype_size(dt);
-}
-
-int vk_pack_conv_weight(const float *w, const float *bn, const float *bias, int cout, int cin, int kh, int kw, int groups,
-                        vk_dtype dt, void *w_packed, float *bias_packed) {
-    VK_REQUIRE(dt == VK_F16 || dt == VK_F32 || dt == VK_BF16, VK_EINVAL, "pack: dtype must be f16, bf16 or f32");
-    VK_REQUIRE(groups >= 1, VK_EINVAL, "pack: groups=%d", groups);
-    const int sw = vk_conv_slice_channels(cin, groups);     // K channels per tap in the packed row (== cin when dense)
-    VK_REQUIRE(sw > 0, VK_EINVAL, "pack: cin=%d / groups=%d must be a power of two", cin, groups);
-    VK_REQUIRE(groups == 1 || cin == cout, VK_EINVAL, "pack: grouped convolution needs cin == cout (got %d, %d)", cin, cout);
-    VK_REQUIRE((sw * (int)dtype_size(dt)) % CONV_KTILE_BYTES == 0, VK_EINVAL,
-               "pack: %d channels per tap is not a whole number of 128-byte K-tiles for this dtype", sw);
-    const int cp = vk_packed_cout(cout);
-    const int cpg = cin / groups;                           // input channels of one group (= row length of w_oihw)
-    const size_t K = (size_t)kh * kw * sw;
-    std::vector<float> row(K);
-    for (int co = 0; co < cp; ++co) {
-        double s = 1.0;
-        float b = 0.f;
-        std::fill(row.begin(), row.end(), 0.f);
-        if (co < cout) {
-            if (bn) {   // eval BatchNorm folded into the conv: eps 1e-5 (nn.BatchNorm2d default)
-                const double g = bn[co], be = bn[cout + co], mu = bn[2 * (size_t)cout + co], var = bn[3 * (size_t)cout + co];
-                s = g / std::sqrt(var + 1e-5);
-                b = (float)(be - mu * s);
-            } else if (bias) {
-                b = bias[co];
-            }
-            // the slice this channel's 64-wide output tile reads starts at slice0; its own group at g0
-            const int slice0 = groups == 1 ? 0 : (co / 64 * 64) / sw * sw;
-            const int g0 = groups == 1 ? 0 : co / cpg * cpg;
-            for (int c = 0; c < cpg; ++c)
-                for (int y = 0; y < kh; ++y)
-                    for (int x = 0; x < kw; ++x)
-                        row[((size_t)y * kw + x) * sw + (g0 + c - slice0)] =
-                            (float)((double)w[(((size_t)co * cpg + c) * kh + y) * kw + x] * s);
-        }
-        bias_packed[co] = b;
-        to_dt(row.data(), K, dt, (char *)w_packed + (size_t)co * K * dtype_size(dt));
-    }
-    return VK_OK;
-}
-
-size_t vk_packed_stem_bytes(int cout, vk_dtype dt) {
-    const int ktiles = dt == VK_F16 ? 4 : 7;
-    return (size_t)vk_packed_cout(cout) * ktiles * CONV_KTILE_BYTES;
-}
-
-int vk_pack_stem_weight(const float *w, const float *bn, int cout, vk_dtype dt, void *w_packed, float *bias_packed) {
-    VK_REQUIRE(dt == VK_F16 || dt == VK_F32, VK_EINVAL, "pack_stem: dtype must be f16 or f32");
-    const int cp = vk_packed_cout(cout);
-    const int ktiles = dt == VK_F16 ? 4 : 7;
-    const size_t K = (size_t)ktiles * CONV_KTILE_BYTES / dtype_size(dt);   // 256 (f16) / 224 (f32)
-    std::vector<float> row(K);
-    for (int co = 0; co < cp; ++co) {
-        std::fill(row.begin(), row.end(), 0.f);
-        float b = 0.f;
-        if (co < cout) {
-            double s = 1.0;
-            if (bn) {
-                const double g = bn[co], be = bn[cout + co], mu = bn[2 * (size_t)cout + co], var = bn[3 * (size_t)cout + co];
-                s = g / std::sqrt(var + 1e-5);
-                b = (float)(be - mu * s);
-            }
-            for (int c = 0; c < 3; ++c)
-                for (int y = 0; y < 7; ++y)
-                    for (int x = 0; x < 7; ++x)   // K index = kernel row * 32 + (kernel col * 4 + channel)
-                        row[(size_t)y * 32 + x * 4 + c] = (float)((double)w[(((size_t)co * 3 + c) * 7 + y) * 7 + x] * s);
-        }
-        bias_packed[co] = b;
-        to_dt(row.data(), K, dt, (char *)w_packed + (size_t)co * K * dtype_size(dt));
-    }
-    return VK_OK;
-}
-
-// The layer of a stage-level launch as the dispatcher sees it: the one place vk_conv2d, vk_conv1x1_dual, vk_linear,
-// vk_conv1x1_meanpool and vk_conv_route build their ConvArgs, so what the query describes is what the launch passes.  The
-// pointers (and Cin2 with x2) are the caller's to set.
-static void fill_conv_args(ConvArgs &a, int N, int H, int W, int cin, int cout, int ldy, int k, int stride, int pad, int dil, int groups,
-                           int relu, vk_dtype dt, vk_dtype out_dt) {
-    memset(&a, 0, sizeof(a));
-    a.N = N;
-    a.H = H;
-    a.W = W;
-    a.Cin = cin;
-    conv_out_hw(H, W, k, stride, pad, dil, &a.Ho, &a.Wo);
-    a.Cout = cout;
-    a.ldy = ldy;
-    a.kh = a.kw = k;
-    a.stride = stride;
-    a.pad = pad;
-    a.dil = dil;
-    a.groups = groups;
-    a.relu = relu;
-    a.dt = dt;
-    a.out_dt = out_dt;
-}
-
-int vk_conv2d(const void *x, int N, int H, int W, int cin, const void *w_packed, const float *bias_packed,
-              const void *residual, void *y, int cout, int ldy, int kh, int kw, int stride, int pad, int dil, int groups,
-              int relu, vk_dtype dt, vk_dtype out_dt, void *stream) {
-    VK_REQUIRE(kh == kw && kh >= 1 && stride >= 1 && dil >= 1 && pad >= 0 && groups >= 1, VK_EINVAL, "conv2d: bad geometry");
-    ConvArgs a;
-    fill_conv_args(a, N, H, W, cin, cout, ldy, kh, stride, pad, dil, groups, relu, dt, out_dt);
-    VK_REQUIRE(a.Ho > 0 && a.Wo > 0 && N > 0, VK_EINVAL, "conv2d: empty output");
-    a.x = x;
-    a.w = w_packed;
-    a.bias = bias_packed;
-    a.res = residual;
-    a.y = y;
-    return launch_conv(a, (hipStream_t)stream);
-}
-
-int vk_conv_route(int N, int H, int W, int cin, int cin2, int has_residual, int fused_mean, int cout, int ldy, int kh, int kw,
-                  int stride, int pad, int dil, int groups, int relu, vk_dtype dt, vk_dtype out_dt) {
-    if (!(kh == kw && kh >= 1 && stride >= 1 && dil >= 1 && pad >= 0 && groups >= 1 && cin2 >= 0)) {
-        set_error("conv_route: bad geometry");
-        return -VK_EINVAL;
-    }
-    static const char here = 0;              // the rules only ask whether a pointer is set
-    ConvArgs a;
-    fill_conv_args(a, N, H, W, cin, cout, ldy, kh, stride, pad, dil, groups, relu, dt, out_dt);
-    if (!(a.Ho > 0 && a.Wo > 0 && N > 0)) {
-        set_error("conv_route: empty output");
-        return -VK_EINVAL;
-    }
-    a.x = a.w = &here;
-    a.res = has_residual ? &here : nullptr;
-    a.x2 = cin2 > 0 ? &here : nullptr;
-    a.Cin2 = cin2;
-    a.pool_part = fused_mean ? (float *)&here : nullptr;
-    return conv_route_checked(a);
-}
-
-int vk_panel_phase_images(int N, int H, int W, int dil) {
-    ConvArgs a;
-    fill_conv_args(a, N, H, W, 128, 256, 256, 3, 1, dil, dil, 1, 0, VK_F16, VK_F16);
-    return conv3x3_panel_phase_images(a);
-}
-
-int vk_conv1x1_dual(const void *x1, int cin1, const void *x2, int cin2, long M, const void *w_packed, const float *bias_packed,
-                    const void *residual, void *y, int cout, int relu, void *stream) {
-    VK_REQUIRE(x1 && x2 && M > 0 && M < (1L << 31), VK_EINVAL, "conv1x1_dual: bad arguments");
-    ConvArgs a;
-    fill_conv_args(a, 1, 1, (int)M, cin1, cout, cout, 1, 1, 0, 1, 1, relu, VK_F16, VK_F16);
-    a.x = x1;
-    a.x2 = x2;
-    a.Cin2 = cin2;
-    a.w = w_packed;
-    a.bias = bias_packed;
-    a.res = residual;
-    a.y = y;
-    return launch_conv(a, (hipStream_t)stream);
-}
-
-int vk_conv1x1_rows(const void *x1, int cin1, const void *x2, int cin2, long M, const int32_t *m_dev, const int32_t *x2_idx,
-                    const void *w_packed, const float *bias_packed, void *y, int cout, int relu, void *stream) {
-    VK_REQUIRE(x1 && w_packed && bias_packed && y && M > 0 && M < (1L << 31), VK_EINVAL, "conv1x1_rows: bad arguments");
-    VK_REQUIRE(!x2_idx || x2, VK_EINVAL, "conv1x1_rows: a row index needs a second input");
-    ConvArgs a;
-    fill_conv_args(a, 1, 1, (int)M, cin1, cout, cout, 1, 1, 0, 1, 1, relu, VK_F16, VK_F16);
-    a.x = x1;
-    a.x2 = x2;
-    a.Cin2 = x2 ? cin2 : 0;
-    a.w = w_packed;
-    a.bias = bias_packed;
-    a.y = y;
-    VK_REQUIRE(conv_route(a) == VK_ROUTE_GEMM4, VK_EINVAL, "conv1x1_rows: the layer does not run as VK_ROUTE_GEMM4 at %ld rows", M);
-    a.m_dev = m_dev;
-    a.x2_idx = x2_idx;
-    return launch_conv_gemm4(a, (hipStream_t)stream);
-}
-
-int vk_linear(const void *x, long M, int K, const void *w_packed, const float *bias_packed, const void *residual, void *y, int N, int ldy,
-              int act, vk_dtype dt, vk_dtype out_dt, void *stream) {
-    VK_REQUIRE(x && w_packed && bias_packed && y && M > 0 && M < (1L << 31), VK_EINVAL, "linear: bad arguments");
-    ConvArgs a;
-    fill_conv_args(a, 1, 1, (int)M, K, N, ldy, 1, 1, 0, 1, 1, act, dt, out_dt);
-    a.x = x;
-    a.w = w_packed;
-    a.bias = bias_packed;
-    a.res = residual;
-    a.y = y;
-    return launch_conv(a, (hipStream_t)stream);
-}
-
-// The fused-shortcut rule is restated in oracle/frcnn_oracle.py (fp16 emulation): keep the two in step.
-int vk_fuse_shortcut(int cin, int cin_shortcut, int cout, int stride, vk_dtype dt) {
-    static const bool off = getenv("VK_NO_FUSED_SHORTCUT") != nullptr;      // A/B switch
-    return !off && dt == VK_F16 && stride == 1 && cout % 256 == 0 && cin % 32 == 0 && cin_shortcut % 32 == 0;
-}
-
-int vk_bottleneck64_eligible(int cin, int cmid, int cout, int stride, int dil, int groups, int proj, int fused_shortcut, long N,
-                             int H, int W, vk_dtype dt) {
-    return stride == 1 && dil == 1 && (!proj || fused_shortcut) &&
-           bneck_fused_eligible(cin, cmid, cout, stride, groups, proj != 0, N, H, W, dt);
-}
-
-int vk_bottleneck64(const void *x, int N, int H, int W, int cin, int proj, const void *w1, const float *b1, const void *w2,
-                    const float *b2, const void *w3, const float *b3, void *y, void *stream) {
-    VK_REQUIRE(x && w1 && b1 && w2 && b2 && w3 && b3 && y && N > 0 && H > 0 && W > 0, VK_EINVAL, "bottleneck64: bad arguments");
-    VK_REQUIRE((cin == 256 && !proj) || (cin == 64 && proj), VK_EINVAL, "bottleneck64: cin must be 256 (identity) or 64 (projection)");
-    VK_REQUIRE(bneck_fused_eligible(cin, 64, 256, 1, 1, proj != 0, N, H, W, VK_F16) || getenv("VK_BNECK_FUSED"), VK_EINVAL,
-               "bottleneck64: tensor beyond the 32-bit byte offsets");
-    VK_REQUIRE((long)N * H * W * 512 < (1L << 32) - (1L << 20), VK_EINVAL, "bottleneck64: tensor beyond the 32-bit byte offsets");
-    return launch_bneck_fused(x, N, H, W, cin, proj != 0, w1, b1, w2, b2, w3, b3, y, false, (hipStream_t)stream);
-}
-
-size_t vk_conv1x1_meanpool_workspace_bytes(int N, int HW, int cout) { return conv_duo_pool_part_bytes((long)N * HW, cout); }
-
-int vk_conv1x1_meanpool(const void *x, int N, int HW, int cin, const void *w_packed, const float *bias_packed,
-                        const void *residual, int cout, int relu, float *out_mean, void *workspace, size_t workspace_bytes,
-                        void *stream) {
-    VK_REQUIRE(x && out_mean && workspace && N > 0 && HW > 0, VK_EINVAL, "conv1x1_meanpool: bad arguments");
-    VK_REQUIRE(workspace_bytes >= vk_conv1x1_meanpool_workspace_bytes(N, HW, cout), VK_EINVAL, "conv1x1_meanpool: workspace too small");
-    ConvArgs a;
-    fill_conv_args(a, N, 1, HW, cin, cout, cout, 1, 1, 0, 1, 1, relu, VK_F16, VK_F16);
-    a.x = x;
-    a.w = w_packed;
-    a.bias = bias_packed;
-    a.res = residual;
-    a.pool_part = (float *)workspace;
-    VK_TRY(launch_conv(a, (hipStream_t)stream));
-    return launch_pool_finish((const float *)workspace, N, HW, cin, cout, false, out_mean, (hipStream_t)stream);
-}
-
-static void stem_geom(int H, int W, int *H1, int *W1, int *Hp, int *Wp) {
-    conv_out_hw(H, W, 7, 2, 3, 1, H1, W1);
-    *Hp = std::max(H + 6, 2 * *H1 + 6);
-    *Wp = (std::max(W + 6, 2 * *W1 + 6) + 1) & ~1;
-}
-
-size_t vk_stem_workspace_bytes(int N, int H, int W, int cout, vk_dtype dt) {
-    int H1, W1, Hp, Wp;
-    stem_geom(H, W, &H1, &W1, &Hp, &Wp);
-    return align_up((size_t)N * Hp * Wp * 4 * dtype_size(dt), 256) + align_up((size_t)N * H1 * W1 * cout * dtype_size(dt), 256);
-}
-
-static int stem_impl(const float *x, int N, int H, int W, const void *w, const float *b, int cout, int caffe, void *y,
-                     vk_dtype dt, void *img_pad, void *stem_out, hipStream_t s, int32_t *nonfinite = nullptr) {
-    int H1, W1, Hp, Wp;
-    stem_geom(H, W, &H1, &W1, &Hp, &Wp);
-    VK_TRY(launch_stem_pack(x, img_pad, N, H, W, Hp, Wp, dt, s, nonfinite));
-    if (stem_pool_eligible(cout, dt)) return launch_stem_pool(img_pad, N, Hp, Wp, H1, W1, w, b, caffe, y, s);
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = img_pad;
-    a.w = w;
-    a.bias = b;
-    a.y = stem_out;
-    a.N = N;
-    a.H = Hp;
-    a.W = Wp;
-    a.Cin = 4;
-    a.Ho = H1;
-    a.Wo = W1;
-    a.Cout = cout;
-    a.ldy = (cout + 7) / 8 * 8;
-    a.kh = a.kw = 7;
-    a.stride = 2;
-    a.pad = 0;
-    a.dil = 1;
-    a.relu = 1;
-    a.stem = 1;
-    a.dt = a.out_dt = dt;
-    VK_TRY(launch_conv(a, s));
-    return launch_maxpool(stem_out, y, N, H1, W1, cout, caffe, dt, s);
-}
-
-int vk_stem(const float *x, int N, int H, int W, const void *w_packed, const float *bias_packed, int cout,
-            int caffe_maxpool, void *y, vk_dtype dt, void *workspace, size_t workspace_bytes, void *stream) {
-    VK_REQUIRE(dt == VK_F16 || dt == VK_F32, VK_EINVAL, "stem: bad dtype");
-    VK_REQUIRE(cout % 8 == 0, VK_EINVAL, "stem: cout must be a multiple of 8");
-    VK_REQUIRE(H >= 16 && W >= 16, VK_EINVAL, "stem: image %dx%d too small", H, W);
-    VK_REQUIRE(workspace && workspace_bytes >= vk_stem_workspace_bytes(N, H, W, cout, dt), VK_EINVAL, "stem: workspace too small");
-    int H1, W1, Hp, Wp;
-    stem_geom(H, W, &H1, &W1, &Hp, &Wp);
-    char *img_pad = (char *)workspace;
-    char *stem_out = img_pad + align_up((size_t)N * Hp * Wp * 4 * dtype_size(dt), 256);
-    return stem_impl(x, N, H, W, w_packed, bias_packed, cout, caffe_maxpool, y, dt, img_pad, stem_out, (hipStream_t)stream);
-}
-
-// ---------------------------------------------------------------------------
 int vk_create(const vk_config *cfg, int device, vk_handle **out) {
     VK_REQUIRE(cfg && out, VK_EINVAL, "create: null argument");
     VK_REQUIRE(cfg->depth == 50 || cfg->depth == 101 || cfg->depth == 152, VK_EINVAL, "create: depth %d unsupported", cfg->depth);
@@ -1008,11 +605,7 @@ int vk_create(const vk_config *cfg, int device, vk_handle **out) {
     h->device = device;
     h->dt = (vk_dtype)cfg->precision;
     if (getenv("VK_PREDICTOR_FP16")) h->pdt = h->dt;            // A/B switch: round 1's 16-bit predictor
-    (void)vk_option_default("head_chunk", &h->head_chunk);              // the built-in defaults or the VK_* variables
-    (void)vk_option_default("backbone_streams", &h->backbone_streams);
-    (void)vk_option_default("head_streams", &h->head_streams);
-    (void)vk_option_default("forward_lanes", &h->forward_lanes);
-    (void)vk_option_default("head_dedupe", &h->head_dedupe);
+    for (const OptionRow &o : kOptions) (void)vk_option_default(o.key, &(h->*o.member));     // the built-in defaults or the VK_* variables
     const int di = cfg->depth == 50 ? 0 : (cfg->depth == 101 ? 1 : 2);
     add_conv_names(h->names, "backbone.stem.conv1", true);
     h->stem = ConvLayer{"backbone.stem.conv1", 3, cfg->stem_out_channels, 7, 2, 3, 1, true, true};
@@ -1111,13 +704,8 @@ int vk_finalize(vk_handle *h) {
     {
         const HostTensor *w = get_t(h, "backbone.stem.conv1.weight", {c.stem_out_channels, 3, 7, 7});
         if (!w) return VK_EWEIGHTS;
-        std::vector<float> bn(4 * (size_t)c.stem_out_channels);
-        const char *parts[4] = {".norm.weight", ".norm.bias", ".norm.running_mean", ".norm.running_var"};
-        for (int i = 0; i < 4; ++i) {
-            const HostTensor *t = get_t(h, std::string("backbone.stem.conv1") + parts[i], {c.stem_out_channels});
-            if (!t) return VK_EWEIGHTS;
-            memcpy(bn.data() + (size_t)i * c.stem_out_channels, t->data.data(), sizeof(float) * c.stem_out_channels);
-        }
+        std::vector<float> bn;
+        VK_TRY(gather_bn(h, "backbone.stem.conv1", c.stem_out_channels, bn));
         std::vector<char> packed(vk_packed_stem_bytes(c.stem_out_channels, h->dt));
         std::vector<float> pb(vk_packed_cout(c.stem_out_channels));
         VK_TRY(vk_pack_stem_weight(w->data.data(), bn.data(), c.stem_out_channels, h->dt, packed.data(), pb.data()));
@@ -1180,65 +768,38 @@ int vk_finalize(vk_handle *h) {
 
 int vk_option_check(const char *key, int value) {
     VK_REQUIRE(key, VK_EINVAL, "option: null key");
-    if (!strcmp(key, "head_chunk")) {
-        VK_REQUIRE(value >= 0, VK_EINVAL, "head_chunk must be >= 0 (0 = all RoIs at once)");
-    } else if (!strcmp(key, "backbone_streams")) {
-        VK_REQUIRE(value >= 1 && value <= 4, VK_EINVAL, "backbone_streams must be 1..4");
-    } else if (!strcmp(key, "head_streams")) {
-        VK_REQUIRE(value == 1 || value == 2, VK_EINVAL, "head_streams must be 1 or 2");
-    } else if (!strcmp(key, "forward_lanes")) {
-        VK_REQUIRE(value == 1 || value == 2, VK_EINVAL, "forward_lanes must be 1 or 2");
-    } else if (!strcmp(key, "head_dedupe")) {
-        VK_REQUIRE(value == 0 || value == 1, VK_EINVAL, "head_dedupe must be 0 or 1");
-    } else if (!strcmp(key, "head_split_min_rois")) {
-        VK_REQUIRE(value >= 2, VK_EINVAL, "head_split_min_rois must be >= 2");
-    } else if (!strcmp(key, "backbone_split_min_batch")) {
-        VK_REQUIRE(value >= 2, VK_EINVAL, "backbone_split_min_batch must be >= 2");
-    } else {
-        VK_REQUIRE(false, VK_EINVAL, "unknown option '%s'", key);
-    }
+    const OptionRow *o = find_option(key);
+    if (!o) return VK_EINVAL;
+    VK_REQUIRE(value >= o->lo && value <= o->hi, VK_EINVAL, "%s", o->range_msg);
     return VK_OK;
 }
 
 int vk_option_default(const char *key, int *value) {
     VK_REQUIRE(key && value, VK_EINVAL, "option: null argument");
-    if (!strcmp(key, "head_chunk")) {
-        const char *env = getenv("VK_HEAD_CHUNK");
-        *value = env && atoi(env) > 0 ? atoi(env) : kDefaults.head_chunk;          // (0 is set with vk_set_option only)
-    } else if (!strcmp(key, "backbone_streams")) {
-        const char *bs = getenv("VK_BACKBONE_STREAMS");
-        *value = bs && bs[0] >= '1' && bs[0] <= '4' ? bs[0] - '0' : kDefaults.backbone_streams;
-    } else if (!strcmp(key, "head_streams")) {
-        const char *hs = getenv("VK_HEAD_STREAMS");
-        *value = hs && (hs[0] == '1' || hs[0] == '2') ? hs[0] - '0' : kDefaults.head_streams;
-    } else if (!strcmp(key, "forward_lanes")) {     // "1" or "2" exactly; anything else is ignored
-        const char *fl = getenv("VK_FORWARD_LANES");
-        *value = fl && (fl[0] == '1' || fl[0] == '2') && !fl[1] ? fl[0] - '0' : kDefaults.forward_lanes;
-    } else if (!strcmp(key, "head_dedupe")) {       // "0" or "1" exactly; anything else is ignored
-        const char *hd = getenv("VK_HEAD_DEDUPE");
-        *value = hd && (hd[0] == '0' || hd[0] == '1') && !hd[1] ? hd[0] - '0' : kDefaults.head_dedupe;
-    } else if (!strcmp(key, "head_split_min_rois")) {
-        *value = kDefaults.head_split_min_rois;
-    } else if (!strcmp(key, "backbone_split_min_batch")) {
-        *value = kDefaults.backbone_split_min_batch;
-    } else {
-        VK_REQUIRE(false, VK_EINVAL, "unknown option '%s'", key);
+    const OptionRow *o = find_option(key);
+    if (!o) return VK_EINVAL;
+    *value = o->def;
+    const char *env = o->env ? getenv(o->env) : nullptr;
+    if (!env) return VK_OK;
+    if (o->rule == ENV_ATOI_POSITIVE) {
+        if (atoi(env) > 0) *value = atoi(env);
+    } else if (env[0] >= '0' + o->lo && env[0] <= '0' + o->hi && (o->rule == ENV_FIRST_DIGIT || !env[1])) {
+        *value = env[0] - '0';
     }
     return VK_OK;
 }
 
 int vk_get_option(vk_handle *h, const char *key, int *value) {
     VK_REQUIRE(h && key && value, VK_EINVAL, "get_option: null argument");
-    if (!strcmp(key, "head_chunk")) *value = h->head_chunk;
-    else if (!strcmp(key, "backbone_streams")) *value = h->backbone_streams;
-    else if (!strcmp(key, "head_streams")) *value = h->head_streams;
-    else if (!strcmp(key, "forward_lanes")) *value = h->forward_lanes;
-    else if (!strcmp(key, "head_dedupe")) *value = h->head_dedupe;
-    else if (!strcmp(key, "dedupe_chunks")) *value = (int)std::min<int64_t>(h->dedupe_chunks, INT32_MAX);   // read-only: head chunks that took the dedupe path
-    else if (!strcmp(key, "head_split_min_rois")) *value = h->head_split_min_rois;
-    else if (!strcmp(key, "backbone_split_min_batch")) *value = h->backbone_split_min_batch;
-    else if (!strcmp(key, "working_sets")) *value = (h->sets[0].arena ? 1 : 0) + (h->sets[1].arena ? 1 : 0);   // read-only: arenas held
-    else if (!strcmp(key, "lane_forwards")) *value = (int)std::min<int64_t>(h->lane_forwards, INT32_MAX);    // read-only: forwards enqueued on a lane's stream
+    for (const OptionRow &o : kOptions)
+        if (!strcmp(key, o.key)) {
+            *value = h->*o.member;
+            return VK_OK;
+        }
+    // read-only
+    if (!strcmp(key, "dedupe_chunks")) *value = (int)std::min<int64_t>(h->dedupe_chunks, INT32_MAX);      // head chunks that took the dedupe path
+    else if (!strcmp(key, "working_sets")) *value = (h->sets[0].arena ? 1 : 0) + (h->sets[1].arena ? 1 : 0);   // arenas held
+    else if (!strcmp(key, "lane_forwards")) *value = (int)std::min<int64_t>(h->lane_forwards, INT32_MAX);    // forwards enqueued on a lane's stream
     else VK_REQUIRE(false, VK_EINVAL, "unknown option '%s'", key);
     return VK_OK;
 }
@@ -1246,13 +807,7 @@ int vk_get_option(vk_handle *h, const char *key, int *value) {
 int vk_set_option(vk_handle *h, const char *key, int value) {
     VK_REQUIRE(h && key, VK_EINVAL, "set_option: null argument");
     VK_TRY(vk_option_check(key, value));
-    if (!strcmp(key, "head_chunk")) h->head_chunk = value;
-    if (!strcmp(key, "backbone_streams")) h->backbone_streams = value;
-    if (!strcmp(key, "head_streams")) h->head_streams = value;
-    if (!strcmp(key, "forward_lanes")) h->forward_lanes = value;
-    if (!strcmp(key, "head_dedupe")) h->head_dedupe = value;
-    if (!strcmp(key, "head_split_min_rois")) h->head_split_min_rois = value;
-    if (!strcmp(key, "backbone_split_min_batch")) h->backbone_split_min_batch = value;
+    h->*find_option(key)->member = value;
     return VK_OK;
 }
 
@@ -1306,12 +861,6 @@ int vk_get_stage_timing(vk_handle *h, float *ms6) {
     return VK_OK;
 }
 
-int vk_memcpy_d2d(void *dst_dev, const void *src_dev, size_t bytes, void *stream) {
-    VK_REQUIRE(dst_dev && src_dev, VK_EINVAL, "memcpy_d2d: null pointer");
-    VK_CHECK_HIP(hipMemcpyAsync(dst_dev, src_dev, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return VK_OK;
-}
-
 int vk_get_stage(vk_handle *h, const char *name, const void **dev_ptr, vk_dtype *dtype, int64_t *shape, int *ndim) {
     VK_REQUIRE(h && name && dev_ptr && dtype && shape && ndim, VK_EINVAL, "null argument");
     auto it = h->stages_out.find(name);
@@ -1359,34 +908,37 @@ static int ensure_ticket_state(vk_handle *h) {
     return VK_OK;
 }
 
-// One working set's arena of at least `bytes`.  Growing frees the old block after hipDeviceSynchronize, which also waits
-// for a forward in flight on the other set (it keeps its own block).  soft: a failed allocation is reported as 1 with
-// the HIP error cleared, not as an error.
-static int ensure_arena(vk_handle *h, int set, size_t bytes, bool soft) {
-    vk_handle::WorkSet &ws = h->sets[set];
-    if (bytes <= ws.arena_bytes) return VK_OK;
-    if (ws.arena) {
+// A device block of at least `need` bytes: the arenas of a working set grow through this.  Growing frees the old block after
+// hipDeviceSynchronize, which also waits for a forward in flight on the other set (it keeps its own blocks).  soft: a failed
+// allocation is reported as 1 with the HIP error cleared, not as an error.
+static int grow_device_block(char **p, size_t *bytes, size_t need, bool soft) {
+    if (need <= *bytes) return VK_OK;
+    if (*p) {
         VK_CHECK_HIP(hipDeviceSynchronize());
-        VK_CHECK_HIP(hipFree(ws.arena));
-        ws.arena = nullptr;
-        ws.arena_bytes = 0;
+        VK_CHECK_HIP(hipFree(*p));
+        *p = nullptr;
+        *bytes = 0;
     }
     if (soft) {
-        if (hipMalloc((void **)&ws.arena, bytes) != hipSuccess) {
+        if (hipMalloc((void **)p, need) != hipSuccess) {
             (void)hipGetLastError();
-            ws.arena = nullptr;
+            *p = nullptr;
             return 1;
         }
     } else {
-        VK_CHECK_HIP(hipMalloc((void **)&ws.arena, bytes));
+        VK_CHECK_HIP(hipMalloc((void **)p, need));
     }
-    ws.arena_bytes = bytes;
+    *bytes = need;
     return VK_OK;
+}
+
+static int ensure_arena(vk_handle *h, int set, size_t bytes, bool soft) {
+    return grow_device_block(&h->sets[set].arena, &h->sets[set].arena_bytes, bytes, soft);
 }
 
 // Where the forward that is about to be enqueued (ticket h->next_ticket) runs: its working set (h->cur_set, with an arena
 // of arena_need bytes) and its stream (*s_out).
-// One lane (option "forward_lanes" = 1, timers on, no forward has overlapped another yet, or the second arena did not fit):
+// One lane (option forward_lanes = 1, timers on, no forward has overlapped another yet, or the second arena did not fit):
 // set 0 on the caller's stream, as a handle with one arena does.  The per-launch and per-stage timers need this: their
 // event pairs bracket launches whose durations must not overlap.
 // Two lanes: ticket t takes set t & 1 and the lane's own stream, which waits for the caller's stream as it stands now
@@ -1504,7 +1056,7 @@ static int fwd_backbone(vk_handle *h, const Plan &p, const float *images_dev, hi
     int ch = p.Hs[0], cw = p.Ws[0];
     // res4 at batch 32 is 2.05 rounds of tiles on 256 CUs: every N = 256 layer pays 3 rounds.  Its two half-batches run on
     // two streams, so the tail of one half's layer k overlaps the other half's layer k (images are independent; the
-    // halves touch disjoint parts of every buffer).  Option "backbone_streams" = 1 / VK_BACKBONE_STREAMS=1 disables it.
+    // halves touch disjoint parts of every buffer).  Option backbone_streams = 1 / VK_BACKBONE_STREAMS=1 disables it.
     for (int st = 0; st < 3; ++st) {
         const bool split = h->backbone_streams >= 2 && st >= 1 && N >= h->backbone_streams && N >= h->backbone_split_min_batch && h->dt == VK_F16;
         const int ns = split ? h->backbone_streams : 1;      // image groups, one stream each
@@ -1567,12 +1119,12 @@ static int head_block0_dedupe(vk_handle *h, const Plan &p, const void *res4, int
     void *pooled_u = p.h_sc, *t1_u = p.h_t2;
     VK_TRY(vk_roi_windows(p.rois + 5 * (size_t)k0, kc, p.N, p.Hf, p.Wf, P, 1.0f / 16.0f, p.dd_idx, p.dd_win, u, p.dd_ws, p.dd_ws_bytes, s));
     VK_TRY(vk_roi_pool_windows(res4, p.N, p.Hf, p.Wf, h->res4_c, p.dd_win, u, (int)rows, pooled_u, h->dt, s));
-    ConvArgs a1 = layer_args(h, b.conv1, pooled_u, 1, 1, (int)rows, nullptr, t1_u, true, h->dt, 0);
+    ConvArgs a1 = layer_args(h, b.conv1, pooled_u, 1, 1, (int)rows, t1_u, {.relu = true});
     a1.m_dev = u;
     VK_TRY(launch_conv_gemm4(a1, s));
     VK_TRY(vk_gather_rows(t1_u, p.dd_idx, rows, (int)(b.conv1.cout * es), p.h_t1, s));
-    VK_TRY(run_conv(h, b.conv2, p.h_t1, kc, P, P, nullptr, p.h_t2, true, h->dt, 0, s));
-    ConvArgs a3 = layer_args(h, b.conv3, p.h_t2, 1, 1, (int)rows, nullptr, p.h_a, true, h->dt, 0, pooled_u, b.shortcut.cin);
+    VK_TRY(run_conv(h, b.conv2, p.h_t1, kc, P, P, p.h_t2, s, {.relu = true}));
+    ConvArgs a3 = layer_args(h, b.conv3, p.h_t2, 1, 1, (int)rows, p.h_a, {.x2 = pooled_u, .cin2 = b.shortcut.cin, .relu = true});
     a3.x2_idx = p.dd_idx;
     VK_TRY(launch_conv_gemm4(a3, s));
     h->dedupe_chunks++;
@@ -1594,7 +1146,7 @@ static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s
     int dd_chunks = 0;
     for (int k0 = 0; k0 < p.K; k0 += p.chunk) {
         const int kc = std::min(p.chunk, p.K - k0);
-        // option "head_streams" = 2: the chunk's two halves run on two streams (RoIs are independent; the halves use disjoint
+        // option head_streams = 2: the chunk's two halves run on two streams (RoIs are independent; the halves use disjoint
         // rows of every head buffer).  Measured +0.9 % end to end at 9600 RoIs (tails of 58-round launches overlap); starting
         // the second half one or two layers late, so that a 3x3 MFMA loop runs beside a memory-bound 1x1 epilogue, is 1.5 %
         // SLOWER than one stream.  Off by default: it buys little and makes per-kernel durations overlap.
@@ -1612,8 +1164,8 @@ static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s
         bool dd = p.dd_idx && !split && head_dedupe_planned(h);
         if (dd) {
             const Block &b0 = h->res5[0];
-            const ConvArgs a1 = layer_args(h, b0.conv1, p.h_sc, 1, 1, kc * P * P, nullptr, p.h_t2, true, h->dt, 0);
-            const ConvArgs a3 = layer_args(h, b0.conv3, p.h_t2, 1, 1, kc * P * P, nullptr, p.h_a, true, h->dt, 0, p.h_sc, b0.shortcut.cin);
+            const ConvArgs a1 = layer_args(h, b0.conv1, p.h_sc, 1, 1, kc * P * P, p.h_t2, {.relu = true});
+            const ConvArgs a3 = layer_args(h, b0.conv3, p.h_t2, 1, 1, kc * P * P, p.h_a, {.x2 = p.h_sc, .cin2 = b0.shortcut.cin, .relu = true});
             dd = conv_route(a1) == VK_ROUTE_GEMM4 && conv_route(a3) == VK_ROUTE_GEMM4;
         }
         for (int half = 0; half < (split ? 2 : 1); ++half) {
@@ -1671,11 +1223,11 @@ static int fwd_predictor(vk_handle *h, const Plan &p, hipStream_t s) {
     const int C = c.num_classes, F = h->res5_c, E = h->emb_dim, AT = c.num_attrs;
     const int ld_cls = (C + 1 + 7) / 8 * 8, ld_attr = (AT + 1 + 7) / 8 * 8;
     VK_TRY(launch_concat_embed(p.feat, nullptr, nullptr, F, 0, p.K, p.featT, h->pdt, s));
-    VK_TRY(run_conv(h, h->cls_score, p.featT, p.K, 1, 1, nullptr, p.cls_logits, false, VK_F32, ld_cls, s));
+    VK_TRY(run_conv(h, h->cls_score, p.featT, p.K, 1, 1, p.cls_logits, s, {.out_dt = VK_F32, .ldy = ld_cls}));
     VK_TRY(launch_softmax_argmax(p.cls_logits, ld_cls, p.K, C + 1, C, p.obj_prob, p.obj_cls, p.max_class, s));
     VK_TRY(launch_concat_embed(p.feat, h->emb, p.max_class, F, E, p.K, p.concat, h->pdt, s));
-    VK_TRY(run_conv(h, h->fc_attr, p.concat, p.K, 1, 1, nullptr, p.attr_hid, true, h->pdt, 0, s));
-    VK_TRY(run_conv(h, h->attr_score, p.attr_hid, p.K, 1, 1, nullptr, p.attr_logits, false, VK_F32, ld_attr, s));
+    VK_TRY(run_conv(h, h->fc_attr, p.concat, p.K, 1, 1, p.attr_hid, s, {.relu = true}));
+    VK_TRY(run_conv(h, h->attr_score, p.attr_hid, p.K, 1, 1, p.attr_logits, s, {.out_dt = VK_F32, .ldy = ld_attr}));
     VK_TRY(launch_softmax_argmax(p.attr_logits, ld_attr, p.K, AT, AT, p.attr_prob, p.attr_cls, nullptr, s));
     set_stage(h, "obj_logits", p.cls_logits, VK_F32, {p.K, ld_cls});
     set_stage(h, "attr_logits", p.attr_logits, VK_F32, {p.K, ld_attr});
@@ -1704,6 +1256,38 @@ static int fwd_close(vk_handle *h, const int32_t *nonfinite, hipStream_t s, int6
     return VK_OK;
 }
 
+// ---- the admission checks the *_begin entry points share; `who` is the entry point's prefix in the error text.  They are
+// separate pieces because each entry point has its own order (the detection forward looks at the handle first, the other
+// two at their arguments) ----
+static int check_forward_size(const char *who, int N, int H, int W) {
+    VK_REQUIRE(N >= 1 && H >= 32 && W >= 32, VK_EINVAL, "%s: bad input size N=%d H=%d W=%d", who, N, H, W);
+    return VK_OK;
+}
+
+// image_shapes only bound the box clipping (frcnn.py:147-153); the reference does not check them
+// against the tensor size (its own adapter passes PIL (w,h) order, adapters/frcnn.py:50-52)
+static int check_image_shape(const char *who, const int32_t *image_hw, int n) {
+    VK_REQUIRE(image_hw[2 * n] >= 1 && image_hw[2 * n + 1] >= 1, VK_EINVAL, "%s: image_shapes[%d]=(%d,%d) must be positive", who, n,
+               image_hw[2 * n], image_hw[2 * n + 1]);
+    return VK_OK;
+}
+
+static int check_forward_handle(const char *who, const vk_handle *h) {
+    VK_REQUIRE(h->next_ticket - h->oldest_open < vk_handle::VK_MAX_INFLIGHT, VK_EINVAL,
+               "%s_begin: %d forwards are already in flight; end the oldest first", who, vk_handle::VK_MAX_INFLIGHT);
+    VK_REQUIRE(h->finalized, VK_EINVAL, "%s: vk_finalize has not been called", who);
+    return VK_OK;
+}
+
+// the output arrays of a forward that writes one row per box / cell
+static int check_row_outputs(const char *who, const vk_outputs *out) {
+    VK_REQUIRE(out->obj_ids && out->obj_probs && out->attr_ids && out->attr_probs && out->boxes && out->preds_per_image &&
+                   out->roi_features,
+               VK_EINVAL, "%s: null output array", who);
+    VK_REQUIRE(((uintptr_t)out->roi_features & 15) == 0, VK_EINVAL, "%s: roi_features must be 16-byte aligned", who);
+    return VK_OK;
+}
+
 struct TimerScope {   // per-launch events only inside one forward
     explicit TimerScope(KernelTimer *t) { g_timer = t; }
     ~TimerScope() { g_timer = nullptr; }
@@ -1716,27 +1300,6 @@ extern "C" {
 int vk_forward_begin(vk_handle *h, const float *images_dev, int N, int H, int W, const int32_t *image_hw,
                      const float *scales_yx, const vk_roi_params *rp, const vk_outputs *out, void *stream, int64_t *ticket) {
     return vk_forward_begin_ignorey(h, images_dev, N, H, W, image_hw, scales_yx, rp, out, stream, ticket, nullptr);
-}
-
-static int check_select_params(const vk_select_params *sp, const char *who) {
-    const vk_roi_params &rp = sp->roi;
-    VK_REQUIRE(rp.num_nms_thresh == 1, VK_EINVAL, "%s: per-class selection takes one NMS threshold, got a list of %d", who, rp.num_nms_thresh);
-    VK_REQUIRE(sp->score_thresh >= 0.0 && sp->score_thresh <= 1.0, VK_EINVAL, "%s: score_thresh=%g must be in [0, 1]", who, sp->score_thresh);
-    VK_REQUIRE(rp.min_detections <= rp.max_detections, VK_EINVAL, "%s: min_detections=%d exceeds max_detections=%d", who,
-               rp.min_detections, rp.max_detections);
-    return VK_OK;
-}
-
-static int check_detections_params(const vk_select_params *sp, const char *who) {
-    const vk_roi_params &rp = sp->roi;
-    VK_REQUIRE(rp.num_nms_thresh == 1, VK_EINVAL, "%s: the detections selection takes one NMS threshold, got a list of %d", who, rp.num_nms_thresh);
-    VK_REQUIRE(sp->score_thresh >= 0.0 && sp->score_thresh <= 1.0, VK_EINVAL, "%s: score_thresh=%g must be in [0, 1]", who, sp->score_thresh);
-    VK_REQUIRE(rp.min_detections == 0, VK_EINVAL, "%s: min_detections=%d must be 0 with the detections selection: a detector reports "
-               "nothing when nothing clears score_thresh, so there is no minimum count to fill (clear the config's MIN_DETECTIONS)",
-               who, rp.min_detections);
-    VK_REQUIRE(rp.max_detections >= 1 && rp.max_detections <= 1024, VK_EINVAL, "%s: max_detections=%d must be in 1..1024", who,
-               rp.max_detections);
-    return VK_OK;
 }
 
 // Shared by the two all-class selections (after fwd_head).  bbox_pred in the packed form of the linear path, once per handle
@@ -1763,20 +1326,6 @@ static int ensure_bbox_lin(vk_handle *h, int nrow, int F, hipStream_t s) {
     return VK_OK;
 }
 
-// a selection's own arena (WorkSet::pc_arena / det_arena), grown on need
-static int grow_select_arena(char **arena, size_t *bytes, size_t need) {
-    if (need <= *bytes) return VK_OK;
-    if (*arena) {
-        VK_CHECK_HIP(hipDeviceSynchronize());
-        VK_CHECK_HIP(hipFree(*arena));
-        *arena = nullptr;
-        *bytes = 0;
-    }
-    VK_CHECK_HIP(hipMalloc((void **)arena, need));
-    *bytes = need;
-    return VK_OK;
-}
-
 // soft-max of every class and bbox_pred over all its rows through the linear path: stages "obj_scores", "box_deltas", "attr_prob"
 static int class_scores_and_deltas(vk_handle *h, const Plan &p, float *scores, int ld_cls, float *deltas, int ld_box, int nrow,
                                    hipStream_t s) {
@@ -1796,46 +1345,13 @@ static int class_scores_and_deltas(vk_handle *h, const Plan &p, float *scores, i
     return VK_OK;
 }
 
-static void fill_select_args(PerClassArgs &a, const vk_handle *h, const Plan &p, const vk_select_params *sp, const float *scores,
-                             int ld_cls, const float *deltas, int ld_box, const float *scales_dev, const vk_outputs *out) {
+// What the two all-class selections do before their own kernel: bbox_pred in the linear form, the selection's arena grown to
+// [scores | deltas | extra_bytes of the caller's own] (256-byte aligned pieces, in that order), the scores and deltas computed
+// into it, and `a` built on them (fill_per_class_args).  *extra is where the caller's bytes start.
+static int select_open(vk_handle *h, const Plan &p, const vk_select_params *sp, const float *scales_dev, const vk_outputs *out,
+                       char **arena, size_t *arena_bytes, size_t extra_bytes, hipStream_t s, PerClassArgs &a, char **extra) {
     const vk_config &c = h->cfg;
-    memset(&a, 0, sizeof(a));
-    a.scores = scores;
-    a.ld_scores = ld_cls;
-    a.deltas = deltas;
-    a.ld_box = ld_box;
-    a.agnostic = c.cls_agnostic_bbox_reg ? 1 : 0;
-    a.proposals = p.prop_boxes;
-    a.counts = p.prop_counts;
-    a.features = p.feat;
-    a.attr_prob = p.attr_prob;
-    a.attr_cls = p.attr_cls;
-    a.F = h->res5_c;
-    a.R = p.R;
-    a.D = sp->roi.max_detections;
-    a.C = c.num_classes;
-    a.image_hw = p.image_hw;
-    a.scales_yx = scales_dev;
-    a.wx = c.roi_bbox_weights[0];
-    a.wy = c.roi_bbox_weights[1];
-    a.ww = c.roi_bbox_weights[2];
-    a.wh = c.roi_bbox_weights[3];
-    a.clampv = (float)std::log(1000.0 / 16.0);
-    a.thresh = sp->roi.nms_thresh[0];
-    a.score_thresh = sp->score_thresh;
-    a.mind = sp->roi.min_detections;
-    a.maxd = sp->roi.max_detections;
-    a.out = *out;
-    a.keep_ids = p.keep_ids;
-    a.nonfinite = p.nonfinite;
-}
-
-// The per-class end of a detection forward (after fwd_head): soft-max of every class, bbox_pred over all its rows through the
-// linear path, per-class NMS + finalize (per_class.hip).  Stages "obj_scores", "box_deltas", "max_conf", "keep_ids".
-static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp, const float *scales_dev, const vk_outputs *out,
-                         hipStream_t s) {
-    const vk_config &c = h->cfg;
-    const int C = c.num_classes, F = h->res5_c, K = p.K, D = sp->roi.max_detections;
+    const int C = c.num_classes, F = h->res5_c, K = p.K;
     const int nrow = 4 * (c.cls_agnostic_bbox_reg ? 1 : C);
     const int ld_cls = (C + 1 + 7) / 8 * 8, ld_box = (nrow + 7) / 8 * 8;
     VK_TRY(ensure_bbox_lin(h, nrow, F, s));
@@ -1844,23 +1360,34 @@ static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp
     cv.take((size_t)K * ld_cls * sizeof(float));
     const size_t o_deltas = cv.off;
     cv.take((size_t)K * ld_box * sizeof(float));
-    const size_t o_best = cv.off;
-    cv.take((size_t)K * sizeof(unsigned long long));
-    const size_t o_conf = cv.off;
-    cv.take((size_t)K * sizeof(float));
-    vk_handle::WorkSet &ws = h->sets[h->cur_set];
-    VK_TRY(grow_select_arena(&ws.pc_arena, &ws.pc_arena_bytes, cv.off));
-    float *scores = (float *)(ws.pc_arena + o_scores), *deltas = (float *)(ws.pc_arena + o_deltas);
-    float *max_conf = (float *)(ws.pc_arena + o_conf);
+    const size_t o_extra = cv.off;
+    VK_TRY(grow_device_block(arena, arena_bytes, o_extra + extra_bytes, false));
+    float *scores = (float *)(*arena + o_scores), *deltas = (float *)(*arena + o_deltas);
+    *extra = *arena + o_extra;
     VK_TRY(class_scores_and_deltas(h, p, scores, ld_cls, deltas, ld_box, nrow, s));
+    fill_per_class_args(a, scores, ld_cls, deltas, ld_box, c.cls_agnostic_bbox_reg, p.prop_boxes, p.prop_counts, p.feat, p.attr_prob,
+                        p.attr_cls, F, p.R, C, p.image_hw, scales_dev, c.roi_bbox_weights, sp, out, p.keep_ids, p.nonfinite);
+    return VK_OK;
+}
 
+// The per-class end of a detection forward (after fwd_head): soft-max of every class, bbox_pred over all its rows through the
+// linear path, per-class NMS + finalize (per_class.hip).  Stages "obj_scores", "box_deltas", "max_conf", "keep_ids".
+static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp, const float *scales_dev, const vk_outputs *out,
+                         hipStream_t s) {
+    Carver own(nullptr);
+    const size_t o_best = own.off;
+    own.take((size_t)p.K * sizeof(unsigned long long));
+    const size_t o_conf = own.off;
+    own.take((size_t)p.K * sizeof(float));
+    vk_handle::WorkSet &ws = h->sets[h->cur_set];
     PerClassArgs a;
-    fill_select_args(a, h, p, sp, scores, ld_cls, deltas, ld_box, scales_dev, out);
-    a.best = (unsigned long long *)(ws.pc_arena + o_best);
-    a.max_conf = max_conf;
+    char *mine = nullptr;
+    VK_TRY(select_open(h, p, sp, scales_dev, out, &ws.pc_arena, &ws.pc_arena_bytes, own.off, s, a, &mine));
+    a.best = (unsigned long long *)(mine + o_best);
+    a.max_conf = (float *)(mine + o_conf);
     VK_TRY(launch_per_class_select(a, p.N, s));
-    set_stage(h, "max_conf", max_conf, VK_F32, {p.N, p.R});
-    set_stage(h, "keep_ids", p.keep_ids, VK_I64, {p.N, D});
+    set_stage(h, "max_conf", a.max_conf, VK_F32, {p.N, p.R});
+    set_stage(h, "keep_ids", p.keep_ids, VK_I64, {p.N, sp->roi.max_detections});
     return VK_OK;
 }
 
@@ -1868,34 +1395,23 @@ static int fwd_per_class(vk_handle *h, const Plan &p, const vk_select_params *sp
 // detections.hip.  Stages "obj_scores", "box_deltas", "attr_prob", "keep_ids", "n_survivors".
 static int fwd_detections(vk_handle *h, const Plan &p, const vk_select_params *sp, const float *scales_dev, const vk_outputs *out,
                           hipStream_t s) {
-    const vk_config &c = h->cfg;
-    const int C = c.num_classes, F = h->res5_c, K = p.K, D = sp->roi.max_detections;
+    const int C = h->cfg.num_classes;
     VK_REQUIRE(p.N <= 65535 && p.R <= 1024 && C < (1 << 20), VK_EINVAL, "forward: the detections selection takes N=%d <= 65535, "
                "R=%d <= 1024, C=%d < 2^20", p.N, p.R, C);
-    const int nrow = 4 * (c.cls_agnostic_bbox_reg ? 1 : C);
-    const int ld_cls = (C + 1 + 7) / 8 * 8, ld_box = (nrow + 7) / 8 * 8;
-    VK_TRY(ensure_bbox_lin(h, nrow, F, s));
-    Carver cv(nullptr);
-    const size_t o_scores = cv.off;
-    cv.take((size_t)K * ld_cls * sizeof(float));
-    const size_t o_deltas = cv.off;
-    cv.take((size_t)K * ld_box * sizeof(float));
-    const size_t o_nsurv = cv.off;
-    cv.take((size_t)p.N * sizeof(int32_t));
-    const size_t o_work = cv.off;
-    cv.take(det_workspace_bytes(p.N, p.R, C));
+    Carver own(nullptr);
+    const size_t o_nsurv = own.off;
+    own.take((size_t)p.N * sizeof(int32_t));
+    const size_t o_work = own.off;
+    own.take(det_workspace_bytes(p.N, p.R, C));
     vk_handle::WorkSet &ws = h->sets[h->cur_set];
-    VK_TRY(grow_select_arena(&ws.det_arena, &ws.det_arena_bytes, cv.off));
-    float *scores = (float *)(ws.det_arena + o_scores), *deltas = (float *)(ws.det_arena + o_deltas);
-    VK_TRY(class_scores_and_deltas(h, p, scores, ld_cls, deltas, ld_box, nrow, s));
-
     DetArgs d;
     memset(&d, 0, sizeof(d));
-    fill_select_args(d.pc, h, p, sp, scores, ld_cls, deltas, ld_box, scales_dev, out);
-    det_carve(d, ws.det_arena + o_work, p.N, p.R, C);
-    d.n_survivors = (int32_t *)(ws.det_arena + o_nsurv);
+    char *mine = nullptr;
+    VK_TRY(select_open(h, p, sp, scales_dev, out, &ws.det_arena, &ws.det_arena_bytes, own.off, s, d.pc, &mine));
+    det_carve(d, mine + o_work, p.N, p.R, C);
+    d.n_survivors = (int32_t *)(mine + o_nsurv);
     VK_TRY(launch_detections_select(d, p.N, s));
-    set_stage(h, "keep_ids", p.keep_ids, VK_I64, {p.N, D});
+    set_stage(h, "keep_ids", p.keep_ids, VK_I64, {p.N, sp->roi.max_detections});
     set_stage(h, "n_survivors", d.n_survivors, VK_I32, {p.N});
     return VK_OK;
 }
@@ -1947,21 +1463,15 @@ static int forward_detect(vk_handle *h, const float *images_dev, int N, int H, i
             }
         }
     }
-    VK_REQUIRE(h->next_ticket - h->oldest_open < vk_handle::VK_MAX_INFLIGHT, VK_EINVAL,
-               "forward_begin: %d forwards are already in flight; end the oldest first", vk_handle::VK_MAX_INFLIGHT);
-    VK_REQUIRE(h->finalized, VK_EINVAL, "forward: vk_finalize has not been called");
-    VK_REQUIRE(N >= 1 && H >= 32 && W >= 32, VK_EINVAL, "forward: bad input size N=%d H=%d W=%d", N, H, W);
+    VK_TRY(check_forward_handle("forward", h));
+    VK_TRY(check_forward_size("forward", N, H, W));
     VK_REQUIRE(rp->num_nms_thresh >= 1 && rp->num_nms_thresh <= VK_MAX_NMS_THRESH, VK_EINVAL, "forward: 1..%d nms thresholds", VK_MAX_NMS_THRESH);
     if (sel && sel->mode == VK_SELECT_DETECTIONS)       // a proposal may come out under several classes (check_detections_params)
         VK_REQUIRE(N <= 65535, VK_EINVAL, "forward: the detections selection takes at most 65535 images, got N=%d", N);
     else
         VK_REQUIRE(rp->max_detections >= 1 && rp->max_detections <= h->cfg.post_nms_topk, VK_EINVAL,
                    "forward: max_detections=%d must be in 1..POST_NMS_TOPK_TEST", rp->max_detections);
-    // image_shapes only bound the box clipping (frcnn.py:147-153); the reference does not check them
-    // against the tensor size (its own adapter passes PIL (w,h) order, adapters/frcnn.py:50-52)
-    for (int n = 0; n < N; ++n)
-        VK_REQUIRE(image_hw[2 * n] >= 1 && image_hw[2 * n + 1] >= 1, VK_EINVAL, "forward: image_shapes[%d]=(%d,%d) must be positive",
-                   n, image_hw[2 * n], image_hw[2 * n + 1]);
+    for (int n = 0; n < N; ++n) VK_TRY(check_image_shape("forward", image_hw, n));
     VK_CHECK_HIP(hipSetDevice(h->device));
     hipStream_t s = nullptr;            // the forward's stream: the caller's, or the ticket's lane (fwd_route)
     const vk_config &c = h->cfg;
@@ -1976,8 +1486,8 @@ static int forward_detect(vk_handle *h, const float *images_dev, int N, int H, i
 
     // ---- RPN head (RPNHead.forward frcnn.py:1561-1572) ----
     const int ld_rpn = (5 * h->A + 7) / 8 * 8;
-    VK_TRY(run_conv(h, h->rpn_conv, res4, N, p.Hf, p.Wf, nullptr, p.rpn_hid, true, h->dt, 0, s));
-    VK_TRY(run_conv(h, h->rpn_heads, p.rpn_hid, N, p.Hf, p.Wf, nullptr, p.rpn_out, false, VK_F32, ld_rpn, s));
+    VK_TRY(run_conv(h, h->rpn_conv, res4, N, p.Hf, p.Wf, p.rpn_hid, s, {.relu = true}));
+    VK_TRY(run_conv(h, h->rpn_heads, p.rpn_hid, N, p.Hf, p.Wf, p.rpn_out, s, {.out_dt = VK_F32, .ldy = ld_rpn}));
     set_stage(h, "rpn_out", p.rpn_out, VK_F32, {N, p.Hf, p.Wf, ld_rpn});
     if (tm) VK_CHECK_HIP(hipEventRecord(h->ev[2], s));
 
@@ -2015,34 +1525,8 @@ static int forward_detect(vk_handle *h, const float *images_dev, int N, int H, i
 
     // ---- outputs (ROIOutputs.inference frcnn.py:1262-1294) ----
     RoiFinalArgs a;
-    memset(&a, 0, sizeof(a));
-    a.obj_prob = p.obj_prob;
-    a.obj_cls = p.obj_cls;
-    a.attr_prob = p.attr_prob;
-    a.attr_cls = p.attr_cls;
-    a.box_deltas = p.chosen;
-    a.ld_box = 4;
-    a.delta_mode = 1;
-    a.proposals = p.prop_boxes;
-    a.counts = p.prop_counts;
-    a.features = p.feat;
-    a.F = F;
-    a.R = p.R;
-    a.D = D;
-    a.image_hw = p.image_hw;
-    a.scales_yx = scales_yx ? p.scales : nullptr;
-    a.wx = c.roi_bbox_weights[0];
-    a.wy = c.roi_bbox_weights[1];
-    a.ww = c.roi_bbox_weights[2];
-    a.wh = c.roi_bbox_weights[3];
-    a.clampv = (float)std::log(1000.0 / 16.0);
-    a.n_thresh = rp->num_nms_thresh;
-    for (int i = 0; i < rp->num_nms_thresh; ++i) a.thresh[i] = rp->nms_thresh[i];
-    a.mind = rp->min_detections;
-    a.maxd = rp->max_detections;
-    a.out = *out;
-    a.keep_ids = p.keep_ids;
-    a.nonfinite = p.nonfinite;
+    fill_roi_final_args(a, p.obj_prob, p.obj_cls, p.attr_prob, p.attr_cls, p.chosen, 4, 1, p.prop_boxes, p.prop_counts, p.feat, F, p.R,
+                        p.image_hw, scales_yx ? p.scales : nullptr, c.roi_bbox_weights, rp, out, p.keep_ids, p.nonfinite);
     VK_TRY(launch_roi_final(a, N, s));
     set_stage(h, "keep_ids", p.keep_ids, VK_I64, {N, D});
     return fwd_close(h, p.nonfinite, s, ticket);
@@ -2053,22 +1537,17 @@ int vk_forward_boxes_begin(vk_handle *h, const float *images_dev, int N, int H, 
                            void *stream, int64_t *ticket) {
     // the arguments first, then the handle: every check here runs before anything touches the device
     VK_REQUIRE(images_dev && image_hw && counts && out && ticket, VK_EINVAL, "forward_boxes: null argument");
-    VK_REQUIRE(N >= 1 && H >= 32 && W >= 32, VK_EINVAL, "forward_boxes: bad input size N=%d H=%d W=%d", N, H, W);
+    VK_TRY(check_forward_size("forward_boxes", N, H, W));
     VK_REQUIRE(B >= 0 && B <= 1024, VK_EINVAL, "forward_boxes: B=%d boxes per image must be in 0..1024", B);
     VK_REQUIRE(B == 0 || boxes_dev, VK_EINVAL, "forward_boxes: null boxes with B=%d", B);
     VK_REQUIRE(out->preds_per_image, VK_EINVAL, "forward_boxes: null preds_per_image");
-    VK_REQUIRE(B == 0 || (out->obj_ids && out->obj_probs && out->attr_ids && out->attr_probs && out->boxes && out->roi_features),
-               VK_EINVAL, "forward_boxes: null output array");
-    VK_REQUIRE(B == 0 || ((uintptr_t)out->roi_features & 15) == 0, VK_EINVAL, "forward_boxes: roi_features must be 16-byte aligned");
+    if (B > 0) VK_TRY(check_row_outputs("forward_boxes", out));       // (B == 0 writes preds_per_image alone)
     for (int n = 0; n < N; ++n) {
         VK_REQUIRE(counts[n] >= 0 && counts[n] <= B, VK_EINVAL, "forward_boxes: counts[%d]=%d must be in 0..B=%d", n, counts[n], B);
-        VK_REQUIRE(image_hw[2 * n] >= 1 && image_hw[2 * n + 1] >= 1, VK_EINVAL,
-                   "forward_boxes: image_shapes[%d]=(%d,%d) must be positive", n, image_hw[2 * n], image_hw[2 * n + 1]);
+        VK_TRY(check_image_shape("forward_boxes", image_hw, n));
     }
     VK_REQUIRE(h, VK_EINVAL, "forward_boxes: null handle");
-    VK_REQUIRE(h->next_ticket - h->oldest_open < vk_handle::VK_MAX_INFLIGHT, VK_EINVAL,
-               "forward_boxes_begin: %d forwards are already in flight; end the oldest first", vk_handle::VK_MAX_INFLIGHT);
-    VK_REQUIRE(h->finalized, VK_EINVAL, "forward_boxes: vk_finalize has not been called");
+    VK_TRY(check_forward_handle("forward_boxes", h));
     VK_CHECK_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     if (B == 0) {       // every image is empty: a zero-detection block, no kernel, no stage events; on the caller's stream, no working set
@@ -2108,19 +1587,12 @@ int vk_forward_grid_begin(vk_handle *h, const float *images_dev, int N, int H, i
                           const float *scales_yx, int Gh, int Gw, const vk_outputs *out, void *stream, int64_t *ticket) {
     // the arguments first, then the handle: every check here runs before anything touches the device
     VK_REQUIRE(images_dev && image_hw && out && ticket, VK_EINVAL, "forward_grid: null argument");
-    VK_REQUIRE(N >= 1 && H >= 32 && W >= 32, VK_EINVAL, "forward_grid: bad input size N=%d H=%d W=%d", N, H, W);
+    VK_TRY(check_forward_size("forward_grid", N, H, W));
     VK_REQUIRE(Gh >= 1 && Gw >= 1 && (long)Gh * Gw <= 1024, VK_EINVAL, "forward_grid: grid (%d, %d) must have 1..1024 cells", Gh, Gw);
-    VK_REQUIRE(out->obj_ids && out->obj_probs && out->attr_ids && out->attr_probs && out->boxes && out->preds_per_image &&
-                   out->roi_features,
-               VK_EINVAL, "forward_grid: null output array");
-    VK_REQUIRE(((uintptr_t)out->roi_features & 15) == 0, VK_EINVAL, "forward_grid: roi_features must be 16-byte aligned");
-    for (int n = 0; n < N; ++n)
-        VK_REQUIRE(image_hw[2 * n] >= 1 && image_hw[2 * n + 1] >= 1, VK_EINVAL,
-                   "forward_grid: image_shapes[%d]=(%d,%d) must be positive", n, image_hw[2 * n], image_hw[2 * n + 1]);
+    VK_TRY(check_row_outputs("forward_grid", out));
+    for (int n = 0; n < N; ++n) VK_TRY(check_image_shape("forward_grid", image_hw, n));
     VK_REQUIRE(h, VK_EINVAL, "forward_grid: null handle");
-    VK_REQUIRE(h->next_ticket - h->oldest_open < vk_handle::VK_MAX_INFLIGHT, VK_EINVAL,
-               "forward_grid_begin: %d forwards are already in flight; end the oldest first", vk_handle::VK_MAX_INFLIGHT);
-    VK_REQUIRE(h->finalized, VK_EINVAL, "forward_grid: vk_finalize has not been called");
+    VK_TRY(check_forward_handle("forward_grid", h));
     const int G = Gh * Gw;
     // the working set this forward will get must hold the whole map in each head buffer: refuse before anything is enqueued
     const Plan need = make_plan(h, nullptr, N, H, W, G, G, true);
@@ -2214,252 +1686,6 @@ int vk_get_kernel_timing(vk_handle *h, int64_t *launches, double *ms, double *fl
             h->ktimer->flops[i] = 0;
         }
     }
-    return VK_OK;
-}
-
-// ---- pieces of FastRCNNOutputLayers.forward (frcnn.py:1726-1740) / ROIPooler input format (:426-441) for callers that
-// compose a box head themselves (the FPN detector, vltk_amd/frcnn_fpn.py) ----
-int vk_make_rois(const float *boxes, int N, int R, float *rois, void *stream) {
-    VK_REQUIRE(boxes && rois && N > 0 && R > 0, VK_EINVAL, "make_rois: bad arguments");
-    return launch_make_rois(boxes, N, R, rois, (hipStream_t)stream);
-}
-
-int vk_softmax_argmax(const float *logits, int ld, int K, int n_softmax, int n_argmax, float *prob_out, int32_t *cls_out,
-                      int32_t *raw_argmax_out, void *stream) {
-    VK_REQUIRE(logits && prob_out && cls_out && K >= 0 && n_softmax >= 1 && n_argmax >= 1 && n_argmax <= n_softmax && ld >= n_softmax,
-               VK_EINVAL, "softmax_argmax: bad arguments");
-    return launch_softmax_argmax(logits, ld, K, n_softmax, n_argmax, prob_out, cls_out, raw_argmax_out, (hipStream_t)stream);
-}
-
-int vk_concat_embed(const float *features, int F, const void *emb, int E, const int32_t *cls, int K, void *out, vk_dtype dt,
-                    void *stream) {
-    VK_REQUIRE(features && out && F > 0 && E >= 0 && K >= 0 && (E == 0 || (emb && cls)), VK_EINVAL, "concat_embed: bad arguments");
-    VK_REQUIRE(dt == VK_F16 || dt == VK_F32, VK_EINVAL, "concat_embed: dtype must be f16 or f32");
-    return launch_concat_embed(features, emb, cls, F, E, K, out, dt, (hipStream_t)stream);
-}
-
-int vk_chosen_deltas(const void *x, int ldx, const void *w_rows, const float *bias, const int32_t *cls, int cls_agnostic, int F,
-                     int K, float *out, vk_dtype dt, void *stream) {
-    VK_REQUIRE(x && w_rows && bias && out && (cls || cls_agnostic) && F > 0 && ldx >= F && K >= 0, VK_EINVAL, "chosen_deltas: bad arguments");
-    VK_REQUIRE(dt == VK_F16 || dt == VK_F32, VK_EINVAL, "chosen_deltas: dtype must be f16 or f32");
-    return launch_chosen_deltas(x, ldx, w_rows, bias, cls, cls_agnostic, F, K, out, dt, (hipStream_t)stream);
-}
-
-int vk_roi_outputs(const float *obj_logits, int ld_obj, const float *attr_logits, int ld_attr, const float *box_deltas,
-                   int ld_box, int chosen_only, const float *proposals, const int32_t *counts, const float *features, int F,
-                   int N, int R, int C, int A, const int32_t *image_hw, const float *scales_yx_dev,
-                   const float *weights4_host, const vk_roi_params *rp, const vk_outputs *out, int64_t *keep_ids_out,
-                   int32_t *nonfinite_flag, void *stream) {
-    VK_REQUIRE(obj_logits && box_deltas && proposals && counts && features && image_hw && rp && out && nonfinite_flag, VK_EINVAL,
-               "roi_outputs: null argument");
-    VK_REQUIRE(rp->num_nms_thresh >= 1 && rp->num_nms_thresh <= VK_MAX_NMS_THRESH, VK_EINVAL, "roi_outputs: 1..%d nms thresholds", VK_MAX_NMS_THRESH);
-    hipStream_t s = (hipStream_t)stream;
-    const int K = N * R;
-    // scratch for the per-RoI scores (freed after the stream drains; stage-level entry point only)
-    char *scratch = nullptr;
-    const size_t per = align_up((size_t)K * 4, 256);
-    VK_CHECK_HIP(hipMalloc((void **)&scratch, per * 4));
-    float *obj_prob = (float *)scratch, *attr_prob = (float *)(scratch + per);
-    int32_t *obj_cls = (int32_t *)(scratch + 2 * per), *attr_cls = (int32_t *)(scratch + 3 * per);
-    int st = launch_softmax_argmax(obj_logits, ld_obj, K, C + 1, C, obj_prob, obj_cls, nullptr, s);
-    if (st == VK_OK && attr_logits) st = launch_softmax_argmax(attr_logits, ld_attr, K, A, A, attr_prob, attr_cls, nullptr, s);
-    if (st == VK_OK) {
-        RoiFinalArgs a;
-        memset(&a, 0, sizeof(a));
-        a.obj_prob = obj_prob;
-        a.obj_cls = obj_cls;
-        a.attr_prob = attr_logits ? attr_prob : nullptr;
-        a.attr_cls = attr_logits ? attr_cls : nullptr;
-        a.box_deltas = box_deltas;
-        a.ld_box = ld_box;
-        a.delta_mode = chosen_only ? 1 : 0;
-        a.proposals = proposals;
-        a.counts = counts;
-        a.features = features;
-        a.F = F;
-        a.R = R;
-        a.D = rp->max_detections;
-        a.image_hw = image_hw;
-        a.scales_yx = scales_yx_dev;
-        a.wx = weights4_host[0];
-        a.wy = weights4_host[1];
-        a.ww = weights4_host[2];
-        a.wh = weights4_host[3];
-        a.clampv = (float)std::log(1000.0 / 16.0);
-        a.n_thresh = rp->num_nms_thresh;
-        for (int i = 0; i < rp->num_nms_thresh; ++i) a.thresh[i] = rp->nms_thresh[i];
-        a.mind = rp->min_detections;
-        a.maxd = rp->max_detections;
-        a.out = *out;
-        a.keep_ids = keep_ids_out;
-        a.nonfinite = nonfinite_flag;
-        st = launch_roi_final(a, N, s);
-    }
-    hipError_t e = hipStreamSynchronize(s);
-    (void)hipFree(scratch);
-    if (st != VK_OK) return st;
-    VK_CHECK_HIP(e);
-    return VK_OK;
-}
-
-int vk_class_probs(const float *logits, int ld, int K, int n, float *out, int ld_out, void *stream) {
-    VK_REQUIRE(logits && out && K >= 0 && n >= 1 && ld >= n && ld_out >= n, VK_EINVAL, "class_probs: bad arguments");
-    return launch_class_probs(logits, ld, K, n, out, ld_out, (hipStream_t)stream);
-}
-
-int vk_class_boxes(const float *box_deltas, int ld_box, int cls_agnostic, const float *proposals, const int32_t *counts, int N, int R,
-                   int C, const int32_t *image_hw, const float *weights4_host, float *out, int32_t *nonfinite_flag, void *stream) {
-    VK_REQUIRE(box_deltas && proposals && counts && image_hw && weights4_host && out, VK_EINVAL, "class_boxes: null argument");
-    PerClassArgs a;
-    memset(&a, 0, sizeof(a));
-    a.deltas = box_deltas;
-    a.ld_box = ld_box;
-    a.agnostic = cls_agnostic ? 1 : 0;
-    a.proposals = proposals;
-    a.counts = counts;
-    a.R = R;
-    a.C = C;
-    a.image_hw = image_hw;
-    a.wx = weights4_host[0];
-    a.wy = weights4_host[1];
-    a.ww = weights4_host[2];
-    a.wh = weights4_host[3];
-    a.clampv = (float)std::log(1000.0 / 16.0);
-    a.nonfinite = nonfinite_flag;
-    return launch_class_boxes(a, N, out, (hipStream_t)stream);
-}
-
-int vk_per_class_select(const float *obj_scores, int ld_scores, const float *attr_logits, int ld_attr, const float *box_deltas,
-                        int ld_box, int cls_agnostic, const float *proposals, const int32_t *counts, const float *features, int F,
-                        int N, int R, int C, int A, const int32_t *image_hw, const float *scales_yx_dev,
-                        const float *weights4_host, const vk_select_params *sp, const vk_outputs *out, int64_t *keep_ids_out,
-                        float *max_conf_out, int32_t *nonfinite_flag, void *stream) {
-    VK_REQUIRE(obj_scores && box_deltas && proposals && counts && features && image_hw && weights4_host && sp && out && nonfinite_flag,
-               VK_EINVAL, "per_class_select: null argument");
-    VK_REQUIRE(sp->mode == VK_SELECT_PER_CLASS, VK_EINVAL, "per_class_select: mode=%d is not VK_SELECT_PER_CLASS", sp->mode);
-    VK_TRY(check_select_params(sp, "per_class_select"));
-    VK_REQUIRE(N >= 1 && N <= 65535 && R >= 1 && R <= 1024 && C >= 1, VK_EINVAL, "per_class_select: N=%d R=%d C=%d (R at most 1024)", N, R, C);
-    VK_REQUIRE(sp->roi.max_detections >= 1 && sp->roi.max_detections <= R, VK_EINVAL, "per_class_select: max_detections=%d must be in 1..R=%d",
-               sp->roi.max_detections, R);
-    VK_REQUIRE(F >= 4 && F % 4 == 0, VK_EINVAL, "per_class_select: F=%d must be a positive multiple of 4", F);
-    VK_REQUIRE(!attr_logits || (A >= 1 && ld_attr >= A), VK_EINVAL, "per_class_select: A=%d ld_attr=%d", A, ld_attr);
-    hipStream_t s = (hipStream_t)stream;
-    const int K = N * R;
-    // scratch: the best-class words and the per-row attribute predictions (freed after the stream drains; stage-level entry point only)
-    char *scratch = nullptr;
-    const size_t per = align_up((size_t)K * 8, 256);
-    VK_CHECK_HIP(hipMalloc((void **)&scratch, per * 3));
-    float *attr_prob = (float *)(scratch + per);
-    int32_t *attr_cls = (int32_t *)(scratch + 2 * per);
-    int st = VK_OK;
-    if (attr_logits) st = launch_softmax_argmax(attr_logits, ld_attr, K, A, A, attr_prob, attr_cls, nullptr, s);
-    if (st == VK_OK) {
-        PerClassArgs a;
-        memset(&a, 0, sizeof(a));
-        a.scores = obj_scores;
-        a.ld_scores = ld_scores;
-        a.deltas = box_deltas;
-        a.ld_box = ld_box;
-        a.agnostic = cls_agnostic ? 1 : 0;
-        a.proposals = proposals;
-        a.counts = counts;
-        a.features = features;
-        a.attr_prob = attr_logits ? attr_prob : nullptr;
-        a.attr_cls = attr_logits ? attr_cls : nullptr;
-        a.F = F;
-        a.R = R;
-        a.D = sp->roi.max_detections;
-        a.C = C;
-        a.image_hw = image_hw;
-        a.scales_yx = scales_yx_dev;
-        a.wx = weights4_host[0];
-        a.wy = weights4_host[1];
-        a.ww = weights4_host[2];
-        a.wh = weights4_host[3];
-        a.clampv = (float)std::log(1000.0 / 16.0);
-        a.thresh = sp->roi.nms_thresh[0];
-        a.score_thresh = sp->score_thresh;
-        a.mind = sp->roi.min_detections;
-        a.maxd = sp->roi.max_detections;
-        a.best = (unsigned long long *)scratch;
-        a.max_conf = max_conf_out;
-        a.out = *out;
-        a.keep_ids = keep_ids_out;
-        a.nonfinite = nonfinite_flag;
-        st = launch_per_class_select(a, N, s);
-    }
-    hipError_t e = hipStreamSynchronize(s);
-    (void)hipFree(scratch);
-    if (st != VK_OK) return st;
-    VK_CHECK_HIP(e);
-    return VK_OK;
-}
-
-int vk_detections_lds_keys(void) { return VK_DETECTIONS_LDS_KEYS; }
-
-int vk_detections_select(const float *obj_scores, int ld_scores, const float *attr_logits, int ld_attr, const float *box_deltas,
-                         int ld_box, int cls_agnostic, const float *proposals, const int32_t *counts, const float *features, int F,
-                         int N, int R, int C, int A, const int32_t *image_hw, const float *scales_yx_dev,
-                         const float *weights4_host, const vk_select_params *sp, const vk_outputs *out, int64_t *keep_ids_out,
-                         int32_t *n_survivors_out, int32_t *nonfinite_flag, void *stream) {
-    VK_REQUIRE(obj_scores && box_deltas && proposals && counts && features && image_hw && weights4_host && sp && out && nonfinite_flag,
-               VK_EINVAL, "detections_select: null argument");
-    VK_REQUIRE(sp->mode == VK_SELECT_DETECTIONS, VK_EINVAL, "detections_select: mode=%d is not VK_SELECT_DETECTIONS", sp->mode);
-    VK_TRY(check_detections_params(sp, "detections_select"));
-    VK_REQUIRE(N >= 1 && N <= 65535 && R >= 1 && R <= 1024 && C >= 1 && C < (1 << 20), VK_EINVAL,
-               "detections_select: N=%d R=%d C=%d (N at most 65535, R at most 1024, C below 2^20)", N, R, C);
-    VK_REQUIRE(F >= 4 && F % 4 == 0, VK_EINVAL, "detections_select: F=%d must be a positive multiple of 4", F);
-    VK_REQUIRE(!attr_logits || (A >= 1 && ld_attr >= A), VK_EINVAL, "detections_select: A=%d ld_attr=%d", A, ld_attr);
-    VK_REQUIRE(ld_scores >= C && ld_box >= (cls_agnostic ? 4 : 4 * C), VK_EINVAL, "detections_select: row strides ld_scores=%d "
-               "ld_box=%d are shorter than the rows", ld_scores, ld_box);
-    hipStream_t s = (hipStream_t)stream;
-    const int K = N * R;
-    // scratch: the per-row attribute predictions and the candidate / survivor lists, from the device's pool in stream order
-    const size_t per = align_up((size_t)K * 4, 256);
-    char *scratch = nullptr;
-    VK_CHECK_HIP(hipMallocAsync((void **)&scratch, 2 * per + det_workspace_bytes(N, R, C), s));
-    float *attr_prob = (float *)scratch;
-    int32_t *attr_cls = (int32_t *)(scratch + per);
-    int st = VK_OK;
-    if (attr_logits) st = launch_softmax_argmax(attr_logits, ld_attr, K, A, A, attr_prob, attr_cls, nullptr, s);
-    if (st == VK_OK) {
-        DetArgs d;
-        memset(&d, 0, sizeof(d));
-        PerClassArgs &a = d.pc;
-        a.scores = obj_scores;
-        a.ld_scores = ld_scores;
-        a.deltas = box_deltas;
-        a.ld_box = ld_box;
-        a.agnostic = cls_agnostic ? 1 : 0;
-        a.proposals = proposals;
-        a.counts = counts;
-        a.features = features;
-        a.attr_prob = attr_logits ? attr_prob : nullptr;
-        a.attr_cls = attr_logits ? attr_cls : nullptr;
-        a.F = F;
-        a.R = R;
-        a.D = sp->roi.max_detections;
-        a.C = C;
-        a.image_hw = image_hw;
-        a.scales_yx = scales_yx_dev;
-        a.wx = weights4_host[0];
-        a.wy = weights4_host[1];
-        a.ww = weights4_host[2];
-        a.wh = weights4_host[3];
-        a.clampv = (float)std::log(1000.0 / 16.0);
-        a.thresh = sp->roi.nms_thresh[0];
-        a.score_thresh = sp->score_thresh;
-        a.maxd = sp->roi.max_detections;
-        a.out = *out;
-        a.keep_ids = keep_ids_out;
-        a.nonfinite = nonfinite_flag;
-        det_carve(d, scratch + 2 * per, N, R, C);
-        d.n_survivors = n_survivors_out;
-        st = launch_detections_select(d, N, s);
-    }
-    hipError_t e = hipFreeAsync(scratch, s);
-    if (st != VK_OK) return st;
-    VK_CHECK_HIP(e);
     return VK_OK;
 }
 

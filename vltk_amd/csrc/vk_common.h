@@ -139,7 +139,7 @@ struct Timed {
     int end(hipStream_t stream, int bucket, double flops, int M, int cout, int cin, int k, int stride, double bytes);
 };
 
-// ---- launcher state, per device (model.hip) ----
+// ---- launcher state, per device (runtime.hip) ----
 // A process may hold handles on several devices: everything a launcher keeps between launches lives here, one record per
 // device, created on the first launch on that device (under a lock) and kept for the life of the process.
 constexpr int BN_TRASH_BYTES = 1 << 16;
@@ -155,6 +155,36 @@ int device_state(DeviceState **out);  // the current HIP device's record
 int set_max_lds(const void *kernel, size_t bytes);
 template <typename... A>
 static inline int set_max_lds(void (*kernel)(A...), size_t bytes) { return set_max_lds(reinterpret_cast<const void *>(kernel), bytes); }
+
+// ---- pack.hip (host only) ----
+void to_dt(const float *src, size_t n, vk_dtype dt, void *dst);       // float -> f16 / bf16 (nearest even) / f32
+
+// ---- stage_api.hip: the builders of a launch's arguments, shared by the stage-level entry points and the model (model.hip) ----
+static inline void conv_out_hw(int H, int W, int k, int s, int p, int d, int *Ho, int *Wo) {
+    *Ho = (H + 2 * p - (d * (k - 1) + 1)) / s + 1;
+    *Wo = (W + 2 * p - (d * (k - 1) + 1)) / s + 1;
+}
+// the layer as the dispatcher sees it; the pointers (and Cin2 with x2) are the caller's to set
+void fill_conv_args(ConvArgs &a, int N, int H, int W, int cin, int cout, int ldy, int k, int stride, int pad, int dil, int groups,
+                    int relu, vk_dtype dt, vk_dtype out_dt);
+// stem_pack, then stem_pool or the 7x7 conv + max-pool (vk_stem, and the model's backbone)
+int stem_impl(const float *x, int N, int H, int W, const void *w, const float *b, int cout, int caffe, void *y, vk_dtype dt,
+              void *img_pad, void *stem_out, hipStream_t s, int32_t *nonfinite = nullptr);
+struct PerClassArgs;
+struct RoiFinalArgs;
+void fill_per_class_args(PerClassArgs &a, const float *scores, int ld_scores, const float *deltas, int ld_box, int agnostic,
+                         const float *proposals, const int32_t *counts, const float *features, const float *attr_prob,
+                         const int32_t *attr_cls, int F, int R, int C, const int32_t *image_hw, const float *scales_yx,
+                         const float *weights4, const vk_select_params *sp, const vk_outputs *out, int64_t *keep_ids,
+                         int32_t *nonfinite);
+void fill_roi_final_args(RoiFinalArgs &a, const float *obj_prob, const int32_t *obj_cls, const float *attr_prob,
+                         const int32_t *attr_cls, const float *box_deltas, int ld_box, int delta_mode, const float *proposals,
+                         const int32_t *counts, const float *features, int F, int R, const int32_t *image_hw,
+                         const float *scales_yx, const float *weights4, const vk_roi_params *rp, const vk_outputs *out,
+                         int64_t *keep_ids, int32_t *nonfinite);
+// what a vk_select_params must satisfy in the per-class / detections mode; `who` prefixes the error text
+int check_select_params(const vk_select_params *sp, const char *who);
+int check_detections_params(const vk_select_params *sp, const char *who);
 
 // ---- pool.hip ----
 int launch_stem_pack(const float *x, void *y, int N, int H, int W, int Hp, int Wp, vk_dtype dt, hipStream_t s, int32_t *nonfinite = nullptr);
