@@ -68,7 +68,7 @@ typedef struct vk_config {
     int32_t num_attrs;             /* ROI_BOX_HEAD.NUM_ATTRS */
     int32_t use_attr;              /* ROI_BOX_HEAD.ATTR */
     int32_t pooler_resolution;     /* ROI_BOX_HEAD.POOLER_RESOLUTION */
-    int32_t res5_halve;            /* ROI_BOX_HEAD.RES5HALVE (only 0 supported this round) */
+    int32_t res5_halve;            /* ROI_BOX_HEAD.RES5HALVE (1: the plain stride-2 Res5 stage, 7x7 maps) */
     int32_t cls_agnostic_bbox_reg; /* ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG */
     float   roi_bbox_weights[4];   /* ROI_BOX_HEAD.BBOX_REG_WEIGHTS */
     int32_t precision;             /* VK_F16: fp16 storage / fp32 accumulate (fast);
@@ -187,6 +187,24 @@ int vk_set_option(vk_handle *h, const char *key, int value);
 int vk_get_option(vk_handle *h, const char *key, int *value);
 int vk_option_check(const char *key, int value);
 int vk_option_default(const char *key, int *value);
+
+/* The box pooler of the C4 head (ROI_BOX_HEAD.POOLER_TYPE / POOLER_SAMPLING_RATIO; spatial scale 1/16, resolution
+ * POOLER_RESOLUTION).  VK_POOLER_ROIPOOL is the reference's (frcnn.py:1179) and what a new handle has; the two RoIAlign types
+ * are detectron2's (torchvision roi_align semantics; PARITY UNPINNED for the rule, the reference holds no RoIAlign) and run
+ * wherever the Res5 head runs: detection in every selection mode, ignorey, given boxes.  Not an option of the table above:
+ * the pooler changes the results.  0 <= sampling_ratio <= 8 (0: adaptive, ceil(bin size)); it is kept and unused with
+ * VK_POOLER_ROIPOOL.  With a RoIAlign pooler the "head_dedupe" path is never taken (distinct RoIPool windows mean nothing to
+ * it) and the stage "head_windows" is not set.  The handle pools through vk_roi_align on one level (res4); the boxes that
+ * reach it are finite and inside the image (the RPN's and vk_forward_boxes_begin's _clip_box), a non-finite box having
+ * been flagged before.
+ * vk_pooler_check validates a pair without a handle; vk_set_pooler is legal only before the handle's first forward
+ * (VK_EINVAL after: the working set is planned for the pooler). */
+#define VK_POOLER_ROIPOOL    0
+#define VK_POOLER_ROIALIGN   1   /* aligned = 0 */
+#define VK_POOLER_ROIALIGNV2 2   /* aligned = 1 */
+int vk_pooler_check(int type, int sampling_ratio);
+int vk_set_pooler(vk_handle *h, int type, int sampling_ratio);
+int vk_get_pooler(vk_handle *h, int *type, int *sampling_ratio);
 
 /* Number of weight tensors the model expects and their names (strict load). */
 int vk_num_weights(vk_handle *h, int *count);

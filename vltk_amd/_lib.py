@@ -24,6 +24,7 @@ VK_MAX_ANCHOR_DIM = 8
 VK_MAX_NMS_THRESH = 8
 VK_MAX_IGNOREY = 64
 VK_SELECT_CLASS_MAX, VK_SELECT_PER_CLASS, VK_SELECT_DETECTIONS = 0, 1, 2
+VK_POOLER_ROIPOOL, VK_POOLER_ROIALIGN, VK_POOLER_ROIALIGNV2 = 0, 1, 2
 
 # status code -> the Python exception type the reference raises in the same situation
 # (frcnn.py:1930 NotImplementedError, :148 AssertionError, :1789/:1850 EnvironmentError/OSError)
@@ -92,6 +93,9 @@ SIGNATURES = {
     "vk_get_option": (_I, [_P, C.c_char_p, C.POINTER(_I)]),
     "vk_option_check": (_I, [C.c_char_p, _I]),
     "vk_option_default": (_I, [C.c_char_p, C.POINTER(_I)]),
+    "vk_pooler_check": (_I, [_I, _I]),
+    "vk_set_pooler": (_I, [_P, _I, _I]),
+    "vk_get_pooler": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
     "vk_num_weights": (_I, [_P, C.POINTER(_I)]),
     "vk_weight_name": (_I, [_P, _I, C.POINTER(C.c_char_p)]),
     "vk_forward": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(vk_roi_params), C.POINTER(vk_outputs), _P]),

@@ -112,6 +112,8 @@ struct vk_handle {
     int head_streams = 0;                           // 2: each Res5 chunk as two half-chunks on two streams
     int head_split_min_rois = 0;                    // ... for chunks of at least this many RoIs
     int head_dedupe = 0;                            // 1: Res5 block 0 pools and convolves each distinct RoIPool window once
+    // the box pooler (vk_set_pooler; not an option: it changes the results): VK_POOLER_*, and RoIAlign's samples per bin and axis
+    int pooler_type = VK_POOLER_ROIPOOL, pooler_sampling_ratio = 0;
     int64_t dedupe_chunks = 0;                                            // head chunks that took that path (vk_get_option "dedupe_chunks")
     // "pooled" after a forward whose one chunk took the dedupe path: the dense tensor was never written; vk_get_stage expands
     // src[idx] into the plan's buffer the first time the stage is asked for
@@ -328,6 +330,7 @@ static bool fused_mean_ok(const vk_handle *h, int P, size_t rows) {
 // What does not depend on a chunk's size in the decision for the dedupe path of Res5 block 0 (fwd_head has the rest: the two GEMMs'
 // routes): the plan carves the table's buffers on this.
 static bool head_dedupe_planned(const vk_handle *h) {
+    if (h->pooler_type != VK_POOLER_ROIPOOL) return false;     // distinct RoIPool windows mean nothing to RoIAlign
     if (!h->head_dedupe || h->dt != VK_F16 || h->cfg.res5_halve != 0 || h->head_streams != 1 || h->res5.size() < 2) return false;
     const Block &b = h->res5[0];
     for (size_t i = 1; i < h->res5.size(); ++i)          // (h_sc holds the distinct pooled rows until the forward ends)
@@ -811,6 +814,29 @@ int vk_set_option(vk_handle *h, const char *key, int value) {
     return VK_OK;
 }
 
+int vk_pooler_check(int type, int sampling_ratio) {
+    VK_REQUIRE(type == VK_POOLER_ROIPOOL || type == VK_POOLER_ROIALIGN || type == VK_POOLER_ROIALIGNV2, VK_EINVAL,
+               "pooler type %d must be VK_POOLER_ROIPOOL, VK_POOLER_ROIALIGN or VK_POOLER_ROIALIGNV2", type);
+    VK_REQUIRE(sampling_ratio >= 0 && sampling_ratio <= 8, VK_EINVAL, "POOLER_SAMPLING_RATIO %d must be in 0..8 (0 = adaptive)", sampling_ratio);
+    return VK_OK;
+}
+
+int vk_set_pooler(vk_handle *h, int type, int sampling_ratio) {
+    VK_REQUIRE(h, VK_EINVAL, "set_pooler: null handle");
+    VK_TRY(vk_pooler_check(type, sampling_ratio));
+    VK_REQUIRE(h->next_ticket == 0, VK_EINVAL, "set_pooler: the pooler is fixed once the handle has run a forward");
+    h->pooler_type = type;
+    h->pooler_sampling_ratio = sampling_ratio;
+    return VK_OK;
+}
+
+int vk_get_pooler(vk_handle *h, int *type, int *sampling_ratio) {
+    VK_REQUIRE(h && type && sampling_ratio, VK_EINVAL, "get_pooler: null argument");
+    *type = h->pooler_type;
+    *sampling_ratio = h->pooler_sampling_ratio;
+    return VK_OK;
+}
+
 int vk_destroy(vk_handle *h) {
     if (!h) return VK_OK;
     (void)hipSetDevice(h->device);
@@ -1139,8 +1165,18 @@ static int head_block0_dedupe(vk_handle *h, const Plan &p, const void *res4, int
     return VK_OK;
 }
 
+// The handle's box pooler on nb RoI rows: RoIPool (frcnn.py:1179), or RoIAlign through the pyramid kernel on one level (res4).
+// A C4-shaped LDS-staged kernel was measured against it and lost.
+static int head_pool(vk_handle *h, const Plan &p, const void *res4, const float *rois, int nb, void *pooled, hipStream_t s) {
+    const float scale = 1.0f / 16.0f;
+    if (h->pooler_type == VK_POOLER_ROIPOOL) return vk_roi_pool(res4, p.N, p.Hf, p.Wf, h->res4_c, rois, nb, scale, p.P, pooled, h->dt, s);
+    const int32_t Hf = p.Hf, Wf = p.Wf;
+    return vk_roi_align(&res4, &Hf, &Wf, &scale, 1, p.N, h->res4_c, rois, nullptr, nb, p.P, h->pooler_sampling_ratio,
+                        h->pooler_type == VK_POOLER_ROIALIGNV2, pooled, h->dt, s);
+}
+
 static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s) {
-    const int N = p.N, P = p.P;
+    const int P = p.P;
     vk_handle::Lane &ln = h->lanes[h->cur_set];
     const size_t es5 = dtype_size(h->dt);
     int dd_chunks = 0;
@@ -1175,8 +1211,7 @@ static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s
                 VK_TRY(head_block0_dedupe(h, p, res4, k0, kc, hs));
                 dd_chunks++;
             } else
-                VK_TRY(vk_roi_pool(res4, N, p.Hf, p.Wf, h->res4_c, p.rois + 5 * (size_t)(k0 + n0), nb, 1.0f / 16.0f, P,
-                                   (char *)p.pooled + (size_t)n0 * P * P * h->res4_c * es5, h->dt, hs));
+                VK_TRY(head_pool(h, p, res4, p.rois + 5 * (size_t)(k0 + n0), nb, (char *)p.pooled + (size_t)n0 * P * P * h->res4_c * es5, hs));
             // the fused mean's per-tile partials: the second half gets its own region (tiles are counted per launch)
             float *pp = p.pool_part ? (float *)((char *)p.pool_part + (half ? conv_duo_pool_part_bytes((long)ka * P * P, h->res5_c) : 0)) : nullptr;
             void *a = p.h_a, *b2 = p.h_b;

@@ -137,6 +137,28 @@ def _c_config(cfg, dt):
     return c
 
 
+POOLER_TYPES = {"ROIPool": L.VK_POOLER_ROIPOOL, "ROIAlign": L.VK_POOLER_ROIALIGN, "ROIAlignV2": L.VK_POOLER_ROIALIGNV2}
+
+
+def pooler_from_config(cfg):
+    """The C4 head's box pooler -> (VK_POOLER_*, sampling ratio).  ROI_BOX_HEAD.POOLER_TYPE: absent or "ROIPool" (the
+    reference's RoIPool, frcnn.py:1179), "ROIAlign" (RoIAlign, aligned = False) or "ROIAlignV2" (aligned = True, detectron2's
+    C4 default); anything else is a ValueError.  ROI_BOX_HEAD.POOLER_SAMPLING_RATIO (default 0 = adaptive) is read by the
+    two RoIAlign types only and must be an integer in 0..8.  Host only: the library validates the pair (vk_pooler_check).
+    RoIAlign is torchvision's / detectron2's rule: parity unpinned for the rule."""
+    head = cfg.ROI_BOX_HEAD
+    kind = getattr(head, "POOLER_TYPE", "ROIPool")
+    if not isinstance(kind, str) or kind not in POOLER_TYPES:
+        raise ValueError(f"ROI_BOX_HEAD.POOLER_TYPE={kind!r} must be one of {tuple(POOLER_TYPES)}")
+    if POOLER_TYPES[kind] == L.VK_POOLER_ROIPOOL:
+        return L.VK_POOLER_ROIPOOL, 0
+    ratio = getattr(head, "POOLER_SAMPLING_RATIO", 0)
+    if isinstance(ratio, (bool, np.bool_)) or not isinstance(ratio, (int, np.integer)):
+        raise ValueError(f"ROI_BOX_HEAD.POOLER_SAMPLING_RATIO={ratio!r} must be an integer in 0..8")
+    L.call("vk_pooler_check", POOLER_TYPES[kind], int(ratio))
+    return POOLER_TYPES[kind], int(ratio)
+
+
 MAX_GIVEN_BOXES = 1024          # boxes per image of vk_forward_boxes_begin
 
 
@@ -349,8 +371,10 @@ class FRCNN:
 
     def __init__(self, cfg, precision=None, device=None):
         self._init_host(cfg, precision, device)
+        self.pooler = pooler_from_config(cfg)          # before the handle exists: a bad POOLER_TYPE raises here
         self._h = C.c_void_p()
         L.call("vk_create", C.byref(_c_config(cfg, self.dt)), self.device.index, C.byref(self._h))
+        L.call("vk_set_pooler", self._h, *self.pooler)
 
     def _init_host(self, cfg, precision, device):
         """What the C4 model and the FPN detector (frcnn_fpn.py) set up alike: the GPU and library checks, the device, the
