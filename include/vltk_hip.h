@@ -480,9 +480,27 @@ int vk_embed_layernorm(const int64_t *input_ids, const int64_t *token_type_ids, 
                        const void *position, const void *token_type, const float *gamma, const float *beta,
                        void *y, int C, float eps, vk_dtype dt, void *stream);
 /* LxmertAttention.forward :238-266 after the three projections: out[b, i, h*d:(h+1)*d] =
- * softmax_j(q_i . k_j / sqrt(d) + mask[b, j]) . v_j; q [B*Lq, ldq], k / v [B*Lk, ld*], heads side by side in a row. */
+ * softmax_j(q_i . k_j / sqrt(d) + mask[b, j]) . v_j; q [B*Lq, ldq], k / v [B*Lk, ld*], heads side by side in a row.
+ * Any Lq, Lk >= 1.  The kernel follows vk_attention_route: the matrix-core kernel (16-bit, d 32 / 64, Lq <= 48, Lk <= 64, rows
+ * 16-byte aligned), else the LDS kernel where one head's Q, K, V and scores fit 160 KiB, else an online-soft-max kernel: the
+ * tiled matrix-core form (16-bit, d 32 / 64, aligned) or the strict fp32 streaming form (d <= 256, VK_EINVAL beyond). */
 int vk_attention(const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, const float *mask,
                  void *out, int ldo, int B, int heads, int Lq, int Lk, int d, vk_dtype dt, void *stream);
+/* The same function on the online-soft-max kernels at every shape, small ones included: the tiled matrix-core form where it is
+ * eligible, else the streaming form (d <= 256).  With VK_ATTENTION_TILED=0 in the environment (re-read per call) it is
+ * vk_attention.  The two matrix-core forms round the probabilities to dt before the second product; the LDS and streaming
+ * forms do not. */
+int vk_attention_tiled(const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, const float *mask,
+                       void *out, int ldo, int B, int heads, int Lq, int Lk, int d, vk_dtype dt, void *stream);
+/* Which kernel an attention launch runs on (host only, touches no device; both entry points switch on it, under the same
+ * environment switches, re-read per call).  aligned16: q, k and v are 16-byte aligned; tiled_entry: 1 asks for
+ * vk_attention_tiled, 0 for vk_attention.  VK_ATTENTION_MFMA=0 takes both matrix-core forms out of the choice.  Returns a
+ * VK_ATT_ROUTE_* or, where the launch would refuse the call, the negative of its VK_E* code. */
+#define VK_ATT_ROUTE_MFMA 0     /* attention_mfma_kernel: whole score matrix in registers */
+#define VK_ATT_ROUTE_LDS 1      /* attention_kernel: one head in LDS, fp32 FMAs */
+#define VK_ATT_ROUTE_TILED 2    /* attention_tiled_kernel: 64-key tiles on the matrix cores, online soft-max */
+#define VK_ATT_ROUTE_STREAM 3   /* attention_stream_kernel: 64-key fp32 tiles in LDS, online soft-max */
+int vk_attention_route(int Lq, int Lk, int d, vk_dtype dt, int ldq, int ldk, int ldv, int aligned16, int tiled_entry);
 
 /* ---- N4: FPN-side ops (what north_star names; the reference holds only fragments, see oracle/fpn_oracle.py) ---- */
 

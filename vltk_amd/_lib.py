@@ -20,6 +20,7 @@ VK_OK, VK_EINVAL, VK_ENOTIMPL, VK_ENONFINITE, VK_EWEIGHTS, VK_EHIP, VK_ENOMEM = 
 VK_F32, VK_F16, VK_I64, VK_I32, VK_BF16 = 0, 1, 2, 3, 4
 VK_ACT_NONE, VK_ACT_RELU, VK_ACT_GELU, VK_ACT_TANH = 0, 1, 2, 3
 VK_ROUTE_GENERIC, VK_ROUTE_RING, VK_ROUTE_DUO, VK_ROUTE_WS, VK_ROUTE_GEMM4, VK_ROUTE_PANEL, VK_ROUTE_BLK = range(7)
+VK_ATT_ROUTE_MFMA, VK_ATT_ROUTE_LDS, VK_ATT_ROUTE_TILED, VK_ATT_ROUTE_STREAM = range(4)
 VK_MAX_ANCHOR_DIM = 8
 VK_MAX_NMS_THRESH = 8
 VK_MAX_IGNOREY = 64
@@ -133,6 +134,8 @@ SIGNATURES = {
     "vk_layernorm": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _P]),
     "vk_embed_layernorm": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _F, _I, _P]),
     "vk_attention": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "vk_attention_tiled": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "vk_attention_route": (_I, [_I] * 9),
     "vk_roi_align": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "vk_assign_levels": (_I, [_P, _I, _I, _I, _I, _F, _I, _P, _P]),
     "vk_upsample2x_add": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

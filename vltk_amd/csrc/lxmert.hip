@@ -8,6 +8,7 @@
 //   embed_ln_kernel    LayerNorm(word[id] + position[l] + token_type[tt])
 //   attention_kernel   softmax(Q K^T / sqrt(d) + mask) V per (batch, head); K and V of one head live in LDS (fp32: strict mode)
 //   attention_mfma_kernel  the same on v_mfma_f32_16x16x32 (bf16 / f16), one wave per (batch, head)
+// Sequences these two cannot hold run the kernels of attention_tiled.hip, which also owns the routing rule.
 #include "vk_common.h"
 
 namespace vk {
@@ -208,8 +209,8 @@ __global__ __launch_bounds__(256) void attention_kernel(const T *__restrict__ q,
     }
 }
 
-// ---- the same attention on the matrix cores (bf16 / f16, head dim 32 or 64, Lq <= 48, Lk <= 64: LXMERT runs 20 text
-// and 36 visual tokens) ----
+// ---- the same attention on the matrix cores (bf16 / f16, head dim 32 or 64, Lq <= 48, Lk <= 64: the whole score matrix of
+// LXMERT's usual 20 text and 36 visual tokens in registers; longer sequences run attention_tiled.hip's online-soft-max form) ----
 // One WAVE per (batch, head), four per workgroup.  S = Q K^T and O = P V are v_mfma_f32_16x16x32 tiles:
 //   * Q and K rows are the A / B operand fragments as they lie in memory (8 consecutive head-dim elements per lane):
 //     no staging at all for the first product;
@@ -417,15 +418,17 @@ int vk_attention(const void *q, int ldq, const void *k, int ldk, const void *v, 
                  int heads, int Lq, int Lk, int d, vk_dtype dt, void *stream) {
     VK_REQUIRE(q && k && v && out, VK_EINVAL, "attention: null argument");
     VK_REQUIRE(B > 0 && heads > 0 && Lq >= 1 && Lk >= 1 && d >= 1, VK_EINVAL, "attention: bad geometry (Lq=%d Lk=%d d=%d)", Lq, Lk, d);
-    const size_t smem = ((size_t)(Lq + Lk) * (d + 1) + (size_t)Lk * d + (size_t)Lq * (Lk + 1)) * sizeof(float);
-    VK_REQUIRE(smem <= 160 * 1024, VK_EINVAL,
-               "attention: one head's Q, K, V and scores (%zu bytes at Lq=%d Lk=%d d=%d) must fit the 160 KiB LDS", smem, Lq, Lk, d);
-    const float scale = 1.0f / sqrtf((float)d);
     hipStream_t s = (hipStream_t)stream;
-    // matrix-core form: 16-bit types, head dim 32 / 64, up to 48 queries and 64 keys, 16-byte aligned rows
-    static const bool no_mfma = getenv("VK_ATTENTION_MFMA") && getenv("VK_ATTENTION_MFMA")[0] == '0';     // A/B switch
-    if (!no_mfma && (dt == VK_F16 || dt == VK_BF16) && (d == 32 || d == 64) && Lq <= 48 && Lk <= 64 && ldq % 8 == 0 && ldk % 8 == 0 &&
-        ldv % 8 == 0 && ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0) {
+    // the kernel is the routing function's to pick (attention_tiled.hip): the matrix-core form takes 16-bit types, head dim
+    // 32 / 64, up to 48 queries and 64 keys, 16-byte aligned rows (A/B switch VK_ATTENTION_MFMA=0); the LDS form whatever fits
+    // 160 KiB; beyond that the online-soft-max kernels
+    const int route = attention_route(Lq, Lk, d, dt, ldq, ldk, ldv, ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0, 0);
+    if (route < 0) return -route;
+    if (route == VK_ATT_ROUTE_TILED || route == VK_ATT_ROUTE_STREAM)
+        return launch_attention_long(route, q, ldq, k, ldk, v, ldv, mask, out, ldo, B, heads, Lq, Lk, d, dt, s);
+    const size_t smem = ((size_t)(Lq + Lk) * (d + 1) + (size_t)Lk * d + (size_t)Lq * (Lk + 1)) * sizeof(float);
+    const float scale = 1.0f / sqrtf((float)d);
+    if (route == VK_ATT_ROUTE_MFMA) {
         const int total = B * heads;
         const dim3 grid((total + 3) / 4), block(256);
 #define VK_ATTM(T, DD)                                                                                                   \

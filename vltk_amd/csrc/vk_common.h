@@ -156,6 +156,13 @@ int set_max_lds(const void *kernel, size_t bytes);
 template <typename... A>
 static inline int set_max_lds(void (*kernel)(A...), size_t bytes) { return set_max_lds(reinterpret_cast<const void *>(kernel), bytes); }
 
+// ---- attention_tiled.hip ----
+// the VK_ATT_ROUTE_* vk_attention / vk_attention_tiled switch on (host only; vk_attention_route), or -VK_E*
+int attention_route(int Lq, int Lk, int d, vk_dtype dt, int ldq, int ldk, int ldv, int aligned16, int tiled_entry);
+// VK_ATT_ROUTE_TILED / VK_ATT_ROUTE_STREAM launches
+int launch_attention_long(int route, const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, const float *mask,
+                          void *out, int ldo, int B, int heads, int Lq, int Lk, int d, vk_dtype dt, hipStream_t s);
+
 // ---- pack.hip (host only) ----
 void to_dt(const float *src, size_t n, vk_dtype dt, void *dst);       // float -> f16 / bf16 (nearest even) / f32
 

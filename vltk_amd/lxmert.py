@@ -214,7 +214,15 @@ class LxmertEncoder:
     def _attention(self, q, k, v, mask, B, Lq, Lk):
         H, heads = self.cfg["hidden_size"], self.cfg["num_attention_heads"]
         out = torch.empty((B * Lq, H), dtype=self.tdt, device=self.device)
-        L.call("vk_attention", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+        # 16-bit: the small matrix-core kernel where it reaches (20 / 36 tokens: bits unchanged), the tiled one at every other
+        # length; fp32 stays on vk_attention (the LDS kernel where a head fits it, the streaming kernel beyond)
+        name = "vk_attention"
+        if self.dt != L.VK_F32:
+            aligned = int((q.data_ptr() | k.data_ptr() | v.data_ptr()) % 16 == 0)
+            route = L.load().vk_attention_route(Lq, Lk, H // heads, self.dt, q.stride(0), k.stride(0), v.stride(0), aligned, 0)
+            if route != L.VK_ATT_ROUTE_MFMA:
+                name = "vk_attention_tiled"
+        L.call(name, q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
                mask.data_ptr() if mask is not None else None, out.data_ptr(), H, B, heads, Lq, Lk, H // heads, self.dt, stream(self.device))
         return out
 
