@@ -502,6 +502,20 @@ int vk_attention_tiled(const void *q, int ldq, const void *k, int ldk, const voi
 #define VK_ATT_ROUTE_STREAM 3   /* attention_stream_kernel: 64-key fp32 tiles in LDS, online soft-max */
 int vk_attention_route(int Lq, int Lk, int d, vk_dtype dt, int ldq, int ldk, int ldv, int aligned16, int tiled_entry);
 
+/* VisualBertEmbeddings.forward (transformers modeling_visual_bert.py v5.15 :72-168) for the single-stream encoder: one launch
+ * writes y [B * (Lt + V), C], text rows first in each batch entry, with no concatenation in between:
+ *   text row   (b, t)       LayerNorm(word[ids[b,t]] + token_type[tt[b,t]] + position[t])
+ *   visual row (b, Lt + j)  LayerNorm(proj[b*V + j] + visual_token_type[vtt[b,j]] + visual_position[0] + mean_a position[align[b,j,a]])
+ * proj [B*V, ldp] is visual_projection's output (vk_linear).  image_text_alignment [B, V, A] int32 (A <= 16, -1 pads; the mean
+ * is over the valid entries, summed in order of a, and a box with none adds zero) or NULL with A = 0.  Tables, proj and y in dt;
+ * sums, statistics and the affine in fp32.  C <= 2048; Lt <= max_position.  The kernel clamps every table index into its table;
+ * refusing bad ids is the caller's. */
+int vk_visualbert_embed(const int64_t *input_ids, const int64_t *token_type_ids, const int64_t *visual_token_type_ids,
+                        const int32_t *image_text_alignment, int A, int B, int Lt, int V, const void *word, int vocab,
+                        const void *position, int max_position, const void *token_type, const void *visual_token_type,
+                        int type_vocab, const void *visual_position, const void *proj, int ldp, const float *gamma,
+                        const float *beta, void *y, int C, float eps, vk_dtype dt, void *stream);
+
 /* ---- N4: FPN-side ops (what north_star names; the reference holds only fragments, see oracle/fpn_oracle.py) ---- */
 
 /* RoIAlign over a feature pyramid (torchvision roi_align semantics, `aligned` as detectron2's ROIAlignV2; the level loop of

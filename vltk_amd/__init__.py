@@ -20,4 +20,7 @@ def __getattr__(name):
     if name == "LxmertEncoder":          # N3: the encoder that consumes the extractor's output
         from .lxmert import LxmertEncoder
         return LxmertEncoder
+    if name in ("VisualBertModel", "VisualBertForQuestionAnswering"):   # the single-stream encoder and its VQA head
+        from . import visualbert
+        return getattr(visualbert, name)
     raise AttributeError(name)

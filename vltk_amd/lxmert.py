@@ -89,26 +89,35 @@ def make_lxmert_qa_state_dict(cfg, num_qa_labels, seed=0):
 def make_lxmert_state_dict(cfg, seed=0):
     """Seeded synthetic weights (no checkpoint can be fetched offline): BERT-style N(0, 0.05) matrices (wider than the
     0.02 init so every layer matters in a parity check), LayerNorm gamma ~ U(0.5, 1.5), small biases."""
-    sd = {}
-    for name, shape in lxmert_param_spec(cfg):
-        g = np.random.Generator(np.random.PCG64([seed, zlib.crc32(name.encode())]))
-        if "LayerNorm.weight" in name or "layer_norm.weight" in name:
-            v = g.uniform(0.5, 1.5, shape)
-        elif name.endswith(".bias"):
-            v = g.standard_normal(shape) * 0.05
-        else:
-            v = g.standard_normal(shape) * 0.05
-        sd[name] = v.astype(np.float32)
-    return sd
+    return {name: seeded_tensor(name, shape, seed) for name, shape in lxmert_param_spec(cfg)}
 
 
-class LxmertEncoder:
-    """`transformers.LxmertModel` on the HIP path: `model(input_ids, visual_feats, visual_pos, attention_mask=None,
-    visual_attention_mask=None, token_type_ids=None)` -> (language_output, vision_output, pooled_output)."""
+def seeded_tensor(name, shape, seed):
+    """One tensor of the synthetic state dicts: its own generator, keyed by the seed and the tensor's name."""
+    g = np.random.Generator(np.random.PCG64([seed, zlib.crc32(name.encode())]))
+    if "LayerNorm.weight" in name or "layer_norm.weight" in name:
+        v = g.uniform(0.5, 1.5, shape)
+    else:
+        v = g.standard_normal(shape) * 0.05
+    return v.astype(np.float32)
+
+
+def _to_numpy(sd):
+    return {k: (v.detach().cpu().float().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32)) for k, v in sd.items()}
+
+
+def additive_mask(m, device):
+    """[B, L] 1 / 0 mask -> the additive `(1 - m) * finfo.min` row the attention kernels take (LxmertModel.forward :766-784)."""
+    return None if m is None else ((1.0 - m.to(device, torch.float32)) * torch.finfo(torch.float32).min).contiguous()
+
+
+class BertOps:
+    """What the BERT-style encoders of this package share (LxmertEncoder below, VisualBertModel in visualbert.py): the packed
+    weights, the ops over the C ABI and the BERT layer built from them."""
 
     def __init__(self, config, precision="bf16", device="cuda:0"):
         if not torch.cuda.is_available():
-            raise RuntimeError("vltk_amd.LxmertEncoder needs a GPU: there is no CPU fallback")
+            raise RuntimeError(f"vltk_amd.{type(self).__name__} needs a GPU: there is no CPU fallback")
         L.load()
         self.cfg = dict(config)
         self.dt, self.tdt = DTYPES[precision]
@@ -128,63 +137,37 @@ class LxmertEncoder:
         wp, bp = pack(wk, self.dt, bias=b)
         return torch.from_numpy(wp).to(self.device), torch.from_numpy(bp).to(self.device), N, Kp
 
-    def load_state_dict(self, sd, strict=True):
-        sd = {k: (v.detach().cpu().float().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32)) for k, v in sd.items()}
-        want = dict(lxmert_param_spec(self.cfg))
+    def _check_state_dict(self, sd, want, strict):
+        """Strict load: no missing and no unexpected key; always: the shape of every tensor the model takes."""
         if strict:
             missing, extra = sorted(set(want) - set(sd)), sorted(set(sd) - set(want))
             if missing or extra:
-                raise RuntimeError(f"LxmertEncoder.load_state_dict: missing {missing[:4]} unexpected {extra[:4]}")
+                raise RuntimeError(f"{type(self).__name__}.load_state_dict: missing {missing[:4]} unexpected {extra[:4]}")
         for k, shp in want.items():
             if tuple(sd[k].shape) != tuple(shp):
                 raise RuntimeError(f"weight '{k}' has shape {tuple(sd[k].shape)}, expected {tuple(shp)}")
 
-        def lin(name, *parts):      # one GEMM for several nn.Linear applied to the same input (rows concatenated)
-            w = np.concatenate([sd[p + ".weight"] for p in parts], 0)
-            b = np.concatenate([sd[p + ".bias"] for p in parts], 0)
-            self._lin[name] = self._pack(w, b)
+    def _load_lin(self, sd, name, *parts):   # one GEMM for several nn.Linear applied to the same input (rows concatenated)
+        w = np.concatenate([sd[p + ".weight"] for p in parts], 0)
+        b = np.concatenate([sd[p + ".bias"] for p in parts], 0)
+        self._lin[name] = self._pack(w, b)
 
-        def ln(name, p):
-            self._ln[name] = (torch.from_numpy(sd[p + ".weight"]).to(self.device), torch.from_numpy(sd[p + ".bias"]).to(self.device))
+    def _load_ln(self, sd, name):
+        self._ln[name] = (torch.from_numpy(sd[name + ".weight"]).to(self.device), torch.from_numpy(sd[name + ".bias"]).to(self.device))
 
-        def att_self(p):            # q, k, v of a self-attention share the input: one GEMM
-            lin(p + ".qkv", p + ".query", p + ".key", p + ".value")
+    def _load_tab(self, sd, name):            # embedding tables stay in the storage type
+        self._tab[name] = torch.from_numpy(sd[f"embeddings.{name}.weight"]).to(self.device).to(self.tdt).contiguous()
 
-        def bert_layer(p):
-            att_self(p + ".attention.self")
-            lin(p + ".attention.output.dense", p + ".attention.output.dense")
-            ln(p + ".attention.output.LayerNorm", p + ".attention.output.LayerNorm")
-            lin(p + ".intermediate.dense", p + ".intermediate.dense")
-            lin(p + ".output.dense", p + ".output.dense")
-            ln(p + ".output.LayerNorm", p + ".output.LayerNorm")
+    def _load_att_self(self, sd, p):          # q, k, v of a self-attention share the input: one GEMM
+        self._load_lin(sd, p + ".qkv", p + ".query", p + ".key", p + ".value")
 
-        for t in ("word_embeddings", "position_embeddings", "token_type_embeddings"):
-            self._tab[t] = torch.from_numpy(sd[f"embeddings.{t}.weight"]).to(self.device).to(self.tdt).contiguous()
-        ln("embeddings.LayerNorm", "embeddings.LayerNorm")
-        lin("encoder.visn_fc.visn_fc", "encoder.visn_fc.visn_fc")
-        lin("encoder.visn_fc.box_fc", "encoder.visn_fc.box_fc")
-        ln("encoder.visn_fc.visn_layer_norm", "encoder.visn_fc.visn_layer_norm")
-        ln("encoder.visn_fc.box_layer_norm", "encoder.visn_fc.box_layer_norm")
-        for i in range(self.cfg["l_layers"]):
-            bert_layer(f"encoder.layer.{i}")
-        for i in range(self.cfg["r_layers"]):
-            bert_layer(f"encoder.r_layers.{i}")
-        for i in range(self.cfg["x_layers"]):
-            p = f"encoder.x_layers.{i}"
-            lin(p + ".visual_attention.att.q", p + ".visual_attention.att.query")
-            lin(p + ".visual_attention.att.kv", p + ".visual_attention.att.key", p + ".visual_attention.att.value")
-            lin(p + ".visual_attention.output.dense", p + ".visual_attention.output.dense")
-            ln(p + ".visual_attention.output.LayerNorm", p + ".visual_attention.output.LayerNorm")
-            for m in ("lang", "visn"):
-                att_self(f"{p}.{m}_self_att.self")
-                lin(f"{p}.{m}_self_att.output.dense", f"{p}.{m}_self_att.output.dense")
-                ln(f"{p}.{m}_self_att.output.LayerNorm", f"{p}.{m}_self_att.output.LayerNorm")
-                lin(f"{p}.{m}_inter.dense", f"{p}.{m}_inter.dense")
-                lin(f"{p}.{m}_output.dense", f"{p}.{m}_output.dense")
-                ln(f"{p}.{m}_output.LayerNorm", f"{p}.{m}_output.LayerNorm")
-        lin("pooler.dense", "pooler.dense")
-        self._loaded = True
-        return self
+    def _load_bert_layer(self, sd, p):
+        self._load_att_self(sd, p + ".attention.self")
+        self._load_lin(sd, p + ".attention.output.dense", p + ".attention.output.dense")
+        self._load_ln(sd, p + ".attention.output.LayerNorm")
+        self._load_lin(sd, p + ".intermediate.dense", p + ".intermediate.dense")
+        self._load_lin(sd, p + ".output.dense", p + ".output.dense")
+        self._load_ln(sd, p + ".output.LayerNorm")
 
     def eval(self):
         return self
@@ -207,7 +190,7 @@ class LxmertEncoder:
         g, b = self._ln[name]
         M, Cc = x.shape
         y = torch.empty((M, Cc), dtype=self.tdt, device=self.device) if out is None else out
-        L.call("vk_layernorm", x.data_ptr(), x.stride(0), g.data_ptr(), b.data_ptr(), y.data_ptr(), y.stride(0), M, Cc, LN_EPS, scale,
+        L.call("vk_layernorm", x.data_ptr(), x.stride(0), g.data_ptr(), b.data_ptr(), y.data_ptr(), y.stride(0), M, Cc, self.cfg.get("layer_norm_eps", LN_EPS), scale,
                int(accumulate), self.dt, stream(self.device))
         return y
 
@@ -234,14 +217,6 @@ class LxmertEncoder:
         t = self._linear(ctx, p + ".output.dense", residual=x)
         return self._layernorm(t, p + ".output.LayerNorm")
 
-    def _cross_att_block(self, p, x, ctx_in, ctx_mask, B, Lx, Lc):   # LxmertCrossAttentionLayer :283-295
-        H = self.cfg["hidden_size"]
-        q = self._linear(x, p + ".att.q")
-        kv = self._linear(ctx_in, p + ".att.kv")
-        ctx = self._attention(q, kv[:, :H], kv[:, H:], ctx_mask, B, Lx, Lc)
-        t = self._linear(ctx, p + ".output.dense", residual=x)
-        return self._layernorm(t, p + ".output.LayerNorm")
-
     def _ffn(self, inter, outp, x):                     # LxmertIntermediate + LxmertOutput :319-342
         h = self._linear(x, inter + ".dense", act=L.VK_ACT_GELU)
         t = self._linear(h, outp + ".dense", residual=x)
@@ -250,6 +225,59 @@ class LxmertEncoder:
     def _bert_layer(self, p, x, mask, B, Lx):           # LxmertLayer :345-358
         a = self._self_att_block(p + ".attention", x, mask, B, Lx)
         return self._ffn(p + ".intermediate", p + ".output", a)
+
+    def _pooler(self, x, B, Lx):                        # LxmertPooler :566-572: tanh(dense(first token of each sequence))
+        w, bb, N, Kp = self._lin["pooler.dense"]        # the first rows are picked by a stride-Lx 1x1 "convolution"
+        H = self.cfg["hidden_size"]
+        pooled = torch.empty((B, H), dtype=self.tdt, device=self.device)
+        L.call("vk_conv2d", x.data_ptr(), B, Lx, 1, H, w.data_ptr(), bb.data_ptr(), None, pooled.data_ptr(), H, H, 1, 1, Lx, 0, 1, 1,
+               L.VK_ACT_TANH, self.dt, self.dt, stream(self.device))
+        return pooled
+
+
+class LxmertEncoder(BertOps):
+    """`transformers.LxmertModel` on the HIP path: `model(input_ids, visual_feats, visual_pos, attention_mask=None,
+    visual_attention_mask=None, token_type_ids=None)` -> (language_output, vision_output, pooled_output)."""
+
+    def load_state_dict(self, sd, strict=True):
+        sd = _to_numpy(sd)
+        self._check_state_dict(sd, dict(lxmert_param_spec(self.cfg)), strict)
+        lin, ln = (lambda name, *parts: self._load_lin(sd, name, *parts)), (lambda name: self._load_ln(sd, name))
+        for t in ("word_embeddings", "position_embeddings", "token_type_embeddings"):
+            self._load_tab(sd, t)
+        ln("embeddings.LayerNorm")
+        lin("encoder.visn_fc.visn_fc", "encoder.visn_fc.visn_fc")
+        lin("encoder.visn_fc.box_fc", "encoder.visn_fc.box_fc")
+        ln("encoder.visn_fc.visn_layer_norm")
+        ln("encoder.visn_fc.box_layer_norm")
+        for i in range(self.cfg["l_layers"]):
+            self._load_bert_layer(sd, f"encoder.layer.{i}")
+        for i in range(self.cfg["r_layers"]):
+            self._load_bert_layer(sd, f"encoder.r_layers.{i}")
+        for i in range(self.cfg["x_layers"]):
+            p = f"encoder.x_layers.{i}"
+            lin(p + ".visual_attention.att.q", p + ".visual_attention.att.query")
+            lin(p + ".visual_attention.att.kv", p + ".visual_attention.att.key", p + ".visual_attention.att.value")
+            lin(p + ".visual_attention.output.dense", p + ".visual_attention.output.dense")
+            ln(p + ".visual_attention.output.LayerNorm")
+            for m in ("lang", "visn"):
+                self._load_att_self(sd, f"{p}.{m}_self_att.self")
+                lin(f"{p}.{m}_self_att.output.dense", f"{p}.{m}_self_att.output.dense")
+                ln(f"{p}.{m}_self_att.output.LayerNorm")
+                lin(f"{p}.{m}_inter.dense", f"{p}.{m}_inter.dense")
+                lin(f"{p}.{m}_output.dense", f"{p}.{m}_output.dense")
+                ln(f"{p}.{m}_output.LayerNorm")
+        lin("pooler.dense", "pooler.dense")
+        self._loaded = True
+        return self
+
+    def _cross_att_block(self, p, x, ctx_in, ctx_mask, B, Lx, Lc):   # LxmertCrossAttentionLayer :283-295
+        H = self.cfg["hidden_size"]
+        q = self._linear(x, p + ".att.q")
+        kv = self._linear(ctx_in, p + ".att.kv")
+        ctx = self._attention(q, kv[:, :H], kv[:, H:], ctx_mask, B, Lx, Lc)
+        t = self._linear(ctx, p + ".output.dense", residual=x)
+        return self._layernorm(t, p + ".output.LayerNorm")
 
     def capture(self, input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None):
         """Capture one forward for these input SHAPES into a HIP graph (~430 launches become one graph launch: the
@@ -294,12 +322,8 @@ class LxmertEncoder:
         H = cfg["hidden_size"]
         ids = input_ids.to(dev, torch.int64).contiguous()
         tts = (torch.zeros_like(ids) if token_type_ids is None else token_type_ids.to(dev, torch.int64).contiguous())
-        fmin = torch.finfo(torch.float32).min
-
-        def ext(m):                                     # LxmertModel.forward :766-784
-            return None if m is None else ((1.0 - m.to(dev, torch.float32)) * fmin).contiguous()
-        lmask = ext(torch.ones((B, Lq), device=dev) if attention_mask is None else attention_mask)
-        vmask = ext(visual_attention_mask)
+        lmask = additive_mask(torch.ones((B, Lq), device=dev) if attention_mask is None else attention_mask, dev)
+        vmask = additive_mask(visual_attention_mask, dev)
         # embeddings :191-214
         lang = torch.empty((B * Lq, H), dtype=self.tdt, device=dev)
         g, b = self._ln["embeddings.LayerNorm"]
@@ -325,12 +349,7 @@ class LxmertEncoder:
             v_att = self._self_att_block(p + ".visn_self_att", v_att, vmask, B, V)
             lang = self._ffn(p + ".lang_inter", p + ".lang_output", l_att)
             visn = self._ffn(p + ".visn_inter", p + ".visn_output", v_att)
-        # pooler :566-572: tanh(dense(first token)); the first rows are picked by a stride-Lq 1x1 "convolution"
-        w, bb, N, Kp = self._lin["pooler.dense"]
-        pooled = torch.empty((B, H), dtype=self.tdt, device=dev)
-        L.call("vk_conv2d", lang.data_ptr(), B, Lq, 1, H, w.data_ptr(), bb.data_ptr(), None, pooled.data_ptr(), H, H, 1, 1, Lq, 0, 1, 1,
-               L.VK_ACT_TANH, self.dt, self.dt, stream(self.device))
-        return lang.view(B, Lq, H), visn.view(B, V, H), pooled
+        return lang.view(B, Lq, H), visn.view(B, V, H), self._pooler(lang, B, Lq)
 
 
 class LxmertForQuestionAnswering:
@@ -343,7 +362,7 @@ class LxmertForQuestionAnswering:
         self.num_qa_labels = int(num_qa_labels)
 
     def load_state_dict(self, sd, strict=True):
-        sd = {k: (v.detach().cpu().float().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32)) for k, v in sd.items()}
+        sd = _to_numpy(sd)
         want = dict(lxmert_qa_param_spec(self.lxmert.cfg, self.num_qa_labels))
         if strict and set(want) != set(sd):
             raise RuntimeError(f"LxmertForQuestionAnswering.load_state_dict: missing {sorted(set(want) - set(sd))[:4]} "
