@@ -516,6 +516,20 @@ int vk_visualbert_embed(const int64_t *input_ids, const int64_t *token_type_ids,
                         int type_vocab, const void *visual_position, const void *proj, int ldp, const float *gamma,
                         const float *beta, void *y, int C, float eps, vk_dtype dt, void *stream);
 
+/* The embedding stage of a Vision Transformer (transformers modeling_vit.py v5.15: ViTPatchEmbeddings.forward :62-69,
+ * ViTEmbeddings.forward :129-161) as two launches around one vk_linear.
+ * vk_vit_patchify: pixel_values [B, C, Hi, Wi] fp32 NCHW -> rows [B * gh * gw, ldk] in dt (gh = Hi / P, gw = Wi / P).  Row
+ * b*gh*gw + i*gw + j holds patch (i, j) in the order (c, py, px), the flattening of Conv2d(C, H, P, stride = P).weight.view(H, -1),
+ * so the projection is vk_linear against that matrix; the columns C*P*P .. ldk - 1 (the GEMM's K-tile padding) are written as zero.
+ * VK_EINVAL: B < 1, P < 1, C outside 1..4, Hi or Wi no positive multiple of P, ldk < C*P*P, rows that are no whole 16-byte chunks
+ * (ldk * sizeof(dt) % 16, or a base that is not 16-byte aligned), 2^31 rows or more. */
+int vk_vit_patchify(const float *pixel_values, int B, int C, int Hi, int Wi, int P, void *rows, int ldk, vk_dtype dt, void *stream);
+/* vk_vit_assemble: x [B * (N + 1), H]; row b*(N+1) = cls_token + position[0], row b*(N+1) + 1 + n = proj[b*N + n] + position[1 + n].
+ * proj [B*N, ldp] is the patch projection's output (bias added; its columns past H are never read), cls_token [H] and position
+ * [N + 1, H] in dt; the sum is formed in fp32 and rounded once.  VK_EINVAL: B or N < 1, H < 1, ldp < H, 2^31 rows or more. */
+int vk_vit_assemble(const void *proj, int ldp, const void *cls_token, const void *position, int B, int N, void *x, int H,
+                    vk_dtype dt, void *stream);
+
 /* ---- N4: FPN-side ops (what north_star names; the reference holds only fragments, see oracle/fpn_oracle.py) ---- */
 
 /* RoIAlign over a feature pyramid (torchvision roi_align semantics, `aligned` as detectron2's ROIAlignV2; the level loop of

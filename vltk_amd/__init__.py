@@ -23,4 +23,7 @@ def __getattr__(name):
     if name in ("VisualBertModel", "VisualBertForQuestionAnswering"):   # the single-stream encoder and its VQA head
         from . import visualbert
         return getattr(visualbert, name)
+    if name in ("ViTModel", "ViTForImageClassification", "vit_config", "patch_tokens", "vit_patch_boxes"):   # the patch-token image encoder
+        from . import vit
+        return getattr(vit, name)
     raise AttributeError(name)

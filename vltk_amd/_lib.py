@@ -137,6 +137,8 @@ SIGNATURES = {
     "vk_attention_tiled": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vk_attention_route": (_I, [_I] * 9),
     "vk_visualbert_embed": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _F, _I, _P]),
+    "vk_vit_patchify": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "vk_vit_assemble": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _P]),
     "vk_roi_align": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "vk_assign_levels": (_I, [_P, _I, _I, _I, _I, _F, _I, _P, _P]),
     "vk_upsample2x_add": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
