@@ -132,3 +132,30 @@ def test_refusals_come_before_any_device_call(lib):
     assert lib.vk_attention_route(8, 8, 64, L.VK_I32, 64, 64, 64, 1, 1) == -L.VK_EINVAL
     with pytest.raises(ValueError, match="null"):
         L.call("vk_attention_tiled", None, 64, fake, 64, fake, 64, None, fake, 64, 1, 1, 8, 8, 64, L.VK_F32, None)
+
+
+def test_the_encoders_rule_for_picking_an_entry_point(lib, monkeypatch):
+    """BertOps.attention_entry, the one statement of what a forward calls: 16-bit goes to vk_attention where the small
+    matrix-core kernel reaches and to vk_attention_tiled everywhere else, fp32 always to vk_attention.  The table is written
+    out, not computed; d = 64, 12 heads, ld = 3 * 768, aligned pointers unless a row says otherwise."""
+    from vltk_amd.bert_ops import BertOps
+
+    def entry(dt, Lq, Lk, d=64, aligned=1):
+        ops = object.__new__(BertOps)
+        ops.cfg, ops.dt = dict(hidden_size=12 * d, num_attention_heads=12), dt
+        name, r = ops.attention_entry(Lq, Lk, 3 * 768, 3 * 768, 3 * 768, aligned)
+        return name, NAMES[r]
+
+    for dt in (L.VK_BF16, L.VK_F16):
+        for Lq, Lk in ((20, 20), (36, 36), (20, 36), (36, 20), (47, 47), (48, 64)):
+            assert entry(dt, Lq, Lk) == ("vk_attention", "mfma"), (dt, Lq, Lk)
+        for Lq, Lk in ((49, 49), (48, 65), (56, 56), (197, 197), (577, 577)):
+            assert entry(dt, Lq, Lk) == ("vk_attention_tiled", "tiled"), (dt, Lq, Lk)
+    assert entry(L.VK_BF16, 100, 100, d=48) == ("vk_attention_tiled", "stream")
+    assert entry(L.VK_BF16, 20, 36, aligned=0) == ("vk_attention_tiled", "stream")
+    for Lq, Lk in ((20, 36), (100, 100), (127, 127)):
+        assert entry(L.VK_F32, Lq, Lk) == ("vk_attention", "lds"), (Lq, Lk)
+    for Lq, Lk in ((128, 128), (197, 197)):
+        assert entry(L.VK_F32, Lq, Lk) == ("vk_attention", "stream"), (Lq, Lk)
+    monkeypatch.setenv("VK_ATTENTION_MFMA", "0")
+    assert entry(L.VK_BF16, 20, 36) == ("vk_attention_tiled", "stream")

@@ -50,7 +50,6 @@ def timed(fn, sync, min_seconds=0.5):
 def child(model, V, batches):
     import numpy as np
     import torch
-    from vltk_amd import _lib as L
     from lxmert_bench import gflop as lxmert_gflop
     from vltk_amd.lxmert import LxmertEncoder, lxmert_config, make_lxmert_state_dict
     from vltk_amd.visualbert import VisualBertModel, make_visualbert_state_dict, visualbert_config
@@ -79,9 +78,7 @@ def child(model, V, batches):
             none5 = (None,) * 5
             x, mask = m._embed(ids, feats, *none5)
             qkv = m._linear(x, "encoder.layer.0.attention.self.qkv")
-            route = L.load().vk_attention_route(Lx, Lx, H // cfg["num_attention_heads"], m.dt, 3 * H, 3 * H, 3 * H, 1, 0)
-            if route != L.VK_ATT_ROUTE_MFMA:
-                route = L.load().vk_attention_route(Lx, Lx, H // cfg["num_attention_heads"], m.dt, 3 * H, 3 * H, 3 * H, 1, 1)
+            _, route = m.attention_entry(Lx, Lx, 3 * H, 3 * H, 3 * H, 1)
 
             def events(fn, reps=20):
                 fn()

@@ -70,9 +70,7 @@ def child_encoder():
         graph, _ = timed(lambda: replay(pix), sync)
         N = (side // P) ** 2
         Lx = N + 1
-        route = L.load().vk_attention_route(Lx, Lx, H // cfg["num_attention_heads"], m.dt, 3 * H, 3 * H, 3 * H, 1, 0)
-        if route != L.VK_ATT_ROUTE_MFMA:
-            route = L.load().vk_attention_route(Lx, Lx, H // cfg["num_attention_heads"], m.dt, 3 * H, 3 * H, 3 * H, 1, 1)
+        _, route = m.attention_entry(Lx, Lx, 3 * H, 3 * H, 3 * H, 1)
         # the embedding stage (patch rows + projection GEMM + assembly) and its two new kernels alone
         Kp = m._lin[m._PROJ][3]
         rows = torch.empty((B * N, Kp), dtype=m.tdt, device=m.device)

@@ -29,11 +29,6 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 // (value, index) arg-max with "first index wins" on ties
 __device__ __forceinline__ void wave_argmax(float &v, int &i) {
 #pragma unroll

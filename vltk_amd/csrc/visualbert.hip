@@ -8,7 +8,7 @@
 //   then LayerNorm over the row: sums, statistics and the affine in fp32, one rounding to the storage type on the way out.
 //
 // One wave per row, four rows per workgroup; the text / visual branch is wave-uniform.  A lane owns the chunks lane, lane + 64, ...
-// of the row: 16-byte chunks when the row length allows (layernorm_vec_kernel's layout, lxmert.hip), single elements otherwise.
+// of the row: 16-byte chunks when the row length allows (layernorm_vec_kernel's layout, layernorm.hip), single elements otherwise.
 // No LDS, no atomics.  Every table index is clamped into its table, so a bad id reads a wrong row, never memory outside one;
 // refusing bad ids is the caller's job (vltk_amd/visualbert.py does, before the launch).
 #include "vk_common.h"

@@ -156,13 +156,6 @@ int set_max_lds(const void *kernel, size_t bytes);
 template <typename... A>
 static inline int set_max_lds(void (*kernel)(A...), size_t bytes) { return set_max_lds(reinterpret_cast<const void *>(kernel), bytes); }
 
-// ---- attention_tiled.hip ----
-// the VK_ATT_ROUTE_* vk_attention / vk_attention_tiled switch on (host only; vk_attention_route), or -VK_E*
-int attention_route(int Lq, int Lk, int d, vk_dtype dt, int ldq, int ldk, int ldv, int aligned16, int tiled_entry);
-// VK_ATT_ROUTE_TILED / VK_ATT_ROUTE_STREAM launches
-int launch_attention_long(int route, const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, const float *mask,
-                          void *out, int ldo, int B, int heads, int Lq, int Lk, int d, vk_dtype dt, hipStream_t s);
-
 // ---- pack.hip (host only) ----
 void to_dt(const float *src, size_t n, vk_dtype dt, void *dst);       // float -> f16 / bf16 (nearest even) / f32
 
@@ -231,6 +224,18 @@ int launch_chosen_deltas(const void *x, int ldx, const void *w, const float *bia
                          int K, float *out, vk_dtype dt, hipStream_t s);
 int launch_roi_final(RoiFinalArgs &a, int N, hipStream_t s);
 int launch_make_rois(const float *boxes, int N, int R, float *rois, hipStream_t s);
+
+// One element of any storage type as fp32, and back; the sum of a value over the 64 lanes of a wave, left in every lane.
+// Shared by attention.hip, layernorm.hip and roi_out.hip.
+template <typename T>
+__device__ __forceinline__ float ldf(const T *p) { return (float)*p; }
+template <typename T>
+__device__ __forceinline__ void stf(T *p, float v) { *p = (T)v; }
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 
 // Sort key of a score for an ascending sort that ranks scores descending (-0 ranks as +0); the low word of the 64-bit key
 // holds the row index, so ties go to the lower index.  Shared by roi_out.hip and per_class.hip.

@@ -4,7 +4,7 @@
 Host-side mirror of `transformers.VisualBertModel` / `VisualBertForQuestionAnswering` (modeling_visual_bert.py v5.15:
 `VisualBertEmbeddings.forward` :72-168, `VisualBertModel.forward` :599-662, `VisualBertForQuestionAnswering.forward` :1106-1132)
 with the state-dict key layout of those classes, so a real checkpoint's tensors load by name.  Text and boxes form ONE
-sequence (text first); the layers are BERT layers, shared with `LxmertEncoder` through `lxmert.BertOps`.  What is new here is
+sequence (text first); the layers are BERT layers, shared with `LxmertEncoder` through `bert_ops.BertOps`.  What is new here is
 the embedding stage (`vk_visualbert_embed`, csrc/visualbert.hip) and the gather head.  All arithmetic runs in `libvltk_hip.so`;
 torch only owns the device buffers.  No CPU fallback.
 
@@ -15,8 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .bert_ops import LN_EPS, BertOps, additive_mask, bert_layer_spec, seeded_tensor, to_numpy
 from .layers import stream
-from .lxmert import LN_EPS, BertOps, _bert_layer, _to_numpy, additive_mask, seeded_tensor
 
 DEFAULT_CONFIG = dict(vocab_size=30522, hidden_size=768, num_attention_heads=12, num_hidden_layers=12, intermediate_size=3072,
                       max_position_embeddings=512, type_vocab_size=2, visual_embedding_dim=512, layer_norm_eps=LN_EPS,
@@ -45,7 +45,7 @@ def visualbert_param_spec(cfg):
             ("embeddings.visual_token_type_embeddings.weight", (T, H)), ("embeddings.visual_position_embeddings.weight", (P, H)),
             ("embeddings.visual_projection.weight", (H, cfg["visual_embedding_dim"])), ("embeddings.visual_projection.bias", (H,))]
     for i in range(cfg["num_hidden_layers"]):
-        spec += _bert_layer(f"encoder.layer.{i}", H, I)
+        spec += bert_layer_spec(f"encoder.layer.{i}", H, I)
     spec += [("pooler.dense.weight", (H, H)), ("pooler.dense.bias", (H,))]
     return spec
 
@@ -111,7 +111,7 @@ class VisualBertModel(BertOps):
         super().__init__(visualbert_config(**config), precision, device)
 
     def load_state_dict(self, sd, strict=True):
-        sd = _to_numpy(sd)
+        sd = to_numpy(sd)
         self._check_state_dict(sd, dict(visualbert_param_spec(self.cfg)), strict)
         for t in ("word_embeddings", "position_embeddings", "token_type_embeddings", "visual_token_type_embeddings",
                   "visual_position_embeddings"):
@@ -170,15 +170,7 @@ class VisualBertModel(BertOps):
         args = (input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids, visual_token_type_ids, image_text_alignment)
         self._check(*args)
         static = [None if a is None else a.to(dev).clone() for a in args]
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):                    # warm-up: one-time attribute / lazy-init calls must not be captured
-            self._forward(*static)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            outs = self._forward(*static)
+        graph, outs = self._capture(self._forward, static)
 
         def replay(input_ids, visual_embeds, attention_mask=None, visual_attention_mask=None, token_type_ids=None,
                    visual_token_type_ids=None, image_text_alignment=None):
@@ -207,8 +199,7 @@ class VisualBertModel(BertOps):
     def _embed(self, input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids, visual_token_type_ids,
                image_text_alignment):
         """-> (LayerNormed embeddings [B * (Lt + V), H], additive mask [B, Lt + V])."""
-        if not self._loaded:
-            raise RuntimeError("VisualBertModel: load_state_dict() first")
+        self._require_loaded()
         cfg, dev, tab = self.cfg, self.device, self._tab
         B, Lt = input_ids.shape
         V = visual_embeds.shape[1]
@@ -256,7 +247,7 @@ class VisualBertForQuestionAnswering:
         self.num_labels = int(num_labels)
 
     def load_state_dict(self, sd, strict=True):
-        sd = _to_numpy(sd)
+        sd = to_numpy(sd)
         enc = self.visual_bert
         enc._check_state_dict(sd, dict(visualbert_qa_param_spec(enc.cfg, self.num_labels)), strict)
         enc.load_state_dict({k[len("visual_bert."):]: v for k, v in sd.items() if k.startswith("visual_bert.")}, strict)

@@ -21,8 +21,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
+from .bert_ops import LN_EPS, BertOps, seeded_tensor, to_numpy
 from .layers import stream
-from .lxmert import LN_EPS, BertOps, _to_numpy, seeded_tensor
 
 DEFAULT_CONFIG = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, hidden_act="gelu",
                       layer_norm_eps=LN_EPS, image_size=224, patch_size=16, num_channels=3, qkv_bias=True)
@@ -202,7 +202,7 @@ class ViTModel(BertOps):
         self._pos = {}                                    # (gh, gw) -> position table [gh * gw + 1, H] on the device, storage type
 
     def load_state_dict(self, sd, strict=True):
-        sd = rename_hub_keys(_to_numpy(sd))
+        sd = rename_hub_keys(to_numpy(sd))
         self._check_state_dict(sd, dict(vit_param_spec(self.cfg, self.add_pooling_layer)), strict)
         H = self.cfg["hidden_size"]
         self._lin[self._PROJ] = self._pack(sd[self._PROJ + ".weight"].reshape(H, -1), sd[self._PROJ + ".bias"])
@@ -249,19 +249,10 @@ class ViTModel(BertOps):
         shape raises ValueError."""
         dev = self.device
         _, gh, gw = check_pixel_values(pixel_values, self.cfg, interpolate_pos_encoding)
-        if not self._loaded:
-            raise RuntimeError("ViTModel: load_state_dict() first")
+        self._require_loaded()
         self.position_table(gh, gw)                       # host work and its copy happen before the capture
         static = pixel_values.to(dev, torch.float32).contiguous().clone()
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):                     # warm-up: one-time attribute / lazy-init calls must not be captured
-            self._forward(static)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            outs = self._forward(static)
+        graph, outs = self._capture(self._forward, [static])
 
         def replay(pixel_values):
             if tuple(pixel_values.shape) != tuple(static.shape):
@@ -274,8 +265,7 @@ class ViTModel(BertOps):
     @torch.no_grad()
     def _embed(self, pixel_values):
         """-> embeddings [B * (N + 1), H]: patch rows, the projection GEMM, then class row and positions in one launch."""
-        if not self._loaded:
-            raise RuntimeError("ViTModel: load_state_dict() first")
+        self._require_loaded()
         cfg, dev = self.cfg, self.device
         B, C, Hi, Wi = pixel_values.shape
         P, H = vit_grid(cfg)[2], cfg["hidden_size"]
@@ -329,7 +319,7 @@ class ViTForImageClassification:
             raise ValueError("num_labels must be >= 1")
 
     def load_state_dict(self, sd, strict=True):
-        sd = rename_hub_keys(_to_numpy(sd), prefix="vit.")
+        sd = rename_hub_keys(to_numpy(sd), prefix="vit.")
         enc = self.vit
         enc._check_state_dict(sd, dict(vit_classifier_param_spec(enc.cfg, self.num_labels)), strict)
         enc.load_state_dict({k[len("vit."):]: v for k, v in sd.items() if k.startswith("vit.")}, strict)
