@@ -422,6 +422,11 @@ int vk_conv_route(int N, int H, int W, int cin, int cin2, int has_residual, int 
  * W <= 14), 0 = none.  The other N - that many images run in the plain form, in a second launch when both counts are non-zero.
  * The two forms give the same bits. */
 int vk_panel_phase_images(int N, int H, int W, int dil);
+/* The tile of that phase part (host only; VK_PANEL_TALL is re-read per call): 512 = 512 rows x 128 output channels per workgroup,
+ * 256 = 256 x 256 under VK_PANEL_TALL=0, 0 = the launch has no phase part (vk_panel_phase_images == 0, or cout is not a multiple
+ * of 256 and the layer is not a panel launch at all).  A remainder of fewer than 16 images keeps the plain form's tile.  The two
+ * shapes give the same bits. */
+int vk_panel_phase_tile_rows(int N, int H, int W, int dil, int cout);
 
 /* conv3 + projection shortcut of a stride-1 BottleneckBlock as ONE f16 GEMM (`out = conv3(t) ; out += shortcut(x)`,
  * frcnn.py:970-977): y[M,cout] = relu?([x1 | x2] . W^T + bias (+ residual)), W rows = [conv3 row (cin1) | shortcut row

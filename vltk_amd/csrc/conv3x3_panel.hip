@@ -24,6 +24,9 @@
 //     the (H/2) x (W/2) grid of one phase in 16 images: a tap is a uniform shift of (dy * W/2 + dx) * 16 rows and is inside
 //     the image for all 16 rows or for none.  Validity is a per-wave scalar, a (row tile, tap) outside the image issues no MFMAs.
 //     x and y keep their natural [image][y][x] rows: only the DMA source row of a panel piece and the epilogue's row are permuted.
+//     Its tile is 512 rows x 128 channels (4x2 waves, WR = 4): 2 panel buffers of 768 rows (48 KiB) + 6 weight slots
+//     of 128 channels (8 KiB) = 144 KiB, 9 x 8 + 48 = 120 KiB through the CU per stage and 65 536 outputs instead of 176, one
+//     weight DMA piece per wave and step.  VK_PANEL_TALL=0 selects the 256 x 256 tile (same bits).
 #include <cstdio>
 #include <type_traits>
 #include <vector>
@@ -78,13 +81,17 @@ __device__ __forceinline__ PhaseBlk phase_blk(const PanelK &p, int gb) {
 }
 
 constexpr int P_NW = 6;                     // weight ring slots
-constexpr int P_WSLOT = 256 * 64;           // 16 KiB
+constexpr int P_WSLOT = 256 * 64;           // 16 KiB: 256 output channels x 64 B (the tall phase form's slot is 128 channels, 8 KiB)
 
 #define VKP_GLDS16(gptr, lptr)                                                                         \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),          \
                                      (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
 
-// panel pieces issued in the window of P_NW-2 steps before tap J (taps of the previous stage when negative)
+// The counted vmcnt of a step.  A step's POST issues, in this order, one panel piece of the next stage (taps < PP, not in the last
+// stage) and NWP weight pieces (2 per wave with 256-column tiles, 1 with 128) for step t + P_NW.  The wait at the end of step t's
+// PRE leaves outstanding exactly what was issued after the weights of step t + 1, i.e. by the POSTs of steps t-4 .. t-1 (the
+// "window" of P_NW - 2 steps): NWP * (P_NW - 2) weight pieces plus the panel pieces of those steps.
+// panel pieces issued in the window before tap J (taps of the previous stage when negative)
 template <int J, int PP>
 constexpr int panel_in_window() {
     int c = 0;
@@ -94,15 +101,30 @@ constexpr int panel_in_window() {
     }
     return c;
 }
-// weight pieces (x2) issued in that window during the LAST channel stage (its taps >= 3 issue nothing)
-template <int J>
-constexpr int last_w_in_window() {
+// Not the last stage.  FIRST: step 0 of the tile, whose window is the prologue's weight pieces alone (the prologue issues its
+// panel pieces AHEAD of its weights; only tap 0 can see a panel piece of a previous stage in its window, and only with PP > 5:
+// the window of tap J >= 1 reaches back to tap 5 + J).  Tap 8 hands over to the next stage's panel, so its wait must also cover
+// the last panel piece (tap PP - 1): behind it come only the weight pieces of taps PP-1 .. 7, NWP * (9 - PP).  With PP <= 4 that
+// is more than the window holds and changes nothing (PP = 4, NWP = 2: 10 against 8); with PP = 6, NWP = 1 it is 3 against 4 + 2.
+template <int J, int PP, int NWP, bool FIRST>
+constexpr int pieces_in_window() {
+    static_assert(PP <= 6, "a panel piece of the previous stage in the window of a tap other than 0");
+    if (FIRST) return NWP * (P_NW - 2);
+    const int c = NWP * (P_NW - 2) + panel_in_window<J, PP>();
+    const int after_panel = NWP * (9 - PP);
+    return J == 8 && after_panel < c ? after_panel : c;
+}
+// The LAST channel stage: its taps >= 3 issue no weights and none of its taps a panel piece; the taps of the stage before it
+// (negative t) issue their weights and, below PP, their panel piece (PP = 6: tap 5 is in the window of tap 0)
+template <int J, int PP, int NWP>
+constexpr int last_in_window() {
     int c = 0;
     for (int d = 1; d <= P_NW - 2; ++d) {
         int t = J - d;                     // < 0: previous stage, always issues
-        if (t < 0 || t + P_NW < 9) ++c;
+        if (t < 0 || t + P_NW < 9) c += NWP;
+        if (t < 0 && 9 + t < PP) ++c;
     }
-    return 2 * c;
+    return c;
 }
 
 template <int N>
@@ -121,22 +143,34 @@ __device__ __forceinline__ void vm_wait() {
 // PHASE: 0 = rows in their natural order; 2 = the phase-interleaved internal row order with a scalar branch around the MFMAs of
 // each (row tile, tap); 1 = the same order with the MFMAs of invalid taps still issued on zeroed fragments (tools build: the
 // addressing alone)
-template <int PP, int DBG, int TAG = 0, int MI = 8, int PHASE = 0>
+// WR: the wave grid: WR row blocks of MI*16 rows x 8 / WR column blocks of 64 channels.  2 = 256 x 256 tiles (288 x 256 at MI = 9);
+// 4 = 512 x 128 tiles (the phase form only): the same 128 x 64 per wave and the same step, but a weight slot of 128
+// channels (8 KiB, one DMA piece per wave and step) serves 512 rows, and the panel is 6 pieces (768 rows, halo 128): 72 + 48 KiB
+// through the CU per stage and 65 536 outputs instead of 144 + 32.  Rows are independent and every element sums the same products
+// in the same order, so the tile shape does not change a bit.
+template <int PP, int DBG, int TAG = 0, int MI = 8, int PHASE = 0, int WR = 2>
 __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(MI == 8 || MI == 9, "8 or 9 row tiles per wave");
-    static_assert(!PHASE || (PP == 4 && MI == 8 && !(DBG & 9)), "the phase form: halo 128 = (W / 2 + 1) * 16 at W = 14, 256-row tiles");
+    static_assert(WR == 2 || WR == 4, "2 x 4 or 4 x 2 waves");
+    static_assert(!PHASE || (PP == (WR == 4 ? 6 : 4) && MI == 8 && !(DBG & 9)), "the phase form: halo 128 = (W / 2 + 1) * 16 at W = 14, 256- or 512-row tiles");
+    static_assert(WR == 2 || PHASE == 2, "512 x 128 tiles: the phase form only (a plain res4 launch would read its panel twice)");
     static_assert(MI == 8 || !(DBG & 8), "the LDS-staged epilogue is written for 128-row halves");
-    constexpr int TILE = 2 * MI * 16;             // pixels per tile
+    constexpr int WC = 8 / WR;                    // column blocks of 64 channels
+    constexpr int CT = 64 * WC;                   // channels per tile: 256 or 128
+    constexpr int NWP = CT / 128;                 // weight DMA pieces (16 rows) per wave and step: 2 or 1
+    constexpr int WSLOT = CT * 64;                // a weight slot: 16 or 8 KiB
+    constexpr int TILE = WR * MI * 16;            // pixels per tile
     constexpr int PROWS = PP * 128;               // panel rows
     constexpr int HALO = (PROWS - TILE) / 2;      // 64 or 128 (MI = 9: 48 or 112)
     constexpr int PBYTES = PROWS * 64;
     constexpr int WBASE = 2 * PBYTES;
+    static_assert(HALO >= (PHASE ? 128 : 48) && WBASE + P_NW * WSLOT + (PP == 3 || WR == 4 ? 256 : 0) <= 160 * 1024, "halo / LDS");
     // PP = 3 leaves 16 KiB of the CU's LDS unused: 64 bytes of zeros behind the weight ring.  A fragment read of a pixel whose tap
     // falls outside the image is pointed there (two VALU instructions per read: a sign-extended bit-field and a bit-select
     // of the address) instead of zeroing the fragment afterwards (four v_cndmask per read and a compare): round 3, see DESIGN.md 6b.
     constexpr bool ZROW = PP == 3;
-    constexpr int ZOFF = WBASE + P_NW * P_WSLOT;
+    constexpr int ZOFF = WBASE + P_NW * WSLOT;
 
     int bid = blockIdx.x;
     const int nwg = p.m_tiles * p.n_tiles;        // tiles (== gridDim.x unless the launch has a dynamic tail)
@@ -144,8 +178,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     if constexpr (DBG & 4) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_k0)::"memory");
     if constexpr (PP == 3 || PHASE) {
         if (p.tile_ctr && bid >= p.static_tiles) {               // (uniform) one atomic per workgroup, through the spare LDS behind the zero row
-            // (PHASE: PP = 4 has no spare LDS; the word is the panel's first, and a second barrier keeps the prologue's DMA off it)
-            int *mail = reinterpret_cast<int *>(smem + (PHASE ? 0 : 2 * PP * 128 * 64 + P_NW * P_WSLOT + 128));
+            // (PHASE with 256 x 256 tiles: PP = 4 has no spare LDS; the word is the panel's first, and a second barrier keeps the
+            // prologue's DMA off it.  512 x 128 tiles leave 16 KiB: the word lies behind the weight ring, as with PP = 3)
+            constexpr bool MAIL_IN_PANEL = PHASE && WR == 2;
+            int *mail = reinterpret_cast<int *>(smem + (MAIL_IN_PANEL ? 0 : ZOFF + 128));
             if (threadIdx.x == 0) {
                 const unsigned v = atomicAdd(p.tile_ctr, 1u);
                 if (v == p.ctr_last) *p.tile_ctr = 0u;
@@ -153,18 +189,19 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
             }
             __syncthreads();
             bid = __builtin_amdgcn_readfirstlane(*mail);
-            if constexpr (PHASE) __syncthreads();
+            if constexpr (MAIL_IN_PANEL) __syncthreads();
             if (bid >= nwg) return;
         }
     }
     const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
     const int t_ = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    // (the n_tiles column tiles of one panel, 2 or 4, are consecutive t_: consecutive workgroups of one XCD, whose L2 holds the panel)
     const int n_tile = t_ % p.n_tiles, m_tile = t_ / p.n_tiles;
-    const int m0 = m_tile * TILE, n0 = n_tile * 256;
+    const int m0 = m_tile * TILE, n0 = n_tile * CT;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 2, wc = wave & 3;
+    const int wr = wave / WC, wc = wave & (WC - 1);
     const int g = lane >> 4, j = lane & 15;
 
     unsigned vm0 = 0, vm1 = 0, vm2 = 0;           // per-lane tap validity, taps 0-2 | 3-5 | 6-8: filled behind the prologue's requests
@@ -174,7 +211,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     const int lchunk = (lane & 3) ^ ((-(lrow >> 2)) & 3);
     const int pm_first = m0 - HALO + wave * 16 + lrow;        // pixel of panel row (piece q): + q*128
     // 32-bit byte offsets from the (uniform) tensor bases: the launcher checks both tensors are < 4 GiB
-    const unsigned wsrc0 = (unsigned)(n0 + wave * 32 + lrow) * (unsigned)p.wrow_bytes + lchunk * 16;   // piece i: + i*16 rows
+    const unsigned wsrc0 = (unsigned)(n0 + wave * (16 * NWP) + lrow) * (unsigned)p.wrow_bytes + lchunk * 16;   // piece i: + i*16 rows
     const unsigned wstep = 16u * p.wrow_bytes;
     // PHASE: block m0 / 16 + off of the internal order -> its group (return value: the block inside the group), clamped into the tensor
     int g0 = 0, gb0 = 0;
@@ -224,11 +261,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         const unsigned off = (unsigned)m * (unsigned)p.cin_bytes + cs * 64 + lchunk * 16;
         VKP_GLDS16(p.x + off, smem + (cs & 1) * PBYTES + (piece * 8 + wave) * 1024);
     };
-    auto req_w = [&](int slot, int cs, int tap, int i) {      // rows (wave*2+i)*16 .. +15 of weight slot `slot`
+    auto req_w = [&](int slot, int cs, int tap, int i) {      // rows (wave*NWP+i)*16 .. +15 of weight slot `slot`
         const unsigned koff = (unsigned)(tap * p.cstages + cs) * 64;  // K layout = (tap, channel): tap*Cin*2 + cs*64 bytes
         unsigned wb_ = wsrc0;
         asm volatile("" : "+v"(wb_));                          // opaque (see x_addr_of)
-        VKP_GLDS16(p.w + (wb_ + i * wstep + koff), smem + WBASE + slot * P_WSLOT + (wave * 2 + i) * 1024);
+        VKP_GLDS16(p.w + (wb_ + i * wstep + koff), smem + WBASE + slot * WSLOT + (wave * NWP + i) * 1024);
     };
 
     // ---- fragment addressing ----
@@ -343,8 +380,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         asm volatile("" : "+v"(tw));
         return tw;
     };
-    auto pre = [&](auto last_c, auto odd_c, auto j_c, unsigned xa, unsigned &xa_next, const half8 (&wcur)[4]) {
-        constexpr bool LAST = decltype(last_c)::value;
+    auto pre = [&](auto last_c, auto odd_c, auto j_c, unsigned xa, unsigned &xa_next, const half8 (&wcur)[4], auto first_c) {
+        constexpr bool LAST = decltype(last_c)::value, FIRST = decltype(first_c)::value;      // FIRST: step 0 of the tile
         constexpr int ODD = decltype(odd_c)::value;
         constexpr int J = decltype(j_c)::value;
         const unsigned tm = ZROW ? 0u : tap_mask(j_c);
@@ -367,8 +404,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         if constexpr (has_next) {
             // vmcnt: everything older than the pieces issued in the last P_NW-2 steps has landed = weights of step
             // t+1 (and, before tap 0, the next stage's panel); barrier: weight slot (t % 6) is free for step t+6,
-            // the other panel buffer is free once the stage ends.
-            constexpr int OUT = LAST ? last_w_in_window<J>() : 2 * (P_NW - 2) + panel_in_window<J, PP>();
+            // the other panel buffer is free once the stage ends.  The counts (pieces_in_window / last_in_window above), taps 0..8:
+            //   256 x 256, PP = 4, NWP = 2: 8 9 10 11 12 11 10 9 8, first step 8; last stage 8 8 8 8 6 4 2 0
+            //   512 x 128, PP = 6, NWP = 1: 5 5 6 7 8 8 8 7 3 (tap 8: the panel piece of tap 5 must have landed), first step 4;
+            //                               last stage 5 4 4 4 3 2 1 0
+            constexpr int OUT = LAST ? last_in_window<J, PP, NWP>() : pieces_in_window<J, PP, NWP, FIRST>();
             vm_wait<OUT>();
             // (DBG 16 / 32, timing only, WRONG results: the barrier on every third tap only / never -- what the per-step barrier costs)
             if constexpr (!(DBG & 48) || ((DBG & 16) && J % 3 == 2)) asm volatile("s_barrier" ::: "memory");
@@ -386,7 +426,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         [[maybe_unused]] const unsigned twn = ZROW ? tap_word(std::integral_constant<int, JN>{}) : 0u;
         constexpr bool issue_w = !LAST || (J + P_NW < 9);
         constexpr bool issue_p = !LAST && (J < PP);
-        constexpr unsigned so = (unsigned)((SLOT + 1) % P_NW) * P_WSLOT;
+        constexpr unsigned so = (unsigned)((SLOT + 1) % P_NW) * WSLOT;
         VKP_READ_W(wnext, so);
         VKP_DSRX(xw[0], xa_next, 0, twn, JN, 0);
         VKP_SB();
@@ -398,7 +438,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         VKP_SB();
         VKP_MMA_ROW(6, xw[2], wcur, tm);
         VKP_SB();
-        if constexpr (issue_w) req_w(SLOT, cs + (J + P_NW) / 9, (J + P_NW) % 9, 1);
+        if constexpr (issue_w && NWP == 2) req_w(SLOT, cs + (J + P_NW) / 9, (J + P_NW) % 9, 1);
         VKP_DSRX(xw[2], xa_next, 2048, twn, JN, 2);
         VKP_SB();
         VKP_MMA_ROW(7, xw[3], wcur, tm);
@@ -420,7 +460,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
 #define VKP_UNIT(LP, LC, U)                                                                                          \
     post(LP, VKP_IC(((U) - 1) / 9), VKP_IC(((U) - 1) % 9), cs + ((U) - 1) / 9, xan, wset(VKP_IC((U) - 1)), wset(VKP_IC(U)));  \
     xa = xan;                                                                                                        \
-    pre(LC, VKP_IC((U) / 9), VKP_IC((U) % 9), xa, xan, wset(VKP_IC(U)));
+    pre(LC, VKP_IC((U) / 9), VKP_IC((U) % 9), xa, xan, wset(VKP_IC(U)), F_{});
     using T_ = std::integral_constant<bool, true>;
     using F_ = std::integral_constant<bool, false>;
 
@@ -430,7 +470,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
 #pragma unroll
     for (int st = 0; st < P_NW; ++st) {
         req_w(st, 0, st, 0);
-        req_w(st, 0, st, 1);
+        if constexpr (NWP == 2) req_w(st, 0, st, 1);
     }
     // ---- per-lane tap validity of its MI fragment pixels (rows wr*MI*16 + mi*16 + j): bit ((tap % 3) * 9 + mi) of word tap / 3 ----
     // Computed HERE, behind the prologue's requests, so that it runs under their HBM latency; and without per-pixel integer
@@ -503,7 +543,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         }
     }
 
-    vm_wait<2 * (P_NW - 1)>();
+    vm_wait<NWP * (P_NW - 1)>();                  // all but the weights of steps 1..5: panel(0) and the weights of step 0 are in LDS
     asm volatile("s_barrier" ::: "memory");
     unsigned long st_c0 = 0, st_r0 = 0;
     if constexpr (DBG & 4) asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_c0), "=s"(st_r0)::"memory");
@@ -515,7 +555,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         VKP_DSRX(xw[1], xa, 1024, tw0, 0, 1);
         VKP_DSRX(xw[2], xa, 2048, tw0, 0, 2);
     }
-    pre(F_{}, VKP_IC(0), VKP_IC(0), xa, xan, wa);
+    pre(F_{}, VKP_IC(0), VKP_IC(0), xa, xan, wa, T_{});
     // CS is even: stages go in pairs (18 steps, so the roles of the two fragment sets repeat per pair)
     int cs = 0;
     for (; cs + 2 < CS; cs += 2) {
@@ -526,7 +566,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         // last step of this pair, first step of the next one
         post(F_{}, VKP_IC(1), VKP_IC(8), cs + 1, xan, wb, wa);
         xa = xan;
-        pre(F_{}, VKP_IC(0), VKP_IC(0), xa, xan, wa);
+        pre(F_{}, VKP_IC(0), VKP_IC(0), xa, xan, wa, F_{});
     }
     // final pair: its second stage is the LAST one
     VKP_UNIT(F_{}, F_{}, 1) VKP_UNIT(F_{}, F_{}, 2) VKP_UNIT(F_{}, F_{}, 3) VKP_UNIT(F_{}, F_{}, 4) VKP_UNIT(F_{}, F_{}, 5)
@@ -742,6 +782,14 @@ int conv3x3_panel_phase_images(const ConvArgs &a) {
     return a.N / 16 * 16;
 }
 
+// Rows of a tile of the launch's phase part: 512 (512 x 128 tiles), 256 under VK_PANEL_TALL=0 (the 256 x 256 phase
+// instantiation: A/B switch and bit-identity tests; re-read per call), 0 where no image of the launch takes the phase form.
+int conv3x3_panel_phase_tile_rows(const ConvArgs &a) {
+    if (a.Cout % 256 != 0 || conv3x3_panel_phase_images(a) == 0) return 0;
+    const char *v = getenv("VK_PANEL_TALL");
+    return v && v[0] == '0' ? 256 : 512;
+}
+
 static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase);
 
 int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream) {
@@ -783,11 +831,17 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
     k.cstages = a.Cin / 32;
     k.wrow_bytes = 9 * a.Cin * 2;
     k.relu = a.relu;
-    const int mi = phase ? 8 : panel_mi(a, M, ds->n_cu), pp = phase ? 4 : panel_pp(a, mi);
+    // phase launches take 512 x 128 tiles (4 x 2 waves, 6 panel pieces, 8 KiB weight slots); the plain form and VK_PANEL_TALL=0 keep 256 columns
+    bool tall = phase && conv3x3_panel_phase_tile_rows(a) == 512;
+#ifdef VK_ABLATION
+    if (const char *pv = getenv("VK_PANEL_PHASE"); pv && pv[0] == 'A') tall = false;      // (the PHASE = 1 build has 256 x 256 tiles only)
+#endif
+    const int mi = phase ? 8 : panel_mi(a, M, ds->n_cu), pp = tall ? 6 : (phase ? 4 : panel_pp(a, mi));
+    const int wslot = tall ? P_WSLOT / 2 : P_WSLOT;
     k.groups = phase ? a.N / 16 : 0;
     k.rcp_w2 = phase ? 65536u / (unsigned)(a.W / 2) + 1u : 0u;
-    k.m_tiles = ceil_div(k.M, mi * 32);
-    k.n_tiles = a.Cout / 256;
+    k.m_tiles = ceil_div(k.M, tall ? 512 : mi * 32);
+    k.n_tiles = a.Cout / (tall ? 128 : 256);
     Timed t;
     VK_TRY(t.begin(stream));
     const int total_tiles = k.m_tiles * k.n_tiles;
@@ -798,7 +852,9 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
     const bool dyn_off = dyn_env && dyn_env[0] == '0';
     if (!dyn_off && (pp == 3 || phase) && total_tiles >= 16 * 256) {          // many rounds on every CU: the last sixteenth is handed out dynamically
         VK_TRY(acquire_tile_counter(&k.tile_ctr));
-        k.static_tiles = total_tiles * 15 / 16 / 8 * 8;             // (a multiple of 8: whole rounds of the XCD map; even: column-tile pairs stay together)
+        // (a multiple of 8: whole rounds of the XCD map, and whole panels: the 2 or 4 column tiles of a panel stay together, since the
+        //  kernel takes n_tile = t_ % n_tiles of consecutive tile indices of one XCD)
+        k.static_tiles = total_tiles * 15 / 16 / 8 * 8;
         n_wgs = total_tiles + (total_tiles / 32 + 63) / 64 * 64;    // spare workgroups: an XCD 3 % faster than the mean can take 3 % more tiles
         k.ctr_last = (unsigned)(n_wgs - k.static_tiles - 1);
     }
@@ -806,7 +862,7 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
 #ifdef VK_ABLATION
     const int dbg = getenv("VK_CONV256_DBG") ? atoi(getenv("VK_CONV256_DBG")) : 0;
 #endif
-    const int smem = 2 * pp * 128 * 64 + P_NW * P_WSLOT + (pp == 3 ? 256 : 0);      // PP = 3: + the zero row
+    const int smem = 2 * pp * 128 * 64 + P_NW * wslot + (pp == 3 || tall ? 256 : 0);      // PP = 3: + the zero row; 512 x 128: + the tail's mailbox word
     k.stamps = nullptr;
 #define VKP_LAUNCH(PP_, DBG_, TAG_, MI_)                                                                                                   \
     do {                                                                                                                                   \
@@ -851,7 +907,10 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
         hipLaunchKernelGGL((conv3x3_panel_kernel<4, 0, 0, 8, 1>), grid, block, smem, stream, k);
     } else
 #endif
-    if (phase) {        // (one symbol: the form is not launched beside another stream's kernels)
+    if (tall) {
+        VK_TRY(set_max_lds(conv3x3_panel_kernel<6, 0, 0, 8, 2, 4>, smem));
+        hipLaunchKernelGGL((conv3x3_panel_kernel<6, 0, 0, 8, 2, 4>), grid, block, smem, stream, k);
+    } else if (phase) {        // (one symbol: the form is not launched beside another stream's kernels)
         VK_TRY(set_max_lds(conv3x3_panel_kernel<4, 0, 0, 8, 2>, smem));
         hipLaunchKernelGGL((conv3x3_panel_kernel<4, 0, 0, 8, 2>), grid, block, smem, stream, k);
     } else if (mi == 8 && pp == 3 && a.concurrent)

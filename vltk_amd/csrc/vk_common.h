@@ -87,6 +87,7 @@ int launch_conv256(const ConvArgs &a, hipStream_t stream);
 bool conv3x3_panel_eligible(const ConvArgs &a);           // conv3x3_panel.hip (LDS-resident input panel, 9 taps per fetch)
 int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream);
 int conv3x3_panel_phase_images(const ConvArgs &a);        // leading images of a panel launch that take its phase-interleaved form
+int conv3x3_panel_phase_tile_rows(const ConvArgs &a);     // rows of a tile of that part: 512, 256 (VK_PANEL_TALL=0) or 0 (no phase part)
 bool conv_gemm4_eligible(const ConvArgs &a);              // conv_gemm4.hip (1x1, K >= 1024, one or two inputs: 256x256 tile, four waves of 128x128)
 int launch_conv_gemm4(const ConvArgs &a, hipStream_t stream);
 int acquire_tile_counter(unsigned **ctr);     // a zeroed device word for one launch's dynamic tile tail; its last fetch zeroes it again (conv_gemm4.hip)
