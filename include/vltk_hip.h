@@ -480,7 +480,8 @@ int vk_linear(const void *x, long M, int K, const void *w_packed, const float *b
  * LxmertVisualFeatureEncoder `(LN(a) + LN(b)) / 2` :468-476 as two calls with scale 0.5. */
 int vk_layernorm(const void *x, int ldx, const float *gamma, const float *beta, void *y, int ldy, int M, int C,
                  float eps, float scale, int accumulate, vk_dtype dt, void *stream);
-/* LxmertEmbeddings.forward :191-214: LayerNorm(word[ids] + position[arange(L)] + token_type[tt]); tables in dt. */
+/* LxmertEmbeddings.forward :191-214: LayerNorm(word[ids] + position[arange(L)] + token_type[tt]); tables in dt.
+ * The ids index the tables unchecked: keeping them inside the tables (and L inside `position`) is the caller's responsibility. */
 int vk_embed_layernorm(const int64_t *input_ids, const int64_t *token_type_ids, int B, int L, const void *word,
                        const void *position, const void *token_type, const float *gamma, const float *beta,
                        void *y, int C, float eps, vk_dtype dt, void *stream);

@@ -118,7 +118,7 @@ def test_embed_layernorm(dt):
     assert rel(y, ref) <= EPS[dt]
 
 
-@pytest.mark.parametrize("dt", [L.VK_F32, L.VK_BF16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("dt", [L.VK_F32, L.VK_F16, L.VK_BF16], ids=IDS)
 @pytest.mark.parametrize("B,heads,Lq,Lk,d,masked", [(3, 4, 11, 36, 32, True), (2, 12, 36, 20, 64, True), (1, 2, 5, 5, 16, False),
                                                     (5, 12, 20, 36, 64, True), (3, 12, 36, 36, 64, False), (2, 3, 48, 64, 64, True),
                                                     (7, 1, 1, 1, 32, False), (2, 2, 49, 20, 64, False)])

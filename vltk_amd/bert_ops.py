@@ -33,6 +33,31 @@ def additive_mask(m, device):
     return None if m is None else ((1.0 - m.to(device, torch.float32)) * torch.finfo(torch.float32).min).contiguous()
 
 
+def check_text_inputs(input_ids, token_type_ids, cfg):
+    """What the embedding kernels trust about the text side: `input_ids [B, Lt]` within the word table, `token_type_ids` (or None)
+    of the same shape within the token-type table, `Lt` within the position table.  Host-side (a device tensor is read back), so it
+    runs before a launch or a graph capture, never inside one.  A wrong shape or length raises ValueError, an id outside its table
+    IndexError (as transformers' embedding lookup does)."""
+    if input_ids.dim() != 2:
+        raise ValueError(f"input_ids [B, Lt] expected, got {tuple(input_ids.shape)}")
+    B, Lt = input_ids.shape
+    if Lt > cfg["max_position_embeddings"]:
+        raise ValueError(f"{Lt} text tokens exceed max_position_embeddings = {cfg['max_position_embeddings']}")
+    for name, t, hi in (("input_ids", input_ids, cfg["vocab_size"]), ("token_type_ids", token_type_ids, cfg["type_vocab_size"])):
+        check_ids(name, t, (B, Lt), hi)
+
+
+def check_ids(name, t, shape, hi):
+    """One integer id tensor (or None): the shape, then every entry in [0, hi)."""
+    if t is None:
+        return
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+    lo_, hi_ = int(t.min()), int(t.max())
+    if lo_ < 0 or hi_ >= hi:
+        raise IndexError(f"{name} must lie in [0, {hi}): found {lo_}..{hi_}")
+
+
 # ---- (name, shape) of the tensors of a BERT layer, in transformers' state-dict order ----
 def attention_spec(p, H, ctx=None):
     ctx = H if ctx is None else ctx

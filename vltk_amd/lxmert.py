@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .bert_ops import LN_EPS, BertOps, additive_mask, attention_spec, bert_layer_spec, dense_ln_spec, seeded_tensor, to_numpy
+from .bert_ops import LN_EPS, BertOps, additive_mask, attention_spec, bert_layer_spec, check_text_inputs, dense_ln_spec, seeded_tensor, \
+    to_numpy
 from .layers import stream
 
 DEFAULT_CONFIG = dict(vocab_size=30522, hidden_size=768, num_attention_heads=12, intermediate_size=3072, l_layers=9, x_layers=5,
@@ -122,9 +123,10 @@ class LxmertEncoder(BertOps):
 
     def capture(self, input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None):
         """Capture one forward for these input SHAPES into a HIP graph (~430 launches become one graph launch: the
-        small-batch forward is launch-bound).  Returns `replay(input_ids, visual_feats, visual_pos, ...)`, which copies the
-        new inputs into the captured buffers, launches the graph and returns the (static) output tensors."""
+        small-batch forward is launch-bound).  Returns `replay(input_ids, visual_feats, visual_pos, ...)`, which checks the
+        new ids on the host, copies the new inputs into the captured buffers, launches the graph and returns the (static) output tensors."""
         dev = self.device
+        check_text_inputs(input_ids, token_type_ids, self.cfg)
         static = dict(ids=input_ids.to(dev).clone(), vf=visual_feats.to(dev).clone(), vp=visual_pos.to(dev).clone(),
                       am=None if attention_mask is None else attention_mask.to(dev).clone(),
                       vm=None if visual_attention_mask is None else visual_attention_mask.to(dev).clone(),
@@ -132,6 +134,7 @@ class LxmertEncoder(BertOps):
         graph, outs = self._capture(self._forward, [static[key] for key in ("ids", "vf", "vp", "am", "vm", "tt")])
 
         def replay(input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None):
+            check_text_inputs(input_ids, token_type_ids, self.cfg)
             for key, val in (("ids", input_ids), ("vf", visual_feats), ("vp", visual_pos), ("am", attention_mask),
                              ("vm", visual_attention_mask), ("tt", token_type_ids)):
                 if static[key] is not None:
@@ -141,6 +144,7 @@ class LxmertEncoder(BertOps):
         return replay
 
     def __call__(self, input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None):
+        check_text_inputs(input_ids, token_type_ids, self.cfg)
         out = self._forward(input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids)
         torch.cuda.synchronize(self.device)
         return out
@@ -213,6 +217,7 @@ class LxmertForQuestionAnswering:
     @torch.no_grad()
     def __call__(self, input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None):
         enc = self.lxmert
+        check_text_inputs(input_ids, token_type_ids, enc.cfg)
         _, _, pooled = enc._forward(input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids)
         h = enc._linear(pooled, "answer.fc0", act=L.VK_ACT_GELU)
         h = enc._layernorm(h, "answer.ln")

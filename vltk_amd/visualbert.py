@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .bert_ops import LN_EPS, BertOps, additive_mask, bert_layer_spec, seeded_tensor, to_numpy
+from .bert_ops import LN_EPS, BertOps, additive_mask, bert_layer_spec, check_ids, check_text_inputs, seeded_tensor, to_numpy
 from .layers import stream
 
 DEFAULT_CONFIG = dict(vocab_size=30522, hidden_size=768, num_attention_heads=12, num_hidden_layers=12, intermediate_size=3072,
@@ -134,18 +134,8 @@ class VisualBertModel(BertOps):
         V = visual_embeds.shape[1]
         if visual_embeds.shape[2] != cfg["visual_embedding_dim"]:
             raise ValueError(f"visual_embeds are {visual_embeds.shape[2]} wide, config.visual_embedding_dim is {cfg['visual_embedding_dim']}")
-        if Lt > cfg["max_position_embeddings"]:
-            raise ValueError(f"{Lt} text tokens exceed max_position_embeddings = {cfg['max_position_embeddings']}")
-        for name, t, shape, hi in (("input_ids", input_ids, (B, Lt), cfg["vocab_size"]),
-                                   ("token_type_ids", token_type_ids, (B, Lt), cfg["type_vocab_size"]),
-                                   ("visual_token_type_ids", visual_token_type_ids, (B, V), cfg["type_vocab_size"])):
-            if t is None:
-                continue
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
-            lo_, hi_ = int(t.min()), int(t.max())
-            if lo_ < 0 or hi_ >= hi:
-                raise IndexError(f"{name} must lie in [0, {hi}): found {lo_}..{hi_}")
+        check_text_inputs(input_ids, token_type_ids, cfg)
+        check_ids("visual_token_type_ids", visual_token_type_ids, (B, V), cfg["type_vocab_size"])
         for name, t, shape in (("attention_mask", attention_mask, (B, Lt)), ("visual_attention_mask", visual_attention_mask, (B, V))):
             if t is not None and tuple(t.shape) != shape:
                 raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
