@@ -427,6 +427,11 @@ int vk_panel_phase_images(int N, int H, int W, int dil);
  * of 256 and the layer is not a panel launch at all).  A remainder of fewer than 16 images keeps the plain form's tile.  The two
  * shapes give the same bits. */
 int vk_panel_phase_tile_rows(int N, int H, int W, int dil, int cout);
+/* The A-fragment schedule of that tile (host only; VK_PANEL_REUSE is re-read per call): 1 = the 512-row tile with the three taps of
+ * a tap row sharing one window of fragment registers (66 instead of 108 LDS fragment reads per wave and channel stage), 0 = every
+ * tap reads its own fragments (VK_PANEL_REUSE=0), or the launch has no 512-row phase tile (vk_panel_phase_tile_rows != 512).  The
+ * two schedules issue the same matrix instructions on the same operands in the same order: the same bits. */
+int vk_panel_phase_reuse(int N, int H, int W, int dil, int cout);
 
 /* conv3 + projection shortcut of a stride-1 BottleneckBlock as ONE f16 GEMM (`out = conv3(t) ; out += shortcut(x)`,
  * frcnn.py:970-977): y[M,cout] = relu?([x1 | x2] . W^T + bias (+ residual)), W rows = [conv3 row (cin1) | shortcut row

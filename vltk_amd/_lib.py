@@ -125,6 +125,7 @@ SIGNATURES = {
     "vk_conv_route": (_I, [_I] * 18),
     "vk_panel_phase_images": (_I, [_I, _I, _I, _I]),
     "vk_panel_phase_tile_rows": (_I, [_I, _I, _I, _I, _I]),
+    "vk_panel_phase_reuse": (_I, [_I, _I, _I, _I, _I]),
     "vk_conv1x1_dual": (_I, [_P, _I, _P, _I, C.c_long, _P, _P, _P, _P, _I, _I, _P]),
     "vk_bottleneck64": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vk_fuse_shortcut": (_I, [_I, _I, _I, _I, _I]),

@@ -27,6 +27,10 @@
 //     Its tile is 512 rows x 128 channels (4x2 waves, WR = 4): 2 panel buffers of 768 rows (48 KiB) + 6 weight slots
 //     of 128 channels (8 KiB) = 144 KiB, 9 x 8 + 48 = 120 KiB through the CU per stage and 65 536 outputs instead of 176, one
 //     weight DMA piece per wave and step.  VK_PANEL_TALL=0 selects the 256 x 256 tile (same bits).
+//     On that tile the three taps of a tap row work from ONE window of ten fragment registers (REUSE): a tap shift is
+//     whole 16-row tiles, so (row tile mi, tap dx) and (mi - 1, dx + 1) are the same LDS bytes at the same lane address.  30 A-fragment
+//     ds_read_b128 per wave and stage instead of 72 (66 instead of 108 with the weights), the same MFMAs on the same operands in the
+//     same order.  VK_PANEL_REUSE=0 selects the schedule in which every tap reads its eight fragments (same bits).
 #include <cstdio>
 #include <type_traits>
 #include <vector>
@@ -133,6 +137,31 @@ __device__ __forceinline__ void vm_wait() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// REUSE (the 512 x 128 phase form): the fragment window of one tap row dy.  In the phase form tap (dy, dx) of row tile mi
+// reads panel tile b + mi + dy * W/2 + dx (b: the wave's first row tile in the panel; the shift is whole 16-row tiles, which the
+// swizzle key (row >> 2) & 3 does not see), so (mi, dx) and (mi - 1, dx + 1) are the same tile at the same lane address.  The three
+// taps of a dy share a window of 10 fragments: slot s holds tile b + dy * W/2 + s - 1.  Tap dx = -1 reads slots 0..7 as a step always
+// did (0..2 in the POST of the step before), taps dx = 0 / +1 read the one slot they are first to use (8 / 9) and take the rest from
+// registers: 10 ds_read_b128 per dy where there were 24.
+constexpr int P_WIN = 10;
+constexpr int reuse_slot(int dx, int mi) { return mi + dx + 1; }                      // the slot tap dx (-1, 0, 1) of row tile mi works from
+constexpr int reuse_tile(int dy, int slot, int w2) { return dy * w2 + slot - 1; }     // the panel tile a slot holds, relative to b
+constexpr int reuse_read_dx(int slot) { return slot < 8 ? -1 : slot - 8; }            // the tap that reads the slot from LDS
+constexpr bool reuse_window_ok() {
+    for (int w2 = 1; w2 <= 7; ++w2)                                                    // W / 2 of every phase launch (W even, <= 14)
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx)
+                for (int mi = 0; mi < 8; ++mi) {
+                    const int s = reuse_slot(dx, mi);
+                    if (s < 0 || s >= P_WIN) return false;
+                    if (reuse_tile(dy, s, w2) != mi + dy * w2 + dx) return false;      // == the tile x_addr_of(tap) + mi * 1024 addresses
+                    if (reuse_read_dx(s) > dx) return false;                           // read by this tap or an earlier one of the dy
+                    if (reuse_tile(dy, s, w2) < -8 || reuse_tile(dy, s, w2) > 15) return false;   // the halo: 8 tiles either side
+                }
+    return true;
+}
+static_assert(reuse_window_ok(), "REUSE: (tap, row tile) -> window slot -> panel tile, W / 2 = 1 .. 7, inside tiles b - 8 .. b + 15");
+
 // DBG: diagnostic builds: 1 = no tap-validity masking (VK_CONV256_DBG=1; timing only, WRONG results); 4 = stamps around the K loop
 // and the whole workgroup (VK_PANEL_STAMPS=<file>, tools/panel_stamps.py)
 // TAG 1: second symbol for launches of the two-stream backbone section (see conv_mfma_duo.hip)
@@ -148,7 +177,9 @@ __device__ __forceinline__ void vm_wait() {
 // channels (8 KiB, one DMA piece per wave and step) serves 512 rows, and the panel is 6 pieces (768 rows, halo 128): 72 + 48 KiB
 // through the CU per stage and 65 536 outputs instead of 144 + 32.  Rows are independent and every element sums the same products
 // in the same order, so the tile shape does not change a bit.
-template <int PP, int DBG, int TAG = 0, int MI = 8, int PHASE = 0, int WR = 2>
+// REUSE: 1 = the A-fragment window above (512 x 128 phase tiles only): 66 instead of 108 ds_read_b128 per wave and stage, the same
+// MFMAs on the same operands in the same order.  0 (VK_PANEL_REUSE=0) = every tap reads its eight fragments.
+template <int PP, int DBG, int TAG = 0, int MI = 8, int PHASE = 0, int WR = 2, int REUSE = 0>
 __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(MI == 8 || MI == 9, "8 or 9 row tiles per wave");
@@ -156,6 +187,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     static_assert(!PHASE || (PP == (WR == 4 ? 6 : 4) && MI == 8 && !(DBG & 9)), "the phase form: halo 128 = (W / 2 + 1) * 16 at W = 14, 256- or 512-row tiles");
     static_assert(WR == 2 || PHASE == 2, "512 x 128 tiles: the phase form only (a plain res4 launch would read its panel twice)");
     static_assert(MI == 8 || !(DBG & 8), "the LDS-staged epilogue is written for 128-row halves");
+    static_assert(!REUSE || (PHASE == 2 && WR == 4 && MI == 8 && DBG == 0), "the fragment window: tap shifts of whole 16-row tiles, 512 x 128 tiles");
     constexpr int WC = 8 / WR;                    // column blocks of 64 channels
     constexpr int CT = 64 * WC;                   // channels per tile: 256 or 128
     constexpr int NWP = CT / 128;                 // weight DMA pieces (16 rows) per wave and step: 2 or 1
@@ -165,6 +197,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     constexpr int HALO = (PROWS - TILE) / 2;      // 64 or 128 (MI = 9: 48 or 112)
     constexpr int PBYTES = PROWS * 64;
     constexpr int WBASE = 2 * PBYTES;
+    // a wave's first row tile is panel tile b = HALO / 16 + wr * MI: the window's tiles b - 8 .. b + 15 are panel tiles 0 .. PROWS / 16 - 1
+    static_assert(!REUSE || (HALO / 16 == 8 && HALO / 16 + (WR - 1) * MI + 15 < PROWS / 16), "REUSE: the halo (8 tiles) covers tiles b - 8 .. b + 15");
     static_assert(HALO >= (PHASE ? 128 : 48) && WBASE + P_NW * WSLOT + (PP == 3 || WR == 4 ? 256 : 0) <= 160 * 1024, "halo / LDS");
     // PP = 3 leaves 16 KiB of the CU's LDS unused: 64 bytes of zeros behind the weight ring.  A fragment read of a pixel whose tap
     // falls outside the image is pointed there (two VALU instructions per read: a sign-extended bit-field and a bit-select
@@ -295,7 +329,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = floatx4{0.f, 0.f, 0.f, 0.f};
-    half8 wa[4], wb[4], xw[MI == 9 ? 5 : 4];      // (MI = 9: row tile 8 has a fragment register of its own)
+    half8 wa[4], wb[4], xw[REUSE ? P_WIN : (MI == 9 ? 5 : 4)];      // (MI = 9: row tile 8 has a fragment register of its own; REUSE: the window of a dy)
     const int CS = p.cstages;
 
 #define VKP_DSR(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
@@ -387,18 +421,48 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         const unsigned tm = ZROW ? 0u : tap_mask(j_c);
         [[maybe_unused]] const unsigned tw = ZROW ? tap_word(j_c) : 0u;
         constexpr bool has_next = !(LAST && J == 8);
-        // address of the next step's fragments (next tap; next stage's panel after tap 8)
-        if constexpr (has_next) xa_next = (J == 8) ? x_addr_of(1 - ODD, 0) : x_addr_of(ODD, J + 1);
-        VKP_DSRX(xw[3], xa, 3072, tw, J, 3); VKP_WAIT3(xw[0]); VKP_SB(); VKP_MMA_ROW(0, xw[0], wcur, tm); VKP_SB();
-        VKP_DSRX(xw[0], xa, 4096, tw, J, 4); VKP_WAIT3(xw[1]); VKP_SB(); VKP_MMA_ROW(1, xw[1], wcur, tm); VKP_SB();
-        VKP_DSRX(xw[1], xa, 5120, tw, J, 5); VKP_WAIT3(xw[2]); VKP_SB(); VKP_MMA_ROW(2, xw[2], wcur, tm); VKP_SB();
-        VKP_DSRX(xw[2], xa, 6144, tw, J, 6); VKP_WAIT3(xw[3]); VKP_SB(); VKP_MMA_ROW(3, xw[3], wcur, tm); VKP_SB();
-        if constexpr (MI == 9) {
-            VKP_DSRX(xw[3], xa, 7168, tw, J, 7); VKP_DSRX(xw[4], xa, 8192, tw, J, 8); VKP_WAIT4(xw[0]); VKP_SB(); VKP_MMA_ROW(4, xw[0], wcur, tm); VKP_SB();
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xw[1]), "+v"(xw[2]), "+v"(xw[3]), "+v"(xw[MI == 9 ? 4 : 3])::"memory");
-        } else {
-            VKP_DSRX(xw[3], xa, 7168, tw, J, 7); VKP_WAIT3(xw[0]); VKP_SB(); VKP_MMA_ROW(4, xw[0], wcur, tm); VKP_SB();
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xw[1]), "+v"(xw[2]), "+v"(xw[3])::"memory");
+        if constexpr (REUSE) {
+            // xa addresses slot 0 of the window (tap dx = -1 of this dy) for all three taps; slot s is at + s * 1024
+            constexpr int D = J % 3;
+            if constexpr (has_next && D == 2)
+                xa_next = (J == 8) ? x_addr_of(1 - ODD, 0) : x_addr_of(ODD, J + 1);
+            else
+                xa_next = xa;
+#define VKP_ROWX(MI_) VKP_SB(); VKP_MMA_ROW(MI_, xw[reuse_slot(D - 1, MI_)], wcur, tm); VKP_SB()
+            if constexpr (D == 0) {        // in flight: 4 weight fragments, slots 0 1 2 (POST of the step before / prologue)
+                static_assert(reuse_slot(-1, 4) == 4 && reuse_read_dx(7) == -1);
+                VKP_DSR(xw[3], xa, 3072); VKP_WAIT3(xw[0]); VKP_ROWX(0);
+                VKP_DSR(xw[4], xa, 4096); VKP_WAIT3(xw[1]); VKP_ROWX(1);
+                VKP_DSR(xw[5], xa, 5120); VKP_WAIT3(xw[2]); VKP_ROWX(2);
+                VKP_DSR(xw[6], xa, 6144); VKP_WAIT3(xw[3]); VKP_ROWX(3);
+                VKP_DSR(xw[7], xa, 7168); VKP_WAIT3(xw[4]); VKP_ROWX(4);
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xw[5]), "+v"(xw[6]), "+v"(xw[7])::"memory");
+            } else {                       // in flight: the 4 weight fragments alone; the one new slot is first used by row tile 7 (POST)
+                static_assert(reuse_read_dx(7 + D) == D - 1 && reuse_slot(D - 1, 7) == 7 + D);
+                half8(&wm)[4] = (9 * ODD + J) % 2 == 0 ? wa : wb;           // == wcur, writable: the wait is tied to the fragments it covers
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wm[0]), "+v"(wm[1]), "+v"(wm[2]), "+v"(wm[3]));
+                if constexpr (D == 1)
+                    VKP_DSR(xw[8], xa, 8192);
+                else
+                    VKP_DSR(xw[9], xa, 9216);
+                VKP_ROWX(0); VKP_ROWX(1); VKP_ROWX(2); VKP_ROWX(3); VKP_ROWX(4);
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xw[7 + D])::"memory");
+            }
+#undef VKP_ROWX
+        } else {                           // every tap reads its eight fragments through a window of four
+            // address of the next step's fragments (next tap; next stage's panel after tap 8)
+            if constexpr (has_next) xa_next = (J == 8) ? x_addr_of(1 - ODD, 0) : x_addr_of(ODD, J + 1);
+            VKP_DSRX(xw[3], xa, 3072, tw, J, 3); VKP_WAIT3(xw[0]); VKP_SB(); VKP_MMA_ROW(0, xw[0], wcur, tm); VKP_SB();
+            VKP_DSRX(xw[0], xa, 4096, tw, J, 4); VKP_WAIT3(xw[1]); VKP_SB(); VKP_MMA_ROW(1, xw[1], wcur, tm); VKP_SB();
+            VKP_DSRX(xw[1], xa, 5120, tw, J, 5); VKP_WAIT3(xw[2]); VKP_SB(); VKP_MMA_ROW(2, xw[2], wcur, tm); VKP_SB();
+            VKP_DSRX(xw[2], xa, 6144, tw, J, 6); VKP_WAIT3(xw[3]); VKP_SB(); VKP_MMA_ROW(3, xw[3], wcur, tm); VKP_SB();
+            if constexpr (MI == 9) {
+                VKP_DSRX(xw[3], xa, 7168, tw, J, 7); VKP_DSRX(xw[4], xa, 8192, tw, J, 8); VKP_WAIT4(xw[0]); VKP_SB(); VKP_MMA_ROW(4, xw[0], wcur, tm); VKP_SB();
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xw[1]), "+v"(xw[2]), "+v"(xw[3]), "+v"(xw[MI == 9 ? 4 : 3])::"memory");
+            } else {
+                VKP_DSRX(xw[3], xa, 7168, tw, J, 7); VKP_WAIT3(xw[0]); VKP_SB(); VKP_MMA_ROW(4, xw[0], wcur, tm); VKP_SB();
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xw[1]), "+v"(xw[2]), "+v"(xw[3])::"memory");
+            }
         }
         VKP_SB();
         if constexpr (has_next) {
@@ -427,21 +491,26 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         constexpr bool issue_w = !LAST || (J + P_NW < 9);
         constexpr bool issue_p = !LAST && (J < PP);
         constexpr unsigned so = (unsigned)((SLOT + 1) % P_NW) * WSLOT;
+        // REUSE: row tiles 5 6 7 of tap dx work from slots 6 + dx .. 8 + dx; only the last tap of a dy reads ahead (slots 0 1 2 of the
+        // next dy: their last users were row tile 0 of this dy's three taps, issued before this step's barrier)
+        constexpr int D = J % 3;
+        constexpr bool ahead = !REUSE || D == 2;
+        constexpr int X5 = REUSE ? reuse_slot(D - 1, 5) : 1, X6 = REUSE ? reuse_slot(D - 1, 6) : 2, X7 = REUSE ? reuse_slot(D - 1, 7) : 3;
         VKP_READ_W(wnext, so);
-        VKP_DSRX(xw[0], xa_next, 0, twn, JN, 0);
+        if constexpr (ahead) VKP_DSRX(xw[0], xa_next, 0, twn, JN, 0);
         VKP_SB();
-        VKP_MMA_ROW(5, xw[1], wcur, tm);
+        VKP_MMA_ROW(5, xw[X5], wcur, tm);
         VKP_SB();
         if constexpr (issue_p) req_panel(cs + 1, J);
         if constexpr (issue_w) req_w(SLOT, cs + (J + P_NW) / 9, (J + P_NW) % 9, 0);
-        VKP_DSRX(xw[1], xa_next, 1024, twn, JN, 1);
+        if constexpr (ahead) VKP_DSRX(xw[1], xa_next, 1024, twn, JN, 1);
         VKP_SB();
-        VKP_MMA_ROW(6, xw[2], wcur, tm);
+        VKP_MMA_ROW(6, xw[X6], wcur, tm);
         VKP_SB();
         if constexpr (issue_w && NWP == 2) req_w(SLOT, cs + (J + P_NW) / 9, (J + P_NW) % 9, 1);
-        VKP_DSRX(xw[2], xa_next, 2048, twn, JN, 2);
+        if constexpr (ahead) VKP_DSRX(xw[2], xa_next, 2048, twn, JN, 2);
         VKP_SB();
-        VKP_MMA_ROW(7, xw[3], wcur, tm);
+        VKP_MMA_ROW(7, xw[X7], wcur, tm);
         VKP_SB();
         if constexpr (MI == 9) {
             VKP_MMA_ROW(8, xw[MI == 9 ? 4 : 3], wcur, tm);
@@ -575,9 +644,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     VKP_UNIT(T_{}, T_{}, 16) VKP_UNIT(T_{}, T_{}, 17)
     {
         const unsigned tm = ZROW ? 0u : tap_mask(VKP_IC(8));
-        VKP_MMA_ROW(5, xw[1], wb, tm);
-        VKP_MMA_ROW(6, xw[2], wb, tm);
-        VKP_MMA_ROW(7, xw[3], wb, tm);
+        VKP_MMA_ROW(5, xw[REUSE ? reuse_slot(1, 5) : 1], wb, tm);
+        VKP_MMA_ROW(6, xw[REUSE ? reuse_slot(1, 6) : 2], wb, tm);
+        VKP_MMA_ROW(7, xw[REUSE ? reuse_slot(1, 7) : 3], wb, tm);
         if constexpr (MI == 9) VKP_MMA_ROW(8, xw[MI == 9 ? 4 : 3], wb, tm);
     }
     unsigned long st_c1 = 0, st_r1 = 0;
@@ -790,6 +859,14 @@ int conv3x3_panel_phase_tile_rows(const ConvArgs &a) {
     return v && v[0] == '0' ? 256 : 512;
 }
 
+// 1 where the launch's phase part runs the fragment-window schedule (REUSE): every 512 x 128 launch, unless
+// VK_PANEL_REUSE=0 selects the schedule in which each tap reads its eight fragments (A/B switch and bit-identity tests; re-read per call).
+int conv3x3_panel_phase_reuse(const ConvArgs &a) {
+    if (conv3x3_panel_phase_tile_rows(a) != 512) return 0;
+    const char *v = getenv("VK_PANEL_REUSE");
+    return v && v[0] == '0' ? 0 : 1;
+}
+
 static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase);
 
 int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream) {
@@ -907,7 +984,10 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
         hipLaunchKernelGGL((conv3x3_panel_kernel<4, 0, 0, 8, 1>), grid, block, smem, stream, k);
     } else
 #endif
-    if (tall) {
+    if (tall && conv3x3_panel_phase_reuse(a)) {
+        VK_TRY(set_max_lds(conv3x3_panel_kernel<6, 0, 0, 8, 2, 4, 1>, smem));
+        hipLaunchKernelGGL((conv3x3_panel_kernel<6, 0, 0, 8, 2, 4, 1>), grid, block, smem, stream, k);
+    } else if (tall) {
         VK_TRY(set_max_lds(conv3x3_panel_kernel<6, 0, 0, 8, 2, 4>, smem));
         hipLaunchKernelGGL((conv3x3_panel_kernel<6, 0, 0, 8, 2, 4>), grid, block, smem, stream, k);
     } else if (phase) {        // (one symbol: the form is not launched beside another stream's kernels)

@@ -226,6 +226,12 @@ int vk_panel_phase_tile_rows(int N, int H, int W, int dil, int cout) {
     return conv3x3_panel_phase_tile_rows(a);
 }
 
+int vk_panel_phase_reuse(int N, int H, int W, int dil, int cout) {
+    ConvArgs a;
+    fill_conv_args(a, N, H, W, 128, cout, cout, 3, 1, dil, dil, 1, 0, VK_F16, VK_F16);
+    return conv3x3_panel_phase_reuse(a);
+}
+
 int vk_conv1x1_dual(const void *x1, int cin1, const void *x2, int cin2, long M, const void *w_packed, const float *bias_packed,
                     const void *residual, void *y, int cout, int relu, void *stream) {
     VK_REQUIRE(x1 && x2 && M > 0 && M < (1L << 31), VK_EINVAL, "conv1x1_dual: bad arguments");

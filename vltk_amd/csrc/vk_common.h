@@ -88,6 +88,7 @@ bool conv3x3_panel_eligible(const ConvArgs &a);           // conv3x3_panel.hip (
 int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream);
 int conv3x3_panel_phase_images(const ConvArgs &a);        // leading images of a panel launch that take its phase-interleaved form
 int conv3x3_panel_phase_tile_rows(const ConvArgs &a);     // rows of a tile of that part: 512, 256 (VK_PANEL_TALL=0) or 0 (no phase part)
+int conv3x3_panel_phase_reuse(const ConvArgs &a);         // 1: that part's 512-row tiles share a fragment window per tap row; 0: VK_PANEL_REUSE=0 or no such tile
 bool conv_gemm4_eligible(const ConvArgs &a);              // conv_gemm4.hip (1x1, K >= 1024, one or two inputs: 256x256 tile, four waves of 128x128)
 int launch_conv_gemm4(const ConvArgs &a, hipStream_t stream);
 int acquire_tile_counter(unsigned **ctr);     // a zeroed device word for one launch's dynamic tile tail; its last fetch zeroes it again (conv_gemm4.hip)
