@@ -1,7 +1,8 @@
 """Launcher state is per device and lives in one place (csrc/runtime.hip: device_state, set_max_lds, Timed).
 
 CPU: no other translation unit raises an LDS limit, queries device properties or keeps function-local state, so a process
-may hold handles on several devices.  -m gpu (two or more devices): the same model on cuda:1 and then cuda:0 in one
+may hold handles on several devices; none calls getenv (runtime.hip's env_* read the environment), and the VK_* names they
+are asked for are the rows of DESIGN.md's table of switches.  -m gpu (two or more devices): the same model on cuda:1 and then cuda:0 in one
 process gives the same bits."""
 import glob
 import os
@@ -32,6 +33,36 @@ def test_launchers_keep_no_state_of_their_own():
     assert not bad, "\n".join(bad)
 
 
+ENV_CALL = re.compile(r"\benv_(?:text|set|first|off|int)\(\s*\"(VK_[A-Z0-9_]+)\"")
+
+
+def test_only_the_runtime_reads_the_environment():
+    bad = []
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
+        if os.path.basename(path) != "runtime.hip":
+            with open(path) as f:
+                bad += [f"{os.path.basename(path)}:{n}: {line.strip()}" for n, line in enumerate(f, 1) if "getenv" in line]
+    assert not bad, "\n".join(bad)
+
+
+def test_design_lists_every_switch():
+    """The VK_* names passed to env_* anywhere in csrc, plus the `env` column of model.hip's kOptions, are the names of the
+    table in DESIGN.md's section on the environment switches: no more, no fewer."""
+    read = set()
+    for path in glob.glob(os.path.join(CSRC, "*.hip")):
+        with open(path) as f:
+            read |= set(ENV_CALL.findall(f.read()))
+    with open(os.path.join(CSRC, "model.hip")) as f:
+        table = re.search(r"kOptions\[\] = \{(.*?)\n\};", f.read(), re.S).group(1)
+    options = set(re.findall(r'"(VK_[A-Z0-9_]+)", ENV_', table))
+    assert len(options) == 5 and len(read) > 30, (options, read)
+    with open(os.path.join(ROOT, "DESIGN.md")) as f:
+        section = re.search(r"\n## \d+\. The environment switches[^\n]*\n(.*?)(?=\n## |\Z)", f.read(), re.S).group(1)
+    rows = re.findall(r"^\| `(VK_[A-Z0-9_]+)` \|", section, re.M)
+    assert len(rows) == len(set(rows)), sorted(r for r in rows if rows.count(r) > 1)
+    assert set(rows) == read | options, (sorted(set(rows) - read - options), sorted((read | options) - set(rows)))
+
+
 def test_scan_patterns():
     assert LOCAL_STATIC.search("    static bool attr_set = false;")
     assert LOCAL_STATIC.search("        static char *zero_page = nullptr;   \\")
@@ -40,6 +71,8 @@ def test_scan_patterns():
     assert not LOCAL_STATIC.search("    static constexpr int N = 8;")
     assert not LOCAL_STATIC.search("    static __device__ __forceinline__ floatx4 mfma(vec a, vec b, floatx4 c) {")
     assert not LOCAL_STATIC.search("static int launch_t(const ConvK &k, hipStream_t stream) {")
+    assert not LOCAL_STATIC.search("    static const bool off = env_set(\"X\");")
+    assert ENV_CALL.findall('if (env_off("VK_A") || env_int( "VK_B2", 1) == 0 || env_off(name)) x = env_text("VK_C_D");') == ["VK_A", "VK_B2", "VK_C_D"]
 
 
 @pytest.mark.gpu

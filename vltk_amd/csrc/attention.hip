@@ -516,15 +516,10 @@ __global__ __launch_bounds__(256) void attention_stream_kernel(const T *__restri
     }
 }
 
-static bool env_off(const char *name) {
-    const char *e = getenv(name);
-    return e && e[0] == '0';
-}
-
 // The one routing rule (host only): the launcher switches on it for both entry points, vk_attention_route reports it.  The
 // small matrix-core kernel takes 16-bit types, head dim 32 / 64, up to 48 queries and 64 keys, 16-byte aligned rows; the LDS
 // kernel whatever fits 160 KiB; beyond that, and for every shape at the tiled entry, the online-soft-max kernels
-// (A/B switches VK_ATTENTION_MFMA=0, VK_ATTENTION_TILED=0, read per call).
+// (VK_ATTENTION_MFMA=0, VK_ATTENTION_TILED=0).
 static int attention_route(int Lq, int Lk, int d, vk_dtype dt, int ldq, int ldk, int ldv, int aligned16, int tiled_entry) {
     if (!(Lq >= 1 && Lk >= 1 && d >= 1)) {
         set_error("attention: bad geometry (Lq=%d Lk=%d d=%d)", Lq, Lk, d);
@@ -577,9 +572,8 @@ static int route_of(const AttArgs &a, int tiled_entry) {
 
 template <typename T>
 static int lds_launch(const AttArgs &a, float scale, hipStream_t s) {
-    VK_TRY(set_max_lds(attention_kernel<T>, LDS_KERNEL_MAX));
-    hipLaunchKernelGGL(attention_kernel<T>, dim3(a.B * a.heads), dim3(256), lds_kernel_bytes(a.Lq, a.Lk, a.d), s, VK_ATT_IO(T), a.d, scale);
-    return VK_OK;
+    return launch_lds(attention_kernel<T>, dim3(a.B * a.heads), dim3(256), lds_kernel_bytes(a.Lq, a.Lk, a.d), LDS_KERNEL_MAX, s, VK_ATT_IO(T),
+                      a.d, scale);
 }
 
 template <typename T, int D>
@@ -593,9 +587,7 @@ template <typename T, int D, int QB>
 static int tiled_launch_qb(const AttArgs &a, float scale, hipStream_t s) {
     const int nqb = (a.Lq + QB * 16 - 1) / (QB * 16), total = a.B * a.heads * nqb;
     const size_t smem = (size_t)4 * (QB * 16 + D) * ATT_PP * sizeof(T);
-    VK_TRY(set_max_lds(attention_tiled_kernel<T, D, QB>, smem));
-    hipLaunchKernelGGL((attention_tiled_kernel<T, D, QB>), dim3((total + 3) / 4), dim3(256), smem, s, VK_ATT_IO(T), nqb, total, scale);
-    return VK_OK;
+    return launch_lds(attention_tiled_kernel<T, D, QB>, dim3((total + 3) / 4), dim3(256), smem, smem, s, VK_ATT_IO(T), nqb, total, scale);
 }
 template <typename T, int D>
 static int tiled_launch(const AttArgs &a, float scale, hipStream_t s) {
@@ -605,10 +597,8 @@ static int tiled_launch(const AttArgs &a, float scale, hipStream_t s) {
 template <typename T>
 static int stream_launch(const AttArgs &a, float scale, hipStream_t s) {
     const int nqb = (a.Lq + STR_QB - 1) / STR_QB;
-    VK_TRY(set_max_lds(attention_stream_kernel<T>, stream_lds_bytes(STR_MAXD)));
-    hipLaunchKernelGGL(attention_stream_kernel<T>, dim3(a.B * a.heads * nqb), dim3(256), stream_lds_bytes(a.d), s, VK_ATT_IO(T), a.d, nqb,
-                       scale);
-    return VK_OK;
+    return launch_lds(attention_stream_kernel<T>, dim3(a.B * a.heads * nqb), dim3(256), stream_lds_bytes(a.d), stream_lds_bytes(STR_MAXD), s,
+                      VK_ATT_IO(T), a.d, nqb, scale);
 }
 
 // The one launcher: `route` is attention_route's answer for these arguments, so the dtype and the head dim are the kernel's.

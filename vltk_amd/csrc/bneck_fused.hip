@@ -765,21 +765,22 @@ __global__ __launch_bounds__(512, 2) void bneck64_rows_kernel(BneckRowsK p) {
     }
 }
 
+bool bneck_fused_forced() { return env_set("VK_BNECK_FUSED"); }
+static bool bneck_rows_off() { return env_off("VK_BNECK_ROWS"); }      // VK_BNECK_ROWS=0: the tile form
+
 bool bneck_fused_eligible(int cin, int cmid, int cout, int stride, int groups, bool proj, long N, int H, int W, vk_dtype dt) {
-    const char *v = getenv("VK_BNECK_FUSED");            // "0" disables (A/B switch and comparison tests; re-read per call)
-    if (v && v[0] == '0') return false;
+    if (env_off("VK_BNECK_FUSED")) return false;
     if (dt != VK_F16 || cmid != 64 || cout != 256 || stride != 1 || groups != 1) return false;
     if (!((cin == 256 && !proj) || (cin == 64 && proj))) return false;
     // byte offsets into x: unsigned 32-bit in the row form (64 images of 800 x 1333 are 2.2 GB of res2 map), signed in the tile form
-    const char *rv = getenv("VK_BNECK_ROWS");
-    const long lim = (rv && rv[0] == '0') ? (1L << 31) : (1L << 32) - (1L << 20);
+    const long lim = bneck_rows_off() ? (1L << 31) : (1L << 32) - (1L << 20);
     if (H < 1 || W < 1 || N * H * W * 512 >= lim) return false;
     return true;
 }
 
 int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, const void *w1, const float *b1, const void *w2,
                        const float *b2, const void *w3, const float *b3, void *y, bool concurrent, hipStream_t stream) {
-    VK_REQUIRE(bneck_fused_eligible(cin, 64, 256, 1, 1, proj, N, H, W, VK_F16) || getenv("VK_BNECK_FUSED"), VK_EINVAL,
+    VK_REQUIRE(bneck_fused_eligible(cin, 64, 256, 1, 1, proj, N, H, W, VK_F16) || bneck_fused_forced(), VK_EINVAL,
                "bneck_fused: shape not eligible");
     DeviceState *ds = nullptr;
     VK_TRY(device_state(&ds));
@@ -803,8 +804,13 @@ int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, c
     VK_REQUIRE(nt > 0 && nt < (1L << 31), VK_EINVAL, "bneck_fused: %ld tiles", nt);
     k.ntiles = (int)nt;
     k.x_last = (unsigned)(((long)N * H * W - 1) * cin * 2);
-    const char *rv = getenv("VK_BNECK_ROWS");            // "0": the tile form (A/B switch and comparison tests; re-read per call)
-    if (!(rv && rv[0] == '0')) {
+    const double M = (double)N * H * W;       // Timed::end's counts, the same for both forms
+    const double fl = 2.0 * M * (64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64));
+    const double by = 2.0 * (M * cin + M * 256 + 64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64));
+#define VKN_LAUNCH(K_, SMEM_, WG_, ARG_, ...) VK_TRY(launch_lds(K_<__VA_ARGS__>, dim3(n_cu), dim3(WG_), SMEM_, SMEM_, stream, ARG_))
+#define VKN_ROWS(CIN_, ...) VKN_LAUNCH(bneck64_rows_kernel, br_smem<CIN_>(), 512, r, CIN_, __VA_ARGS__)
+#define VKN_TILE(CIN_, ...) VKN_LAUNCH(bneck64_kernel, bn_smem<CIN_>(), 256, k, CIN_, __VA_ARGS__)
+    if (!bneck_rows_off()) {
         BneckRowsK r;
         r.x = (const char *)x;
         r.w1 = (const char *)w1;
@@ -822,13 +828,12 @@ int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, c
         r.strips = ceil_div(W, r.tw);
         // rows per unit: the split of the image height that takes the fewest steps over the rounds of the grid (a unit of ru rows
         // takes ru + 4 steps and a prologue; at least 16 rows per unit)
-        const int grid_ = n_cu;
         long best = -1;
         r.vsplit = 1;
         for (int vs = 1; vs <= std::max(1, H / 16); ++vs) {
             const int ru_ = ceil_div(H, vs), vs_ = ceil_div(H, ru_);
             const long units_ = (long)N * r.strips * vs_;
-            const long cost = ((units_ + grid_ - 1) / grid_) * (ru_ + 8);
+            const long cost = ((units_ + n_cu - 1) / n_cu) * (ru_ + 8);
             if (best < 0 || cost < best) {
                 best = cost;
                 r.vsplit = vs_;
@@ -843,102 +848,57 @@ int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, c
         Timed t;
         VK_TRY(t.begin(stream));
 #ifdef VK_ABLATION
-        if (const char *sf = getenv("VK_BNECK_STAMPS")) {     // diagnostic: one stamped launch, 8 words per wave appended to the file
-            const size_t nb = (size_t)grid_ * 4 * 8 * sizeof(unsigned long);
-            VK_CHECK_HIP(hipMalloc((void **)&r.stamps, nb));
-            VK_CHECK_HIP(hipMemsetAsync(r.stamps, 0, nb, stream));
-            const int dbg = getenv("VK_BNECK_DBG") ? atoi(getenv("VK_BNECK_DBG")) : 0;
-            if (proj) {
-                VK_TRY(set_max_lds(bneck64_rows_kernel<64, true, true>, br_smem<64>()));
-                hipLaunchKernelGGL((bneck64_rows_kernel<64, true, true>), dim3(grid_), dim3(512), br_smem<64>(), stream, r);
-            } else {
-                switch (dbg) {
-#define VKN_DBG_CASE(D_)                                                                                                                   \
-    case D_:                                                                                                                               \
-        VK_TRY(set_max_lds(bneck64_rows_kernel<256, false, true, D_>, br_smem<256>()));                                                     \
-        hipLaunchKernelGGL((bneck64_rows_kernel<256, false, true, D_>), dim3(grid_), dim3(512), br_smem<256>(), stream, r);                 \
-        break;
+        if (const char *sf = env_text("VK_BNECK_STAMPS")) {     // diagnostic: one stamped launch, 8 words per wave appended to the file
+            Stamps st;
+            VK_TRY(st.open((size_t)n_cu * 4 * 8, stream));
+            r.stamps = st.dev;
+            if (proj)
+                VKN_ROWS(64, true, true);
+            else
+                switch (env_int("VK_BNECK_DBG", 0)) {
+#define VKN_DBG_CASE(D_) case D_: VKN_ROWS(256, false, true, D_); break;
                     VKN_DBG_CASE(1) VKN_DBG_CASE(2) VKN_DBG_CASE(4) VKN_DBG_CASE(8) VKN_DBG_CASE(16) VKN_DBG_CASE(7) VKN_DBG_CASE(15) VKN_DBG_CASE(31) VKN_DBG_CASE(24) VKN_DBG_CASE(3)
 #undef VKN_DBG_CASE
-                    default:
-                        VK_TRY(set_max_lds(bneck64_rows_kernel<256, false, true>, br_smem<256>()));
-                        hipLaunchKernelGGL((bneck64_rows_kernel<256, false, true>), dim3(grid_), dim3(512), br_smem<256>(), stream, r);
+                    default: VKN_ROWS(256, false, true);
                 }
-            }
-            VK_CHECK_HIP(hipStreamSynchronize(stream));
-            std::vector<unsigned long> hst((size_t)grid_ * 4 * 8);
-            VK_CHECK_HIP(hipMemcpy(hst.data(), r.stamps, nb, hipMemcpyDeviceToHost));
-            VK_CHECK_HIP(hipFree(r.stamps));
-            if (FILE *f = fopen(sf, "a")) {
-                fprintf(f, "# rows form: wg wave wait_cycles 0 0 steps kernel_cycles kernel_ticks(10ns)  proj=%d units=%d ru=%d tw=%d\n", (int)proj, r.nunits, r.ru, r.tw);
-                for (int w = 0; w < grid_ * 4; ++w) {
-                    fprintf(f, "%d %d", w / 4, w % 4);
-                    for (int i = 0; i < 6; ++i) fprintf(f, " %lu", hst[(size_t)w * 8 + i]);
-                    fprintf(f, "\n");
-                }
-                fclose(f);
-            }
-            return VK_OK;
+            char header[160];
+            snprintf(header, sizeof(header), "# rows form: wg wave wait_cycles 0 0 steps kernel_cycles kernel_ticks(10ns)  proj=%d units=%d ru=%d tw=%d",
+                     (int)proj, r.nunits, r.ru, r.tw);
+            return st.finish(stream, sf, header, (size_t)n_cu * 4, 8, 6, 4);
         }
 #endif
-        if (proj) {
-            VK_TRY(set_max_lds(bneck64_rows_kernel<64, true>, br_smem<64>()));
-            hipLaunchKernelGGL((bneck64_rows_kernel<64, true>), dim3(grid_), dim3(512), br_smem<64>(), stream, r);
-        } else {
-            VK_TRY(set_max_lds(bneck64_rows_kernel<256, false>, br_smem<256>()));
-            hipLaunchKernelGGL((bneck64_rows_kernel<256, false>), dim3(grid_), dim3(512), br_smem<256>(), stream, r);
-        }
-        VK_CHECK_HIP(hipGetLastError());
-        const double M = (double)N * H * W;
-        const double fl = 2.0 * M * (64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64));
-        return t.end(stream, concurrent ? 6 : 11, fl, (int)M, 256, cin, 3, 1,
-                     2.0 * (M * cin + M * 256 + 64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64)));
+        if (proj)
+            VKN_ROWS(64, true);
+        else
+            VKN_ROWS(256, false);
+        return t.end(stream, concurrent ? 6 : 11, fl, (int)M, 256, cin, 3, 1, by);
     }
     VK_REQUIRE((long)N * H * W * 512 < (1L << 31), VK_EINVAL, "bneck_fused: the tile form keeps signed 32-bit byte offsets");
-    const int grid = n_cu;                        // a multiple of 8: every XCD walks its own range of tiles
     k.stamps = nullptr;
 #ifdef VK_ABLATION
-    if (const char *sf = getenv("VK_BNECK_STAMPS")) {     // diagnostic: one stamped launch, 8 words per wave appended to the file
-        const size_t nb = (size_t)grid * 4 * 8 * sizeof(unsigned long);
-        VK_CHECK_HIP(hipMalloc((void **)&k.stamps, nb));
-        VK_CHECK_HIP(hipMemsetAsync(k.stamps, 0, nb, stream));
-        if (proj) {
-            VK_TRY(set_max_lds(bneck64_kernel<64, true, true>, bn_smem<64>()));
-            hipLaunchKernelGGL((bneck64_kernel<64, true, true>), dim3(grid), dim3(256), bn_smem<64>(), stream, k);
-        } else {
-            VK_TRY(set_max_lds(bneck64_kernel<256, false, true>, bn_smem<256>()));
-            hipLaunchKernelGGL((bneck64_kernel<256, false, true>), dim3(grid), dim3(256), bn_smem<256>(), stream, k);
-        }
-        VK_CHECK_HIP(hipStreamSynchronize(stream));
-        std::vector<unsigned long> hst((size_t)grid * 4 * 8);
-        VK_CHECK_HIP(hipMemcpy(hst.data(), k.stamps, nb, hipMemcpyDeviceToHost));
-        VK_CHECK_HIP(hipFree(k.stamps));
-        if (FILE *f = fopen(sf, "a")) {
-            fprintf(f, "# wg wave phaseA phaseB phaseC tiles kernel_cycles kernel_ticks(10ns)  proj=%d\n", (int)proj);
-            for (int w = 0; w < grid * 4; ++w) {
-                fprintf(f, "%d %d", w / 4, w % 4);
-                for (int i = 0; i < 6; ++i) fprintf(f, " %lu", hst[(size_t)w * 8 + i]);
-                fprintf(f, "\n");
-            }
-            fclose(f);
-        }
-        return VK_OK;
+    if (const char *sf = env_text("VK_BNECK_STAMPS")) {     // diagnostic: one stamped launch, 8 words per wave appended to the file
+        Stamps st;
+        VK_TRY(st.open((size_t)n_cu * 4 * 8, stream));
+        k.stamps = st.dev;
+        if (proj)
+            VKN_TILE(64, true, true);
+        else
+            VKN_TILE(256, false, true);
+        char header[96];
+        snprintf(header, sizeof(header), "# wg wave phaseA phaseB phaseC tiles kernel_cycles kernel_ticks(10ns)  proj=%d", (int)proj);
+        return st.finish(stream, sf, header, (size_t)n_cu * 4, 8, 6, 4);
     }
 #endif
     Timed t;
     VK_TRY(t.begin(stream));
-    if (proj) {
-        VK_TRY(set_max_lds(bneck64_kernel<64, true>, bn_smem<64>()));
-        hipLaunchKernelGGL((bneck64_kernel<64, true>), dim3(grid), dim3(256), bn_smem<64>(), stream, k);
-    } else {
-        VK_TRY(set_max_lds(bneck64_kernel<256, false>, bn_smem<256>()));
-        hipLaunchKernelGGL((bneck64_kernel<256, false>), dim3(grid), dim3(256), bn_smem<256>(), stream, k);
-    }
-    VK_CHECK_HIP(hipGetLastError());
-    const double M = (double)N * H * W;
-    const double fl = 2.0 * M * (64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64));
-    return t.end(stream, concurrent ? 6 : 11, fl, (int)M, 256, cin, 3, 1,
-                 2.0 * (M * cin + M * 256 + 64.0 * cin + 64.0 * 576 + 256.0 * (proj ? 128 : 64)));
+    if (proj)
+        VKN_TILE(64, true);
+    else
+        VKN_TILE(256, false);
+#undef VKN_TILE
+#undef VKN_ROWS
+#undef VKN_LAUNCH
+    return t.end(stream, concurrent ? 6 : 11, fl, (int)M, 256, cin, 3, 1, by);
 }
 
 }  // namespace vk

@@ -232,8 +232,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_blk_kernel(BlkK p) {
 
 // what the kernel takes (see the header): everything else stays on conv_mfma.hip
 static int blk_variant(const ConvArgs &a) {
-    const char *v = getenv("VK_CONV3X3_BLK");            // "0" disables (A/B switch and bit-identity tests; re-read per call)
-    if (v && v[0] == '0') return 0;
+    if (env_off("VK_CONV3X3_BLK")) return 0;
     if (a.stem || a.x2 || a.pool_part || a.res || a.dt != VK_F16 || a.out_dt != VK_F16 || a.relu > 1) return 0;
     if (a.kh != 3 || a.kw != 3 || a.stride != 1 || a.pad != a.dil || a.Cin != a.Cout || a.ldy != a.Cout) return 0;
     if (a.Cin % 64 != 0 || a.H != a.Ho || a.W != a.Wo) return 0;
@@ -260,7 +259,6 @@ static int launch_blk(const ConvArgs &a, hipStream_t stream) {
     constexpr int smem = 2 * ((((TH + 2 * DIL) * (TW + 2 * DIL) + 7) / 8 + 7) / 8) * 8 * 1024 + 256;
     DeviceState *ds = nullptr;
     VK_TRY(device_state(&ds));
-    VK_TRY(set_max_lds(conv3x3_blk_kernel<CB, TH, TW, VW, DIL>, smem));
     BlkK k;
     k.x = (const char *)a.x;
     k.w = (const char *)a.w;
@@ -287,8 +285,7 @@ static int launch_blk(const ConvArgs &a, hipStream_t stream) {
     const long M = (long)a.N * a.H * a.W;
     Timed t;
     VK_TRY(t.begin(stream));
-    hipLaunchKernelGGL((conv3x3_blk_kernel<CB, TH, TW, VW, DIL>), dim3(gx, slabs), dim3(512), smem, stream, k);
-    VK_CHECK_HIP(hipGetLastError());
+    VK_TRY(launch_lds(conv3x3_blk_kernel<CB, TH, TW, VW, DIL>, dim3(gx, slabs), dim3(512), smem, smem, stream, k));
     return t.end(stream, a.concurrent ? 6 : 7, 2.0 * (double)M * a.Cout * 9.0 * cg, (int)M, a.Cout, a.Cin, 3, 1,
                  2.0 * (double)M * a.Cin * 2.0 + (double)a.Cout * 9.0 * cg * 2.0);
 }

@@ -813,13 +813,10 @@ static int panel_pp(const ConvArgs &a, int mi = 8) {
 }
 
 // 8 or 9 row tiles per wave (256- or 288-pixel tiles): whichever takes fewer MFMA rows over the rounds of the grid on a device
-// of n_cu CUs.  VK_PANEL_MI=8 / 9 forces one where it is legal (A/B switch and bit-identity tests; re-read per call).
+// of n_cu CUs.  VK_PANEL_MI=8 / 9 forces one where it is legal.
 static int panel_mi(const ConvArgs &a, long M, int n_cu) {
     if (panel_pp(a, 9) == 0) return 8;
-    if (const char *v = getenv("VK_PANEL_MI")) {
-        if (v[0] == '8') return 8;
-        if (v[0] == '9') return 9;
-    }
+    if (const char v = env_first("VK_PANEL_MI"); v == '8' || v == '9') return v - '0';
     // few rounds: count MFMA rows over the rounds (res4 of 32 images: 3 x 8 against 2 x 9).  Many rounds: the workgroups drift apart
     // and the rounds blur; 36 MFMAs per barrier instead of 32 then win by ~1 % (measured on the Res5 conv2 grids, 14 rounds)
     const long nt = a.Cout / 256;
@@ -829,8 +826,7 @@ static int panel_mi(const ConvArgs &a, long M, int n_cu) {
 }
 
 bool conv3x3_panel_eligible(const ConvArgs &a) {
-    const char *v = getenv("VK_CONV3X3_PANEL");          // "0" disables (A/B switch, re-read per call)
-    if (v && v[0] == '0') return false;
+    if (env_off("VK_CONV3X3_PANEL")) return false;
     if (a.stem || a.dt != VK_F16 || a.out_dt != VK_F16 || a.relu > 1) return false;
     if (a.kh != 3 || a.kw != 3 || a.stride != 1 || a.pad != a.dil) return false;
     if (a.Cout % 256 != 0 || a.ldy != a.Cout || a.Cin % 64 != 0 || a.Cin < 128) return false;
@@ -843,28 +839,30 @@ bool conv3x3_panel_eligible(const ConvArgs &a) {
 
 // The leading images of the launch that take the PHASE form (whole groups of 16), 0 = none.  f16 is implied by the panel kernel;
 // dilation 2, even H, even W <= 14 (halo (W / 2 + 1) * 16 <= 128 rows); H <= 1024 keeps the reciprocal of W / 2 exact.
-// VK_PANEL_PHASE=0 selects the plain form (A/B switch and bit-identity tests; re-read per call).
+// VK_PANEL_PHASE=0 selects the plain form.
+static bool panel_phase_off() { return env_off("VK_PANEL_PHASE"); }
+#ifdef VK_ABLATION      // VK_PANEL_PHASE=A: the phase form's row order with every MFMA still issued, on zeroed fragments (what the order alone costs)
+static bool panel_phase_ablation() { return env_first("VK_PANEL_PHASE") == 'A'; }
+#endif
+
 int conv3x3_panel_phase_images(const ConvArgs &a) {
-    const char *v = getenv("VK_PANEL_PHASE");
-    if (v && v[0] == '0') return 0;
+    if (panel_phase_off()) return 0;
     if (a.dil != 2 || a.H % 2 != 0 || a.W % 2 != 0 || a.W > 14 || a.H > 1024 || a.N < 16) return 0;
     return a.N / 16 * 16;
 }
 
 // Rows of a tile of the launch's phase part: 512 (512 x 128 tiles), 256 under VK_PANEL_TALL=0 (the 256 x 256 phase
-// instantiation: A/B switch and bit-identity tests; re-read per call), 0 where no image of the launch takes the phase form.
+// instantiation), 0 where no image of the launch takes the phase form.
 int conv3x3_panel_phase_tile_rows(const ConvArgs &a) {
     if (a.Cout % 256 != 0 || conv3x3_panel_phase_images(a) == 0) return 0;
-    const char *v = getenv("VK_PANEL_TALL");
-    return v && v[0] == '0' ? 256 : 512;
+    return env_off("VK_PANEL_TALL") ? 256 : 512;
 }
 
 // 1 where the launch's phase part runs the fragment-window schedule (REUSE): every 512 x 128 launch, unless
-// VK_PANEL_REUSE=0 selects the schedule in which each tap reads its eight fragments (A/B switch and bit-identity tests; re-read per call).
+// VK_PANEL_REUSE=0 selects the schedule in which each tap reads its eight fragments.
 int conv3x3_panel_phase_reuse(const ConvArgs &a) {
     if (conv3x3_panel_phase_tile_rows(a) != 512) return 0;
-    const char *v = getenv("VK_PANEL_REUSE");
-    return v && v[0] == '0' ? 0 : 1;
+    return env_off("VK_PANEL_REUSE") ? 0 : 1;
 }
 
 static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase);
@@ -911,7 +909,7 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
     // phase launches take 512 x 128 tiles (4 x 2 waves, 6 panel pieces, 8 KiB weight slots); the plain form and VK_PANEL_TALL=0 keep 256 columns
     bool tall = phase && conv3x3_panel_phase_tile_rows(a) == 512;
 #ifdef VK_ABLATION
-    if (const char *pv = getenv("VK_PANEL_PHASE"); pv && pv[0] == 'A') tall = false;      // (the PHASE = 1 build has 256 x 256 tiles only)
+    if (panel_phase_ablation()) tall = false;      // (the PHASE = 1 build has 256 x 256 tiles only)
 #endif
     const int mi = phase ? 8 : panel_mi(a, M, ds->n_cu), pp = tall ? 6 : (phase ? 4 : panel_pp(a, mi));
     const int wslot = tall ? P_WSLOT / 2 : P_WSLOT;
@@ -925,9 +923,8 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
     k.tile_ctr = nullptr;
     k.static_tiles = total_tiles;
     int n_wgs = total_tiles;
-    const char *dyn_env = getenv("VK_PANEL_DYNAMIC");                        // "0": every tile static (A/B switch and bit-identity test; re-read per call)
-    const bool dyn_off = dyn_env && dyn_env[0] == '0';
-    if (!dyn_off && (pp == 3 || phase) && total_tiles >= 16 * 256) {          // many rounds on every CU: the last sixteenth is handed out dynamically
+    // many rounds on every CU: the last sixteenth is handed out dynamically (VK_PANEL_DYNAMIC=0: every tile static)
+    if (!env_off("VK_PANEL_DYNAMIC") && (pp == 3 || phase) && total_tiles >= 16 * 256) {
         VK_TRY(acquire_tile_counter(&k.tile_ctr));
         // (a multiple of 8: whole rounds of the XCD map, and whole panels: the 2 or 4 column tiles of a panel stay together, since the
         //  kernel takes n_tile = t_ % n_tiles of consecutive tile indices of one XCD)
@@ -937,35 +934,26 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
     }
     const dim3 grid(n_wgs), block(512);
 #ifdef VK_ABLATION
-    const int dbg = getenv("VK_CONV256_DBG") ? atoi(getenv("VK_CONV256_DBG")) : 0;
+    const int dbg = env_int("VK_CONV256_DBG", 0);
 #endif
     const int smem = 2 * pp * 128 * 64 + P_NW * wslot + (pp == 3 || tall ? 256 : 0);      // PP = 3: + the zero row; 512 x 128: + the tail's mailbox word
     k.stamps = nullptr;
-#define VKP_LAUNCH(PP_, DBG_, TAG_, MI_)                                                                                                   \
-    do {                                                                                                                                   \
-        VK_TRY(set_max_lds(conv3x3_panel_kernel<PP_, DBG_, TAG_, MI_>, 2 * PP_ * 128 * 64 + P_NW * P_WSLOT + (PP_ == 3 ? 256 : 0)));        \
-        hipLaunchKernelGGL((conv3x3_panel_kernel<PP_, DBG_, TAG_, MI_>), grid, block, smem, stream, k);                                     \
-    } while (0)
+    // (the limit of a PP-piece build is that of its 256-column form, whatever this launch's smem)
+#define VKP_LAUNCH(PP_, DBG_, TAG_, MI_)                                                                   \
+    VK_TRY(launch_lds(conv3x3_panel_kernel<PP_, DBG_, TAG_, MI_>, grid, block, smem,                       \
+                      2 * PP_ * 128 * 64 + P_NW * P_WSLOT + (PP_ == 3 ? 256 : 0), stream, k))
+#define VKP_LAUNCH_PHASE(...) VK_TRY(launch_lds(conv3x3_panel_kernel<__VA_ARGS__>, grid, block, smem, smem, stream, k))
 #ifdef VK_ABLATION      // stamp / timing-only (dbg 1: WRONG results) / LDS-epilogue builds: tools/ builds only (make ABLATION=1)
-    if (const char *sf = getenv("VK_PANEL_STAMPS"); sf && pp == 3) {   // diagnostic: one stamped launch (halo-64 / 48 build), 4 words per workgroup appended to the file
-        const size_t nb = (size_t)grid.x * 6 * sizeof(unsigned long);
-        VK_CHECK_HIP(hipMalloc((void **)&k.stamps, nb));
-        VK_CHECK_HIP(hipMemset(k.stamps, 0, nb));                 // (spare workgroups of a dynamic tail leave without a stamp)
+    if (const char *sf = env_text("VK_PANEL_STAMPS"); sf && pp == 3) {   // diagnostic: one stamped launch (halo-64 / 48 build), 6 words per workgroup appended to the file
+        Stamps st;
+        VK_TRY(st.open((size_t)grid.x * 6, stream));              // (spare workgroups of a dynamic tail leave without a stamp)
+        k.stamps = st.dev;
         if (mi == 9)
             VKP_LAUNCH(3, 4, 0, 9);
         else
             VKP_LAUNCH(3, 4, 0, 8);
-        VK_CHECK_HIP(hipStreamSynchronize(stream));
-        std::vector<unsigned long> h((size_t)grid.x * 6);
-        VK_CHECK_HIP(hipMemcpy(h.data(), k.stamps, nb, hipMemcpyDeviceToHost));
-        VK_CHECK_HIP(hipFree(k.stamps));
-        if (FILE *f = fopen(sf, "a")) {
-            fprintf(f, "# wg k_loop_cycles k_loop_ticks workgroup_ticks ticks_before_k_loop start_tick end_tick (tick = 10 ns)\n");
-            for (unsigned w = 0; w < grid.x; ++w)
-                fprintf(f, "%u %lu %lu %lu %lu %lu %lu\n", w, h[(size_t)w * 6], h[(size_t)w * 6 + 1], h[(size_t)w * 6 + 2], h[(size_t)w * 6 + 3], h[(size_t)w * 6 + 4],
-                        h[(size_t)w * 6 + 5]);
-            fclose(f);
-        }
+        VK_TRY(st.finish(stream, sf, "# wg k_loop_cycles k_loop_ticks workgroup_ticks ticks_before_k_loop start_tick end_tick (tick = 10 ns)",
+                         grid.x, 6, 6, 0));
     } else if (mi == 8 && pp == 3 && dbg == 8)
         VKP_LAUNCH(3, 8, 0, 8);
     else if (mi == 8 && pp == 3 && dbg == 1)
@@ -976,24 +964,17 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
         VKP_LAUNCH(3, 16, 0, 9);
     else if (mi == 9 && pp == 3 && dbg == 32)
         VKP_LAUNCH(3, 32, 0, 9);
+    else if (phase && panel_phase_ablation())
+        VKP_LAUNCH_PHASE(4, 0, 0, 8, 1);
     else
 #endif
-#ifdef VK_ABLATION      // VK_PANEL_PHASE=A: the phase form's row order with every MFMA still issued, on zeroed fragments (what the order alone costs)
-    if (const char *pv = getenv("VK_PANEL_PHASE"); phase && pv && pv[0] == 'A') {
-        VK_TRY(set_max_lds(conv3x3_panel_kernel<4, 0, 0, 8, 1>, smem));
-        hipLaunchKernelGGL((conv3x3_panel_kernel<4, 0, 0, 8, 1>), grid, block, smem, stream, k);
-    } else
-#endif
-    if (tall && conv3x3_panel_phase_reuse(a)) {
-        VK_TRY(set_max_lds(conv3x3_panel_kernel<6, 0, 0, 8, 2, 4, 1>, smem));
-        hipLaunchKernelGGL((conv3x3_panel_kernel<6, 0, 0, 8, 2, 4, 1>), grid, block, smem, stream, k);
-    } else if (tall) {
-        VK_TRY(set_max_lds(conv3x3_panel_kernel<6, 0, 0, 8, 2, 4>, smem));
-        hipLaunchKernelGGL((conv3x3_panel_kernel<6, 0, 0, 8, 2, 4>), grid, block, smem, stream, k);
-    } else if (phase) {        // (one symbol: the form is not launched beside another stream's kernels)
-        VK_TRY(set_max_lds(conv3x3_panel_kernel<4, 0, 0, 8, 2>, smem));
-        hipLaunchKernelGGL((conv3x3_panel_kernel<4, 0, 0, 8, 2>), grid, block, smem, stream, k);
-    } else if (mi == 8 && pp == 3 && a.concurrent)
+    if (tall && conv3x3_panel_phase_reuse(a))
+        VKP_LAUNCH_PHASE(6, 0, 0, 8, 2, 4, 1);
+    else if (tall)
+        VKP_LAUNCH_PHASE(6, 0, 0, 8, 2, 4);
+    else if (phase)        // (one symbol: the form is not launched beside another stream's kernels)
+        VKP_LAUNCH_PHASE(4, 0, 0, 8, 2);
+    else if (mi == 8 && pp == 3 && a.concurrent)
         VKP_LAUNCH(3, 0, 1, 8);
     else if (mi == 8 && pp == 3)
         VKP_LAUNCH(3, 0, 0, 8);
@@ -1009,8 +990,8 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
         VKP_LAUNCH(4, 0, 1, 9);
     else
         VKP_LAUNCH(4, 0, 0, 9);
+#undef VKP_LAUNCH_PHASE
 #undef VKP_LAUNCH
-    VK_CHECK_HIP(hipGetLastError());
     return t.end(stream, a.concurrent ? 6 : 4, 2.0 * (double)k.M * a.Cout * 9 * a.Cin, k.M, a.Cout, a.Cin, 9, 1,
                  2.0 * ((double)k.M * a.Cin + (double)k.M * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * 9 * a.Cin));
 }

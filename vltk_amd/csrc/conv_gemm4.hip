@@ -540,15 +540,15 @@ int acquire_tile_counter(unsigned **ctr) {
 }
 
 bool conv_gemm4_eligible(const ConvArgs &a) {
-    const char *v = getenv("VK_CONV_GEMM4");             // "0" disables, "2" also takes small grids (A/B switch and bit-identity tests; re-read per call)
-    if (v && v[0] == '0') return false;
-    const bool any_grid = v && v[0] == '2';
+    const char v = env_first("VK_CONV_GEMM4");           // "0" disables, "2" also takes small grids
+    if (v == '0') return false;
+    const bool any_grid = v == '2';
     if (a.stem || a.pool_part || a.groups > 1 || a.dt != VK_F16 || a.out_dt != VK_F16 || a.relu > 1) return false;
     if (a.kh != 1 || a.kw != 1 || a.pad != 0 || a.stride != 1) return false;
     if (a.Cout % 256 != 0 || a.ldy != a.Cout || a.Cout > 8192) return false;      // (the bias rides behind the ring in LDS)
     const int cin2 = a.x2 ? a.Cin2 : 0;
-    int min_k = 1024;
-    if (const char *mk = getenv("VK_GEMM4_MINK")) min_k = atoi(mk) >= 256 ? atoi(mk) : 1024;     // A/B switch (tools/conv_bench.py)
+    int min_k = env_int("VK_GEMM4_MINK", 1024);          // (tools/conv_bench.py)
+    if (min_k < 256) min_k = 1024;
     if (a.Cin % 32 != 0 || cin2 % 32 != 0 || (a.Cin + cin2) % 128 != 0 || a.Cin + cin2 < min_k) return false;   // groups of four 32-channel stages
     // the row pitch is a 14-bit descriptor stride; longer rows (the FPN box head's 12544-wide fc1) run with stride = pitch / 2 or / 4
     // and index = row * 2 or * 4 (one input only: the index is shared)
@@ -604,61 +604,40 @@ int launch_conv_gemm4(const ConvArgs &a, hipStream_t stream) {
     const int grid_wgs = total_tiles < n_cu ? total_tiles : n_cu;
     k.tile_ctr = nullptr;
     k.static_tiles = total_tiles;
-    const char *dyn_env = getenv("VK_GEMM4_DYNAMIC");                        // "0": every tile static (A/B switch and bit-identity test; re-read per call)
-    const bool dyn_off = dyn_env && dyn_env[0] == '0';
-    if (!dyn_off && !a.m_dev && total_tiles >= 16 * grid_wgs && a.Cout <= 4096) {     // long launches (a device-side M keeps the static walk: the tail's fetch count must be known here): the last eighth of a workgroup's tiles is dynamic
+    // long launches: the last eighth of a workgroup's tiles is dynamic (VK_GEMM4_DYNAMIC=0: every tile static; a device-side M keeps
+    // the static walk, since the tail's fetch count must be known here)
+    if (!env_off("VK_GEMM4_DYNAMIC") && !a.m_dev && total_tiles >= 16 * grid_wgs && a.Cout <= 4096) {
         VK_TRY(acquire_tile_counter(&k.tile_ctr));
         k.static_tiles = (total_tiles / grid_wgs) * 7 / 8 * grid_wgs;
         k.ctr_last = (unsigned)(total_tiles - k.static_tiles + grid_wgs - 1);     // the tail's tiles + one miss per workgroup
     }
     const size_t smem_bytes = G_SMEM + (size_t)a.Cout * 4 + 16;           // ring, bias, the tail's mailbox word
+    // (one limit for every launch: the ring and the widest bias, Cout = 8192)
+#define VKG_LAUNCH(...) VK_TRY(launch_lds(conv_gemm4_kernel<__VA_ARGS__>, dim3(grid_wgs), dim3(256), smem_bytes, G_SMEM + 32768, stream, k))
 #ifdef VK_ABLATION      // stamp / timing-only builds (WRONG results for DBG != 0): tools/ builds only (make ABLATION=1)
-    if (const char *sf = getenv("VK_GEMM4_STAMPS")) {    // diagnostic: one stamped launch, 4 words per workgroup appended to the file
-        const int nwg = grid_wgs;
-        const size_t nb = (size_t)nwg * 8 * sizeof(unsigned long);
-        VK_CHECK_HIP(hipMalloc((void **)&k.stamps, nb));
-        const char *d = getenv("VK_GEMM4_DBG");
-        switch (d ? atoi(d) : 0) {
-#define VKG_DBG_CASE(D_)                                                                                                   \
-    case D_:                                                                                                               \
-        VK_TRY(set_max_lds(conv_gemm4_kernel<true, D_>, G_SMEM + 32768));                                                 \
-        hipLaunchKernelGGL((conv_gemm4_kernel<true, D_>), dim3(nwg), dim3(256), smem_bytes, stream, k);                        \
-        break;
+    const int dbg = env_int("VK_GEMM4_DBG", 0);
+    if (const char *sf = env_text("VK_GEMM4_STAMPS")) {    // diagnostic: one stamped launch, 8 words per workgroup appended to the file
+        Stamps st;
+        VK_TRY(st.open((size_t)grid_wgs * 8, stream));
+        k.stamps = st.dev;
+        switch (dbg) {
+#define VKG_DBG_CASE(D_) case D_: VKG_LAUNCH(true, D_); break;
             VKG_DBG_CASE(1) VKG_DBG_CASE(2) VKG_DBG_CASE(3) VKG_DBG_CASE(4) VKG_DBG_CASE(8) VKG_DBG_CASE(12) VKG_DBG_CASE(13) VKG_DBG_CASE(15)
 #undef VKG_DBG_CASE
-            default:
-                VK_TRY(set_max_lds(conv_gemm4_kernel<true>, G_SMEM + 32768));
-                hipLaunchKernelGGL(conv_gemm4_kernel<true>, dim3(nwg), dim3(256), smem_bytes, stream, k);
+            default: VKG_LAUNCH(true);
         }
-        VK_CHECK_HIP(hipStreamSynchronize(stream));
-        std::vector<unsigned long> h((size_t)nwg * 8);
-        VK_CHECK_HIP(hipMemcpy(h.data(), k.stamps, nb, hipMemcpyDeviceToHost));
-        VK_CHECK_HIP(hipFree(k.stamps));
-        if (FILE *f = fopen(sf, "a")) {
-            fprintf(f, "# wg loop_cycles loop_realtime_ticks stages end_realtime\n");
-            for (int w = 0; w < nwg; ++w) {
-                fprintf(f, "%d", w);
-                for (int i = 0; i < 8; ++i) fprintf(f, " %lu", h[(size_t)w * 8 + i]);
-                fprintf(f, "\n");
-            }
-            fclose(f);
-        }
-    } else if (getenv("VK_GEMM4_DBG") && atoi(getenv("VK_GEMM4_DBG")) == 128) {      // bisect: builtin MFMAs
-        VK_TRY(set_max_lds(conv_gemm4_kernel<false, 128>, G_SMEM + 32768));
-        hipLaunchKernelGGL((conv_gemm4_kernel<false, 128>), dim3(grid_wgs), dim3(256), smem_bytes, stream, k);
-    } else
+        VK_TRY(st.finish(stream, sf, "# wg loop_cycles loop_realtime_ticks stages end_realtime", grid_wgs, 8, 8, 0));
+    } else if (dbg == 128)      // bisect: builtin MFMAs
+        VKG_LAUNCH(false, 128);
+    else
 #endif
-    if (dd) {
-        VK_TRY(set_max_lds(conv_gemm4_kernel<false, 0, 2>, G_SMEM + 32768));
-        hipLaunchKernelGGL((conv_gemm4_kernel<false, 0, 2>), dim3(grid_wgs), dim3(256), smem_bytes, stream, k);
-    } else if (!a.concurrent) {
-        VK_TRY(set_max_lds(conv_gemm4_kernel<false>, G_SMEM + 32768));
-        hipLaunchKernelGGL(conv_gemm4_kernel<false>, dim3(grid_wgs), dim3(256), smem_bytes, stream, k);
-    } else {
-        VK_TRY(set_max_lds(conv_gemm4_kernel<false, 0, 1>, G_SMEM + 32768));
-        hipLaunchKernelGGL((conv_gemm4_kernel<false, 0, 1>), dim3(grid_wgs), dim3(256), smem_bytes, stream, k);
-    }
-    VK_CHECK_HIP(hipGetLastError());
+    if (dd)
+        VKG_LAUNCH(false, 0, 2);
+    else if (!a.concurrent)
+        VKG_LAUNCH(false);
+    else
+        VKG_LAUNCH(false, 0, 1);
+#undef VKG_LAUNCH
     const int K = a.Cin + cin2;
     return t.end(stream, a.concurrent ? 6 : 10, 2.0 * (double)M * a.Cout * K, (int)M, a.Cout, K, 1, 1,
                  2.0 * ((double)M * K + (double)M * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * K));

@@ -341,12 +341,9 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvK p) {
 template <typename T, typename OutT, int BN, bool STEM>
 static int launch_t(const ConvK &k, hipStream_t stream) {
     constexpr int smem = 2 * (CONV_BM * 128 + BN * 128);
-    VK_TRY(set_max_lds(conv_mfma_kernel<T, OutT, BN, STEM>, smem));
-    dim3 grid(k.m_tiles * k.n_tiles), block(256);
     Timed t;
     VK_TRY(t.begin(stream));
-    hipLaunchKernelGGL((conv_mfma_kernel<T, OutT, BN, STEM>), grid, block, smem, stream, k);
-    VK_CHECK_HIP(hipGetLastError());
+    VK_TRY(launch_lds(conv_mfma_kernel<T, OutT, BN, STEM>, dim3(k.m_tiles * k.n_tiles), dim3(256), smem, smem, stream, k));
     int bucket = 3;
     if (sizeof(T) == 2 && !STEM) bucket = sizeof(OutT) == 4 ? 2 : 1;
     if (k.concurrent) bucket = 6;

@@ -423,8 +423,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma256_kernel(Conv256K p) {
 }
 
 bool conv256_dual_ok(const ConvArgs &a) {
-    const char *v = getenv("VK_CONV256_DUAL");           // "0": the two-per-CU kernel takes the dual-source form (A/B switch)
-    if (v && v[0] == '0') return false;
+    if (env_off("VK_CONV256_DUAL")) return false;        // "0": the two-per-CU kernel takes the dual-source form
     if (!a.x2 || a.stem || a.pool_part || a.groups > 1 || a.dt != VK_F16 || a.out_dt != VK_F16 || a.relu > 1) return false;
     if (a.kh != 1 || a.kw != 1 || a.pad != 0 || a.stride != 1) return false;
     if (a.Cout % R_BN != 0 || a.ldy != a.Cout || a.Cin % 32 != 0 || a.Cin2 % 32 != 0 || (a.Cin + a.Cin2) % 64 != 0) return false;
@@ -434,7 +433,7 @@ bool conv256_dual_ok(const ConvArgs &a) {
 }
 
 bool conv256_eligible(const ConvArgs &a) {
-    static const bool disabled = getenv("VK_DISABLE_CONV256") != nullptr;
+    static const bool disabled = env_set("VK_DISABLE_CONV256");
     if (disabled || a.stem) return false;
     if (a.relu > 1) return false;             // only the 128-tile kernel has the GELU / tanh epilogues
     if (a.dt != VK_F16 || a.out_dt != VK_F16) return false;
@@ -446,10 +445,7 @@ bool conv256_eligible(const ConvArgs &a) {
 
 template <int DBG, bool DUAL = false>
 static int launch_256(const Conv256K &k, hipStream_t stream) {
-    VK_TRY(set_max_lds(conv_mfma256_kernel<DBG, DUAL>, R_SMEM));
-    hipLaunchKernelGGL((conv_mfma256_kernel<DBG, DUAL>), dim3(k.m_tiles * k.n_tiles), dim3(512), R_SMEM, stream, k);
-    VK_CHECK_HIP(hipGetLastError());
-    return VK_OK;
+    return launch_lds(conv_mfma256_kernel<DBG, DUAL>, dim3(k.m_tiles * k.n_tiles), dim3(512), R_SMEM, R_SMEM, stream, k);
 }
 
 int launch_conv256(const ConvArgs &a, hipStream_t stream) {
@@ -487,7 +483,7 @@ int launch_conv256(const ConvArgs &a, hipStream_t stream) {
     k.n_tiles = a.Cout / R_BN;
     Timed t;
     VK_TRY(t.begin(stream));
-    const int dbg = getenv("VK_CONV256_DBG") ? atoi(getenv("VK_CONV256_DBG")) : 0;   // re-read: lets one process A/B variants
+    const int dbg = env_int("VK_CONV256_DBG", 0);
     int st;
     if (a.x2) {
         st = launch_256<0, true>(k, stream);

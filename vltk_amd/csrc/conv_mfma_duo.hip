@@ -561,8 +561,8 @@ int launch_pool_finish(const float *part, int N, int HoWo, int Cin, int Cout, bo
 bool conv_duo_eligible(const ConvArgs &a) {
     if (a.pool_part) return conv_duo_pool_ok(a);
     if (a.x2) return conv_duo_dual_ok(a);
-    const char *v = getenv("VK_CONV_DUO");               // "0" disables (A/B switch, re-read per call)
-    if (v && v[0] == '0') return false;
+    const char v = env_first("VK_CONV_DUO");             // "0" disables, "1" forces it wherever it is legal
+    if (v == '0') return false;
     if (a.stem || (a.dt != VK_F16 && a.dt != VK_BF16) || a.out_dt != a.dt) return false;
     if (a.relu > 2 || (a.relu == 2 && a.dt != VK_BF16)) return false;     // GELU epilogue: bf16 build only; no tanh
     if (a.kh != 1 || a.kw != 1 || a.pad != 0) return false;
@@ -572,15 +572,13 @@ bool conv_duo_eligible(const ConvArgs &a) {
     if (M < 8 * D_BM) return false;
     // measured (interleaved A/B, one device): -10...-19 % on every K <= 512 layer and on the small-grid K = 1024
     // layers; the large-grid K >= 1024 layers (Res5 conv1 / shortcut) are MFMA-loop bound and equal or 1-2 % slower
-    if (v && v[0] == '1') return true;                   // "1" forces it wherever it is legal (A/B, tests)
+    if (v == '1') return true;
     return a.Cin <= 512 || M < 400000;
 }
 
 template <typename ET, bool STAMP, int DBG = 0, bool GELU = false, int TAG = 0>
 static int launch_duo(const DuoK &k, dim3 grid, hipStream_t stream) {
-    VK_TRY(set_max_lds(conv_duo_kernel<ET, STAMP, 3, DBG, GELU, TAG>, d_smem(3)));
-    hipLaunchKernelGGL((conv_duo_kernel<ET, STAMP, 3, DBG, GELU, TAG>), grid, dim3(256), d_smem(3), stream, k);
-    return VK_OK;
+    return launch_lds(conv_duo_kernel<ET, STAMP, 3, DBG, GELU, TAG>, grid, dim3(256), d_smem(3), d_smem(3), stream, k);
 }
 
 int launch_conv_duo(const ConvArgs &a, hipStream_t stream) {
@@ -620,10 +618,11 @@ int launch_conv_duo(const ConvArgs &a, hipStream_t stream) {
     k.stamps = nullptr;
     int st;
 #ifdef VK_ABLATION      // stamp / timing-only builds: tools/ builds only (make ABLATION=1)
-    if (const char *sf = getenv("VK_DUO_STAMPS")) {      // diagnostic: one launch, phase stamps appended to the file
-        const size_t nb = (size_t)grid.x * 12 * sizeof(unsigned long);
-        VK_CHECK_HIP(hipMalloc((void **)&k.stamps, nb));
-        const int dbg = getenv("VK_DUO_DBG") ? atoi(getenv("VK_DUO_DBG")) : 0;
+    if (const char *sf = env_text("VK_DUO_STAMPS")) {    // diagnostic: one launch, phase stamps appended to the file
+        Stamps stamps;
+        VK_TRY(stamps.open((size_t)grid.x * 12, stream));
+        k.stamps = stamps.dev;
+        const int dbg = env_int("VK_DUO_DBG", 0);
         if (false) {}
 #define VKD_DBG_RUN(D) else if (dbg == D) st = launch_duo<_Float16, true, D>(k, grid, stream)
         VKD_DBG_RUN(1); VKD_DBG_RUN(3); VKD_DBG_RUN(4); VKD_DBG_RUN(7); VKD_DBG_RUN(8); VKD_DBG_RUN(11); VKD_DBG_RUN(12);
@@ -631,19 +630,9 @@ int launch_conv_duo(const ConvArgs &a, hipStream_t stream) {
         else
             st = launch_duo<_Float16, true>(k, grid, stream);
         VK_TRY(st);
-        VK_CHECK_HIP(hipStreamSynchronize(stream));
-        std::vector<unsigned long> h((size_t)grid.x * 12);
-        VK_CHECK_HIP(hipMemcpy(h.data(), k.stamps, nb, hipMemcpyDeviceToHost));
-        VK_CHECK_HIP(hipFree(k.stamps));
-        if (FILE *f = fopen(sf, "a")) {
-            fprintf(f, "# launch M=%d cout=%d cin=%d grid=%u\n", k.M, a.Cout, a.Cin, grid.x);
-            for (unsigned b = 0; b < grid.x; ++b) {
-                fprintf(f, "%u", b);
-                for (int i = 0; i < 12; ++i) fprintf(f, " %lu", h[(size_t)b * 12 + i]);
-                fprintf(f, "\n");
-            }
-            fclose(f);
-        }
+        char header[96];
+        snprintf(header, sizeof(header), "# launch M=%d cout=%d cin=%d grid=%u", k.M, a.Cout, a.Cin, grid.x);
+        st = stamps.finish(stream, sf, header, grid.x, 12, 12, 0);
     } else
 #endif
         if (a.dt == VK_BF16 && a.relu == 2)
@@ -655,7 +644,6 @@ int launch_conv_duo(const ConvArgs &a, hipStream_t stream) {
         else
             st = launch_duo<_Float16, false>(k, grid, stream);
     VK_TRY(st);
-    VK_CHECK_HIP(hipGetLastError());
     const int K = a.Cin + (a.x2 ? a.Cin2 : 0);
     return t.end(stream, a.concurrent ? 6 : 5, 2.0 * (double)k.M * a.Cout * K, k.M, a.Cout, K, 1, a.stride,
                  2.0 * ((double)a.N * a.H * a.W * K + (double)k.M * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * K));

@@ -428,11 +428,10 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_ws_kernel(WsK p) {
 // kernel.  The per-image fp64 sums (Cout x 8 B per image) live in the workspace that kernel sizes for its per-tile partials
 // (Cout x 16 B per 128 rows: larger from 128 rows per image on, which its own eligibility asks for).  Both sides of the
 // hand-over -- launch_conv and launch_pool_finish -- decide with this one function.
+static bool ws_off() { return env_off("VK_CONV_WS"); }      // VK_CONV_WS=0: no layer runs here
+
 bool conv_pool_sums_f64(long N, int HW, int Cin, int Cout, bool dual) {
-    const char *v = getenv("VK_CONV_WS");                // "0" disables (A/B switch and bit-identity tests; re-read per call)
-    if (v && v[0] == '0') return false;
-    const char *q = getenv("VK_WS_POOL");                // "0": the fused mean stays on the two-per-CU kernel
-    if (q && q[0] == '0') return false;
+    if (ws_off() || env_off("VK_WS_POOL")) return false;      // VK_WS_POOL=0: the fused mean stays on the two-per-CU kernel
     if (dual || Cin != 512 || Cout % 256 != 0 || 32 % (Cout / 256) != 0) return false;
     const long M = N * HW;
     return HW >= 128 && HW <= 8192 && M >= 8 * 128 && M < (1L << 31) - 128;
@@ -444,14 +443,13 @@ bool conv_ws_pool_ok(const ConvArgs &a) {
 }
 
 bool conv_ws_eligible(const ConvArgs &a) {
-    const char *v = getenv("VK_CONV_WS");                // "0" disables (A/B switch and bit-identity tests; re-read per call)
-    if (v && v[0] == '0') return false;
+    if (ws_off()) return false;
     if (a.pool_part) return conv_ws_pool_ok(a);
     if (a.stem || a.groups > 1 || a.dt != VK_F16 || a.out_dt != VK_F16 || a.relu > 1) return false;
     if (a.kh != 1 || a.kw != 1 || a.pad != 0 || a.stride < 1) return false;
     if (a.stride != 1) {                                                  // strided: K = 256 / 512, one source, no residual rows to map
-        const char *sv = getenv("VK_WS_STRIDED");                         // "0": strided 1x1 convs stay on the two-per-CU kernel (A/B switch)
-        if ((sv && sv[0] == '0') || a.x2 || a.res || (a.Cin != 256 && a.Cin != 512)) return false;
+        // VK_WS_STRIDED=0: strided 1x1 convs stay on the two-per-CU kernel
+        if (env_off("VK_WS_STRIDED") || a.x2 || a.res || (a.Cin != 256 && a.Cin != 512)) return false;
     }
     if (a.x2 && (a.Cin != 64 || a.Cin2 != 64)) return false;             // two sources: 64 + 64 channels only
     if (a.Cout % 256 != 0 || a.ldy != a.Cout || (a.Cin != 64 && a.Cin != 128 && a.Cin != 256 && a.Cin != 512)) return false;
@@ -464,10 +462,7 @@ bool conv_ws_eligible(const ConvArgs &a) {
 template <int KC, int NW = 8, int DBG = 0, bool POOL = false, bool DUAL = false, bool STRIDED = false>
 static int launch_ws(const WsK &k, hipStream_t stream) {
     constexpr int smem = 6 * WS_BM * 256 + 4 * WS_BM * 128 + 1024;
-    VK_TRY(set_max_lds(conv_ws_kernel<KC, NW, DBG, POOL, DUAL, STRIDED>, smem));
-    hipLaunchKernelGGL((conv_ws_kernel<KC, NW, DBG, POOL, DUAL, STRIDED>), dim3(256), dim3(NW * 64), smem, stream, k);
-    VK_CHECK_HIP(hipGetLastError());
-    return VK_OK;
+    return launch_lds(conv_ws_kernel<KC, NW, DBG, POOL, DUAL, STRIDED>, dim3(256), dim3(NW * 64), smem, smem, stream, k);
 }
 
 int launch_conv_ws(const ConvArgs &a, hipStream_t stream) {
@@ -503,34 +498,20 @@ int launch_conv_ws(const ConvArgs &a, hipStream_t stream) {
         return t.end(stream, a.concurrent ? 6 : 8, 2.0 * (double)M * a.Cout * a.Cin, (int)M, a.Cout, a.Cin, 1, 1,
                      2.0 * ((double)M * a.Cin + (double)M * a.Cout * (a.res ? 1 : 0) + (double)a.Cout * a.Cin));
     }
-    const char *nwv = getenv("VK_WS_WAVES");             // "4" / "8": A/B switch, re-read per call
-    const int nw = nwv ? atoi(nwv) : 8;
+    const int nw = env_int("VK_WS_WAVES", 8);            // 8, or the four-wave build
 #ifdef VK_ABLATION      // stamp build: tools/ builds only (make ABLATION=1)
-    if (const char *sf = getenv("VK_WS_STAMPS")) {       // diagnostic: one stamped launch (K = 512), cycle sums appended to the file
+    if (const char *sf = env_text("VK_WS_STAMPS")) {     // diagnostic: one stamped launch (K = 512), cycle sums appended to the file
         if (a.Cin != 512) return VK_EINVAL;
-        const size_t nb = (size_t)256 * 8 * 16 * sizeof(unsigned long);
-        VK_CHECK_HIP(hipMalloc((void **)&k.stamps, nb));
-        VK_CHECK_HIP(hipMemsetAsync(k.stamps, 0, nb, stream));
-        st = nw == 8 ? launch_ws<16, 8, 32>(k, stream) : launch_ws<16, 4, 32>(k, stream);
-        VK_CHECK_HIP(hipStreamSynchronize(stream));
-        std::vector<unsigned long> h(256 * 8 * 16);
-        VK_CHECK_HIP(hipMemcpy(h.data(), k.stamps, nb, hipMemcpyDeviceToHost));
-        VK_CHECK_HIP(hipFree(k.stamps));
-        if (FILE *f = fopen(sf, "a")) {
-            fprintf(f, "# wg wave total vm_wait barrier stage_body res_wait epilogue tiles realtime\n");
-            for (int w = 0; w < 256 * nw; ++w) {
-                fprintf(f, "%d %d", w / nw, w % nw);
-                for (int i = 0; i < 16; ++i) fprintf(f, " %lu", h[(size_t)w * 16 + i]);
-                fprintf(f, "\n");
-            }
-            fclose(f);
-        }
+        Stamps stamps;
+        VK_TRY(stamps.open((size_t)256 * 8 * 16, stream));
+        k.stamps = stamps.dev;
+        VK_TRY((nw == 8 ? launch_ws<16, 8, 32>(k, stream) : launch_ws<16, 4, 32>(k, stream)));
+        st = stamps.finish(stream, sf, "# wg wave total vm_wait barrier stage_body res_wait epilogue tiles realtime", (size_t)256 * nw, 16, 16, nw);
     } else
 #endif
     {
 #ifdef VK_ABLATION
-        const char *d = getenv("VK_WS_DBG");
-        const int dbg = d ? atoi(d) : 0;
+        const int dbg = env_int("VK_WS_DBG", 0);
 #define VKW_DBG_CASE(NW_, D_) \
     case D_: st = launch_ws<16, NW_, D_>(k, stream); break;
 #else      // the shipped library has no timing-only (WRONG-result) builds and ignores VK_WS_DBG / VK_WS_STAMPS

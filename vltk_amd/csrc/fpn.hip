@@ -392,7 +392,7 @@ int vk_roi_align(const void *const *maps, const int32_t *Hs, const int32_t *Ws, 
     }
     const int vec = 16 / (int)dtype_size(dt);
     if (C % vec == 0 && C / vec <= 256) {            // one workgroup per RoI, 16-byte lanes (the FPN case: C = 256)
-        static const bool per_sample = getenv("VK_ROIALIGN_TABLES") && atoi(getenv("VK_ROIALIGN_TABLES")) == 0;   // A/B switch
+        static const bool per_sample = env_set("VK_ROIALIGN_TABLES") && env_int("VK_ROIALIGN_TABLES", 1) == 0;
         if (P <= RA_MAXP && !per_sample) {
             int groups = 256 / (C / vec);
             while ((P * P) % groups) --groups;       // no idle group in the last pass (P = 7, 32 lanes per bin: 7 groups)

@@ -321,7 +321,7 @@ static int finalize_block(vk_handle *h, Block &b) {
 // (conv_duo_pool_ok): a chunk whose [rows x mid channels] f16 tensor reaches 4 GiB (ResNeXt-152 32x8d at 9600 RoIs: 7.7 GB)
 // keeps the separate mean kernel instead of failing the forward.
 static bool fused_mean_ok(const vk_handle *h, int P, size_t rows) {
-    static const bool off = getenv("VK_NO_FUSED_MEAN") != nullptr;      // A/B switch
+    static const bool off = env_set("VK_NO_FUSED_MEAN");
     const long mid5 = (long)h->cfg.num_groups * h->cfg.width_per_group * 8;
     return !off && h->dt == VK_F16 && h->cfg.res5_halve == 0 && P * P >= 128 && P * P <= 255 && h->res5_c % 256 == 0 &&
            (long)rows * mid5 * 2 < (1L << 32);
@@ -607,7 +607,7 @@ int vk_create(const vk_config *cfg, int device, vk_handle **out) {
     h->cfg = *cfg;
     h->device = device;
     h->dt = (vk_dtype)cfg->precision;
-    if (getenv("VK_PREDICTOR_FP16")) h->pdt = h->dt;            // A/B switch: round 1's 16-bit predictor
+    if (env_set("VK_PREDICTOR_FP16")) h->pdt = h->dt;           // round 1's 16-bit predictor
     for (const OptionRow &o : kOptions) (void)vk_option_default(o.key, &(h->*o.member));     // the built-in defaults or the VK_* variables
     const int di = cfg->depth == 50 ? 0 : (cfg->depth == 101 ? 1 : 2);
     add_conv_names(h->names, "backbone.stem.conv1", true);
@@ -782,7 +782,7 @@ int vk_option_default(const char *key, int *value) {
     const OptionRow *o = find_option(key);
     if (!o) return VK_EINVAL;
     *value = o->def;
-    const char *env = o->env ? getenv(o->env) : nullptr;
+    const char *env = o->env ? env_text(o->env) : nullptr;
     if (!env) return VK_OK;
     if (o->rule == ENV_ATOI_POSITIVE) {
         if (atoi(env) > 0) *value = atoi(env);

@@ -713,10 +713,9 @@ static int launch_nms(const float *boxes, const int32_t *valid, const int32_t *c
                       double thr, int max_keep, unsigned long long *mask, int32_t *keep_idx, int32_t *keep_count, int32_t *done,
                       hipStream_t s) {
     const int nwords = ceil_div(cap, 64);
-    const char *e = getenv("VK_NMS_LEAD");                    // boxes of phase A; "0": one phase (A/B switch and tests; re-read per call)
-    int lead = e ? atoi(e) : (2 * max_keep > 1024 ? 2 * max_keep : 1024);
+    const int lead = env_int("VK_NMS_LEAD", 2 * max_keep > 1024 ? 2 * max_keep : 1024);      // boxes of phase A; <= 0 (explicit only): one phase
     const int na = ceil_div(lead, 64);
-    if ((e && lead <= 0) || na >= nb || !done) {
+    if (lead <= 0 || na >= nb || !done) {
         hipLaunchKernelGGL(nms_mask_kernel, dim3(nb, nb, N), dim3(64), 0, s, boxes, counts, cap, nwords, thr, mask, 0, (const int32_t *)nullptr);
         VK_CHECK_HIP(hipGetLastError());
         hipLaunchKernelGGL(nms_scan_kernel, dim3(N), dim3(128), 0, s, mask, valid, counts, cap, nwords, max_keep, keep_idx, keep_count, 0,
@@ -786,26 +785,20 @@ int vk_rpn_proposals_ignorey(const float *logits, int ld_logits, const float *de
     cfg.offset = offset;
     cfg.stop = 0;
 #ifdef VK_ABLATION
-    if (const char *e = getenv("VK_RPN_STOP")) cfg.stop = atoi(e);
+    cfg.stop = env_int("VK_RPN_STOP", 0);
 #endif
     const size_t smem = (size_t)sortn * 8 + 2048;
-    if (!bands_on) {
-        VK_TRY(set_max_lds(rpn_select_decode_kernel, RPN_MAX_PRE * 8 + 2048));
-        hipLaunchKernelGGL(rpn_select_decode_kernel, dim3(N), dim3(RPN_THREADS), smem, s, logits, ld_logits, deltas, ld_deltas,
-                           Hf, Wf, A, cell_anchors, image_hw, cfg, pre_topk, sortn, w.cand_boxes, w.cand_logit, w.cand_valid,
-                           w.cand_count, nonfinite_flag);
-    } else if (f64) {
-        VK_TRY(set_max_lds(rpn_select_decode_bands_kernel<double>, RPN_MAX_PRE * 8 + 2048));
-        hipLaunchKernelGGL(rpn_select_decode_bands_kernel<double>, dim3(N), dim3(RPN_THREADS), smem, s, logits, ld_logits, deltas, ld_deltas,
-                           Hf, Wf, A, cell_anchors, image_hw, cfg, pre_topk, sortn, w.cand_boxes, w.cand_logit, w.cand_valid,
-                           w.cand_count, nonfinite_flag, bt);
-    } else {
-        VK_TRY(set_max_lds(rpn_select_decode_bands_kernel<float>, RPN_MAX_PRE * 8 + 2048));
-        hipLaunchKernelGGL(rpn_select_decode_bands_kernel<float>, dim3(N), dim3(RPN_THREADS), smem, s, logits, ld_logits, deltas, ld_deltas,
-                           Hf, Wf, A, cell_anchors, image_hw, cfg, pre_topk, sortn, w.cand_boxes, w.cand_logit, w.cand_valid,
-                           w.cand_count, nonfinite_flag, bt);
-    }
-    VK_CHECK_HIP(hipGetLastError());
+    const size_t sel_cap = RPN_MAX_PRE * 8 + 2048;
+#define VK_RPN_SELECT(KERNEL_, ...)                                                                                                     \
+    VK_TRY(launch_lds(KERNEL_, dim3(N), dim3(RPN_THREADS), smem, sel_cap, s, logits, ld_logits, deltas, ld_deltas, Hf, Wf, A, cell_anchors, \
+                      image_hw, cfg, pre_topk, sortn, w.cand_boxes, w.cand_logit, w.cand_valid, w.cand_count, nonfinite_flag, ##__VA_ARGS__))
+    if (!bands_on)
+        VK_RPN_SELECT(rpn_select_decode_kernel);
+    else if (f64)
+        VK_RPN_SELECT(rpn_select_decode_bands_kernel<double>, bt);
+    else
+        VK_RPN_SELECT(rpn_select_decode_bands_kernel<float>, bt);
+#undef VK_RPN_SELECT
     const int nb = ceil_div(K, 64);
     VK_TRY(launch_nms(w.cand_boxes, w.cand_valid, w.cand_count, N, pre_topk, nb, nms_thresh, post_topk, w.mask, w.keep_idx, w.keep_count,
                       w.keep_count + N, s));
@@ -925,25 +918,20 @@ int vk_rpn_proposals_multilevel_ignorey(const float *const *logits, const int32_
     cfg.offset = offset;
     cfg.stop = 0;
     const size_t sel_smem = (size_t)max_sortn * 8 + 2048;
-    if (!bands_on) {
-        VK_TRY(set_max_lds(rpn_select_decode_levels_kernel, RPN_MAX_PRE * 8 + 2048));
-        hipLaunchKernelGGL(rpn_select_decode_levels_kernel, dim3(N, levels), dim3(RPN_THREADS), sel_smem, s, sl, A, image_hw, cfg, pre_topk,
-                           nonfinite_flag);
-    } else if (f64) {
-        VK_TRY(set_max_lds(rpn_select_decode_levels_bands_kernel<double>, RPN_MAX_PRE * 8 + 2048));
-        hipLaunchKernelGGL(rpn_select_decode_levels_bands_kernel<double>, dim3(N, levels), dim3(RPN_THREADS), sel_smem, s, sl, A, image_hw, cfg,
-                           pre_topk, nonfinite_flag, bt);
-    } else {
-        VK_TRY(set_max_lds(rpn_select_decode_levels_bands_kernel<float>, RPN_MAX_PRE * 8 + 2048));
-        hipLaunchKernelGGL(rpn_select_decode_levels_bands_kernel<float>, dim3(N, levels), dim3(RPN_THREADS), sel_smem, s, sl, A, image_hw, cfg,
-                           pre_topk, nonfinite_flag, bt);
-    }
-    VK_CHECK_HIP(hipGetLastError());
+    const dim3 sel_grid(N, levels);
+    const size_t sel_cap = RPN_MAX_PRE * 8 + 2048;
+    if (!bands_on)
+        VK_TRY(launch_lds(rpn_select_decode_levels_kernel, sel_grid, dim3(RPN_THREADS), sel_smem, sel_cap, s, sl, A, image_hw, cfg, pre_topk,
+                          nonfinite_flag));
+    else if (f64)
+        VK_TRY(launch_lds(rpn_select_decode_levels_bands_kernel<double>, sel_grid, dim3(RPN_THREADS), sel_smem, sel_cap, s, sl, A, image_hw, cfg,
+                          pre_topk, nonfinite_flag, bt));
+    else
+        VK_TRY(launch_lds(rpn_select_decode_levels_bands_kernel<float>, sel_grid, dim3(RPN_THREADS), sel_smem, sel_cap, s, sl, A, image_hw, cfg,
+                          pre_topk, nonfinite_flag, bt));
     const int cap = levels * pre_topk, sortn = next_pow2(cap), nwords = ceil_div(cap, 64);
-    VK_TRY(set_max_lds(rpn_merge_levels_kernel, RPN_MAX_PRE * 8 + 256));
-    hipLaunchKernelGGL(rpn_merge_levels_kernel, dim3(N), dim3(RPN_THREADS), (size_t)sortn * 8 + 256, s, lc, cap, sortn, w.m_boxes, w.m_shift,
-                       w.m_logit, w.m_count);
-    VK_CHECK_HIP(hipGetLastError());
+    VK_TRY(launch_lds(rpn_merge_levels_kernel, dim3(N), dim3(RPN_THREADS), (size_t)sortn * 8 + 256, RPN_MAX_PRE * 8 + 256, s, lc, cap, sortn,
+                      w.m_boxes, w.m_shift, w.m_logit, w.m_count));
     VK_TRY(launch_nms(w.m_shift, nullptr, w.m_count, N, cap, nwords, nms_thresh, post_topk, w.mask, w.keep_idx, w.keep_count, w.keep_count + N, s));
     hipLaunchKernelGGL(rpn_gather_kernel, dim3(N), dim3(256), 0, s, w.m_boxes, w.m_logit, cap, w.keep_idx, w.keep_count, post_topk, out_boxes,
                        out_logits, out_counts);
@@ -975,10 +963,8 @@ int vk_nms(const float *boxes, const float *scores, int n, double thresh, int64_
     p += 256;
     RpnWs w = carve_rpn_ws(p, 1, n, n);
     const int sortn = next_pow2(n);
-    VK_TRY(set_max_lds(sort_scores_kernel, RPN_MAX_PRE * 8));
-    hipLaunchKernelGGL(sort_scores_kernel, dim3(1), dim3(RPN_THREADS), (size_t)sortn * 8, s, scores, n, sortn, boxes,
-                       sorted_boxes, order, cnt);
-    VK_CHECK_HIP(hipGetLastError());
+    VK_TRY(launch_lds(sort_scores_kernel, dim3(1), dim3(RPN_THREADS), (size_t)sortn * 8, RPN_MAX_PRE * 8, s, scores, n, sortn, boxes,
+                      sorted_boxes, order, cnt));
     const int nwords = ceil_div(n, 64);
     // (max_keep = n: one phase unless VK_NMS_LEAD forces a short phase A -- which is how the tests reach phase B)
     VK_TRY(launch_nms(sorted_boxes, nullptr, cnt, 1, n, nwords, thresh, n, w.mask, w.keep_idx, w.keep_count, w.keep_count + 1, s));

@@ -1,7 +1,8 @@
 // What every launcher of libvltk_hip.so links against and nothing of which knows what a model is: the per-launch event
-// timer (KernelTimer, Timed), the launcher state per device (device_state, set_max_lds) and the thread's error text.
-// The one translation unit that queries device properties, raises an LDS limit or keeps state between launches
-// (tests/test_launcher_state.py).
+// timer (KernelTimer, Timed), the launcher state per device (device_state, set_max_lds), the reader of the environment (env_*),
+// the stamped launch of the ablation build (Stamps) and the thread's error text.
+// The one translation unit that queries device properties, raises an LDS limit, keeps state between launches or calls
+// getenv (tests/test_launcher_state.py).
 #include <cstdlib>
 #include <mutex>
 #include <set>
@@ -24,7 +25,7 @@ hipEvent_t KernelTimer::get() {
     return e;
 }
 void KernelTimer::collect() {
-    const char *logp = getenv("VK_CONV_LOG");   // debug: one line per conv launch (shape, ms, TFLOP/s)
+    const char *logp = env_text("VK_CONV_LOG");   // debug: one line per conv launch (shape, ms, TFLOP/s)
     FILE *lf = logp ? fopen(logp, "a") : nullptr;
     std::vector<Rec> pending;       // launches of a forward that is still in flight (vk_forward_begin without its _end yet)
     for (auto &r : recs) {
@@ -110,6 +111,47 @@ int set_max_lds(const void *kernel, size_t bytes) {
     g_lds_set.insert({dev, kernel});
     return VK_OK;
 }
+
+const char *env_text(const char *name) { return getenv(name); }
+bool env_set(const char *name) { return getenv(name) != nullptr; }
+char env_first(const char *name) {
+    const char *v = getenv(name);
+    return v ? v[0] : '\0';
+}
+bool env_off(const char *name) { return env_first(name) == '0'; }
+int env_int(const char *name, int dflt) {
+    const char *v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
+
+#ifdef VK_ABLATION
+int Stamps::open(size_t n, hipStream_t stream) {
+    words = n;
+    VK_CHECK_HIP(hipMalloc((void **)&dev, words * sizeof(unsigned long)));
+    VK_CHECK_HIP(hipMemsetAsync(dev, 0, words * sizeof(unsigned long), stream));     // (a workgroup may leave without a stamp)
+    return VK_OK;
+}
+int Stamps::finish(hipStream_t stream, const char *path, const char *header, size_t rows, int stride, int cols, int per_wg) {
+    VK_CHECK_HIP(hipStreamSynchronize(stream));
+    std::vector<unsigned long> h(words);
+    VK_CHECK_HIP(hipMemcpy(h.data(), dev, words * sizeof(unsigned long), hipMemcpyDeviceToHost));
+    VK_CHECK_HIP(hipFree(dev));
+    dev = nullptr;
+    FILE *f = fopen(path, "a");
+    if (!f) return VK_OK;
+    fprintf(f, "%s\n", header);
+    for (size_t r = 0; r < rows && (r + 1) * stride <= words; ++r) {
+        if (per_wg)
+            fprintf(f, "%zu %zu", r / per_wg, r % per_wg);
+        else
+            fprintf(f, "%zu", r);
+        for (int i = 0; i < cols; ++i) fprintf(f, " %lu", h[r * stride + i]);
+        fprintf(f, "\n");
+    }
+    fclose(f);
+    return VK_OK;
+}
+#endif
 
 static thread_local char g_err[1024] = "";
 void set_error(const char *fmt, ...) {

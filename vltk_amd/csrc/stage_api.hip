@@ -280,7 +280,7 @@ int vk_linear(const void *x, long M, int K, const void *w_packed, const float *b
 
 // The fused-shortcut rule is restated in oracle/frcnn_oracle.py (fp16 emulation): keep the two in step.
 int vk_fuse_shortcut(int cin, int cin_shortcut, int cout, int stride, vk_dtype dt) {
-    static const bool off = getenv("VK_NO_FUSED_SHORTCUT") != nullptr;      // A/B switch
+    static const bool off = env_set("VK_NO_FUSED_SHORTCUT");
     return !off && dt == VK_F16 && stride == 1 && cout % 256 == 0 && cin % 32 == 0 && cin_shortcut % 32 == 0;
 }
 
@@ -294,7 +294,7 @@ int vk_bottleneck64(const void *x, int N, int H, int W, int cin, int proj, const
                     const float *b2, const void *w3, const float *b3, void *y, void *stream) {
     VK_REQUIRE(x && w1 && b1 && w2 && b2 && w3 && b3 && y && N > 0 && H > 0 && W > 0, VK_EINVAL, "bottleneck64: bad arguments");
     VK_REQUIRE((cin == 256 && !proj) || (cin == 64 && proj), VK_EINVAL, "bottleneck64: cin must be 256 (identity) or 64 (projection)");
-    VK_REQUIRE(bneck_fused_eligible(cin, 64, 256, 1, 1, proj != 0, N, H, W, VK_F16) || getenv("VK_BNECK_FUSED"), VK_EINVAL,
+    VK_REQUIRE(bneck_fused_eligible(cin, 64, 256, 1, 1, proj != 0, N, H, W, VK_F16) || bneck_fused_forced(), VK_EINVAL,
                "bottleneck64: tensor beyond the 32-bit byte offsets");
     VK_REQUIRE((long)N * H * W * 512 < (1L << 32) - (1L << 20), VK_EINVAL, "bottleneck64: tensor beyond the 32-bit byte offsets");
     return launch_bneck_fused(x, N, H, W, cin, proj != 0, w1, b1, w2, b2, w3, b3, y, false, (hipStream_t)stream);

@@ -154,8 +154,7 @@ __global__ __launch_bounds__(256, 3) void stem_pool_kernel(StemPoolK p) {
 }
 
 bool stem_pool_eligible(int cout, vk_dtype dt) {
-    const char *v = getenv("VK_STEM_FUSED");             // "0": conv and pool as two kernels (A/B switch and bit-identity tests)
-    if (v && v[0] == '0') return false;
+    if (env_off("VK_STEM_FUSED")) return false;          // "0": conv and pool as two kernels
     return dt == VK_F16 && cout == 64;
 }
 
@@ -164,7 +163,6 @@ int launch_stem_pool(const void *x, int N, int Hp, int Wp, int H1, int W1, const
                      hipStream_t stream) {
     DeviceState *ds = nullptr;
     VK_TRY(device_state(&ds));
-    VK_TRY(set_max_lds(stem_pool_kernel, SP_SMEM));
     StemPoolK k;
     k.x = (const char *)x;
     k.w = (const char *)w;
@@ -193,8 +191,7 @@ int launch_stem_pool(const void *x, int N, int Hp, int Wp, int H1, int W1, const
     const int grid = (int)std::min<long>(nt, (long)ds->n_cu * 3);
     Timed t;
     VK_TRY(t.begin(stream));
-    hipLaunchKernelGGL(stem_pool_kernel, dim3(grid), dim3(256), SP_SMEM, stream, k);
-    VK_CHECK_HIP(hipGetLastError());
+    VK_TRY(launch_lds(stem_pool_kernel, dim3(grid), dim3(256), SP_SMEM, SP_SMEM, stream, k));
     const long M = (long)N * H1 * W1;
     return t.end(stream, 3, 2.0 * (double)M * 64 * 147, (int)std::min<long>(M, 1L << 30), 64, 4, 7, 2,
                  (double)N * Hp * Wp * 8 + (double)N * k.H2 * k.W2 * 128 + 64.0 * 512);

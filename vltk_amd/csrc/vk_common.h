@@ -101,6 +101,7 @@ bool conv3x3_blk_eligible(const ConvArgs &a);             // conv3x3_blk.hip (na
 int launch_conv3x3_blk(const ConvArgs &a, hipStream_t stream);
 // bneck_fused.hip: a whole res2 BottleneckBlock (64 bottleneck channels, stride 1) as one kernel
 bool bneck_fused_eligible(int cin, int cmid, int cout, int stride, int groups, bool proj, long N, int H, int W, vk_dtype dt);
+bool bneck_fused_forced();      // VK_BNECK_FUSED set at all, even to "0": a direct launch goes ahead where the route is switched off (comparison tests)
 int launch_bneck_fused(const void *x, int N, int H, int W, int cin, bool proj, const void *w1, const float *b1, const void *w2,
                        const float *b2, const void *w3, const float *b3, void *y, bool concurrent, hipStream_t stream);
 bool conv_duo_dual_ok(const ConvArgs &a);
@@ -157,6 +158,34 @@ int device_state(DeviceState **out);  // the current HIP device's record
 int set_max_lds(const void *kernel, size_t bytes);
 template <typename... A>
 static inline int set_max_lds(void (*kernel)(A...), size_t bytes) { return set_max_lds(reinterpret_cast<const void *>(kernel), bytes); }
+// One launch of a kernel that needs more LDS than the default limit: the limit goes to lds_cap (>= smem; a build-wide maximum
+// where several launches of one instantiation differ in smem), then the launch and its error check.
+template <typename... P, typename... A>
+static inline int launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t smem, size_t lds_cap, hipStream_t s, A &&...args) {
+    VK_TRY(set_max_lds(kernel, lds_cap));
+    hipLaunchKernelGGL(kernel, grid, block, smem, s, static_cast<A &&>(args)...);
+    VK_CHECK_HIP(hipGetLastError());
+    return VK_OK;
+}
+
+// ---- the environment (runtime.hip: the one translation unit that calls getenv; the switches are listed in DESIGN.md) ----
+const char *env_text(const char *name);      // the text, nullptr when unset
+bool env_set(const char *name);              // set at all, even to ""
+char env_first(const char *name);            // first character; '\0' when unset or empty
+bool env_off(const char *name);              // env_first(name) == '0'
+int env_int(const char *name, int dflt);     // atoi of the text when set, else dflt
+
+#ifdef VK_ABLATION
+// One stamped launch (tools/*_stamps.py): open() before the launch of a stamp instantiation, finish() after it.
+struct Stamps {
+    unsigned long *dev = nullptr;
+    size_t words = 0;
+    int open(size_t words, hipStream_t stream);      // `words` 64-bit stamps, zeroed on the stream
+    // waits for the stream, frees the stamps and appends to `path`: the header line, then per row the first `cols` of its
+    // `stride` words, after the row index (per_wg == 0) or after row / per_wg and row % per_wg
+    int finish(hipStream_t stream, const char *path, const char *header, size_t rows, int stride, int cols, int per_wg);
+};
+#endif
 
 // ---- pack.hip (host only) ----
 void to_dt(const float *src, size_t n, vk_dtype dt, void *dst);       // float -> f16 / bf16 (nearest even) / f32
