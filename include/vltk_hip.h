@@ -541,6 +541,36 @@ int vk_vit_patchify(const float *pixel_values, int B, int C, int Hi, int Wi, int
 int vk_vit_assemble(const void *proj, int ldp, const void *cls_token, const void *position, int B, int N, void *x, int H,
                     vk_dtype dt, void *stream);
 
+/* ---- N5: LayoutLM (transformers modeling_layoutlm.py v5.15), the consumer of the reference's OCR word boxes ---- */
+
+/* LayoutLMEmbeddings.forward :66-119 as one launch: out [B * L, C], row (b, t) =
+ *   LayerNorm(word[ids] + position[t] + x[x0] + y[y0] + x[x1] + y[y1] + h[y1 - y0] + w[x1 - x0] + token_type[tt])
+ * with bbox [B, L, 4] int32 (x0, y0, x1, y1).  The sum is formed in fp32 in exactly that order, the statistics and the affine are
+ * fp32, the result is rounded to dt once.  word [vocab, C], position [max_position, C], x / y / h / w [max_2d, C] and token_type
+ * [type_vocab, C] in dt.  The kernel clamps every index into its table (the two extents at 0 as well); refusing bad ids and boxes
+ * is the caller's.  VK_EINVAL before any launch: a null pointer, B or L < 1, L > max_position, 2^31 rows or more, C outside
+ * 1..2048, an empty table, a dtype other than f32 / f16 / bf16. */
+int vk_layoutlm_embed(const int64_t *input_ids, const int64_t *token_type_ids, const int32_t *bbox, int B, int L, const void *word,
+                      int vocab, const void *position, int max_position, const void *x, const void *y, const void *h,
+                      const void *w, int max_2d, const void *token_type, int type_vocab, const float *gamma, const float *beta,
+                      void *out, int C, float eps, vk_dtype dt, void *stream);
+/* The token-classification tail (what vltk/utils/adapters.py map_ocr_predictions does per example on the host; PARITY UNPINNED
+ * for the rule).  logits [B * L, ld] in dt, of which the first C columns count; word_ids [B, L]: the word a token belongs to, -1
+ * for a special or padding token (an id >= W is ignored too).  token_labels [B, L]: the arg-max over C, scanning upward with
+ * v > best from -inf at index 0 (ties give the lowest index, a NaN never wins, a row of NaN / -inf gives 0).  word_labels [B, W]:
+ * the most frequent token label among the tokens of that word, which need not be contiguous; ties give the smallest label
+ * (torch.mode's rule on the CPU); a word with no token gets -1.  1 <= C <= 64, 1 <= L <= 4096, 1 <= W <= L, ld >= C. */
+int vk_token_word_labels(const void *logits, int ld, const int32_t *word_ids, int B, int L, int C, int W, int32_t *token_labels,
+                         int32_t *word_labels, vk_dtype dt, void *stream);
+/* The extractive-QA tail (PARITY UNPINNED for the rule: the reference has no span decode).  Element (b, t) of the start logits is
+ * start_logits[(b * L + t) * start_stride] (dt), likewise the end logits, so the two columns of a [B * L, ld] GEMM output are read
+ * in place.  context_mask [B, L]: non-zero where an answer token may lie.  Candidates are the pairs s <= e with both tokens in the
+ * context and e - s + 1 <= max_answer_tokens; a pair scores float(start[s]) + float(end[e]); the best wins under score > best
+ * from -inf, ties go to the smaller s, then the smaller e.  start / end [B] int32 and score [B] f32; (-1, -1, -inf) when nothing
+ * wins.  1 <= L <= 4096, max_answer_tokens >= 1, strides >= 1. */
+int vk_span_select(const void *start_logits, int start_stride, const void *end_logits, int end_stride, const int32_t *context_mask,
+                   int B, int L, int max_answer_tokens, int32_t *start, int32_t *end, float *score, vk_dtype dt, void *stream);
+
 /* ---- N4: FPN-side ops (what north_star names; the reference holds only fragments, see oracle/fpn_oracle.py) ---- */
 
 /* RoIAlign over a feature pyramid (torchvision roi_align semantics, `aligned` as detectron2's ROIAlignV2; the level loop of

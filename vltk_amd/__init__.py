@@ -26,4 +26,8 @@ def __getattr__(name):
     if name in ("ViTModel", "ViTForImageClassification", "vit_config", "patch_tokens", "vit_patch_boxes"):   # the patch-token image encoder
         from . import vit
         return getattr(vit, name)
+    if name in ("LayoutLMModel", "LayoutLMForTokenClassification", "LayoutLMForQuestionAnswering", "LayoutLMForSequenceClassification",
+                "layoutlm_config", "ocr_token_boxes"):       # the document encoder: OCR words and their boxes
+        from . import layoutlm
+        return getattr(layoutlm, name)
     raise AttributeError(name)

@@ -141,6 +141,9 @@ SIGNATURES = {
     "vk_visualbert_embed": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _F, _I, _P]),
     "vk_vit_patchify": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
     "vk_vit_assemble": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _P]),
+    "vk_layoutlm_embed": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _F, _I, _P]),
+    "vk_token_word_labels": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "vk_span_select": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P]),
     "vk_roi_align": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "vk_assign_levels": (_I, [_P, _I, _I, _I, _I, _F, _I, _P, _P]),
     "vk_upsample2x_add": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

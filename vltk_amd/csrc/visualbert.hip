@@ -28,39 +28,6 @@ struct VbeArgs {
     float eps;
 };
 
-__device__ __forceinline__ float vbe_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-template <typename T, int VW>
-__device__ __forceinline__ void vbe_load(const T *p, float (&out)[VW]) {
-    if constexpr (VW == 1) {
-        out[0] = (float)*p;
-    } else {
-        typedef T vecT __attribute__((ext_vector_type(VW)));
-        const vecT t = *reinterpret_cast<const vecT *>(p);
-#pragma unroll
-        for (int e = 0; e < VW; ++e) out[e] = (float)t[e];
-    }
-}
-
-template <typename T, int VW>
-__device__ __forceinline__ void vbe_store(T *p, const float (&v)[VW]) {
-    if constexpr (VW == 1) {
-        *p = (T)v[0];
-    } else {
-        typedef T vecT __attribute__((ext_vector_type(VW)));
-        vecT o;
-#pragma unroll
-        for (int e = 0; e < VW; ++e) o[e] = (T)v[e];
-        *reinterpret_cast<vecT *>(p) = o;
-    }
-}
-
-__device__ __forceinline__ long vbe_clamp(long i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-
 // VW: elements per chunk (16 / sizeof(T) on the vector path, 1 on the scalar one); C % VW == 0.
 template <typename T, int VW>
 __global__ __launch_bounds__(256) void visualbert_embed_kernel(const VbeArgs a) {
@@ -82,13 +49,13 @@ __global__ __launch_bounds__(256) void visualbert_embed_kernel(const VbeArgs a) 
     int count = 0;
     if (text) {
         const long i = (long)b * a.Lt + r;
-        s0 = (const T *)a.word + vbe_clamp(a.ids[i], a.vocab) * C;
-        s1 = (const T *)a.token_type + vbe_clamp(a.tts[i], a.type_vocab) * C;
+        s0 = (const T *)a.word + clamp_row(a.ids[i], a.vocab) * C;
+        s1 = (const T *)a.token_type + clamp_row(a.tts[i], a.type_vocab) * C;
         s2 = pos + (long)r * C;                          // Lt <= max_position (checked by the entry point)
     } else {
         const long j = (long)b * a.V + (r - a.Lt);
         s0 = (const T *)a.proj + j * a.ldp;
-        s1 = (const T *)a.visual_token_type + vbe_clamp(a.vtts[j], a.type_vocab) * C;
+        s1 = (const T *)a.visual_token_type + clamp_row(a.vtts[j], a.type_vocab) * C;
         s2 = (const T *)a.visual_position;               // visual position id 0
         if (a.align) {
 #pragma unroll
@@ -110,9 +77,9 @@ __global__ __launch_bounds__(256) void visualbert_embed_kernel(const VbeArgs a) 
         const int ch = lane + 64 * i;
         if (ch < chunks) {
             float t0[VW], t1[VW], t2[VW];
-            vbe_load<T, VW>(s0 + ch * VW, t0);
-            vbe_load<T, VW>(s1 + ch * VW, t1);
-            vbe_load<T, VW>(s2 + ch * VW, t2);
+            ld_chunk<T, VW>(s0 + ch * VW, t0);
+            ld_chunk<T, VW>(s1 + ch * VW, t1);
+            ld_chunk<T, VW>(s2 + ch * VW, t2);
 #pragma unroll
             for (int e = 0; e < VW; ++e) v[i][e] = t0[e] + t1[e] + t2[e];
             if (!text && count > 0) {
@@ -123,7 +90,7 @@ __global__ __launch_bounds__(256) void visualbert_embed_kernel(const VbeArgs a) 
                 for (int k = 0; k < VBE_MAX_ALIGN; ++k)
                     if (k < a.A && al[k] >= 0) {
                         float p[VW];
-                        vbe_load<T, VW>(pos + (long)al[k] * C + ch * VW, p);
+                        ld_chunk<T, VW>(pos + (long)al[k] * C + ch * VW, p);
 #pragma unroll
                         for (int e = 0; e < VW; ++e) m[e] += p[e];
                     }
@@ -134,7 +101,7 @@ __global__ __launch_bounds__(256) void visualbert_embed_kernel(const VbeArgs a) 
             for (int e = 0; e < VW; ++e) s += v[i][e];
         }
     }
-    const float mean = vbe_wave_sum(s) / (float)C;
+    const float mean = wave_sum(s) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXC; ++i)
@@ -145,7 +112,7 @@ __global__ __launch_bounds__(256) void visualbert_embed_kernel(const VbeArgs a) 
                 q += d * d;
             }
         }
-    const float rstd = 1.0f / sqrtf(vbe_wave_sum(q) / (float)C + a.eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + a.eps);
     T *yr = (T *)a.y + row * C;
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) {
@@ -154,7 +121,7 @@ __global__ __launch_bounds__(256) void visualbert_embed_kernel(const VbeArgs a) 
             float o[VW];
 #pragma unroll
             for (int e = 0; e < VW; ++e) o[e] = (v[i][e] - mean) * rstd * a.gamma[ch * VW + e] + a.beta[ch * VW + e];
-            vbe_store<T, VW>(yr + ch * VW, o);
+            st_chunk<T, VW>(yr + ch * VW, o);
         }
     }
 }

@@ -268,6 +268,34 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// VW consecutive elements as fp32, and back with one rounding each: one 16-byte access where VW = 16 / sizeof(T) (p then 16-byte
+// aligned), one element where VW = 1.  A table index clamped into a table of n rows.  Shared by the embedding kernels of
+// visualbert.hip and layoutlm.hip.
+template <typename T, int VW>
+__device__ __forceinline__ void ld_chunk(const T *p, float (&out)[VW]) {
+    if constexpr (VW == 1) {
+        out[0] = (float)*p;
+    } else {
+        typedef T vecT __attribute__((ext_vector_type(VW)));
+        const vecT t = *reinterpret_cast<const vecT *>(p);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) out[e] = (float)t[e];
+    }
+}
+template <typename T, int VW>
+__device__ __forceinline__ void st_chunk(T *p, const float (&v)[VW]) {
+    if constexpr (VW == 1) {
+        *p = (T)v[0];
+    } else {
+        typedef T vecT __attribute__((ext_vector_type(VW)));
+        vecT o;
+#pragma unroll
+        for (int e = 0; e < VW; ++e) o[e] = (T)v[e];
+        *reinterpret_cast<vecT *>(p) = o;
+    }
+}
+__device__ __forceinline__ long clamp_row(long i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
 // Sort key of a score for an ascending sort that ranks scores descending (-0 ranks as +0); the low word of the 64-bit key
 // holds the row index, so ties go to the lower index.  Shared by roi_out.hip and per_class.hip.
 __device__ __forceinline__ uint32_t desc_key32(float v) {
