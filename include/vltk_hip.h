@@ -571,6 +571,34 @@ int vk_token_word_labels(const void *logits, int ld, const int32_t *word_ids, in
 int vk_span_select(const void *start_logits, int start_stride, const void *end_logits, int end_stride, const int32_t *context_mask,
                    int B, int L, int max_answer_tokens, int32_t *start, int32_t *end, float *score, vk_dtype dt, void *stream);
 
+/* ---- N6: the losses of LXMERT's pre-training heads (transformers LxmertForPreTraining.forward :1059-1095; csrc/losses.hip) ----
+ * fp32 arithmetic on values read from dt (f32, f16 or bf16); no atomics, so the same input gives the same bits on every run. */
+/* row_loss[m] = logsumexp(logits[m, :C]) - logits[m, labels[m]], the row maximum subtracted before the exponential; 0 where
+ * labels[m] == ignore_index (the row is then not read).  `CrossEntropyLoss(reduction="none")`.  A label that is neither
+ * ignore_index nor in [0, C) gives NaN and reads nothing: keeping labels in range is the caller's responsibility.
+ * ignore_index < 0, ld >= C.  The kernel follows vk_cross_entropy_form. */
+int vk_cross_entropy(const void *logits, int ld, int M, int C, const int64_t *labels, int ignore_index, float *row_loss,
+                     vk_dtype dt, void *stream);
+/* Which kernel a cross-entropy launch runs on (host only).  aligned16: `logits` is 16-byte aligned.  VEC where the rows are
+ * 16-byte addressable (aligned16 and ld a multiple of 16 / sizeof(dt) elements) and C >= 128; SCALAR elsewhere.  Returns a
+ * VK_CE_FORM_* or -VK_EINVAL where the launch would refuse the call. */
+#define VK_CE_FORM_VEC 0        /* ce_vec_kernel: a 256-thread workgroup per row, 16-byte chunks, online max and sum */
+#define VK_CE_FORM_SCALAR 1     /* ce_scalar_kernel: a wave per row, one element per lane and step */
+int vk_cross_entropy_form(int C, int ld, vk_dtype dt, int aligned16);
+/* row_loss[m] = mean over C of SmoothL1(pred[m, c] - target[m, c]) with beta = 1: `SmoothL1Loss(reduction="none")(..).mean(1)`.
+ * pred [M, ld] in dt, target [M, ldt] f32. */
+int vk_smooth_l1_rows(const void *pred, int ld, const float *target, int ldt, int M, int C, float *row_loss, vk_dtype dt,
+                      void *stream);
+/* One number from M row losses: an fp64 sum in a fixed order, rounded to f32 once after the division.
+ * labels given (weight null): out = sum of row_loss over the rows with labels[m] != ignore_index / their count: `CrossEntropyLoss()`'s
+ * mean, NaN when no row counts (scale unused).  labels null: out = scale * sum_m row_loss[m] * weight[m] / M (weight null: all
+ * ones): `(loss * mask_conf).mean() * visual_loss_normalizer`. */
+int vk_loss_reduce(const float *row_loss, const float *weight, const int64_t *labels, int ignore_index, int M, float scale,
+                   float *out, void *stream);
+/* out = the fp32 sum of the present terms in transformers' order.  terms [6]: masked-LM, matched, obj, attr, feat, answer; bit i
+ * of `present` says that term i takes part: total = 0 + mlm + matched + (0 + obj + attr + feat) + answer. */
+int vk_loss_total(const float *terms, int present, float *out, void *stream);
+
 /* ---- N4: FPN-side ops (what north_star names; the reference holds only fragments, see oracle/fpn_oracle.py) ---- */
 
 /* RoIAlign over a feature pyramid (torchvision roi_align semantics, `aligned` as detectron2's ROIAlignV2; the level loop of

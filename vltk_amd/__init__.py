@@ -20,6 +20,10 @@ def __getattr__(name):
     if name == "LxmertEncoder":          # N3: the encoder that consumes the extractor's output
         from .lxmert import LxmertEncoder
         return LxmertEncoder
+    if name in ("LxmertForPreTraining", "lxmert_pretraining_config", "lxmert_pretraining_param_spec",
+                "make_lxmert_pretraining_state_dict"):     # N6: the pre-training heads and their losses
+        from . import lxmert_pretrain
+        return getattr(lxmert_pretrain, name)
     if name in ("VisualBertModel", "VisualBertForQuestionAnswering"):   # the single-stream encoder and its VQA head
         from . import visualbert
         return getattr(visualbert, name)

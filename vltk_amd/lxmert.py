@@ -6,6 +6,9 @@ the host-side mirror of `transformers.LxmertModel` (modeling_lxmert.py v5.15: `L
 `LxmertEncoder.forward` :498-557) with the state-dict key layout of that class, so a real checkpoint's tensors load by
 name.  All arithmetic runs in `libvltk_hip.so` (MFMA GEMM with bias / residual / GELU / tanh epilogues, LayerNorm,
 attention, embedding kernels); torch only owns the device buffers.  No CPU fallback.
+
+`LxmertForQuestionAnswering` is here too; the pre-training heads and their losses (`LxmertForPreTraining`) are in
+lxmert_pretrain.py, which shares the answer head and the cross-entropy helpers below with it.
 """
 import zlib
 
@@ -188,10 +191,56 @@ class LxmertEncoder(BertOps):
         return lang.view(B, Lq, H), visn.view(B, V, H), self._pooler(lang, B, Lq)
 
 
+IGNORE_INDEX = -100                      # `CrossEntropyLoss`'s default, what the reference's `config.ignore_id` carries
+
+
+def check_class_labels(name, t, shape, num_classes):
+    """One tensor of class labels, host-side, before any launch: integer, of `shape`, every entry IGNORE_INDEX or in
+    [0, num_classes).  -> int64 numpy array.  A wrong shape or type raises ValueError, a label outside IndexError (torch's
+    cross-entropy would fault on the device there)."""
+    a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    if tuple(a.shape) != tuple(shape) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{name} must be an integer {tuple(shape)} array, got {a.dtype} {tuple(a.shape)}")
+    bad = (a != IGNORE_INDEX) & ((a < 0) | (a >= num_classes))
+    if bad.any():
+        raise IndexError(f"{name} must be {IGNORE_INDEX} or lie in [0, {num_classes}): found {int(a[bad].flat[0])}")
+    return np.ascontiguousarray(a, np.int64)
+
+
+def load_answer_head(enc, sd):
+    """`LxmertVisualAnswerHead` :602-614 into the encoder's packed weights."""
+    enc._load_lin(sd, "answer.fc0", "answer_head.logit_fc.0")
+    enc._load_lin(sd, "answer.fc3", "answer_head.logit_fc.3")
+    enc._load_ln(sd, "answer_head.logit_fc.2")
+
+
+def answer_head(enc, pooled):
+    h = enc._linear(pooled, "answer.fc0", act=L.VK_ACT_GELU)
+    h = enc._layernorm(h, "answer_head.logit_fc.2")
+    return enc._linear(h, "answer.fc3")
+
+
+def cross_entropy_rows(enc, logits, labels):
+    """`CrossEntropyLoss(reduction="none")` of logits [M, C] (storage type, unit column stride, any row stride) under int64
+    device labels [M] -> fp32 [M]."""
+    M, Cn = logits.shape
+    assert logits.stride(1) == 1 and labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == M
+    rows = torch.empty((M,), dtype=torch.float32, device=enc.device)
+    L.call("vk_cross_entropy", logits.data_ptr(), logits.stride(0), M, Cn, labels.data_ptr(), IGNORE_INDEX, rows.data_ptr(), enc.dt,
+           stream(enc.device))
+    return rows
+
+
+def cross_entropy_mean(enc, logits, labels, out):
+    """`CrossEntropyLoss()` into the fp32 device scalar `out`: the mean over the rows whose label is not IGNORE_INDEX."""
+    rows = cross_entropy_rows(enc, logits, labels)
+    L.call("vk_loss_reduce", rows.data_ptr(), None, labels.data_ptr(), IGNORE_INDEX, rows.numel(), 1.0, out.data_ptr(), stream(enc.device))
+
+
 class LxmertForQuestionAnswering:
     """`transformers.LxmertForQuestionAnswering` (modeling_lxmert.py :1123-1290, the VQA/GQA model of BASELINE config 5) on the
     HIP path: encoder + `LxmertVisualAnswerHead` :602-614 (Linear -> GELU -> LayerNorm -> Linear on the pooled output).
-    `model(...)` returns `question_answering_score [B, num_qa_labels]` (storage dtype)."""
+    `model(...)` returns `question_answering_score [B, num_qa_labels]` (storage dtype); with `labels=` it returns (loss, score)."""
 
     def __init__(self, config, num_qa_labels, precision="bf16", device="cuda:0"):
         self.lxmert = LxmertEncoder(config, precision, device)
@@ -205,22 +254,27 @@ class LxmertForQuestionAnswering:
                                f"unexpected {sorted(set(sd) - set(want))[:4]}")
         enc = self.lxmert
         enc.load_state_dict({k[len("lxmert."):]: v for k, v in sd.items() if k.startswith("lxmert.")}, strict)
-        enc._lin["answer.fc0"] = enc._pack(sd["answer_head.logit_fc.0.weight"], sd["answer_head.logit_fc.0.bias"])
-        enc._lin["answer.fc3"] = enc._pack(sd["answer_head.logit_fc.3.weight"], sd["answer_head.logit_fc.3.bias"])
-        enc._ln["answer.ln"] = (torch.from_numpy(sd["answer_head.logit_fc.2.weight"]).to(enc.device),
-                                torch.from_numpy(sd["answer_head.logit_fc.2.bias"]).to(enc.device))
+        load_answer_head(enc, sd)
         return self
 
     def eval(self):
         return self
 
     @torch.no_grad()
-    def __call__(self, input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None):
+    def __call__(self, input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None,
+                 labels=None):
+        """`labels [B]` (an answer id each, -100 to leave an example out) -> (loss, score): `CrossEntropyLoss()` of the scores
+        (:1270-1272), fp32, from `vk_cross_entropy` + `vk_loss_reduce`.  Without labels: the score alone."""
         enc = self.lxmert
         check_text_inputs(input_ids, token_type_ids, enc.cfg)
+        if labels is not None:
+            labels = check_class_labels("labels", labels, (input_ids.shape[0],), self.num_qa_labels)
         _, _, pooled = enc._forward(input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids)
-        h = enc._linear(pooled, "answer.fc0", act=L.VK_ACT_GELU)
-        h = enc._layernorm(h, "answer.ln")
-        score = enc._linear(h, "answer.fc3")
+        score = answer_head(enc, pooled)
+        if labels is None:
+            torch.cuda.synchronize(enc.device)
+            return score
+        loss = torch.empty((), dtype=torch.float32, device=enc.device)
+        cross_entropy_mean(enc, score, torch.from_numpy(labels).to(enc.device), loss)
         torch.cuda.synchronize(enc.device)
-        return score
+        return loss, score
