@@ -1,7 +1,10 @@
-"""-m gpu: vk_layernorm and vk_embed_layernorm (csrc/layernorm.hip) per element against float64 and bit-exact (DESIGN.md section
-20a).  The row strides are walked as the encoders pass them: ld == C, the padded strides vk_linear leaves behind (the 16-byte
-vector kernel where C allows it) and odd strides (the one-element-per-lane kernel at every C); the columns of y past C must stay
-untouched and the columns of x past C unread."""
+"""-m gpu: vk_layernorm and vk_embed_layernorm (csrc/layernorm.hip, the row body of csrc/row_norm.h) per element against float64
+and bit-exact.  The row strides are walked as the encoders pass them: ld == C, the padded strides vk_linear
+leaves behind (layernorm_kernel<T, 16 / sizeof(T)>, the 16-byte-chunk form, where C and the bases allow it) and odd strides
+(layernorm_kernel<T, 1>, one element per lane and step, at every C); the columns of y past C must stay untouched and the columns
+of x past C unread.  The entries that share the row body (vk_layoutlm_embed among them) are bit-equal on equal rows."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -31,21 +34,24 @@ def bits(t):
     return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
 
 
-def layernorm(x, gm, bt, dt, ldx, ldy, scale, y_old=None):
+def layernorm(x, gm, bt, dt, ldx, ldy, scale, y_old=None, offset=0):
     """x [M, C] (storage type, CPU) -> y [M, C] (CPU).  x lies in a [M, ldx] buffer whose other columns hold 1e4 (a kernel that
     reads them lands far off); y in a [M, ldy] buffer prefilled with the sentinel (y_old in the first C columns when accumulating),
-    whose columns past C are asserted untouched."""
+    whose columns past C are asserted untouched.  Both buffers start `offset` elements into their allocations (1e4 / the sentinel
+    in front), and the elements in front of y must keep their bytes too."""
     M, C = x.shape
     td = TDT[dt]
-    xb = torch.full((M, ldx), 1e4, dtype=td)
-    xb[:, :C] = x
-    yb = torch.full((M, ldy), SENTINEL, dtype=td)
+    xf = torch.full((offset + M * ldx,), 1e4, dtype=td)
+    xf[offset:].view(M, ldx)[:, :C] = x
+    yf = torch.full((offset + M * ldy,), SENTINEL, dtype=td)
     if y_old is not None:
-        yb[:, :C] = y_old
-    xd, yd, gd, bd = xb.to(G.DEV), yb.to(G.DEV), gm.to(G.DEV), bt.to(G.DEV)
-    L.call("vk_layernorm", G.P(xd), ldx, G.P(gd), G.P(bd), G.P(yd), ldy, M, C, EPS, scale, int(y_old is not None), dt, G.stream())
+        yf[offset:].view(M, ldy)[:, :C] = y_old
+    xd, yd, gd, bd = xf.to(G.DEV), yf.to(G.DEV), gm.to(G.DEV), bt.to(G.DEV)
+    L.call("vk_layernorm", G.P(xd[offset:]), ldx, G.P(gd), G.P(bd), G.P(yd[offset:]), ldy, M, C, EPS, scale, int(y_old is not None), dt,
+           G.stream())
     torch.cuda.synchronize()
-    y = yd.cpu()
+    assert torch.equal(bits(yd[:offset]), bits(yf[:offset])), "elements in front of y were written"
+    y, yb = yd.cpu()[offset:].view(M, ldy), yf[offset:].view(M, ldy)
     assert torch.equal(bits(y[:, C:]), bits(yb[:, C:])), "columns of y past C were written"
     return y[:, :C]
 
@@ -72,6 +78,25 @@ def test_layernorm_per_element(dt, C, ld):
                     r = T.layernorm_reference(x, gm, bt, EPS, scale, acc)
                     T.assert_within(y, r["ref"], T.layernorm_bound(r, td),
                                     f"layernorm {IDS[dt]} {ld} M {M} C {C} {kind} scale {scale} acc {int(acc is not None)}")
+
+
+@pytest.mark.parametrize("dt", ALL, ids=[IDS[d] for d in ALL])
+def test_layernorm_misaligned_bases(dt):
+    """Strides that are multiples of the 16-byte chunk under bases that are not 16-byte aligned (x and y start one element into
+    their allocations): the one-element form has to take the launch."""
+    td = TDT[dt]
+    M, C = 5, 128
+    ldx, ldy = strides(C, "padded")
+    gen = np.random.Generator(np.random.PCG64([C, 77]))
+    gm = torch.from_numpy(gen.uniform(0.5, 1.5, C).astype(np.float32))
+    bt = torch.from_numpy(gen.standard_normal(C).astype(np.float32))
+    y_old = torch.from_numpy(gen.standard_normal((M, C)).astype(np.float32)).to(td)
+    x = torch.from_numpy((gen.standard_normal((M, C)) * 3 + 1).astype(np.float32)).to(td)
+    for scale in (1.0, 0.5):
+        for acc in (None, y_old):
+            y = layernorm(x, gm, bt, dt, ldx, ldy, scale, acc, offset=1)
+            r = T.layernorm_reference(x, gm, bt, EPS, scale, acc)
+            T.assert_within(y, r["ref"], T.layernorm_bound(r, td), f"layernorm {IDS[dt]} misaligned scale {scale} acc {int(acc is not None)}")
 
 
 # ---- 2. exact --------------------------------------------------------------------------------------------------------------
@@ -143,6 +168,54 @@ def test_embed_layernorm_per_element(dt, C, Lt):
     T.assert_within(y, r["ref"], T.layernorm_bound(r, td), f"embed layernorm {IDS[dt]} C {C} L {Lt}")
 
 
+@functools.lru_cache(maxsize=None)
+def shared_rows(dt, C):
+    """One set of word / position / token-type tables, ids and gamma / beta through vk_embed_layernorm and through
+    vk_layoutlm_embed with all-zero x, y, h and w tables (B = 3, L = 9).  Adding a +0 row is exact and leaves
+    (word + position) + token_type, vk_embed_layernorm's order, unless a sum is -0: the host asserts that none is.  Returns both
+    outputs and that sum in fp32 (CPU)."""
+    td = TDT[dt]
+    B, Lt, V, P, M2 = 3, 9, 50, 16, 8
+    gen = np.random.Generator(np.random.PCG64([C, 9]))
+    word, pos, typ = (torch.from_numpy(gen.standard_normal(s).astype(np.float32)).to(td) for s in ((V, C), (P, C), (2, C)))
+    ids = torch.from_numpy(gen.integers(0, V, (B, Lt)))
+    tts = torch.from_numpy(gen.integers(0, 2, (B, Lt)))
+    box = torch.from_numpy(np.sort(gen.integers(0, M2, (B, Lt, 2, 2)), -2).reshape(B, Lt, 4).astype(np.int32))   # x0 y0 x1 y1
+    gm = torch.from_numpy(gen.uniform(0.5, 1.5, C).astype(np.float32))
+    bt = torch.from_numpy(gen.standard_normal(C).astype(np.float32))
+    part = word.float()[ids] + pos.float()[:Lt][None]
+    total = (part + typ.float()[tts]).view(B * Lt, C)
+    for t in (part, total):
+        assert not ((t == 0) & torch.signbit(t)).any(), "a -0 sum: adding the +0 rows would change it"
+    zero = torch.zeros((M2, C), dtype=td, device=G.DEV)
+    d = [t.to(G.DEV) for t in (ids, tts, word, pos, typ, gm, bt, box)]
+    ye, yl = (torch.full((B * Lt, C), SENTINEL, dtype=td, device=G.DEV) for _ in range(2))
+    L.call("vk_embed_layernorm", G.P(d[0]), G.P(d[1]), B, Lt, G.P(d[2]), G.P(d[3]), G.P(d[4]), G.P(d[5]), G.P(d[6]), G.P(ye), C, EPS, dt,
+           G.stream())
+    L.call("vk_layoutlm_embed", G.P(d[0]), G.P(d[1]), G.P(d[7]), B, Lt, G.P(d[2]), V, G.P(d[3]), P, G.P(zero), G.P(zero), G.P(zero),
+           G.P(zero), M2, G.P(d[4]), 2, G.P(d[5]), G.P(d[6]), G.P(yl), C, EPS, dt, G.stream())
+    torch.cuda.synchronize()
+    return dict(embed=ye.cpu(), layoutlm=yl.cpu(), total=total, gm=gm, bt=bt)
+
+
+@pytest.mark.parametrize("dt", ALL, ids=[IDS[d] for d in ALL])
+@pytest.mark.parametrize("C", [63, 65, 2047])
+def test_layoutlm_embed_bit_equals_embed_layernorm(dt, C):
+    """Odd C: both entries take the one-element form, and the shared row body makes equal rows equal bits."""
+    r = shared_rows(dt, C)
+    assert torch.equal(bits(r["layoutlm"]), bits(r["embed"]))
+
+
+@pytest.mark.parametrize("C", [63, 65, 128])
+def test_embed_entries_bit_equal_layernorm_of_the_host_sum(C):
+    """fp32: vk_layernorm (tight strides, scale 1, no accumulate) on (word[ids] + position) + token_type summed on the host gives
+    the bits of vk_embed_layernorm at odd C (both on the one-element form) and of vk_layoutlm_embed at C = 128 (both on the
+    16-byte-chunk form; vk_embed_layernorm stays on the one-element form there)."""
+    r = shared_rows(L.VK_F32, C)
+    y = layernorm(r["total"], r["gm"], r["bt"], L.VK_F32, C, C, 1.0)
+    assert torch.equal(bits(y), bits(r["embed" if C % 4 else "layoutlm"]))
+
+
 # ---- 4. refusals -----------------------------------------------------------------------------------------------------------
 def test_entries_refuse_bad_sizes():
     """C beyond 2048 and an empty batch are refused by the host check, before any launch: y keeps its bytes."""
@@ -157,6 +230,7 @@ def test_entries_refuse_bad_sizes():
         assert lib.vk_layernorm(*args) == L.VK_EINVAL
         with pytest.raises(ValueError):
             L.call("vk_layernorm", *args)
+    assert lib.vk_layernorm(G.P(x), 2056, G.P(gm), G.P(bt), G.P(y), 2056, 4, 2048, EPS, 1.0, 0, L.VK_I32, G.stream()) == L.VK_EINVAL
     ids = torch.zeros((4,), dtype=torch.int64, device=G.DEV)
     for B, Lt, C in ((4, 1, 2049), (0, 1, 128), (4, 0, 128)):
         with pytest.raises(ValueError):

@@ -95,9 +95,10 @@ def embed_case(dt, Cc):
     return dict(B=B, Lt=Lt, vocab=vocab, P=P, M2=M2, Cc=Cc, td=td, dt=dt), dev, ref
 
 
-def run_embed(geo, d):
+def run_embed(geo, d, y=None):
     rows = geo["B"] * geo["Lt"]
-    y = torch.full((rows + 1, geo["Cc"]), 77.0, dtype=geo["td"], device=G.DEV)       # one guard row behind the output
+    if y is None:
+        y = torch.full((rows + 1, geo["Cc"]), 77.0, dtype=geo["td"], device=G.DEV)   # one guard row behind the output
     L.call("vk_layoutlm_embed", G.P(d["ids"]), G.P(d["tts"]), G.P(d["box"]), geo["B"], geo["Lt"], G.P(d["word"]), geo["vocab"],
            G.P(d["pos"]), geo["P"], G.P(d["xt"]), G.P(d["yt"]), G.P(d["ht"]), G.P(d["wt"]), geo["M2"], G.P(d["typ"]), 2, G.P(d["gm"]),
            G.P(d["bt"]), G.P(y), geo["Cc"], 1e-12, geo["dt"], G.stream())
@@ -124,6 +125,15 @@ def test_embed_reference_tells_the_tables_apart():
     for perm in ((1, 0, 2, 3), (2, 1, 0, 3)):
         swapped = dict(dev, box=dev["box"][..., list(perm)].contiguous())
         assert rel(run_embed(geo, swapped), ref) > 0.1
+
+
+def test_embed_entry_refuses_a_bad_dtype():
+    geo, dev, _ = embed_case(L.VK_F32, 128)
+    y = torch.full((geo["B"] * geo["Lt"] + 1, geo["Cc"]), 77.0, device=G.DEV)
+    with pytest.raises(ValueError):
+        run_embed(dict(geo, dt=L.VK_I32), dev, y)
+    torch.cuda.synchronize()
+    assert (y == 77.0).all(), "a refused dtype wrote the output"
 
 
 # ---- 2. vk_token_word_labels, bit-equal to the restatement ---------------------------------------------------------------------------

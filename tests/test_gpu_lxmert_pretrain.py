@@ -173,6 +173,14 @@ def test_smooth_l1_rows_within_bound(dt, C):
     assert w <= 1.0 and got[5] == 0
 
 
+def test_smooth_l1_rows_refuses_a_bad_dtype():
+    pred, target = torch.zeros((2, 8), device=G.DEV), torch.zeros((2, 8), device=G.DEV)
+    rows = torch.full((2,), 77.0, device=G.DEV)
+    assert L.load().vk_smooth_l1_rows(G.P(pred), 8, G.P(target), 8, 2, 8, G.P(rows), L.VK_I32, G.stream()) == L.VK_EINVAL
+    torch.cuda.synchronize()
+    assert (rows == 77.0).all(), "a refused dtype wrote the output"
+
+
 # ---- 3. vk_loss_reduce and vk_loss_total -------------------------------------------------------------------------------------------
 def reduce_call(rows, weight=None, labels=None, scale=1.0):
     out = torch.full((2,), 77.0, dtype=torch.float32, device=G.DEV)

@@ -96,9 +96,10 @@ def embed_case(dt, Cc, aligned, split_ranges=False):
     return dict(B=B, Lt=Lt, V=V, A=A if aligned else 0, vocab=vocab, P=P, ldp=ldp, Cc=Cc, td=td, dt=dt), dev, ref
 
 
-def run_embed(geo, d):
+def run_embed(geo, d, y=None):
     rows = geo["B"] * (geo["Lt"] + geo["V"])
-    y = torch.full((rows + 1, geo["Cc"]), 77.0, dtype=geo["td"], device=G.DEV)       # one guard row behind the output
+    if y is None:
+        y = torch.full((rows + 1, geo["Cc"]), 77.0, dtype=geo["td"], device=G.DEV)   # one guard row behind the output
     L.call("vk_visualbert_embed", G.P(d["ids"]), G.P(d["tts"]), G.P(d["vtts"]), G.P(d["align"]), geo["A"], geo["B"], geo["Lt"], geo["V"],
            G.P(d["word"]), geo["vocab"], G.P(d["pos"]), geo["P"], G.P(d["typ"]), G.P(d["vtyp"]), 2, G.P(d["vpos"]), G.P(d["proj"]),
            geo["ldp"], G.P(d["gm"]), G.P(d["bt"]), G.P(y), geo["Cc"], 1e-12, geo["dt"], G.stream())
@@ -140,6 +141,11 @@ def test_embed_entry_refuses_bad_sizes():
             run_embed(dict(geo, **patch), dev)
     with pytest.raises(ValueError):
         run_embed(dict(geo, A=3), dict(dev, align=None))
+    y = torch.full((geo["B"] * (geo["Lt"] + geo["V"]) + 1, geo["Cc"]), 77.0, device=G.DEV)
+    with pytest.raises(ValueError):
+        run_embed(dict(geo, dt=L.VK_I32), dev, y)
+    torch.cuda.synchronize()
+    assert (y == 77.0).all(), "a refused dtype wrote the output"
 
 
 # ---- 2. fp32 against transformers' vectors --------------------------------------------------------------------------------------

@@ -149,6 +149,12 @@ def test_entries_refuse_bad_sizes():
         with pytest.raises(ValueError):
             L.call("vk_vit_assemble", G.P(dev["proj"]), bad["ldp"], G.P(dev["cls"]), G.P(dev["pos"]), bad["B"], bad["N"], G.P(x), bad["H"],
                    geo["dt"], G.stream())
+    x = torch.full((64, 128), 77.0, device=G.DEV)
+    with pytest.raises(ValueError):
+        L.call("vk_vit_assemble", G.P(dev["proj"]), geo["ldp"], G.P(dev["cls"]), G.P(dev["pos"]), geo["B"], geo["N"], G.P(x), geo["H"],
+               L.VK_I32, G.stream())
+    torch.cuda.synchronize()
+    assert (x == 77.0).all(), "a refused dtype wrote the output"
 
 
 # ---- 2. fp32 against transformers' vectors --------------------------------------------------------------------------------------

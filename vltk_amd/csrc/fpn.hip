@@ -362,14 +362,6 @@ __global__ void relu_copy_kernel(const T *__restrict__ x, T *__restrict__ y, lon
 
 using namespace vk;
 
-#define VK_DT_SWITCH(dt, CALL)                                                          \
-    switch (dt) {                                                                       \
-        case VK_F32: { typedef float T; CALL; } break;                                  \
-        case VK_F16: { typedef _Float16 T; CALL; } break;                               \
-        case VK_BF16: { typedef __bf16 T; CALL; } break;                                \
-        default: VK_REQUIRE(false, VK_EINVAL, "dtype must be f32, f16 or bf16");        \
-    }
-
 extern "C" {
 
 int vk_roi_align(const void *const *maps, const int32_t *Hs, const int32_t *Ws, const float *scales, int levels, int N, int C,
@@ -396,16 +388,19 @@ int vk_roi_align(const void *const *maps, const int32_t *Hs, const int32_t *Ws, 
         if (P <= RA_MAXP && !per_sample) {
             int groups = 256 / (C / vec);
             while ((P * P) % groups) --groups;       // no idle group in the last pass (P = 7, 32 lanes per bin: 7 groups)
-            VK_DT_SWITCH(dt, hipLaunchKernelGGL(roi_align_sep_kernel<T>, dim3(K), dim3(256), 0, (hipStream_t)stream, py, C, rois, roi_levels, P,
-                                                sampling_ratio, aligned, groups, (T *)out));
+            VK_DT_SWITCH(dt, "roi_align",
+                         hipLaunchKernelGGL(roi_align_sep_kernel<T>, dim3(K), dim3(256), 0, (hipStream_t)stream, py, C, rois, roi_levels, P,
+                                            sampling_ratio, aligned, groups, (T *)out));
         } else {
-            VK_DT_SWITCH(dt, hipLaunchKernelGGL(roi_align_vec_kernel<T>, dim3(K), dim3(256), 0, (hipStream_t)stream, py, C, rois, roi_levels, P,
-                                                sampling_ratio, aligned, (T *)out));
+            VK_DT_SWITCH(dt, "roi_align",
+                         hipLaunchKernelGGL(roi_align_vec_kernel<T>, dim3(K), dim3(256), 0, (hipStream_t)stream, py, C, rois, roi_levels, P,
+                                            sampling_ratio, aligned, (T *)out));
         }
     } else {
         const dim3 grid((unsigned)((long)K * P * P)), block(C >= 256 ? 256 : 64);
-        VK_DT_SWITCH(dt, hipLaunchKernelGGL(roi_align_kernel<T>, grid, block, 0, (hipStream_t)stream, py, C, rois, roi_levels, P, sampling_ratio,
-                                            aligned, (T *)out));
+        VK_DT_SWITCH(dt, "roi_align",
+                     hipLaunchKernelGGL(roi_align_kernel<T>, grid, block, 0, (hipStream_t)stream, py, C, rois, roi_levels, P, sampling_ratio,
+                                        aligned, (T *)out));
     }
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
@@ -437,8 +432,9 @@ int vk_upsample2x_add(const void *lateral, const void *top, void *y, int N, int 
         VK_CHECK_HIP(hipGetLastError());
         return VK_OK;
     }
-    VK_DT_SWITCH(dt, hipLaunchKernelGGL(upsample2x_add_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                                        (const T *)lateral, (const T *)top, (T *)y, H, W, Ht, Wt, C, total));
+    VK_DT_SWITCH(dt, "upsample2x_add",
+                 hipLaunchKernelGGL(upsample2x_add_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                                    (const T *)lateral, (const T *)top, (T *)y, H, W, Ht, Wt, C, total));
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
 }
@@ -447,8 +443,9 @@ int vk_subsample2(const void *x, void *y, int N, int H, int W, int C, vk_dtype d
     VK_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0, VK_EINVAL, "subsample2: bad arguments");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const long total = (long)N * Ho * Wo * C;
-    VK_DT_SWITCH(dt, hipLaunchKernelGGL(subsample2_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                                        (const T *)x, (T *)y, H, W, Ho, Wo, C, total));
+    VK_DT_SWITCH(dt, "subsample2",
+                 hipLaunchKernelGGL(subsample2_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                                    (const T *)x, (T *)y, H, W, Ho, Wo, C, total));
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
 }
@@ -456,8 +453,9 @@ int vk_subsample2(const void *x, void *y, int N, int H, int W, int C, vk_dtype d
 int vk_relu_copy(const void *x, void *y, long n, vk_dtype dt, void *stream) {
     VK_REQUIRE(x && y && n >= 0, VK_EINVAL, "relu_copy: bad arguments");
     if (n == 0) return VK_OK;
-    VK_DT_SWITCH(dt, hipLaunchKernelGGL(relu_copy_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T *)x,
-                                        (T *)y, n));
+    VK_DT_SWITCH(dt, "relu_copy",
+                 hipLaunchKernelGGL(relu_copy_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T *)x,
+                                    (T *)y, n));
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
 }

@@ -3,22 +3,21 @@
 //
 //   vk_layoutlm_embed     LayoutLMEmbeddings.forward :66-119 as one launch: nine table rows summed in fp32 in transformers' order
 //                         word[id] + position[t] + x[x0] + y[y0] + x[x1] + y[y1] + h[y1 - y0] + w[x1 - x0] + token_type[tt],
-//                         LayerNorm in fp32, one rounding to the storage type.  visualbert_embed_kernel's shape: one wave per row,
-//                         four rows per workgroup, a lane owns the chunks lane, lane + 64, ...; 16-byte chunks when the row
-//                         length and the bases allow, single elements otherwise.  No LDS, no atomics.  Every index is clamped
-//                         into its table (the extents at 0 too), so a bad id or box reads a wrong row, never memory outside one.
+//                         LayerNorm in fp32, one rounding to the storage type.  row_norm.h's shape: one wave per row, four rows
+//                         per workgroup, a lane owns the chunks lane, lane + 64, ...; 16-byte chunks when the row length and
+//                         the bases allow, single elements otherwise; the kernel is the source rows and the loader that sums
+//                         them.  No LDS, no atomics.  Every index is clamped into its table (the extents at 0 too), so a bad
+//                         id or box reads a wrong row, never memory outside one.
 //   vk_token_word_labels  arg-max label per token, then per word the most frequent label of its tokens (ties: the smallest label).
 //                         One workgroup per example; (word id, label) of every token packed into one LDS word; a thread per word
 //                         first collects which labels its tokens carry (a 64-bit set), then counts label by label, ascending.
 //   vk_span_select        best (start, end) pair of an extractive-QA head.  One workgroup per example; end logits and the context
 //                         mask in LDS; a thread per start scans its ends upward; block reduction on (score, -s, -e).
-#include "vk_common.h"
+#include "row_norm.h"
 
 namespace vk {
 
 // ---- vk_layoutlm_embed ------------------------------------------------------------------------------------------------------------
-constexpr int LLE_MAX_PER_LANE = 32;     // rows up to 2048 elements, as vk_layernorm
-
 struct LleArgs {
     const int64_t *ids, *tts;            // [B, L]
     const int32_t *bbox;                 // [B, L, 4] (x0, y0, x1, y1)
@@ -32,13 +31,11 @@ struct LleArgs {
 // VW: elements per chunk (16 / sizeof(T) on the vector path, 1 on the scalar one); C % VW == 0.
 template <typename T, int VW>
 __global__ __launch_bounds__(256) void layoutlm_embed_kernel(const LleArgs a) {
-    constexpr int MAXC = LLE_MAX_PER_LANE / VW;          // chunks per lane
     const int C = a.C;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= (long)a.B * a.L) return;
     const int t = (int)(row % a.L);                      // L <= max_position (checked by the entry point)
-    const int chunks = C / VW;
 
     // the nine source rows of this output row, in the order they are summed
     const int32_t *bb = a.bbox + row * 4;
@@ -54,63 +51,28 @@ __global__ __launch_bounds__(256) void layoutlm_embed_kernel(const LleArgs a) {
     src[7] = (const T *)a.w + clamp_row(x1 - x0, a.max_2d) * C;
     src[8] = (const T *)a.token_type + clamp_row(a.tts[row], a.type_vocab) * C;
 
-    float v[MAXC][VW];
-    float s = 0.f;
+    const auto load = [&](int ch, float (&out)[VW]) {
+        float p[9][VW];
 #pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-        const int ch = lane + 64 * i;
-        if (ch < chunks) {
-            float p[9][VW];
+        for (int k = 0; k < 9; ++k) ld_chunk<T, VW>(src[k] + ch * VW, p[k]);
 #pragma unroll
-            for (int k = 0; k < 9; ++k) ld_chunk<T, VW>(src[k] + ch * VW, p[k]);
+        for (int e = 0; e < VW; ++e) {
+            float acc = p[0][e];
 #pragma unroll
-            for (int e = 0; e < VW; ++e) {
-                float acc = p[0][e];
-#pragma unroll
-                for (int k = 1; k < 9; ++k) acc += p[k][e];
-                v[i][e] = acc;
-                s += acc;
-            }
+            for (int k = 1; k < 9; ++k) acc += p[k][e];
+            out[e] = acc;
         }
-    }
-    const float mean = wave_sum(s) / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i)
-        if (lane + 64 * i < chunks) {
-#pragma unroll
-            for (int e = 0; e < VW; ++e) {
-                const float d = v[i][e] - mean;
-                q += d * d;
-            }
-        }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + a.eps);
-    T *yr = (T *)a.out + row * C;
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-        const int ch = lane + 64 * i;
-        if (ch < chunks) {
-            float o[VW];
-#pragma unroll
-            for (int e = 0; e < VW; ++e) o[e] = (v[i][e] - mean) * rstd * a.gamma[ch * VW + e] + a.beta[ch * VW + e];
-            st_chunk<T, VW>(yr + ch * VW, o);
-        }
-    }
+    };
+    row_layernorm<T, VW>(C, lane, load, a.gamma, a.beta, a.eps, 1.0f, 0, (T *)a.out + row * C);
 }
 
 template <typename T>
 static int lle_launch(const LleArgs &a, hipStream_t s) {
     constexpr int VW = 16 / sizeof(T);
-    const long rows = (long)a.B * a.L;
-    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
     const uintptr_t bases = (uintptr_t)a.word | (uintptr_t)a.position | (uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)a.h |
                             (uintptr_t)a.w | (uintptr_t)a.token_type | (uintptr_t)a.out;
-    if (a.C % VW == 0 && bases % 16 == 0)
-        hipLaunchKernelGGL((layoutlm_embed_kernel<T, VW>), grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL((layoutlm_embed_kernel<T, 1>), grid, block, 0, s, a);
-    VK_CHECK_HIP(hipGetLastError());
-    return VK_OK;
+    const bool chunked = row_chunked(VW, a.C, bases);
+    return row_launch(chunked ? layoutlm_embed_kernel<T, VW> : layoutlm_embed_kernel<T, 1>, (long)a.B * a.L, s, a);
 }
 
 // ---- vk_token_word_labels -----------------------------------------------------------------------------------------------------------
@@ -227,7 +189,7 @@ int vk_layoutlm_embed(const int64_t *input_ids, const int64_t *token_type_ids, c
     VK_REQUIRE(input_ids && token_type_ids && bbox && word && position && x && y && h && w && token_type && gamma && beta && out,
                VK_EINVAL, "layoutlm_embed: null argument");
     VK_REQUIRE(B > 0 && L > 0 && (long)B * (long)L < (1L << 31), VK_EINVAL, "layoutlm_embed: bad geometry (B=%d L=%d)", B, L);
-    VK_REQUIRE(C > 0 && C <= 64 * LLE_MAX_PER_LANE, VK_EINVAL, "layoutlm_embed: C=%d must be in 1..%d", C, 64 * LLE_MAX_PER_LANE);
+    VK_REQUIRE(C > 0 && C <= ROW_MAX_C, VK_EINVAL, "layoutlm_embed: C=%d must be in 1..%d", C, ROW_MAX_C);
     VK_REQUIRE(vocab > 0 && type_vocab > 0 && max_2d > 0 && max_position > 0 && L <= max_position, VK_EINVAL,
                "layoutlm_embed: %d tokens need max_position >= that (%d); vocab %d, type_vocab %d, max_2d %d", L, max_position, vocab,
                type_vocab, max_2d);
@@ -237,14 +199,7 @@ int vk_layoutlm_embed(const int64_t *input_ids, const int64_t *token_type_ids, c
     a.gamma = gamma, a.beta = beta, a.out = out;
     a.B = B, a.L = L, a.C = C, a.vocab = vocab, a.max_position = max_position, a.max_2d = max_2d, a.type_vocab = type_vocab;
     a.eps = eps;
-    switch (dt) {
-        case VK_F32: return lle_launch<float>(a, (hipStream_t)stream);
-        case VK_F16: return lle_launch<_Float16>(a, (hipStream_t)stream);
-        case VK_BF16: return lle_launch<__bf16>(a, (hipStream_t)stream);
-        default: break;
-    }
-    VK_REQUIRE(false, VK_EINVAL, "layoutlm_embed: dtype must be f32, f16 or bf16");
-    return VK_EINVAL;
+    VK_DT_SWITCH(dt, "layoutlm_embed", return lle_launch<T>(a, (hipStream_t)stream));
 }
 
 int vk_token_word_labels(const void *logits, int ld, const int32_t *word_ids, int B, int L, int C, int W, int32_t *token_labels,
@@ -256,18 +211,9 @@ int vk_token_word_labels(const void *logits, int ld, const int32_t *word_ids, in
     VK_REQUIRE(W >= 1 && W <= L, VK_EINVAL, "token_word_labels: W=%d words per example must be in 1..L=%d", W, L);
     const dim3 grid((unsigned)B), block(TWL_THREADS);
     hipStream_t s = (hipStream_t)stream;
-    switch (dt) {
-        case VK_F32:
-            hipLaunchKernelGGL(token_word_labels_kernel<float>, grid, block, 0, s, (const float *)logits, ld, word_ids, L, C, W, token_labels, word_labels);
-            break;
-        case VK_F16:
-            hipLaunchKernelGGL(token_word_labels_kernel<_Float16>, grid, block, 0, s, (const _Float16 *)logits, ld, word_ids, L, C, W, token_labels, word_labels);
-            break;
-        case VK_BF16:
-            hipLaunchKernelGGL(token_word_labels_kernel<__bf16>, grid, block, 0, s, (const __bf16 *)logits, ld, word_ids, L, C, W, token_labels, word_labels);
-            break;
-        default: VK_REQUIRE(false, VK_EINVAL, "token_word_labels: dtype must be f32, f16 or bf16");
-    }
+    VK_DT_SWITCH(dt, "token_word_labels",
+                 hipLaunchKernelGGL(token_word_labels_kernel<T>, grid, block, 0, s, (const T *)logits, ld, word_ids, L, C, W, token_labels,
+                                    word_labels));
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
 }
@@ -282,21 +228,9 @@ int vk_span_select(const void *start_logits, int start_stride, const void *end_l
     const dim3 grid((unsigned)B), block(SPN_THREADS);
     hipStream_t s = (hipStream_t)stream;
     const int ml = max_answer_tokens < L ? max_answer_tokens : L;
-    switch (dt) {
-        case VK_F32:
-            hipLaunchKernelGGL(span_select_kernel<float>, grid, block, 0, s, (const float *)start_logits, start_stride, (const float *)end_logits,
-                               end_stride, context_mask, L, ml, start, end, score);
-            break;
-        case VK_F16:
-            hipLaunchKernelGGL(span_select_kernel<_Float16>, grid, block, 0, s, (const _Float16 *)start_logits, start_stride,
-                               (const _Float16 *)end_logits, end_stride, context_mask, L, ml, start, end, score);
-            break;
-        case VK_BF16:
-            hipLaunchKernelGGL(span_select_kernel<__bf16>, grid, block, 0, s, (const __bf16 *)start_logits, start_stride,
-                               (const __bf16 *)end_logits, end_stride, context_mask, L, ml, start, end, score);
-            break;
-        default: VK_REQUIRE(false, VK_EINVAL, "span_select: dtype must be f32, f16 or bf16");
-    }
+    VK_DT_SWITCH(dt, "span_select",
+                 hipLaunchKernelGGL(span_select_kernel<T>, grid, block, 0, s, (const T *)start_logits, start_stride, (const T *)end_logits,
+                                    end_stride, context_mask, L, ml, start, end, score));
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
 }

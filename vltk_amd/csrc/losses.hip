@@ -15,7 +15,7 @@
 // are rounded once each before v_exp_f32; a running maximum that moves rescales the running sum by exp(m_old - m_new); the joins
 // (six shuffle steps in a wave, then the four waves of a workgroup in order) rescale likewise; then lse = m + logf(s) and
 // loss = lse - x[label], one rounding each.
-#include "vk_common.h"
+#include "row_norm.h"      // ld_chunk
 
 namespace vk {
 
@@ -225,30 +225,21 @@ int vk_cross_entropy_form(int C, int ld, vk_dtype dt, int aligned16) {
 int vk_cross_entropy(const void *logits, int ld, int M, int C, const int64_t *labels, int ignore_index, float *row_loss, vk_dtype dt,
                      void *stream) {
     VK_REQUIRE(logits && labels && row_loss, VK_EINVAL, "cross_entropy: null argument");
-    VK_REQUIRE(float_dt(dt), VK_EINVAL, "cross_entropy: dtype must be f32, f16 or bf16");
+    VK_REQUIRE(float_dt(dt), VK_EINVAL, "cross_entropy: dtype must be f32, f16 or bf16");      // ce_form divides by the dtype's size
     VK_REQUIRE(M >= 1 && C >= 1 && ld >= C, VK_EINVAL, "cross_entropy: bad shape M=%d C=%d ld=%d", M, C, ld);
     VK_REQUIRE(ignore_index < 0, VK_EINVAL, "cross_entropy: ignore_index=%d must be negative (it may not name a class)", ignore_index);
     const int form = ce_form(C, ld, dt, ((uintptr_t)logits & 15) == 0);
     hipStream_t s = (hipStream_t)stream;
-    switch (dt) {
-        case VK_F32: ce_launch<float>(form, logits, ld, M, C, labels, ignore_index, row_loss, s); break;
-        case VK_F16: ce_launch<_Float16>(form, logits, ld, M, C, labels, ignore_index, row_loss, s); break;
-        default: ce_launch<__bf16>(form, logits, ld, M, C, labels, ignore_index, row_loss, s); break;
-    }
+    VK_DT_SWITCH(dt, "cross_entropy", ce_launch<T>(form, logits, ld, M, C, labels, ignore_index, row_loss, s));
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
 }
 
 int vk_smooth_l1_rows(const void *pred, int ld, const float *target, int ldt, int M, int C, float *row_loss, vk_dtype dt, void *stream) {
     VK_REQUIRE(pred && target && row_loss, VK_EINVAL, "smooth_l1_rows: null argument");
-    VK_REQUIRE(float_dt(dt), VK_EINVAL, "smooth_l1_rows: dtype must be f32, f16 or bf16");
     VK_REQUIRE(M >= 1 && C >= 1 && ld >= C && ldt >= C, VK_EINVAL, "smooth_l1_rows: bad shape M=%d C=%d ld=%d ldt=%d", M, C, ld, ldt);
     hipStream_t s = (hipStream_t)stream;
-    switch (dt) {
-        case VK_F32: sl1_launch<float>(pred, ld, target, ldt, M, C, row_loss, s); break;
-        case VK_F16: sl1_launch<_Float16>(pred, ld, target, ldt, M, C, row_loss, s); break;
-        default: sl1_launch<__bf16>(pred, ld, target, ldt, M, C, row_loss, s); break;
-    }
+    VK_DT_SWITCH(dt, "smooth_l1_rows", sl1_launch<T>(pred, ld, target, ldt, M, C, row_loss, s));
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
 }

@@ -26,11 +26,6 @@ namespace vk {
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 constexpr int PC_XCDS = 8;      // accelerator dies of an MI355X; only the order of the classes depends on it, no result does
 
-static __device__ __forceinline__ float pc_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 static __device__ __forceinline__ float pc_wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
@@ -54,7 +49,7 @@ __global__ __launch_bounds__(256) void class_probs_kernel(const float *__restric
     m = pc_wave_max(m);
     float s = 0.f;
     for (int c = lane; c < n; c += 64) s += expf(x[c] - m);
-    s = pc_wave_sum(s);
+    s = wave_sum(s);
     float *o = out + (long)k * ld_out;
     for (int c = lane; c < n; c += 64) o[c] = expf(x[c] - m) / s;
 }

@@ -7,15 +7,15 @@
 //                            (+ mean over the valid a of position[align[b, j, a]]; -1 pads, a box with none adds zero)
 //   then LayerNorm over the row: sums, statistics and the affine in fp32, one rounding to the storage type on the way out.
 //
-// One wave per row, four rows per workgroup; the text / visual branch is wave-uniform.  A lane owns the chunks lane, lane + 64, ...
-// of the row: 16-byte chunks when the row length allows (layernorm_vec_kernel's layout, layernorm.hip), single elements otherwise.
-// No LDS, no atomics.  Every table index is clamped into its table, so a bad id reads a wrong row, never memory outside one;
-// refusing bad ids is the caller's job (vltk_amd/visualbert.py does, before the launch).
-#include "vk_common.h"
+// One wave per row, four rows per workgroup; the text / visual branch is wave-uniform.  The kernel sets up the source rows and the
+// loader that sums a chunk of them; the lane partition, the LayerNorm and the launch rule (16-byte chunks when the row length, the
+// projection's stride and the bases allow, single elements otherwise) are row_norm.h's.  No LDS, no atomics.  Every table index
+// is clamped into its table, so a bad id reads a wrong row, never memory outside one; refusing bad ids is the caller's job
+// (vltk_amd/visualbert.py does, before the launch).
+#include "row_norm.h"
 
 namespace vk {
 
-constexpr int VBE_MAX_PER_LANE = 32;     // rows up to 2048 elements, as vk_layernorm
 constexpr int VBE_MAX_ALIGN = 16;        // alignment entries per box
 
 struct VbeArgs {
@@ -31,14 +31,12 @@ struct VbeArgs {
 // VW: elements per chunk (16 / sizeof(T) on the vector path, 1 on the scalar one); C % VW == 0.
 template <typename T, int VW>
 __global__ __launch_bounds__(256) void visualbert_embed_kernel(const VbeArgs a) {
-    constexpr int MAXC = VBE_MAX_PER_LANE / VW;          // chunks per lane
     const int L = a.Lt + a.V, C = a.C;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= (long)a.B * L) return;
     const int b = (int)(row / L), r = (int)(row - (long)b * L);
     const bool text = r < a.Lt;                          // wave-uniform
-    const int chunks = C / VW;
     const T *pos = (const T *)a.position;
 
     // the three (four) source rows of this output row
@@ -70,75 +68,40 @@ __global__ __launch_bounds__(256) void visualbert_embed_kernel(const VbeArgs a) 
     }
     const float denom = (float)(count > 0 ? count : 1);
 
-    float v[MAXC][VW];
-    float s = 0.f;
+    // by value but for the index array: captured by reference, the scalars cost the f32 chunk form two VGPRs and a wave per SIMD
+    const auto load = [=, &al](int ch, float (&out)[VW]) {
+        float t0[VW], t1[VW], t2[VW];
+        ld_chunk<T, VW>(s0 + ch * VW, t0);
+        ld_chunk<T, VW>(s1 + ch * VW, t1);
+        ld_chunk<T, VW>(s2 + ch * VW, t2);
 #pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-        const int ch = lane + 64 * i;
-        if (ch < chunks) {
-            float t0[VW], t1[VW], t2[VW];
-            ld_chunk<T, VW>(s0 + ch * VW, t0);
-            ld_chunk<T, VW>(s1 + ch * VW, t1);
-            ld_chunk<T, VW>(s2 + ch * VW, t2);
+        for (int e = 0; e < VW; ++e) out[e] = t0[e] + t1[e] + t2[e];
+        if (!text && count > 0) {
+            float m[VW];
 #pragma unroll
-            for (int e = 0; e < VW; ++e) v[i][e] = t0[e] + t1[e] + t2[e];
-            if (!text && count > 0) {
-                float m[VW];
+            for (int e = 0; e < VW; ++e) m[e] = 0.f;
 #pragma unroll
-                for (int e = 0; e < VW; ++e) m[e] = 0.f;
+            for (int k = 0; k < VBE_MAX_ALIGN; ++k)
+                if (k < a.A && al[k] >= 0) {
+                    float p[VW];
+                    ld_chunk<T, VW>(pos + (long)al[k] * C + ch * VW, p);
 #pragma unroll
-                for (int k = 0; k < VBE_MAX_ALIGN; ++k)
-                    if (k < a.A && al[k] >= 0) {
-                        float p[VW];
-                        ld_chunk<T, VW>(pos + (long)al[k] * C + ch * VW, p);
+                    for (int e = 0; e < VW; ++e) m[e] += p[e];
+                }
 #pragma unroll
-                        for (int e = 0; e < VW; ++e) m[e] += p[e];
-                    }
-#pragma unroll
-                for (int e = 0; e < VW; ++e) v[i][e] += m[e] / denom;
-            }
-#pragma unroll
-            for (int e = 0; e < VW; ++e) s += v[i][e];
+            for (int e = 0; e < VW; ++e) out[e] += m[e] / denom;
         }
-    }
-    const float mean = wave_sum(s) / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i)
-        if (lane + 64 * i < chunks) {
-#pragma unroll
-            for (int e = 0; e < VW; ++e) {
-                const float d = v[i][e] - mean;
-                q += d * d;
-            }
-        }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + a.eps);
-    T *yr = (T *)a.y + row * C;
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-        const int ch = lane + 64 * i;
-        if (ch < chunks) {
-            float o[VW];
-#pragma unroll
-            for (int e = 0; e < VW; ++e) o[e] = (v[i][e] - mean) * rstd * a.gamma[ch * VW + e] + a.beta[ch * VW + e];
-            st_chunk<T, VW>(yr + ch * VW, o);
-        }
-    }
+    };
+    row_layernorm<T, VW>(C, lane, load, a.gamma, a.beta, a.eps, 1.0f, 0, (T *)a.y + row * C);
 }
 
 template <typename T>
 static int vbe_launch(const VbeArgs &a, hipStream_t s) {
     constexpr int VW = 16 / sizeof(T);
-    const long rows = (long)a.B * (a.Lt + a.V);
-    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
     const uintptr_t bases = (uintptr_t)a.word | (uintptr_t)a.position | (uintptr_t)a.token_type | (uintptr_t)a.visual_token_type |
                             (uintptr_t)a.visual_position | (uintptr_t)a.proj | (uintptr_t)a.y;
-    if (a.C % VW == 0 && a.ldp % VW == 0 && bases % 16 == 0)
-        hipLaunchKernelGGL((visualbert_embed_kernel<T, VW>), grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL((visualbert_embed_kernel<T, 1>), grid, block, 0, s, a);
-    VK_CHECK_HIP(hipGetLastError());
-    return VK_OK;
+    const bool chunked = row_chunked(VW, a.C | a.ldp, bases);
+    return row_launch(chunked ? visualbert_embed_kernel<T, VW> : visualbert_embed_kernel<T, 1>, (long)a.B * (a.Lt + a.V), s, a);
 }
 
 }  // namespace vk
@@ -157,7 +120,7 @@ int vk_visualbert_embed(const int64_t *input_ids, const int64_t *token_type_ids,
                VK_EINVAL, "visualbert_embed: null argument");
     VK_REQUIRE(B > 0 && Lt > 0 && V > 0 && (long)B * ((long)Lt + V) < (1L << 31), VK_EINVAL,
                "visualbert_embed: bad geometry (B=%d Lt=%d V=%d)", B, Lt, V);
-    VK_REQUIRE(C > 0 && C <= 64 * VBE_MAX_PER_LANE, VK_EINVAL, "visualbert_embed: C=%d must be in 1..%d", C, 64 * VBE_MAX_PER_LANE);
+    VK_REQUIRE(C > 0 && C <= ROW_MAX_C, VK_EINVAL, "visualbert_embed: C=%d must be in 1..%d", C, ROW_MAX_C);
     VK_REQUIRE(ldp >= C, VK_EINVAL, "visualbert_embed: projection row stride %d below the row length %d", ldp, C);
     VK_REQUIRE(vocab > 0 && type_vocab > 0 && max_position > 0 && Lt <= max_position, VK_EINVAL,
                "visualbert_embed: %d text tokens need max_position >= that (%d); vocab %d, type_vocab %d", Lt, max_position, vocab,
@@ -170,14 +133,7 @@ int vk_visualbert_embed(const int64_t *input_ids, const int64_t *token_type_ids,
     a.visual_position = visual_position, a.proj = proj, a.gamma = gamma, a.beta = beta, a.y = y;
     a.A = A, a.B = B, a.Lt = Lt, a.V = V, a.C = C, a.ldp = ldp, a.vocab = vocab, a.type_vocab = type_vocab, a.max_position = max_position;
     a.eps = eps;
-    switch (dt) {
-        case VK_F32: return vbe_launch<float>(a, (hipStream_t)stream);
-        case VK_F16: return vbe_launch<_Float16>(a, (hipStream_t)stream);
-        case VK_BF16: return vbe_launch<__bf16>(a, (hipStream_t)stream);
-        default: break;
-    }
-    VK_REQUIRE(false, VK_EINVAL, "visualbert_embed: dtype must be f32, f16 or bf16");
-    return VK_EINVAL;
+    VK_DT_SWITCH(dt, "visualbert_embed", return vbe_launch<T>(a, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@
 //
 // Both are one thread per 16-byte output chunk (a chunk never straddles two rows: ldk * es and, on the chunk form, H * es are
 // multiples of 16), adjacent threads on adjacent chunks.  No LDS, no atomics, every index in 64 bits.
-#include "vk_common.h"
+#include "row_norm.h"      // ld_chunk, st_chunk
 
 namespace vk {
 
@@ -92,7 +92,6 @@ struct AssembleArgs {
 // VW: elements per chunk (16 / sizeof(T) on the chunk form, 1 on the scalar one); H % VW == 0.
 template <typename T, int VW>
 __global__ __launch_bounds__(256) void vit_assemble_kernel(const AssembleArgs a) {
-    typedef T vecT __attribute__((ext_vector_type(VW)));
     const int cpr = a.H / VW;
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= a.n_rows * cpr) return;
@@ -102,16 +101,12 @@ __global__ __launch_bounds__(256) void vit_assemble_kernel(const AssembleArgs a)
     const int r = (int)(row - b * (a.N + 1));
     const T *src = r == 0 ? (const T *)a.cls : (const T *)a.proj + (b * a.N + (r - 1)) * a.ldp;
     const T *pos = (const T *)a.pos + (long)r * a.H;
-    T *dst = (T *)a.x + row * a.H + col;
-    if constexpr (VW == 1) {
-        *dst = (T)((float)src[col] + (float)pos[col]);
-    } else {
-        const vecT u = *reinterpret_cast<const vecT *>(src + col), p = *reinterpret_cast<const vecT *>(pos + col);
-        vecT o;
+    float u[VW], p[VW];
+    ld_chunk<T, VW>(src + col, u);
+    ld_chunk<T, VW>(pos + col, p);
 #pragma unroll
-        for (int e = 0; e < VW; ++e) o[e] = (T)((float)u[e] + (float)p[e]);
-        *reinterpret_cast<vecT *>(dst) = o;
-    }
+    for (int e = 0; e < VW; ++e) u[e] += p[e];
+    st_chunk<T, VW>((T *)a.x + row * a.H + col, u);
 }
 
 template <typename T>
@@ -137,7 +132,6 @@ extern "C" {
 
 int vk_vit_patchify(const float *pixel_values, int B, int C, int Hi, int Wi, int P, void *rows, int ldk, vk_dtype dt, void *stream) {
     VK_REQUIRE(pixel_values && rows, VK_EINVAL, "vit_patchify: null argument");
-    VK_REQUIRE(dt == VK_F32 || dt == VK_F16 || dt == VK_BF16, VK_EINVAL, "vit_patchify: dtype must be f32, f16 or bf16");
     VK_REQUIRE(B >= 1 && P >= 1 && C >= 1 && C <= 4, VK_EINVAL, "vit_patchify: bad geometry (B=%d C=%d P=%d; C in 1..4)", B, C, P);
     VK_REQUIRE(Hi >= P && Wi >= P && Hi % P == 0 && Wi % P == 0, VK_EINVAL,
                "vit_patchify: a %d x %d image is no positive multiple of the %d x %d patch", Hi, Wi, P, P);
@@ -150,17 +144,12 @@ int vk_vit_patchify(const float *pixel_values, int B, int C, int Hi, int Wi, int
     a.B = B, a.C = C, a.Hi = Hi, a.Wi = Wi, a.P = P, a.gh = Hi / P, a.gw = Wi / P, a.ldk = ldk;
     a.n_rows = (long)B * a.gh * a.gw;
     VK_REQUIRE(a.n_rows < (1L << 31), VK_EINVAL, "vit_patchify: %ld patch rows", a.n_rows);
-    switch (dt) {
-        case VK_F32: return patchify_launch<float>(a, (hipStream_t)stream);
-        case VK_F16: return patchify_launch<_Float16>(a, (hipStream_t)stream);
-        default: return patchify_launch<__bf16>(a, (hipStream_t)stream);
-    }
+    VK_DT_SWITCH(dt, "vit_patchify", return patchify_launch<T>(a, (hipStream_t)stream));
 }
 
 int vk_vit_assemble(const void *proj, int ldp, const void *cls_token, const void *position, int B, int N, void *x, int H,
                     vk_dtype dt, void *stream) {
     VK_REQUIRE(proj && cls_token && position && x, VK_EINVAL, "vit_assemble: null argument");
-    VK_REQUIRE(dt == VK_F32 || dt == VK_F16 || dt == VK_BF16, VK_EINVAL, "vit_assemble: dtype must be f32, f16 or bf16");
     VK_REQUIRE(B > 0 && N > 0 && (long)B * ((long)N + 1) < (1L << 31), VK_EINVAL, "vit_assemble: bad geometry (B=%d N=%d)", B, N);
     VK_REQUIRE(H > 0, VK_EINVAL, "vit_assemble: H=%d", H);
     VK_REQUIRE(ldp >= H, VK_EINVAL, "vit_assemble: projection row stride %d below the row length %d", ldp, H);
@@ -168,11 +157,7 @@ int vk_vit_assemble(const void *proj, int ldp, const void *cls_token, const void
     a.proj = proj, a.cls = cls_token, a.pos = position, a.x = x;
     a.B = B, a.N = N, a.H = H, a.ldp = ldp;
     a.n_rows = (long)B * (N + 1);
-    switch (dt) {
-        case VK_F32: return assemble_launch<float>(a, (hipStream_t)stream);
-        case VK_F16: return assemble_launch<_Float16>(a, (hipStream_t)stream);
-        default: return assemble_launch<__bf16>(a, (hipStream_t)stream);
-    }
+    VK_DT_SWITCH(dt, "vit_assemble", return assemble_launch<T>(a, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -38,6 +38,15 @@ void set_error(const char *fmt, ...);
         if (_s != VK_OK) return _s; \
     } while (0)
 
+// CALL with T = float, _Float16 or __bf16 as dt says; any other dt is refused in the entry's name (`who`, a string literal).
+#define VK_DT_SWITCH(dt, who, CALL)                                                     \
+    switch (dt) {                                                                       \
+        case VK_F32: { typedef float T; CALL; } break;                                  \
+        case VK_F16: { typedef _Float16 T; CALL; } break;                               \
+        case VK_BF16: { typedef __bf16 T; CALL; } break;                                \
+        default: VK_REQUIRE(false, VK_EINVAL, who ": dtype must be f32, f16 or bf16");  \
+    }
+
 static inline size_t dtype_size(vk_dtype dt) {
     switch (dt) {
         case VK_F32: return 4;
@@ -257,7 +266,7 @@ int launch_roi_final(RoiFinalArgs &a, int N, hipStream_t s);
 int launch_make_rois(const float *boxes, int N, int R, float *rois, hipStream_t s);
 
 // One element of any storage type as fp32, and back; the sum of a value over the 64 lanes of a wave, left in every lane.
-// Shared by attention.hip, layernorm.hip and roi_out.hip.
+// Shared by attention.hip, row_norm.h, losses.hip, roi_out.hip and per_class.hip.
 template <typename T>
 __device__ __forceinline__ float ldf(const T *p) { return (float)*p; }
 template <typename T>
@@ -267,34 +276,6 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-
-// VW consecutive elements as fp32, and back with one rounding each: one 16-byte access where VW = 16 / sizeof(T) (p then 16-byte
-// aligned), one element where VW = 1.  A table index clamped into a table of n rows.  Shared by the embedding kernels of
-// visualbert.hip and layoutlm.hip.
-template <typename T, int VW>
-__device__ __forceinline__ void ld_chunk(const T *p, float (&out)[VW]) {
-    if constexpr (VW == 1) {
-        out[0] = (float)*p;
-    } else {
-        typedef T vecT __attribute__((ext_vector_type(VW)));
-        const vecT t = *reinterpret_cast<const vecT *>(p);
-#pragma unroll
-        for (int e = 0; e < VW; ++e) out[e] = (float)t[e];
-    }
-}
-template <typename T, int VW>
-__device__ __forceinline__ void st_chunk(T *p, const float (&v)[VW]) {
-    if constexpr (VW == 1) {
-        *p = (T)v[0];
-    } else {
-        typedef T vecT __attribute__((ext_vector_type(VW)));
-        vecT o;
-#pragma unroll
-        for (int e = 0; e < VW; ++e) o[e] = (T)v[e];
-        *reinterpret_cast<vecT *>(p) = o;
-    }
-}
-__device__ __forceinline__ long clamp_row(long i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
 
 // Sort key of a score for an ascending sort that ranks scores descending (-0 ranks as +0); the low word of the 64-bit key
 // holds the row index, so ties go to the lower index.  Shared by roi_out.hip and per_class.hip.
