@@ -607,6 +607,15 @@ int vk_loss_total(const float *terms, int present, float *out, void *stream);
 int vk_roi_align(const void *const *maps, const int32_t *Hs, const int32_t *Ws, const float *scales, int levels,
                  int N, int C, const float *rois, const int32_t *roi_levels, int K, int P, int sampling_ratio,
                  int aligned, void *out, vk_dtype dt, void *stream);
+/* Which kernel a RoIAlign launch runs on (host only, touches no device).  SCALAR where C is not a whole number of 16-byte
+ * chunks or C * sizeof(dt) / 16 > 256; else SEP where P <= 16, unless VK_ROIALIGN_TABLES (re-read per call) is set to a
+ * text whose atoi is 0; VEC elsewhere.  The vector forms read maps and write `out` in 16-byte chunks: both must be
+ * 16-byte aligned, which the entry does not check.  Returns a VK_RA_FORM_* or -VK_EINVAL where the launch would refuse
+ * the call (C < 1, P < 1, a dtype that is not f32 / f16 / bf16). */
+#define VK_RA_FORM_SEP 0        /* roi_align_sep_kernel: per-axis weight tables in LDS, each footprint pixel read once */
+#define VK_RA_FORM_VEC 1        /* roi_align_vec_kernel: the per-sample loop, 16-byte lanes */
+#define VK_RA_FORM_SCALAR 2     /* roi_align_kernel: a workgroup per (RoI, bin), one channel per lane and step */
+int vk_roi_align_form(int C, int P, vk_dtype dt);
 /* assign_boxes_to_levels frcnn.py:444-460: floor(canonical_level + log2(sqrt(area)/canonical_box_size + 1e-8)),
  * clamped to [min_level, max_level], minus min_level.  boxes [K, ld] (x1,y1,x2,y2 first). */
 int vk_assign_levels(const float *boxes, int ld, int K, int min_level, int max_level, float canonical_box_size,
@@ -616,7 +625,8 @@ int vk_upsample2x_add(const void *lateral, const void *top, void *y, int N, int 
                       vk_dtype dt, void *stream);
 /* LastLevelMaxPool frcnn.py:835-836: max_pool2d(kernel 1, stride 2) = every second pixel.  y [N,(H-1)/2+1,(W-1)/2+1,C] */
 int vk_subsample2(const void *x, void *y, int N, int H, int W, int C, vk_dtype dt, void *stream);
-/* the ReLU between LastLevelP6P7's convolutions frcnn.py:852-853 (p6 itself stays un-rectified) */
+/* the ReLU between LastLevelP6P7's convolutions frcnn.py:852-853 (p6 itself stays un-rectified); as torch.relu, NaN stays
+ * NaN and -0.0 stays -0.0 */
 int vk_relu_copy(const void *x, void *y, long n, vk_dtype dt, void *stream);
 
 /* find_top_rpn_proposals frcnn.py:264-390 over SEVERAL levels (the reference's RPN class itself cannot run them: its
@@ -667,7 +677,9 @@ void vk_stem_out_hw(int H, int W, int caffe_maxpool, int *Ho, int *Wo);
 /* Image pre-processing  <- ResizeShortestEdge + Preprocess, vltk/legacy/processing.py:29-150:
  * per image bilinear resize (align_corners=False) of a float HWC (BGR 0-255) device image to new_hw, (x-mean)/std,
  * pad with pad_value to [N,3,Hmax,Wmax] f32 NCHW.  raw_dev_ptrs_host: host array of N device pointers;
- * raw_hw_host / new_hw_host: host [N,2] (h, w); the resize size rule itself is host logic (vltk_amd/preprocess.py). */
+ * raw_hw_host / new_hw_host: host [N,2] (h, w); the resize size rule itself is host logic (vltk_amd/preprocess.py).
+ * Every image (a non-null pointer, sizes >= 1, new_hw within Hmax x Wmax) is validated before the first launch: VK_EINVAL
+ * leaves the output untouched, whatever the image's index. */
 int vk_preprocess(const float *const *raw_dev_ptrs_host, const int32_t *raw_hw_host, const int32_t *new_hw_host,
                   int N, int Hmax, int Wmax, const float *mean3_host, const float *std3_host, float pad_value,
                   float *out_nchw_dev, void *stream);

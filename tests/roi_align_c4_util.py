@@ -61,43 +61,71 @@ def exact_rois(seed=0):
     return np.asarray(rows, dtype=np.float32)
 
 
-def roi_align_fp64(x, rois, P, scale, sampling_ratio, aligned):
+def roi_geometry(r, P, scale, sampling_ratio, aligned, ft=np.float64):
+    """(sh, sw, bh, bw, gh, gw) of one RoI row (batch, x1, y1, x2, y2) in the float type `ft`, by the expressions of
+    csrc/fpn.hip and oracle/tv_ops.c, one rounding per operation."""
+    r = np.asarray(r, dtype=ft)
+    s, off, Pf = ft(scale), ft(0.5 if aligned else 0.0), ft(P)
+    sw, sh, ew, eh = (r[1:] * s - off)
+    rw, rh = ew - sw, eh - sh
+    if not aligned:
+        rw, rh = max(rw, ft(1.0)), max(rh, ft(1.0))       # fmaxf: a NaN side becomes 1
+    bh, bw = rh / Pf, rw / Pf
+    gh = sampling_ratio if sampling_ratio > 0 else int(np.ceil(rh / Pf))
+    gw = sampling_ratio if sampling_ratio > 0 else int(np.ceil(rw / Pf))
+    return sh, sw, bh, bw, gh, gw
+
+
+def axis_weights(start, bsz, g, size, P, ft=np.float64):
+    """[P, size] float64: per output index the summed bilinear weights its g samples give every row (column) of the map.
+    Positions `start + p * bsz + (i + 0.5) * bsz / g`, the `< -1 || > size` skip, the clamps at 0 and size - 1 and the weights
+    `l = v - lo`, `1 - l` are computed in `ft`, operation by operation as the kernel writes them; the sums are float64."""
+    m = np.zeros((P, size))
+    if g <= 0:
+        return m
+    p, i = np.arange(P, dtype=ft)[:, None], np.arange(g, dtype=ft)[None, :]
+    v = (start + p * bsz) + ((i + ft(0.5)) * bsz) / ft(g)
+    keep = ~((v < ft(-1.0)) | (v > ft(size)))
+    v = np.where(v <= ft(0.0), ft(0.0), v)
+    lo = np.where(keep, v, 0).astype(np.int64)
+    top = lo >= size - 1
+    lo = np.where(top, size - 1, lo)
+    hi = np.where(top, lo, lo + 1)
+    v = np.where(top, lo.astype(ft), v)
+    l = (v - lo.astype(ft)).astype(ft)
+    h = (ft(1.0) - l).astype(ft)
+    rows = np.broadcast_to(np.arange(P)[:, None], lo.shape)
+    np.add.at(m, (rows[keep], lo[keep]), h[keep].astype(np.float64))
+    np.add.at(m, (rows[keep], hi[keep]), l[keep].astype(np.float64))
+    return m
+
+
+def roi_align_fp64(x, rois, P, scale, sampling_ratio, aligned, geometry=np.float64, magnitude=False):
     """torchvision roi_align restated in float64, separably: per box and axis a dense [P, size] matrix of the summed bilinear
     weights of every sample (positions, the `< -1 || > size` skip, the clamps at 0 and size - 1 as oracle/tv_ops.c), then
-    out[c, p, q] = sum_yx Wy[p, y] * x[c, y, x] * Wx[q, x] / max(gh * gw, 1).  Returns [K, C, P, P] float64."""
+    out[c, p, q] = sum_yx Wy[p, y] * x[c, y, x] * Wx[q, x] / max(gh * gw, 1).  Returns [K, C, P, P] float64.
+
+    geometry=np.float32: the sample positions and the weights are the kernel's own fp32 numbers (csrc/fpn.hip is built without
+    contraction, so one numpy fp32 operation per operation of the source reproduces them); the products and sums stay float64.
+    magnitude=True: also returns sum |w * x| / count per element, the size the rounding bounds scale with."""
     x = np.asarray(x, dtype=np.float64)
-    rois = np.asarray(rois, dtype=np.float64)
     N, C_, H, W = x.shape
     out = np.zeros((len(rois), C_, P, P))
-    off = 0.5 if aligned else 0.0
-    for k, r in enumerate(rois):
+    mag = np.zeros_like(out) if magnitude else None
+    xa = np.abs(x) if magnitude else None
+    for k, r in enumerate(np.asarray(rois)):
         b = int(r[0])
-        sw, sh, ew, eh = (r[1:] * scale - off)
-        rw, rh = ew - sw, eh - sh
-        if not aligned:
-            rw, rh = max(rw, 1.0), max(rh, 1.0)
-        gh = sampling_ratio if sampling_ratio > 0 else int(np.ceil(rh / P))
-        gw = sampling_ratio if sampling_ratio > 0 else int(np.ceil(rw / P))
-        mats = []
-        for start, bsz, g, size in ((sh, rh / P, gh, H), (sw, rw / P, gw, W)):
-            m = np.zeros((P, size))
-            for p in range(P):
-                for i in range(g):
-                    v = start + p * bsz + (i + 0.5) * bsz / g
-                    if v < -1.0 or v > size:
-                        continue
-                    v = max(v, 0.0)
-                    lo = int(v)
-                    if lo >= size - 1:
-                        lo = hi = size - 1
-                        v = float(lo)
-                    else:
-                        hi = lo + 1
-                    m[p, lo] += 1.0 - (v - lo)
-                    m[p, hi] += v - lo
-            mats.append(m)
-        out[k] = np.einsum("py,cyx,qx->cpq", mats[0], x[b], mats[1]) / max(gh * gw, 1)
-    return out
+        sh, sw, bh, bw, gh, gw = roi_geometry(r, P, scale, sampling_ratio, aligned, geometry)
+        wy, wx = axis_weights(sh, bh, gh, H, P, geometry), axis_weights(sw, bw, gw, W, P, geometry)
+        ys, xs = np.nonzero(wy.any(0))[0], np.nonzero(wx.any(0))[0]
+        if len(ys) == 0 or len(xs) == 0:
+            continue
+        y0, y1, x0, x1 = ys[0], ys[-1] + 1, xs[0], xs[-1] + 1
+        for src, dst in ((x, out), (xa, mag)):
+            if src is not None:
+                t = np.tensordot(src[b, :, y0:y1, x0:x1], wx[:, x0:x1], axes=(2, 1))             # [C, y, Q]
+                dst[k] = np.tensordot(wy[:, y0:y1], t, axes=(1, 1)).transpose(1, 0, 2) / max(gh * gw, 1)
+    return (out, mag) if magnitude else out
 
 
 # ---- the library's entry points (device tensors; GPU tests only) ----------------------------------------------------

@@ -15,6 +15,7 @@ TEXTS = (None, "", "0", "00", "1", "2", "8", "9", "A", "x")          # None: uns
 F16, BF16 = L.VK_F16, L.VK_BF16
 ROUTES = ("generic", "ring", "duo", "ws", "gemm4", "panel", "blk")      # VK_ROUTE_* by value (tests/gpu_util.py)
 ATT = ("mfma", "lds", "tiled", "stream")                                # VK_ATT_ROUTE_* by value
+RA = ("sep", "vec", "scalar")                                           # VK_RA_FORM_* by value
 
 
 def conv_route_args(N, H, W, cin, cout, k=1, stride=1, pad=0, dil=1, groups=1, relu=0, cin2=0, res=False, mean=False):
@@ -53,6 +54,7 @@ PER_CALL = {
     "VK_ATTENTION_TILED": ({}, lambda lib: ATT[lib.vk_attention_route(100, 100, 64, BF16, 64, 64, 64, 1, 1)]),
     "VK_BNECK_FUSED": ({}, lambda lib: lib.vk_bottleneck64_eligible(256, 64, 256, 1, 1, 1, 0, 0, 32, 200, 334, F16)),
     "VK_BNECK_ROWS": ({}, lambda lib: lib.vk_bottleneck64_eligible(256, 64, 256, 1, 1, 1, 0, 0, 64, 200, 334, F16)),    # 2.19 GB of res2 map
+    "VK_ROIALIGN_TABLES": ({}, lambda lib: RA[lib.vk_roi_align_form(256, 7, F16)]),                      # the FPN head's shape
 }
 # the texts an atoi switch tells apart, beyond TEXTS
 MORE_TEXTS = {"VK_GEMM4_MINK": ("255", "256", "768", "1025", "-1")}
@@ -84,6 +86,8 @@ EXPECTED = {
     "VK_ATTENTION_TILED":  ("tiled",   "tiled",   "lds",     "lds",     "tiled",   "tiled",   "tiled",   "tiled",   "tiled",   "tiled"),
     "VK_BNECK_FUSED":      (1,         1,         0,         0,         1,         1,         1,         1,         1,         1),
     "VK_BNECK_ROWS":       (1,         1,         0,         0,         1,         1,         1,         1,         1,         1),
+    # set and atoi == 0 takes the tables out, "" and non-numbers included
+    "VK_ROIALIGN_TABLES":  ("sep",     "vec",     "vec",     "vec",     "sep",     "sep",     "sep",     "sep",     "vec",     "vec"),
     # presence alone decides, "" included: (vk_fuse_shortcut, route) per text
     "once":                ("1 1",     "0 0",     "0 0",     "0 0",     "0 0",     "0 0",     "0 0",     "0 0",     "0 0",     "0 0"),
 }

@@ -22,6 +22,7 @@ VK_ACT_NONE, VK_ACT_RELU, VK_ACT_GELU, VK_ACT_TANH = 0, 1, 2, 3
 VK_ROUTE_GENERIC, VK_ROUTE_RING, VK_ROUTE_DUO, VK_ROUTE_WS, VK_ROUTE_GEMM4, VK_ROUTE_PANEL, VK_ROUTE_BLK = range(7)
 VK_ATT_ROUTE_MFMA, VK_ATT_ROUTE_LDS, VK_ATT_ROUTE_TILED, VK_ATT_ROUTE_STREAM = range(4)
 VK_CE_FORM_VEC, VK_CE_FORM_SCALAR = 0, 1
+VK_RA_FORM_SEP, VK_RA_FORM_VEC, VK_RA_FORM_SCALAR = 0, 1, 2
 VK_MAX_ANCHOR_DIM = 8
 VK_MAX_NMS_THRESH = 8
 VK_MAX_IGNOREY = 64
@@ -151,6 +152,7 @@ SIGNATURES = {
     "vk_loss_reduce": (_I, [_P, _P, _P, _I, _I, _F, _P, _P]),
     "vk_loss_total": (_I, [_P, _I, _P, _P]),
     "vk_roi_align": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
+    "vk_roi_align_form": (_I, [_I, _I, _I]),
     "vk_assign_levels": (_I, [_P, _I, _I, _I, _I, _F, _I, _P, _P]),
     "vk_upsample2x_add": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vk_subsample2": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),

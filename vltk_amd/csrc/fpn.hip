@@ -354,7 +354,7 @@ __global__ void relu_copy_kernel(const T *__restrict__ x, T *__restrict__ y, lon
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < total) {
         const float v = (float)x[i];
-        y[i] = (T)(v > 0.f ? v : 0.f);
+        y[i] = (T)(v < 0.f ? 0.f : v);               // as torch.relu: NaN stays NaN, -0.0 stays -0.0
     }
 }
 
@@ -362,7 +362,22 @@ __global__ void relu_copy_kernel(const T *__restrict__ x, T *__restrict__ y, lon
 
 using namespace vk;
 
+static bool ra_float_dt(vk_dtype dt) { return dt == VK_F32 || dt == VK_F16 || dt == VK_BF16; }
+
+// Which of the three RoIAlign kernels a launch runs on; the tables switch is re-read per call.
+static int roi_align_form(int C, int P, vk_dtype dt) {
+    const int vec = 16 / (int)dtype_size(dt);
+    if (C % vec != 0 || C / vec > 256) return VK_RA_FORM_SCALAR;
+    const bool per_sample = env_set("VK_ROIALIGN_TABLES") && env_int("VK_ROIALIGN_TABLES", 1) == 0;
+    return (P <= RA_MAXP && !per_sample) ? VK_RA_FORM_SEP : VK_RA_FORM_VEC;
+}
+
 extern "C" {
+
+int vk_roi_align_form(int C, int P, vk_dtype dt) {
+    if (!ra_float_dt(dt) || C < 1 || P < 1) return -VK_EINVAL;
+    return roi_align_form(C, P, dt);
+}
 
 int vk_roi_align(const void *const *maps, const int32_t *Hs, const int32_t *Ws, const float *scales, int levels, int N, int C,
                  const float *rois, const int32_t *roi_levels, int K, int P, int sampling_ratio, int aligned, void *out, vk_dtype dt,
@@ -372,6 +387,7 @@ int vk_roi_align(const void *const *maps, const int32_t *Hs, const int32_t *Ws, 
                FPN_MAX_LEVELS);
     VK_REQUIRE(N > 0 && C > 0 && P > 0 && K >= 0 && sampling_ratio >= 0, VK_EINVAL, "roi_align: bad sizes");
     if (K == 0) return VK_OK;
+    VK_REQUIRE(ra_float_dt(dt), VK_EINVAL, "roi_align: dtype must be f32, f16 or bf16");      // roi_align_form divides by the dtype's size
     PyramidArgs py;
     memset(&py, 0, sizeof(py));
     py.levels = levels;
@@ -382,10 +398,9 @@ int vk_roi_align(const void *const *maps, const int32_t *Hs, const int32_t *Ws, 
         py.W[i] = Ws[i];
         py.scale[i] = scales[i];
     }
-    const int vec = 16 / (int)dtype_size(dt);
-    if (C % vec == 0 && C / vec <= 256) {            // one workgroup per RoI, 16-byte lanes (the FPN case: C = 256)
-        static const bool per_sample = env_set("VK_ROIALIGN_TABLES") && env_int("VK_ROIALIGN_TABLES", 1) == 0;
-        if (P <= RA_MAXP && !per_sample) {
+    const int vec = 16 / (int)dtype_size(dt), form = roi_align_form(C, P, dt);
+    if (form != VK_RA_FORM_SCALAR) {                 // one workgroup per RoI, 16-byte lanes (the FPN case: C = 256)
+        if (form == VK_RA_FORM_SEP) {
             int groups = 256 / (C / vec);
             while ((P * P) % groups) --groups;       // no idle group in the last pass (P = 7, 32 lanes per bin: 7 groups)
             VK_DT_SWITCH(dt, "roi_align",

@@ -70,6 +70,10 @@ extern "C" int vk_preprocess(const float *const *raw_dev_ptrs_host, const int32_
     VK_REQUIRE(raw_dev_ptrs_host && raw_hw_host && new_hw_host && mean3_host && std3_host && out_nchw_dev, VK_EINVAL,
                "preprocess: null argument");
     VK_REQUIRE(N >= 1 && Hmax >= 1 && Wmax >= 1, VK_EINVAL, "preprocess: empty batch");
+    for (int i = 0; i < N; ++i)                      // every image before the first launch: a refusal leaves `out` untouched
+        VK_REQUIRE(raw_dev_ptrs_host[i] && raw_hw_host[2 * i] >= 1 && raw_hw_host[2 * i + 1] >= 1 && new_hw_host[2 * i] >= 1 &&
+                       new_hw_host[2 * i + 1] >= 1 && new_hw_host[2 * i] <= Hmax && new_hw_host[2 * i + 1] <= Wmax,
+                   VK_EINVAL, "preprocess: bad geometry for image %d", i);
     for (int base = 0; base < N; base += PRE_MAX_IMAGES) {
         PreArgs a;
         memset(&a, 0, sizeof(a));
@@ -80,8 +84,6 @@ extern "C" int vk_preprocess(const float *const *raw_dev_ptrs_host, const int32_
             a.raw_w[i] = raw_hw_host[2 * (base + i) + 1];
             a.new_h[i] = new_hw_host[2 * (base + i)];
             a.new_w[i] = new_hw_host[2 * (base + i) + 1];
-            VK_REQUIRE(a.raw[i] && a.raw_h[i] >= 1 && a.raw_w[i] >= 1 && a.new_h[i] >= 1 && a.new_w[i] >= 1 &&
-                           a.new_h[i] <= Hmax && a.new_w[i] <= Wmax, VK_EINVAL, "preprocess: bad geometry for image %d", base + i);
         }
         a.Hmax = Hmax;
         a.Wmax = Wmax;
