@@ -394,7 +394,12 @@ int vk_pack_conv_weight(const float *w_oihw_host, const float *bn_host, const fl
                         void *w_packed_host, float *bias_packed_host);
 
 /* conv + folded-BN bias (+ residual) (+ ReLU)  <- Conv2d.forward frcnn.py:794-822,
- * BottleneckBlock.forward :963-979.  x [N,H,W,cin] (dt), residual/y [N*Ho*Wo, ldy]. */
+ * BottleneckBlock.forward :963-979.  x [N,H,W,cin] (dt), residual/y [N*Ho*Wo, ldy].  `relu` is a vk_act; a value outside
+ * 0..3 is VK_EINVAL before any launch (vk_conv_route answers the same).
+ * What a launch writes (vk_linear too): rows 0 .. N*Ho*Wo - 1, columns 0 .. round_up(cout, 8) - 1 of y.  The columns
+ * cout .. round_up(cout, 8) - 1 are PADS: they are written, with unspecified contents.  Columns from round_up(cout, 8) up to
+ * ldy, rows past the last, and memory in front of y are left alone; rows of the residual past the last are not read into
+ * any output. */
 int vk_conv2d(const void *x, int N, int H, int W, int cin,
               const void *w_packed, const float *bias_packed, const void *residual,
               void *y, int cout, int ldy, int kh, int kw, int stride, int pad, int dil, int groups,
@@ -478,7 +483,9 @@ int vk_conv1x1_meanpool(const void *x, int N, int HW, int cin, const void *w_pac
  * vltk/legacy/legacy_train.py:30-39; restated from transformers/models/lxmert/modeling_lxmert.py v5.15) ---- */
 
 /* nn.Linear (+ residual) (+ activation): y[M, ldy] = act(x[M,K] . W^T + bias + residual).  W packed by
- * vk_pack_conv_weight(w [N,K,1,1], NULL, bias, ...); K a whole number of 128-byte K-tiles; dt f32 | f16 | bf16. */
+ * vk_pack_conv_weight(w [N,K,1,1], NULL, bias, ...); K a whole number of 128-byte K-tiles; dt f32 | f16 | bf16.  The sum and
+ * the activation are fp32 and the result is rounded once to out_dt (dt or f32).  act is a vk_act: outside 0..3 VK_EINVAL.
+ * Written columns and pads: as vk_conv2d. */
 int vk_linear(const void *x, long M, int K, const void *w_packed, const float *bias_packed, const void *residual,
               void *y, int N, int ldy, int act, vk_dtype dt, vk_dtype out_dt, void *stream);
 /* y = scale * LayerNorm(x) (+ y when accumulate): LxmertAttentionOutput / LxmertOutput :269-342 (eps 1e-12),

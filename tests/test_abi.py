@@ -230,17 +230,20 @@ def test_conv_routes_resnet101_c4(lib, dt, monkeypatch):
 
 def test_gpu_tests_run_the_kernels_they_name(lib, monkeypatch):
     """Every launch of the GPU conv tests that names its kernel (`expect_route=` in tests/test_gpu_stages.py,
-    test_gpu_bneck_fused.py, test_gpu_lxmert.py::test_linear, test_gpu_conv_exact.py), asked of the dispatcher here, under that
-    run's environment: no A/B test compares a kernel with itself, and each table covers every kernel its test is about."""
+    test_gpu_bneck_fused.py, test_gpu_lxmert.py::test_linear, test_gpu_conv_exact.py, test_gpu_linear.py), asked of the dispatcher
+    here, under that run's environment: no A/B test compares a kernel with itself, and each table covers every kernel its test is about."""
     import gpu_util as G
     import test_gpu_bneck_fused
     import test_gpu_conv_exact
+    import test_gpu_linear
     import test_gpu_lxmert
     import test_gpu_stages
-    seen = {}
-    for mod in (test_gpu_stages, test_gpu_bneck_fused, test_gpu_lxmert, test_gpu_conv_exact):
+    seen, duo_builds = {}, set()
+    for mod in (test_gpu_stages, test_gpu_bneck_fused, test_gpu_lxmert, test_gpu_conv_exact, test_gpu_linear):
         n = 0
         for label, env, geom, route in mod.route_plan():
+            if mod is test_gpu_linear and route == "duo":
+                duo_builds.add((geom["dt"], min(geom["relu"], 2) // 2 * 2))      # the GELU build, or the one of act <= 1
             _clear_switches(monkeypatch)
             for k, v in env.items():
                 if v is not None:
@@ -251,6 +254,9 @@ def test_gpu_tests_run_the_kernels_they_name(lib, monkeypatch):
         assert n > 0
     assert seen["test_gpu_stages"] == set(G.ROUTES) and seen["test_gpu_conv_exact"] == set(G.ROUTES)
     assert seen["test_gpu_lxmert"] == {"generic", "duo"}
+    # the epilogue tests: both kernels vk_linear runs on, and both bf16 builds of the two-per-CU kernel (GELU; act <= 1) beside the f16 one
+    assert seen["test_gpu_linear"] == {"generic", "duo"}
+    assert duo_builds == {(L.VK_BF16, 2), (L.VK_BF16, 0), (L.VK_F16, 0)}
 
 
 def test_conv_route_refuses_what_the_launch_refuses(lib):
@@ -262,6 +268,12 @@ def test_conv_route_refuses_what_the_launch_refuses(lib):
     with pytest.raises(ValueError, match="fused-mean"):
         G.conv_route(4, 1, 64, 512, 512, mean=True, res=True)       # fewer than 128 rows per image
     assert lib.vk_conv_route(0, 8, 8, 64, 0, 0, 0, 64, 64, 1, 1, 1, 0, 1, 1, 0, L.VK_F16, L.VK_F16) == -L.VK_EINVAL
+    for act in (4, -1):                                     # an activation no epilogue knows, on every route's geometry
+        with pytest.raises(ValueError, match="activation"):
+            G.conv_route(1, 1, 2600, 768, 768, relu=act, dt=L.VK_BF16)
+        with pytest.raises(ValueError, match="activation"):
+            G.conv_route(4, 14, 14, 128, 256, k=3, pad=1, relu=act)
+    assert G.conv_route(1, 1, 2600, 768, 768, relu=3, dt=L.VK_BF16) == "generic"
 
 
 def test_every_pinned_launch_states_its_route():

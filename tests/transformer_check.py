@@ -1,7 +1,8 @@
-"""The per-element checker of the attention and LayerNorm op tests: float64 references computed from the
-STORED (already rounded) operands, and for every output element a bound derived from the kernels' rounding points.  Nothing here
-touches a GPU; tests/test_transformer_check_host.py proves on the CPU that correct arithmetic fits the bounds and that wrong
-arithmetic (a dropped key, swapped V rows, a wrong divisor) does not.
+"""The per-element checker of the attention, LayerNorm and linear-epilogue op tests: float64 references
+computed from the STORED (already rounded) operands, and for every output element a bound derived from the kernels' rounding
+points.  Nothing here needs a GPU; tests/test_transformer_check_host.py and tests/test_linear_check_host.py prove on the CPU that
+correct arithmetic fits the bounds and that wrong arithmetic (a dropped key, swapped V rows, a wrong divisor, a tanh-approximation
+GELU, the activation before the residual) does not.
 
 Why not max|a - b| / max|b|: one large reference element (a one-hot row returns a whole V element, about 4) sets the scale for
 rows that average a hundred keys (about 0.1), so a bf16 kernel may be 0.03 off on an output of 0.1 and still pass.
@@ -83,6 +84,81 @@ def layernorm_bound(r, td):
     accumulate are a few more roundings of the running value, bounded by |ref| and the terms before it."""
     K = r["C"] / 64.0 + 16
     return U[td] * r["ref"].abs() + K * U32 * (r["gamma"].abs() * (r["xmax"] * r["rstd"] + r["xh"].abs()) * abs(r["scale"]) + r["ref"].abs())
+
+
+# The device math library's allowance, in ulps of the result, for erff and tanhf (the one figure of linear_bound that is not derived:
+# no accuracy statement for them ships with the toolchain).  Measured on an MI355X with torch.erf / torch.tanh in fp32 on the device
+# against float64 on the host, over z on the 2^-7 grid of [-10, 10] (erf at z / sqrt(2)); E = twice the worst error seen, rounded
+# up to a whole number, and at least 2.  Measured (tests/test_gpu_linear.py::test_math_library_allowance prints them and holds
+# the constants to the rule): erf 1.163 ulp worst, tanh 0.929 ulp worst.
+E_ERF = 3                                                   # ceil(2 * 1.163)
+E_TANH = 2                                                  # ceil(2 * 0.929)
+GELU_SLOPE = 1.13                                           # sup |GELU'|: 1.1289, at z = sqrt 2
+SQRT2 = float(np.sqrt(2.0))
+
+
+def linear_reference(x, w, bias, res, act, exact):
+    """float64 act(x . w^T + bias + res) from the stored operands: x [M, K], w [N, K] (any dtype), bias [N], res [M, N] or None.
+    act: 0 none | 1 ReLU | 2 GELU (erf form) | 3 tanh.  Returns a dict: ref, z (the pre-activation) and err_z, the bound on the
+    kernel's own error in z: 0 where the data makes z exact (`exact`), else (K + 2) 2^-24 (sum_k |x_k w_k| + |bias| + |res|), a
+    K-term fp32 sum in any order and the two additions.  The products run on the caller's device (a float64 GEMM); the result is
+    on the CPU."""
+    xd, wd = x.double(), w.to(x.device).double()
+    b = bias.to(x.device).double()
+    z = xd @ wd.t() + b
+    if res is not None:
+        z = z + res.to(x.device).double()
+    if exact:
+        err_z = torch.zeros((), dtype=torch.float64).expand(z.shape)
+    else:
+        S = xd.abs() @ wd.abs().t() + b.abs()
+        if res is not None:
+            S = S + res.to(x.device).double().abs()
+        err_z = ((x.shape[1] + 2) * U32 * S).cpu()
+    z = z.cpu()
+    ref = {0: lambda t: t, 1: lambda t: t.clamp_min(0.0), 2: lambda t: 0.5 * t * torch.erfc(-t / SQRT2), 3: torch.tanh}[act](z)
+    return dict(ref=ref, z=z, err_z=err_z, act=act)
+
+
+def linear_bound(r, out_td):
+    """Per element, with t = z / sqrt 2, e = erf(t), phi = (2 / sqrt pi) exp(-t^2), E the math library's allowance in ulps:
+
+        none, ReLU   err_z
+        tanh         E 2^-23 |ref| + err_z
+        GELU         1/2 |z| (E 2^-23 |e| + 2 2^-24 |t| phi + 2^-24 |1 + e|) + 2^-24 |ref| + 1.13 err_z
+        16-bit out   + u |ref|     [fp16: + 2^-25]
+
+    GELU in the kernel is 0.5f * z * (1.0f + erff(z * 0.70710678f)): erff returns e within E ulps (2^-23 |e| each); its argument
+    carries the rounding of the product and of the constant, 2 2^-24 |t| in all, which erf' = phi turns into 2 2^-24 |t| phi; the
+    sum 1 + e is rounded once, 2^-24 |1 + e| (where erf has saturated it cancels to zero and only E 2^-23 is left: the planted
+    tails); the factor 1/2 |z| carries these to the result, whose last product rounds once more, 2^-24 |ref| (0.5f * z is exact).
+    err_z reaches the result through the slope: at most 1 for ReLU and tanh, 1.13 = sup |GELU'|.  The output type rounds once,
+    u |ref|; fp16's subnormal spacing 2^-24 is invisible to that term: half of it.  An fp32 output has no storage term: the last
+    fp32 operation IS the output."""
+    z, ref, err_z = r["z"], r["ref"], r["err_z"]
+    if r["act"] in (0, 1):
+        bound = err_z.clone()
+    elif r["act"] == 3:
+        bound = E_TANH * 2.0 ** -23 * ref.abs() + err_z
+    else:
+        t = z / SQRT2
+        e = torch.erf(t)
+        phi = 2.0 / np.sqrt(np.pi) * torch.exp(-t * t)
+        one_plus_e = torch.erfc(-t)
+        bound = 0.5 * z.abs() * (E_ERF * 2.0 ** -23 * e.abs() + 2 * U32 * t.abs() * phi + U32 * one_plus_e) + U32 * ref.abs() + GELU_SLOPE * err_z
+    if out_td != torch.float32:
+        bound = bound + U[out_td] * ref.abs()
+        if out_td == torch.float16:
+            bound = bound + 2.0 ** -25
+    return bound
+
+
+def ulp_error(got32, want64):
+    """Worst |got - want| in ulps of the fp32 result (the spacing of fp32 numbers at |want|; at least the smallest normal's):
+    how E_ERF and E_TANH are measured."""
+    want64 = want64.double()
+    spacing = 2.0 ** (torch.floor(torch.log2(want64.abs().clamp_min(2.0 ** -126))) - 23)
+    return float(((got32.double() - want64).abs() / spacing).max())
 
 
 def worst_ratio(out, ref, bound):

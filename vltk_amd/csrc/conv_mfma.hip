@@ -353,8 +353,13 @@ static int launch_t(const ConvK &k, hipStream_t stream) {
 // Which kernel takes the layer: the dispatcher's one decision (host only: eligibility rules and their A/B switches, re-read per
 // call).  launch_conv switches on it and vk_conv_route (stage_api.hip) returns it, so the query cannot drift from the launch.
 // Order: fused-mean and dual-source forms first; then block -> panel -> weight-stationary -> four-wave GEMM -> two-per-CU -> ring ->
-// generic.  A form no kernel takes is -VK_EINVAL with the error text set.
+// generic.  A form no kernel takes is -VK_EINVAL with the error text set; so is an activation no epilogue knows (the kernels
+// compare `relu` with 1, 2 and 3 and would run anything else as "none").
 int conv_route(const ConvArgs &a) {
+    if (a.relu < 0 || a.relu > 3) {
+        set_error("conv: activation %d is not one of 0 (none), 1 (ReLU), 2 (GELU, erf form), 3 (tanh)", a.relu);
+        return -VK_EINVAL;
+    }
     if (a.pool_part) {
         if (!(conv_duo_pool_ok(a) && (!a.x2 || conv_duo_dual_ok(a)) && a.relu <= 1 && a.ldy == a.Cout)) {
             set_error("conv: the fused-mean form is 1x1, stride 1, f16, Cout %% 256 == 0, Ho*Wo >= 128");
