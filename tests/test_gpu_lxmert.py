@@ -239,6 +239,17 @@ def test_graph_replay_matches_eager(g):
     for a, b in zip(got2, eager2):
         assert torch.equal(a, b)
     assert not torch.equal(eager2[0], eager[0])
+    # a replay that differs from the captured call in None or shape is refused, and leaves the captured buffers usable
+    with pytest.raises(ValueError, match="visual_attention_mask differs from the captured call"):
+        replay(ids, f, p, attention_mask=am)
+    with pytest.raises(ValueError, match="token_type_ids differs from the captured call"):
+        replay(ids, f, p, attention_mask=am, visual_attention_mask=vm, token_type_ids=torch.zeros_like(ids))
+    with pytest.raises(ValueError, match="attention_mask differs from the captured call"):
+        replay(ids, f, p, attention_mask=am[:1], visual_attention_mask=vm)
+    got3 = replay(ids, f, p, attention_mask=am, visual_attention_mask=vm)
+    torch.cuda.synchronize()
+    for a, b in zip(got3, eager):
+        assert torch.equal(a, b)
 
 
 @pytest.mark.parametrize("precision,tol", [("fp32", 1e-3), ("bf16", 4e-2)])

@@ -1,7 +1,8 @@
-"""What the encoders of this package share (`LxmertEncoder` in lxmert.py, `VisualBertModel` in visualbert.py, `ViTModel` in vit.py):
-the draw of the synthetic weights, the parameter spec of a BERT layer, and `BertOps`: the packed weights, the ops over the C ABI,
-the BERT layer built from them, the rule that picks an attention entry point and the graph-capture sequence.  All arithmetic
-runs in `libvltk_hip.so`; torch only owns the device buffers.  No CPU fallback.
+"""What the encoders of this package share (`LxmertEncoder` in lxmert.py, `VisualBertModel` in visualbert.py, `ViTModel` in vit.py,
+`LayoutLMModel` in layoutlm.py): the draw of the synthetic weights, the parameter spec of a BERT layer, the load of a head wrapper's
+state dict, and `BertOps`: the packed weights, the ops over the C ABI, the BERT layer built from them, the rule that picks an
+attention entry point, and the front between a caller and `_forward` (check -> forward -> synchronize; capture and replay).  All
+arithmetic runs in `libvltk_hip.so`; torch only owns the device buffers.  No CPU fallback.
 """
 import zlib
 
@@ -14,10 +15,15 @@ from .layers import DTYPES, pack, stream
 LN_EPS = 1e-12
 
 
+def is_gamma(name):
+    """Whether a state-dict name is a LayerNorm's weight: spelled out, or the LayerNorm at index 2 of the answer head's nn.Sequential."""
+    return "LayerNorm.weight" in name or "layer_norm.weight" in name or name.endswith("logit_fc.2.weight")
+
+
 def seeded_tensor(name, shape, seed):
     """One tensor of the synthetic state dicts: its own generator, keyed by the seed and the tensor's name."""
     g = np.random.Generator(np.random.PCG64([seed, zlib.crc32(name.encode())]))
-    if "LayerNorm.weight" in name or "layer_norm.weight" in name:
+    if is_gamma(name):
         v = g.uniform(0.5, 1.5, shape)
     else:
         v = g.standard_normal(shape) * 0.05
@@ -26,6 +32,16 @@ def seeded_tensor(name, shape, seed):
 
 def to_numpy(sd):
     return {k: (v.detach().cpu().float().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32)) for k, v in sd.items()}
+
+
+def host_array(a):
+    """A tensor (read back from its device) or anything array-like -> numpy, for the checks that need an input's values."""
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def require_gelu(cfg):
+    if cfg["hidden_act"] != "gelu":
+        raise NotImplementedError(f"hidden_act '{cfg['hidden_act']}': the GEMM epilogue has the erf GELU only")
 
 
 def additive_mask(m, device):
@@ -75,8 +91,54 @@ def bert_layer_spec(p, H, I):
             [(p + ".intermediate.dense.weight", (I, H)), (p + ".intermediate.dense.bias", (I,))] + dense_ln_spec(p + ".output", I, H))
 
 
-class BertOps:
-    """The base of the three encoders: the packed weights, the ops over the C ABI and the BERT layer built from them."""
+# ---- replay against a captured call: plain functions of (names, static, new), so they run on CPU tensors ----------------------------
+def check_against_captured(names, static, new):
+    """`new`, the inputs of a replay, against `static`, the buffers of the captured call: None where that call had None, a tensor
+    of the same shape where it had a tensor.  `Tensor.copy_` alone would broadcast [1, L] into a [B, L] buffer."""
+    for name, s, n in zip(names, static, new):
+        if (s is None) != (n is None) or (s is not None and tuple(s.shape) != tuple(n.shape)):
+            raise ValueError(f"replay: {name} differs from the captured call (None or another shape)")
+
+
+def refill(static, new):
+    """The new values into the captured buffers; what was None at capture stays None."""
+    for s, n in zip(static, new):
+        if s is not None:
+            s.copy_(n)
+
+
+class Model:
+    """What an encoder and a head wrapper around one have in common as objects."""
+
+    def eval(self):
+        return self
+
+    def _check_state_dict(self, sd, want, strict):
+        """Strict load: no missing and no unexpected key; always: the shape of every tensor the model takes."""
+        if strict:
+            missing, extra = sorted(set(want) - set(sd)), sorted(set(sd) - set(want))
+            if missing or extra:
+                raise RuntimeError(f"{type(self).__name__}.load_state_dict: missing {missing[:4]} unexpected {extra[:4]}")
+        for k, shp in want.items():
+            if tuple(sd[k].shape) != tuple(shp):
+                raise RuntimeError(f"weight '{k}' has shape {tuple(sd[k].shape)}, expected {tuple(shp)}")
+
+    def _load_with_encoder(self, enc, prefix, spec, sd, strict, rekey=None):
+        """A head wrapper's `load_state_dict` up to its own tensors: numpy, `rekey(sd)` where key names need work (ViT's hub-era
+        names, the tied decoder of the pre-training heads), the strict check of keys and shapes against the wrapper's whole
+        `spec`, then the tensors under `prefix` into the encoder.  -> the dict, for the wrapper's own `_load_lin` / `_load_ln`."""
+        sd = to_numpy(sd)
+        if rekey is not None:
+            sd = rekey(sd)
+        self._check_state_dict(sd, dict(spec), strict)
+        enc.load_state_dict({k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}, strict)
+        return sd
+
+
+class BertOps(Model):
+    """The base of the encoders: the packed weights, the ops over the C ABI, the BERT layer built from them and the front."""
+
+    _INPUTS = ()                             # the tensors a call takes, in the order of `__call__`, `_check`, `_forward` and `_embed`
 
     def __init__(self, config, precision="bf16", device="cuda:0"):
         if not torch.cuda.is_available():
@@ -99,16 +161,6 @@ class BertOps:
         wk[:, :K] = w
         wp, bp = pack(wk, self.dt, bias=b)
         return torch.from_numpy(wp).to(self.device), torch.from_numpy(bp).to(self.device), N, Kp
-
-    def _check_state_dict(self, sd, want, strict):
-        """Strict load: no missing and no unexpected key; always: the shape of every tensor the model takes."""
-        if strict:
-            missing, extra = sorted(set(want) - set(sd)), sorted(set(sd) - set(want))
-            if missing or extra:
-                raise RuntimeError(f"{type(self).__name__}.load_state_dict: missing {missing[:4]} unexpected {extra[:4]}")
-        for k, shp in want.items():
-            if tuple(sd[k].shape) != tuple(shp):
-                raise RuntimeError(f"weight '{k}' has shape {tuple(sd[k].shape)}, expected {tuple(shp)}")
 
     def _load_lin(self, sd, name, *parts):   # one GEMM for several nn.Linear applied to the same input (rows concatenated)
         w = np.concatenate([sd[p + ".weight"] for p in parts], 0)
@@ -135,9 +187,6 @@ class BertOps:
     def _require_loaded(self):
         if not self._loaded:
             raise RuntimeError(f"{type(self).__name__}: load_state_dict() first")
-
-    def eval(self):
-        return self
 
     # ---- ops (each one call into the C ABI) ----------------------------------------------------------------------
     def _linear(self, x, name, act=L.VK_ACT_NONE, residual=None):
@@ -186,6 +235,15 @@ class BertOps:
                mask.data_ptr() if mask is not None else None, out.data_ptr(), H, B, heads, Lq, Lk, H // heads, self.dt, stream(self.device))
         return out
 
+    def _gather_rows(self, x, idx):
+        """Rows `idx` (int32, on the device) of contiguous `x [M, C]` -> [len(idx), C].  The kernel copies 16-byte lanes."""
+        n, Cc = idx.numel(), x.shape[1]
+        if Cc * self.es % 16:
+            raise ValueError(f"gather of rows of {Cc} elements: their size must be a multiple of 16 bytes")
+        rows = torch.empty((n, Cc), dtype=self.tdt, device=self.device)
+        L.call("vk_gather_rows", x.data_ptr(), idx.data_ptr(), n, Cc * self.es, rows.data_ptr(), stream(self.device))
+        return rows
+
     # ---- layers (modeling_lxmert.py) -----------------------------------------------------------------------------
     def _self_att_block(self, p, x, mask, B, Lx):       # LxmertSelfAttentionLayer :298-316
         H = self.cfg["hidden_size"]
@@ -211,7 +269,37 @@ class BertOps:
                L.VK_ACT_TANH, self.dt, self.dt, stream(self.device))
         return pooled
 
-    # ---- graph capture -------------------------------------------------------------------------------------------------
+    # ---- the front: what stands between a caller and `_forward` --------------------------------------------------------------
+    # An encoder supplies `_INPUTS`, `_check(*inputs, **options)` (host-side: everything that needs the VALUES of an input, so it
+    # runs before a launch or a capture, never inside one), `_forward(*inputs)`, and where it has them `_embed` and `_before_capture`.
+    def _run(self, forward, inputs, **options):
+        """One eager call, of the encoder or of a head over it: check -> `forward(*inputs)` -> synchronize."""
+        self._check(*inputs, **options)
+        out = forward(*inputs)
+        torch.cuda.synchronize(self.device)
+        return out
+
+    def _before_capture(self, *inputs):
+        """Host work that a forward of these inputs does once and keeps (ViT: the position table of the grid)."""
+
+    def _capture_inputs(self, inputs, **options):
+        """Capture one forward for the SHAPES of `inputs` into a HIP graph -> `run(new)`: refuses inputs that differ from the
+        captured call's in None or shape, repeats the host check, copies them into the captured buffers, launches the graph and
+        returns the (static) output tensors.  An input that was None at capture stays at its default."""
+        self._check(*inputs, **options)
+        self._require_loaded()
+        self._before_capture(*inputs)
+        static = [None if a is None else a.to(self.device).clone() for a in inputs]
+        graph, outs = self._capture(self._forward, static)
+
+        def run(new):
+            check_against_captured(self._INPUTS, static, new)
+            self._check(*new, **options)
+            refill(static, new)
+            graph.replay()
+            return outs
+        return run
+
     def _capture(self, forward, static_inputs):
         """`forward(*static_inputs)` once on a side stream (one-time attribute / lazy-init calls must not be captured), then
         captured into a HIP graph -> (graph, the static output tensors)."""

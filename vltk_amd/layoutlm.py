@@ -19,7 +19,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .bert_ops import LN_EPS, BertOps, additive_mask, bert_layer_spec, check_text_inputs, seeded_tensor, to_numpy
+from .bert_ops import LN_EPS, BertOps, Model, additive_mask, bert_layer_spec, check_text_inputs, host_array, require_gelu, seeded_tensor, \
+    to_numpy
 from .layers import stream
 
 DEFAULT_CONFIG = dict(vocab_size=30522, hidden_size=768, num_attention_heads=12, num_hidden_layers=12, intermediate_size=3072,
@@ -36,8 +37,7 @@ def layoutlm_config(**kw):
     """transformers' `LayoutLMConfig` defaults."""
     cfg = dict(DEFAULT_CONFIG)
     cfg.update(kw)
-    if cfg["hidden_act"] != "gelu":
-        raise NotImplementedError(f"hidden_act '{cfg['hidden_act']}': the GEMM epilogue has the erf GELU only")
+    require_gelu(cfg)
     assert cfg["hidden_size"] % cfg["num_attention_heads"] == 0
     return cfg
 
@@ -75,17 +75,13 @@ def make_layoutlm_head_state_dict(cfg, head, num_labels, seed=0):
     return sd
 
 
-def _host(a):
-    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-
-
 def check_bbox(bbox, B, Lt, max_2d):
     """`bbox [B, L, 4]` (x0, y0, x1, y1): integer, every coordinate in [0, max_2d), x1 >= x0 and y1 >= y0.  Host-side (a device
     tensor is read back), so it runs before a launch or a graph capture, never inside one.  transformers raises this IndexError
     for a coordinate past its table; a negative extent would index the h / w table from its end there, which is refused here."""
     if bbox is None:
         return
-    b = _host(bbox)
+    b = host_array(bbox)
     if b.shape != (B, Lt, 4) or not np.issubdtype(b.dtype, np.integer):
         raise ValueError(f"bbox must be an integer [B={B}, L={Lt}, 4] array, got {b.dtype} {b.shape}")
     if b.min() < 0 or b.max() >= max_2d:
@@ -158,41 +154,21 @@ class LayoutLMModel(BertOps):
             raise ValueError(f"attention_mask must be {(B, Lt)}, got {tuple(attention_mask.shape)}")
 
     def __call__(self, input_ids, bbox=None, attention_mask=None, token_type_ids=None):
-        args = (input_ids, bbox, attention_mask, token_type_ids)
-        self._check(*args)
-        out = self._forward(*args)
-        torch.cuda.synchronize(self.device)
-        return out
+        return self._run(self._forward, (input_ids, bbox, attention_mask, token_type_ids))
 
     def capture(self, input_ids, bbox=None, attention_mask=None, token_type_ids=None):
         """Capture one forward for these input SHAPES into a HIP graph.  Returns `replay(...)` with the model's signature, which
         checks the new inputs on the host, copies them into the captured buffers, launches the graph and returns the (static)
         output tensors.  An input given as None at capture stays at its default."""
-        dev = self.device
-        args = (input_ids, bbox, attention_mask, token_type_ids)
-        self._check(*args)
-        static = [None if a is None else a.to(dev).clone() for a in args]
-        graph, outs = self._capture(self._forward, static)
+        run = self._capture_inputs((input_ids, bbox, attention_mask, token_type_ids))
 
         def replay(input_ids, bbox=None, attention_mask=None, token_type_ids=None):
-            new = (input_ids, bbox, attention_mask, token_type_ids)
-            for name, s, n in zip(self._INPUTS, static, new):
-                if (s is None) != (n is None) or (s is not None and tuple(s.shape) != tuple(n.shape)):
-                    raise ValueError(f"replay: {name} differs from the captured call (None or another shape)")
-            self._check(*new)
-            for s, n in zip(static, new):
-                if s is not None:
-                    s.copy_(n)
-            graph.replay()
-            return outs
+            return run((input_ids, bbox, attention_mask, token_type_ids))
         return replay
 
     def embeddings(self, input_ids, bbox=None, attention_mask=None, token_type_ids=None):
         """The embedding stage alone: what transformers' `model.embeddings` returns, [B, L, H]."""
-        args = (input_ids, bbox, attention_mask, token_type_ids)
-        self._check(*args)
-        x, _ = self._embed(*args)
-        torch.cuda.synchronize(self.device)
+        x, _ = self._run(self._embed, (input_ids, bbox, attention_mask, token_type_ids))
         return x.view(input_ids.shape[0], -1, self.cfg["hidden_size"])
 
     @torch.no_grad()
@@ -230,7 +206,7 @@ class LayoutLMModel(BertOps):
         return x.view(B, Lt, self.cfg["hidden_size"]), self._pooler(x, B, Lt)
 
 
-class _Head:
+class _Head(Model):
     """What the three heads share: the whole model under the `layoutlm.` prefix and one nn.Linear on top of it."""
 
     _HEAD = "classifier"
@@ -240,14 +216,9 @@ class _Head:
         self.num_labels = int(num_labels)
 
     def load_state_dict(self, sd, strict=True):
-        sd = to_numpy(sd)
         enc = self.layoutlm
-        enc._check_state_dict(sd, dict(layoutlm_head_param_spec(enc.cfg, self._HEAD, self.num_labels)), strict)
-        enc.load_state_dict({k[len("layoutlm."):]: v for k, v in sd.items() if k.startswith("layoutlm.")}, strict)
+        sd = self._load_with_encoder(enc, "layoutlm.", layoutlm_head_param_spec(enc.cfg, self._HEAD, self.num_labels), sd, strict)
         enc._load_lin(sd, self._HEAD, self._HEAD)
-        return self
-
-    def eval(self):
         return self
 
 
@@ -265,10 +236,7 @@ class LayoutLMForTokenClassification(_Head):
     @torch.no_grad()
     def __call__(self, input_ids, bbox=None, attention_mask=None, token_type_ids=None):
         enc = self.layoutlm
-        args = (input_ids, bbox, attention_mask, token_type_ids)
-        enc._check(*args)
-        logits = enc._linear(enc._encode(*args), "classifier")
-        torch.cuda.synchronize(enc.device)
+        logits = enc._run(lambda *inputs: enc._linear(enc._encode(*inputs), "classifier"), (input_ids, bbox, attention_mask, token_type_ids))
         return logits.view(input_ids.shape[0], input_ids.shape[1], self.num_labels)
 
     @torch.no_grad()
@@ -307,11 +275,8 @@ class LayoutLMForQuestionAnswering(_Head):
 
     @torch.no_grad()
     def __call__(self, input_ids, bbox=None, attention_mask=None, token_type_ids=None):
-        enc = self.layoutlm
-        args = (input_ids, bbox, attention_mask, token_type_ids)
-        enc._check(*args)
-        logits = enc._linear(enc._encode(*args), "qa_outputs")       # [B * L, 2], rows as far apart as the GEMM pads them
-        torch.cuda.synchronize(enc.device)
+        enc = self.layoutlm                                           # logits [B * L, 2], rows as far apart as the GEMM pads them
+        logits = enc._run(lambda *inputs: enc._linear(enc._encode(*inputs), "qa_outputs"), (input_ids, bbox, attention_mask, token_type_ids))
         B, Lt = input_ids.shape
         return logits[:, 0].view(B, Lt), logits[:, 1].view(B, Lt)
 
@@ -347,9 +312,4 @@ class LayoutLMForSequenceClassification(_Head):
     @torch.no_grad()
     def __call__(self, input_ids, bbox=None, attention_mask=None, token_type_ids=None):
         enc = self.layoutlm
-        args = (input_ids, bbox, attention_mask, token_type_ids)
-        enc._check(*args)
-        _, pooled = enc._forward(*args)
-        logits = enc._linear(pooled, "classifier")
-        torch.cuda.synchronize(enc.device)
-        return logits
+        return enc._run(lambda *inputs: enc._linear(enc._forward(*inputs)[1], "classifier"), (input_ids, bbox, attention_mask, token_type_ids))

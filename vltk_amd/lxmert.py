@@ -10,14 +10,12 @@ attention, embedding kernels); torch only owns the device buffers.  No CPU fallb
 `LxmertForQuestionAnswering` is here too; the pre-training heads and their losses (`LxmertForPreTraining`) are in
 lxmert_pretrain.py, which shares the answer head and the cross-entropy helpers below with it.
 """
-import zlib
-
 import numpy as np
 import torch
 
 from . import _lib as L
-from .bert_ops import LN_EPS, BertOps, additive_mask, attention_spec, bert_layer_spec, check_text_inputs, dense_ln_spec, seeded_tensor, \
-    to_numpy
+from .bert_ops import LN_EPS, BertOps, Model, additive_mask, attention_spec, bert_layer_spec, check_text_inputs, dense_ln_spec, host_array, \
+    seeded_tensor, to_numpy
 from .layers import stream
 
 DEFAULT_CONFIG = dict(vocab_size=30522, hidden_size=768, num_attention_heads=12, intermediate_size=3072, l_layers=9, x_layers=5,
@@ -69,8 +67,7 @@ def lxmert_qa_param_spec(cfg, num_qa_labels):
 def make_lxmert_qa_state_dict(cfg, num_qa_labels, seed=0):
     sd = {"lxmert." + k: v for k, v in make_lxmert_state_dict(cfg, seed).items()}
     for name, shape in lxmert_qa_param_spec(cfg, num_qa_labels)[-6:]:
-        g = np.random.Generator(np.random.PCG64([seed, zlib.crc32(name.encode())]))
-        sd[name] = (g.uniform(0.5, 1.5, shape) if name.endswith("fc.2.weight") else g.standard_normal(shape) * 0.05).astype(np.float32)
+        sd[name] = seeded_tensor(name, shape, seed)
     return sd
 
 
@@ -83,6 +80,8 @@ def make_lxmert_state_dict(cfg, seed=0):
 class LxmertEncoder(BertOps):
     """`transformers.LxmertModel` on the HIP path: `model(input_ids, visual_feats, visual_pos, attention_mask=None,
     visual_attention_mask=None, token_type_ids=None)` -> (language_output, vision_output, pooled_output)."""
+
+    _INPUTS = ("input_ids", "visual_feats", "visual_pos", "attention_mask", "visual_attention_mask", "token_type_ids")
 
     def load_state_dict(self, sd, strict=True):
         sd = to_numpy(sd)
@@ -127,30 +126,19 @@ class LxmertEncoder(BertOps):
     def capture(self, input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None):
         """Capture one forward for these input SHAPES into a HIP graph (~430 launches become one graph launch: the
         small-batch forward is launch-bound).  Returns `replay(input_ids, visual_feats, visual_pos, ...)`, which checks the
-        new ids on the host, copies the new inputs into the captured buffers, launches the graph and returns the (static) output tensors."""
-        dev = self.device
-        check_text_inputs(input_ids, token_type_ids, self.cfg)
-        static = dict(ids=input_ids.to(dev).clone(), vf=visual_feats.to(dev).clone(), vp=visual_pos.to(dev).clone(),
-                      am=None if attention_mask is None else attention_mask.to(dev).clone(),
-                      vm=None if visual_attention_mask is None else visual_attention_mask.to(dev).clone(),
-                      tt=None if token_type_ids is None else token_type_ids.to(dev).clone())
-        graph, outs = self._capture(self._forward, [static[key] for key in ("ids", "vf", "vp", "am", "vm", "tt")])
+        new ids on the host, copies the new inputs into the captured buffers, launches the graph and returns the (static) output tensors.
+        A replay with None where the capture had a tensor (or the reverse), or with another shape, raises ValueError."""
+        run = self._capture_inputs((input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids))
 
         def replay(input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None):
-            check_text_inputs(input_ids, token_type_ids, self.cfg)
-            for key, val in (("ids", input_ids), ("vf", visual_feats), ("vp", visual_pos), ("am", attention_mask),
-                             ("vm", visual_attention_mask), ("tt", token_type_ids)):
-                if static[key] is not None:
-                    static[key].copy_(val)
-            graph.replay()
-            return outs
+            return run((input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids))
         return replay
 
-    def __call__(self, input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None):
+    def _check(self, input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids):
         check_text_inputs(input_ids, token_type_ids, self.cfg)
-        out = self._forward(input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids)
-        torch.cuda.synchronize(self.device)
-        return out
+
+    def __call__(self, input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None):
+        return self._run(self._forward, (input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids))
 
     @torch.no_grad()
     def _forward(self, input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None):
@@ -198,7 +186,7 @@ def check_class_labels(name, t, shape, num_classes):
     """One tensor of class labels, host-side, before any launch: integer, of `shape`, every entry IGNORE_INDEX or in
     [0, num_classes).  -> int64 numpy array.  A wrong shape or type raises ValueError, a label outside IndexError (torch's
     cross-entropy would fault on the device there)."""
-    a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    a = host_array(t)
     if tuple(a.shape) != tuple(shape) or not np.issubdtype(a.dtype, np.integer):
         raise ValueError(f"{name} must be an integer {tuple(shape)} array, got {a.dtype} {tuple(a.shape)}")
     bad = (a != IGNORE_INDEX) & ((a < 0) | (a >= num_classes))
@@ -237,7 +225,7 @@ def cross_entropy_mean(enc, logits, labels, out):
     L.call("vk_loss_reduce", rows.data_ptr(), None, labels.data_ptr(), IGNORE_INDEX, rows.numel(), 1.0, out.data_ptr(), stream(enc.device))
 
 
-class LxmertForQuestionAnswering:
+class LxmertForQuestionAnswering(Model):
     """`transformers.LxmertForQuestionAnswering` (modeling_lxmert.py :1123-1290, the VQA/GQA model of BASELINE config 5) on the
     HIP path: encoder + `LxmertVisualAnswerHead` :602-614 (Linear -> GELU -> LayerNorm -> Linear on the pooled output).
     `model(...)` returns `question_answering_score [B, num_qa_labels]` (storage dtype); with `labels=` it returns (loss, score)."""
@@ -247,17 +235,8 @@ class LxmertForQuestionAnswering:
         self.num_qa_labels = int(num_qa_labels)
 
     def load_state_dict(self, sd, strict=True):
-        sd = to_numpy(sd)
-        want = dict(lxmert_qa_param_spec(self.lxmert.cfg, self.num_qa_labels))
-        if strict and set(want) != set(sd):
-            raise RuntimeError(f"LxmertForQuestionAnswering.load_state_dict: missing {sorted(set(want) - set(sd))[:4]} "
-                               f"unexpected {sorted(set(sd) - set(want))[:4]}")
         enc = self.lxmert
-        enc.load_state_dict({k[len("lxmert."):]: v for k, v in sd.items() if k.startswith("lxmert.")}, strict)
-        load_answer_head(enc, sd)
-        return self
-
-    def eval(self):
+        load_answer_head(enc, self._load_with_encoder(enc, "lxmert.", lxmert_qa_param_spec(enc.cfg, self.num_qa_labels), sd, strict))
         return self
 
     @torch.no_grad()
@@ -266,15 +245,13 @@ class LxmertForQuestionAnswering:
         """`labels [B]` (an answer id each, -100 to leave an example out) -> (loss, score): `CrossEntropyLoss()` of the scores
         (:1270-1272), fp32, from `vk_cross_entropy` + `vk_loss_reduce`.  Without labels: the score alone."""
         enc = self.lxmert
-        check_text_inputs(input_ids, token_type_ids, enc.cfg)
-        if labels is not None:
-            labels = check_class_labels("labels", labels, (input_ids.shape[0],), self.num_qa_labels)
-        _, _, pooled = enc._forward(input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids)
-        score = answer_head(enc, pooled)
-        if labels is None:
-            torch.cuda.synchronize(enc.device)
-            return score
-        loss = torch.empty((), dtype=torch.float32, device=enc.device)
-        cross_entropy_mean(enc, score, torch.from_numpy(labels).to(enc.device), loss)
-        torch.cuda.synchronize(enc.device)
-        return loss, score
+
+        def forward(*inputs):
+            lab = None if labels is None else check_class_labels("labels", labels, (input_ids.shape[0],), self.num_qa_labels)
+            score = answer_head(enc, enc._forward(*inputs)[2])
+            if lab is None:
+                return score
+            loss = torch.empty((), dtype=torch.float32, device=enc.device)
+            cross_entropy_mean(enc, score, torch.from_numpy(lab).to(enc.device), loss)
+            return loss, score
+        return enc._run(forward, (input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids))

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .bert_ops import check_text_inputs, dense_ln_spec, seeded_tensor, to_numpy
+from .bert_ops import Model, check_against_captured, check_text_inputs, dense_ln_spec, refill, seeded_tensor
 from .layers import stream
 from .lxmert import (IGNORE_INDEX, LxmertEncoder, answer_head, check_class_labels, cross_entropy_mean, cross_entropy_rows,
                      load_answer_head, lxmert_config, lxmert_param_spec)
@@ -64,7 +64,7 @@ def make_lxmert_pretraining_state_dict(cfg, seed=0):
     for name, shape in lxmert_pretraining_param_spec(cfg):
         key = name[len("lxmert."):] if name.startswith("lxmert.") else name
         if key == "answer_head.logit_fc.2.weight":
-            key = "answer_head.logit_fc.2.LayerNorm.weight"          # a LayerNorm's gamma under nn.Sequential's index: drawn as one
+            key = "answer_head.logit_fc.2.LayerNorm.weight"          # the name this gamma's generator has been keyed by from the start
         sd[name] = seeded_tensor(key, shape, seed)
     if cfg["tie_word_embeddings"]:
         sd[DECODER] = sd[WORDS]
@@ -139,7 +139,7 @@ class LxmertForPreTrainingOutput:
         self.visual_prediction_scores = visual_prediction_scores
 
 
-class LxmertForPreTraining:
+class LxmertForPreTraining(Model):
     """`transformers.LxmertForPreTraining` on the HIP path: `model(input_ids, visual_feats, visual_pos, attention_mask=None,
     visual_attention_mask=None, token_type_ids=None, labels=None, matched_label=None, obj_labels=None, ans=None, logits=True)`
     -> `LxmertForPreTrainingOutput`.  `obj_labels` is transformers' dict {"obj": (label [B, V], conf [B, V]), "attr": (..),
@@ -148,25 +148,17 @@ class LxmertForPreTraining:
     `logits=False` is the loss-only mode: it needs `labels`, and runs the transform, the decoder over the word table and the
     cross-entropy on the labelled rows only (`vk_gather_rows`, about 15 % of the rows at the reference's `word_mask_rate`)."""
 
-    _INPUTS = ("input_ids", "visual_feats", "visual_pos", "attention_mask", "visual_attention_mask", "token_type_ids")
-
     def __init__(self, config, precision="bf16", device="cuda:0"):
         self.cfg = lxmert_pretraining_config(**config)
         self.lxmert = LxmertEncoder(self.cfg, precision, device)
 
-    def eval(self):
-        return self
-
     def load_state_dict(self, sd, strict=True):
-        sd = to_numpy(sd)
         enc, cfg = self.lxmert, self.cfg
-        want = dict(lxmert_pretraining_param_spec(cfg))
-        decoder = resolve_decoder_weight(cfg, sd)
-        enc._check_state_dict({DECODER: decoder, **sd}, want, strict)
-        enc.load_state_dict({k[len("lxmert."):]: v for k, v in sd.items() if k.startswith("lxmert.")}, strict)
+        sd = self._load_with_encoder(enc, "lxmert.", lxmert_pretraining_param_spec(cfg), sd, strict,
+                                     rekey=lambda sd: {**sd, DECODER: resolve_decoder_weight(cfg, sd)})    # tied: the key may be absent
         enc._load_lin(sd, "cls.predictions.transform.dense", "cls.predictions.transform.dense")
         enc._load_ln(sd, "cls.predictions.transform.LayerNorm")
-        enc._lin["cls.predictions.decoder"] = enc._pack(decoder, sd["cls.predictions.bias"])     # a packed copy of the table
+        enc._lin["cls.predictions.decoder"] = enc._pack(sd[DECODER], sd["cls.predictions.bias"])     # a packed copy of the table
         enc._load_lin(sd, "cls.seq_relationship", "cls.seq_relationship")
         if cfg["task_obj_predict"]:
             enc._load_lin(sd, "obj_predict_head.transform.dense", "obj_predict_head.transform.dense")
@@ -250,11 +242,8 @@ class LxmertForPreTraining:
                 present |= 1
         else:
             idx, picked = gather
-            n = idx.numel()
-            if n:
-                rows = torch.empty((n, H), dtype=enc.tdt, device=enc.device)
-                L.call("vk_gather_rows", lang.data_ptr(), idx.data_ptr(), n, H * enc.es, rows.data_ptr(), stream(enc.device))
-                scores = enc._linear(self._transform("cls.predictions.transform", rows), "cls.predictions.decoder")
+            if idx.numel():
+                scores = enc._linear(self._transform("cls.predictions.transform", enc._gather_rows(lang, idx)), "cls.predictions.decoder")
                 cross_entropy_mean(enc, scores, picked, terms[0])
             else:                  # no labelled row: no GEMM; the reduction over rows that all are ignored gives NaN, as torch
                 unread = torch.empty((B * Lt,), dtype=torch.float32, device=enc.device)
@@ -284,8 +273,6 @@ class LxmertForPreTraining:
         if not logits:
             if "labels" not in lab:
                 raise ValueError("logits=False (the loss-only mode) needs `labels` and a config with task_mask_lm")
-            if enc.cfg["hidden_size"] * enc.es % 16:
-                raise ValueError("logits=False gathers rows of hidden_size elements: their size must be a multiple of 16 bytes")
             gather = tuple(torch.from_numpy(a).to(enc.device) for a in loss_only_index(lab["labels"]))
         out = self._forward(inputs, self._to_device(lab), any(a is not None for a in label_args), logits, gather)
         torch.cuda.synchronize(enc.device)
@@ -297,28 +284,22 @@ class LxmertForPreTraining:
         (without `logits`), which repeats the host checks, copies the new inputs and labels into the captured buffers, launches
         the graph and returns the (static) output.  What was None at capture stays None."""
         enc = self.lxmert
-        dev = enc.device
         inputs = (input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids)
         label_args = (labels, matched_label, obj_labels, ans)
         s_lab = {k: v.clone() for k, v in self._to_device(self._check(inputs, label_args)).items()}
-        s_in = [None if a is None else a.to(dev).clone() for a in inputs]
+        s_in = [None if a is None else a.to(enc.device).clone() for a in inputs]
         any_label = any(a is not None for a in label_args)
         graph, out = enc._capture(lambda: self._forward(s_in, s_lab, any_label), [])
 
         def replay(input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None,
                    labels=None, matched_label=None, obj_labels=None, ans=None):
             new = (input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids)
-            for name, s, n in zip(self._INPUTS, s_in, new):
-                if (s is None) != (n is None) or (s is not None and tuple(s.shape) != tuple(n.shape)):
-                    raise ValueError(f"replay: {name} differs from the captured call (None or another shape)")
+            check_against_captured(enc._INPUTS, s_in, new)
             lab = self._check(new, (labels, matched_label, obj_labels, ans))
             if set(lab) != set(s_lab):
                 raise ValueError(f"replay: labels {sorted(lab)} differ from the captured call's {sorted(s_lab)}")
-            for s, n in zip(s_in, new):
-                if s is not None:
-                    s.copy_(n)
-            for k, v in lab.items():
-                s_lab[k].copy_(torch.as_tensor(v))
+            refill(s_in, new)
+            refill(s_lab.values(), [torch.as_tensor(lab[k]) for k in s_lab])     # their shapes follow from the inputs' (_check)
             graph.replay()
             return out
         return replay

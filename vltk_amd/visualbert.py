@@ -15,7 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .bert_ops import LN_EPS, BertOps, additive_mask, bert_layer_spec, check_ids, check_text_inputs, seeded_tensor, to_numpy
+from .bert_ops import LN_EPS, BertOps, Model, additive_mask, bert_layer_spec, check_ids, check_text_inputs, host_array, require_gelu, \
+    seeded_tensor, to_numpy
 from .layers import stream
 
 DEFAULT_CONFIG = dict(vocab_size=30522, hidden_size=768, num_attention_heads=12, num_hidden_layers=12, intermediate_size=3072,
@@ -30,8 +31,7 @@ def visualbert_config(**kw):
     cfg.update(kw)
     if cfg["bypass_transformer"]:
         raise NotImplementedError("VisualBERT with bypass_transformer=True (the extra layer over [text encoder | raw visual rows]) is not built")
-    if cfg["hidden_act"] != "gelu":
-        raise NotImplementedError(f"hidden_act '{cfg['hidden_act']}': the GEMM epilogue has the erf GELU only")
+    require_gelu(cfg)
     assert cfg["hidden_size"] % cfg["num_attention_heads"] == 0
     return cfg
 
@@ -72,8 +72,7 @@ def make_visualbert_qa_state_dict(cfg, num_labels, seed=0):
 def check_alignment(image_text_alignment, B, V, max_position):
     """`image_text_alignment [B, V, A]`: integer, A <= 16, entries in [-1, max_position).  Host-side (a device tensor is read
     back), so it runs before a launch or a graph capture, never inside one."""
-    a = image_text_alignment
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    a = host_array(image_text_alignment)
     if a.ndim != 3 or a.shape[:2] != (B, V) or not np.issubdtype(a.dtype, np.integer):
         raise ValueError(f"image_text_alignment must be an integer [B={B}, V={V}, A] array, got {a.dtype} {a.shape}")
     if not 1 <= a.shape[2] <= MAX_ALIGNMENT:
@@ -89,7 +88,7 @@ def qa_gather_index(attention_mask, B, Lt, V):
     if attention_mask is None:
         idx = np.full((B,), Lt - 2, np.int64)
     else:
-        m = attention_mask.detach().cpu().numpy() if isinstance(attention_mask, torch.Tensor) else np.asarray(attention_mask)
+        m = host_array(attention_mask)
         if m.shape != (B, Lt):
             raise ValueError(f"attention_mask must be [B={B}, Lt={Lt}], got {m.shape}")
         idx = m.sum(1).astype(np.int64) - 2
@@ -144,11 +143,8 @@ class VisualBertModel(BertOps):
 
     def __call__(self, input_ids, visual_embeds, attention_mask=None, visual_attention_mask=None, token_type_ids=None,
                  visual_token_type_ids=None, image_text_alignment=None):
-        args = (input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids, visual_token_type_ids, image_text_alignment)
-        self._check(*args)
-        out = self._forward(*args)
-        torch.cuda.synchronize(self.device)
-        return out
+        return self._run(self._forward, (input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids,
+                                         visual_token_type_ids, image_text_alignment))
 
     def capture(self, input_ids, visual_embeds, attention_mask=None, visual_attention_mask=None, token_type_ids=None,
                 visual_token_type_ids=None, image_text_alignment=None):
@@ -156,33 +152,20 @@ class VisualBertModel(BertOps):
         launch).  Returns `replay(...)` with the model's signature, which checks the new inputs on the host, copies them into the
         captured buffers, launches the graph and returns the (static) output tensors.  An input given as None at capture stays
         at its default."""
-        dev = self.device
-        args = (input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids, visual_token_type_ids, image_text_alignment)
-        self._check(*args)
-        static = [None if a is None else a.to(dev).clone() for a in args]
-        graph, outs = self._capture(self._forward, static)
+        run = self._capture_inputs((input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids, visual_token_type_ids,
+                                    image_text_alignment))
 
         def replay(input_ids, visual_embeds, attention_mask=None, visual_attention_mask=None, token_type_ids=None,
                    visual_token_type_ids=None, image_text_alignment=None):
-            new = (input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids, visual_token_type_ids, image_text_alignment)
-            for name, s, n in zip(self._INPUTS, static, new):
-                if (s is None) != (n is None) or (s is not None and tuple(s.shape) != tuple(n.shape)):
-                    raise ValueError(f"replay: {name} differs from the captured call (None or another shape)")
-            self._check(*new)
-            for s, n in zip(static, new):
-                if s is not None:
-                    s.copy_(n)
-            graph.replay()
-            return outs
+            return run((input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids, visual_token_type_ids,
+                        image_text_alignment))
         return replay
 
     def embeddings(self, input_ids, visual_embeds, attention_mask=None, visual_attention_mask=None, token_type_ids=None,
                    visual_token_type_ids=None, image_text_alignment=None):
         """The embedding stage alone: what transformers returns as `hidden_states[0]`, [B, Lt + V, H]."""
-        args = (input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids, visual_token_type_ids, image_text_alignment)
-        self._check(*args)
-        x, _ = self._embed(*args)
-        torch.cuda.synchronize(self.device)
+        x, _ = self._run(self._embed, (input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids,
+                                       visual_token_type_ids, image_text_alignment))
         return x.view(input_ids.shape[0], -1, self.cfg["hidden_size"])
 
     @torch.no_grad()
@@ -223,7 +206,7 @@ class VisualBertModel(BertOps):
         return x.view(B, Lx, H), self._pooler(x, B, Lx)
 
 
-class VisualBertForQuestionAnswering:
+class VisualBertForQuestionAnswering(Model):
     """`transformers.VisualBertForQuestionAnswering` (modeling_visual_bert.py :1106-1132, the model `legacy_train.py` builds) on
     the HIP path: the encoder, then `cls` on the row `attention_mask.sum(1) - 2` of each example's sequence output (the last
     text token before [SEP]; the TEXT mask counts).  `model(...)` takes the encoder's arguments and returns logits
@@ -237,28 +220,19 @@ class VisualBertForQuestionAnswering:
         self.num_labels = int(num_labels)
 
     def load_state_dict(self, sd, strict=True):
-        sd = to_numpy(sd)
         enc = self.visual_bert
-        enc._check_state_dict(sd, dict(visualbert_qa_param_spec(enc.cfg, self.num_labels)), strict)
-        enc.load_state_dict({k[len("visual_bert."):]: v for k, v in sd.items() if k.startswith("visual_bert.")}, strict)
-        enc._load_lin(sd, "cls", "cls")
-        return self
-
-    def eval(self):
+        enc._load_lin(self._load_with_encoder(enc, "visual_bert.", visualbert_qa_param_spec(enc.cfg, self.num_labels), sd, strict), "cls", "cls")
         return self
 
     @torch.no_grad()
     def __call__(self, input_ids, visual_embeds, attention_mask=None, visual_attention_mask=None, token_type_ids=None,
                  visual_token_type_ids=None, image_text_alignment=None):
         enc = self.visual_bert
-        args = (input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids, visual_token_type_ids, image_text_alignment)
-        enc._check(*args)
-        B, Lt = input_ids.shape
-        idx = torch.from_numpy(qa_gather_index(attention_mask, B, Lt, visual_embeds.shape[1])).to(enc.device)
-        seq, _ = enc._forward(*args)
-        H = enc.cfg["hidden_size"]
-        rows = torch.empty((B, H), dtype=enc.tdt, device=enc.device)
-        L.call("vk_gather_rows", seq.data_ptr(), idx.data_ptr(), B, H * enc.es, rows.data_ptr(), stream(enc.device))
-        logits = enc._linear(rows, "cls")
-        torch.cuda.synchronize(enc.device)
-        return logits
+
+        def forward(*inputs):
+            B, Lt = input_ids.shape
+            idx = torch.from_numpy(qa_gather_index(attention_mask, B, Lt, visual_embeds.shape[1])).to(enc.device)    # host, before any launch
+            seq, _ = enc._forward(*inputs)
+            return enc._linear(enc._gather_rows(seq.view(-1, enc.cfg["hidden_size"]), idx), "cls")
+        return enc._run(forward, (input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids, visual_token_type_ids,
+                                  image_text_alignment))

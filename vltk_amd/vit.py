@@ -21,7 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .bert_ops import LN_EPS, BertOps, seeded_tensor, to_numpy
+from .bert_ops import LN_EPS, BertOps, Model, require_gelu, seeded_tensor, to_numpy
 from .layers import stream
 
 DEFAULT_CONFIG = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, hidden_act="gelu",
@@ -42,8 +42,7 @@ def vit_config(geometry=None, **kw):
     if geometry is not None:
         cfg.update(zip(("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "patch_size"), GEOMETRIES[geometry]))
     cfg.update(kw)
-    if cfg["hidden_act"] != "gelu":
-        raise NotImplementedError(f"hidden_act '{cfg['hidden_act']}': the GEMM epilogue has the erf GELU only")
+    require_gelu(cfg)
     if not cfg["qkv_bias"]:
         raise NotImplementedError("qkv_bias=False: the packed q/k/v GEMM always adds its bias")
     ph, pw = _pair(cfg["patch_size"])
@@ -194,6 +193,7 @@ class ViTModel(BertOps):
     """`transformers.ViTModel` on the HIP path: `model(pixel_values [B, C, Hi, Wi], interpolate_pos_encoding=False)` ->
     (last_hidden_state [B, N + 1, H] with the class token first, pooler_output [B, H] or None without a pooling layer)."""
 
+    _INPUTS = ("pixel_values",)
     _PROJ = "embeddings.patch_embeddings.projection"
 
     def __init__(self, config, precision="bf16", device="cuda:0", add_pooling_layer=True):
@@ -230,36 +230,29 @@ class ViTModel(BertOps):
             self._pos[(gh, gw)] = t.to(self.device).to(self.tdt).contiguous()
         return self._pos[(gh, gw)]
 
-    def __call__(self, pixel_values, interpolate_pos_encoding=False):
+    def _check(self, pixel_values, interpolate_pos_encoding=False):
         check_pixel_values(pixel_values, self.cfg, interpolate_pos_encoding)
-        out = self._forward(pixel_values)
-        torch.cuda.synchronize(self.device)
-        return out
+
+    def __call__(self, pixel_values, interpolate_pos_encoding=False):
+        return self._run(self._forward, (pixel_values,), interpolate_pos_encoding=interpolate_pos_encoding)
 
     def embeddings(self, pixel_values, interpolate_pos_encoding=False):
         """The embedding stage alone: what transformers returns as `hidden_states[0]`, [B, N + 1, H]."""
-        check_pixel_values(pixel_values, self.cfg, interpolate_pos_encoding)
-        x = self._embed(pixel_values)
-        torch.cuda.synchronize(self.device)
+        x = self._run(self._embed, (pixel_values,), interpolate_pos_encoding=interpolate_pos_encoding)
         return x.view(pixel_values.shape[0], -1, self.cfg["hidden_size"])
+
+    def _before_capture(self, pixel_values):              # the table's host work and its copy happen before the capture
+        P = vit_grid(self.cfg)[2]
+        self.position_table(pixel_values.shape[2] // P, pixel_values.shape[3] // P)
 
     def capture(self, pixel_values, interpolate_pos_encoding=False):
         """Capture one forward for this input SHAPE into a HIP graph (one stream, no branches).  Returns `replay(pixel_values)`,
         which copies the new pixels into the captured buffer, launches the graph and returns the (static) output tensors; another
         shape raises ValueError."""
-        dev = self.device
-        _, gh, gw = check_pixel_values(pixel_values, self.cfg, interpolate_pos_encoding)
-        self._require_loaded()
-        self.position_table(gh, gw)                       # host work and its copy happen before the capture
-        static = pixel_values.to(dev, torch.float32).contiguous().clone()
-        graph, outs = self._capture(self._forward, [static])
+        run = self._capture_inputs((pixel_values,), interpolate_pos_encoding=interpolate_pos_encoding)
 
         def replay(pixel_values):
-            if tuple(pixel_values.shape) != tuple(static.shape):
-                raise ValueError(f"replay: pixel_values {tuple(pixel_values.shape)} differ from the captured {tuple(static.shape)}")
-            static.copy_(pixel_values)
-            graph.replay()
-            return outs
+            return run((pixel_values,))
         return replay
 
     @torch.no_grad()
@@ -307,7 +300,7 @@ class ViTModel(BertOps):
         return x.view(B, Lx, self.cfg["hidden_size"]), (self._pooler(x, B, Lx) if self.add_pooling_layer else None)
 
 
-class ViTForImageClassification:
+class ViTForImageClassification(Model):
     """`transformers.ViTForImageClassification` on the HIP path: the encoder without its pooler, then `classifier` on the class
     row of the normalised sequence output.  `model(pixel_values, interpolate_pos_encoding=False)` returns logits
     `[B, num_labels]` in the storage type."""
@@ -319,25 +312,18 @@ class ViTForImageClassification:
             raise ValueError("num_labels must be >= 1")
 
     def load_state_dict(self, sd, strict=True):
-        sd = rename_hub_keys(to_numpy(sd), prefix="vit.")
         enc = self.vit
-        enc._check_state_dict(sd, dict(vit_classifier_param_spec(enc.cfg, self.num_labels)), strict)
-        enc.load_state_dict({k[len("vit."):]: v for k, v in sd.items() if k.startswith("vit.")}, strict)
+        sd = self._load_with_encoder(enc, "vit.", vit_classifier_param_spec(enc.cfg, self.num_labels), sd, strict,
+                                     rekey=lambda sd: rename_hub_keys(sd, prefix="vit."))
         enc._load_lin(sd, "classifier", "classifier")
-        return self
-
-    def eval(self):
         return self
 
     @torch.no_grad()
     def __call__(self, pixel_values, interpolate_pos_encoding=False):
         enc = self.vit
-        check_pixel_values(pixel_values, enc.cfg, interpolate_pos_encoding)
-        x, B, Lx = enc._sequence(pixel_values)
-        H = enc.cfg["hidden_size"]
-        idx = (torch.arange(B, dtype=torch.int32, device=enc.device) * Lx).contiguous()
-        first = torch.empty((B, H), dtype=enc.tdt, device=enc.device)
-        L.call("vk_gather_rows", x.data_ptr(), idx.data_ptr(), B, H * enc.es, first.data_ptr(), stream(enc.device))
-        logits = enc._linear(first, "classifier")
-        torch.cuda.synchronize(enc.device)
-        return logits
+
+        def forward(pixel_values):
+            x, B, Lx = enc._sequence(pixel_values)
+            idx = (torch.arange(B, dtype=torch.int32, device=enc.device) * Lx).contiguous()
+            return enc._linear(enc._gather_rows(x, idx), "classifier")          # the class row of each sequence
+        return enc._run(forward, (pixel_values,), interpolate_pos_encoding=interpolate_pos_encoding)
