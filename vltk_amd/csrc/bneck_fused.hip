@@ -13,7 +13,7 @@
 //     SIMD, 2 (halves of the output channels) x 2 (halves of the pixel blocks); weights cost no memory traffic;
 //   * HBM traffic per pixel: 512 B x 340 / 256 read (the halo overlap is served by L2: neighbouring tiles run on the same XCD)
 //     + 512 B written; no t1 / t2 / second read of x.
-// Same MFMA (v_mfma_f32_16x16x32_f16), same K order and the same epilogue arithmetic as conv_ws.hip / conv3x3_blk.hip.
+// Same MFMA (v_mfma_f32_16x16x32_f16), same K order as conv_ws.hip / conv3x3_blk.hip and the epilogue arithmetic of conv_prims.h.
 // Residual reads and output stores are hand-issued (asm) so that their waits can be counted: hipcc waits vmcnt(0) for any load
 // it sees while LDS-DMA is in flight.  Lanes whose pixel is outside the image load from a clamped address and store to a
 // scratch page, so every wave issues the same number of vector-memory instructions and the static counts hold.
@@ -22,12 +22,9 @@
 #include <vector>
 
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 struct BneckK {
     const char *x;       // [N, H, W, CIN] f16
@@ -52,10 +49,6 @@ constexpr int BN_T1_BYTES = BN_NP * 128, BN_T2_BYTES = BN_TH * BN_TW * 128;
 
 template <int CIN>
 constexpr int bn_smem() { return bn_ring(CIN) * bn_chpx(CIN) * CIN * 2 + BN_T1_BYTES + BN_T2_BYTES + 384 * 4; }   // + the biases
-
-#define VKN_GLDS16(gptr, lptr)                                                                         \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),          \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
 
 template <int N>
 __device__ __forceinline__ void bn_vm_wait() {
@@ -164,7 +157,7 @@ __global__ __launch_bounds__(256, 1) void bneck64_kernel(BneckK p) {
             int off = org + (pr * p.W + pc) * PXB;
             off = min(max(off, 0), (int)p.x_last);                // outside the image: clamped (phase A writes zeros there)
             off += (lsl ^ (pic & KM)) << 4;
-            VKN_GLDS16(p.x + (unsigned)off, smem + slot * CHB + (wave * NQ + q) * 1024);
+            glds16(p.x + (unsigned)off, smem + slot * CHB + (wave * NQ + q) * 1024);
         }
     };
 
@@ -421,8 +414,8 @@ __global__ __launch_bounds__(256, 1) void bneck64_kernel(BneckK p) {
                     }
                     const float *bl = B3 + cp * 128 + u * 32 + g * 8;
                     floatx4 v0 = acc0 + *reinterpret_cast<const floatx4 *>(bl), v1 = acc1 + *reinterpret_cast<const floatx4 *>(bl + 4);
+                    half8 &rr = cur[PROJ ? 0 : u];           // the residual piece (PROJ: none, not read)
                     if constexpr (!PROJ) {
-                        half8 &rr = cur[u];
                         // piece u: + the 3 - u pieces behind it + this block's u stores so far = 3 more
                         if (3 + 4 * (nL + nS) == 11)
                             asm volatile("s_waitcnt vmcnt(11)" : "+v"(rr)::"memory");
@@ -430,12 +423,8 @@ __global__ __launch_bounds__(256, 1) void bneck64_kernel(BneckK p) {
                             asm volatile("s_waitcnt vmcnt(15)" : "+v"(rr)::"memory");
                         else
                             asm volatile("s_waitcnt vmcnt(19)" : "+v"(rr)::"memory");
-                        v0 += __builtin_convertvector(__builtin_shufflevector(rr, rr, 0, 1, 2, 3), floatx4);
-                        v1 += __builtin_convertvector(__builtin_shufflevector(rr, rr, 4, 5, 6, 7), floatx4);
                     }
-                    const half4 h0 = __builtin_convertvector(v0, half4), h1 = __builtin_convertvector(v1, half4);
-                    half8 o = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-                    o = __builtin_elementwise_max(o, half8{0, 0, 0, 0, 0, 0, 0, 0});
+                    const half8 o = epi_finish<!PROJ, true>(v0, v1, rr);     // (the bias add above, the wait, then the rest of the unit)
                     char *ya_ = ya[i % 3];
                     if (u == 0) bn_gstore<0>(ya_, o);
                     if (u == 1) bn_gstore<64>(ya_, o);
@@ -626,7 +615,7 @@ __global__ __launch_bounds__(512, 2) void bneck64_rows_kernel(BneckRowsK p) {
             const unsigned rowb = (unsigned)((img + (long)yy * p.W) * PXB);
             const int sl = h % BR_R;
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) VKN_GLDS16(p.x + (rowb + (unsigned)dcol[q]), smem + sl * XROW + (wave * NQ + q) * 1024);
+            for (int q = 0; q < NQ; ++q) glds16(p.x + (rowb + (unsigned)dcol[q]), smem + sl * XROW + (wave * NQ + q) * 1024);
         };
 #pragma unroll
         for (int h = 0; h < BR_P; ++h) request(h);
@@ -727,13 +716,7 @@ __global__ __launch_bounds__(512, 2) void bneck64_rows_kernel(BneckRowsK p) {
                         acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(w3f[u][1][KS3 - 1], xs[1], acc1, 0, 0, 0);
                     }
                     const float *bl = BI + cq * 64 + u * 32 + g * 8;
-                    floatx4 v0 = acc0 + *reinterpret_cast<const floatx4 *>(bl), v1 = acc1 + *reinterpret_cast<const floatx4 *>(bl + 4);
-                    if constexpr (!PROJ) {
-                        v0 += __builtin_convertvector(__builtin_shufflevector(xs[u], xs[u], 0, 1, 2, 3), floatx4);
-                        v1 += __builtin_convertvector(__builtin_shufflevector(xs[u], xs[u], 4, 5, 6, 7), floatx4);
-                    }
-                    const half4 h0 = __builtin_convertvector(v0, half4), h1 = __builtin_convertvector(v1, half4);
-                    o[u] = __builtin_elementwise_max(__builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7), half8{0, 0, 0, 0, 0, 0, 0, 0});
+                    o[u] = epi_unit<!PROJ, true>(acc0, acc1, *reinterpret_cast<const floatx4 *>(bl), *reinterpret_cast<const floatx4 *>(bl + 4), xs[u]);
                 }
                 if constexpr (!(DBG & 8)) {
                     bn_gstore<0>(yrow, o[0]);

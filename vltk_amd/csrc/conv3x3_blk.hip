@@ -21,12 +21,9 @@
 // Weights are read in the layout vk_pack_conv_weight already produces ([cout][9 taps][64-channel slice], zero outside a
 // channel's group), so nothing about the packing or the ABI changes.
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct BlkK {
     const char *x;
@@ -40,10 +37,6 @@ struct BlkK {
     int tiles_x, tiles_y, ntiles;
     const char *zero;        // >= 16 zero bytes: source of the out-of-image pixels
 };
-
-#define VKB_GLDS16(gptr, lptr)                                                                         \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),          \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
 
 template <int N>
 __device__ __forceinline__ void blk_vm_wait() {
@@ -127,7 +120,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_blk_kernel(BlkK p) {
             if (pc >= PW) pc -= PW, ++pr;
             const bool ok = P0 + 8 * q < PH * PW && (unsigned)(y0 + pr) < nrow && (unsigned)(x0 + pc) < ncol;
             const char *src = ok ? org + ((pr * p.W + pc) * p.cbytes + (((lane & 7) ^ (pc & 7)) << 4)) : p.zero;
-            VKB_GLDS16(src, smem + buf * BUF + (wave * NQ + q) * 1024);
+            glds16(src, smem + buf * BUF + (wave * NQ + q) * 1024);
             __builtin_amdgcn_sched_barrier(0);          // one piece's address at a time (registers)
         }
     };

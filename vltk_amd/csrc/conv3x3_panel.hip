@@ -17,8 +17,8 @@
 //   * per step (one tap of one stage) = 32 MFMAs per wave, one raw barrier, 2 weight DMA pieces per wave,
 //     plus one panel piece of the NEXT channel stage on the first PP taps; hand-issued ds_read_b128 with
 //     counted lgkmcnt, counted vmcnt (the count depends only on the tap index: compile-time).
-//   * same per-wave geometry (2x4 waves, 128x64 per wave, 16x16x32 f16 MFMA) and the same LDS-staged
-//     whole-row epilogue as conv_mfma256.hip.
+//   * same per-wave geometry (2x4 waves, 128x64 per wave, 16x16x32 f16 MFMA) as conv_mfma256.hip and, in its first
+//     form (DBG & 8), the same LDS-staged whole-row epilogue (StagedEpi, conv_prims.h).
 //   * PHASE form (dilation 2, even H, even W <= 14): the kernel's INTERNAL row order is
 //     [group of 16 images][phase = (y & 1, x & 1)][qy][qx][image % 16], so an aligned 16-row MFMA tile is one position of
 //     the (H/2) x (W/2) grid of one phase in 16 images: a tap is a uniform shift of (dy * W/2 + dx) * 16 rows and is inside
@@ -36,13 +36,9 @@
 #include <vector>
 
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 
 struct PanelK {
     const char *x;
@@ -86,10 +82,6 @@ __device__ __forceinline__ PhaseBlk phase_blk(const PanelK &p, int gb) {
 
 constexpr int P_NW = 6;                     // weight ring slots
 constexpr int P_WSLOT = 256 * 64;           // 16 KiB: 256 output channels x 64 B (the tall phase form's slot is 128 channels, 8 KiB)
-
-#define VKP_GLDS16(gptr, lptr)                                                                         \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),          \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
 
 // The counted vmcnt of a step.  A step's POST issues, in this order, one panel piece of the next stage (taps < PP, not in the last
 // stage) and NWP weight pieces (2 per wave with 256-column tiles, 1 with 128) for step t + P_NW.  The wait at the end of step t's
@@ -227,8 +219,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
             if (bid >= nwg) return;
         }
     }
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int t_ = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int t_ = xcd_tile(bid, nwg);
     // (the n_tiles column tiles of one panel, 2 or 4, are consecutive t_: consecutive workgroups of one XCD, whose L2 holds the panel)
     const int n_tile = t_ % p.n_tiles, m_tile = t_ / p.n_tiles;
     const int m0 = m_tile * TILE, n0 = n_tile * CT;
@@ -284,7 +275,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         if constexpr (PHASE) {
             unsigned pl = ps_lane;
             asm volatile("" : "+v"(pl));                       // opaque (see x_addr_of)
-            VKP_GLDS16(p.x + (pl + (ps_blk[piece] + cs * 64)), smem + (cs & 1) * PBYTES + (piece * 8 + wave) * 1024);
+            glds16(p.x + (pl + (ps_blk[piece] + cs * 64)), smem + (cs & 1) * PBYTES + (piece * 8 + wave) * 1024);
             return;
         }
         int pf = pm_first;
@@ -293,13 +284,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         // will do there, so clamp to a real row instead of branching to a zero page
         const int m = min(max(pf + piece * 128, 0), p.M - 1);
         const unsigned off = (unsigned)m * (unsigned)p.cin_bytes + cs * 64 + lchunk * 16;
-        VKP_GLDS16(p.x + off, smem + (cs & 1) * PBYTES + (piece * 8 + wave) * 1024);
+        glds16(p.x + off, smem + (cs & 1) * PBYTES + (piece * 8 + wave) * 1024);
     };
     auto req_w = [&](int slot, int cs, int tap, int i) {      // rows (wave*NWP+i)*16 .. +15 of weight slot `slot`
         const unsigned koff = (unsigned)(tap * p.cstages + cs) * 64;  // K layout = (tap, channel): tap*Cin*2 + cs*64 bytes
         unsigned wb_ = wsrc0;
         asm volatile("" : "+v"(wb_));                          // opaque (see x_addr_of)
-        VKP_GLDS16(p.w + (wb_ + i * wstep + koff), smem + WBASE + slot * WSLOT + (wave * NWP + i) * 1024);
+        glds16(p.w + (wb_ + i * wstep + koff), smem + WBASE + slot * WSLOT + (wave * NWP + i) * 1024);
     };
 
     // ---- fragment addressing ----
@@ -362,7 +353,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
             break;                                                                                   \
         }                                                                                            \
         if constexpr (!(DBG & 1) && !ZROW) {                                                         \
-            uintx4 u_ = __builtin_bit_cast(uintx4, XR);                                              \
+            u32x4 u_ = __builtin_bit_cast(u32x4, XR);                                              \
             const bool v_ = ((TM) >> (MI)) & 1u;                                                     \
             u_[0] = v_ ? u_[0] : 0u;                                                                 \
             u_[1] = v_ ? u_[1] : 0u;                                                                 \
@@ -697,18 +688,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
                 }
 #pragma unroll
                 for (int qn = 0; qn < 2; ++qn) {
-                    floatx4 x0 = acc[mi][2 * qn] + bq[qn][0], x1 = acc[mi][2 * qn + 1] + bq[qn][1];
-                    if constexpr (RES) {
-                        x0 += __builtin_convertvector(__builtin_shufflevector(rr[qn], rr[qn], 0, 1, 2, 3), floatx4);
-                        x1 += __builtin_convertvector(__builtin_shufflevector(rr[qn], rr[qn], 4, 5, 6, 7), floatx4);
-                    }
-                    half4 h0 = __builtin_convertvector(x0, half4), h1 = __builtin_convertvector(x1, half4);
-                    half8 o = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-                    if constexpr (RELU) o = __builtin_elementwise_max(o, half8{0, 0, 0, 0, 0, 0, 0, 0});
+                    const half8 o = epi_unit<RES, RELU>(acc[mi][2 * qn], acc[mi][2 * qn + 1], bq[qn][0], bq[qn][1], rr[qn]);
                     if (FULL || m < p.M) *reinterpret_cast<half8 *>(p.y + (mo * p.ldy + ch0 + qn * 32) * 2) = o;
                 }
             }
         };
+        // (epi_dispatch of conv_prims.h, written out: called through it, the 256 x 256 builds' K loops get other registers)
         const bool full = m0 + TILE <= p.M;
         auto by_full = [&](auto r_, auto l_) {
             if (full)
@@ -729,67 +714,17 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     } else {
     asm volatile("s_barrier" ::: "memory");
     floatx4 *stg = reinterpret_cast<floatx4 *>(smem);
-    auto load_res = [&](int h, half8 (&rr)[8]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int it = tid + 512 * i, row = it >> 5, k8 = it & 31;
-            const int m = min(m0 + h * 128 + row, p.M - 1);
-            if (p.res)
-                rr[i] = *reinterpret_cast<const half8 *>(p.res + ((long)m * p.ldy + n0 + k8 * 8) * 2);
-            else
-                rr[i] = half8{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-    };
-    auto stage_half = [&](int h) {
-        if (wr == h) {
-#pragma unroll
-            for (int qn = 0; qn < 2; ++qn) {
-                const int col = wc * 64 + qn * 32 + g * 8;
-                const floatx4 b0 = reinterpret_cast<const floatx4 *>(p.bias + n0 + col)[0];
-                const floatx4 b1 = reinterpret_cast<const floatx4 *>(p.bias + n0 + col)[1];
-#pragma unroll
-                for (int mi = 0; mi < 8; ++mi) {
-                    const int row = mi * 16 + j;
-                    const int c16 = col >> 2;
-                    stg[row * 64 + (c16 ^ (row & 7))] = acc[mi][2 * qn] + b0;
-                    stg[row * 64 + ((c16 + 1) ^ (row & 7))] = acc[mi][2 * qn + 1] + b1;
-                }
-            }
-        }
-    };
-    auto write_half = [&](int h, const half8 (&rr)[8]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int it = tid + 512 * i, row = it >> 5, k8 = it & 31;
-            const int m = m0 + h * 128 + row;
-            const floatx4 v0 = stg[row * 64 + ((2 * k8) ^ (row & 7))];
-            const floatx4 v1 = stg[row * 64 + ((2 * k8 + 1) ^ (row & 7))];
-            half8 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float a = v0[e] + (float)rr[i][e], b = v1[e] + (float)rr[i][4 + e];
-                if (p.relu) {
-                    a = a > 0.f ? a : 0.f;
-                    b = b > 0.f ? b : 0.f;
-                }
-                o[e] = (_Float16)a;
-                o[4 + e] = (_Float16)b;
-            }
-            if (m < p.M) *reinterpret_cast<half8 *>(p.y + ((long)m * p.ldy + n0 + k8 * 8) * 2) = o;
-        }
-    };
-#define VKP_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
     half8 r0[8];
-    load_res(0, r0);
-    stage_half(0);
-    VKP_LDS_BARRIER();
-    write_half(0, r0);
-    load_res(1, r0);
-    VKP_LDS_BARRIER();
-    stage_half(1);
-    VKP_LDS_BARRIER();
-    write_half(1, r0);
-#undef VKP_LDS_BARRIER
+    const StagedEpi<512, _Float16, half8, PanelK> epi{p, tid, g, j, m0, n0, stg};     // (conv_prims.h; one residual set, loaded twice)
+    epi.load_res(0, r0);
+    if (wr == 0) epi.stage<0, 8>(wc * 64, acc);
+    lds_barrier();
+    epi.write(0, r0);
+    epi.load_res(1, r0);
+    lds_barrier();
+    if (wr == 1) epi.stage<0, 8>(wc * 64, acc);
+    lds_barrier();
+    epi.write(1, r0);
     }
     if constexpr (DBG & 4) {
         unsigned long st_k1;

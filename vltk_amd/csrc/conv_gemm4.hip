@@ -14,19 +14,16 @@
 //   * one wave per SIMD, 512 registers per lane: 256 accumulator registers, two sets of 8 weight fragments, a 4-deep window of
 //     pixel-row fragments.
 // The epilogue stores straight from the accumulator layout (a lane owns 8 consecutive channels of a pixel: 16-byte stores,
-// 64 B per pixel row and instruction), specialised on residual / ReLU / ragged tile like conv_ws.hip.  Same K order and
-// epilogue arithmetic as the other 1x1 kernels: a layer's bits do not depend on which one the dispatcher picks.
+// 64 B per pixel row and instruction), specialised on residual / ReLU / ragged tile like conv_ws.hip.  Same K order as
+// the other 1x1 kernels and the one epilogue arithmetic of conv_prims.h: a layer's bits do not depend on which one the dispatcher picks.
 #include <cstdio>
 #include <type_traits>
 #include <vector>
 
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 struct Gemm4K {
     const char *x;       // [M, cin] rows
@@ -86,7 +83,7 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
     // K stages: the ring does not stop at a tile boundary -- the last four stages of a tile request the first stages of the next
     // one (S % 4 == 0, so the slots line up), and a tile's epilogue sits between two MFMA rows with nothing to wait for.
     // (A workgroup per tile paid, per tile, the first stage's HBM latency, the store tail and a dispatch: 14 % of its time.)
-    // XCD-aware (bijective) tile map, column tiles of one row tile next to each other on one XCD (conv_mfma.hip); the grid is
+    // XCD-aware (bijective) tile map, column tiles of one row tile next to each other on one XCD (xcd_tile, conv_prims.h); the grid is
     // a multiple of 8 (or the whole tile count), so a workgroup's tiles all map to its own XCD.
     const int bid = blockIdx.x;
     int Mrows = p.M, m_tiles = p.m_tiles;
@@ -127,9 +124,7 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) wv[i] = (unsigned)((wave * 4 + i) * 16 + lrow) * (unsigned)p.wrow_bytes + lchunk * 16;
     auto setup_tile = [&](int tt, Gemm4Tile &T) {
-        const int nwg = total_tiles;
-        const int q = nwg >> 3, r = nwg & 7, xcd = tt & 7;
-        const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (tt >> 3);
+        const int t = xcd_tile(tt, total_tiles);
         const int n_tile = t % p.n_tiles, m_tile = t / p.n_tiles;
         T.m0 = m_tile * 256;
         T.n0 = n_tile * 256;
@@ -474,35 +469,12 @@ __global__ __launch_bounds__(256, 1) void conv_gemm4_kernel(Gemm4K p) {
                 }
 #pragma unroll
                 for (int qn = 0; qn < 4; ++qn) {
-                    floatx4 x0 = acc[mi][2 * qn] + bq[qn][0], x1 = acc[mi][2 * qn + 1] + bq[qn][1];
-                    if constexpr (RES) {
-                        x0 += __builtin_convertvector(__builtin_shufflevector(rr[qn], rr[qn], 0, 1, 2, 3), floatx4);
-                        x1 += __builtin_convertvector(__builtin_shufflevector(rr[qn], rr[qn], 4, 5, 6, 7), floatx4);
-                    }
-                    half4 h0 = __builtin_convertvector(x0, half4), h1 = __builtin_convertvector(x1, half4);
-                    half8 o = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-                    if constexpr (RELU) o = __builtin_elementwise_max(o, half8{0, 0, 0, 0, 0, 0, 0, 0});
+                    const half8 o = epi_unit<RES, RELU>(acc[mi][2 * qn], acc[mi][2 * qn + 1], bq[qn][0], bq[qn][1], rr[qn]);
                     if (FULL || m < Mrows) *reinterpret_cast<half8 *>(p.y + (m * p.ldy + ch0 + qn * 32) * 2) = o;
                 }
             }
         };
-        const bool full = em0 + 256 <= Mrows;
-        auto by_full = [&](auto r_, auto l_) {
-            if (full)
-                epilogue(r_, l_, std::true_type{});
-            else
-                epilogue(r_, l_, std::false_type{});
-        };
-        auto by_relu = [&](auto r_) {
-            if (p.relu)
-                by_full(r_, std::true_type{});
-            else
-                by_full(r_, std::false_type{});
-        };
-        if (p.res)
-            by_relu(std::true_type{});
-        else
-            by_relu(std::false_type{});
+        epi_dispatch(p.res, p.relu, em0 + 256 <= Mrows, epilogue);
         if constexpr (STAMP) {
             unsigned long te;
             asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(te)::"memory");

@@ -22,14 +22,9 @@
 // fp16 mode: v_mfma_f32_16x16x32_f16, fp32 accumulate.  fp32 ("strict") mode:
 // v_mfma_f32_16x16x4_f32 (exact f32 FMA chain) on the same loader/epilogue.
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct ConvK {
     const char *x;
@@ -156,12 +151,8 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvK p) {
     constexpr int KSTEPS = Frag<T>::KSTEPS;
     typedef typename Frag<T>::type frag_t;
 
-    // XCD-aware (bijective) workgroup -> tile map: the 8 XCDs each get a contiguous range of
-    // tiles, and within it tiles that share the same 128 pixels (different channel tiles) are
-    // adjacent, so the pixel panel is fetched from HBM once per XCD L2.
-    const int bid = blockIdx.x, nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    // XCD-aware (bijective) workgroup -> tile map (xcd_tile, conv_prims.h)
+    const int t = xcd_tile(blockIdx.x, gridDim.x);
     const int n_tile = t % p.n_tiles, m_tile = t / p.n_tiles;
     const int m0 = m_tile * CONV_BM, n0 = n_tile * BN;
 

@@ -23,11 +23,9 @@
 #include <type_traits>
 
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 struct Conv256K {
     const char *x;
@@ -53,10 +51,6 @@ constexpr int R_XB = R_BM * R_ROWB;          // 16 KiB
 constexpr int R_SLOT = 2 * R_XB;             // 32 KiB
 constexpr int R_SMEM = R_NSLOT * R_SLOT;     // 128 KiB
 
-#define VK_GLDS16(gptr, lptr)                                                                          \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),          \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
-
 // DBG != 0 are diagnostic / A-B builds selected with VK_CONV256_DBG (never used by the product path):
 // 1 = no LDS-DMA in the steady state, 2 = no pixel-row fragment reads, 3 = both (timing only, WRONG results);
 // 16 = taps innermost (no gain), 32 / 64 = weight / pixel DMA pieces all read ONE cached line (timing only),
@@ -69,12 +63,11 @@ template <int DBG, bool DUAL = false>
 __global__ __launch_bounds__(512, 2) void conv_mfma256_kernel(Conv256K p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-    // XCD-aware (bijective) workgroup -> tile map (see conv_mfma.hip).  A persistent-workgroup variant
+    // XCD-aware (bijective) workgroup -> tile map (xcd_tile, conv_prims.h).  A persistent-workgroup variant
     // (tile loop inside the kernel) was tried and rejected: the loop-carried state pushed the kernel over
     // the 256-VGPR budget (79 spilled registers, 8-25 % slower on every shape).
     const int bid = blockIdx.x, nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int t = xcd_tile(bid, nwg);
     const int n_tile = t % p.n_tiles, m_tile = t / p.n_tiles;
     const int m0 = m_tile * R_BM, n0 = n_tile * R_BN;
 
@@ -152,7 +145,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma256_kernel(Conv256K p) {
     int wtap = 0, wkc = 0;          // (tap, channel stage) of the NEXT weight request (DBG & 16 order)
     auto req_x = [&](int stage, int i) {
         if constexpr (DBG & 1) return;
-        VK_GLDS16(xsrc[i], smem + (stage & (R_NSLOT - 1)) * R_SLOT + dma_x0 + i * 1024);
+        glds16(xsrc[i], smem + (stage & (R_NSLOT - 1)) * R_SLOT + dma_x0 + i * 1024);
     };
     auto req_w = [&](int stage, int i) {
         if constexpr (DBG & 1) return;
@@ -166,7 +159,7 @@ __global__ __launch_bounds__(512, 2) void conv_mfma256_kernel(Conv256K p) {
                 wkc += c;
             }
         }
-        VK_GLDS16((DBG & 32) ? p.zero : wsrc[i] + woff, smem + (stage & (R_NSLOT - 1)) * R_SLOT + dma_w0 + i * 1024);
+        glds16((DBG & 32) ? p.zero : wsrc[i] + woff, smem + (stage & (R_NSLOT - 1)) * R_SLOT + dma_w0 + i * 1024);
     };
 
     // ---- fragment read addresses (bytes inside a slot) ----
@@ -348,78 +341,25 @@ __global__ __launch_bounds__(512, 2) void conv_mfma256_kernel(Conv256K p) {
 #undef VK_MMA_ROW
 #undef VK_READ_W
 
-    // ---- epilogue: + bias (+ residual) (ReLU) -> f16, through LDS so that HBM sees whole lines ----
-    // In the accumulator layout a wave-instruction touches 16 rows x 64 B (half cache lines), and the
-    // per-CU memory pipeline (not HBM) bounds the epilogue of the small-K layers.  The ring is dead now,
-    // so the f32 tile goes through LDS in two 128-row halves ([128][256] f32 = 128 KiB, 16-B chunks
-    // XOR-swizzled by row) and is read back row-contiguous: every residual load and every store of a
-    // wave covers 2 rows x 512 B = 8 whole 128-B lines.
+    // ---- epilogue: + bias (+ residual) (ReLU) -> f16, through LDS so that HBM sees whole lines (StagedEpi, conv_prims.h) ----
+    // The per-CU memory pipeline (not HBM) bounds the epilogue of the small-K layers.  The ring is dead now, so the f32 tile
+    // goes through it in two 128-row halves ([128][256] f32 = 128 KiB).
     asm volatile("s_barrier" ::: "memory");          // every wave has finished reading its fragments
     floatx4 *stg = reinterpret_cast<floatx4 *>(smem);
     // Residual loads are issued a phase ahead of their use (half 0 before the staging writes, half 1
     // before half 0 is written out) and the barriers are raw (lgkmcnt only), so the HBM latency of one
     // half hides behind the LDS work of the other instead of adding up.
-    auto load_res = [&](int h, half8 (&rr)[8]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int it = tid + 512 * i, row = it >> 5, k8 = it & 31;
-            const int m = min(m0 + h * 128 + row, p.M - 1);
-            if (p.res)
-                rr[i] = *reinterpret_cast<const half8 *>(p.res + ((long)m * p.ldy + n0 + k8 * 8) * 2);
-            else
-                rr[i] = half8{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-    };
-    auto stage_half = [&](int h) {
-        if (wr == h) {
-#pragma unroll
-            for (int qn = 0; qn < 2; ++qn) {
-                const int col = wc * 64 + qn * 32 + g * 8;              // tile-local channel of this lane's 8 values
-                const floatx4 b0 = reinterpret_cast<const floatx4 *>(p.bias + n0 + col)[0];
-                const floatx4 b1 = reinterpret_cast<const floatx4 *>(p.bias + n0 + col)[1];
-#pragma unroll
-                for (int mi = 0; mi < 8; ++mi) {
-                    const int row = mi * 16 + j;
-                    const int c16 = col >> 2;
-                    stg[row * 64 + (c16 ^ (row & 7))] = acc[mi][2 * qn] + b0;
-                    stg[row * 64 + ((c16 + 1) ^ (row & 7))] = acc[mi][2 * qn + 1] + b1;
-                }
-            }
-        }
-    };
-    auto write_half = [&](int h, const half8 (&rr)[8]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int it = tid + 512 * i, row = it >> 5, k8 = it & 31;
-            const int m = m0 + h * 128 + row;
-            const floatx4 v0 = stg[row * 64 + ((2 * k8) ^ (row & 7))];
-            const floatx4 v1 = stg[row * 64 + ((2 * k8 + 1) ^ (row & 7))];
-            half8 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float a = v0[e] + (float)rr[i][e], b = v1[e] + (float)rr[i][4 + e];
-                if (p.relu) {
-                    a = a > 0.f ? a : 0.f;
-                    b = b > 0.f ? b : 0.f;
-                }
-                o[e] = (_Float16)a;
-                o[4 + e] = (_Float16)b;
-            }
-            if (m < p.M) *reinterpret_cast<half8 *>(p.y + ((long)m * p.ldy + n0 + k8 * 8) * 2) = o;
-        }
-    };
-#define VK_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
     half8 r0[8], r1[8];
-    load_res(0, r0);
-    stage_half(0);
-    VK_LDS_BARRIER();
-    load_res(1, r1);
-    write_half(0, r0);
-    VK_LDS_BARRIER();
-    stage_half(1);
-    VK_LDS_BARRIER();
-    write_half(1, r1);
-#undef VK_LDS_BARRIER
+    const StagedEpi<512, _Float16, half8, Conv256K> epi{p, tid, g, j, m0, n0, stg};
+    epi.load_res(0, r0);
+    if (wr == 0) epi.stage<0, 8>(wc * 64, acc);
+    lds_barrier();
+    epi.load_res(1, r1);
+    epi.write(0, r0);
+    lds_barrier();
+    if (wr == 1) epi.stage<0, 8>(wc * 64, acc);
+    lds_barrier();
+    epi.write(1, r1);
 }
 
 bool conv256_dual_ok(const ConvArgs &a) {

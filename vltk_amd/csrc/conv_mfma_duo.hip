@@ -25,12 +25,9 @@
 #include <vector>
 
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // element type of the operands / output: f16 (detector) or bf16 (the encoder's GEMMs); accumulation is fp32 either way
 template <typename ET>
@@ -76,10 +73,6 @@ constexpr int D_WB = D_BN * 64;              // 16 KiB: one stage of weight rows
 // MFMA loop (tools/duo_stamps.py), so the product uses XS = 3.
 constexpr int d_smem(int XS) { return XS * D_XB + D_NSLOT * D_WB; }
 
-#define VKD_GLDS16(gptr, lptr)                                                                         \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),          \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
-
 // STAMP: diagnostic build (VK_DUO_STAMPS=<file>): wave 0 records s_memrealtime at the phase boundaries into a
 // buffer nothing else reads (cdna guide section 7, in-kernel stamps); never used by the product path.
 // DBG: ablation bit mask (timing-only STAMP builds, WRONG results; VK_DUO_DBG with VK_DUO_STAMPS): 1 no weight DMA, 2 no pixel
@@ -107,8 +100,7 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(DuoK p) {
     // XCD-aware (bijective) workgroup -> tile map: consecutive tiles (same pixel rows, next channel block)
     // stay on one XCD's L2
     const int bid = blockIdx.x, nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int t = xcd_tile(bid, nwg);
     const int n_tile = t % p.n_tiles, m_tile = t / p.n_tiles;
     const int m0 = m_tile * D_BM, n0 = n_tile * D_BN;
 
@@ -146,13 +138,13 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(DuoK p) {
         if constexpr ((DBG & 2) != 0)
             if (stage >= XS) return;                                 // ablation: no pixel DMA after the prologue
         const char *base = second ? p.x2 : p.x;
-        VKD_GLDS16(base + (a + (unsigned)(stage - (second ? p.split : 0)) * 64u), smem + slot * D_XB + (wave * 2 + i) * 1024);
+        glds16(base + (a + (unsigned)(stage - (second ? p.split : 0)) * 64u), smem + slot * D_XB + (wave * 2 + i) * 1024);
     };
     auto req_w = [&](int stage, int slot, int i) {
         unsigned a = wsrc0;
         asm volatile("" : "+v"(a));
         if constexpr ((DBG & 1) != 0) return;                        // ablation: no weight DMA
-        VKD_GLDS16(p.w + (a + i * wstep + (unsigned)stage * 64u), smem + D_WBASE + slot * D_WB + (wave * 4 + i) * 1024);
+        glds16(p.w + (a + i * wstep + (unsigned)stage * 64u), smem + D_WBASE + slot * D_WB + (wave * 4 + i) * 1024);
     };
 
     // ---- fragment read addresses ----
@@ -353,33 +345,7 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(DuoK p) {
         ts[2] = __builtin_amdgcn_s_memrealtime();
     }
     floatx4 *stg = reinterpret_cast<floatx4 *>(smem);
-    auto load_res = [&](int h, vec8 (&rr)[8]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int it = tid + 256 * i, row = it >> 5, k8 = it & 31;
-            const int m = min(m0 + h * 64 + row, p.M - 1);
-            if (p.res)
-                rr[i] = *reinterpret_cast<const vec8 *>(p.res + ((long)m * p.ldy + n0 + k8 * 8) * 2);
-            else
-                rr[i] = vec8{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-    };
-    auto stage_half = [&](auto h_c) {
-        constexpr int h = decltype(h_c)::value;
-#pragma unroll
-        for (int qn = 0; qn < 2; ++qn) {
-            const int col = wave * 64 + qn * 32 + g * 8;              // tile-local channel of this lane's 8 values
-            const floatx4 b0 = reinterpret_cast<const floatx4 *>(p.bias + n0 + col)[0];
-            const floatx4 b1 = reinterpret_cast<const floatx4 *>(p.bias + n0 + col)[1];
-#pragma unroll
-            for (int mq = 0; mq < 4; ++mq) {
-                const int row = mq * 16 + j;
-                const int c16 = col >> 2;
-                stg[row * 64 + (c16 ^ (row & 7))] = acc[h * 4 + mq][2 * qn] + b0;
-                stg[row * 64 + ((c16 + 1) ^ (row & 7))] = acc[h * 4 + mq][2 * qn + 1] + b1;
-            }
-        }
-    };
+    const StagedEpi<256, ET, vec8, DuoK> epi{p, tid, g, j, m0, n0, stg};      // (conv_prims.h; every wave stages four of its row tiles per half)
     // fused spatial mean: a tile (128 rows) touches at most two images when HoWo >= 128.  This thread's 16 rows
     // of channel group k8 are summed per image from the f16 values a separate mean kernel would read back,
     // EXACTLY: v = floor(v) + frac, both parts accumulated as integers (|floor| <= 65504, frac * 2^24 < 2^24 and
@@ -398,6 +364,8 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(DuoK p) {
         }
     const int img0 = m0 / p.HoWo;
     const int m_split = (img0 + 1) * p.HoWo;         // first row of the tile's second image
+    // (StagedEpi::write of conv_prims.h with the GELU branch and the fused mean hooked in: not used here -- as a per-8-values
+    // hook the GELU build's epilogue came out with other registers, and no benchmark of ours covers that build; same arithmetic)
     auto write_half = [&](int h, const vec8 (&rr)[8]) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -440,21 +408,20 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(DuoK p) {
             }
         }
     };
-#define VKD_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
     vec8 r0[8], r1[8];
-    load_res(0, r0);
-    stage_half(std::integral_constant<int, 0>{});
-    VKD_LDS_BARRIER();
-    load_res(1, r1);
+    epi.load_res(0, r0);
+    epi.template stage<0, 4>(wave * 64, acc);
+    lds_barrier();
+    epi.load_res(1, r1);
     write_half(0, r0);
-    VKD_LDS_BARRIER();
+    lds_barrier();
     if constexpr (STAMP) ts[3] = __builtin_amdgcn_s_memrealtime();
-    stage_half(std::integral_constant<int, 1>{});
-    VKD_LDS_BARRIER();
+    epi.template stage<4, 4>(wave * 64, acc);
+    lds_barrier();
     write_half(1, r1);
     if (p.pool_part) {
         // reduce the 8 row groups (tid >> 5) through LDS, then one thread per channel stores (hi, lo)
-        VKD_LDS_BARRIER();                            // staging reads done
+        lds_barrier();                            // staging reads done
         int *red = reinterpret_cast<int *>(smem);     // [8 groups][2 images][256 channels][hi, lo]
         const int grp = tid >> 5, k8 = tid & 31;
 #pragma unroll
@@ -465,7 +432,7 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(DuoK p) {
                 red[(((grp * 2 + sg) * 256) + k8 * 8 + e) * 2] = bad ? 0x7fffffff : ph[sg][e];
                 red[(((grp * 2 + sg) * 256) + k8 * 8 + e) * 2 + 1] = (int)pl[sg][e];
             }
-        VKD_LDS_BARRIER();
+        lds_barrier();
 #pragma unroll
         for (int sg = 0; sg < 2; ++sg) {
             int hi = 0;
@@ -483,7 +450,6 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(DuoK p) {
             dst[1] = (int)lo;
         }
     }
-#undef VKD_LDS_BARRIER
     if constexpr (STAMP) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ts[4] = __builtin_amdgcn_s_memrealtime();

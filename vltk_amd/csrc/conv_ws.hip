@@ -18,9 +18,10 @@
 //     has no load to wait for;
 //   * workgroups that share an XCD (blockIdx mod 8) and an M lane walk the same pixel tiles with different column blocks,
 //     so a pixel tile is fetched from HBM once per XCD L2 and read from L2 by the other column blocks.
-// Same K order and epilogue arithmetic as conv_mfma_duo.hip / conv_mfma256.hip ((acc + bias) + residual, ReLU, round to f16):
-// a layer's bits do not depend on which of the three the dispatcher picks.
+// Same K order as conv_mfma_duo.hip / conv_mfma256.hip and the epilogue arithmetic of conv_prims.h ((acc + bias) + residual, ReLU on
+// the rounded f16): a layer's bits do not depend on which of the three the dispatcher picks.
 #include "vk_common.h"
+#include "conv_prims.h"
 
 #include <cstdio>
 #include <type_traits>
@@ -28,10 +29,6 @@
 
 namespace vk {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 
 struct WsK {
@@ -51,10 +48,6 @@ struct WsK {
     int HW;                  // rows per image (>= 64: a 64-row tile touches at most two images)
     int H, W, Wo, HoWo, stride;   // STRIDED builds: input geometry of a strided 1x1 conv (x rows are input pixels, M counts output pixels)
 };
-
-#define VKW_GLDS16(gptr, lptr)                                                                         \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),          \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
 
 template <int N>
 __device__ __forceinline__ void ws_vm_wait() {
@@ -153,12 +146,12 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_ws_kernel(WsK p) {
                 const int n_ = m / p.HoWo, r_ = m - n_ * p.HoWo;
                 const int ho = r_ / p.Wo, wo = r_ - ho * p.Wo;
                 const long src = ((long)n_ * p.H + ho * p.stride) * p.W + wo * p.stride;
-                VKW_GLDS16(p.x + src * p.kbytes + st * PITCH + ((dslot ^ (row & (LPR - 1))) << 4), dst + q * 1024);
+                glds16(p.x + src * p.kbytes + st * PITCH + ((dslot ^ (row & (LPR - 1))) << 4), dst + q * 1024);
             } else if constexpr (DUAL) {
                 const int c = dslot ^ (row & (LPR - 1));                          // chunk 0-7: x, 8-15: x2 (one stage per tile)
-                VKW_GLDS16((c < 8 ? p.x : p.x2) + (long)m * 128 + ((c & 7) << 4), dst + q * 1024);
+                glds16((c < 8 ? p.x : p.x2) + (long)m * 128 + ((c & 7) << 4), dst + q * 1024);
             } else {
-                VKW_GLDS16(p.x + (long)m * p.kbytes + st * PITCH + ((dslot ^ (row & (LPR - 1))) << 4), dst + q * 1024);
+                glds16(p.x + (long)m * p.kbytes + st * PITCH + ((dslot ^ (row & (LPR - 1))) << 4), dst + q * 1024);
             }
         }
     };
@@ -213,20 +206,13 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_ws_kernel(WsK p) {
                 const int qn = u >> 2, pt = u & 3;
                 const int ch = wave * WCH + qn * 32 + g * 8;
                 const floatx4 b0 = *reinterpret_cast<const floatx4 *>(bias_lds + ch), b1 = *reinterpret_cast<const floatx4 *>(bias_lds + ch + 4);
-                floatx4 x0 = acc[pt][2 * qn] + b0, x1 = acc[pt][2 * qn + 1] + b1;
-                if constexpr (RES) {
-                    x0 += __builtin_convertvector(__builtin_shufflevector(rr[u - u0], rr[u - u0], 0, 1, 2, 3), floatx4);
-                    x1 += __builtin_convertvector(__builtin_shufflevector(rr[u - u0], rr[u - u0], 4, 5, 6, 7), floatx4);
-                }
-                half4 h0 = __builtin_convertvector(x0, half4), h1 = __builtin_convertvector(x1, half4);
-                half8 o = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-                if constexpr (RELU) o = __builtin_elementwise_max(o, half8{0, 0, 0, 0, 0, 0, 0, 0});
+                half8 o = epi_unit<RES, RELU>(acc[pt][2 * qn], acc[pt][2 * qn + 1], b0, b1, rr[u - u0]);
                 const long m = mbase + pt * 16 + j;
                 if constexpr (POOL) {
                     // the lane's 4 channel pairs of row pt * 16 + j -> the wave's (consumed) residual rows, pair-major: dword
                     // [pair g * 4 + k][(row + g * 16) & 63]; the rotation spreads the 64 lanes over the 64 banks
                     if (!FULL && m >= p.M) o = half8{0, 0, 0, 0, 0, 0, 0, 0};
-                    const uintx4 ov = __builtin_bit_cast(uintx4, o);
+                    const u32x4 ov = __builtin_bit_cast(u32x4, o);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) scr[(gp * 4 + k) * 64 + ((pt * 16 + jp + gp * 16) & 63)] = ov[k];
                 } else {
@@ -242,8 +228,8 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_ws_kernel(WsK p) {
             // lane (pair = lane & 15, quarter = lane >> 4) adds rows quarter * 16 ... + 15 of its two channels in fp64 (exact),
             // the four quarters meet through two lane exchanges, and lanes 0 ... 15 hand the tile's sums to the image's totals
             const int pr = jp, q = gp;
-            const uintx4 *src = reinterpret_cast<const uintx4 *>(scr + pr * 64 + ((q + (pr >> 2)) & 3) * 16);
-            uintx4 v[4];
+            const u32x4 *src = reinterpret_cast<const u32x4 *>(scr + pr * 64 + ((q + (pr >> 2)) & 3) * 16);
+            u32x4 v[4];
 #pragma unroll
             for (int c4 = 0; c4 < 4; ++c4) v[c4] = src[c4];
             double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
@@ -305,11 +291,11 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_ws_kernel(WsK p) {
                 if constexpr (NW == 4) {
                     const int row = q * 8 + (lane >> 3);
                     const int m = min(m0 + row, p.M - 1);
-                    VKW_GLDS16(p.res + ((long)m * p.ldy + n0 + wave * 64) * 2 + (((lane & 7) ^ (row & 7)) << 4), res_lds + q * 1024);
+                    glds16(p.res + ((long)m * p.ldy + n0 + wave * 64) * 2 + (((lane & 7) ^ (row & 7)) << 4), res_lds + q * 1024);
                 } else {
                     const int row = q * 16 + (lane >> 2);
                     const int m = min(m0 + row, p.M - 1);
-                    VKW_GLDS16(p.res + ((long)m * p.ldy + n0 + wave * 32) * 2 + (((lane & 3) ^ rsw(row)) << 4), res_lds + q * 1024);
+                    glds16(p.res + ((long)m * p.ldy + n0 + wave * 32) * 2 + (((lane & 3) ^ rsw(row)) << 4), res_lds + q * 1024);
                 }
             }
         }
@@ -385,23 +371,7 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_ws_kernel(WsK p) {
                 t_b = __builtin_amdgcn_s_memtime();
                 c_rw += t_b - t_a;
             }
-            const bool full = (long)(first + it * ML + 1) * WS_BM <= p.M;
-            auto by_full = [&](auto r, auto l) {
-                if (full)
-                    epilogue(it, r, l, std::true_type{});
-                else
-                    epilogue(it, r, l, std::false_type{});
-            };
-            auto by_relu = [&](auto r) {
-                if (p.relu)
-                    by_full(r, std::true_type{});
-                else
-                    by_full(r, std::false_type{});
-            };
-            if (p.res)
-                by_relu(std::true_type{});
-            else
-                by_relu(std::false_type{});
+            epi_dispatch(p.res, p.relu, (long)(first + it * ML + 1) * WS_BM <= p.M, [&](auto r, auto l, auto f) { epilogue(it, r, l, f); });
             if constexpr (DBG & 32) c_epi += __builtin_amdgcn_s_memtime() - t_b;
         }
     }

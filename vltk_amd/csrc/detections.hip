@@ -26,10 +26,10 @@
 #include <cfloat>
 
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 constexpr int DET_XCDS = 8;                        // as PC_XCDS (per_class.hip): orders the classes, changes no result
 constexpr int DET_LDS_KEYS = VK_DETECTIONS_LDS_KEYS;
 constexpr int DET_FINAL_THREADS = 1024;

@@ -11,10 +11,9 @@
 //
 // fp32 box math, no FMA contraction (-ffp-contract=off for this file), IEEE division.
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 // The pyramid-level rule of the FPN form of the ingest (box_level, vk_common.h); unused in the C4 form.
 struct LevelRule {

@@ -9,10 +9,9 @@
 #include <hip/hip_fp16.h>
 
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 struct GridCell {
     int ys, ye, xs, xe;

@@ -20,10 +20,10 @@
 #include <cfloat>
 
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 constexpr int PC_XCDS = 8;      // accelerator dies of an MI355X; only the order of the classes depends on it, no result does
 
 static __device__ __forceinline__ float pc_wave_max(float v) {

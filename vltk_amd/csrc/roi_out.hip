@@ -18,11 +18,9 @@
 #include <cfloat>
 
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll

@@ -11,8 +11,8 @@
 //   * the conv is an MFMA GEMM with K = 7 kernel rows x 32 (7 taps x 4 channels + 4 zero-weighted elements: the K layout
 //     vk_pack_stem_weight already produces): the B fragment of kernel row kh for 16 consecutive stem pixels is 16 B per lane
 //     straight out of the staged image (pixel stride 16 B, kernel-row stride one image row), the 64 x 224 weights live in
-//     REGISTERS (28 fragments) for the lifetime of the persistent workgroup; same MFMA, same K order, same epilogue arithmetic
-//     as the im2col kernel -> the same bits (its eighth, all-zero K step adds +0);
+//     REGISTERS (28 fragments) for the lifetime of the persistent workgroup; same MFMA and K order as the im2col kernel, the epilogue
+//     arithmetic of conv_prims.h -> the same bits (its eighth, all-zero K step adds +0);
 //   * stem pixels go to LDS as f16 ([pixel][64 ch], 16-B chunks XOR-swizzled by pixel), pixels outside the map as -inf;
 //     then every thread takes the max of 9 chunks (v_pk_max_f16) and writes 16 B of the pooled map;
 //   * 256 threads, 51 KiB of LDS, <= 168 registers: three workgroups per CU overlap each other's phases.
@@ -21,13 +21,9 @@
 #include <cstdlib>
 
 #include "vk_common.h"
+#include "conv_prims.h"
 
 namespace vk {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct StemPoolK {
     const char *x;           // [N, Hp, Wp, 4] f16, zero border of 3
@@ -120,11 +116,7 @@ __global__ __launch_bounds__(256, 3) void stem_pool_kernel(StemPoolK p) {
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const floatx4 bq0 = *reinterpret_cast<const floatx4 *>(bias_lds + q * 32 + gb), bq1 = *reinterpret_cast<const floatx4 *>(bias_lds + q * 32 + gb + 4);
-                // packed adds, v_cvt_pk_f16_f32, ReLU on the rounded halves (the same bits as max before rounding; NaN -> 0 either way)
-                const floatx4 x0 = acc[2 * q] + bq0, x1 = acc[2 * q + 1] + bq1;
-                const half4 h0 = __builtin_convertvector(x0, half4), h1 = __builtin_convertvector(x1, half4);
-                half8 o = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-                o = __builtin_elementwise_max(o, half8{0, 0, 0, 0, 0, 0, 0, 0});
+                half8 o = epi_unit<false, true>(acc[2 * q], acc[2 * q + 1], bq0, bq1, ninf);      // (no residual: the last argument is not read)
                 if (!valid) o = ninf;
                 *reinterpret_cast<half8 *>(st_lds + idx * 128 + (((q * 4 + g) ^ (idx & 7)) << 4)) = o;
             }
