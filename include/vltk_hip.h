@@ -606,6 +606,55 @@ int vk_loss_reduce(const float *row_loss, const float *weight, const int64_t *la
  * of `present` says that term i takes part: total = 0 + mlm + matched + (0 + obj + attr + feat) + answer. */
 int vk_loss_total(const float *terms, int present, float *out, void *stream);
 
+/* ---- N7: training an answer head over a frozen encoder (vltk/legacy/legacy_train.py; csrc/train.hip) ----
+ * fp32 in memory; no atomics and no split-K: one writer and one summation order per output, the same bits on every run. */
+/* C[M, N] = op(A) . op(B) (+ bias[N]) (+ C when accumulate), row-major fp32 with leading dimensions of their own.  transA 0: A is
+ * [M, K] (lda >= K), 1: A is [K, M] (lda >= M); transB 0: B is [K, N] (ldb >= N), 1: B is [N, K] (ldb >= K), the layout of
+ * nn.Linear's weight.  Y = X . W^T + b is (0, 1), dX = dY . W is (0, 0), dW = dY^T . X is (1, 0).  Any M, N, K >= 1; edges are
+ * masked.  Each output element is one fmaf chain in ascending k on the fp32-input matrix instruction, started from
+ * (accumulate ? C : 0) + bias: data whose sums stay below 2^24 is exact.  bias may be NULL. */
+int vk_gemm_f32(const float *A, long lda, int transA, const float *B, long ldb, int transB, const float *bias, float *C, long ldc,
+                int M, int N, int K, int accumulate, void *stream);
+/* What the launch refuses, without a device: a size below 1, a flag that is neither 0 nor 1, a leading dimension below the row
+ * width.  VK_OK or VK_EINVAL. */
+int vk_gemm_f32_check(int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB);
+/* out[c] = sum_m x[m, c]: fp64 adds in a fixed order, rounded to f32 once.  M > 256 runs in two stages through `workspace`
+ * (8-byte aligned, the bytes the size function names; 0 bytes and NULL where M <= 256). */
+size_t vk_col_sums_workspace_bytes(int M, int N);
+int vk_col_sums(const float *x, long ld, int M, int N, float *out, void *workspace, size_t workspace_bytes, void *stream);
+/* dlogits[m, :C] = (softmax(logits[m, :C]) - onehot(labels[m])) * scale, the row maximum subtracted before the exponential: the
+ * gradient of `CrossEntropyLoss()` with scale = 1 / (rows whose label is not ignore_index).  Rows with that label are written as
+ * zeros; a label that is neither it nor in [0, C) gives a row of NaN and reads nothing.  ignore_index < 0; ld, ldd >= C. */
+int vk_cross_entropy_grad(const float *logits, long ld, int M, int C, const int64_t *labels, int ignore_index, float scale,
+                          float *dlogits, long ldd, void *stream);
+/* y = act(x) and dx = dy * act'(x) over n elements; act VK_ACT_GELU (erf form) or VK_ACT_TANH, anything else VK_EINVAL.  The
+ * backward takes the pre-activation x, which the caller keeps.  fp64 arithmetic, one rounding at the store. */
+int vk_act_f32(const float *x, float *y, long n, int act, void *stream);
+int vk_act_grad_f32(const float *x, const float *dy, float *dx, long n, int act, void *stream);
+/* The backward of y = gamma * (x - mean) / sqrt(var + eps) + beta over rows of C: dx [M, lddx], dgamma [C], dbeta [C] from x, gamma
+ * and dy.  Mean and variance are recomputed from x; fp64 arithmetic, fixed-order column sums, one rounding at each store.
+ * workspace: 8-byte aligned, the bytes the size function names. */
+size_t vk_layernorm_grad_workspace_bytes(int M, int C);
+int vk_layernorm_grad(const float *x, long ldx, const float *gamma, const float *dy, long lddy, float *dx, long lddx, float *dgamma,
+                      float *dbeta, int M, int C, double eps, void *workspace, size_t workspace_bytes, void *stream);
+/* One record of vk_adamw_step's table (device memory): n elements of a parameter, its gradient and its two moments, each
+ * starting at any 4-byte boundary; decay != 0: the tensor takes weight decay. */
+typedef struct {
+    float *p;
+    const float *g;
+    float *m;
+    float *v;
+    int64_t n;
+    int32_t decay;
+    int32_t reserved;
+} vk_adamw_tensor;
+/* torch.optim.AdamW's step over `count` tensors in one launch (max_n: the largest n of the table):
+ * m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g^2; p = p (1 - lr weight_decay) where the record decays;
+ * p = p - lr / bias_correction1 * m / (sqrt(v) / sqrt(bias_correction2) + eps).  The caller computes bias_correction_i =
+ * 1 - beta_i^step in fp64.  fp64 arithmetic on the fp32 values; m, v and p are rounded once each, at the store. */
+int vk_adamw_step(const vk_adamw_tensor *table, int count, int64_t max_n, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, double bias_correction1, double bias_correction2, void *stream);
+
 /* ---- N4: FPN-side ops (what north_star names; the reference holds only fragments, see oracle/fpn_oracle.py) ---- */
 
 /* RoIAlign over a feature pyramid (torchvision roi_align semantics, `aligned` as detectron2's ROIAlignV2; the level loop of

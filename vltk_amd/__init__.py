@@ -34,4 +34,7 @@ def __getattr__(name):
                 "layoutlm_config", "ocr_token_boxes"):       # the document encoder: OCR words and their boxes
         from . import layoutlm
         return getattr(layoutlm, name)
+    if name in ("HeadTrainer", "step_lr", "linear_warmup"):    # N7: train a head over a frozen encoder
+        from . import train
+        return getattr(train, name)
     raise AttributeError(name)

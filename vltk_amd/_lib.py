@@ -78,6 +78,11 @@ class vk_outputs(C.Structure):
     ]
 
 
+class vk_adamw_tensor(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64), ("decay", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class vk_ignorey(C.Structure):
     _fields_ = [("bands", C.c_void_p), ("counts", C.c_void_p), ("max_per_image", C.c_int32), ("f64", C.c_int32)]
 
@@ -151,6 +156,16 @@ SIGNATURES = {
     "vk_smooth_l1_rows": (_I, [_P, _I, _P, _I, _I, _I, _P, _I, _P]),
     "vk_loss_reduce": (_I, [_P, _P, _P, _I, _I, _F, _P, _P]),
     "vk_loss_total": (_I, [_P, _I, _P, _P]),
+    "vk_gemm_f32": (_I, [_P, C.c_long, _I, _P, C.c_long, _I, _P, _P, C.c_long, _I, _I, _I, _I, _P]),
+    "vk_gemm_f32_check": (_I, [_I, _I, _I, C.c_long, C.c_long, C.c_long, _I, _I]),
+    "vk_col_sums_workspace_bytes": (_SZ, [_I, _I]),
+    "vk_col_sums": (_I, [_P, C.c_long, _I, _I, _P, _P, _SZ, _P]),
+    "vk_cross_entropy_grad": (_I, [_P, C.c_long, _I, _I, _P, _I, _F, _P, C.c_long, _P]),
+    "vk_act_f32": (_I, [_P, _P, C.c_long, _I, _P]),
+    "vk_act_grad_f32": (_I, [_P, _P, _P, C.c_long, _I, _P]),
+    "vk_layernorm_grad_workspace_bytes": (_SZ, [_I, _I]),
+    "vk_layernorm_grad": (_I, [_P, C.c_long, _P, _P, C.c_long, _P, C.c_long, _P, _P, _I, _I, _D, _P, _SZ, _P]),
+    "vk_adamw_step": (_I, [_P, _I, C.c_int64, _D, _D, _D, _D, _D, _D, _D, _P]),
     "vk_roi_align": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "vk_roi_align_form": (_I, [_I, _I, _I]),
     "vk_assign_levels": (_I, [_P, _I, _I, _I, _I, _F, _I, _P, _P]),

@@ -107,6 +107,16 @@ def refill(static, new):
             s.copy_(n)
 
 
+def keep_head(enc, sd, *prefixes):
+    """The fp32 host tensors of a head's layers (`<prefix>.weight`, `<prefix>.bias`) into `enc._head`, by state-dict key, beside
+    their packed copies: a few MB, where `HeadTrainer`'s masters start.  A plain function: whatever stands where the encoder
+    stands in a wrapper's `load_state_dict` takes it."""
+    head = enc.__dict__.setdefault("_head", {})
+    for p in prefixes:
+        for k in (p + ".weight", p + ".bias"):
+            head[k] = np.array(sd[k], np.float32)
+
+
 class Model:
     """What an encoder and a head wrapper around one have in common as objects."""
 

@@ -19,8 +19,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .bert_ops import LN_EPS, BertOps, Model, additive_mask, bert_layer_spec, check_text_inputs, host_array, require_gelu, seeded_tensor, \
-    to_numpy
+from .bert_ops import LN_EPS, BertOps, Model, additive_mask, bert_layer_spec, check_text_inputs, host_array, keep_head, require_gelu, \
+    seeded_tensor, to_numpy
 from .layers import stream
 
 DEFAULT_CONFIG = dict(vocab_size=30522, hidden_size=768, num_attention_heads=12, num_hidden_layers=12, intermediate_size=3072,
@@ -219,6 +219,7 @@ class _Head(Model):
         enc = self.layoutlm
         sd = self._load_with_encoder(enc, "layoutlm.", layoutlm_head_param_spec(enc.cfg, self._HEAD, self.num_labels), sd, strict)
         enc._load_lin(sd, self._HEAD, self._HEAD)
+        keep_head(enc, sd, self._HEAD)
         return self
 
 
@@ -309,7 +310,15 @@ class LayoutLMForQuestionAnswering(_Head):
 class LayoutLMForSequenceClassification(_Head):
     """`transformers.LayoutLMForSequenceClassification`: `classifier` on the pooled output -> logits [B, num_labels]."""
 
+    def _head_features(self, *inputs):
+        return self.layoutlm._forward(*inputs)[1]
+
+    @torch.no_grad()
+    def head_features(self, input_ids, bbox=None, attention_mask=None, token_type_ids=None):
+        """What `classifier` consumes: the pooled output [B, H], storage type (`HeadTrainer.step_features` takes it)."""
+        return self.layoutlm._run(self._head_features, (input_ids, bbox, attention_mask, token_type_ids))
+
     @torch.no_grad()
     def __call__(self, input_ids, bbox=None, attention_mask=None, token_type_ids=None):
         enc = self.layoutlm
-        return enc._run(lambda *inputs: enc._linear(enc._forward(*inputs)[1], "classifier"), (input_ids, bbox, attention_mask, token_type_ids))
+        return enc._run(lambda *inputs: enc._linear(self._head_features(*inputs), "classifier"), (input_ids, bbox, attention_mask, token_type_ids))

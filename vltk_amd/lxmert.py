@@ -15,7 +15,7 @@ import torch
 
 from . import _lib as L
 from .bert_ops import LN_EPS, BertOps, Model, additive_mask, attention_spec, bert_layer_spec, check_text_inputs, dense_ln_spec, host_array, \
-    seeded_tensor, to_numpy
+    keep_head, seeded_tensor, to_numpy
 from .layers import stream
 
 DEFAULT_CONFIG = dict(vocab_size=30522, hidden_size=768, num_attention_heads=12, intermediate_size=3072, l_layers=9, x_layers=5,
@@ -200,6 +200,7 @@ def load_answer_head(enc, sd):
     enc._load_lin(sd, "answer.fc0", "answer_head.logit_fc.0")
     enc._load_lin(sd, "answer.fc3", "answer_head.logit_fc.3")
     enc._load_ln(sd, "answer_head.logit_fc.2")
+    keep_head(enc, sd, "answer_head.logit_fc.0", "answer_head.logit_fc.2", "answer_head.logit_fc.3")
 
 
 def answer_head(enc, pooled):
@@ -239,6 +240,13 @@ class LxmertForQuestionAnswering(Model):
         load_answer_head(enc, self._load_with_encoder(enc, "lxmert.", lxmert_qa_param_spec(enc.cfg, self.num_qa_labels), sd, strict))
         return self
 
+    def _head_features(self, *inputs):
+        return self.lxmert._forward(*inputs)[2]
+
+    def head_features(self, input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None):
+        """What the answer head consumes: the pooled output [B, H], storage type (`HeadTrainer.step_features` takes it)."""
+        return self.lxmert._run(self._head_features, (input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids))
+
     @torch.no_grad()
     def __call__(self, input_ids, visual_feats, visual_pos, attention_mask=None, visual_attention_mask=None, token_type_ids=None,
                  labels=None):
@@ -248,7 +256,7 @@ class LxmertForQuestionAnswering(Model):
 
         def forward(*inputs):
             lab = None if labels is None else check_class_labels("labels", labels, (input_ids.shape[0],), self.num_qa_labels)
-            score = answer_head(enc, enc._forward(*inputs)[2])
+            score = answer_head(enc, self._head_features(*inputs))
             if lab is None:
                 return score
             loss = torch.empty((), dtype=torch.float32, device=enc.device)

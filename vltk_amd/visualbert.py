@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .bert_ops import LN_EPS, BertOps, Model, additive_mask, bert_layer_spec, check_ids, check_text_inputs, host_array, require_gelu, \
+from .bert_ops import LN_EPS, BertOps, Model, additive_mask, bert_layer_spec, check_ids, check_text_inputs, host_array, keep_head, require_gelu, \
     seeded_tensor, to_numpy
 from .layers import stream
 
@@ -221,8 +221,25 @@ class VisualBertForQuestionAnswering(Model):
 
     def load_state_dict(self, sd, strict=True):
         enc = self.visual_bert
-        enc._load_lin(self._load_with_encoder(enc, "visual_bert.", visualbert_qa_param_spec(enc.cfg, self.num_labels), sd, strict), "cls", "cls")
+        sd = self._load_with_encoder(enc, "visual_bert.", visualbert_qa_param_spec(enc.cfg, self.num_labels), sd, strict)
+        enc._load_lin(sd, "cls", "cls")
+        keep_head(enc, sd, "cls")
         return self
+
+    def _head_features(self, *inputs):
+        enc = self.visual_bert
+        input_ids, visual_embeds, attention_mask = inputs[:3]
+        B, Lt = input_ids.shape
+        idx = torch.from_numpy(qa_gather_index(attention_mask, B, Lt, visual_embeds.shape[1])).to(enc.device)    # host, before any launch
+        seq, _ = enc._forward(*inputs)
+        return enc._gather_rows(seq.view(-1, enc.cfg["hidden_size"]), idx)
+
+    def head_features(self, input_ids, visual_embeds, attention_mask=None, visual_attention_mask=None, token_type_ids=None,
+                      visual_token_type_ids=None, image_text_alignment=None):
+        """What `cls` consumes: row `attention_mask.sum(1) - 2` of each sequence [B, H], storage type (`HeadTrainer.step_features`
+        takes it; the dropout transformers puts before `cls` in training mode is not applied)."""
+        return self.visual_bert._run(self._head_features, (input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids,
+                                                          visual_token_type_ids, image_text_alignment))
 
     @torch.no_grad()
     def __call__(self, input_ids, visual_embeds, attention_mask=None, visual_attention_mask=None, token_type_ids=None,
@@ -230,9 +247,6 @@ class VisualBertForQuestionAnswering(Model):
         enc = self.visual_bert
 
         def forward(*inputs):
-            B, Lt = input_ids.shape
-            idx = torch.from_numpy(qa_gather_index(attention_mask, B, Lt, visual_embeds.shape[1])).to(enc.device)    # host, before any launch
-            seq, _ = enc._forward(*inputs)
-            return enc._linear(enc._gather_rows(seq.view(-1, enc.cfg["hidden_size"]), idx), "cls")
+            return enc._linear(self._head_features(*inputs), "cls")
         return enc._run(forward, (input_ids, visual_embeds, attention_mask, visual_attention_mask, token_type_ids, visual_token_type_ids,
                                   image_text_alignment))

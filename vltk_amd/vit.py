@@ -21,7 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .bert_ops import LN_EPS, BertOps, Model, require_gelu, seeded_tensor, to_numpy
+from .bert_ops import LN_EPS, BertOps, Model, keep_head, require_gelu, seeded_tensor, to_numpy
 from .layers import stream
 
 DEFAULT_CONFIG = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, hidden_act="gelu",
@@ -316,14 +316,23 @@ class ViTForImageClassification(Model):
         sd = self._load_with_encoder(enc, "vit.", vit_classifier_param_spec(enc.cfg, self.num_labels), sd, strict,
                                      rekey=lambda sd: rename_hub_keys(sd, prefix="vit."))
         enc._load_lin(sd, "classifier", "classifier")
+        keep_head(enc, sd, "classifier")
         return self
+
+    def _head_features(self, pixel_values):
+        enc = self.vit
+        x, B, Lx = enc._sequence(pixel_values)
+        idx = (torch.arange(B, dtype=torch.int32, device=enc.device) * Lx).contiguous()
+        return enc._gather_rows(x, idx)                                         # the class row of each sequence
+
+    @torch.no_grad()
+    def head_features(self, pixel_values, interpolate_pos_encoding=False):
+        """What `classifier` consumes: the class row of the normalised sequence output [B, H], storage type
+        (`HeadTrainer.step_features` takes it)."""
+        return self.vit._run(self._head_features, (pixel_values,), interpolate_pos_encoding=interpolate_pos_encoding)
 
     @torch.no_grad()
     def __call__(self, pixel_values, interpolate_pos_encoding=False):
         enc = self.vit
-
-        def forward(pixel_values):
-            x, B, Lx = enc._sequence(pixel_values)
-            idx = (torch.arange(B, dtype=torch.int32, device=enc.device) * Lx).contiguous()
-            return enc._linear(enc._gather_rows(x, idx), "classifier")          # the class row of each sequence
-        return enc._run(forward, (pixel_values,), interpolate_pos_encoding=interpolate_pos_encoding)
+        return enc._run(lambda pixel_values: enc._linear(self._head_features(pixel_values), "classifier"), (pixel_values,),
+                        interpolate_pos_encoding=interpolate_pos_encoding)
