@@ -182,7 +182,8 @@ int vk_destroy(vk_handle *h);
  * vk_option_default gives the value a new handle starts with (the variable, where it holds a valid value); both are host only.
  * vk_get_option reads an option back, and two read-only counters for tests and tools: "working_sets" (arenas the handle
  * holds: 0, 1 or 2), "lane_forwards" (forwards that ran on a stream of the handle's own since vk_create) and
- * "dedupe_chunks" (Res5 chunks that took the "head_dedupe" path since vk_create). */
+ * "dedupe_chunks" (Res5 chunks that took the "head_dedupe" path since vk_create), "indexed_chunks" (those of them whose conv2 read
+ * conv1's distinct rows through the index, without the row gather: vk_panel_phase_indexed). */
 int vk_set_option(vk_handle *h, const char *key, int value);
 int vk_get_option(vk_handle *h, const char *key, int *value);
 int vk_option_check(const char *key, int value);
@@ -437,6 +438,12 @@ int vk_panel_phase_tile_rows(int N, int H, int W, int dil, int cout);
  * tap reads its own fragments (VK_PANEL_REUSE=0), or the launch has no 512-row phase tile (vk_panel_phase_tile_rows != 512).  The
  * two schedules issue the same matrix instructions on the same operands in the same order: the same bits. */
 int vk_panel_phase_reuse(int N, int H, int W, int dil, int cout);
+/* Whether that launch can read its input through a row index (vk_conv2d_rows; host only; VK_PANEL_INDEXED is re-read per call):
+ * 1 = the WHOLE launch runs the 512-row fragment-window tile (vk_panel_phase_images == N and vk_panel_phase_reuse == 1), the one
+ * form that takes an index; 0 = it does not (N is not a multiple of 16, the shape has no phase form, one of VK_PANEL_PHASE / TALL /
+ * REUSE is 0), or VK_PANEL_INDEXED=0 keeps the gather + dense launch everywhere.  A row's bits do not depend on where its input
+ * row lives: the indexed launch and vk_gather_rows + vk_conv2d give the same bits. */
+int vk_panel_phase_indexed(int N, int H, int W, int dil, int cout);
 
 /* conv3 + projection shortcut of a stride-1 BottleneckBlock as ONE f16 GEMM (`out = conv3(t) ; out += shortcut(x)`,
  * frcnn.py:970-977): y[M,cout] = relu?([x1 | x2] . W^T + bias (+ residual)), W rows = [conv3 row (cin1) | shortcut row
@@ -790,6 +797,13 @@ int vk_gather_rows(const void *src, const int32_t *idx, long rows, int row_bytes
  * position, on M' or on which of these forms computes it. */
 int vk_conv1x1_rows(const void *x1, int cin1, const void *x2, int cin2, long M, const int32_t *m_dev, const int32_t *x2_idx,
                     const void *w_packed, const float *bias_packed, void *y, int cout, int relu, void *stream);
+/* The VK_ROUTE_PANEL kernel on de-duplicated input rows (f16, 3x3, stride 1, pad == dil): vk_conv2d of the tensor whose row m is
+ * x[x_idx[m]], m < N*H*W, without that tensor being written.  x is [x_rows, cin]; x_idx holds N*H*W entries, every one in
+ * [0, x_rows): the index is a contract, the kernel does not check it.  residual / y [N*H*W, cout] go by m.  VK_EINVAL, before any
+ * launch, where vk_panel_phase_indexed answers 0 for the launch, where the layer is not a VK_ROUTE_PANEL launch, or where
+ * x_rows * cin * 2 reaches 2^32.  Same bits as vk_gather_rows + vk_conv2d. */
+int vk_conv2d_rows(const void *x, long x_rows, const int32_t *x_idx, int N, int H, int W, int cin, const void *w_packed,
+                   const float *bias_packed, const void *residual, void *y, int cout, int dil, int relu, void *stream);
 
 /* mean over the P*P positions of each RoI  <- frcnn.py:1401: x [K,S,C] (dt) -> out [K,C] f32 */
 int vk_mean_pool(const void *x, int K, int S, int C, float *out, vk_dtype dt, void *stream);

@@ -24,7 +24,7 @@ rm -rf $OUT/${TAG}_pmc_mfma
 find $OUT/${TAG}_prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${TAG}_kernel_stats.csv
 # HBM bytes per launch of the three kernels with the most GPU time (the two-per-CU kernel no longer has launches that run alone) (launches that run alone: the half-batch launches of the
 # two-stream backbone section carry other template arguments)
-python tools/pmc_summary.py $OUT/${TAG}_pmc "conv3x3_panel_kernel<6, 0, 0, 8, 2, 4, 1>" --json $OUT/${TAG}_pmc_panel.json --name conv3x3_panel_kernel --batch 32 --proposals 300 --alg-bytes 3858235392 > $OUT/${TAG}_pmc_summary.txt
+python tools/pmc_summary.py $OUT/${TAG}_pmc "conv3x3_panel_kernel<6, 0, 0, 8, 2, 4, 1," --json $OUT/${TAG}_pmc_panel.json --name conv3x3_panel_kernel --batch 32 --proposals 300 --alg-bytes 3858235392 > $OUT/${TAG}_pmc_summary.txt
 python tools/pmc_summary.py $OUT/${TAG}_pmc "conv_gemm4_kernel<false, 0, 0>" --json $OUT/${TAG}_pmc_gemm4.json --name conv_gemm4_kernel --batch 32 --proposals 300 >> $OUT/${TAG}_pmc_summary.txt
 python tools/pmc_summary.py $OUT/${TAG}_pmc "conv_ws_kernel" --json $OUT/${TAG}_pmc_ws.json --name conv_ws_kernel --batch 32 --proposals 300 --min-workgroups 200 >> $OUT/${TAG}_pmc_summary.txt
 python - <<PY

@@ -65,6 +65,8 @@ struct PanelK {
     // PHASE form only
     int groups;               // M / (16 * HW)
     unsigned rcp_w2;          // 65536 / (W / 2) + 1: q / (W / 2) == (q * rcp_w2) >> 16 for q < 9362
+    // IDX builds only: natural row m of the launch reads row x_idx[m] of x; [groups * 16 * HW] entries
+    const int *x_idx;
 };
 
 // PHASE form: 16-row block `gb` of a group ([phase][qy][qx], HW blocks) -> its position in the phase's grid, and the natural row
@@ -171,7 +173,12 @@ static_assert(reuse_window_ok(), "REUSE: (tap, row tile) -> window slot -> panel
 // in the same order, so the tile shape does not change a bit.
 // REUSE: 1 = the A-fragment window above (512 x 128 phase tiles only): 66 instead of 108 ds_read_b128 per wave and stage, the same
 // MFMAs on the same operands in the same order.  0 (VK_PANEL_REUSE=0) = every tap reads its eight fragments.
-template <int PP, int DBG, int TAG = 0, int MI = 8, int PHASE = 0, int WR = 2, int REUSE = 0>
+// IDX: 1 = INDEXED INPUT ROWS (the 512 x 128 REUSE phase form only): output and internal row m reads row x_idx[m] of x,
+// which is then [*, Cin] and not [M, Cin] (Res5 block 0: conv1's rows exist once per distinct RoIPool window).  y, res, the validity
+// words and the epilogue go by m.  req_panel is the only place the input is addressed: a lane's six source offsets of a tile are
+// x_idx[its natural row] * cin_bytes, six registers loaded once per tile, where the dense form adds a uniform block offset to ps_lane.
+// The K loop, its vmcnt / lgkmcnt tables, the fragment window and the MFMAs are those of IDX = 0.
+template <int PP, int DBG, int TAG = 0, int MI = 8, int PHASE = 0, int WR = 2, int REUSE = 0, int IDX = 0>
 __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(MI == 8 || MI == 9, "8 or 9 row tiles per wave");
@@ -180,6 +187,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     static_assert(WR == 2 || PHASE == 2, "512 x 128 tiles: the phase form only (a plain res4 launch would read its panel twice)");
     static_assert(MI == 8 || !(DBG & 8), "the LDS-staged epilogue is written for 128-row halves");
     static_assert(!REUSE || (PHASE == 2 && WR == 4 && MI == 8 && DBG == 0), "the fragment window: tap shifts of whole 16-row tiles, 512 x 128 tiles");
+    static_assert(!IDX || (PHASE == 2 && WR == 4 && REUSE == 1 && DBG == 0 && PP == 6), "indexed input rows: the 512 x 128 REUSE phase form only");
     constexpr int WC = 8 / WR;                    // column blocks of 64 channels
     constexpr int CT = 64 * WC;                   // channels per tile: 256 or 128
     constexpr int NWP = CT / 128;                 // weight DMA pieces (16 rows) per wave and step: 2 or 1
@@ -262,7 +270,20 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     // PHASE: a wave's 16 rows of a panel piece are one block: image lrow of the group (per lane) at one pixel (uniform).  The PP
     // source offsets are found once per tile; rows outside the tensor are clamped to a real block as below.
     [[maybe_unused]] unsigned ps_lane = 0, ps_blk[PP] = {};
-    if constexpr (PHASE) {
+    // IDX: the index of the lane's row of each piece, requested HERE, ahead of everything else the tile asks of memory: one
+    // global_load_dword per piece at natural row (G * 16 + lrow) * HW + the block's pixel.  blk_of clamps every halo block into
+    // [0, groups * 16 * HW), so x_idx is never read out of range (a clamped halo row is only read by taps the validity words drop).
+    // The prologue turns the six indices into byte offsets once they have landed.
+    [[maybe_unused]] unsigned ps_idx[PP] = {};
+    if constexpr (IDX) {
+#pragma unroll
+        for (int q2 = 0; q2 < PP; ++q2) {
+            int G;
+            const int t = blk_of(wave - HALO / 16 + q2 * 8, G);
+            const int *ip = p.x_idx + ((long)(G * 16 + lrow) * p.HW + phase_blk(p, t).row);
+            asm volatile("global_load_dword %0, %1, off" : "=v"(ps_idx[q2]) : "v"(ip));
+        }
+    } else if constexpr (PHASE) {
         ps_lane = (unsigned)(lrow * p.HW) * (unsigned)p.cin_bytes + lchunk * 16;
 #pragma unroll
         for (int q2 = 0; q2 < PP; ++q2) {
@@ -272,6 +293,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         }
     }
     auto req_panel = [&](int cs, int piece) {                 // rows (piece*8 + wave)*16 .. +15 of panel(cs)
+        if constexpr (IDX) {
+            unsigned pl = ps_idx[piece];
+            asm volatile("" : "+v"(pl));                       // opaque (see x_addr_of)
+            glds16(p.x + (pl + cs * 64), smem + (cs & 1) * PBYTES + (piece * 8 + wave) * 1024);
+            return;
+        }
         if constexpr (PHASE) {
             unsigned pl = ps_lane;
             asm volatile("" : "+v"(pl));                       // opaque (see x_addr_of)
@@ -525,8 +552,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     using F_ = std::integral_constant<bool, false>;
 
     // ---- prologue: panel(0), weights of steps 0..5; panel(0) and weights(0) must have landed ----
+    // (IDX: the panel pieces wait for their indices and go out behind the validity words, see below)
+    if constexpr (!IDX) {
 #pragma unroll
-    for (int q2 = 0; q2 < PP; ++q2) req_panel(0, q2);
+        for (int q2 = 0; q2 < PP; ++q2) req_panel(0, q2);
+    }
 #pragma unroll
     for (int st = 0; st < P_NW; ++st) {
         req_w(st, 0, st, 0);
@@ -603,7 +633,27 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
         }
     }
 
-    vm_wait<NWP * (P_NW - 1)>();                  // all but the weights of steps 1..5: panel(0) and the weights of step 0 are in LDS
+    if constexpr (IDX) {
+        // The index loads count in vmcnt like every vector-memory instruction, and loads retire in order: behind them only the
+        // P_NW * NWP weight pieces have been issued, so vmcnt(P_NW * NWP) says all six indices are in their registers (the wait names
+        // them, so nothing that reads them moves above it).  Offsets: x_idx[m] * cin_bytes < 2^32, the launcher checks x's rows.
+        // Then the panel pieces, and vmcnt(0): the pieces are now the NEWEST requests, so no count short of zero covers them.
+        // That keeps every table of the K loop as it is: a step's wait says "at most N requests outstanding, all issued inside the
+        // window"; step 0 (FIRST) allows the prologue's NWP * (P_NW - 2) newest weight pieces and finds none outstanding, which
+        // satisfies it, and every later window reaches back to POSTs of the K loop alone, whose issue order has not changed.
+        static_assert(PP == 6 && P_NW * NWP <= 15);
+        asm volatile("s_waitcnt vmcnt(%6)"
+                     : "+v"(ps_idx[0]), "+v"(ps_idx[1]), "+v"(ps_idx[2]), "+v"(ps_idx[3]), "+v"(ps_idx[4]), "+v"(ps_idx[5])
+                     : "n"(P_NW * NWP)
+                     : "memory");
+#pragma unroll
+        for (int q2 = 0; q2 < PP; ++q2) ps_idx[q2] = ps_idx[q2] * (unsigned)p.cin_bytes + lchunk * 16;
+#pragma unroll
+        for (int q2 = 0; q2 < PP; ++q2) req_panel(0, q2);
+        vm_wait<0>();
+    } else {
+        vm_wait<NWP * (P_NW - 1)>();              // all but the weights of steps 1..5: panel(0) and the weights of step 0 are in LDS
+    }
     asm volatile("s_barrier" ::: "memory");
     unsigned long st_c0 = 0, st_r0 = 0;
     if constexpr (DBG & 4) asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_c0), "=s"(st_r0)::"memory");
@@ -766,7 +816,7 @@ bool conv3x3_panel_eligible(const ConvArgs &a) {
     if (a.kh != 3 || a.kw != 3 || a.stride != 1 || a.pad != a.dil) return false;
     if (a.Cout % 256 != 0 || a.ldy != a.Cout || a.Cin % 64 != 0 || a.Cin < 128) return false;
     if (panel_pp(a) == 0) return false;
-    if ((long)a.N * a.H * a.W * a.Cin * 2 >= (1L << 32)) return false;   // 32-bit DMA offsets
+    if ((a.x_idx ? a.x_rows : (long)a.N * a.H * a.W) * a.Cin * 2 >= (1L << 32)) return false;   // 32-bit DMA offsets (of the indexed tensor, with x_idx)
     // no lower bound on M: the K walk (channel-stage major, tap minor) sums in a different order than the
     // im2col kernels, and a layer's bits must not depend on how many RoIs share a launch (head chunking)
     return true;
@@ -800,10 +850,22 @@ int conv3x3_panel_phase_reuse(const ConvArgs &a) {
     return env_off("VK_PANEL_REUSE") ? 0 : 1;
 }
 
+// 1 where the WHOLE launch runs the 512 x 128 fragment-window phase form, the one form that reads its input through a row index
+// (ConvArgs::x_idx): every image in a group of 16, none of VK_PANEL_PHASE / TALL / REUSE = 0.  VK_PANEL_INDEXED=0
+// answers 0 everywhere: callers then gather the rows and launch the dense form (the A/B and bit-identity partner).
+int conv3x3_panel_phase_indexed(const ConvArgs &a) {
+    if (env_off("VK_PANEL_INDEXED")) return 0;
+    return conv3x3_panel_phase_images(a) == a.N && conv3x3_panel_phase_reuse(a) == 1 ? 1 : 0;
+}
+
 static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase);
 
 int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream) {
     const int np = conv3x3_panel_phase_images(a);
+    // a row index is read by one instantiation alone: any other form would run on the wrong rows
+    VK_REQUIRE(!a.x_idx || conv3x3_panel_phase_indexed(a), VK_EINVAL,
+               "conv3x3_panel: x_idx needs the whole launch in the 512 x 128 fragment-window phase form (N %% 16 == 0, dilation 2, even H, "
+               "even W <= 14; VK_PANEL_PHASE / TALL / REUSE / INDEXED not 0): N=%d H=%d W=%d dil=%d", a.N, a.H, a.W, a.dil);
     if (np == 0) return launch_panel_one(a, stream, false);
     ConvArgs b = a;
     b.N = np;
@@ -832,8 +894,12 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
     k.HW = a.H * a.W;
     const long M = (long)a.N * a.H * a.W;
     VK_REQUIRE(M > 0 && M < (1L << 31) - 512, VK_EINVAL, "conv3x3_panel: M=%ld out of range", M);
-    VK_REQUIRE(M * a.Cin * 2 < (1L << 32) && (long)a.Cout * 9 * a.Cin * 2 < (1L << 32), VK_EINVAL,
-               "conv3x3_panel: tensor beyond the 32-bit DMA offsets (M=%ld Cin=%d Cout=%d)", M, a.Cin, a.Cout);
+    // (with x_idx the offsets are those of the indexed tensor: the caller states its rows)
+    VK_REQUIRE(!a.x_idx || a.x_rows > 0, VK_EINVAL, "conv3x3_panel: x_idx needs x_rows > 0, the rows of x (got %ld)", a.x_rows);
+    const long xr = a.x_idx ? a.x_rows : M;
+    VK_REQUIRE(xr * a.Cin * 2 < (1L << 32) && (long)a.Cout * 9 * a.Cin * 2 < (1L << 32), VK_EINVAL,
+               "conv3x3_panel: tensor beyond the 32-bit DMA offsets (rows of x=%ld Cin=%d Cout=%d)", xr, a.Cin, a.Cout);
+    k.x_idx = a.x_idx;
     k.M = (int)M;
     k.cin_bytes = a.Cin * 2;
     k.ldy = a.ldy;
@@ -903,7 +969,10 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
         VKP_LAUNCH_PHASE(4, 0, 0, 8, 1);
     else
 #endif
-    if (tall && conv3x3_panel_phase_reuse(a))
+    if (a.x_idx) {
+        VK_REQUIRE(tall && conv3x3_panel_phase_reuse(a), VK_EINVAL, "conv3x3_panel: x_idx outside the fragment-window phase form");
+        VKP_LAUNCH_PHASE(6, 0, 0, 8, 2, 4, 1, 1);
+    } else if (tall && conv3x3_panel_phase_reuse(a))
         VKP_LAUNCH_PHASE(6, 0, 0, 8, 2, 4, 1);
     else if (tall)
         VKP_LAUNCH_PHASE(6, 0, 0, 8, 2, 4);

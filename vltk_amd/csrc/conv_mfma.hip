@@ -452,7 +452,11 @@ int conv_route_checked(const ConvArgs &a) {
 }
 
 int launch_conv(const ConvArgs &a, hipStream_t stream) {
-    switch (conv_route(a)) {
+    const int route = conv_route(a);
+    // (the panel launcher refuses the forms of its own that do not read the index)
+    VK_REQUIRE(!a.x_idx || route == VK_ROUTE_PANEL || route < 0, VK_EINVAL,
+               "conv: x_idx is read by the 3x3 panel kernel alone, and this layer takes route %d", route);
+    switch (route) {
         case VK_ROUTE_GENERIC: break;
         case VK_ROUTE_RING: return launch_conv256(a, stream);
         case VK_ROUTE_DUO: return launch_conv_duo(a, stream);

@@ -115,6 +115,7 @@ struct vk_handle {
     // the box pooler (vk_set_pooler; not an option: it changes the results): VK_POOLER_*, and RoIAlign's samples per bin and axis
     int pooler_type = VK_POOLER_ROIPOOL, pooler_sampling_ratio = 0;
     int64_t dedupe_chunks = 0;                                            // head chunks that took that path (vk_get_option "dedupe_chunks")
+    int64_t indexed_chunks = 0;                                           // those of them whose conv2 read conv1's rows through the index ("indexed_chunks")
     // "pooled" after a forward whose one chunk took the dedupe path: the dense tensor was never written; vk_get_stage expands
     // src[idx] into the plan's buffer the first time the stage is asked for
     struct {
@@ -365,7 +366,8 @@ struct Plan {
     void *pooled, *h_t1, *h_t2, *h_a, *h_b, *h_sc;
     // the dedupe path of Res5 block 0 (fwd_head), or null: idx [chunk rows], win [chunk rows][5], one window count per chunk, the
     // table's workspace.  The distinct pooled rows live in h_sc (unused where the shortcut is fused) and conv1's distinct rows in
-    // h_t2 (dead until conv2 writes it), each large enough for a chunk without a single repeated window.
+    // h_t2 (dead until conv2 writes it), or in h_t1 where conv2 reads them through the index (head_block0_dedupe), each large enough
+    // for a chunk without a single repeated window.
     int32_t *dd_idx, *dd_win, *dd_u;
     void *dd_ws;
     size_t dd_ws_bytes;
@@ -801,6 +803,7 @@ int vk_get_option(vk_handle *h, const char *key, int *value) {
         }
     // read-only
     if (!strcmp(key, "dedupe_chunks")) *value = (int)std::min<int64_t>(h->dedupe_chunks, INT32_MAX);      // head chunks that took the dedupe path
+    else if (!strcmp(key, "indexed_chunks")) *value = (int)std::min<int64_t>(h->indexed_chunks, INT32_MAX);   // ... and ran conv2 without the row gather
     else if (!strcmp(key, "working_sets")) *value = (h->sets[0].arena ? 1 : 0) + (h->sets[1].arena ? 1 : 0);   // arenas held
     else if (!strcmp(key, "lane_forwards")) *value = (int)std::min<int64_t>(h->lane_forwards, INT32_MAX);    // forwards enqueued on a lane's stream
     else VK_REQUIRE(false, VK_EINVAL, "unknown option '%s'", key);
@@ -1136,20 +1139,30 @@ static int fwd_predictor(vk_handle *h, const Plan &p, hipStream_t s);
 // DESIGN.md 6c): window table -> pool of the U distinct windows -> conv1 over U rows (M read on the device) -> gather into the dense
 // [kc, P, P, mid] input of conv2 -> conv2 -> the fused conv3 + shortcut GEMM, whose second input is pooled_u[idx].  Every row of
 // the output h_a goes through the same kernels with the same K order as on the plain path, so it has the same bits.
+// Where the whole conv2 launch takes the panel kernel's indexed form (kc a multiple of 16, no panel switch off) there
+// is no gather: conv2 reads t1_u[idx[m]] itself.  conv2 writes h_t2, so t1_u then lives in h_t1, which the gather no longer fills;
+// h_t1 and h_t2 have the same size (make_plan: a chunk's dense rows), so a chunk without one repeated window (U == rows) still fits.
 static int head_block0_dedupe(vk_handle *h, const Plan &p, const void *res4, int k0, int kc, hipStream_t s) {
     const Block &b = h->res5[0];
     const int P = p.P;
     const long rows = (long)kc * P * P;
     const size_t es = dtype_size(h->dt);
     int32_t *u = p.dd_u + k0 / p.chunk;
-    void *pooled_u = p.h_sc, *t1_u = p.h_t2;
+    ConvArgs a2 = layer_args(h, b.conv2, p.h_t1, kc, P, P, p.h_t2, {.relu = true});
+    const bool indexed = conv_route(a2) == VK_ROUTE_PANEL && conv3x3_panel_phase_indexed(a2) == 1;
+    void *pooled_u = p.h_sc, *t1_u = indexed ? p.h_t1 : p.h_t2;
     VK_TRY(vk_roi_windows(p.rois + 5 * (size_t)k0, kc, p.N, p.Hf, p.Wf, P, 1.0f / 16.0f, p.dd_idx, p.dd_win, u, p.dd_ws, p.dd_ws_bytes, s));
     VK_TRY(vk_roi_pool_windows(res4, p.N, p.Hf, p.Wf, h->res4_c, p.dd_win, u, (int)rows, pooled_u, h->dt, s));
     ConvArgs a1 = layer_args(h, b.conv1, pooled_u, 1, 1, (int)rows, t1_u, {.relu = true});
     a1.m_dev = u;
     VK_TRY(launch_conv_gemm4(a1, s));
-    VK_TRY(vk_gather_rows(t1_u, p.dd_idx, rows, (int)(b.conv1.cout * es), p.h_t1, s));
-    VK_TRY(run_conv(h, b.conv2, p.h_t1, kc, P, P, p.h_t2, s, {.relu = true}));
+    if (indexed) {
+        a2.x_idx = p.dd_idx;
+        a2.x_rows = rows;              // (U <= rows is on the device; every index is below U)
+        h->indexed_chunks++;
+    } else
+        VK_TRY(vk_gather_rows(t1_u, p.dd_idx, rows, (int)(b.conv1.cout * es), p.h_t1, s));
+    VK_TRY(launch_conv(a2, s));
     ConvArgs a3 = layer_args(h, b.conv3, p.h_t2, 1, 1, (int)rows, p.h_a, {.x2 = pooled_u, .cin2 = b.shortcut.cin, .relu = true});
     a3.x2_idx = p.dd_idx;
     VK_TRY(launch_conv_gemm4(a3, s));

@@ -86,6 +86,8 @@ struct ConvArgs {
     int stem;            // 1: K-tiles are runs of consecutive input pixels (7x7 s2 stem)
     const int32_t *m_dev;   // conv_gemm4 only: the row count M is read on the device (N * Ho * Wo bounds it and sizes the grid)
     const int32_t *x2_idx;  // conv_gemm4 only: output row m reads row x2_idx[m] of x2
+    const int32_t *x_idx;   // conv3x3_panel only, where conv3x3_panel_phase_indexed: output row m reads row x_idx[m] of x [x_rows, Cin]
+    long x_rows;            // with x_idx: the rows of x (every index lies in [0, x_rows))
     vk_dtype dt, out_dt;
 };
 int launch_conv(const ConvArgs &a, hipStream_t stream);
@@ -98,6 +100,7 @@ int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream);
 int conv3x3_panel_phase_images(const ConvArgs &a);        // leading images of a panel launch that take its phase-interleaved form
 int conv3x3_panel_phase_tile_rows(const ConvArgs &a);     // rows of a tile of that part: 512, 256 (VK_PANEL_TALL=0) or 0 (no phase part)
 int conv3x3_panel_phase_reuse(const ConvArgs &a);         // 1: that part's 512-row tiles share a fragment window per tap row; 0: VK_PANEL_REUSE=0 or no such tile
+int conv3x3_panel_phase_indexed(const ConvArgs &a);       // 1: the WHOLE launch runs that form, which takes x_idx; 0: it does not (N % 16, the three switches) or VK_PANEL_INDEXED=0
 bool conv_gemm4_eligible(const ConvArgs &a);              // conv_gemm4.hip (1x1, K >= 1024, one or two inputs: 256x256 tile, four waves of 128x128)
 int launch_conv_gemm4(const ConvArgs &a, hipStream_t stream);
 int acquire_tile_counter(unsigned **ctr);     // a zeroed device word for one launch's dynamic tile tail; its last fetch zeroes it again (conv_gemm4.hip)
