@@ -661,6 +661,36 @@ typedef struct {
  * 1 - beta_i^step in fp64.  fp64 arithmetic on the fp32 values; m, v and p are rounded once each, at the store. */
 int vk_adamw_step(const vk_adamw_tensor *table, int count, int64_t max_n, double lr, double beta1, double beta2, double eps,
                   double weight_decay, double bias_correction1, double bias_correction2, void *stream);
+/* y = a + b over n dense fp32 elements, one rounding each; y may be a or b.  The residual adds of a trained layer: a residual
+ * passed to vk_gemm_f32 through `accumulate` instead takes K roundings at the residual's magnitude, one per step of the chain. */
+int vk_add_f32(const float *a, const float *b, float *y, long n, void *stream);
+/* The backward of a row gather: dst [M, C] (dense rows, ld_dst == C) is cleared, then row idx[i] receives src[i], i < n.  The
+ * indices must be distinct (one per example; the caller checks); one outside [0, M) is skipped. */
+int vk_scatter_rows_f32(const float *src, long ld_src, const int32_t *idx, int n, float *dst, long ld_dst, int M, int C, void *stream);
+/* torch.nn.utils.clip_grad_norm_(params, max_norm) over the gradients of vk_adamw_step's table, without a host round trip:
+ * fp64 sums of squares per (tensor, block) into `workspace` (8-byte aligned, the bytes the size function names), one workgroup
+ * adds them in a fixed order and writes norm_coef[0] = the total norm and norm_coef[1] = min(1, max_norm / (norm + 1e-6)) (f32,
+ * device memory), then every gradient is multiplied by norm_coef[1] as read from the device.  A non-finite norm propagates
+ * (torch's error_if_nonfinite=False); a coefficient of 1 leaves every gradient's bits unchanged. */
+size_t vk_grad_clip_workspace_bytes(int count);
+int vk_grad_clip(const vk_adamw_tensor *table, int count, int64_t max_n, double max_norm, float *norm_coef, void *workspace,
+                 size_t workspace_bytes, void *stream);
+/* The backward of vk_attention in fp32: O = softmax(Q K^T / sqrt(d) + mask) V per (batch, head), head h in columns h d .. h d + d
+ * of rows [B * L, ld]; q, dout, o, dq have B * Lq rows, k, v, dk, dv B * Lk rows, each matrix its own leading dimension (a packed
+ * QKV projection passes 3 * heads * d three times).  mask [B, Lk] is additive, may be NULL and receives no gradient.  From what
+ * the forward kept (q, k, v, o) and dout it writes dq = scale dS K, dk = scale dS^T Q, dv = P^T dout, with scale = 1 / sqrt(d),
+ * s = (q . k) scale + mask, P = expf(s - m) * (1 / l) recomputed from a row maximum m and row sum l, D = sum_c dout o per row and
+ * dS = P (dP - D).  1 <= d <= 128, any Lq, Lk >= 1, any 4-byte alignment.  Three launches (row statistics into `workspace`, dq,
+ * dk and dv), no atomics: the same input gives the same bits.  vk_attention_grad_check: what the launch refuses, host only (no
+ * pointer is read through): a NULL pointer other than mask, a size below 1, d outside 1..128, a leading dimension below
+ * heads * d, a workspace below the size function's bytes. */
+size_t vk_attention_grad_workspace_bytes(int B, int heads, int Lq);
+int vk_attention_grad_check(const float *q, long ldq, const float *k, long ldk, const float *v, long ldv, const float *mask, const float *o,
+                            long ldo, const float *dout, long lddo, const float *dq, long lddq, const float *dk, long lddk, const float *dv,
+                            long lddv, int B, int heads, int Lq, int Lk, int d, const void *workspace, size_t workspace_bytes);
+int vk_attention_grad(const float *q, long ldq, const float *k, long ldk, const float *v, long ldv, const float *mask, const float *o,
+                      long ldo, const float *dout, long lddo, float *dq, long lddq, float *dk, long lddk, float *dv, long lddv, int B,
+                      int heads, int Lq, int Lk, int d, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- N4: FPN-side ops (what north_star names; the reference holds only fragments, see oracle/fpn_oracle.py) ---- */
 

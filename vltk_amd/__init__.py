@@ -37,4 +37,7 @@ def __getattr__(name):
     if name in ("HeadTrainer", "step_lr", "linear_warmup"):    # N7: train a head over a frozen encoder
         from . import train
         return getattr(train, name)
+    if name == "EncoderTrainer":         # N8: fine-tune the top encoder layers and the head
+        from .finetune import EncoderTrainer
+        return EncoderTrainer
     raise AttributeError(name)

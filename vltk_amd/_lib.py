@@ -167,6 +167,13 @@ SIGNATURES = {
     "vk_layernorm_grad_workspace_bytes": (_SZ, [_I, _I]),
     "vk_layernorm_grad": (_I, [_P, C.c_long, _P, _P, C.c_long, _P, C.c_long, _P, _P, _I, _I, _D, _P, _SZ, _P]),
     "vk_adamw_step": (_I, [_P, _I, C.c_int64, _D, _D, _D, _D, _D, _D, _D, _P]),
+    "vk_add_f32": (_I, [_P, _P, _P, C.c_long, _P]),
+    "vk_scatter_rows_f32": (_I, [_P, C.c_long, _P, _I, _P, C.c_long, _I, _I, _P]),
+    "vk_grad_clip_workspace_bytes": (_SZ, [_I]),
+    "vk_grad_clip": (_I, [_P, _I, C.c_int64, _D, _P, _P, _SZ, _P]),
+    "vk_attention_grad_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "vk_attention_grad_check": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 5 + [_P, _SZ]),
+    "vk_attention_grad": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 5 + [_P, _SZ, _P]),
     "vk_roi_align": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "vk_roi_align_form": (_I, [_I, _I, _I]),
     "vk_assign_levels": (_I, [_P, _I, _I, _I, _I, _F, _I, _P, _P]),

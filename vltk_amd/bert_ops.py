@@ -271,6 +271,16 @@ class BertOps(Model):
         a = self._self_att_block(p + ".attention", x, mask, B, Lx)
         return self._ffn(p + ".intermediate", p + ".output", a)
 
+    def _hidden_after(self, n_layers, *inputs):
+        """The single-stream encoders (`_embed`, layers `encoder.layer.i`) stopped after layer `n_layers - 1`: -> (its rows
+        [B * L, H], the additive mask or None).  `EncoderTrainer` runs the frozen layers through it; `_forward` does not."""
+        x, mask = self._embed(*inputs)
+        B = inputs[0].shape[0]
+        Lx = x.shape[0] // B
+        for i in range(n_layers):
+            x = self._bert_layer(f"encoder.layer.{i}", x, mask, B, Lx)
+        return x, mask
+
     def _pooler(self, x, B, Lx):                        # LxmertPooler :566-572: tanh(dense(first token of each sequence))
         w, bb, N, Kp = self._lin["pooler.dense"]        # the first rows are picked by a stride-Lx 1x1 "convolution"
         H = self.cfg["hidden_size"]

@@ -20,6 +20,7 @@
 //   act_kernel / act_grad_kernel     elementwise
 //   ln_grad_rows_kernel    a wave per row: statistics recomputed from x, dx; ln_grad_cols_kernel: dgamma, dbeta as col_sums
 //   adamw_kernel           grid (blocks, tensors) over a device table of tensors
+//   scatter_rows_kernel    the backward of a row gather (after fill_zero_kernel); clip_*_kernel: clip_grad_norm_ over that table
 //
 // Rounding points (tests/train_util.py derives its bounds from them; u = 2^-24):
 //   gemm        acc = (accumulate ? C : 0) + bias, one rounding where both are given; then per output element ONE chain
@@ -366,6 +367,68 @@ __global__ __launch_bounds__(256) void adamw_kernel(const vk_adamw_tensor *__res
     }
 }
 
+// ---- a residual add: y = a + b, one rounding (y may be a or b) ----------------------------------------------------------------------
+__global__ __launch_bounds__(256) void add_kernel(const float *a, const float *b, float *y, long n) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) y[i] = a[i] + b[i];
+}
+
+// ---- the backward of a row gather ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void fill_zero_kernel(float *__restrict__ x, long n) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) x[i] = 0.f;
+}
+// dst[idx[i]] = src[i], a workgroup per source row; the indices are distinct (the caller's contract), one outside [0, M) is skipped
+__global__ __launch_bounds__(256) void scatter_rows_kernel(const float *__restrict__ src, long lds, const int32_t *__restrict__ idx,
+                                                           float *__restrict__ dst, long ldd, int M, int C) {
+    const long row = idx[blockIdx.x];
+    if (row < 0 || row >= M) return;
+    for (int c = threadIdx.x; c < C; c += 256) dst[row * ldd + c] = src[(long)blockIdx.x * lds + c];
+}
+
+// ---- gradient clipping by global norm ------------------------------------------------------------------------------------------------
+// torch.nn.utils.clip_grad_norm_ over the AdamW table.  clip_sumsq_kernel: block x of tensor y adds the squares of elements
+// x * 256 + tid, + CLIP_BLOCKS * 256, .. in fp64 per thread, then the 256 threads in a fixed tree; part[y][x].  clip_finish_kernel:
+// one workgroup adds the count * CLIP_BLOCKS partial sums (thread t takes t, t + 256, ..; the same tree), norm = sqrt,
+// coef = min(1, max_norm / (norm + 1e-6)) with a NaN kept, both rounded to f32 once into out[0], out[1].  clip_scale_kernel:
+// g = g * coef, one rounding, coef read from device memory.
+constexpr int CLIP_BLOCKS = 32;
+__device__ __forceinline__ double block_sum_d(double v, double *s) {      // s[256]; the result in every thread
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+        __syncthreads();
+    }
+    return s[0];
+}
+__global__ __launch_bounds__(256) void clip_sumsq_kernel(const vk_adamw_tensor *__restrict__ table, double *__restrict__ part) {
+    __shared__ double s[256];
+    const vk_adamw_tensor t = table[blockIdx.y];
+    double acc = 0.0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < t.n; i += (long)CLIP_BLOCKS * 256) {
+        const double g = (double)t.g[i];
+        acc += g * g;
+    }
+    acc = block_sum_d(acc, s);
+    if (threadIdx.x == 0) part[(long)blockIdx.y * CLIP_BLOCKS + blockIdx.x] = acc;
+}
+__global__ __launch_bounds__(256) void clip_finish_kernel(const double *__restrict__ part, int n, double max_norm, float *__restrict__ out) {
+    __shared__ double s[256];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += part[i];
+    acc = block_sum_d(acc, s);
+    if (threadIdx.x == 0) {
+        const double norm = sqrt(acc), c = max_norm / (norm + 1e-6);
+        out[0] = (float)norm;
+        out[1] = (float)(c < 1.0 ? c : (c != c ? c : 1.0));
+    }
+}
+__global__ __launch_bounds__(256) void clip_scale_kernel(const vk_adamw_tensor *__restrict__ table, const float *__restrict__ norm_coef) {
+    const vk_adamw_tensor t = table[blockIdx.y];
+    const float coef = norm_coef[1];
+    float *g = const_cast<float *>(t.g);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < t.n; i += (long)gridDim.x * 256) g[i] = g[i] * coef;
+}
+
 static int gemm_check(int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB) {
     VK_REQUIRE(M >= 1 && N >= 1 && K >= 1, VK_EINVAL, "gemm_f32: sizes must be positive, got M=%d N=%d K=%d", M, N, K);
     VK_REQUIRE((transA == 0 || transA == 1) && (transB == 0 || transB == 1), VK_EINVAL, "gemm_f32: transA=%d transB=%d must be 0 or 1", transA,
@@ -498,6 +561,45 @@ int vk_adamw_step(const vk_adamw_tensor *table, int count, int64_t max_n, double
     VK_REQUIRE(bias_correction1 > 0.0 && bias_correction2 > 0.0, VK_EINVAL, "adamw_step: the bias corrections must be positive");
     const AdamwArgs a = {lr / bias_correction1, beta1, beta2, eps, 1.0 - lr * weight_decay, 1.0 / sqrt(bias_correction2)};
     hipLaunchKernelGGL(adamw_kernel, dim3(elementwise_blocks(max_n), count), dim3(256), 0, (hipStream_t)stream, table, a);
+    VK_CHECK_HIP(hipGetLastError());
+    return VK_OK;
+}
+
+int vk_add_f32(const float *a, const float *b, float *y, long n, void *stream) {
+    VK_REQUIRE(a && b && y, VK_EINVAL, "add_f32: null argument");
+    VK_REQUIRE(n >= 1, VK_EINVAL, "add_f32: n=%ld must be positive", n);
+    hipLaunchKernelGGL(add_kernel, dim3(elementwise_blocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, y, n);
+    VK_CHECK_HIP(hipGetLastError());
+    return VK_OK;
+}
+
+int vk_scatter_rows_f32(const float *src, long ld_src, const int32_t *idx, int n, float *dst, long ld_dst, int M, int C, void *stream) {
+    VK_REQUIRE(src && idx && dst, VK_EINVAL, "scatter_rows_f32: null argument");
+    VK_REQUIRE(n >= 1 && M >= 1 && C >= 1 && ld_src >= C && ld_dst >= C, VK_EINVAL, "scatter_rows_f32: bad shape n=%d M=%d C=%d ld_src=%ld ld_dst=%ld",
+               n, M, C, ld_src, ld_dst);
+    VK_REQUIRE(ld_dst == C, VK_EINVAL, "scatter_rows_f32: dst is cleared as one block, so its rows must be dense (ld_dst=%ld, C=%d)", ld_dst, C);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(fill_zero_kernel, dim3(elementwise_blocks((long)M * C)), dim3(256), 0, s, dst, (long)M * C);
+    hipLaunchKernelGGL(scatter_rows_kernel, dim3(n), dim3(256), 0, s, src, ld_src, idx, dst, ld_dst, M, C);
+    VK_CHECK_HIP(hipGetLastError());
+    return VK_OK;
+}
+
+size_t vk_grad_clip_workspace_bytes(int count) { return count >= 1 ? (size_t)count * CLIP_BLOCKS * sizeof(double) : 0; }
+
+int vk_grad_clip(const vk_adamw_tensor *table, int count, int64_t max_n, double max_norm, float *norm_coef, void *workspace,
+                 size_t workspace_bytes, void *stream) {
+    VK_REQUIRE(table && norm_coef, VK_EINVAL, "grad_clip: null argument");
+    VK_REQUIRE(count >= 1 && count <= 65535 && max_n >= 1, VK_EINVAL, "grad_clip: count=%d (1..65535) max_n=%lld (>= 1)", count, (long long)max_n);
+    VK_REQUIRE(max_norm > 0.0, VK_EINVAL, "grad_clip: max_norm must be positive");
+    const size_t need = vk_grad_clip_workspace_bytes(count);
+    VK_REQUIRE(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 7) == 0, VK_EINVAL,
+               "grad_clip: needs an 8-byte aligned workspace of %zu bytes, got %zu", need, workspace_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    hipLaunchKernelGGL(clip_sumsq_kernel, dim3(CLIP_BLOCKS, count), dim3(256), 0, s, table, part);
+    hipLaunchKernelGGL(clip_finish_kernel, dim3(1), dim3(256), 0, s, part, count * CLIP_BLOCKS, max_norm, norm_coef);
+    hipLaunchKernelGGL(clip_scale_kernel, dim3(elementwise_blocks(max_n), count), dim3(256), 0, s, table, norm_coef);
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
 }

@@ -10,7 +10,8 @@ CPU fallback.
 
 Out of scope: dropout (the heads here have none in eval mode; the dropout transformers' VisualBERT puts before `cls` is omitted),
 gradient clipping, HIP-graph capture of a step, 16-bit training GEMMs, any gradient into an encoder, and the soft-label KL loss of
-transformers' VisualBERT-QA (the reference's script passes hard labels).
+transformers' VisualBERT-QA (the reference's script passes hard labels).  Gradient clipping and the gradient into the top
+encoder layers are `EncoderTrainer`'s (finetune.py).
 """
 import numpy as np
 import torch
