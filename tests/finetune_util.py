@@ -147,15 +147,21 @@ FIXTURE_LABELS, FIXTURE_SEED, FIXTURE_LR, FIXTURE_STEP_LR = 16, 3, 1e-3, (20, 0.
 WIDE = dict(hidden_size=128, num_attention_heads=4, intermediate_size=256)      # a 16-bit model's pooler needs hidden % 64 == 0
 
 
-def trajectory_fixture(seed=FIXTURE_SEED, wide=False):
-    """-> (cfg, state dict, inputs {name: numpy}, labels int64 [16]): partial text and visual masks (every text mask keeps at
+# Where the trainer's fp32 forward streams: Lx = 24 + 116 = 140 rows of d = 64 are past the LDS kernel's image (187 600 bytes).
+LONG = dict(hidden_size=128, num_attention_heads=2, intermediate_size=256, max_position_embeddings=24)
+LONG_SHAPE = (2, 24, 116)                                                       # B, Lt, V
+
+
+def trajectory_fixture(seed=FIXTURE_SEED, wide=False, long=False):
+    """-> (cfg, state dict, inputs {name: numpy}, labels int64 [B]): partial text and visual masks (every text mask keeps at
     least 3 tokens, so the gathered row exists), every ninth label -100.  `wide`: the same fixture at hidden 128, I = 256, which
-    a bf16 model can run (its own forward ends in the pooler, whose kernel takes channels in multiples of 64 in 16-bit types)."""
+    a bf16 model can run (its own forward ends in the pooler, whose kernel takes channels in multiples of 64 in 16-bit types).
+    `long`: hidden 128 in 2 heads (d = 64), B = 2, Lt = 24, V = 116, drawn in the same order from the same generator."""
     from vltk_amd.visualbert import make_visualbert_qa_state_dict, visualbert_config
-    cfg = visualbert_config(**dict(FIXTURE_CFG, **(WIDE if wide else {})))
+    cfg = visualbert_config(**dict(FIXTURE_CFG, **(WIDE if wide else {}), **(LONG if long else {})))
     sd = make_visualbert_qa_state_dict(cfg, FIXTURE_LABELS, seed)
     r = np.random.Generator(np.random.PCG64([seed, 77]))
-    B, Lt, V = 16, 9, 7
+    B, Lt, V = LONG_SHAPE if long else (16, 9, 7)
     ids = r.integers(1, cfg["vocab_size"], (B, Lt)).astype(np.int64)
     feats = (np.maximum(r.standard_normal((B, V, cfg["visual_embedding_dim"])), 0) * 2.0).astype(np.float32)
     am = (np.arange(Lt)[None] < r.integers(3, Lt + 1, (B, 1))).astype(np.int64)
@@ -179,9 +185,9 @@ def fixture_boundary_cpu(cfg, sd, inputs, first):
     return x.numpy()
 
 
-def fixture_run(n, steps, dtype, x0, max_norm=None, seed=FIXTURE_SEED):
+def fixture_run(n, steps, dtype, x0, max_norm=None, seed=FIXTURE_SEED, long=False):
     """The yardstick on the trajectory fixture with the last n layers trained, from the boundary state x0."""
-    cfg, sd, inputs, labels = trajectory_fixture(seed)
+    cfg, sd, inputs, labels = trajectory_fixture(seed, long=long)
     nl = cfg["num_hidden_layers"]
     layers = [f"visual_bert.encoder.layer.{i}" for i in range(nl - n, nl)]
     keys = trained_keys("visual_bert.", range(nl - n, nl), "cls")
@@ -192,14 +198,21 @@ def fixture_run(n, steps, dtype, x0, max_norm=None, seed=FIXTURE_SEED):
 
 
 # ---- the attention backward in float64 numpy, with the per-element bounds ----------------------------------------------------------------
-def attention_grad_reference(q, k, v, mask, dout, heads, o_given=None):
+def launcher_scale(d):
+    """The scale vk_attention_grad's launcher passes to its kernels, 1.0f / sqrtf((float)d), as a float64."""
+    return float(np.float32(1.0) / np.sqrt(np.float32(d)))
+
+
+def attention_grad_reference(q, k, v, mask, dout, heads, o_given=None, scale=None):
     """q, dout [B, Lq, heads * d]; k, v [B, Lk, heads * d]; mask additive [B, Lk] or None; all float64 (the stored fp32 values).
     -> dict(o, dq, dk, dv, b_dq, b_dk, b_dv): the reference and the bounds of the module docstring.  `o_given`: the O the kernel
-    receives (default: the reference's own, rounded to fp32)."""
+    receives (default: the reference's own, rounded to fp32).  `scale`: the factor in place of 1 / sqrt(d) (the exact cases at a
+    head dim that is no power of four pass `launcher_scale(d)`: dQ and dK are then S * scale with S the exact sum, a product of
+    two 24-bit numbers, exact in float64, which one rounding takes to the kernel's bits)."""
     q, k, v, dout = (np.asarray(t, np.float64) for t in (q, k, v, dout))
     B, Lq, H = q.shape
     Lk, d = k.shape[1], H // heads
-    scale = 1.0 / math.sqrt(d)
+    scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
     split = lambda t: t.reshape(B, -1, heads, d).transpose(0, 2, 1, 3)          # [B, heads, L, d]
     join = lambda t: t.transpose(0, 2, 1, 3).reshape(B, -1, H)
     qh, kh, vh, doh = split(q), split(k), split(v), split(dout)

@@ -116,6 +116,58 @@ def test_environment_switches_are_read_per_call(lib, monkeypatch):
     assert route(lib, 20, 36, 64, L.VK_BF16, 0) == "mfma"
 
 
+def test_routes_the_every_build_and_head_dim_tests_expect(lib, monkeypatch):
+    """The kernel of every (shape, dtype, entry) that test_gpu_attention_builds.py, the long rows of test_gpu_attention_small.py's
+    surroundings test and the forward / backward pair of test_gpu_attention_grad.py launch, on the strides those tests use (column
+    slices of [rows, 2 H] buffers; the trainer's packed [rows, 3 H]): a change of the rule cannot quietly move one of them to
+    another kernel.  The shapes are read from the GPU file, the routes are written out here."""
+    import test_gpu_attention_builds as TB
+    sixteen = (L.VK_F16, L.VK_BF16)
+
+    def on(entry, dt, Lq, Lk, d, B_heads, width=2):
+        ld = width * B_heads[1] * d
+        return route(lib, Lq, Lk, d, dt, int(entry == "vk_attention_tiled"), ld=(ld, ld, ld))
+
+    # 1. every build: (3, 3) everywhere, (1, 1) and (2, 2) at two pairs
+    assert len(TB.BUILD_PAIRS) == 10 and TB.HEAD_DIMS == [32, 64]
+    for Lq, Lk in TB.BUILD_PAIRS:
+        for d in TB.HEAD_DIMS:
+            for bh in [(3, 3)] + ([(1, 1), (2, 2)] if (Lq, Lk) in TB.OTHER_BH else []):
+                for dt in sixteen:
+                    assert on("vk_attention_tiled", dt, Lq, Lk, d, bh) == "tiled", (Lq, Lk, d, bh)
+                assert on("vk_attention_tiled", L.VK_F32, Lq, Lk, d, bh) == "stream", (Lq, Lk, d, bh)
+    # 2. the permutation across three key tiles (contiguous rows), 3. the surroundings at (36, 70) and (17, 70)
+    for Lq, Lk, width in ((50, 150, 1), (13, 150, 1), (36, 70, 2), (17, 70, 2)):
+        for d in (32, 64) if width == 1 else (64,):
+            for dt in sixteen:
+                assert on("vk_attention_tiled", dt, Lq, Lk, d, (3, 3), width) == "tiled"
+            assert on("vk_attention_tiled", L.VK_F32, Lq, Lk, d, (3, 3), width) == "stream"
+    # 4. head dims: what the matrix cores do not take streams at the tiled entry whatever the switch says
+    assert len(TB.STREAM_DIMS) == 15
+    for dt, d in TB.STREAM_DIMS:
+        for Lq, Lk in ((17, 65), (33, 129)):
+            assert on("vk_attention_tiled", dt, Lq, Lk, d, (3, 2)) == "stream", (dt, d)
+    for dt in (L.VK_F32,) + sixteen:
+        for d in (128, 256):
+            assert on("vk_attention_tiled", dt, 50, 150, d, (2, 3), 1) == "stream"
+            assert on("vk_attention", dt, 20, 36, d, (3, 3)) == "lds"
+        assert on("vk_attention", dt, 31, 128, 128, (2, 3), 1) == "lds"          # 163 576 bytes: the largest image, as (127, 127, 64)
+        assert on("vk_attention", dt, 32, 128, 128, (2, 3), 1) == "stream"
+    assert on("vk_attention", L.VK_F32, 127, 127, 64, (3, 3)) == "lds"
+    assert on("vk_attention", L.VK_F32, 128, 128, 64, (3, 3)) == "stream"
+    # 5. the forward of the pair, on the trainer's packed projection
+    assert on("vk_attention", L.VK_F32, 35, 35, 16, (3, 2), 3) == "lds"
+    assert on("vk_attention_tiled", L.VK_F32, 35, 35, 16, (3, 2), 3) == "stream"
+    assert on("vk_attention", L.VK_F32, 140, 140, 64, (3, 2), 3) == "stream"
+    assert route(lib, 140, 140, 64, L.VK_F32, 0, ld=(384, 384, 384)) == "stream"          # the trainer's fixture at Lx = 140
+    # the 16-bit types reach the LDS and streaming kernels of these tests with the matrix cores switched off
+    monkeypatch.setenv("VK_ATTENTION_MFMA", "0")
+    for dt in sixteen:
+        for Lq, Lk in TB.BUILD_PAIRS + [(50, 150), (36, 70), (17, 70)]:
+            for d in TB.HEAD_DIMS:
+                assert on("vk_attention_tiled", dt, Lq, Lk, d, (3, 3)) == "stream"
+
+
 def test_refusals_come_before_any_device_call(lib):
     """Head dims past 256 are refused by name of the limit, through the launch entry points themselves with made-up pointers:
     the refusal is decided on the host."""

@@ -7,7 +7,10 @@ ask for the reference's bits (the sign of a zero aside: an exact 0 is +0 or -0 b
 that its own data is exact in fp32 whatever the order (`exact_in_fp32`).  Bound cases hold every element under the bound derived
 in finetune_util's docstring and every tensor within 8 x torch's own fp32 distance to float64.  Every matrix lies in a buffer
 with poisoned padding columns (1e30 in the inputs) and a guard behind it; the outputs' padding and guards must come back
-untouched."""
+untouched.  Head dims 1 and 128 (AG_MAXD) run in exact cases of every kind and in bound cases, 96 in bound cases; at d = 128 the scale is
+no power of two and dQ, dK are asked as the one rounding of S * scale.  The pair tests put the library's own fp32 forward
+(vk_attention, vk_attention_tiled: the LDS and the streaming kernel) in front of the backward, where every other test passes
+O = fp32(reference O)."""
 import functools
 
 import numpy as np
@@ -141,16 +144,17 @@ def exact_case(kind, B, heads, Lq, Lk, d, packed, left=None, dense=False):
         mask = keep_mask(r, B, Lk, 1)
     if kind == "d":
         mask = keep_mask(r, B, Lk, left)
-    ref = U.attention_grad_reference(q, k, v, mask, dout, heads)
+    ref = U.attention_grad_reference(q, k, v, mask, dout, heads, scale=U.launcher_scale(d))      # d a power of four: 1 / sqrt(d) itself
     assert U.exact_in_fp32(ref), "the case's own data is not exact in fp32"
     got = run_attention_grad(*(t.astype(np.float32) for t in (q, k, v)), mask, ref["o"].astype(np.float32), dout.astype(np.float32), heads, packed, dense=dense)
     return ref, dict(zip(("dq", "dk", "dv"), got))
 
 
-def same_bits(got, ref):
-    """Equal values everywhere and equal bits wherever the reference is not zero."""
+def same_bits(got, ref, rounded=False):
+    """Equal values everywhere and equal bits wherever the reference is not zero.  `rounded`: the reference is an exact float64
+    product with a scale that is no power of two, and its one rounding to fp32 is what is asked (else it is an fp32 number)."""
     want = ref.astype(np.float32)
-    assert (want.astype(np.float64) == ref).all()
+    assert rounded or (want.astype(np.float64) == ref).all()
     nz = want != 0
     return np.array_equal(got, want) and (got[nz].view(np.uint32) == want[nz].view(np.uint32)).all()
 
@@ -202,8 +206,38 @@ def test_exact_dense_leading_dimensions(kind, case):
     assert ref["dv"].any()
 
 
+# ---- head dims 128 (AG_MAXD: every one of a thread's 8 accumulators live, 87 and 91 KiB of LDS in the dQ and dK/dV kernels) and 1 ------
+# One case of each kind at each.  At d = 128 scale = fp32(1 / sqrt(128)) is no power of two: dV and the exact zeros as above; dQ and
+# dK are asked as float32(S * float64(scale)) with S the exact sum (exact_in_fp32 is asserted of the data first, as everywhere):
+# the kernel's last operation is that one product.
+WIDE = [("a", (1, 2, 17, 64, 128, False)), ("b", (1, 1, 64, 64, 128, True)), ("c", (2, 1, 35, 70, 128, False)), ("d", (1, 2, 17, 65, 128, False, 32)),
+        ("a", (2, 3, 17, 16, 1, False)), ("b", (1, 3, 16, 16, 1, True)), ("c", (1, 1, 35, 131, 1, False)), ("d", (2, 1, 65, 65, 1, True, 16))]
+
+
+@pytest.mark.parametrize("kind,case", WIDE, ids=str)
+def test_exact_head_dims_128_and_1(kind, case):
+    ref, got = exact_case(kind, *case)
+    assert case[4] in (1, 128) and np.float32(U.launcher_scale(case[4])) == np.float32(1.0) / np.sqrt(np.float32(case[4]))
+    zero = {"a": ("dk",), "b": ("dq",), "c": ("dq", "dk"), "d": ("dk",)}[kind]
+    assert same_bits(got["dv"], ref["dv"]) and ref["dv"].any()
+    for name in ("dq", "dk"):
+        if name in zero:
+            assert not got[name].any() and not ref[name].any(), name
+        else:
+            assert same_bits(got[name], ref[name], rounded=True) and ref[name].any(), name
+
+
+def test_backward_at_its_largest_head_dim_is_covered():
+    """d = 128 = AG_MAXD runs in every exact kind and in bound cases that are padded, dense and packed."""
+    assert {kind for kind, case in WIDE if case[4] == 128} == set("abcd")
+    assert {case[4] for case in BOUND if case[3] == 128} == {False, True}
+
+
 # ---- bound cases: (heads, Lq, Lk, d, packed); B = 3: a partial mask, every key masked, no key masked ---------------------------------
-BOUND = [(2, 35, 70, 8, False), (1, 17, 131, 24, False), (3, 65, 65, 64, True), (1, 20, 17, 80, False)]
+# d = 96 and 128: accumulator slots 5 .. 7, and more than 64 KiB of LDS in the dQ and dK/dV kernels; d = 1: one column.  A packed
+# projection has as many queries as keys, so d = 96 runs (35, 70) with matrices of their own and (70, 70) packed.
+BOUND = [(2, 35, 70, 8, False), (1, 17, 131, 24, False), (3, 65, 65, 64, True), (1, 20, 17, 80, False),
+         (2, 17, 65, 128, False), (1, 35, 70, 96, False), (1, 70, 70, 96, True), (1, 33, 33, 128, True), (3, 20, 17, 1, False)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -239,6 +273,39 @@ def test_same_input_same_bits():
     runs = [run_attention_grad(q, k, v, mask, ref["o"].astype(np.float32), dout, case[0], case[4]) for _ in range(2)]
     for a, b in zip(*runs):
         assert a.tobytes() == b.tobytes()
+
+
+# ---- the pair: the library's own fp32 forward in front of the backward ------------------------------------------------------------------
+# (heads, L, d, entry, route): q, k, v, the masks and dO of a packed bound case, in the trainer's layout (a packed projection
+# [B * L, 3H], dense O and dO).  O comes from vk_attention / vk_attention_tiled, not from the reference: the LDS kernel forms
+# P = e * (1 / l) as the backward does, the streaming kernel divides O by l where the backward multiplies by 1 / l.
+PAIR = [(2, 35, 16, "vk_attention", "lds"), (2, 35, 16, "vk_attention_tiled", "stream"), (2, 140, 64, "vk_attention", "stream")]
+
+
+@pytest.mark.parametrize("heads,Lx,d,entry,route", PAIR, ids=[f"{c[1]}-{c[2]}-{c[4]}" for c in PAIR])
+def test_backward_of_the_librarys_own_forward(heads, Lx, d, entry, route):
+    """O per element within transformer_check.attention_bound; dQ, dK, dV within the bounds with `o_given` = that O (the term
+    |sum_c dO_c (O_given - O_ref)_c| of D is computed from it) and within 8 x torch's fp32 distance to float64."""
+    import gpu_util as G
+    import transformer_check as T
+    from test_gpu_attention_long import attention
+    q, k, v, mask, dout, _, g32 = bound_case(heads, Lx, Lx, d, True)
+    B, H = 3, heads * d
+    qkv = torch.from_numpy(np.concatenate((q, k, v), 2).reshape(B * Lx, 3 * H)).to(G.DEV)
+    add = torch.from_numpy(mask)
+    o = attention(entry, qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], add.to(G.DEV), B, heads, Lx, Lx, d, L.VK_F32, route)
+    t = [torch.from_numpy(a.reshape(B * Lx, H)) for a in (q, k, v)]
+    r = T.attention_reference(*t, add, B, heads, Lx, Lx, d)
+    T.assert_within(o, r["ref"], T.attention_bound(r, torch.float32, route), f"forward {entry} -> {route} L {Lx} d {d}")
+    o = o.cpu().numpy().reshape(B, Lx, H)
+    ref = U.attention_grad_reference(q, k, v, mask, dout, heads, o_given=o)
+    got = dict(zip(("dq", "dk", "dv"), run_attention_grad(q, k, v, mask, o, dout, heads, packed=True, dense=True)))
+    for name in ("dq", "dk", "dv"):
+        ratio = np.abs(got[name].astype(np.float64) - ref[name]) / ref["b_" + name]
+        d_cpu, d_gpu = U.maxnorm_rel(g32[name], ref[name]), U.maxnorm_rel(got[name], ref[name])
+        print(f"pair {route} L {Lx} d {d} {name}: worst error / bound {ratio.max():.3f}; d_cpu {d_cpu:.2e} d_gpu {d_gpu:.2e} ratio {d_gpu / max(d_cpu, FLOOR):.2f}")
+        assert ratio.max() <= 1.0, (name, ratio.max())
+        assert d_gpu <= 8 * max(d_cpu, FLOOR), (name, d_cpu, d_gpu)
 
 
 # ---- the two small kernels ---------------------------------------------------------------------------------------------------------------

@@ -161,13 +161,18 @@ def kernels_of(dt, monkeypatch):
             ("stream", lambda: monkeypatch.setenv("VK_ATTENTION_MFMA", "0"))]
 
 
+# (Lk, d): the head dim 64 cases keep the ids they had before d = 32 (the tiled kernel's D = 32 builds) joined them
+UNIFORM = [(Lk, d) for d in (64, 32) for Lk in (128, 256, 1024)]
+UNIFORM_IDS = [str(Lk) if d == 64 else f"{Lk}-d{d}" for Lk, d in UNIFORM]
+
+
 @pytest.mark.parametrize("dt", ALL, ids=[IDS[d] for d in ALL])
-@pytest.mark.parametrize("Lk", [128, 256, 1024])
-def test_exact_uniform_average(dt, Lk, monkeypatch):
+@pytest.mark.parametrize("Lk,d", UNIFORM, ids=UNIFORM_IDS)
+def test_exact_uniform_average(dt, Lk, d, monkeypatch):
     """q = 0: every live key weighs the same, so with integer v the output is the fp32 value sum(v) / count rounded once to the
     storage type, whatever the tiling: unmasked, the first half of the keys masked (leading tiles all masked) and every odd key
-    masked."""
-    B, heads, Lq, d, td = 1, 3, 33, 64, TDT[dt]
+    masked.  Head dim 64 and 32 (the seed is Lk alone, so the d = 64 data is what it was)."""
+    B, heads, Lq, td = 1, 3, 33, TDT[dt]
     gen = np.random.Generator(np.random.PCG64(Lk))
     H = heads * d
     q = torch.zeros((B * Lq, H), dtype=td, device=G.DEV)
@@ -184,11 +189,14 @@ def test_exact_uniform_average(dt, Lk, monkeypatch):
             assert torch.equal(out.cpu(), want[None].expand(B * Lq, H)), (label, int(live.sum()))
 
 
-@pytest.mark.parametrize("dt", ALL, ids=[IDS[d] for d in ALL])
-def test_exact_one_hot(dt, monkeypatch):
-    """q = 32 e0 and one key j* = 32 e0, the others 0: the scaled gap is 128, every other weight underflows to 0 and the output
-    row is v[j*] bit for bit.  One batch per j*: first, last, and both sides of every multiple of 32 up to Lk = 257."""
-    Lk, Lq, d, td = 257, 5, 64, TDT[dt]
+ONE_HOT = [(dt, d) for d in (64, 32) for dt in ALL]
+
+
+@pytest.mark.parametrize("dt,d", ONE_HOT, ids=[IDS[dt] if d == 64 else f"{IDS[dt]}-d{d}" for dt, d in ONE_HOT])
+def test_exact_one_hot(dt, d, monkeypatch):
+    """q = 32 e0 and one key j* = 32 e0, the others 0: the scaled gap is 1024 / sqrt(d) >= 128, every other weight underflows to 0
+    and the output row is v[j*] bit for bit.  One batch per j*: first, last, and both sides of every multiple of 32 up to Lk = 257."""
+    Lk, Lq, td = 257, 5, TDT[dt]
     stars = sorted({0, Lk - 1} | {m - 1 for m in range(32, Lk, 32)} | {m for m in range(32, Lk, 32)})
     B = len(stars)
     gen = np.random.Generator(np.random.PCG64(7))

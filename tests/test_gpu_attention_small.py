@@ -6,7 +6,10 @@ builds.
    the 16- and 32-element block edges, every dtype, both staging branches of the LDS kernel, idle waves in the last workgroup;
 2. - 4. bit-exact: the uniform average (the key index through the P and V^T images), one-hot over every key, and a row / head
    permutation (the row mapping qb*16 + 4g + e and the head offset);
-5. the output's surroundings: nothing written outside [B*Lq, H], two launches give the same bytes.
+5. the output's surroundings: nothing written outside [B*Lq, H], two launches give the same bytes; the tiled and streaming
+   kernels too, at lengths whose last query block is mostly padding rows.
+
+tests/test_gpu_attention_builds.py holds every build of the tiled and streaming kernels, and the head dims up to the limits, to 1. - 4.
 
 Every launch goes through vk_attention / vk_attention_tiled, with the route asked of vk_attention_route immediately before it."""
 import numpy as np
@@ -45,16 +48,17 @@ def same_bits(a, b):
     return torch.equal(bits(a), bits(b))
 
 
-def per_element(dt, route, B, heads, Lq, Lk, d, masked, extra=0):
+def per_element(dt, route, B, heads, Lq, Lk, d, masked, extra=0, entry=None):
     """One launch on column slices of fused projections [rows, 2H + extra] (q the second half of its own buffer, k and v the
-    halves of theirs), every element against float64 -> the worst ratio."""
+    halves of theirs), every element against float64 -> the worst ratio.  `entry`: the entry point, where it is not the route's
+    usual one (vk_attention reaches the streaming kernel by itself past the LDS kernel's image)."""
     td, H = TDT[dt], heads * d
     gen = np.random.Generator(np.random.PCG64([Lq, Lk, d, B, heads, extra]))
     qq = torch.from_numpy(gen.standard_normal((B * Lq, 2 * H + extra)).astype(np.float32)).to(td)
     kv = torch.from_numpy(gen.standard_normal((B * Lk, 2 * H + extra)).astype(np.float32)).to(td)
     add = mixed_mask(B, Lk) if masked else None
     qd, kvd = qq.to(G.DEV), kv.to(G.DEV)
-    entry = "vk_attention_tiled" if route in ("tiled", "stream") else "vk_attention"
+    entry = entry or ("vk_attention_tiled" if route in ("tiled", "stream") else "vk_attention")
     out = attention(entry, qd[:, H:2 * H], kvd[:, :H], kvd[:, H:2 * H], add.to(G.DEV) if masked else None, B, heads, Lq, Lk, d, dt, route)
     r = T.attention_reference(qq[:, H:2 * H], kv[:, :H], kv[:, H:2 * H], add, B, heads, Lq, Lk, d)
     return T.assert_within(out, r["ref"], T.attention_bound(r, td, route),
@@ -224,12 +228,10 @@ def test_exact_row_and_head_permutation(dt, route, d, monkeypatch):
 
 
 # ---- 5. the output's surroundings -------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dt,route", ROUTE_CASES, ids=ROUTE_IDS)
-def test_output_surroundings_and_repeatability(dt, route, monkeypatch):
+def surroundings(dt, route, entry, Lq, Lk):
     """out is [B*Lq + 1, H + 8], prefilled with a finite sentinel: the 8 columns past H and the row past the last hold it bit for
     bit after the launch, the rest is within the bound, and a second launch of the same arguments gives the same bytes."""
-    on_route(route, dt, monkeypatch)
-    B, heads, Lq, Lk, d, td = 3, 3, 36, 20, 64, TDT[dt]
+    B, heads, d, td = 3, 3, 64, TDT[dt]
     H, lib = heads * d, L.load()
     gen = np.random.Generator(np.random.PCG64(11))
     qq = torch.from_numpy(gen.standard_normal((B * Lq, 2 * H)).astype(np.float32)).to(td)
@@ -241,9 +243,9 @@ def test_output_surroundings_and_repeatability(dt, route, monkeypatch):
     for _ in range(2):
         out = torch.full((B * Lq + 1, H + 8), -77.0, dtype=td, device=G.DEV)
         aligned = int((q.data_ptr() | k.data_ptr() | v.data_ptr()) % 16 == 0)
-        got = lib.vk_attention_route(Lq, Lk, d, dt, q.stride(0), k.stride(0), v.stride(0), aligned, 0)
+        got = lib.vk_attention_route(Lq, Lk, d, dt, q.stride(0), k.stride(0), v.stride(0), aligned, int(entry == "vk_attention_tiled"))
         assert got >= 0 and ROUTES[got] == route
-        L.call("vk_attention", G.P(q), q.stride(0), G.P(k), k.stride(0), G.P(v), v.stride(0), G.P(md), G.P(out), H + 8, B, heads, Lq, Lk, d,
+        L.call(entry, G.P(q), q.stride(0), G.P(k), k.stride(0), G.P(v), v.stride(0), G.P(md), G.P(out), H + 8, B, heads, Lq, Lk, d,
                dt, G.stream())
         torch.cuda.synchronize()
         outs.append(out.cpu())
@@ -251,4 +253,20 @@ def test_output_surroundings_and_repeatability(dt, route, monkeypatch):
     assert same_bits(outs[0][:-1, H:], sentinel.expand(B * Lq, 8)) and same_bits(outs[0][-1], sentinel.expand(H + 8))
     assert same_bits(outs[0], outs[1])
     r = T.attention_reference(qq[:, H:], kv[:, :H], kv[:, H:], add, B, heads, Lq, Lk, d)
-    T.assert_within(outs[0][:-1, :H], r["ref"], T.attention_bound(r, td, route), f"attention {route} {IDS[dt]} into a wider out")
+    T.assert_within(outs[0][:-1, :H], r["ref"], T.attention_bound(r, td, route), f"attention {route} {IDS[dt]} Lq {Lq} Lk {Lk} into a wider out")
+
+
+@pytest.mark.parametrize("dt,route", ROUTE_CASES, ids=ROUTE_IDS)
+def test_output_surroundings_and_repeatability(dt, route, monkeypatch):
+    on_route(route, dt, monkeypatch)
+    surroundings(dt, route, "vk_attention", 36, 20)
+
+
+@pytest.mark.parametrize("dt,route", LONG_CASES, ids=[f"{IDS[dt]}-{r}" for dt, r in LONG_CASES])
+@pytest.mark.parametrize("Lq", [36, 17])
+def test_output_surroundings_and_repeatability_long(dt, route, Lq, monkeypatch):
+    """The same around the tiled and streaming kernels, two key tiles (Lk = 70).  Lq = 36: the last query block (rows 32 .. 35 of
+    the tiled kernel's 32, rows 32 .. 35 of the streaming kernel's 16) is mostly padding rows, whose stores would land in the next
+    batch's rows or, for the last batch, in the guard row; Lq = 17: a last block of one live row."""
+    on_route(route, dt, monkeypatch)
+    surroundings(dt, route, "vk_attention_tiled", Lq, 70)

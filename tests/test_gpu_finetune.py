@@ -7,7 +7,10 @@ in another order).
 `attention.self.key.bias` has its own rule: its gradient is mathematically zero (soft-max ignores a shift of a score row), so what
 anyone computes for it is rounding noise, and AdamW divides noise below its eps by eps.  Gradient: |g[c]| <= gamma[c] =
 8 * max(max |g32|, 2^-23 * sum_m |dK[m, c]|).  Tensor after `steps` steps: |p - p64| <= steps * lr * gamma / eps + 8 * 2^-23 * max |p|,
-gamma the largest of the steps.  The measured ratios are printed (DESIGN.md section 27 records them)."""
+gamma the largest of the steps.  The measured ratios are printed (DESIGN.md section 27 records them).
+
+The fixture runs 16 rows of d = 8, so its fp32 forward is the LDS kernel; the `long` fixture (140 rows of d = 64) is past that
+kernel's image and runs attention_stream_kernel, which divides by l where the backward multiplies by 1 / l: the same rules."""
 import functools
 import os
 
@@ -36,11 +39,14 @@ NL = U.FIXTURE_CFG["num_hidden_layers"]
 
 class _Fixture:
     """The trajectory fixture, built at first use (collection builds nothing): .CFG, .SD, .INPUTS, .LABELS at hidden 32, and .WCFG,
-    .WSD at hidden 128, what a bf16 model can run; its inputs and labels are the same draws."""
+    .WSD at hidden 128, what a bf16 model can run; its inputs and labels are the same draws.  `long`: the fixture of 140 rows."""
+
+    def __init__(self, long=False):
+        self.long = long
 
     def __getattr__(self, name):
         wide = name.startswith("W")
-        made = dict(zip(("CFG", "SD", "INPUTS", "LABELS"), U.trajectory_fixture(wide=wide)))
+        made = dict(zip(("CFG", "SD", "INPUTS", "LABELS"), U.trajectory_fixture(wide=wide, long=self.long)))
         if name[wide:] not in made:
             raise AttributeError(name)
         for k, v in made.items():
@@ -49,6 +55,7 @@ class _Fixture:
 
 
 FX = _Fixture()
+FXL = _Fixture(long=True)                                 # Lx = 140, d = 64: the trainer's fp32 forward runs the streaming kernel
 
 
 class Recorder:
@@ -59,46 +66,46 @@ class Recorder:
         monkeypatch.setattr(L, "call", lambda name, *a: (self.calls.append(name), real(name, *a))[1])
 
 
-def make(precision="fp32"):
+def make(precision="fp32", fx=FX):
     """The fixture's model; a bf16 model is the wide one (its pooler takes hidden sizes in multiples of 64)."""
-    cfg, sd = (FX.CFG, FX.SD) if precision == "fp32" else (FX.WCFG, FX.WSD)
+    cfg, sd = (fx.CFG, fx.SD) if precision == "fp32" else (fx.WCFG, fx.WSD)
     return VisualBertForQuestionAnswering(cfg, U.FIXTURE_LABELS, precision=precision).load_state_dict(sd)
 
 
-def args():
+def args(fx=FX):
     """(positional inputs, keyword inputs) of the fixture as tensors."""
-    t = {k: torch.from_numpy(v) for k, v in FX.INPUTS.items()}
+    t = {k: torch.from_numpy(v) for k, v in fx.INPUTS.items()}
     return (t["input_ids"], t["visual_embeds"]), dict(attention_mask=t["attention_mask"], visual_attention_mask=t["visual_attention_mask"])
 
 
-def full_inputs():
-    pos, kw = args()
+def full_inputs(fx=FX):
+    pos, kw = args(fx)
     return pos + (kw["attention_mask"], kw["visual_attention_mask"], None, None, None)
 
 
-def trainer(n, model=None, sd=None, **kw):
+def trainer(n, model=None, sd=None, fx=FX, **kw):
     kw.setdefault("lr", U.FIXTURE_LR)
     kw.setdefault("schedule", step_lr(*U.FIXTURE_STEP_LR))
-    return EncoderTrainer(make() if model is None else model, FX.SD if sd is None else sd, train_layers=n, **kw)
+    return EncoderTrainer(make(fx=fx) if model is None else model, fx.SD if sd is None else sd, train_layers=n, **kw)
 
 
-def run_gpu(tr, steps):
-    pos, kw = args()
-    return np.array([float(tr.step(*pos, labels=FX.LABELS, **kw)) for _ in range(steps)], np.float64)
+def run_gpu(tr, steps, fx=FX):
+    pos, kw = args(fx)
+    return np.array([float(tr.step(*pos, labels=fx.LABELS, **kw)) for _ in range(steps)], np.float64)
 
 
 @functools.lru_cache(maxsize=None)
-def boundary(n):
+def boundary(n, fx=FX):
     """The fp32 model's own hidden state after its first NL - n layers -> [B, L, H] numpy."""
-    enc = make().visual_bert
-    x, _ = enc._hidden_after(NL - n, *full_inputs())
+    enc = make(fx=fx).visual_bert
+    x, _ = enc._hidden_after(NL - n, *full_inputs(fx))
     torch.cuda.synchronize()
-    return x.float().cpu().numpy().reshape(FX.INPUTS["input_ids"].shape[0], -1, FX.CFG["hidden_size"])
+    return x.float().cpu().numpy().reshape(fx.INPUTS["input_ids"].shape[0], -1, fx.CFG["hidden_size"])
 
 
 @functools.lru_cache(maxsize=None)
-def yardstick(n, steps, max_norm=None):
-    runs = [U.fixture_run(n, steps, dt, boundary(n), max_norm=max_norm) for dt in (torch.float32, torch.float64)]
+def yardstick(n, steps, max_norm=None, fx=FX):
+    runs = [U.fixture_run(n, steps, dt, boundary(n, fx), max_norm=max_norm, long=fx.long) for dt in (torch.float32, torch.float64)]
     return runs[0][0], runs[0][1], runs[1][1]
 
 
@@ -128,11 +135,10 @@ def hold(tag, keys, losses, tensors, run32, run64, lr=U.FIXTURE_LR):
     print(f"{tag}: worst ratio {worst:.2f}")
 
 
-@pytest.mark.parametrize("n", [1, 2])
-def test_first_step_gradients(n):
-    tr = trainer(n)
-    run_gpu(tr, 1)
-    keys, run32, run64 = yardstick(n, 3)
+def first_step_gradients(n, fx):
+    tr = trainer(n, fx=fx)
+    run_gpu(tr, 1, fx)
+    keys, run32, run64 = yardstick(n, 3, fx=fx)
     grads = tr.grads()
     assert tuple(grads) == keys == tuple(tr.state_dict())
     for k in keys:
@@ -147,14 +153,46 @@ def test_first_step_gradients(n):
         assert d_gpu <= 8 * max(d_cpu, FLOOR), k
 
 
+@pytest.mark.parametrize("n", [1, 2])
+def test_first_step_gradients(n):
+    first_step_gradients(n, FX)
+
+
+def trajectory(n, steps, fx, tag=""):
+    tr = trainer(n, fx=fx)
+    losses = run_gpu(tr, steps, fx)
+    assert tr.steps == steps and tr.lr == U.FIXTURE_LR and tr.grad_norm is None
+    keys, run32, run64 = yardstick(n, steps, fx=fx)
+    hold(f"{tag}n={n} {steps} steps", keys, losses, tr.state_dict(), run32, run64)
+
+
 @pytest.mark.parametrize("steps", [3, 10])
 @pytest.mark.parametrize("n", [1, 2])
 def test_trajectory(n, steps):
-    tr = trainer(n)
-    losses = run_gpu(tr, steps)
-    assert tr.steps == steps and tr.lr == U.FIXTURE_LR and tr.grad_norm is None
-    keys, run32, run64 = yardstick(n, steps)
-    hold(f"n={n} {steps} steps", keys, losses, tr.state_dict(), run32, run64)
+    trajectory(n, steps, FX)
+
+
+# ---- the trainer where its forward streams: Lx = 140 rows, 2 heads of d = 64 (the LDS kernel's image would be 187 600 bytes) -----------
+def streams(fx):
+    """The fixture's attention runs attention_stream_kernel: asked of the dispatcher on the trainer's packed projection."""
+    Lx = fx.INPUTS["input_ids"].shape[1] + fx.INPUTS["visual_embeds"].shape[1]
+    H, heads = fx.CFG["hidden_size"], fx.CFG["num_attention_heads"]
+    assert (Lx, H // heads, 3 * H) == (140, 64, 384) and fx.INPUTS["input_ids"].shape[0] == 2
+    assert not fx.INPUTS["attention_mask"].all() and not fx.INPUTS["visual_attention_mask"].all()          # both masks are partial
+    return L.load().vk_attention_route(140, 140, 64, L.VK_F32, 384, 384, 384, 1, 0) == L.VK_ATT_ROUTE_STREAM
+
+
+def test_first_step_gradients_where_the_forward_streams(monkeypatch):
+    """The forward divides by l (attention_stream_kernel), the backward multiplies by 1 / l: the pair under the file's rules."""
+    assert streams(FXL)
+    rec = Recorder(monkeypatch)
+    first_step_gradients(2, FXL)
+    assert rec.calls.count("vk_attention") == NL and rec.calls.count("vk_attention_grad") == 2
+
+
+def test_trajectory_where_the_forward_streams():
+    assert streams(FXL)
+    trajectory(2, 3, FXL, "Lx=140 ")
 
 
 @pytest.mark.parametrize("n", [1, 2])

@@ -15,7 +15,11 @@ DTYPES = [torch.float32, torch.float16, torch.bfloat16]
 FMIN = float(np.finfo(np.float32).min)
 ATT_CASES = [("mfma", 32, 1, 1), ("mfma", 64, 15, 17), ("mfma", 32, 20, 36), ("mfma", 64, 36, 20), ("mfma", 64, 48, 64), ("mfma", 32, 47, 49),
              ("lds", 16, 33, 31), ("lds", 64, 50, 100), ("lds", 20, 20, 36), ("lds", 64, 1, 64),
-             ("tiled", 64, 17, 65), ("tiled", 64, 33, 129), ("stream", 64, 17, 65), ("stream", 64, 33, 129)]
+             ("tiled", 64, 17, 65), ("tiled", 64, 33, 129), ("stream", 64, 17, 65), ("stream", 64, 33, 129),
+             # the D = 32 builds and three key tiles; then the head dims up to the contracts' limits (test_gpu_attention_builds.py)
+             ("tiled", 32, 13, 150), ("tiled", 32, 50, 129), ("stream", 32, 13, 150),
+             ("stream", 128, 17, 65), ("stream", 128, 33, 129), ("stream", 256, 17, 65), ("stream", 256, 33, 129), ("stream", 1, 17, 65),
+             ("lds", 128, 20, 36), ("lds", 256, 20, 36), ("lds", 64, 127, 127)]
 
 
 def draw(seed, B, heads, Lq, Lk, d, td):
