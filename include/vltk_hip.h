@@ -692,6 +692,41 @@ int vk_attention_grad(const float *q, long ldq, const float *k, long ldk, const 
                       long ldo, const float *dout, long lddo, float *dq, long lddq, float *dk, long lddk, float *dv, long lddv, int B,
                       int heads, int Lq, int Lk, int d, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- mixed-precision fine-tuning: 16-bit operands on the matrix cores, fp32 accumulation ---- */
+
+/* y[i] = x[i] rounded to dt (VK_BF16 or VK_F16, nearest even) over n dense elements, as the conversion instruction does it: Inf
+ * stays Inf, NaN stays NaN, values below the target's normal range become its subnormals. */
+int vk_cast_16(const float *x, void *y, long n, vk_dtype dt, void *stream);
+/* vk_gemm_f32's contract on 16-bit operands: C [M, N] = op(A) . op(B) (+ bias), the same three forms, A and B in dt (VK_BF16 or
+ * VK_F16), fp32 accumulation on v_mfma_f32_16x16x32, the fp32 bias (NULL: none) added in fp32, C written as fp32 (out_dt = VK_F32)
+ * or with one rounding as dt (out_dt = dt).  Any M, N, K >= 1; edges are masked and nothing outside the matrices is read, padding
+ * included.  A, B and C are 16-byte aligned and the leading dimensions of 16-bit matrices are multiples of 8 elements.  There is
+ * no accumulate flag (a residual is vk_add_f32's).  No split-K, no atomics: the same input gives the same bits; integer data
+ * whose sums stay below 2^24 is exact.  vk_gemm_16_check: what the launch refuses, host only (no pointer is read through): what
+ * vk_gemm_f32_check refuses, a NULL or misaligned A, B or C, a dt that is not 16-bit, an out_dt that is neither VK_F32 nor dt, a
+ * leading dimension of a 16-bit matrix that is no multiple of 8. */
+int vk_gemm_16_check(const void *A, long lda, int transA, const void *B, long ldb, int transB, const void *C, long ldc, int M, int N, int K,
+                     vk_dtype dt, vk_dtype out_dt);
+int vk_gemm_16(const void *A, long lda, int transA, const void *B, long ldb, int transB, const float *bias, void *C, long ldc, int M, int N,
+               int K, vk_dtype dt, vk_dtype out_dt, void *stream);
+/* The backward of the forward vk_attention_tiled runs in dt (VK_BF16 or VK_F16): vk_attention_grad's arguments and layout with
+ * q, k, v, o and dout in dt and dq, dk, dv in fp32.  Every product runs on the matrix cores with fp32 accumulation:
+ * s = (q . k) scale + mask and the online row maximum m and row sum l over 64-key tiles in fp32, P = exp(s - m) (1 / l) (rounded to
+ * dt for dv = P^T dout), D = sum_c dout o, dP = dout V^T, dS = P (dP - D) in fp32 (rounded to dt for dq = scale dS K and
+ * dk = scale dS^T Q).  d is 32 or 64, any Lq, Lk >= 1; every matrix is 16-byte aligned with a leading dimension that is a multiple
+ * of 8.  Two launches (statistics into `workspace` and dq; dk and dv), no atomics: the same input gives the same bits.
+ * vk_attention_grad_16_check: what the launch refuses, host only: a NULL pointer other than mask, a dt that is not 16-bit, a size
+ * below 1, d other than 32 or 64, a leading dimension below heads * d or no multiple of 8, a pointer that is not 16-byte
+ * aligned, a workspace below the size function's bytes. */
+size_t vk_attention_grad_16_workspace_bytes(int B, int heads, int Lq);
+int vk_attention_grad_16_check(const void *q, long ldq, const void *k, long ldk, const void *v, long ldv, const float *mask, const void *o,
+                               long ldo, const void *dout, long lddo, const float *dq, long lddq, const float *dk, long lddk,
+                               const float *dv, long lddv, int B, int heads, int Lq, int Lk, int d, vk_dtype dt, const void *workspace,
+                               size_t workspace_bytes);
+int vk_attention_grad_16(const void *q, long ldq, const void *k, long ldk, const void *v, long ldv, const float *mask, const void *o, long ldo,
+                         const void *dout, long lddo, float *dq, long lddq, float *dk, long lddk, float *dv, long lddv, int B, int heads,
+                         int Lq, int Lk, int d, vk_dtype dt, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- N4: FPN-side ops (what north_star names; the reference holds only fragments, see oracle/fpn_oracle.py) ---- */
 
 /* RoIAlign over a feature pyramid (torchvision roi_align semantics, `aligned` as detectron2's ROIAlignV2; the level loop of

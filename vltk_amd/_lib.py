@@ -174,6 +174,12 @@ SIGNATURES = {
     "vk_attention_grad_workspace_bytes": (_SZ, [_I, _I, _I]),
     "vk_attention_grad_check": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 5 + [_P, _SZ]),
     "vk_attention_grad": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 5 + [_P, _SZ, _P]),
+    "vk_cast_16": (_I, [_P, _P, C.c_long, _I, _P]),
+    "vk_gemm_16_check": (_I, [_P, C.c_long, _I, _P, C.c_long, _I, _P, C.c_long, _I, _I, _I, _I, _I]),
+    "vk_gemm_16": (_I, [_P, C.c_long, _I, _P, C.c_long, _I, _P, _P, C.c_long, _I, _I, _I, _I, _I, _P]),
+    "vk_attention_grad_16_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "vk_attention_grad_16_check": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 6 + [_P, _SZ]),
+    "vk_attention_grad_16": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 6 + [_P, _SZ, _P]),
     "vk_roi_align": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "vk_roi_align_form": (_I, [_I, _I, _I]),
     "vk_assign_levels": (_I, [_P, _I, _I, _I, _I, _F, _I, _P, _P]),

@@ -15,9 +15,16 @@ cast there is, at the boundary: the frozen layers' 16-bit hidden state to fp32, 
 and what the kernels (and torch) compute for it is rounding noise below AdamW's eps.  It is trained as torch trains it; only weight
 decay moves it in earnest.
 
-Out of scope: dropout, 16-bit training GEMMs, HIP-graph capture of a step, training the embeddings, ViT (pre-LN layers) and LXMERT
-(cross-attention top layers), and running the top layer only on the rows the head reads (for `train_layers=1` the FFN is needed
-on B rows, not B * L: measure first, then build it as its own change).
+`compute_dtype=torch.bfloat16` is the mixed-precision mode, what `torch.autocast` gives: fp32 masters,
+gradients and optimiser; bf16 operands on the matrix cores for every layer GEMM (`vk_gemm_16` after `vk_cast_16`) and for attention
+(`vk_attention_tiled` forward, `vk_attention_grad_16` backward, csrc/gemm16.hip and csrc/attention_grad16.hip); fp32 accumulation,
+LayerNorm, GELU, column sums, residual adds, head and loss, on the kernels of the fp32 mode.  The default, `None`, is the fp32
+trainer with every launch and every bit as before.
+
+Out of scope: dropout, HIP-graph capture of a step, training the embeddings, ViT (pre-LN layers) and LXMERT (cross-attention top
+layers), running the top layer only on the rows the head reads (for `train_layers=1` the FFN is needed on B rows, not B * L:
+measure first, then build it as its own change), fp16 as the compute type (its gradients need loss scaling) and producers that
+write both precisions at once (the cast passes are measured first).
 """
 import numpy as np
 import torch
@@ -26,7 +33,8 @@ from . import _lib as L
 from .bert_ops import LN_EPS, bert_layer_spec, to_numpy
 from .layers import stream
 from .lxmert import IGNORE_INDEX, check_class_labels
-from .train import _ptr, act_f32, act_grad_f32, adamw_step, adamw_table, col_sums, cross_entropy_grad, gemm_f32, layernorm_f32, layernorm_grad
+from .train import (VK_16, _ptr, act_f32, act_grad_f32, adamw_step, adamw_table, cast_16, col_sums, cross_entropy_grad, gemm_16, gemm_f32,
+                    layernorm_f32, layernorm_grad)
 
 
 # ---- the ops train.py does not have: one call into the C ABI each -----------------------------------------------------------------
@@ -50,6 +58,31 @@ def attention_grad(qkv, mask, ctx, dctx, B, Lx, heads):
     L.call("vk_attention_grad", qkv.data_ptr(), ld, qkv.data_ptr() + H * es, ld, qkv.data_ptr() + 2 * H * es, ld, _ptr(mask), ctx.data_ptr(),
            ctx.stride(0), dctx.data_ptr(), dctx.stride(0), dqkv.data_ptr(), ld, dqkv.data_ptr() + H * es, ld, dqkv.data_ptr() + 2 * H * es, ld,
            B, heads, Lx, Lx, H // heads, work.data_ptr(), nbytes, stream(qkv.device))
+    return dqkv
+
+
+def attention_16(qkv, mask, B, Lx, heads):
+    """`vk_attention_tiled` on a packed bf16 / fp16 projection `qkv [B * Lx, 3H]` -> the context rows [B * Lx, H] in its dtype."""
+    H = qkv.shape[1] // 3
+    out = torch.empty((B * Lx, H), dtype=qkv.dtype, device=qkv.device)
+    ld, es = qkv.stride(0), qkv.element_size()
+    L.call("vk_attention_tiled", qkv.data_ptr(), ld, qkv.data_ptr() + H * es, ld, qkv.data_ptr() + 2 * H * es, ld, _ptr(mask), out.data_ptr(),
+           H, B, heads, Lx, Lx, H // heads, VK_16[qkv.dtype], stream(qkv.device))
+    return out
+
+
+def attention_grad_16(qkv, mask, ctx, dctx, B, Lx, heads):
+    """`vk_attention_grad_16` on the packed 16-bit projection the forward kept, its context rows and their gradient (all of one
+    dtype) -> dqkv [B * Lx, 3H] (dQ | dK | dV) in fp32."""
+    H = qkv.shape[1] // 3
+    assert qkv.dtype in VK_16 and ctx.dtype == dctx.dtype == qkv.dtype
+    dqkv = torch.empty(qkv.shape, dtype=torch.float32, device=qkv.device)
+    ld, es = qkv.stride(0), qkv.element_size()
+    nbytes = L.load().vk_attention_grad_16_workspace_bytes(B, heads, Lx)
+    work = torch.empty((nbytes // 4,), dtype=torch.float32, device=qkv.device)
+    L.call("vk_attention_grad_16", qkv.data_ptr(), ld, qkv.data_ptr() + H * es, ld, qkv.data_ptr() + 2 * H * es, ld, _ptr(mask),
+           ctx.data_ptr(), ctx.stride(0), dctx.data_ptr(), dctx.stride(0), dqkv.data_ptr(), ld, dqkv.data_ptr() + H * 4, ld,
+           dqkv.data_ptr() + 2 * H * 4, ld, B, heads, Lx, Lx, H // heads, VK_16[qkv.dtype], work.data_ptr(), nbytes, stream(qkv.device))
     return dqkv
 
 
@@ -111,6 +144,28 @@ def _describe(model):
     raise TypeError(f"EncoderTrainer takes VisualBertForQuestionAnswering or LayoutLMForSequenceClassification, not {type(model).__name__}{why}")
 
 
+def _check_compute_dtype(compute_dtype, cfg):
+    """None (the fp32 trainer) or torch.bfloat16 where the encoder's sizes allow the 16-bit kernels; ValueError otherwise."""
+    if compute_dtype is None:
+        return None
+    if compute_dtype == torch.float16:
+        raise ValueError("compute_dtype=torch.float16: fp16 gradients underflow without loss scaling, which the trainer does not do; "
+                         "use torch.bfloat16 (the kernels themselves take fp16)")
+    if compute_dtype != torch.bfloat16:
+        raise ValueError(f"compute_dtype must be None (fp32) or torch.bfloat16, not {compute_dtype}: the mixed mode's kernels take 16-bit operands")
+    H, I, heads = cfg["hidden_size"], cfg["intermediate_size"], cfg["num_attention_heads"]
+    if H // heads not in (32, 64) or H % heads:
+        raise ValueError(f"compute_dtype=torch.bfloat16: the head dim is {H // heads}, and the 16-bit attention kernels take 32 or 64 only")
+    if H % 8 or I % 8:
+        raise ValueError(f"compute_dtype=torch.bfloat16: hidden size {H} and intermediate size {I} must be multiples of 8 "
+                         "(16-byte rows of 16-bit matrices)")
+    return compute_dtype
+
+
+# the weight matrices of a trained layer that the mixed mode keeps a 16-bit copy of (the packed [3H, H] QKV master beside them)
+_LAYER_MATRICES = (".attention.output.dense.weight", ".intermediate.dense.weight", ".output.dense.weight")
+
+
 class EncoderTrainer:
     """`EncoderTrainer(model, state_dict, train_layers=1, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, no_decay=(),
     schedule=None, max_grad_norm=None)`: trains the last `train_layers` BERT layers and the head of
@@ -124,15 +179,22 @@ class EncoderTrainer:
     trainer holds fp32 masters, gradients and AdamW's `m`, `v` under transformers' key names.  `no_decay`, `schedule`: as
     `HeadTrainer`.  `train_layers=0` is `HeadTrainer`'s job.
 
+    `compute_dtype=torch.bfloat16` runs the trained layers in mixed precision: each step casts the trained weight matrices to
+    bf16 copies, every layer GEMM and attention, forward and backward, takes bf16 operands on the matrix cores and accumulates
+    in fp32; masters, gradients, AdamW, clipping, LayerNorm, GELU, the head and the loss stay fp32.  It needs a head dim of 32 or
+    64 and hidden / intermediate sizes that are multiples of 8; `torch.float16` and every other dtype are refused (ValueError).
+    It is independent of the model's own precision.  `compute_dtype` (read-only) tells the mode; `None` is the fp32 trainer.
+
     The model keeps answering with the weights it was loaded with until `commit()`.  Out of scope: see the module docstring."""
 
     def __init__(self, model, state_dict, train_layers=1, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, no_decay=(),
-                 schedule=None, max_grad_norm=None):
+                 schedule=None, max_grad_norm=None, compute_dtype=None):
         if not torch.cuda.is_available():
             raise RuntimeError("vltk_amd.EncoderTrainer needs a GPU: there is no CPU fallback")
         self.enc, self.enc_prefix, self.head, self.pooled = _describe(model)
         self.model = model
         enc, cfg = self.enc, self.enc.cfg
+        self._compute_dtype = _check_compute_dtype(compute_dtype, cfg)
         nl = cfg["num_hidden_layers"]
         n = int(train_layers)
         if n == 0:
@@ -180,6 +242,13 @@ class EncoderTrainer:
             if k not in self.p:
                 self.p[k] = torch.from_numpy(np.ascontiguousarray(sd[k])).to(dev)
                 self.g[k] = torch.zeros_like(self.p[k])
+        # the mixed mode's 16-bit copies of the weight matrices, refreshed from the masters at the start of every step
+        self._w16 = {}
+        if self._compute_dtype is not None:
+            for lay in self._layers:
+                self._w16[lay["prefix"] + ".qkv"] = torch.empty_like(lay["qkv_weight"], dtype=self._compute_dtype)
+                for t in _LAYER_MATRICES:
+                    self._w16[lay["prefix"] + t] = torch.empty_like(self.p[lay["prefix"] + t], dtype=self._compute_dtype)
         self.m, self.v = ({k: torch.zeros_like(self.p[k]) for k in self.keys} for _ in range(2))
         self.base_lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.schedule = schedule
@@ -205,6 +274,71 @@ class EncoderTrainer:
         if self.max_grad_norm is None or self.steps == 0:
             return None
         return float(self._norm_coef[0])
+
+    @property
+    def compute_dtype(self):
+        """None: the fp32 trainer; torch.bfloat16: the mixed-precision mode."""
+        return self._compute_dtype
+
+    # ---- the mixed mode: the same layer with 16-bit operands on the matrix cores, fp32 everywhere else ------------------------------
+    def _cast_weights(self):
+        """The 16-bit copies of the trained weight matrices from the fp32 masters; the packed QKV master of a layer is one cast."""
+        for lay in self._layers:
+            P = lay["prefix"]
+            cast_16(lay["qkv_weight"], self._compute_dtype, out=self._w16[P + ".qkv"])
+            for t in _LAYER_MATRICES:
+                cast_16(self.p[P + t], self._compute_dtype, out=self._w16[P + t])
+
+    def _layer_forward_16(self, lay, x, mask, B, Lx):
+        """`_layer_forward` with every GEMM and the attention on 16-bit operands.  Kept for the backward: the 16-bit copies of what
+        only a GEMM or the attention backward reads again (x, qkv, ctx, a, h) and the fp32 inputs of the fp32 backward kernels
+        (t1, t2, z)."""
+        P, p, w, dt = lay["prefix"], self.p, self._w16, self._compute_dtype
+        kept = {"x": cast_16(x, dt)}
+        qkv = kept["qkv"] = gemm_16(kept["x"], w[P + ".qkv"], lay["qkv_bias"], trans_b=True, out_dtype=dt)
+        ctx = kept["ctx"] = attention_16(qkv, mask, B, Lx, self.heads)
+        t1 = gemm_16(ctx, w[P + ".attention.output.dense.weight"], p[P + ".attention.output.dense.bias"], trans_b=True)
+        kept["t1"] = add_f32(t1, x, out=t1)                              # the residual, fp32
+        a = layernorm_f32(t1, p[P + ".attention.output.LayerNorm.weight"], p[P + ".attention.output.LayerNorm.bias"], self.ln_eps)
+        kept["a"] = cast_16(a, dt)
+        z = kept["z"] = gemm_16(kept["a"], w[P + ".intermediate.dense.weight"], p[P + ".intermediate.dense.bias"], trans_b=True)
+        kept["h"] = cast_16(act_f32(z, L.VK_ACT_GELU), dt)
+        t2 = gemm_16(kept["h"], w[P + ".output.dense.weight"], p[P + ".output.dense.bias"], trans_b=True)
+        kept["t2"] = add_f32(t2, a, out=t2)
+        return layernorm_f32(t2, p[P + ".output.LayerNorm.weight"], p[P + ".output.LayerNorm.bias"], self.ln_eps), kept
+
+    def _layer_backward_16(self, lay, kept, dy, mask, B, Lx, need_dx):
+        """`_layer_backward` in the mixed mode: an fp32 gradient is cast once and feeds both of its GEMMs (dW straight into the fp32
+        gradient buffer, dX in fp32, or in 16 bits where attention reads it); bias gradients are column sums of the fp32 gradient."""
+        P, p, g, w, dt = lay["prefix"], self.p, self.g, self._w16, self._compute_dtype
+        k = P + ".output.LayerNorm"
+        dt2, _, _ = layernorm_grad(kept["t2"], p[k + ".weight"], dy, self.ln_eps, dgamma=g[k + ".weight"], dbeta=g[k + ".bias"])
+        k = P + ".output.dense"
+        dt2_16 = cast_16(dt2, dt)
+        gemm_16(dt2_16, kept["h"], out=g[k + ".weight"], trans_a=True)   # dW = dY^T . X
+        col_sums(dt2, out=g[k + ".bias"])
+        dz = act_grad_f32(kept["z"], gemm_16(dt2_16, w[k + ".weight"]), L.VK_ACT_GELU)
+        k = P + ".intermediate.dense"
+        dz_16 = cast_16(dz, dt)
+        gemm_16(dz_16, kept["a"], out=g[k + ".weight"], trans_a=True)
+        col_sums(dz, out=g[k + ".bias"])
+        da = gemm_16(dz_16, w[k + ".weight"])
+        add_f32(da, dt2, out=da)                                         # the residual path
+        k = P + ".attention.output.LayerNorm"
+        dt1, _, _ = layernorm_grad(kept["t1"], p[k + ".weight"], da, self.ln_eps, dgamma=g[k + ".weight"], dbeta=g[k + ".bias"])
+        k = P + ".attention.output.dense"
+        dt1_16 = cast_16(dt1, dt)
+        gemm_16(dt1_16, kept["ctx"], out=g[k + ".weight"], trans_a=True)
+        col_sums(dt1, out=g[k + ".bias"])
+        dctx = gemm_16(dt1_16, w[k + ".weight"], out_dtype=dt)
+        dqkv = attention_grad_16(kept["qkv"], mask, kept["ctx"], dctx, B, Lx, self.heads)
+        dqkv_16 = cast_16(dqkv, dt)
+        gemm_16(dqkv_16, kept["x"], out=lay["g_qkv_weight"], trans_a=True)
+        col_sums(dqkv, out=lay["g_qkv_bias"])
+        if not need_dx:
+            return None
+        dx = gemm_16(dqkv_16, w[P + ".qkv"])
+        return add_f32(dx, dt1, out=dx)
 
     # ---- one BERT layer in fp32 (bert_ops.BertOps._bert_layer), activations kept ----------------------------------------------------
     def _layer_forward(self, lay, x, mask, B, Lx):
@@ -272,7 +406,7 @@ class EncoderTrainer:
     @torch.no_grad()
     def step(self, *model_inputs, labels, **options):
         """One training step on `model_inputs` (the model's own arguments): the frozen layers' forward in the model's precision,
-        the trained layers and the head in fp32, cross-entropy against `labels [B]` (a class each, -100 to leave a row out),
+        the trained layers in fp32 (or in the mixed mode `compute_dtype` names) and the head in fp32, cross-entropy against `labels [B]` (a class each, -100 to leave a row out),
         backward, clipping where asked, one AdamW step over every trained tensor; the schedule advances.  -> the loss before
         the step, an fp32 device scalar.  Labels are checked on the host before any launch, as `HeadTrainer.step` checks them."""
         inputs = self._inputs(model_inputs, options)
@@ -285,9 +419,12 @@ class EncoderTrainer:
         labels_dev = torch.from_numpy(lab).to(dev)
         x, mask = enc._hidden_after(self.first, *inputs)
         x = x.to(torch.float32).contiguous()                             # the boundary hidden state
+        mixed = self._compute_dtype is not None
+        if mixed:
+            self._cast_weights()
         kept = []
         for lay in self._layers:
-            x, act = self._layer_forward(lay, x, mask, B, Lx)
+            x, act = (self._layer_forward_16 if mixed else self._layer_forward)(lay, x, mask, B, Lx)
             kept.append(act)
         # head forward
         kw, kb = self.head + ".weight", self.head + ".bias"
@@ -317,7 +454,7 @@ class EncoderTrainer:
         dy = scatter_rows_f32(drows, idx, B * Lx)
         # backward: layers, top down
         for j in range(len(self._layers) - 1, -1, -1):
-            dy = self._layer_backward(self._layers[j], kept[j], dy, mask, B, Lx, need_dx=j > 0)
+            dy = (self._layer_backward_16 if mixed else self._layer_backward)(self._layers[j], kept[j], dy, mask, B, Lx, need_dx=j > 0)
         if self.max_grad_norm is not None:
             grad_clip(self._table, len(self.keys), self._max_n, self.max_grad_norm, self._norm_coef, self._clip_work)
         adamw_step(self._table, len(self.keys), self._max_n, self.lr, self.betas, self.eps, self.weight_decay, self.steps + 1, dev)

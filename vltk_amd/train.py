@@ -72,6 +72,35 @@ def gemm_f32(a, b, bias=None, out=None, trans_a=False, trans_b=False, accumulate
     return out
 
 
+# the 16-bit ops of EncoderTrainer's mixed-precision mode (finetune.py): bf16 / fp16 operands, fp32 accumulation
+VK_16 = {torch.bfloat16: L.VK_BF16, torch.float16: L.VK_F16}
+
+
+def cast_16(x, dtype=torch.bfloat16, out=None):
+    """Contiguous fp32 `x` rounded to `dtype` (bf16 / fp16, nearest even): `vk_cast_16`, into `out` or a new tensor."""
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    out = torch.empty(x.shape, dtype=dtype, device=x.device) if out is None else out
+    assert out.dtype == dtype and out.is_contiguous() and out.shape == x.shape
+    L.call("vk_cast_16", x.data_ptr(), out.data_ptr(), x.numel(), VK_16[dtype], stream(x.device))
+    return out
+
+
+def gemm_16(a, b, bias=None, out=None, trans_a=False, trans_b=False, out_dtype=torch.float32):
+    """out [M, N] = op(a) . op(b) (+ bias): `vk_gemm_16` on 2-D bf16 / fp16 tensors of one dtype, fp32 accumulation; `out` (or
+    `out_dtype` for a new tensor) is fp32 or the operands' dtype.  The fp32 bias is added in fp32."""
+    M, K = (a.shape[1], a.shape[0]) if trans_a else a.shape
+    N = b.shape[0] if trans_b else b.shape[1]
+    if out is None:
+        out = torch.empty((M, N), dtype=out_dtype, device=a.device)
+    assert a.dtype == b.dtype and a.dtype in VK_16 and out.dtype in (torch.float32, a.dtype)
+    assert bias is None or bias.dtype == torch.float32
+    for t in (a, b, out):
+        assert t.stride(1) == 1
+    L.call("vk_gemm_16", a.data_ptr(), a.stride(0), int(trans_a), b.data_ptr(), b.stride(0), int(trans_b), _ptr(bias), out.data_ptr(),
+           out.stride(0), M, N, K, VK_16[a.dtype], L.VK_F32 if out.dtype == torch.float32 else VK_16[a.dtype], stream(a.device))
+    return out
+
+
 def col_sums(x, out=None):
     M, N = x.shape
     out = torch.empty((N,), dtype=torch.float32, device=x.device) if out is None else out
