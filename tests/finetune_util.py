@@ -151,17 +151,23 @@ WIDE = dict(hidden_size=128, num_attention_heads=4, intermediate_size=256)      
 LONG = dict(hidden_size=128, num_attention_heads=2, intermediate_size=256, max_position_embeddings=24)
 LONG_SHAPE = (2, 24, 116)                                                       # B, Lt, V
 
+# BERT-base width: 12 heads of d = 64, I = 3072; 16 sequences of Lx = 20 + 36 = 56 rows are 896 rows, where vk_gemm_f32 and
+# vk_gemm_16 pick the 128 x 128 tile for some of a layer's products and the 64 x 64 tile for the others.
+BASE = dict(hidden_size=768, num_attention_heads=12, intermediate_size=3072, max_position_embeddings=24)
+BASE_SHAPE = (16, 20, 36)                                                       # B, Lt, V
 
-def trajectory_fixture(seed=FIXTURE_SEED, wide=False, long=False):
+
+def trajectory_fixture(seed=FIXTURE_SEED, wide=False, long=False, base=False):
     """-> (cfg, state dict, inputs {name: numpy}, labels int64 [B]): partial text and visual masks (every text mask keeps at
     least 3 tokens, so the gathered row exists), every ninth label -100.  `wide`: the same fixture at hidden 128, I = 256, which
     a bf16 model can run (its own forward ends in the pooler, whose kernel takes channels in multiples of 64 in 16-bit types).
-    `long`: hidden 128 in 2 heads (d = 64), B = 2, Lt = 24, V = 116, drawn in the same order from the same generator."""
+    `long`: hidden 128 in 2 heads (d = 64), B = 2, Lt = 24, V = 116, drawn in the same order from the same generator.
+    `base`: BASE at B = 16, Lt = 20, V = 36, likewise."""
     from vltk_amd.visualbert import make_visualbert_qa_state_dict, visualbert_config
-    cfg = visualbert_config(**dict(FIXTURE_CFG, **(WIDE if wide else {}), **(LONG if long else {})))
+    cfg = visualbert_config(**dict(FIXTURE_CFG, **(WIDE if wide else {}), **(LONG if long else {}), **(BASE if base else {})))
     sd = make_visualbert_qa_state_dict(cfg, FIXTURE_LABELS, seed)
     r = np.random.Generator(np.random.PCG64([seed, 77]))
-    B, Lt, V = LONG_SHAPE if long else (16, 9, 7)
+    B, Lt, V = LONG_SHAPE if long else BASE_SHAPE if base else (16, 9, 7)
     ids = r.integers(1, cfg["vocab_size"], (B, Lt)).astype(np.int64)
     feats = (np.maximum(r.standard_normal((B, V, cfg["visual_embedding_dim"])), 0) * 2.0).astype(np.float32)
     am = (np.arange(Lt)[None] < r.integers(3, Lt + 1, (B, 1))).astype(np.int64)
@@ -185,9 +191,9 @@ def fixture_boundary_cpu(cfg, sd, inputs, first):
     return x.numpy()
 
 
-def fixture_run(n, steps, dtype, x0, max_norm=None, seed=FIXTURE_SEED, long=False):
+def fixture_run(n, steps, dtype, x0, max_norm=None, seed=FIXTURE_SEED, long=False, base=False):
     """The yardstick on the trajectory fixture with the last n layers trained, from the boundary state x0."""
-    cfg, sd, inputs, labels = trajectory_fixture(seed, long=long)
+    cfg, sd, inputs, labels = trajectory_fixture(seed, long=long, base=base)
     nl = cfg["num_hidden_layers"]
     layers = [f"visual_bert.encoder.layer.{i}" for i in range(nl - n, nl)]
     keys = trained_keys("visual_bert.", range(nl - n, nl), "cls")

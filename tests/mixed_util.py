@@ -223,10 +223,10 @@ def finetune_run(sd, keys, x0, mask01, labels, steps, layers, heads, eps, kind, 
     return out
 
 
-def fixture_run(n, steps, x0, compute_dtype, wide=False, long=False, max_norm=None):
-    """`finetune_run` on the trajectory fixture (wide: hidden 128, 4 heads of d = 32; long: 2 heads of d = 64, 140 rows) with the
-    last n layers trained, from the boundary state x0."""
-    cfg, sd, inputs, labels = U.trajectory_fixture(wide=wide, long=long)
+def fixture_run(n, steps, x0, compute_dtype, wide=False, long=False, max_norm=None, base=False):
+    """`finetune_run` on the trajectory fixture (wide: hidden 128, 4 heads of d = 32; long: 2 heads of d = 64, 140 rows; base:
+    BERT-base width, 12 heads of d = 64, 896 rows) with the last n layers trained, from the boundary state x0."""
+    cfg, sd, inputs, labels = U.trajectory_fixture(wide=wide, long=long, base=base)
     nl = cfg["num_hidden_layers"]
     layers = [f"visual_bert.encoder.layer.{i}" for i in range(nl - n, nl)]
     keys = U.trained_keys("visual_bert.", range(nl - n, nl), "cls")

@@ -131,7 +131,8 @@ CASE_D = [(2, 3, 16, 17, 16, False, 8), (1, 1, 35, 35, 4, False, 32), (1, 3, 1, 
           (1, 1, 15, 131, 16, False, 128), (1, 3, 35, 35, 16, True, 16), (2, 1, 131, 131, 4, True, 64)]
 
 
-def exact_case(kind, B, heads, Lq, Lk, d, packed, left=None, dense=False):
+def exact_data(kind, B, heads, Lq, Lk, d, packed, left=None):
+    """-> (q, k, v, mask, dout) of an exact case, float64."""
     r = np.random.Generator(np.random.PCG64([ord(kind), B, heads, Lq, Lk, d]))
     H = heads * d
     q, k, v, dout = ints(r, B, Lq, H), ints(r, B, Lk, H), ints(r, B, Lk, H), ints(r, B, Lq, H)
@@ -144,6 +145,11 @@ def exact_case(kind, B, heads, Lq, Lk, d, packed, left=None, dense=False):
         mask = keep_mask(r, B, Lk, 1)
     if kind == "d":
         mask = keep_mask(r, B, Lk, left)
+    return q, k, v, mask, dout
+
+
+def exact_case(kind, B, heads, Lq, Lk, d, packed, left=None, dense=False):
+    q, k, v, mask, dout = exact_data(kind, B, heads, Lq, Lk, d, packed, left)
     ref = U.attention_grad_reference(q, k, v, mask, dout, heads, scale=U.launcher_scale(d))      # d a power of four: 1 / sqrt(d) itself
     assert U.exact_in_fp32(ref), "the case's own data is not exact in fp32"
     got = run_attention_grad(*(t.astype(np.float32) for t in (q, k, v)), mask, ref["o"].astype(np.float32), dout.astype(np.float32), heads, packed, dense=dense)

@@ -57,8 +57,12 @@ def run_gemm(A, B, ta, tb, bias=None, C0=None):
 
 
 # ---- vk_gemm_f32 ---------------------------------------------------------------------------------------------------------------------
+GEMM_EXACT = [(1, 1, 1), (33, 65, 3), (31, 130, 34), (130, 33, 65), (64, 259, 7)]           # the exact sizes (M, N, K); other files run them too
+GEMM_EXACT_LARGE = (1400, 1500, 40)                                                         # the 128 x 128 tile
+
+
 @pytest.mark.parametrize("form", list(FORMS))
-@pytest.mark.parametrize("M,N,K", [(1, 1, 1), (33, 65, 3), (31, 130, 34), (130, 33, 65), (64, 259, 7)])
+@pytest.mark.parametrize("M,N,K", GEMM_EXACT)
 def test_gemm_exact_on_integers(M, N, K, form):
     """Integers in [-8, 8]: every partial sum is an integer below 2^24, so the fmaf chain is exact and the result is numpy's integer
     product bit for bit: plain, with bias, and accumulated onto a non-zero C with bias."""
@@ -78,7 +82,7 @@ def test_gemm_exact_on_integers(M, N, K, form):
 @pytest.mark.parametrize("form", ["NT", "NN", "TN"])
 def test_gemm_exact_on_integers_large_tile(form):
     """A shape whose 128 x 128 tiles fill half the CUs and so runs the large-tile kernel, ragged in M, N and K (two K steps)."""
-    M, N, K = 1400, 1500, 40
+    M, N, K = GEMM_EXACT_LARGE
     assert 2 * (-(-M // 128)) * (-(-N // 128)) >= torch.cuda.get_device_properties(0).multi_processor_count
     ta, tb = FORMS[form]
     r = np.random.Generator(np.random.PCG64([7, ta, tb]))

@@ -22,14 +22,20 @@ namespace vk {
 constexpr int CE_VEC_MIN_C = 128;       // narrower rows go to the wave-per-row form
 
 // The running (max, sum of exp(x - max)) of a row.  exp(m_old - m_new) is skipped where the maximum did not move: the factor is
-// then exactly 1, and -inf - -inf (a lane that has seen nothing yet) never reaches the exponential.
+// then exactly 1, and the -inf - -inf of two sides that have seen nothing finite yet never reaches rescale's exponential.  That
+// covers the joins only.  An ELEMENT's own term is exp(x - m) with m = max(running, x), and a -inf logit in front of every finite
+// one gives -inf - -inf there: `term` adds 0 for a -inf element (what exp(-inf - m) is for every other m, so no bit changes
+// where the maximum is finite, and what torch gives).  The select looks at the element, not at m: fmaxf drops a NaN, so m can
+// still be -inf when a NaN logit arrives, and that NaN must reach the exponential.  A NaN logit gives NaN, a +inf logit
+// inf - inf = NaN, and a row of nothing but -inf lse = -inf and the loss -inf - -inf = NaN, all as torch.
 struct OnlineLse {
     float m, s;
 };
 __device__ __forceinline__ float rescale(float m_old, float m_new) { return m_old == m_new ? 1.0f : __expf(m_old - m_new); }
+__device__ __forceinline__ float term(float x, float m) { return x == -INFINITY ? 0.0f : __expf(x - m); }
 __device__ __forceinline__ void lse_add(OnlineLse &a, float x) {
     const float m = fmaxf(a.m, x);
-    a.s = a.s * rescale(a.m, m) + __expf(x - m);
+    a.s = a.s * rescale(a.m, m) + term(x, m);
     a.m = m;
 }
 __device__ __forceinline__ void lse_join(OnlineLse &a, float m2, float s2) {
@@ -74,7 +80,7 @@ __global__ __launch_bounds__(256) void ce_vec_kernel(const T *__restrict__ logit
         const float m = fmaxf(a.m, cm);
         float t = 0.0f;
 #pragma unroll
-        for (int e = 0; e < VW; ++e) t += __expf(v[e] - m);
+        for (int e = 0; e < VW; ++e) t += term(v[e], m);
         a.s = a.s * rescale(a.m, m) + t;
         a.m = m;
     }
