@@ -83,8 +83,7 @@ def device_ms(launch, warmup, steps):
 
 def kernels_alone(warmup, steps):
     """Each new kernel beside the fp32 kernel it stands in for -> {name: {fp32_ms, bf16_ms, speedup, tflops of both}}."""
-    from vltk_amd.finetune import attention_grad, attention_grad_16
-    from vltk_amd.train import gemm_16, gemm_f32
+    from vltk_amd.train import attention_grad, gemm_16, gemm_f32
     g = torch.Generator(device="cuda").manual_seed(0)
     out = {}
     for B, heads, Lx, d in ((1024, 12, 56, 64), (32, 12, 512, 64)):
@@ -92,7 +91,7 @@ def kernels_alone(warmup, steps):
         qkv, ctx, dctx = (torch.randn((B * Lx, w), device="cuda", generator=g) for w in (3 * H, H, H))
         h16 = [t.to(torch.bfloat16) for t in (qkv, ctx, dctx)]
         t32 = device_ms(lambda: attention_grad(qkv, None, ctx, dctx, B, Lx, heads), warmup, steps)
-        t16 = device_ms(lambda: attention_grad_16(*h16[:1], None, *h16[1:], B, Lx, heads), warmup, steps)
+        t16 = device_ms(lambda: attention_grad(*h16[:1], None, *h16[1:], B, Lx, heads), warmup, steps)      # bf16: vk_attention_grad_16
         flop = 10.0 * B * heads * Lx * Lx * d
         out[f"attention_grad B{B} h{heads} L{Lx} d{d}"] = dict(fp32_ms=round(t32, 3), bf16_ms=round(t16, 3), speedup=round(t32 / t16, 2),
                                                                    fp32_tflops=round(flop / t32 * 1e-9, 2), bf16_tflops=round(flop / t16 * 1e-9, 2))

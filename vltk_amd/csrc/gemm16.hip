@@ -192,12 +192,7 @@ static int gemm16_check(const void *A, long lda, int transA, const void *B, long
     VK_REQUIRE(A && B && C, VK_EINVAL, "gemm_16: null argument");
     VK_REQUIRE(is16(dt), VK_EINVAL, "gemm_16: dt must be f16 or bf16 (fp32 operands are vk_gemm_f32's)");
     VK_REQUIRE(out_dt == VK_F32 || out_dt == dt, VK_EINVAL, "gemm_16: out_dt must be f32 or dt");
-    VK_REQUIRE(M >= 1 && N >= 1 && K >= 1, VK_EINVAL, "gemm_16: sizes must be positive, got M=%d N=%d K=%d", M, N, K);
-    VK_REQUIRE((transA == 0 || transA == 1) && (transB == 0 || transB == 1), VK_EINVAL, "gemm_16: transA=%d transB=%d must be 0 or 1", transA,
-               transB);
-    VK_REQUIRE(lda >= (transA ? M : K), VK_EINVAL, "gemm_16: lda=%ld is below A's row width %d", lda, transA ? M : K);
-    VK_REQUIRE(ldb >= (transB ? K : N), VK_EINVAL, "gemm_16: ldb=%ld is below B's row width %d", ldb, transB ? K : N);
-    VK_REQUIRE(ldc >= N, VK_EINVAL, "gemm_16: ldc=%ld is below C's row width %d", ldc, N);
+    VK_TRY(gemm_shape_check("gemm_16", M, N, K, lda, ldb, ldc, transA, transB));
     VK_REQUIRE(lda % 8 == 0 && ldb % 8 == 0, VK_EINVAL, "gemm_16: lda=%ld and ldb=%ld must be multiples of 8 elements (16-byte rows)", lda, ldb);
     VK_REQUIRE(out_dt == VK_F32 || ldc % 8 == 0, VK_EINVAL, "gemm_16: ldc=%ld of a 16-bit C must be a multiple of 8 elements", ldc);
     VK_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0, VK_EINVAL, "gemm_16: A, B and C must be 16-byte aligned");
@@ -207,8 +202,7 @@ static int gemm16_check(const void *A, long lda, int transA, const void *B, long
 
 template <typename T>
 static int gemm16_launch(const Gemm16Args &g, int n_cu, hipStream_t s) {
-    const long big = (long)ceil_div(g.M, 128) * ceil_div(g.N, 128);
-    if (big * 2 >= n_cu) {
+    if (large_tile(g.M, g.N, n_cu)) {
         const size_t smem = (size_t)2 * 128 * G16_PP * sizeof(T);
         return launch_lds(gemm16_kernel<T, 4>, dim3(ceil_div(g.N, 128), ceil_div(g.M, 128)), dim3(256), smem, smem, s, g);
     }

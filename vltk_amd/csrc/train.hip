@@ -429,16 +429,6 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(const vk_adamw_tensor *
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < t.n; i += (long)gridDim.x * 256) g[i] = g[i] * coef;
 }
 
-static int gemm_check(int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB) {
-    VK_REQUIRE(M >= 1 && N >= 1 && K >= 1, VK_EINVAL, "gemm_f32: sizes must be positive, got M=%d N=%d K=%d", M, N, K);
-    VK_REQUIRE((transA == 0 || transA == 1) && (transB == 0 || transB == 1), VK_EINVAL, "gemm_f32: transA=%d transB=%d must be 0 or 1", transA,
-               transB);
-    VK_REQUIRE(lda >= (transA ? M : K), VK_EINVAL, "gemm_f32: lda=%ld is below A's row width %d", lda, transA ? M : K);
-    VK_REQUIRE(ldb >= (transB ? K : N), VK_EINVAL, "gemm_f32: ldb=%ld is below B's row width %d", ldb, transB ? K : N);
-    VK_REQUIRE(ldc >= N, VK_EINVAL, "gemm_f32: ldc=%ld is below C's row width %d", ldc, N);
-    return VK_OK;
-}
-
 static bool train_act(int act) { return act == VK_ACT_GELU || act == VK_ACT_TANH; }
 static int elementwise_blocks(long n) { return (int)((n + 1023) / 1024 < 4096 ? (n + 1023) / 1024 : 4096); }
 static int col_slices(int M) { return ceil_div(M, COLS_SLICE); }
@@ -450,19 +440,18 @@ using namespace vk;
 extern "C" {
 
 int vk_gemm_f32_check(int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB) {
-    return gemm_check(M, N, K, lda, ldb, ldc, transA, transB);
+    return gemm_shape_check("gemm_f32", M, N, K, lda, ldb, ldc, transA, transB);
 }
 
 int vk_gemm_f32(const float *A, long lda, int transA, const float *B, long ldb, int transB, const float *bias, float *C, long ldc, int M,
                 int N, int K, int accumulate, void *stream) {
     VK_REQUIRE(A && B && C, VK_EINVAL, "gemm_f32: null argument");
-    VK_TRY(gemm_check(M, N, K, lda, ldb, ldc, transA, transB));
+    VK_TRY(gemm_shape_check("gemm_f32", M, N, K, lda, ldb, ldc, transA, transB));
     VK_REQUIRE(accumulate == 0 || accumulate == 1, VK_EINVAL, "gemm_f32: accumulate=%d must be 0 or 1", accumulate);
     DeviceState *ds;
     VK_TRY(device_state(&ds));
     const GemmArgs g = {A, B, bias, C, M, N, K, lda, ldb, ldc, transA, transB, accumulate};
-    const long big = (long)ceil_div(M, 128) * ceil_div(N, 128);
-    const int T = big * 2 >= ds->n_cu ? 128 : 64;
+    const int T = large_tile(M, N, ds->n_cu) ? 128 : 64;
     VK_REQUIRE(ceil_div(M, T) <= 65535, VK_EINVAL, "gemm_f32: M=%d is beyond the grid", M);
     const dim3 grid(ceil_div(N, T), ceil_div(M, T));
     if (T == 128) {

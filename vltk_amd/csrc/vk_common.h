@@ -63,6 +63,20 @@ constexpr int VK_MAX_DEVICES = 64;      // slots of per-device launcher state (D
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// ---- what the launchers of vk_gemm_f32 (train.hip) and vk_gemm_16 (gemm16.hip) share ----
+// The shape and leading-dimension rules of C [M, N] = op(A) . op(B), refused in the entry's name (`who`: "gemm_f32", "gemm_16").
+static inline int gemm_shape_check(const char *who, int M, int N, int K, long lda, long ldb, long ldc, int transA, int transB) {
+    VK_REQUIRE(M >= 1 && N >= 1 && K >= 1, VK_EINVAL, "%s: sizes must be positive, got M=%d N=%d K=%d", who, M, N, K);
+    VK_REQUIRE((transA == 0 || transA == 1) && (transB == 0 || transB == 1), VK_EINVAL, "%s: transA=%d transB=%d must be 0 or 1", who, transA,
+               transB);
+    VK_REQUIRE(lda >= (transA ? M : K), VK_EINVAL, "%s: lda=%ld is below A's row width %d", who, lda, transA ? M : K);
+    VK_REQUIRE(ldb >= (transB ? K : N), VK_EINVAL, "%s: ldb=%ld is below B's row width %d", who, ldb, transB ? K : N);
+    VK_REQUIRE(ldc >= N, VK_EINVAL, "%s: ldc=%ld is below C's row width %d", who, ldc, N);
+    return VK_OK;
+}
+// The tile of both: 128 x 128 where such tiles fill half the CUs, 64 x 64 elsewhere.
+static inline bool large_tile(int M, int N, int n_cu) { return (long)ceil_div(M, 128) * ceil_div(N, 128) * 2 >= n_cu; }
+
 // ---- convolution as implicit GEMM (conv_mfma.hip) --------------------------
 constexpr int CONV_BM = 128;        // output pixels per workgroup tile
 constexpr int CONV_KTILE_BYTES = 128;  // bytes of K per row per K-tile (64 f16 / 32 f32)
