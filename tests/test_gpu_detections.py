@@ -96,6 +96,7 @@ def check_exact(d, got, refs, D):
 CASES = [   # N, R, C, keyword arguments of craft, max_detections
     (1, 1, 5, {}, 3), (3, 37, 5, dict(counts=[37, 0, 11]), 20), (1, 1024, 5, {}, 20), (2, 300, 1600, dict(counts=[123, 300]), 100),
     (2, 37, 5, dict(agnostic=True), 20), (2, 37, 5, dict(ties=True), 20), (1, 300, 5, dict(ties=True), 100),
+    (1, 2, 5, {}, 3), (2, 64, 5, {}, 20), (2, 65, 5, {}, 20),      # the rows of test_gpu_per_class.py's CASES at the shared code's edges
 ]
 
 

@@ -123,6 +123,7 @@ CASES = [   # N, R, C, keyword arguments of craft
     (2, 37, 5, dict(agnostic=True)), (1, 300, 1600, dict(agnostic=True)),
     (2, 37, 5, dict(ties=True)), (2, 300, 5, dict(ties=True)), (1, 300, 1600, dict(ties=True)),
     (3, 37, 5, dict(counts=[37, 0, 11])), (2, 300, 1600, dict(counts=[123, 300])),
+    (1, 2, 5, {}), (2, 64, 5, {}), (2, 65, 5, {}),      # the shared sort at n == T (one wavefront), the sweep's stride at 64 / 65 rows
 ]
 
 

@@ -11,7 +11,7 @@
 //
 // fp32 box math, no FMA contraction (-ffp-contract=off for this file), IEEE division.
 #include "vk_common.h"
-#include "conv_prims.h"
+#include "select_prims.h"
 
 namespace vk {
 
@@ -103,34 +103,15 @@ __global__ __launch_bounds__(128) void given_box_outputs_kernel(const float *__r
     const bool valid = b < cnt;
     const long k = (long)n * B + b;
     if (tid == 0) {
-        float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f, op = 0.f, ap = 0.f;
-        int64_t oc = 0, ac = 0;
+        OutRow o;
         if (valid) {
-            const float *pb = prop_boxes + k * 4;
-            b0 = pb[0];
-            b1 = pb[1];
-            b2 = pb[2];
-            b3 = pb[3];
-            if (scales_yx) {   // boxes[:,0::2] *= scale_yx[1]; boxes[:,1::2] *= scale_yx[0]  (:1280-1283, as roi_final_kernel)
-                const float sy = scales_yx[2 * n], sx = scales_yx[2 * n + 1];
-                b0 *= sx;
-                b2 *= sx;
-                b1 *= sy;
-                b3 *= sy;
-            }
-            op = obj_prob[k];
-            oc = obj_cls[k];
-            ap = attr_prob[k];
-            ac = attr_cls[k];
+            for (int c = 0; c < 4; ++c) o.box[c] = prop_boxes[k * 4 + c];
+            o.obj_prob = obj_prob[k];
+            o.obj_id = obj_cls[k];
+            o.attr_prob = attr_prob[k];
+            o.attr_id = attr_cls[k];
         }
-        out.boxes[k * 4 + 0] = b0;
-        out.boxes[k * 4 + 1] = b1;
-        out.boxes[k * 4 + 2] = b2;
-        out.boxes[k * 4 + 3] = b3;
-        out.obj_probs[k] = op;
-        out.obj_ids[k] = oc;
-        out.attr_probs[k] = ap;
-        out.attr_ids[k] = ac;
+        store_output_row(out, nullptr, k, valid, o, scales_yx, n);      // the scales multiply of the selection kernels
         if (b == 0) out.preds_per_image[n] = cnt;
     }
     const int F4 = F / 4;

@@ -18,15 +18,10 @@
 #include <cfloat>
 
 #include "vk_common.h"
-#include "conv_prims.h"
+#include "select_prims.h"
 
 namespace vk {
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 // (value, index) arg-max with "first index wins" on ties
 __device__ __forceinline__ void wave_argmax(float &v, int &i) {
 #pragma unroll
@@ -120,15 +115,19 @@ __global__ __launch_bounds__(256) void chosen_deltas_kernel(const T *__restrict_
         for (int j = 0; j < 4; ++j) out[(long)k * 4 + j] = acc[j] + bias[row0 + j];
     }
 }
-// One workgroup per image.  LDS: keys[Rp2] u64 | box[R][4] f32 | removed[R] i32 | kept[D] i32
-__global__ __launch_bounds__(256) void roi_final_kernel(RoiFinalArgs a, int Rp2) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem_raw);
-    float *sbox = reinterpret_cast<float *>(keys + Rp2);
-    int *removed = reinterpret_cast<int *>(sbox + (size_t)a.R * 4);
-    int *kept = removed + a.R;
 
-    const int n = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+constexpr int ROI_FINAL_THREADS = 256;
+
+// One workgroup per image.  LDS: SelectLds (select_prims.h) with kept[D] as its fourth piece.
+__global__ __launch_bounds__(ROI_FINAL_THREADS) void roi_final_kernel(RoiFinalArgs a, int Rp2) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const SelectLds lds(smem_raw, Rp2, a.R);
+    unsigned long long *keys = lds.keys;
+    float *sbox = lds.box;
+    int *removed = lds.removed, *kept = lds.extra;
+    constexpr int T = ROI_FINAL_THREADS;
+
+    const int n = blockIdx.x, tid = threadIdx.x;
     const int cnt = min(a.counts[n], a.R);
     const float img_h = (float)a.image_hw[2 * n], img_w = (float)a.image_hw[2 * n + 1];
     const long k0 = (long)n * a.R;
@@ -152,30 +151,16 @@ __global__ __launch_bounds__(256) void roi_final_kernel(RoiFinalArgs a, int Rp2)
             sbox[4 * r + 1] = b[1];
             sbox[4 * r + 2] = b[2];
             sbox[4 * r + 3] = b[3];
-            keys[r] = ((unsigned long long)desc_key32(a.obj_prob[k0 + r]) << 32) | (uint32_t)r;
+            keys[r] = score_key(a.obj_prob[k0 + r], (uint32_t)r);
         } else {
-            keys[r] = ~0ull;
+            keys[r] = KEY_BEHIND_ALL;
         }
     }
     if (bad) atomicOr(a.nonfinite, 1);
     __syncthreads();
 
     // 2. rank by probability, descending, ties -> lower RoI index (stable)
-    for (int k2 = 2; k2 <= Rp2; k2 <<= 1)
-        for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-            for (int i = tid; i < Rp2; i += T) {
-                int ixj = i ^ j2;
-                if (ixj > i) {
-                    unsigned long long x = keys[i], y = keys[ixj];
-                    bool up = (i & k2) == 0;
-                    if ((x > y) == up) {
-                        keys[i] = y;
-                        keys[ixj] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
+    lds_sort_keys<T>(keys, Rp2);
 
     // 3. greedy NMS per threshold until the kept count lands in [mind, maxd] (:1274-1278)
     int nk = 0;
@@ -189,21 +174,7 @@ __global__ __launch_bounds__(256) void roi_final_kernel(RoiFinalArgs a, int Rp2)
             if (tid == 0) kept[nk] = i;
             ++nk;
             if (nk == a.maxd) break;   // keep[:maxd]
-            const int ri = (int)(keys[i] & 0xFFFFFFFFull);
-            const float ix1 = sbox[4 * ri], iy1 = sbox[4 * ri + 1], ix2 = sbox[4 * ri + 2], iy2 = sbox[4 * ri + 3];
-            const float ia = (ix2 - ix1) * (iy2 - iy1);
-            for (int j = i + 1 + tid; j < cnt; j += T) {
-                if (removed[j]) continue;
-                const int rj = (int)(keys[j] & 0xFFFFFFFFull);
-                const float jx1 = sbox[4 * rj], jy1 = sbox[4 * rj + 1], jx2 = sbox[4 * rj + 2], jy2 = sbox[4 * rj + 3];
-                const float xx1 = fmaxf(ix1, jx1), yy1 = fmaxf(iy1, jy1);
-                const float xx2 = fminf(ix2, jx2), yy2 = fminf(iy2, jy2);
-                const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
-                const float inter = w * h;
-                const float ja = (jx2 - jx1) * (jy2 - jy1);
-                const float ovr = inter / (ia + ja - inter);
-                if ((double)ovr > thr) removed[j] = 1;
-            }
+            sweep_mark<T, true>(keys, sbox, removed, i, (int)key_low(keys[i]), cnt, thr);
         }
         __syncthreads();
         if (nk >= a.mind && nk <= a.maxd) break;
@@ -212,52 +183,23 @@ __global__ __launch_bounds__(256) void roi_final_kernel(RoiFinalArgs a, int Rp2)
     //  base stays 16-byte aligned)
 
     // 4. gather the outputs (rows >= nk are zero)
-    const float sy = a.scales_yx ? a.scales_yx[2 * n] : 1.f, sx = a.scales_yx ? a.scales_yx[2 * n + 1] : 1.f;
     const long o0 = (long)n * a.D;
     for (int d = tid; d < a.D; d += T) {
-        float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f, op = 0.f, ap = 0.f;
-        int64_t oc = 0, ac = 0, kid = 0;
+        OutRow o;
         if (d < nk) {
-            const int r = (int)(keys[kept[d]] & 0xFFFFFFFFull);
-            b0 = sbox[4 * r];
-            b1 = sbox[4 * r + 1];
-            b2 = sbox[4 * r + 2];
-            b3 = sbox[4 * r + 3];
-            if (a.scales_yx) {   // boxes[:,0::2] *= scale_yx[1]; boxes[:,1::2] *= scale_yx[0]  (:1280-1283)
-                b0 *= sx;
-                b2 *= sx;
-                b1 *= sy;
-                b3 *= sy;
-            }
-            op = a.obj_prob[k0 + r];
-            oc = a.obj_cls[k0 + r];
-            ap = a.attr_prob ? a.attr_prob[k0 + r] : 0.f;
-            ac = a.attr_cls ? a.attr_cls[k0 + r] : 0;
-            kid = r;
+            const int r = (int)key_low(keys[kept[d]]);
+            for (int c = 0; c < 4; ++c) o.box[c] = sbox[4 * r + c];
+            o.obj_prob = a.obj_prob[k0 + r];
+            o.obj_id = a.obj_cls[k0 + r];
+            o.attr_prob = a.attr_prob ? a.attr_prob[k0 + r] : 0.f;
+            o.attr_id = a.attr_cls ? a.attr_cls[k0 + r] : 0;
+            o.keep_id = r;
         }
-        a.out.boxes[(o0 + d) * 4 + 0] = b0;
-        a.out.boxes[(o0 + d) * 4 + 1] = b1;
-        a.out.boxes[(o0 + d) * 4 + 2] = b2;
-        a.out.boxes[(o0 + d) * 4 + 3] = b3;
-        a.out.obj_probs[o0 + d] = op;
-        a.out.obj_ids[o0 + d] = oc;
-        a.out.attr_probs[o0 + d] = ap;
-        a.out.attr_ids[o0 + d] = ac;
-        if (a.keep_ids) a.keep_ids[o0 + d] = kid;
+        store_output_row(a.out, a.keep_ids, o0 + d, d < nk, o, a.scales_yx, n);
     }
     if (tid == 0) a.out.preds_per_image[n] = nk;
-    const int F4 = a.F / 4;
-    for (int d = 0; d < a.D; ++d) {
-        floatx4 *dst = reinterpret_cast<floatx4 *>(a.out.roi_features + (o0 + d) * a.F);
-        if (d < nk) {
-            const int r = (int)(keys[kept[d]] & 0xFFFFFFFFull);
-            const floatx4 *src = reinterpret_cast<const floatx4 *>(a.features + (k0 + r) * a.F);
-            for (int i = tid; i < F4; i += T) dst[i] = src[i];
-        } else {
-            const floatx4 z = {0.f, 0.f, 0.f, 0.f};
-            for (int i = tid; i < F4; i += T) dst[i] = z;
-        }
-    }
+    copy_feature_rows<T>(a.features + k0 * a.F, a.out.roi_features + o0 * a.F, a.F, a.D, nk,
+                         [&](int d) { return (int)key_low(keys[kept[d]]); });
 }
 
 // rois[k] = (batch index, x1, y1, x2, y2)   (convert_boxes_to_pooler_format, frcnn.py:426-441)
@@ -276,12 +218,6 @@ int launch_make_rois(const float *boxes, int N, int R, float *rois, hipStream_t 
     hipLaunchKernelGGL(make_rois_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, boxes, R, total, rois);
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
-}
-
-static int next_pow2i(int v) {
-    int p = 2;
-    while (p < v) p <<= 1;
-    return p;
 }
 
 int launch_softmax_argmax(const float *logits, int ld, int K, int n_soft, int n_max, float *prob, int32_t *cls,
@@ -320,12 +256,10 @@ int launch_chosen_deltas(const void *x, int ldx, const void *w, const float *bia
 }
 
 int launch_roi_final(RoiFinalArgs &a, int N, hipStream_t s) {
-    VK_REQUIRE(a.R >= 1 && a.R <= 1024, VK_EINVAL, "roi_outputs: R=%d must be in 1..1024", a.R);
-    VK_REQUIRE(a.D >= 1 && a.D <= a.R, VK_EINVAL, "roi_outputs: max_detections=%d must be in 1..R", a.D);
+    VK_TRY(check_select_shape("roi_outputs", a.R, a.D, a.R, "R"));
     VK_REQUIRE(a.F % 4 == 0, VK_EINVAL, "roi_outputs: F must be a multiple of 4");
-    const int Rp2 = next_pow2i(a.R);
-    const size_t smem = (size_t)Rp2 * 8 + (size_t)a.R * 16 + (size_t)a.R * 4 + (size_t)a.D * 4;
-    hipLaunchKernelGGL(roi_final_kernel, dim3(N), dim3(256), smem, s, a, Rp2);
+    const int Rp2 = next_pow2(a.R);
+    hipLaunchKernelGGL(roi_final_kernel, dim3(N), dim3(ROI_FINAL_THREADS), SelectLds::bytes(Rp2, a.R, a.D), s, a, Rp2);
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
 }

@@ -10,8 +10,8 @@
 //   torchvision.ops.boxes.batched_nms / nms (third party; single level => plain nms)
 //
 // Arithmetic contract: all box math is fp32 with the reference's operation order and NO fused
-// multiply-add (this file is compiled with -ffp-contract=off); the IoU test is
-// (double)(inter / (a_i + a_j - inter)) > thr as in torchvision's CPU kernel; ranking is
+// multiply-add (this file is compiled with -ffp-contract=off); the IoU test is nms_suppresses
+// (select_prims.h), the arithmetic of torchvision's CPU kernel; ranking is
 // "score descending, ties -> lower flat index" (stable), the order this build defines where the
 // reference's un-stable torch.sort leaves it open.
 //
@@ -29,18 +29,12 @@
 #include <type_traits>
 
 #include "vk_common.h"
+#include "select_prims.h"
 
 namespace vk {
 
 constexpr int RPN_MAX_PRE = 8192;
 constexpr int RPN_THREADS = 1024;
-
-__device__ __forceinline__ uint32_t desc_key(float v) {
-    uint32_t u = __float_as_uint(v);
-    if (u == 0x80000000u) u = 0u;                       // -0.0 ranks equal to +0.0
-    uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ~asc;                                        // ascending key order == descending score
-}
 
 struct DecodeCfg {
     float wx, wy, ww, wh;
@@ -140,7 +134,7 @@ __device__ __forceinline__ void rpn_select_decode_body(
 
     auto key_at = [&](int i) -> uint32_t {
         int pix = i / A, a = i - pix * A;
-        return desc_key(lg[(long)pix * ld_logits + a]);
+        return desc_key32(lg[(long)pix * ld_logits + a]);
     };
 
     // ---- radix select: the K-th smallest key (== K-th best logit) ----
@@ -185,7 +179,7 @@ __device__ __forceinline__ void rpn_select_decode_body(
 #endif
 
     // ---- compaction in flat-index order ----
-    for (int i = tid; i < sortn; i += RPN_THREADS) skey[i] = ~0ull;
+    for (int i = tid; i < sortn; i += RPN_THREADS) skey[i] = KEY_BEHIND_ALL;
     if (tid == 0) {
         sh_base_lt = 0;
         sh_base_eq = 0;
@@ -216,7 +210,7 @@ __device__ __forceinline__ void rpn_select_decode_body(
         eq_before += (uint32_t)__popcll(beq & lower);
         if (lt || (eq && eq_before < need)) {
             uint32_t pos = lt_before + min(eq_before, need);
-            skey[pos] = ((unsigned long long)k << 32) | (uint32_t)i;
+            skey[pos] = pack_key(k, (uint32_t)i);
         }
         __syncthreads();
         if (tid == 0) {
@@ -235,22 +229,7 @@ __device__ __forceinline__ void rpn_select_decode_body(
     if (cfg.stop == 2) return;
 #endif
     // ---- bitonic sort (ascending composite key == score desc, index asc) ----
-    for (int k2 = 2; k2 <= sortn; k2 <<= 1) {
-        for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-            for (int i = tid; i < sortn; i += RPN_THREADS) {
-                int ixj = i ^ j2;
-                if (ixj > i) {
-                    unsigned long long a = skey[i], b = skey[ixj];
-                    bool up = (i & k2) == 0;
-                    if ((a > b) == up) {
-                        skey[i] = b;
-                        skey[ixj] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    lds_sort_keys<RPN_THREADS>(skey, sortn);
 
 #ifdef VK_ABLATION
     if (cfg.stop == 3) return;
@@ -265,7 +244,7 @@ __device__ __forceinline__ void rpn_select_decode_body(
     }
     bool bad = false;
     for (int e = tid; e < K; e += RPN_THREADS) {
-        const uint32_t idx = (uint32_t)(skey[e] & 0xFFFFFFFFull);
+        const uint32_t idx = key_low(skey[e]);
         const int pix = idx / A, a = idx - pix * A;
         const int y = pix / Wf, x = pix - y * Wf;
         const float sx = (float)((double)cfg.offset * cfg.stride + (double)x * cfg.stride);
@@ -371,19 +350,13 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const float *__restrict__ 
     if (i >= cnt) return;
     const float *s = bb + (long)i * 4;
     const float ix1 = s[0], iy1 = s[1], ix2 = s[2], iy2 = s[3];
-    const float ia = (ix2 - ix1) * (iy2 - iy1);
+    const float ia = box_area(ix1, iy1, ix2, iy2);
     unsigned long long bits = 0;
     const int jn = min(64, cnt - j0);
     for (int b = 0; b < jn; ++b) {
         const int jdx = j0 + b;
         if (jdx <= i) continue;
-        const float xx1 = fmaxf(ix1, cbx[b][0]), yy1 = fmaxf(iy1, cbx[b][1]);
-        const float xx2 = fminf(ix2, cbx[b][2]), yy2 = fminf(iy2, cbx[b][3]);
-        const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
-        const float inter = w * h;
-        const float ja = (cbx[b][2] - cbx[b][0]) * (cbx[b][3] - cbx[b][1]);
-        const float ovr = inter / (ia + ja - inter);
-        if ((double)ovr > thr) bits |= 1ull << b;
+        if (nms_suppresses(ix1, iy1, ix2, iy2, ia, cbx[b][0], cbx[b][1], cbx[b][2], cbx[b][3], thr)) bits |= 1ull << b;
     }
     mask[((long)n * cap + i) * nwords + cb] = bits;
 }
@@ -518,25 +491,11 @@ __global__ __launch_bounds__(RPN_THREADS) void sort_scores_kernel(const float *_
     unsigned long long *skey = reinterpret_cast<unsigned long long *>(smem_raw);
     const int tid = threadIdx.x;
     for (int i = tid; i < sortn; i += RPN_THREADS)
-        skey[i] = i < n ? (((unsigned long long)desc_key(scores[i]) << 32) | (uint32_t)i) : ~0ull;
+        skey[i] = i < n ? score_key(scores[i], (uint32_t)i) : KEY_BEHIND_ALL;
     __syncthreads();
-    for (int k2 = 2; k2 <= sortn; k2 <<= 1)
-        for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-            for (int i = tid; i < sortn; i += RPN_THREADS) {
-                int ixj = i ^ j2;
-                if (ixj > i) {
-                    unsigned long long a = skey[i], b = skey[ixj];
-                    bool up = (i & k2) == 0;
-                    if ((a > b) == up) {
-                        skey[i] = b;
-                        skey[ixj] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
+    lds_sort_keys<RPN_THREADS>(skey, sortn);
     for (int e = tid; e < n; e += RPN_THREADS) {
-        int i = (int)(skey[e] & 0xFFFFFFFFull);
+        int i = (int)key_low(skey[e]);
         order[e] = i;
         sorted_boxes[4 * e + 0] = boxes[4 * i + 0];
         sorted_boxes[4 * e + 1] = boxes[4 * i + 1];
@@ -585,12 +544,6 @@ static int band_tab(const vk_ignorey *ig, BandTab *bt, bool *on, bool *f64) {
     return VK_OK;
 }
 
-static int next_pow2(int v) {
-    int p = 2;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 // ---------------------------------------------------------------------------
 // Several levels (find_top_rpn_proposals frcnn.py:264-390 with a list of levels; N4): the per-level candidates (each
 // level's top-k, decoded / clipped / size-flagged by rpn_select_decode_kernel) are merged per image in the concat order
@@ -619,11 +572,11 @@ __global__ __launch_bounds__(RPN_THREADS) void rpn_merge_levels_kernel(LevelCand
     float mx = -INFINITY;
     int local = 0;
     for (int i = tid; i < sortn; i += RPN_THREADS) {
-        unsigned long long key = ~0ull;
+        unsigned long long key = KEY_BEHIND_ALL;
         if (i < lc.levels * pre) {
             const int l = i / pre, r = i - l * pre;
             if (r < lc.count[l][n] && lc.valid[l][(long)n * pre + r]) {
-                key = ((unsigned long long)desc_key(lc.logit[l][(long)n * pre + r]) << 32) | (uint32_t)i;
+                key = score_key(lc.logit[l][(long)n * pre + r], (uint32_t)i);
                 const float *b = lc.boxes[l] + ((long)n * pre + r) * 4;
                 mx = fmaxf(mx, fmaxf(fmaxf(b[0], b[1]), fmaxf(b[2], b[3])));
                 ++local;
@@ -632,31 +585,16 @@ __global__ __launch_bounds__(RPN_THREADS) void rpn_merge_levels_kernel(LevelCand
         skey[i] = key;
     }
     atomicAdd(&sh_cnt, local);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    mx = wave_max(mx);
     if ((tid & 63) == 0) red[tid >> 6] = mx;
     __syncthreads();
     mx = red[0];
     for (int w = 1; w < RPN_THREADS / 64; ++w) mx = fmaxf(mx, red[w]);
     const int cnt = sh_cnt;
-    for (int k2 = 2; k2 <= sortn; k2 <<= 1)
-        for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-            for (int i = tid; i < sortn; i += RPN_THREADS) {
-                int ixj = i ^ j2;
-                if (ixj > i) {
-                    unsigned long long a = skey[i], b = skey[ixj];
-                    bool up = (i & k2) == 0;
-                    if ((a > b) == up) {
-                        skey[i] = b;
-                        skey[ixj] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
+    lds_sort_keys<RPN_THREADS>(skey, sortn);
     const float step = mx + 1.0f;                       // offsets = idxs.to(boxes) * (max_coordinate + 1)
     for (int e = tid; e < cnt; e += RPN_THREADS) {
-        const uint32_t slot = (uint32_t)(skey[e] & 0xFFFFFFFFull);
+        const uint32_t slot = key_low(skey[e]);
         const int l = slot / pre, r = slot - l * pre;
         const float *b = lc.boxes[l] + ((long)n * pre + r) * 4;
         const float off = (float)l * step;

@@ -214,11 +214,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // out[row, :C] = (softmax(logits[row, :C]) - onehot(label)) * scale; zeros where the label is ignore_index; NaN where it is
 // neither that nor a class (nothing is read through it).

@@ -62,6 +62,12 @@ constexpr int VK_MAX_DEVICES = 64;      // slots of per-device launcher state (D
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// the extent of a bitonic sort over v keys: the power of two at or above v, at least 2
+__host__ __device__ static inline int next_pow2(int v) {
+    int p = 2;
+    while (p < v) p <<= 1;
+    return p;
+}
 
 // ---- what the launchers of vk_gemm_f32 (train.hip) and vk_gemm_16 (gemm16.hip) share ----
 // The shape and leading-dimension rules of C [M, N] = op(A) . op(B), refused in the entry's name (`who`: "gemm_f32", "gemm_16").
@@ -282,8 +288,8 @@ int launch_chosen_deltas(const void *x, int ldx, const void *w, const float *bia
 int launch_roi_final(RoiFinalArgs &a, int N, hipStream_t s);
 int launch_make_rois(const float *boxes, int N, int R, float *rois, hipStream_t s);
 
-// One element of any storage type as fp32, and back; the sum of a value over the 64 lanes of a wave, left in every lane.
-// Shared by attention.hip, row_norm.h, losses.hip, roi_out.hip and per_class.hip.
+// One element of any storage type as fp32, and back; the sum and the maximum of a value over the 64 lanes of a wave, left in
+// every lane.  Shared by attention.hip, row_norm.h, losses.hip, train.hip, roi_out.hip and per_class.hip.
 template <typename T>
 __device__ __forceinline__ float ldf(const T *p) { return (float)*p; }
 template <typename T>
@@ -293,14 +299,10 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-
-// Sort key of a score for an ascending sort that ranks scores descending (-0 ranks as +0); the low word of the 64-bit key
-// holds the row index, so ties go to the lower index.  Shared by roi_out.hip and per_class.hip.
-__device__ __forceinline__ uint32_t desc_key32(float v) {
-    uint32_t u = __float_as_uint(v);
-    if (u == 0x80000000u) u = 0u;
-    uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ~asc;
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
 }
 
 // Box2BoxTransform.apply_deltas (frcnn.py:548-584) for one box, reference op order.  The one copy of the RoI decode:
