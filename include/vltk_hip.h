@@ -178,12 +178,19 @@ int vk_destroy(vk_handle *h);
  *                              forward (the stage "pooled" is built when it is asked for).  Taken per chunk in the f16 mode,
  *                              with stride-1 Res5 and "head_streams" = 1, where both 1x1 GEMMs of block 0 run as
  *                              VK_ROUTE_GEMM4; every other chunk takes the plain path.
+ *   "head_dedupe_taps"         0 or 1 (default 1, VK_HEAD_DEDUPE_TAPS): with 1, a chunk on the "head_dedupe" path whose conv2 reads
+ *                              through the index goes on over its distinct nine-window NEIGHBOURHOODS (vk_roi_neighbourhoods):
+ *                              block 0's conv3 + shortcut GEMM and conv1 of block 1 run once per neighbourhood, conv2 and conv3
+ *                              of block 1 read those rows through the index.  Taken where Res5 has three blocks or more and
+ *                              block 1's layers run as VK_ROUTE_GEMM4 / the indexed VK_ROUTE_PANEL form / VK_ROUTE_WS at K = 512;
+ *                              every other chunk runs what "head_dedupe" alone runs.
  * The environment variables are read by vk_create.  vk_option_check validates a value without a handle and
  * vk_option_default gives the value a new handle starts with (the variable, where it holds a valid value); both are host only.
  * vk_get_option reads an option back, and two read-only counters for tests and tools: "working_sets" (arenas the handle
  * holds: 0, 1 or 2), "lane_forwards" (forwards that ran on a stream of the handle's own since vk_create) and
  * "dedupe_chunks" (Res5 chunks that took the "head_dedupe" path since vk_create), "indexed_chunks" (those of them whose conv2 read
- * conv1's distinct rows through the index, without the row gather: vk_panel_phase_indexed). */
+ * conv1's distinct rows through the index, without the row gather: vk_panel_phase_indexed), "tap_dedupe_chunks" (those of them
+ * that took the "head_dedupe_taps" path). */
 int vk_set_option(vk_handle *h, const char *key, int value);
 int vk_get_option(vk_handle *h, const char *key, int *value);
 int vk_option_check(const char *key, int value);
@@ -855,6 +862,21 @@ int vk_roi_pool_windows(const void *feat, int N, int H, int W, int C, const int3
                         void *out, vk_dtype dt, void *stream);
 /* dst[row] = src[idx[row]] for rows of row_bytes bytes (a multiple of 16) */
 int vk_gather_rows(const void *src, const int32_t *idx, long rows, int row_bytes, void *dst, void *stream);
+/* ... for row < min(*rows_dev, rows): the row count lives on the device and `rows` bounds it (idx entries beyond it are not read).
+ * rows_dev may be null (vk_gather_rows). */
+int vk_gather_rows_dev(const void *src, const int32_t *idx, long rows, const int32_t *rows_dev, int row_bytes, void *dst, void *stream);
+/* The distinct NINE-WINDOW NEIGHBOURHOODS of K RoIs of P x P bins, from the window ids idx [K*P*P] of vk_roi_windows.  The
+ * neighbourhood of bin (k, i, j) is the nine ids at (i + {-dil, 0, dil}, j + {-dil, 0, dil}) of RoI k, a position outside the
+ * P x P map counting as a value of its own: what a stride-1 3x3 convolution of dilation `dil` over rows that depend on the window
+ * alone reads at that bin.  nid [K*P*P] i32: the id of each row's neighbourhood; rep [K*P*P] i32, of which the first *v_dev
+ * entries are written: the smallest row with that id; idx_rep likewise: idx[rep[id]]; v_dev [1] i32: the number of ids.  Two
+ * rows share an id exactly when their nine window ids are equal (compared in full; the hash inside only orders the probes).
+ * Ids number the neighbourhoods in the order of their smallest rows, so rep is ascending and nothing depends on the order in
+ * which the device runs anything.  Nothing is read back to the host.  The workspace (vk_roi_neighbourhoods_workspace_bytes,
+ * 16-byte aligned; 0 = too many rows) holds two slots per row and one bit per row. */
+size_t vk_roi_neighbourhoods_workspace_bytes(long rows);
+int vk_roi_neighbourhoods(const int32_t *idx, int K, int P, int dil, int32_t *nid, int32_t *rep, int32_t *idx_rep, int32_t *v_dev,
+                          void *workspace, size_t workspace_bytes, void *stream);
 /* The VK_ROUTE_GEMM4 kernel on de-duplicated rows (f16): y[m] = relu?([x1[m] | x2[x2_idx[m]]] . W^T + bias) for m < M', where
  * M' = min(*m_dev, M) when m_dev is given (M then only bounds the launch) and M otherwise.  x2 / x2_idx may be null (one input,
  * x2 [M,cin2] read by m).  Weights and bias as for vk_conv1x1_dual.  VK_EINVAL where vk_conv_route would not give
@@ -869,6 +891,14 @@ int vk_conv1x1_rows(const void *x1, int cin1, const void *x2, int cin2, long M, 
  * x_rows * cin * 2 reaches 2^32.  Same bits as vk_gather_rows + vk_conv2d. */
 int vk_conv2d_rows(const void *x, long x_rows, const int32_t *x_idx, int N, int H, int W, int cin, const void *w_packed,
                    const float *bias_packed, const void *residual, void *y, int cout, int dil, int relu, void *stream);
+/* The VK_ROUTE_WS kernel with a de-duplicated residual (f16, 1x1, K = 512): y[m] = relu?(x[m] . W^T + bias + residual[res_idx[m]]),
+ * m < M, without the dense residual being written.  res_idx holds M entries, every one a row of `residual`: the index is a
+ * contract, the kernel does not check it.  res_idx may be null (residual [M, cout] read by m: the plain build, same entry).
+ * The kernel is launched whatever M is (the dispatcher sends it layers from 1024 rows on).  VK_EINVAL, before any launch, where
+ * the layer is not one of that kernel's K = 512 build with two waves per SIMD (cin 512, cout a multiple of 256 that divides
+ * 8192, VK_CONV_WS / VK_WS_WAVES not set against it).  Same bits as vk_gather_rows of the residual + the plain build. */
+int vk_conv1x1_res_rows(const void *x, int cin, long M, const void *w_packed, const float *bias_packed, const void *residual,
+                        const int32_t *res_idx, void *y, int cout, int relu, void *stream);
 
 /* mean over the P*P positions of each RoI  <- frcnn.py:1401: x [K,S,C] (dt) -> out [K,C] f32 */
 int vk_mean_pool(const void *x, int K, int S, int C, float *out, vk_dtype dt, void *stream);

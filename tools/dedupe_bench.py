@@ -3,13 +3,18 @@
 of the bench's own batch, and the path's worst case -- given boxes whose windows are ALL distinct, where it can save nothing
 and pays for the window table and the row gather.
 
-    python tools/dedupe_bench.py [--batch 32 --boxes 300 --steps 10 --warmup 2 --pairs 3 --out FILE]
+    python tools/dedupe_bench.py [--batch 32 --boxes 300 --steps 10 --warmup 2 --pairs 3 --option head_dedupe --out FILE]
 
 The model, weights and images are bench.py's (ResNet-101-C4 fp16, weights of seed 1234, synthetic_images(seed=0xF2C), R = 300).
 Ratio: one detection forward, bins / windows read from the stage "head_windows" (the device-side count).  Worst case: `boxes`
 boxes per image, built so that no two of an image's boxes * 196 bins pool the same window (distinct_boxes), forwards with
 head_dedupe 0 and 1 interleaved `pairs` times; a timed window is `steps` forwards issued back to back between two device
 synchronisations.  Writes one JSON file and prints it.
+
+--option head_dedupe_taps: the same two measurements for the neighbourhood path -- the bench batch's distinct
+nine-window neighbourhoods (stage "head_neighbourhoods") beside its windows, and the all-distinct boxes with head_dedupe_taps 0
+against 1 (head_dedupe stays 1): what the neighbourhood table, the gather of conv2's rows and the index loads cost where no two
+bins share a neighbourhood.
 """
 import argparse
 import json
@@ -87,8 +92,8 @@ def timed(m, x, hw, steps, **kw):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def windows(m):
-    return [int(v) for v in m.get_stage("head_windows").cpu().tolist()]
+def windows(m, stage="head_windows"):
+    return [int(v) for v in m.get_stage(stage).cpu().tolist()]
 
 
 def main():
@@ -100,8 +105,12 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--pairs", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dedupe_worst_case.json"))
+    ap.add_argument("--option", choices=("head_dedupe", "head_dedupe_taps"), default="head_dedupe")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    taps = a.option == "head_dedupe_taps"
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "tap_dedupe_worst_case.json" if taps else "dedupe_worst_case.json")
     import torch
     from vltk_amd import FRCNN, make_state_dict, synthetic_images, vg_c4_config
     if not torch.cuda.is_available():
@@ -118,24 +127,29 @@ def main():
     u = windows(m)
     bins = N * 300 * P * P
     res["bench_batch"] = {"bins": bins, "windows_per_chunk": u, "bins_per_window": round(bins / sum(u), 3)}
+    if taps:
+        v = windows(m, "head_neighbourhoods")
+        res["bench_batch"].update({"neighbourhoods_per_chunk": v, "neighbourhoods_per_bin": round(sum(v) / bins, 4)})
+    res["option"] = a.option
 
     res4 = m.get_stage("res4")
     boxes = distinct_boxes(a.boxes, res4.shape[1], res4.shape[2])
     props = torch.from_numpy(np.broadcast_to(boxes, (N,) + boxes.shape).copy()).cuda()
     runs = {0: [], 1: []}
     for dd in (0, 1):                   # warmed up as timed: overlapped forwards (the second working set is allocated here)
-        m.set_option("head_dedupe", dd)
+        m.set_option(a.option, dd)
         timed(m, x, hw, max(a.warmup, 2), proposals=props)
     u = windows(m)
+    extra = {"neighbourhoods_per_chunk": windows(m, "head_neighbourhoods")} if taps else {}
     for _ in range(a.pairs):
         for dd in (0, 1):
-            m.set_option("head_dedupe", dd)
+            m.set_option(a.option, dd)
             runs[dd].append(round(timed(m, x, hw, a.steps, proposals=props), 3))
     bins = N * a.boxes * P * P
     res["all_distinct_given_boxes"] = {
         "boxes_per_image": a.boxes, "bins": bins, "windows_per_chunk": u, "bins_per_window": round(bins / sum(u), 4),
-        "ms_per_batch_dedupe0": runs[0], "ms_per_batch_dedupe1": runs[1],
-        "median_cost_ms": round(float(np.median(runs[1]) - np.median(runs[0])), 3)}
+        "ms_per_batch_dedupe0": runs[0], "ms_per_batch_dedupe1": runs[1],      # (the option of --option at 0 and at 1)
+        "median_cost_ms": round(float(np.median(runs[1]) - np.median(runs[0])), 3), **extra}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)

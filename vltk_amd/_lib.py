@@ -212,6 +212,10 @@ SIGNATURES = {
     "vk_roi_windows": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _SZ, _P]),
     "vk_roi_pool_windows": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
     "vk_gather_rows": (_I, [_P, _P, C.c_long, _I, _P, _P]),
+    "vk_gather_rows_dev": (_I, [_P, _P, C.c_long, _P, _I, _P, _P]),
+    "vk_roi_neighbourhoods_workspace_bytes": (_SZ, [C.c_long]),
+    "vk_roi_neighbourhoods": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vk_conv1x1_res_rows": (_I, [_P, _I, C.c_long, _P, _P, _P, _P, _P, _I, _I, _P]),
     "vk_conv1x1_rows": (_I, [_P, _I, _P, _I, C.c_long, _P, _P, _P, _P, _P, _I, _I, _P]),
     "vk_conv2d_rows": (_I, [_P, C.c_long, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vk_mean_pool": (_I, [_P, _I, _I, _I, _P, _I, _P]),

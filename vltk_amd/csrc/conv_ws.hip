@@ -47,6 +47,7 @@ struct WsK {
     double *pool;            // POOL builds: per-image column sums [M / HW][Cout] (exact in fp64), y is not written
     int HW;                  // rows per image (>= 64: a 64-row tile touches at most two images)
     int H, W, Wo, HoWo, stride;   // STRIDED builds: input geometry of a strided 1x1 conv (x rows are input pixels, M counts output pixels)
+    const int *res_idx;      // RIDX builds: output row m adds row res_idx[m] of res ([*, Cout], not [M, Cout]); [M] entries
 };
 
 template <int N>
@@ -78,7 +79,24 @@ constexpr int WS_BM = 64;                    // rows per tile
 // one GEMM (`out += shortcut`, frcnn.py:970-977; the weights hold the concatenated rows); a DMA lane picks its source by chunk.
 // STRIDED: 1x1 conv with a stride (the stride-2 projection shortcuts and first conv1s of res3 / res4): the DMA lane turns its output
 // row into (image, ho, wo) and reads input pixel (ho * stride, wo * stride); everything behind the ring is unchanged.
-template <int KC, int NW, int DBG = 0, bool POOL = false, bool DUAL = false, bool STRIDED = false>
+// RIDX (KC = 16, two waves per SIMD, storing build): INDEXED RESIDUAL ROWS -- output row m adds res[res_idx[m]], so that a
+// residual held once per distinct row (Res5 block 0's output over the distinct neighbourhoods) is expanded here, by the residual DMA,
+// and never written densely.  A lane requests four residual rows per tile (row q * 16 + lane / 4, q = 0..3) and so needs four
+// indices per tile, four global_load_dword.  Their order in the vector-memory queue (loads return in order):
+//   prologue   the indices of the workgroup's first tile, in front of the vmcnt(0) that ends the weight loads
+//   tile it    1. the indices of tile it + 1 (of the last tile once more on the last one: no run-time case), by asm, so that hipcc
+//                 puts no wait of its own behind them;  2. the four residual pieces of tile it, addressed by the indices held since
+//                 tile it - 1;  3. the K loop: per stage one counted wait (the WS_D - 1 later stages stay in flight) and the
+//                 pieces of the stage WS_D ahead -- a counted wait for an entry holds as long as at least that many entries are
+//                 younger than it: the index loads and residual pieces of steps 1 and 2 are younger than the stages the first
+//                 waits of the tile are for, which only makes those waits stricter, and older than every later stage, which
+//                 changes nothing;  4. the wait in front of the epilogue (the tile's SPT stages' pieces may stay in flight, or
+//                 vmcnt(0) near the end): the residual pieces have landed, and the index loads of step 1 are OLDER than
+//                 they are, so they have landed too.  The registers are re-defined there (an empty asm), and only what follows
+//                 that statement reads them: nothing that uses an index can be scheduled above the wait.
+// The row is clamped to M - 1 BEFORE the index is read, so res_idx is never read out of range; the residual's byte offset is
+// formed in 64 bits, so the indexed tensor has no size limit of its own.
+template <int KC, int NW, int DBG = 0, bool POOL = false, bool DUAL = false, bool STRIDED = false, bool RIDX = false>
 __global__ __launch_bounds__(NW * 64, 1) void conv_ws_kernel(WsK p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!DUAL || KC == 4, "two sources: 64 + 64 channels");
@@ -96,6 +114,7 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_ws_kernel(WsK p) {
     constexpr int RPW = 32 / NW;             // residual DMA pieces per wave and tile
     constexpr int NU = NI * 2;               // epilogue units (32 channels x 16 pixels) per wave
     static_assert(!POOL || NW == 8, "the fused-mean epilogue is written for 32 channels per wave");
+    static_assert(!RIDX || (KC == 16 && NW == 8 && !POOL && !DUAL && !STRIDED && DBG == 0), "indexed residual rows: the K = 512 storing build");
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -126,7 +145,21 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_ws_kernel(WsK p) {
     char *res_lds = smem + RING + wave * (WS_BM * WCH * 2);       // this wave's 64 rows x WCH channels of residual
     float *bias_lds = reinterpret_cast<float *>(smem + RING + 4 * WS_BM * 128);
     if (tid < 256) bias_lds[tid] = p.bias[n0 + tid];
+    // RIDX: ri = the lane's four residual rows of the tile about to start, rn = those of the tile after it (see the template's comments)
+    unsigned ri[4] = {0u, 0u, 0u, 0u}, rn[4] = {0u, 0u, 0u, 0u};
+    auto load_ridx = [&](int it_, unsigned (&dst)[4]) {
+        const int mt = (first + it_ * ML) * WS_BM;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int *ip = p.res_idx + min(mt + q * 16 + (lane >> 2), p.M - 1);
+            asm volatile("global_load_dword %0, %1, off" : "=v"(dst[q]) : "v"(ip) : "memory");
+        }
+    };
+    if constexpr (RIDX) {
+        if (ntw > 0) load_ridx(0, ri);
+    }
     ws_vm_wait<0>();                         // from here on vmcnt counts DMA pieces, residual loads and stores
+    if constexpr (RIDX) asm volatile("" : "+v"(ri[0]), "+v"(ri[1]), "+v"(ri[2]), "+v"(ri[3]));
     __syncthreads();
 
     // ---- LDS-DMA: piece q of the wave = rows (wave * PPW + q) * 4 + (lane >> 4) of the stage, 16-byte slot lane & 15 of the
@@ -285,6 +318,7 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_ws_kernel(WsK p) {
         // lane & 7 of a row holding chunk slot ^ (row & 7); NW = 8: 4 pieces of 16 rows x 64 B, slot lane & 3 holding chunk
         // slot ^ rsw(row)
         const int m0 = (first + it * ML) * WS_BM;
+        if constexpr (RIDX) load_ridx(min(it + 1, ntw - 1), rn);
         if (p.res && !(DBG & 8)) {
 #pragma unroll
             for (int q = 0; q < RPW; ++q) {
@@ -294,8 +328,8 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_ws_kernel(WsK p) {
                     glds16(p.res + ((long)m * p.ldy + n0 + wave * 64) * 2 + (((lane & 7) ^ (row & 7)) << 4), res_lds + q * 1024);
                 } else {
                     const int row = q * 16 + (lane >> 2);
-                    const int m = min(m0 + row, p.M - 1);
-                    glds16(p.res + ((long)m * p.ldy + n0 + wave * 32) * 2 + (((lane & 3) ^ rsw(row)) << 4), res_lds + q * 1024);
+                    const long m = RIDX ? (long)ri[q] : (long)min(m0 + row, p.M - 1);
+                    glds16(p.res + (m * p.ldy + n0 + wave * 32) * 2 + (((lane & 3) ^ rsw(row)) << 4), res_lds + q * 1024);
                 }
             }
         }
@@ -367,6 +401,11 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_ws_kernel(WsK p) {
                 else
                     ws_vm_wait<0>();
             }
+            if constexpr (RIDX) {            // (p.res is set: the launcher checks) the next tile's indices are older than the pieces just waited for
+                asm volatile("" : "+v"(rn[0]), "+v"(rn[1]), "+v"(rn[2]), "+v"(rn[3]));
+#pragma unroll
+                for (int q = 0; q < 4; ++q) ri[q] = rn[q];
+            }
             if constexpr (DBG & 32) {
                 t_b = __builtin_amdgcn_s_memtime();
                 c_rw += t_b - t_a;
@@ -429,10 +468,21 @@ bool conv_ws_eligible(const ConvArgs &a) {
     return M >= 8 * 128 && M < (1L << 31) - 128;      // (a.Cin % 128 == 0: whole 128-channel ring stages)
 }
 
-template <int KC, int NW = 8, int DBG = 0, bool POOL = false, bool DUAL = false, bool STRIDED = false>
+template <int KC, int NW = 8, int DBG = 0, bool POOL = false, bool DUAL = false, bool STRIDED = false, bool RIDX = false>
 static int launch_ws(const WsK &k, hipStream_t stream) {
     constexpr int smem = 6 * WS_BM * 256 + 4 * WS_BM * 128 + 1024;
-    return launch_lds(conv_ws_kernel<KC, NW, DBG, POOL, DUAL, STRIDED>, dim3(256), dim3(NW * 64), smem, smem, stream, k);
+    return launch_lds(conv_ws_kernel<KC, NW, DBG, POOL, DUAL, STRIDED, RIDX>, dim3(256), dim3(NW * 64), smem, smem, stream, k);
+}
+
+// Whether launch_conv_ws takes the layer with ConvArgs::res_idx (the RIDX build: K = 512, stride 1, one input, a residual, no fused
+// mean, two waves per SIMD); a.res_idx itself is not looked at, and neither is the row count from which the dispatcher sends a
+// layer here (conv_ws_eligible: the kernel itself runs from one row on)
+bool conv_ws_res_indexed(const ConvArgs &a) {
+    if (ws_off() || a.pool_part || !a.res || a.x2 || a.stem || a.groups > 1 || a.dt != VK_F16 || a.out_dt != VK_F16 || a.relu > 1) return false;
+    if (a.kh != 1 || a.kw != 1 || a.pad != 0 || a.stride != 1 || a.Cin != 512) return false;
+    if (a.Cout % 256 != 0 || a.ldy != a.Cout || 32 % (a.Cout / 256) != 0 || env_int("VK_WS_WAVES", 8) != 8) return false;
+    const long M = (long)a.N * a.Ho * a.Wo;
+    return M >= 1 && M < (1L << 31) - 128;
 }
 
 int launch_conv_ws(const ConvArgs &a, hipStream_t stream) {
@@ -458,6 +508,9 @@ int launch_conv_ws(const ConvArgs &a, hipStream_t stream) {
     k.Wo = a.Wo;
     k.HoWo = a.Ho * a.Wo;
     k.stride = a.stride;
+    k.res_idx = a.res_idx;
+    VK_REQUIRE(!a.res_idx || conv_ws_res_indexed(a), VK_EINVAL,
+               "conv_ws: res_idx needs K = 512, stride 1, one input, a residual, no fused mean and VK_WS_WAVES = 8 (conv_ws_res_indexed)");
 
     Timed t;
     VK_TRY(t.begin(stream));
@@ -488,7 +541,9 @@ int launch_conv_ws(const ConvArgs &a, hipStream_t stream) {
         const int dbg = 0;
 #define VKW_DBG_CASE(NW_, D_)
 #endif
-        if (a.stride != 1)
+        if (a.res_idx)
+            st = launch_ws<16, 8, 0, false, false, false, true>(k, stream);
+        else if (a.stride != 1)
             st = a.Cin == 256 ? launch_ws<8, 8, 0, false, false, true>(k, stream) : launch_ws<16, 8, 0, false, false, true>(k, stream);
         else if (a.x2)
             st = launch_ws<4, 8, 0, false, true>(k, stream);

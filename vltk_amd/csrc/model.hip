@@ -112,10 +112,12 @@ struct vk_handle {
     int head_streams = 0;                           // 2: each Res5 chunk as two half-chunks on two streams
     int head_split_min_rois = 0;                    // ... for chunks of at least this many RoIs
     int head_dedupe = 0;                            // 1: Res5 block 0 pools and convolves each distinct RoIPool window once
+    int head_dedupe_taps = 0;                       // 1: ... and its 1x1 GEMMs, with conv1 of block 1, run once per distinct nine-window neighbourhood
     // the box pooler (vk_set_pooler; not an option: it changes the results): VK_POOLER_*, and RoIAlign's samples per bin and axis
     int pooler_type = VK_POOLER_ROIPOOL, pooler_sampling_ratio = 0;
     int64_t dedupe_chunks = 0;                                            // head chunks that took that path (vk_get_option "dedupe_chunks")
     int64_t indexed_chunks = 0;                                           // those of them whose conv2 read conv1's rows through the index ("indexed_chunks")
+    int64_t tap_dedupe_chunks = 0;                                        // those of them that went on over the distinct neighbourhoods ("tap_dedupe_chunks")
     // "pooled" after a forward whose one chunk took the dedupe path: the dense tensor was never written; vk_get_stage expands
     // src[idx] into the plan's buffer the first time the stage is asked for
     struct {
@@ -178,6 +180,7 @@ static constexpr struct OptionRow {
     {"head_streams", &vk_handle::head_streams, 1, 1, 2, "head_streams must be 1 or 2", "VK_HEAD_STREAMS", ENV_FIRST_DIGIT},
     {"forward_lanes", &vk_handle::forward_lanes, 2, 1, 2, "forward_lanes must be 1 or 2", "VK_FORWARD_LANES", ENV_ONE_DIGIT},
     {"head_dedupe", &vk_handle::head_dedupe, 1, 0, 1, "head_dedupe must be 0 or 1", "VK_HEAD_DEDUPE", ENV_ONE_DIGIT},
+    {"head_dedupe_taps", &vk_handle::head_dedupe_taps, 1, 0, 1, "head_dedupe_taps must be 0 or 1", nullptr, ENV_ONE_DIGIT},   // (variable: vk_option_default)
     {"head_split_min_rois", &vk_handle::head_split_min_rois, 512, 2, INT_MAX, "head_split_min_rois must be >= 2", nullptr, ENV_NONE},
     {"backbone_split_min_batch", &vk_handle::backbone_split_min_batch, 8, 2, INT_MAX, "backbone_split_min_batch must be >= 2", nullptr, ENV_NONE},
 };
@@ -371,6 +374,11 @@ struct Plan {
     int32_t *dd_idx, *dd_win, *dd_u;
     void *dd_ws;
     size_t dd_ws_bytes;
+    // ... over the distinct nine-window neighbourhoods (head_dedupe_taps), or null: nid [chunk rows], rep and idx_rep
+    // [chunk rows] (a chunk without one repeated neighbourhood fits), one neighbourhood count per chunk, the table's workspace
+    int32_t *nb_nid, *nb_rep, *nb_idx_rep, *nb_v;
+    void *nb_ws;
+    size_t nb_ws_bytes;
     size_t head_rows;        // pixels that h_t1 .. h_sc hold each (a Res5 chunk, or the whole res4 map of a grid forward)
     float *pool_part;        // per-tile column sums of the last Res5 conv3 (fused spatial mean), or nullptr
     float *feat;
@@ -456,6 +464,15 @@ static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D, int 
             p.dd_idx = (int32_t *)cv.take(roi_rows * sizeof(int32_t));
             p.dd_win = (int32_t *)cv.take(roi_rows * 5 * sizeof(int32_t));
             p.dd_u = (int32_t *)cv.take((size_t)ceil_div(p.K, p.chunk) * sizeof(int32_t));
+            const size_t nws = h->res5.size() >= 3 ? vk_roi_neighbourhoods_workspace_bytes((long)roi_rows) : 0;
+            if (nws > 0) {
+                p.nb_ws_bytes = nws;
+                p.nb_ws = cv.take(nws);
+                p.nb_nid = (int32_t *)cv.take(roi_rows * sizeof(int32_t));
+                p.nb_rep = (int32_t *)cv.take(roi_rows * sizeof(int32_t));
+                p.nb_idx_rep = (int32_t *)cv.take(roi_rows * sizeof(int32_t));
+                p.nb_v = (int32_t *)cv.take((size_t)ceil_div(p.K, p.chunk) * sizeof(int32_t));
+            }
         }
     }
     p.pool_part = nullptr;
@@ -785,6 +802,8 @@ int vk_option_default(const char *key, int *value) {
     if (!o) return VK_EINVAL;
     *value = o->def;
     const char *env = o->env ? env_text(o->env) : nullptr;
+    // (the one option whose variable is named here and not in its row)
+    if (o->member == &vk_handle::head_dedupe_taps) env = env_text("VK_HEAD_DEDUPE_TAPS");
     if (!env) return VK_OK;
     if (o->rule == ENV_ATOI_POSITIVE) {
         if (atoi(env) > 0) *value = atoi(env);
@@ -804,6 +823,7 @@ int vk_get_option(vk_handle *h, const char *key, int *value) {
     // read-only
     if (!strcmp(key, "dedupe_chunks")) *value = (int)std::min<int64_t>(h->dedupe_chunks, INT32_MAX);      // head chunks that took the dedupe path
     else if (!strcmp(key, "indexed_chunks")) *value = (int)std::min<int64_t>(h->indexed_chunks, INT32_MAX);   // ... and ran conv2 without the row gather
+    else if (!strcmp(key, "tap_dedupe_chunks")) *value = (int)std::min<int64_t>(h->tap_dedupe_chunks, INT32_MAX);   // ... and went on over the distinct neighbourhoods
     else if (!strcmp(key, "working_sets")) *value = (h->sets[0].arena ? 1 : 0) + (h->sets[1].arena ? 1 : 0);   // arenas held
     else if (!strcmp(key, "lane_forwards")) *value = (int)std::min<int64_t>(h->lane_forwards, INT32_MAX);    // forwards enqueued on a lane's stream
     else VK_REQUIRE(false, VK_EINVAL, "unknown option '%s'", key);
@@ -1142,7 +1162,29 @@ static int fwd_predictor(vk_handle *h, const Plan &p, hipStream_t s);
 // Where the whole conv2 launch takes the panel kernel's indexed form (kc a multiple of 16, no panel switch off) there
 // is no gather: conv2 reads t1_u[idx[m]] itself.  conv2 writes h_t2, so t1_u then lives in h_t1, which the gather no longer fills;
 // h_t1 and h_t2 have the same size (make_plan: a chunk's dense rows), so a chunk without one repeated window (U == rows) still fits.
-static int head_block0_dedupe(vk_handle *h, const Plan &p, const void *res4, int k0, int kc, hipStream_t s) {
+//
+// head_dedupe_taps: block 0's output row, its shortcut operand and conv1 of block 1 depend on the bin's nine-window
+// neighbourhood alone, so from conv2 on the 1x1 GEMMs run over the chunk's V distinct neighbourhoods (vk_roi_neighbourhoods; V stays
+// on the device): t2's representative rows are gathered into t2_v (h_t1, where conv1's distinct rows are dead by then), the fused
+// conv3 + shortcut GEMM writes Y0_v [V, 2048] into h_a, conv1 of block 1 writes t1_v [V, 512] into h_t2, conv2 of block 1 reads
+// t1_v through nid (the panel kernel's indexed form) and conv3 of block 1 takes its residual from Y0_v through nid (conv_ws's
+// indexed-residual build) and writes the dense Y1 into h_b.  Each row goes through the same kernels with the same K order as on
+// the path above: same bits.  *block1_done tells fwd_head that block 1 has run.  Taken where conv2 of block 0 took the indexed
+// form, Res5 has a block behind block 1 (whose conv3 then stores: the last block's feeds the fused mean) and block 1's three
+// layers run as conv_gemm4 (decided at the chunk's dense row count) / the indexed panel form / conv_ws's indexed-residual build.
+static bool head_taps_ok(const vk_handle *h, const Plan &p, int kc) {
+    if (!h->head_dedupe_taps || !p.nb_nid || h->res5.size() < 3) return false;
+    const Block &b1 = h->res5[1];
+    const int P = p.P;
+    if (b1.has_shortcut || b1.conv1.stride != 1 || b1.conv2.stride != 1 || b1.conv1.cin != h->res5[0].conv3.cout) return false;
+    const ConvArgs a1 = layer_args(h, b1.conv1, p.h_a, 1, 1, kc * P * P, p.h_t2, {.relu = true});
+    const ConvArgs a2 = layer_args(h, b1.conv2, p.h_t2, kc, P, P, p.h_t1, {.relu = true});
+    const ConvArgs a3 = layer_args(h, b1.conv3, p.h_t1, 1, 1, kc * P * P, p.h_b, {.res = p.h_a, .relu = true});
+    return conv_route(a1) == VK_ROUTE_GEMM4 && conv_route(a2) == VK_ROUTE_PANEL && conv3x3_panel_phase_indexed(a2) == 1 &&
+           conv_route(a3) == VK_ROUTE_WS && conv_ws_res_indexed(a3);
+}
+
+static int head_block0_dedupe(vk_handle *h, const Plan &p, const void *res4, int k0, int kc, hipStream_t s, bool *block1_done) {
     const Block &b = h->res5[0];
     const int P = p.P;
     const long rows = (long)kc * P * P;
@@ -1163,9 +1205,33 @@ static int head_block0_dedupe(vk_handle *h, const Plan &p, const void *res4, int
     } else
         VK_TRY(vk_gather_rows(t1_u, p.dd_idx, rows, (int)(b.conv1.cout * es), p.h_t1, s));
     VK_TRY(launch_conv(a2, s));
-    ConvArgs a3 = layer_args(h, b.conv3, p.h_t2, 1, 1, (int)rows, p.h_a, {.x2 = pooled_u, .cin2 = b.shortcut.cin, .relu = true});
-    a3.x2_idx = p.dd_idx;
-    VK_TRY(launch_conv_gemm4(a3, s));
+    *block1_done = indexed && head_taps_ok(h, p, kc);
+    if (*block1_done) {
+        const Block &b1 = h->res5[1];
+        int32_t *v = p.nb_v + k0 / p.chunk;
+        void *t2_v = p.h_t1, *y0_v = p.h_a, *t1_v = p.h_t2;
+        VK_TRY(vk_roi_neighbourhoods(p.dd_idx, kc, P, b.conv2.dil, p.nb_nid, p.nb_rep, p.nb_idx_rep, v, p.nb_ws, p.nb_ws_bytes, s));
+        VK_TRY(vk_gather_rows_dev(p.h_t2, p.nb_rep, rows, v, (int)(b.conv2.cout * es), t2_v, s));
+        ConvArgs a3 = layer_args(h, b.conv3, t2_v, 1, 1, (int)rows, y0_v, {.x2 = pooled_u, .cin2 = b.shortcut.cin, .relu = true});
+        a3.x2_idx = p.nb_idx_rep;
+        a3.m_dev = v;
+        VK_TRY(launch_conv_gemm4(a3, s));
+        ConvArgs c1 = layer_args(h, b1.conv1, y0_v, 1, 1, (int)rows, t1_v, {.relu = true});
+        c1.m_dev = v;
+        VK_TRY(launch_conv_gemm4(c1, s));
+        ConvArgs c2 = layer_args(h, b1.conv2, t1_v, kc, P, P, p.h_t1, {.relu = true});
+        c2.x_idx = p.nb_nid;
+        c2.x_rows = rows;                  // (V <= rows is on the device; every id is below V)
+        VK_TRY(launch_conv(c2, s));
+        ConvArgs c3 = layer_args(h, b1.conv3, p.h_t1, 1, 1, (int)rows, p.h_b, {.res = y0_v, .relu = true});
+        c3.res_idx = p.nb_nid;
+        VK_TRY(launch_conv(c3, s));
+        h->tap_dedupe_chunks++;
+    } else {
+        ConvArgs a3 = layer_args(h, b.conv3, p.h_t2, 1, 1, (int)rows, p.h_a, {.x2 = pooled_u, .cin2 = b.shortcut.cin, .relu = true});
+        a3.x2_idx = p.dd_idx;
+        VK_TRY(launch_conv_gemm4(a3, s));
+    }
     h->dedupe_chunks++;
     if (p.chunk >= p.K) {
         h->pooled_expand.pending = true;
@@ -1192,7 +1258,7 @@ static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s
     const int P = p.P;
     vk_handle::Lane &ln = h->lanes[h->cur_set];
     const size_t es5 = dtype_size(h->dt);
-    int dd_chunks = 0;
+    int dd_chunks = 0, tap_chunks = 0;
     for (int k0 = 0; k0 < p.K; k0 += p.chunk) {
         const int kc = std::min(p.chunk, p.K - k0);
         // option head_streams = 2: the chunk's two halves run on two streams (RoIs are independent; the halves use disjoint
@@ -1220,9 +1286,11 @@ static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s
         for (int half = 0; half < (split ? 2 : 1); ++half) {
             const int n0 = half ? ka : 0, nb = half ? kc - ka : ka;
             hipStream_t hs = half ? h->side : s;
+            bool block1_done = false;
             if (dd) {
-                VK_TRY(head_block0_dedupe(h, p, res4, k0, kc, hs));
+                VK_TRY(head_block0_dedupe(h, p, res4, k0, kc, hs, &block1_done));
                 dd_chunks++;
+                tap_chunks += block1_done ? 1 : 0;
             } else
                 VK_TRY(head_pool(h, p, res4, p.rois + 5 * (size_t)(k0 + n0), nb, (char *)p.pooled + (size_t)n0 * P * P * h->res4_c * es5, hs));
             // the fused mean's per-tile partials: the second half gets its own region (tiles are counted per launch)
@@ -1235,7 +1303,11 @@ static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s
                 x = a;
                 std::swap(a, b2);
             }
-            for (size_t bi = dd ? 1 : 0; bi < h->res5.size(); ++bi) {
+            if (block1_done) {     // ... and block 1 h_b
+                x = a;
+                std::swap(a, b2);
+            }
+            for (size_t bi = dd ? (block1_done ? 2 : 1) : 0; bi < h->res5.size(); ++bi) {
                 int ho, wo;
                 const bool last = bi + 1 == h->res5.size();
                 VK_TRY(run_block(h, h->res5[bi], x, kc, hh, ww, p.h_t1, p.h_t2, p.h_sc, a, hs, &ho, &wo, last ? pp : nullptr,
@@ -1258,6 +1330,8 @@ static int fwd_head(vk_handle *h, const Plan &p, const void *res4, hipStream_t s
     if (p.chunk >= p.K) set_stage(h, "pooled", p.pooled, h->dt, {p.K, P, P, h->res4_c});
     if (dd_chunks > 0 && dd_chunks == ceil_div(p.K, p.chunk))      // (every chunk took the dedupe path: each count has been written)
         set_stage(h, "head_windows", p.dd_u, VK_I32, {dd_chunks});    // distinct RoIPool windows per chunk
+    if (tap_chunks > 0 && tap_chunks == ceil_div(p.K, p.chunk))
+        set_stage(h, "head_neighbourhoods", p.nb_v, VK_I32, {tap_chunks});    // distinct nine-window neighbourhoods per chunk
     return fwd_predictor(h, p, s);
 }
 

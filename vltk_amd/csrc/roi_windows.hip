@@ -7,6 +7,8 @@
 //   vk_roi_windows        idx[row] = id of the row's window, win[id] = (image, y0, y1, x0, x1), *u_dev = number of ids
 //   vk_roi_pool_windows   pooled_u[id] = the row roi_pool_kernel writes for every bin with that window (bit-equal)
 //   vk_gather_rows        dst[row] = src[idx[row]] in 16-byte lanes (conv1's rows back to the dense tensor; "pooled" on demand)
+//   vk_roi_neighbourhoods nid[row] = id of the row's NINE-window neighbourhood (its own window and the eight a dilated 3x3 reads),
+//                         rep[id] = the smallest row with it, idx_rep[id] = idx[rep[id]], *v_dev = number of ids
 // Ids are the RANK of the window's key (image, y0, y1, x0, x1) among the keys present, so they do not depend on the order in which
 // the device happens to run anything: one bit per possible key, a marking pass, popcount sums over 8-word blocks, a two-level
 // exclusive scan of the block sums, and id = scanned sum + popcount of the bits below the key's own.  No host read-back, no
@@ -105,6 +107,15 @@ __global__ __launch_bounds__(256) void rw_top_scan_kernel(unsigned *__restrict__
     if (threadIdx.x == 0) *u_dev = (int32_t)carry;
 }
 
+// the rank of set bit `key`: set bits below it (scanned block sums + popcounts inside its block)
+__device__ __forceinline__ unsigned rw_rank(const unsigned *__restrict__ bits, const unsigned *__restrict__ bsum, const unsigned *__restrict__ gsum,
+                                            unsigned long long key) {
+    const unsigned long long word = key >> 5, blk = word / RW_BLK;
+    unsigned id = gsum[blk / RW_GRP] + bsum[blk];
+    for (unsigned long long w = blk * RW_BLK; w < word; ++w) id += __popc(bits[w]);
+    return id + __popc(bits[word] & ((1u << (unsigned)(key & 31)) - 1u));
+}
+
 // every bin of one window writes the same five values to win[id]
 __global__ void rw_assign_kernel(const float *__restrict__ rois, long rows, int N, int H, int W, int P, float scale,
                                  const unsigned *__restrict__ bits, const unsigned *__restrict__ bsum, const unsigned *__restrict__ gsum,
@@ -115,10 +126,7 @@ __global__ void rw_assign_kernel(const float *__restrict__ rois, long rows, int 
     int b, y0, y1, x0, x1;
     roi_bin_window(rois + 5 * (row / ((long)P * P)), ph, pw, N, H, W, P, scale, b, y0, y1, x0, x1);
     const unsigned long long key = window_key(b, y0, y1, x0, x1, H, W);
-    const unsigned long long word = key >> 5, blk = word / RW_BLK;
-    unsigned id = gsum[blk / RW_GRP] + bsum[blk];
-    for (unsigned long long w = blk * RW_BLK; w < word; ++w) id += __popc(bits[w]);
-    id += __popc(bits[word] & ((1u << (unsigned)(key & 31)) - 1u));
+    const unsigned id = rw_rank(bits, bsum, gsum, key);
     idx[row] = (int32_t)id;
     int32_t *o = win + 5 * (long)id;
     o[0] = b;
@@ -156,8 +164,10 @@ __global__ __launch_bounds__(256) void roi_pool_windows_kernel(const _Float16 *_
 }
 
 // dst[row] = src[idx[row]], rows of `chunks` 16-byte lanes
+// (rows_dev: the row count lives on the device, `rows` bounds it)
 __global__ __launch_bounds__(256) void gather_rows_kernel(const uint4 *__restrict__ src, const int32_t *__restrict__ idx, long rows,
-                                                          int chunks, uint4 *__restrict__ dst) {
+                                                          const int32_t *__restrict__ rows_dev, int chunks, uint4 *__restrict__ dst) {
+    if (rows_dev) rows = min((long)*rows_dev, rows);
     const long total = rows * chunks;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long row = i / chunks;
@@ -166,23 +176,127 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const uint4 *__restric
     }
 }
 
+// ---- distinct nine-window neighbourhoods ----
+// Res5 block 0 is stride 1 with a 3x3 of dilation d, so its output row at bin (k, i, j) -- and with it block 0's shortcut operand and
+// conv1 of block 1 -- is a function of the nine windows at (i + {-d, 0, d}, j + {-d, 0, d}), "outside the P x P map" being a value of
+// its own.  Window ids are ranks of the full (image, y0, y1, x0, x1) key, so nine equal ids (-1 = outside) ARE nine equal keys.
+// Two rows are merged only after all nine ids compared equal: the hash below picks where a probe starts and nothing else.
+//   insert   open addressing over row numbers: a slot is claimed by the first row that finds it empty; a row whose nine ids equal those
+//            of the slot's row lowers the slot to min(row) (the ids a slot stands for never change once it is claimed), any other row
+//            moves on to the next slot.  After the kernel a slot holds the SMALLEST row of its neighbourhood, whatever ran first.
+//   find     every row probes to its slot again and notes that smallest row (in nid[], for the moment); the smallest rows mark their
+//            bit in a bitmap over the rows
+//   rank     the window table's block sums and two-level scan over that bitmap; *v_dev = set bits
+//   assign   nid[row] = rank of the row's smallest row; the smallest rows write rep[] and idx_rep[]
+// So ids number the neighbourhoods in the order of their smallest rows: a function of the chunk's boxes alone, rep[] ascending.
+constexpr int NB_OUT = -1;
+
+__device__ __forceinline__ void nbr_ids(const int32_t *__restrict__ idx, long row, int P, int d, int (&k)[9]) {
+    const int pw = (int)(row % P), ph = (int)((row / P) % P);
+    const int32_t *roi = idx + (row - (long)ph * P - pw);
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            const int i = ph + (a - 1) * d, j = pw + (b - 1) * d;
+            k[a * 3 + b] = (i >= 0 && i < P && j >= 0 && j < P) ? roi[i * P + j] : NB_OUT;
+        }
+}
+
+__device__ __forceinline__ bool nbr_same(const int32_t *__restrict__ idx, long other, int P, int d, const int (&k)[9]) {
+    int o[9];
+    nbr_ids(idx, other, P, d, o);
+    bool same = true;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) same = same && o[t] == k[t];
+    return same;
+}
+
+__device__ __forceinline__ unsigned nbr_hash(const int (&k)[9]) {
+    unsigned h = 2166136261u;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) h = (h ^ (unsigned)k[t]) * 16777619u;
+    return h ^ (h >> 15);
+}
+
+__global__ void nb_insert_kernel(const int32_t *__restrict__ idx, long rows, int P, int d, int *__restrict__ table, unsigned mask) {
+    const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    int k[9];
+    nbr_ids(idx, row, P, d, k);
+    for (unsigned slot = nbr_hash(k) & mask;; slot = (slot + 1) & mask) {       // (the table has at least two slots per row: a probe ends)
+        const int cur = atomicCAS(table + slot, -1, (int)row);
+        if (cur < 0) return;                                                     // claimed
+        if (nbr_same(idx, cur, P, d, k)) {
+            atomicMin(table + slot, (int)row);
+            return;
+        }
+    }
+}
+
+__global__ void nb_find_kernel(const int32_t *__restrict__ idx, long rows, int P, int d, const int *__restrict__ table, unsigned mask,
+                               int32_t *__restrict__ first, unsigned *__restrict__ bits) {
+    const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    int k[9];
+    nbr_ids(idx, row, P, d, k);
+    for (unsigned slot = nbr_hash(k) & mask;; slot = (slot + 1) & mask) {
+        int cur = table[slot];                                                   // (never empty before the row's own slot: it was inserted)
+        if (cur < 0) cur = (int)row;
+        if (cur == (int)row || nbr_same(idx, cur, P, d, k)) {
+            first[row] = cur;
+            if (cur == (int)row) atomicOr(bits + (row >> 5), 1u << (unsigned)(row & 31));
+            return;
+        }
+    }
+}
+
+__global__ void nb_assign_kernel(const int32_t *__restrict__ idx, long rows, const unsigned *__restrict__ bits, const unsigned *__restrict__ bsum,
+                                 const unsigned *__restrict__ gsum, int32_t *__restrict__ nid, int32_t *__restrict__ rep,
+                                 int32_t *__restrict__ idx_rep) {
+    const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    const int32_t f = nid[row];                                                  // the smallest row of this row's neighbourhood (nb_find_kernel)
+    const unsigned id = rw_rank(bits, bsum, gsum, (unsigned long long)f);
+    nid[row] = (int32_t)id;
+    if (f == (int32_t)row) {
+        rep[id] = (int32_t)row;
+        idx_rep[id] = idx[row];
+    }
+}
+
 struct RwLayout {
     size_t n_words, n_blocks, n_blocks_padded, n_groups;
     size_t off_bsum, off_gsum, total;
 };
+
+// the bitmap over `nbits` keys with its block sums and group sums, from byte `base` of a workspace on
+static void rw_carve(size_t nbits, size_t base, RwLayout *L) {
+    L->n_blocks = (nbits + 32 * RW_BLK - 1) / (32 * RW_BLK);
+    L->n_words = L->n_blocks * RW_BLK;
+    L->n_groups = (L->n_blocks + RW_GRP - 1) / RW_GRP;
+    L->n_blocks_padded = L->n_groups * RW_GRP;
+    L->off_bsum = base + align_up(L->n_words * 4, 256);
+    L->off_gsum = L->off_bsum + align_up(L->n_blocks_padded * 4, 256);
+    L->total = L->off_gsum + align_up(L->n_groups * 4, 256);
+}
+
+// the neighbourhood table's workspace: the slots (a power of two, two per row at least), then a bitmap over the rows
+static bool nb_layout(long rows, size_t *slots, RwLayout *L) {
+    if (rows <= 0 || rows >= (1L << 30)) return false;
+    size_t t = 1024;
+    while (t < 2 * (size_t)rows) t <<= 1;
+    *slots = t;
+    rw_carve((size_t)rows, t * sizeof(int), L);
+    return true;
+}
 
 static bool rw_layout(int N, int H, int W, RwLayout *L) {
     if (N <= 0 || H <= 0 || W <= 0) return false;
     const double nbits_d = (double)N * (H + 1) * (H + 1) * (double)(W + 1) * (W + 1);
     if (nbits_d >= 34359738368.0) return false;                    // 2^35 bits = 4 GiB of bitmap: beyond any map this is meant for
     const size_t nbits = (size_t)N * (H + 1) * (H + 1) * (size_t)(W + 1) * (W + 1);
-    L->n_blocks = (nbits + 32 * RW_BLK - 1) / (32 * RW_BLK);
-    L->n_words = L->n_blocks * RW_BLK;
-    L->n_groups = (L->n_blocks + RW_GRP - 1) / RW_GRP;
-    L->n_blocks_padded = L->n_groups * RW_GRP;
-    L->off_bsum = align_up(L->n_words * 4, 256);
-    L->off_gsum = L->off_bsum + align_up(L->n_blocks_padded * 4, 256);
-    L->total = L->off_gsum + align_up(L->n_groups * 4, 256);
+    rw_carve(nbits, 0, L);
     return true;
 }
 
@@ -221,6 +335,39 @@ int vk_roi_windows(const float *rois, int K, int N, int H, int W, int P, float s
     return VK_OK;
 }
 
+size_t vk_roi_neighbourhoods_workspace_bytes(long rows) {
+    size_t slots;
+    RwLayout L;
+    return nb_layout(rows, &slots, &L) ? L.total : 0;
+}
+
+int vk_roi_neighbourhoods(const int32_t *idx, int K, int P, int dil, int32_t *nid, int32_t *rep, int32_t *idx_rep, int32_t *v_dev,
+                          void *workspace, size_t workspace_bytes, void *stream) {
+    VK_REQUIRE(idx && nid && rep && idx_rep && v_dev && workspace && K > 0 && P > 0 && dil >= 1, VK_EINVAL, "roi_neighbourhoods: bad arguments");
+    const long rows = (long)K * P * P;
+    size_t slots;
+    RwLayout L;
+    VK_REQUIRE(nb_layout(rows, &slots, &L), VK_EINVAL, "roi_neighbourhoods: %ld rows", rows);
+    VK_REQUIRE(workspace_bytes >= L.total, VK_EINVAL, "roi_neighbourhoods: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
+    VK_REQUIRE(((uintptr_t)workspace & 15) == 0, VK_EINVAL, "roi_neighbourhoods: workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    int *table = (int *)workspace;
+    unsigned *bits = (unsigned *)((char *)workspace + slots * sizeof(int));
+    unsigned *bsum = (unsigned *)((char *)workspace + L.off_bsum), *gsum = (unsigned *)((char *)workspace + L.off_gsum);
+    VK_CHECK_HIP(hipMemsetAsync(table, 0xff, slots * sizeof(int), s));          // every slot empty (-1)
+    VK_CHECK_HIP(hipMemsetAsync(bits, 0, L.n_words * 4, s));
+    const unsigned row_grid = (unsigned)((rows + 255) / 256);
+    hipLaunchKernelGGL(nb_insert_kernel, dim3(row_grid), dim3(256), 0, s, idx, rows, P, dil, table, (unsigned)(slots - 1));
+    hipLaunchKernelGGL(nb_find_kernel, dim3(row_grid), dim3(256), 0, s, idx, rows, P, dil, table, (unsigned)(slots - 1), nid, bits);
+    hipLaunchKernelGGL(rw_block_sums_kernel, dim3((unsigned)(L.n_blocks_padded / 256)), dim3(256), 0, s, bits, (long)L.n_blocks,
+                       (long)L.n_blocks_padded, bsum);
+    hipLaunchKernelGGL(rw_group_scan_kernel, dim3((unsigned)L.n_groups), dim3(256), 0, s, bsum, gsum);
+    hipLaunchKernelGGL(rw_top_scan_kernel, dim3(1), dim3(256), 0, s, gsum, (int)L.n_groups, v_dev);
+    hipLaunchKernelGGL(nb_assign_kernel, dim3(row_grid), dim3(256), 0, s, idx, rows, bits, bsum, gsum, nid, rep, idx_rep);
+    VK_CHECK_HIP(hipGetLastError());
+    return VK_OK;
+}
+
 int vk_roi_pool_windows(const void *feat, int N, int H, int W, int C, const int32_t *win, const int32_t *u_dev, int max_u, void *out,
                         vk_dtype dt, void *stream) {
     (void)N;
@@ -237,6 +384,10 @@ int vk_roi_pool_windows(const void *feat, int N, int H, int W, int C, const int3
 }
 
 int vk_gather_rows(const void *src, const int32_t *idx, long rows, int row_bytes, void *dst, void *stream) {
+    return vk_gather_rows_dev(src, idx, rows, nullptr, row_bytes, dst, stream);
+}
+
+int vk_gather_rows_dev(const void *src, const int32_t *idx, long rows, const int32_t *rows_dev, int row_bytes, void *dst, void *stream) {
     VK_REQUIRE(src && idx && dst && rows > 0, VK_EINVAL, "gather_rows: bad arguments");
     VK_REQUIRE(row_bytes > 0 && row_bytes % 16 == 0, VK_EINVAL, "gather_rows: rows of whole 16-byte lanes only (%d bytes)", row_bytes);
     DeviceState *ds = nullptr;
@@ -244,7 +395,7 @@ int vk_gather_rows(const void *src, const int32_t *idx, long rows, int row_bytes
     const int chunks = row_bytes / 16;
     const long need = (rows * chunks + 255) / 256, cap = (long)ds->n_cu * 16;
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(need < cap ? need : cap)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)src,
-                       idx, rows, chunks, (uint4 *)dst);
+                       idx, rows, rows_dev, chunks, (uint4 *)dst);
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
 }

@@ -286,6 +286,22 @@ int vk_conv1x1_rows(const void *x1, int cin1, const void *x2, int cin2, long M, 
     return launch_conv_gemm4(a, (hipStream_t)stream);
 }
 
+int vk_conv1x1_res_rows(const void *x, int cin, long M, const void *w_packed, const float *bias_packed, const void *residual,
+                        const int32_t *res_idx, void *y, int cout, int relu, void *stream) {
+    VK_REQUIRE(x && w_packed && bias_packed && residual && y && M > 0 && M < (1L << 31), VK_EINVAL, "conv1x1_res_rows: bad arguments");
+    ConvArgs a;
+    fill_conv_args(a, 1, 1, (int)M, cin, cout, cout, 1, 1, 0, 1, 1, relu, VK_F16, VK_F16);
+    a.x = x;
+    a.w = w_packed;
+    a.bias = bias_packed;
+    a.res = residual;
+    a.y = y;
+    VK_REQUIRE(conv_ws_res_indexed(a), VK_EINVAL,
+               "conv1x1_res_rows: not a layer of the VK_ROUTE_WS kernel's K = 512 build with two waves per SIMD (cin %d, cout %d)", cin, cout);
+    a.res_idx = res_idx;
+    return launch_conv_ws(a, (hipStream_t)stream);
+}
+
 int vk_linear(const void *x, long M, int K, const void *w_packed, const float *bias_packed, const void *residual, void *y, int N, int ldy,
               int act, vk_dtype dt, vk_dtype out_dt, void *stream) {
     VK_REQUIRE(x && w_packed && bias_packed && y && M > 0 && M < (1L << 31), VK_EINVAL, "linear: bad arguments");

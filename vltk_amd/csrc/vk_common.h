@@ -108,6 +108,7 @@ struct ConvArgs {
     const int32_t *x2_idx;  // conv_gemm4 only: output row m reads row x2_idx[m] of x2
     const int32_t *x_idx;   // conv3x3_panel only, where conv3x3_panel_phase_indexed: output row m reads row x_idx[m] of x [x_rows, Cin]
     long x_rows;            // with x_idx: the rows of x (every index lies in [0, x_rows))
+    const int32_t *res_idx; // conv_ws only, where conv_ws_res_indexed: output row m adds row res_idx[m] of res
     vk_dtype dt, out_dt;
 };
 int launch_conv(const ConvArgs &a, hipStream_t stream);
@@ -129,6 +130,7 @@ bool conv_duo_eligible(const ConvArgs &a);                // conv_mfma_duo.hip (
 int launch_conv_duo(const ConvArgs &a, hipStream_t stream);
 bool conv_ws_eligible(const ConvArgs &a);                 // conv_ws.hip (1x1, K <= 512: weight-stationary, weights in registers)
 int launch_conv_ws(const ConvArgs &a, hipStream_t stream);
+bool conv_ws_res_indexed(const ConvArgs &a);              // the layer runs on conv_ws's build that reads ConvArgs::res_idx
 bool conv3x3_blk_eligible(const ConvArgs &a);             // conv3x3_blk.hip (narrow channel blocks: ResNeXt grouped 3x3, dense 64 -> 64)
 int launch_conv3x3_blk(const ConvArgs &a, hipStream_t stream);
 // bneck_fused.hip: a whole res2 BottleneckBlock (64 bottleneck channels, stride 1) as one kernel
