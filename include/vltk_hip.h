@@ -190,7 +190,8 @@ int vk_destroy(vk_handle *h);
  * holds: 0, 1 or 2), "lane_forwards" (forwards that ran on a stream of the handle's own since vk_create) and
  * "dedupe_chunks" (Res5 chunks that took the "head_dedupe" path since vk_create), "indexed_chunks" (those of them whose conv2 read
  * conv1's distinct rows through the index, without the row gather: vk_panel_phase_indexed), "tap_dedupe_chunks" (those of them
- * that took the "head_dedupe_taps" path). */
+ * that took the "head_dedupe_taps" path), "out_indexed_chunks" (those of these whose conv2 of block 0 stored the distinct
+ * neighbourhoods' rows itself, without the row gather behind it: vk_panel_out_indexed). */
 int vk_set_option(vk_handle *h, const char *key, int value);
 int vk_get_option(vk_handle *h, const char *key, int *value);
 int vk_option_check(const char *key, int value);
@@ -451,6 +452,10 @@ int vk_panel_phase_reuse(int N, int H, int W, int dil, int cout);
  * REUSE is 0), or VK_PANEL_INDEXED=0 keeps the gather + dense launch everywhere.  A row's bits do not depend on where its input
  * row lives: the indexed launch and vk_gather_rows + vk_conv2d give the same bits. */
 int vk_panel_phase_indexed(int N, int H, int W, int dil, int cout);
+/* Whether that launch can STORE its rows through an index (vk_conv2d_rows_out; host only; VK_PANEL_OUT_INDEXED is re-read per call):
+ * 1 = the whole launch runs the 512-row fragment-window tile, as above; 0 = it does not, or VK_PANEL_OUT_INDEXED=0 keeps the dense
+ * output + vk_gather_rows_dev everywhere.  It does not read VK_PANEL_INDEXED: the two indices are independent. */
+int vk_panel_out_indexed(int N, int H, int W, int dil, int cout);
 
 /* conv3 + projection shortcut of a stride-1 BottleneckBlock as ONE f16 GEMM (`out = conv3(t) ; out += shortcut(x)`,
  * frcnn.py:970-977): y[M,cout] = relu?([x1 | x2] . W^T + bias (+ residual)), W rows = [conv3 row (cin1) | shortcut row
@@ -877,6 +882,10 @@ int vk_gather_rows_dev(const void *src, const int32_t *idx, long rows, const int
 size_t vk_roi_neighbourhoods_workspace_bytes(long rows);
 int vk_roi_neighbourhoods(const int32_t *idx, int K, int P, int dil, int32_t *nid, int32_t *rep, int32_t *idx_rep, int32_t *v_dev,
                           void *workspace, size_t workspace_bytes, void *stream);
+/* Where each dense row goes among the distinct neighbourhoods' rows: out_row[m] = nid[m] where rep[nid[m]] == m, -1 elsewhere
+ * (nid, rep of vk_roi_neighbourhoods; `rows` = K*P*P entries each).  Every id of [0, V) appears exactly once and the non-negative
+ * entries ascend with m.  vk_conv2d_rows_out stores through it. */
+int vk_roi_out_rows(const int32_t *nid, const int32_t *rep, long rows, int32_t *out_row, void *stream);
 /* The VK_ROUTE_GEMM4 kernel on de-duplicated rows (f16): y[m] = relu?([x1[m] | x2[x2_idx[m]]] . W^T + bias) for m < M', where
  * M' = min(*m_dev, M) when m_dev is given (M then only bounds the launch) and M otherwise.  x2 / x2_idx may be null (one input,
  * x2 [M,cin2] read by m).  Weights and bias as for vk_conv1x1_dual.  VK_EINVAL where vk_conv_route would not give
@@ -891,6 +900,14 @@ int vk_conv1x1_rows(const void *x1, int cin1, const void *x2, int cin2, long M, 
  * x_rows * cin * 2 reaches 2^32.  Same bits as vk_gather_rows + vk_conv2d. */
 int vk_conv2d_rows(const void *x, long x_rows, const int32_t *x_idx, int N, int H, int W, int cin, const void *w_packed,
                    const float *bias_packed, const void *residual, void *y, int cout, int dil, int relu, void *stream);
+/* The same launch storing its rows through an index: row m of the result goes to y[y_idx[m]] and is not stored where y_idx[m] is
+ * outside [0, y_rows) (-1 by convention).  y is [y_rows, cout]; y_idx holds N*H*W entries, and no two entries inside [0, y_rows)
+ * may be equal (two rows would race for one place).  x_idx may be null: x is then the dense [N*H*W, cin] tensor and x_rows is
+ * not read.  No residual.  VK_EINVAL, before any launch, where vk_panel_out_indexed answers 0 for the launch (with x_idx: or
+ * vk_panel_phase_indexed), with a residual, or with y_rows <= 0.  The rows stored have the bits vk_conv2d gives them. */
+int vk_conv2d_rows_out(const void *x, long x_rows, const int32_t *x_idx, int N, int H, int W, int cin, const void *w_packed,
+                       const float *bias_packed, const void *residual, void *y, long y_rows, const int32_t *y_idx, int cout, int dil,
+                       int relu, void *stream);
 /* The VK_ROUTE_WS kernel with a de-duplicated residual (f16, 1x1, K = 512): y[m] = relu?(x[m] . W^T + bias + residual[res_idx[m]]),
  * m < M, without the dense residual being written.  res_idx holds M entries, every one a row of `residual`: the index is a
  * contract, the kernel does not check it.  res_idx may be null (residual [M, cout] read by m: the plain build, same entry).

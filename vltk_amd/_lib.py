@@ -134,6 +134,7 @@ SIGNATURES = {
     "vk_panel_phase_tile_rows": (_I, [_I, _I, _I, _I, _I]),
     "vk_panel_phase_reuse": (_I, [_I, _I, _I, _I, _I]),
     "vk_panel_phase_indexed": (_I, [_I, _I, _I, _I, _I]),
+    "vk_panel_out_indexed": (_I, [_I, _I, _I, _I, _I]),
     "vk_conv1x1_dual": (_I, [_P, _I, _P, _I, C.c_long, _P, _P, _P, _P, _I, _I, _P]),
     "vk_bottleneck64": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vk_fuse_shortcut": (_I, [_I, _I, _I, _I, _I]),
@@ -218,6 +219,8 @@ SIGNATURES = {
     "vk_conv1x1_res_rows": (_I, [_P, _I, C.c_long, _P, _P, _P, _P, _P, _I, _I, _P]),
     "vk_conv1x1_rows": (_I, [_P, _I, _P, _I, C.c_long, _P, _P, _P, _P, _P, _I, _I, _P]),
     "vk_conv2d_rows": (_I, [_P, C.c_long, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "vk_conv2d_rows_out": (_I, [_P, C.c_long, _P, _I, _I, _I, _I, _P, _P, _P, _P, C.c_long, _P, _I, _I, _I, _P]),
+    "vk_roi_out_rows": (_I, [_P, _P, C.c_long, _P, _P]),
     "vk_mean_pool": (_I, [_P, _I, _I, _I, _P, _I, _P]),
     "vk_box_decode": (_I, [_P, _P, _I, _I, C.POINTER(_F), _P, _P]),
     "vk_make_rois": (_I, [_P, _I, _I, _P, _P]),

@@ -31,6 +31,7 @@
 //     whole 16-row tiles, so (row tile mi, tap dx) and (mi - 1, dx + 1) are the same LDS bytes at the same lane address.  30 A-fragment
 //     ds_read_b128 per wave and stage instead of 72 (66 instead of 108 with the weights), the same MFMAs on the same operands in the
 //     same order.  VK_PANEL_REUSE=0 selects the schedule in which every tap reads its eight fragments (same bits).
+#include <algorithm>
 #include <cstdio>
 #include <type_traits>
 #include <vector>
@@ -67,6 +68,10 @@ struct PanelK {
     unsigned rcp_w2;          // 65536 / (W / 2) + 1: q / (W / 2) == (q * rcp_w2) >> 16 for q < 9362
     // IDX builds only: natural row m of the launch reads row x_idx[m] of x; [groups * 16 * HW] entries
     const int *x_idx;
+    // OIDX builds only: natural row m of the launch is stored to row y_idx[m] of y, and not at all where that entry
+    // is outside [0, y_rows); [groups * 16 * HW] entries
+    const int *y_idx;
+    unsigned y_rows;
 };
 
 // PHASE form: 16-row block `gb` of a group ([phase][qy][qx], HW blocks) -> its position in the phase's grid, and the natural row
@@ -178,7 +183,12 @@ static_assert(reuse_window_ok(), "REUSE: (tap, row tile) -> window slot -> panel
 // words and the epilogue go by m.  req_panel is the only place the input is addressed: a lane's six source offsets of a tile are
 // x_idx[its natural row] * cin_bytes, six registers loaded once per tile, where the dense form adds a uniform block offset to ps_lane.
 // The K loop, its vmcnt / lgkmcnt tables, the fragment window and the MFMAs are those of IDX = 0.
-template <int PP, int DBG, int TAG = 0, int MI = 8, int PHASE = 0, int WR = 2, int REUSE = 0, int IDX = 0>
+// OIDX: 1 = INDEXED OUTPUT ROWS (the same form only, with or without IDX): the epilogue stores natural row m to row
+// y_idx[m] of y, which is then [y_rows, ldy], and drops the store where y_idx[m] is outside [0, y_rows) (Res5 block 0: conv2 writes
+// the representative row of each nine-window neighbourhood and no other).  No residual.  A lane's eight indices, one per row tile,
+// are requested behind the K loop's LAST counted wait (the vmcnt(0) of the final stage's tap 7: no later step issues or waits for
+// anything), so they travel under the last 44 MFMAs of the wave and no table of the loop sees them.
+template <int PP, int DBG, int TAG = 0, int MI = 8, int PHASE = 0, int WR = 2, int REUSE = 0, int IDX = 0, int OIDX = 0>
 __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(MI == 8 || MI == 9, "8 or 9 row tiles per wave");
@@ -188,6 +198,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     static_assert(MI == 8 || !(DBG & 8), "the LDS-staged epilogue is written for 128-row halves");
     static_assert(!REUSE || (PHASE == 2 && WR == 4 && MI == 8 && DBG == 0), "the fragment window: tap shifts of whole 16-row tiles, 512 x 128 tiles");
     static_assert(!IDX || (PHASE == 2 && WR == 4 && REUSE == 1 && DBG == 0 && PP == 6), "indexed input rows: the 512 x 128 REUSE phase form only");
+    static_assert(!OIDX || (PHASE == 2 && WR == 4 && REUSE == 1 && DBG == 0 && PP == 6), "indexed output rows: the 512 x 128 REUSE phase form only");
     constexpr int WC = 8 / WR;                    // column blocks of 64 channels
     constexpr int CT = 64 * WC;                   // channels per tile: 256 or 128
     constexpr int NWP = CT / 128;                 // weight DMA pieces (16 rows) per wave and step: 2 or 1
@@ -682,7 +693,24 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     VKP_UNIT(F_{}, F_{}, 1) VKP_UNIT(F_{}, F_{}, 2) VKP_UNIT(F_{}, F_{}, 3) VKP_UNIT(F_{}, F_{}, 4) VKP_UNIT(F_{}, F_{}, 5)
     VKP_UNIT(F_{}, F_{}, 6) VKP_UNIT(F_{}, F_{}, 7) VKP_UNIT(F_{}, F_{}, 8) VKP_UNIT(F_{}, T_{}, 9) VKP_UNIT(T_{}, T_{}, 10)
     VKP_UNIT(T_{}, T_{}, 11) VKP_UNIT(T_{}, T_{}, 12) VKP_UNIT(T_{}, T_{}, 13) VKP_UNIT(T_{}, T_{}, 14) VKP_UNIT(T_{}, T_{}, 15)
-    VKP_UNIT(T_{}, T_{}, 16) VKP_UNIT(T_{}, T_{}, 17)
+    VKP_UNIT(T_{}, T_{}, 16)
+    // OIDX: the output rows of the lane's eight row tiles.  Step 16 (tap 7 of the last stage) has just waited for vmcnt(0) and neither
+    // its POST nor step 17 issues or waits for a vector-memory request (last_in_window<7> == 0, no weights from tap 3 on, no wait
+    // behind tap 8), so these loads are alone in the queue until the epilogue's own wait.  min(mo, M - 1) as for the residual: blk_of
+    // clamps every block into the tensor, so y_idx is never read out of range.
+    [[maybe_unused]] int yrow[MI] = {};
+    if constexpr (OIDX) {
+        static_assert(last_in_window<7, PP, NWP>() == 0, "the index loads go out behind the loop's last counted wait");
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) {
+            int G;
+            const int t = blk_of(wr * MI + mi, G);
+            const long mo = (long)(G * 16 + j) * p.HW + phase_blk(p, t).row;
+            const int *ip = p.y_idx + min(mo, (long)p.M - 1);
+            asm volatile("global_load_dword %0, %1, off" : "=v"(yrow[mi]) : "v"(ip));
+        }
+    }
+    VKP_UNIT(T_{}, T_{}, 17)
     {
         const unsigned tm = ZROW ? 0u : tap_mask(VKP_IC(8));
         VKP_MMA_ROW(5, xw[REUSE ? reuse_slot(1, 5) : 1], wb, tm);
@@ -710,6 +738,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
     if constexpr (!(DBG & 8)) {
         // (PHASE: the epilogue places its row tiles afresh: held from the prologue, their 16 scalars would be spilled across the K loop)
         if constexpr (PHASE) asm volatile("" : "+s"(g0), "+s"(gb0));
+        if constexpr (OIDX) {                                  // the eight indices have landed (the wait names them: no reader moves above it)
+            static_assert(MI == 8);
+            asm volatile("s_waitcnt vmcnt(0)"
+                         : "+v"(yrow[0]), "+v"(yrow[1]), "+v"(yrow[2]), "+v"(yrow[3]), "+v"(yrow[4]), "+v"(yrow[5]), "+v"(yrow[6]), "+v"(yrow[7])
+                         :
+                         : "memory");
+        }
         auto epilogue = [&](auto res_c, auto relu_c, auto full_c) {
             constexpr bool RES = decltype(res_c)::value, RELU = decltype(relu_c)::value, FULL = decltype(full_c)::value;
             // row tile outer, channel half inner: the two 64-byte halves of a pixel's 128-byte line (this wave's 64 channels) leave in
@@ -739,7 +774,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
 #pragma unroll
                 for (int qn = 0; qn < 2; ++qn) {
                     const half8 o = epi_unit<RES, RELU>(acc[mi][2 * qn], acc[mi][2 * qn + 1], bq[qn][0], bq[qn][1], rr[qn]);
-                    if (FULL || m < p.M) *reinterpret_cast<half8 *>(p.y + (mo * p.ldy + ch0 + qn * 32) * 2) = o;
+                    if constexpr (OIDX) {                      // row y_idx[mo], or no store (one unsigned compare: not negative, below y_rows)
+                        if ((FULL || m < p.M) && (unsigned)yrow[mi] < p.y_rows)
+                            *reinterpret_cast<half8 *>(p.y + ((long)yrow[mi] * p.ldy + ch0 + qn * 32) * 2) = o;
+                    } else if (FULL || m < p.M)
+                        *reinterpret_cast<half8 *>(p.y + (mo * p.ldy + ch0 + qn * 32) * 2) = o;
                 }
             }
         };
@@ -757,7 +796,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_panel_kernel(PanelK p) {
             else
                 by_full(r_, std::false_type{});
         };
-        if (p.res)
+        if (!OIDX && p.res)                                    // (OIDX: the launcher refuses a residual)
             by_relu(std::true_type{});
         else
             by_relu(std::false_type{});
@@ -858,10 +897,24 @@ int conv3x3_panel_phase_indexed(const ConvArgs &a) {
     return conv3x3_panel_phase_images(a) == a.N && conv3x3_panel_phase_reuse(a) == 1 ? 1 : 0;
 }
 
+// 1 where the launch can store its rows through an index (ConvArgs::y_idx): the form above, whatever
+// VK_PANEL_INDEXED says (the output index does not need the input one).  VK_PANEL_OUT_INDEXED=0 answers 0 everywhere: Res5 block 0
+// then writes the dense rows and gathers the representatives (the A/B and bit-identity partner).
+int conv3x3_panel_out_indexed(const ConvArgs &a) {
+    if (env_off("VK_PANEL_OUT_INDEXED")) return 0;
+    return conv3x3_panel_phase_images(a) == a.N && conv3x3_panel_phase_reuse(a) == 1 ? 1 : 0;
+}
+
 static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase);
 
 int launch_conv3x3_panel(const ConvArgs &a, hipStream_t stream) {
     const int np = conv3x3_panel_phase_images(a);
+    // ... and so is an output index: any other form would store every row where it always did
+    VK_REQUIRE(!a.y_idx || conv3x3_panel_out_indexed(a), VK_EINVAL,
+               "conv3x3_panel: y_idx needs the whole launch in the 512 x 128 fragment-window phase form (N %% 16 == 0, dilation 2, even H, "
+               "even W <= 14; VK_PANEL_PHASE / TALL / REUSE / OUT_INDEXED not 0): N=%d H=%d W=%d dil=%d", a.N, a.H, a.W, a.dil);
+    VK_REQUIRE(!a.y_idx || !a.res, VK_EINVAL, "conv3x3_panel: y_idx takes no residual (its rows would be those of the dense output)");
+    VK_REQUIRE(!a.y_idx || a.y_rows > 0, VK_EINVAL, "conv3x3_panel: y_idx needs y_rows > 0, the rows of y (got %ld)", a.y_rows);
     // a row index is read by one instantiation alone: any other form would run on the wrong rows
     VK_REQUIRE(!a.x_idx || conv3x3_panel_phase_indexed(a), VK_EINVAL,
                "conv3x3_panel: x_idx needs the whole launch in the 512 x 128 fragment-window phase form (N %% 16 == 0, dilation 2, even H, "
@@ -900,6 +953,8 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
     VK_REQUIRE(xr * a.Cin * 2 < (1L << 32) && (long)a.Cout * 9 * a.Cin * 2 < (1L << 32), VK_EINVAL,
                "conv3x3_panel: tensor beyond the 32-bit DMA offsets (rows of x=%ld Cin=%d Cout=%d)", xr, a.Cin, a.Cout);
     k.x_idx = a.x_idx;
+    k.y_idx = a.y_idx;
+    k.y_rows = (unsigned)std::min<long>(a.y_idx ? a.y_rows : 0, 1L << 31);      // (an index is below 2^31)
     k.M = (int)M;
     k.cin_bytes = a.Cin * 2;
     k.ldy = a.ldy;
@@ -969,7 +1024,13 @@ static int launch_panel_one(const ConvArgs &a, hipStream_t stream, bool phase) {
         VKP_LAUNCH_PHASE(4, 0, 0, 8, 1);
     else
 #endif
-    if (a.x_idx) {
+    if (a.y_idx) {
+        VK_REQUIRE(tall && conv3x3_panel_phase_reuse(a) && !a.res, VK_EINVAL, "conv3x3_panel: y_idx outside the fragment-window phase form");
+        if (a.x_idx)
+            VKP_LAUNCH_PHASE(6, 0, 0, 8, 2, 4, 1, 1, 1);
+        else
+            VKP_LAUNCH_PHASE(6, 0, 0, 8, 2, 4, 1, 0, 1);
+    } else if (a.x_idx) {
         VK_REQUIRE(tall && conv3x3_panel_phase_reuse(a), VK_EINVAL, "conv3x3_panel: x_idx outside the fragment-window phase form");
         VKP_LAUNCH_PHASE(6, 0, 0, 8, 2, 4, 1, 1);
     } else if (tall && conv3x3_panel_phase_reuse(a))

@@ -456,6 +456,8 @@ int launch_conv(const ConvArgs &a, hipStream_t stream) {
     // (the panel launcher refuses the forms of its own that do not read the index)
     VK_REQUIRE(!a.x_idx || route == VK_ROUTE_PANEL || route < 0, VK_EINVAL,
                "conv: x_idx is read by the 3x3 panel kernel alone, and this layer takes route %d", route);
+    VK_REQUIRE(!a.y_idx || route == VK_ROUTE_PANEL || route < 0, VK_EINVAL,
+               "conv: y_idx is read by the 3x3 panel kernel alone, and this layer takes route %d", route);
     VK_REQUIRE(!a.res_idx || route == VK_ROUTE_WS || route < 0, VK_EINVAL,
                "conv: res_idx is read by the weight-stationary 1x1 kernel alone, and this layer takes route %d", route);
     switch (route) {

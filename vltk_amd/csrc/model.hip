@@ -118,6 +118,7 @@ struct vk_handle {
     int64_t dedupe_chunks = 0;                                            // head chunks that took that path (vk_get_option "dedupe_chunks")
     int64_t indexed_chunks = 0;                                           // those of them whose conv2 read conv1's rows through the index ("indexed_chunks")
     int64_t tap_dedupe_chunks = 0;                                        // those of them that went on over the distinct neighbourhoods ("tap_dedupe_chunks")
+    int64_t out_indexed_chunks = 0;                                       // those of these whose conv2 of block 0 stored the distinct rows itself ("out_indexed_chunks")
     // "pooled" after a forward whose one chunk took the dedupe path: the dense tensor was never written; vk_get_stage expands
     // src[idx] into the plan's buffer the first time the stage is asked for
     struct {
@@ -375,8 +376,9 @@ struct Plan {
     void *dd_ws;
     size_t dd_ws_bytes;
     // ... over the distinct nine-window neighbourhoods (head_dedupe_taps), or null: nid [chunk rows], rep and idx_rep
-    // [chunk rows] (a chunk without one repeated neighbourhood fits), one neighbourhood count per chunk, the table's workspace
-    int32_t *nb_nid, *nb_rep, *nb_idx_rep, *nb_v;
+    // [chunk rows] (a chunk without one repeated neighbourhood fits), one neighbourhood count per chunk, the table's workspace;
+    // out_row [chunk rows]: where conv2 of block 0 stores each dense row among the distinct ones, -1 = nowhere
+    int32_t *nb_nid, *nb_rep, *nb_idx_rep, *nb_v, *nb_out_row;
     void *nb_ws;
     size_t nb_ws_bytes;
     size_t head_rows;        // pixels that h_t1 .. h_sc hold each (a Res5 chunk, or the whole res4 map of a grid forward)
@@ -471,6 +473,7 @@ static Plan make_plan(vk_handle *h, char *base, int N, int H, int W, int D, int 
                 p.nb_nid = (int32_t *)cv.take(roi_rows * sizeof(int32_t));
                 p.nb_rep = (int32_t *)cv.take(roi_rows * sizeof(int32_t));
                 p.nb_idx_rep = (int32_t *)cv.take(roi_rows * sizeof(int32_t));
+                p.nb_out_row = (int32_t *)cv.take(roi_rows * sizeof(int32_t));
                 p.nb_v = (int32_t *)cv.take((size_t)ceil_div(p.K, p.chunk) * sizeof(int32_t));
             }
         }
@@ -824,6 +827,7 @@ int vk_get_option(vk_handle *h, const char *key, int *value) {
     if (!strcmp(key, "dedupe_chunks")) *value = (int)std::min<int64_t>(h->dedupe_chunks, INT32_MAX);      // head chunks that took the dedupe path
     else if (!strcmp(key, "indexed_chunks")) *value = (int)std::min<int64_t>(h->indexed_chunks, INT32_MAX);   // ... and ran conv2 without the row gather
     else if (!strcmp(key, "tap_dedupe_chunks")) *value = (int)std::min<int64_t>(h->tap_dedupe_chunks, INT32_MAX);   // ... and went on over the distinct neighbourhoods
+    else if (!strcmp(key, "out_indexed_chunks")) *value = (int)std::min<int64_t>(h->out_indexed_chunks, INT32_MAX);   // ... with conv2 of block 0 storing the distinct rows itself
     else if (!strcmp(key, "working_sets")) *value = (h->sets[0].arena ? 1 : 0) + (h->sets[1].arena ? 1 : 0);   // arenas held
     else if (!strcmp(key, "lane_forwards")) *value = (int)std::min<int64_t>(h->lane_forwards, INT32_MAX);    // forwards enqueued on a lane's stream
     else VK_REQUIRE(false, VK_EINVAL, "unknown option '%s'", key);
@@ -1165,13 +1169,18 @@ static int fwd_predictor(vk_handle *h, const Plan &p, hipStream_t s);
 //
 // head_dedupe_taps: block 0's output row, its shortcut operand and conv1 of block 1 depend on the bin's nine-window
 // neighbourhood alone, so from conv2 on the 1x1 GEMMs run over the chunk's V distinct neighbourhoods (vk_roi_neighbourhoods; V stays
-// on the device): t2's representative rows are gathered into t2_v (h_t1, where conv1's distinct rows are dead by then), the fused
-// conv3 + shortcut GEMM writes Y0_v [V, 2048] into h_a, conv1 of block 1 writes t1_v [V, 512] into h_t2, conv2 of block 1 reads
-// t1_v through nid (the panel kernel's indexed form) and conv3 of block 1 takes its residual from Y0_v through nid (conv_ws's
-// indexed-residual build) and writes the dense Y1 into h_b.  Each row goes through the same kernels with the same K order as on
-// the path above: same bits.  *block1_done tells fwd_head that block 1 has run.  Taken where conv2 of block 0 took the indexed
-// form, Res5 has a block behind block 1 (whose conv3 then stores: the last block's feeds the fused mean) and block 1's three
+// on the device).  The table is a function of the boxes alone, so it is built AHEAD of conv2, and conv2 stores each neighbourhood's
+// representative row, and no other, straight into t2_v through out_row (the panel kernel's indexed output rows, DESIGN.md 6i;
+// t2_v in h_t2: conv2 reads t1_u from h_t1).  The fused conv3 + shortcut GEMM writes Y0_v [V, 2048] into h_a, conv1 of block 1 writes
+// t1_v [V, 512] into h_t1 (t1_u is dead behind conv2), conv2 of block 1 reads t1_v through nid (the panel kernel's indexed form) and
+// writes its dense t2 into h_t2 (t2_v is dead behind the fused GEMM), and conv3 of block 1 takes its residual from Y0_v through nid
+// (conv_ws's indexed-residual build) and writes the dense Y1 into h_b.  Each row goes through the same kernels with the same K
+// order as on the path above: same bits.  *block1_done tells fwd_head that block 1 has run.  Taken where conv2 of block 0 took the
+// indexed form, Res5 has a block behind block 1 (whose conv3 then stores: the last block's feeds the fused mean) and block 1's three
 // layers run as conv_gemm4 (decided at the chunk's dense row count) / the indexed panel form / conv_ws's indexed-residual build.
+// Where conv2 cannot store through an index (conv3x3_panel_out_indexed: VK_PANEL_OUT_INDEXED=0) it writes the dense t2 into h_t2
+// and vk_gather_rows_dev copies the representative rows into t2_v (h_t1), t1_v then lives in h_t2 and block 1's t2 in h_t1: the
+// path of DESIGN.md 6h, same bits.
 static bool head_taps_ok(const vk_handle *h, const Plan &p, int kc) {
     if (!h->head_dedupe_taps || !p.nb_nid || h->res5.size() < 3) return false;
     const Block &b1 = h->res5[1];
@@ -1204,14 +1213,22 @@ static int head_block0_dedupe(vk_handle *h, const Plan &p, const void *res4, int
         h->indexed_chunks++;
     } else
         VK_TRY(vk_gather_rows(t1_u, p.dd_idx, rows, (int)(b.conv1.cout * es), p.h_t1, s));
-    VK_TRY(launch_conv(a2, s));
     *block1_done = indexed && head_taps_ok(h, p, kc);
+    const bool out_indexed = *block1_done && p.nb_out_row && conv3x3_panel_out_indexed(a2) == 1;
+    int32_t *v = p.nb_v ? p.nb_v + k0 / p.chunk : nullptr;
+    if (*block1_done) VK_TRY(vk_roi_neighbourhoods(p.dd_idx, kc, P, b.conv2.dil, p.nb_nid, p.nb_rep, p.nb_idx_rep, v, p.nb_ws, p.nb_ws_bytes, s));
+    if (out_indexed) {
+        VK_TRY(vk_roi_out_rows(p.nb_nid, p.nb_rep, rows, p.nb_out_row, s));
+        a2.y_idx = p.nb_out_row;
+        a2.y_rows = rows;              // (V <= rows is on the device; every entry is -1 or an id below V)
+        h->out_indexed_chunks++;
+    }
+    VK_TRY(launch_conv(a2, s));
     if (*block1_done) {
         const Block &b1 = h->res5[1];
-        int32_t *v = p.nb_v + k0 / p.chunk;
-        void *t2_v = p.h_t1, *y0_v = p.h_a, *t1_v = p.h_t2;
-        VK_TRY(vk_roi_neighbourhoods(p.dd_idx, kc, P, b.conv2.dil, p.nb_nid, p.nb_rep, p.nb_idx_rep, v, p.nb_ws, p.nb_ws_bytes, s));
-        VK_TRY(vk_gather_rows_dev(p.h_t2, p.nb_rep, rows, v, (int)(b.conv2.cout * es), t2_v, s));
+        // out_indexed: conv2 has written t2_v into h_t2; otherwise the dense t2 is there and its representative rows are gathered into h_t1
+        void *t2_v = out_indexed ? p.h_t2 : p.h_t1, *y0_v = p.h_a, *t1_v = out_indexed ? p.h_t1 : p.h_t2, *t2_1 = out_indexed ? p.h_t2 : p.h_t1;
+        if (!out_indexed) VK_TRY(vk_gather_rows_dev(p.h_t2, p.nb_rep, rows, v, (int)(b.conv2.cout * es), t2_v, s));
         ConvArgs a3 = layer_args(h, b.conv3, t2_v, 1, 1, (int)rows, y0_v, {.x2 = pooled_u, .cin2 = b.shortcut.cin, .relu = true});
         a3.x2_idx = p.nb_idx_rep;
         a3.m_dev = v;
@@ -1219,11 +1236,11 @@ static int head_block0_dedupe(vk_handle *h, const Plan &p, const void *res4, int
         ConvArgs c1 = layer_args(h, b1.conv1, y0_v, 1, 1, (int)rows, t1_v, {.relu = true});
         c1.m_dev = v;
         VK_TRY(launch_conv_gemm4(c1, s));
-        ConvArgs c2 = layer_args(h, b1.conv2, t1_v, kc, P, P, p.h_t1, {.relu = true});
+        ConvArgs c2 = layer_args(h, b1.conv2, t1_v, kc, P, P, t2_1, {.relu = true});
         c2.x_idx = p.nb_nid;
         c2.x_rows = rows;                  // (V <= rows is on the device; every id is below V)
         VK_TRY(launch_conv(c2, s));
-        ConvArgs c3 = layer_args(h, b1.conv3, p.h_t1, 1, 1, (int)rows, p.h_b, {.res = y0_v, .relu = true});
+        ConvArgs c3 = layer_args(h, b1.conv3, t2_1, 1, 1, (int)rows, p.h_b, {.res = y0_v, .relu = true});
         c3.res_idx = p.nb_nid;
         VK_TRY(launch_conv(c3, s));
         h->tap_dedupe_chunks++;

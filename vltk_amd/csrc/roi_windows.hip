@@ -9,6 +9,7 @@
 //   vk_gather_rows        dst[row] = src[idx[row]] in 16-byte lanes (conv1's rows back to the dense tensor; "pooled" on demand)
 //   vk_roi_neighbourhoods nid[row] = id of the row's NINE-window neighbourhood (its own window and the eight a dilated 3x3 reads),
 //                         rep[id] = the smallest row with it, idx_rep[id] = idx[rep[id]], *v_dev = number of ids
+//   vk_roi_out_rows       out_row[row] = nid[row] where rep[nid[row]] == row, -1 elsewhere: where conv2 stores the row
 // Ids are the RANK of the window's key (image, y0, y1, x0, x1) among the keys present, so they do not depend on the order in which
 // the device happens to run anything: one bit per possible key, a marking pass, popcount sums over 8-word blocks, a two-level
 // exclusive scan of the block sums, and id = scanned sum + popcount of the bits below the key's own.  No host read-back, no
@@ -265,6 +266,15 @@ __global__ void nb_assign_kernel(const int32_t *__restrict__ idx, long rows, con
     }
 }
 
+// out_row[row] = the row's neighbourhood id where the row is that neighbourhood's representative, -1 elsewhere: every
+// id of [0, V) exactly once, ascending with the row since rep[] is.  The panel kernel stores its output rows through it.
+__global__ void nb_out_rows_kernel(const int32_t *__restrict__ nid, const int32_t *__restrict__ rep, long rows, int32_t *__restrict__ out_row) {
+    const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    const int32_t id = nid[row];
+    out_row[row] = rep[id] == (int32_t)row ? id : -1;
+}
+
 struct RwLayout {
     size_t n_words, n_blocks, n_blocks_padded, n_groups;
     size_t off_bsum, off_gsum, total;
@@ -364,6 +374,13 @@ int vk_roi_neighbourhoods(const int32_t *idx, int K, int P, int dil, int32_t *ni
     hipLaunchKernelGGL(rw_group_scan_kernel, dim3((unsigned)L.n_groups), dim3(256), 0, s, bsum, gsum);
     hipLaunchKernelGGL(rw_top_scan_kernel, dim3(1), dim3(256), 0, s, gsum, (int)L.n_groups, v_dev);
     hipLaunchKernelGGL(nb_assign_kernel, dim3(row_grid), dim3(256), 0, s, idx, rows, bits, bsum, gsum, nid, rep, idx_rep);
+    VK_CHECK_HIP(hipGetLastError());
+    return VK_OK;
+}
+
+int vk_roi_out_rows(const int32_t *nid, const int32_t *rep, long rows, int32_t *out_row, void *stream) {
+    VK_REQUIRE(nid && rep && out_row && rows > 0 && rows < (1L << 30), VK_EINVAL, "roi_out_rows: bad arguments (%ld rows)", rows);
+    hipLaunchKernelGGL(nb_out_rows_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nid, rep, rows, out_row);
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
 }

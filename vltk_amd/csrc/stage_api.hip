@@ -253,6 +253,30 @@ int vk_conv2d_rows(const void *x, long x_rows, const int32_t *x_idx, int N, int 
     return launch_conv(a, (hipStream_t)stream);
 }
 
+int vk_panel_out_indexed(int N, int H, int W, int dil, int cout) {
+    ConvArgs a;
+    fill_conv_args(a, N, H, W, 128, cout, cout, 3, 1, dil, dil, 1, 0, VK_F16, VK_F16);
+    return conv3x3_panel_out_indexed(a);
+}
+
+int vk_conv2d_rows_out(const void *x, long x_rows, const int32_t *x_idx, int N, int H, int W, int cin, const void *w_packed,
+                       const float *bias_packed, const void *residual, void *y, long y_rows, const int32_t *y_idx, int cout, int dil,
+                       int relu, void *stream) {
+    VK_REQUIRE(y_idx && (!x_idx || x_rows > 0) && N > 0 && H > 0 && W > 0 && dil >= 1, VK_EINVAL, "conv2d_rows_out: bad arguments");
+    ConvArgs a;
+    fill_conv_args(a, N, H, W, cin, cout, cout, 3, 1, dil, dil, 1, relu, VK_F16, VK_F16);
+    a.x = x;
+    a.x_idx = x_idx;
+    a.x_rows = x_idx ? x_rows : 0;
+    a.y_idx = y_idx;
+    a.y_rows = y_rows;
+    a.w = w_packed;
+    a.bias = bias_packed;
+    a.res = residual;
+    a.y = y;
+    return launch_conv(a, (hipStream_t)stream);
+}
+
 int vk_conv1x1_dual(const void *x1, int cin1, const void *x2, int cin2, long M, const void *w_packed, const float *bias_packed,
                     const void *residual, void *y, int cout, int relu, void *stream) {
     VK_REQUIRE(x1 && x2 && M > 0 && M < (1L << 31), VK_EINVAL, "conv1x1_dual: bad arguments");

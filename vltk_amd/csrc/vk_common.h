@@ -108,6 +108,8 @@ struct ConvArgs {
     const int32_t *x2_idx;  // conv_gemm4 only: output row m reads row x2_idx[m] of x2
     const int32_t *x_idx;   // conv3x3_panel only, where conv3x3_panel_phase_indexed: output row m reads row x_idx[m] of x [x_rows, Cin]
     long x_rows;            // with x_idx: the rows of x (every index lies in [0, x_rows))
+    const int32_t *y_idx;   // conv3x3_panel only, where conv3x3_panel_out_indexed: output row m goes to row y_idx[m] of y [y_rows, ldy], nowhere if that is outside [0, y_rows); no residual
+    long y_rows;            // with y_idx: the rows of y
     const int32_t *res_idx; // conv_ws only, where conv_ws_res_indexed: output row m adds row res_idx[m] of res
     vk_dtype dt, out_dt;
 };
@@ -122,6 +124,7 @@ int conv3x3_panel_phase_images(const ConvArgs &a);        // leading images of a
 int conv3x3_panel_phase_tile_rows(const ConvArgs &a);     // rows of a tile of that part: 512, 256 (VK_PANEL_TALL=0) or 0 (no phase part)
 int conv3x3_panel_phase_reuse(const ConvArgs &a);         // 1: that part's 512-row tiles share a fragment window per tap row; 0: VK_PANEL_REUSE=0 or no such tile
 int conv3x3_panel_phase_indexed(const ConvArgs &a);       // 1: the WHOLE launch runs that form, which takes x_idx; 0: it does not (N % 16, the three switches) or VK_PANEL_INDEXED=0
+int conv3x3_panel_out_indexed(const ConvArgs &a);         // 1: the WHOLE launch runs that form, which takes y_idx; 0: it does not, or VK_PANEL_OUT_INDEXED=0
 bool conv_gemm4_eligible(const ConvArgs &a);              // conv_gemm4.hip (1x1, K >= 1024, one or two inputs: 256x256 tile, four waves of 128x128)
 int launch_conv_gemm4(const ConvArgs &a, hipStream_t stream);
 int acquire_tile_counter(unsigned **ctr);     // a zeroed device word for one launch's dynamic tile tail; its last fetch zeroes it again (conv_gemm4.hip)
