@@ -687,6 +687,38 @@ int vk_scatter_rows_f32(const float *src, long ld_src, const int32_t *idx, int n
 size_t vk_grad_clip_workspace_bytes(int count);
 int vk_grad_clip(const vk_adamw_tensor *table, int count, int64_t max_n, double max_norm, float *norm_coef, void *workspace,
                  size_t workspace_bytes, void *stream);
+/* The backward of a row lookup (an embedding table's gradient), deterministic, csrc/index_add.hip:
+ *   dst[r, :C] = sum over the entries i < n, ascending, with idx[i] == r and r != padding_idx, of src[src_row ? src_row[i] : i, :C]
+ * src [M, ld_src] and dst [R, ld_dst] are fp32; idx [n] and src_row [n] (or NULL: entry i reads row i) are int32, so one table
+ * can take several index columns of one gradient matrix.  padding_idx: -1 for none.  That row and every row no entry names are
+ * written as zeros: the launch writes all of dst[:, :C] and the caller clears nothing.  An idx[i] outside [0, R) and a source row
+ * outside [0, M) are skipped; nothing outside src, dst and the workspace is read or written for any input.  Any n, R, C >= 1,
+ * ld_src, ld_dst >= C, 4-byte alignment (16-byte accesses where C, both leading dimensions and both bases allow).  A stable radix
+ * sort of (idx[i], i), 8 bits in each of ceil(bits(R) / 8) passes, a segmented fp64 sum over chunks of 32 sorted entries, a
+ * stitch of the runs that cross chunks in chunk order, one rounding to fp32 at the store; no floating-point atomics: the same
+ * input gives the same bits.  workspace: 8-byte aligned, the bytes the size function names (0 for sizes the launch refuses).
+ * vk_index_add_rows_check: what the launch refuses, host only (no pointer is read through): a NULL src, idx, dst or workspace,
+ * a size below 1, a leading dimension below C, n or R at or past 2^31, a padding_idx that is neither -1 nor in [0, R), a pointer
+ * off its 4-byte (workspace: 8-byte) alignment, a workspace below the size function's bytes. */
+size_t vk_index_add_rows_workspace_bytes(long n, long R, int C);
+int vk_index_add_rows_check(const float *src, long ld_src, long M, const int32_t *idx, const int32_t *src_row, long n, float *dst,
+                            long ld_dst, long R, int C, int padding_idx, void *workspace, size_t workspace_bytes);
+int vk_index_add_rows(const float *src, long ld_src, long M, const int32_t *idx, const int32_t *src_row, long n, float *dst, long ld_dst,
+                      long R, int C, int padding_idx, void *workspace, size_t workspace_bytes, void *stream);
+/* The tables of one vk_embed_sum_f32 launch, passed by value into the kernel: table[t] is dense fp32 [rows[t], C]. */
+#define VK_EMBED_MAX_TABLES 12
+typedef struct {
+    const float *table[VK_EMBED_MAX_TABLES];
+    int32_t rows[VK_EMBED_MAX_TABLES];
+    int32_t count;
+} vk_embed_tables;
+/* The fp32 embedding sum a trainer's forward needs: for m < M
+ *   out[out_row ? out_row[m] : m, :C] = (base ? base[m, :C] : 0) + table_0[idx[0, m]] + table_1[idx[1, m]] + ...
+ * in fp32, left to right (without base the first table's row starts the sum): transformers' own order of `+`.  idx [count, M]
+ * int32, an index clamped into its table; base [M, ld_base] or NULL (VisualBERT's projected visual rows); out_row [M] int32 or
+ * NULL places the rows of one modality into a joint sequence, one outside [0, out_rows) is skipped.  One wave per row. */
+int vk_embed_sum_f32(const vk_embed_tables *tables, const int32_t *idx, long M, int C, const float *base, long ld_base, const int32_t *out_row,
+                     float *out, long ld_out, long out_rows, void *stream);
 /* The backward of vk_attention in fp32: O = softmax(Q K^T / sqrt(d) + mask) V per (batch, head), head h in columns h d .. h d + d
  * of rows [B * L, ld]; q, dout, o, dq have B * Lq rows, k, v, dk, dv B * Lk rows, each matrix its own leading dimension (a packed
  * QKV projection passes 3 * heads * d three times).  mask [B, Lk] is additive, may be NULL and receives no gradient.  From what

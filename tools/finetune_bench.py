@@ -13,8 +13,15 @@ section 28) under the same keys with `_mixed` appended, and each of its kernels 
 `vk_gemm_f32` in the three forms at a layer's shapes at B = 1024 (57 344 rows; 768 x 3072 and 768 x 768), device events around
 `--steps` launches after `--warmup`.  Both modes and the kernel table go to `--mixed-out`; `--out` keeps its columns.
 
+`--train-embeddings` measures the full fine-tune instead and writes `--embeddings-out` alone: a mixed-mode
+step with 12 trained layers at B = 64 / 256 / 1024 without and with `train_embeddings=True` and the share of the embedding stage's
+two kernels in the latter; `vk_index_add_rows` alone at the word table's shape of that batch (n = B * 20, R = 30 522, C = 768) and
+at the position table's (every id B times, R = 512), beside `torch.Tensor.index_add_` on the same data (atomic, not reproducible;
+with and without the clear of its destination, which `vk_index_add_rows` includes) and a plain copy of n * C floats.
+
     python tools/finetune_bench.py [--steps 10] [--warmup 3] [--out profiles/finetune_bench.json]
                                    [--mixed-out profiles/finetune_mixed_bench.json]
+    python tools/finetune_bench.py --train-embeddings [--embeddings-out profiles/finetune_embeddings_bench.json]
 """
 import argparse
 import json
@@ -114,13 +121,63 @@ def kernels_alone(warmup, steps):
     return out
 
 
+def embeddings_bench(a):
+    from vltk_amd.train import index_add_rows
+    r = np.random.Generator(np.random.PCG64(0))
+    res = {"device": torch.cuda.get_device_name(0), "precision": "bf16", "compute_dtype": "bfloat16", "steps": a.steps, "warmup": a.warmup,
+           "visualbert": {}, "index_add": {}}
+    cfg, labels_n, Lt, V = visualbert_config(visual_embedding_dim=2048), 3129, 20, 36
+    sd = make_visualbert_qa_state_dict(cfg, labels_n, seed=0)
+    model = VisualBertForQuestionAnswering(cfg, labels_n, precision="bf16").load_state_dict(sd)
+    stage = ("vk_embed_sum_f32", "vk_index_add_rows")
+    for B in (64, 256, 1024):
+        ids = torch.from_numpy(r.integers(1, cfg["vocab_size"], (B, Lt)))
+        feats = torch.from_numpy(np.maximum(r.standard_normal((B, V, 2048)), 0).astype(np.float32)).cuda()
+        am = torch.ones((B, Lt), dtype=torch.int64)
+        labels = r.integers(0, labels_n, B).astype(np.int64)
+        row = {}
+        for flag in (False, True):
+            tr = EncoderTrainer(model, sd, train_layers=12, max_grad_norm=5.0, compute_dtype=torch.bfloat16, train_embeddings=flag)
+            step = lambda: tr.step(ids, feats, labels=labels, attention_mask=am)          # noqa: E731
+            row["step_ms_embeddings" if flag else "step_ms"] = round(ms_per_step(step, a.warmup, a.steps), 3)
+            if flag:
+                by, row["device_ms_embeddings"] = shares(step)
+                row["stage_kernel_shares"] = {k: by.get(k, 0.0) for k in stage}
+            del tr
+            torch.cuda.empty_cache()
+        res["visualbert"][f"B{B}"] = row
+        print(json.dumps({f"B{B}": row}), flush=True)
+        n, C, ksteps = B * Lt, cfg["hidden_size"], max(100, 20 * a.steps)              # a kernel alone: a longer window
+        src = torch.randn((n, C), device="cuda")
+        for name, idx, R in (("word", ids.reshape(-1), cfg["vocab_size"]), ("position", torch.arange(Lt).repeat(B), cfg["max_position_embeddings"])):
+            i32, i64 = idx.to("cuda", torch.int32), idx.to("cuda", torch.int64)
+            dst, other = torch.empty((R, C), device="cuda"), torch.empty_like(src)
+            ours = device_ms(lambda: index_add_rows(src, i32, R, out=dst), a.warmup, ksteps)
+            ref = dst.clone()
+            vendor = device_ms(lambda: dst.index_add_(0, i64, src), a.warmup, ksteps)
+            cleared = device_ms(lambda: dst.zero_().index_add_(0, i64, src), a.warmup, ksteps)
+            worst = float((dst - ref).abs().max())                                        # the atomic path against the deterministic one
+            copy = device_ms(lambda: other.copy_(src), a.warmup, ksteps)
+            res["index_add"][f"{name} B{B} n{n} R{R} C{C}"] = dict(
+                vk_index_add_rows_ms=round(ours, 4), torch_index_add_ms=round(vendor, 4), torch_zero_index_add_ms=round(cleared, 4),
+                copy_ms=round(copy, 4), ratio_to_torch_zero_index_add=round(ours / cleared, 2), max_abs_difference=worst)
+        print(json.dumps(res["index_add"]), flush=True)
+    with open(a.embeddings_out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "finetune_bench.json"))
     ap.add_argument("--mixed-out", default=os.path.join(ROOT, "profiles", "finetune_mixed_bench.json"))
+    ap.add_argument("--train-embeddings", action="store_true")
+    ap.add_argument("--embeddings-out", default=os.path.join(ROOT, "profiles", "finetune_embeddings_bench.json"))
     a = ap.parse_args()
+    if a.train_embeddings:
+        return embeddings_bench(a)
     r = np.random.Generator(np.random.PCG64(0))
     mixed = {"device": torch.cuda.get_device_name(0), "precision": "bf16", "compute_dtype": "bfloat16", "steps": a.steps, "warmup": a.warmup,
              "visualbert": {}, "layoutlm": {}}

@@ -83,6 +83,13 @@ class vk_adamw_tensor(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+VK_EMBED_MAX_TABLES = 12
+
+
+class vk_embed_tables(C.Structure):
+    _fields_ = [("table", C.c_void_p * VK_EMBED_MAX_TABLES), ("rows", C.c_int32 * VK_EMBED_MAX_TABLES), ("count", C.c_int32)]
+
+
 class vk_ignorey(C.Structure):
     _fields_ = [("bands", C.c_void_p), ("counts", C.c_void_p), ("max_per_image", C.c_int32), ("f64", C.c_int32)]
 
@@ -172,6 +179,10 @@ SIGNATURES = {
     "vk_scatter_rows_f32": (_I, [_P, C.c_long, _P, _I, _P, C.c_long, _I, _I, _P]),
     "vk_grad_clip_workspace_bytes": (_SZ, [_I]),
     "vk_grad_clip": (_I, [_P, _I, C.c_int64, _D, _P, _P, _SZ, _P]),
+    "vk_index_add_rows_workspace_bytes": (_SZ, [C.c_long, C.c_long, _I]),
+    "vk_index_add_rows_check": (_I, [_P, C.c_long, C.c_long, _P, _P, C.c_long, _P, C.c_long, C.c_long, _I, _I, _P, _SZ]),
+    "vk_index_add_rows": (_I, [_P, C.c_long, C.c_long, _P, _P, C.c_long, _P, C.c_long, C.c_long, _I, _I, _P, _SZ, _P]),
+    "vk_embed_sum_f32": (_I, [C.POINTER(vk_embed_tables), _P, C.c_long, _I, _P, C.c_long, _P, _P, C.c_long, C.c_long, _P]),
     "vk_attention_grad_workspace_bytes": (_SZ, [_I, _I, _I]),
     "vk_attention_grad_check": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 5 + [_P, _SZ]),
     "vk_attention_grad": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 5 + [_P, _SZ, _P]),

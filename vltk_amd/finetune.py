@@ -5,9 +5,9 @@ clip_grad_norm_(params, config.train.max_norm); optim.step(); scheduler.step()` 
 features.  `EncoderTrainer` is that recipe: the first `L - n` layers run the encoder's own forward in its own precision, the last
 `n` layers and the head run in fp32 with every activation the backward needs kept, and are walked backwards.
 
-Forward, loss, backward, clipping and the optimiser step are kernels of csrc/train.hip and csrc/attention_grad.hip
-(`vk_gemm_f32`, `vk_attention` in fp32, `vk_attention_grad`, `vk_layernorm`, `vk_layernorm_grad`, `vk_act_f32`, `vk_act_grad_f32`,
-`vk_col_sums`, `vk_add_f32` for the residuals, `vk_scatter_rows_f32`, `vk_cross_entropy(_grad)`, `vk_grad_clip`, `vk_adamw_step`)
+Forward, loss, backward, clipping and the optimiser step are kernels of csrc/train.hip, csrc/attention_grad.hip and
+csrc/index_add.hip (`vk_gemm_f32`, `vk_attention` in fp32, `vk_attention_grad`, `vk_layernorm`, `vk_layernorm_grad`, `vk_act_f32`, `vk_act_grad_f32`,
+`vk_col_sums`, `vk_add_f32` for the residuals, `vk_scatter_rows_f32`, `vk_embed_sum_f32`, `vk_index_add_rows`, `vk_cross_entropy(_grad)`, `vk_grad_clip`, `vk_adamw_step`)
 through the op wrappers of train.py.  All arithmetic runs in `libvltk_hip.so`; torch owns the device buffers and makes the one
 cast there is, at the boundary: the frozen layers' 16-bit hidden state to fp32, which is exact.  No CPU fallback.
 
@@ -27,8 +27,16 @@ use in the mixed mode), the GEMM entry, and whether a product is written in 16 b
 attention reads).  The weight a product reads comes from `self._w`: the fp32 master, or its 16-bit copy that `_cast_weights`
 refreshes at the start of a step.  The attention wrappers pick their entry from the dtype of what they are given.
 
-Out of scope: dropout, HIP-graph capture of a step, training the embeddings, ViT (pre-LN layers) and LXMERT (cross-attention top
-layers), running the top layer only on the rows the head reads (for `train_layers=1` the FFN is needed on B rows, not B * L:
+`train_embeddings=True` is the reference script's own setting, every parameter to AdamW: with all layers trained, the tables, the
+embedding LayerNorm and VisualBERT's `visual_projection` join the trained set.  The stage runs in fp32 in both modes (only the
+projection, a Linear, follows `Precision`): index columns built with torch on the device, `vk_embed_sum_f32` per modality (the sum
+in transformers' order of `+`), `vk_layernorm` with the sum kept; backwards `vk_layernorm_grad`, then one `vk_index_add_rows` per
+table over the gradient of the sum (csrc/index_add.hip: a stable radix sort by table row and a segmented fp64 sum, no atomics, the
+same bits on every run).  VisualBERT's text and visual rows are picked out of the joint sequence by the
+kernel's `src_row`; LayoutLM's x table takes `left` and `right`, its y table `upper` and `lower`, as two index columns of one launch.
+
+Out of scope: dropout, HIP-graph capture of a step, `image_text_alignment` under `train_embeddings` (a weighted lookup), sparse
+(row-wise) AdamW, 16-bit tables, ViT (pre-LN layers) and LXMERT (cross-attention top layers), running the top layer only on the rows the head reads (for `train_layers=1` the FFN is needed on B rows, not B * L:
 measure first, then build it as its own change), fp16 as the compute type (its gradients need loss scaling) and producers that
 write both precisions at once (the cast passes are measured first).
 """
@@ -36,9 +44,10 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .bert_ops import LN_EPS, bert_layer_spec, to_numpy
+from .bert_ops import LN_EPS, additive_mask, bert_layer_spec, to_numpy
 from .train import (Precision, _Trainer, act_f32, act_grad_f32, add_f32, attention, attention_grad, cast_16, check_scatter_index,
-                    gather_rows_f32, gemm_f32, grad_clip, layernorm_f32, layernorm_grad, linear_backward, loss_and_grad, scatter_rows_f32)
+                    embed_sum_f32, gather_rows_f32, gemm_f32, grad_clip, index_add_rows, layernorm_f32, layernorm_grad, linear_backward,
+                    loss_and_grad, scatter_rows_f32)
 
 
 # ---- what is trained ---------------------------------------------------------------------------------------------------------------------
@@ -73,6 +82,19 @@ def _check_compute_dtype(compute_dtype, cfg):
     return compute_dtype
 
 
+# transformers' `pad_token_id` of `VisualBertConfig` and `LayoutLMConfig`, where the model's config dict names none: the word
+# table's `padding_idx`
+DEFAULT_PAD_TOKEN_ID = {"visual_bert.": 1, "layoutlm.": 0}
+
+
+def _embedding_spec(enc_prefix, cfg):
+    """(key, shape) of the embedding stage's tensors under transformers' names, in the state dict's order."""
+    from .layoutlm import layoutlm_param_spec
+    from .visualbert import visualbert_param_spec
+    spec = (visualbert_param_spec if enc_prefix == "visual_bert." else layoutlm_param_spec)(cfg)
+    return [(enc_prefix + k, shp) for k, shp in spec if k.startswith("embeddings.")]
+
+
 # the weight matrices of a trained layer that the mixed mode keeps a 16-bit copy of (the packed [3H, H] QKV master beside them)
 _LAYER_MATRICES = (".attention.output.dense.weight", ".intermediate.dense.weight", ".output.dense.weight")
 
@@ -96,10 +118,19 @@ class EncoderTrainer(_Trainer):
     64 and hidden / intermediate sizes that are multiples of 8; `torch.float16` and every other dtype are refused (ValueError).
     It is independent of the model's own precision.  `compute_dtype` (read-only) tells the mode; `None` is the fp32 trainer.
 
+    `train_embeddings=True` (needs `train_layers == num_hidden_layers`, else ValueError) also trains the embedding stage:
+    VisualBERT's word, position, token-type, visual token-type and visual position tables, `visual_projection` and
+    `embeddings.LayerNorm`; LayoutLM's word, position, x, y, h, w and token-type tables and `embeddings.LayerNorm`, under
+    transformers' key names, which `state_dict` must hold in their shapes.  The word table's `padding_idx` row takes no gradient
+    (weight decay still moves it, as in torch): it is the config's `pad_token_id`, by default transformers' own, 1 for
+    `VisualBertConfig` and 0 for `LayoutLMConfig`.  `image_text_alignment` in a step is then refused (ValueError).  `commit()` also
+    writes the tables (one rounding to the storage type), the projection and the LayerNorm back.  The default, `False`, is the
+    trainer as before, launch for launch.
+
     The model keeps answering with the weights it was loaded with until `commit()`.  Out of scope: see the module docstring."""
 
     def __init__(self, model, state_dict, train_layers=1, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, no_decay=(),
-                 schedule=None, max_grad_norm=None, compute_dtype=None):
+                 schedule=None, max_grad_norm=None, compute_dtype=None, train_embeddings=False):
         self._need_gpu()
         self.enc, self.enc_prefix, self.head, self.pooled = _describe(model)
         self.model = model
@@ -114,11 +145,21 @@ class EncoderTrainer(_Trainer):
         head_keys = (self.head + ".weight", self.head + ".bias")
         if any(k not in getattr(enc, "_head", {}) for k in head_keys):
             raise RuntimeError(f"{type(model).__name__}: load_state_dict() first (no head tensor {head_keys[0]})")
+        self.train_embeddings = bool(train_embeddings)
+        if self.train_embeddings and n != nl:
+            raise ValueError(f"train_embeddings=True needs every layer trained: train_layers must be {nl} (num_hidden_layers), got {train_layers}")
         self.train_layers, self.first = n, nl - n
         H, I = cfg["hidden_size"], cfg["intermediate_size"]
         self.H, self.heads = H, cfg["num_attention_heads"]
         self.ln_eps = cfg.get("layer_norm_eps", LN_EPS)
         spec = []
+        if self.train_embeddings:
+            spec += _embedding_spec(self.enc_prefix, cfg)
+            self._emb = self.enc_prefix + "embeddings."
+            self._tables = tuple(k[len(self._emb):-len(".weight")] for k, _ in spec if k.endswith("_embeddings.weight"))
+            self.pad_token_id = int(cfg.get("pad_token_id", DEFAULT_PAD_TOKEN_ID[self.enc_prefix]))
+            if self._compute_dtype is not None and cfg.get("visual_embedding_dim", 8) % 8:
+                raise ValueError(f"compute_dtype=torch.bfloat16: visual_embedding_dim {cfg['visual_embedding_dim']} must be a multiple of 8")
         for i in range(self.first, nl):
             spec += bert_layer_spec(f"{self.enc_prefix}encoder.layer.{i}", H, I)
         if self.pooled:
@@ -158,6 +199,8 @@ class EncoderTrainer(_Trainer):
         self._prec = Precision(self._compute_dtype)
         self._masters = {lay["prefix"] + t: lay["qkv_weight"] if t == ".qkv" else p[lay["prefix"] + t]
                          for lay in self._layers for t in (".qkv",) + _LAYER_MATRICES}
+        if self.train_embeddings and not self.pooled:
+            self._masters[self._emb + "visual_projection.weight"] = p[self._emb + "visual_projection.weight"]
         self._w = self._masters if self._compute_dtype is None else {k: torch.empty_like(t, dtype=self._compute_dtype)
                                                                      for k, t in self._masters.items()}
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
@@ -226,6 +269,73 @@ class EncoderTrainer(_Trainer):
         dx = linear_backward(dqkv, kept["x"], w[P + ".qkv"], lay["g_qkv_weight"], lay["g_qkv_bias"], need_dx, prec=pr)
         return add_f32(dx, dt1, out=dx) if need_dx else None             # dX = dQKV . Wqkv + the residual path
 
+    # ---- the embedding stage (train_embeddings): fp32 tables, sums and LayerNorm; only visual_projection follows self._prec -----------
+    def _embed_columns(self, inputs, B):
+        """The int32 index columns of a step, built with torch on the device -> (forward, backward, mask, visual): `forward` lists
+        (table names, their index columns, the rows of the joint sequence they fill or None for all); `backward` lists (table name,
+        its indices, the rows of the sequence they read or None); `visual`: (the visual features [B * V, D] fp32, their rows)."""
+        dev = self.device
+
+        def col(t, shape, fill=0):
+            return (torch.full(shape, fill, dtype=torch.int32, device=dev) if t is None else t.to(dev).to(torch.int32)).reshape(-1).contiguous()
+
+        Lt = inputs[0].shape[1]
+        ids, pos = col(inputs[0], None), torch.arange(Lt, dtype=torch.int32, device=dev).repeat(B)
+        if self.pooled:                                                  # LayoutLMEmbeddings.forward: the nine terms in its order
+            _, bbox, attention_mask, token_type_ids = inputs
+            box = col(bbox, (B, Lt, 4)).view(-1, 4)
+            left, upper, right, lower = (box[:, i].contiguous() for i in range(4))
+            cols = dict(word_embeddings=ids, position_embeddings=pos, x_position_embeddings=torch.cat((left, right)),
+                        y_position_embeddings=torch.cat((upper, lower)), h_position_embeddings=lower - upper,
+                        w_position_embeddings=right - left, token_type_embeddings=col(token_type_ids, (B, Lt)))
+            order = (("word_embeddings", ids), ("position_embeddings", pos), ("x_position_embeddings", left), ("y_position_embeddings", upper),
+                     ("x_position_embeddings", right), ("y_position_embeddings", lower), ("h_position_embeddings", cols["h_position_embeddings"]),
+                     ("w_position_embeddings", cols["w_position_embeddings"]), ("token_type_embeddings", cols["token_type_embeddings"]))
+            twice = torch.arange(B * Lt, dtype=torch.int32, device=dev).repeat(2)           # one token, two rows of the x / y table
+            backward = [(t, c, twice if c.numel() == 2 * B * Lt else None) for t, c in cols.items()]
+            return [(order, None)], backward, additive_mask(attention_mask, dev), None
+        _, visual_embeds, attention_mask, visual_attention_mask, token_type_ids, visual_token_type_ids, _ = inputs
+        V = visual_embeds.shape[1]
+        first = torch.arange(B, dtype=torch.int32, device=dev)[:, None] * (Lt + V)
+        text_rows = (first + torch.arange(Lt, dtype=torch.int32, device=dev)).reshape(-1).contiguous()
+        vis_rows = (first + Lt + torch.arange(V, dtype=torch.int32, device=dev)).reshape(-1).contiguous()
+        # VisualBertEmbeddings.forward: word + token type + position; projection + visual position (id 0) + visual token type (1)
+        text = (("word_embeddings", ids), ("token_type_embeddings", col(token_type_ids, (B, Lt))), ("position_embeddings", pos))
+        vis = (("visual_position_embeddings", col(None, (B, V))), ("visual_token_type_embeddings", col(visual_token_type_ids, (B, V), 1)))
+        am = torch.ones((B, Lt), device=dev) if attention_mask is None else attention_mask.to(dev, torch.float32)
+        vm = torch.ones((B, V), device=dev) if visual_attention_mask is None else visual_attention_mask.to(dev, torch.float32)
+        backward = [(t, c, text_rows) for t, c in text] + [(t, c, vis_rows) for t, c in vis]
+        vf = visual_embeds.to(dev, torch.float32).reshape(B * V, -1).contiguous()
+        return [(text, text_rows), (vis, vis_rows)], backward, additive_mask(torch.cat((am, vm), dim=1), dev), (vf, vis_rows)
+
+    def _embed_forward(self, inputs, B, Lx):
+        """-> (the LayerNormed embeddings [B * Lx, H] fp32, the additive mask, what `_embed_backward` reads again)."""
+        E, p, pr = self._emb, self.p, self._prec
+        forward, backward, mask, visual = self._embed_columns(inputs, B)
+        pre = torch.empty((B * Lx, self.H), dtype=torch.float32, device=self.device)
+        kept = {"pre": pre, "backward": backward}
+        for terms, rows in forward:
+            base = None
+            if rows is not None and rows is visual[1]:                   # the visual rows start from their projection, a Linear
+                kept["vf"], kept["vis_rows"] = pr.operand(visual[0]), rows
+                base = pr.gemm(kept["vf"], self._w[E + "visual_projection.weight"], p[E + "visual_projection.bias"], trans_b=True)
+            embed_sum_f32([p[E + t + ".weight"] for t, _ in terms], torch.stack([c for _, c in terms]), base=base, out=pre, out_row=rows)
+        return layernorm_f32(pre, p[E + "LayerNorm.weight"], p[E + "LayerNorm.bias"], self.ln_eps), mask, kept
+
+    def _embed_backward(self, kept, dy):
+        """The gradients of the embedding LayerNorm, of every table (one deterministic index-add over `dsum` each; the word
+        table's `padding_idx` row stays zero) and of `visual_projection`, from the gradient `dy` of the stage's output."""
+        E, p, g = self._emb, self.p, self.g
+        dsum, _, _ = layernorm_grad(kept["pre"], p[E + "LayerNorm.weight"], dy, self.ln_eps, dgamma=g[E + "LayerNorm.weight"],
+                                    dbeta=g[E + "LayerNorm.bias"])
+        for t, idx, rows in kept["backward"]:
+            out = g[E + t + ".weight"]
+            index_add_rows(dsum, idx, out.shape[0], rows, self.pad_token_id if t == "word_embeddings" else -1, out=out)
+        if "vf" in kept:
+            k = E + "visual_projection"
+            linear_backward(gather_rows_f32(dsum, kept["vis_rows"]), kept["vf"], None, g[k + ".weight"], g[k + ".bias"], need_dx=False,
+                            prec=self._prec)
+
     # ---- one step ---------------------------------------------------------------------------------------------------------------------------
     def _inputs(self, model_inputs, options):
         names = self.enc._INPUTS
@@ -254,10 +364,16 @@ class EncoderTrainer(_Trainer):
         Lx = inputs[0].shape[1] + (0 if self.pooled else inputs[1].shape[1])
         idx = torch.from_numpy(self._head_rows(inputs, B, Lx)).to(dev)
         labels_dev = torch.from_numpy(lab).to(dev)
-        x, mask = enc._hidden_after(self.first, *inputs)
-        x = x.to(torch.float32).contiguous()                             # the boundary hidden state
+        if self.train_embeddings and not self.pooled and inputs[6] is not None:
+            raise ValueError("image_text_alignment with train_embeddings=True: the mean over aligned positions is a weighted lookup, "
+                             "whose backward is not built")
+        if not self.train_embeddings:
+            x, mask = enc._hidden_after(self.first, *inputs)
+            x = x.to(torch.float32).contiguous()                         # the boundary hidden state
         if self._compute_dtype is not None:
             self._cast_weights()
+        if self.train_embeddings:
+            x, mask, emb = self._embed_forward(inputs, B, Lx)
         kept = []
         for lay in self._layers:
             x, act = self._layer_forward(lay, x, mask, B, Lx)
@@ -280,7 +396,9 @@ class EncoderTrainer(_Trainer):
         dy = scatter_rows_f32(drows, idx, B * Lx)
         # backward: layers, top down
         for j in range(len(self._layers) - 1, -1, -1):
-            dy = self._layer_backward(self._layers[j], kept[j], dy, mask, B, Lx, need_dx=j > 0)
+            dy = self._layer_backward(self._layers[j], kept[j], dy, mask, B, Lx, need_dx=j > 0 or self.train_embeddings)
+        if self.train_embeddings:
+            self._embed_backward(emb, dy)
         if self.max_grad_norm is not None:
             grad_clip(self._table, len(self.keys), self._max_n, self.max_grad_norm, self._norm_coef, self._clip_work)
         self._adamw()
@@ -300,4 +418,10 @@ class EncoderTrainer(_Trainer):
         if self.pooled:
             lins.append(("pooler.dense", self.enc_prefix + "pooler.dense"))
         lins.append((self.head, self.head))
+        if self.train_embeddings:                                        # the tables: one rounding to the storage type, on the device
+            for t in self._tables:
+                self.enc._tab[t].copy_(self.p[self._emb + t + ".weight"])
+            lns.append(("embeddings.LayerNorm", self._emb + "LayerNorm"))
+            if not self.pooled:
+                lins.append(("embeddings.visual_projection", self._emb + "visual_projection"))
         return self._commit(lins, lns, (self.head + ".weight", self.head + ".bias"))

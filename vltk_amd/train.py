@@ -241,6 +241,42 @@ def scatter_rows_f32(src, idx_dev, M):
     return dst
 
 
+def index_add_rows(src, idx, R, src_row=None, padding_idx=-1, out=None):
+    """The backward of a row lookup: out [R, C] with row r = the sum of the rows `src[src_row[i]]` (`src[i]` without `src_row`)
+    over the entries i with `idx[i] == r`, zeros for `padding_idx` and for every row no entry names (`vk_index_add_rows`:
+    deterministic, fp64 sums in entry order, no atomics).  `src [M, C]` fp32; `idx`, `src_row`: int32 [n] on the device."""
+    M, Cn = src.shape
+    n = idx.numel()
+    out = torch.empty((R, Cn), dtype=torch.float32, device=src.device) if out is None else out
+    assert src.dtype == out.dtype == torch.float32 and src.stride(1) == 1 and out.stride(1) == 1 and tuple(out.shape) == (R, Cn)
+    for t in (idx, src_row):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n)
+    nbytes = L.load().vk_index_add_rows_workspace_bytes(n, R, Cn)
+    work = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=src.device)
+    L.call("vk_index_add_rows", src.data_ptr(), src.stride(0), M, idx.data_ptr(), _ptr(src_row), n, out.data_ptr(), out.stride(0), R, Cn,
+           int(padding_idx), work.data_ptr(), nbytes, stream(src.device))
+    return out
+
+
+def embed_sum_f32(tables, idx, base=None, out=None, out_row=None):
+    """out[out_row[m]] (row m without `out_row`) = (base[m] +) tables[0][idx[0, m]] + tables[1][idx[1, m]] + ..: fp32 adds, left to
+    right (`vk_embed_sum_f32`).  `tables`: contiguous fp32 [rows_t, C]; `idx`: int32 [len(tables), M] on the device; `out`: a new
+    [M, C] tensor, or the rows of a joint sequence that `out_row` (int32 [M]) names."""
+    T, M = idx.shape
+    Cn = tables[0].shape[1]
+    assert T == len(tables) <= L.VK_EMBED_MAX_TABLES and idx.dtype == torch.int32 and idx.is_contiguous()
+    out = torch.empty((M, Cn), dtype=torch.float32, device=idx.device) if out is None else out
+    arg = L.vk_embed_tables()
+    for t, tab in enumerate(tables):
+        assert tab.dtype == torch.float32 and tab.is_contiguous() and tab.shape[1] == Cn
+        arg.table[t], arg.rows[t] = tab.data_ptr(), tab.shape[0]
+    arg.count = T
+    assert out.dtype == torch.float32 and out.stride(1) == 1 and (base is None or (base.dtype == torch.float32 and base.stride(1) == 1))
+    L.call("vk_embed_sum_f32", arg, idx.data_ptr(), M, Cn, _ptr(base), 0 if base is None else base.stride(0), _ptr(out_row), out.data_ptr(),
+           out.stride(0), out.shape[0], stream(idx.device))
+    return out
+
+
 def grad_clip(table, count, max_n, max_norm, norm_coef, work):
     """`clip_grad_norm_` over the table's gradients; `norm_coef` (fp32 [2], device) receives the total norm and the coefficient."""
     L.call("vk_grad_clip", table.data_ptr(), count, max_n, float(max_norm), norm_coef.data_ptr(), work.data_ptr(),
