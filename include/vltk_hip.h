@@ -771,6 +771,39 @@ int vk_attention_grad_16(const void *q, long ldq, const void *k, long ldk, const
                          const void *dout, long lddo, float *dq, long lddq, float *dk, long lddk, float *dv, long lddv, int B, int heads,
                          int Lq, int Lk, int d, vk_dtype dt, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- dropout for the trainers (csrc/philox.h states the mask) ----
+ * A decision is a pure function of (seed, drop_stream, granule, byte) through Philox4x32-10 with key (seed_lo, seed_hi) and counter
+ * (granule_lo, granule_hi, stream_lo, stream_hi); byte i of a call is bits 8 (i & 3).. of output word i >> 2.  With
+ * t = lrintf(p * 256) an element is kept iff its byte >= t and a survivor is scaled by rs = 256.0f / (256 - t): the rate in effect is
+ * t / 256.  Every entry refuses p < 0, p >= 1, NaN and a t above 255 (VK_EINVAL).  The same (input, seed, drop_stream) gives the
+ * same bits whatever the launch geometry; p = 0 gives the bits of the entry without dropout. */
+/* out = (keep ? x * rs : 0) + residual over n dense fp32 elements (element i: byte i & 15 of granule i >> 4), one rounding per
+ * product and one per sum; residual NULL: no add, which is also the backward of the site, dy -> keep ? dy * rs : 0.  out may be x
+ * or residual.  16-byte accesses and one Philox call per 16 elements where x, residual and out are 16-byte aligned; the rest of n
+ * behind the last 1024, and ALL of n at any other 4-byte alignment, take a slow path: element accesses and a Philox call per
+ * element (16 times the generator work). */
+int vk_dropout_add_f32(const float *x, const float *residual, float *out, long n, float p, uint64_t seed, uint64_t drop_stream,
+                       void *stream);
+/* vk_attention_tiled with transformers' dropout(softmax(s)): element (b, h, q, k) of the probabilities is byte 4 (q & 3) + (k & 3) of
+ * granule ((b heads + h) ceil(Lq / 4) + (q >> 2)) ceil(Lk / 4) + (k >> 2).  The row maximum and sum run over the undropped
+ * exp(s - m); a dropped probability is zeroed before the rounding to dt and rs is applied once, in O rs / l.  Only the tiled
+ * matrix-core kernel has the form: arguments the rule routes elsewhere (fp32, another head dim, unaligned rows) are refused. */
+int vk_attention_tiled_dropout(const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, const float *mask, void *out, int ldo,
+                               int B, int heads, int Lq, int Lk, int d, vk_dtype dt, void *stream, float p, uint64_t seed,
+                               uint64_t drop_stream);
+/* Its backward, vk_attention_grad_16 under the same (p, seed, drop_stream), o being the dropped forward's output: D = sum_c dout o
+ * unchanged, dP~ = keep ? rs dP : 0, dS = P (dP~ - D) from the undropped P, dv = P~^T dout with P~ = keep ? rs P : 0 rounded to dt.
+ * The size function and the check are vk_attention_grad_16's, the check also refusing p. */
+size_t vk_attention_grad_16_dropout_workspace_bytes(int B, int heads, int Lq);
+int vk_attention_grad_16_dropout_check(const void *q, long ldq, const void *k, long ldk, const void *v, long ldv, const float *mask,
+                                       const void *o, long ldo, const void *dout, long lddo, const float *dq, long lddq, const float *dk,
+                                       long lddk, const float *dv, long lddv, int B, int heads, int Lq, int Lk, int d, vk_dtype dt,
+                                       const void *workspace, size_t workspace_bytes, float p);
+int vk_attention_grad_16_dropout(const void *q, long ldq, const void *k, long ldk, const void *v, long ldv, const float *mask, const void *o,
+                                 long ldo, const void *dout, long lddo, float *dq, long lddq, float *dk, long lddk, float *dv, long lddv,
+                                 int B, int heads, int Lq, int Lk, int d, vk_dtype dt, void *workspace, size_t workspace_bytes, void *stream,
+                                 float p, uint64_t seed, uint64_t drop_stream);
+
 /* ---- N4: FPN-side ops (what north_star names; the reference holds only fragments, see oracle/fpn_oracle.py) ---- */
 
 /* RoIAlign over a feature pyramid (torchvision roi_align semantics, `aligned` as detectron2's ROIAlignV2; the level loop of

@@ -19,13 +19,22 @@ two kernels in the latter; `vk_index_add_rows` alone at the word table's shape o
 at the position table's (every id B times, R = 512), beside `torch.Tensor.index_add_` on the same data (atomic, not reproducible;
 with and without the clear of its destination, which `vk_index_add_rows` includes) and a plain copy of n * C floats.
 
+`--dropout` measures dropout and writes `--dropout-out` alone: a mixed-mode step with 12 trained layers at
+B = 64 / 256 / 1024, and LayoutLM at 512 tokens (B = 32), at rates 0 / 0 and 0.1 / 0.1; with `--parent-lib` (another build's library,
+the parent commit's) the 0 / 0 step once more in a child process that loads it through VLTK_AMD_LIB, in the same job; then, by device
+events, taking the smaller of two alternating rounds: `vk_attention_tiled` and `vk_attention_grad_16` (its two kernels together)
+beside their `_dropout` forms at (B, heads, L, d) = (1024, 12, 56, 64) and (32, 12, 512, 64), and `vk_dropout_add_f32` beside
+`vk_add_f32` on B * L * 768 floats.
+
     python tools/finetune_bench.py [--steps 10] [--warmup 3] [--out profiles/finetune_bench.json]
                                    [--mixed-out profiles/finetune_mixed_bench.json]
     python tools/finetune_bench.py --train-embeddings [--embeddings-out profiles/finetune_embeddings_bench.json]
+    python tools/finetune_bench.py --dropout [--parent-lib OTHER/libvltk_hip.so] [--dropout-out profiles/finetune_dropout_bench.json]
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -167,6 +176,78 @@ def embeddings_bench(a):
         f.write("\n")
 
 
+def dropout_steps(a, rates):
+    """ms per mixed-mode step with every layer trained at the rates (hidden, attention) -> {case: ms}."""
+    r = np.random.Generator(np.random.PCG64(0))
+    out = {}
+    kw = dict(max_grad_norm=5.0, compute_dtype=torch.bfloat16)
+    if any(rates):
+        kw.update(hidden_dropout=rates[0], attention_dropout=rates[1], seed=1)
+    cfg, labels_n, Lt, V = visualbert_config(visual_embedding_dim=2048), 3129, 20, 36
+    sd = make_visualbert_qa_state_dict(cfg, labels_n, seed=0)
+    model = VisualBertForQuestionAnswering(cfg, labels_n, precision="bf16").load_state_dict(sd)
+    for B in (64, 256, 1024):
+        ids = torch.from_numpy(r.integers(1, cfg["vocab_size"], (B, Lt)))
+        feats = torch.from_numpy(np.maximum(r.standard_normal((B, V, 2048)), 0).astype(np.float32)).cuda()
+        am, labels = torch.ones((B, Lt), dtype=torch.int64), r.integers(0, labels_n, B).astype(np.int64)
+        tr = EncoderTrainer(model, sd, train_layers=12, **kw)
+        out[f"visualbert B{B}"] = round(ms_per_step(lambda: tr.step(ids, feats, labels=labels, attention_mask=am), a.warmup, a.steps), 3)
+        del tr
+        torch.cuda.empty_cache()
+    del model, sd
+    cfg = layoutlm_config()
+    sd = make_layoutlm_head_state_dict(cfg, "classifier", 16, seed=0)
+    model = LayoutLMForSequenceClassification(cfg, 16, precision="bf16").load_state_dict(sd)
+    ids, labels = torch.from_numpy(r.integers(1, cfg["vocab_size"], (32, 512))), r.integers(0, 16, 32).astype(np.int64)
+    tr = EncoderTrainer(model, sd, train_layers=12, **kw)
+    out["layoutlm B32 L512"] = round(ms_per_step(lambda: tr.step(ids, labels=labels), a.warmup, a.steps), 3)
+    return out
+
+
+def dropout_kernels(warmup, steps):
+    """Each kernel entry alone, plain beside DROP (rate 0.1) -> {name: {plain_ms, drop_ms, ratio}}: the smaller of two alternating rounds."""
+    from vltk_amd.train import add_f32, attention, attention_grad, dropout_add_f32
+    g = torch.Generator(device="cuda").manual_seed(0)
+    drop, out = (26 / 256, 1, 7), {}
+
+    def pair(name, plain, dropped):
+        t = [min(device_ms(f, warmup, steps) for _ in range(2)) for f in (plain, dropped, plain, dropped)]
+        p, d = min(t[0], t[2]), min(t[1], t[3])
+        out[name] = dict(plain_ms=round(p, 4), drop_ms=round(d, 4), ratio=round(d / p, 3))
+    for B, heads, Lx, d in ((1024, 12, 56, 64), (32, 12, 512, 64)):
+        H = heads * d
+        qkv, ctx, dctx = (torch.randn((B * Lx, w), device="cuda", generator=g).to(torch.bfloat16) for w in (3 * H, H, H))
+        tag = f"B{B} h{heads} L{Lx} d{d}"
+        pair(f"vk_attention_tiled {tag}", lambda: attention(qkv, None, B, Lx, heads), lambda: attention(qkv, None, B, Lx, heads, drop))
+        pair(f"vk_attention_grad_16 {tag}", lambda: attention_grad(qkv, None, ctx, dctx, B, Lx, heads),
+             lambda: attention_grad(qkv, None, ctx, dctx, B, Lx, heads, drop))
+        x, res = (torch.randn((B * Lx, H), device="cuda", generator=g) for _ in range(2))
+        y = torch.empty_like(x)
+        pair(f"vk_add_f32 / vk_dropout_add_f32 n{x.numel()}", lambda: add_f32(x, res, out=y), lambda: dropout_add_f32(x, res, drop, out=y))
+        del qkv, ctx, dctx, x, res, y
+    return out
+
+
+def dropout_bench(a):
+    if a.steps_only:                                                   # the child of --parent-lib: one JSON line
+        return print(json.dumps(dropout_steps(a, (0.0, 0.0))), flush=True)
+    res = {"device": torch.cuda.get_device_name(0), "compute_dtype": "bfloat16", "train_layers": 12, "steps": a.steps, "warmup": a.warmup}
+    res["step_ms_rates_0_0"] = dropout_steps(a, (0.0, 0.0))
+    if a.parent_lib:
+        torch.cuda.empty_cache()
+        child = subprocess.run([sys.executable, os.path.abspath(__file__), "--dropout", "--steps-only", "--steps", str(a.steps), "--warmup", str(a.warmup)],
+                               env=dict(os.environ, VLTK_AMD_LIB=os.path.abspath(a.parent_lib)), check=True, capture_output=True, text=True)
+        res["step_ms_parent_library"] = json.loads(child.stdout.strip().splitlines()[-1])
+    res["step_ms_rates_0.1_0.1"] = dropout_steps(a, (0.1, 0.1))
+    res["step_ms_rates_0_0_again"] = dropout_steps(a, (0.0, 0.0))
+    print(json.dumps(res), flush=True)
+    res["kernels"] = dropout_kernels(a.warmup, max(50, 5 * a.steps))
+    print(json.dumps(res["kernels"]), flush=True)
+    with open(a.dropout_out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
@@ -175,7 +256,13 @@ def main():
     ap.add_argument("--mixed-out", default=os.path.join(ROOT, "profiles", "finetune_mixed_bench.json"))
     ap.add_argument("--train-embeddings", action="store_true")
     ap.add_argument("--embeddings-out", default=os.path.join(ROOT, "profiles", "finetune_embeddings_bench.json"))
+    ap.add_argument("--dropout", action="store_true")
+    ap.add_argument("--dropout-out", default=os.path.join(ROOT, "profiles", "finetune_dropout_bench.json"))
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--steps-only", action="store_true")
     a = ap.parse_args()
+    if a.dropout:
+        return dropout_bench(a)
     if a.train_embeddings:
         return embeddings_bench(a)
     r = np.random.Generator(np.random.PCG64(0))

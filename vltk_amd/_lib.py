@@ -192,6 +192,11 @@ SIGNATURES = {
     "vk_attention_grad_16_workspace_bytes": (_SZ, [_I, _I, _I]),
     "vk_attention_grad_16_check": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 6 + [_P, _SZ]),
     "vk_attention_grad_16": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 6 + [_P, _SZ, _P]),
+    "vk_dropout_add_f32": (_I, [_P, _P, _P, C.c_long, _F, C.c_uint64, C.c_uint64, _P]),
+    "vk_attention_tiled_dropout": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _F, C.c_uint64, C.c_uint64]),
+    "vk_attention_grad_16_dropout_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "vk_attention_grad_16_dropout_check": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 6 + [_P, _SZ, _F]),
+    "vk_attention_grad_16_dropout": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 6 + [_P, _SZ, _P, _F, C.c_uint64, C.c_uint64]),
     "vk_roi_align": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "vk_roi_align_form": (_I, [_I, _I, _I]),
     "vk_assign_levels": (_I, [_P, _I, _I, _I, _I, _F, _I, _P, _P]),
@@ -262,6 +267,8 @@ def load():
                 "(or `make -C vltk_amd/csrc`).  vltk_amd has no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
+            if "dropout" in name and os.environ.get("VLTK_AMD_LIB") and not hasattr(lib, name):
+                continue                            # tools only: an older build in an A/B lacks the dropout entries; calling one raises
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

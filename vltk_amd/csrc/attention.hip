@@ -16,6 +16,7 @@
 // (a masked key scores about finfo.min, which is finite).
 #include <cstdlib>
 
+#include "attention_tiled.h"
 #include "vk_common.h"
 
 namespace vk {
@@ -112,24 +113,7 @@ constexpr size_t LDS_KERNEL_MAX = 160 * 1024;
 //     key blocks in registers and over the 16 lanes of a group with four shuffles; fp32 throughout;
 //   * P (rounded to the storage type, as the reference's own bf16 matmul sees it) and V^T go through a per-wave LDS
 //     image to become the second product's operands; padded keys carry P = 0 and V = 0.
-typedef _Float16 att_h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 att_b8 __attribute__((ext_vector_type(8)));
-typedef float att_f4 __attribute__((ext_vector_type(4)));
-template <typename T>
-struct AttFrag;
-template <>
-struct AttFrag<_Float16> {
-    typedef att_h8 type;
-    static __device__ __forceinline__ att_f4 mma(att_h8 a, att_h8 b, att_f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-template <>
-struct AttFrag<__bf16> {
-    typedef att_b8 type;
-    static __device__ __forceinline__ att_f4 mma(att_b8 a, att_b8 b, att_f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-
 constexpr int ATT_MAXQB = 3, ATT_MAXKB = 4;     // 48 queries, 64 keys
-constexpr int ATT_PP = 72;                      // row pitch (elements) of the P and V^T images: 64 keys + 8 (bank skew)
 
 template <typename T, int D>
 __global__ __launch_bounds__(256) void attention_mfma_kernel(const T *__restrict__ q, int ldq, const T *__restrict__ k, int ldk,
@@ -251,175 +235,6 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const T *__restrict
             }
         }
     }
-}
-
-// The tiled kernel's exponential: v_exp_f32 on x * log2(e).  Its error (about 1e-6 relative at a soft-max's arguments) is far
-// below the rounding of P to a 16-bit type; exp(0) = 1 and exp(-inf) = 0 exactly, and a result below the normal range is 0.
-static __device__ __forceinline__ float tat_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-
-constexpr int TAT_KT = 64;                      // keys per tile (four 16-key score blocks, two 32-key slices of the second product)
-
-// One WAVE per (batch, head, block of QB * 16 queries), four per workgroup; the lane layouts are attention_mfma_kernel's:
-//   * Q fragments of the block stay in registers; a tile's K rows are the B fragments as they lie in memory;
-//   * a score tile leaves a lane with S[q = 4g + e][key = j]: row maximum and row sum reduce over the four key blocks in
-//     registers and over the 16 lanes of a group with four shuffles;
-//   * O's accumulator rows are the same 4g + e, so the rescale factor of a row is already in the lanes that hold it;
-//   * P (rounded to T) and V^T go through a per-wave LDS image; a lane transposes two keys at a time (32-bit LDS writes,
-//     consecutive lanes on consecutive words).  Padded keys carry P = 0 and V = 0.
-// Every wave of a workgroup runs the same number of tiles (idle waves redo the last item and store nothing), so the
-// barriers are uniform.
-template <typename T, int D, int QB>
-__global__ __launch_bounds__(256) void attention_tiled_kernel(const T *__restrict__ q, int ldq, const T *__restrict__ k, int ldk,
-                                                             const T *__restrict__ v, int ldv, const float *__restrict__ mask,
-                                                             T *__restrict__ out, int ldo, int heads, int Lq, int Lk, int nqb, int total,
-                                                             float scale) {
-    typedef typename AttFrag<T>::type frag;
-    constexpr int KD = D / 32, NDB = D / 16, KB = TAT_KT / 16, PER_WAVE = (QB * 16 + D) * ATT_PP;
-    extern __shared__ __attribute__((aligned(16))) unsigned char tat_lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, j = lane & 15;
-    const int item = blockIdx.x * 4 + wave;
-    const bool live = item < total;
-    const int ic = live ? item : total - 1;
-    const int bh = ic / nqb, q0 = (ic - bh * nqb) * (QB * 16);
-    const int b = bh / heads, h = bh - b * heads;
-    T *pt = reinterpret_cast<T *>(tat_lds) + wave * PER_WAVE, *vt = pt + QB * 16 * ATT_PP;
-    unsigned *vt32 = reinterpret_cast<unsigned *>(vt);
-    const frag zf = {};
-
-    frag qf[QB][KD];
-#pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
-        const int r = q0 + qb * 16 + j;
-        const bool ok = r < Lq;
-        const T *src = q + ((long)b * Lq + (ok ? r : 0)) * ldq + h * D + g * 8;
-#pragma unroll
-        for (int ks = 0; ks < KD; ++ks) {
-            const frag t = *reinterpret_cast<const frag *>(src + ks * 32);
-            qf[qb][ks] = ok ? t : zf;
-        }
-    }
-    att_f4 o[QB][NDB];
-    float m[QB][4], l[QB][4];
-#pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) o[qb][db] = att_f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            m[qb][e] = -INFINITY;
-            l[qb][e] = 0.f;
-        }
-    }
-
-    for (int k0 = 0; k0 < Lk; k0 += TAT_KT) {
-        // ---- K fragments straight from memory ----
-        frag kf[KB][KD];
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-            const int r = k0 + kb * 16 + j;
-            const bool ok = r < Lk;
-            const T *src = k + ((long)b * Lk + (ok ? r : 0)) * ldk + h * D + g * 8;
-#pragma unroll
-            for (int ks = 0; ks < KD; ++ks) {
-                const frag t = *reinterpret_cast<const frag *>(src + ks * 32);
-                kf[kb][ks] = ok ? t : zf;
-            }
-        }
-        // ---- V^T image of the tile: vt[d][key]; lane = (key pair, half of the 16-byte chunks of a row) ----
-        {
-            constexpr int CH = D / 8, HALF = CH / 2;
-            const int kp = lane & 31, c0 = (lane >> 5) * HALF;
-            const int key = k0 + 2 * kp;
-#pragma unroll
-            for (int it = 0; it < HALF; ++it) {
-                const int c = c0 + it;
-                frag t0 = zf, t1 = zf;
-                if (key < Lk) t0 = *reinterpret_cast<const frag *>(v + ((long)b * Lk + key) * ldv + h * D + c * 8);
-                if (key + 1 < Lk) t1 = *reinterpret_cast<const frag *>(v + ((long)b * Lk + key + 1) * ldv + h * D + c * 8);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const T lo = t0[e], hi = t1[e];
-                    unsigned short ulo, uhi;
-                    __builtin_memcpy(&ulo, &lo, 2);
-                    __builtin_memcpy(&uhi, &hi, 2);
-                    vt32[((c * 8 + e) * ATT_PP) / 2 + kp] = (unsigned)ulo | ((unsigned)uhi << 16);
-                }
-            }
-        }
-        // ---- S = Q K^T * scale + mask; online soft-max; P image ----
-        float mk[KB];
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-            const int key = k0 + kb * 16 + j;
-            mk[kb] = key < Lk ? (mask ? mask[(long)b * Lk + key] : 0.f) : -INFINITY;
-        }
-#pragma unroll
-        for (int qb = 0; qb < QB; ++qb) {
-            att_f4 sc[KB];
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) {
-                att_f4 a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int ks = 0; ks < KD; ++ks) a = AttFrag<T>::mma(qf[qb][ks], kf[kb][ks], a);
-                const bool ok = k0 + kb * 16 + j < Lk;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a[e] = ok ? a[e] * scale + mk[kb] : -INFINITY;
-                sc[kb] = a;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float mx = sc[0][e];
-#pragma unroll
-                for (int kb = 1; kb < KB; ++kb) mx = fmaxf(mx, sc[kb][e]);
-#pragma unroll
-                for (int s = 8; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-                const float mn = fmaxf(m[qb][e], mx);
-                const float alpha = tat_exp(m[qb][e] - mn);      // first tile: exp(-inf) = 0
-                float sum = 0.f;
-                const int row = qb * 16 + g * 4 + e;
-#pragma unroll
-                for (int kb = 0; kb < KB; ++kb) {
-                    const float p = tat_exp(sc[kb][e] - mn);     // padded keys: exp(-inf) = 0
-                    sum += p;
-                    pt[row * ATT_PP + kb * 16 + j] = (T)p;
-                }
-#pragma unroll
-                for (int s = 8; s > 0; s >>= 1) sum += __shfl_xor(sum, s, 64);
-                m[qb][e] = mn;
-                l[qb][e] = alpha * l[qb][e] + sum;
-#pragma unroll
-                for (int db = 0; db < NDB; ++db) o[qb][db][e] *= alpha;
-            }
-        }
-        __syncthreads();
-        // ---- O += P V: A = P rows (keys contiguous), B = V^T rows (keys contiguous) ----
-        const int nk2 = Lk - k0 > 32 ? 2 : 1;
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-            if (k2 >= nk2) continue;
-            frag pf[QB];
-#pragma unroll
-            for (int qb = 0; qb < QB; ++qb) pf[qb] = *reinterpret_cast<const frag *>(pt + (qb * 16 + j) * ATT_PP + k2 * 32 + g * 8);
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) {
-                const frag vf = *reinterpret_cast<const frag *>(vt + (db * 16 + j) * ATT_PP + k2 * 32 + g * 8);
-#pragma unroll
-                for (int qb = 0; qb < QB; ++qb) o[qb][db] = AttFrag<T>::mma(pf[qb], vf, o[qb][db]);
-            }
-        }
-        __syncthreads();            // the next tile overwrites the images
-    }
-    if (!live) return;
-#pragma unroll
-    for (int qb = 0; qb < QB; ++qb)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int row = q0 + qb * 16 + g * 4 + e;
-            if (row >= Lq) continue;
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) out[((long)b * Lq + row) * ldo + h * D + db * 16 + j] = (T)(o[qb][db][e] / l[qb][e]);
-        }
 }
 
 // ---- the strict form ----
@@ -547,24 +362,6 @@ static int attention_route(int Lq, int Lk, int d, vk_dtype dt, int ldq, int ldk,
     return route;
 }
 
-// The arguments of vk_attention / vk_attention_tiled.
-struct AttArgs {
-    const void *q, *k, *v;
-    const float *mask;
-    void *out;
-    int ldq, ldk, ldv, ldo, B, heads, Lq, Lk, d;
-    vk_dtype dt;
-};
-// the leading arguments every kernel takes, as T
-#define VK_ATT_IO(T) (const T *)a.q, a.ldq, (const T *)a.k, a.ldk, (const T *)a.v, a.ldv, a.mask, (T *)a.out, a.ldo, a.heads, a.Lq, a.Lk
-
-// what both entry points ask of their arguments before the rule sees them (which checks Lq, Lk, d and the dtype)
-static int check_attention_args(const AttArgs &a) {
-    VK_REQUIRE(a.q && a.k && a.v && a.out, VK_EINVAL, "attention: null argument");
-    VK_REQUIRE(a.B > 0 && a.heads > 0, VK_EINVAL, "attention: bad geometry (B=%d heads=%d)", a.B, a.heads);
-    return VK_OK;
-}
-
 static int route_of(const AttArgs &a, int tiled_entry) {
     const int aligned = ((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 16 == 0;
     return attention_route(a.Lq, a.Lk, a.d, a.dt, a.ldq, a.ldk, a.ldv, aligned, tiled_entry);
@@ -581,17 +378,6 @@ static int mfma_launch(const AttArgs &a, float scale, hipStream_t s) {
     const int total = a.B * a.heads;
     hipLaunchKernelGGL((attention_mfma_kernel<T, D>), dim3((total + 3) / 4), dim3(256), 0, s, VK_ATT_IO(T), total, scale);
     return VK_OK;
-}
-
-template <typename T, int D, int QB>
-static int tiled_launch_qb(const AttArgs &a, float scale, hipStream_t s) {
-    const int nqb = (a.Lq + QB * 16 - 1) / (QB * 16), total = a.B * a.heads * nqb;
-    const size_t smem = (size_t)4 * (QB * 16 + D) * ATT_PP * sizeof(T);
-    return launch_lds(attention_tiled_kernel<T, D, QB>, dim3((total + 3) / 4), dim3(256), smem, smem, s, VK_ATT_IO(T), nqb, total, scale);
-}
-template <typename T, int D>
-static int tiled_launch(const AttArgs &a, float scale, hipStream_t s) {
-    return a.Lq <= 16 ? tiled_launch_qb<T, D, 1>(a, scale, s) : tiled_launch_qb<T, D, 2>(a, scale, s);
 }
 
 template <typename T>

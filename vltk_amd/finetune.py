@@ -35,7 +35,16 @@ table over the gradient of the sum (csrc/index_add.hip: a stable radix sort by t
 same bits on every run).  VisualBERT's text and visual rows are picked out of the joint sequence by the
 kernel's `src_row`; LayoutLM's x table takes `left` and `right`, its y table `upper` and `lower`, as two index columns of one launch.
 
-Out of scope: dropout, HIP-graph capture of a step, `image_text_alignment` under `train_embeddings` (a weighted lookup), sparse
+`hidden_dropout`, `attention_dropout` and `seed` give the step transformers' training-mode dropout, at the
+sites transformers has it: the embedding stage's output (under `train_embeddings`), per trained layer the attention probabilities
+and the outputs of `attention.output.dense` and `output.dense` before their residuals, and the head's input rows.  A decision is
+Philox4x32-10 of (seed, stream = steps * 2^16 + the site's number, granule, byte), regenerated in registers wherever it is needed:
+no mask tensor exists.  A hidden site is `vk_dropout_add_f32` in place of the residual's `vk_add_f32`, and once more, without a
+residual, on the gradient that enters the site's Linear; the attention site is `vk_attention_tiled_dropout` and
+`vk_attention_grad_16_dropout` under one (rate, seed, stream), so it needs the mixed mode.  Both rates 0.0, the default, is the
+trainer without the arguments, launch for launch.  The frozen layers run the model's own eval forward.
+
+Out of scope: dropout on the fp32 attention pair, HIP-graph capture of a step, `image_text_alignment` under `train_embeddings` (a weighted lookup), sparse
 (row-wise) AdamW, 16-bit tables, ViT (pre-LN layers) and LXMERT (cross-attention top layers), running the top layer only on the rows the head reads (for `train_layers=1` the FFN is needed on B rows, not B * L:
 measure first, then build it as its own change), fp16 as the compute type (its gradients need loss scaling) and producers that
 write both precisions at once (the cast passes are measured first).
@@ -46,8 +55,8 @@ import torch
 from . import _lib as L
 from .bert_ops import LN_EPS, additive_mask, bert_layer_spec, to_numpy
 from .train import (Precision, _Trainer, act_f32, act_grad_f32, add_f32, attention, attention_grad, cast_16, check_scatter_index,
-                    embed_sum_f32, gather_rows_f32, gemm_f32, grad_clip, index_add_rows, layernorm_f32, layernorm_grad, linear_backward,
-                    loss_and_grad, scatter_rows_f32)
+                    dropout_add_f32, dropout_rate, embed_sum_f32, gather_rows_f32, gemm_f32, grad_clip, index_add_rows, layernorm_f32,
+                    layernorm_grad, linear_backward, loss_and_grad, scatter_rows_f32)
 
 
 # ---- what is trained ---------------------------------------------------------------------------------------------------------------------
@@ -127,11 +136,27 @@ class EncoderTrainer(_Trainer):
     writes the tables (one rounding to the storage type), the projection and the LayerNorm back.  The default, `False`, is the
     trainer as before, launch for launch.
 
+    `hidden_dropout`, `attention_dropout` (rates in [0, 1), else ValueError) and `seed` (an integer below 2^64): training-mode
+    dropout in the trained part of a step, where transformers has it (the module docstring lists the sites).  A rate p acts as
+    lrintf(p * 256) / 256, which the read-only properties of the same names return.  The mask of a step is a function of (`seed`, the
+    number of steps taken, the site): two trainers with one seed take the same steps, bit for bit.  `attention_dropout > 0` needs
+    `compute_dtype=torch.bfloat16` (ValueError in the fp32 mode); `hidden_dropout` works in both modes.  The frozen layers,
+    `model(...)` and `commit()` know no dropout.  Both rates 0.0: the trainer as before, launch for launch.
+
     The model keeps answering with the weights it was loaded with until `commit()`.  Out of scope: see the module docstring."""
 
     def __init__(self, model, state_dict, train_layers=1, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, no_decay=(),
-                 schedule=None, max_grad_norm=None, compute_dtype=None, train_embeddings=False):
+                 schedule=None, max_grad_norm=None, compute_dtype=None, train_embeddings=False, hidden_dropout=0.0,
+                 attention_dropout=0.0, seed=0):
         self._need_gpu()
+        self._hidden_dropout = dropout_rate(hidden_dropout, "hidden_dropout")
+        self._attention_dropout = dropout_rate(attention_dropout, "attention_dropout")
+        self.seed = int(seed)
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError(f"seed must lie in [0, 2^64), got {seed}")
+        if self._attention_dropout > 0 and compute_dtype is None:
+            raise ValueError("attention_dropout > 0 needs the mixed mode, compute_dtype=torch.bfloat16: the fp32 attention kernels have no "
+                             "dropout form")
         self.enc, self.enc_prefix, self.head, self.pooled = _describe(model)
         self.model = model
         enc, cfg = self.enc, self.enc.cfg
@@ -222,6 +247,34 @@ class EncoderTrainer(_Trainer):
         """None: the fp32 trainer; torch.bfloat16: the mixed-precision mode."""
         return self._compute_dtype
 
+    @property
+    def hidden_dropout(self):
+        """The hidden dropout rate in effect, t / 256."""
+        return self._hidden_dropout
+
+    @property
+    def attention_dropout(self):
+        """The rate in effect on the attention probabilities, t / 256."""
+        return self._attention_dropout
+
+    def _drop(self, site, attention=False):
+        """(rate, seed, stream) of dropout site number `site` in the step being taken, or None where its rate is 0: the sites are
+        0 the embedding output; 1 + 3 i, 2 + 3 i, 3 + 3 i the probabilities, `attention.output.dense` and `output.dense` of trained
+        layer i; 1 + 3 n the head's input rows."""
+        rate = self._attention_dropout if attention else self._hidden_dropout
+        return (rate, self.seed, (self.steps << 16) + site) if rate > 0 else None
+
+    @staticmethod
+    def _residual(t, res, drop):
+        """t <- dropout(t) + res (dropout: the identity without `drop`), in place."""
+        return add_f32(t, res, out=t) if drop is None else dropout_add_f32(t, res, drop, out=t)
+
+    @staticmethod
+    def _undrop(dy, drop):
+        """The gradient that enters a dropout site's producer from the gradient `dy` of its output (a new tensor; `dy` itself is
+        the residual path's)."""
+        return dy if drop is None else dropout_add_f32(dy, None, drop)
+
     def _cast_weights(self):
         """The mixed mode's 16-bit copies of the trained weight matrices from the fp32 masters; the packed QKV master of a layer is
         one cast."""
@@ -229,25 +282,25 @@ class EncoderTrainer(_Trainer):
             cast_16(master, self._compute_dtype, out=self._w[k])
 
     # ---- one post-LN BERT layer (bert_ops.BertOps._bert_layer), activations kept; fp32, or 16-bit operands under self._prec -----------
-    def _layer_forward(self, lay, x, mask, B, Lx):
+    def _layer_forward(self, lay, x, mask, B, Lx, site=1):
         """-> (the layer's output, what the backward reads again).  fp32 mode keeps x, qkv, ctx, t1, a, z, h, t2 in fp32.  The mixed
         mode keeps the 16-bit copies of what only a GEMM or the attention backward reads again (x, qkv, ctx, a, h) and the fp32
         inputs of the fp32 backward kernels (t1, t2, z)."""
         P, p, w, pr = lay["prefix"], self.p, self._w, self._prec
         kept = {"x": pr.operand(x)}
         qkv = kept["qkv"] = pr.gemm(kept["x"], w[P + ".qkv"], lay["qkv_bias"], trans_b=True, out16=True)
-        ctx = kept["ctx"] = attention(qkv, mask, B, Lx, self.heads)
+        ctx = kept["ctx"] = attention(qkv, mask, B, Lx, self.heads, self._drop(site, attention=True))
         t1 = pr.gemm(ctx, w[P + ".attention.output.dense.weight"], p[P + ".attention.output.dense.bias"], trans_b=True)
-        kept["t1"] = add_f32(t1, x, out=t1)                              # the residual, fp32
+        kept["t1"] = self._residual(t1, x, self._drop(site + 1))         # the residual, fp32
         a = layernorm_f32(t1, p[P + ".attention.output.LayerNorm.weight"], p[P + ".attention.output.LayerNorm.bias"], self.ln_eps)
         kept["a"] = pr.operand(a)
         z = kept["z"] = pr.gemm(kept["a"], w[P + ".intermediate.dense.weight"], p[P + ".intermediate.dense.bias"], trans_b=True)
         kept["h"] = pr.operand(act_f32(z, L.VK_ACT_GELU))
         t2 = pr.gemm(kept["h"], w[P + ".output.dense.weight"], p[P + ".output.dense.bias"], trans_b=True)
-        kept["t2"] = add_f32(t2, a, out=t2)
+        kept["t2"] = self._residual(t2, a, self._drop(site + 2))
         return layernorm_f32(t2, p[P + ".output.LayerNorm.weight"], p[P + ".output.LayerNorm.bias"], self.ln_eps), kept
 
-    def _layer_backward(self, lay, kept, dy, mask, B, Lx, need_dx):
+    def _layer_backward(self, lay, kept, dy, mask, B, Lx, need_dx, site=1):
         """The layer walked backwards under the fp32 gradient `dy` of its output -> the gradient of its input, or None for the
         lowest trained layer (`need_dx=False`: nothing below it is trained).  Each Linear is one `linear_backward`: in the mixed
         mode an fp32 gradient is cast once and feeds both of its GEMMs (dW straight into the fp32 gradient buffer, dX in fp32, or
@@ -259,13 +312,13 @@ class EncoderTrainer(_Trainer):
 
         k = P + ".output.LayerNorm"
         dt2, _, _ = layernorm_grad(kept["t2"], p[k + ".weight"], dy, self.ln_eps, dgamma=g[k + ".weight"], dbeta=g[k + ".bias"])
-        dz = act_grad_f32(kept["z"], linear(dt2, kept["h"], P + ".output.dense"), L.VK_ACT_GELU)
+        dz = act_grad_f32(kept["z"], linear(self._undrop(dt2, self._drop(site + 2)), kept["h"], P + ".output.dense"), L.VK_ACT_GELU)
         da = linear(dz, kept["a"], P + ".intermediate.dense")
         add_f32(da, dt2, out=da)                                         # the residual path
         k = P + ".attention.output.LayerNorm"
         dt1, _, _ = layernorm_grad(kept["t1"], p[k + ".weight"], da, self.ln_eps, dgamma=g[k + ".weight"], dbeta=g[k + ".bias"])
-        dctx = linear(dt1, kept["ctx"], P + ".attention.output.dense", dx16=True)
-        dqkv = attention_grad(kept["qkv"], mask, kept["ctx"], dctx, B, Lx, self.heads)
+        dctx = linear(self._undrop(dt1, self._drop(site + 1)), kept["ctx"], P + ".attention.output.dense", dx16=True)
+        dqkv = attention_grad(kept["qkv"], mask, kept["ctx"], dctx, B, Lx, self.heads, self._drop(site, attention=True))
         dx = linear_backward(dqkv, kept["x"], w[P + ".qkv"], lay["g_qkv_weight"], lay["g_qkv_bias"], need_dx, prec=pr)
         return add_f32(dx, dt1, out=dx) if need_dx else None             # dX = dQKV . Wqkv + the residual path
 
@@ -320,12 +373,14 @@ class EncoderTrainer(_Trainer):
                 kept["vf"], kept["vis_rows"] = pr.operand(visual[0]), rows
                 base = pr.gemm(kept["vf"], self._w[E + "visual_projection.weight"], p[E + "visual_projection.bias"], trans_b=True)
             embed_sum_f32([p[E + t + ".weight"] for t, _ in terms], torch.stack([c for _, c in terms]), base=base, out=pre, out_row=rows)
-        return layernorm_f32(pre, p[E + "LayerNorm.weight"], p[E + "LayerNorm.bias"], self.ln_eps), mask, kept
+        x = layernorm_f32(pre, p[E + "LayerNorm.weight"], p[E + "LayerNorm.bias"], self.ln_eps)
+        return self._undrop(x, self._drop(0)), mask, kept              # forward and backward of the site are one function
 
     def _embed_backward(self, kept, dy):
         """The gradients of the embedding LayerNorm, of every table (one deterministic index-add over `dsum` each; the word
         table's `padding_idx` row stays zero) and of `visual_projection`, from the gradient `dy` of the stage's output."""
         E, p, g = self._emb, self.p, self.g
+        dy = self._undrop(dy, self._drop(0))
         dsum, _, _ = layernorm_grad(kept["pre"], p[E + "LayerNorm.weight"], dy, self.ln_eps, dgamma=g[E + "LayerNorm.weight"],
                                     dbeta=g[E + "LayerNorm.bias"])
         for t, idx, rows in kept["backward"]:
@@ -375,8 +430,8 @@ class EncoderTrainer(_Trainer):
         if self.train_embeddings:
             x, mask, emb = self._embed_forward(inputs, B, Lx)
         kept = []
-        for lay in self._layers:
-            x, act = self._layer_forward(lay, x, mask, B, Lx)
+        for i, lay in enumerate(self._layers):
+            x, act = self._layer_forward(lay, x, mask, B, Lx, site=1 + 3 * i)
             kept.append(act)
         # head forward
         kw, kb = self.head + ".weight", self.head + ".bias"
@@ -387,16 +442,18 @@ class EncoderTrainer(_Trainer):
             feats = act_f32(zp, L.VK_ACT_TANH)
         else:
             feats = rows
+        head_drop = self._drop(1 + 3 * len(self._layers))
+        feats = self._undrop(feats, head_drop)                           # the head's input rows, dropped
         logits = gemm_f32(feats, p[kw], p[kb], trans_b=True)
         loss, dlogits = loss_and_grad(logits, labels_dev, counted)
         # backward: head
-        drows = linear_backward(dlogits, feats, p[kw], g[kw], g[kb])
+        drows = self._undrop(linear_backward(dlogits, feats, p[kw], g[kw], g[kb]), head_drop)
         if self.pooled:
             drows = linear_backward(act_grad_f32(zp, drows, L.VK_ACT_TANH), rows, p[pw], g[pw], g[pb])
         dy = scatter_rows_f32(drows, idx, B * Lx)
         # backward: layers, top down
         for j in range(len(self._layers) - 1, -1, -1):
-            dy = self._layer_backward(self._layers[j], kept[j], dy, mask, B, Lx, need_dx=j > 0 or self.train_embeddings)
+            dy = self._layer_backward(self._layers[j], kept[j], dy, mask, B, Lx, need_dx=j > 0 or self.train_embeddings, site=1 + 3 * j)
         if self.train_embeddings:
             self._embed_backward(emb, dy)
         if self.max_grad_norm is not None:

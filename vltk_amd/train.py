@@ -13,8 +13,7 @@ attention, residual, gather / scatter and clipping wrappers of `EncoderTrainer` 
 the `Precision` of a trained layer's products, and `_Trainer`, the base that holds masters, gradients, AdamW's state, the
 schedule and `commit()`'s repacking.
 
-Out of scope: dropout (the heads here have none in eval mode; the dropout transformers' VisualBERT puts before `cls` is omitted),
-gradient clipping, HIP-graph capture of a step, 16-bit training GEMMs, any gradient into an encoder, and the soft-label KL loss of
+Out of scope: dropout in `HeadTrainer` (`EncoderTrainer` has it: finetune.py), gradient clipping, HIP-graph capture of a step, 16-bit training GEMMs, any gradient into an encoder, and the soft-label KL loss of
 transformers' VisualBERT-QA (the reference's script passes hard labels).  Gradient clipping and the gradient into the top
 encoder layers are `EncoderTrainer`'s (finetune.py).
 """
@@ -179,28 +178,56 @@ def packed_qkv(t):
     return ptr, ld, ptr + step, ld, ptr + 2 * step, ld
 
 
-def attention(qkv, mask, B, Lx, heads):
+def dropout_rate(p, name="p"):
+    """The rate in effect for a requested rate `p`: t / 256 with t = lrintf(p * 256), the rule of csrc/philox.h.  ValueError for
+    p < 0, p >= 1, NaN, or a t above 255, which the entry points refuse too."""
+    p = float(p)
+    t = int(np.rint(np.float32(p) * np.float32(256.0))) if 0.0 <= p < 1.0 else 256
+    if t > 255:
+        raise ValueError(f"{name}={p} must lie in [0, 1) and round to at most 255 / 256")
+    return t / 256.0
+
+
+def attention(qkv, mask, B, Lx, heads, drop=None):
     """Self-attention on a packed projection `qkv [B * Lx, 3H]` -> the context rows [B * Lx, H] in its dtype: `vk_attention` in
-    fp32, `vk_attention_tiled` on bf16 / fp16."""
+    fp32, `vk_attention_tiled` on bf16 / fp16.  `drop`: (rate, seed, stream) of dropout on the probabilities,
+    `vk_attention_tiled_dropout` (16-bit only)."""
     H = qkv.shape[1] // 3
     out = torch.empty((B * Lx, H), dtype=qkv.dtype, device=qkv.device)
     entry, dt = ("vk_attention", L.VK_F32) if qkv.dtype == torch.float32 else ("vk_attention_tiled", VK_16[qkv.dtype])
-    L.call(entry, *packed_qkv(qkv), _ptr(mask), out.data_ptr(), H, B, heads, Lx, Lx, H // heads, dt, stream(qkv.device))
+    if drop is not None:
+        assert qkv.dtype != torch.float32
+        entry += "_dropout"
+    L.call(entry, *packed_qkv(qkv), _ptr(mask), out.data_ptr(), H, B, heads, Lx, Lx, H // heads, dt, stream(qkv.device), *(drop or ()))
     return out
 
 
-def attention_grad(qkv, mask, ctx, dctx, B, Lx, heads):
+def attention_grad(qkv, mask, ctx, dctx, B, Lx, heads, drop=None):
     """The backward of `attention` on the packed projection the forward kept, its context rows and their gradient (all of one
-    dtype) -> dqkv [B * Lx, 3H] (dQ | dK | dV) in fp32: `vk_attention_grad` in fp32, `vk_attention_grad_16` on bf16 / fp16."""
+    dtype) -> dqkv [B * Lx, 3H] (dQ | dK | dV) in fp32: `vk_attention_grad` in fp32, `vk_attention_grad_16` on bf16 / fp16.
+    `drop`: the forward's (rate, seed, stream), `vk_attention_grad_16_dropout`."""
     H = qkv.shape[1] // 3
     assert ctx.dtype == dctx.dtype == qkv.dtype
     dqkv = torch.empty(qkv.shape, dtype=torch.float32, device=qkv.device)
     entry, dt = ("vk_attention_grad", ()) if qkv.dtype == torch.float32 else ("vk_attention_grad_16", (VK_16[qkv.dtype],))
+    if drop is not None:
+        assert qkv.dtype != torch.float32
+        entry += "_dropout"
     nbytes = getattr(L.load(), entry + "_workspace_bytes")(B, heads, Lx)
     work = torch.empty((nbytes // 4,), dtype=torch.float32, device=qkv.device)
     L.call(entry, *packed_qkv(qkv), _ptr(mask), ctx.data_ptr(), ctx.stride(0), dctx.data_ptr(), dctx.stride(0), *packed_qkv(dqkv),
-           B, heads, Lx, Lx, H // heads, *dt, work.data_ptr(), nbytes, stream(qkv.device))
+           B, heads, Lx, Lx, H // heads, *dt, work.data_ptr(), nbytes, stream(qkv.device), *(drop or ()))
     return dqkv
+
+
+def dropout_add_f32(x, residual, drop, out=None):
+    """(keep ? x * rs : 0) + residual under `drop` = (rate, seed, stream): `vk_dropout_add_f32`, into `out` (which may be x or the
+    residual) or a new tensor.  `residual=None`: no add, which is also the backward of the site on its output's gradient."""
+    out = torch.empty_like(x) if out is None else out
+    assert x.dtype == torch.float32 and x.is_contiguous() and out.is_contiguous() and out.shape == x.shape
+    assert residual is None or (residual.is_contiguous() and residual.shape == x.shape and residual.dtype == torch.float32)
+    L.call("vk_dropout_add_f32", x.data_ptr(), _ptr(residual), out.data_ptr(), x.numel(), *drop, stream(x.device))
+    return out
 
 
 def add_f32(a, b, out=None):
