@@ -539,6 +539,37 @@ int vk_attention_tiled(const void *q, int ldq, const void *k, int ldk, const voi
 #define VK_ATT_ROUTE_STREAM 3   /* attention_stream_kernel: 64-key fp32 tiles in LDS, online soft-max */
 int vk_attention_route(int Lq, int Lk, int d, vk_dtype dt, int ldq, int ldk, int ldv, int aligned16, int tiled_entry);
 
+/* Attention with LayoutLMv3's relative-position bias formed inside the kernel (transformers modeling_layoutlmv3.py v5.15,
+ * LayoutLMv3Encoder._cal_1d_pos_emb / _cal_2d_pos_emb and LayoutLMv3SelfAttention.forward), never materialised as [B, heads, L, L]:
+ *   O = softmax((Q K^T + bias) / sqrt(d) + mask) V
+ *   bias[b, h, i, j] = T1[h][c1(pk - pq)] + (TX[h][c2(xk - xq)] + TY[h][c2(yk - yq)]),   c_r(t) = clamp(t, -r, r) + r
+ * rel_q [B, Lq, 3] and rel_k [B, Lk, 3] are int32 (pos, x, y) per token (self-attention passes one pointer twice; values within
+ * +- 2^30, so that a difference fits an int32).  lut [heads, (2 r1 + 1) + 2 (2 r2 + 1)] is fp32: T1, TX and TY of a head side by
+ * side, the distance -> bucket -> weight fold done by the host (exact: the bucket is constant from max_distance on; r = max_distance).
+ * A score is (dot + (t1 + (tx + ty))) * scale + mask in fp32.  q, k, v, mask, out and the leading dimensions as vk_attention_tiled.
+ * No atomics: the same input gives the same bits.
+ *
+ * vk_attention_relpos_form: which kernel a launch runs on (host only, touches no device), or the negative of the VK_E* code the
+ * launch would return.  The matrix-core form takes bf16 / f16, d 32 / 64, 16-byte aligned q, k, v and leading dimensions in
+ * multiples of 8, at any Lq, Lk >= 1 (VK_ATTENTION_MFMA=0 takes it out of the choice); the strict fp32 form everything else up to
+ * d = 256.  vk_attention_relpos_queries: the queries a workgroup of that form serves.  Matrix-core form: a wave serves 16 queries
+ * up to Lq = 16 and 32 beyond, and a workgroup, all of whose waves share one (batch, head), has as many waves as cover Lq, four at
+ * the most: 16, 32, 64, 96, and 128 from Lq = 97 on.  Strict form: 16.
+ * vk_attention_relpos_check: what the launch refuses, host only and reading through no pointer: a NULL pointer other than mask,
+ * a size below 1, a radius below 1 or a table past the LDS budget of 8 KiB a head ((2 r1 + 1) + 2 (2 r2 + 1) floats; 128 / 256
+ * takes 5132 bytes), a leading dimension below heads * d, q / k / v / out off their element's alignment or rel_q / rel_k / lut /
+ * mask off 4 bytes, and whatever vk_attention_relpos_form refuses. */
+#define VK_RELPOS_FORM_MFMA 0     /* attention_relpos_kernel: 64-key tiles on the matrix cores, a workgroup per head and query run */
+#define VK_RELPOS_FORM_STRICT 1   /* attention_relpos_strict_kernel: 64-key fp32 tiles in LDS */
+int vk_attention_relpos_form(int Lq, int Lk, int d, vk_dtype dt, int ldq, int ldk, int ldv, int aligned16);
+int vk_attention_relpos_queries(int form, int Lq);
+int vk_attention_relpos_check(const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, const float *mask,
+                              const int32_t *rel_q, const int32_t *rel_k, const float *lut, int r1, int r2, const void *out, int ldo,
+                              int B, int heads, int Lq, int Lk, int d, vk_dtype dt);
+int vk_attention_relpos(const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, const float *mask,
+                        const int32_t *rel_q, const int32_t *rel_k, const float *lut, int r1, int r2, void *out, int ldo, int B,
+                        int heads, int Lq, int Lk, int d, vk_dtype dt, void *stream);
+
 /* VisualBertEmbeddings.forward (transformers modeling_visual_bert.py v5.15 :72-168) for the single-stream encoder: one launch
  * writes y [B * (Lt + V), C], text rows first in each batch entry, with no concatenation in between:
  *   text row   (b, t)       LayerNorm(word[ids[b,t]] + token_type[tt[b,t]] + position[t])

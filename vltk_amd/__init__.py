@@ -34,7 +34,10 @@ def __getattr__(name):
                 "layoutlm_config", "ocr_token_boxes"):       # the document encoder: OCR words and their boxes
         from . import layoutlm
         return getattr(layoutlm, name)
-    if name in ("HeadTrainer", "step_lr", "linear_warmup"):    # N7: train a head over a frozen encoder
+    if name in ("attention_relpos", "attention_relpos_form", "relpos_lut", "relpos_triples"):   # LayoutLMv3's attention: the bias in-kernel
+        from . import layoutlmv3
+        return getattr(layoutlmv3, name)
+    if name in ("HeadTrainer", "step_lr", "linear_warmup"):   # N7: train a head over a frozen encoder
         from . import train
         return getattr(train, name)
     if name == "EncoderTrainer":         # N8: fine-tune the top encoder layers and the head

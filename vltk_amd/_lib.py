@@ -21,6 +21,7 @@ VK_F32, VK_F16, VK_I64, VK_I32, VK_BF16 = 0, 1, 2, 3, 4
 VK_ACT_NONE, VK_ACT_RELU, VK_ACT_GELU, VK_ACT_TANH = 0, 1, 2, 3
 VK_ROUTE_GENERIC, VK_ROUTE_RING, VK_ROUTE_DUO, VK_ROUTE_WS, VK_ROUTE_GEMM4, VK_ROUTE_PANEL, VK_ROUTE_BLK = range(7)
 VK_ATT_ROUTE_MFMA, VK_ATT_ROUTE_LDS, VK_ATT_ROUTE_TILED, VK_ATT_ROUTE_STREAM = range(4)
+VK_RELPOS_FORM_MFMA, VK_RELPOS_FORM_STRICT = 0, 1
 VK_CE_FORM_VEC, VK_CE_FORM_SCALAR = 0, 1
 VK_RA_FORM_SEP, VK_RA_FORM_VEC, VK_RA_FORM_SCALAR = 0, 1, 2
 VK_MAX_ANCHOR_DIM = 8
@@ -154,6 +155,10 @@ SIGNATURES = {
     "vk_attention": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vk_attention_tiled": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vk_attention_route": (_I, [_I] * 9),
+    "vk_attention_relpos_form": (_I, [_I] * 8),
+    "vk_attention_relpos_queries": (_I, [_I, _I]),
+    "vk_attention_relpos_check": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I]),
+    "vk_attention_relpos": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vk_visualbert_embed": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _F, _I, _P]),
     "vk_vit_patchify": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
     "vk_vit_assemble": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _P]),
@@ -267,8 +272,8 @@ def load():
                 "(or `make -C vltk_amd/csrc`).  vltk_amd has no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if "dropout" in name and os.environ.get("VLTK_AMD_LIB") and not hasattr(lib, name):
-                continue                            # tools only: an older build in an A/B lacks the dropout entries; calling one raises
+            if ("dropout" in name or "relpos" in name) and os.environ.get("VLTK_AMD_LIB") and not hasattr(lib, name):
+                continue                            # tools only: an older build in an A/B lacks the dropout / relpos entries; calling one raises
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
