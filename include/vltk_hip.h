@@ -611,6 +611,36 @@ int vk_layoutlm_embed(const int64_t *input_ids, const int64_t *token_type_ids, c
                       int vocab, const void *position, int max_position, const void *x, const void *y, const void *h,
                       const void *w, int max_2d, const void *token_type, int type_vocab, const float *gamma, const float *beta,
                       void *out, int C, float eps, vk_dtype dt, void *stream);
+/* The embedding stage of LayoutLMv3 (transformers modeling_layoutlmv3.py v5.15: LayoutLMv3TextEmbeddings.forward :160-199,
+ * LayoutLMv3Model.forward_image :603-618, LayoutLMv3Model.forward :729-774) as one launch over the joint sequence of L = Lt + V rows
+ * (V = 1 + patches, or 0 without an image), text rows first in each batch entry:
+ *   text row   (b, t)       LN_text(((word[id] + token_type[tt]) + position[p]) + spatial)
+ *                           p = pad_token_id for a pad id, else pad_token_id + (number of non-pad ids among ids[b, 0..t]), counted
+ *                           in the kernel; spatial = x[x0] | y[y0] | x[x1] | y[y1] | h[clip(y1 - y0, 0, 1023)] | w[clip(x1 - x0, 0, 1023)]
+ *                           side by side: x / y [max_2d, coordinate_size], h / w [max_2d, shape_size], 4 cs + 2 ss = C
+ *   visual row (b, Lt + v)  LN_norm(v == 0 ? cls_token + pos_embed[0] : proj[b * (V - 1) + v - 1] + pos_embed[v])
+ *   with V > 0 both kinds pass LN_out as well, applied to the first LayerNorm's fp32 result; sums, statistics and affines are fp32
+ *   and out [B * L, C] is rounded to dt once.
+ *   rel [B, L, 3] int32, what vk_attention_relpos reads: text (t, x0, y1) of bbox [B, Lt, 4], visual (v, x0, y1) of visual_bbox [V, 4].
+ *   mask [B, L] fp32 additive: (1 - attention_mask[b, t]) * -FLT_MAX on a text column (0 without attention_mask), 0 on a visual one.
+ * Tables, proj [B * (V - 1), ldp], cls_token [C], pos_embed [V, C] and out in dt; attention_mask [B, Lt] fp32 or NULL.  The kernel
+ * clamps every index into its table; refusing bad ids, boxes and positions past the table is the caller's.  VK_EINVAL before any
+ * launch: a null pointer, B or Lt < 1, V = 1 or < 0, 2^31 rows or more, C outside 1..2048, 4 cs + 2 ss != C, an empty table, a
+ * pad_token_id outside the position table, V = 0 with a visual argument or V > 0 without one of them (ldp < C), a mask pointer that
+ * is NULL although there is an attention_mask or an image (or given with neither), a dtype other than f32 / f16 / bf16.
+ * vk_layoutlmv3_embed_form: the kernel form of a launch, or -VK_EINVAL where the launch would refuse the shape: 16-byte chunks when
+ * coordinate_size and shape_size are multiples of the chunk (8 elements in 16-bit, 4 in f32) and every base and ldp is 16-byte
+ * aligned (aligned16); single elements, the table picked per element, otherwise. */
+#define VK_L3E_FORM_VEC 0       /* layoutlmv3_embed_kernel<T, 16 / sizeof(T)> */
+#define VK_L3E_FORM_SCALAR 1    /* layoutlmv3_embed_kernel<T, 1> */
+int vk_layoutlmv3_embed_form(int C, int coordinate_size, int shape_size, vk_dtype dt, int aligned16);
+int vk_layoutlmv3_embed(const int64_t *input_ids, const int64_t *token_type_ids, const int32_t *bbox, const float *attention_mask,
+                        int B, int Lt, int pad_token_id, const void *word, int vocab, const void *token_type, int type_vocab,
+                        const void *position, int max_position, const void *x, const void *y, const void *h, const void *w,
+                        int max_2d, int coordinate_size, int shape_size, const float *text_gamma, const float *text_beta, float eps,
+                        const void *proj, int ldp, const void *cls_token, const void *pos_embed, const int32_t *visual_bbox, int V,
+                        const float *norm_gamma, const float *norm_beta, float norm_eps, const float *out_gamma,
+                        const float *out_beta, void *out, int32_t *rel, float *mask, int C, vk_dtype dt, void *stream);
 /* The token-classification tail (what vltk/utils/adapters.py map_ocr_predictions does per example on the host; PARITY UNPINNED
  * for the rule).  logits [B * L, ld] in dt, of which the first C columns count; word_ids [B, L]: the word a token belongs to, -1
  * for a special or padding token (an id >= W is ignored too).  token_labels [B, L]: the arg-max over C, scanning upward with

@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
-"""vk_attention_relpos measured on one MI355X: writes profiles/layoutlmv3_bench.json.
+"""LayoutLMv3 measured on one MI355X: vk_attention_relpos alone -> profiles/layoutlmv3_bench.json, and the
+12-layer model -> profiles/layoutlmv3_model_bench.json.
 
-usage: python tools/layoutlmv3_bench.py [--out PATH]
+usage: python tools/layoutlmv3_bench.py [--out PATH]              the attention kernel
+       python tools/layoutlmv3_bench.py --model [--out PATH]      the model
+
+The model section: LayoutLMv3Model in bf16 at transformers' base geometry, 512 text tokens + 197 patch rows (L = 709), B = 8 and 32,
+one forward captured into a graph and replayed.  In the same process and the same alternating windows: LayoutLMModel (v1) at 512
+tokens and the same B, also replayed.  Per B: ms and pages/s of both, and by device events around those launches alone the
+embedding stage (patchify, projection GEMM and vk_layoutlmv3_embed) and one layer's attention, as shares of the replayed forward.
+
+The kernel section:
 
 One job; the GPU step is a child process under its own time limit.  At B = 32, 12 heads, d = 64, bf16, L = 709 (512 text tokens +
 197 patches) and L = 197, alternating in the same windows:
@@ -23,6 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 B, HEADS, D, R1, R2 = 32, 12, 64, 128, 256
 LENGTHS = (709, 197)
+MODEL_BATCHES = (8, 32)
 
 
 def step_kernel():
@@ -74,30 +84,73 @@ def step_kernel():
     return rows
 
 
+def step_model():
+    import numpy as np
+    import torch
+    from long_attention_bench import _time_ms
+    from vltk_amd import layoutlm as V1
+    from vltk_amd import layoutlmv3 as V3
+    gen = np.random.Generator(np.random.PCG64(0))
+    cfg3, cfg1 = V3.layoutlmv3_config(max_position_embeddings=514), V1.layoutlm_config()
+    m3 = V3.LayoutLMv3Model(cfg3, precision="bf16").load_state_dict(V3.make_layoutlmv3_state_dict(cfg3, 1))
+    m1 = V1.LayoutLMModel(cfg1, precision="bf16").load_state_dict(V1.make_layoutlm_state_dict(cfg1, 1))
+    H, Lt = cfg3["hidden_size"], 512
+    rows = []
+    for Bm in MODEL_BATCHES:
+        ids = torch.from_numpy(gen.integers(2, cfg1["vocab_size"], (Bm, Lt))).cuda()
+        xs, ys = np.sort(gen.integers(0, 1001, (Bm, Lt, 2)), -1), np.sort(gen.integers(0, 1001, (Bm, Lt, 2)), -1)
+        bbox = torch.from_numpy(np.stack((xs[..., 0], ys[..., 0], xs[..., 1], ys[..., 1]), -1)).cuda()
+        mask = torch.ones((Bm, Lt), device="cuda")
+        pix = torch.from_numpy(gen.standard_normal((Bm, 3, 224, 224)).astype(np.float32)).cuda()
+        in3, in1 = (ids, bbox, mask, None, pix), (ids, bbox, mask, None)
+        m3._check(*in3), m1._check(*in1)
+        g3, out3 = m3._capture(m3._forward, list(in3))
+        g1, _ = m1._capture(m1._forward, list(in1))
+        eager = m3(*in3).clone()
+        g3.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out3, eager), "the replayed graph differs from the eager forward"
+        x, amask = m3._embed(*in3)
+        Lx = x.shape[0] // Bm
+        qkv = m3._linear(x, "encoder.layer.0.attention.self.qkv")
+        t3, t1, t_emb, t_att = _time_ms([g3.replay, g1.replay, lambda: m3._embed(*in3),
+                                         lambda: m3._self_attention(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], amask, Bm, Lx)])
+        rows.append(dict(B=Bm, L=Lx, text_tokens=Lt, patch_rows=Lx - Lt, embed_form=m3.embed_form(), relpos_form=m3.relpos_form(Lx),
+                         v3_graph_ms=t3, v3_pages_per_s=Bm / t3 * 1e3, v1_graph_ms=t1, v1_pages_per_s=Bm / t1 * 1e3, v3_over_v1=t3 / t1,
+                         embed_stage_ms=t_emb, embed_stage_share=t_emb / t3, attention_ms_per_layer=t_att,
+                         attention_share=t_att * cfg3["num_hidden_layers"] / t3))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "layoutlmv3_bench.json"))
+    ap.add_argument("--model", action="store_true", help="measure the 12-layer model instead of the attention kernel")
+    ap.add_argument("--out")
     ap.add_argument("--step")
     a = ap.parse_args()
     if a.step:
         import torch
         assert torch.cuda.is_available(), "layoutlmv3_bench needs a GPU"
-        print("RESULT " + json.dumps(step_kernel()), flush=True)
+        print("RESULT " + json.dumps(step_model() if a.step == "model" else step_kernel()), flush=True)
         return 0
-    result = {"geometry": dict(B=B, heads=HEADS, d=D, r1=R1, r2=R2, dtype="bf16"), "steps": {}}
+    step = "model" if a.model else "kernel"
+    a.out = a.out or os.path.join(ROOT, "profiles", "layoutlmv3_model_bench.json" if a.model else "layoutlmv3_bench.json")
+    geometry = dict(model="LayoutLMv3 base: 12 layers, hidden 768, 12 heads", text_tokens=512, patch_rows=197, dtype="bf16",
+                    beside="LayoutLM (v1) base at 512 tokens") if a.model else dict(B=B, heads=HEADS, d=D, r1=R1, r2=R2, dtype="bf16")
+    result = {"geometry": geometry, "steps": {}}
     status = 0
     try:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", "kernel"], timeout=420, capture_output=True, text=True)
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", step], timeout=420, capture_output=True, text=True)
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
         if p.returncode != 0 or not lines:
-            result["steps"]["kernel"] = {"error": f"exit status {p.returncode}", "stderr": p.stderr[-2000:]}
+            result["steps"][step] = {"error": f"exit status {p.returncode}", "stderr": p.stderr[-2000:]}
             status = 1
         else:
-            result["steps"]["kernel"] = json.loads(lines[-1][len("RESULT "):])
+            result["steps"][step] = json.loads(lines[-1][len("RESULT "):])
     except subprocess.TimeoutExpired:
-        result["steps"]["kernel"] = {"error": "no result within 420 s"}
+        result["steps"][step] = {"error": "no result within 420 s"}
         status = 1
-    print(json.dumps(result["steps"]["kernel"]), flush=True)
+    print(json.dumps(result["steps"][step]), flush=True)
     with open(a.out, "w") as f:
         json.dump(result, f, indent=1)
         f.write("\n")

@@ -34,7 +34,9 @@ def __getattr__(name):
                 "layoutlm_config", "ocr_token_boxes"):       # the document encoder: OCR words and their boxes
         from . import layoutlm
         return getattr(layoutlm, name)
-    if name in ("attention_relpos", "attention_relpos_form", "relpos_lut", "relpos_triples"):   # LayoutLMv3's attention: the bias in-kernel
+    if name in ("attention_relpos", "attention_relpos_form", "relpos_lut", "relpos_triples",    # LayoutLMv3: the bias in-kernel,
+                "LayoutLMv3Model", "LayoutLMv3ForTokenClassification", "LayoutLMv3ForQuestionAnswering",    # the model and its heads
+                "LayoutLMv3ForSequenceClassification", "layoutlmv3_config"):
         from . import layoutlmv3
         return getattr(layoutlmv3, name)
     if name in ("HeadTrainer", "step_lr", "linear_warmup"):   # N7: train a head over a frozen encoder

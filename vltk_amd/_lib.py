@@ -22,6 +22,7 @@ VK_ACT_NONE, VK_ACT_RELU, VK_ACT_GELU, VK_ACT_TANH = 0, 1, 2, 3
 VK_ROUTE_GENERIC, VK_ROUTE_RING, VK_ROUTE_DUO, VK_ROUTE_WS, VK_ROUTE_GEMM4, VK_ROUTE_PANEL, VK_ROUTE_BLK = range(7)
 VK_ATT_ROUTE_MFMA, VK_ATT_ROUTE_LDS, VK_ATT_ROUTE_TILED, VK_ATT_ROUTE_STREAM = range(4)
 VK_RELPOS_FORM_MFMA, VK_RELPOS_FORM_STRICT = 0, 1
+VK_L3E_FORM_VEC, VK_L3E_FORM_SCALAR = 0, 1
 VK_CE_FORM_VEC, VK_CE_FORM_SCALAR = 0, 1
 VK_RA_FORM_SEP, VK_RA_FORM_VEC, VK_RA_FORM_SCALAR = 0, 1, 2
 VK_MAX_ANCHOR_DIM = 8
@@ -163,6 +164,9 @@ SIGNATURES = {
     "vk_vit_patchify": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
     "vk_vit_assemble": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _P]),
     "vk_layoutlm_embed": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _F, _I, _P]),
+    "vk_layoutlmv3_embed_form": (_I, [_I] * 5),
+    "vk_layoutlmv3_embed": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _F, _P, _I, _P, _P, _P,
+                                 _I, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _P]),
     "vk_token_word_labels": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vk_span_select": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P]),
     "vk_cross_entropy": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P]),
@@ -272,8 +276,8 @@ def load():
                 "(or `make -C vltk_amd/csrc`).  vltk_amd has no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if ("dropout" in name or "relpos" in name) and os.environ.get("VLTK_AMD_LIB") and not hasattr(lib, name):
-                continue                            # tools only: an older build in an A/B lacks the dropout / relpos entries; calling one raises
+            if ("dropout" in name or "relpos" in name or "layoutlmv3" in name) and os.environ.get("VLTK_AMD_LIB") and not hasattr(lib, name):
+                continue                            # tools only: an older build in an A/B lacks the dropout / relpos / layoutlmv3 entries; calling one raises
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

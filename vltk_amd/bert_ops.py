@@ -245,6 +245,11 @@ class BertOps(Model):
                mask.data_ptr() if mask is not None else None, out.data_ptr(), H, B, heads, Lq, Lk, H // heads, self.dt, stream(self.device))
         return out
 
+    def _self_attention(self, q, k, v, mask, B, Lx):
+        """The attention of a self-attention block, on the q / k / v column slices of its fused projection.  The one point a model
+        with another attention overrides (LayoutLMv3: the in-kernel position bias)."""
+        return self._attention(q, k, v, mask, B, Lx, Lx)
+
     def _gather_rows(self, x, idx):
         """Rows `idx` (int32, on the device) of contiguous `x [M, C]` -> [len(idx), C].  The kernel copies 16-byte lanes."""
         n, Cc = idx.numel(), x.shape[1]
@@ -258,7 +263,7 @@ class BertOps(Model):
     def _self_att_block(self, p, x, mask, B, Lx):       # LxmertSelfAttentionLayer :298-316
         H = self.cfg["hidden_size"]
         qkv = self._linear(x, p + ".self.qkv")
-        ctx = self._attention(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], mask, B, Lx, Lx)
+        ctx = self._self_attention(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], mask, B, Lx)
         t = self._linear(ctx, p + ".output.dense", residual=x)
         return self._layernorm(t, p + ".output.LayerNorm")
 

@@ -230,6 +230,56 @@ def _strided_rows(t, what):
     return t.stride(1)
 
 
+# The two tails on a head's logits, shared with LayoutLMv3's heads: `enc` is the encoder whose storage type and device the logits have.
+@torch.no_grad()
+def token_word_labels(enc, logits, word_ids, num_words):
+    """The reference's `map_ocr_predictions` on the device (`vk_token_word_labels`): logits [B, L, C <= 64], word_ids [B, L]
+    (the word of each token, -1 for special and padding tokens; `ocr_token_boxes` returns them) -> (token_labels [B, L],
+    word_labels [B, num_words]) int32.  A token's label is the first arg-max; a word's label is the most frequent label of
+    its tokens, the smallest on a tie, -1 for a word with no token."""
+    if logits.dim() != 3 or logits.dtype != enc.tdt:
+        raise ValueError(f"logits [B, L, C] in {enc.tdt} expected, got {logits.dtype} {tuple(logits.shape)}")
+    B, Lt, Cn = logits.shape
+    if tuple(word_ids.shape) != (B, Lt):
+        raise ValueError(f"word_ids must be {(B, Lt)}, got {tuple(word_ids.shape)}")
+    if not (1 <= Cn <= MAX_LABELS and 1 <= Lt <= MAX_TOKENS and 1 <= num_words <= Lt):
+        raise ValueError(f"word_labels takes 1..{MAX_LABELS} labels, 1..{MAX_TOKENS} tokens and 1..L words: got C={Cn} L={Lt} W={num_words}")
+    logits = logits.to(enc.device)
+    ld = _strided_rows(logits, "logits")
+    wid = word_ids.to(enc.device, torch.int32).contiguous()
+    tok = torch.empty((B, Lt), dtype=torch.int32, device=enc.device)
+    words = torch.empty((B, num_words), dtype=torch.int32, device=enc.device)
+    L.call("vk_token_word_labels", logits.data_ptr(), ld, wid.data_ptr(), B, Lt, Cn, num_words, tok.data_ptr(), words.data_ptr(),
+           enc.dt, stream(enc.device))
+    torch.cuda.synchronize(enc.device)
+    return tok, words
+
+
+@torch.no_grad()
+def span_select(enc, start_logits, end_logits, context_mask, max_answer_tokens=30):
+    """`vk_span_select`: the best pair s <= e of context tokens with e - s + 1 <= max_answer_tokens under
+    start_logits[s] + end_logits[e] -> (start [B], end [B]) int32, score [B] fp32; (-1, -1, -inf) where there is none.  Ties
+    go to the smaller s, then the smaller e.  The logits are read where they are (the columns `model(...)` returned)."""
+    for t in (start_logits, end_logits):
+        if t.dim() != 2 or t.dtype != enc.tdt or t.shape != start_logits.shape:
+            raise ValueError(f"start_logits and end_logits [B, L] in {enc.tdt} expected, got {t.dtype} {tuple(t.shape)}")
+    B, Lt = start_logits.shape
+    if tuple(context_mask.shape) != (B, Lt):
+        raise ValueError(f"context_mask must be {(B, Lt)}, got {tuple(context_mask.shape)}")
+    if not (1 <= Lt <= MAX_TOKENS) or max_answer_tokens < 1:
+        raise ValueError(f"best_span takes 1..{MAX_TOKENS} tokens and max_answer_tokens >= 1: got L={Lt}, {max_answer_tokens}")
+    s_log, e_log = start_logits.to(enc.device), end_logits.to(enc.device)
+    ctx = (context_mask.to(enc.device) != 0).to(torch.int32).contiguous()
+    start = torch.empty((B,), dtype=torch.int32, device=enc.device)
+    end = torch.empty((B,), dtype=torch.int32, device=enc.device)
+    score = torch.empty((B,), dtype=torch.float32, device=enc.device)
+    L.call("vk_span_select", s_log.data_ptr(), _strided_rows(s_log, "start_logits"), e_log.data_ptr(),
+           _strided_rows(e_log, "end_logits"), ctx.data_ptr(), B, Lt, int(min(max_answer_tokens, Lt)), start.data_ptr(),
+           end.data_ptr(), score.data_ptr(), enc.dt, stream(enc.device))
+    torch.cuda.synchronize(enc.device)
+    return start, end, score
+
+
 class LayoutLMForTokenClassification(_Head):
     """`transformers.LayoutLMForTokenClassification`: `classifier` over every token in one GEMM.  `model(...)` takes the
     encoder's arguments and returns logits [B, L, num_labels] in the storage type (a view of the GEMM's padded output)."""
@@ -240,29 +290,9 @@ class LayoutLMForTokenClassification(_Head):
         logits = enc._run(lambda *inputs: enc._linear(enc._encode(*inputs), "classifier"), (input_ids, bbox, attention_mask, token_type_ids))
         return logits.view(input_ids.shape[0], input_ids.shape[1], self.num_labels)
 
-    @torch.no_grad()
     def word_labels(self, logits, word_ids, num_words):
-        """The reference's `map_ocr_predictions` on the device (`vk_token_word_labels`): logits [B, L, C <= 64], word_ids [B, L]
-        (the word of each token, -1 for special and padding tokens; `ocr_token_boxes` returns them) -> (token_labels [B, L],
-        word_labels [B, num_words]) int32.  A token's label is the first arg-max; a word's label is the most frequent label of
-        its tokens, the smallest on a tie, -1 for a word with no token."""
-        enc = self.layoutlm
-        if logits.dim() != 3 or logits.dtype != enc.tdt:
-            raise ValueError(f"logits [B, L, C] in {enc.tdt} expected, got {logits.dtype} {tuple(logits.shape)}")
-        B, Lt, Cn = logits.shape
-        if tuple(word_ids.shape) != (B, Lt):
-            raise ValueError(f"word_ids must be {(B, Lt)}, got {tuple(word_ids.shape)}")
-        if not (1 <= Cn <= MAX_LABELS and 1 <= Lt <= MAX_TOKENS and 1 <= num_words <= Lt):
-            raise ValueError(f"word_labels takes 1..{MAX_LABELS} labels, 1..{MAX_TOKENS} tokens and 1..L words: got C={Cn} L={Lt} W={num_words}")
-        logits = logits.to(enc.device)
-        ld = _strided_rows(logits, "logits")
-        wid = word_ids.to(enc.device, torch.int32).contiguous()
-        tok = torch.empty((B, Lt), dtype=torch.int32, device=enc.device)
-        words = torch.empty((B, num_words), dtype=torch.int32, device=enc.device)
-        L.call("vk_token_word_labels", logits.data_ptr(), ld, wid.data_ptr(), B, Lt, Cn, num_words, tok.data_ptr(), words.data_ptr(),
-               enc.dt, stream(enc.device))
-        torch.cuda.synchronize(enc.device)
-        return tok, words
+        """`token_word_labels` on this model's logits."""
+        return token_word_labels(self.layoutlm, logits, word_ids, num_words)
 
 
 class LayoutLMForQuestionAnswering(_Head):
@@ -281,30 +311,9 @@ class LayoutLMForQuestionAnswering(_Head):
         B, Lt = input_ids.shape
         return logits[:, 0].view(B, Lt), logits[:, 1].view(B, Lt)
 
-    @torch.no_grad()
     def best_span(self, start_logits, end_logits, context_mask, max_answer_tokens=30):
-        """`vk_span_select`: the best pair s <= e of context tokens with e - s + 1 <= max_answer_tokens under
-        start_logits[s] + end_logits[e] -> (start [B], end [B]) int32, score [B] fp32; (-1, -1, -inf) where there is none.  Ties
-        go to the smaller s, then the smaller e.  The logits are read where they are (the columns `model(...)` returned)."""
-        enc = self.layoutlm
-        for t in (start_logits, end_logits):
-            if t.dim() != 2 or t.dtype != enc.tdt or t.shape != start_logits.shape:
-                raise ValueError(f"start_logits and end_logits [B, L] in {enc.tdt} expected, got {t.dtype} {tuple(t.shape)}")
-        B, Lt = start_logits.shape
-        if tuple(context_mask.shape) != (B, Lt):
-            raise ValueError(f"context_mask must be {(B, Lt)}, got {tuple(context_mask.shape)}")
-        if not (1 <= Lt <= MAX_TOKENS) or max_answer_tokens < 1:
-            raise ValueError(f"best_span takes 1..{MAX_TOKENS} tokens and max_answer_tokens >= 1: got L={Lt}, {max_answer_tokens}")
-        s_log, e_log = start_logits.to(enc.device), end_logits.to(enc.device)
-        ctx = (context_mask.to(enc.device) != 0).to(torch.int32).contiguous()
-        start = torch.empty((B,), dtype=torch.int32, device=enc.device)
-        end = torch.empty((B,), dtype=torch.int32, device=enc.device)
-        score = torch.empty((B,), dtype=torch.float32, device=enc.device)
-        L.call("vk_span_select", s_log.data_ptr(), _strided_rows(s_log, "start_logits"), e_log.data_ptr(),
-               _strided_rows(e_log, "end_logits"), ctx.data_ptr(), B, Lt, int(min(max_answer_tokens, Lt)), start.data_ptr(),
-               end.data_ptr(), score.data_ptr(), enc.dt, stream(enc.device))
-        torch.cuda.synchronize(enc.device)
-        return start, end, score
+        """`span_select` on this model's logits."""
+        return span_select(self.layoutlm, start_logits, end_logits, context_mask, max_answer_tokens)
 
 
 class LayoutLMForSequenceClassification(_Head):
