@@ -832,6 +832,37 @@ int vk_attention_grad_16(const void *q, long ldq, const void *k, long ldk, const
                          const void *dout, long lddo, float *dq, long lddq, float *dk, long lddk, float *dv, long lddv, int B, int heads,
                          int Lq, int Lk, int d, vk_dtype dt, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The backward of the matrix-core form of vk_attention_relpos (csrc/attention_relpos_grad.hip): vk_attention_grad_16 with the
+ * forward's score, s = (q . k + (t1 + (tx + ty))) * scale + mask, the bias read from the head's table inside the kernels; nothing of
+ * [B, heads, Lq, Lk] is materialised.  q, k, v, mask, rel_q, rel_k, lut, r1, r2 as the forward takes them; o is the forward's
+ * output.  dq, dk, dv: fp32, with the layout, leading dimensions and alignment rules of vk_attention_grad_16.  dlut [heads,
+ * (2 r1 + 1) + 2 (2 r2 + 1)] fp32, the gradient of the folded table: dlut[h][e] = scale * the sum of the unrounded fp32 dS over
+ * every (b, i, j) whose clamped distance for that term is e; the mask receives no gradient.  The sum is taken in 64-bit fixed point
+ * with integer atomics, the quantum of a head a power of two from max ||dout row|| max ||v row||, so the same input gives the same
+ * bits; a head with a NaN or inf in dout or v (or a NaN dS) gets a NaN row of dlut.  Five launches on `stream`, the first of which clears
+ * the workspace's counters.
+ * vk_attention_relpos_grad_check: what the launch refuses, host only and reading through no pointer: what
+ * vk_attention_grad_16_check and vk_attention_relpos_check refuse between them, a NULL or misaligned dlut, a workspace below the
+ * size function's bytes or off 8 bytes, and B * Lq * Lk >= 2^32 (the fixed-point sum keeps at least 30 bits below its bound;
+ * 32 x 709 x 709 keeps 38). */
+size_t vk_attention_relpos_grad_workspace_bytes(int B, int heads, int Lq, int r1, int r2);
+int vk_attention_relpos_grad_check(const void *q, long ldq, const void *k, long ldk, const void *v, long ldv, const float *mask,
+                                   const int32_t *rel_q, const int32_t *rel_k, const float *lut, int r1, int r2, const void *o, long ldo,
+                                   const void *dout, long lddo, const float *dq, long lddq, const float *dk, long lddk, const float *dv,
+                                   long lddv, const float *dlut, int B, int heads, int Lq, int Lk, int d, vk_dtype dt, const void *workspace,
+                                   size_t workspace_bytes);
+int vk_attention_relpos_grad(const void *q, long ldq, const void *k, long ldk, const void *v, long ldv, const float *mask, const int32_t *rel_q,
+                             const int32_t *rel_k, const float *lut, int r1, int r2, const void *o, long ldo, const void *dout, long lddo,
+                             float *dq, long lddq, float *dk, long lddk, float *dv, long lddv, float *dlut, int B, int heads, int Lq, int Lk,
+                             int d, vk_dtype dt, void *workspace, size_t workspace_bytes, void *stream);
+/* From the folded table's gradient to a bias matrix's: dweight [heads, bins] fp32 (+)= the sum of the entries of term `term` (0: the
+ * 1-D table, 1: x, 2: y) of dlut [heads, (2 r1 + 1) + 2 (2 r2 + 1)] whose bucket it is, bucket [(2 r1 + 1) + 2 (2 r2 + 1)] int32
+ * being the fold's map from table entry to bucket (device memory; the caller guarantees it is that map: its values are not read on the
+ * host, and an entry whose bucket lies outside [0, bins) is left out of every sum).  dlut, bucket and dweight 4-byte aligned.  fp64 sums in ascending entry order, one rounding; `accumulate`
+ * adds to dweight (in fp64, one rounding) instead of overwriting it.  No atomics. */
+int vk_relpos_lut_grad(const float *dlut, int heads, int r1, int r2, int term, const int32_t *bucket, int bins, float *dweight,
+                       int accumulate, void *stream);
+
 /* ---- dropout for the trainers (csrc/philox.h states the mask) ----
  * A decision is a pure function of (seed, drop_stream, granule, byte) through Philox4x32-10 with key (seed_lo, seed_hi) and counter
  * (granule_lo, granule_hi, stream_lo, stream_hi); byte i of a call is bits 8 (i & 3).. of output word i >> 2.  With

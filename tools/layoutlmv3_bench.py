@@ -4,11 +4,19 @@
 
 usage: python tools/layoutlmv3_bench.py [--out PATH]              the attention kernel
        python tools/layoutlmv3_bench.py --model [--out PATH]      the model
+       python tools/layoutlmv3_bench.py --grad [--out PATH]       the attention backward -> profiles/layoutlmv3_grad_bench.json
 
 The model section: LayoutLMv3Model in bf16 at transformers' base geometry, 512 text tokens + 197 patch rows (L = 709), B = 8 and 32,
 one forward captured into a graph and replayed.  In the same process and the same alternating windows: LayoutLMModel (v1) at 512
 tokens and the same B, also replayed.  Per B: ms and pages/s of both, and by device events around those launches alone the
 embedding stage (patchify, projection GEMM and vk_layoutlmv3_embed) and one layer's attention, as shares of the replayed forward.
+
+The backward section: vk_attention_relpos_grad beside vk_attention_grad_16 on the same q, k, v, o and dout (the bias-free floor) at
+B = 8 and 32, 12 heads, d = 64, bf16, L = 709 and 197, in alternating windows; once with random triples and once document-like
+(about 12 tokens a text line share y, x grows along the line: the same-address collisions of the table-gradient histogram show
+there).  The new entry is called as the floor is, through `L.call` with a workspace and `dlut` allocated once.  A second child process
+times one `EncoderTrainer` step on LayoutLMv3ForSequenceClassification (base geometry, B = 8) at train_layers 1 and 12; a third loads the tools build (make ABLATION=1) with VK_RELPOS_GRAD_HIST=0 and times the same launches
+without the histogram, where that library exists.
 
 The kernel section:
 
@@ -84,6 +92,88 @@ def step_kernel():
     return rows
 
 
+GRAD_BATCHES = (8, 32)
+
+
+def step_grad():
+    import numpy as np
+    import torch
+    from long_attention_bench import _time_ms
+    from vltk_amd import _lib as L
+    from vltk_amd.layoutlmv3 import attention_relpos, attention_relpos_grad
+    rows, H = [], HEADS * D
+    stream = torch.cuda.current_stream().cuda_stream
+    for Bg in GRAD_BATCHES:
+        for Lx in LENGTHS:
+            gen = np.random.Generator(np.random.PCG64([Bg, Lx]))
+            qkv = torch.from_numpy(gen.standard_normal((Bg * Lx, 3 * H)).astype(np.float32)).cuda().bfloat16()
+            q, k, v = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
+            dout = torch.from_numpy(gen.standard_normal((Bg * Lx, H)).astype(np.float32)).cuda().bfloat16()
+            lut = torch.from_numpy(gen.standard_normal((HEADS, 2 * R1 + 1 + 2 * (2 * R2 + 1))).astype(np.float32)).cuda()
+            pos = np.broadcast_to(np.concatenate([np.arange(max(Lx - 197, 0)), np.arange(min(Lx, 197))]), (Bg, Lx))
+            tok = np.arange(Lx)
+            doc = np.stack([pos, np.broadcast_to(40 + 75 * (tok % 12), (Bg, Lx)), np.broadcast_to(30 + 16 * (tok // 12), (Bg, Lx))], -1)
+            rand = np.stack([pos, gen.integers(0, 1001, (Bg, Lx)), gen.integers(0, 1001, (Bg, Lx))], -1)
+            rel = {n: torch.from_numpy(t.astype(np.int32)).cuda().contiguous() for n, t in (("random", rand), ("document", doc))}
+            o = {n: attention_relpos(q, k, v, r, r, lut, R1, R2, HEADS) for n, r in rel.items()}
+            dqkv = torch.empty((Bg * Lx, 3 * H), dtype=torch.float32, device="cuda")
+            outs = tuple(dqkv[:, i * H:(i + 1) * H] for i in range(3))
+            need = L.load().vk_attention_grad_16_workspace_bytes(Bg, HEADS, Lx)
+            ws = torch.empty((need // 4,), dtype=torch.float32, device="cuda")
+
+            def floor():
+                L.call("vk_attention_grad_16", q.data_ptr(), 3 * H, k.data_ptr(), 3 * H, v.data_ptr(), 3 * H, None, o["random"].data_ptr(), H,
+                       dout.data_ptr(), H, outs[0].data_ptr(), 3 * H, outs[1].data_ptr(), 3 * H, outs[2].data_ptr(), 3 * H, Bg, HEADS, Lx, Lx, D,
+                       L.VK_BF16, ws.data_ptr(), need, stream)
+
+            need_g = L.load().vk_attention_relpos_grad_workspace_bytes(Bg, HEADS, Lx, R1, R2)
+            ws_g = torch.empty((need_g // 8,), dtype=torch.int64, device="cuda")
+            dlut = torch.empty_like(lut)
+            check = attention_relpos_grad(q, k, v, o["random"], dout, rel["random"], rel["random"], lut, R1, R2, HEADS)[3]
+
+            def grad(name):          # the entry itself with a workspace and dlut allocated once, as the floor is timed
+                r = rel[name].data_ptr()
+                return lambda: L.call("vk_attention_relpos_grad", q.data_ptr(), 3 * H, k.data_ptr(), 3 * H, v.data_ptr(), 3 * H, None, r, r,
+                                      lut.data_ptr(), R1, R2, o[name].data_ptr(), H, dout.data_ptr(), H, outs[0].data_ptr(), 3 * H,
+                                      outs[1].data_ptr(), 3 * H, outs[2].data_ptr(), 3 * H, dlut.data_ptr(), Bg, HEADS, Lx, Lx, D, L.VK_BF16,
+                                      ws_g.data_ptr(), need_g, stream)
+            grad("random")()
+            torch.cuda.synchronize()
+            assert torch.equal(dlut, check), "the raw call and the wrapper disagree"
+            t_rand, t_doc, t_floor = _time_ms([grad("random"), grad("document"), floor])
+            rows.append(dict(B=Bg, L=Lx, histogram=os.environ.get("VK_RELPOS_GRAD_HIST") != "0", relpos_grad_random_ms=t_rand,
+                             relpos_grad_document_ms=t_doc, grad16_ms=t_floor, random_over_floor=t_rand / t_floor,
+                             document_over_floor=t_doc / t_floor))
+    return rows
+
+
+def step_train():
+    """One EncoderTrainer step on LayoutLMv3ForSequenceClassification at the base geometry (512 text tokens + 197 patch rows, B = 8,
+    bf16 model, compute_dtype bf16) with the last 1 and all 12 layers trained; a step ends with a device synchronisation."""
+    import numpy as np
+    import torch
+    from long_attention_bench import _time_ms
+    from vltk_amd import EncoderTrainer
+    from vltk_amd import layoutlmv3 as V3
+    gen = np.random.Generator(np.random.PCG64(0))
+    cfg = V3.layoutlmv3_config(max_position_embeddings=514)
+    sd = V3.make_layoutlmv3_head_state_dict(cfg, "seq", 16, 1)
+    model = V3.LayoutLMv3ForSequenceClassification(cfg, 16, precision="bf16").load_state_dict(sd)
+    Bm, Lt = 8, 512
+    ids = torch.from_numpy(gen.integers(2, cfg["vocab_size"], (Bm, Lt)))
+    xs, ys = np.sort(gen.integers(0, 1001, (Bm, Lt, 2)), -1), np.sort(gen.integers(0, 1001, (Bm, Lt, 2)), -1)
+    bbox = torch.from_numpy(np.stack((xs[..., 0], ys[..., 0], xs[..., 1], ys[..., 1]), -1))
+    pix = torch.from_numpy(gen.standard_normal((Bm, 3, 224, 224)).astype(np.float32))
+    labels = gen.integers(0, 16, Bm)
+    rows = []
+    for n in (1, 12):
+        tr = EncoderTrainer(model, sd, train_layers=n, compute_dtype=torch.bfloat16, max_grad_norm=1.0)
+        (t,) = _time_ms([lambda: tr.step(ids, bbox, None, None, pix, labels=labels)])
+        rows.append(dict(B=Bm, L=Lt + 197, train_layers=n, step_ms=t, pages_per_s=Bm / t * 1e3))
+        del tr
+    return rows
+
+
 def step_model():
     import numpy as np
     import torch
@@ -122,17 +212,48 @@ def step_model():
     return rows
 
 
+def main_grad(out):
+    """The shipped library, then the tools build without the histogram where it exists: one child process each, one at a time."""
+    result = {"geometry": dict(heads=HEADS, d=D, r1=R1, r2=R2, dtype="bf16", batches=GRAD_BATCHES, lengths=LENGTHS), "steps": {}}
+    legs = [("grad", "grad", {}), ("train_step", "train", {})]
+    if os.path.exists(os.path.join(ROOT, "vltk_amd", "libvltk_hip_ablation.so")):
+        legs.append(("grad_no_histogram", "grad", {"VLTK_AMD_ABLATION_LIB": "1", "VK_RELPOS_GRAD_HIST": "0"}))
+    status = 0
+    for name, step, env in legs:
+        try:
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", step], timeout=300, capture_output=True, text=True,
+                               env=dict(os.environ, **env))
+        except subprocess.TimeoutExpired:
+            result["steps"][name] = {"error": "no result within 300 s"}
+            status = 1
+            break                                   # nothing more on the GPU after a step that did not end
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+        if p.returncode != 0 or not lines:
+            result["steps"][name] = {"error": f"exit status {p.returncode}", "stderr": p.stderr[-2000:]}
+            status = 1
+            break
+        result["steps"][name] = json.loads(lines[-1][len("RESULT "):])
+    print(json.dumps(result["steps"]), flush=True)
+    with open(out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    return status
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", action="store_true", help="measure the 12-layer model instead of the attention kernel")
+    ap.add_argument("--grad", action="store_true", help="measure the attention backward beside vk_attention_grad_16")
     ap.add_argument("--out")
     ap.add_argument("--step")
     a = ap.parse_args()
     if a.step:
         import torch
         assert torch.cuda.is_available(), "layoutlmv3_bench needs a GPU"
-        print("RESULT " + json.dumps(step_model() if a.step == "model" else step_kernel()), flush=True)
+        print("RESULT " + json.dumps({"model": step_model, "kernel": step_kernel, "grad": step_grad, "train": step_train}[a.step]()), flush=True)
         return 0
+    if a.grad:
+        return main_grad(a.out or os.path.join(ROOT, "profiles", "layoutlmv3_grad_bench.json"))
     step = "model" if a.model else "kernel"
     a.out = a.out or os.path.join(ROOT, "profiles", "layoutlmv3_model_bench.json" if a.model else "layoutlmv3_bench.json")
     geometry = dict(model="LayoutLMv3 base: 12 layers, hidden 768, 12 heads", text_tokens=512, patch_rows=197, dtype="bf16",

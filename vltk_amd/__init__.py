@@ -35,6 +35,7 @@ def __getattr__(name):
         from . import layoutlm
         return getattr(layoutlm, name)
     if name in ("attention_relpos", "attention_relpos_form", "relpos_lut", "relpos_triples",    # LayoutLMv3: the bias in-kernel,
+                "attention_relpos_grad", "relpos_bucket_map", "relpos_lut_grad",                 # and its backward
                 "LayoutLMv3Model", "LayoutLMv3ForTokenClassification", "LayoutLMv3ForQuestionAnswering",    # the model and its heads
                 "LayoutLMv3ForSequenceClassification", "layoutlmv3_config"):
         from . import layoutlmv3

@@ -203,6 +203,10 @@ SIGNATURES = {
     "vk_attention_grad_16": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 6 + [_P, _SZ, _P]),
     "vk_dropout_add_f32": (_I, [_P, _P, _P, C.c_long, _F, C.c_uint64, C.c_uint64, _P]),
     "vk_attention_tiled_dropout": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _F, C.c_uint64, C.c_uint64]),
+    "vk_attention_relpos_grad_workspace_bytes": (_SZ, [_I] * 5),
+    "vk_attention_relpos_grad_check": (_I, [_P, C.c_long] * 3 + [_P] * 4 + [_I, _I] + [_P, C.c_long] * 5 + [_P] + [_I] * 6 + [_P, _SZ]),
+    "vk_attention_relpos_grad": (_I, [_P, C.c_long] * 3 + [_P] * 4 + [_I, _I] + [_P, C.c_long] * 5 + [_P] + [_I] * 6 + [_P, _SZ, _P]),
+    "vk_relpos_lut_grad": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P]),
     "vk_attention_grad_16_dropout_workspace_bytes": (_SZ, [_I, _I, _I]),
     "vk_attention_grad_16_dropout_check": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 6 + [_P, _SZ, _F]),
     "vk_attention_grad_16_dropout": (_I, [_P, C.c_long] * 3 + [_P] + [_P, C.c_long] * 5 + [_I] * 6 + [_P, _SZ, _P, _F, C.c_uint64, C.c_uint64]),

@@ -21,17 +21,11 @@
 #include <algorithm>
 
 #include "attention_tiled.h"
-#include "vk_common.h"
+#include "relpos.h"
 
 namespace vk {
 
-constexpr size_t RELPOS_LUT_MAX = 8 * 1024;     // LDS budget of one head's table: (2 r1 + 1) + 2 (2 r2 + 1) floats (128 / 256: 5132 bytes)
-constexpr int RP_KT = 64;                       // keys per tile
 constexpr int RP_MAXW = 4;                      // waves per workgroup at most
-
-static inline int relpos_lut_len(int r1, int r2) { return (2 * r1 + 1) + 2 * (2 * r2 + 1); }
-
-__device__ __forceinline__ int rp_idx(int dk, int dq, int r) { return min(max(dk - dq, -r), r) + r; }
 
 // ---- the matrix-core form ----
 // A WORKGROUP of 1 .. 4 waves per (batch, head, run of waves * QB * 16 queries): wave w serves the w-th block of QB * 16 queries

@@ -44,7 +44,17 @@ residual, on the gradient that enters the site's Linear; the attention site is `
 `vk_attention_grad_16_dropout` under one (rate, seed, stream), so it needs the mixed mode.  Both rates 0.0, the default, is the
 trainer without the arguments, launch for launch.  The frozen layers run the model's own eval forward.
 
-Out of scope: dropout on the fp32 attention pair, HIP-graph capture of a step, `image_text_alignment` under `train_embeddings` (a weighted lookup), sparse
+`LayoutLMv3ForSequenceClassification`: row 0 goes through `classifier.dense` + tanh to
+`classifier.out_proj`, the pooled path under other keys; the attention pair of a trained layer is `vk_attention_relpos` /
+`vk_attention_relpos_grad`, and the bias matrices that exist (`layoutlmv3.encoder.rel_pos_bias.weight`, `...rel_pos_x_bias.weight`,
+`...rel_pos_y_bias.weight`), shared by all layers, are trained like any other tensor.  Each step builds the device table from their
+fp32 masters by a gather through `relpos_bucket_map`; the frozen layers read the same tables, so they run with the trainer's table
+(the model's own is written by `commit()` only); backwards, `vk_relpos_lut_grad` sums each trained layer's table gradient by bucket
+into the matrices' gradients, the top layer writing and the others adding.  With neither bias flag the existing kernels run.
+Refused (ValueError): `compute_dtype=None` with a bias term, `attention_dropout > 0`, `train_embeddings=True`.
+
+Out of scope: the strict fp32 backward of the position-bias attention, attention dropout and embedding training for LayoutLMv3,
+`LayoutLMv3ForTokenClassification`, dropout on the fp32 attention pair, HIP-graph capture of a step, `image_text_alignment` under `train_embeddings` (a weighted lookup), sparse
 (row-wise) AdamW, 16-bit tables, ViT (pre-LN layers) and LXMERT (cross-attention top layers), running the top layer only on the rows the head reads (for `train_layers=1` the FFN is needed on B rows, not B * L:
 measure first, then build it as its own change), fp16 as the compute type (its gradients need loss scaling) and producers that
 write both precisions at once (the cast passes are measured first).
@@ -61,16 +71,21 @@ from .train import (Precision, _Trainer, act_f32, act_grad_f32, add_f32, attenti
 
 # ---- what is trained ---------------------------------------------------------------------------------------------------------------------
 def _describe(model):
-    """-> (encoder, its state-dict prefix, head prefix, whether `pooler.dense` stands between the layers and the head)."""
+    """-> (encoder, its state-dict prefix, head prefix, the prefix of the dense + tanh on row 0 that stands between the layers and
+    the head, or None)."""
     from .layoutlm import LayoutLMForSequenceClassification
+    from .layoutlmv3 import LayoutLMv3ForSequenceClassification
     from .visualbert import VisualBertForQuestionAnswering
     if isinstance(model, VisualBertForQuestionAnswering):
-        return model.visual_bert, "visual_bert.", "cls", False
+        return model.visual_bert, "visual_bert.", "cls", None
     if isinstance(model, LayoutLMForSequenceClassification):
-        return model.layoutlm, "layoutlm.", "classifier", True
+        return model.layoutlm, "layoutlm.", "classifier", "layoutlm.pooler.dense"
+    if isinstance(model, LayoutLMv3ForSequenceClassification):
+        return model.layoutlmv3, "layoutlmv3.", "classifier.out_proj", "classifier.dense"
     why = {"ViTForImageClassification": ": ViT's layers are pre-LN, the backward here is the post-LN BERT layer's",
            "LxmertForQuestionAnswering": ": LXMERT's top layers are cross-attention layers"}.get(type(model).__name__, "")
-    raise TypeError(f"EncoderTrainer takes VisualBertForQuestionAnswering or LayoutLMForSequenceClassification, not {type(model).__name__}{why}")
+    raise TypeError("EncoderTrainer takes VisualBertForQuestionAnswering, LayoutLMForSequenceClassification or "
+                    f"LayoutLMv3ForSequenceClassification, not {type(model).__name__}{why}")
 
 
 def _check_compute_dtype(compute_dtype, cfg):
@@ -111,8 +126,9 @@ _LAYER_MATRICES = (".attention.output.dense.weight", ".intermediate.dense.weight
 class EncoderTrainer(_Trainer):
     """`EncoderTrainer(model, state_dict, train_layers=1, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, no_decay=(),
     schedule=None, max_grad_norm=None)`: trains the last `train_layers` BERT layers and the head of
-    `VisualBertForQuestionAnswering` (layers -> the gathered row -> `cls`) or `LayoutLMForSequenceClassification` (layers ->
-    `pooler.dense` + tanh on the first token -> `classifier`; `pooler.dense` is trained too) with cross-entropy, optional clipping
+    `VisualBertForQuestionAnswering` (layers -> the gathered row -> `cls`), `LayoutLMForSequenceClassification` (layers ->
+    `pooler.dense` + tanh on the first token -> `classifier`; `pooler.dense` is trained too) or `LayoutLMv3ForSequenceClassification`
+    (layers -> `classifier.dense` + tanh on row 0 -> `classifier.out_proj`, and the relative-position bias matrices; mixed mode only) with cross-entropy, optional clipping
     of the global gradient norm and `torch.optim.AdamW`'s rule.  The lower layers and the embeddings stay frozen.  Any other
     model: TypeError.
 
@@ -157,9 +173,23 @@ class EncoderTrainer(_Trainer):
         if self._attention_dropout > 0 and compute_dtype is None:
             raise ValueError("attention_dropout > 0 needs the mixed mode, compute_dtype=torch.bfloat16: the fp32 attention kernels have no "
                              "dropout form")
-        self.enc, self.enc_prefix, self.head, self.pooled = _describe(model)
+        self.enc, self.enc_prefix, self.head, self._pool = _describe(model)
+        self.pooled = self._pool is not None
         self.model = model
         enc, cfg = self.enc, self.enc.cfg
+        # LayoutLMv3 with a bias term: the attention pair is vk_attention_relpos / vk_attention_relpos_grad and the bias matrices,
+        # shared by all layers, are trained; without one the model runs the plain attention and so does the trainer
+        self._relpos = self.enc_prefix == "layoutlmv3." and getattr(enc, "_lut", None) is not None
+        if self.enc_prefix == "layoutlmv3.":
+            if self._relpos and compute_dtype is None:
+                raise ValueError("LayoutLMv3 with a relative-position bias needs compute_dtype=torch.bfloat16: the backward of its attention "
+                                 "is built for 16-bit operands only (no strict fp32 form)")
+            if self._attention_dropout > 0:
+                raise ValueError("attention_dropout > 0 with LayoutLMv3: the backward of the position-bias attention has no dropout form; use "
+                                 "hidden_dropout, whose sites lie outside the attention")
+            if train_embeddings:
+                raise ValueError("train_embeddings=True with LayoutLMv3: the backward of its joint embedding stage is not built; train the "
+                                 "layers and the head (train_embeddings=False)")
         self._compute_dtype = _check_compute_dtype(compute_dtype, cfg)
         nl = cfg["num_hidden_layers"]
         n = int(train_layers)
@@ -178,6 +208,13 @@ class EncoderTrainer(_Trainer):
         self.H, self.heads = H, cfg["num_attention_heads"]
         self.ln_eps = cfg.get("layer_norm_eps", LN_EPS)
         spec = []
+        self._bias_keys = ()
+        if self._relpos:                                                 # (key, term of the table, buckets) of the matrices that exist
+            terms = ((("rel_pos_bias", 0, cfg["rel_pos_bins"]),) +
+                     ((("rel_pos_x_bias", 1, cfg["rel_2d_pos_bins"]), ("rel_pos_y_bias", 2, cfg["rel_2d_pos_bins"]))
+                      if cfg["has_spatial_attention_bias"] else ()))
+            self._bias_keys = tuple((f"{self.enc_prefix}encoder.{t}.weight", term, bins) for t, term, bins in terms)
+            spec += [(k, (cfg["num_attention_heads"], bins)) for k, _, bins in self._bias_keys]
         if self.train_embeddings:
             spec += _embedding_spec(self.enc_prefix, cfg)
             self._emb = self.enc_prefix + "embeddings."
@@ -188,7 +225,7 @@ class EncoderTrainer(_Trainer):
         for i in range(self.first, nl):
             spec += bert_layer_spec(f"{self.enc_prefix}encoder.layer.{i}", H, I)
         if self.pooled:
-            spec += [(self.enc_prefix + "pooler.dense.weight", (H, H)), (self.enc_prefix + "pooler.dense.bias", (H,))]
+            spec += [(self._pool + ".weight", (H, H)), (self._pool + ".bias", (H,))]
         spec += [(k, enc._head[k].shape) for k in head_keys]
         keys = tuple(k for k, _ in spec)
         sd = to_numpy({k: state_dict[k] for k in keys if k in state_dict})
@@ -228,6 +265,10 @@ class EncoderTrainer(_Trainer):
             self._masters[self._emb + "visual_projection.weight"] = p[self._emb + "visual_projection.weight"]
         self._w = self._masters if self._compute_dtype is None else {k: torch.empty_like(t, dtype=self._compute_dtype)
                                                                      for k, t in self._masters.items()}
+        if self._relpos:                                                 # the fold's entry -> bucket map, uploaded once
+            from .layoutlmv3 import relpos_bucket_map
+            self._r1, self._r2 = cfg["max_rel_pos"], cfg["max_rel_2d_pos"]
+            self._bucket = relpos_bucket_map(cfg["rel_pos_bins"], cfg["rel_2d_pos_bins"], self._r1, self._r2).to(dev)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         if self.max_grad_norm is not None:
             if not self.max_grad_norm > 0:
@@ -275,6 +316,50 @@ class EncoderTrainer(_Trainer):
         the residual path's)."""
         return dy if drop is None else dropout_add_f32(dy, None, drop)
 
+    # ---- LayoutLMv3's shared bias tables ------------------------------------------------------------------------------------------------
+    def _build_lut(self):
+        """The device table the attention kernels read, from the fp32 masters by a gather through the bucket map (`relpos_lut`'s
+        fold: T1 | TX | TY side by side); a term the config switches off is zeros."""
+        n1, n2 = 2 * self._r1 + 1, 2 * self._r2 + 1
+        lut = torch.zeros((self.heads, n1 + 2 * n2), dtype=torch.float32, device=self.device)
+        for k, term, _ in self._bias_keys:
+            off, n = (0, n1) if term == 0 else (n1 + (term - 1) * n2, n2)
+            lut[:, off:off + n] = self.p[k][:, self._bucket[off:off + n].long()]
+        return lut
+
+    def _frozen_forward(self, inputs):
+        """The frozen layers on the model's own kernels.  LayoutLMv3's frozen layers read the shared tables too, so they run with the
+        trainer's current table; the model's own is put back (only `commit()` writes it)."""
+        if not self._relpos:
+            return self.enc._hidden_after(self.first, *inputs)
+        own, self.enc._lut = self.enc._lut, self._lut
+        try:
+            return self.enc._hidden_after(self.first, *inputs)
+        finally:
+            self.enc._lut = own
+
+    def _attention(self, qkv, mask, B, Lx, drop):
+        if not self._relpos:
+            return attention(qkv, mask, B, Lx, self.heads, drop)
+        from .layoutlmv3 import attention_relpos
+        H, rel = self.H, self.enc._rel
+        return attention_relpos(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], rel, rel, self._lut, self._r1, self._r2, self.heads, mask)
+
+    def _attention_grad(self, qkv, mask, ctx, dctx, B, Lx, drop):
+        """-> dqkv.  LayoutLMv3: also the table's gradient, summed by bucket into the bias matrices' gradients; the layers are
+        walked top to bottom, the first writes and the others add, so the order of the sum is fixed."""
+        if not self._relpos:
+            return attention_grad(qkv, mask, ctx, dctx, B, Lx, self.heads, drop)
+        from .layoutlmv3 import attention_relpos_grad, relpos_lut_grad
+        H, rel = self.H, self.enc._rel
+        dqkv = torch.empty(qkv.shape, dtype=torch.float32, device=qkv.device)
+        *_, dlut = attention_relpos_grad(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ctx, dctx, rel, rel, self._lut, self._r1, self._r2,
+                                         self.heads, mask, out=tuple(dqkv[:, i * H:(i + 1) * H] for i in range(3)))
+        for k, term, _ in self._bias_keys:
+            relpos_lut_grad(dlut, self._bucket, self._r1, self._r2, term, self.g[k], accumulate=self._bias_seen)
+        self._bias_seen = True
+        return dqkv
+
     def _cast_weights(self):
         """The mixed mode's 16-bit copies of the trained weight matrices from the fp32 masters; the packed QKV master of a layer is
         one cast."""
@@ -289,7 +374,7 @@ class EncoderTrainer(_Trainer):
         P, p, w, pr = lay["prefix"], self.p, self._w, self._prec
         kept = {"x": pr.operand(x)}
         qkv = kept["qkv"] = pr.gemm(kept["x"], w[P + ".qkv"], lay["qkv_bias"], trans_b=True, out16=True)
-        ctx = kept["ctx"] = attention(qkv, mask, B, Lx, self.heads, self._drop(site, attention=True))
+        ctx = kept["ctx"] = self._attention(qkv, mask, B, Lx, self._drop(site, attention=True))
         t1 = pr.gemm(ctx, w[P + ".attention.output.dense.weight"], p[P + ".attention.output.dense.bias"], trans_b=True)
         kept["t1"] = self._residual(t1, x, self._drop(site + 1))         # the residual, fp32
         a = layernorm_f32(t1, p[P + ".attention.output.LayerNorm.weight"], p[P + ".attention.output.LayerNorm.bias"], self.ln_eps)
@@ -318,7 +403,7 @@ class EncoderTrainer(_Trainer):
         k = P + ".attention.output.LayerNorm"
         dt1, _, _ = layernorm_grad(kept["t1"], p[k + ".weight"], da, self.ln_eps, dgamma=g[k + ".weight"], dbeta=g[k + ".bias"])
         dctx = linear(self._undrop(dt1, self._drop(site + 1)), kept["ctx"], P + ".attention.output.dense", dx16=True)
-        dqkv = attention_grad(kept["qkv"], mask, kept["ctx"], dctx, B, Lx, self.heads, self._drop(site, attention=True))
+        dqkv = self._attention_grad(kept["qkv"], mask, kept["ctx"], dctx, B, Lx, self._drop(site, attention=True))
         dx = linear_backward(dqkv, kept["x"], w[P + ".qkv"], lay["g_qkv_weight"], lay["g_qkv_bias"], need_dx, prec=pr)
         return add_f32(dx, dt1, out=dx) if need_dx else None             # dX = dQKV . Wqkv + the residual path
 
@@ -417,13 +502,17 @@ class EncoderTrainer(_Trainer):
         enc, dev, p, g = self.enc, self.device, self.p, self.g
         enc._check(*inputs)
         Lx = inputs[0].shape[1] + (0 if self.pooled else inputs[1].shape[1])
+        if self.enc_prefix == "layoutlmv3." and inputs[4] is not None:   # the class token and the patch rows behind the text
+            Lx += (enc.cfg["input_size"] // enc.cfg["patch_size"]) ** 2 + 1
         idx = torch.from_numpy(self._head_rows(inputs, B, Lx)).to(dev)
         labels_dev = torch.from_numpy(lab).to(dev)
         if self.train_embeddings and not self.pooled and inputs[6] is not None:
             raise ValueError("image_text_alignment with train_embeddings=True: the mean over aligned positions is a weighted lookup, "
                              "whose backward is not built")
+        if self._relpos:
+            self._lut, self._bias_seen = self._build_lut(), False
         if not self.train_embeddings:
-            x, mask = enc._hidden_after(self.first, *inputs)
+            x, mask = self._frozen_forward(inputs)
             x = x.to(torch.float32).contiguous()                         # the boundary hidden state
         if self._compute_dtype is not None:
             self._cast_weights()
@@ -437,7 +526,7 @@ class EncoderTrainer(_Trainer):
         kw, kb = self.head + ".weight", self.head + ".bias"
         rows = gather_rows_f32(x, idx)
         if self.pooled:
-            pw, pb = self.enc_prefix + "pooler.dense.weight", self.enc_prefix + "pooler.dense.bias"
+            pw, pb = self._pool + ".weight", self._pool + ".bias"
             zp = gemm_f32(rows, p[pw], p[pb], trans_b=True)
             feats = act_f32(zp, L.VK_ACT_TANH)
         else:
@@ -472,13 +561,17 @@ class EncoderTrainer(_Trainer):
             lins.append((n + ".attention.self.qkv", *(P + ".attention.self." + t for t in ("query", "key", "value"))))
             lins += [(n + lin, P + lin) for lin in (".attention.output.dense", ".intermediate.dense", ".output.dense")]
             lns += [(n + ln, P + ln) for ln in (".attention.output.LayerNorm", ".output.LayerNorm")]
-        if self.pooled:
-            lins.append(("pooler.dense", self.enc_prefix + "pooler.dense"))
+        head_keys = (self.head + ".weight", self.head + ".bias")
+        if self.pooled:                                                  # `pooler.dense` in the encoder, or the head's own `classifier.dense`
+            lins.append((self._pool[len(self.enc_prefix):] if self._pool.startswith(self.enc_prefix) else self._pool, self._pool))
+            head_keys += tuple(k for k in (self._pool + ".weight", self._pool + ".bias") if k in self.enc._head)
         lins.append((self.head, self.head))
+        if self._relpos:                                                 # the model's own table, written here only
+            self.enc._lut.copy_(self._build_lut())
         if self.train_embeddings:                                        # the tables: one rounding to the storage type, on the device
             for t in self._tables:
                 self.enc._tab[t].copy_(self.p[self._emb + t + ".weight"])
             lns.append(("embeddings.LayerNorm", self._emb + "LayerNorm"))
             if not self.pooled:
                 lins.append(("embeddings.visual_projection", self._emb + "visual_projection"))
-        return self._commit(lins, lns, (self.head + ".weight", self.head + ".bias"))
+        return self._commit(lins, lns, head_keys)

@@ -10,7 +10,8 @@ materialised as [B, heads, L, L] (`LayoutLMv3Encoder.relative_position_bucket`, 
   relpos_triples         position ids and boxes -> the kernel's per-token (pos, x, y)
   attention_relpos       one launch of vk_attention_relpos on device tensors
   attention_relpos_form  which kernel that launch runs on, and the queries a workgroup of it serves
-
+  attention_relpos_grad  its backward: dq, dk, dv and the gradient of the table, one call of vk_attention_relpos_grad
+  relpos_bucket_map      the fold's map from table entry to bucket; relpos_lut_grad sums a table gradient back into a bias matrix's
 
 The model: `LayoutLMv3Model` (`LayoutLMv3Model.forward` :623-796) and its three inference heads (:799-823, :834-1121).  Its layers
 are the shared post-LN BERT layers of `bert_ops.BertOps` with that attention in place of the plain one; what is new on the device is
@@ -53,15 +54,22 @@ def relative_position_bucket(relative_position, num_buckets=32, max_distance=128
     return ret + torch.where(is_small, n, val_if_large)
 
 
+def relpos_bucket_map(rel_pos_bins, rel_2d_pos_bins, max_rel_pos=128, max_rel_2d_pos=256):
+    """int32 [(2 r1 + 1) + 2 (2 r2 + 1)] on the CPU: the bucket of every entry of the folded table, T1 | TX | TY side by side (entry
+    `delta + r` of a table holds the weight of delta's bucket)."""
+    return torch.cat([relative_position_bucket(torch.arange(-r, r + 1), bins, r)
+                      for bins, r in ((rel_pos_bins, max_rel_pos), (rel_2d_pos_bins, max_rel_2d_pos), (rel_2d_pos_bins, max_rel_2d_pos))]).to(torch.int32)
+
+
 def relpos_lut(rel_pos_bias, rel_pos_x_bias, rel_pos_y_bias, max_rel_pos=128, max_rel_2d_pos=256):
     """`encoder.rel_pos_bias.weight [heads, rel_pos_bins]`, `encoder.rel_pos_x_bias.weight` and `encoder.rel_pos_y_bias.weight
     [heads, rel_2d_pos_bins]` -> (lut [heads, (2 r1 + 1) + 2 (2 r2 + 1)] fp32 on the CPU, r1, r2): T1, TX, TY of a head side by side,
     entry `delta + r` of a table being the weight of delta's bucket.  The bucket is constant from max_distance on, so r = max_distance
     and a lookup by the clamped difference is exact."""
-    parts = []
-    for w, r in ((rel_pos_bias, max_rel_pos), (rel_pos_x_bias, max_rel_2d_pos), (rel_pos_y_bias, max_rel_2d_pos)):
-        w = torch.as_tensor(w, dtype=torch.float32)
-        parts.append(w[:, relative_position_bucket(torch.arange(-r, r + 1), w.shape[1], r)])
+    ws = [torch.as_tensor(w, dtype=torch.float32) for w in (rel_pos_bias, rel_pos_x_bias, rel_pos_y_bias)]
+    bucket = relpos_bucket_map(ws[0].shape[1], ws[1].shape[1], max_rel_pos, max_rel_2d_pos).long()
+    n1, n2 = 2 * max_rel_pos + 1, 2 * max_rel_2d_pos + 1
+    parts = [w[:, bucket[o:o + n]] for w, o, n in zip(ws, (0, n1, n1 + n2), (n1, n2, n2))]
     return torch.cat(parts, 1).contiguous(), max_rel_pos, max_rel_2d_pos
 
 
@@ -105,6 +113,59 @@ def attention_relpos(q, k, v, rel_q, rel_k, lut, r1, r2, heads, mask=None):
     L.call("vk_attention_relpos", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
            mask.data_ptr() if mask is not None else None, rel_q.data_ptr(), rel_k.data_ptr(), lut.data_ptr(), r1, r2, out.data_ptr(), H, B,
            heads, Lq, Lk, H // heads, _DT[q.dtype], stream(q.device))
+    return out
+
+
+def attention_relpos_grad(q, k, v, o, dout, rel_q, rel_k, lut, r1, r2, heads, mask=None, out=None):
+    """The backward of `attention_relpos` on its matrix-core form (bf16 / fp16, head dim 32 / 64): q, k, v, rel_q, rel_k, lut, r1,
+    r2, heads and mask as the forward took them, o its output and dout [B * Lq, heads * d] the gradient of that output, in the
+    type of q.  -> (dq [B * Lq, H], dk, dv [B * Lk, H], dlut [heads, (2 r1 + 1) + 2 (2 r2 + 1)]), all fp32; dlut is the gradient of
+    `lut`, summed in fixed point: the same bits on every run.  `out`: (dq, dk, dv) to write into, fp32 2-D tensors with unit column
+    stride (the column blocks of one [B * L, 3H] buffer are fine).  Everything the kernel refuses raises ValueError."""
+    B, Lq, Lk, H = rel_q.shape[0], rel_q.shape[1], rel_k.shape[1], q.shape[1]
+    dev = q.device
+    if out is None:
+        out = tuple(torch.empty((B * n, H), dtype=torch.float32, device=dev) for n in (Lq, Lk, Lk))
+    for name, t, rows, dt in (("q", q, B * Lq, q.dtype), ("k", k, B * Lk, q.dtype), ("v", v, B * Lk, q.dtype), ("o", o, B * Lq, q.dtype),
+                              ("dout", dout, B * Lq, q.dtype), ("dq", out[0], B * Lq, torch.float32), ("dk", out[1], B * Lk, torch.float32),
+                              ("dv", out[2], B * Lk, torch.float32)):
+        if t.dim() != 2 or tuple(t.shape) != (rows, H) or t.stride(1) != 1 or t.dtype != dt or t.device != dev:
+            raise ValueError(f"{name} must be [{rows}, {H}] of {dt} on {dev} with unit column stride, got {tuple(t.shape)} {t.dtype} {t.device}")
+    if q.dtype not in (torch.bfloat16, torch.float16) or H % heads:
+        raise ValueError(f"attention_relpos_grad takes bf16 or fp16 with heads dividing the width, got {q.dtype}, {H} columns, {heads} heads")
+    for name, t, shape in (("rel_q", rel_q, (B, Lq, 3)), ("rel_k", rel_k, (B, Lk, 3))):
+        if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be contiguous int32 {shape} on {dev}")
+    nlut = (2 * r1 + 1) + 2 * (2 * r2 + 1)
+    if tuple(lut.shape) != (heads, nlut) or lut.dtype != torch.float32 or not lut.is_contiguous() or lut.device != dev:
+        raise ValueError(f"lut must be contiguous fp32 [{heads}, {nlut}] on {dev}")
+    if mask is not None and (tuple(mask.shape) != (B, Lk) or mask.dtype != torch.float32 or not mask.is_contiguous() or mask.device != dev):
+        raise ValueError(f"mask must be contiguous fp32 [{B}, {Lk}] on {dev}")
+    dlut = torch.empty((heads, nlut), dtype=torch.float32, device=dev)
+    need = L.load().vk_attention_relpos_grad_workspace_bytes(B, heads, Lq, r1, r2)
+    ws = torch.empty((max(need, 8) // 8,), dtype=torch.int64, device=dev)
+    args = []
+    for t in (q, k, v):
+        args += [t.data_ptr(), t.stride(0)]
+    args += [mask.data_ptr() if mask is not None else None, rel_q.data_ptr(), rel_k.data_ptr(), lut.data_ptr(), r1, r2]
+    for t in (o, dout) + tuple(out):
+        args += [t.data_ptr(), t.stride(0)]
+    L.call("vk_attention_relpos_grad", *args, dlut.data_ptr(), B, heads, Lq, Lk, H // heads, _DT[q.dtype], ws.data_ptr(), need, stream(dev))
+    return out[0], out[1], out[2], dlut
+
+
+def relpos_lut_grad(dlut, bucket, r1, r2, term, out, accumulate=False):
+    """`out [heads, bins]` fp32 (a bias matrix's gradient) = or, with `accumulate`, += the entries of term `term` (0: the 1-D table,
+    1: x, 2: y) of `dlut` that share a bucket, by `bucket` (`relpos_bucket_map` on the device): fp64 sums in ascending entry order."""
+    heads, nlut = dlut.shape
+    if nlut != (2 * r1 + 1) + 2 * (2 * r2 + 1) or dlut.dtype != torch.float32 or not dlut.is_contiguous():
+        raise ValueError(f"dlut must be contiguous fp32 [heads, {(2 * r1 + 1) + 2 * (2 * r2 + 1)}], got {tuple(dlut.shape)} {dlut.dtype}")
+    if tuple(bucket.shape) != (nlut,) or bucket.dtype != torch.int32 or not bucket.is_contiguous() or bucket.device != dlut.device:
+        raise ValueError(f"bucket must be contiguous int32 [{nlut}] on {dlut.device}")
+    if out.dim() != 2 or out.shape[0] != heads or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dlut.device:
+        raise ValueError(f"out must be contiguous fp32 [{heads}, bins] on {dlut.device}")
+    L.call("vk_relpos_lut_grad", dlut.data_ptr(), heads, r1, r2, term, bucket.data_ptr(), out.shape[1], out.data_ptr(), int(accumulate),
+           stream(dlut.device))
     return out
 
 
