@@ -560,7 +560,7 @@ int vk_attention_route(int Lq, int Lk, int d, vk_dtype dt, int ldq, int ldk, int
  * takes 5132 bytes), a leading dimension below heads * d, q / k / v / out off their element's alignment or rel_q / rel_k / lut /
  * mask off 4 bytes, and whatever vk_attention_relpos_form refuses. */
 #define VK_RELPOS_FORM_MFMA 0     /* attention_relpos_kernel: 64-key tiles on the matrix cores, a workgroup per head and query run */
-#define VK_RELPOS_FORM_STRICT 1   /* attention_relpos_strict_kernel: 64-key fp32 tiles in LDS */
+#define VK_RELPOS_FORM_STRICT 1   /* attention_stream_kernel with the bias: 64-key fp32 tiles in LDS */
 int vk_attention_relpos_form(int Lq, int Lk, int d, vk_dtype dt, int ldq, int ldk, int ldv, int aligned16);
 int vk_attention_relpos_queries(int form, int Lq);
 int vk_attention_relpos_check(const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, const float *mask,

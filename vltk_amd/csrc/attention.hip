@@ -14,10 +14,14 @@
 // per tile m' = max(m, rowmax), a = exp(m - m'), p = exp(s - m'), O = a O + p V, l = a l + sum p; the output is O / l (a true
 // division), rounded once.  A padding key of the last tile scores -inf; no tile is all padding, so m is finite after the first tile
 // (a masked key scores about finfo.min, which is finite).
+//
+// attention_kernel and attention_mfma_kernel are written here; attention_tiled_kernel is attention_tiled.h's and
+// attention_stream_kernel attention_stream.h's (each shared with one more unit), and the matrix-core kernels' common device pieces
+// are attention_mma.h's.
 #include <cstdlib>
 
+#include "attention_stream.h"
 #include "attention_tiled.h"
-#include "vk_common.h"
 
 namespace vk {
 
@@ -120,7 +124,7 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const T *__restrict
                                                             const T *__restrict__ v, int ldv, const float *__restrict__ mask,
                                                             T *__restrict__ out, int ldo, int heads, int Lq, int Lk, int total,
                                                             float scale) {
-    typedef typename AttFrag<T>::type frag;
+    typedef typename Mma16<T>::frag frag;
     constexpr int KD = D / 32, NDB = D / 16;
     __shared__ __attribute__((aligned(16))) T lds[4][(48 + D) * ATT_PP];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -133,30 +137,12 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const T *__restrict
     T *pt = lds[wave], *vt = pt + 48 * ATT_PP;
     const frag zf = {};
 
-    // ---- operand fragments straight from memory ----
+    // ---- operand fragments straight from memory (a block past QB or KB lies past the sequence: zeros) ----
     frag qf[ATT_MAXQB][KD], kf[ATT_MAXKB][KD];
 #pragma unroll
-    for (int qb = 0; qb < ATT_MAXQB; ++qb) {
-        const int r = qb * 16 + j;
-        const bool ok = qb < QB && r < Lq;
-        const T *src = q + ((long)b * Lq + (ok ? r : 0)) * ldq + h * D + g * 8;
+    for (int qb = 0; qb < ATT_MAXQB; ++qb) att_row_frags<T, KD>(qf[qb], q + (long)b * Lq * ldq + h * D, ldq, qb * 16 + j, Lq, g);
 #pragma unroll
-        for (int ks = 0; ks < KD; ++ks) {
-            const frag t = *reinterpret_cast<const frag *>(src + ks * 32);
-            qf[qb][ks] = ok ? t : zf;
-        }
-    }
-#pragma unroll
-    for (int kb = 0; kb < ATT_MAXKB; ++kb) {
-        const int r = kb * 16 + j;
-        const bool ok = kb < KB && r < Lk;
-        const T *src = k + ((long)b * Lk + (ok ? r : 0)) * ldk + h * D + g * 8;
-#pragma unroll
-        for (int ks = 0; ks < KD; ++ks) {
-            const frag t = *reinterpret_cast<const frag *>(src + ks * 32);
-            kf[kb][ks] = ok ? t : zf;
-        }
-    }
+    for (int kb = 0; kb < ATT_MAXKB; ++kb) att_row_frags<T, KD>(kf[kb], k + (long)b * Lk * ldk + h * D, ldk, kb * 16 + j, Lk, g);
     // ---- V^T image: vt[d][key], zero for the padded keys ----
     {
         constexpr int CH = D / 8;                        // 16-byte chunks per V row
@@ -169,15 +155,15 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const T *__restrict
         }
     }
     // ---- S = Q K^T * scale + mask ----
-    att_f4 sc[ATT_MAXQB][ATT_MAXKB];
+    m16_f4 sc[ATT_MAXQB][ATT_MAXKB];
 #pragma unroll
     for (int qb = 0; qb < ATT_MAXQB; ++qb)
 #pragma unroll
         for (int kb = 0; kb < ATT_MAXKB; ++kb) {
-            att_f4 a = {0.f, 0.f, 0.f, 0.f};
+            m16_f4 a = {0.f, 0.f, 0.f, 0.f};
             if (qb < QB && kb < KB) {
 #pragma unroll
-                for (int ks = 0; ks < KD; ++ks) a = AttFrag<T>::mma(qf[qb][ks], kf[kb][ks], a);
+                for (int ks = 0; ks < KD; ++ks) a = Mma16<T>::mma(qf[qb][ks], kf[kb][ks], a);
             }
             const int key = kb * 16 + j;
             const float m = key < Lk ? (mask ? mask[(long)b * Lk + key] : 0.f) : -INFINITY;
@@ -221,112 +207,18 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const T *__restrict
         for (int k2 = 0; k2 < 2; ++k2) pf[k2] = *reinterpret_cast<const frag *>(pt + (qb * 16 + j) * ATT_PP + k2 * 32 + g * 8);
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
-            att_f4 o = {0.f, 0.f, 0.f, 0.f};
+            m16_f4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2) {
                 if (k2 >= KS2) continue;
                 const frag vf = *reinterpret_cast<const frag *>(vt + (db * 16 + j) * ATT_PP + k2 * 32 + g * 8);
-                o = AttFrag<T>::mma(pf[k2], vf, o);
+                o = Mma16<T>::mma(pf[k2], vf, o);
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int row = qb * 16 + g * 4 + e;
                 if (live && row < Lq) out[((long)b * Lq + row) * ldo + h * D + db * 16 + j] = (T)o[e];
             }
-        }
-    }
-}
-
-// ---- the strict form ----
-// One workgroup per (batch, head, block of 16 queries).  The Q block and a 64-key K / V tile are staged in LDS as fp32 (K and Q
-// rows padded by one float, as attention_kernel pads them); 256 threads share the 16 x 64 scores, a wave owns every fourth
-// row's running maximum and sum, then a thread owns up to 16 of the 16 x d outputs in registers across the tiles.
-constexpr int STR_QB = 16, STR_KT = 64, STR_MAXD = 256;
-constexpr int STR_OUT = STR_QB * STR_MAXD / 256;          // outputs per thread at the largest head dim
-
-static size_t stream_lds_bytes(int d) {
-    return ((size_t)(STR_QB + STR_KT) * (d + 1) + (size_t)STR_KT * d + (size_t)STR_QB * (STR_KT + 1) + 3 * STR_QB) * sizeof(float);
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void attention_stream_kernel(const T *__restrict__ q, int ldq, const T *__restrict__ k, int ldk,
-                                                              const T *__restrict__ v, int ldv, const float *__restrict__ mask,
-                                                              T *__restrict__ out, int ldo, int heads, int Lq, int Lk, int d, int nqb,
-                                                              float scale) {
-    extern __shared__ float str_lds[];
-    const int dp = d + 1, lp = STR_KT + 1;
-    float *qs = str_lds, *ks = qs + STR_QB * dp, *vs = ks + STR_KT * dp, *ps = vs + STR_KT * d, *ms = ps + STR_QB * lp,
-          *ls = ms + STR_QB, *as = ls + STR_QB;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int bh = blockIdx.x / nqb, q0 = (blockIdx.x - bh * nqb) * STR_QB;
-    const int b = bh / heads, h = bh - b * heads;
-    const int nq = min(STR_QB, Lq - q0);
-    for (int i = tid; i < STR_QB * d; i += 256) {
-        const int r = i / d, c = i - r * d;
-        qs[r * dp + c] = r < nq ? ldf(q + ((long)b * Lq + q0 + r) * ldq + h * d + c) : 0.f;
-    }
-    if (tid < STR_QB) {
-        ms[tid] = -INFINITY;
-        ls[tid] = 0.f;
-    }
-    float o[STR_OUT];
-#pragma unroll
-    for (int n = 0; n < STR_OUT; ++n) o[n] = 0.f;
-
-    for (int k0 = 0; k0 < Lk; k0 += STR_KT) {
-        const int nk = min(STR_KT, Lk - k0);
-        for (int i = tid; i < STR_KT * d; i += 256) {
-            const int r = i / d, c = i - r * d;
-            const bool ok = r < nk;
-            ks[r * dp + c] = ok ? ldf(k + ((long)b * Lk + k0 + r) * ldk + h * d + c) : 0.f;
-            vs[i] = ok ? ldf(v + ((long)b * Lk + k0 + r) * ldv + h * d + c) : 0.f;
-        }
-        __syncthreads();
-        for (int i = tid; i < STR_QB * STR_KT; i += 256) {
-            const int r = i / STR_KT, jj = i - r * STR_KT;
-            float s = 0.f;
-            for (int c = 0; c < d; ++c) s += qs[r * dp + c] * ks[jj * dp + c];
-            ps[r * lp + jj] = jj < nk ? s * scale + (mask ? mask[(long)b * Lk + k0 + jj] : 0.f) : -INFINITY;
-        }
-        __syncthreads();
-        for (int r = wave; r < STR_QB; r += 4) {
-            const float x = ps[r * lp + lane];
-            float mx = x;
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-            const float mo = ms[r], mn = fmaxf(mo, mx);
-            const float alpha = expf(mo - mn);                   // first tile: exp(-inf) = 0
-            const float p = expf(x - mn);                        // padded keys: exp(-inf) = 0
-            ps[r * lp + lane] = p;
-            float sum = p;
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor(sum, s, 64);
-            const float lo = ls[r];
-            if (lane == 0) {
-                ms[r] = mn;
-                ls[r] = alpha * lo + sum;
-                as[r] = alpha;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int n = 0; n < STR_OUT; ++n) {
-            const int i = tid + 256 * n;
-            if (i < STR_QB * d) {
-                const int r = i / d, c = i - r * d;
-                float acc = as[r] * o[n];
-                for (int jj = 0; jj < STR_KT; ++jj) acc += ps[r * lp + jj] * vs[jj * d + c];
-                o[n] = acc;
-            }
-        }
-        __syncthreads();            // the next tile overwrites K, V and the scores
-    }
-#pragma unroll
-    for (int n = 0; n < STR_OUT; ++n) {
-        const int i = tid + 256 * n;
-        if (i < STR_QB * d) {
-            const int r = i / d, c = i - r * d;
-            if (r < nq) out[((long)b * Lq + q0 + r) * ldo + h * d + c] = (T)(o[n] / ls[r]);
         }
     }
 }
@@ -383,7 +275,7 @@ static int mfma_launch(const AttArgs &a, float scale, hipStream_t s) {
 template <typename T>
 static int stream_launch(const AttArgs &a, float scale, hipStream_t s) {
     const int nqb = (a.Lq + STR_QB - 1) / STR_QB;
-    return launch_lds(attention_stream_kernel<T>, dim3(a.B * a.heads * nqb), dim3(256), stream_lds_bytes(a.d), stream_lds_bytes(STR_MAXD), s,
+    return launch_lds(attention_stream_kernel<T, false>, dim3(a.B * a.heads * nqb), dim3(256), stream_lds_bytes(a.d), stream_lds_bytes(STR_MAXD), s,
                       VK_ATT_IO(T), a.d, nqb, scale);
 }
 
@@ -391,23 +283,12 @@ static int stream_launch(const AttArgs &a, float scale, hipStream_t s) {
 static int launch_attention(int route, const AttArgs &a, hipStream_t s) {
     const float scale = 1.0f / sqrtf((float)a.d);
     VK_REQUIRE((long)a.B * a.heads * ((a.Lq + 15) / 16) < (1L << 31), VK_EINVAL, "attention: too many (batch, head, query block) items");
-    const bool f16 = a.dt == VK_F16, d64 = a.d == 64;
     int st = VK_EINVAL;
     switch (route) {
-        case VK_ATT_ROUTE_MFMA:
-            st = f16 ? (d64 ? mfma_launch<_Float16, 64>(a, scale, s) : mfma_launch<_Float16, 32>(a, scale, s))
-                     : (d64 ? mfma_launch<__bf16, 64>(a, scale, s) : mfma_launch<__bf16, 32>(a, scale, s));
-            break;
-        case VK_ATT_ROUTE_TILED:
-            st = f16 ? (d64 ? tiled_launch<_Float16, 64>(a, scale, s) : tiled_launch<_Float16, 32>(a, scale, s))
-                     : (d64 ? tiled_launch<__bf16, 64>(a, scale, s) : tiled_launch<__bf16, 32>(a, scale, s));
-            break;
-        case VK_ATT_ROUTE_LDS:
-            st = a.dt == VK_F32 ? lds_launch<float>(a, scale, s) : f16 ? lds_launch<_Float16>(a, scale, s) : lds_launch<__bf16>(a, scale, s);
-            break;
-        case VK_ATT_ROUTE_STREAM:
-            st = a.dt == VK_F32 ? stream_launch<float>(a, scale, s) : f16 ? stream_launch<_Float16>(a, scale, s) : stream_launch<__bf16>(a, scale, s);
-            break;
+        case VK_ATT_ROUTE_MFMA: VK_DT16_D_SWITCH(a.dt, a.d, st = mfma_launch<T, D>(a, scale, s)); break;
+        case VK_ATT_ROUTE_TILED: VK_DT16_D_SWITCH(a.dt, a.d, st = tiled_launch<T, D>(a, scale, s)); break;
+        case VK_ATT_ROUTE_LDS: VK_DT_SWITCH(a.dt, "attention", st = lds_launch<T>(a, scale, s)); break;
+        case VK_ATT_ROUTE_STREAM: VK_DT_SWITCH(a.dt, "attention", st = stream_launch<T>(a, scale, s)); break;
         default: VK_REQUIRE(false, VK_EINVAL, "attention: route %d names no kernel", route);
     }
     VK_TRY(st);

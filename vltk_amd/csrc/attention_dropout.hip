@@ -10,9 +10,9 @@ namespace vk {
 static int launch_attention_dropout(const AttArgs &a, const DropArgs &da, hipStream_t s) {
     const float scale = 1.0f / sqrtf((float)a.d);
     VK_REQUIRE((long)a.B * a.heads * ((a.Lq + 15) / 16) < (1L << 31), VK_EINVAL, "attention: too many (batch, head, query block) items");
-    const bool f16 = a.dt == VK_F16, d64 = a.d == 64;
-    VK_TRY(f16 ? (d64 ? tiled_drop_launch<_Float16, 64>(a, scale, da, s) : tiled_drop_launch<_Float16, 32>(a, scale, da, s))
-               : (d64 ? tiled_drop_launch<__bf16, 64>(a, scale, da, s) : tiled_drop_launch<__bf16, 32>(a, scale, da, s)));
+    int st = VK_EINVAL;
+    VK_DT16_D_SWITCH(a.dt, a.d, st = tiled_launch<T, D>(a, scale, s, da));
+    VK_TRY(st);
     VK_CHECK_HIP(hipGetLastError());
     return VK_OK;
 }
@@ -68,10 +68,7 @@ int vk_attention_grad_16_dropout(const void *q, long ldq, const void *k, long ld
                              B, heads, Lq, Lk, 1.0f / sqrtf((float)d)};
     const int t = dropout_threshold(p);
     const DropArgs da = {(uint32_t)t, dropout_scale(t), seed, drop_stream};
-    hipStream_t s = (hipStream_t)stream;
-    if (dt == VK_BF16) return d == 64 ? ag16_drop_launch<__bf16, 64>(a, da, s) : ag16_drop_launch<__bf16, 32>(a, da, s);
-    return d == 64 ? ag16_drop_launch<_Float16, 64>(a, da, s) : ag16_drop_launch<_Float16, 32>(a, da, s);
+    VK_DT16_D_SWITCH(dt, d, return ag16_launch<T, D>(a, (hipStream_t)stream, da));
 }
-
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// The backward of the 16-bit attention forward (attention_tiled_kernel of attention.hip) on the matrix cores: what mixed-precision
+// The backward of the 16-bit attention forward (attention_tiled_kernel of attention_tiled.h) on the matrix cores: what mixed-precision
 // fine-tuning needs beside gemm16.hip.  q, k, v, o and dout are bf16 / fp16; dq, dk and dv are fp32.  It
 // keeps the ownership scheme of attention_grad.hip, so it needs no atomics and no split accumulation: every output element has
 // one writer and one fixed summation order, and the same input gives the same bits.
@@ -47,13 +47,16 @@
 // block 4 qb + (j >> 2) and key block g: the 4 x 4 block is its own transpose, so the three kernels agree.  LDS as above; VGPRs
 // as the compiler reports them, plain -> DROP: dQ 94 -> 100 (d = 64), 74 -> 82 (d = 32); dK/dV 98 -> 108, 88 -> 90: both keep
 // four waves per SIMD at d = 64.  DROP = false takes no trailing argument and is the kernel as it was.
+//
+// Row fragments, the transposed images, the online row update of pass 1 (att_online_row), D, the statistics store,
+// the image products and the scaled stores are attention_mma.h's; what stays here is how a score, dP and dS are formed.
 #pragma once
-#include "mfma16.h"
+#include "attention_mma.h"
 #include "philox.h"
 
 namespace vk {
 
-constexpr int AG16_OWN = 16, AG16_STEP = 64, AG16_PP = 72;
+constexpr int AG16_OWN = 16;                        // queries (dQ kernel) or keys (dK/dV kernel) a wave owns
 
 struct AttGrad16Args {
     const void *q, *k, *v, *o, *dout;
@@ -65,51 +68,14 @@ struct AttGrad16Args {
     float scale;
 };
 
-// the forward's exponential (tat_exp of attention.hip): exp(0) = 1 and exp(-inf) = 0 exactly
-static __device__ __forceinline__ float ag16_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-
-// row r of a sequence of R rows that starts at `base` (row 0, this head's first column): the lane's fragments of the KD 32-wide
-// slices, zero for a row outside the sequence
-template <typename T, int KD>
-__device__ __forceinline__ void ag16_row_frags(typename Mma16<T>::frag (&f)[KD], const T *base, long ld, int r, int R, int g) {
-    typedef typename Mma16<T>::frag frag;
-    const bool ok = r < R;
-    const T *src = base + (long)(ok ? r : 0) * ld + g * 8;
-#pragma unroll
-    for (int ks = 0; ks < KD; ++ks) {
-        const frag t = *reinterpret_cast<const frag *>(src + ks * 32);
-        f[ks] = ok ? t : frag{};
-    }
-}
-
-// rows [r0, r0 + 64) of that sequence, transposed, into img[c][row - r0] (pitch AG16_PP), zero for the rows outside it: a lane
-// takes two rows and half of their 16-byte chunks, and writes (row, row + 1) pairs as words (attention_tiled_kernel's V^T image)
-template <typename T, int D>
-__device__ __forceinline__ void ag16_image_t(T *img, const T *base, long ld, int r0, int R, int lane) {
-    typedef typename Mma16<T>::frag frag;
-    constexpr int HALF = D / 16;
-    unsigned *img32 = reinterpret_cast<unsigned *>(img);
-    const int kp = lane & 31, c0 = (lane >> 5) * HALF;
-    const int row = r0 + 2 * kp;
-#pragma unroll
-    for (int it = 0; it < HALF; ++it) {
-        const int c = c0 + it;
-        frag t0 = {}, t1 = {};
-        if (row < R) t0 = *reinterpret_cast<const frag *>(base + (long)row * ld + c * 8);
-        if (row + 1 < R) t1 = *reinterpret_cast<const frag *>(base + (long)(row + 1) * ld + c * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) img32[((c * 8 + e) * AG16_PP) / 2 + kp] = pack16<T>(t0[e], t1[e]);
-    }
-}
-
 template <typename T, int D, bool DROP, typename... DA>
 __global__ __launch_bounds__(64) void ag16_dq_kernel(AttGrad16Args a, int nqb, DA... drop) {
     static_assert(sizeof...(DA) == (DROP ? 1 : 0), "a DropArgs behind the arguments of the DROP form, nothing otherwise");
     const DropArgs da = drop_args_of(drop...);
     typedef typename Mma16<T>::frag frag;
-    constexpr int KD = D / 32, NDB = D / 16, KB = AG16_STEP / 16;
+    constexpr int KD = D / 32, NDB = D / 16, KB = ATT_KT / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char ag16_lds[];
-    T *dsi = reinterpret_cast<T *>(ag16_lds), *kt = dsi + AG16_OWN * AG16_PP;
+    T *dsi = reinterpret_cast<T *>(ag16_lds), *kt = dsi + AG16_OWN * ATT_PP;
     const int lane = threadIdx.x, g = lane >> 4, j = lane & 15;
     const int bh = blockIdx.x / nqb, q0 = (blockIdx.x - bh * nqb) * AG16_OWN;
     const int b = bh / a.heads, h = bh - b * a.heads;
@@ -122,8 +88,8 @@ __global__ __launch_bounds__(64) void ag16_dq_kernel(AttGrad16Args a, int nqb, D
     const float *mrow = a.mask ? a.mask + (long)b * a.Lk : nullptr;
 
     frag qf[KD], dof[KD];
-    ag16_row_frags<T, KD>(qf, qb_, a.ldq, j, nq, g);
-    ag16_row_frags<T, KD>(dof, dob, a.lddo, j, nq, g);
+    att_row_frags<T, KD>(qf, qb_, a.ldq, j, nq, g);
+    att_row_frags<T, KD>(dof, dob, a.lddo, j, nq, g);
 
     // ---- pass 1: m and l of rows 4 g + e, online over the key tiles as the forward keeps them ----
     float m[4], l[4];
@@ -132,12 +98,12 @@ __global__ __launch_bounds__(64) void ag16_dq_kernel(AttGrad16Args a, int nqb, D
         m[e] = -INFINITY;
         l[e] = 0.f;
     }
-    for (int k0 = 0; k0 < a.Lk; k0 += AG16_STEP) {
+    for (int k0 = 0; k0 < a.Lk; k0 += ATT_KT) {
         m16_f4 sc[KB];
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
             frag kf[KD];
-            ag16_row_frags<T, KD>(kf, kbase, a.ldk, k0 + kb * 16 + j, a.Lk, g);
+            att_row_frags<T, KD>(kf, kbase, a.ldk, k0 + kb * 16 + j, a.Lk, g);
             m16_f4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KD; ++ks) s = Mma16<T>::mma(qf[ks], kf[ks], s);
@@ -149,61 +115,20 @@ __global__ __launch_bounds__(64) void ag16_dq_kernel(AttGrad16Args a, int nqb, D
             sc[kb] = s;
         }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float mx = sc[0][e];
-#pragma unroll
-            for (int kb = 1; kb < KB; ++kb) mx = fmaxf(mx, sc[kb][e]);
-#pragma unroll
-            for (int s = 8; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-            const float mn = fmaxf(m[e], mx);
-            const float alpha = ag16_exp(m[e] - mn);            // first tile: exp(-inf) = 0
-            float sum = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) sum += ag16_exp(sc[kb][e] - mn);      // keys outside: exp(-inf) = 0
-#pragma unroll
-            for (int s = 8; s > 0; s >>= 1) sum += __shfl_xor(sum, s, 64);
-            m[e] = mn;
-            l[e] = fmaf(alpha, l[e], sum);
-        }
+        for (int e = 0; e < 4; ++e) att_online_row(sc, e, m[e], l[e]);
     }
     float il[4], dd[4];
-    {
-        // D of row j: this lane's 8 KD columns, then the four lanes of the row; rows 4 g + e fetch theirs from lanes 4 g + e
-        float part = 0.f;
-        frag of[KD];
-        ag16_row_frags<T, KD>(of, ob, a.ldo, j, nq, g);
-#pragma unroll
-        for (int ks = 0; ks < KD; ++ks)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) part = fmaf((float)dof[ks][e], (float)of[ks][e], part);
-        part += __shfl_xor(part, 16, 64);
-        part += __shfl_xor(part, 32, 64);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            dd[e] = __shfl(part, 4 * g + e, 64);
-            il[e] = 1.0f / l[e];
-        }
-    }
-    if (j == 0) {
-        const long n = (long)a.B * a.heads * a.Lq;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int r = 4 * g + e;
-            if (r < nq) {
-                const long srow = (long)bh * a.Lq + q0 + r;
-                a.stats[srow] = m[e];
-                a.stats[n + srow] = il[e];
-                a.stats[2 * n + srow] = dd[e];
-            }
-        }
-    }
+    frag of[KD];
+    att_row_frags<T, KD>(of, ob, a.ldo, j, nq, g);
+    att_grad_d<T, KD>(dd, il, dof, of, l, g);
+    att_store_stats(a.stats, (long)a.B * a.heads * a.Lq, (long)bh * a.Lq + q0, nq, m, il, dd, g, j);
 
     // ---- pass 2: dQ ----
     m16_f4 acc[NDB];
 #pragma unroll
     for (int db = 0; db < NDB; ++db) acc[db] = m16_f4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < a.Lk; k0 += AG16_STEP) {
-        ag16_image_t<T, D>(kt, kbase, a.ldk, k0, a.Lk, lane);
+    for (int k0 = 0; k0 < a.Lk; k0 += ATT_KT) {
+        att_image_t<T, D>(kt, kbase, a.ldk, k0, a.Lk, lane);
         uint32_t keep[KB] = {};
         if constexpr (DROP) {
             drop_tile_bits(keep, da, (uint64_t)bh * ((a.Lq + 3) >> 2), (uint64_t)((a.Lk + 3) >> 2), q0 >> 2, k0 >> 2, true, g, j);
@@ -213,8 +138,8 @@ __global__ __launch_bounds__(64) void ag16_dq_kernel(AttGrad16Args a, int nqb, D
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
             frag kf[KD], vf[KD];
-            ag16_row_frags<T, KD>(kf, kbase, a.ldk, k0 + kb * 16 + j, a.Lk, g);
-            ag16_row_frags<T, KD>(vf, vbase, a.ldv, k0 + kb * 16 + j, a.Lk, g);
+            att_row_frags<T, KD>(kf, kbase, a.ldk, k0 + kb * 16 + j, a.Lk, g);
+            att_row_frags<T, KD>(vf, vbase, a.ldv, k0 + kb * 16 + j, a.Lk, g);
             m16_f4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KD; ++ks) {
@@ -228,33 +153,18 @@ __global__ __launch_bounds__(64) void ag16_dq_kernel(AttGrad16Args a, int nqb, D
             for (int e = 0; e < 4; ++e) {
                 float dsv = 0.f;
                 if (okk && 4 * g + e < nq) {
-                    const float p = ag16_exp(fmaf(s[e], a.scale, mk) - m[e]) * il[e];
+                    const float p = att_exp(fmaf(s[e], a.scale, mk) - m[e]) * il[e];
                     if constexpr (DROP) dsv = p * (((keep[kb] >> e) & 1u ? da.rs * dp[e] : 0.f) - dd[e]);
                     else dsv = p * (dp[e] - dd[e]);
                 }
-                dsi[(4 * g + e) * AG16_PP + kb * 16 + j] = (T)dsv;
+                dsi[(4 * g + e) * ATT_PP + kb * 16 + j] = (T)dsv;
             }
         }
         __syncthreads();
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-            const frag pf = *reinterpret_cast<const frag *>(dsi + j * AG16_PP + k2 * 32 + g * 8);
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) {
-                const frag kf = *reinterpret_cast<const frag *>(kt + (db * 16 + j) * AG16_PP + k2 * 32 + g * 8);
-                acc[db] = Mma16<T>::mma(pf, kf, acc[db]);
-            }
-        }
+        att_image_mma<T, NDB>(acc, dsi, kt, g, j);
         __syncthreads();            // the next tile overwrites the images
     }
-    float *dqb = a.dq + ((long)b * a.Lq + q0) * a.lddq + h * D;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int r = 4 * g + e;
-        if (r >= nq) continue;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) dqb[(long)r * a.lddq + db * 16 + j] = acc[db][e] * a.scale;
-    }
+    att_store_rows<NDB>(a.dq + ((long)b * a.Lq + q0) * a.lddq + h * D, a.lddq, acc, a.scale, nq, g, j);
 }
 
 template <typename T, int D, bool DROP, typename... DA>
@@ -262,9 +172,9 @@ __global__ __launch_bounds__(64) void ag16_dkv_kernel(AttGrad16Args a, int nkb, 
     static_assert(sizeof...(DA) == (DROP ? 1 : 0), "a DropArgs behind the arguments of the DROP form, nothing otherwise");
     const DropArgs da = drop_args_of(drop...);
     typedef typename Mma16<T>::frag frag;
-    constexpr int KD = D / 32, NDB = D / 16, QB = AG16_STEP / 16;
+    constexpr int KD = D / 32, NDB = D / 16, QB = ATT_KT / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char ag16_lds[];
-    T *pt = reinterpret_cast<T *>(ag16_lds), *dst = pt + AG16_OWN * AG16_PP, *qt = dst + AG16_OWN * AG16_PP, *dot = qt + D * AG16_PP;
+    T *pt = reinterpret_cast<T *>(ag16_lds), *dst = pt + AG16_OWN * ATT_PP, *qt = dst + AG16_OWN * ATT_PP, *dot = qt + D * ATT_PP;
     const int lane = threadIdx.x, g = lane >> 4, j = lane & 15;
     const int bh = blockIdx.x / nkb, j0 = (blockIdx.x - bh * nkb) * AG16_OWN;
     const int b = bh / a.heads, h = bh - b * a.heads;
@@ -277,8 +187,8 @@ __global__ __launch_bounds__(64) void ag16_dkv_kernel(AttGrad16Args a, int nkb, 
     const float *st = a.stats + (long)bh * a.Lq;
 
     frag kf[KD], vf[KD];
-    ag16_row_frags<T, KD>(kf, kb_, a.ldk, j, nk, g);
-    ag16_row_frags<T, KD>(vf, vb_, a.ldv, j, nk, g);
+    att_row_frags<T, KD>(kf, kb_, a.ldk, j, nk, g);
+    att_row_frags<T, KD>(vf, vb_, a.ldv, j, nk, g);
     float mk[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) mk[e] = a.mask && 4 * g + e < nk ? a.mask[(long)b * a.Lk + j0 + 4 * g + e] : 0.f;
@@ -286,9 +196,9 @@ __global__ __launch_bounds__(64) void ag16_dkv_kernel(AttGrad16Args a, int nkb, 
     m16_f4 acck[NDB], accv[NDB];
 #pragma unroll
     for (int db = 0; db < NDB; ++db) acck[db] = accv[db] = m16_f4{0.f, 0.f, 0.f, 0.f};
-    for (int q0 = 0; q0 < a.Lq; q0 += AG16_STEP) {
-        ag16_image_t<T, D>(qt, qbase, a.ldq, q0, a.Lq, lane);
-        ag16_image_t<T, D>(dot, dobase, a.lddo, q0, a.Lq, lane);
+    for (int q0 = 0; q0 < a.Lq; q0 += ATT_KT) {
+        att_image_t<T, D>(qt, qbase, a.ldq, q0, a.Lq, lane);
+        att_image_t<T, D>(dot, dobase, a.lddo, q0, a.Lq, lane);
         uint32_t keep[QB] = {};
         if constexpr (DROP) {
             drop_tile_bits(keep, da, (uint64_t)bh * ((a.Lq + 3) >> 2), (uint64_t)((a.Lk + 3) >> 2), q0 >> 2, j0 >> 2, false, g, j);
@@ -300,8 +210,8 @@ __global__ __launch_bounds__(64) void ag16_dkv_kernel(AttGrad16Args a, int nkb, 
             const int qr = q0 + qb * 16 + j;
             const bool okq = qr < a.Lq;
             frag qf[KD], dof[KD];
-            ag16_row_frags<T, KD>(qf, qbase, a.ldq, qr, a.Lq, g);
-            ag16_row_frags<T, KD>(dof, dobase, a.lddo, qr, a.Lq, g);
+            att_row_frags<T, KD>(qf, qbase, a.ldq, qr, a.Lq, g);
+            att_row_frags<T, KD>(dof, dobase, a.lddo, qr, a.Lq, g);
             m16_f4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KD; ++ks) {
@@ -313,7 +223,7 @@ __global__ __launch_bounds__(64) void ag16_dkv_kernel(AttGrad16Args a, int nkb, 
             for (int e = 0; e < 4; ++e) {
                 float p = 0.f, dsv = 0.f;
                 if (okq && 4 * g + e < nk) {
-                    p = ag16_exp(fmaf(s[e], a.scale, mk[e]) - mm) * il;
+                    p = att_exp(fmaf(s[e], a.scale, mk[e]) - mm) * il;
                     if constexpr (DROP) {
                         const bool kept = (keep[qb] >> (8 * e)) & 1u;
                         dsv = p * ((kept ? da.rs * dp[e] : 0.f) - dd);
@@ -322,19 +232,20 @@ __global__ __launch_bounds__(64) void ag16_dkv_kernel(AttGrad16Args a, int nkb, 
                         dsv = p * (dp[e] - dd);
                     }
                 }
-                pt[(4 * g + e) * AG16_PP + qb * 16 + j] = (T)p;
-                dst[(4 * g + e) * AG16_PP + qb * 16 + j] = (T)dsv;
+                pt[(4 * g + e) * ATT_PP + qb * 16 + j] = (T)p;
+                dst[(4 * g + e) * ATT_PP + qb * 16 + j] = (T)dsv;
             }
         }
         __syncthreads();
+        // the two products interleaved: att_image_mma's step, for two accumulators at once
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2) {
-            const frag pf = *reinterpret_cast<const frag *>(pt + j * AG16_PP + k2 * 32 + g * 8);
-            const frag sf = *reinterpret_cast<const frag *>(dst + j * AG16_PP + k2 * 32 + g * 8);
+            const frag pf = *reinterpret_cast<const frag *>(pt + j * ATT_PP + k2 * 32 + g * 8);
+            const frag sf = *reinterpret_cast<const frag *>(dst + j * ATT_PP + k2 * 32 + g * 8);
 #pragma unroll
             for (int db = 0; db < NDB; ++db) {
-                const frag of = *reinterpret_cast<const frag *>(dot + (db * 16 + j) * AG16_PP + k2 * 32 + g * 8);
-                const frag qf = *reinterpret_cast<const frag *>(qt + (db * 16 + j) * AG16_PP + k2 * 32 + g * 8);
+                const frag of = *reinterpret_cast<const frag *>(dot + (db * 16 + j) * ATT_PP + k2 * 32 + g * 8);
+                const frag qf = *reinterpret_cast<const frag *>(qt + (db * 16 + j) * ATT_PP + k2 * 32 + g * 8);
                 accv[db] = Mma16<T>::mma(pf, of, accv[db]);
                 acck[db] = Mma16<T>::mma(sf, qf, acck[db]);
             }
@@ -387,22 +298,14 @@ static int ag16_check(const void *q, long ldq, const void *k, long ldk, const vo
     return VK_OK;
 }
 
-template <typename T, int D>
-static int ag16_launch(const AttGrad16Args &a, hipStream_t s) {
+// the DROP forms (a DropArgs behind the stream) have the same grids and LDS
+template <typename T, int D, typename... DA>
+static int ag16_launch(const AttGrad16Args &a, hipStream_t s, DA... da) {
+    constexpr bool DROP = sizeof...(DA) != 0;
     const int nqb = ceil_div(a.Lq, AG16_OWN), nkb = ceil_div(a.Lk, AG16_OWN);
-    const size_t lq = (size_t)(AG16_OWN + D) * AG16_PP * sizeof(T), lk = (size_t)(2 * AG16_OWN + 2 * D) * AG16_PP * sizeof(T);
-    VK_TRY(launch_lds(ag16_dq_kernel<T, D, false>, dim3(a.B * a.heads * nqb), dim3(64), lq, lq, s, a, nqb));
-    VK_TRY(launch_lds(ag16_dkv_kernel<T, D, false>, dim3(a.B * a.heads * nkb), dim3(64), lk, lk, s, a, nkb));
-    return VK_OK;
-}
-
-// the DROP forms: the same grids and LDS
-template <typename T, int D>
-static int ag16_drop_launch(const AttGrad16Args &a, const DropArgs &da, hipStream_t s) {
-    const int nqb = ceil_div(a.Lq, AG16_OWN), nkb = ceil_div(a.Lk, AG16_OWN);
-    const size_t lq = (size_t)(AG16_OWN + D) * AG16_PP * sizeof(T), lk = (size_t)(2 * AG16_OWN + 2 * D) * AG16_PP * sizeof(T);
-    VK_TRY(launch_lds(ag16_dq_kernel<T, D, true, DropArgs>, dim3(a.B * a.heads * nqb), dim3(64), lq, lq, s, a, nqb, da));
-    VK_TRY(launch_lds(ag16_dkv_kernel<T, D, true, DropArgs>, dim3(a.B * a.heads * nkb), dim3(64), lk, lk, s, a, nkb, da));
+    const size_t lq = (size_t)(AG16_OWN + D) * ATT_PP * sizeof(T), lk = (size_t)(2 * AG16_OWN + 2 * D) * ATT_PP * sizeof(T);
+    VK_TRY(launch_lds(ag16_dq_kernel<T, D, DROP, DA...>, dim3(a.B * a.heads * nqb), dim3(64), lq, lq, s, a, nqb, da...));
+    VK_TRY(launch_lds(ag16_dkv_kernel<T, D, DROP, DA...>, dim3(a.B * a.heads * nkb), dim3(64), lk, lk, s, a, nkb, da...));
     return VK_OK;
 }
 

@@ -23,9 +23,7 @@ int vk_attention_grad_16(const void *q, long ldq, const void *k, long ldk, const
                       workspace_bytes));
     const AttGrad16Args a = {q, k, v, o, dout, mask, dq, dk, dv, (float *)workspace, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv,
                              B, heads, Lq, Lk, 1.0f / sqrtf((float)d)};
-    hipStream_t s = (hipStream_t)stream;
-    if (dt == VK_BF16) return d == 64 ? ag16_launch<__bf16, 64>(a, s) : ag16_launch<__bf16, 32>(a, s);
-    return d == 64 ? ag16_launch<_Float16, 64>(a, s) : ag16_launch<_Float16, 32>(a, s);
+    VK_DT16_D_SWITCH(dt, d, return ag16_launch<T, D>(a, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -9,23 +9,23 @@
 // transformers gathers the bias into [B, heads, L, L] and every layer reads it; here a pair's bias is three reads of the head's
 // table in LDS, indexed by differences of integers the lanes hold.  The host folds distance -> bucket -> weight into the table
 // once per model (vltk_amd/layoutlmv3.py relpos_lut): relative_position_bucket is constant from max_distance on, so a table over
-// the clamped difference is exact and no kernel takes a logarithm.  A score is (dot + (t1 + (tx + ty))) * scale + mask in fp32.
+// the clamped difference is exact and no kernel takes a logarithm.  A score is (dot + (t1 + (tx + ty))) * scale + mask in fp32
+// (rp_score of relpos.h).
 //
 //   attention_relpos_kernel         bf16 / f16, head dim 32 / 64, 16-byte aligned rows: v_mfma_f32_16x16x32, 64-key tiles, online
 //                                   soft-max, P rounded to the storage type for the second product (attention_tiled_kernel's
-//                                   arithmetic), with a work split of its own (below)
-//   attention_relpos_strict_kernel  every type, head dim <= 256, any alignment: attention_stream_kernel's scheme, fp32 FMAs over
-//                                   LDS tiles, P not rounded
+//                                   arithmetic), with a work split of its own (below).  Like that kernel it keeps its body written
+//                                   out: a boundary rule changed in attention_mma.h has to be changed here too
+//   attention_stream_kernel, BIAS   every type, head dim <= 256, any alignment: the strict form, attention_stream.h's kernel with
+//                                   the bias switched on: fp32 FMAs over LDS tiles, P not rounded
 //
 // No atomics: the same input gives the same bits.
 #include <algorithm>
 
+#include "attention_stream.h"
 #include "attention_tiled.h"
-#include "relpos.h"
 
 namespace vk {
-
-constexpr int RP_MAXW = 4;                      // waves per workgroup at most
 
 // ---- the matrix-core form ----
 // A WORKGROUP of 1 .. 4 waves per (batch, head, run of waves * QB * 16 queries): wave w serves the w-th block of QB * 16 queries
@@ -46,8 +46,8 @@ __global__ __launch_bounds__(256) void attention_relpos_kernel(const T *__restri
                                                               const int32_t *__restrict__ rel_q, const int32_t *__restrict__ rel_k,
                                                               const float *__restrict__ lut, int r1, int r2, T *__restrict__ out, int ldo,
                                                               int heads, int Lq, int Lk, int nrun, float scale) {
-    typedef typename AttFrag<T>::type frag;
-    constexpr int KD = D / 32, NDB = D / 16, KB = RP_KT / 16, CH = D / 8;
+    typedef typename Mma16<T>::frag frag;
+    constexpr int KD = D / 32, NDB = D / 16, KB = ATT_KT / 16, CH = D / 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char rp_lds[];
     const int tid = threadIdx.x, nthr = blockDim.x, nw = nthr >> 6;
     const int lane = tid & 63, wave = tid >> 6, g = lane >> 4, j = lane & 15;
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void attention_relpos_kernel(const T *__restri
     const int n1 = 2 * r1 + 1, n2 = 2 * r2 + 1, nlut = n1 + 2 * n2;
     T *vt0 = reinterpret_cast<T *>(rp_lds), *pt = vt0 + 2 * D * ATT_PP + wave * (QB * 16 * ATT_PP);
     int *kr0 = reinterpret_cast<int *>(vt0 + 2 * D * ATT_PP + nw * (QB * 16 * ATT_PP));
-    float *t1s = reinterpret_cast<float *>(kr0 + 2 * 3 * RP_KT), *txs = t1s + n1, *tys = txs + n2;
+    float *t1s = reinterpret_cast<float *>(kr0 + 2 * 3 * ATT_KT), *txs = t1s + n1, *tys = txs + n2;
     const frag zf = {};
 
     for (int i = tid; i < nlut; i += nthr) t1s[i] = lut[(long)h * nlut + i];
@@ -73,21 +73,17 @@ __global__ __launch_bounds__(256) void attention_relpos_kernel(const T *__restri
             if (key + 1 < Lk) t1 = *reinterpret_cast<const frag *>(v + ((long)b * Lk + key + 1) * ldv + h * D + c * 8);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const T lo = t0[e], hi = t1[e];
-                unsigned short ulo, uhi;
-                __builtin_memcpy(&ulo, &lo, 2);
-                __builtin_memcpy(&uhi, &hi, 2);
-                vt32[((c * 8 + e) * ATT_PP) / 2 + kp] = (unsigned)ulo | ((unsigned)uhi << 16);
+                vt32[((c * 8 + e) * ATT_PP) / 2 + kp] = pack16<T>(t0[e], t1[e]);
             }
         }
-        if (tid < RP_KT) {
+        if (tid < ATT_KT) {
             const int key = k0 + tid;
             const bool ok = key < Lk;
             const int32_t *src = rel_k + ((long)b * Lk + (ok ? key : 0)) * 3;
-            int *kr = kr0 + buf * (3 * RP_KT);
+            int *kr = kr0 + buf * (3 * ATT_KT);
             kr[tid] = ok ? src[0] : 0;
-            kr[RP_KT + tid] = ok ? src[1] : 0;
-            kr[2 * RP_KT + tid] = ok ? src[2] : 0;
+            kr[ATT_KT + tid] = ok ? src[1] : 0;
+            kr[2 * ATT_KT + tid] = ok ? src[2] : 0;
         }
     };
 
@@ -113,12 +109,12 @@ __global__ __launch_bounds__(256) void attention_relpos_kernel(const T *__restri
             qy[qb][e] = rok ? rs[2] : 0;
         }
     }
-    att_f4 o[QB][NDB];
+    m16_f4 o[QB][NDB];
     float m[QB][4], l[QB][4];
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
 #pragma unroll
-        for (int db = 0; db < NDB; ++db) o[qb][db] = att_f4{0.f, 0.f, 0.f, 0.f};
+        for (int db = 0; db < NDB; ++db) o[qb][db] = m16_f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             m[qb][e] = -INFINITY;
@@ -128,7 +124,7 @@ __global__ __launch_bounds__(256) void attention_relpos_kernel(const T *__restri
 
     stage(0, 0);
     int buf = 0;
-    for (int k0 = 0; k0 < Lk; k0 += RP_KT, buf ^= 1) {
+    for (int k0 = 0; k0 < Lk; k0 += ATT_KT, buf ^= 1) {
         // ---- K fragments straight from memory ----
         frag kf[KB][KD];
         float mk[KB];
@@ -145,31 +141,31 @@ __global__ __launch_bounds__(256) void attention_relpos_kernel(const T *__restri
             mk[kb] = ok ? (mask ? mask[(long)b * Lk + r] : 0.f) : -INFINITY;
         }
         __syncthreads();            // this tile's V^T image and key triples (first tile: the table too) are in LDS
-        const int *kr = kr0 + buf * (3 * RP_KT);
+        const int *kr = kr0 + buf * (3 * ATT_KT);
         const T *vt = vt0 + buf * (D * ATT_PP);
         int kp[KB], kx[KB], ky[KB];
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
             kp[kb] = kr[kb * 16 + j];
-            kx[kb] = kr[RP_KT + kb * 16 + j];
-            ky[kb] = kr[2 * RP_KT + kb * 16 + j];
+            kx[kb] = kr[ATT_KT + kb * 16 + j];
+            ky[kb] = kr[2 * ATT_KT + kb * 16 + j];
         }
         // ---- S = (Q K^T + bias) * scale + mask; online soft-max; P image ----
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) {
-            att_f4 sc[KB];
+            m16_f4 sc[KB];
 #pragma unroll
             for (int kb = 0; kb < KB; ++kb) {
-                att_f4 a = {0.f, 0.f, 0.f, 0.f};
+                m16_f4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int ks = 0; ks < KD; ++ks) a = AttFrag<T>::mma(qf[qb][ks], kf[kb][ks], a);
+                for (int ks = 0; ks < KD; ++ks) a = Mma16<T>::mma(qf[qb][ks], kf[kb][ks], a);
                 const bool ok = k0 + kb * 16 + j < Lk;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float t1 = t1s[rp_idx(kp[kb], qp[qb][e], r1)];
                     const float tx = txs[rp_idx(kx[kb], qx[qb][e], r2)];
                     const float ty = tys[rp_idx(ky[kb], qy[qb][e], r2)];
-                    a[e] = ok ? (a[e] + (t1 + (tx + ty))) * scale + mk[kb] : -INFINITY;
+                    a[e] = ok ? rp_score(a[e], t1, tx, ty, scale, mk[kb]) : -INFINITY;
                 }
                 sc[kb] = a;
             }
@@ -181,12 +177,12 @@ __global__ __launch_bounds__(256) void attention_relpos_kernel(const T *__restri
 #pragma unroll
                 for (int s = 8; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
                 const float mn = fmaxf(m[qb][e], mx);
-                const float alpha = tat_exp(m[qb][e] - mn);      // first tile: exp(-inf) = 0
+                const float alpha = att_exp(m[qb][e] - mn);      // first tile: exp(-inf) = 0
                 float sum = 0.f;
                 const int row = qb * 16 + g * 4 + e;
 #pragma unroll
                 for (int kb = 0; kb < KB; ++kb) {
-                    const float p = tat_exp(sc[kb][e] - mn);     // padded keys: exp(-inf) = 0
+                    const float p = att_exp(sc[kb][e] - mn);     // padded keys: exp(-inf) = 0
                     sum += p;
                     pt[row * ATT_PP + kb * 16 + j] = (T)p;
                 }
@@ -199,7 +195,7 @@ __global__ __launch_bounds__(256) void attention_relpos_kernel(const T *__restri
             }
         }
         __syncthreads();            // P is written; every wave is past the previous tile's second product, whose buffer is free
-        if (k0 + RP_KT < Lk) stage(k0 + RP_KT, buf ^ 1);
+        if (k0 + ATT_KT < Lk) stage(k0 + ATT_KT, buf ^ 1);
         // ---- O += P V: A = P rows (keys contiguous), B = V^T rows (keys contiguous) ----
         const int nk2 = Lk - k0 > 32 ? 2 : 1;
 #pragma unroll
@@ -212,7 +208,7 @@ __global__ __launch_bounds__(256) void attention_relpos_kernel(const T *__restri
             for (int db = 0; db < NDB; ++db) {
                 const frag vf = *reinterpret_cast<const frag *>(vt + (db * 16 + j) * ATT_PP + k2 * 32 + g * 8);
 #pragma unroll
-                for (int qb = 0; qb < QB; ++qb) o[qb][db] = AttFrag<T>::mma(pf[qb], vf, o[qb][db]);
+                for (int qb = 0; qb < QB; ++qb) o[qb][db] = Mma16<T>::mma(pf[qb], vf, o[qb][db]);
             }
         }
     }
@@ -225,106 +221,6 @@ __global__ __launch_bounds__(256) void attention_relpos_kernel(const T *__restri
 #pragma unroll
             for (int db = 0; db < NDB; ++db) out[((long)b * Lq + row) * ldo + h * D + db * 16 + j] = (T)(o[qb][db][e] / l[qb][e]);
         }
-}
-
-// ---- the strict form ----
-// attention_stream_kernel's scheme: a workgroup per (batch, head, 16 queries); the Q block and a 64-key K / V tile in LDS as fp32,
-// 256 threads share the 16 x 64 scores, a wave owns every fourth row's running maximum and sum, a thread owns up to 16 of the
-// 16 x d outputs across the tiles.  Beside them in LDS: the 16 query triples, the tile's 64 key triples and the head's table.
-constexpr int RS_QB = 16, RS_MAXD = 256, RS_OUT = RS_QB * RS_MAXD / 256;
-
-static size_t strict_lds_bytes(int d, int nlut) {
-    return ((size_t)(RS_QB + RP_KT) * (d + 1) + (size_t)RP_KT * d + (size_t)RS_QB * (RP_KT + 1) + 3 * RS_QB + 3 * (RS_QB + RP_KT) + nlut) *
-           sizeof(float);
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void attention_relpos_strict_kernel(const T *__restrict__ q, int ldq, const T *__restrict__ k, int ldk,
-                                                                     const T *__restrict__ v, int ldv, const float *__restrict__ mask,
-                                                                     const int32_t *__restrict__ rel_q, const int32_t *__restrict__ rel_k,
-                                                                     const float *__restrict__ lut, int r1, int r2, T *__restrict__ out,
-                                                                     int ldo, int heads, int Lq, int Lk, int d, int nqb, float scale) {
-    extern __shared__ float rs_lds[];
-    const int dp = d + 1, lp = RP_KT + 1;
-    const int n1 = 2 * r1 + 1, n2 = 2 * r2 + 1, nlut = n1 + 2 * n2;
-    float *qs = rs_lds, *ks = qs + RS_QB * dp, *vs = ks + RP_KT * dp, *ps = vs + RP_KT * d, *ms = ps + RS_QB * lp, *ls = ms + RS_QB,
-          *as = ls + RS_QB;
-    int *qr = reinterpret_cast<int *>(as + RS_QB), *kr = qr + 3 * RS_QB;
-    float *t1s = reinterpret_cast<float *>(kr + 3 * RP_KT), *txs = t1s + n1, *tys = txs + n2;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int bh = blockIdx.x / nqb, q0 = (blockIdx.x - bh * nqb) * RS_QB;
-    const int b = bh / heads, h = bh - b * heads;
-    const int nq = min(RS_QB, Lq - q0);
-    for (int i = tid; i < RS_QB * d; i += 256) {
-        const int r = i / d, c = i - r * d;
-        qs[r * dp + c] = r < nq ? ldf(q + ((long)b * Lq + q0 + r) * ldq + h * d + c) : 0.f;
-    }
-    for (int i = tid; i < nlut; i += 256) t1s[i] = lut[(long)h * nlut + i];
-    if (tid < 3 * RS_QB) qr[tid] = tid / 3 < nq ? rel_q[((long)b * Lq + q0) * 3 + tid] : 0;
-    if (tid < RS_QB) {
-        ms[tid] = -INFINITY;
-        ls[tid] = 0.f;
-    }
-    float o[RS_OUT];
-#pragma unroll
-    for (int n = 0; n < RS_OUT; ++n) o[n] = 0.f;
-
-    for (int k0 = 0; k0 < Lk; k0 += RP_KT) {
-        const int nk = min(RP_KT, Lk - k0);
-        for (int i = tid; i < RP_KT * d; i += 256) {
-            const int r = i / d, c = i - r * d;
-            const bool ok = r < nk;
-            ks[r * dp + c] = ok ? ldf(k + ((long)b * Lk + k0 + r) * ldk + h * d + c) : 0.f;
-            vs[i] = ok ? ldf(v + ((long)b * Lk + k0 + r) * ldv + h * d + c) : 0.f;
-        }
-        if (tid < 3 * RP_KT) kr[tid] = tid / 3 < nk ? rel_k[((long)b * Lk + k0) * 3 + tid] : 0;
-        __syncthreads();
-        for (int i = tid; i < RS_QB * RP_KT; i += 256) {
-            const int r = i / RP_KT, jj = i - r * RP_KT;
-            float s = 0.f;
-            for (int c = 0; c < d; ++c) s += qs[r * dp + c] * ks[jj * dp + c];
-            const float t1 = t1s[rp_idx(kr[3 * jj], qr[3 * r], r1)];
-            const float tx = txs[rp_idx(kr[3 * jj + 1], qr[3 * r + 1], r2)];
-            const float ty = tys[rp_idx(kr[3 * jj + 2], qr[3 * r + 2], r2)];
-            ps[r * lp + jj] = jj < nk ? (s + (t1 + (tx + ty))) * scale + (mask ? mask[(long)b * Lk + k0 + jj] : 0.f) : -INFINITY;
-        }
-        __syncthreads();
-        for (int r = wave; r < RS_QB; r += 4) {
-            const float x = ps[r * lp + lane];
-            const float mx = wave_max(x);
-            const float mo = ms[r], mn = fmaxf(mo, mx);
-            const float alpha = expf(mo - mn);                   // first tile: exp(-inf) = 0
-            const float p = expf(x - mn);                        // padded keys: exp(-inf) = 0
-            ps[r * lp + lane] = p;
-            const float sum = wave_sum(p);
-            const float lo = ls[r];
-            if (lane == 0) {
-                ms[r] = mn;
-                ls[r] = alpha * lo + sum;
-                as[r] = alpha;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int n = 0; n < RS_OUT; ++n) {
-            const int i = tid + 256 * n;
-            if (i < RS_QB * d) {
-                const int r = i / d, c = i - r * d;
-                float acc = as[r] * o[n];
-                for (int jj = 0; jj < RP_KT; ++jj) acc += ps[r * lp + jj] * vs[jj * d + c];
-                o[n] = acc;
-            }
-        }
-        __syncthreads();            // the next tile overwrites K, V, the key triples and the scores
-    }
-#pragma unroll
-    for (int n = 0; n < RS_OUT; ++n) {
-        const int i = tid + 256 * n;
-        if (i < RS_QB * d) {
-            const int r = i / d, c = i - r * d;
-            if (r < nq) out[((long)b * Lq + q0 + r) * ldo + h * d + c] = (T)(o[n] / ls[r]);
-        }
-    }
 }
 
 // ---- the rule (host only) ----
@@ -340,8 +236,8 @@ static int relpos_form(int Lq, int Lk, int d, vk_dtype dt, int ldq, int ldk, int
     if (!env_off("VK_ATTENTION_MFMA") && (dt == VK_F16 || dt == VK_BF16) && (d == 32 || d == 64) && ldq % 8 == 0 && ldk % 8 == 0 &&
         ldv % 8 == 0 && aligned16)
         return VK_RELPOS_FORM_MFMA;
-    if (d > RS_MAXD) {
-        set_error("attention_relpos: head dim %d is beyond the strict form's limit of %d", d, RS_MAXD);
+    if (d > STR_MAXD) {
+        set_error("attention_relpos: head dim %d is beyond the strict form's limit of %d", d, STR_MAXD);
         return -VK_EINVAL;
     }
     return VK_RELPOS_FORM_STRICT;
@@ -351,31 +247,28 @@ static int relpos_form(int Lq, int Lk, int d, vk_dtype dt, int ldq, int ldk, int
 // cover Lq, four at the most: 16, 32, 64, 96, then 128 from Lq = 97 on (27 tokens: one wave; 77: three; 709: six workgroups of four
 // per head).  Strict form: 16.
 static int relpos_queries(int form, int Lq) {
-    if (form != VK_RELPOS_FORM_MFMA) return RS_QB;
-    return Lq <= 16 ? 16 : 32 * std::min(RP_MAXW, ceil_div(Lq, 32));
+    if (form != VK_RELPOS_FORM_MFMA) return STR_QB;
+    return Lq <= 16 ? 16 : 32 * std::min(ATT_MAXW, ceil_div(Lq, 32));
 }
 
 struct RelArgs {
     AttArgs a;
-    const int32_t *rel_q, *rel_k;
-    const float *lut;
-    int r1, r2;
+    RelBias rb;
 };
-#define VK_REL_IO(T)                                                                                                                  \
-    (const T *)r.a.q, r.a.ldq, (const T *)r.a.k, r.a.ldk, (const T *)r.a.v, r.a.ldv, r.a.mask, r.rel_q, r.rel_k, r.lut, r.r1, r.r2, \
-        (T *)r.a.out, r.a.ldo, r.a.heads, r.a.Lq, r.a.Lk
 
 static size_t mfma_lds_bytes(int D, int QB, int waves, int nlut) {
-    return (size_t)(2 * D + waves * QB * 16) * ATT_PP * 2 + (size_t)2 * 3 * RP_KT * sizeof(int) + (size_t)nlut * sizeof(float);
+    return (size_t)(2 * D + waves * QB * 16) * ATT_PP * 2 + (size_t)2 * 3 * ATT_KT * sizeof(int) + (size_t)nlut * sizeof(float);
 }
 
 template <typename T, int D, int QB>
 static int relpos_mfma_launch_qb(const RelArgs &r, float scale, hipStream_t s) {
-    const int per = relpos_queries(VK_RELPOS_FORM_MFMA, r.a.Lq), waves = per / (QB * 16), nrun = ceil_div(r.a.Lq, per);
-    const size_t smem = mfma_lds_bytes(D, QB, waves, relpos_lut_len(r.r1, r.r2));
-    const size_t cap = mfma_lds_bytes(D, QB, RP_MAXW, 0) + RELPOS_LUT_MAX;
-    return launch_lds(attention_relpos_kernel<T, D, QB>, dim3(r.a.B * r.a.heads * nrun), dim3(64 * waves), smem, cap, s, VK_REL_IO(T), nrun,
-                      scale);
+    const AttArgs &a = r.a;
+    const int per = relpos_queries(VK_RELPOS_FORM_MFMA, a.Lq), waves = per / (QB * 16), nrun = ceil_div(a.Lq, per);
+    const size_t smem = mfma_lds_bytes(D, QB, waves, relpos_lut_len(r.rb.r1, r.rb.r2));
+    const size_t cap = mfma_lds_bytes(D, QB, ATT_MAXW, 0) + RELPOS_LUT_MAX;
+    return launch_lds(attention_relpos_kernel<T, D, QB>, dim3(a.B * a.heads * nrun), dim3(64 * waves), smem, cap, s, (const T *)a.q, a.ldq,
+                      (const T *)a.k, a.ldk, (const T *)a.v, a.ldv, a.mask, r.rb.rel_q, r.rb.rel_k, r.rb.lut, r.rb.r1, r.rb.r2, (T *)a.out,
+                      a.ldo, a.heads, a.Lq, a.Lk, nrun, scale);
 }
 template <typename T, int D>
 static int relpos_mfma_launch(const RelArgs &r, float scale, hipStream_t s) {
@@ -384,23 +277,20 @@ static int relpos_mfma_launch(const RelArgs &r, float scale, hipStream_t s) {
 
 template <typename T>
 static int relpos_strict_launch(const RelArgs &r, float scale, hipStream_t s) {
-    const int nqb = ceil_div(r.a.Lq, RS_QB);
-    return launch_lds(attention_relpos_strict_kernel<T>, dim3(r.a.B * r.a.heads * nqb), dim3(256),
-                      strict_lds_bytes(r.a.d, relpos_lut_len(r.r1, r.r2)), strict_lds_bytes(RS_MAXD, 0) + RELPOS_LUT_MAX, s, VK_REL_IO(T), r.a.d,
-                      nqb, scale);
+    const AttArgs &a = r.a;
+    const int nqb = ceil_div(a.Lq, STR_QB);
+    return launch_lds(attention_stream_kernel<T, true, RelBias>, dim3(a.B * a.heads * nqb), dim3(256),
+                      stream_bias_lds_bytes(a.d, relpos_lut_len(r.rb.r1, r.rb.r2)), stream_bias_lds_bytes(STR_MAXD, 0) + RELPOS_LUT_MAX, s,
+                      VK_ATT_IO(T), a.d, nqb, scale, r.rb);
 }
-#undef VK_REL_IO
 
 // what the launch refuses, reading through no pointer
 static int relpos_check(const RelArgs &r) {
     const AttArgs &a = r.a;
-    VK_REQUIRE(a.q && a.k && a.v && a.out && r.rel_q && r.rel_k && r.lut, VK_EINVAL, "attention_relpos: null argument");
+    VK_REQUIRE(a.q && a.k && a.v && a.out && r.rb.rel_q && r.rb.rel_k && r.rb.lut, VK_EINVAL, "attention_relpos: null argument");
     VK_REQUIRE(a.B >= 1 && a.heads >= 1 && a.Lq >= 1 && a.Lk >= 1 && a.d >= 1, VK_EINVAL,
                "attention_relpos: sizes must be positive (B=%d heads=%d Lq=%d Lk=%d d=%d)", a.B, a.heads, a.Lq, a.Lk, a.d);
-    VK_REQUIRE(r.r1 >= 1 && r.r2 >= 1, VK_EINVAL, "attention_relpos: radii must be at least 1 (r1=%d r2=%d)", r.r1, r.r2);
-    VK_REQUIRE((size_t)r.r1 + 2 * (size_t)r.r2 <= RELPOS_LUT_MAX / 8 && relpos_lut_len(r.r1, r.r2) * sizeof(float) <= RELPOS_LUT_MAX, VK_EINVAL,
-               "attention_relpos: the table of radii %d / %d, %zu floats a head, is past the LDS budget of %zu bytes", r.r1, r.r2,
-               (size_t)2 * r.r1 + 4 * (size_t)r.r2 + 3, RELPOS_LUT_MAX);
+    VK_TRY(relpos_lut_check("attention_relpos", r.rb.r1, r.rb.r2));
     const long H = (long)a.heads * a.d;
     VK_REQUIRE(a.ldq >= H && a.ldk >= H && a.ldv >= H && a.ldo >= H, VK_EINVAL,
                "attention_relpos: a leading dimension (%d %d %d %d) is below heads * d = %ld", a.ldq, a.ldk, a.ldv, a.ldo, H);
@@ -408,7 +298,7 @@ static int relpos_check(const RelArgs &r) {
     const uintptr_t es = dtype_size(a.dt);
     VK_REQUIRE(((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.out) % es == 0, VK_EINVAL,
                "attention_relpos: q, k, v and out must be aligned to their element");
-    VK_REQUIRE(((uintptr_t)r.rel_q | (uintptr_t)r.rel_k | (uintptr_t)r.lut | (uintptr_t)a.mask) % 4 == 0, VK_EINVAL,
+    VK_REQUIRE(((uintptr_t)r.rb.rel_q | (uintptr_t)r.rb.rel_k | (uintptr_t)r.rb.lut | (uintptr_t)a.mask) % 4 == 0, VK_EINVAL,
                "attention_relpos: rel_q, rel_k, lut and mask must be 4-byte aligned");
     VK_REQUIRE((long)a.B * a.heads * ceil_div(a.Lq, 16) < (1L << 31), VK_EINVAL, "attention_relpos: too many (batch, head, query block) items");
     return VK_OK;
@@ -435,7 +325,7 @@ int vk_attention_relpos_queries(int form, int Lq) {
 int vk_attention_relpos_check(const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, const float *mask,
                               const int32_t *rel_q, const int32_t *rel_k, const float *lut, int r1, int r2, const void *out, int ldo, int B,
                               int heads, int Lq, int Lk, int d, vk_dtype dt) {
-    const RelArgs r = {{q, k, v, mask, const_cast<void *>(out), ldq, ldk, ldv, ldo, B, heads, Lq, Lk, d, dt}, rel_q, rel_k, lut, r1, r2};
+    const RelArgs r = {{q, k, v, mask, const_cast<void *>(out), ldq, ldk, ldv, ldo, B, heads, Lq, Lk, d, dt}, {rel_q, rel_k, lut, r1, r2}};
     VK_TRY(relpos_check(r));
     const int aligned = ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0;
     const int form = relpos_form(Lq, Lk, d, dt, ldq, ldk, ldv, aligned);
@@ -445,18 +335,14 @@ int vk_attention_relpos_check(const void *q, int ldq, const void *k, int ldk, co
 int vk_attention_relpos(const void *q, int ldq, const void *k, int ldk, const void *v, int ldv, const float *mask, const int32_t *rel_q,
                         const int32_t *rel_k, const float *lut, int r1, int r2, void *out, int ldo, int B, int heads, int Lq, int Lk, int d,
                         vk_dtype dt, void *stream) {
-    const RelArgs r = {{q, k, v, mask, out, ldq, ldk, ldv, ldo, B, heads, Lq, Lk, d, dt}, rel_q, rel_k, lut, r1, r2};
+    const RelArgs r = {{q, k, v, mask, out, ldq, ldk, ldv, ldo, B, heads, Lq, Lk, d, dt}, {rel_q, rel_k, lut, r1, r2}};
     VK_TRY(relpos_check(r));
     const int aligned = ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0;
     const int form = relpos_form(Lq, Lk, d, dt, ldq, ldk, ldv, aligned);
     if (form < 0) return -form;
     const float scale = 1.0f / sqrtf((float)d);
     hipStream_t s = (hipStream_t)stream;
-    if (form == VK_RELPOS_FORM_MFMA) {
-        const bool d64 = d == 64;
-        return dt == VK_F16 ? (d64 ? relpos_mfma_launch<_Float16, 64>(r, scale, s) : relpos_mfma_launch<_Float16, 32>(r, scale, s))
-                            : (d64 ? relpos_mfma_launch<__bf16, 64>(r, scale, s) : relpos_mfma_launch<__bf16, 32>(r, scale, s));
-    }
+    if (form == VK_RELPOS_FORM_MFMA) VK_DT16_D_SWITCH(dt, d, return relpos_mfma_launch<T, D>(r, scale, s));
     VK_DT_SWITCH(dt, "attention_relpos", return relpos_strict_launch<T>(r, scale, s));
     return VK_EINVAL;
 }

@@ -50,7 +50,6 @@
 
 namespace vk {
 
-constexpr int RG_MAXW = 4;              // waves per workgroup at most
 constexpr int RG_MIN_SHIFT = 30;        // bits below the bound the size rule keeps
 
 struct RelGradArgs {
@@ -114,39 +113,11 @@ __device__ __forceinline__ bool rg_bound(const unsigned *norm2, int heads, int h
     return true;
 }
 
-// the (row, row + 1) pairs of rows [r0, r0 + 64) of a sequence, transposed, into img[c][row - r0] (ag16_image_t's layout), by all
-// threads of the workgroup: thread = (row pair, 16-byte chunk)
-template <typename T, int D>
-__device__ __forceinline__ void rg_image_t(T *img, const T *base, long ld, int r0, int R, int tid, int nthr) {
-    typedef typename Mma16<T>::frag frag;
-    unsigned *img32 = reinterpret_cast<unsigned *>(img);
-    for (int i = tid; i < 32 * (D / 8); i += nthr) {
-        const int kp = i & 31, c = i >> 5, row = r0 + 2 * kp;
-        frag t0 = {}, t1 = {};
-        if (row < R) t0 = *reinterpret_cast<const frag *>(base + (long)row * ld + c * 8);
-        if (row + 1 < R) t1 = *reinterpret_cast<const frag *>(base + (long)(row + 1) * ld + c * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) img32[((c * 8 + e) * AG16_PP) / 2 + kp] = pack16<T>(t0[e], t1[e]);
-    }
-}
-
-// the triples of rows [r0, r0 + 64) of rel [R, 3] into tr[3][64], (0, 0, 0) past the end
-__device__ __forceinline__ void rg_triples(int *tr, const int32_t *rel, int r0, int R, int tid) {
-    if (tid < RP_KT) {
-        const int row = r0 + tid;
-        const bool ok = row < R;
-        const int32_t *src = rel + (long)(ok ? row : 0) * 3;
-        tr[tid] = ok ? src[0] : 0;
-        tr[RP_KT + tid] = ok ? src[1] : 0;
-        tr[2 * RP_KT + tid] = ok ? src[2] : 0;
-    }
-}
-
 template <typename T, int D, bool HIST>
 __global__ __launch_bounds__(256) void rg_dq_kernel(RelGradArgs r, int nrun) {
     const AttGrad16Args &a = r.a;
     typedef typename Mma16<T>::frag frag;
-    constexpr int KD = D / 32, NDB = D / 16, KB = RP_KT / 16;
+    constexpr int KD = D / 32, NDB = D / 16, KB = ATT_KT / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char rg_lds[];
     const int tid = threadIdx.x, nthr = blockDim.x, nw = nthr >> 6;
     const int lane = tid & 63, wave = tid >> 6, g = lane >> 4, j = lane & 15;
@@ -155,9 +126,9 @@ __global__ __launch_bounds__(256) void rg_dq_kernel(RelGradArgs r, int nrun) {
     const int q0 = (run * nw + wave) * AG16_OWN;
     const int nq = a.Lq - q0;                       // owned rows inside the sequence: 16 or more (all), or none (an idle wave)
     const int n1 = 2 * r.r1 + 1, n2 = 2 * r.r2 + 1, nlut = n1 + 2 * n2;
-    T *kt0 = reinterpret_cast<T *>(rg_lds), *dsi = kt0 + 2 * D * AG16_PP + wave * (AG16_OWN * AG16_PP);
-    int *kr0 = reinterpret_cast<int *>(kt0 + 2 * D * AG16_PP + nw * (AG16_OWN * AG16_PP));
-    unsigned long long *hs = reinterpret_cast<unsigned long long *>(kr0 + 2 * 3 * RP_KT);
+    T *kt0 = reinterpret_cast<T *>(rg_lds), *dsi = kt0 + 2 * D * ATT_PP + wave * (AG16_OWN * ATT_PP);
+    int *kr0 = reinterpret_cast<int *>(kt0 + 2 * D * ATT_PP + nw * (AG16_OWN * ATT_PP));
+    unsigned long long *hs = reinterpret_cast<unsigned long long *>(kr0 + 2 * 3 * ATT_KT);
     float *t1s = reinterpret_cast<float *>(hs + nlut), *txs = t1s + n1, *tys = txs + n2;
     const T *qseq = static_cast<const T *>(a.q) + (long)b * a.Lq * a.ldq + h * D;
     const T *doseq = static_cast<const T *>(a.dout) + (long)b * a.Lq * a.lddo + h * D;
@@ -172,18 +143,10 @@ __global__ __launch_bounds__(256) void rg_dq_kernel(RelGradArgs r, int nrun) {
         if (HIST) hs[i] = 0;
     }
     frag qf[KD], dof[KD];
-    ag16_row_frags<T, KD>(qf, qseq, a.ldq, q0 + j, a.Lq, g);
-    ag16_row_frags<T, KD>(dof, doseq, a.lddo, q0 + j, a.Lq, g);
+    att_row_frags<T, KD>(qf, qseq, a.ldq, q0 + j, a.Lq, g);
+    att_row_frags<T, KD>(dof, doseq, a.lddo, q0 + j, a.Lq, g);
     int qp[4], qx[4], qy[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int row = q0 + 4 * g + e;
-        const bool rok = row < a.Lq;
-        const int32_t *rs = r.rel_q + ((long)b * a.Lq + (rok ? row : 0)) * 3;
-        qp[e] = rok ? rs[0] : 0;
-        qx[e] = rok ? rs[1] : 0;
-        qy[e] = rok ? rs[2] : 0;
-    }
+    att_lane_triples(qp, qx, qy, r.rel_q + (long)b * a.Lq * 3, q0 + 4 * g, a.Lq);
 
     // ---- pass 1: m and l of rows 4 g + e, online over the key tiles; the next tile's triples go into the other buffer ----
     float m[4], l[4];
@@ -192,80 +155,39 @@ __global__ __launch_bounds__(256) void rg_dq_kernel(RelGradArgs r, int nrun) {
         m[e] = -INFINITY;
         l[e] = 0.f;
     }
-    rg_triples(kr0, relk, 0, a.Lk, tid);
+    att_stage_triples(kr0, relk, 0, a.Lk, tid);
     int buf = 0;
-    for (int k0 = 0; k0 < a.Lk; k0 += RP_KT, buf ^= 1) {
+    for (int k0 = 0; k0 < a.Lk; k0 += ATT_KT, buf ^= 1) {
         __syncthreads();            // this tile's triples (first tile: the table too) are in LDS; the other buffer is free
-        if (k0 + RP_KT < a.Lk) rg_triples(kr0 + (buf ^ 1) * (3 * RP_KT), relk, k0 + RP_KT, a.Lk, tid);
-        const int *kr = kr0 + buf * (3 * RP_KT);
+        if (k0 + ATT_KT < a.Lk) att_stage_triples(kr0 + (buf ^ 1) * (3 * ATT_KT), relk, k0 + ATT_KT, a.Lk, tid);
+        const int *kr = kr0 + buf * (3 * ATT_KT);
         m16_f4 sc[KB];
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
             frag kf[KD];
-            ag16_row_frags<T, KD>(kf, kbase, a.ldk, k0 + kb * 16 + j, a.Lk, g);
+            att_row_frags<T, KD>(kf, kbase, a.ldk, k0 + kb * 16 + j, a.Lk, g);
             m16_f4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KD; ++ks) s = Mma16<T>::mma(qf[ks], kf[ks], s);
             const int key = k0 + kb * 16 + j;
             const bool ok = key < a.Lk;
             const float mk = ok && mrow ? mrow[key] : 0.f;
-            const int kp = kr[kb * 16 + j], kx = kr[RP_KT + kb * 16 + j], ky = kr[2 * RP_KT + kb * 16 + j];
+            const int kp = kr[kb * 16 + j], kx = kr[ATT_KT + kb * 16 + j], ky = kr[2 * ATT_KT + kb * 16 + j];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float t1 = t1s[rp_idx(kp, qp[e], r.r1)], tx = txs[rp_idx(kx, qx[e], r.r2)], ty = tys[rp_idx(ky, qy[e], r.r2)];
-                s[e] = ok ? (s[e] + (t1 + (tx + ty))) * a.scale + mk : -INFINITY;
+                s[e] = ok ? rp_score(s[e], t1, tx, ty, a.scale, mk) : -INFINITY;
             }
             sc[kb] = s;
         }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float mx = sc[0][e];
-#pragma unroll
-            for (int kb = 1; kb < KB; ++kb) mx = fmaxf(mx, sc[kb][e]);
-#pragma unroll
-            for (int s = 8; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-            const float mn = fmaxf(m[e], mx);
-            const float alpha = ag16_exp(m[e] - mn);            // first tile: exp(-inf) = 0
-            float sum = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) sum += ag16_exp(sc[kb][e] - mn);      // keys outside: exp(-inf) = 0
-#pragma unroll
-            for (int s = 8; s > 0; s >>= 1) sum += __shfl_xor(sum, s, 64);
-            m[e] = mn;
-            l[e] = fmaf(alpha, l[e], sum);
-        }
+        for (int e = 0; e < 4; ++e) att_online_row(sc, e, m[e], l[e]);
     }
     float il[4], dd[4];
-    {
-        // D of row j: this lane's 8 KD columns, then the four lanes of the row; rows 4 g + e fetch theirs from lanes 4 g + e
-        float part = 0.f;
-        frag of[KD];
-        ag16_row_frags<T, KD>(of, oseq, a.ldo, q0 + j, a.Lq, g);
-#pragma unroll
-        for (int ks = 0; ks < KD; ++ks)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) part = fmaf((float)dof[ks][e], (float)of[ks][e], part);
-        part += __shfl_xor(part, 16, 64);
-        part += __shfl_xor(part, 32, 64);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            dd[e] = __shfl(part, 4 * g + e, 64);
-            il[e] = 1.0f / l[e];
-        }
-    }
-    if (j == 0) {
-        const long n = (long)a.B * a.heads * a.Lq;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int row = 4 * g + e;
-            if (row < nq) {
-                const long srow = (long)bh * a.Lq + q0 + row;
-                a.stats[srow] = m[e];
-                a.stats[n + srow] = il[e];
-                a.stats[2 * n + srow] = dd[e];
-            }
-        }
-    }
+    frag of[KD];
+    att_row_frags<T, KD>(of, oseq, a.ldo, q0 + j, a.Lq, g);
+    att_grad_d<T, KD>(dd, il, dof, of, l, g);
+    att_store_stats(a.stats, (long)a.B * a.heads * a.Lq, (long)bh * a.Lq + q0, nq, m, il, dd, g, j);
 
     // ---- pass 2: dS -> the histogram and dQ ----
     float M = 0.f, lim = 0.f;
@@ -280,18 +202,18 @@ __global__ __launch_bounds__(256) void rg_dq_kernel(RelGradArgs r, int nrun) {
 #pragma unroll
     for (int db = 0; db < NDB; ++db) acc[db] = m16_f4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();                // every wave is past pass 1's last triples
-    rg_image_t<T, D>(kt0, kbase, a.ldk, 0, a.Lk, tid, nthr);
-    rg_triples(kr0, relk, 0, a.Lk, tid);
+    att_image_t_wg<T, D>(kt0, kbase, a.ldk, 0, a.Lk, tid, nthr);
+    att_stage_triples(kr0, relk, 0, a.Lk, tid);
     buf = 0;
-    for (int k0 = 0; k0 < a.Lk; k0 += RP_KT, buf ^= 1) {
+    for (int k0 = 0; k0 < a.Lk; k0 += ATT_KT, buf ^= 1) {
         __syncthreads();            // this tile's K^T image and triples are in LDS
-        const int *kr = kr0 + buf * (3 * RP_KT);
-        const T *kt = kt0 + buf * (D * AG16_PP);
+        const int *kr = kr0 + buf * (3 * ATT_KT);
+        const T *kt = kt0 + buf * (D * ATT_PP);
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
             frag kf[KD], vf[KD];
-            ag16_row_frags<T, KD>(kf, kbase, a.ldk, k0 + kb * 16 + j, a.Lk, g);
-            ag16_row_frags<T, KD>(vf, vbase, a.ldv, k0 + kb * 16 + j, a.Lk, g);
+            att_row_frags<T, KD>(kf, kbase, a.ldk, k0 + kb * 16 + j, a.Lk, g);
+            att_row_frags<T, KD>(vf, vbase, a.ldv, k0 + kb * 16 + j, a.Lk, g);
             m16_f4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KD; ++ks) {
@@ -301,14 +223,14 @@ __global__ __launch_bounds__(256) void rg_dq_kernel(RelGradArgs r, int nrun) {
             const int key = k0 + kb * 16 + j;
             const bool okk = key < a.Lk;
             const float mk = okk && mrow ? mrow[key] : 0.f;
-            const int kp = kr[kb * 16 + j], kx = kr[RP_KT + kb * 16 + j], ky = kr[2 * RP_KT + kb * 16 + j];
+            const int kp = kr[kb * 16 + j], kx = kr[ATT_KT + kb * 16 + j], ky = kr[2 * ATT_KT + kb * 16 + j];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float dsv = 0.f;
                 if (okk && 4 * g + e < nq) {
                     const int i1 = rp_idx(kp, qp[e], r.r1), ix = rp_idx(kx, qx[e], r.r2), iy = rp_idx(ky, qy[e], r.r2);
-                    const float sb = (s[e] + (t1s[i1] + (txs[ix] + tys[iy]))) * a.scale + mk;
-                    dsv = ag16_exp(sb - m[e]) * il[e] * (dp[e] - dd[e]);
+                    const float sb = rp_score(s[e], t1s[i1], txs[ix], tys[iy], a.scale, mk);
+                    dsv = att_exp(sb - m[e]) * il[e] * (dp[e] - dd[e]);
                     if (HIST && hist_on) {
                         if (!(fabsf(dsv) <= lim)) {
                             bad = true;
@@ -320,32 +242,17 @@ __global__ __launch_bounds__(256) void rg_dq_kernel(RelGradArgs r, int nrun) {
                         }
                     }
                 }
-                dsi[(4 * g + e) * AG16_PP + kb * 16 + j] = (T)dsv;
+                dsi[(4 * g + e) * ATT_PP + kb * 16 + j] = (T)dsv;
             }
         }
         __syncthreads();            // dS is written; every wave is past the previous tile's product, whose buffer is free
-        if (k0 + RP_KT < a.Lk) {
-            rg_image_t<T, D>(kt0 + (buf ^ 1) * (D * AG16_PP), kbase, a.ldk, k0 + RP_KT, a.Lk, tid, nthr);
-            rg_triples(kr0 + (buf ^ 1) * (3 * RP_KT), relk, k0 + RP_KT, a.Lk, tid);
+        if (k0 + ATT_KT < a.Lk) {
+            att_image_t_wg<T, D>(kt0 + (buf ^ 1) * (D * ATT_PP), kbase, a.ldk, k0 + ATT_KT, a.Lk, tid, nthr);
+            att_stage_triples(kr0 + (buf ^ 1) * (3 * ATT_KT), relk, k0 + ATT_KT, a.Lk, tid);
         }
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-            const frag pf = *reinterpret_cast<const frag *>(dsi + j * AG16_PP + k2 * 32 + g * 8);
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) {
-                const frag kf = *reinterpret_cast<const frag *>(kt + (db * 16 + j) * AG16_PP + k2 * 32 + g * 8);
-                acc[db] = Mma16<T>::mma(pf, kf, acc[db]);
-            }
-        }
+        att_image_mma<T, NDB>(acc, dsi, kt, g, j);
     }
-    float *dqb = a.dq + ((long)b * a.Lq + q0) * a.lddq + h * D;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int row = 4 * g + e;
-        if (row >= nq) continue;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) dqb[(long)row * a.lddq + db * 16 + j] = acc[db][e] * a.scale;
-    }
+    att_store_rows<NDB>(a.dq + ((long)b * a.Lq + q0) * a.lddq + h * D, a.lddq, acc, a.scale, nq, g, j);
     if (HIST) {
         if (bad) atomicOr(r.bad + h, 1u);
         __syncthreads();            // every wave's histogram adds are done
@@ -361,7 +268,7 @@ template <typename T, int D>
 __global__ __launch_bounds__(256) void rg_dkv_kernel(RelGradArgs r, int nrun) {
     const AttGrad16Args &a = r.a;
     typedef typename Mma16<T>::frag frag;
-    constexpr int KD = D / 32, NDB = D / 16, QB = RP_KT / 16;
+    constexpr int KD = D / 32, NDB = D / 16, QB = ATT_KT / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char rg_lds[];
     const int tid = threadIdx.x, nthr = blockDim.x, nw = nthr >> 6;
     const int lane = tid & 63, wave = tid >> 6, g = lane >> 4, j = lane & 15;
@@ -370,10 +277,10 @@ __global__ __launch_bounds__(256) void rg_dkv_kernel(RelGradArgs r, int nrun) {
     const int j0 = (run * nw + wave) * AG16_OWN;
     const int nk = a.Lk - j0;                       // owned keys inside the sequence: 16 or more (all), or none (an idle wave)
     const int n1 = 2 * r.r1 + 1, n2 = 2 * r.r2 + 1, nlut = n1 + 2 * n2;
-    T *qt = reinterpret_cast<T *>(rg_lds), *dot = qt + D * AG16_PP;
-    T *pt = dot + D * AG16_PP + wave * (2 * AG16_OWN * AG16_PP), *dst = pt + AG16_OWN * AG16_PP;
-    int *qr = reinterpret_cast<int *>(dot + D * AG16_PP + nw * (2 * AG16_OWN * AG16_PP));
-    float *t1s = reinterpret_cast<float *>(qr + 3 * RP_KT), *txs = t1s + n1, *tys = txs + n2;
+    T *qt = reinterpret_cast<T *>(rg_lds), *dot = qt + D * ATT_PP;
+    T *pt = dot + D * ATT_PP + wave * (2 * AG16_OWN * ATT_PP), *dst = pt + AG16_OWN * ATT_PP;
+    int *qr = reinterpret_cast<int *>(dot + D * ATT_PP + nw * (2 * AG16_OWN * ATT_PP));
+    float *t1s = reinterpret_cast<float *>(qr + 3 * ATT_KT), *txs = t1s + n1, *tys = txs + n2;
     const T *qbase = static_cast<const T *>(a.q) + (long)b * a.Lq * a.ldq + h * D;
     const T *dobase = static_cast<const T *>(a.dout) + (long)b * a.Lq * a.lddo + h * D;
     const T *kseq = static_cast<const T *>(a.k) + (long)b * a.Lk * a.ldk + h * D;
@@ -384,36 +291,29 @@ __global__ __launch_bounds__(256) void rg_dkv_kernel(RelGradArgs r, int nrun) {
 
     for (int i = tid; i < nlut; i += nthr) t1s[i] = r.lut[(long)h * nlut + i];
     frag kf[KD], vf[KD];
-    ag16_row_frags<T, KD>(kf, kseq, a.ldk, j0 + j, a.Lk, g);
-    ag16_row_frags<T, KD>(vf, vseq, a.ldv, j0 + j, a.Lk, g);
+    att_row_frags<T, KD>(kf, kseq, a.ldk, j0 + j, a.Lk, g);
+    att_row_frags<T, KD>(vf, vseq, a.ldv, j0 + j, a.Lk, g);
     float mk[4];
     int kp[4], kx[4], ky[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int key = j0 + 4 * g + e;
-        const bool ok = key < a.Lk;
-        mk[e] = a.mask && ok ? a.mask[(long)b * a.Lk + key] : 0.f;
-        const int32_t *rs = r.rel_k + ((long)b * a.Lk + (ok ? key : 0)) * 3;
-        kp[e] = ok ? rs[0] : 0;
-        kx[e] = ok ? rs[1] : 0;
-        ky[e] = ok ? rs[2] : 0;
-    }
+    for (int e = 0; e < 4; ++e) mk[e] = a.mask && j0 + 4 * g + e < a.Lk ? a.mask[(long)b * a.Lk + j0 + 4 * g + e] : 0.f;
+    att_lane_triples(kp, kx, ky, r.rel_k + (long)b * a.Lk * 3, j0 + 4 * g, a.Lk);
 
     m16_f4 acck[NDB], accv[NDB];
 #pragma unroll
     for (int db = 0; db < NDB; ++db) acck[db] = accv[db] = m16_f4{0.f, 0.f, 0.f, 0.f};
-    for (int q0 = 0; q0 < a.Lq; q0 += RP_KT) {
-        rg_image_t<T, D>(qt, qbase, a.ldq, q0, a.Lq, tid, nthr);
-        rg_image_t<T, D>(dot, dobase, a.lddo, q0, a.Lq, tid, nthr);
-        rg_triples(qr, relq, q0, a.Lq, tid);
+    for (int q0 = 0; q0 < a.Lq; q0 += ATT_KT) {
+        att_image_t_wg<T, D>(qt, qbase, a.ldq, q0, a.Lq, tid, nthr);
+        att_image_t_wg<T, D>(dot, dobase, a.lddo, q0, a.Lq, tid, nthr);
+        att_stage_triples(qr, relq, q0, a.Lq, tid);
         __syncthreads();            // the tile's images and triples (first tile: the table too) are in LDS
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) {
             const int row = q0 + qb * 16 + j;
             const bool okq = row < a.Lq;
             frag qf[KD], dof[KD];
-            ag16_row_frags<T, KD>(qf, qbase, a.ldq, row, a.Lq, g);
-            ag16_row_frags<T, KD>(dof, dobase, a.lddo, row, a.Lq, g);
+            att_row_frags<T, KD>(qf, qbase, a.ldq, row, a.Lq, g);
+            att_row_frags<T, KD>(dof, dobase, a.lddo, row, a.Lq, g);
             m16_f4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KD; ++ks) {
@@ -421,45 +321,26 @@ __global__ __launch_bounds__(256) void rg_dkv_kernel(RelGradArgs r, int nrun) {
                 dp = Mma16<T>::mma(vf[ks], dof[ks], dp);
             }
             const float mm = okq ? st[row] : 0.f, il = okq ? st[n + row] : 0.f, dd = okq ? st[2 * n + row] : 0.f;
-            const int qp = qr[qb * 16 + j], qx = qr[RP_KT + qb * 16 + j], qy = qr[2 * RP_KT + qb * 16 + j];
+            const int qp = qr[qb * 16 + j], qx = qr[ATT_KT + qb * 16 + j], qy = qr[2 * ATT_KT + qb * 16 + j];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float p = 0.f, dsv = 0.f;
                 if (okq && 4 * g + e < nk) {
                     const float t1 = t1s[rp_idx(kp[e], qp, r.r1)], tx = txs[rp_idx(kx[e], qx, r.r2)], ty = tys[rp_idx(ky[e], qy, r.r2)];
-                    p = ag16_exp((s[e] + (t1 + (tx + ty))) * a.scale + mk[e] - mm) * il;
+                    p = att_exp(rp_score(s[e], t1, tx, ty, a.scale, mk[e]) - mm) * il;
                     dsv = p * (dp[e] - dd);
                 }
-                pt[(4 * g + e) * AG16_PP + qb * 16 + j] = (T)p;
-                dst[(4 * g + e) * AG16_PP + qb * 16 + j] = (T)dsv;
+                pt[(4 * g + e) * ATT_PP + qb * 16 + j] = (T)p;
+                dst[(4 * g + e) * ATT_PP + qb * 16 + j] = (T)dsv;
             }
         }
         __syncthreads();            // P^T and dS^T are written
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-            const frag pf = *reinterpret_cast<const frag *>(pt + j * AG16_PP + k2 * 32 + g * 8);
-            const frag sf = *reinterpret_cast<const frag *>(dst + j * AG16_PP + k2 * 32 + g * 8);
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) {
-                const frag of = *reinterpret_cast<const frag *>(dot + (db * 16 + j) * AG16_PP + k2 * 32 + g * 8);
-                const frag qf = *reinterpret_cast<const frag *>(qt + (db * 16 + j) * AG16_PP + k2 * 32 + g * 8);
-                accv[db] = Mma16<T>::mma(pf, of, accv[db]);
-                acck[db] = Mma16<T>::mma(sf, qf, acck[db]);
-            }
-        }
+        att_image_mma<T, NDB>(accv, pt, dot, g, j);
+        att_image_mma<T, NDB>(acck, dst, qt, g, j);
         __syncthreads();            // the next tile overwrites the images and the triples
     }
-    float *dkb = a.dk + ((long)b * a.Lk + j0) * a.lddk + h * D, *dvb = a.dv + ((long)b * a.Lk + j0) * a.lddv + h * D;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int row = 4 * g + e;
-        if (row >= nk) continue;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) {
-            dkb[(long)row * a.lddk + db * 16 + j] = acck[db][e] * a.scale;
-            dvb[(long)row * a.lddv + db * 16 + j] = accv[db][e];
-        }
-    }
+    att_store_rows<NDB>(a.dk + ((long)b * a.Lk + j0) * a.lddk + h * D, a.lddk, acck, a.scale, nk, g, j);
+    att_store_rows<NDB>(a.dv + ((long)b * a.Lk + j0) * a.lddv + h * D, a.lddv, accv, 1.f, nk, g, j);
 }
 
 // dlut[h][e] = (double)count * q_h * scale, rounded once to fp32; NaN rows where M_h is not finite or a dS was refused
@@ -507,10 +388,7 @@ static int rg_check(const AttGrad16Args &a, const int32_t *rel_q, const int32_t 
     VK_TRY(ag16_check(a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, a.o, a.ldo, a.dout, a.lddo, a.dq, a.lddq, a.dk, a.lddk, a.dv, a.lddv, a.B, a.heads,
                       a.Lq, a.Lk, d, dt, workspace, workspace_bytes));
     VK_REQUIRE(rel_q && rel_k && lut && dlut, VK_EINVAL, "attention_relpos_grad: null argument");
-    VK_REQUIRE(r1 >= 1 && r2 >= 1, VK_EINVAL, "attention_relpos_grad: radii must be at least 1 (r1=%d r2=%d)", r1, r2);
-    VK_REQUIRE((size_t)r1 + 2 * (size_t)r2 <= RELPOS_LUT_MAX / 8 && relpos_lut_len(r1, r2) * sizeof(float) <= RELPOS_LUT_MAX, VK_EINVAL,
-               "attention_relpos_grad: the table of radii %d / %d, %zu floats a head, is past the LDS budget of %zu bytes", r1, r2,
-               (size_t)2 * r1 + 4 * (size_t)r2 + 3, RELPOS_LUT_MAX);
+    VK_TRY(relpos_lut_check("attention_relpos_grad", r1, r2));
     VK_REQUIRE(((uintptr_t)rel_q | (uintptr_t)rel_k | (uintptr_t)lut | (uintptr_t)dlut | (uintptr_t)a.mask) % 4 == 0, VK_EINVAL,
                "attention_relpos_grad: rel_q, rel_k, lut, dlut and mask must be 4-byte aligned");
     VK_REQUIRE(rg_shift(a.B, a.Lq, a.Lk) >= RG_MIN_SHIFT, VK_EINVAL,
@@ -524,10 +402,10 @@ static int rg_check(const AttGrad16Args &a, const int32_t *rel_q, const int32_t 
 }
 
 static size_t rg_dq_lds(int D, int waves, int nlut) {
-    return (size_t)(2 * D + waves * AG16_OWN) * AG16_PP * 2 + (size_t)2 * 3 * RP_KT * sizeof(int) + (size_t)nlut * 12;
+    return (size_t)(2 * D + waves * AG16_OWN) * ATT_PP * 2 + (size_t)2 * 3 * ATT_KT * sizeof(int) + (size_t)nlut * 12;
 }
 static size_t rg_dkv_lds(int D, int waves, int nlut) {
-    return (size_t)(2 * D + 2 * waves * AG16_OWN) * AG16_PP * 2 + (size_t)3 * RP_KT * sizeof(int) + (size_t)nlut * 4;
+    return (size_t)(2 * D + 2 * waves * AG16_OWN) * ATT_PP * 2 + (size_t)3 * ATT_KT * sizeof(int) + (size_t)nlut * 4;
 }
 
 template <typename T, int D>
@@ -542,9 +420,9 @@ static int rg_launch(const RelGradArgs &r, hipStream_t s) {
     hipLaunchKernelGGL((rg_norm_kernel<T, D>), dim3((unsigned)((std::max(rows_do, rows_v) + 255) / 256), a.heads, 2), dim3(256), 0, s,
                        static_cast<const T *>(a.dout), a.lddo, rows_do, static_cast<const T *>(a.v), a.ldv, rows_v, a.heads, r.norm2);
     VK_CHECK_HIP(hipGetLastError());
-    const int wq = std::min(RG_MAXW, ceil_div(a.Lq, AG16_OWN)), wk = std::min(RG_MAXW, ceil_div(a.Lk, AG16_OWN));
+    const int wq = std::min(ATT_MAXW, ceil_div(a.Lq, AG16_OWN)), wk = std::min(ATT_MAXW, ceil_div(a.Lk, AG16_OWN));
     const int nrq = ceil_div(a.Lq, wq * AG16_OWN), nrk = ceil_div(a.Lk, wk * AG16_OWN);
-    const size_t capq = rg_dq_lds(D, RG_MAXW, 0) + RELPOS_LUT_MAX * 3, capk = rg_dkv_lds(D, RG_MAXW, 0) + RELPOS_LUT_MAX;
+    const size_t capq = rg_dq_lds(D, ATT_MAXW, 0) + RELPOS_LUT_MAX * 3, capk = rg_dkv_lds(D, ATT_MAXW, 0) + RELPOS_LUT_MAX;
 #ifdef VK_ABLATION
     if (env_off("VK_RELPOS_GRAD_HIST"))             // tools only: the launches without the table gradient (dlut is zeros)
         VK_TRY(launch_lds(rg_dq_kernel<T, D, false>, dim3(a.B * a.heads * nrq), dim3(64 * wq), rg_dq_lds(D, wq, nlut), capq, s, r, nrq));
@@ -589,9 +467,7 @@ int vk_attention_relpos_grad(const void *q, long ldq, const void *k, long ldk, c
     r.norm2 = reinterpret_cast<unsigned *>(r.hist + (size_t)heads * nlut);
     r.bad = r.norm2 + 2 * heads;
     r.shift = rg_shift(B, Lq, Lk);
-    hipStream_t s = (hipStream_t)stream;
-    if (dt == VK_BF16) return d == 64 ? rg_launch<__bf16, 64>(r, s) : rg_launch<__bf16, 32>(r, s);
-    return d == 64 ? rg_launch<_Float16, 64>(r, s) : rg_launch<_Float16, 32>(r, s);
+    VK_DT16_D_SWITCH(dt, d, return rg_launch<T, D>(r, (hipStream_t)stream));
 }
 
 int vk_relpos_lut_grad(const float *dlut, int heads, int r1, int r2, int term, const int32_t *bucket, int bins, float *dweight,

@@ -1,35 +1,14 @@
-// attention_tiled_kernel, the online-soft-max attention on the matrix cores, with what its two translation units share: the 16-bit
-// fragment types, the argument struct of the entry points and the launchers.  attention.hip instantiates the plain forms,
-// attention_dropout.hip the DROP forms: a kernel is instantiated in one unit only.
+// attention_tiled_kernel, the online-soft-max attention on the matrix cores, with what its two translation units share: the
+// argument struct of the entry points and the launchers.  attention.hip instantiates the plain forms, attention_dropout.hip the DROP
+// forms: a kernel is instantiated in one unit only.  The fragment types, the constants, the exponential and pack16 are the shared
+// ones of mfma16.h and attention_mma.h.  The kernel's body stays written out and compiles to the instructions it always had.  Keep in
+// step with attention_mma.h: the row loads with att_row_frags, the V^T image with att_image_t, and the m / l update with
+// att_online_row (the backward's pass 1 must reproduce this kernel's m and l bit for bit; the tests of the backward hold that).
 #pragma once
+#include "attention_mma.h"
 #include "philox.h"
-#include "vk_common.h"
 
 namespace vk {
-
-typedef _Float16 att_h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 att_b8 __attribute__((ext_vector_type(8)));
-typedef float att_f4 __attribute__((ext_vector_type(4)));
-template <typename T>
-struct AttFrag;
-template <>
-struct AttFrag<_Float16> {
-    typedef att_h8 type;
-    static __device__ __forceinline__ att_f4 mma(att_h8 a, att_h8 b, att_f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-template <>
-struct AttFrag<__bf16> {
-    typedef att_b8 type;
-    static __device__ __forceinline__ att_f4 mma(att_b8 a, att_b8 b, att_f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-
-constexpr int ATT_PP = 72;                      // row pitch (elements) of the P and V^T images: 64 keys + 8 (bank skew)
-
-// The tiled kernel's exponential: v_exp_f32 on x * log2(e).  Its error (about 1e-6 relative at a soft-max's arguments) is far
-// below the rounding of P to a 16-bit type; exp(0) = 1 and exp(-inf) = 0 exactly, and a result below the normal range is 0.
-static __device__ __forceinline__ float tat_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-
-constexpr int TAT_KT = 64;                      // keys per tile (four 16-key score blocks, two 32-key slices of the second product)
 
 // One WAVE per (batch, head, block of QB * 16 queries), four per workgroup; the lane layouts are attention_mfma_kernel's:
 //   * Q fragments of the block stay in registers; a tile's K rows are the B fragments as they lie in memory;
@@ -57,8 +36,8 @@ __global__ __launch_bounds__(256) void attention_tiled_kernel(const T *__restric
                                                              float scale, DA... drop) {
     static_assert(sizeof...(DA) == (DROP ? 1 : 0), "a DropArgs behind the arguments of the DROP form, nothing otherwise");
     const DropArgs da = drop_args_of(drop...);
-    typedef typename AttFrag<T>::type frag;
-    constexpr int KD = D / 32, NDB = D / 16, KB = TAT_KT / 16, PER_WAVE = (QB * 16 + D) * ATT_PP;
+    typedef typename Mma16<T>::frag frag;
+    constexpr int KD = D / 32, NDB = D / 16, KB = ATT_KT / 16, PER_WAVE = (QB * 16 + D) * ATT_PP;
     extern __shared__ __attribute__((aligned(16))) unsigned char tat_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 4, j = lane & 15;
@@ -83,12 +62,12 @@ __global__ __launch_bounds__(256) void attention_tiled_kernel(const T *__restric
             qf[qb][ks] = ok ? t : zf;
         }
     }
-    att_f4 o[QB][NDB];
+    m16_f4 o[QB][NDB];
     float m[QB][4], l[QB][4];
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
 #pragma unroll
-        for (int db = 0; db < NDB; ++db) o[qb][db] = att_f4{0.f, 0.f, 0.f, 0.f};
+        for (int db = 0; db < NDB; ++db) o[qb][db] = m16_f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             m[qb][e] = -INFINITY;
@@ -96,7 +75,7 @@ __global__ __launch_bounds__(256) void attention_tiled_kernel(const T *__restric
         }
     }
 
-    for (int k0 = 0; k0 < Lk; k0 += TAT_KT) {
+    for (int k0 = 0; k0 < Lk; k0 += ATT_KT) {
         // ---- K fragments straight from memory ----
         frag kf[KB][KD];
 #pragma unroll
@@ -122,13 +101,7 @@ __global__ __launch_bounds__(256) void attention_tiled_kernel(const T *__restric
                 if (key < Lk) t0 = *reinterpret_cast<const frag *>(v + ((long)b * Lk + key) * ldv + h * D + c * 8);
                 if (key + 1 < Lk) t1 = *reinterpret_cast<const frag *>(v + ((long)b * Lk + key + 1) * ldv + h * D + c * 8);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const T lo = t0[e], hi = t1[e];
-                    unsigned short ulo, uhi;
-                    __builtin_memcpy(&ulo, &lo, 2);
-                    __builtin_memcpy(&uhi, &hi, 2);
-                    vt32[((c * 8 + e) * ATT_PP) / 2 + kp] = (unsigned)ulo | ((unsigned)uhi << 16);
-                }
+                for (int e = 0; e < 8; ++e) vt32[((c * 8 + e) * ATT_PP) / 2 + kp] = pack16<T>(t0[e], t1[e]);
             }
         }
         // ---- S = Q K^T * scale + mask; online soft-max; P image ----
@@ -140,12 +113,12 @@ __global__ __launch_bounds__(256) void attention_tiled_kernel(const T *__restric
         }
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) {
-            att_f4 sc[KB];
+            m16_f4 sc[KB];
 #pragma unroll
             for (int kb = 0; kb < KB; ++kb) {
-                att_f4 a = {0.f, 0.f, 0.f, 0.f};
+                m16_f4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int ks = 0; ks < KD; ++ks) a = AttFrag<T>::mma(qf[qb][ks], kf[kb][ks], a);
+                for (int ks = 0; ks < KD; ++ks) a = Mma16<T>::mma(qf[qb][ks], kf[kb][ks], a);
                 const bool ok = k0 + kb * 16 + j < Lk;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) a[e] = ok ? a[e] * scale + mk[kb] : -INFINITY;
@@ -165,12 +138,12 @@ __global__ __launch_bounds__(256) void attention_tiled_kernel(const T *__restric
 #pragma unroll
                 for (int s = 8; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
                 const float mn = fmaxf(m[qb][e], mx);
-                const float alpha = tat_exp(m[qb][e] - mn);      // first tile: exp(-inf) = 0
+                const float alpha = att_exp(m[qb][e] - mn);      // first tile: exp(-inf) = 0
                 float sum = 0.f;
                 const int row = qb * 16 + g * 4 + e;
 #pragma unroll
                 for (int kb = 0; kb < KB; ++kb) {
-                    const float p = tat_exp(sc[kb][e] - mn);     // padded keys: exp(-inf) = 0
+                    const float p = att_exp(sc[kb][e] - mn);     // padded keys: exp(-inf) = 0
                     sum += p;
                     if constexpr (DROP) pt[row * ATT_PP + kb * 16 + j] = (T)((keep[kb] >> e) & 1u ? p : 0.f);
                     else pt[row * ATT_PP + kb * 16 + j] = (T)p;
@@ -178,7 +151,7 @@ __global__ __launch_bounds__(256) void attention_tiled_kernel(const T *__restric
 #pragma unroll
                 for (int s = 8; s > 0; s >>= 1) sum += __shfl_xor(sum, s, 64);
                 m[qb][e] = mn;
-                l[qb][e] = alpha * l[qb][e] + sum;
+                l[qb][e] = alpha * l[qb][e] + sum;               // contracts to att_online_row's fmaf
 #pragma unroll
                 for (int db = 0; db < NDB; ++db) o[qb][db][e] *= alpha;
             }
@@ -196,7 +169,7 @@ __global__ __launch_bounds__(256) void attention_tiled_kernel(const T *__restric
             for (int db = 0; db < NDB; ++db) {
                 const frag vf = *reinterpret_cast<const frag *>(vt + (db * 16 + j) * ATT_PP + k2 * 32 + g * 8);
 #pragma unroll
-                for (int qb = 0; qb < QB; ++qb) o[qb][db] = AttFrag<T>::mma(pf[qb], vf, o[qb][db]);
+                for (int qb = 0; qb < QB; ++qb) o[qb][db] = Mma16<T>::mma(pf[qb], vf, o[qb][db]);
             }
         }
         __syncthreads();            // the next tile overwrites the images
@@ -234,28 +207,17 @@ static int check_attention_args(const AttArgs &a) {
     return VK_OK;
 }
 
-template <typename T, int D, int QB>
-static int tiled_launch_qb(const AttArgs &a, float scale, hipStream_t s) {
+// the DROP form (a DropArgs behind the stream) has the same grid, LDS and choice of QB
+template <typename T, int D, int QB, typename... DA>
+static int tiled_launch_qb(const AttArgs &a, float scale, hipStream_t s, DA... da) {
     const int nqb = (a.Lq + QB * 16 - 1) / (QB * 16), total = a.B * a.heads * nqb;
     const size_t smem = (size_t)4 * (QB * 16 + D) * ATT_PP * sizeof(T);
-    return launch_lds(attention_tiled_kernel<T, D, QB, false>, dim3((total + 3) / 4), dim3(256), smem, smem, s, VK_ATT_IO(T), nqb, total, scale);
+    return launch_lds(attention_tiled_kernel<T, D, QB, sizeof...(DA) != 0, DA...>, dim3((total + 3) / 4), dim3(256), smem, smem, s, VK_ATT_IO(T),
+                      nqb, total, scale, da...);
 }
-template <typename T, int D>
-static int tiled_launch(const AttArgs &a, float scale, hipStream_t s) {
-    return a.Lq <= 16 ? tiled_launch_qb<T, D, 1>(a, scale, s) : tiled_launch_qb<T, D, 2>(a, scale, s);
-}
-
-// the DROP forms: the same grid, LDS and choice of QB
-template <typename T, int D, int QB>
-static int tiled_drop_launch_qb(const AttArgs &a, float scale, const DropArgs &da, hipStream_t s) {
-    const int nqb = (a.Lq + QB * 16 - 1) / (QB * 16), total = a.B * a.heads * nqb;
-    const size_t smem = (size_t)4 * (QB * 16 + D) * ATT_PP * sizeof(T);
-    return launch_lds(attention_tiled_kernel<T, D, QB, true, DropArgs>, dim3((total + 3) / 4), dim3(256), smem, smem, s, VK_ATT_IO(T), nqb, total,
-                      scale, da);
-}
-template <typename T, int D>
-static int tiled_drop_launch(const AttArgs &a, float scale, const DropArgs &da, hipStream_t s) {
-    return a.Lq <= 16 ? tiled_drop_launch_qb<T, D, 1>(a, scale, da, s) : tiled_drop_launch_qb<T, D, 2>(a, scale, da, s);
+template <typename T, int D, typename... DA>
+static int tiled_launch(const AttArgs &a, float scale, hipStream_t s, DA... da) {
+    return a.Lq <= 16 ? tiled_launch_qb<T, D, 1>(a, scale, s, da...) : tiled_launch_qb<T, D, 2>(a, scale, s, da...);
 }
 
 }  // namespace vk

@@ -1,5 +1,5 @@
-// v_mfma_f32_16x16x32 on 16-bit operands for the training kernels (gemm16.hip, attention_grad16.hip), templated on the storage type
-// the way AttFrag<T> is in attention.hip.  Lane l = 16 g + j holds, in element e = 0..7 of its fragment, A[row j][k = 8 g + e] and
+// v_mfma_f32_16x16x32 on 16-bit operands for gemm16.hip and every matrix-core attention kernel (attention_mma.h), templated on the
+// storage type.  Lane l = 16 g + j holds, in element e = 0..7 of its fragment, A[row j][k = 8 g + e] and
 // B[k = 8 g + e][column j]; register r of the result is D[row 4 g + r][column j].
 #pragma once
 #include "vk_common.h"

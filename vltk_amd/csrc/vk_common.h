@@ -47,6 +47,19 @@ void set_error(const char *fmt, ...);
         default: VK_REQUIRE(false, VK_EINVAL, who ": dtype must be f32, f16 or bf16");  \
     }
 
+// CALL with T = _Float16 (dt is VK_F16) or __bf16 and the constant D = 64 (d is 64) or 32: the reach of the 16-bit matrix-core
+// attention kernels, which the entry has checked before.
+#define VK_DT16_D_SWITCH(dt, d, ...)                                                                      \
+    do {                                                                                                  \
+        if ((dt) == VK_F16) {                                                                             \
+            typedef _Float16 T;                                                                           \
+            if ((d) == 64) { constexpr int D = 64; __VA_ARGS__; } else { constexpr int D = 32; __VA_ARGS__; } \
+        } else {                                                                                          \
+            typedef __bf16 T;                                                                             \
+            if ((d) == 64) { constexpr int D = 64; __VA_ARGS__; } else { constexpr int D = 32; __VA_ARGS__; } \
+        }                                                                                                 \
+    } while (0)
+
 static inline size_t dtype_size(vk_dtype dt) {
     switch (dt) {
         case VK_F32: return 4;
